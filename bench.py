@@ -8,8 +8,12 @@ on synthetic audio already resident in HBM.  Workload = BASELINE.json configs[1]
 compute, per-GPU batch 32.  N > 1: one process per GPU (torch.distributed / RCCL), the minibatch is sharded, the
 flat G / D gradient buffers are all-reduced over xGMI; weak scaling.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel: the implicit-GEMM conv of
-the residual trunk, timed live with HIP events) and `cpu_baseline` (the CPU oracle on a bounded sample).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what that line needs: set-up, warm-up,
+the --steps timed steps.  --full adds the measurements that take runs of their own: `roofline` (dominant kernel: the
+implicit-GEMM conv of the residual trunk, timed live with HIP events), the generator alone, MDCT4 / IMDCT4 alone and
+`cpu_baseline` (the CPU oracle on a bounded sample).  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy; inputs are seeded and that step starts from the initial weights (initial_state below), so two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -229,6 +233,52 @@ def cpu_baseline(sample_batch=2, steps=3):
                          "sample": f"same step with configs[0]'s generator (ngf 32) at batch {sample_batch}, {dt0:.2f} s/step"}}
 
 
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: at most 4 Mi float32 per array (16 MB), a fixed seeded sample beyond that
+
+
+# --dump-outputs: the step is bit-reproducible from a given state except for the bias gradients of the convs in front of an
+# InstanceNorm (exact value 0, added atomically: DESIGN.md "Run-to-run reproducibility"); Adam turns their rounding noise into
+# +-lr moves, and bf16 rounding carries those into everything else: two runs part by 1e-2 (weights) and 0.3 (generated
+# spectrogram, relative L2) after 10 updates.  So with --dump-outputs the last timed step starts from the initial weights
+# and optimiser state again (restored outside the clock): its losses, spectrogram and weights repeat from run to run, up
+# to those biases.
+def initial_state(model):
+    return ([(o, o.flat_p.clone(), o.step_count) for o in (model.optimizer_G, model.optimizer_D)],
+            None if getattr(model, "scaler", None) is None else model.scaler.state.clone())
+
+
+def restore_state(model, snap):
+    from pix2pixhdaudiosr_amd import _ops
+    opts, scaler_state = snap
+    for o, p0, n0 in opts:
+        o.flat_p.copy_(p0)
+        o.exp_avg.zero_()
+        o.exp_avg_sq.zero_()
+        o.step_dev.zero_()
+        o.step_count = n0
+    if scaler_state is not None:
+        model.scaler.state.copy_(scaler_state)
+    _ops.bump_weight_epoch()                                       # packed weight copies cached by eager steps are stale
+
+
+def dump_outputs(out_dir, model, losses):
+    """What the timed path computed in its last step, as float32 .npy files: the loss values it returned, the generated
+    spectrogram and the master weights of G and D after that step's Adam.  An array larger than DUMP_SAMPLE elements is
+    written as the elements at sorted indices drawn from a fixed seed (the same indices for the same shape), flattened."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"loss_{k}": v for k, v in losses.items() if torch.is_tensor(v)}
+    arrays["sr_spectro"] = model._visual[1]
+    arrays["netG_weights"] = model.optimizer_G.flat_p
+    arrays["netD_weights"] = model.optimizer_D.flat_p
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -267,6 +317,12 @@ def main():
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="cfg2",
                     help="cfg2 (default) = BASELINE configs[1], the headline workload.  cfg3 / cfg5 = the per-rank workloads of configs[2]/[3] and "
                          "configs[4]: NON-headline variants, marked `headline: false` in the JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the dominant kernel (roofline), the generator alone, MDCT4 / IMDCT4 alone "
+                         "and the CPU baseline (--no-probes / --no-mdct / --no-cpu-baseline leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (losses, generated spectrogram, G / D weights; float32) as DIR/<name>.npy; "
+                         "that step starts from the initial weights and optimiser state")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager step on one GPU too (default: captured HIP graph)")
     ap.add_argument("--allow-eager-fallback", action="store_true",
@@ -291,6 +347,8 @@ def main():
 
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # ONE JSON line on stdout, nothing else: libraries print banners there (RCCL 2.26 writes its version block to stdout
     # when the first communicator is created), so fd 1 is pointed at stderr for the whole run and the line goes to a
     # duplicate of the original stdout
@@ -301,7 +359,10 @@ def main():
         os.dup2(2, 1)
     if "WORLD_SIZE" not in os.environ:
         if a.gpus > 1:
-            launch_ranks(a.gpus, sys.argv[1:])                     # does not return
+            argv = sys.argv[1:]
+            if a.dump_outputs:                                     # the ranks run in ROOT: a relative DIR means this cwd's
+                argv += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
+            launch_ranks(a.gpus, argv)                             # does not return
         world, rank, local = 1, 0, 0
     else:
         world = int(os.environ["WORLD_SIZE"])
@@ -350,6 +411,7 @@ def main():
     if dist_on:
         parallel_state.enable_data_parallel(model, world, force_collectives=rehearse,
                                             wire_dtype=torch.bfloat16 if a.wire_bf16 else torch.float32)
+    snap = initial_state(model) if a.dump_outputs else None
     T = (frames - 1) * opt.hop_length
     g = torch.Generator(device="cuda").manual_seed(1234 + rank)
     hr = 0.1 * torch.randn(a.batch, T, device="cuda", generator=g)
@@ -405,11 +467,19 @@ def main():
     barrier()
     for o_ in (model.optimizer_G, model.optimizer_D):
         o_.reset_exchange_timing(dist_on)                          # events around every wait for a collective (N > 1 / rehearsal)
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step(lr, hr)
+    dt, t0 = 0.0, time.perf_counter()
+    for i in range(a.steps):
+        if snap is not None and i == a.steps - 1:                  # --dump-outputs: see initial_state
+            barrier()
+            dt += time.perf_counter() - t0
+            restore_state(model, snap)
+            barrier()
+            t0 = time.perf_counter()
+        losses = step(lr, hr)
     barrier()
-    dt = time.perf_counter() - t0
+    dt += time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                               # before anything else runs a step on this model
+        dump_outputs(a.dump_outputs, model, losses)
     exch = {"G": model.optimizer_G.exchange_timing(), "D": model.optimizer_D.exchange_timing()} if dist_on else None
     for o_ in (model.optimizer_G, model.optimizer_D):
         o_.reset_exchange_timing(False)
@@ -485,6 +555,13 @@ def main():
         if graph_error is not None:
             out["graph_error"] = graph_error
         log(f"timed region done: {ms:.1f} ms/step")
+        # a plain run ends here; so do byte / launch counting runs (--no-probes): nothing beyond the steps themselves
+        if not a.full or a.no_probes:
+            print(json.dumps(out), file=_JSON_OUT or sys.stdout, flush=True)
+            if dist_on:
+                torch.distributed.barrier()
+                torch.distributed.destroy_process_group()
+            return
         # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process; the figure comes
         # from the separate rocprofv3 --pmc passes recorded in profiles/ (same kernel, same shapes, per launch)
         traffic, traffic_source = None, None
@@ -502,12 +579,6 @@ def main():
         # launches of two extra eager steps (the graph-replayed steps above run exactly these kernels).  The
         # stand-alone back-to-back figure is logged too: 20 MFMA-bound launches in a row run at a lower sustained clock.
         from pix2pixhdaudiosr_amd import _ops
-        if a.no_probes:                                            # byte / launch counting runs: nothing beyond the steps themselves
-            print(json.dumps(out), file=_JSON_OUT or sys.stdout, flush=True)
-            if dist_on:
-                torch.distributed.barrier()
-                torch.distributed.destroy_process_group()
-            return
         tch, trows, tcols = wl["trunk"]
         sec_iso, flops = time_trunk_conv(a.batch, trunk=wl["trunk"])
         sec = sec_iso

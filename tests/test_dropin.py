@@ -2,9 +2,10 @@
 `models.mdct`, `models.models`, `util.util`, `dct.dct`, `data.data_loader` (train.py:12-17,56-58; generate_audio.py:6-8,21-23).
 `python -m pix2pixhdaudiosr_amd.dropin <script>` serves exactly those names from this package through one meta-path finder
 and leaves the out-of-scope modules (`options.*`, `util.visualizer`, ...) to the reference's own files.  CPU: names resolve
-to the SAME objects, a script written against the reference's names runs under the launcher unedited, and -- where the
-reference checkout is present (build container only) -- every hot-path import statement of its two scripts resolves."""
-import ast
+to the SAME objects, a script written against the reference's names runs under the launcher unedited, and every hot-path
+import statement of its two scripts resolves (tests/golden/script_imports.json: those statements, read from the reference by
+tools/gen_golden.py)."""
+import json
 import os
 import subprocess
 import sys
@@ -13,7 +14,6 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 SCRIPT = textwrap.dedent('''
     # a stand-in for the reference's script: the same module names, written for this test
@@ -72,18 +72,17 @@ def test_without_the_launcher_the_names_do_not_resolve(tmp_path):
 OUT_OF_SCOPE = ("options", "util.visualizer", "util.spectro_img", "util.html", "torchaudio", "debugpy")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout only exists in the build container")
 @pytest.mark.parametrize("script", ["train.py", "generate_audio.py"])
 def test_every_hot_path_import_of_the_reference_scripts_resolves(script):
-    """Reads the reference script's import statements (ast, nothing is executed or copied) and resolves each one that is not
+    """Takes the reference script's import statements (tests/golden/script_imports.json) and resolves each one that is not
     CLI / UI / a third-party package through the alias finder, down to the imported attribute."""
-    tree = ast.parse(open(os.path.join(REF, script)).read())
+    with open(os.path.join(ROOT, "tests", "golden", "script_imports.json")) as f:
+        statements = json.load(f)[script]
     wanted = []
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.level == 0 and node.module:
-            top = node.module.split(".")[0]
-            if top in ("models", "util", "dct", "data") and not node.module.startswith(OUT_OF_SCOPE):
-                wanted += [(node.module, a.name) for a in node.names]
+    for module, names in statements:
+        top = module.split(".")[0]
+        if top in ("models", "util", "dct", "data") and not module.startswith(OUT_OF_SCOPE):
+            wanted += [(module, name) for name in names]
     assert len(wanted) >= 6, wanted
     code = ("import sys, importlib\nfrom pix2pixhdaudiosr_amd import dropin\ndropin.install()\n"
             "import types; sys.modules.setdefault('util', types.ModuleType('util')).__path__ = []\n"

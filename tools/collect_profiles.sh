@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 fresh() { rm -rf "$OUT/$1"; mkdir -p "$OUT/$1"; }
 if [ "$WHAT" = "trace" ] || [ "$WHAT" = "all" ]; then
   fresh step
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/step" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-mdct > "$OUT/step.log" 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/step" -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-mdct > "$OUT/step.log" 2>&1
 fi
 if [ "$WHAT" = "pmc" ] || [ "$WHAT" = "all" ]; then
   fresh fetch; fresh write; fresh mfma; fresh sq

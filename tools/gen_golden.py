@@ -531,6 +531,22 @@ def gen_feeder(out):
     print("feeder.npz", len(d), "arrays")
 
 
+def gen_script_imports(out):
+    """Every top-level `from X import a, b` of the reference's two entry scripts (read with ast, nothing executed), in
+    ast.walk order: what tests/test_dropin.py resolves through the drop-in finder without the reference at hand."""
+    import ast
+    import json
+    d = {}
+    for script in ("train.py", "generate_audio.py"):
+        tree = ast.parse(open(os.path.join(REF, script)).read())
+        d[script] = [[node.module, [a.name for a in node.names]] for node in ast.walk(tree)
+                     if isinstance(node, ast.ImportFrom) and node.level == 0 and node.module]
+    with open(os.path.join(out, "script_imports.json"), "w") as f:
+        json.dump(d, f, indent=1)
+        f.write("\n")
+    print("script_imports.json", sum(len(v) for v in d.values()), "statements")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -540,7 +556,8 @@ def main():
     _stub_modules()
     sys.path.insert(0, REF)
     torch.set_num_threads(4)
-    todo = a.only.split(",") if a.only else ["mdct", "mdct2", "networks", "networks_d3", "model", "spectro_modes", "evaltail", "feeder"]
+    todo = a.only.split(",") if a.only else ["mdct", "mdct2", "networks", "networks_d3", "model", "spectro_modes", "evaltail", "feeder",
+                                                 "script_imports"]
     if "mdct2" in todo:
         gen_mdct2(a.out)
     if "mdct" in todo:
@@ -557,6 +574,8 @@ def main():
         gen_evaltail(a.out)
     if "feeder" in todo:
         gen_feeder(a.out)
+    if "script_imports" in todo:
+        gen_script_imports(a.out)
 
 
 if __name__ == "__main__":
