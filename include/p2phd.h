@@ -81,7 +81,8 @@ int p2phd_probe_read(float* ms_out, int cap);
 /* Launch counters: how many launches of a kernel family the library has made since the last reset -- "gconv" (every
  * gather-GEMM launch), "halo" (those on the patch-staged 3x3 main loop), "cls_skip" (tap-skipping merged stride-2 launches),
  * "splitk" (launches with a split-K tail), "tile256" (256 x 256 tiles), "tile128x192" (128 x 192 tiles of small planes),
- * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient).  family == NULL with reset != 0 clears all.
+ * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient), and the dedicated single-layer kernels "dfirst",
+ * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);

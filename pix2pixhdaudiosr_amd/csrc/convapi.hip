@@ -55,25 +55,11 @@ int check_desc(const p2phd_conv_desc* c) {
   return P2PHD_OK;
 }
 
-// shape tests only (what the packed buffer must hold whatever the options say at the moment: an option can change between
-// the pack and the call, the buffer layout must not).  Pure functions: no global is touched (advisor, round 4).
-bool c7_fast_shape(const p2phd_conv_desc* c) { return c7_in_ok(c, true); }
-bool c7_out_shape(const p2phd_conv_desc* c) { return c7_out_ok(c, true); }
-bool c7_dgrad_shape(const p2phd_conv_desc* c) { return c7_out_dgrad_ok(c, true); }
-size_t march_shape_elems(const p2phd_conv_desc* c, int which) { return march_packed_elems(c, which); }
-size_t generic_packed_elems(const std::vector<struct Plan>& plans);
-
 int fold_mode(const p2phd_conv_desc* c) {
   if (c->transposed || c->stride != 1) return FOLD_NONE;
   if (c->K <= 4 && c->S * c->K <= 32) return FOLD_OUT;
   if (c->C <= 4 && c->S * c->C <= 32) return FOLD_IN;
   return FOLD_NONE;
-}
-
-size_t generic_packed_elems(const std::vector<Plan>& plans) {
-  size_t n = 0;
-  for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-  return n;
 }
 
 GDesc base_desc(int N) {
@@ -212,6 +198,21 @@ WMap cfold_map(const p2phd_conv_desc* c) {          // rows k, inner (tw,c)
   return WMap{c->K, c->S * c->C, c->C * RS, RS, c->K, 0, c->C, 1, c->S, 1};
 }
 
+// Fragment-ordered weight copy a dedicated kernel reads, behind the generic pack.  Chosen by shape alone: an option can change
+// between the pack and the call, the buffer layout must not.
+enum Tail { TAIL_NONE, TAIL_MARCH, TAIL_DLAST, TAIL_DFIRST, TAIL_C7_IN, TAIL_C7_OUT, TAIL_C7_DGRAD };
+
+// everything a call derives from (desc, which), once.  which: 0 = forward, 1 = input gradient
+struct Layer {
+  const p2phd_conv_desc* c = nullptr;
+  int Ho = 0, Wo = 0, fold = FOLD_NONE, tail = TAIL_NONE;
+  std::vector<Plan> plans;         // the generic launches
+  WMap m{};                        // their map of the master weights
+  size_t tail_off = 0;             // elements of the generic pack = element offset of the fragment copy
+  size_t tail_elems = 0;           // elements of the fragment copy
+  const char* frag(const void* wp) const { return static_cast<const char*>(wp) + tail_off * elem_size(c->dtype); }
+};
+
 // which: 0 = forward, 1 = input gradient
 void make_plans(const p2phd_conv_desc* c, int which, std::vector<Plan>& plans, WMap* m) {
   int Ho, Wo;
@@ -247,6 +248,77 @@ void make_plans(const p2phd_conv_desc* c, int which, std::vector<Plan>& plans, W
   }
 }
 
+// (the shape rules of the dedicated kernels are disjoint: at most one fragment copy follows the generic pack)
+Layer layer(const p2phd_conv_desc* c, int which) {
+  Layer L;
+  L.c = c;
+  out_size(c, &L.Ho, &L.Wo);
+  L.fold = fold_mode(c);
+  make_plans(c, which, L.plans, &L.m);
+  for (auto& p : L.plans) L.tail_off += (size_t)p.rows_pad * p.d.KK;
+  if (march_shape_kind(c, which)) { L.tail = TAIL_MARCH; L.tail_elems = march_packed_elems(c, which); }
+  else if (dlast_shape_ok(c)) { L.tail = TAIL_DLAST; L.tail_elems = dlast_packed_elems(c, which); }
+  else if (which == 0 && dfirst_shape_ok(c)) { L.tail = TAIL_DFIRST; L.tail_elems = dfirst_packed_elems(c); }
+  else if (which == 0 && c7_in_shape_ok(c)) { L.tail = TAIL_C7_IN; L.tail_elems = c7_in_packed_elems(c); }
+  else if (which == 0 && c7_out_shape_ok(c)) { L.tail = TAIL_C7_OUT; L.tail_elems = c7_out_packed_elems(c); }
+  else if (which == 1 && c7_dgrad_shape_ok(c)) { L.tail = TAIL_C7_DGRAD; L.tail_elems = c7_out_dgrad_packed_elems(c); }
+  return L;
+}
+
+// the 7x7 input gradient's border fix reads the f32 master weights, kept behind its fragment copy
+size_t master_bytes(const p2phd_conv_desc* c) { return (size_t)c->K * c->C * c->R * c->S * sizeof(float); }
+
+// 3x3 behind ReflectionPad2d(1), stride 1 (the residual trunk, networks.py:231-252) ...
+bool reflect3x3(const p2phd_conv_desc* c) {
+  return c->pad_mode == 1 && !c->transposed && c->R == 3 && c->S == 3 && c->pad == 1 && c->stride == 1;
+}
+// ... whose input gradient can run on the exact H x W grid (see p2phd_conv_dgrad)
+bool reflect_exact_shape(const p2phd_conv_desc* c) { return reflect3x3(c) && fold_mode(c) != FOLD_OUT && c->H >= 4 && c->W >= 4; }
+
+// negative slope of an activation applied on load or in a backward pass (1 = none)
+float act_slope(int act) { return act == P2PHD_ACT_RELU ? 0.f : (act == P2PHD_ACT_LRELU ? 0.2f : 1.f); }
+
+// ---- routes: which kernel serves (layer, pass) ------------------------------------------------------------------------
+// The route functions are the only readers of the kernel-selection options.  A dedicated kernel takes its layer only under
+// the gates of its launch; otherwise the layer runs on the generic gather-GEMM (W-fold forms where fold_mode says so).
+enum Route { R_GEMM, R_KFOLD, R_CFOLD, R_REFLECT_EXACT, R_DLAST, R_C7_OUT, R_C7_IN, R_C7_DGRAD, R_MARCH, R_DFIRST, R_MARCH_W, R_THIN };
+
+// every dedicated route is counted here, where it is taken (p2phd_launch_count)
+Route counted(Route r) {
+  static const int family[] = {-1, -1, -1, -1, LC_DLAST, LC_C7, LC_C7, LC_C7, LC_MARCH, LC_DFIRST, LC_MARCH_W, LC_THIN_WGRAD};
+  if (family[r] >= 0) ++g_launch_count[family[r]];
+  return r;
+}
+
+Route fwd_route(const Layer& L, int act, bool stats) {
+  switch (L.tail) {
+    case TAIL_DLAST: if (g_opt_dlast && !stats && act == P2PHD_ACT_NONE) return R_DLAST; break;
+    case TAIL_C7_OUT: if (!g_opt_c7_generic && !stats) return R_C7_OUT; break;
+    case TAIL_MARCH: if (g_opt_march && act == P2PHD_ACT_NONE) return R_MARCH; break;
+    case TAIL_DFIRST: if (g_opt_dfirst && !stats && act != P2PHD_ACT_TANH) return R_DFIRST; break;   // (none, ReLU, LeakyReLU)
+    case TAIL_C7_IN: if (!g_opt_c7_generic && act == P2PHD_ACT_NONE) return R_C7_IN; break;
+  }
+  return L.fold == FOLD_OUT ? R_KFOLD : (L.fold == FOLD_IN ? R_CFOLD : R_GEMM);
+}
+
+// also the route of the fused-sums input gradient (p2phd_conv_dgrad_bsum): its layers have zero padding, so neither the
+// 7x7 kernel nor the exact-grid reflect form applies to them
+Route dgrad_route(const Layer& L, bool addend) {
+  switch (L.tail) {
+    case TAIL_C7_DGRAD: if (!g_opt_c7_generic && !addend) return R_C7_DGRAD; break;
+    case TAIL_MARCH: if (g_opt_march && !addend) return R_MARCH; break;
+    case TAIL_DLAST: if (g_opt_dlast) return R_DLAST; break;
+  }
+  if (!g_opt_reflect_generic && reflect_exact_shape(L.c)) return R_REFLECT_EXACT;
+  return R_GEMM;                   // (with the output W-fold's dy expansion / the reflect fold where the layer needs them)
+}
+
+Route wgrad_route(const p2phd_conv_desc* c) {
+  if (g_opt_march && march_shape_kind(c, 0)) return R_MARCH_W;
+  if (!g_opt_c7_generic && thin_wgrad_shape_kind(c)) return R_THIN;
+  return R_GEMM;
+}
+
 size_t padded_dx_bytes(const p2phd_conv_desc* c) {
   if (c->pad_mode != 1) return 0;
   return align256((size_t)c->N * (c->H + 2 * c->pad) * (c->W + 2 * c->pad) * cpitch(c->C) * elem_size(c->dtype));
@@ -258,6 +330,21 @@ size_t folded_x_bytes(const p2phd_conv_desc* c, int Wo) {
   return align256((size_t)c->N * c->H * Wo * cpitch(c->S * c->C) * elem_size(c->dtype));
 }
 
+// per-wave InstanceNorm partials of the conv epilogues: [N][slots][classes][Cp][2] floats behind the layer's other scratch
+size_t stat_table_bytes(const std::vector<Plan>& plans) {
+  size_t n = 0;
+  for (const auto& p : plans) n = std::max(n, stat_table_floats(p.d));
+  return align256(n * sizeof(float));
+}
+
+// statistics of a marching forward launch from its per-wave partials
+int march_stats_merge(const p2phd_conv_desc* c, const float* table, float* stats, hipStream_t st) {
+  int slots = 0, ncls = 1, slot_rows = 0;
+  long npix_cls = 0;
+  march_plan(c, 0, &slots, &ncls, &slot_rows, &npix_cls, nullptr);
+  return launch_stats_merge(table, stats, c->N, slots, ncls, cpitch(c->K), c->K, npix_cls, slot_rows, st);
+}
+
 }  // namespace
 
 extern "C" int p2phd_channel_pitch(int channels) { return p2phd::cpitch(channels); }
@@ -266,9 +353,7 @@ extern "C" int p2phd_conv_kmajor_ok(const p2phd_conv_desc* c) {
   if (c == nullptr) return 0;
   p2phd_conv_desc t = *c;
   t.w_layout = 0;
-  if (check_desc(&t) != P2PHD_OK) return 0;
-  return (kmajor_shape_ok(c) && fold_mode(c) == FOLD_NONE && !c7_fast_shape(c) && !c7_out_shape(c) && !c7_dgrad_shape(c) &&
-          !thin_wgrad_kind(c)) ? 1 : 0;
+  return check_desc(&t) == P2PHD_OK && kmajor_shape_ok(c) ? 1 : 0;
 }
 
 extern "C" int p2phd_conv_out_size(const p2phd_conv_desc* c, int* Ho, int* Wo) {
@@ -279,18 +364,8 @@ extern "C" int p2phd_conv_out_size(const p2phd_conv_desc* c, int* Ho, int* Wo) {
 
 extern "C" size_t p2phd_conv_packed_bytes(const p2phd_conv_desc* c, int which) {
   if (check_desc(c) != P2PHD_OK || (which != 0 && which != 1)) return 0;
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, which, plans, &m);
-  size_t n = 0;
-  for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-  if (dlast_ok(c, true)) n += dlast_packed_elems(c, which);                 // fragment-ordered copy for dlast.hip, behind the W-fold pack
-  if (which == 0 && dfirst_ok(c, true)) n += dfirst_packed_elems(c);        // fragment-ordered copy for dfirst.hip, behind the generic pack
-  if (which == 0 && c7_fast_shape(c)) n += c7_in_packed_elems(c);           // fragment-ordered copy for c7.hip, behind the W-fold pack
-  if (which == 0 && c7_out_shape(c)) n += c7_out_packed_elems(c);
-  if (which == 1 && c7_dgrad_shape(c))                                       // + fragment-ordered copy + f32 master copy (border fix)
-    return (n + c7_out_dgrad_packed_elems(c)) * elem_size(c->dtype) + (size_t)c->K * c->C * c->R * c->S * sizeof(float);
-  n += march_shape_elems(c, which);                                          // fragment-ordered copy for march.hip, behind the generic pack
-  return n * elem_size(c->dtype);
+  const Layer L = layer(c, which);
+  return (L.tail_off + L.tail_elems) * elem_size(c->dtype) + (L.tail == TAIL_C7_DGRAD ? master_bytes(c) : 0);
 }
 
 // Which variant of the packed layout the launches of (desc, which) read.  The packed buffer of a layer is NOT a function of the
@@ -300,10 +375,8 @@ extern "C" size_t p2phd_conv_packed_bytes(const p2phd_conv_desc* c, int which) {
 // inference on a smaller last batch between training steps).
 extern "C" int p2phd_conv_pack_layout(const p2phd_conv_desc* c, int which) {
   if (check_desc(c) != P2PHD_OK || (which != 0 && which != 1)) return -1;
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, which, plans, &m);
   int id = 0;
-  for (auto& p : plans) if (p.d.cls_skip != 0) id |= 1;
+  for (auto& p : layer(c, which).plans) if (p.d.cls_skip != 0) id |= 1;
   return id;
 }
 
@@ -311,68 +384,43 @@ extern "C" int p2phd_conv_pack_weights(const p2phd_conv_desc* c, int which, cons
   if (int rc = check_desc(c)) return rc;
   P2PHD_REQUIRE(which == 0 || which == 1, "pack_weights: which must be 0 (forward) or 1 (input gradient)");
   P2PHD_REQUIRE(w && packed, "pack_weights: null pointer");
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, which, plans, &m);
-  for (auto& p : plans) {
+  hipStream_t st = (hipStream_t)stream;
+  const Layer L = layer(c, which);
+  const WMap& m = L.m;
+  for (auto& p : L.plans) {
     char* dst = static_cast<char*>(packed) + p.w_off * elem_size(c->dtype);
     if (p.d.cls_cp > 0) {
       // rows = m.rows output channels, inner = m.inner reduction channels, master strides from the plain map
       const int pad_eff = (which == 1 && c->pad_mode == 1) ? 0 : c->pad;
       if (int rc = launch_pack_merged(p.d, c->dtype, w, dst, p.rows_pad, m.rows, m.inner, c->R, c->S, pad_eff, m.s_row, m.s_inner,
-                                      (hipStream_t)stream)) return rc;
-    } else if (int rc = launch_pack(p.d, m, c->dtype, w, dst, p.rows_pad, (hipStream_t)stream)) return rc;
+                                      st)) return rc;
+    } else if (int rc = launch_pack(p.d, m, c->dtype, w, dst, p.rows_pad, st)) return rc;
   }
-  if (march_shape_elems(c, which) > 0) {
-    return march_pack(c, which, w, static_cast<char*>(packed) + generic_packed_elems(plans) * elem_size(c->dtype), (hipStream_t)stream);
-  }
-  if (dlast_ok(c, true))
-    return dlast_pack(c, which, w, static_cast<char*>(packed) + generic_packed_elems(plans) * elem_size(c->dtype), (hipStream_t)stream);
-  if (which == 0 && dfirst_ok(c, true))
-    return dfirst_pack(c, w, static_cast<char*>(packed) + generic_packed_elems(plans) * elem_size(c->dtype), (hipStream_t)stream);
-  if (which == 0 && c7_fast_shape(c)) {
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    return c7_in_pack(c, w, static_cast<char*>(packed) + n * elem_size(c->dtype), (hipStream_t)stream);
-  }
-  if (which == 0 && c7_out_shape(c)) {
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    return c7_out_pack(c, w, static_cast<char*>(packed) + n * elem_size(c->dtype), (hipStream_t)stream);
-  }
-  if (which == 1 && c7_dgrad_shape(c)) {
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    char* frag = static_cast<char*>(packed) + n * elem_size(c->dtype);
-    if (int rc = c7_out_dgrad_pack(c, w, frag, (hipStream_t)stream)) return rc;
-    char* master = frag + c7_out_dgrad_packed_elems(c) * elem_size(c->dtype);
-    if (hipMemcpyAsync(master, w, (size_t)c->K * c->C * c->R * c->S * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-      set_error("pack_weights: copy of the master weights failed");
-      return P2PHD_ELAUNCH;
-    }
+  char* frag = static_cast<char*>(packed) + L.tail_off * elem_size(c->dtype);
+  switch (L.tail) {
+    case TAIL_MARCH: return march_pack(c, which, w, frag, st);
+    case TAIL_DLAST: return dlast_pack(c, which, w, frag, st);
+    case TAIL_DFIRST: return dfirst_pack(c, w, frag, st);
+    case TAIL_C7_IN: return c7_in_pack(c, w, frag, st);
+    case TAIL_C7_OUT: return c7_out_pack(c, w, frag, st);
+    case TAIL_C7_DGRAD:
+      if (int rc = c7_out_dgrad_pack(c, w, frag, st)) return rc;
+      if (hipMemcpyAsync(frag + L.tail_elems * elem_size(c->dtype), w, master_bytes(c), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        set_error("pack_weights: copy of the master weights failed");
+        return P2PHD_ELAUNCH;
+      }
   }
   return P2PHD_OK;
 }
 
-// per-wave InstanceNorm partials of the conv epilogues: [N][slots][classes][Cp][2] floats behind the layer's other scratch
-size_t stat_table_bytes(const std::vector<Plan>& plans) {
-  size_t n = 0;
-  for (const auto& p : plans) n = std::max(n, stat_table_floats(p.d));
-  return align256(n * sizeof(float));
-}
-
 extern "C" size_t p2phd_conv_fwd_workspace_bytes(const p2phd_conv_desc* c) {
   if (check_desc(c) != P2PHD_OK) return 0;
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  const int fold = fold_mode(c);
-  if (fold == FOLD_OUT)                                          // Y has the shape of the folded dy; statistics: plane pass  (dlast.hip: per-pixel tap partials)
-    return std::max(folded_dy_bytes(c, Ho, Wo) + align256(plane_stats_scratch_floats(c->N, (long)Ho * Wo, c->K) * sizeof(float)),
-                    dlast_ok(c, true) ? align256(dlast_fwd_workspace_floats(c) * sizeof(float)) : (size_t)0);
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, 0, plans, &m);
-  const size_t table = stat_table_bytes(plans);
-  if (fold == FOLD_IN) return folded_x_bytes(c, Wo) + table;
-  return table;
+  const Layer L = layer(c, 0);
+  if (L.fold == FOLD_OUT)                                        // Y has the shape of the folded dy; statistics: plane pass  (dlast.hip: per-pixel tap partials)
+    return std::max(folded_dy_bytes(c, L.Ho, L.Wo) + align256(plane_stats_scratch_floats(c->N, (long)L.Ho * L.Wo, c->K) * sizeof(float)),
+                    L.tail == TAIL_DLAST ? align256(dlast_fwd_workspace_floats(c) * sizeof(float)) : (size_t)0);
+  const size_t table = stat_table_bytes(L.plans);
+  return L.fold == FOLD_IN ? folded_x_bytes(c, L.Wo) + table : table;
 }
 
 extern "C" int p2phd_conv_fwd(const p2phd_conv_desc* c, const void* x, const void* wp, const float* bias, int act,
@@ -383,73 +431,50 @@ extern "C" int p2phd_conv_fwd(const p2phd_conv_desc* c, const void* x, const voi
   if (c->N == 0) return P2PHD_OK;
   P2PHD_REQUIRE(x && wp && y, "conv_fwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, 0, plans, &m);
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  const int fold = fold_mode(c);
-  P2PHD_REQUIRE((fold == FOLD_NONE && stats == nullptr) || workspace,
+  Layer L = layer(c, 0);
+  const int Ho = L.Ho, Wo = L.Wo;
+  P2PHD_REQUIRE((L.fold == FOLD_NONE && stats == nullptr) || workspace,
                 "conv_fwd: this layer needs p2phd_conv_fwd_workspace_bytes of scratch (W-fold image / statistics partials)");
-  if (fold == FOLD_OUT && stats == nullptr && act == P2PHD_ACT_NONE && dlast_ok(c)) {
-    // the discriminator's head (512 -> 1, 4 x 4): one pass over x with the 16 taps as an MFMA dimension, then a 16-term gather (dlast.hip)
-    const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    return dlast_fwd(c, x, wf, bias, y, static_cast<float*>(workspace), st);
-  }
-  if (fold == FOLD_OUT && stats == nullptr && c7_out_ok(c)) {     // the generator head: marching kernel of c7.hip
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    return c7_out_fwd(c, x, static_cast<const char*>(wp) + n * elem_size(c->dtype), bias, act, y, st);
-  }
-  if (fold == FOLD_OUT) {
-    Plan& p = plans[0];
-    if (int rc = launch_gconv(p.d, c->dtype, x, wp, nullptr, nullptr, workspace, nullptr, st)) return rc;
-    if (int rc = launch_hsum(c->dtype, workspace, bias, y, c->N, Ho, Wo, Wo + c->S - 1, c->K, c->S, act, st)) return rc;
-    if (stats == nullptr) return P2PHD_OK;
-    float* scratch = reinterpret_cast<float*>(static_cast<char*>(workspace) + folded_dy_bytes(c, Ho, Wo));
-    return launch_plane_stats(c->dtype, y, stats, scratch, c->N, (long)Ho * Wo, c->K, st);
-  }
   const void* src = x;
   float* table = static_cast<float*>(workspace);
-  if (fold == FOLD_NONE && act == P2PHD_ACT_NONE && march_kind(c, 0)) {
-    // the generator's outermost stride-2 layer: marching kernel (march.hip), weights behind the generic pack
-    const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    if (int rc = march_run(c, 0, x, wf, bias, y, stats ? table : nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, st)) return rc;
-    if (stats == nullptr) return P2PHD_OK;
-    int slots = 0, ncls = 1, slot_rows = 0;
-    long npix_cls = 0;
-    march_plan(c, 0, &slots, &ncls, &slot_rows, &npix_cls, nullptr);
-    return launch_stats_merge(table, stats, c->N, slots, ncls, cpitch(c->K), c->K, npix_cls, slot_rows, st);
-  }
-  if (fold == FOLD_NONE && stats == nullptr && dfirst_ok(c)) {
-    // the discriminator's first layer (4 -> 64, 4 x 4 stride 2): pixels straight into MFMA fragments, weights in registers (dfirst.hip)
-    const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    return dfirst_fwd(c, x, wf, bias, act, y, st);
-  }
-  if (fold == FOLD_IN && act == P2PHD_ACT_NONE && c7_in_ok(c)) {
-    // dedicated 2-channel 7x7 kernel (c7.hip): halo once through LDS, weights in registers, whole-row stores
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    const void* wf = static_cast<const char*>(wp) + n * elem_size(c->dtype);
-    if (int rc = c7_in_fwd(c, x, wf, bias, y, stats ? table : nullptr, st)) return rc;
-    if (stats == nullptr) return P2PHD_OK;
-    return launch_stats_merge(table, stats, c->N, c7_in_slots(c), 1, cpitch(c->K), c->K, (long)Ho * Wo, 256, st);
-  }
-  if (fold == FOLD_IN) {
-    if (int rc = launch_expand_in(c->dtype, x, workspace, c->N, c->H, c->W, Wo, c->C, c->S, c->pad, c->pad_mode, st)) return rc;
-    src = workspace;
-    table = reinterpret_cast<float*>(static_cast<char*>(workspace) + folded_x_bytes(c, Wo));
+  switch (counted(fwd_route(L, act, stats != nullptr))) {
+    case R_DLAST:    // the discriminator's head (512 -> 1, 4 x 4): one pass over x with the 16 taps as an MFMA dimension, then a 16-term gather (dlast.hip)
+      return dlast_fwd(c, x, L.frag(wp), bias, y, table, st);
+    case R_C7_OUT:   // the generator head: marching kernel of c7.hip
+      return c7_out_fwd(c, x, L.frag(wp), bias, act, y, st);
+    case R_KFOLD: {
+      if (int rc = launch_gconv(L.plans[0].d, c->dtype, x, wp, nullptr, nullptr, workspace, nullptr, st)) return rc;
+      if (int rc = launch_hsum(c->dtype, workspace, bias, y, c->N, Ho, Wo, Wo + c->S - 1, c->K, c->S, act, st)) return rc;
+      if (stats == nullptr) return P2PHD_OK;
+      float* scratch = reinterpret_cast<float*>(static_cast<char*>(workspace) + folded_dy_bytes(c, Ho, Wo));
+      return launch_plane_stats(c->dtype, y, stats, scratch, c->N, (long)Ho * Wo, c->K, st);
+    }
+    case R_MARCH:    // the generator's outermost stride-2 layer: marching kernel (march.hip)
+      if (int rc = march_run(c, 0, x, L.frag(wp), bias, y, stats ? table : nullptr, nullptr, st)) return rc;
+      return stats ? march_stats_merge(c, table, stats, st) : P2PHD_OK;
+    case R_DFIRST:   // the discriminator's first layer (4 -> 64, 4 x 4 stride 2): pixels straight into MFMA fragments, weights in registers (dfirst.hip)
+      return dfirst_fwd(c, x, L.frag(wp), bias, act, y, st);
+    case R_C7_IN:    // dedicated 2-channel 7x7 kernel (c7.hip): halo once through LDS, weights in registers, whole-row stores
+      if (int rc = c7_in_fwd(c, x, L.frag(wp), bias, y, stats ? table : nullptr, st)) return rc;
+      return stats ? launch_stats_merge(table, stats, c->N, c7_in_slots(c), 1, cpitch(c->K), c->K, (long)Ho * Wo, 256, st) : P2PHD_OK;
+    case R_CFOLD:
+      if (int rc = launch_expand_in(c->dtype, x, workspace, c->N, c->H, c->W, Wo, c->C, c->S, c->pad, c->pad_mode, st)) return rc;
+      src = workspace;
+      table = reinterpret_cast<float*>(static_cast<char*>(workspace) + folded_x_bytes(c, Wo));
+      break;
+    default: break;
   }
   // InstanceNorm statistics: every wave of the conv epilogue stores the partial of its rows (plain stores), one merge
   // launch turns them into (mean, sum of squared deviations) per (sample, channel)
-  P2PHD_REQUIRE(stats == nullptr || plans.size() == 1, "conv_fwd: statistics need a single-launch plan");
+  P2PHD_REQUIRE(stats == nullptr || L.plans.size() == 1, "conv_fwd: statistics need a single-launch plan");
   int slot_rows = 0;
-  for (auto& p : plans) {
+  for (auto& p : L.plans) {
     p.d.act = act;
     const char* w = static_cast<const char*>(wp) + p.w_off * elem_size(c->dtype);
     if (int rc = launch_gconv(p.d, c->dtype, src, w, bias, nullptr, y, stats ? table : nullptr, st, &slot_rows)) return rc;
   }
   if (stats == nullptr) return P2PHD_OK;
-  const GDesc& d = plans[0].d;
+  const GDesc& d = L.plans[0].d;
   const long npix = (long)d.Hg * d.Wg;
   return launch_stats_merge(table, stats, c->N, (int)((npix + slot_rows - 1) / slot_rows), d.cls_cp > 0 ? 4 : 1, cpitch(c->K), c->K,
                             npix, slot_rows, st);
@@ -467,6 +492,14 @@ bool fp8_eligible(const p2phd_conv_desc* c) {
          (c->R * c->S * c->C) % 128 == 0;
 }
 size_t fp8_weight_bytes(const p2phd_conv_desc* c) { return align256((size_t)round_up(c->K, 128) * c->R * c->S * c->C); }
+// the single direct launch of an fp8 layer: GEMM-K = R * S * C unpadded (a multiple of 128)
+Plan fp8_plan(const p2phd_conv_desc* c) {
+  int Ho, Wo;
+  out_size(c, &Ho, &Wo);
+  Plan p = direct_plan(c->N, c->H, c->W, c->C, Ho, Wo, c->K, c->R, c->S, c->stride, c->pad, c->pad_mode);
+  p.d.KK = c->R * c->S * c->C;
+  return p;
+}
 }  // namespace
 
 extern "C" int p2phd_conv_fp8_eligible(const p2phd_conv_desc* c) { return check_desc(c) == P2PHD_OK && fp8_eligible(c) ? 1 : 0; }
@@ -480,10 +513,7 @@ extern "C" int p2phd_conv_fp8_pack_weights(const p2phd_conv_desc* c, const float
   if (int rc = check_desc(c)) return rc;
   P2PHD_REQUIRE(fp8_eligible(c), "conv_fp8: layer not eligible (stride-1 Conv2d, channels %% 16, taps * channels %% 128)");
   P2PHD_REQUIRE(w && packed8, "conv_fp8_pack_weights: null pointer");
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  Plan p = direct_plan(c->N, c->H, c->W, c->C, Ho, Wo, c->K, c->R, c->S, c->stride, c->pad, c->pad_mode);
-  p.d.KK = c->R * c->S * c->C;
+  const Plan p = fp8_plan(c);
   const long RS = (long)c->R * c->S;
   const WMap m = c->w_layout == 1 ? plain_map(c->K, c->C, c->C * RS, 1, c->S, c->C) : plain_map(c->K, c->C, c->C * RS, RS, c->S);
   char* tail = static_cast<char*>(packed8) + fp8_weight_bytes(c);
@@ -500,10 +530,7 @@ extern "C" int p2phd_conv_fwd_fp8(const p2phd_conv_desc* c, const void* x8, cons
   if (c->N == 0) return P2PHD_OK;
   P2PHD_REQUIRE(x8 && packed8 && y && (stats == nullptr || workspace), "conv_fwd_fp8: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  Plan p = direct_plan(c->N, c->H, c->W, c->C, Ho, Wo, c->K, c->R, c->S, c->stride, c->pad, c->pad_mode);
-  p.d.KK = c->R * c->S * c->C;
+  Plan p = fp8_plan(c);
   p.d.act = act;
   p.d.out_scale = reinterpret_cast<const float*>(static_cast<const char*>(packed8) + fp8_weight_bytes(c));
   float* table = static_cast<float*>(workspace);
@@ -515,15 +542,8 @@ extern "C" int p2phd_conv_fwd_fp8(const p2phd_conv_desc* c, const void* x8, cons
 }
 
 // ---- reflect-padded 3x3 input gradient whose pair-sum rows / columns were written by the producer of dy ----------------
-namespace {
-bool reflect3x3_exact(const p2phd_conv_desc* c) {
-  return c->pad_mode == 1 && fold_mode(c) != FOLD_OUT && !c->transposed && c->R == 3 && c->S == 3 && c->pad == 1 && c->stride == 1 &&
-         c->H >= 4 && c->W >= 4 && !g_opt_reflect_generic;
-}
-}  // namespace
-
 extern "C" size_t p2phd_conv_reflect_extras_elems(const p2phd_conv_desc* c) {
-  if (check_desc(c) != P2PHD_OK || !reflect3x3_exact(c) || c->N == 0) return 0;
+  if (check_desc(c) != P2PHD_OK || c->N == 0 || dgrad_route(layer(c, 1), false) != R_REFLECT_EXACT) return 0;
   if (p2phd_instnorm_act_bwd_two_pass(c->dtype, c->N, (int64_t)c->H * c->W, c->K)) return 0;   // (only the single-launch backward appends them)
   return (size_t)c->N * (2 * (c->W + 2) + 2 * c->H) * cpitch(c->K);
 }
@@ -533,13 +553,13 @@ extern "C" int p2phd_conv_dgrad_rx(const p2phd_conv_desc* c, const void* dy, con
   if (c->N == 0) return P2PHD_OK;
   P2PHD_REQUIRE(dy && wp && dx, "conv_dgrad_rx: null pointer");
   P2PHD_REQUIRE(p2phd_conv_reflect_extras_elems(c) > 0, "conv_dgrad_rx: layer has no reflection-extras form (p2phd_conv_reflect_extras_elems)");
-  std::vector<Plan> plans, ex; WMap m;
-  make_plans(c, 1, plans, &m);
+  const Layer L = layer(c, 1);
+  std::vector<Plan> ex;
   transposed_plans(c->N, c->H, c->W, c->K, c->H, c->W, c->C, c->R, c->S, 1, 1, ex);
-  P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == plans[0].d.KK && ex[0].rows_pad == plans[0].rows_pad, "conv_dgrad_rx: plan mismatch");
+  P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == L.plans[0].d.KK && ex[0].rows_pad == L.plans[0].rows_pad, "conv_dgrad_rx: plan mismatch");
   ex[0].d.pad_mode = 3;
   ex[0].d.rx_base = c->N * c->H * c->W;                          // dy [N, H, W, Cp(K)], then the extras [N][2 (W + 2) + 2 H][Cp(K)]
-  return launch_gconv(ex[0].d, c->dtype, dy, static_cast<const char*>(wp) + plans[0].w_off * elem_size(c->dtype), nullptr, addend, dx,
+  return launch_gconv(ex[0].d, c->dtype, dy, static_cast<const char*>(wp) + L.plans[0].w_off * elem_size(c->dtype), nullptr, addend, dx,
                       nullptr, (hipStream_t)stream);
 }
 
@@ -551,8 +571,7 @@ extern "C" size_t p2phd_conv_dgrad_workspace_bytes(const p2phd_conv_desc* c) {
   if (fold_mode(c) == FOLD_OUT) n += folded_dy_bytes(c, Ho, Wo);
   // the exact-grid form of a reflect-padded 3x3 input gradient keeps dy + its pair-sum rows / columns here instead:
   // [N][H + 2][W + 2][Cp(K)] -- K channels, where the padded-grid gradient has C
-  if (c->pad_mode == 1 && c->R == 3 && c->S == 3 && c->pad == 1 && c->stride == 1 && !c->transposed)
-    n = std::max(n, align256((size_t)c->N * (c->H + 2) * (c->W + 2) * cpitch(c->K) * elem_size(c->dtype)));
+  if (reflect3x3(c)) n = std::max(n, align256((size_t)c->N * (c->H + 2) * (c->W + 2) * cpitch(c->K) * elem_size(c->dtype)));
   return n;
 }
 
@@ -562,43 +581,35 @@ extern "C" int p2phd_conv_dgrad(const p2phd_conv_desc* c, const void* dy, const 
   if (c->N == 0) return P2PHD_OK;
   P2PHD_REQUIRE(dy && wp && dx, "conv_dgrad: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, 1, plans, &m);
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
+  const Layer L = layer(c, 1);
   const bool reflect = c->pad_mode == 1;
-  const bool kfold = fold_mode(c) == FOLD_OUT;
-  if (addend == nullptr && c7_out_dgrad_ok(c)) {
-    // Conv2d(ngf, 2, 7): the dedicated 2 -> ngf kernel with flipped weights and zero padding + the reflection fold of
-    // the 3-pixel frame (c7.hip); no padded-grid tensor, no fold pass over the whole gradient
-    size_t n = 0;
-    for (auto& p : plans) n += (size_t)p.rows_pad * p.d.KK;
-    const char* frag = static_cast<const char*>(wp) + n * elem_size(c->dtype);
-    const float* master = reinterpret_cast<const float*>(frag + c7_out_dgrad_packed_elems(c) * elem_size(c->dtype));
-    return c7_out_dgrad(c, dy, frag, master, dx, st);
-  }
-  if (addend == nullptr && march_kind(c, 1)) {
-    const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    return march_run(c, 1, dy, wf, nullptr, dx, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, st);
-  }
-  if (kfold && dlast_ok(c)) {
-    // the discriminator's head: dx in one pass, the 16 taps as the MFMA's K (dlast.hip)
-    const void* wg = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    return dlast_dgrad(c, dy, wg, addend, dx, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, st);
+  const bool kfold = L.fold == FOLD_OUT;
+  const Route route = counted(dgrad_route(L, addend != nullptr));
+  switch (route) {
+    case R_C7_DGRAD: {
+      // Conv2d(ngf, 2, 7): the dedicated 2 -> ngf kernel with flipped weights and zero padding + the reflection fold of
+      // the 3-pixel frame (c7.hip); no padded-grid tensor, no fold pass over the whole gradient
+      const char* frag = L.frag(wp);
+      return c7_out_dgrad(c, dy, frag, reinterpret_cast<const float*>(frag + L.tail_elems * elem_size(c->dtype)), dx, st);
+    }
+    case R_MARCH:
+      return march_run(c, 1, dy, L.frag(wp), nullptr, dx, nullptr, nullptr, st);
+    case R_DLAST:    // the discriminator's head: dx in one pass, the 16 taps as the MFMA's K (dlast.hip)
+      return dlast_dgrad(c, dy, L.frag(wp), addend, dx, nullptr, st);
+    default: break;
   }
   P2PHD_REQUIRE(!(reflect || kfold) || workspace, "conv_dgrad: this layer needs p2phd_conv_dgrad_workspace_bytes of scratch");
-  if (reflect && !kfold && !c->transposed && c->R == 3 && c->S == 3 && c->pad == 1 && c->stride == 1 && c->H >= 4 && c->W >= 4 &&
-      !g_opt_reflect_generic) {
-    // 3x3 behind ReflectionPad2d(1) (the residual trunk, networks.py:231-252): the adjoint of the reflection is moved
-    // in front of the GEMM -- dy gets two virtual rows / columns holding the pair sums the mirrored taps need -- and the
-    // input gradient runs on the exact H x W grid (pad_mode 2 gather), straight into dx with the skip gradient as
-    // addend: no padded-grid tensor (+19.5 % rows at 32 x 16) and no fold pass
+  if (route == R_REFLECT_EXACT) {
+    // 3x3 behind ReflectionPad2d(1): the adjoint of the reflection is moved in front of the GEMM -- dy gets two virtual
+    // rows / columns holding the pair sums the mirrored taps need -- and the input gradient runs on the exact H x W grid
+    // (pad_mode 2 gather), straight into dx with the skip gradient as addend: no padded-grid tensor (+19.5 % rows at
+    // 32 x 16) and no fold pass
     std::vector<Plan> ex;
     transposed_plans(c->N, c->H + 2, c->W + 2, c->K, c->H, c->W, c->C, c->R, c->S, 1, 1, ex);
-    P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == plans[0].d.KK && ex[0].rows_pad == plans[0].rows_pad, "conv_dgrad: plan mismatch");
+    P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == L.plans[0].d.KK && ex[0].rows_pad == L.plans[0].rows_pad, "conv_dgrad: plan mismatch");
     ex[0].d.pad_mode = 2;
     if (int rc = launch_reflect_expand(c->dtype, dy, workspace, c->N, c->H, c->W, cpitch(c->K), st)) return rc;
-    return launch_gconv(ex[0].d, c->dtype, workspace, static_cast<const char*>(wp) + plans[0].w_off * elem_size(c->dtype), nullptr,
+    return launch_gconv(ex[0].d, c->dtype, workspace, static_cast<const char*>(wp) + L.plans[0].w_off * elem_size(c->dtype), nullptr,
                         addend, dx, nullptr, st);
   }
   char* ws = static_cast<char*>(workspace);
@@ -606,10 +617,10 @@ extern "C" int p2phd_conv_dgrad(const p2phd_conv_desc* c, const void* dy, const 
   const void* src = dy;
   if (kfold) {
     void* dye = ws + padded_dx_bytes(c);
-    if (int rc = launch_expand_dy(c->dtype, dy, dye, c->N, Ho, Wo, Wo + c->S - 1, c->K, c->S, st)) return rc;
+    if (int rc = launch_expand_dy(c->dtype, dy, dye, c->N, L.Ho, L.Wo, L.Wo + c->S - 1, c->K, c->S, st)) return rc;
     src = dye;
   }
-  for (auto& p : plans) {
+  for (auto& p : L.plans) {
     const char* w = static_cast<const char*>(wp) + p.w_off * elem_size(c->dtype);
     if (int rc = launch_gconv(p.d, c->dtype, src, w, nullptr, reflect ? nullptr : addend, reflect ? dxp : dx, nullptr, st)) return rc;
   }
@@ -621,85 +632,81 @@ extern "C" int p2phd_conv_dgrad(const p2phd_conv_desc* c, const void* dy, const 
 namespace {
 // one plain or merged sub-pixel gather-GEMM launch writing dx directly (no reflect fold, no W-fold, not the 7x7 kernel),
 // on a tile shape that has the fused store loop (gconv 256x256 does not: see launch_gconv_t)
-bool dgrad_bsum_plans(const p2phd_conv_desc* c, std::vector<Plan>& plans) {
+bool bsum_layer(const p2phd_conv_desc* c, Layer* L) {
   if (check_desc(c) != P2PHD_OK || c->N == 0) return false;
-  if (c->pad_mode == 1 || c7_out_dgrad_ok(c)) return false;     // (the output W-fold is fine: its launch writes dx directly too)
-  WMap m;
-  make_plans(c, 1, plans, &m);
-  return plans.size() == 1;
+  if (c->pad_mode == 1) return false;                            // (the output W-fold is fine: its launch writes dx directly too)
+  *L = layer(c, 1);
+  return L->plans.size() == 1;
+}
+
+// the fused forms' source: dy, or its W-folded image (output-fold layers) behind the partial table in the workspace
+int bsum_src(const Layer& L, const void* dy, void* workspace, const void** src, hipStream_t st) {
+  *src = dy;
+  if (L.fold != FOLD_OUT) return P2PHD_OK;
+  P2PHD_REQUIRE(workspace, "conv_dgrad_bsum / _act: this layer needs p2phd_conv_dgrad_bsum_workspace_bytes of scratch");
+  const p2phd_conv_desc* c = L.c;
+  void* dye = static_cast<char*>(workspace) + align256(bsum_table_floats(L.plans[0].d) * sizeof(float));
+  *src = dye;
+  return launch_expand_dy(c->dtype, dy, dye, c->N, L.Ho, L.Wo, L.Wo + c->S - 1, c->K, c->S, st);
 }
 }  // namespace
 
 extern "C" int p2phd_conv_dgrad_bsum_ok(const p2phd_conv_desc* c) {
-  std::vector<Plan> plans;
-  return dgrad_bsum_plans(c, plans) ? 1 : 0;
+  Layer L;
+  return bsum_layer(c, &L) ? 1 : 0;
 }
 
 extern "C" int p2phd_conv_dgrad_bsum_pays(const p2phd_conv_desc* c) {
-  std::vector<Plan> plans;
-  if (!dgrad_bsum_plans(c, plans)) return 0;
+  Layer L;
+  if (!bsum_layer(c, &L)) return 0;
   // (deep reductions only: on the generator's 3072..3456-deep layers the two extra reduce launches cost what the tile gains)
-  return (gconv_plain_launch_takes_256x256(plans[0].d, c->dtype) && plans[0].d.KK >= 6144) ? 0 : 1;
+  return (gconv_plain_launch_takes_256x256(L.plans[0].d, c->dtype) && L.plans[0].d.KK >= 6144) ? 0 : 1;
 }
 
 extern "C" size_t p2phd_conv_dgrad_bsum_workspace_bytes(const p2phd_conv_desc* c) {
-  std::vector<Plan> plans;
-  if (!dgrad_bsum_plans(c, plans)) return 0;
-  size_t n = align256(bsum_table_floats(plans[0].d) * sizeof(float));
-  if (fold_mode(c) == FOLD_OUT) {                                // + the W-folded dy image of the 1-channel head
-    int Ho, Wo;
-    out_size(c, &Ho, &Wo);
-    n += folded_dy_bytes(c, Ho, Wo);
-  }
-  if (dlast_ok(c, true)) n = std::max(n, align256(dlast_bsum_table_floats(c) * sizeof(float)));
+  Layer L;
+  if (!bsum_layer(c, &L)) return 0;
+  size_t n = align256(bsum_table_floats(L.plans[0].d) * sizeof(float));
+  if (L.fold == FOLD_OUT) n += folded_dy_bytes(c, L.Ho, L.Wo);   // + the W-folded dy image of the 1-channel head
+  if (L.tail == TAIL_DLAST) n = std::max(n, align256(dlast_bsum_table_floats(c) * sizeof(float)));
   return n;
 }
 
 extern "C" int p2phd_conv_dgrad_bsum(const p2phd_conv_desc* c, const void* dy, const void* wp, const void* addend, void* dx,
                                      const void* prev_y, const float* prev_stats, int prev_act, float eps, float* bstats,
                                      void* workspace, void* stream) {
-  std::vector<Plan> plans;
-  P2PHD_REQUIRE(dgrad_bsum_plans(c, plans), "conv_dgrad_bsum: this layer's input gradient has no fused-sums form (p2phd_conv_dgrad_bsum_ok)");
+  Layer L;
+  P2PHD_REQUIRE(bsum_layer(c, &L), "conv_dgrad_bsum: this layer's input gradient has no fused-sums form (p2phd_conv_dgrad_bsum_ok)");
   P2PHD_REQUIRE(dy && wp && dx && prev_y && prev_stats && bstats && workspace, "conv_dgrad_bsum: null pointer");
   P2PHD_REQUIRE(prev_act == P2PHD_ACT_NONE || prev_act == P2PHD_ACT_RELU || prev_act == P2PHD_ACT_LRELU, "conv_dgrad_bsum: activation %d", prev_act);
   hipStream_t st = (hipStream_t)stream;
-  Plan& p = plans[0];
-  if (addend == nullptr && march_kind(c, 1)) {
-    // marching kernel with the producer's sums riding on its store pass; one partial row per workgroup
-    const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    const float slope = prev_act == P2PHD_ACT_RELU ? 0.f : (prev_act == P2PHD_ACT_LRELU ? 0.2f : 1.f);
-    float* part = static_cast<float*>(workspace);
-    if (int rc = march_run(c, 1, dy, wf, nullptr, dx, nullptr, prev_y, prev_stats, part, 1.f / ((float)c->H * (float)c->W), eps, slope, st)) return rc;
-    int tiles = 0;
-    march_plan(c, 1, nullptr, nullptr, nullptr, nullptr, &tiles);
-    const long npix = (long)c->H * c->W;
-    return launch_bsum_merge(part, bstats, c->N, npix, (int)(npix / tiles), cpitch(c->C), 0, cpitch(c->C), c->C, st);
+  const long npix = (long)c->H * c->W;                           // dx has the conv INPUT's geometry [N, H, W, C]
+  const BSum bs{prev_y, prev_stats, static_cast<float*>(workspace), 1.f / ((float)c->H * (float)c->W), eps, act_slope(prev_act)};
+  switch (counted(dgrad_route(L, addend != nullptr))) {
+    case R_MARCH: {  // marching kernel with the producer's sums riding on its store pass; one partial row per workgroup
+      if (int rc = march_run(c, 1, dy, L.frag(wp), nullptr, dx, nullptr, &bs, st)) return rc;
+      int tiles = 0;
+      march_plan(c, 1, nullptr, nullptr, nullptr, nullptr, &tiles);
+      return launch_bsum_merge(bs.out, bstats, c->N, npix, (int)(npix / tiles), cpitch(c->C), 0, cpitch(c->C), c->C, st);
+    }
+    case R_DLAST: {  // the discriminator's head (dlast.hip): one partial row per wave (slot) and sample
+      if (int rc = dlast_dgrad(c, dy, L.frag(wp), addend, dx, &bs, st)) return rc;
+      int bpw = 0;
+      dlast_dgrad_plan(c, &bpw, nullptr);
+      return launch_bsum_merge(bs.out, bstats, c->N, npix, bpw * 16, cpitch(c->C), 0, cpitch(c->C), c->C, st);
+    }
+    default: break;
   }
-  if (dlast_ok(c)) {
-    // the discriminator's head (dlast.hip): one partial row per wave (slot) and sample
-    const void* wg = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
-    const float slope = prev_act == P2PHD_ACT_RELU ? 0.f : (prev_act == P2PHD_ACT_LRELU ? 0.2f : 1.f);
-    float* part = static_cast<float*>(workspace);
-    if (int rc = dlast_dgrad(c, dy, wg, addend, dx, prev_y, prev_stats, part, 1.f / ((float)c->H * (float)c->W), eps, slope, st)) return rc;
-    int bpw = 0;
-    dlast_dgrad_plan(c, &bpw, nullptr);
-    return launch_bsum_merge(part, bstats, c->N, (long)c->H * c->W, bpw * 16, cpitch(c->C), 0, cpitch(c->C), c->C, st);
-  }
-  p.d.bs_y = prev_y;
-  p.d.bs_stats = prev_stats;
-  p.d.bs_out = static_cast<float*>(workspace);
-  p.d.bs_inv_hw = 1.f / ((float)c->H * (float)c->W);            // dx has the conv INPUT's geometry [N, H, W, C]
-  p.d.bs_eps = eps;
-  p.d.bs_slope = prev_act == P2PHD_ACT_RELU ? 0.f : (prev_act == P2PHD_ACT_LRELU ? 0.2f : 1.f);
+  Plan& p = L.plans[0];
+  p.d.bs_y = bs.y;
+  p.d.bs_stats = bs.stats;
+  p.d.bs_out = bs.out;
+  p.d.bs_inv_hw = bs.inv_hw;
+  p.d.bs_eps = bs.eps;
+  p.d.bs_slope = bs.slope;
   const char* w = static_cast<const char*>(wp) + p.w_off * elem_size(c->dtype);
-  const void* src = dy;
-  if (fold_mode(c) == FOLD_OUT) {
-    int Ho, Wo;
-    out_size(c, &Ho, &Wo);
-    void* dye = static_cast<char*>(workspace) + align256(bsum_table_floats(p.d) * sizeof(float));
-    if (int rc = launch_expand_dy(c->dtype, dy, dye, c->N, Ho, Wo, Wo + c->S - 1, c->K, c->S, st)) return rc;
-    src = dye;
-  }
+  const void* src;
+  if (int rc = bsum_src(L, dy, workspace, &src, st)) return rc;
   int tile_rows = 0;
   if (int rc = launch_gconv(p.d, c->dtype, src, w, nullptr, addend, dx, nullptr, st, &tile_rows)) return rc;
   const int n_extent = p.d.n_extent ? p.d.n_extent : p.d.Cp_out;
@@ -708,33 +715,26 @@ extern "C" int p2phd_conv_dgrad_bsum(const p2phd_conv_desc* c, const void* dy, c
 
 extern "C" int p2phd_conv_dgrad_act(const p2phd_conv_desc* c, const void* dy, const void* wp, const void* addend, void* dx,
                                     const void* x_act, int prev_act, void* workspace, void* stream) {
-  std::vector<Plan> plans;
-  P2PHD_REQUIRE(dgrad_bsum_plans(c, plans), "conv_dgrad_act: this layer's input gradient has no fused form (p2phd_conv_dgrad_bsum_ok)");
+  Layer L;
+  P2PHD_REQUIRE(bsum_layer(c, &L), "conv_dgrad_act: this layer's input gradient has no fused form (p2phd_conv_dgrad_bsum_ok)");
   P2PHD_REQUIRE(dy && wp && dx && x_act, "conv_dgrad_act: null pointer");
   P2PHD_REQUIRE(prev_act == P2PHD_ACT_RELU || prev_act == P2PHD_ACT_LRELU, "conv_dgrad_act: activation %d", prev_act);
   hipStream_t st = (hipStream_t)stream;
-  Plan& p = plans[0];
+  Plan& p = L.plans[0];                                          // (always the generic launch, on marching and dlast layers too)
   p.d.as_x = x_act;
-  p.d.bs_slope = prev_act == P2PHD_ACT_RELU ? 0.f : 0.2f;
+  p.d.bs_slope = act_slope(prev_act);
   const char* w = static_cast<const char*>(wp) + p.w_off * elem_size(c->dtype);
-  const void* src = dy;
-  if (fold_mode(c) == FOLD_OUT) {
-    P2PHD_REQUIRE(workspace, "conv_dgrad_act: this layer needs p2phd_conv_dgrad_bsum_workspace_bytes of scratch");
-    int Ho, Wo;
-    out_size(c, &Ho, &Wo);
-    void* dye = static_cast<char*>(workspace) + align256(bsum_table_floats(p.d) * sizeof(float));
-    if (int rc = launch_expand_dy(c->dtype, dy, dye, c->N, Ho, Wo, Wo + c->S - 1, c->K, c->S, st)) return rc;
-    src = dye;
-  }
+  const void* src;
+  if (int rc = bsum_src(L, dy, workspace, &src, st)) return rc;
   return launch_gconv(p.d, c->dtype, src, w, nullptr, addend, dx, nullptr, st);
 }
 
 namespace {
 // everything p2phd_conv_wgrad needs, derived once for both the workspace query and the call
-struct WgradSetup { Plan p; WMap m; int M; int Cp_r; int fold; size_t dwp_bytes; };
+struct WgradSetup { Plan p; WMap m; int M; int Cp_r; int fold; size_t dwp_bytes; int Ho, Wo; };
 void wgrad_setup(const p2phd_conv_desc* c, WgradSetup* w) {
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
+  out_size(c, &w->Ho, &w->Wo);
+  const int Ho = w->Ho, Wo = w->Wo;
   const long RS = (long)c->R * c->S;
   w->fold = fold_mode(c);
   if (w->fold == FOLD_OUT) {       // dWp[(tw,k)][th][c] = sum dyE[n,ho,w',(tw,k)] * x[n, ho+th-pad, w'-pad, c]
@@ -751,42 +751,11 @@ void wgrad_setup(const p2phd_conv_desc* c, WgradSetup* w) {
   }
   w->dwp_bytes = align256(wgrad_workspace_floats(w->p.d, c->dtype, w->M, round_up(w->M, 128)) * sizeof(float));
 }
-}  // namespace
 
-extern "C" size_t p2phd_conv_wgrad_workspace_bytes(const p2phd_conv_desc* c) {
-  if (check_desc(c) != P2PHD_OK) return 0;
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  if (thin_wgrad_kind(c)) return align256(thin_wgrad_workspace_floats(c) * sizeof(float));
+int wgrad_generic(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, int accumulate, void* workspace, hipStream_t st) {
   WgradSetup w;
   wgrad_setup(c, &w);
-  size_t extra = 0;
-  if (w.fold == FOLD_OUT) extra = folded_dy_bytes(c, Ho, Wo);
-  else if (w.fold == FOLD_IN) extra = folded_x_bytes(c, Wo);
-  // (the marching weight-gradient kernel keeps one slab per workgroup; sized for it whatever the option says at the moment)
-  const size_t mw = align256(march_w_workspace_floats(c) * sizeof(float));
-  return std::max(w.dwp_bytes + extra, mw);
-}
-
-static int conv_wgrad_impl(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, float* db, int accumulate,
-                           void* workspace, void* stream) {
-  if (int rc = check_desc(c)) return rc;
-  P2PHD_REQUIRE(x && dy && dw && workspace, "conv_wgrad: null pointer");
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  hipStream_t st = (hipStream_t)stream;
-  if (c->dtype == P2PHD_BF16 && march_w_ok(c)) {                  // the generator's outermost stride-2 layers (march.hip)
-    if (int rc = march_w_run(c, x, dy, dw, accumulate, nullptr, 1.f, 0.f, static_cast<float*>(workspace), st)) return rc;
-    if (db != nullptr) return launch_colsum(c->dtype, dy, (long)c->N * Ho * Wo, cpitch(c->K), c->K, db, accumulate, st);
-    return P2PHD_OK;
-  }
-  if (thin_wgrad_kind(c)) {                                       // dedicated kernel for the <= 4-channel layers (thinwgrad.hip)
-    if (int rc = thin_wgrad(c, x, dy, dw, accumulate, static_cast<float*>(workspace), st)) return rc;
-    if (db != nullptr) return launch_colsum(c->dtype, dy, (long)c->N * Ho * Wo, cpitch(c->K), c->K, db, accumulate, st);
-    return P2PHD_OK;
-  }
-  WgradSetup w;
-  wgrad_setup(c, &w);
+  const int Ho = w.Ho, Wo = w.Wo;
   float* dwp = static_cast<float*>(workspace);
   char* extra = static_cast<char*>(workspace) + w.dwp_bytes;
   const void *rows_t, *gat_t;
@@ -801,9 +770,44 @@ static int conv_wgrad_impl(const p2phd_conv_desc* c, const void* x, const void* 
   } else {
     rows_t = x; gat_t = dy;
   }
-  if (int rc = launch_wgrad(w.p.d, w.m, c->dtype, rows_t, w.Cp_r, w.M, round_up(w.M, 128), gat_t, dwp, dw, accumulate, st)) return rc;
-  if (db != nullptr) return launch_colsum(c->dtype, dy, (long)c->N * Ho * Wo, cpitch(c->K), c->K, db, accumulate, st);
-  return P2PHD_OK;
+  return launch_wgrad(w.p.d, w.m, c->dtype, rows_t, w.Cp_r, w.M, round_up(w.M, 128), gat_t, dwp, dw, accumulate, st);
+}
+
+// the bias gradient of every weight-gradient form: column sums of dy
+int wgrad_bias(const p2phd_conv_desc* c, const void* dy, float* db, int accumulate, hipStream_t st) {
+  if (db == nullptr) return P2PHD_OK;
+  int Ho, Wo;
+  out_size(c, &Ho, &Wo);
+  return launch_colsum(c->dtype, dy, (long)c->N * Ho * Wo, cpitch(c->K), c->K, db, accumulate, st);
+}
+}  // namespace
+
+extern "C" size_t p2phd_conv_wgrad_workspace_bytes(const p2phd_conv_desc* c) {
+  if (check_desc(c) != P2PHD_OK) return 0;
+  if (wgrad_route(c) == R_THIN) return align256(thin_wgrad_workspace_floats(c) * sizeof(float));
+  WgradSetup w;
+  wgrad_setup(c, &w);
+  size_t extra = 0;
+  if (w.fold == FOLD_OUT) extra = folded_dy_bytes(c, w.Ho, w.Wo);
+  else if (w.fold == FOLD_IN) extra = folded_x_bytes(c, w.Wo);
+  // (the marching weight-gradient kernel keeps one slab per workgroup; sized for it whatever the option says at the moment)
+  const size_t mw = align256(march_w_workspace_floats(c) * sizeof(float));
+  return std::max(w.dwp_bytes + extra, mw);
+}
+
+static int conv_wgrad_impl(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, float* db, int accumulate,
+                           void* workspace, void* stream) {
+  if (int rc = check_desc(c)) return rc;
+  P2PHD_REQUIRE(x && dy && dw && workspace, "conv_wgrad: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  float* slabs = static_cast<float*>(workspace);
+  int rc;
+  switch (counted(wgrad_route(c))) {
+    case R_MARCH_W: rc = march_w_run(c, x, dy, dw, accumulate, nullptr, 1.f, 0.f, slabs, st); break;   // the generator's outermost stride-2 layers (march.hip)
+    case R_THIN: rc = thin_wgrad(c, x, dy, dw, accumulate, slabs, st); break;                          // the <= 4-channel layers (thinwgrad.hip)
+    default: rc = wgrad_generic(c, x, dy, dw, accumulate, workspace, st);
+  }
+  return rc ? rc : wgrad_bias(c, dy, db, accumulate, st);
 }
 
 extern "C" int p2phd_conv_wgrad(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, float* db,
@@ -823,7 +827,7 @@ extern "C" int p2phd_conv_wgrad_acc(const p2phd_conv_desc* c, const void* x, con
 // the p2phd_instnorm_act_fwd pass over that plane never runs.  Values are those of the materialised form, bit for bit.
 extern "C" int p2phd_conv_lazy_ok(const p2phd_conv_desc* c) {
   if (c == nullptr || check_desc(c) != P2PHD_OK || c->N == 0) return 0;
-  return (c->dtype == P2PHD_BF16 && march_kind(c, 0) != 0 && march_w_ok(c)) ? 1 : 0;
+  return wgrad_route(c) == R_MARCH_W ? 1 : 0;                    // (the layers of march_w are those of the forward's march)
 }
 
 extern "C" int p2phd_conv_fwd_lazy(const p2phd_conv_desc* c, const void* x_raw, const float* x_stats, int x_act, float x_eps,
@@ -833,19 +837,10 @@ extern "C" int p2phd_conv_fwd_lazy(const p2phd_conv_desc* c, const void* x_raw, 
   P2PHD_REQUIRE(x_raw && x_stats && wp && y && (stats == nullptr || workspace), "conv_fwd_lazy: null pointer");
   P2PHD_REQUIRE(x_act == P2PHD_ACT_NONE || x_act == P2PHD_ACT_RELU || x_act == P2PHD_ACT_LRELU, "conv_fwd_lazy: activation %d", x_act);
   hipStream_t st = (hipStream_t)stream;
-  std::vector<Plan> plans; WMap m;
-  make_plans(c, 0, plans, &m);
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  const float slope = x_act == P2PHD_ACT_RELU ? 0.f : (x_act == P2PHD_ACT_LRELU ? 0.2f : 1.f);
-  const void* wf = static_cast<const char*>(wp) + generic_packed_elems(plans) * elem_size(c->dtype);
   float* table = static_cast<float*>(workspace);
-  if (int rc = march_run(c, 0, x_raw, wf, bias, y, stats ? table : nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, st, x_stats, slope, x_eps)) return rc;
-  if (stats == nullptr) return P2PHD_OK;
-  int slots = 0, ncls = 1, slot_rows = 0;
-  long npix_cls = 0;
-  march_plan(c, 0, &slots, &ncls, &slot_rows, &npix_cls, nullptr);
-  return launch_stats_merge(table, stats, c->N, slots, ncls, cpitch(c->K), c->K, npix_cls, slot_rows, st);
+  counted(R_MARCH);
+  if (int rc = march_run(c, 0, x_raw, layer(c, 0).frag(wp), bias, y, stats ? table : nullptr, nullptr, st, x_stats, act_slope(x_act), x_eps)) return rc;
+  return stats ? march_stats_merge(c, table, stats, st) : P2PHD_OK;
 }
 
 extern "C" int p2phd_conv_wgrad_lazy(const p2phd_conv_desc* c, const void* x_raw, const float* x_stats, int x_act, float x_eps,
@@ -855,10 +850,7 @@ extern "C" int p2phd_conv_wgrad_lazy(const p2phd_conv_desc* c, const void* x_raw
   P2PHD_REQUIRE(x_raw && x_stats && dy && dw && workspace, "conv_wgrad_lazy: null pointer");
   P2PHD_REQUIRE(x_act == P2PHD_ACT_NONE || x_act == P2PHD_ACT_RELU || x_act == P2PHD_ACT_LRELU, "conv_wgrad_lazy: activation %d", x_act);
   hipStream_t st = (hipStream_t)stream;
-  int Ho, Wo;
-  out_size(c, &Ho, &Wo);
-  const float slope = x_act == P2PHD_ACT_RELU ? 0.f : (x_act == P2PHD_ACT_LRELU ? 0.2f : 1.f);
-  if (int rc = march_w_run(c, x_raw, dy, dw, accumulate, x_stats, slope, x_eps, static_cast<float*>(workspace), st)) return rc;
-  if (db != nullptr) return launch_colsum(c->dtype, dy, (long)c->N * Ho * Wo, cpitch(c->K), c->K, db, accumulate, st);
-  return P2PHD_OK;
+  counted(R_MARCH_W);
+  if (int rc = march_w_run(c, x_raw, dy, dw, accumulate, x_stats, act_slope(x_act), x_eps, static_cast<float*>(workspace), st)) return rc;
+  return wgrad_bias(c, dy, db, accumulate, st);
 }

@@ -69,8 +69,10 @@ int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, in
                     hipStream_t st);
 
 // launch counters (p2phd_launch_count): which kernel family a call really took -- tests assert that the benchmarked step runs
-// on the round-4/5 kernels and not on the generic loop behind them
-enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192, LC_FAMILIES };
+// on the round-3..5 kernels and not on the generic loop behind them.  The dedicated routes (march, march_w, dfirst, dlast, c7,
+// thin_wgrad) are counted where convapi.hip picks them, the tile-level families (gconv .. tile128x192) inside conv.hip
+enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192,
+                    LC_DFIRST, LC_DLAST, LC_C7, LC_THIN_WGRAD, LC_FAMILIES };
 extern unsigned long long g_launch_count[LC_FAMILIES];
 
 // tuning overrides (p2phd_set_option): 0 = heuristic
@@ -85,54 +87,54 @@ int device_cus();                   // multiProcessorCount of the current device
 extern int g_opt_reflect_generic;   // 1: reflect-padded 3x3 input gradients on the padded grid + fold (the general form)
 extern int g_opt_c7_abl;          // timing experiments only (tools/time_c7.py): skip parts of c7_out_fwd      // 1: the 7x7 2-channel layers always take the generic W-fold path
 
+// Dedicated kernels of single layers.  Each file exports its shape rule only (`*_shape_ok`, `*_shape_kind`): which launch
+// takes the kernel, given the options of p2phd_set_option, is decided by the route functions of convapi.hip.
+// fused first pass of the consumer's InstanceNorm backward on a dedicated input-gradient kernel (the GDesc::bs_* fields)
+struct BSum { const void* y; const float* stats; float* out; float inv_hw, eps, slope; };
 // c7.hip: dedicated bf16 kernels of the generator's 7x7 end layers (full tiles of 8 x 128 pixels only)
-bool c7_in_ok(const p2phd_conv_desc* c, bool ignore_option = false);
+bool c7_in_shape_ok(const p2phd_conv_desc* c);
 size_t c7_in_packed_elems(const p2phd_conv_desc* c);
 int c7_in_pack(const p2phd_conv_desc* c, const float* w, void* wf, hipStream_t st);
 int c7_in_slots(const p2phd_conv_desc* c);
 int c7_in_fwd(const p2phd_conv_desc* c, const void* x, const void* wf, const float* bias, void* y, float* table, hipStream_t st);
-bool c7_out_ok(const p2phd_conv_desc* c, bool ignore_option = false);
+bool c7_out_shape_ok(const p2phd_conv_desc* c);
 size_t c7_out_packed_elems(const p2phd_conv_desc* c);
 int c7_out_pack(const p2phd_conv_desc* c, const float* w, void* wf, hipStream_t st);
 int c7_out_fwd(const p2phd_conv_desc* c, const void* x, const void* wf, const float* bias, int act, void* y, hipStream_t st);
-bool c7_out_dgrad_ok(const p2phd_conv_desc* c, bool ignore_option = false);
+bool c7_dgrad_shape_ok(const p2phd_conv_desc* c);
 size_t c7_out_dgrad_packed_elems(const p2phd_conv_desc* c);
 int c7_out_dgrad_pack(const p2phd_conv_desc* c, const float* w, void* wf, hipStream_t st);
 int c7_out_dgrad(const p2phd_conv_desc* c, const void* dy, const void* wf, const float* w_master, void* dx, hipStream_t st);
 // dfirst.hip: forward of the discriminator's first layer (Conv2d(<= 8, 64, 4, stride 2, padding 2) + activation, no statistics), bf16
 extern int g_opt_dfirst;
-bool dfirst_ok(const p2phd_conv_desc* c, bool ignore_option = false);
+bool dfirst_shape_ok(const p2phd_conv_desc* c);
 size_t dfirst_packed_elems(const p2phd_conv_desc* c);
 int dfirst_pack(const p2phd_conv_desc* c, const float* w, void* wf, hipStream_t st);
 int dfirst_fwd(const p2phd_conv_desc* c, const void* x, const void* wf, const float* bias, int act, void* y, hipStream_t st);
 // dlast.hip: the discriminator's last layer (Conv2d(C, 1, 4, stride 1, padding 2), C a multiple of 128 up to 512), bf16: forward and input gradient
 extern int g_opt_dlast;
-bool dlast_ok(const p2phd_conv_desc* c, bool ignore_option = false);
+bool dlast_shape_ok(const p2phd_conv_desc* c);
 size_t dlast_packed_elems(const p2phd_conv_desc* c, int which);
 int dlast_pack(const p2phd_conv_desc* c, int which, const float* w, void* wfrag, hipStream_t st);
 size_t dlast_fwd_workspace_floats(const p2phd_conv_desc* c);
 int dlast_fwd(const p2phd_conv_desc* c, const void* x, const void* wf, const float* bias, void* y, float* part, hipStream_t st);
 void dlast_dgrad_plan(const p2phd_conv_desc* c, int* bpw, int* slots);
 size_t dlast_bsum_table_floats(const p2phd_conv_desc* c);
-int dlast_dgrad(const p2phd_conv_desc* c, const void* dy, const void* wg, const void* addend, void* dx, const void* bs_y,
-                const float* bs_stats, float* bs_out, float bs_inv_hw, float bs_eps, float bs_slope, hipStream_t st);
+int dlast_dgrad(const p2phd_conv_desc* c, const void* dy, const void* wg, const void* addend, void* dx, const BSum* bs, hipStream_t st);
 // march.hip: marching kernels of the generator's outermost stride-2 3x3 layers (bf16); which: 0 = forward, 1 = input gradient
 extern int g_opt_march; extern int g_opt_cls_skip; extern int g_opt_gconv_halo; extern int g_opt_cw_inject;            // 1 (default): eligible layers take the marching kernels, 0: the generic gather-GEMM (A/B, parity tests)
-int march_kind(const p2phd_conv_desc* c, int which);
-int march_shape_kind(const p2phd_conv_desc* c, int which);     // the shape rule without the option (pack / workspace sizes)
+int march_shape_kind(const p2phd_conv_desc* c, int which);
 size_t march_packed_elems(const p2phd_conv_desc* c, int which);
 int march_pack(const p2phd_conv_desc* c, int which, const float* w, void* wf, hipStream_t st);
 void march_plan(const p2phd_conv_desc* c, int which, int* slots, int* ncls, int* slot_rows, long* npix_cls, int* bs_tiles);
 // in_stats != nullptr (forward launches): `in` is the raw output of an InstanceNorm block, normalised + activated on load
 int march_run(const p2phd_conv_desc* c, int which, const void* in, const void* wf, const float* bias, void* out, float* table,
-              const void* bs_y, const float* bs_stats, float* bs_out, float bs_inv_hw, float bs_eps, float bs_slope, hipStream_t st,
-              const float* in_stats = nullptr, float in_slope = 1.f, float in_eps = 0.f);
-bool march_w_ok(const p2phd_conv_desc* c);
+              const BSum* bs, hipStream_t st, const float* in_stats = nullptr, float in_slope = 1.f, float in_eps = 0.f);
 size_t march_w_workspace_floats(const p2phd_conv_desc* c);
 int march_w_run(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, int accumulate, const float* x_stats, float x_slope,
                 float x_eps, float* slabs, hipStream_t st);
 // thinwgrad.hip: weight gradient of the layers with <= 4 channels on one side (bf16); kind 0 = not eligible
-int thin_wgrad_kind(const p2phd_conv_desc* c);
+int thin_wgrad_shape_kind(const p2phd_conv_desc* c);
 size_t thin_wgrad_workspace_floats(const p2phd_conv_desc* c);
 int thin_wgrad(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, int accumulate, float* slabs, hipStream_t st);
 

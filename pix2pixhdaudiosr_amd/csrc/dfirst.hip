@@ -143,10 +143,8 @@ __global__ __launch_bounds__(256) void dfirst_fwd_kernel(const DFirstArgs a) {
 
 namespace p2phd {
 
-int g_opt_dfirst = 1;
-
-bool dfirst_ok(const p2phd_conv_desc* c, bool ignore_option) {
-  return (ignore_option || g_opt_dfirst != 0) && c->dtype == P2PHD_BF16 && !c->transposed && c->C >= 1 && c->C <= 8 && c->K == 64 &&
+bool dfirst_shape_ok(const p2phd_conv_desc* c) {
+  return c->dtype == P2PHD_BF16 && !c->transposed && c->C >= 1 && c->C <= 8 && c->K == 64 &&
          c->R == 4 && c->S == 4 && c->stride == 2 && c->pad == 2 && c->pad_mode == 0 && c->H >= 2 && c->W >= 2 &&
          (size_t)c->N * c->H * c->W * 16 < 0xFFFFFFF0ull;
 }

@@ -246,10 +246,8 @@ __global__ __launch_bounds__(256) void dlast_dgrad_kernel(const DLastGradArgs a)
 
 namespace p2phd {
 
-int g_opt_dlast = 1;
-
-bool dlast_ok(const p2phd_conv_desc* c, bool ignore_option) {
-  return (ignore_option || g_opt_dlast != 0) && c->dtype == P2PHD_BF16 && !c->transposed && c->K == 1 && c->C % kQCH == 0 && c->C >= kQCH &&
+bool dlast_shape_ok(const p2phd_conv_desc* c) {
+  return c->dtype == P2PHD_BF16 && !c->transposed && c->K == 1 && c->C % kQCH == 0 && c->C >= kQCH &&
          c->C <= 32 * kMaxKS && c->R == 4 && c->S == 4 && c->stride == 1 && c->pad == 2 && c->pad_mode == 0 &&
          (size_t)c->N * c->H * c->W * c->C * 2 < 0xFFFFFFF0ull;
 }
@@ -304,16 +302,17 @@ size_t dlast_bsum_table_floats(const p2phd_conv_desc* c) {
   return (size_t)c->N * slots * c->C * 2;
 }
 
-// dx [N, H, W, C] = input gradient (+ addend); bs_out != nullptr: partial sums [N][slots][C][2] of the producer's InstanceNorm backward
-int dlast_dgrad(const p2phd_conv_desc* c, const void* dy, const void* wg, const void* addend, void* dx, const void* bs_y,
-                const float* bs_stats, float* bs_out, float bs_inv_hw, float bs_eps, float bs_slope, hipStream_t st) {
+// dx [N, H, W, C] = input gradient (+ addend); bs != nullptr: partial sums [N][slots][C][2] of the producer's InstanceNorm backward
+int dlast_dgrad(const p2phd_conv_desc* c, const void* dy, const void* wg, const void* addend, void* dx, const BSum* bs, hipStream_t st) {
   DLastGradArgs a{};
   a.dy = (const bf16_t*)dy; a.wg = (const bf16_t*)wg; a.addend = (const bf16_t*)addend; a.dx = (bf16_t*)dx;
   a.N = c->N; a.H = c->H; a.W = c->W; a.C = c->C;
   a.Ho = c->H + 2 * c->pad - c->R + 1; a.Wo = c->W + 2 * c->pad - c->S + 1;
   dlast_dgrad_plan(c, &a.bpw, &a.slots);
-  a.bs_y = (const bf16_t*)bs_y; a.bs_stats = bs_stats; a.bs_out = bs_out;
-  a.bs_inv_hw = bs_inv_hw; a.bs_eps = bs_eps; a.bs_slope = bs_slope;
+  if (bs) {
+    a.bs_y = (const bf16_t*)bs->y; a.bs_stats = bs->stats; a.bs_out = bs->out;
+    a.bs_inv_hw = bs->inv_hw; a.bs_eps = bs->eps; a.bs_slope = bs->slope;
+  }
   const long waves = (long)c->N * a.slots * (c->C / kQCH);
   hipLaunchKernelGGL(dlast_dgrad_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
   return check_launch("dlast_dgrad");

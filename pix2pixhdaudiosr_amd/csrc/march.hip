@@ -879,8 +879,7 @@ namespace p2phd {
 // kind of marching kernel a layer's launch takes (0 = none).  which: 0 = forward, 1 = input gradient.
 //   1 = "S" 48 -> 96 gather: Conv2d(48, 96, 3, s2, p1) forward; input gradient of ConvTranspose2d(96, 48, 3, s2, p1, op1)
 //   2 = "U" 96 -> 48 transposed form: that ConvTranspose2d's forward; that Conv2d's input gradient
-// march_shape_kind: the shape rule alone (what the packed buffer and the workspace must hold whatever the option says at the
-// moment of the pack); march_kind: what a launch takes now.
+// The shape rule alone: whether a launch takes the kernel is decided by the conv API (convapi.hip), which reads the option.
 int march_shape_kind(const p2phd_conv_desc* c, int which) {
   if (c->dtype != P2PHD_BF16 || c->R != 3 || c->S != 3 || c->stride != 2 || c->pad != 1 || c->pad_mode != 0) return 0;
   const bool conv = !c->transposed && c->C == 48 && c->K == 96 && c->H % 2 == 0 && c->W % 128 == 0 && c->H >= 8;
@@ -889,7 +888,6 @@ int march_shape_kind(const p2phd_conv_desc* c, int which) {
   if (which == 1) return convt ? 1 : (conv ? 2 : 0);
   return 0;
 }
-int march_kind(const p2phd_conv_desc* c, int which) { return g_opt_march == 0 ? 0 : march_shape_kind(c, which); }
 
 namespace {
 typedef SGeom<48, 96, 64> GS;
@@ -939,7 +937,7 @@ int march_pack(const p2phd_conv_desc* c, int which, const float* w, void* wf, hi
 // geometry of the launch `march_run` will make: statistics slots per sample, classes per slot, pixels per (slot, class) and
 // per-class plane size (what launch_stats_merge needs); fused-sums partial rows per sample
 void march_plan(const p2phd_conv_desc* c, int which, int* slots, int* ncls, int* slot_rows, long* npix_cls, int* bs_tiles) {
-  const int kind = march_kind(c, which);
+  const int kind = march_shape_kind(c, which);
   const MarchGeom g = march_geom(c, kind, which);
   const int nwm = kind == 1 ? GS::NWM : GU::NWM;
   if (slots) *slots = g.strips * g.nseg * nwm;
@@ -950,9 +948,8 @@ void march_plan(const p2phd_conv_desc* c, int which, int* slots, int* ncls, int*
 }
 
 int march_run(const p2phd_conv_desc* c, int which, const void* in, const void* wf, const float* bias, void* out, float* table,
-              const void* bs_y, const float* bs_stats, float* bs_out, float bs_inv_hw, float bs_eps, float bs_slope, hipStream_t st,
-              const float* in_stats, float in_slope, float in_eps) {
-  const int kind = march_kind(c, which);
+              const BSum* bs, hipStream_t st, const float* in_stats, float in_slope, float in_eps) {
+  const int kind = march_shape_kind(c, which);
   P2PHD_REQUIRE(kind == 1 || kind == 2, "march_run: layer has no marching kernel");
   const MarchGeom g = march_geom(c, kind, which);
   MarchArgs a{};
@@ -963,12 +960,13 @@ int march_run(const p2phd_conv_desc* c, int which, const void* in, const void* w
   const size_t ib = (size_t)a.N * a.Hin * a.Win * (kind == 1 ? 48 : 96) * 2;
   P2PHD_REQUIRE(ib < 0xFFFFFFF0ull, "march: tensor larger than 4 GiB");
   a.in_bytes = (unsigned)ib;
-  a.bs_y = (const bf16_t*)bs_y; a.bs_stats = bs_stats; a.bs_out = bs_out;
-  a.bs_inv_hw = bs_inv_hw; a.bs_eps = bs_eps; a.bs_slope = bs_slope;
+  if (bs) {
+    a.bs_y = (const bf16_t*)bs->y; a.bs_stats = bs->stats; a.bs_out = bs->out;
+    a.bs_inv_hw = bs->inv_hw; a.bs_eps = bs->eps; a.bs_slope = bs->slope;
+  }
   a.in_stats = in_stats; a.in_slope = in_slope; a.in_eps = in_eps; a.in_inv_hw = 1.f / ((float)a.Hin * (float)a.Win);
-  P2PHD_REQUIRE(in_stats == nullptr || bs_out == nullptr, "march_run: a lazily normalised input goes with forward launches");
+  P2PHD_REQUIRE(in_stats == nullptr || bs == nullptr, "march_run: a lazily normalised input goes with forward launches");
   const dim3 grid((unsigned)(a.N * a.strips * a.nseg));
-  ++g_launch_count[LC_MARCH];
   auto launch = [&](auto kern, int lds, const char* what) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, st, a);
@@ -976,17 +974,15 @@ int march_run(const p2phd_conv_desc* c, int which, const void* in, const void* w
   };
   if (kind == 1) {
     if (in_stats) return launch(march_s_kernel<48, 96, 64, false, true>, GS::LDS, "march_s(lazy)");
-    return bs_out ? launch(march_s_kernel<48, 96, 64, true, false>, GS::LDS, "march_s") : launch(march_s_kernel<48, 96, 64, false, false>, GS::LDS, "march_s");
+    return bs ? launch(march_s_kernel<48, 96, 64, true, false>, GS::LDS, "march_s") : launch(march_s_kernel<48, 96, 64, false, false>, GS::LDS, "march_s");
   }
   if (in_stats) return launch(march_u_kernel<96, 48, 64, false, true>, GU::LDS, "march_u(lazy)");
-  return bs_out ? launch(march_u_kernel<96, 48, 64, true, false>, GU::LDS, "march_u") : launch(march_u_kernel<96, 48, 64, false, false>, GU::LDS, "march_u");
+  return bs ? launch(march_u_kernel<96, 48, 64, true, false>, GU::LDS, "march_u") : launch(march_u_kernel<96, 48, 64, false, false>, GU::LDS, "march_u");
 }
 
 // ---- weight gradient of both layers (march_w_kernel) --------------------------------------------------------------------
-bool march_w_ok(const p2phd_conv_desc* c) { return march_kind(c, 0) != 0; }   // same layers, same geometry rule as the forward
-
 size_t march_w_workspace_floats(const p2phd_conv_desc* c) {
-  if (march_shape_kind(c, 0) == 0) return 0;
+  if (march_shape_kind(c, 0) == 0) return 0;                      // same layers, same geometry rule as the forward
   const MarchGeom g = march_geom(c, 1, 0);
   return (size_t)c->N * g.strips * g.nseg * 96 * 432;
 }
@@ -994,7 +990,7 @@ size_t march_w_workspace_floats(const p2phd_conv_desc* c) {
 // x / dy in the layer's own orientation; x_stats != nullptr: x is the RAW output of its producer's InstanceNorm block
 int march_w_run(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, int accumulate, const float* x_stats, float x_slope,
                 float x_eps, float* slabs, hipStream_t st) {
-  P2PHD_REQUIRE(march_w_ok(c), "march_w_run: layer has no marching weight-gradient kernel");
+  P2PHD_REQUIRE(march_shape_kind(c, 0) != 0, "march_w_run: layer has no marching weight-gradient kernel");
   const bool conv = !c->transposed;
   const MarchGeom g = march_geom(c, 1, 0);                        // Ho x Wo = the 96-channel plane, Hin x Win = the 48-channel plane
   MarchWArgs a{};
@@ -1006,7 +1002,6 @@ int march_w_run(const p2phd_conv_desc* c, const void* x, const void* dy, float* 
   a.stats = x_stats; a.slope = x_slope; a.eps = x_eps;
   a.inv_hw = conv ? 1.f / ((float)(2 * a.Hs) * (float)(2 * a.Ws)) : 1.f / ((float)a.Hs * (float)a.Ws);   // plane of x
   const int wgs = a.N * a.strips * a.nseg;
-  ++g_launch_count[LC_MARCH_W];
   auto launch = [&](auto kern) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, WGeom::LDS);
     hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(kThreads), WGeom::LDS, st, a);

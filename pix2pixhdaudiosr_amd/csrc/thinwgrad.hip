@@ -332,9 +332,9 @@ int launch_thin(const ThinDesc& d, const void* wide, const void* thin, float* sl
 
 namespace p2phd {
 
-// which layers take this kernel: bf16, square 7x7 s1 p3 reflect with 2 channels on one side, or 4x4 s2 p2 zero with 4 in
-int thin_wgrad_kind(const p2phd_conv_desc* c) {
-  if (g_opt_c7_generic || c->dtype != P2PHD_BF16 || c->transposed) return 0;
+// which layers this kernel serves: bf16, square 7x7 s1 p3 reflect with 2 channels on one side, or 4x4 s2 p2 zero with 4 in
+int thin_wgrad_shape_kind(const p2phd_conv_desc* c) {
+  if (c->dtype != P2PHD_BF16 || c->transposed) return 0;
   if (c->R == 7 && c->S == 7 && c->stride == 1 && c->pad == 3 && c->pad_mode == 1) {
     if (c->C == 2 && c->K >= 8 && c->K <= 128) return 1;          // 2 -> K
     if (c->K == 2 && c->C >= 8 && c->C <= 128) return 2;          // C -> 2
@@ -344,7 +344,7 @@ int thin_wgrad_kind(const p2phd_conv_desc* c) {
 }
 
 size_t thin_wgrad_workspace_floats(const p2phd_conv_desc* c) {
-  const int kind = thin_wgrad_kind(c);
+  const int kind = thin_wgrad_shape_kind(c);
   if (!kind) return 0;
   const int M = kind == 2 ? c->C : c->K;
   const int mb = (M + 31) / 32, nblk = kind == 3 ? 2 : 4;
@@ -352,7 +352,7 @@ size_t thin_wgrad_workspace_floats(const p2phd_conv_desc* c) {
 }
 
 int thin_wgrad(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, int accumulate, float* slabs, hipStream_t st) {
-  const int kind = thin_wgrad_kind(c);
+  const int kind = thin_wgrad_shape_kind(c);
   int Ho = (c->H + 2 * c->pad - c->R) / c->stride + 1, Wo = (c->W + 2 * c->pad - c->S) / c->stride + 1;
   ThinDesc d{};
   d.N = c->N;

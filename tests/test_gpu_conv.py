@@ -934,13 +934,14 @@ def test_dfirst_kernel_equals_the_generic_path(dtype):
     """Round 5: csrc/dfirst.hip (option dfirst = 1: the discriminator's 4 -> 64 first layer with the input pixels loaded straight
     into MFMA fragments) against the generic gather-GEMM path it replaces (option 0), at the layer's real plane of the second
     scale (256 x 128 -> 129 x 65) and on an odd plane: same products, fp32 accumulation in another order -> equal to the 16-bit
-    rounding of the output; and against the fp32 oracle."""
+    rounding of the output; and against the fp32 oracle.  The kernel has no tanh: a tanh layer of that shape takes the generic
+    path under both settings."""
     from pix2pixhdaudiosr_amd import _ops, _lib
     import ctypes as C
     L = _ops.lib_for(dtype)
-    for (N, H, W) in ((4, 256, 128), (3, 37, 51)):
+    for (N, H, W, act) in ((4, 256, 128, _ops.ACT_LRELU), (3, 37, 51, _ops.ACT_LRELU), (3, 37, 51, _ops.ACT_TANH)):
         gen = torch.Generator().manual_seed(H)
-        spec = _ops.ConvSpec(4, 64, 4, 2, 2, 0, False, 0, False, _ops.ACT_LRELU)
+        spec = _ops.ConvSpec(4, 64, 4, 2, 2, 0, False, 0, False, act)
         d = spec.desc(N, H, W, dtype)
         Ho, Wo = spec.out_size(d)
         xc = torch.randn(N, 4, H, W, generator=gen)
@@ -955,13 +956,14 @@ def test_dfirst_kernel_equals_the_generic_path(dtype):
             for opt in (0, 1):
                 _lib.check(L.p2phd_set_option(b"dfirst", opt))
                 y.fill_(7.0)
-                _ops.check(L.p2phd_conv_fwd(C.byref(d), _ops.ptr(x), _ops.ptr(wp), _ops.ptr(b), _ops.ACT_LRELU, _ops.ptr(y), None, _ops.ptr(ws), _ops.stream_ptr()))
+                _ops.check(L.p2phd_conv_fwd(C.byref(d), _ops.ptr(x), _ops.ptr(wp), _ops.ptr(b), act, _ops.ptr(y), None, _ops.ptr(ws), _ops.stream_ptr()))
                 torch.cuda.synchronize()
                 res[opt] = y.float().cpu().numpy().copy()
         finally:
             _lib.check(L.p2phd_set_option(b"dfirst", 1))
         q = lambda t: t.to(dtype).float()
-        ref = F.leaky_relu(F.conv2d(q(xc), q(w.cpu()), b.cpu(), stride=2, padding=2), 0.2).permute(0, 2, 3, 1).numpy()
+        z = F.conv2d(q(xc), q(w.cpu()), b.cpu(), stride=2, padding=2)
+        ref = (F.leaky_relu(z, 0.2) if act == _ops.ACT_LRELU else torch.tanh(z)).permute(0, 2, 3, 1).numpy()
         ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
         assert rel_err(res[1], res[0]) < ulp, rel_err(res[1], res[0])
         assert rel_err(res[1], ref) < 2 * ulp and rel_err(res[0], ref) < 2 * ulp, (rel_err(res[1], ref), rel_err(res[0], ref))

@@ -537,7 +537,8 @@ def test_configs1_step_at_the_benchmarked_batch():
         L.p2phd_launch_count(None, 1)
         ld = m.train_step(lr, hr, noise=noise)
         torch.cuda.synchronize()
-        counts = {k: int(L.p2phd_launch_count(k.encode(), 0)) for k in ("gconv", "halo", "cls_skip", "march", "march_w", "wgrad", "splitk", "tile256")}
+        counts = {k: int(L.p2phd_launch_count(k.encode(), 0)) for k in ("gconv", "halo", "cls_skip", "march", "march_w", "wgrad", "splitk", "tile256",
+                                                                          "dfirst", "dlast", "c7", "thin_wgrad")}
         lr_s, sr = m._visual[0].detach().float().cpu(), m._visual[1].detach().float().cpu()
         gG = {k: p.grad.detach().float().cpu().clone() for k, p in m.netG.named_parameters()}
         gD = {k: p.grad.detach().float().cpu().clone() for k, p in m.netD.named_parameters()}
@@ -570,7 +571,13 @@ def test_configs1_step_at_the_benchmarked_batch():
     assert c16["cls_skip"] >= 6, c16
     assert c16["march"] >= 4 and c16["march_w"] >= 2, c16
     assert c16["wgrad"] >= 18 and c16["tile256"] >= 1, c16
+    # the dedicated single-layer kernels: each of the 2 discriminator scales runs its 4 -> 64 first layer forward (dfirst) and
+    # its 512 -> 1 head forward + input gradient (dlast); the weight gradients of the generator's two 7 x 7 end layers and of
+    # both first discriminator layers take thinwgrad; the generator's 7 x 7 head forward + input gradient and its input layer's
+    # forward take c7
+    assert c16["dfirst"] >= 2 and c16["dlast"] >= 4 and c16["thin_wgrad"] >= 4 and c16["c7"] >= 3, c16
     assert c32["halo"] == 0 and c32["march"] == 0, c32             # fp32 is the generic loop: the two runs are different kernels
+    assert c32["dfirst"] == c32["dlast"] == c32["thin_wgrad"] == c32["c7"] == 0, c32   # (bf16-only kernels)
 
     # (ii) bf16 against fp32, the bounds of test_configs1_bf16_step_tracks_the_fp32_step_at_full_size
     assert rel_err(lr_s16.numpy(), lr_s32.numpy()) < 1e-5           # the codec is fp32 in both modes
