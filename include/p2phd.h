@@ -82,7 +82,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * gather-GEMM launch), "halo" (those on the patch-staged 3x3 main loop), "cls_skip" (tap-skipping merged stride-2 launches),
  * "splitk" (launches with a split-K tail), "tile256" (256 x 256 tiles), "tile128x192" (128 x 192 tiles of small planes),
  * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient), and the dedicated single-layer kernels "dfirst",
- * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them).  family == NULL with reset != 0 clears all.
+ * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them), "timed_pack" / "timed_frames" (the time-domain
+ * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -148,6 +149,38 @@ int p2phd_mdct2_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, in
 int p2phd_imdct2_fwd(const float* spec, int64_t B, int64_t n_frames, int n_fft, int hop, int win, const float* window,
                      const float* tables, int64_t crop_start, int64_t out_len, float scale, float k0_scale,
                      float* out, void* stream);
+/* MDCT2.forward(signal, return_ola=True) (models/mdct.py:377-403): p2phd_mdct2_fwd plus a second output
+ * frames[b,t,i] = w[i] * xpad[b, t*hop + i], i < win ([B, n_frames, win] f32): the windowed frame the kernel already holds
+ * in LDS, written by the same launch.  `out` is bit-identical to p2phd_mdct2_fwd's. */
+int p2phd_mdct2_fwd_frames(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win, const float* window,
+                           const float* tables, int64_t start_pad, int64_t n_frames, float scale, float k0_scale,
+                           float* out, float* frames, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Time-domain discriminator (--use_time_D; pix2pixHD_model.py:251-258, 314-320, 375-387), csrc/timed.hip.
+ *
+ * p2phd_timed_pack_pair: the input of time_D's first conv.  lr_frames / other_frames: n_pixels f32 values each (a
+ *   [N, F, win] tensor); dst: NHWC [N, F, win, 8] in `dtype`, channel 0 = lr, channel 1 = other, channels 2..7 zero.
+ *   mode_db = 1: both through 20 log10(max(|x|, min_value)) - 20, i.e. aF.amplitude_to_DB(torch.abs(x), 20, min_value, 1)
+ *   followed by torch.cat(dim=1) (discriminate_time_D, :314-320); mode_db = 0: the raw values (the generator-loss pass,
+ *   torch.cat((lr_frames, sr_frames), dim=1) of :386).  dst 16-byte aligned.
+ * p2phd_timed_frames_fwd: sr [B, 2, n_fft, n_frames] f32 (the generator's output), minmax = (min, max) of the low-rate
+ *   clip's normalisation -> out[b,t,i] = scale * window[i] * IDCT_2N_native(S)[b,t,i], S[b,t,k] = (A0 - A1) / (2 alpha - 1),
+ *   A_c = 10 * 10^((|sr[b,c,k,t]| (max - min) + min) / 20) - min_value: denormalize + to_frames (:229-232, :251-258) and
+ *   the np.sqrt(up_ratio - 1) * window * . of :376 (scale = sqrt(up_ratio - 1), window of n_fft values).  tables:
+ *   p2phd_dct_tables_fill(n_fft).  out [B, n_frames, n_fft] f32, 16-byte aligned.
+ * p2phd_timed_frames_bwd: the adjoint.  g_frames [B, n_frames, n_fft] f32 (8-byte aligned), sr / minmax as in the
+ *   forward -> g_sr [B, 2, n_fft, n_frames] = d<g_frames, out>/d sr (d|x|/dx = sign(x), 0 at 0; no gradient to minmax,
+ *   which the reference computes under no_grad).
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_timed_pack_pair(int dtype, const float* lr_frames, const float* other_frames, int64_t n_pixels, int mode_db,
+                          float min_value, void* dst, void* stream);
+int p2phd_timed_frames_fwd(const float* sr, const float* minmax, int64_t B, int64_t n_frames, int n_fft,
+                           const float* window, const float* tables, float alpha, float min_value, float scale,
+                           float* out, void* stream);
+int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* minmax, int64_t B, int64_t n_frames,
+                           int n_fft, const float* window, const float* tables, float alpha, float scale, float* g_sr,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -386,6 +386,71 @@ def to_physical_pair(dtype, a, b_real, b_fake):
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# time-domain discriminator input (csrc/timed.hip)
+# ------------------------------------------------------------------------------------------
+
+def pack_frame_pair(dtype, lr_frames, other_frames, db, min_value):
+    """(lr_frames, other_frames) [N,1,F,win] or [N,F,win] f32 -> physical [N,F,win,8]: channel 0 = lr, 1 = other, in dB
+    (amplitude_to_DB(|x|, 20, min_value, 1)) or raw."""
+    a, b = lr_frames.contiguous().float(), other_frames.contiguous().float()
+    if a.dim() == 4:
+        a, b = a[:, 0], b[:, 0]
+    if a.shape != b.shape or a.dim() != 3:
+        raise _lib.P2PHDError(f"pack_frame_pair: frame tensors must both be [N, F, win], got {tuple(a.shape)} and {tuple(b.shape)}")
+    _lib.require_gpu_tensor(a, "time_D frames")
+    _lib.require_gpu_tensor(b, "time_D frames")
+    N, F, W = a.shape
+    out = empty((N, F, W, 8), dtype, a.device)
+    check(lib_for(dtype).p2phd_timed_pack_pair(dt_code(dtype), ptr(a), ptr(b), N * F * W, int(bool(db)), float(min_value), ptr(out),
+                                               stream_ptr()), "timed_pack_pair")
+    return out
+
+
+class PackFramePair(torch.autograd.Function):
+    """pack_frame_pair in raw mode with a gradient for `other_frames` (channel 1); lr_frames are data."""
+
+    @staticmethod
+    def forward(ctx, dtype, lr_frames, other_frames):
+        ctx.shape = tuple(other_frames.shape)
+        return pack_frame_pair(dtype, lr_frames, other_frames, False, 0.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[2]:
+            return None, None, None
+        return None, None, from_physical(g.contiguous(), 1, 1).reshape(ctx.shape)
+
+
+class SpectroToFrames(torch.autograd.Function):
+    """sr_result [B,2,N,F] -> scale * window * IDCT_2N_native(decode(sr_result)) [B,F,N] (pix2pixHD_model.py:251-258, :376)
+    in one launch, adjoint in one launch."""
+
+    @staticmethod
+    def forward(ctx, sr, minmax, window, tables, alpha, min_value, scale):
+        sr = sr.contiguous().float()
+        B, C2, N, F = sr.shape
+        if C2 != 2 or window.numel() != N:
+            raise _lib.P2PHDError(f"SpectroToFrames: needs a two-channel spectrogram and a window of n_fft values, got {tuple(sr.shape)}")
+        out = empty((B, F, N), torch.float32, sr.device)
+        check(lib().p2phd_timed_frames_fwd(ptr(sr), ptr(minmax), B, F, N, ptr(window), ptr(tables), float(alpha), float(min_value),
+                                           float(scale), ptr(out), stream_ptr()), "timed_frames_fwd")
+        ctx.save_for_backward(sr, minmax, window, tables)
+        ctx.cfg = (float(alpha), float(scale))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        sr, minmax, window, tables = ctx.saved_tensors
+        alpha, scale = ctx.cfg
+        B, _, N, F = sr.shape
+        g = g.contiguous().float()
+        g_sr = empty(tuple(sr.shape), torch.float32, sr.device)
+        check(lib().p2phd_timed_frames_bwd(ptr(g), ptr(sr), ptr(minmax), B, F, N, ptr(window), ptr(tables), alpha, scale, ptr(g_sr),
+                                           stream_ptr()), "timed_frames_bwd")
+        return g_sr, None, None, None, None, None, None
+
+
 class FromPhysical(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_phys, channels):
@@ -975,8 +1040,8 @@ class LossAcc:
         self.slot = zeros((), device)
         self.terms = []
 
-    def mse_const(self, a_phys, channels, target, rows=None):
-        self.terms.append(LossFn.apply(a_phys, None, 0, target, 1.0, channels, False, rows, self.slot))
+    def mse_const(self, a_phys, channels, target, rows=None, coeff=1.0):
+        self.terms.append(LossFn.apply(a_phys, None, 0, target, coeff, channels, False, rows, self.slot))
 
     def l1(self, a_phys, b_phys, channels, coeff=1.0, park=False):
         self.terms.append(LossFn.apply(a_phys, b_phys.detach(), 1, 0.0, coeff, channels, park, None, self.slot))

@@ -25,7 +25,7 @@ constexpr int kWaves = 4;
 __global__ __launch_bounds__(kThreads) void mdct2_fwd_kernel(
     const float* __restrict__ x, long T, int N, int hop, int win, const float* __restrict__ window,
     const float* __restrict__ tables, long start_pad, long F, float scale, float k0_scale, float* __restrict__ out,
-    int f_tile, int n_tiles, int seg_cap, int win_cap, int fft_waves) {
+    float* __restrict__ frames, int frames_vec4, int f_tile, int n_tiles, int seg_cap, int win_cap, int fft_waves) {
   extern __shared__ float4 smem_raw[];
   float* smem = reinterpret_cast<float*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,6 +62,18 @@ __global__ __launch_bounds__(kThreads) void mdct2_fwd_kernel(
       for (int n = lane; n < (N >> 1); n += 64) {               // Makhoul: v[n] = u[2n], v[N-1-n] = u[2n+1]
         buf0[n] = make_float2(U(2 * n), 0.f);
         buf0[N - 1 - n] = make_float2(U(2 * n + 1), 0.f);
+      }
+      if (frames != nullptr) {                                  // MDCT2.forward(return_ola=True): the windowed frame itself
+        float* fo = frames + (b * F + t0 + f) * (long)win;
+        if (frames_vec4) {
+          for (int i = lane; i < (win >> 2); i += 64) {
+            const int n = 4 * i;
+            reinterpret_cast<float4*>(fo)[i] = make_float4(u[n] * s_win[n], u[n + 1] * s_win[n + 1], u[n + 2] * s_win[n + 2],
+                                                           u[n + 3] * s_win[n + 3]);
+          }
+        } else {
+          for (int n = lane; n < win; n += 64) fo[n] = u[n] * s_win[n];
+        }
       }
     }
     __syncthreads();
@@ -192,9 +204,10 @@ extern "C" int p2phd_dct_tables_fill(int n_fft, float* host_out) {
   return P2PHD_OK;
 }
 
-extern "C" int p2phd_mdct2_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win, const float* window,
-                               const float* tables, int64_t start_pad, int64_t n_frames, float scale, float k0_scale,
-                               float* out, void* stream) {
+namespace {
+int mdct2_fwd_launch(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win, const float* window,
+                     const float* tables, int64_t start_pad, int64_t n_frames, float scale, float k0_scale,
+                     float* out, float* frames, void* stream) {
   if (int rc = check_common(n_fft, hop, win)) return rc;
   P2PHD_REQUIRE(B >= 0 && T >= 0 && n_frames >= 0 && start_pad >= 0, "mdct2_fwd: negative size");
   if (B == 0 || n_frames == 0) return P2PHD_OK;
@@ -209,9 +222,26 @@ extern "C" int p2phd_mdct2_fwd(const float* x, int64_t B, int64_t T, int n_fft, 
   P2PHD_REQUIRE(lds <= 160 * 1024, "mdct2_fwd: hop %d / window %d need %zu B of LDS", hop, win, lds);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mdct2_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // 16-byte frame stores when every frame row starts on a 16-byte boundary
+  const int frames_vec4 = frames != nullptr && win % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0;
   hipLaunchKernelGGL(mdct2_fwd_kernel, dim3((unsigned)(B * n_tiles)), dim3(kThreads), lds, (hipStream_t)stream, x, (long)T, n_fft, hop,
-                     win, window, tables, (long)start_pad, (long)n_frames, scale, k0_scale, out, f_tile, (int)n_tiles, seg_cap, win_cap, fw);
+                     win, window, tables, (long)start_pad, (long)n_frames, scale, k0_scale, out, frames, frames_vec4, f_tile, (int)n_tiles,
+                     seg_cap, win_cap, fw);
   return p2phd::check_launch("mdct2_fwd");
+}
+}  // namespace
+
+extern "C" int p2phd_mdct2_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win, const float* window,
+                               const float* tables, int64_t start_pad, int64_t n_frames, float scale, float k0_scale,
+                               float* out, void* stream) {
+  return mdct2_fwd_launch(x, B, T, n_fft, hop, win, window, tables, start_pad, n_frames, scale, k0_scale, out, nullptr, stream);
+}
+
+extern "C" int p2phd_mdct2_fwd_frames(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win, const float* window,
+                                      const float* tables, int64_t start_pad, int64_t n_frames, float scale, float k0_scale,
+                                      float* out, float* frames, void* stream) {
+  P2PHD_REQUIRE(frames != nullptr || B == 0 || n_frames == 0, "mdct2_fwd_frames: null frame output");
+  return mdct2_fwd_launch(x, B, T, n_fft, hop, win, window, tables, start_pad, n_frames, scale, k0_scale, out, frames, stream);
 }
 
 extern "C" int p2phd_imdct2_fwd(const float* spec, int64_t B, int64_t n_frames, int n_fft, int hop, int win, const float* window,

@@ -200,6 +200,17 @@ def _run_mdct2(x2d, n_fft, hop, win, window, tables, start_pad, n_frames, scale,
     return out
 
 
+def _run_mdct2_frames(x2d, n_fft, hop, win, window, tables, start_pad, n_frames):
+    """MDCT2 spectrogram and the windowed frames [B, F, win] it is the DCT of, from one launch."""
+    B, T = x2d.shape
+    out = torch.empty((B, n_frames, n_fft), dtype=torch.float32, device=x2d.device)
+    frames = torch.empty((B, n_frames, win), dtype=torch.float32, device=x2d.device)
+    _lib.check(_lib.lib().p2phd_mdct2_fwd_frames(_lib.ptr(x2d), B, T, n_fft, hop, win, _lib.ptr(window), _lib.ptr(tables),
+                                                 start_pad, n_frames, 1.0, 1.0, _lib.ptr(out), _lib.ptr(frames),
+                                                 _lib.stream_ptr()), "mdct2_fwd_frames")
+    return out, frames
+
+
 def _run_imdct2(spec, n_fft, hop, win, window, tables, crop, out_len, scale, k0):
     B, F, _ = spec.shape
     out = torch.empty((B, out_len), dtype=torch.float32, device=spec.device)
@@ -268,14 +279,23 @@ class MDCT2(_Base2):
         self._setup2(n_fft, hop_length, win_length, window, center, pad_mode, device, out_dtype)
 
     def forward(self, signal, return_ola=False, _dim0=None):
-        if return_ola:
-            raise NotImplementedError("return_ola (time-domain discriminator frames) is outside the hot path")
+        """``return_ola=True`` returns ``(spec, frames)`` like the reference (mdct.py:396-403): frames [.., F, win] are the
+        windowed slices the DCT is taken of, written by the same launch.  Both results of that call are
+        non-differentiable: the model only asks for frames under ``no_grad`` (pix2pixHD_model.py:302-320); call without
+        ``return_ola`` for a spectrogram with a gradient."""
         signal = signal.to(self.device)
         start_pad, _, n_frames = frame_layout(len(signal) if _dim0 is None else int(_dim0), signal.shape[-1], self.hop_length,
                                               self.win_length, self.center)
         lead = signal.shape[:-1]
         x2d = signal.reshape(-1, signal.shape[-1]).to(torch.float32).contiguous()
         _lib.require_gpu_tensor(x2d, "MDCT2 input")
+        if return_ola:
+            with torch.no_grad():
+                S, frames = _run_mdct2_frames(x2d, self.n_fft, self.hop_length, self.win_length, self.window, self._tables(),
+                                              start_pad, n_frames)
+            S = S.reshape(*lead, n_frames, self.n_fft)
+            frames = frames.reshape(*lead, n_frames, self.win_length)
+            return (S if self.out_dtype is None else S.to(self.out_dtype)), frames
         S = _MDCT2Fn.apply(x2d, self.n_fft, self.hop_length, self.win_length, self.window, self._tables(),
                            start_pad, n_frames, 1.0, 1.0)
         S = S.reshape(*lead, n_frames, self.n_fft)

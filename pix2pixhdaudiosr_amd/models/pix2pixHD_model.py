@@ -12,7 +12,7 @@ Deliberate differences:
     'mdct2'`` selects the reference's own MDCT2/IMDCT2 (n_fft bins) and enables to_frames / --use_match_loss;
   * MDCT output is fp32 (the reference's complex128 twiddles make it fp64, which its own fp32 convs reject);
   * every to_spectro configuration (explicit two-channel or single-channel encoding, all mask / phase modes);
-    LSGAN, no VGG / hifigan / time-domain discriminator / feature encoder;
+    LSGAN, the time-domain discriminator (--use_time_D, MDCT2 with explicit encoding); no VGG / hifigan D / feature encoder;
   * the D weight gradients of the G-loss pass are not computed (train.py:176 zeroes them unread);
   * the per-step device->host copies of pix2pixHD_model.py:418-428 are deferred to get_current_visuals();
   * ``--fp16`` selects bf16 MFMA compute with fp32 master weights instead of fp16 autocast + GradScaler;
@@ -65,9 +65,17 @@ class Pix2PixHDModel(BaseModel):
             unsupported.append("phase_encoding_mode must be None, 'uni_dist', 'norm_dist', 'norm_dist2' or 'scale'")
         if not _opt(opt, 'explicit_encoding', False) and _opt(opt, 'use_match_loss', False):
             unsupported.append("--use_match_loss needs explicit_encoding (to_frames returns None without it, pix2pixHD_model.py:255-256)")
-        for flag in ('use_hifigan_D', 'use_time_D', 'instance_feat', 'label_feat'):
+        for flag in ('use_hifigan_D', 'instance_feat', 'label_feat'):
             if _opt(opt, flag, False):
                 unsupported.append("--%s is outside the HIP hot path" % flag)
+        if _opt(opt, 'use_time_D', False):
+            # the time-domain discriminator judges windowed MDCT2 frames against s * window * IDCT(decode(sr)) (pix2pixHD_model.py:375-387)
+            if not _opt(opt, 'explicit_encoding', False):
+                unsupported.append("--use_time_D needs explicit_encoding (to_frames returns None without it, pix2pixHD_model.py:255-256)")
+            if _opt(opt, 'mdct_type', _default_mdct_type()) != 'mdct2':
+                unsupported.append("--use_time_D compares MDCT2 frames (MDCT2.forward(return_ola=True)): it needs mdct_type='mdct2'")
+            if _opt(opt, 'n_fft', None) != _opt(opt, 'win_length', None):
+                unsupported.append("--use_time_D needs n_fft == win_length (window * IDCT frames does not broadcast otherwise, pix2pixHD_model.py:376)")
         if not _opt(opt, 'no_vgg_loss', True):
             unsupported.append("VGG loss (deprecated in the reference) needs --no_vgg_loss")
         if not _opt(opt, 'no_instance', True):
@@ -126,6 +134,14 @@ class Pix2PixHDModel(BaseModel):
             self.netD = networks.define_D(input_nc + opt.output_nc, opt.ndf, opt.n_layers_D, opt.norm, False, opt.num_D,
                                           not opt.no_ganFeat_loss, gpu_ids=self.gpu_ids, dtype=self.compute_dtype,
                                           verbose=verbose)
+            # --use_time_D (pix2pixHD_model.py:64-65): the same multiscale discriminator on the plane frames x win_length of
+            # (low-rate frames, other frames), last-stage output only
+            self.use_time_D = bool(_opt(opt, 'use_time_D', False))
+            if self.use_time_D:
+                self.time_D = networks.define_D(2, opt.ndf, opt.n_layers_D, opt.norm, False, opt.num_D, False,
+                                                gpu_ids=self.gpu_ids, dtype=self.compute_dtype, verbose=verbose)
+        else:
+            self.use_time_D = False
         # opt.fp8: e4m3 forward of the wide layers on top of bf16 compute (BASELINE configs[4])
         self.fp8_layers = 0
         if _opt(opt, 'fp8', False):
@@ -142,10 +158,13 @@ class Pix2PixHDModel(BaseModel):
             self.load_network(self.netG, 'G', opt.which_epoch, pretrained_path)
             if self.isTrain:
                 self.load_network(self.netD, 'D', opt.which_epoch, pretrained_path)
+                if self.use_time_D:
+                    self.load_network(self.time_D, 'time_D', opt.which_epoch, pretrained_path)     # pix2pixHD_model.py:84-85
 
         if self.isTrain:
             self.old_lr = opt.lr
-            self.loss_filter = self.init_loss_filter(not opt.no_ganFeat_loss, False, bool(_opt(opt, 'use_match_loss', False)), False)
+            self.loss_filter = self.init_loss_filter(not opt.no_ganFeat_loss, False, bool(_opt(opt, 'use_match_loss', False)),
+                                                     self.use_time_D)
             self.criterionGAN = networks.GANLoss(use_lsgan=True, tensor=self.Tensor)
             self.criterionFeat = networks.FeatLoss()
             self.loss_names = self.loss_filter('G_GAN', 'G_GAN_Feat', 'G_VGG', 'G_mat', 'G_GAN_t', 'D_real_t', 'D_fake_t', 'D_real', 'D_fake')
@@ -160,6 +179,8 @@ class Pix2PixHDModel(BaseModel):
                 print('Total number of parameters of G: %d' % (sum([param.numel() for param in params])))
             self.optimizer_G = FlatAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
             params = list(self.netD.parameters())
+            if self.use_time_D:
+                params += list(self.time_D.parameters())          # pix2pixHD_model.py:137-138: one optimiser for both
             if verbose:
                 print('Total number of parameters of D: %d' % (sum([param.numel() for param in params])))
             self.optimizer_D = FlatAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
@@ -171,12 +192,18 @@ class Pix2PixHDModel(BaseModel):
     # ------------------------------------------------------------------------------------------
     # spectrogram codec (HIP: csrc/spectro.hip)
     # ------------------------------------------------------------------------------------------
-    def to_spectro(self, audio, mask=False, noise=None, phase_noise=None, noise_sign=None, _spec=None):
+    def to_spectro(self, audio, mask=False, noise=None, phase_noise=None, noise_sign=None, _spec=None, _frames=None):
         """audio [B,T] -> (log_spectro [B,C,bins,frames] in [0,1], pha [B,1,bins,frames], norm dict); C = 2 with
         explicit_encoding, else 1 (pix2pixHD_model.py:142-227).  The random tensors the reference draws inside can be
         handed in (parity tests): ``noise`` [B,C,mask_rows,frames] (torch.randn of :202), ``noise_sign`` (+-1, the randint of
-        :215 for mask_mode 'mode1'), ``phase_noise`` [B,1,bins,frames] (the rand / randn of :180-188)."""
-        spec = _spec if _spec is not None else self._mdct(audio.to(self.device))   # [B, frames, bins] f32
+        :215 for mask_mode 'mode1'), ``phase_noise`` [B,1,bins,frames] (the rand / randn of :180-188).  With --use_time_D
+        the norm dict's 'frames' holds the windowed MDCT2 frames [B, frames, win] (:143-145, :227)."""
+        if _spec is not None:
+            spec, frames = _spec, _frames
+        elif getattr(self, 'use_time_D', False):
+            spec, frames = self._mdct(audio.to(self.device), True)
+        else:
+            spec, frames = self._mdct(audio.to(self.device)), None                 # [B, frames, bins] f32
         B, Fr, M = spec.shape
         L = _lib.lib()
         explicit = bool(_opt(self.opt, 'explicit_encoding', False))
@@ -222,7 +249,7 @@ class Pix2PixHDModel(BaseModel):
                 elif pem == 'norm_dist2':
                     pn = pn.abs()
                 pha = pha * pn
-        norm = {'min': norm8[0], 'max': norm8[1], 'mean': norm8[2], 'std': norm8[3], 'frames': None, '_minmax': norm8[:2]}
+        norm = {'min': norm8[0], 'max': norm8[1], 'mean': norm8[2], 'std': norm8[3], 'frames': frames, '_minmax': norm8[:2]}
         return log_spectro, pha, norm
 
     def _minmax(self, norm_param):
@@ -275,18 +302,23 @@ class Pix2PixHDModel(BaseModel):
 
     def encode_input(self, lr_audio, inst_map=None, hr_audio=None, feat_map=None, noise=None):
         with torch.no_grad():
-            hr_spec = lr_spec = None
+            hr_spec = lr_spec = hr_fr = lr_fr = None
             if hr_audio is not None and tuple(hr_audio.shape) == tuple(lr_audio.shape) and hr_audio.dim() == 2:
                 # both clips through ONE transform launch (2B rows: the launch ramp of a 12 us kernel is paid once); the
                 # codec then normalises each half on its own, as the reference does (pix2pixHD_model.py:302-320)
-                both = self._mdct(torch.cat((hr_audio.to(self.device), lr_audio.to(self.device)), dim=0), _dim0=hr_audio.shape[0])
+                both = torch.cat((hr_audio.to(self.device), lr_audio.to(self.device)), dim=0)
+                if getattr(self, 'use_time_D', False):
+                    both, fr = self._mdct(both, True, _dim0=hr_audio.shape[0])
+                    hr_fr, lr_fr = fr[:hr_audio.shape[0]], fr[hr_audio.shape[0]:]
+                else:
+                    both = self._mdct(both, _dim0=hr_audio.shape[0])
                 hr_spec, lr_spec = both[:hr_audio.shape[0]], both[hr_audio.shape[0]:]
             if hr_audio is not None:
-                hr_spectro, hr_pha, hr_norm_param = self.to_spectro(hr_audio, mask=False, _spec=hr_spec)
+                hr_spectro, hr_pha, hr_norm_param = self.to_spectro(hr_audio, mask=False, _spec=hr_spec, _frames=hr_fr)
             else:
                 hr_spectro = hr_pha = hr_norm_param = None
             lr_spectro, lr_pha, lr_norm_param = self.to_spectro(lr_audio, mask=bool(_opt(self.opt, 'mask', False)), noise=noise,
-                                                                _spec=lr_spec)
+                                                                _spec=lr_spec, _frames=lr_fr)
         return lr_spectro, lr_pha, hr_spectro, hr_pha, feat_map, inst_map, hr_norm_param, lr_norm_param
 
     # ------------------------------------------------------------------------------------------
@@ -309,6 +341,38 @@ class Pix2PixHDModel(BaseModel):
     def discriminate_F(self, input_label, test_image, use_pool=False):
         return self.netD.forward(torch.cat((input_label, test_image.detach()), dim=1))
 
+    def discriminate_time_D(self, label_spectro, test_spectro):
+        """Time-domain discriminator on dB frames (pix2pixHD_model.py:314-320); ``test_spectro`` is detached.  Arguments are
+        frame tensors [B,1,F,win] despite the reference's names."""
+        x = _ops.pack_frame_pair(self.compute_dtype, label_spectro.to(self.device), test_spectro.detach().to(self.device), True,
+                                 self.opt.min_value)
+        return [[networks._view(t, c) for (t, c) in scale] for scale in self.time_D.forward_physical(x)]
+
+    def sr_frames(self, sr_result, norm_param):
+        """sqrt(up_ratio - 1) * window * to_frames(sr_result, norm_param) (pix2pixHD_model.py:376) as [B,F,win]: one launch
+        forward, one backward (csrc/timed.hip) instead of the element-wise chain of `to_frames` around the IDCT."""
+        return _ops.SpectroToFrames.apply(sr_result, self._minmax(norm_param), self.window, self._mdct._tables(),
+                                          self.opt.alpha, self.opt.min_value, float(np.sqrt(self.up_ratio - 1)))
+
+    def _time_losses(self, sr_result, lr_norm_param, hr_norm_param):
+        """(G_GAN_t, D_real_t, D_fake_t) of pix2pixHD_model.py:375-387, in the reference's order.  The two discriminator
+        passes see dB frames, the generator pass the raw ones (:386); the three inputs differ, so they stay three passes."""
+        cd, lt, mv = self.compute_dtype, float(self.opt.lambda_time), self.opt.min_value
+        sr_frames = self.sr_frames(sr_result, lr_norm_param)
+        lr_frames, hr_frames = lr_norm_param['frames'], hr_norm_param['frames']
+
+        def gan(x, target):
+            acc = _ops.LossAcc(self.device)
+            for scale in self.time_D.forward_physical(x, exclusive=True):
+                t, c = scale[-1]
+                acc.mse_const(t, c, target, coeff=lt)
+            return acc.total()
+        loss_D_fake_t = gan(_ops.pack_frame_pair(cd, lr_frames, sr_frames.detach(), True, mv), 0.0)
+        loss_D_real_t = gan(_ops.pack_frame_pair(cd, lr_frames, hr_frames, True, mv), 1.0)
+        with _ops.no_weight_grad():                                # time_D's weight gradients of this pass: train.py:176
+            loss_G_GAN_t = gan(_ops.PackFramePair.apply(cd, lr_frames, sr_frames), 1.0)
+        return loss_G_GAN_t, loss_D_real_t, loss_D_fake_t
+
     def _d_pair(self):
         """Run D(real) and D(fake) of the training step as one batch (default; opt.d_pair = False or P2PHD_DPAIR=0 keeps
         the two passes of rounds 1-2 for A/B runs).  Needs intermediate features only through the parked losses."""
@@ -321,25 +385,8 @@ class Pix2PixHDModel(BaseModel):
         n = getattr(self, '_pair_batch', None)
         return _ops.backward_on_samples(n, n // 2, n) if n else contextlib.nullcontext()
 
-    def _losses(self, lr_audio, hr_audio, noise, share_fake_pass):
-        """All loss terms of one step.  share_fake_pass=False is the reference's schedule (pix2pixHD_model.py:331-415):
-        D(fake.detach()), D(real), D(fake).  share_fake_pass=True runs D on the generated spectrogram ONCE: the detached
-        and the attached pass compute identical values, only their backward differs, so `train_step` walks the one
-        retained graph twice (G loss without D weight gradients, then D loss restricted to D's parameters)."""
-        _ops.begin_step(self.device)                               # one memset for every statistics / loss accumulator
-        lr_spectro, lr_pha, hr_spectro, hr_pha, _, _, hr_norm_param, lr_norm_param = \
-            self.encode_input(lr_audio, None, hr_audio, None, noise=noise)
-
-        # cut points of the staged generator backward (data parallel: one gradient bucket per stage, see _g_stages)
-        _, cut_after, _ = self._bucket_plan()
-        self._cuts = [] if cut_after else None
-        if cut_after:
-            sr_phys = self.netG.forward_physical(self.netG.input_physical(lr_spectro), cuts=self._cuts,
-                                                 cut_after=set(cut_after))
-        else:
-            sr_phys = self.netG.forward_physical(self.netG.input_physical(lr_spectro))
-        sr_result = _ops.FromPhysical.apply(sr_phys, self.opt.output_nc)
-
+    def _spectral_losses(self, lr_spectro, hr_spectro, sr_result, share_fake_pass):
+        """(G_GAN, G_GAN_Feat, D_real, D_fake): the passes of the spectral discriminator and their losses (see _losses)."""
         pair = share_fake_pass and self._d_pair()
         if pair:
             # D(real) and D(fake) as ONE batch of 2B (real half first): same weights, one launch per layer instead of two,
@@ -390,6 +437,29 @@ class Pix2PixHDModel(BaseModel):
                     (a, c), (b, _) = pred_fake[i][j], pred_real[i][j]
                     a_feat.l1(a, b, c, w_feat, park=True)
             loss_G_GAN_Feat = a_feat.total()
+        return loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake
+
+    def _losses(self, lr_audio, hr_audio, noise, share_fake_pass):
+        """All loss terms of one step.  share_fake_pass=False is the reference's schedule (pix2pixHD_model.py:331-415):
+        D(fake.detach()), D(real), D(fake).  share_fake_pass=True runs D on the generated spectrogram ONCE: the detached
+        and the attached pass compute identical values, only their backward differs, so `train_step` walks the one
+        retained graph twice (G loss without D weight gradients, then D loss restricted to D's parameters)."""
+        _ops.begin_step(self.device)                               # one memset for every statistics / loss accumulator
+        lr_spectro, lr_pha, hr_spectro, hr_pha, _, _, hr_norm_param, lr_norm_param = \
+            self.encode_input(lr_audio, None, hr_audio, None, noise=noise)
+
+        # cut points of the staged generator backward (data parallel: one gradient bucket per stage, see _g_stages)
+        _, cut_after, _ = self._bucket_plan()
+        self._cuts = [] if cut_after else None
+        if cut_after:
+            sr_phys = self.netG.forward_physical(self.netG.input_physical(lr_spectro), cuts=self._cuts,
+                                                 cut_after=set(cut_after))
+        else:
+            sr_phys = self.netG.forward_physical(self.netG.input_physical(lr_spectro))
+        sr_result = _ops.FromPhysical.apply(sr_phys, self.opt.output_nc)
+
+        loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake = self._spectral_losses(lr_spectro, hr_spectro, sr_result,
+                                                                                      share_fake_pass)
 
         # TDAC frame-matching loss (pix2pixHD_model.py:408-415): the second half of frame t and the first half of frame
         # t+1, each under its window half, must coincide
@@ -401,10 +471,15 @@ class Pix2PixHDModel(BaseModel):
             b = sr_frames[..., 1:, :half] * self.window[half:]
             loss_G_match = torch.nn.functional.mse_loss(a, b) * self.opt.lambda_mat
 
+        loss_G_GAN_t = loss_D_real_t = loss_D_fake_t = 0
+        if self.use_time_D:
+            loss_G_GAN_t, loss_D_real_t, loss_D_fake_t = self._time_losses(sr_result, lr_norm_param, hr_norm_param)
+
         # visuals are fetched lazily (no device->host copy in the step)
         self._visual = (lr_spectro, sr_result.detach(), hr_spectro, hr_pha)
         _ops.end_arena(self.device)
-        return self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, 0, loss_G_match, 0, 0, 0, loss_D_real, loss_D_fake), sr_result
+        return self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, 0, loss_G_match, loss_G_GAN_t, loss_D_real_t, loss_D_fake_t,
+                                loss_D_real, loss_D_fake), sr_result
 
     def forward(self, lr_audio, inst, hr_audio, feat, infer=False, noise=None):
         losses, sr_result = self._losses(lr_audio, hr_audio, noise, share_fake_pass=False)
@@ -459,6 +534,9 @@ class Pix2PixHDModel(BaseModel):
         ld = dict(zip(self.loss_names, losses))
         self._loss_D = (ld['D_fake'] + ld['D_real']) * 0.5
         self._loss_G = ld['G_GAN'] + ld.get('G_GAN_Feat', 0) + ld.get('G_mat', 0)
+        if self.use_time_D:                                        # train.py:159-160
+            self._loss_D = self._loss_D + (ld['D_fake_t'] + ld['D_real_t']) * 0.5
+            self._loss_G = self._loss_G + ld['G_GAN_t']
         if self.scaler is not None:                                # scaler.scale(loss).backward() of train.py:165-181
             self._loss_D, self._loss_G = self.scaler.scale(self._loss_D), self.scaler.scale(self._loss_G)
         self.optimizer_G.zero_grad(lazy=True)                       # (first weight gradient of the step overwrites: no memset)
@@ -520,6 +598,8 @@ class Pix2PixHDModel(BaseModel):
         """Backward of the discriminator loss through the graph phase A kept."""
         loss_D, self._loss_D = self._loss_D, None
         firsts = [self.netD._scale_steps(d)[0][0].spec for d in range(self.opt.num_D)]
+        if self.use_time_D:
+            firsts += [self.time_D._scale_steps(d)[0][0].spec for d in range(self.opt.num_D)]
         with _ops.backward_without_input_grads(firsts):   # no gradient towards the generator in this pass
             loss_D.backward(inputs=list(self.optimizer_D._params))
 
@@ -653,6 +733,8 @@ class Pix2PixHDModel(BaseModel):
     def save(self, which_epoch):
         self.save_network(self.netG, 'G', which_epoch, self.gpu_ids)
         self.save_network(self.netD, 'D', which_epoch, self.gpu_ids)
+        if self.use_time_D:
+            self.save_network(self.time_D, 'time_D', which_epoch, self.gpu_ids)       # pix2pixHD_model.py:518-519
         if getattr(self, 'scaler', None) is not None:
             # fp16 storage: scale + growth tracker of the device loss scaler, in a file of its own beside the reference's two
             # (the reference restarts GradScaler at 65536 on resume, train.py:67; a resume without the file does the same)
