@@ -83,7 +83,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * "splitk" (launches with a split-K tail), "tile256" (256 x 256 tiles), "tile128x192" (128 x 192 tiles of small planes),
  * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient), and the dedicated single-layer kernels "dfirst",
  * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them), "timed_pack" / "timed_frames" (the time-domain
- * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip).  family == NULL with reset != 0 clears all.
+ * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
+ * cross-fading stitch of whole-file generation, csrc/stitch.hip).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -181,6 +182,21 @@ int p2phd_timed_frames_fwd(const float* sr, const float* minmax, int64_t B, int6
 int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* minmax, int64_t B, int64_t n_frames,
                            int n_fft, const float* window, const float* tables, float alpha, float scale, float* g_sr,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Whole-file generation (pix2pixhdaudiosr_amd/generate.py), csrc/stitch.hip.  Launch family "stitch".
+ *
+ * p2phd_segments_gather: audio [L] f32 -> out [S, T] f32, out[s,i] = audio[s * stride + i], zero beyond L.  1 <= stride <= T;
+ *   stride = T is seg_pad_audio of the reference (data/audio_dataset.py:124-135).
+ * p2phd_segments_stitch: seg [S, T] f32 -> out [L_out] f32 with V = T - stride shared samples between neighbours:
+ *   out[n] = gain * sum_s w_s(n - s stride) seg[s, n - s stride] over the one or two segments that cover n.  w = 1 outside
+ *   the overlaps; inside one the later segment has sin^2(pi (i + 1/2) / (2 V)) at its sample i < V and the earlier one
+ *   1 - that value.  The first segment does not fade in, the last does not fade out.  V = 0: a scaled copy.  Evaluated in
+ *   double, rounded once.  Errors (P2PHD_EINVAL): V outside [0, T/2], S < 1, L_out > (S - 1) stride + T.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_segments_gather(const float* audio, int64_t L, int64_t T, int64_t stride, int64_t S, float* out, void* stream);
+int p2phd_segments_stitch(const float* seg, int64_t S, int64_t T, int64_t stride, float gain, float* out, int64_t L_out,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

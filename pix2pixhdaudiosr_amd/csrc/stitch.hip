@@ -1,0 +1,122 @@
+// Whole-file generation (pix2pixhdaudiosr_amd/generate.py): the two ends of the waveform -> segments -> generator -> segments ->
+// waveform path that are not a transform or a conv.
+//
+//   gather  audio[L] -> seg[S,T], seg[s,i] = audio[s * stride + i], zero beyond L.  stride = T is the reference's
+//           seg_pad_audio (data/audio_dataset.py:124-135); stride < T makes neighbouring segments share V = T - stride samples.
+//   stitch  seg[S,T] -> out[L_out]: each sample from the one or two segments that cover it.  Inside an overlap the later
+//           segment fades in with w = sin^2(pi (i + 1/2) / (2 V)) and the earlier one fades out with 1 - w; V = 0 is the
+//           reference's torch.cat(...).view(1, -1) times `gain`.
+//
+// Both are streaming kernels (one pass, no reuse, no atomics): one thread per four consecutive outputs, 16-byte accesses
+// where the addresses allow.  The cross-fade is evaluated in double and rounded once, so an output is the correctly rounded
+// value of the formula whatever the two operands' signs (a float evaluation loses bits where they cancel); the fp64 sine
+// runs on at most half of the samples of a kernel that is a few microseconds long.
+#include "common.h"
+#include "convplan.h"
+#include <algorithm>
+#include <cstdint>
+
+namespace {
+constexpr int kThreads = 256;
+
+__global__ __launch_bounds__(kThreads) void segments_gather_kernel(const float* __restrict__ audio, long L, long T, long stride,
+                                                                   long total, float* __restrict__ out, int vec4) {
+  const long quads = (total + 3) >> 2;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+    const long e0 = q << 2;
+    if (vec4) {                                                   // T, stride multiples of 4: a quad stays in one row, 16-byte aligned
+      const long s = e0 / T, src = s * stride + (e0 - s * T);
+      float4 v;
+      if (src + 4 <= L) {
+        v = *reinterpret_cast<const float4*>(audio + src);
+      } else {
+        v.x = src < L ? audio[src] : 0.f;
+        v.y = src + 1 < L ? audio[src + 1] : 0.f;
+        v.z = src + 2 < L ? audio[src + 2] : 0.f;
+        v.w = 0.f;
+      }
+      *reinterpret_cast<float4*>(out + e0) = v;
+    } else {
+      const long n = min(4l, total - e0);
+      for (long j = 0; j < n; ++j) {
+        const long e = e0 + j, s = e / T, src = s * stride + (e - s * T);
+        out[e] = src < L ? audio[src] : 0.f;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ float stitch_one(const float* __restrict__ seg, long n, long S, long T, long stride, long V, double gain,
+                                            double step) {
+  const long a = min(n / stride, S - 1);                          // the latest segment that covers n
+  const long i = n - a * stride;
+  const double cur = (double)seg[a * T + i];
+  if (a == 0 || i >= V) return (float)(gain * cur);
+  const double sn = sin(((double)i + 0.5) * step);
+  const double w = sn * sn;
+  return (float)(gain * (w * cur + (1.0 - w) * (double)seg[(a - 1) * T + i + stride]));
+}
+
+__global__ __launch_bounds__(kThreads) void segments_stitch_kernel(const float* __restrict__ seg, long S, long T, long stride, long V,
+                                                                   float gain, float* __restrict__ out, long L_out, int vec4) {
+  const long quads = (L_out + 3) >> 2;
+  const double step = V > 0 ? 3.14159265358979323846 / (2.0 * (double)V) : 0.0;
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+    const long n0 = q << 2;
+    if (vec4 && n0 + 4 <= L_out) {
+      const long a = min(n0 / stride, S - 1), i0 = n0 - a * stride;
+      const long src = a * T + i0;
+      float4 v;
+      if ((a == 0 || i0 >= V) && a == min((n0 + 3) / stride, S - 1) && (src & 3) == 0) {     // plain run of one segment
+        v = *reinterpret_cast<const float4*>(seg + src);
+        v.x *= gain; v.y *= gain; v.z *= gain; v.w *= gain;
+      } else {
+        v.x = stitch_one(seg, n0, S, T, stride, V, gain, step);
+        v.y = stitch_one(seg, n0 + 1, S, T, stride, V, gain, step);
+        v.z = stitch_one(seg, n0 + 2, S, T, stride, V, gain, step);
+        v.w = stitch_one(seg, n0 + 3, S, T, stride, V, gain, step);
+      }
+      *reinterpret_cast<float4*>(out + n0) = v;
+    } else {
+      for (long n = n0; n < min(n0 + 4, L_out); ++n) out[n] = stitch_one(seg, n, S, T, stride, V, gain, step);
+    }
+  }
+}
+
+int stream_grid(int64_t elems) {
+  const int64_t quads = (elems + 3) / 4;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(p2phd::cdiv(quads, kThreads), 16384));
+}
+
+}  // namespace
+
+extern "C" int p2phd_segments_gather(const float* audio, int64_t L, int64_t T, int64_t stride, int64_t S, float* out, void* stream) {
+  P2PHD_REQUIRE(L >= 0 && T >= 1 && S >= 1, "segments_gather: need L >= 0, T >= 1, S >= 1 (L %lld, T %lld, S %lld)", (long long)L,
+                (long long)T, (long long)S);
+  P2PHD_REQUIRE(stride >= 1 && stride <= T, "segments_gather: stride must be in [1, T], got %lld (T %lld)", (long long)stride, (long long)T);
+  P2PHD_REQUIRE(S <= (int64_t(1) << 40) / T, "segments_gather: S * T too large");
+  P2PHD_REQUIRE(out && (audio || L == 0), "segments_gather: null pointer");
+  const int vec4 = (T & 3) == 0 && (stride & 3) == 0 && ((reinterpret_cast<uintptr_t>(audio) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  hipLaunchKernelGGL(segments_gather_kernel, dim3(stream_grid(S * T)), dim3(kThreads), 0, (hipStream_t)stream, audio, (long)L, (long)T,
+                     (long)stride, (long)(S * T), out, vec4);
+  ++p2phd::g_launch_count[p2phd::LC_STITCH];
+  return p2phd::check_launch("segments_gather");
+}
+
+extern "C" int p2phd_segments_stitch(const float* seg, int64_t S, int64_t T, int64_t stride, float gain, float* out, int64_t L_out,
+                                     void* stream) {
+  P2PHD_REQUIRE(S >= 1 && T >= 1, "segments_stitch: need S >= 1 and T >= 1 (S %lld, T %lld)", (long long)S, (long long)T);
+  const int64_t V = T - stride;
+  P2PHD_REQUIRE(V >= 0 && V <= T / 2, "segments_stitch: the overlap T - stride must be in [0, T/2], got %lld (T %lld)", (long long)V,
+                (long long)T);
+  P2PHD_REQUIRE(S <= (int64_t(1) << 40) / T, "segments_stitch: S * T too large");
+  P2PHD_REQUIRE(L_out >= 0 && L_out <= (S - 1) * stride + T, "segments_stitch: L_out %lld is beyond the %lld samples the segments span",
+                (long long)L_out, (long long)((S - 1) * stride + T));
+  if (L_out == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(seg && out, "segments_stitch: null pointer");
+  const int vec4 = ((reinterpret_cast<uintptr_t>(seg) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  hipLaunchKernelGGL(segments_stitch_kernel, dim3(stream_grid(L_out)), dim3(kThreads), 0, (hipStream_t)stream, seg, (long)S, (long)T,
+                     (long)stride, (long)V, gain, out, (long)L_out, vec4);
+  ++p2phd::g_launch_count[p2phd::LC_STITCH];
+  return p2phd::check_launch("segments_stitch");
+}

@@ -162,6 +162,14 @@ class AudioDataset(BaseDataset):
         return waveform[0][:self.segment_length] if missing <= 0 else F.pad(waveform, (0, missing))
 
 
+def lr_round_trip(raw_audio, in_rate, lr_rate, hr_rate, is_lr_input=False):
+    """The model's input for a whole clip (audio_dataset.py:109-113): down to the low rate and back up to the high one, or
+    with `is_lr_input` a plain upsample of a clip that is already band-limited.  GPU resampler, any leading dims."""
+    if is_lr_input:
+        return resample(raw_audio, in_rate, hr_rate)
+    return resample(resample(raw_audio, in_rate, lr_rate), lr_rate, hr_rate)
+
+
 class AudioTestDataset(BaseDataset):
     """Whole-file inference input (audio_dataset.py:89-135): `raw_audio`, `lr_audio` [1, T] and `seg_audio`
     [segments, segment_length] live on the GPU; the LR round trip runs on csrc/resample.hip."""
@@ -181,11 +189,8 @@ class AudioTestDataset(BaseDataset):
         self.raw_audio = raw.to(self.device)
         self.audio_len = self.raw_audio.size(-1)
         print("Audio length:", self.audio_len)
-        if getattr(opt, 'is_lr_input', False):
-            self.lr_audio = resample(self.raw_audio, self.in_sampling_rate, self.hr_sampling_rate)
-        else:
-            self.lr_audio = resample(self.raw_audio, self.in_sampling_rate, self.lr_sampling_rate)
-            self.lr_audio = resample(self.lr_audio, self.lr_sampling_rate, self.hr_sampling_rate)
+        self.lr_audio = lr_round_trip(self.raw_audio, self.in_sampling_rate, self.lr_sampling_rate, self.hr_sampling_rate,
+                                      getattr(opt, 'is_lr_input', False))
         self.seg_audio = self.seg_pad_audio(self.lr_audio)
 
     def __len__(self):

@@ -218,7 +218,7 @@ class Pix2PixHDModel(BaseModel):
         mask_rows = 0
         mode = _opt(self.opt, 'mask_mode', None)
         if mask:
-            mask_rows = int(M * (1 - 1 / self.up_ratio))                    # pix2pixHD_model.py:199
+            mask_rows = self._mask_rows(M)
             if mode in ('mode0', 'mode1', 'mode2'):
                 if noise is None:
                     noise = torch.randn(B, C, mask_rows, Fr, device=spec.device)
@@ -251,6 +251,19 @@ class Pix2PixHDModel(BaseModel):
                 pha = pha * pn
         norm = {'min': norm8[0], 'max': norm8[1], 'mean': norm8[2], 'std': norm8[3], 'frames': frames, '_minmax': norm8[:2]}
         return log_spectro, pha, norm
+
+    def _mask_rows(self, bins):
+        return int(bins * (1 - 1 / self.up_ratio))                          # pix2pixHD_model.py:199
+
+    def mask_noise_shape(self, B, T):
+        """Shape of the `noise` tensor to_spectro(mask=True) takes for a [B, T] batch, or None when the options draw none."""
+        from .mdct import frame_layout
+        if not _opt(self.opt, 'mask', False) or _opt(self.opt, 'mask_mode', None) not in ('mode0', 'mode1', 'mode2'):
+            return None
+        m = self._mdct
+        bins = m.n_fft if self.mdct_type == 'mdct2' else m.n_fft // 2
+        frames = frame_layout(B, T, m.hop_length, m.win_length, m.center)[2]
+        return (B, 2 if _opt(self.opt, 'explicit_encoding', False) else 1, self._mask_rows(bins), frames)
 
     def _minmax(self, norm_param):
         mm = norm_param.get('_minmax')

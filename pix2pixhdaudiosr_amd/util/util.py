@@ -1,6 +1,7 @@
 """Host-side helpers of the hot path with the reference's names (util/util.py)."""
 import os
 
+import numpy as np
 import torch
 
 
@@ -13,6 +14,33 @@ def mkdirs(paths):
     """util/util.py:43-48: one path or a list of them."""
     for p in ([paths] if isinstance(paths, str) else list(paths)):
         mkdir(p)
+
+
+def tensor2im(image_tensor, imtype=np.uint8, normalize=True):
+    """util/util.py:12-26: a [C, H, W] tensor (or a list of them) in [-1, 1] (`normalize`) or [0, 1] -> an [H, W, C] image
+    array; a single channel, or more than three, gives the 2-D first channel."""
+    if isinstance(image_tensor, list):
+        return [tensor2im(t, imtype, normalize) for t in image_tensor]
+    image_numpy = np.transpose(image_tensor.cpu().float().numpy(), (1, 2, 0))
+    image_numpy = (image_numpy + 1) / 2.0 * 255.0 if normalize else image_numpy * 255.0
+    image_numpy = np.clip(image_numpy, 0, 255)
+    if image_numpy.shape[2] == 1 or image_numpy.shape[2] > 3:
+        image_numpy = image_numpy[:, :, 0]
+    return image_numpy.astype(imtype)
+
+
+def save_image(image_numpy, image_path):
+    """util/util.py:39-41 (the reference's Visualizer calls it, util/visualizer.py:61-64,126).  uint8 arrays -- what
+    tensor2im and the reference's matplotlib renderings give -- are written as they are.  `get_current_visuals` of this
+    build returns the plotted data itself, 2-D float arrays, which no 8-bit image format holds: those are min-max scaled
+    to uint8 first."""
+    from PIL import Image
+    a = np.asarray(image_numpy)
+    if a.dtype != np.uint8:
+        a = a.astype(np.float64)
+        lo, hi = (float(a.min()), float(a.max())) if a.size else (0.0, 0.0)
+        a = np.round((a - lo) * (255.0 / (hi - lo) if hi > lo else 0.0)).astype(np.uint8)
+    Image.fromarray(a).save(image_path)
 
 
 def kbdwin(N: int, beta: float = 12.0, device='cpu') -> torch.Tensor:

@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Whole-file generation at the published geometry, timed: G3L2, ngf 48, n_fft 512 (MDCT2), segments of 32 512 samples,
+bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
+
+  hand      the hand-composed loop (seg_pad_audio -> model.inference -> util.imdct per group -> cat)
+  eager     generate.SuperResolver(graph=False), overlap 0 and 0.25
+  graphed   generate.SuperResolver(graph=True), overlap 0 and 0.25
+  seams     RMS of the first difference at the joins (the first sample of every segment but the first) relative to the
+            first-difference RMS of the whole output, at overlap 0 and 0.25, same weights and noise seed
+
+Without a mode every one of them runs in a process of its own under its own time limit, in that order, and the run stops at
+the first that fails; the lines are also written to --log.
+
+Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] [--reps 5] [--log profiles/time_generate.log]
+"""
+import argparse
+import os
+import subprocess
+import sys
+import time
+from math import sqrt
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+LIMITS = {"hand": 240, "eager": 300, "graphed": 300, "seams": 240}
+
+
+def _opt():
+    return SimpleNamespace(
+        gpu_ids=[0], isTrain=False, checkpoints_dir=None, name="t", model="pix2pixHD", input_nc=2, output_nc=2,
+        label_nc=0, hr_sampling_rate=48000, lr_sampling_rate=8000, n_fft=512, hop_length=256, win_length=512, center=True,
+        no_instance=True, ngf=48, netG="local", n_downsample_global=4, n_blocks_global=3, n_local_enhancers=1, n_blocks_local=2,
+        norm="instance", no_lsgan=False, ndf=64, n_layers_D=3, num_D=2, no_ganFeat_loss=False, use_hifigan_D=False, use_time_D=False,
+        verbose=False, continue_train=False, load_pretrain="", which_epoch="latest", pool_size=0, lr=0.0002, beta1=0.5,
+        no_vgg_loss=True, use_match_loss=False, niter_fix_global=0, explicit_encoding=True, alpha=0.6, min_value=1e-7, mask=True,
+        mask_mode="mode2", phase_encoding_mode=None, lambda_feat=10.0, fp16=True, niter_decay=100, instance_feat=False,
+        label_feat=False, mdct_type="mdct2", segment_length=32512, batchSize=4)
+
+
+def _setup(seconds):
+    import torch
+    from pix2pixhdaudiosr_amd.models.models import create_model
+    import copy
+    import tempfile
+    opt = _opt()
+    torch.manual_seed(1234)
+    with tempfile.TemporaryDirectory() as folder:                 # generation runs an inference model: it loads its generator
+        opt.checkpoints_dir = folder
+        seed_opt = copy.copy(opt)
+        seed_opt.isTrain = True
+        create_model(seed_opt).save('latest')                     # untrained weights, written once, outside every timed region
+        torch.cuda.empty_cache()
+        model = create_model(opt)
+    model.eval()
+    n = int(seconds * opt.hr_sampling_rate)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    g = torch.Generator().manual_seed(7)
+    # a band-limited clip: a few partials below the low rate's 4 kHz with a slow envelope, and a little noise
+    x = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.2, 220.0, 0.0), (0.1, 660.0, 1.0), (0.05, 1870.0, 2.0), (0.03, 3300.0, 0.5)))
+    x = x * (0.6 + 0.4 * torch.sin(2 * torch.pi * 0.7 * t)) + 0.002 * torch.randn(n, generator=g, dtype=torch.float64)
+    return torch, model, opt, x.float().cuda()[None]
+
+
+def _hand(torch, model, opt, lr):
+    from pix2pixhdaudiosr_amd.data.audio_dataset import AudioTestDataset
+    from pix2pixhdaudiosr_amd.dct.dct import IDCT
+    from pix2pixhdaudiosr_amd.models.mdct import IMDCT2
+    from pix2pixhdaudiosr_amd.util import util as U
+    ds = AudioTestDataset.__new__(AudioTestDataset)
+    ds.segment_length = opt.segment_length
+    _imdct = IMDCT2(window=U.kbdwin, win_length=opt.win_length, hop_length=opt.hop_length, n_fft=opt.n_fft, center=opt.center,
+                    out_length=opt.segment_length, device='cuda', idct_op=IDCT())
+    up = opt.hr_sampling_rate / opt.lr_sampling_rate
+
+    def run():
+        seg = ds.seg_pad_audio(lr)
+        audio = []
+        with torch.no_grad():
+            for s0 in range(0, seg.shape[0], opt.batchSize):
+                sr_spectro, lr_pha, norm_param, _ = model.inference(seg[s0:s0 + opt.batchSize], None)
+                audio.append(U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=_imdct,
+                                     up_ratio=up, explicit_encoding=True))
+        return sqrt(up - 1) * torch.cat(audio, dim=0).view(1, -1)
+    return run
+
+
+def _time(torch, fn, reps):
+    fn(); fn()                                                     # warm-up (and capture, where there is one)
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def run_mode(mode, seconds, reps):
+    torch, model, opt, lr = _setup(seconds)
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, segment_plan
+    if mode == "hand":
+        dt = _time(torch, _hand(torch, model, opt, lr), reps)
+        print(f"hand-composed loop    overlap 0     {seconds / dt:8.1f} s of audio / s   ({dt * 1e3:.3f} ms for {seconds:g} s, best of {reps})")
+    elif mode in ("eager", "graphed"):
+        for overlap in (0.0, 0.25):
+            sr = SuperResolver(model, opt, overlap=overlap, graph=mode == "graphed")
+            dt = _time(torch, lambda: sr.enhance_lr(lr), reps)
+            S = segment_plan(lr.shape[-1], opt.segment_length, overlap)[0]
+            print(f"pipeline {mode:8s}     overlap {overlap:<5g} {seconds / dt:8.1f} s of audio / s   ({dt * 1e3:.3f} ms, {S} segments, best of {reps})")
+    elif mode == "seams":
+        for overlap in (0.0, 0.25):
+            S, stride, V = segment_plan(lr.shape[-1], opt.segment_length, overlap)
+            torch.manual_seed(99)
+            y = SuperResolver(model, opt, overlap=overlap).enhance_lr(lr)[0].double()
+            d = y[1:] - y[:-1]                                      # d[n - 1] = y[n] - y[n - 1]
+            joins = torch.arange(1, S, device=y.device) * stride
+            joins = joins[joins < y.numel()]
+            at = d[joins - 1].pow(2).mean().sqrt().item()
+            allrms = d.pow(2).mean().sqrt().item()
+            print(f"seams  overlap {overlap:<5g} {len(joins)} joins: first-difference RMS at the joins {at:.4e}, whole clip {allrms:.4e}, ratio {at / allrms:.3f}")
+    else:
+        raise SystemExit("unknown mode " + mode)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS))
+    ap.add_argument("--seconds", type=float, default=15.0)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
+    a = ap.parse_args()
+    if a.mode is not None:
+        return run_mode(a.mode, a.seconds, a.reps)
+    lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
+    for mode, limit in LIMITS.items():
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--seconds", str(a.seconds), "--reps", str(a.reps)],
+                               capture_output=True, text=True, timeout=limit)
+        except subprocess.TimeoutExpired:
+            lines.append(f"{mode}: no result within {limit} s")
+            break
+        out = [l for l in p.stdout.splitlines() if l.startswith(("hand", "pipeline", "seams"))]
+        lines += out
+        if p.returncode != 0:
+            lines.append(f"{mode}: exit status {p.returncode}: {p.stderr.strip().splitlines()[-1] if p.stderr.strip() else ''}")
+            break
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    with open(a.log, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
