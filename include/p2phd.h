@@ -84,7 +84,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient), and the dedicated single-layer kernels "dfirst",
  * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them), "timed_pack" / "timed_frames" (the time-domain
  * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
- * cross-fading stitch of whole-file generation, csrc/stitch.hip).  family == NULL with reset != 0 clears all.
+ * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode and encode of its file ends,
+ * csrc/pcm.hip).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -193,10 +194,42 @@ int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* 
  *   the overlaps; inside one the later segment has sin^2(pi (i + 1/2) / (2 V)) at its sample i < V and the earlier one
  *   1 - that value.  The first segment does not fade in, the last does not fade out.  V = 0: a scaled copy.  Evaluated in
  *   double, rounded once.  Errors (P2PHD_EINVAL): V outside [0, T/2], S < 1, L_out > (S - 1) stride + T.
+ * p2phd_segments_gather_planar / p2phd_segments_stitch_planar: the same two over the C rows of a planar clip in ONE launch
+ *   each (two "stitch" launches per clip whatever C is): audio [C][ld] -> out [C * S, T], channel-major (row c * S + s is
+ *   segment s of channel c), and seg [C * S, T] -> out [C][ld], L_out samples per row, the rest of a row untouched.  Row c is
+ *   bit-identical to the single-row entry on audio[c] / seg[c * S : (c + 1) * S].  Same errors, plus C < 1, ld < L, ld < L_out.
  * ---------------------------------------------------------------------------------------- */
 int p2phd_segments_gather(const float* audio, int64_t L, int64_t T, int64_t stride, int64_t S, float* out, void* stream);
 int p2phd_segments_stitch(const float* seg, int64_t S, int64_t T, int64_t stride, float gain, float* out, int64_t L_out,
                           void* stream);
+int p2phd_segments_gather_planar(const float* audio, int64_t C, int64_t ld, int64_t L, int64_t T, int64_t stride, int64_t S,
+                                 float* out, void* stream);
+int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t T, int64_t stride, float gain, float* out,
+                                 int64_t ld, int64_t L_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * PCM codec of whole-file generation, csrc/pcm.hip.  Launch family "pcm" (a decode and an encode count 1 each; frames = 0
+ * launches nothing).  The payload is the little-endian INTERLEAVED sample stream of a RIFF data chunk (frame n, channel c at
+ * sample n * channels + c); the float side is PLANAR, row c at c * ld, ld >= frames.  The payload pointer needs byte
+ * alignment only.
+ *
+ * p2phd_pcm_decode: payload -> out[c * ld + n] f32, the scaling of data/wavio.py load and bit-identical to it: (u - 128) / 128
+ *   for unsigned 8-bit, s / 2^(bits - 1) for signed 16 / 24 / 32-bit (one int -> float conversion, round to nearest even for
+ *   32-bit, then an exact power-of-two scale), a bit copy for float32 (a NaN keeps its payload), round to nearest even for
+ *   float64.
+ * p2phd_pcm_encode: planar f32 -> payload.  P2PHD_PCM_S16 / _S24: clamp to [-1, (2^(bits-1) - 1) / 2^(bits-1)], times
+ *   2^(bits-1), round half to even -- for PCM16 the bytes data/wavio.py save writes.  NaN encodes as 0 (wavio.save leaves
+ *   that case undefined: the int16 conversion of a NaN is whatever the host gives).  P2PHD_PCM_F32: a bit copy.  Other
+ *   formats: P2PHD_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+#define P2PHD_PCM_U8  0   /* format tag 1,  8 bit */
+#define P2PHD_PCM_S16 1   /* format tag 1, 16 bit */
+#define P2PHD_PCM_S24 2   /* format tag 1, 24 bit */
+#define P2PHD_PCM_S32 3   /* format tag 1, 32 bit */
+#define P2PHD_PCM_F32 4   /* format tag 3, 32 bit */
+#define P2PHD_PCM_F64 5   /* format tag 3, 64 bit */
+int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels, int format, float* out, int64_t ld, void* stream);
+int p2phd_pcm_encode(const float* planar, int64_t frames, int channels, int64_t ld, int format, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

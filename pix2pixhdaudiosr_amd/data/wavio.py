@@ -2,6 +2,7 @@
 header parse + a seek to the requested frame window, so a random training segment costs one read of segment_length
 frames, not the file.  PCM 8/16/24/32-bit and IEEE float, WAVE_FORMAT_EXTENSIBLE included; samples are scaled the way
 `torchaudio.load(normalize=True)` documents (signed PCM / 2^(bits-1)).  Host I/O only -- no arithmetic of the hot path."""
+import os
 import struct
 from collections import namedtuple
 
@@ -63,15 +64,64 @@ def load(path, frame_offset=0, num_frames=-1):
     return torch.from_numpy(np.ascontiguousarray(a.reshape(-1, meta.num_channels).T)), meta.sample_rate
 
 
-def save(path, waveform, sample_rate):
-    """PCM16 writer (torchaudio.save's default for float input is float32; the reference's outputs are listened to,
-    not re-read, generate_audio.py:65): waveform [channels, frames] or [frames] in [-1, 1)."""
+def read_payload(path, into=None):
+    """-> (payload, WavInfo): the bytes of the data chunk, `num_frames * block_align` of them, undecoded (the device decodes
+    them, generate.pcm_decode).  `into`: a writable buffer at least that long, or a callable that is given the byte count
+    and returns one (a pinned host tensor's memory); the payload is a view of it, cut to size.  Default: a bytearray.  A
+    data chunk that promises more than the file holds is cut to the whole frames that are there, as `load` reads it."""
+    meta = info(path)
+    with open(path, "rb") as f:
+        there = max(os.fstat(f.fileno()).st_size - meta.data_offset, 0) // meta.block_align
+        if there < meta.num_frames:
+            meta = meta._replace(num_frames=there)
+        n = meta.num_frames * meta.block_align
+        buf = bytearray(n) if into is None else into(n) if callable(into) else into
+        buf = memoryview(buf).cast("B")
+        if len(buf) < n:
+            raise ValueError(f"{path}: the buffer holds {len(buf)} bytes, the data chunk {n}")
+        f.seek(meta.data_offset)
+        if f.readinto(buf[:n]) != n:
+            raise ValueError(f"{path}: short read of the data chunk")
+    return buf[:n], meta
+
+
+# encoding -> (format tag, bits per sample)
+ENCODINGS = {"pcm16": (1, 16), "pcm24": (1, 24), "float32": (3, 32)}
+
+
+def write_payload(path, payload, sample_rate, channels, encoding="pcm16"):
+    """A 44-byte header (format tag 1 for the PCM encodings, 3 for float32) and `payload`, the interleaved little-endian
+    samples as they stand."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"wavio: encoding must be one of {sorted(ENCODINGS)}, got {encoding!r}")
+    tag, bits = ENCODINGS[encoding]
+    align = int(channels) * bits // 8
+    payload = memoryview(payload).cast("B")
+    if channels < 1 or len(payload) % align:
+        raise ValueError(f"wavio: {len(payload)} bytes are not whole frames of {channels} x {bits} bit")
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 36 + len(payload) + (len(payload) & 1)) + b"WAVE")
+        f.write(b"fmt " + struct.pack("<IHHIIHH", 16, tag, int(channels), int(sample_rate), int(sample_rate) * align, align, bits))
+        f.write(b"data" + struct.pack("<I", len(payload)))
+        f.write(payload)
+        if len(payload) & 1:
+            f.write(b"\0")                                            # RIFF chunks are word-aligned
+
+
+def save(path, waveform, sample_rate, encoding="pcm16"):
+    """Writer (torchaudio.save's default for float input is float32; the reference's outputs are listened to, not re-read,
+    generate_audio.py:65): waveform [channels, frames] or [frames].  `encoding`: 'pcm16' (default) and 'pcm24' clamp to
+    [-1, 1 - 2^-(bits-1)], scale by 2^(bits-1) and round half to even; 'float32' writes the values as they are."""
+    if encoding not in ENCODINGS:
+        raise ValueError(f"wavio: encoding must be one of {sorted(ENCODINGS)}, got {encoding!r}")
     w = torch.as_tensor(waveform).detach().cpu().float()
     if w.dim() == 1:
         w = w.unsqueeze(0)
-    pcm = (w.clamp(-1.0, 32767.0 / 32768.0) * 32768.0).round().to(torch.int16).T.contiguous().numpy().tobytes()
-    ch = w.shape[0]
-    with open(path, "wb") as f:
-        f.write(b"RIFF" + struct.pack("<I", 36 + len(pcm)) + b"WAVE")
-        f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, ch, int(sample_rate), int(sample_rate) * ch * 2, ch * 2, 16))
-        f.write(b"data" + struct.pack("<I", len(pcm)) + pcm)
+    if encoding == "pcm16":
+        pcm = (w.clamp(-1.0, 32767.0 / 32768.0) * 32768.0).round().to(torch.int16).T.contiguous().numpy().tobytes()
+    elif encoding == "pcm24":
+        q = (w.clamp(-1.0, 8388607.0 / 8388608.0) * 8388608.0).round().to(torch.int32).T.contiguous().numpy()
+        pcm = np.ascontiguousarray(q.astype("<i4").reshape(-1, 1).view(np.uint8)[:, :3]).tobytes()
+    else:
+        pcm = w.T.contiguous().numpy().astype("<f4").tobytes()
+    write_payload(path, pcm, sample_rate, w.shape[0], encoding)

@@ -1,6 +1,7 @@
 """Whole-file super-resolution: wav in, wav out, on the device from the waveform to the waveform.
 
     python -m pix2pixhdaudiosr_amd.generate --input in.wav --output out.wav --load_pretrain DIR [--overlap 0.25]
+    python -m pix2pixhdaudiosr_amd.generate --input DIR_IN --output DIR_OUT --load_pretrain DIR --channels all [--metrics_csv m.csv]
 
     from pix2pixhdaudiosr_amd.generate import SuperResolver
     sr = SuperResolver(model, opt).enhance_file("in.wav", "out.wav")["sr"]
@@ -15,12 +16,17 @@ full amplitude -- 6 dB more; `SuperResolver(reference_amplitude=...)` and `--ref
 
 A group is semantics: `to_spectro` normalises by the min / max of the whole batch tensor (pix2pixHD_model.py:165-168 of the
 reference), so a group holds exactly the segments the reference's loader would put in it and a last, smaller group runs at
-its own size -- padding it with silent segments would change its normalisation.
+its own size -- padding it with silent segments would change its normalisation.  For the same reason a channel of a file is
+a clip of its own: a group never mixes channels, and channel c of a [C, L] clip is grouped exactly as the mono clip audio[c].
+
+The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
+decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
 """
 import argparse
 import ast
 import math
 import os
+import struct
 import sys
 from types import SimpleNamespace
 
@@ -69,6 +75,109 @@ def segments_stitch(seg, stride, gain=1.0, out_length=None):
     return out
 
 
+def _rows(t, name):
+    """A [C, L] f32 GPU tensor whose rows are contiguous (a row pitch >= L is fine) -> (tensor, C, L, pitch)."""
+    from . import _lib
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise _lib.P2PHDError("%s: expected a float32 tensor on the GPU (this build has no CPU path)" % name)
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError("%s: expected [C, L] with C >= 1, got shape %s" % (name, tuple(t.shape)))
+    C, L = t.shape
+    if L > 1 and t.stride(1) != 1 or C > 1 and t.stride(0) < L:
+        raise _lib.P2PHDError("%s: expected rows that are contiguous" % name)
+    return t, C, L, (t.stride(0) if C > 1 else max(L, 1))
+
+
+def segments_gather_planar(audio, T, stride, S):
+    """audio [C, L] f32 on the GPU (rows contiguous, any row pitch) -> [C * S, T], channel-major: row c * S + s holds
+    audio[c, s * stride : s * stride + T], zeros beyond the end.  One launch whatever C is."""
+    from . import _lib
+    a, C, L, ld = _rows(audio, "segments_gather_planar: audio")
+    out = torch.empty((C * max(int(S), 0), max(int(T), 0)), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().p2phd_segments_gather_planar(_lib.ptr(a), C, max(ld, L), L, int(T), int(stride), int(S), _lib.ptr(out),
+                                                       _lib.stream_ptr()), "segments_gather_planar")
+    return out
+
+
+def segments_stitch_planar(seg, C, stride, gain=1.0, out_length=None, ld=None):
+    """seg [C * S, T] f32 on the GPU, channel-major -> [C, out_length]: segments_stitch on every channel's S rows, in one
+    launch.  `ld`: row pitch of the buffer the result is a view of (default: out_length)."""
+    from . import _lib
+    s = _lib.require_gpu_tensor(seg, "segments_stitch_planar: seg", torch.float32)
+    C = int(C)
+    if s.dim() != 2 or C < 1 or s.shape[0] % C:
+        raise ValueError("segments_stitch_planar: expected [C * S, T] with C = %d, got shape %s" % (C, tuple(s.shape)))
+    S, T = s.shape[0] // C, s.shape[1]
+    L_out = (S - 1) * int(stride) + T if out_length is None else int(out_length)
+    ld = max(L_out, 0) if ld is None else int(ld)
+    out = torch.empty((C, max(ld, 0)), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_segments_stitch_planar(_lib.ptr(s), C, S, T, int(stride), float(gain), _lib.ptr(out), ld, L_out,
+                                                       _lib.stream_ptr()), "segments_stitch_planar")
+    return out[:, :max(L_out, 0)]
+
+
+# (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
+PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
+# encoding of wavio.save / wavio.write_payload -> (P2PHD_PCM_* code, bytes per sample)
+PCM_ENCODINGS = {'pcm16': (1, 2), 'pcm24': (2, 3), 'float32': (4, 4)}
+
+
+def pcm_decode(payload, frames, channels, format_tag, bits):
+    """payload: uint8 tensor on the GPU holding the interleaved little-endian samples of a data chunk (any byte offset into
+    its storage) -> [channels, frames] f32, bit-identical to what wavio.load returns for the file."""
+    from . import _lib
+    b = _lib.require_gpu_tensor(payload, "pcm_decode: payload", torch.uint8)
+    fmt = PCM_FORMATS.get((int(format_tag), int(bits)))
+    if fmt is None:
+        raise ValueError("pcm_decode: unsupported format (tag %s, %s bit)" % (format_tag, bits))
+    frames, channels = int(frames), int(channels)
+    if b.numel() < frames * channels * (int(bits) // 8):
+        raise ValueError("pcm_decode: %d bytes do not hold %d frames of %d x %d bit" % (b.numel(), frames, channels, bits))
+    out = torch.empty((channels, frames), dtype=torch.float32, device=b.device)
+    _lib.check(_lib.lib().p2phd_pcm_decode(_lib.ptr(b), frames, channels, fmt, _lib.ptr(out), frames, _lib.stream_ptr()), "pcm_decode")
+    return out
+
+
+def pcm_encode(waveform, encoding='pcm16'):
+    """waveform [C, L] f32 on the GPU (rows contiguous) -> uint8 tensor of L * C samples, interleaved: the payload
+    wavio.write_payload takes.  'pcm16' gives the bytes wavio.save writes; NaN encodes as 0 in the integer formats."""
+    from . import _lib
+    if encoding not in PCM_ENCODINGS:
+        raise ValueError("pcm_encode: encoding must be one of %s, got %r" % (sorted(PCM_ENCODINGS), encoding))
+    w, C, L, ld = _rows(waveform, "pcm_encode: waveform")
+    fmt, nbytes = PCM_ENCODINGS[encoding]
+    out = torch.empty((L * C * nbytes,), dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.lib().p2phd_pcm_encode(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(out), _lib.stream_ptr()), "pcm_encode")
+    return out
+
+
+def select_channels(channels, available):
+    """How many leading channels of a file with `available` channels are enhanced and written: 'first' -> 1, 'all' -> every
+    one, an int N -> the first N (all of them where the file has fewer)."""
+    if channels == 'first':
+        return 1
+    if channels == 'all':
+        return int(available)
+    if isinstance(channels, bool) or not isinstance(channels, int) or channels < 1:
+        raise ValueError("channels must be 'first', 'all' or an int >= 1, got %r" % (channels,))
+    return min(channels, int(available))
+
+
+def plan_folder(dir_in, dir_out):
+    """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
+    output keeps the relative path under dir_out.  Other files are ignored."""
+    if not os.path.isdir(dir_in):
+        raise NotADirectoryError("%s is not a directory" % dir_in)
+    if os.path.exists(dir_out) and not os.path.isdir(dir_out):
+        raise NotADirectoryError("--input is a directory, so --output must be one too: %s is a file" % dir_out)
+    rel = []
+    for root, _, files in os.walk(dir_in):
+        for f in files:
+            if f.lower().endswith('.wav'):
+                rel.append(os.path.relpath(os.path.join(root, f), dir_in))
+    return [(r, os.path.join(dir_in, r), os.path.join(dir_out, r)) for r in sorted(rel)]
+
+
 class SuperResolver:
     """`model`: anything with `.inference(lr_audio, inst, noise=None) -> (sr_spectro, lr_pha, norm_param, lr_spectro)`
     (Pix2PixHDModel); its `mdct_type` picks the inverse transform.  `overlap`: shared fraction of a segment, [0, 0.5].
@@ -113,6 +222,7 @@ class SuperResolver:
         self.reference_amplitude = bool(reference_amplitude) and self.mdct_type == 'mdct2'
         self.gain = math.sqrt(self.up_ratio - 1) * (1.0 if self.reference_amplitude else 2.0)
         self._g = None                                                      # captured chain of a full group
+        self._pins = {}                                                     # pinned host buffers of the file path, grow-only
 
     # -- one group ---------------------------------------------------------------------------------
     def noise_shape(self, b):
@@ -176,58 +286,143 @@ class SuperResolver:
 
     # -- one clip ----------------------------------------------------------------------------------
     def enhance_lr(self, lr_audio, noise=None):
-        """lr_audio: [1, L] or [L] on the GPU, already at the high rate -> the generated clip [1, L].  `noise`: the mask noise
-        of all S segments, [S, C, mask_rows, frames], sliced per group; drawn per group (one torch.randn) when absent."""
+        """lr_audio: [C, L] or [L] on the GPU, already at the high rate -> the generated clip [C, L] ([1, L] for [L]).  Every
+        channel is a clip of its own: its S segments are grouped as if it were a mono clip, so
+        enhance_lr(x)[c] == enhance_lr(x[c:c+1])[0] given the same noise rows.  `noise`: the mask noise of all C * S segments,
+        [C * S, channels, mask_rows, frames], channel-major, sliced per group; drawn per group (one torch.randn) when absent."""
         run = getattr(self.model, '_on_step_stream', None)
         with torch.no_grad():
             return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
 
     def _enhance_lr(self, lr_audio, noise):
         x = lr_audio.to(self.device).float()
-        if x.dim() == 2 and x.shape[0] == 1:
-            x = x[0]
-        if x.dim() != 1:
-            raise ValueError("enhance_lr: expected a [1, L] or [L] waveform, got shape %s" % (tuple(lr_audio.shape),))
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError("enhance_lr: expected a [C, L] or [L] waveform, got shape %s" % (tuple(lr_audio.shape),))
         x = x.contiguous()
-        L = x.numel()
+        C, L = x.shape
         S, stride, V = segment_plan(L, self.T, self.overlap)
-        seg = segments_gather(x, self.T, stride, S)
+        seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
-        for s0 in range(0, S, self.batch):
-            b = min(self.batch, S - s0)
-            shape = self.noise_shape(b)
-            nz = None
-            if shape is not None:
-                nz = noise[s0:s0 + b] if noise is not None else torch.randn(shape, device=self.device)
-                if tuple(nz.shape) != shape:
-                    raise ValueError("enhance_lr: noise for segments %d..%d has shape %s, expected %s"
-                                     % (s0, s0 + b - 1, tuple(nz.shape), shape))
-            if self.graph and b == self.batch and self._graph_ok():
-                out[s0:s0 + b].copy_(self._run_graphed(seg[s0:s0 + b], nz))
-            else:
-                out[s0:s0 + b].copy_(self._group(seg[s0:s0 + b], nz))
-        return segments_stitch(out, stride, self.gain, L).view(1, L)
+        for c in range(C):
+            for s0 in range(0, S, self.batch):
+                b = min(self.batch, S - s0)
+                r0 = c * S + s0
+                shape = self.noise_shape(b)
+                nz = None
+                if shape is not None:
+                    nz = noise[r0:r0 + b] if noise is not None else torch.randn(shape, device=self.device)
+                    if tuple(nz.shape) != shape:
+                        raise ValueError("enhance_lr: noise for segments %d..%d of channel %d has shape %s, expected %s"
+                                         % (s0, s0 + b - 1, c, tuple(nz.shape), shape))
+                if self.graph and b == self.batch and self._graph_ok():
+                    out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz))
+                else:
+                    out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz))
+        return segments_stitch_planar(out, C, stride, self.gain, L)
 
-    def enhance_file(self, path_in, path_out=None, is_lr_input=False):
-        """wav -> first channel -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a
-        clip that is already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  Returns {'sr', 'lr', 'hr',
-        'metrics'}: [1, L] tensors on the GPU; 'hr' and 'metrics' (util.compute_matrics against the input) are None unless the
-        input is a full-band clip at the high rate."""
+    # -- files -------------------------------------------------------------------------------------
+    def _pinned(self, slot, nbytes):
+        """Grow-only pinned byte buffer `slot`, free to be overwritten: the copy that last read it has finished.  Allocating
+        one goes through the HIP runtime: call from the thread that owns the device."""
+        t, busy = self._pins.get(slot, (None, None))
+        if busy is not None:
+            busy.synchronize()
+        if t is None or t.numel() < nbytes:
+            t = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, pin_memory=True)
+        self._pins[slot] = (t, None)
+        return t
+
+    def _read(self, path, slot='in0'):
+        """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo)."""
         from .data import wavio
+        payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
+        return self._pins[slot][0][:len(payload)], meta, slot
+
+    def _decode(self, host, meta, slot):
+        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel."""
+        if host.numel() == 0:
+            return torch.zeros((meta.num_channels, 0), dtype=torch.float32, device=self.device)
+        dev = torch.empty((host.numel(),), dtype=torch.uint8, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        busy = torch.cuda.Event()
+        busy.record()
+        self._pins[slot] = (self._pins[slot][0], busy)
+        return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
+
+    def _write(self, path_out, sr, encoding):
+        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload."""
+        from .data import wavio
+        dev = pcm_encode(sr.contiguous(), encoding)
+        host = self._pinned('out', dev.numel())[:dev.numel()]
+        host.copy_(dev, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        folder = os.path.dirname(os.path.abspath(path_out))
+        os.makedirs(folder, exist_ok=True)
+        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), sr.shape[0], encoding)
+
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding):
         from .data.audio_dataset import lr_round_trip
         from .util import util as U
         o = self.opt
-        raw, rate = wavio.load(path_in)
-        raw = raw[:1].to(self.device)
+        host, meta, slot = read
+        if encoding not in PCM_ENCODINGS:
+            raise ValueError("enhance_file: encoding must be one of %s, got %r" % (sorted(PCM_ENCODINGS), encoding))
+        k = select_channels(channels, meta.num_channels)
+        rate = meta.sample_rate
+        raw = self._decode(host, meta, slot)[:k]
         lr = lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
         has_hr = not is_lr_input and int(rate) == int(o.hr_sampling_rate)
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         sr = self.enhance_lr(lr)
-        metrics = U.compute_matrics(raw, lr, sr, o) if has_hr else None
+        metrics = None
+        if has_hr and channels == 'first':
+            metrics = U.compute_matrics(raw, lr, sr, o)
+        elif has_hr:
+            metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
         if path_out is not None:
-            wavio.save(path_out, sr, int(o.hr_sampling_rate))
-        return {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics}
+            self._write(path_out, sr, encoding)
+        return {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+
+    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16'):
+        """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
+        already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
+        int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
+        output encoded on the device (csrc/pcm.hip).  Returns {'sr', 'lr', 'hr', 'metrics', 'info'}: [C, L] tensors on the GPU;
+        'hr' and 'metrics' are None unless the input is a full-band clip at the high rate; 'metrics' is
+        util.compute_matrics against the input with 'first', else a list with one such 7-tuple per written channel, each
+        computed on that channel alone; 'info' is the input's wavio.WavInfo."""
+        return self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding)
+
+    def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None):
+        """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
+        and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
+        generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
+        `report(record)` is called after every file.  Returns one record per file: {'path' (relative), 'rate', 'channels',
+        'frames' (of the input), 'written_channels', 'out_frames', 'metrics' (as enhance_file(channels != 'first') returns
+        them: a list per channel, or None), 'error' (None, or the text of what went wrong)}."""
+        records = []
+        for rel, path_in, path_out in plan_folder(dir_in, dir_out):
+            rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
+                   'metrics': None, 'error': None}
+            try:
+                read = self._read(path_in)
+            except (ValueError, OSError, EOFError, struct.error) as e:
+                rec['error'] = '%s: %s' % (type(e).__name__, e)
+            else:
+                if seed is not None:
+                    torch.manual_seed(int(seed))
+                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding)
+                m, meta = res['metrics'], res['info']
+                rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
+                           written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
+                           metrics=[m] if m is not None and channels == 'first' else m)
+            records.append(rec)
+            if report is not None:
+                report(rec)
+        return records
 
 
 # ------------------------------------------------------------------------------------------
@@ -267,10 +462,67 @@ def opt_from_file(path, **overrides):
     return SimpleNamespace(**d)
 
 
+def _channels_arg(text):
+    if text in ("all", "first"):
+        return text
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError("expected all, first or a count >= 1, got %r" % text)
+    return n
+
+
+def check_paths(path_in, path_out):
+    """-> True for folder mode (both are directories; the output one may not exist yet), False for one file.  Mixing a file
+    and a directory is an error."""
+    if os.path.isdir(path_in):
+        if os.path.isfile(path_out):
+            raise ValueError("--input %s is a directory, so --output must be a directory too, and %s is a file" % (path_in, path_out))
+        return True
+    if os.path.isdir(path_out):
+        raise ValueError("--input %s is a file, so --output must be a file too, and %s is a directory" % (path_in, path_out))
+    return False
+
+
+METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd")
+
+
+def metrics_rows(records):
+    """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
+    (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
+    nothing was measured."""
+    rows = []
+    for r in records:
+        for c, m in enumerate(r['metrics'] or ()):
+            rows.append((r['path'], c, r['out_frames'], m[0], m[1], m[2], m[6]))
+    if rows:
+        rows.append(("mean", "", "") + tuple(sum(row[k] for row in rows) / len(rows) for k in range(3, 7)))
+    return rows
+
+
+def write_metrics_csv(path, records):
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(METRICS_COLUMNS)
+        for row in metrics_rows(records):
+            w.writerow([repr(v) if isinstance(v, float) else v for v in row])
+
+
 def _parser():
     ap = argparse.ArgumentParser(prog="python -m pix2pixhdaudiosr_amd.generate", description=__doc__.split("\n")[0])
-    ap.add_argument("--input", required=True, help="wav file to enhance")
-    ap.add_argument("--output", required=True, help="wav file to write (PCM16 at hr_sampling_rate)")
+    ap.add_argument("--input", required=True, help="wav file to enhance, or a folder: every *.wav below it")
+    ap.add_argument("--output", required=True, help="wav file to write (at hr_sampling_rate), or the folder that takes the "
+                                                    "outputs at the inputs' relative paths")
+    ap.add_argument("--channels", type=_channels_arg, default="first", metavar="all|first|N",
+                    help="channels of a file to enhance and write: the first one (default), all, or the first N; every "
+                         "channel is enhanced as a clip of its own")
+    ap.add_argument("--encoding", default="pcm16", choices=sorted(PCM_ENCODINGS), help="sample format of the output (default pcm16)")
+    ap.add_argument("--metrics_csv", default=None, metavar="PATH",
+                    help="write file, channel, frames, mse, snr_sr, snr_lr, lsd of every written channel that has a full-band "
+                         "original, and a last `mean` row")
     ap.add_argument("--load_pretrain", required=True, help="folder with <which_epoch>_net_G.pth (and opt.txt)")
     ap.add_argument("--opt_file", default=None, help="options dump of the training run (default: <load_pretrain>/opt.txt)")
     ap.add_argument("--which_epoch", default=None)
@@ -288,8 +540,26 @@ def _parser():
     return ap
 
 
+def _print_metrics(m, prefix=''):
+    mse, snr_sr, snr_lr, _, _, _, lsd = m
+    print('%sMSE: %.4f' % (prefix, mse))                                    # generate_audio.py:53-59
+    print('%sSNR_SR: %.4f' % (prefix, snr_sr))
+    print('%sSNR_LR: %.4f' % (prefix, snr_lr))
+    print('%sLSD: %.4f' % (prefix, lsd))
+
+
+def _print_unwritten(name, available, written):
+    if written < available:
+        print('%s: %d of %d channels enhanced and written (--channels all writes every channel)' % (name, written, available))
+
+
 def main(argv=None):
-    a = _parser().parse_args(argv)
+    ap = _parser()
+    a = ap.parse_args(argv)
+    try:
+        folder_mode = check_paths(a.input, a.output)
+    except ValueError as e:
+        ap.error(str(e))
     folder = os.path.abspath(a.load_pretrain)
     over = dict(checkpoints_dir=os.path.dirname(folder), name=os.path.basename(folder), load_pretrain='', continue_train=False)
     for k in ("which_epoch", "batchSize"):
@@ -303,19 +573,46 @@ def main(argv=None):
     from .models.models import create_model
     model = create_model(opt)
     model.eval()
-    if getattr(opt, 'seed', None) is not None:
-        torch.manual_seed(int(opt.seed))                                    # the mask noise: one run, one result
+    seed = getattr(opt, 'seed', None)
+    if seed is not None:
+        torch.manual_seed(int(seed))                                        # the mask noise: one run, one result
     sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
                        reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude))
     print('amplitude: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full'))
-    res = sr.enhance_file(a.input, a.output, a.is_lr_input)
-    if res['metrics'] is not None:
-        mse, snr_sr, snr_lr, _, _, _, lsd = res['metrics']
-        print('MSE: %.4f' % mse)                                            # generate_audio.py:53-59
-        print('SNR_SR: %.4f' % snr_sr)
-        print('SNR_LR: %.4f' % snr_lr)
-        print('LSD: %.4f' % lsd)
-    print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], int(opt.hr_sampling_rate)))
+    rate = int(opt.hr_sampling_rate)
+    if folder_mode:
+        def report(r):
+            if r['error'] is not None:
+                print('skipped %s: %s' % (r['path'], r['error']))
+                return
+            _print_unwritten(r['path'], r['channels'], r['written_channels'])
+            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
+                                                                   r['written_channels'], '' if r['written_channels'] == 1 else 's'))
+        # every file starts from the seed, so it comes out as a run of its own would write it
+        records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report)
+        done = [r for r in records if r['error'] is None]
+        print('%d of %d files enhanced, %d skipped' % (len(done), len(records), len(records) - len(done)))
+        rows = metrics_rows(records)
+        if rows:
+            print('mean over %d channels: MSE %.4f  SNR_SR %.4f  SNR_LR %.4f  LSD %.4f' % ((len(rows) - 1,) + rows[-1][3:]))
+    else:
+        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding)
+        m, written = res['metrics'], res['sr'].shape[0]
+        _print_unwritten(a.input, res['info'].num_channels, written)
+        if m is not None and a.channels == 'first':
+            _print_metrics(m)
+        elif m is not None:
+            for c, mc in enumerate(m):
+                _print_metrics(mc, 'channel %d ' % c)
+        if written == 1:
+            print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
+        else:
+            print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
+        records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
+                    'metrics': [m] if m is not None and a.channels == 'first' else m}]
+    if a.metrics_csv:
+        write_metrics_csv(a.metrics_csv, records)
+        print('metrics: %s' % a.metrics_csv)
     return 0
 
 

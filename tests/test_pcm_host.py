@@ -1,0 +1,224 @@
+"""Host side of the multi-channel / folder / device-codec file path (pix2pixhdaudiosr_amd/generate.py, data/wavio.py): the
+numpy restatement of the codec (tests/_pcm_ref.py) against wavio as it stands, the new encodings of the writer, folder
+planning and the command line's new flags."""
+import os
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+import _pcm_ref as P
+
+FRAMES = (0, 1, 5, 4097)
+CHANNELS = (1, 2, 3, 6)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------
+# 1. the yardstick is the code as it stands
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(P.FORMATS))
+@pytest.mark.parametrize("extensible", [False, True])
+def test_restated_decode_is_wavio_load(tmp_path, name, extensible):
+    from pix2pixhdaudiosr_amd.data import wavio
+    for channels in CHANNELS:
+        for frames in FRAMES:
+            pay = P.payload(name, frames, channels)
+            path = str(tmp_path / f"{name}_{channels}_{frames}.wav")
+            with open(path, "wb") as f:
+                f.write(P.wav_bytes(pay, 44100, channels, name, extensible))
+            got, rate = wavio.load(path)
+            want = P.decode(pay, channels, name)
+            assert rate == 44100 and tuple(got.shape) == (channels, frames) == want.shape
+            assert np.array_equal(_bits(got.numpy()), _bits(want)), (name, channels, frames)
+            raw, meta = wavio.read_payload(path)
+            assert bytes(raw) == pay and (meta.num_channels, meta.num_frames) == (channels, frames)
+            assert (meta.format_tag, meta.bits_per_sample) == P.FORMATS[name][:2]
+
+
+@pytest.mark.parametrize("channels", [1, 2, 3])
+@pytest.mark.parametrize("frames", [1, 5, 4097])
+def test_restated_pcm16_encode_is_wavio_save(tmp_path, channels, frames):
+    from pix2pixhdaudiosr_amd.data import wavio
+    x = P.encode_input(frames, channels)
+    path = str(tmp_path / "a.wav")
+    wavio.save(path, torch.from_numpy(x), 48000)
+    data = open(path, "rb").read()
+    assert data[44:] == P.encode(x, "pcm16")
+
+
+def test_encode_input_holds_the_ties():
+    x = P.encode_input(4097, 1)[0]
+    ties = (np.arange(-40, 40) + 0.5) / 32768.0
+    assert np.isin(ties.astype(np.float32), x).all() and np.isinf(x).any() and not np.isnan(x).any()
+    q = np.frombuffer(P.encode(x[None], "pcm16"), dtype="<i2")
+    assert q.min() == -32768 and q.max() == 32767
+    # round half to even: (k + 1/2) / 32768 -> the even neighbour
+    t = np.frombuffer(P.encode(ties.astype(np.float32)[None], "pcm16"), dtype="<i2")
+    assert (t % 2 == 0).all() and np.abs(t - (np.arange(-40, 40) + 0.5)).max() == 0.5
+    assert np.frombuffer(P.encode(np.array([[np.nan, -np.nan]], dtype=np.float32), "pcm16"), dtype="<i2").tolist() == [0, 0]
+    assert P.encode(np.array([[np.nan]], dtype=np.float32), "pcm24") == b"\0\0\0"
+
+
+# ------------------------------------------------------------------------------------------
+# 2. the writer's encodings
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("encoding", ["pcm16", "pcm24", "float32"])
+@pytest.mark.parametrize("channels,frames", [(1, 5), (2, 7), (3, 4097), (1, 0)])
+def test_save_encodings_round_trip(tmp_path, encoding, channels, frames):
+    from pix2pixhdaudiosr_amd.data import wavio
+    x = P.encode_input(frames, channels, seed=3)
+    path = str(tmp_path / "a.wav")
+    wavio.save(path, torch.from_numpy(x), 22050, encoding=encoding)
+    tag, bits, _ = P.ENCODINGS[encoding]
+    meta = wavio.info(path)
+    assert (meta.format_tag, meta.bits_per_sample, meta.block_align, meta.num_channels, meta.num_frames, meta.sample_rate) == \
+        (tag, bits, channels * bits // 8, channels, frames, 22050)
+    data = open(path, "rb").read()
+    assert struct.unpack("<I", data[4:8])[0] == len(data) - 8 and len(data) % 2 == 0
+    assert data[44:44 + frames * meta.block_align] == P.encode(x, encoding)
+    back = wavio.load(path)[0].numpy()
+    assert back.shape == x.shape
+    if encoding == "float32":
+        assert np.array_equal(_bits(back), _bits(x))
+    else:
+        step = 2.0 ** -(bits - 1)
+        inside = np.abs(x) <= 1.0 - step
+        assert np.abs(back.astype(np.float64) - x.astype(np.float64))[inside].max(initial=0.0) <= step / 2
+        assert back.min(initial=0.0) >= -1.0 and back.max(initial=0.0) <= 1.0 - step
+
+
+def test_pcm24_is_exact_on_its_grid(tmp_path):
+    from pix2pixhdaudiosr_amd.data import wavio
+    k = np.concatenate([np.arange(-(1 << 23), -(1 << 23) + 50), np.arange(-50, 50), np.arange((1 << 23) - 50, 1 << 23),
+                        np.random.default_rng(0).integers(-(1 << 23), 1 << 23, 1000)])
+    x = (k.astype(np.float64) * 2.0 ** -23).astype(np.float32)[None]
+    path = str(tmp_path / "a.wav")
+    wavio.save(path, torch.from_numpy(x), 48000, encoding="pcm24")
+    assert np.array_equal(wavio.load(path)[0].numpy(), x)
+
+
+def test_default_save_writes_the_bytes_it_always_wrote(tmp_path):
+    from pix2pixhdaudiosr_amd.data import wavio
+    x = np.array([[0.0, 0.5, -1.0, 1.0, 1.5 / 32768, 2.5 / 32768, -0.5 / 32768], [0.25, -0.25, 2.0, -2.0, 0.1, -0.1, 32767 / 32768]],
+                 dtype=np.float32)
+    q = [0, 8192, 16384, -8192, -32768, 32767, 32767, -32768, 2, 3277, 2, -3277, 0, 32767]          # frame by frame, by hand
+    assert round(0.1 * 32768) == 3277
+    pcm = struct.pack("<14h", *q)
+    want = (b"RIFF" + struct.pack("<I", 36 + 28) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, 2, 16000, 16000 * 4, 4, 16) +
+            b"data" + struct.pack("<I", 28) + pcm)
+    for kw in ({}, {"encoding": "pcm16"}):
+        path = str(tmp_path / "a.wav")
+        wavio.save(path, torch.from_numpy(x), 16000, **kw)
+        assert open(path, "rb").read() == want
+    path2 = str(tmp_path / "b.wav")
+    wavio.write_payload(path2, pcm, 16000, 2, "pcm16")
+    assert open(path2, "rb").read() == want
+    with pytest.raises(ValueError, match="encoding"):
+        wavio.save(path, torch.from_numpy(x), 16000, encoding="pcm8")
+    with pytest.raises(ValueError, match="whole frames"):
+        wavio.write_payload(path2, pcm[:-1], 16000, 2, "pcm16")
+
+
+def test_read_payload_into_a_buffer_and_a_short_file(tmp_path):
+    from pix2pixhdaudiosr_amd.data import wavio
+    pay = P.payload("s24", 11, 3)
+    path = str(tmp_path / "a.wav")
+    with open(path, "wb") as f:
+        f.write(P.wav_bytes(pay, 8000, 3, "s24"))
+    buf = bytearray(200)
+    raw, meta = wavio.read_payload(path, into=buf)
+    assert bytes(raw) == pay and bytes(buf[:len(pay)]) == pay and meta.num_frames == 11
+    asked = []
+    raw, _ = wavio.read_payload(path, into=lambda n: asked.append(n) or bytearray(n))
+    assert asked == [99] and bytes(raw) == pay
+    with pytest.raises(ValueError, match="buffer"):
+        wavio.read_payload(path, into=bytearray(98))
+    # a data chunk that promises more than the file holds: the whole frames that are there, as load reads them
+    cut = str(tmp_path / "cut.wav")
+    with open(cut, "wb") as f:
+        f.write(P.wav_bytes(pay, 8000, 3, "s24")[:44 + 9 * 4 + 2])
+    raw, meta = wavio.read_payload(cut)
+    assert meta.num_frames == 4 and bytes(raw) == pay[:36]
+    bad = str(tmp_path / "bad.wav")
+    with open(bad, "wb") as f:
+        f.write(b"RIFF\x10\0\0\0WA")
+    with pytest.raises(ValueError):
+        wavio.read_payload(bad)
+
+
+# ------------------------------------------------------------------------------------------
+# 3. folders and the command line
+# ------------------------------------------------------------------------------------------
+def test_plan_folder(tmp_path):
+    from pix2pixhdaudiosr_amd.generate import check_paths, plan_folder
+    src, dst = tmp_path / "in", tmp_path / "out"
+    for rel in ("b.wav", "a.WAV", "sub/deep/c.wav", "sub/a.wav", "notes.txt", "sub/x.flac", "wav"):
+        p = src / rel
+        p.parent.mkdir(parents=True, exist_ok=True)
+        p.write_bytes(b"")
+    plan = plan_folder(str(src), str(dst))
+    rels = [r for r, _, _ in plan]
+    assert rels == sorted(rels) == ["a.WAV", "b.wav", os.path.join("sub", "a.wav"), os.path.join("sub", "deep", "c.wav")]
+    for rel, pin, pout in plan:
+        assert pin == os.path.join(str(src), rel) and pout == os.path.join(str(dst), rel)
+    assert not dst.exists()                                       # planning creates nothing
+    assert check_paths(str(src), str(dst)) is True and check_paths(str(src / "b.wav"), str(tmp_path / "o.wav")) is False
+    with pytest.raises(ValueError, match="directory"):
+        check_paths(str(src), str(src / "b.wav"))                 # folder in, file out
+    with pytest.raises(ValueError, match="directory"):
+        check_paths(str(src / "b.wav"), str(src))                 # file in, folder out
+    with pytest.raises(NotADirectoryError):
+        plan_folder(str(src / "b.wav"), str(dst))
+
+
+def test_select_channels():
+    from pix2pixhdaudiosr_amd.generate import select_channels
+    assert [select_channels(c, 6) for c in ("first", "all", 1, 4, 6, 9)] == [1, 6, 1, 4, 6, 6]
+    for bad in (0, -1, "both", 1.5, True, None):
+        with pytest.raises(ValueError):
+            select_channels(bad, 2)
+
+
+def test_new_cli_flags_and_old_argument_lists():
+    from pix2pixhdaudiosr_amd.generate import _parser
+    base = ["--input", "a.wav", "--output", "b.wav", "--load_pretrain", "ck"]
+    # the argument lists of test_generate_host.py::test_cli_parser_flags parse as before, with the new defaults
+    a = _parser().parse_args(base + ["--overlap", "0.1", "--batchSize", "2", "--which_epoch", "20", "--is_lr_input", "--no_graph", "--fp16"])
+    assert (a.overlap, a.batchSize, a.which_epoch, a.is_lr_input, a.no_graph, a.fp16, a.opt_file) == (0.1, 2, "20", True, True, True, None)
+    assert (a.channels, a.encoding, a.metrics_csv) == ("first", "pcm16", None)
+    b = _parser().parse_args(base + ["--reference_amplitude", "0"])
+    assert b.reference_amplitude == 0 and b.overlap == 0.25 and b.channels == "first"
+    c = _parser().parse_args(base + ["--channels", "all", "--encoding", "pcm24", "--metrics_csv", "m.csv"])
+    assert (c.channels, c.encoding, c.metrics_csv) == ("all", "pcm24", "m.csv")
+    assert _parser().parse_args(base + ["--channels", "3"]).channels == 3
+    assert _parser().parse_args(base + ["--encoding", "float32"]).encoding == "float32"
+    for bad in (["--channels", "0"], ["--channels", "both"], ["--encoding", "pcm8"]):
+        with pytest.raises(SystemExit):
+            _parser().parse_args(base + bad)
+    assert "--channels all" in _parser().format_help() or "all|first|N" in _parser().format_help()
+
+
+def test_metrics_rows_and_csv(tmp_path):
+    import csv
+    from pix2pixhdaudiosr_amd.generate import METRICS_COLUMNS, metrics_rows, write_metrics_csv
+    m = lambda k: (0.1 * k, 1.0 / 3 + k, 2.0 + k, 0, 0, 0, 0.7 * k)
+    records = [{"path": "a.wav", "out_frames": 10, "metrics": [m(1), m(2)]},
+               {"path": "bad.wav", "out_frames": 0, "metrics": None},
+               {"path": os.path.join("s", "b.wav"), "out_frames": 20, "metrics": [m(5)]}]
+    rows = metrics_rows(records)
+    assert [r[:3] for r in rows] == [("a.wav", 0, 10), ("a.wav", 1, 10), (os.path.join("s", "b.wav"), 0, 20), ("mean", "", "")]
+    assert metrics_rows([records[1]]) == []
+    path = str(tmp_path / "m.csv")
+    write_metrics_csv(path, records)
+    with open(path, newline="") as f:
+        got = list(csv.reader(f))
+    assert tuple(got[0]) == METRICS_COLUMNS == ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd")
+    body = [[float(v) for v in r[3:]] for r in got[1:]]
+    for k in range(4):
+        assert body[-1][k] == sum(r[k] for r in body[:-1]) / 3    # floats are written so that they read back exactly
+    assert body[0] == [m(1)[0], m(1)[1], m(1)[2], m(1)[6]]

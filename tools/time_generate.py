@@ -8,10 +8,16 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
   seams     RMS of the first difference at the joins (the first sample of every segment but the first) relative to the
             first-difference RMS of the whole output, at overlap 0 and 0.25, same weights and noise seed
 
-Without a mode every one of them runs in a process of its own under its own time limit, in that order, and the run stops at
+  folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
+            ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
+            file, what the package did before the device codec) and generate.SuperResolver.enhance_folder(channels='all')
+            on the stereo files; --reps repeats each, best and spread; log in --folder_log
+
+Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
 Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] [--reps 5] [--log profiles/time_generate.log]
+        python tools/time_generate.py folder [--files 8] [--folder_log profiles/time_generate_folder.log]
 """
 import argparse
 import os
@@ -97,6 +103,59 @@ def _time(torch, fn, reps):
     return best
 
 
+def run_folder(seconds, reps, files, log):
+    """Seconds of audio per second, files to files.  Audio counted: files * 2 channels * seconds for either way."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    sr = SuperResolver(model, opt)
+    rate = int(opt.hr_sampling_rate)
+    stereo = torch.cat([x, -0.7 * x.flip(-1)]).cpu()
+    audio = files * 2 * seconds
+    lines = ["# tools/time_generate.py folder: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25; %d stereo "
+             "PCM16 clips of %g s at 48 kHz (%g s of audio), files to files, %d repeats" % (files, seconds, audio, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        d_st, d_mono, d_out = (os.path.join(tmp, n) for n in ("stereo", "mono", "out"))
+        for d in (d_st, d_mono, d_out):
+            os.makedirs(d)
+        for i in range(files):
+            wavio.save(os.path.join(d_st, "clip%03d.wav" % i), stereo, rate)
+            for c in range(2):
+                wavio.save(os.path.join(d_mono, "clip%03d_%d.wav" % (i, c)), stereo[c:c + 1], rate)
+        monos = sorted(os.listdir(d_mono))
+
+        def host_loop():                                           # enhance_file as it was before the device codec, per channel-file
+            for name in monos:
+                raw, r = wavio.load(os.path.join(d_mono, name))
+                raw = raw[:1].cuda()
+                lr = lr_round_trip(raw, r, opt.lr_sampling_rate, opt.hr_sampling_rate)[..., :raw.shape[-1]]
+                wavio.save(os.path.join(d_out, name), sr.enhance_lr(lr), rate)
+
+        def folder():
+            recs = sr.enhance_folder(d_st, d_out, channels='all')
+            assert len(recs) == files and all(r['error'] is None and r['written_channels'] == 2 for r in recs)
+
+        for name, fn in (("host-codec loop over %d channel-files" % (2 * files), host_loop), ("enhance_folder, %d stereo files      " % files, folder)):
+            fn()                                                   # warm-up: capture, packed weights, pinned buffers, page cache
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            rates = sorted(audio / t for t in ts)
+            lines.append("%s  best %8.1f s of audio / s   spread %6.1f (worst %8.1f)   runs: %s"
+                         % (name, rates[-1], rates[-1] - rates[0], rates[0], " ".join("%.1f" % (audio / t) for t in ts)))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def run_mode(mode, seconds, reps):
     torch, model, opt, lr = _setup(seconds)
     from pix2pixhdaudiosr_amd.generate import SuperResolver, segment_plan
@@ -126,11 +185,15 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS))
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder"])
+    ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
+    ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
+    if a.mode == "folder":
+        return run_folder(a.seconds, a.reps, a.files, a.folder_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
