@@ -5,6 +5,7 @@ Internal activation format ("physical" tensors): contiguous NHWC ``[N, H, W, Cp]
 is plumbing: allocation through torch's caching allocator, pointers and the current stream handed to the
 C ABI, and ``torch.autograd.Function`` wrappers whose backward calls the HIP backward kernels.
 """
+import collections
 import ctypes as C
 import contextlib
 
@@ -483,7 +484,6 @@ class ConvSpec:
         # e4m3 twin; `emit_q8` = the InstanceNorm pass of this layer also writes the e4m3 twin of its output
         self.fp8 = False
         self.emit_q8 = False
-        self._q8_out = None
 
     def fp8_ok(self, N, H, W):
         d = self.desc(N, H, W, torch.bfloat16)
@@ -560,11 +560,78 @@ def _bsum_enabled():
     return os.environ.get("P2PHD_BSUM", "1") != "0"
 
 
+class _Handover:
+    """What couples one conv block's backward to its neighbours', kept on the block's ctx (`ctx.ho`): how many forward calls
+    read its output, a loss gradient parked on it, and what its consumer's input-gradient kernel already did of ITS backward
+    (the InstanceNorm sums, or the activation derivative).  A kernel's work is only usable when the gradient that arrives
+    IS the tensor that kernel wrote -- same storage, untouched since (`_same`).  Every take_* empties its slot, matched or
+    not: a marker must not outlive its backward pass."""
+    __slots__ = ("consumers", "_parked", "_sums", "_act_done")
+
+    def __init__(self):
+        self.consumers = 0            # forward calls that read the block's output (see _note_consumer)
+        self._parked = self._sums = self._act_done = None
+
+    @staticmethod
+    def _mark(t):
+        return t.data_ptr(), t._version
+
+    @staticmethod
+    def _same(g, mark):
+        return mark == (g.data_ptr(), g._version)
+
+    def park(self, da):
+        """A loss's gradient of the block's output (LossFn, park=True); several losses add up."""
+        self._parked = da if self._parked is None else self._parked + da
+
+    def take_parked(self):
+        da, self._parked = self._parked, None
+        return da
+
+    def leave_sums(self, bstats, gx):
+        """p2phd_conv_dgrad_bsum wrote gx and the per-(n, c) sums of the block's InstanceNorm backward."""
+        self._sums = (bstats, self._mark(gx))
+
+    def sums_left(self):
+        return self._sums is not None
+
+    def take_sums(self, g, shape):
+        s, self._sums = self._sums, None
+        return s[0] if s is not None and self._same(g, s[1]) and g.shape == shape else None
+
+    def leave_act_done(self, gx):
+        """p2phd_conv_dgrad_act wrote gx with the block's activation derivative applied."""
+        self._act_done = self._mark(gx)
+
+    def take_act_done(self, g, shape, has_plain_act):
+        """True when g already carries the block's activation derivative (`has_plain_act`: the block is conv + activation
+        without normalisation, the only kind whose consumer may do that)."""
+        mark, self._act_done = self._act_done, None
+        if mark is None:
+            return False
+        if not (self._same(g, mark) and g.shape == shape and has_plain_act):
+            raise _lib.P2PHDError("conv backward: the consumer's input-gradient kernel already applied this block's activation "
+                                  "derivative, but the gradient that arrived is not the tensor it wrote (a second consumer of "
+                                  "an `exclusive` chain?); rerun with P2PHD_BSUM=0")
+        return True
+
+
 def _note_consumer(t):
     gf = getattr(t, "grad_fn", None)
-    if gf is not None and hasattr(gf, "_p2phd_consumers"):
-        gf._p2phd_consumers += 1
+    if gf is not None and hasattr(gf, "ho"):
+        gf.ho.consumers += 1
     return gf
+
+
+def _sole_producer(src, view):
+    """(src.y, src.stats) cut to the view's sample range when `src` -- the conv block that produced the view's x, stated
+    `exclusive` by the caller -- has exactly one consumer and its output matches x in shape and dtype; else None."""
+    if src is None or src.ho.consumers != 1 or src.y is None:
+        return None
+    src_y = view.cut(src.y)
+    if src_y.shape != view.x.shape or src_y.dtype != view.x.dtype:
+        return None
+    return src_y, view.cut(src.stats)
 
 
 # Lazily normalised activations (round 4).  A conv block asked to `defer` returns its RAW conv output tagged with a LazyNorm
@@ -580,7 +647,9 @@ class LazyNorm:
         self.stats, self.act, self.channels, self.gen = stats, act, channels, gen
 
 
-_LAST_LAZY = [None]        # hand-over from ConvBlockFn.forward (which cannot tag its own output) to conv_block
+# (LazyNorm, e4m3 twin) of the output ConvBlockFn.forward just made, or None: a Function cannot tag its own output, so
+# conv_block drains this into out._p2phd_lazy / out._p2phd_q8
+_FWD_TAGS = [None]
 
 
 def lazy_static_ok(spec):
@@ -637,11 +706,11 @@ class ConvBlockFn(torch.autograd.Function):
                                         ptr(ws), stream_ptr()), "conv_fwd_lazy")
         else:
             check(L.p2phd_conv_fwd(C.byref(d), ptr(x), ptr(wp), ptr(b), fused_act, ptr(y), ptr(stats), ptr(ws), stream_ptr()), "conv_fwd")
-        _LAST_LAZY[0] = None
+        _FWD_TAGS[0] = None
         if spec.norm and defer and residual is None and not spec.emit_q8:
             # the consumer normalises on load: hand out the raw output, tagged by conv_block
             out = y
-            _LAST_LAZY[0] = LazyNorm(stats, spec.act, spec.cout, arena_generation(x.device))
+            _FWD_TAGS[0] = (LazyNorm(stats, spec.act, spec.cout, arena_generation(x.device)), None)
         elif spec.norm:
             if _STATS_TRACE[0] is not None:
                 _STATS_TRACE[0].append((spec, stats.detach().clone(), Ho * Wo))
@@ -651,7 +720,7 @@ class ConvBlockFn(torch.autograd.Function):
                 out8 = empty(tuple(y.shape), torch.uint8, y.device)
                 check(L.p2phd_instnorm_act_fwd_q8(d.dtype, ptr(y), ptr(stats), ptr(res), ptr(out), ptr(out8), N, Ho * Wo, spec.cout,
                                                   IN_EPS, spec.act, stream_ptr()), "instnorm_act_fwd_q8")
-                spec._q8_out = out8
+                _FWD_TAGS[0] = (None, out8)                        # e4m3 twin of this output for the next layer's fp8 forward
             else:
                 check(L.p2phd_instnorm_act_fwd(d.dtype, ptr(y), ptr(stats), ptr(res), ptr(out), N, Ho * Wo, spec.cout, IN_EPS,
                                                spec.act, stream_ptr()), "instnorm_act_fwd")
@@ -669,192 +738,225 @@ class ConvBlockFn(torch.autograd.Function):
         ctx.x_lazy = lazy_in                                       # x is RAW: the weight gradient normalises it on load too
         ctx.link = link
         ctx.arena_gen = arena_generation(x.device) if spec.norm else 0
-        ctx._p2phd_consumers = 0                                   # forward calls that read `out` (see _note_consumer)
-        ctx._bs = None                                             # (bstats, data_ptr, version) left by the consumer's dgrad
-        ctx._parked = None                                         # gradient of `out` parked by a loss (LossFn, park=True)
-        ctx._dy_done = None                                        # (data_ptr, version) of a gradient that already carries act' 
-        ctx.src = src if (src is not None and hasattr(src, "_p2phd_consumers") and getattr(src, "spec", None) is not None) else None
+        ctx.ho = _Handover()
+        ctx.src = src if hasattr(src, "ho") else None              # the producer of x, when it is a conv block
         return out
 
     @staticmethod
     def backward(ctx, g):
-        spec, d = ctx.spec, ctx.d
-        x, y, stats, weight = ctx.x, ctx.y, ctx.stats, ctx.weight
-        L = lib_for(y.dtype)
-        _check_arena(ctx, y.device)
-        g = g.contiguous()
-        if g.dtype != y.dtype:
-            g = g.to(y.dtype)
-        rng = _bwd_range(d.N, ctx.pair)
-        x_full = x
-        if rng is not None:
-            # sample-range backward (see backward_on_samples): everything below runs on the sub-batch views
-            lo, hi = rng
-            x, y, g = x[lo:hi], y[lo:hi], g[lo:hi]
-            stats = None if stats is None else stats[lo:hi]
-            d = spec.desc(hi - lo, x.shape[1], x.shape[2], x.dtype, d.w_layout)
-        parked, ctx._parked = ctx._parked, None
-        dy_done, ctx._dy_done = ctx._dy_done, None                 # (consumed once: a marker must not outlive its backward pass)
-        # the consumer's input-gradient kernel (p2phd_conv_dgrad_act) may have applied this block's activation derivative
-        # to g already; that is only usable when g IS the tensor it wrote (same storage, untouched since)
-        carries_act = False
-        if dy_done is not None:
-            if not (dy_done == (g.data_ptr(), g._version) and g.shape == y.shape and not spec.norm and spec.act != ACT_NONE):
-                raise _lib.P2PHDError("conv backward: the consumer's input-gradient kernel already applied this block's activation "
-                                      "derivative, but the gradient that arrived is not the tensor it wrote (a second consumer of "
-                                      "an `exclusive` chain?); rerun with P2PHD_BSUM=0")
-            carries_act = True
-        if parked is not None:
-            # a loss parked its gradient of this block's output for the consumer's input-gradient kernel to add, and that
-            # kernel did not take it (it ran first, or does not exist in this backward pass): add it here
-            parked = parked.to(g.dtype)
-            if carries_act:
-                # g is already dL/d(pre-activation) of the conv path; the parked part is still dL/d(output): give it act' alone
-                pk = empty_like(y)
-                check(L.p2phd_act_bwd(d.dtype, ptr(parked.contiguous()), ptr(y), ptr(pk), y.numel(), spec.act, stream_ptr()), "act_bwd")
-                parked = pk
-            g = g + parked
-            ctx._bs = None
-        N, Ho, Wo, Cp_out = y.shape
-        need_w = ((ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) and not ctx.skip_wgrad
-                  and id(weight) not in _BWD_SKIP_WGRAD_IDS)
-        # Parameters owned by FlatAdam carry their gradient as a view of its flat buffer: the kernels then add into it
-        # directly (p2phd_*_acc) and autograd gets None, which saves a temporary and a `grad += new` launch per parameter.
-        direct = need_w and _direct_grad(weight) and (not ctx.has_bias or _direct_grad(ctx.bias))
-        # Lazily zeroed gradients (FlatAdam.zero_grad(lazy=True)): a parameter marked fresh holds stale values; its first
-        # gradient of the step OVERWRITES them (the non-accumulating entry points), later ones add -- no 410 MB memset per step
-        # (biases are zeroed eagerly by that zero_grad -- one launch for all of them -- and always accumulate)
-        fresh = need_w and getattr(weight, "_p2phd_fresh", False)
-        if fresh and not direct and weight.grad is not None:
-            weight.grad.zero_()
-        acc = direct and not fresh                                 # weight gradient: add (else overwrite)
-        acc_b = direct                                             # bias gradient: always add into the flat buffer
-        if need_w:
-            weight._p2phd_fresh = False
-        gb = None
-        if need_w and ctx.has_bias:
-            gb = ctx.bias.grad if direct else empty((spec.cout,), torch.float32, y.device)
-        gb_done = False
-        rx = None                                                  # reflection extras behind dy (p2phd_conv_dgrad_rx)
-        if spec.norm:
-            bs, ctx._bs = ctx._bs, None
-            want_gx = ctx.needs_input_grad[0] and id(spec) not in _BWD_SKIP_DGRAD_SPECS
-            n_rx = L.p2phd_conv_reflect_extras_elems(C.byref(d)) if (spec.pad_mode == 1 and want_gx and bs is None) else 0
-            if n_rx:
-                # residual trunk: the kernel that writes dy appends the pair-sum rows / columns its input-gradient GEMM reads
-                buf = empty((y.numel() + n_rx,), y.dtype, y.device)
-                dy, rx = buf[:y.numel()].view(y.shape), buf[y.numel():]
-                check(L.p2phd_instnorm_act_bwd_rx(d.dtype, ptr(g), ptr(y), ptr(stats), ptr(dy), ptr(gb), 1 if acc_b else 0, N, Ho, Wo,
-                                                  spec.cout, IN_EPS, spec.act, ptr(rx), stream_ptr()), "instnorm_act_bwd_rx")
-            elif bs is not None and g.data_ptr() == bs[1] and g._version == bs[2] and g.shape == y.shape:
-                # the consumer's input-gradient kernel already summed (g', g' * yhat): apply pass only
-                dy = empty_like(y)
-                check(L.p2phd_instnorm_act_bwd_apply(d.dtype, ptr(g), ptr(y), ptr(stats), ptr(bs[0]), ptr(dy), ptr(gb), 1 if acc_b else 0,
-                                                     N, Ho * Wo, spec.cout, IN_EPS, spec.act, stream_ptr()), "instnorm_act_bwd_apply")
-                _BSUM_CALLS[0] += 1
-            else:
-                dy = empty_like(y)
-                bstats = empty((N, Cp_out, 2), torch.float32, y.device)
-                # the bias gradient (column sums of dy) rides on the apply pass
-                bwd = L.p2phd_instnorm_act_bwd_acc if acc_b else L.p2phd_instnorm_act_bwd
-                check(bwd(d.dtype, ptr(g), ptr(y), ptr(stats), ptr(bstats), ptr(dy), ptr(gb), N, Ho * Wo, spec.cout, IN_EPS, spec.act,
-                          stream_ptr()), "instnorm_act_bwd")
-            gb_done = gb is not None
-        elif carries_act:
-            dy = g                                                 # the consumer's input-gradient kernel applied act' already
-            _BSUM_CALLS[0] += 1
-        elif spec.act != ACT_NONE:
-            dy = empty_like(y)
-            if gb is not None:                                     # bias gradient rides on the activation-backward pass
-                check(L.p2phd_act_bwd_db(d.dtype, ptr(g), ptr(y), ptr(dy), N * Ho * Wo, spec.cout, spec.act, ptr(gb),
-                                         1 if acc_b else 0, stream_ptr()), "act_bwd_db")
-                gb_done = True
-            else:
-                check(L.p2phd_act_bwd(d.dtype, ptr(g), ptr(y), ptr(dy), y.numel(), spec.act, stream_ptr()), "act_bwd")
-        else:
-            dy = g
-        gx = gw = None
-        if need_w:
-            gw = weight.grad if direct else empty(tuple(weight.shape), torch.float32, y.device)
-            wgrad = L.p2phd_conv_wgrad_acc if acc else L.p2phd_conv_wgrad
-            dwd = d if w_layout(gw) == d.w_layout else spec.desc(d.N, d.H, d.W, y.dtype, w_layout(gw))   # layout of what is WRITTEN
-            ws = workspace(L.p2phd_conv_wgrad_workspace_bytes(C.byref(dwd)), y.device)
-            if ctx.x_lazy is not None:
-                lz = ctx.x_lazy
-                if lz.gen and lz.gen != (_ARENA.get(str(y.device)) or {}).get("gen", 0):
-                    raise _lib.P2PHDError("the InstanceNorm statistics of this layer's lazily normalised input were recycled: a new "
-                                          "training-step forward started before this backward ran")
-                if rng is not None:
-                    raise _lib.P2PHDError("sample-range backward through a lazily normalised input is not supported")
-                check(L.p2phd_conv_wgrad_lazy(C.byref(dwd), ptr(x), ptr(lz.stats), lz.act, IN_EPS, ptr(dy), ptr(gw),
-                                              None if gb_done else ptr(gb), 1 if acc else 0, ptr(ws), stream_ptr()), "conv_wgrad_lazy")
-            else:
-                check(wgrad(C.byref(dwd), ptr(x), ptr(dy), ptr(gw), None if gb_done else ptr(gb), ptr(ws), stream_ptr()), "conv_wgrad")
-            if direct:
-                gw = gb = None
-        gx_full = None
-        if ctx.needs_input_grad[0] and id(spec) not in _BWD_SKIP_DGRAD_SPECS:
-            wp = spec.packed(weight, 1, d)
-            gx_full = empty_like(x_full)
-            gx = gx_full if rng is None else gx_full[rng[0]:rng[1]]
-            if rng is not None:
-                _zero_unused(gx_full, rng)
-            wsb = L.p2phd_conv_dgrad_workspace_bytes(C.byref(d))
-            ws = workspace(wsb, y.device) if wsb else None
-            # first conv of a residual block: the skip gradient parked by the block's second conv is added inside the
-            # dgrad (epilogue / reflect fold) instead of by a separate autograd add
-            addend = None
-            if ctx.link is not None and ctx.link.role_of(ctx) == "a":
-                addend = ctx.link.take()
-            if ctx.in_link is not None:
-                pk = ctx.in_link.take()                            # gradient of x through the pooling branch (PoolLink)
-                if pk is not None:
-                    pk = pk if rng is None else pk[rng[0]:rng[1]]
-                    addend = pk if addend is None else addend + pk
-            src = ctx.src
-            if src is not None and src._parked is not None and src._p2phd_consumers == 1:
-                # feature-matching gradient of x parked by the loss: summed inside this kernel instead of by autograd
-                pk, src._parked = src._parked, None
-                if pk.shape != gx.shape:
-                    raise _lib.P2PHDError(f"conv backward: a parked loss gradient of shape {tuple(pk.shape)} meets an input gradient of "
-                                          f"shape {tuple(gx.shape)} (a half-batch loss needs backward_on_samples around this pass)")
-                addend = pk if addend is None else addend + pk
-            src_y = src_stats = None
-            if src is not None and src.y is not None:
-                src_y = src.y if rng is None else src.y[rng[0]:rng[1]]
-                if src.stats is not None:
-                    src_stats = src.stats if rng is None else src.stats[rng[0]:rng[1]]
-            fuse = (src is not None and src.spec.norm and src._p2phd_consumers == 1 and _bsum_enabled() and src_y is not None
-                    and src_y.shape == x.shape and src_y.dtype == x.dtype and src.spec.act in (ACT_NONE, ACT_RELU, ACT_LRELU)
-                    and L.p2phd_instnorm_act_bwd_two_pass(d.dtype, x.shape[0], x.shape[1] * x.shape[2], spec.cin)
-                    and (L.p2phd_conv_dgrad_bsum_ok(C.byref(d)) if _BSUM_ALWAYS else L.p2phd_conv_dgrad_bsum_pays(C.byref(d))))
-            if fuse:
-                _check_arena(src, y.device)
-                bst = empty((x.shape[0], x.shape[3], 2), torch.float32, y.device)
-                wsf = workspace(max(L.p2phd_conv_dgrad_bsum_workspace_bytes(C.byref(d)), 256), y.device)
-                check(L.p2phd_conv_dgrad_bsum(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(src_y), ptr(src_stats),
-                                              src.spec.act, IN_EPS, ptr(bst), ptr(wsf), stream_ptr()), "conv_dgrad_bsum")
-                src._bs = (bst, gx.data_ptr(), gx._version)
-            elif (src is not None and not src.spec.norm and src.spec.act in (ACT_RELU, ACT_LRELU) and src._p2phd_consumers == 1
-                  and _bsum_enabled() and src_y is not None and src_y.shape == x.shape and src_y.dtype == x.dtype
-                  and L.p2phd_conv_dgrad_bsum_ok(C.byref(d))):
-                # producer = Conv + (Leaky)ReLU without normalisation: its activation derivative is applied to gx here
-                wsf = workspace(max(L.p2phd_conv_dgrad_bsum_workspace_bytes(C.byref(d)), 256), y.device)
-                check(L.p2phd_conv_dgrad_act(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(src_y), src.spec.act, ptr(wsf),
-                                             stream_ptr()), "conv_dgrad_act")
-                src._dy_done = (gx.data_ptr(), gx._version)
-            elif rx is not None:
-                check(L.p2phd_conv_dgrad_rx(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), stream_ptr()), "conv_dgrad_rx")
-            else:
-                check(L.p2phd_conv_dgrad(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(ws), stream_ptr()), "conv_dgrad")
+        _check_arena(ctx, ctx.y.device)
+        v = _BwdView(ctx, g)
+        g, carries_act = _arrived_grad(ctx, v)
+        t = _grad_targets(ctx, v)
+        dy, rx, gb_done = _output_grad(ctx, v, t, g, carries_act)
+        gw, gb = _weight_grad(ctx, v, t, dy, gb_done)
+        gx_full = _input_grad(ctx, v, dy, rx)
         if _BWD_TRACE[0] is not None:
-            _BWD_TRACE[0].append((spec, g.detach().clone(), dy.detach().clone(), None if gx is None else gx.detach().clone()))
+            _BWD_TRACE[0].append((ctx.spec, g.detach().clone(), dy.detach().clone(),
+                                  None if gx_full is None else v.cut(gx_full).detach().clone()))
         gres = g if (ctx.has_res and ctx.needs_input_grad[3]) else None
-        if gres is not None and rng is not None:
+        if gres is not None and v.rng is not None:
             raise _lib.P2PHDError("sample-range backward through a residual block is not supported")
         if gres is not None and ctx.link is not None and ctx.link.park(gres, ctx):
             gres = None
         return gx_full, gw, gb, gres, None, None, None, None
+
+
+# The stages of ConvBlockFn.backward, in the order they run.  Each allocates and launches exactly what it names; their order
+# is fixed (a captured step records allocation addresses, and runs are compared bit for bit per stream).
+
+class _BwdView:
+    """The tensors one backward pass works on: x, y, g, stats and the descriptor, cut to the sample range `rng` when the pass
+    is restricted to one (backward_on_samples; NHWC is sample-major, so the cuts are contiguous views)."""
+
+    def __init__(self, ctx, g):
+        y = ctx.y
+        g = g.contiguous()
+        if g.dtype != y.dtype:
+            g = g.to(y.dtype)
+        self.L = lib_for(y.dtype)
+        self.rng = _bwd_range(ctx.d.N, ctx.pair)
+        self.x_full = ctx.x
+        self.x, self.y, self.g, self.stats = self.cut(ctx.x), self.cut(y), self.cut(g), self.cut(ctx.stats)
+        self.d = ctx.d
+        if self.rng is not None:
+            self.d = ctx.spec.desc(self.x.shape[0], self.x.shape[1], self.x.shape[2], self.x.dtype, ctx.d.w_layout)
+
+    def cut(self, t):
+        return t if (t is None or self.rng is None) else t[self.rng[0]:self.rng[1]]
+
+
+def _arrived_grad(ctx, v):
+    """The gradient of the block's output, complete: what autograd delivered plus what a loss parked on the block and the
+    consumer's input-gradient kernel did not take (it ran first, or is not part of this backward pass).  Returns
+    (g, carries_act); carries_act: the consumer's kernel (p2phd_conv_dgrad_act) applied this block's activation derivative
+    to g already."""
+    spec, y, g = ctx.spec, v.y, v.g
+    parked = ctx.ho.take_parked()
+    carries_act = ctx.ho.take_act_done(g, y.shape, not spec.norm and spec.act != ACT_NONE)
+    if parked is not None:
+        parked = parked.to(g.dtype)
+        if carries_act:
+            # g is already dL/d(pre-activation) of the conv path; the parked part is still dL/d(output): give it act' alone
+            pk = empty_like(y)
+            check(v.L.p2phd_act_bwd(v.d.dtype, ptr(parked.contiguous()), ptr(y), ptr(pk), y.numel(), spec.act, stream_ptr()), "act_bwd")
+            parked = pk
+        g = g + parked
+        ctx.ho.take_sums(g, y.shape)                               # (dropped: sums of the conv path alone no longer describe g)
+    return g, carries_act
+
+
+_GradTargets = collections.namedtuple("_GradTargets", "need_w direct acc acc_b gw gb")
+
+
+def _grad_targets(ctx, v):
+    """Where the weight and bias gradients go.  `direct`: into the parameter's own .grad (then autograd gets None); `acc` /
+    `acc_b`: the kernels add to what is there (else overwrite).  gw / gb are the tensors to write; gw is None when the
+    weight-gradient stage is to allocate it."""
+    weight = ctx.weight
+    need_w = ((ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) and not ctx.skip_wgrad
+              and id(weight) not in _BWD_SKIP_WGRAD_IDS)
+    # Parameters owned by FlatAdam carry their gradient as a view of its flat buffer: the kernels then add into it
+    # directly (p2phd_*_acc) and autograd gets None, which saves a temporary and a `grad += new` launch per parameter.
+    direct = need_w and _direct_grad(weight) and (not ctx.has_bias or _direct_grad(ctx.bias))
+    # Lazily zeroed gradients (FlatAdam.zero_grad(lazy=True)): a parameter marked fresh holds stale values; its first
+    # gradient of the step OVERWRITES them (the non-accumulating entry points), later ones add -- no 410 MB memset per step
+    # (biases are zeroed eagerly by that zero_grad -- one launch for all of them -- and always accumulate)
+    fresh = need_w and getattr(weight, "_p2phd_fresh", False)
+    if fresh and not direct and weight.grad is not None:
+        weight.grad.zero_()
+    if need_w:
+        weight._p2phd_fresh = False
+    gb = None
+    if need_w and ctx.has_bias:
+        gb = ctx.bias.grad if direct else empty((ctx.spec.cout,), torch.float32, v.y.device)
+    return _GradTargets(need_w, direct, direct and not fresh, direct, weight.grad if direct else None, gb)
+
+
+def _output_grad(ctx, v, t, g, carries_act):
+    """g -> dy, the gradient of the raw conv output, by one of five ways.  Returns (dy, rx, gb_done); rx: the reflection
+    extras behind dy (p2phd_conv_dgrad_rx), gb_done: the bias gradient rode on this pass."""
+    spec, d, y, L = ctx.spec, v.d, v.y, v.L
+    N, Ho, Wo, Cp_out = y.shape
+    gb, acc_b = t.gb, 1 if t.acc_b else 0
+    if spec.norm:
+        want_gx = ctx.needs_input_grad[0] and id(spec) not in _BWD_SKIP_DGRAD_SPECS
+        n_rx = L.p2phd_conv_reflect_extras_elems(C.byref(d)) if (spec.pad_mode == 1 and want_gx and not ctx.ho.sums_left()) else 0
+        bs = ctx.ho.take_sums(g, y.shape)
+        if n_rx:
+            # residual trunk: the kernel that writes dy appends the pair-sum rows / columns its input-gradient GEMM reads
+            buf = empty((y.numel() + n_rx,), y.dtype, y.device)
+            dy, rx = buf[:y.numel()].view(y.shape), buf[y.numel():]
+            check(L.p2phd_instnorm_act_bwd_rx(d.dtype, ptr(g), ptr(y), ptr(v.stats), ptr(dy), ptr(gb), acc_b, N, Ho, Wo,
+                                              spec.cout, IN_EPS, spec.act, ptr(rx), stream_ptr()), "instnorm_act_bwd_rx")
+            return dy, rx, gb is not None
+        dy = empty_like(y)
+        if bs is not None:
+            # the consumer's input-gradient kernel already summed (g', g' * yhat): apply pass only
+            check(L.p2phd_instnorm_act_bwd_apply(d.dtype, ptr(g), ptr(y), ptr(v.stats), ptr(bs), ptr(dy), ptr(gb), acc_b,
+                                                 N, Ho * Wo, spec.cout, IN_EPS, spec.act, stream_ptr()), "instnorm_act_bwd_apply")
+            _BSUM_CALLS[0] += 1
+        else:
+            bstats = empty((N, Cp_out, 2), torch.float32, y.device)
+            # the bias gradient (column sums of dy) rides on the apply pass
+            bwd = L.p2phd_instnorm_act_bwd_acc if acc_b else L.p2phd_instnorm_act_bwd
+            check(bwd(d.dtype, ptr(g), ptr(y), ptr(v.stats), ptr(bstats), ptr(dy), ptr(gb), N, Ho * Wo, spec.cout, IN_EPS, spec.act,
+                      stream_ptr()), "instnorm_act_bwd")
+        return dy, None, gb is not None
+    if carries_act:
+        _BSUM_CALLS[0] += 1
+        return g, None, False
+    if spec.act == ACT_NONE:
+        return g, None, False
+    dy = empty_like(y)
+    if gb is not None:                                             # bias gradient rides on the activation-backward pass
+        check(L.p2phd_act_bwd_db(d.dtype, ptr(g), ptr(y), ptr(dy), N * Ho * Wo, spec.cout, spec.act, ptr(gb), acc_b,
+                                 stream_ptr()), "act_bwd_db")
+        return dy, None, True
+    check(L.p2phd_act_bwd(d.dtype, ptr(g), ptr(y), ptr(dy), y.numel(), spec.act, stream_ptr()), "act_bwd")
+    return dy, None, False
+
+
+def _weight_grad(ctx, v, t, dy, gb_done):
+    """Weight (and, unless it rode on the output-gradient pass, bias) gradient.  Returns what autograd gets: (gw, gb), or
+    (None, None) when the kernels wrote the parameters' own .grad or no weight gradient is wanted."""
+    if not t.need_w:
+        return None, None
+    spec, d, y, L = ctx.spec, v.d, v.y, v.L
+    gw = t.gw if t.direct else empty(tuple(ctx.weight.shape), torch.float32, y.device)
+    dwd = d if w_layout(gw) == d.w_layout else spec.desc(d.N, d.H, d.W, y.dtype, w_layout(gw))   # layout of what is WRITTEN
+    ws = workspace(L.p2phd_conv_wgrad_workspace_bytes(C.byref(dwd)), y.device)
+    gb = None if gb_done else t.gb
+    lz = ctx.x_lazy
+    if lz is not None:
+        if lz.gen and lz.gen != (_ARENA.get(str(y.device)) or {}).get("gen", 0):
+            raise _lib.P2PHDError("the InstanceNorm statistics of this layer's lazily normalised input were recycled: a new "
+                                  "training-step forward started before this backward ran")
+        if v.rng is not None:
+            raise _lib.P2PHDError("sample-range backward through a lazily normalised input is not supported")
+        check(L.p2phd_conv_wgrad_lazy(C.byref(dwd), ptr(v.x), ptr(lz.stats), lz.act, IN_EPS, ptr(dy), ptr(gw), ptr(gb),
+                                      1 if t.acc else 0, ptr(ws), stream_ptr()), "conv_wgrad_lazy")
+    else:
+        wgrad = L.p2phd_conv_wgrad_acc if t.acc else L.p2phd_conv_wgrad
+        check(wgrad(C.byref(dwd), ptr(v.x), ptr(dy), ptr(gw), ptr(gb), ptr(ws), stream_ptr()), "conv_wgrad")
+    return (None, None) if t.direct else (gw, t.gb)
+
+
+def _input_grad(ctx, v, dy, rx):
+    """Input gradient, whole-batch tensor (written on the view's sample range only), or None when it is not wanted.  The
+    kernel adds what others parked for x (`addend`) and, for a sole conv-block producer of x, does the first part of that
+    block's backward on the way, leaving the hand-over on the producer."""
+    spec, d, x, y, L = ctx.spec, v.d, v.x, v.y, v.L
+    if not ctx.needs_input_grad[0] or id(spec) in _BWD_SKIP_DGRAD_SPECS:
+        return None
+    wp = spec.packed(ctx.weight, 1, d)
+    gx_full = empty_like(v.x_full)
+    gx = v.cut(gx_full)
+    if v.rng is not None:
+        _zero_unused(gx_full, v.rng)
+    wsb = L.p2phd_conv_dgrad_workspace_bytes(C.byref(d))
+    ws = workspace(wsb, y.device) if wsb else None
+    # first conv of a residual block: the skip gradient parked by the block's second conv is added inside the
+    # dgrad (epilogue / reflect fold) instead of by a separate autograd add
+    addend = None
+    if ctx.link is not None and ctx.link.role_of(ctx) == "a":
+        addend = ctx.link.take()
+    if ctx.in_link is not None:
+        pk = v.cut(ctx.in_link.take())                             # gradient of x through the pooling branch (PoolLink)
+        if pk is not None:
+            addend = pk if addend is None else addend + pk
+    src = ctx.src
+    if src is not None and src.ho.consumers == 1:
+        # feature-matching gradient of x parked by the loss: summed inside this kernel instead of by autograd
+        pk = src.ho.take_parked()
+        if pk is not None:
+            if pk.shape != gx.shape:
+                raise _lib.P2PHDError(f"conv backward: a parked loss gradient of shape {tuple(pk.shape)} meets an input gradient of "
+                                      f"shape {tuple(gx.shape)} (a half-batch loss needs backward_on_samples around this pass)")
+            addend = pk if addend is None else addend + pk
+    prod = _sole_producer(src, v) if _bsum_enabled() else None
+    if (prod is not None and src.spec.norm and src.spec.act in (ACT_NONE, ACT_RELU, ACT_LRELU)
+            and L.p2phd_instnorm_act_bwd_two_pass(d.dtype, x.shape[0], x.shape[1] * x.shape[2], spec.cin)
+            and (L.p2phd_conv_dgrad_bsum_ok(C.byref(d)) if _BSUM_ALWAYS else L.p2phd_conv_dgrad_bsum_pays(C.byref(d)))):
+        # producer = Conv + InstanceNorm (+ activation): the kernel also leaves the sums its backward starts with
+        _check_arena(src, y.device)
+        bst = empty((x.shape[0], x.shape[3], 2), torch.float32, y.device)
+        wsf = workspace(max(L.p2phd_conv_dgrad_bsum_workspace_bytes(C.byref(d)), 256), y.device)
+        check(L.p2phd_conv_dgrad_bsum(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(prod[0]), ptr(prod[1]),
+                                      src.spec.act, IN_EPS, ptr(bst), ptr(wsf), stream_ptr()), "conv_dgrad_bsum")
+        src.ho.leave_sums(bst, gx)
+    elif (prod is not None and not src.spec.norm and src.spec.act in (ACT_RELU, ACT_LRELU)
+          and L.p2phd_conv_dgrad_bsum_ok(C.byref(d))):
+        # producer = Conv + (Leaky)ReLU without normalisation: its activation derivative is applied to gx here
+        wsf = workspace(max(L.p2phd_conv_dgrad_bsum_workspace_bytes(C.byref(d)), 256), y.device)
+        check(L.p2phd_conv_dgrad_act(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(prod[0]), src.spec.act, ptr(wsf),
+                                     stream_ptr()), "conv_dgrad_act")
+        src.ho.leave_act_done(gx)
+    elif rx is not None:
+        check(L.p2phd_conv_dgrad_rx(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), stream_ptr()), "conv_dgrad_rx")
+    else:
+        check(L.p2phd_conv_dgrad(C.byref(d), ptr(dy), ptr(wp), ptr(addend), ptr(gx), ptr(ws), stream_ptr()), "conv_dgrad")
+    return gx_full
 
 
 class SkipLink:
@@ -890,10 +992,13 @@ def conv_block(x, weight, bias, spec, residual=None, link=None, exclusive=False,
     if pool_link is not None:
         pool_link.conv_spec = spec if (x.requires_grad and torch.is_grad_enabled()) else None
     out = _tag_pair(ConvBlockFn.apply(x, weight, bias, residual, spec, link, exclusive, defer), x)
-    if _LAST_LAZY[0] is not None:
-        out._p2phd_lazy, _LAST_LAZY[0] = _LAST_LAZY[0], None
-    if spec._q8_out is not None:                                    # e4m3 twin of this output for the next layer's fp8 forward
-        out._p2phd_q8, spec._q8_out = spec._q8_out, None
+    tags, _FWD_TAGS[0] = _FWD_TAGS[0], None
+    if tags is not None:
+        lazy, q8 = tags
+        if lazy is not None:
+            out._p2phd_lazy = lazy
+        if q8 is not None:
+            out._p2phd_q8 = q8
     return out
 
 
@@ -945,11 +1050,10 @@ class AvgPoolFn(torch.autograd.Function):
         dx = empty((N, H, W, Cp), g.dtype, g.device)
         rng = _bwd_range(N, ctx.pair)
         if rng is not None:                                        # sample-range backward (backward_on_samples)
-            lo, hi = rng
             _zero_unused(dx, rng)
-            check(lib_for(g.dtype).p2phd_avgpool3s2_bwd(dt_code(g.dtype), ptr(g[lo:hi]), ptr(dx[lo:hi]), hi - lo, H, W, channels, stream_ptr()), "avgpool_bwd")
-        else:
-            check(lib_for(g.dtype).p2phd_avgpool3s2_bwd(dt_code(g.dtype), ptr(g), ptr(dx), N, H, W, channels, stream_ptr()), "avgpool_bwd")
+        lo, hi = rng or (0, N)
+        check(lib_for(g.dtype).p2phd_avgpool3s2_bwd(dt_code(g.dtype), ptr(g[lo:hi]), ptr(dx[lo:hi]), hi - lo, H, W, channels,
+                                                    stream_ptr()), "avgpool_bwd")
         link = ctx.link
         if (link is not None and not link.taken and link.g is None and link.conv_spec is not None
                 and id(link.conv_spec) not in _BWD_SKIP_DGRAD_SPECS):
@@ -974,7 +1078,7 @@ class LossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, kind, target, coeff, channels, park=False, rows=None, into=None):
         gf = getattr(a, "grad_fn", None)
-        ctx.park_src = gf if (park and gf is not None and hasattr(gf, "_p2phd_consumers") and hasattr(gf, "_parked")) else None
+        ctx.park_src = gf if (park and hasattr(gf, "ho")) else None
         if ctx.park_src is None:
             _note_consumer(a)
         a = phys(_no_lazy(a, "loss"), "loss input")
@@ -1012,8 +1116,7 @@ class LossFn(torch.autograd.Function):
         if parked:
             # hand the gradient to the block that produced `a`: its exclusive consumer adds it inside its input-gradient
             # kernel (or the block itself does, if that kernel is not part of this backward pass); autograd gets nothing
-            src = ctx.park_src
-            src._parked = da if src._parked is None else src._parked + da
+            ctx.park_src.ho.park(da)
             return None, None, None, None, None, None, None, None, None
         return (da if da_full is None else da_full), None, None, None, None, None, None, None, None
 
@@ -1047,15 +1150,21 @@ class LossAcc:
         self.terms.append(LossFn.apply(a_phys, b_phys.detach(), 1, 0.0, coeff, channels, park, None, self.slot))
 
     def l1_halves(self, t_phys, channels, coeff=1.0, park=False):
-        n = t_phys.shape[0]
-        if n % 2:
-            raise _lib.P2PHDError("l1_halves_loss: the batch must hold two equal halves")
-        self.terms.append(LossFn.apply(t_phys, t_phys.detach()[:n // 2], 1, 0.0, coeff, channels, park, (n // 2, n), self.slot))
+        first, rows = _halves(t_phys)
+        self.terms.append(LossFn.apply(t_phys, first, 1, 0.0, coeff, channels, park, rows, self.slot))
 
     def total(self):
         if not self.terms:
             return 0
         return LossSum.apply(self.slot, *self.terms)
+
+
+def _halves(t_phys):
+    """(first half of a tensor holding two stacked batches, detached; sample rows of the second half)."""
+    n = t_phys.shape[0]
+    if n % 2:
+        raise _lib.P2PHDError("l1_halves_loss: the batch must hold two equal halves")
+    return t_phys.detach()[:n // 2], (n // 2, n)
 
 
 def mse_const_loss(a_phys, channels, target, rows=None):
@@ -1074,7 +1183,5 @@ def l1_halves_loss(t_phys, channels, coeff=1.0, park=False):
     feature-matching term when D(real) and D(fake) ran as one batch.  The gradient exists on the fake half only; with
     `park` it is parked (half-shaped) on the producer for the consumer's input-gradient kernel of a sample-range
     backward pass (backward_on_samples) to add."""
-    n = t_phys.shape[0]
-    if n % 2:
-        raise _lib.P2PHDError("l1_halves_loss: the batch must hold two equal halves")
-    return LossFn.apply(t_phys, t_phys.detach()[:n // 2], 1, 0.0, coeff, channels, park, (n // 2, n))
+    first, rows = _halves(t_phys)
+    return LossFn.apply(t_phys, first, 1, 0.0, coeff, channels, park, rows)
