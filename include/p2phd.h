@@ -490,6 +490,25 @@ int p2phd_audio_metrics(const float* hr, const float* lr, const float* sr, int64
                         const float* window2, const float* tables, int center, float* sr_matched, float* result4,
                         void* workspace, void* stream);
 
+/* The same figures per row, and the ones the reference's eval_matric.py leaves at zero.  Arguments as above; rows_out (device,
+ * [B][8] f32) receives for every row b alone -- no mean over rows --
+ *   mse, snr_sr, snr_lr, lsd, lsd_lf, lsd_hf, ssnr_sr, ssnr_lr;
+ * matched_out [B][T] receives sr', the moment-matched sr; every sr figure is taken on sr', every lr figure on lr as given.
+ *   lsd_lf / lsd_hf: per STFT frame sqrt(mean over the band's bins of (log10(P_hr + 1e-6) - log10(P_sr' + 1e-6))^2), averaged over
+ *     the row's frames; the low band is k < cut_bin, the high band cut_bin <= k <= n_fft2/2 (lsd: all bins).  1 <= cut_bin <= n_fft2/2.
+ *   ssnr_x: segmental SNR.  Frames of seg_win samples start at f * seg_hop, f < F = (T - seg_win) / seg_hop (integer division),
+ *     window w[i] = 0.5 (1 - cos(2 pi (i + 1) / (seg_win + 1))); per frame 10 log10(Es / (En + eps) + eps) clamped to [-10, 35] with
+ *     Es = sum (w hr)^2, En = sum (w hr - w x)^2, eps = 2^-52; the row's value is the mean over its F frames.  A row too short
+ *     for one frame (F < 1) gets NaN in both slots; the call succeeds and the other six columns are valid.
+ * Seven launches whatever B is, no host synchronisation, no atomics: a row's figures are the same bits from run to run and do
+ * not depend on the other rows of the call.  workspace: p2phd_metrics_rows_workspace_bytes bytes (host arithmetic only; 0 and
+ * p2phd_last_error() on bad arguments). */
+size_t p2phd_metrics_rows_workspace_bytes(int64_t B, int64_t T, int n_fft2, int hop2, int win2, int center, int cut_bin,
+                                          int seg_win, int seg_hop);
+int p2phd_audio_metrics_rows(const float* hr, const float* lr, const float* sr, int64_t B, int64_t T, int n_fft2, int hop2, int win2,
+                             const float* window2, const float* tables, int center, int cut_bin, int seg_win, int seg_hop,
+                             float* matched_out, float* rows_out, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Input feeder resampler (csrc/resample.hip): the HR -> LR -> HR conversions of data/audio_dataset.py:55-57,109-113
  * (torchaudio.functional.resample there; its source is not in the reference, so the definition -- Hann-windowed sinc,

@@ -112,6 +112,9 @@ SIGNATURES = {
     "p2phd_resample_out_len": (_i64, [_i64, _i32, _i32]),
     "p2phd_resample_fwd": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _i64, _vp]),
     "p2phd_audio_metrics": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "p2phd_metrics_rows_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "p2phd_audio_metrics_rows": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                        _vp]),
 }
 
 

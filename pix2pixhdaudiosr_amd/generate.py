@@ -1,7 +1,7 @@
 """Whole-file super-resolution: wav in, wav out, on the device from the waveform to the waveform.
 
     python -m pix2pixhdaudiosr_amd.generate --input in.wav --output out.wav --load_pretrain DIR [--overlap 0.25]
-    python -m pix2pixhdaudiosr_amd.generate --input DIR_IN --output DIR_OUT --load_pretrain DIR --channels all [--metrics_csv m.csv]
+    python -m pix2pixhdaudiosr_amd.generate --input DIR_IN --output DIR_OUT --load_pretrain DIR --channels all [--metrics_csv m.csv [--metrics_ext]]
 
     from pix2pixhdaudiosr_amd.generate import SuperResolver
     sr = SuperResolver(model, opt).enhance_file("in.wav", "out.wav")["sr"]
@@ -362,7 +362,7 @@ class SuperResolver:
         os.makedirs(folder, exist_ok=True)
         wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), sr.shape[0], encoding)
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding):
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False):
         from .data.audio_dataset import lr_round_trip
         from .util import util as U
         o = self.opt
@@ -377,36 +377,52 @@ class SuperResolver:
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         sr = self.enhance_lr(lr)
-        metrics = None
-        if has_hr and channels == 'first':
+        metrics = ext = None
+        if has_hr and extended_metrics:
+            # every written channel in one call and one copy back; the 7-tuples are read off the same rows
+            ext = U.compute_matrics_ext(raw, lr, sr, o)
+            metrics = [(e['mse'], e['snr_sr'], e['snr_lr'], 0, 0, 0, e['lsd']) for e in ext]
+            if channels == 'first':
+                metrics = metrics[0]
+        elif has_hr and channels == 'first':
             metrics = U.compute_matrics(raw, lr, sr, o)
         elif has_hr:
             metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
         if path_out is not None:
             self._write(path_out, sr, encoding)
-        return {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+        res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+        if extended_metrics:
+            res['metrics_ext'] = ext
+        return res
 
-    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16'):
+    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
         output encoded on the device (csrc/pcm.hip).  Returns {'sr', 'lr', 'hr', 'metrics', 'info'}: [C, L] tensors on the GPU;
         'hr' and 'metrics' are None unless the input is a full-band clip at the high rate; 'metrics' is
         util.compute_matrics against the input with 'first', else a list with one such 7-tuple per written channel, each
-        computed on that channel alone; 'info' is the input's wavio.WavInfo."""
-        return self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding)
+        computed on that channel alone; 'info' is the input's wavio.WavInfo.  `extended_metrics`: the result gains
+        'metrics_ext', util.compute_matrics_ext of all written channels from one device call -- a list with one dict
+        (util.METRIC_ROW_NAMES -> float) per written channel, also with 'first'; None where 'metrics' is None -- and 'metrics'
+        holds the same rows' figures."""
+        return self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics)
 
-    def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None):
+    def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
+                       extended_metrics=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
         `report(record)` is called after every file.  Returns one record per file: {'path' (relative), 'rate', 'channels',
         'frames' (of the input), 'written_channels', 'out_frames', 'metrics' (as enhance_file(channels != 'first') returns
-        them: a list per channel, or None), 'error' (None, or the text of what went wrong)}."""
+        them: a list per channel, or None), 'error' (None, or the text of what went wrong)}; with `extended_metrics` also
+        'metrics_ext' (as enhance_file returns it)."""
         records = []
         for rel, path_in, path_out in plan_folder(dir_in, dir_out):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
                    'metrics': None, 'error': None}
+            if extended_metrics:
+                rec['metrics_ext'] = None
             try:
                 read = self._read(path_in)
             except (ValueError, OSError, EOFError, struct.error) as e:
@@ -414,11 +430,13 @@ class SuperResolver:
             else:
                 if seed is not None:
                     torch.manual_seed(int(seed))
-                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding)
+                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics)
                 m, meta = res['metrics'], res['info']
                 rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
                            written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
                            metrics=[m] if m is not None and channels == 'first' else m)
+                if extended_metrics:
+                    rec['metrics_ext'] = res['metrics_ext']
             records.append(rec)
             if report is not None:
                 report(rec)
@@ -487,13 +505,27 @@ def check_paths(path_in, path_out):
 
 
 METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd")
+METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")     # --metrics_ext
 
 
-def metrics_rows(records):
+def _nanmean(values):
+    kept = [v for v in values if v == v]
+    return sum(kept) / len(kept) if kept else float('nan')
+
+
+def metrics_rows(records, extended=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
-    nothing was measured."""
+    nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
+    mean of a column then runs over its entries that are not NaN (a clip too short for one segment has no segmental SNR)."""
     rows = []
+    if extended:
+        for r in records:
+            for c, e in enumerate(r['metrics_ext'] or ()):
+                rows.append((r['path'], c, r['out_frames']) + tuple(e[name] for name in METRICS_COLUMNS_EXT[3:]))
+        if rows:
+            rows.append(("mean", "", "") + tuple(_nanmean([row[k] for row in rows]) for k in range(3, len(METRICS_COLUMNS_EXT))))
+        return rows
     for r in records:
         for c, m in enumerate(r['metrics'] or ()):
             rows.append((r['path'], c, r['out_frames'], m[0], m[1], m[2], m[6]))
@@ -502,12 +534,12 @@ def metrics_rows(records):
     return rows
 
 
-def write_metrics_csv(path, records):
+def write_metrics_csv(path, records, extended=False):
     import csv
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(METRICS_COLUMNS)
-        for row in metrics_rows(records):
+        w.writerow(METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS)
+        for row in metrics_rows(records, extended):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
@@ -523,6 +555,10 @@ def _parser():
     ap.add_argument("--metrics_csv", default=None, metavar="PATH",
                     help="write file, channel, frames, mse, snr_sr, snr_lr, lsd of every written channel that has a full-band "
                          "original, and a last `mean` row")
+    ap.add_argument("--metrics_ext", action="store_true",
+                    help="also measure, per channel, the log-spectral distance below and from the low rate's Nyquist frequency "
+                         "(lsd_lf, lsd_hf) and the segmental SNR of the output and of the low-rate input (ssnr_sr, ssnr_lr): "
+                         "printed, and four more columns of --metrics_csv")
     ap.add_argument("--load_pretrain", required=True, help="folder with <which_epoch>_net_G.pth (and opt.txt)")
     ap.add_argument("--opt_file", default=None, help="options dump of the training run (default: <load_pretrain>/opt.txt)")
     ap.add_argument("--which_epoch", default=None)
@@ -546,6 +582,13 @@ def _print_metrics(m, prefix=''):
     print('%sSNR_SR: %.4f' % (prefix, snr_sr))
     print('%sSNR_LR: %.4f' % (prefix, snr_lr))
     print('%sLSD: %.4f' % (prefix, lsd))
+
+
+def _print_metrics_ext(e, prefix=''):
+    print('%sLSD_LF: %.4f' % (prefix, e['lsd_lf']))
+    print('%sLSD_HF: %.4f' % (prefix, e['lsd_hf']))
+    print('%sSSNR_SR: %.4f' % (prefix, e['ssnr_sr']))
+    print('%sSSNR_LR: %.4f' % (prefix, e['ssnr_lr']))
 
 
 def _print_unwritten(name, available, written):
@@ -589,29 +632,37 @@ def main(argv=None):
             print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
         # every file starts from the seed, so it comes out as a run of its own would write it
-        records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report)
+        records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
+                                    extended_metrics=a.metrics_ext)
         done = [r for r in records if r['error'] is None]
         print('%d of %d files enhanced, %d skipped' % (len(done), len(records), len(records) - len(done)))
-        rows = metrics_rows(records)
+        rows = metrics_rows(records, a.metrics_ext)
         if rows:
-            print('mean over %d channels: MSE %.4f  SNR_SR %.4f  SNR_LR %.4f  LSD %.4f' % ((len(rows) - 1,) + rows[-1][3:]))
+            print('mean over %d channels: MSE %.4f  SNR_SR %.4f  SNR_LR %.4f  LSD %.4f' % ((len(rows) - 1,) + rows[-1][3:7]))
+            if a.metrics_ext:
+                print('mean over %d channels: LSD_LF %.4f  LSD_HF %.4f  SSNR_SR %.4f  SSNR_LR %.4f' % ((len(rows) - 1,) + rows[-1][7:]))
     else:
-        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding)
+        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding, extended_metrics=a.metrics_ext)
         m, written = res['metrics'], res['sr'].shape[0]
+        ext = res.get('metrics_ext')
         _print_unwritten(a.input, res['info'].num_channels, written)
         if m is not None and a.channels == 'first':
             _print_metrics(m)
+            if ext is not None:
+                _print_metrics_ext(ext[0])
         elif m is not None:
             for c, mc in enumerate(m):
                 _print_metrics(mc, 'channel %d ' % c)
+                if ext is not None:
+                    _print_metrics_ext(ext[c], 'channel %d ' % c)
         if written == 1:
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
-                    'metrics': [m] if m is not None and a.channels == 'first' else m}]
+                    'metrics': [m] if m is not None and a.channels == 'first' else m, 'metrics_ext': ext}]
     if a.metrics_csv:
-        write_metrics_csv(a.metrics_csv, records)
+        write_metrics_csv(a.metrics_csv, records, a.metrics_ext)
         print('metrics: %s' % a.metrics_csv)
     return 0
 

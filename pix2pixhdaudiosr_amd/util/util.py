@@ -134,3 +134,54 @@ def compute_matrics(hr_audio, lr_audio, sr_audio, opt):
     result, _ = audio_metrics(hr_audio, lr_audio, sr_audio, opt.n_fft, opt.hop_length, opt.win_length, opt.center)
     mse, snr_sr, snr_lr, lsd = result.tolist()
     return mse, snr_sr, snr_lr, 0, 0, 0, lsd
+
+
+METRIC_ROW_NAMES = ("mse", "snr_sr", "snr_lr", "lsd", "lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")
+
+
+def metric_rows_geometry(n_fft, hr_sampling_rate, lr_sampling_rate):
+    """(cut_bin, seg_win, seg_hop) of audio_metrics_rows.  cut_bin: the bin of the low rate's Nyquist frequency in the
+    2*n_fft-point STFT -- the first bin of the high band (equal rates: n_fft, the high band is the Nyquist bin alone).
+    Segments of 30 ms every quarter of that (240 / 60 samples at 8 kHz, 1440 / 360 at 48 kHz)."""
+    hr_rate, lr_rate = int(hr_sampling_rate), int(lr_sampling_rate)
+    cut_bin = (2 * int(n_fft) * lr_rate) // (2 * hr_rate)
+    return cut_bin, int(round(0.03 * hr_rate)), int(np.floor(0.25 * 0.03 * hr_rate))
+
+
+def audio_metrics_rows(hr_audio, lr_audio, sr_audio, n_fft, hop_length, win_length, center, hr_sampling_rate, lr_sampling_rate):
+    """Per-row metrics on the device: returns (rows [B, 8] float32 on the GPU, columns METRIC_ROW_NAMES, every row measured on
+    its own; sr moment-matched to hr).  One call for any number of rows, no host synchronisation.  Beside the four figures of
+    `audio_metrics` a row holds the LSD of the bins below / from the low rate's Nyquist frequency (lsd_lf, lsd_hf) and the
+    segmental SNR of sr and lr (NaN for a row shorter than one segment and one hop); definitions: csrc/metrics.hip."""
+    from .. import _lib
+    _lib.require_gpu_tensor(sr_audio, "sr_audio")
+    dev = sr_audio.device
+    T = sr_audio.shape[-1]
+    sr = sr_audio.float().reshape(-1, T).contiguous()
+    hr = hr_audio.to(dev).float().reshape(-1, T).contiguous()
+    lr = lr_audio.to(dev).float().reshape(-1, T).contiguous()
+    if hr.shape != sr.shape or lr.shape != sr.shape:
+        raise ValueError(f"audio_metrics_rows: shapes differ: hr {tuple(hr.shape)} lr {tuple(lr.shape)} sr {tuple(sr.shape)}")
+    B = sr.shape[0]
+    n2, hop2, win2 = 2 * int(n_fft), 2 * int(hop_length), 2 * int(win_length)
+    cut_bin, seg_win, seg_hop = metric_rows_geometry(n_fft, hr_sampling_rate, lr_sampling_rate)
+    window2 = kbdwin(win2).to(dev).contiguous()
+    L = _lib.lib()
+    nbytes = L.p2phd_metrics_rows_workspace_bytes(B, T, n2, hop2, win2, int(bool(center)), cut_bin, seg_win, seg_hop)
+    if nbytes == 0:
+        raise _lib.P2PHDError("audio_metrics_rows: " + L.p2phd_last_error().decode("utf-8", "replace"))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    matched = torch.empty_like(sr)
+    rows = torch.empty((B, len(METRIC_ROW_NAMES)), dtype=torch.float32, device=dev)
+    _lib.check(L.p2phd_audio_metrics_rows(_lib.ptr(hr), _lib.ptr(lr), _lib.ptr(sr), B, T, n2, hop2, win2, _lib.ptr(window2),
+                                          _lib.ptr(_stft_tables(n2, dev)), int(bool(center)), cut_bin, seg_win, seg_hop,
+                                          _lib.ptr(matched), _lib.ptr(rows), _lib.ptr(ws), _lib.stream_ptr()), "audio_metrics_rows")
+    return rows, matched.reshape(sr_audio.shape)
+
+
+def compute_matrics_ext(hr_audio, lr_audio, sr_audio, opt):
+    """The eight per-row figures as Python floats: a list with one dict (METRIC_ROW_NAMES -> float) per row of the inputs, from
+    one device call and one copy to the host.  `compute_matrics` above keeps the reference's 7-tuple and its zeros."""
+    rows, _ = audio_metrics_rows(hr_audio, lr_audio, sr_audio, opt.n_fft, opt.hop_length, opt.win_length, opt.center,
+                                 opt.hr_sampling_rate, opt.lr_sampling_rate)
+    return [dict(zip(METRIC_ROW_NAMES, row)) for row in rows.tolist()]
