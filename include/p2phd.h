@@ -330,6 +330,18 @@ int p2phd_conv_dgrad_bsum(const p2phd_conv_desc* c, const void* dy, const void* 
 int p2phd_conv_dgrad_act(const p2phd_conv_desc* c, const void* dy, const void* packed, const void* addend, void* dx,
                          const void* x_act, int prev_act, void* workspace, void* stream);
 
+/* Which gather-GEMM tile would each generic launch of (desc, form) take under the current options?  Host arithmetic only:
+ * nothing is launched and no device is needed (tests pin the answers and compare them with p2phd_launch_count).
+ *   form : 0 forward | 1 input gradient on its generic plans | 2 input gradient on the exact reflect grid, dy expanded |
+ *          3 the same through the reflection extras (p2phd_conv_dgrad_rx) | 4 fp8 forward
+ *   flags: 1 InstanceNorm statistics wanted (forms 0, 4) | 2 fused InstanceNorm-backward sums (p2phd_conv_dgrad_bsum) |
+ *          4 fused activation backward (p2phd_conv_dgrad_act); 2 and 4 belong to form 1, one at a time
+ * Writes 9 ints per launch, for up to `cap` launches: tile rows, tile columns, 32-row blocks per wave, 32-column blocks per
+ * wave, LDS ring slots, HALO loop (0 | 1), M tiles across samples (0 | 1), tap-skipping merged launch (0 | 1), and the rows per
+ * statistics slot / fused-sums partial.  Returns the number of launches, or a negative error code when the form or a flag does
+ * not apply to the layer.  A dedicated kernel may serve the layer instead: the answer is what the generic path would run. */
+int p2phd_conv_gconv_tiles(const p2phd_conv_desc* c, int form, int flags, int* out9, int cap);
+
 /* dw (master layout, f32, overwritten) and db (f32 [K], overwritten, may be NULL) from x and dy. */
 size_t p2phd_conv_wgrad_workspace_bytes(const p2phd_conv_desc* c);
 int p2phd_conv_wgrad(const p2phd_conv_desc* c, const void* x, const void* dy, float* dw, float* db, void* workspace,

@@ -69,6 +69,7 @@ SIGNATURES = {
     "p2phd_conv_dgrad_bsum_workspace_bytes": (_sz, [_vp]),
     "p2phd_conv_dgrad_bsum": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
     "p2phd_conv_dgrad_act": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "p2phd_conv_gconv_tiles": (_i32, [_vp, _i32, _i32, _vp, _i32]),
     "p2phd_conv_wgrad_workspace_bytes": (C.c_size_t, [_vp]),
     "p2phd_conv_wgrad": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "p2phd_conv_wgrad_acc": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

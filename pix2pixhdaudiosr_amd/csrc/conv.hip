@@ -36,6 +36,7 @@
 namespace {
 
 using p2phd::GDesc;
+using p2phd::GconvTile;
 
 typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
 typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
@@ -1859,7 +1860,7 @@ int launch_gconv_cfg(const GDesc& d_in, const void* in, const void* wp, const fl
   GDesc d = d_in;
   // InstanceNorm partials: one slot per wave row block (MR * 32 rows) of a sample, see the epilogue
   d.stats_slots = (d.Hg * d.Wg + MR * 32 - 1) / (MR * 32);
-  if (slot_rows) *slot_rows = d.bs_out != nullptr ? BM : MR * 32;   // (fused backward sums: one partial per TILE)
+  if (slot_rows) *slot_rows = p2phd::gconv_slot_rows(BM, MR, d.bs_out != nullptr);
   constexpr int STAGE = (BM + BN) * kRowBytes;
   constexpr int CT = BM * (BN * (int)sizeof(typename OutOf<T>::type) + 16);
   const int tab = (HALO ? 0 : ((d.nth * d.ntw * BM * 4 + 15) & ~15)) + BM * 8;        // gather table + row table
@@ -1940,135 +1941,154 @@ int launch_gconv_cfg(const GDesc& d_in, const void* in, const void* wp, const fl
   return p2phd::check_launch("gconv");
 }
 
-// The HALO main loop of the 256 x 192 tile (gconv_halo.inc): 3 x 3 taps within one pixel of the centre on a 16-wide plane whose
-// height is a multiple of 16, gathered tensor of the same size, 64-channel chunks, full K rows (no padding tail)
-bool gconv_halo_ok(const GDesc& d) {
-  const bool taps = d.nth == 3 && d.ntw == 3 && d.sh == 1 && d.sw == 1 &&
-                    ((d.dh0 == -1 && d.dh_step == 1) || (d.dh0 == 1 && d.dh_step == -1)) &&
-                    ((d.dw0 == -1 && d.dw_step == 1) || (d.dw0 == 1 && d.dw_step == -1));
-  return p2phd::g_opt_gconv_halo != 0 && taps && d.cls_cp == 0 && d.Wg == 16 && d.Hg % 16 == 0 && d.Hg >= 16 && d.Hin == d.Hg && d.Win == d.Wg &&
-         d.Cp_in % 64 == 0 && d.KK == 9 * d.Cp_in && (d.pad_mode == 0 || d.pad_mode == 1 || d.pad_mode == 3) && d.flat_m == 0 &&
-         d.oh_mul == 1 && d.ow_mul == 1 && d.oh_off == 0 && d.ow_off == 0;
-}
+// Dispatch: the instantiations each element type can reach, keyed by the tile gconv_choose_tile returns.  A tile that is
+// not listed for its type is an error, never a fall-back to another tile.
+typedef int (*GconvLaunch)(const GDesc&, const void*, const void*, const float*, const void*, void*, float*, hipStream_t, int*);
+struct GconvRow { int bm, bn, mr, nr, nstage, halo; GconvLaunch launch; };
+#define GCONV_ROW(T, BM, BN, MR, NR, NS, HALO) {BM, BN, MR, NR, NS, HALO, launch_gconv_cfg<T, BM, BN, MR, NR, NS, HALO>}
+#define GCONV_ROWS_EVERY_TYPE(T) \
+  GCONV_ROW(T, 128, 128, 2, 2, 2, 0), GCONV_ROW(T, 128, 64, 2, 1, 2, 0), GCONV_ROW(T, 128, 32, 1, 1, 2, 0), \
+  GCONV_ROW(T, 256, 128, 2, 2, 3, 0), GCONV_ROW(T, 256, 128, 2, 2, 2, 0), GCONV_ROW(T, 256, 64, 2, 1, 3, 0), GCONV_ROW(T, 256, 64, 2, 1, 2, 0)
+const GconvRow kTilesF32[] = {GCONV_ROWS_EVERY_TYPE(float)};
+const GconvRow kTilesFp8[] = {GCONV_ROWS_EVERY_TYPE(fp8_t), GCONV_ROW(fp8_t, 256, 192, 2, 3, 2, 0)};   // (256 x 256 spills with the two-MFMA fp8 fragments)
+const GconvRow kTiles16[] = {GCONV_ROWS_EVERY_TYPE(bf16_t), GCONV_ROW(bf16_t, 256, 192, 2, 3, 2, 0), GCONV_ROW(bf16_t, 256, 256, 4, 2, 2, 0),
+                             GCONV_ROW(bf16_t, 256, 192, 2, 3, 2, 1), GCONV_ROW(bf16_t, 256, 128, 2, 2, 2, 1), GCONV_ROW(bf16_t, 128, 192, 2, 3, 2, 0)};
+#undef GCONV_ROWS_EVERY_TYPE
+#undef GCONV_ROW
 
-template <typename T>
-int launch_gconv_t(GDesc d, const void* in, const void* wp, const float* bias, const void* addend, void* out,
-                   float* stats, hipStream_t st, int* slot_rows) {
-  // N tile: the 128-wide tile has the best MFMA density (64x64 per wave) and reads the gathered A operand once;
-  // narrower tiles only for layers that would leave most of it empty
+template <size_t ROWS>
+int launch_gconv_tile(const GconvRow (&table)[ROWS], int dtype, GDesc d, const void* in, const void* wp, const float* bias, const void* addend,
+                      void* out, float* stats, hipStream_t st, int* slot_rows) {
   if (d.n_extent == 0) d.n_extent = d.Cp_out;
-  const int k = d.n_extent;
-  if constexpr (sizeof(T) == 2) {
-    if (d.cls_skip != 0) {                                     // (planned for this tile: merged_plan)
-      d.flat_m = 0;
-      return launch_gconv_cfg<T, 256, 192, 2, 3, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-    }
-  } else if (d.cls_skip != 0) {
-    p2phd::set_error("gconv: a tap-skipping merged plan reached a non-16-bit launch");
-    return P2PHD_EINVAL;
-  }
-  const int bn = k > 64 ? 128 : (k > 32 ? 64 : 32);
-  const int npix = d.Hg * d.Wg;
-  const int taps = d.nth * d.ntw;
-  // 256-row tiles (8 waves, 3-slot ring) halve the weight traffic per FLOP: used when a sample has enough pixels to
-  // fill them, the grid still covers the chip, and ring + gather table fit the 160 KiB of LDS
-  d.flat_m = stats == nullptr && d.bs_out == nullptr && (npix % 256 != 0);   // no per-sample sums wanted: tiles may straddle samples
-  const long mt256 = d.flat_m ? ((long)d.N * npix + 255) / 256 : (long)((npix + 255) / 256) * d.N;
-  const long tabb = (long)taps * 256 * 4 + 16 + 256 * 8;
-  const long kLds = 160 * 1024;
-  const bool enough_px = d.flat_m ? (long)d.N * npix >= 2048 : (npix >= 256 && (npix % 256 == 0 || npix >= 2048));
-  // 256 x 256 tiles (8 waves of 128 x 64, 2-slot ring): twice the MFMA work per LDS-DMA piece; for wide layers whose
-  // grid still fills most of the chip.  256 x {128,64}: 3-slot ring when it fits beside the gather table, else 2-slot.
-  const bool fits_huge = sizeof(T) == 2 && 2 * 512 * kRowBytes + tabb <= kLds && 256 * (256 * 2 + 16) + tabb <= kLds;
-  bool huge = fits_huge && enough_px && k >= 256 && (k % 256 == 0 || k >= 1024) && mt256 * ((k + 255) / 256) >= 160;
-  if (d.bs_out != nullptr || d.as_x != nullptr) huge = false;   // (the 128-accumulator tile has no fused store loop)
-  const bool fits3 = bn >= 64 && 3 * (256 + bn) * kRowBytes + tabb <= kLds && p2phd::g_opt_gconv_bm != 258;   // (258: experiments, 256 rows on the 2-slot ring)
-  const bool fits2 = bn >= 64 && 2 * (256 + bn) * kRowBytes + tabb <= kLds && 256 * (bn * (long)sizeof(typename OutOf<T>::type) + 16) + tabb <= kLds;
-  // short reductions (<= 4 K steps: the folded 2-channel layers, the 4-channel D input) are all prologue and epilogue:
-  // keep the light 128-row kernel there, several of which fit on a CU and overlap each other's fixed costs
-  const bool short_k = d.KK <= 4 * 8 * Elem<T>::EPP;
-  bool big = (fits3 || fits2) && enough_px && !short_k && mt256 * ((k + bn - 1) / bn) >= 192;
-  const int force = p2phd::g_opt_gconv_bm;
-  if (force == 128) { big = false; huge = false; }
-  if (force == 256 || force == 258) { big = fits3 || fits2; huge = false; }
-  if (force == 512) { huge = fits_huge && k > 128 && d.bs_out == nullptr && d.as_x == nullptr; }
-  // 256 x 192 (8 waves of 64 x 96): when the 256 x 256 grid would leave CUs idle that a 192-wide N tile fills
-  // (the residual trunk: 768 = 4 x 192 -> 64 x 4 = 256 workgroups instead of 64 x 3 = 192)
-  if (force == 192 && sizeof(T) <= 2 && k % 192 == 0 && 2 * 448 * kRowBytes + tabb <= kLds)
-    return launch_gconv_cfg<T, 256, 192, 2, 3, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  // (fp8 operands: no 256 x 256 instantiation -- it spills -- so the 192-wide tile is taken whenever it divides the output)
-  const bool wide = enough_px && k >= 256 && (k % 256 == 0 || k >= 1024) && mt256 * ((k + 255) / 256) >= 160;
-  if ((huge || (sizeof(T) == 1 && wide)) && force == 0 && k % 192 == 0) {
-    const long wg256 = mt256 * ((k + 255) / 256), wg192 = mt256 * (k / 192);
-    const double c256 = std::ceil(wg256 / 256.0) * 256.0 * 256.0, c192 = std::ceil(wg192 / 256.0) * 256.0 * 192.0 / 0.95;
-    if ((sizeof(T) == 1 || c192 < c256) && 2 * 448 * kRowBytes + tabb <= kLds) {
-      if constexpr (sizeof(T) == 2) {
-        if (gconv_halo_ok(d)) return launch_gconv_cfg<T, 256, 192, 2, 3, 2, 1>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-      }
-      return launch_gconv_cfg<T, 256, 192, 2, 3, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-    }
-  }
-  // ... and for 192- / 384-wide outputs (the 96-channel layers and the merged sub-pixel launches of the up path),
-  // where 128-wide tiles would gather the A operand once more and pad the last tile
-  if (!huge && force == 0 && sizeof(T) <= 2 && enough_px && !short_k && k % 192 == 0 && (k <= 384 || d.bs_out != nullptr || d.as_x != nullptr) &&
-      2 * 448 * kRowBytes + tabb <= kLds && mt256 * (k / 192) >= 192)
-    return launch_gconv_cfg<T, 256, 192, 2, 3, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  if constexpr (sizeof(T) == 2) {                              // (the 256 x 256 tile spills with the two-MFMA fp8 fragments; f32 never takes it)
-    if (huge) return launch_gconv_cfg<T, 256, 256, 4, 2, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  }
-  if (big && bn == 128) {
-    if constexpr (sizeof(T) == 2) {                            // the HALO loop on 128-wide tiles: 16-wide planes whose 192- / 256-wide grids leave CUs idle
-      if (force == 0 && k % 128 == 0 && !short_k && gconv_halo_ok(d))   // (configs[4]'s 2048-channel trunk at B = 8; the 768-channel trunk below B = 27)
-        return launch_gconv_cfg<T, 256, 128, 2, 2, 2, 1>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-    }
-    if (fits3) return launch_gconv_cfg<T, 256, 128, 2, 2, 3>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-    return launch_gconv_cfg<T, 256, 128, 2, 2, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  }
-  if (big && bn == 64) {
-    if (fits3) return launch_gconv_cfg<T, 256, 64, 2, 1, 3>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-    return launch_gconv_cfg<T, 256, 64, 2, 1, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  }
-  // 128 x 192 (4 waves of 64 x 96): planes too small for 256-row tiles whose 128 x 128 grid would run a second, half-empty
-  // round (the 1536-channel trunk of the two-scale generator at 16 x 8: 32 x 12 = 384 tiles -> 32 x 8 = 256)
-  if constexpr (sizeof(T) == 2) {
-    const long mt128 = (long)((npix + 127) / 128) * d.N;
-    const long wg128 = mt128 * ((k + 127) / 128), wg192 = mt128 * (k / 192);
-    if (force == 0 && !d.flat_m && !short_k && k % 192 == 0 && k >= 384 && p2phd::g_opt_tile128x192 != 0 &&
-        std::ceil(wg192 / 256.0) * 192.0 < std::ceil(wg128 / 512.0) * 2.0 * 128.0 && wg192 >= 192)
-      return launch_gconv_cfg<T, 128, 192, 2, 3, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  }
-  if (bn == 128) return launch_gconv_cfg<T, 128, 128, 2, 2, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  if (bn == 64) return launch_gconv_cfg<T, 128, 64, 2, 1, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  return launch_gconv_cfg<T, 128, 32, 1, 1, 2>(d, in, wp, bias, addend, out, stats, st, slot_rows);
+  const GconvTile t = p2phd::gconv_choose_tile(d, dtype, stats != nullptr);
+  if (t.bm == 0) return P2PHD_EINVAL;                            // (refused: error text set by the chooser)
+  d.flat_m = t.flat_m;
+  for (const GconvRow& r : table)
+    if (r.bm == t.bm && r.bn == t.bn && r.mr == t.mr && r.nr == t.nr && r.nstage == t.nstage && r.halo == t.halo)
+      return r.launch(d, in, wp, bias, addend, out, stats, st, slot_rows);
+  p2phd::set_error("gconv: no %d x %d tile (waves %d x %d, %d ring slots, halo %d) for dtype %d", t.bm, t.bn, t.mr, t.nr, t.nstage, t.halo, dtype);
+  return P2PHD_EINVAL;
 }
 
 }  // namespace
 
 namespace p2phd {
 
-// launch_gconv_t's tile choice for a bf16 launch WITHOUT statistics / fused sums: does it take the 256 x 256 tile?  That
-// tile has no fused store loop, so an input gradient carrying the producer's InstanceNorm-backward sums falls back to
-// 256 x 128 tiles and loses more (D 128->256 <- 256->512 at B = 64: 735 + 40 us against 539 + 89 us for plain input
-// gradient + two-pass backward) than the saved pass is worth: p2phd_conv_dgrad_bsum_pays says no for such a layer.
-bool gconv_plain_launch_takes_256x256(const GDesc& d_in, int dtype) {
-  if (dtype != P2PHD_BF16 || d_in.cls_skip != 0) return false;
-  const int k = d_in.n_extent ? d_in.n_extent : d_in.Cp_out;
-  const int npix = d_in.Hg * d_in.Wg, taps = d_in.nth * d_in.ntw;
-  const bool flat = npix % 256 != 0;
-  const long mt256 = flat ? ((long)d_in.N * npix + 255) / 256 : (long)((npix + 255) / 256) * d_in.N;
-  const long tabb = (long)taps * 256 * 4 + 16 + 256 * 8, kLds = 160 * 1024;
-  const bool enough_px = flat ? (long)d_in.N * npix >= 2048 : (npix >= 256 && (npix % 256 == 0 || npix >= 2048));
-  const bool fits_huge = 2 * 512 * kRowBytes + tabb <= kLds && 256 * (256 * 2 + 16) + tabb <= kLds;
-  bool huge = fits_huge && enough_px && k >= 256 && (k % 256 == 0 || k >= 1024) && mt256 * ((k + 255) / 256) >= 160;
-  const int force = g_opt_gconv_bm;
-  if (force == 512) huge = fits_huge && k > 128;
-  else if (force != 0) huge = false;
-  if (huge && force == 0 && k % 192 == 0) {
-    const long wg256 = mt256 * ((k + 255) / 256), wg192 = mt256 * (k / 192);
-    const double c256 = std::ceil(wg256 / 256.0) * 256.0 * 256.0, c192 = std::ceil(wg192 / 256.0) * 256.0 * 192.0 / 0.95;
-    if (c192 < c256 && 2 * 448 * kRowBytes + tabb <= kLds) huge = false;
+// ---- the tile of a gather-GEMM launch ------------------------------------------------------------------------------------
+namespace {
+// The 160 KiB of LDS beside the tables of a 256-row tile (gather table of `taps` offsets per row + row table, launch_gconv_cfg)
+struct LdsBudget {
+  long tables;
+  explicit LdsBudget(int taps) : tables((long)taps * 256 * 4 + 16 + 256 * 8) {}
+  bool holds(long bytes) const { return bytes + tables <= 160 * 1024; }
+  bool ring(int slots, int bn) const { return holds((long)slots * (256 + bn) * kRowBytes); }          // `slots` stages of the A and B tiles
+  bool c_tile(int bn, int out_bytes) const { return holds(256 * ((long)bn * out_bytes + 16)); }       // the output tile staged for the store loop
+};
+
+// Workgroups one round of the chip runs, as the two cost comparisons below count them: one 8-wave or 192-wide workgroup per CU;
+// the light 128 x 128 workgroups go two to a CU.  A literal, NOT the device's CU count (that belongs to the split-K tail of
+// launch_gconv_cfg): replacing it would move layers between tiles on other chips or under the "cus" option, which is a change
+// of behaviour with its own measurements.
+constexpr double kWgsPerRound = 256.0;
+double rounds(long wgs, double per_round) { return std::ceil(wgs / per_round); }
+
+// The HALO main loop (gconv_halo.inc): 3 x 3 taps within one pixel of the centre on a 16-wide plane whose height is a multiple
+// of 16, gathered tensor of the same size, 64-channel chunks, full K rows (no padding tail), per-sample M tiles
+bool gconv_halo_ok(const GDesc& d, bool flat_m) {
+  const bool taps = d.nth == 3 && d.ntw == 3 && d.sh == 1 && d.sw == 1 &&
+                    ((d.dh0 == -1 && d.dh_step == 1) || (d.dh0 == 1 && d.dh_step == -1)) &&
+                    ((d.dw0 == -1 && d.dw_step == 1) || (d.dw0 == 1 && d.dw_step == -1));
+  return g_opt_gconv_halo != 0 && taps && d.cls_cp == 0 && d.Wg == 16 && d.Hg % 16 == 0 && d.Hg >= 16 && d.Hin == d.Hg && d.Win == d.Wg &&
+         d.Cp_in % 64 == 0 && d.KK == 9 * d.Cp_in && (d.pad_mode == 0 || d.pad_mode == 1 || d.pad_mode == 3) && !flat_m &&
+         d.oh_mul == 1 && d.ow_mul == 1 && d.oh_off == 0 && d.ow_off == 0;
+}
+}  // namespace
+
+long gconv_mtiles256(const GDesc& d, bool flat_m) {
+  const int npix = d.Hg * d.Wg;
+  return flat_m ? ((long)d.N * npix + 255) / 256 : (long)((npix + 255) / 256) * d.N;
+}
+
+bool gconv_256x192_fills_chip(const GDesc& d, bool flat_m) {
+  return gconv_mtiles256(d, flat_m) * ((d.n_extent ? d.n_extent : d.Cp_out) / kGconvCols192) >= 192;
+}
+
+GconvTile gconv_choose_tile(const GDesc& d, int dtype, bool stats_wanted) {
+  // what the operand type fixes: 16-bit (bf16 / fp16), fp8 (bf16 outputs) or f32
+  const bool h16 = dtype == P2PHD_BF16, fp8 = dtype == P2PHD_FP8_INTERNAL, f32 = !h16 && !fp8;
+  const int epp = fp8 ? 16 : (h16 ? 8 : 4), out_bytes = f32 ? 4 : 2;   // elements per 16-byte piece of K; bytes of an output element
+  const int k = d.n_extent ? d.n_extent : d.Cp_out;              // GEMM N extent
+  if (d.cls_skip != 0) {                                         // (planned for this tile: merged_plan)
+    if (h16) return GconvTile{256, 192, 2, 3, 2, 0, 0};
+    set_error("gconv: a tap-skipping merged plan reached a non-16-bit launch");
+    return GconvTile{};
   }
-  return huge;
+  const int force = g_opt_gconv_bm;                              // 0 = heuristic
+  const bool fused = d.bs_out != nullptr || d.as_x != nullptr;   // fused store loop of the input gradient (sums / activation backward)
+  const int npix = d.Hg * d.Wg;
+  // no per-sample sums wanted: M tiles may straddle samples
+  const bool flat_m = !stats_wanted && d.bs_out == nullptr && npix % 256 != 0;
+  const long mt256 = gconv_mtiles256(d, flat_m);
+  const LdsBudget lds(d.nth * d.ntw);
+  // N tile: the 128-wide tile has the best MFMA density (64x64 per wave) and reads the gathered A operand once;
+  // narrower tiles only for layers that would leave most of it empty
+  const int bn = k > 64 ? 128 : (k > 32 ? 64 : 32);
+
+  // ---- eligibility, each stated once ----
+  // a sample (or, flat, the batch) has enough pixels to fill 256-row tiles
+  const bool enough_px = flat_m ? (long)d.N * npix >= 2048 : (npix >= 256 && (npix % 256 == 0 || npix >= 2048));
+  // short reductions (<= 4 K steps: the folded 2-channel layers, the 4-channel D input) are all prologue and epilogue:
+  // keep the light 128-row kernel there, several of which fit on a CU and overlap each other's fixed costs
+  const bool short_k = d.KK <= 4 * 8 * epp;
+  // a wide output whose 256 x 256 grid still fills most of the chip
+  const bool wide = enough_px && k >= 256 && (k % 256 == 0 || k >= 1024) && mt256 * ((k + 255) / 256) >= 160;
+  // 256 x 256 (8 waves of 128 x 64, 2-slot ring): 16-bit only (it spills with the two-MFMA fp8 fragments, f32 never takes it),
+  // and its 128-accumulator waves have no fused store loop
+  const bool fits256 = h16 && lds.ring(2, 256) && lds.c_tile(256, 2) && !fused;
+  const bool take256 = force == 512 ? fits256 && k > 128 : ((force == 0 || force == 192) && fits256 && wide);   // (192 forces its own tile only)
+  // 256 x 192 (8 waves of 64 x 96, 2-slot ring): 16-bit and fp8, outputs the tile divides
+  const bool fits192 = !f32 && k % kGconvCols192 == 0 && lds.ring(2, kGconvCols192);
+  // 256 x {128, 64}: 3-slot ring when it fits beside the gather table, else 2-slot (258: experiments, 256 rows on the 2-slot ring)
+  const bool ring3 = bn >= 64 && lds.ring(3, bn) && force != 258;
+  const bool ring2 = bn >= 64 && lds.ring(2, bn) && lds.c_tile(bn, out_bytes);
+  // 256-row tiles (8 waves) halve the weight traffic per FLOP: when a sample has enough pixels to fill them and the grid
+  // still covers the chip
+  const bool rows256 = (ring3 || ring2) && (force == 256 || force == 258 ||
+                                            (force != 128 && enough_px && !short_k && mt256 * ((k + bn - 1) / bn) >= 192));
+
+  // ---- the tiles, first match wins ----
+  if (force == 192 && fits192) return GconvTile{256, 192, 2, 3, 2, 0, flat_m};
+  // 256 x 192 where the 256 x 256 grid would leave CUs idle that a 192-wide N tile fills (the residual trunk: 768 = 4 x 192 ->
+  // 64 x 4 = 256 workgroups instead of 64 x 3 = 192); fp8 has no 256 x 256 tile and takes it whenever it divides a wide output.
+  // With the HALO loop where the plane allows.
+  if (force == 0 && fits192 && (take256 || (fp8 && wide))) {
+    const long wg256 = mt256 * ((k + 255) / 256), wg192 = mt256 * (k / kGconvCols192);
+    const double c256 = rounds(wg256, kWgsPerRound) * 256.0 * 256.0, c192 = rounds(wg192, kWgsPerRound) * 256.0 * 192.0 / 0.95;
+    if (fp8 || c192 < c256) return GconvTile{256, 192, 2, 3, 2, h16 && gconv_halo_ok(d, flat_m) ? 1 : 0, flat_m};
+  }
+  // ... and for 192- / 384-wide outputs (the 96-channel layers and the merged sub-pixel launches of the up path), where
+  // 128-wide tiles would gather the A operand once more and pad the last tile; wider ones only with a fused store loop
+  if (force == 0 && fits192 && !take256 && enough_px && !short_k && (k <= 384 || fused) && gconv_256x192_fills_chip(d, flat_m))
+    return GconvTile{256, 192, 2, 3, 2, 0, flat_m};
+  if (take256) return GconvTile{256, 256, 4, 2, 2, 0, flat_m};
+  if (rows256 && bn == 128) {
+    // the HALO loop on 128-wide tiles: 16-wide planes whose 192- / 256-wide grids leave CUs idle
+    // (configs[4]'s 2048-channel trunk at B = 8; the 768-channel trunk below B = 27)
+    if (h16 && force == 0 && k % 128 == 0 && gconv_halo_ok(d, flat_m)) return GconvTile{256, 128, 2, 2, 2, 1, flat_m};
+    return GconvTile{256, 128, 2, 2, ring3 ? 3 : 2, 0, flat_m};
+  }
+  if (rows256 && bn == 64) return GconvTile{256, 64, 2, 1, ring3 ? 3 : 2, 0, flat_m};
+  // 128 x 192 (4 waves of 64 x 96): planes too small for 256-row tiles whose 128 x 128 grid would run a second, half-empty
+  // round (the 1536-channel trunk of the two-scale generator at 16 x 8: 32 x 12 = 384 tiles -> 32 x 8 = 256)
+  if (h16 && force == 0 && g_opt_tile128x192 != 0 && !flat_m && !short_k && k % 192 == 0 && k >= 384) {
+    const long mt128 = (long)((npix + 127) / 128) * d.N;
+    const long wg128 = mt128 * ((k + 127) / 128), wg192 = mt128 * (k / 192);
+    if (rounds(wg192, kWgsPerRound) * 192.0 < rounds(wg128, 2 * kWgsPerRound) * 2.0 * 128.0 && wg192 >= 192)
+      return GconvTile{128, 192, 2, 3, 2, 0, flat_m};
+  }
+  if (bn == 128) return GconvTile{128, 128, 2, 2, 2, 0, flat_m};
+  if (bn == 64) return GconvTile{128, 64, 2, 1, 2, 0, flat_m};
+  return GconvTile{128, 32, 1, 1, 2, 0, flat_m};
 }
 
 }  // namespace p2phd
@@ -2108,6 +2128,9 @@ int launch_bsum_merge(const float* table, float* bstats, int N, long npix, int t
   return check_launch("bsum_merge");
 }
 
+// the launches below exist for the 16-bit type and for f32: run `...` with T naming the element type of `dtype`
+#define FOR_ELEM(dtype, T, ...) do { if ((dtype) == P2PHD_BF16) { typedef bf16_t T; __VA_ARGS__; } else { typedef float T; __VA_ARGS__; } } while (0)
+
 int launch_gconv(const GDesc& d_in, int dtype, const void* in, const void* wp, const float* bias, const void* addend,
                  void* out, float* stats, hipStream_t st, int* slot_rows) {
   if (d_in.N == 0 || d_in.Hg * d_in.Wg == 0) return P2PHD_OK;
@@ -2125,10 +2148,10 @@ int launch_gconv(const GDesc& d_in, int dtype, const void* in, const void* wp, c
   P2PHD_REQUIRE((long)d.N * d.Hin * d.Win < (1l << 31) && (long)d.N * d.Hout * d.Wout < (1l << 31), "gconv: too many pixels");
   if (dtype == P2PHD_FP8_INTERNAL) {
     P2PHD_REQUIRE(d.Cp_in % 16 == 0 && d.KK % 128 == 0 && d.out_scale != nullptr, "gconv(fp8): channel pitch %% 16, GEMM-K %% 128 and a scale are required");
-    return launch_gconv_t<fp8_t>(d, in, wp, bias, addend, out, stats, st, slot_rows);
+    return launch_gconv_tile(kTilesFp8, dtype, d, in, wp, bias, addend, out, stats, st, slot_rows);
   }
-  if (dtype == P2PHD_BF16) return launch_gconv_t<bf16_t>(d, in, wp, bias, addend, out, stats, st, slot_rows);
-  if (dtype == P2PHD_F32) return launch_gconv_t<float>(d, in, wp, bias, addend, out, stats, st, slot_rows);
+  if (dtype == P2PHD_BF16) return launch_gconv_tile(kTiles16, dtype, d, in, wp, bias, addend, out, stats, st, slot_rows);
+  if (dtype == P2PHD_F32) return launch_gconv_tile(kTilesF32, dtype, d, in, wp, bias, addend, out, stats, st, slot_rows);
   set_error("gconv: unsupported dtype %d", dtype);
   return P2PHD_EUNSUPPORTED;
 }
@@ -2196,14 +2219,12 @@ int launch_wgrad(const GDesc& d_in, const WMap& m, int dtype, const void* rows, 
   if (P == 0) {
     (void)hipMemsetAsync(dwp, 0, sizeof(float) * (size_t)slab, st);
     splits = 1;
-  } else if (dtype == P2PHD_BF16) {
-    if (tm == 32) launch_wgrad_cfg<bf16_t, 32>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
-    else if (tm == 256) launch_wgrad_cfg<bf16_t, 256>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
-    else launch_wgrad_cfg<bf16_t, 128>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
-  } else if (dtype == P2PHD_F32) {
-    if (tm == 32) launch_wgrad_cfg<float, 32>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
-    else if (tm == 256) launch_wgrad_cfg<float, 256>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
-    else launch_wgrad_cfg<float, 128>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
+  } else if (dtype == P2PHD_BF16 || dtype == P2PHD_F32) {
+    FOR_ELEM(dtype, T, {
+      if (tm == 32) launch_wgrad_cfg<T, 32>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
+      else if (tm == 256) launch_wgrad_cfg<T, 256>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
+      else launch_wgrad_cfg<T, 128>(d, rows, gat, dwp, Cp_r, mrows, sps, splits, slab, (unsigned)rbytes, st);
+    });
   } else {
     set_error("wgrad: unsupported dtype %d", dtype);
     return P2PHD_EUNSUPPORTED;
@@ -2233,10 +2254,7 @@ int launch_pack_merged(const GDesc& d, int dtype, const float* w, void* wp, int 
                        long s_k, long s_c, hipStream_t st) {
   const long total = (long)rows_pad * d.KK;
   const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
-  if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(pack_merged_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, d, w, (bf16_t*)wp, rows_pad, K, C, R, S, pad, s_k, s_c);
-  else
-    hipLaunchKernelGGL(pack_merged_kernel<float>, dim3(blocks), dim3(256), 0, st, d, w, (float*)wp, rows_pad, K, C, R, S, pad, s_k, s_c);
+  FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_merged_kernel<T>, dim3(blocks), dim3(256), 0, st, d, w, (T*)wp, rows_pad, K, C, R, S, pad, s_k, s_c));
   return check_launch("pack_weights(merged)");
 }
 
@@ -2246,41 +2264,26 @@ int launch_pack(const GDesc& d, const WMap& m, int dtype, const float* w, void* 
     const int row_len = d.nth * d.ntw * m.inner;
     const long total4 = (long)rows_pad * (d.KK / 4);
     const dim3 grid((unsigned)std::min<long>((total4 + 255) / 256, 8192));
-    if (dtype == P2PHD_BF16)
-      hipLaunchKernelGGL(pack_kmajor_dense_kernel<bf16_t>, grid, dim3(256), 0, st, w, (bf16_t*)wp, m.rows, rows_pad, row_len, d.KK);
-    else
-      hipLaunchKernelGGL(pack_kmajor_dense_kernel<float>, grid, dim3(256), 0, st, w, (float*)wp, m.rows, rows_pad, row_len, d.KK);
+    FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kmajor_dense_kernel<T>, grid, dim3(256), 0, st, w, (T*)wp, m.rows, rows_pad, row_len, d.KK));
     return check_launch("pack_weights(k-major)");
   }
   if (kmajor_transposed_map(d, m)) {
     const dim3 grid((unsigned)((std::max(m.inner, d.Cp_in) + 63) / 64), (unsigned)((rows_pad + 63) / 64), (unsigned)(d.nth * d.ntw));
-    if (dtype == P2PHD_BF16)
-      hipLaunchKernelGGL(pack_kmajor_transposed_kernel<bf16_t>, grid, dim3(64, 4), 0, st, d, m, w, (bf16_t*)wp, rows_pad);
-    else
-      hipLaunchKernelGGL(pack_kmajor_transposed_kernel<float>, grid, dim3(64, 4), 0, st, d, m, w, (float*)wp, rows_pad);
+    FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kmajor_transposed_kernel<T>, grid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(k-major transposed)");
   }
   if (dense_map(d, m)) {
     const dim3 dgrid((unsigned)((d.Cp_in + 63) / 64), (unsigned)((rows_pad + 3) / 4));
-    if (dtype == P2PHD_BF16)
-      hipLaunchKernelGGL(pack_dense_kernel<bf16_t>, dgrid, dim3(64, 4), 0, st, d, m, w, (bf16_t*)wp, rows_pad);
-    else
-      hipLaunchKernelGGL(pack_dense_kernel<float>, dgrid, dim3(64, 4), 0, st, d, m, w, (float*)wp, rows_pad);
+    FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_dense_kernel<T>, dgrid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(dense)");
   }
   if (transposed_map(d, m)) {
     const dim3 tgrid((unsigned)((d.Cp_in + 63) / 64), (unsigned)((rows_pad + 15) / 16));
-    if (dtype == P2PHD_BF16)
-      hipLaunchKernelGGL(pack_transposed_kernel<bf16_t>, tgrid, dim3(64, 4), 0, st, d, m, w, (bf16_t*)wp, rows_pad);
-    else
-      hipLaunchKernelGGL(pack_transposed_kernel<float>, tgrid, dim3(64, 4), 0, st, d, m, w, (float*)wp, rows_pad);
+    FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_transposed_kernel<T>, tgrid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(transposed)");
   }
   const dim3 grid((unsigned)std::min((d.Cp_in + 63) / 64, 64), (unsigned)((rows_pad + 3) / 4));
-  if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(pack_kernel<bf16_t>, grid, dim3(64, 4), 0, st, d, m, w, (bf16_t*)wp, rows_pad);
-  else
-    hipLaunchKernelGGL(pack_kernel<float>, grid, dim3(64, 4), 0, st, d, m, w, (float*)wp, rows_pad);
+  FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
   return check_launch("pack_weights");
 }
 
@@ -2301,10 +2304,7 @@ int launch_reflect_fold(int dtype, const void* dxp, const void* addend, void* dx
   const int epp = dtype == P2PHD_BF16 ? 8 : 4;
   const long total = (long)N * H * W * (Cp / epp);
   const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-  if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(reflect_fold_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)dxp, (const bf16_t*)addend, (bf16_t*)dx, N, H, W, Cp, P);
-  else
-    hipLaunchKernelGGL(reflect_fold_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)dxp, (const float*)addend, (float*)dx, N, H, W, Cp, P);
+  FOR_ELEM(dtype, T, hipLaunchKernelGGL(reflect_fold_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)dxp, (const T*)addend, (T*)dx, N, H, W, Cp, P));
   return check_launch("reflect_fold");
 }
 
@@ -2312,10 +2312,7 @@ int launch_reflect_expand(int dtype, const void* dy, void* e_out, int N, int H, 
   const int epp = dtype == P2PHD_BF16 ? 8 : 4;
   const long total = (long)N * (H + 2) * (W + 2) * (Cp / epp);
   const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-  if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(reflect_expand_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)dy, (bf16_t*)e_out, N, H, W, Cp);
-  else
-    hipLaunchKernelGGL(reflect_expand_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)dy, (float*)e_out, N, H, W, Cp);
+  FOR_ELEM(dtype, T, hipLaunchKernelGGL(reflect_expand_kernel<T>, dim3(blocks), dim3(256), 0, st, (const T*)dy, (T*)e_out, N, H, W, Cp));
   return check_launch("reflect_expand");
 }
 
@@ -2337,14 +2334,13 @@ int launch_colsum(int dtype, const void* x, long P, int Cp, int K, float* db, in
   P2PHD_REQUIRE(rows_max >= 1, "colsum: too many channels for the reduction scratch");
   const int xblocks = (int)std::max<long>(1, std::min<long>(std::min<long>((P + R * 32 - 1) / (R * 32), 512), rows_max));
   dim3 grid(xblocks, ygroups);
-  if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, P, Cp, K, db, cpg, accumulate, fs.part, fs.ticket);
-  else
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)x, P, Cp, K, db, cpg, accumulate, fs.part, fs.ticket);
+  FOR_ELEM(dtype, T, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, st, (const T*)x, P, Cp, K, db, cpg, accumulate, fs.part, fs.ticket));
   return check_launch("colsum");
 }
 
 }  // namespace p2phd
+
+#undef FOR_ELEM
 
 // Wait checker (-DP2PHD_CHECK_WAITS build, libp2phd_hip_chk.so): out[0] = bit mask of the kernel families (1 gather-GEMM generic
 // loop, 2 HALO loop, 4 weight gradient, 8 its f32 form) in which a relaxed s_waitcnt vmcnt(n) left a piece in flight that

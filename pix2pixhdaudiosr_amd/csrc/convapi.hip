@@ -149,9 +149,9 @@ bool merged_plan(int N, int Hin, int Win, int Cin, int Hout, int Wout, int Kout,
   {
     const long npix = (long)d.Hg * d.Wg;
     const bool taps_3x3 = R == 3 && S == 3 && pad == 1 && d.nth == 2 && d.ntw == 2 && lo == 0 && lo_w == 0;
-    const bool aligned = d.cls_cp >= 96 && (d.cls_cp % 192 == 0 || 192 % d.cls_cp == 0);
-    d.cls_skip = g_opt_cls_skip != 0 && dtype == P2PHD_BF16 && taps_3x3 && aligned && npix % 256 == 0 && d.Cp_in % 32 == 0 &&
-                 (long)N * (npix / 256) * (d.n_extent / 192) >= 192 ? 1 : 0;
+    const bool aligned = d.cls_cp >= kGconvCols192 / 2 && (d.cls_cp % kGconvCols192 == 0 || kGconvCols192 % d.cls_cp == 0);
+    d.cls_skip = g_opt_cls_skip != 0 && dtype == P2PHD_BF16 && taps_3x3 && aligned && npix % kGconvRows256 == 0 && d.Cp_in % 32 == 0 &&
+                 gconv_256x192_fills_chip(d, false) ? 1 : 0;
   }
   *out = p;
   return true;
@@ -274,6 +274,21 @@ bool reflect3x3(const p2phd_conv_desc* c) {
 }
 // ... whose input gradient can run on the exact H x W grid (see p2phd_conv_dgrad)
 bool reflect_exact_shape(const p2phd_conv_desc* c) { return reflect3x3(c) && fold_mode(c) != FOLD_OUT && c->H >= 4 && c->W >= 4; }
+// That launch: the transposed form on the exact H x W grid, reading L's packed weights.  pad_mode 2 gathers dy expanded by its
+// pair-sum rows / columns ([N][H + 2][W + 2][Cp(K)]), pad_mode 3 dy [N][H][W][Cp(K)] with the reflection extras
+// [N][2 (W + 2) + 2 H][Cp(K)] right behind it.
+int reflect_exact_plan(const Layer& L, int pad_mode, Plan* out) {
+  const p2phd_conv_desc* c = L.c;
+  const int grown = pad_mode == 2 ? 2 : 0;
+  std::vector<Plan> ex;
+  transposed_plans(c->N, c->H + grown, c->W + grown, c->K, c->H, c->W, c->C, c->R, c->S, 1, 1, ex);
+  P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == L.plans[0].d.KK && ex[0].rows_pad == L.plans[0].rows_pad, "conv_dgrad: reflect plan mismatch");
+  *out = ex[0];
+  out->w_off = L.plans[0].w_off;
+  out->d.pad_mode = pad_mode;
+  out->d.rx_base = pad_mode == 3 ? c->N * c->H * c->W : 0;
+  return P2PHD_OK;
+}
 
 // negative slope of an activation applied on load or in a backward pass (1 = none)
 float act_slope(int act) { return act == P2PHD_ACT_RELU ? 0.f : (act == P2PHD_ACT_LRELU ? 0.2f : 1.f); }
@@ -553,14 +568,10 @@ extern "C" int p2phd_conv_dgrad_rx(const p2phd_conv_desc* c, const void* dy, con
   if (c->N == 0) return P2PHD_OK;
   P2PHD_REQUIRE(dy && wp && dx, "conv_dgrad_rx: null pointer");
   P2PHD_REQUIRE(p2phd_conv_reflect_extras_elems(c) > 0, "conv_dgrad_rx: layer has no reflection-extras form (p2phd_conv_reflect_extras_elems)");
-  const Layer L = layer(c, 1);
-  std::vector<Plan> ex;
-  transposed_plans(c->N, c->H, c->W, c->K, c->H, c->W, c->C, c->R, c->S, 1, 1, ex);
-  P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == L.plans[0].d.KK && ex[0].rows_pad == L.plans[0].rows_pad, "conv_dgrad_rx: plan mismatch");
-  ex[0].d.pad_mode = 3;
-  ex[0].d.rx_base = c->N * c->H * c->W;                          // dy [N, H, W, Cp(K)], then the extras [N][2 (W + 2) + 2 H][Cp(K)]
-  return launch_gconv(ex[0].d, c->dtype, dy, static_cast<const char*>(wp) + L.plans[0].w_off * elem_size(c->dtype), nullptr, addend, dx,
-                      nullptr, (hipStream_t)stream);
+  Plan ex;
+  if (int rc = reflect_exact_plan(layer(c, 1), 3, &ex)) return rc;
+  return launch_gconv(ex.d, c->dtype, dy, static_cast<const char*>(wp) + ex.w_off * elem_size(c->dtype), nullptr, addend, dx, nullptr,
+                      (hipStream_t)stream);
 }
 
 extern "C" size_t p2phd_conv_dgrad_workspace_bytes(const p2phd_conv_desc* c) {
@@ -604,13 +615,10 @@ extern "C" int p2phd_conv_dgrad(const p2phd_conv_desc* c, const void* dy, const 
     // rows / columns holding the pair sums the mirrored taps need -- and the input gradient runs on the exact H x W grid
     // (pad_mode 2 gather), straight into dx with the skip gradient as addend: no padded-grid tensor (+19.5 % rows at
     // 32 x 16) and no fold pass
-    std::vector<Plan> ex;
-    transposed_plans(c->N, c->H + 2, c->W + 2, c->K, c->H, c->W, c->C, c->R, c->S, 1, 1, ex);
-    P2PHD_REQUIRE(ex.size() == 1 && ex[0].d.KK == L.plans[0].d.KK && ex[0].rows_pad == L.plans[0].rows_pad, "conv_dgrad: plan mismatch");
-    ex[0].d.pad_mode = 2;
+    Plan ex;
+    if (int rc = reflect_exact_plan(L, 2, &ex)) return rc;
     if (int rc = launch_reflect_expand(c->dtype, dy, workspace, c->N, c->H, c->W, cpitch(c->K), st)) return rc;
-    return launch_gconv(ex[0].d, c->dtype, workspace, static_cast<const char*>(wp) + L.plans[0].w_off * elem_size(c->dtype), nullptr,
-                        addend, dx, nullptr, st);
+    return launch_gconv(ex.d, c->dtype, workspace, static_cast<const char*>(wp) + ex.w_off * elem_size(c->dtype), nullptr, addend, dx, nullptr, st);
   }
   char* ws = static_cast<char*>(workspace);
   void* dxp = ws;                                   // padded-grid gradient (reflect only)
@@ -631,7 +639,7 @@ extern "C" int p2phd_conv_dgrad(const p2phd_conv_desc* c, const void* dy, const 
 // ---- input gradient with the consumer's InstanceNorm-backward sums fused into its store loop -------------------------
 namespace {
 // one plain or merged sub-pixel gather-GEMM launch writing dx directly (no reflect fold, no W-fold, not the 7x7 kernel),
-// on a tile shape that has the fused store loop (gconv 256x256 does not: see launch_gconv_t)
+// on a tile shape that has the fused store loop (gconv 256x256 does not: see gconv_choose_tile)
 bool bsum_layer(const p2phd_conv_desc* c, Layer* L) {
   if (check_desc(c) != P2PHD_OK || c->N == 0) return false;
   if (c->pad_mode == 1) return false;                            // (the output W-fold is fine: its launch writes dx directly too)
@@ -659,8 +667,17 @@ extern "C" int p2phd_conv_dgrad_bsum_ok(const p2phd_conv_desc* c) {
 extern "C" int p2phd_conv_dgrad_bsum_pays(const p2phd_conv_desc* c) {
   Layer L;
   if (!bsum_layer(c, &L)) return 0;
-  // (deep reductions only: on the generator's 3072..3456-deep layers the two extra reduce launches cost what the tile gains)
-  return (gconv_plain_launch_takes_256x256(L.plans[0].d, c->dtype) && L.plans[0].d.KK >= 6144) ? 0 : 1;
+  // The plain input gradient (no fused outputs, no statistics) on the 256 x 256 tile: that tile has no fused store loop, so the
+  // fused form falls back to 256 x 128 tiles and loses more (D 128->256 <- 256->512 at B = 64: 735 + 40 us against 539 + 89 us for
+  // plain input gradient + two-pass backward) than the saved pass is worth.  Deep reductions only: on the generator's
+  // 3072..3456-deep layers the two extra reduce launches cost what the tile gains.
+  GDesc plain = L.plans[0].d;
+  plain.bs_out = nullptr;
+  plain.as_x = nullptr;
+  const GconvTile t = gconv_choose_tile(plain, c->dtype, false);
+  // (gconv_bm = 192 leaves layers its own tile does not divide to the heuristic, 256 x 256 included; this advice has always
+  // answered "pays" under it, and which backward route a step takes is not this option's to change)
+  return (t.bm == 256 && t.bn == 256 && plain.KK >= 6144 && g_opt_gconv_bm != 192) ? 0 : 1;
 }
 
 extern "C" size_t p2phd_conv_dgrad_bsum_workspace_bytes(const p2phd_conv_desc* c) {
@@ -727,6 +744,57 @@ extern "C" int p2phd_conv_dgrad_act(const p2phd_conv_desc* c, const void* dy, co
   const void* src;
   if (int rc = bsum_src(L, dy, workspace, &src, st)) return rc;
   return launch_gconv(p.d, c->dtype, src, w, nullptr, addend, dx, nullptr, st);
+}
+
+// ---- which tile would each generic launch take? (host only: nothing is launched, no device is needed) ------------------
+// form: 0 forward, 1 input gradient on its generic plans, 2 input gradient on the exact reflect grid (dy expanded, pad_mode 2),
+// 3 the same through the reflection extras (pad_mode 3), 4 fp8 forward.  flags: 1 = InstanceNorm statistics wanted (forms 0, 4),
+// 2 = fused InstanceNorm-backward sums, 4 = fused activation backward (form 1, one of the two).  Writes 9 ints per launch --
+// the GconvTile fields, cls_skip, and the slot_rows launch_gconv reports -- for up to `cap` launches; returns the launch count
+// of the form under the current options, whichever route the entry point would take, or a negative error code when the form
+// or a flag does not apply to the layer.
+extern "C" int p2phd_conv_gconv_tiles(const p2phd_conv_desc* c, int form, int flags, int* out, int cap) {
+  if (int rc = check_desc(c)) return rc;
+  const bool stats = (flags & 1) != 0, sums = (flags & 2) != 0, act = (flags & 4) != 0;
+  P2PHD_REQUIRE(form >= 0 && form <= 4 && flags >= 0 && flags <= 7 && (out != nullptr || cap <= 0), "conv_gconv_tiles: bad form, flags or buffer");
+  P2PHD_REQUIRE(!stats || form == 0 || form == 4, "conv_gconv_tiles: statistics are taken by the forward forms");
+  P2PHD_REQUIRE(!(sums || act) || (form == 1 && !(sums && act)), "conv_gconv_tiles: the fused backward forms belong to form 1, one at a time");
+  int dtype = c->dtype;
+  Layer L;
+  std::vector<Plan> plans;
+  bool table = stats;                                            // does the launch get a statistics table?
+  if (form == 4) {
+    P2PHD_REQUIRE(fp8_eligible(c), "conv_gconv_tiles: layer not eligible for the fp8 forward");
+    plans.push_back(fp8_plan(c));
+    dtype = P2PHD_FP8_INTERNAL;
+  } else if (form == 2 || form == 3) {
+    P2PHD_REQUIRE(reflect_exact_shape(c), "conv_gconv_tiles: layer has no exact-grid reflect input gradient");
+    plans.resize(1);
+    if (int rc = reflect_exact_plan(layer(c, 1), form, &plans[0])) return rc;
+  } else if (sums || act) {
+    P2PHD_REQUIRE(bsum_layer(c, &L), "conv_gconv_tiles: this layer's input gradient has no fused form (p2phd_conv_dgrad_bsum_ok)");
+    plans = L.plans;
+    static float set;                                            // (the chooser asks "set or not" only)
+    if (sums) plans[0].d.bs_out = &set; else plans[0].d.as_x = &set;
+  } else {
+    L = layer(c, form);
+    plans = L.plans;
+    P2PHD_REQUIRE(!stats || plans.size() == 1, "conv_gconv_tiles: statistics need a single-launch plan");
+    if (L.fold == FOLD_OUT) table = false;                       // (output W-fold: the statistics come from a plane pass behind the launch)
+  }
+  if (c->N == 0) return 0;
+  int n = 0;
+  for (const Plan& p : plans) {
+    if (p.d.Hg * p.d.Wg == 0) continue;                          // (launch_gconv returns before launching)
+    const GconvTile t = gconv_choose_tile(p.d, dtype, table);
+    if (t.bm == 0) return P2PHD_EINVAL;
+    if (n < cap) {
+      const int row[9] = {t.bm, t.bn, t.mr, t.nr, t.nstage, t.halo, t.flat_m, p.d.cls_skip, gconv_slot_rows(t.bm, t.mr, p.d.bs_out != nullptr)};
+      std::copy(row, row + 9, out + 9 * n);
+    }
+    ++n;
+  }
+  return n;
 }
 
 namespace {

@@ -70,7 +70,9 @@ int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, in
 
 // launch counters (p2phd_launch_count): which kernel family a call really took -- tests assert that the benchmarked step runs
 // on the round-3..5 kernels and not on the generic loop behind them.  The dedicated routes (march, march_w, dfirst, dlast, c7,
-// thin_wgrad) are counted where convapi.hip picks them, the tile-level families (gconv .. tile128x192) inside conv.hip
+// thin_wgrad) are counted where convapi.hip picks them, the tile-level families (gconv .. tile128x192) inside conv.hip, where
+// launch_gconv_cfg runs the tile gconv_choose_tile picked; p2phd_conv_gconv_tiles (convapi.hip) answers on the host which tile
+// that is -- every instantiation, also those without a family of their own (256 x 128 with the HALO loop)
 enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192,
                     LC_DFIRST, LC_DLAST, LC_C7, LC_THIN_WGRAD, LC_TIMED_PACK, LC_TIMED_FRAMES, LC_STITCH, LC_PCM, LC_METRICS_ROWS,
                     LC_FAMILIES };
@@ -147,6 +149,19 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // with launch_stats_merge.  stat_table_floats() bounds its size for any tile configuration.
 int launch_gconv(const GDesc& d, int dtype, const void* in, const void* wp, const float* bias, const void* addend,
                  void* out, float* stats, hipStream_t st, int* slot_rows = nullptr);
+// The tile of one gather-GEMM launch: bm x bn outputs per workgroup, waves of (mr * 32) x (nr * 32), an LDS ring of nstage slots
+// (halo = 1: the HALO main loop of gconv_halo.inc instead), flat_m = M tiles run across samples.  gconv_choose_tile is the one
+// place that picks it -- a pure host function of the descriptor (bs_out / as_x count as set or not), the operand type (P2PHD_F32,
+// P2PHD_BF16 or P2PHD_FP8_INTERNAL) and the options gconv_bm / gconv_halo / tile128x192; bm == 0: refused, error text set.
+struct GconvTile { int bm, bn, mr, nr, nstage, halo, flat_m; };
+GconvTile gconv_choose_tile(const GDesc& d, int dtype, bool stats_wanted);
+// M tiles of 256 rows (per sample, or across samples when flat_m), and "the 256 x 192 tile's grid fills the chip": the chooser's
+// rule for that tile, which merged_plan (convapi.hip) applies when it plans a tap-skipping launch for it
+constexpr int kGconvRows256 = 256, kGconvCols192 = 192;
+long gconv_mtiles256(const GDesc& d, bool flat_m);
+bool gconv_256x192_fills_chip(const GDesc& d, bool flat_m);
+// rows per slot of the statistics table / per partial of the fused sums, as launch_gconv reports them through slot_rows
+inline int gconv_slot_rows(int bm, int mr, bool fused_sums) { return fused_sums ? bm : mr * 32; }   // (fused backward sums: one partial per TILE)
 inline size_t stat_table_floats(const GDesc& d) {
   return (size_t)d.N * ((d.Hg * d.Wg + 31) / 32) * (d.cls_cp > 0 ? 4 : 1) * d.Cp_out * 2;
 }
@@ -168,7 +183,6 @@ int launch_wgrad(const GDesc& d, const WMap& m, int dtype, const void* rows, int
 int launch_pack_merged(const GDesc& d, int dtype, const float* w, void* wp, int rows_pad, int K, int C, int R, int S, int pad,
                        long s_k, long s_c, hipStream_t st);
 int launch_pack(const GDesc& d, const WMap& m, int dtype, const float* w, void* wp, int rows_pad, hipStream_t st);
-bool gconv_plain_launch_takes_256x256(const GDesc& d, int dtype);
 int launch_reflect_expand(int dtype, const void* dy, void* e_out, int N, int H, int W, int Cp, hipStream_t st);
 int launch_reflect_fold(int dtype, const void* dxp, const void* addend, void* dx, int N, int H, int W, int Cp, int P,
                         hipStream_t st);

@@ -72,7 +72,7 @@ HALO_DGRAD = [                                                          # input 
 ]
 TILE128X192_FWD = L("t128x192_192to1536", 192, 1536, 3, 1, 1, 1, 0, 0, (32, 16, 8))
 # (input gradient: a 128-pixel plane reaches this tile only with per-sample tiles, i.e. with the fused InstanceNorm-backward sums,
-# which zero-padded layers have: conv.hip launch_gconv_t, `flat_m`)
+# which zero-padded layers have: conv.hip gconv_choose_tile, `flat_m`)
 TILE128X192_DGRAD = L("t128x192_1152to64", 1152, 64, 3, 1, 1, 0, 0, 0, (32, 16, 8))
 SPLITK = [
     L("c3_64to96", 64, 96, 3, 1, 1, 1, 0, 0, (3, 40, 28)),
