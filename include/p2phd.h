@@ -487,6 +487,19 @@ int p2phd_spectro_decode(const float* log_spectro, const float* norm_min_max, in
 int p2phd_spectro_decode_signed(const float* log_spectro, const float* pha, const float* norm_min_max, int64_t B, int64_t F,
                                 int64_t M, int channels, int keep_rows, float min_value, float scale, float* spec, void* stream);
 
+/* The same decode (util/util.py:104-126) with the low band taken from the input: sr_log_spectro (the generator's) and
+ * lr_log_spectro (the input's), both [B,channels,M,F] under the same (min,max).  With dec(X) = what
+ * p2phd_spectro_decode_signed writes for X, row m of spec is
+ *   dec(lr)[m]                                    m < keep_rows - fade_rows   (bit for bit)
+ *   s + w (l - s), s = dec(sr)[m], l = dec(lr)[m]  keep_rows - fade_rows <= m < keep_rows,
+ *       w = cos^2(pi (j + 1/2) / (2 fade_rows)), j = m - (keep_rows - fade_rows): the input's weight, fp32
+ *   dec(sr)[m]                                    m >= keep_rows              (bit for bit)
+ * A row reads only the tensors it decodes.  0 <= fade_rows <= keep_rows <= M.  One launch, nothing allocated, no
+ * synchronisation: capturable. */
+int p2phd_spectro_decode_spliced(const float* sr_log_spectro, const float* lr_log_spectro, const float* pha,
+                                 const float* norm_min_max, int64_t B, int64_t F, int64_t M, int channels,
+                                 int keep_rows, int fade_rows, float min_value, float scale, float* spec, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics (csrc/metrics.hip): compute_matrics (util/util.py:133-184).
  * hr, lr, sr [B,T] f32.  sr_matched [B,T] receives sr moment-matched to hr (:139-140); result4 (device) receives

@@ -182,6 +182,69 @@ __global__ __launch_bounds__(256) void decode_signed_kernel(const float* __restr
   }
 }
 
+// One element of decode_signed_kernel for tensor x: the same expressions in the same order, so a row decoded here carries
+// the bits that kernel writes for it.  `sgn` is the pha value (not read where the channels give the sign).
+__device__ __forceinline__ float decode_signed_at(const float* __restrict__ x, size_t o, size_t plane, float sgn, int channels,
+                                                  bool sign_from_channels, float mn, float range, float min_value, float scale) {
+  const float a0 = 10.f * exp10f((fabsf(x[o]) * range + mn) * 0.05f) - min_value;
+  float amp = a0;
+  if (channels == 2) {
+    const float a1 = 10.f * exp10f((fabsf(x[o + plane]) * range + mn) * 0.05f) - min_value;
+    amp = a0 + a1;
+    if (sign_from_channels) sgn = a0 > a1 ? 1.f : (a0 < a1 ? -1.f : 0.f);
+  }
+  return amp * sgn * scale;
+}
+
+// s + w (l - s) from rounded operands, one rounding per operation: no contraction across the decode, so that l == s gives s.
+__device__ __forceinline__ float splice_blend(float s, float l, float w) {
+#pragma clang fp contract(off)
+  const float d = l - s;
+  const float wd = w * d;
+  return s + wd;
+}
+
+// decode_signed_kernel with the low band taken from the input's own spectrogram: rows below keep - fade decode `lr`, rows
+// from keep decode `sr`, the fade rows between cross-fade the two decoded values with the input's weight
+// w = cos^2(pi (j + 1/2) / (2 fade)) = (1 + cos(pi (2 j + 1) / (2 fade))) / 2, j = m - (keep - fade).  A row loads only
+// the tensors it decodes (and pha only where it gives the sign).  Same tile, grid and block as decode_signed_kernel.
+__global__ __launch_bounds__(256) void decode_spliced_kernel(const float* __restrict__ sr, const float* __restrict__ lr,
+                                                             const float* __restrict__ pha, const float* __restrict__ norm2,
+                                                             float* __restrict__ spec, int F, int M, int channels, int keep,
+                                                             int fade, float min_value, float scale) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, m0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const float mn = norm2[0], range = norm2[1] - norm2[0];
+  const size_t plane = (size_t)M * F;
+  const int lo = keep - fade;                                     // first fade row
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty + 8 * i, f = f0 + tx;
+    float v = 0.f;
+    if (m < M && f < F) {
+      const size_t o = ((size_t)b * channels * M + m) * F + f;
+      const bool from_channels = channels == 2 && m >= keep;
+      const float sgn = from_channels ? 0.f : pha[((size_t)b * M + m) * F + f];
+      if (m >= keep) {
+        v = decode_signed_at(sr, o, plane, sgn, channels, from_channels, mn, range, min_value, scale);
+      } else if (m < lo) {
+        v = decode_signed_at(lr, o, plane, sgn, channels, false, mn, range, min_value, scale);
+      } else {
+        const float s = decode_signed_at(sr, o, plane, sgn, channels, false, mn, range, min_value, scale);
+        const float l = decode_signed_at(lr, o, plane, sgn, channels, false, mn, range, min_value, scale);
+        const float w = 0.5f + 0.5f * cospif((float)(2 * (m - lo) + 1) / (float)(2 * fade));
+        v = splice_blend(s, l, w);
+      }
+    }
+    tile[ty + 8 * i][tx] = v;
+  }
+  __syncthreads();
+  for (int i = 0; i < 4; ++i) {
+    const int f = f0 + ty + 8 * i, m = m0 + tx;
+    if (f < F && m < M) spec[((size_t)b * F + f) * M + m] = tile[tx][ty + 8 * i];
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t p2phd_spectro_partials_floats(int64_t B, int64_t F, int64_t M) {
@@ -250,4 +313,22 @@ extern "C" int p2phd_spectro_decode_signed(const float* log_spectro, const float
   hipLaunchKernelGGL(decode_signed_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, log_spectro, pha, norm_min_max, spec, (int)F,
                      (int)M, channels, keep_rows, min_value, scale);
   return p2phd::check_launch("spectro_decode_signed");
+}
+
+extern "C" int p2phd_spectro_decode_spliced(const float* sr_log_spectro, const float* lr_log_spectro, const float* pha,
+                                            const float* norm_min_max, int64_t B, int64_t F, int64_t M, int channels,
+                                            int keep_rows, int fade_rows, float min_value, float scale, float* spec,
+                                            void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_decode_spliced: bad geometry");
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_decode_spliced: channels must be 1 or 2, got %d", channels);
+  P2PHD_REQUIRE(keep_rows >= 0 && keep_rows <= M, "spectro_decode_spliced: keep_rows %d outside [0, %lld]", keep_rows, (long long)M);
+  P2PHD_REQUIRE(fade_rows >= 0 && fade_rows <= keep_rows, "spectro_decode_spliced: fade_rows %d outside [0, keep_rows = %d]",
+                fade_rows, keep_rows);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(sr_log_spectro && lr_log_spectro && pha && norm_min_max && spec, "spectro_decode_spliced: null pointer");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode_spliced: grid too large");
+  dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(decode_spliced_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, sr_log_spectro, lr_log_spectro, pha,
+                     norm_min_max, spec, (int)F, (int)M, channels, keep_rows, fade_rows, min_value, scale);
+  return p2phd::check_launch("spectro_decode_spliced");
 }

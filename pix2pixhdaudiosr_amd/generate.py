@@ -163,6 +163,20 @@ def select_channels(channels, available):
     return min(channels, int(available))
 
 
+LOWBANDS = ('model', 'input')
+
+
+def check_lowband(lowband, lowband_fade, bins, up_ratio):
+    """Validates the low-band options of SuperResolver for a spectrogram of `bins` rows: `lowband` is 'model' or 'input' and
+    `lowband_fade` a whole number of rows in [0, keep], keep = int(bins / up_ratio) -- the rows the low-rate input carried
+    (all of them at up_ratio <= 1).  Returns (lowband, lowband_fade, keep)."""
+    from .util.util import check_lowband_fade, lowband_keep_rows
+    if lowband not in LOWBANDS:
+        raise ValueError("SuperResolver: lowband must be 'model' or 'input', got %r" % (lowband,))
+    keep = lowband_keep_rows(bins, up_ratio)
+    return lowband, check_lowband_fade(lowband_fade, keep, "SuperResolver"), keep
+
+
 def plan_folder(dir_in, dir_out):
     """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
     output keeps the relative path under dir_out.  Other files are ignored."""
@@ -185,9 +199,16 @@ class SuperResolver:
     (options that draw random numbers inside the chain -- mask_mode 'mode1', the single-channel encodings -- run eagerly).
     `reference_amplitude` (mdct2 only): True keeps the amplitude of the reference's generate_audio.py, which is
     sqrt(up_ratio - 1) * x / 2 for a spectrogram that encodes x; False returns sqrt(up_ratio - 1) * x.  Default: True at
-    overlap 0, the reference-exact mode, False with overlapping segments."""
+    overlap 0, the reference-exact mode, False with overlapping segments.
+    `lowband`: 'model' (default) decodes every row of the generator's spectrogram; 'input' keeps the input's own low band:
+    the rows below keep = int(bins / up_ratio), which the low-rate input carried, are decoded from the input's spectrogram
+    (the fourth value of `inference`) and only the rows from keep come from the generator (util.imdct, `lr_spectro`).
+    `lowband_fade`: rows below keep over which the two are cross-faded, 0 (a hard switch at keep) .. keep.  Both are fixed
+    for the object's life, so the captured chain holds them.  With up_ratio <= 1 keep is every row: 'input' is accepted and
+    returns the input's own transform round trip."""
 
-    def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None):
+    def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
+                 lowband_fade=0):
         from .models.mdct import IMDCT2, IMDCT4
         from .util import util as U
         self.model, self.opt = model, opt
@@ -212,6 +233,8 @@ class SuperResolver:
             raise ValueError("SuperResolver: mdct_type must be 'mdct2' or 'mdct4', got %r" % (self.mdct_type,))
         if self.up_ratio < 1:
             raise ValueError("SuperResolver: lr_sampling_rate above hr_sampling_rate")
+        bins = int(opt.n_fft) if self.mdct_type == 'mdct2' else int(opt.n_fft) // 2
+        self.lowband, self.lowband_fade, _ = check_lowband(lowband, lowband_fade, bins, self.up_ratio)
         # Both inverse transforms return x for the spectrogram of x and util.imdct halves that (util/util.py:127 of the
         # reference), so the hand-composed chain is a factor 2 short of generate_audio.py:47's sqrt(up_ratio - 1) * x; the
         # stitch gain puts the factor back.  The reference's own output (MDCT2, back-to-back segments; tests/golden/generate.npz)
@@ -244,9 +267,10 @@ class SuperResolver:
     def _group(self, seg, noise):
         """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44)."""
         from .util import util as U
-        sr_spectro, lr_pha, norm_param, _ = self.model.inference(seg, None, noise=noise)
+        sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
+        splice = {} if self.lowband == 'model' else dict(lr_spectro=lr_spectro, lowband_fade=self.lowband_fade)
         audio = U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=self._imdct,
-                        up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)))
+                        up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)), **splice)
         audio = audio.reshape(seg.shape[0], -1)
         if audio.shape[1] != self.T:
             raise ValueError("SuperResolver: segment_length %d does not come back from the transform (got %d samples): use "
@@ -569,6 +593,13 @@ def _parser():
     ap.add_argument("--reference_amplitude", type=int, choices=(0, 1), default=None,
                     help="MDCT2 checkpoints: 1 keeps the half amplitude of the reference's generate_audio.py, 0 writes the full "
                          "one, 6 dB more (default: 1 at --overlap 0, the reference-exact mode, else 0)")
+    ap.add_argument("--lowband", default="model", choices=LOWBANDS,
+                    help="where the band the input already had comes from: the generator's spectrogram like every other row "
+                         "(model, default), or the input's own spectrogram (input): only the rows from the low rate's Nyquist "
+                         "frequency up are then the generator's")
+    ap.add_argument("--lowband_fade", type=int, default=0, metavar="N",
+                    help="--lowband input: cross-fade input and generator over the N spectrogram rows below that frequency "
+                         "(default 0: a hard switch)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -613,6 +644,11 @@ def main(argv=None):
     opt = opt_from_file(a.opt_file or os.path.join(folder, "opt.txt"), **over)
     if a.mdct_type is not None or not hasattr(opt, 'mdct_type'):
         opt.mdct_type = a.mdct_type or os.environ.get('P2PHD_MDCT_TYPE', 'mdct2')
+    try:                                                                    # before the model is built
+        check_lowband(a.lowband, a.lowband_fade, int(opt.n_fft) if opt.mdct_type == 'mdct2' else int(opt.n_fft) // 2,
+                      opt.hr_sampling_rate / opt.lr_sampling_rate)
+    except ValueError as e:
+        ap.error(str(e))
     from .models.models import create_model
     model = create_model(opt)
     model.eval()
@@ -620,8 +656,11 @@ def main(argv=None):
     if seed is not None:
         torch.manual_seed(int(seed))                                        # the mask noise: one run, one result
     sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
-                       reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude))
-    print('amplitude: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full'))
+                       reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
+                       lowband=a.lowband, lowband_fade=a.lowband_fade)
+    print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
+                                           "the model's" if sr.lowband == 'model' else
+                                           "the input's (fade over %d rows)" % sr.lowband_fade))
     rate = int(opt.hr_sampling_rate)
     if folder_mode:
         def report(r):

@@ -53,11 +53,35 @@ def kbdwin(N: int, beta: float = 12.0, device='cpu') -> torch.Tensor:
     return torch.cat((wdw_half, wdw_half.flip(dims=(0,))), dim=0)
 
 
-def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit_encoding=False):
+def lowband_keep_rows(bins, up_ratio):
+    """Rows of a `bins`-row spectrogram that the low-rate input carried: util/util.py:113 of the reference (all of them at
+    up_ratio <= 1)."""
+    return int(bins * (1 / up_ratio)) if up_ratio > 1 else int(bins)
+
+
+def check_lowband_fade(lowband_fade, keep, who="imdct"):
+    """The fade of the low-band splice is a whole number of rows in [0, keep]; returns it as an int."""
+    if isinstance(lowband_fade, bool) or not isinstance(lowband_fade, (int, np.integer)):
+        raise ValueError(f"{who}: lowband_fade must be an int (rows), got {lowband_fade!r}")
+    if not 0 <= lowband_fade <= keep:
+        raise ValueError(f"{who}: lowband_fade {lowband_fade} outside [0, {keep}] (the rows the input carried)")
+    return int(lowband_fade)
+
+
+def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit_encoding=False, lr_spectro=None, lowband_fade=0):
     """Generation tail of the reference (util/util.py:104-131, caller generate_audio.py:40-42): de-normalise, dB ->
     amplitude, restore the sign (LR sign on the low band, sign(ch0 - ch1) -- or a random sign without explicit
     encoding -- above it), and run the inverse transform `_imdct` on [B, frames, bins]; returns `_imdct(.) / 2`.
-    One HIP launch (p2phd_spectro_decode_signed) replaces the elementwise chain and the permute."""
+    One HIP launch (p2phd_spectro_decode_signed) replaces the elementwise chain and the permute.
+
+    `lr_spectro` (default None: the chain above, unchanged): the input's own encoding, shaped like `spectro` and under the same
+    `norm_param` -- the fourth value of `model.inference`.  The rows below `keep = int(M / up_ratio)`, whose sign already
+    comes from the input, then take their amplitude from it as well (p2phd_spectro_decode_spliced): rows < keep -
+    lowband_fade are the input's, rows >= keep the generator's, and the `lowband_fade` rows between cross-fade the two
+    decoded values with the input's weight cos^2(pi (j + 1/2) / (2 lowband_fade)).  This rests on one fact: the mask noise of
+    `to_spectro` fills the top int(M * (1 - 1 / up_ratio)) rows, and M - int(M * (1 - 1 / up_ratio)) >= int(M / up_ratio)
+    = keep, so every noise row is a row >= keep and the spliced rows of `lr_spectro` never hold noise.  With up_ratio <= 1
+    keep = M: every row is the input's, and the result is the input's own transform round trip."""
     from .. import _lib
     dev = spectro.device
     _lib.require_gpu_tensor(spectro, "spectro")
@@ -74,6 +98,17 @@ def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit
     if p.shape[0] != B:
         raise ValueError(f"imdct: pha batch {p.shape[0]} != spectro batch {B}")
     keep = int(M * (1 / up_ratio)) if up_ratio > 1 else M
+    lr = None
+    if lr_spectro is not None:
+        if not isinstance(lr_spectro, torch.Tensor) or not lr_spectro.is_cuda:
+            raise _lib.P2PHDError("lr_spectro: expected a tensor on the GPU (this build has no CPU path)")
+        lr = lr_spectro.float()
+        if lr.dim() == 3:
+            lr = lr.unsqueeze(1)
+        if lr.shape != x.shape:
+            raise ValueError(f"imdct: lr_spectro shape {tuple(lr.shape)} != spectro shape {tuple(x.shape)}")
+        lr = lr.contiguous()
+        fade = check_lowband_fade(lowband_fade, keep)
     if not explicit_encoding and keep < M:
         pseudo = (2 * torch.randint(low=0, high=2, size=(B, M, Fr), device=dev) - 1).float()
         p = torch.cat((p[:, :keep], pseudo[:, keep:]), dim=1)
@@ -81,6 +116,11 @@ def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit
     mm = torch.stack([torch.as_tensor(norm_param['min']).float().reshape(()),
                       torch.as_tensor(norm_param['max']).float().reshape(())]).to(dev).contiguous()
     spec = torch.empty((B, Fr, M), dtype=torch.float32, device=dev)
+    if lr is not None:
+        _lib.check(_lib.lib().p2phd_spectro_decode_spliced(_lib.ptr(x), _lib.ptr(lr), _lib.ptr(p), _lib.ptr(mm), B, Fr, M, Cc, keep,
+                                                           fade, float(min_value), 1.0, _lib.ptr(spec), _lib.stream_ptr()),
+                   "spectro_decode_spliced")
+        return _imdct(spec) / 2
     _lib.check(_lib.lib().p2phd_spectro_decode_signed(_lib.ptr(x), _lib.ptr(p), _lib.ptr(mm), B, Fr, M, Cc, keep,
                                                       float(min_value), 1.0, _lib.ptr(spec), _lib.stream_ptr()),
                "spectro_decode_signed")

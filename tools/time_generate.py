@@ -13,11 +13,16 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             file, what the package did before the device codec) and generate.SuperResolver.enhance_folder(channels='all')
             on the stereo files; --reps repeats each, best and spread; log in --folder_log
 
+  lowband   (only when asked for) generate.SuperResolver(lowband='model') against lowband='input' (fade 0 and 8 rows), graphed,
+            overlap 0.25: seconds of audio per second, best of --reps with the spread, and lsd_lf / lsd_hf of each output against
+            a full-band original whose low-rate round trip is the input; log in --lowband_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
 Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] [--reps 5] [--log profiles/time_generate.log]
         python tools/time_generate.py folder [--files 8] [--folder_log profiles/time_generate_folder.log]
+        python tools/time_generate.py lowband [--lowband_log profiles/time_generate_lowband.log]
 """
 import argparse
 import os
@@ -156,6 +161,54 @@ def run_folder(seconds, reps, files, log):
         f.write(text)
 
 
+def run_lowband(seconds, reps, log):
+    """Seconds of audio per second of the graphed pipeline at overlap 0.25 with the model's and with the input's low band, the
+    runs of the variants interleaved so that a drift of the machine falls on all of them; and what each does to the two bands."""
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    from pix2pixhdaudiosr_amd.util import util as U
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    # the full-band original: the band-limited clip plus partials and noise above the low rate's 4 kHz
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float().cuda()[None]
+    lr = lr_round_trip(hr, opt.hr_sampling_rate, opt.lr_sampling_rate, opt.hr_sampling_rate)[..., :n].contiguous()
+    variants = [("lowband model          ", dict()), ("lowband input, fade 0  ", dict(lowband='input')),
+                ("lowband input, fade 8  ", dict(lowband='input', lowband_fade=8))]
+    srs = [SuperResolver(model, opt, overlap=0.25, **kw) for _, kw in variants]
+    lines = ["# tools/time_generate.py lowband: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; "
+             "%g s synthetic clip at 48 kHz, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    outs = []
+    for sr in srs:                                                 # warm-up and capture; the same noise seed for every variant
+        sr.enhance_lr(lr)
+        torch.manual_seed(99)
+        outs.append(sr.enhance_lr(lr))
+    torch.cuda.synchronize()
+    ts = [[] for _ in srs]
+    for _ in range(reps):
+        for k, sr in enumerate(srs):
+            t0 = time.perf_counter()
+            sr.enhance_lr(lr)
+            torch.cuda.synchronize()
+            ts[k].append(time.perf_counter() - t0)
+    for (name, _), tk, y in zip(variants, ts, outs):
+        rates = sorted(seconds / v for v in tk)
+        e = U.compute_matrics_ext(hr, lr, y, opt)[0]
+        lines.append("%s best %8.1f s of audio / s   spread %6.1f (worst %8.1f)   lsd_lf %.4f  lsd_hf %.4f  lsd %.4f   runs: %s"
+                     % (name, rates[-1], rates[-1] - rates[0], rates[0], e['lsd_lf'], e['lsd_hf'], e['lsd'],
+                        " ".join("%.1f" % (seconds / v) for v in tk)))
+    e = U.compute_matrics_ext(hr, lr, lr, opt)[0]
+    lines.append("the input itself as output                                                                lsd_lf %.4f  lsd_hf %.4f  lsd %.4f"
+                 % (e['lsd_lf'], e['lsd_hf'], e['lsd']))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def run_mode(mode, seconds, reps):
     torch, model, opt, lr = _setup(seconds)
     from pix2pixhdaudiosr_amd.generate import SuperResolver, segment_plan
@@ -185,15 +238,18 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
+    ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "folder":
         return run_folder(a.seconds, a.reps, a.files, a.folder_log)
+    if a.mode == "lowband":
+        return run_lowband(a.seconds, a.reps, a.lowband_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
