@@ -84,8 +84,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * "march" / "march_w" (marching kernels), "wgrad" (MFMA weight gradient), and the dedicated single-layer kernels "dfirst",
  * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them), "timed_pack" / "timed_frames" (the time-domain
  * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
- * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode and encode of its file ends,
- * csrc/pcm.hip).  family == NULL with reset != 0 clears all.
+ * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
+ * ends, csrc/pcm.hip).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -221,6 +221,29 @@ int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t
  *   2^(bits-1), round half to even -- for PCM16 the bytes data/wavio.py save writes.  NaN encodes as 0 (wavio.save leaves
  *   that case undefined: the int16 conversion of a NaN is whatever the host gives).  P2PHD_PCM_F32: a bit copy.  Other
  *   formats: P2PHD_EINVAL.
+ *
+ * The output stage (opt-in; p2phd_pcm_encode is unchanged).  Each of the two counts 1 in the launch family "pcm".
+ * p2phd_pcm_peak: what the encoder of `format` (P2PHD_PCM_S16 / _S24 / _F32) would meet in the rows of `planar` (layout and
+ *   argument checks of p2phd_pcm_encode).  Per channel c: peak[c] = max |x| over the finite samples (0 for an empty row or one
+ *   without a finite sample); over[c] = samples the encoder would clamp -- x > hi or x < -1 with hi = (2^(bits-1) - 1) / 2^(bits-1)
+ *   for the integer formats, |x| > 1 for float32; +-inf counts, NaN does not; nonfinite[c] = NaN and +-inf samples.  And one gain
+ *   for all channels (the stereo image is kept): with m = max_c peak[c], gain[0] = m > ceiling ? ceiling / m : 1 -- one fp32
+ *   division; ceiling <= 0 stands for hi of the format (1 for float32).  All four are device pointers, written by every call
+ *   (frames = 0 included) without having been zeroed, and hold the same bits on every run: a maximum of bit patterns and integer
+ *   counts, folded by the last workgroup; no float atomics, no host synchronisation.  Like every fixed-order reduction of the
+ *   library, two calls must be ordered (see "Streams" above).
+ * p2phd_pcm_encode_ex: y = x * gain[0] (`gain`: device pointer, e.g. the one p2phd_pcm_peak wrote, read by the kernel; NULL: y = x).
+ *   Integer formats: v = y * 2^(bits-1), v = v + d when dithering (one fp32 addition), r = rint(v) clamped to
+ *   [-2^(bits-1), 2^(bits-1) - 1]; NaN -> 0.  float32 writes the bits of y.  dither: 0 = none, 1 = TPDF of +-1 LSB, P2PHD_PCM_S16
+ *   only (with another format: P2PHD_EINVAL).  The dither of the interleaved sample with global index
+ *   i = first_index + frame * channels + c (64-bit) is, in uint32 arithmetic,
+ *     fmix(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16
+ *     h = fmix(lo(i) ^ fmix(hi(i) ^ lo(seed) ^ 0x9E3779B9) ^ hi(seed))
+ *     d = ((int)(h & 0xFFFF) - (int)(h >> 16)) * 2^-16            exact in fp32, in (-1, 1), triangular
+ *   so a payload encoded in pieces (first_index = samples before the piece, >= 0) has the bytes of one call.  By construction
+ *   (seed, i) = (0, 2^32) and (1, 0) draw the same value: harmless, the streams of two seeds are otherwise unrelated.
+ *   gain = NULL and dither = 0: the bytes of p2phd_pcm_encode for every input (clamping before or after rounding gives the
+ *   same codes).
  * ---------------------------------------------------------------------------------------- */
 #define P2PHD_PCM_U8  0   /* format tag 1,  8 bit */
 #define P2PHD_PCM_S16 1   /* format tag 1, 16 bit */
@@ -230,6 +253,10 @@ int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t
 #define P2PHD_PCM_F64 5   /* format tag 3, 64 bit */
 int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels, int format, float* out, int64_t ld, void* stream);
 int p2phd_pcm_encode(const float* planar, int64_t frames, int channels, int64_t ld, int format, void* out, void* stream);
+int p2phd_pcm_peak(const float* planar, int64_t frames, int channels, int64_t ld, int format, float ceiling, float* peak,
+                   int64_t* over, int64_t* nonfinite, float* gain, void* stream);
+int p2phd_pcm_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
+                        uint64_t seed, int64_t first_index, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -50,6 +50,8 @@ SIGNATURES = {
     "p2phd_segments_stitch_planar": (_i32, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _i64, _i64, _vp]),
     "p2phd_pcm_decode": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "p2phd_pcm_encode": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "p2phd_pcm_peak": (_i32, [_vp, _i64, _i32, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "p2phd_pcm_encode_ex": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, C.c_uint64, _i64, _vp, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

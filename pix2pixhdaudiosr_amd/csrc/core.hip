@@ -29,14 +29,16 @@ int device_cus() {
 
 // scratch of the fixed-order cross-workgroup reductions (common.h): zero-initialised with the code object
 namespace {
-constexpr size_t kFoldFloats[5] = {size_t(4) << 20, size_t(1) << 20, size_t(1) << 20, 4096, size_t(16) << 20};
-constexpr int kFoldTickets[5] = {2048, 1024, 8, 8, 256};
-__device__ float g_fold_part[(size_t(22) << 20) + 4096];      // 88 MiB, zero-initialised with the code object
-__device__ unsigned g_fold_ticket[2048 + 1024 + 16 + 256];
+constexpr int kFoldRegions = 6;
+constexpr size_t kFoldFloats[kFoldRegions] = {size_t(4) << 20, size_t(1) << 20, size_t(1) << 20, 4096, size_t(16) << 20, size_t(5) << 16};
+constexpr int kFoldTickets[kFoldRegions] = {2048, 1024, 8, 8, 256, 8};
+constexpr int kFoldTicketsAll = 2048 + 1024 + 16 + 256 + 8;
+__device__ float g_fold_part[(size_t(22) << 20) + 4096 + (size_t(5) << 16)];      // 89 MiB, zero-initialised with the code object
+__device__ unsigned g_fold_ticket[kFoldTicketsAll];
 }  // namespace
 namespace p2phd {
 namespace {
-struct FoldDev { float* part = nullptr; unsigned* ticket = nullptr; hipStream_t last[5] = {}; bool used[5] = {}; hipEvent_t ev[5] = {}; bool ev_set[5] = {}; };
+struct FoldDev { float* part = nullptr; unsigned* ticket = nullptr; hipStream_t last[kFoldRegions] = {}; bool used[kFoldRegions] = {}; hipEvent_t ev[kFoldRegions] = {}; bool ev_set[kFoldRegions] = {}; };
 FoldDev g_fold_dev[64];
 thread_local hipStream_t g_fold_pending_stream = nullptr;
 FoldDev* fold_dev() {
@@ -67,7 +69,7 @@ thread_local int g_fold_pending = -1;
 // capture is entered behind a synchronisation), so they neither wait nor record.
 FoldScratch fold_scratch(int region, hipStream_t stream) {
   FoldDev* f = fold_dev();
-  if (f == nullptr || region < 0 || region >= 5) { set_error("reduction scratch unavailable"); return FoldScratch{nullptr, nullptr, 0, 0}; }
+  if (f == nullptr || region < 0 || region >= kFoldRegions) { set_error("reduction scratch unavailable"); return FoldScratch{nullptr, nullptr, 0, 0}; }
   const bool cap = capturing(stream);
   if (f->used[region] && f->last[region] != stream && f->ev_set[region] && !cap) {
     if (hipStreamWaitEvent(stream, f->ev[region], 0) != hipSuccess) {
@@ -90,7 +92,7 @@ void fold_launched() {
   const int region = g_fold_pending;
   g_fold_pending = -1;
   FoldDev* f = fold_dev();
-  if (f == nullptr || region < 0 || region >= 5) return;
+  if (f == nullptr || region < 0 || region >= kFoldRegions) return;
   if (f->ev[region] == nullptr && hipEventCreateWithFlags(&f->ev[region], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); f->ev[region] = nullptr; return; }
   if (hipEventRecord(f->ev[region], g_fold_pending_stream) == hipSuccess) f->ev_set[region] = true;
   else (void)hipGetLastError();
@@ -103,7 +105,7 @@ void fold_launched() {
 extern "C" int p2phd_reduction_reset(void* stream) {
   void* t = nullptr;
   if (hipGetSymbolAddress(&t, HIP_SYMBOL(g_fold_ticket)) != hipSuccess) { p2phd::set_error("reduction_reset: no device symbol"); return P2PHD_ELAUNCH; }
-  if (hipMemsetAsync(t, 0, sizeof(unsigned) * (2048 + 1024 + 16 + 256), (hipStream_t)stream) != hipSuccess) {
+  if (hipMemsetAsync(t, 0, sizeof(unsigned) * kFoldTicketsAll, (hipStream_t)stream) != hipSuccess) {
     p2phd::set_error("reduction_reset: memset failed");
     return P2PHD_ELAUNCH;
   }

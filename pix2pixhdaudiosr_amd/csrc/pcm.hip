@@ -5,6 +5,18 @@
 //           conversion and an exact power-of-two scale (data/wavio.py load), so the result is the bits wavio.load returns.
 //   encode  planar fp32 -> interleaved payload: PCM16 / PCM24 (clamp, scale, round half to even; NaN -> 0) or a float32 bit copy.
 //
+// and the output stage in front of the encoder, for a file that must not clip silently (all opt-in: p2phd_pcm_encode is as it was):
+//
+//   peak       per channel max |x| over the finite samples, the number of samples the encoder of the format would clamp and
+//              the number of NaN / inf samples; one gain for all channels, gain = m > ceiling ? ceiling / m : 1 with m the
+//              largest channel peak.  A maximum of bit patterns and integer counts: the same bits on every run.  Workgroup
+//              partials are stored and folded by the last workgroup (common.h: fold_arrive_last), so nothing is zeroed before
+//              the launch and there is no float atomic.  HBM-bound: 16-byte pieces, four in flight per thread.
+//   encode_ex  y = x * gain[0] (read from device memory: the peak launch in front needs no host round trip), v = y * 2^(bits-1)
+//              [+ d], r = rint(v) clamped to the integer range, NaN -> 0; float32 writes y.  d: TPDF dither of +-1 LSB for
+//              PCM16, a counter-based hash of (seed, index of the interleaved sample) -- a payload encoded in pieces, or twice,
+//              gets the same bytes.  Without gain and dither: the bytes of `encode`.
+//
 // Streaming kernels, one thread per sample of the interleaved stream: the payload side is contiguous across a wave, the
 // planar side is `channels` contiguous runs.  The payload pointer has byte alignment only (24-bit samples, a data chunk
 // at any file offset): typed loads / stores where the pointer is aligned to the sample size, byte accesses otherwise.
@@ -80,6 +92,152 @@ __global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const uint32_t* __
   }
 }
 
+// ---- output stage: peak report, clip guard, dither ----------------------------------------------------------------------
+// TPDF dither of the interleaved sample with global index i, in LSB: the difference of the two 16-bit halves of a hash of
+// (seed, i), times 2^-16 -- exact in fp32, in (-1, 1), triangular.  fmix is the 32-bit finaliser of MurmurHash3.
+__device__ __forceinline__ uint32_t fmix(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+__device__ __forceinline__ float tpdf(uint64_t seed, uint64_t i) {
+  const uint32_t h = fmix((uint32_t)i ^ fmix((uint32_t)(i >> 32) ^ (uint32_t)seed ^ 0x9E3779B9u) ^ (uint32_t)(seed >> 32));
+  return (float)((int)(h & 0xFFFFu) - (int)(h >> 16)) * (1.0f / 65536.0f);
+}
+
+// y * 2^(bits-1) [+ d], round half to even, clamp to the integer range; NaN -> 0
+template <int BITS> __device__ __forceinline__ uint32_t quantise_ex(float y, float d, bool dither) {
+  constexpr float scale = (float)(1u << (BITS - 1));
+  float v = y * scale;
+  if (dither) v = v + d;
+  if (v != v) return 0u;
+  return (uint32_t)(int32_t)fminf(fmaxf(rintf(v), -scale), scale - 1.0f);
+}
+
+template <int FORMAT, int BYTES, bool DITHER>
+__global__ __launch_bounds__(kThreads) void pcm_encode_ex_kernel(const uint32_t* __restrict__ planar, long frames, long channels, long ld,
+                                                                 const float* __restrict__ gain, uint64_t seed, uint64_t first_index,
+                                                                 uint8_t* __restrict__ out, int aligned) {
+  const long total = frames * channels;
+  const bool scaled = gain != nullptr;
+  const float g = scaled ? *gain : 1.0f;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const long n = e / channels, c = e - n * channels;
+    const uint32_t bits = planar[c * ld + n];
+    const float y = scaled ? __uint_as_float(bits) * g : __uint_as_float(bits);
+    const float d = DITHER ? tpdf(seed, first_index + (uint64_t)e) : 0.0f;
+    uint32_t v;
+    if (FORMAT == P2PHD_PCM_S16) v = quantise_ex<16>(y, d, DITHER);
+    else if (FORMAT == P2PHD_PCM_S24) v = quantise_ex<24>(y, d, false);
+    else v = scaled ? __float_as_uint(y) : bits;               // no gain: a bit copy, a NaN keeps its payload
+    store_le<BYTES>(out + e * BYTES, v, aligned);
+  }
+}
+
+// Peak statistics of one sample (the rare path: a piece that holds a sample above the format's limit or a non-finite one)
+template <int FORMAT> __device__ __forceinline__ void peak_tally(uint32_t bits, uint32_t& pk, unsigned long long& ov, unsigned long long& nf) {
+  const uint32_t a = bits & 0x7FFFFFFFu;
+  const float x = __uint_as_float(bits);
+  if (a < 0x7F800000u) pk = max(pk, a); else ++nf;
+  if (FORMAT == P2PHD_PCM_F32) ov += fabsf(x) > 1.0f;                                        // (false for NaN, true for +-inf)
+  else {
+    constexpr float scale = FORMAT == P2PHD_PCM_S16 ? 32768.0f : 8388608.0f;
+    ov += (x > (scale - 1.0f) / scale) || (x < -1.0f);
+  }
+}
+
+constexpr int kPeakWords = 5;      // a workgroup's partial: peak bits, clamped count lo / hi, non-finite count lo / hi
+constexpr int kPeakU = 4;          // 16-byte pieces in flight per thread
+
+__device__ __forceinline__ void peak_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t peak_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// grid (gx, channels): workgroup (b, c) walks its share of row c.  A row starts at any float (ld is the caller's): the samples in
+// front of the first 16-byte boundary and behind the last whole piece are read one by one by workgroup b = 0.
+template <int FORMAT>
+__global__ __launch_bounds__(kThreads) void pcm_peak_kernel(const float* __restrict__ planar, long frames, long ld, float ceiling,
+                                                            uint32_t* __restrict__ part, unsigned* __restrict__ ticket,
+                                                            float* __restrict__ peak, long long* __restrict__ over,
+                                                            long long* __restrict__ nonfinite, float* __restrict__ gain) {
+  // at or below `limit` (bit pattern of |x|) a sample is finite and inside the format's range: only the maximum is kept
+  constexpr uint32_t limit = FORMAT == P2PHD_PCM_S16 ? 0x3F7FFE00u : FORMAT == P2PHD_PCM_S24 ? 0x3F7FFFFEu : 0x3F800000u;
+  static_assert(__builtin_bit_cast(uint32_t, 32767.0f / 32768.0f) == 0x3F7FFE00u && __builtin_bit_cast(uint32_t, 8388607.0f / 8388608.0f) == 0x3F7FFFFEu &&
+                __builtin_bit_cast(uint32_t, 1.0f) == 0x3F800000u, "limit: the bit patterns of hi and 1");
+  __shared__ uint32_t s_pk[kThreads];
+  __shared__ unsigned long long s_ov[kThreads], s_nf[kThreads];
+  const int tid = threadIdx.x, c = blockIdx.y, gx = gridDim.x, C = gridDim.y;
+  const float* row = planar + (long)c * ld;
+  const long head = min(frames, (long)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2));
+  const long pieces = (frames - head) >> 2;
+  const long tail0 = head + (pieces << 2);
+  const uint4* body = reinterpret_cast<const uint4*>(row + head);
+  uint32_t pk = 0u;
+  unsigned long long ov = 0ull, nf = 0ull;
+  const long stride = (long)gx * kThreads;
+  for (long e0 = (long)blockIdx.x * kThreads + tid; e0 < pieces; e0 += kPeakU * stride) {
+    uint4 q[kPeakU];
+#pragma unroll
+    for (int u = 0; u < kPeakU; ++u) q[u] = body[min(e0 + u * stride, pieces - 1)];          // unconditional, clamped
+    __builtin_amdgcn_sched_barrier(0);                            // all four requests go out before the first piece is looked at
+#pragma unroll
+    for (int u = 0; u < kPeakU; ++u) {
+      if (e0 + u * stride >= pieces) continue;
+      const uint32_t a0 = q[u].x & 0x7FFFFFFFu, a1 = q[u].y & 0x7FFFFFFFu, a2 = q[u].z & 0x7FFFFFFFu, a3 = q[u].w & 0x7FFFFFFFu;
+      const uint32_t m = max(max(a0, a1), max(a2, a3));
+      if (m <= limit) pk = max(pk, m);
+      else {
+        peak_tally<FORMAT>(q[u].x, pk, ov, nf); peak_tally<FORMAT>(q[u].y, pk, ov, nf);
+        peak_tally<FORMAT>(q[u].z, pk, ov, nf); peak_tally<FORMAT>(q[u].w, pk, ov, nf);
+      }
+    }
+  }
+  if (blockIdx.x == 0) {
+    if (tid < head) peak_tally<FORMAT>(__float_as_uint(row[tid]), pk, ov, nf);
+    if (tid < frames - tail0) peak_tally<FORMAT>(__float_as_uint(row[tail0 + tid]), pk, ov, nf);
+  }
+  s_pk[tid] = pk; s_ov[tid] = ov; s_nf[tid] = nf;
+  __syncthreads();
+  for (int o = kThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) { s_pk[tid] = max(s_pk[tid], s_pk[tid + o]); s_ov[tid] += s_ov[tid + o]; s_nf[tid] += s_nf[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    uint32_t* w = part + ((size_t)c * gx + blockIdx.x) * kPeakWords;
+    peak_store(w + 0, s_pk[0]);
+    peak_store(w + 1, (uint32_t)s_ov[0]); peak_store(w + 2, (uint32_t)(s_ov[0] >> 32));
+    peak_store(w + 3, (uint32_t)s_nf[0]); peak_store(w + 4, (uint32_t)(s_nf[0] >> 32));
+  }
+  if (!p2phd::fold_arrive_last(ticket, (unsigned)(gx * C))) return;
+  // the last workgroup: wave w folds channels w, w + 4, ...; a maximum and integer sums do not depend on the order
+  __shared__ uint32_t s_max[kThreads / 64];
+  const int lane = tid & 63, wave = tid >> 6;
+  uint32_t top = 0u;
+  for (int ch = wave; ch < C; ch += kThreads / 64) {
+    uint32_t p = 0u;
+    unsigned long long o = 0ull, f = 0ull;
+    for (int b = lane; b < gx; b += 64) {
+      const uint32_t* w = part + ((size_t)ch * gx + b) * kPeakWords;
+      p = max(p, peak_load(w + 0));
+      o += (unsigned long long)peak_load(w + 1) | ((unsigned long long)peak_load(w + 2) << 32);
+      f += (unsigned long long)peak_load(w + 3) | ((unsigned long long)peak_load(w + 4) << 32);
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+      p = max(p, (uint32_t)__shfl_xor((int)p, s));
+      o += (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)o, s) | ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(o >> 32), s) << 32);
+      f += (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)f, s) | ((unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)(f >> 32), s) << 32);
+    }
+    if (lane == 0) { peak[ch] = __uint_as_float(p); over[ch] = (long long)o; nonfinite[ch] = (long long)f; }
+    top = max(top, p);
+  }
+  if (lane == 0) s_max[wave] = top;
+  __syncthreads();
+  if (tid == 0) {
+    constexpr float own = FORMAT == P2PHD_PCM_S16 ? 32767.0f / 32768.0f : FORMAT == P2PHD_PCM_S24 ? 8388607.0f / 8388608.0f : 1.0f;
+    const float m = __uint_as_float(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    const float cl = ceiling <= 0.0f ? own : ceiling;
+    *gain = m > cl ? cl / m : 1.0f;
+  }
+}
+
 int sample_grid(int64_t samples) { return (int)std::max<int64_t>(1, std::min<int64_t>(p2phd::cdiv(samples, kThreads), 16384)); }
 
 template <int FORMAT, int BYTES>
@@ -94,6 +252,22 @@ void launch_encode(const float* planar, int64_t frames, int channels, int64_t ld
   const int aligned = (reinterpret_cast<uintptr_t>(out) & (BYTES - 1)) == 0 && (BYTES & (BYTES - 1)) == 0;
   hipLaunchKernelGGL((pcm_encode_kernel<FORMAT, BYTES>), dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st,
                      reinterpret_cast<const uint32_t*>(planar), (long)frames, (long)channels, (long)ld, static_cast<uint8_t*>(out), aligned);
+}
+
+template <int FORMAT, int BYTES, bool DITHER>
+void launch_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, const float* gain, uint64_t seed, uint64_t first_index,
+                      void* out, hipStream_t st) {
+  const int aligned = (reinterpret_cast<uintptr_t>(out) & (BYTES - 1)) == 0 && (BYTES & (BYTES - 1)) == 0;
+  hipLaunchKernelGGL((pcm_encode_ex_kernel<FORMAT, BYTES, DITHER>), dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st,
+                     reinterpret_cast<const uint32_t*>(planar), (long)frames, (long)channels, (long)ld, gain, seed, first_index,
+                     static_cast<uint8_t*>(out), aligned);
+}
+
+// workgroups per row: enough to keep every CU busy with rows of any count, a partial table that fits the scratch region
+int peak_grid(int64_t frames, int channels, size_t scratch_words) {
+  const int64_t want = p2phd::cdiv(frames / 4, (int64_t)kThreads * kPeakU);
+  const int64_t cap = std::min<int64_t>(std::max<int64_t>(1, 2048 / channels), (int64_t)(scratch_words / ((size_t)kPeakWords * channels)));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
 }
 
 }  // namespace
@@ -138,4 +312,64 @@ extern "C" int p2phd_pcm_encode(const float* planar, int64_t frames, int channel
   }
   ++p2phd::g_launch_count[p2phd::LC_PCM];
   return p2phd::check_launch("pcm_encode");
+}
+
+extern "C" int p2phd_pcm_peak(const float* planar, int64_t frames, int channels, int64_t ld, int format, float ceiling, float* peak,
+                              int64_t* over, int64_t* nonfinite, float* gain, void* stream) {
+  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_peak: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
+                (long long)frames, channels);
+  P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32,
+                "pcm_peak: format %d is not one of PCM16, PCM24, float32", format);
+  P2PHD_REQUIRE(ld >= frames, "pcm_peak: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
+  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_peak: frames * channels too large");
+  P2PHD_REQUIRE(peak && over && nonfinite && gain, "pcm_peak: null output pointer");
+  P2PHD_REQUIRE(frames == 0 || planar, "pcm_peak: null pointer");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0, "pcm_peak: planar is not aligned to a float");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(over) & 7) == 0 && (reinterpret_cast<uintptr_t>(nonfinite) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(peak) & 3) == 0 && (reinterpret_cast<uintptr_t>(gain) & 3) == 0, "pcm_peak: an output is not aligned to its type");
+  hipStream_t st = (hipStream_t)stream;
+  const p2phd::FoldScratch fs = p2phd::fold_scratch(p2phd::FOLD_PCM, st);
+  if (fs.part == nullptr) return P2PHD_EINVAL;                   // (refused: error text set by fold_scratch)
+  P2PHD_REQUIRE(fs.floats >= (size_t)kPeakWords * channels, "pcm_peak: reduction scratch too small for %d channels", channels);
+  // frames = 0 launches too: the outputs (zeros, gain 1) are valid after every call
+  const dim3 grid(peak_grid(frames, channels, fs.floats), channels);
+  uint32_t* part = reinterpret_cast<uint32_t*>(fs.part);
+  long long* ov = reinterpret_cast<long long*>(over);
+  long long* nf = reinterpret_cast<long long*>(nonfinite);
+  switch (format) {
+    case P2PHD_PCM_S16: hipLaunchKernelGGL(pcm_peak_kernel<P2PHD_PCM_S16>, grid, dim3(kThreads), 0, st, planar, (long)frames, (long)ld, ceiling, part, fs.ticket, peak, ov, nf, gain); break;
+    case P2PHD_PCM_S24: hipLaunchKernelGGL(pcm_peak_kernel<P2PHD_PCM_S24>, grid, dim3(kThreads), 0, st, planar, (long)frames, (long)ld, ceiling, part, fs.ticket, peak, ov, nf, gain); break;
+    default:            hipLaunchKernelGGL(pcm_peak_kernel<P2PHD_PCM_F32>, grid, dim3(kThreads), 0, st, planar, (long)frames, (long)ld, ceiling, part, fs.ticket, peak, ov, nf, gain); break;
+  }
+  ++p2phd::g_launch_count[p2phd::LC_PCM];
+  return p2phd::check_launch("pcm_peak");
+}
+
+extern "C" int p2phd_pcm_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
+                                   uint64_t seed, int64_t first_index, void* out, void* stream) {
+  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_encode_ex: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
+                (long long)frames, channels);
+  P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32,
+                "pcm_encode_ex: format %d is not one of PCM16, PCM24, float32", format);
+  P2PHD_REQUIRE(dither == 0 || (dither == 1 && format == P2PHD_PCM_S16), "pcm_encode_ex: dither must be 0, or 1 (TPDF) with PCM16 (dither %d, format %d)",
+                dither, format);
+  P2PHD_REQUIRE(first_index >= 0, "pcm_encode_ex: first_index %lld is negative", (long long)first_index);
+  P2PHD_REQUIRE(ld >= frames, "pcm_encode_ex: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
+  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_encode_ex: frames * channels too large");
+  if (frames == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(planar && out, "pcm_encode_ex: null pointer");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(gain) & 3) == 0,
+                "pcm_encode_ex: planar or gain is not aligned to a float");
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t first = (uint64_t)first_index;
+  switch (format) {
+    case P2PHD_PCM_S16:
+      if (dither) launch_encode_ex<P2PHD_PCM_S16, 2, true>(planar, frames, channels, ld, gain, seed, first, out, st);
+      else        launch_encode_ex<P2PHD_PCM_S16, 2, false>(planar, frames, channels, ld, gain, seed, first, out, st);
+      break;
+    case P2PHD_PCM_S24: launch_encode_ex<P2PHD_PCM_S24, 3, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
+    default:            launch_encode_ex<P2PHD_PCM_F32, 4, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
+  }
+  ++p2phd::g_launch_count[p2phd::LC_PCM];
+  return p2phd::check_launch("pcm_encode_ex");
 }

@@ -21,6 +21,11 @@ a clip of its own: a group never mixes channels, and channel c of a [C, L] clip 
 
 The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
 decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
+
+The output stage is opt-in and on the device too: `--report_peaks` (peak, clipped and non-finite samples per channel),
+`--clip guard [--ceiling_dbfs X]` (one gain for the whole file so that nothing clips), `--clip error` (refuse to write a
+file that would clip) and `--dither tpdf` (PCM16).  Without them every byte written and every line printed is as before:
+the integer encodings clamp, silently.
 """
 import argparse
 import ast
@@ -138,17 +143,111 @@ def pcm_decode(payload, frames, channels, format_tag, bits):
     return out
 
 
-def pcm_encode(waveform, encoding='pcm16'):
+def pcm_encode(waveform, encoding='pcm16', gain=None, dither=None, seed=0, first_index=0):
     """waveform [C, L] f32 on the GPU (rows contiguous) -> uint8 tensor of L * C samples, interleaved: the payload
-    wavio.write_payload takes.  'pcm16' gives the bytes wavio.save writes; NaN encodes as 0 in the integer formats."""
+    wavio.write_payload takes.  'pcm16' gives the bytes wavio.save writes; NaN encodes as 0 in the integer formats.
+    `gain`: a float32 tensor of one element on the GPU (pcm_peaks' fourth value) that the kernel reads: every sample is
+    multiplied by it first.  `dither`: None or 'tpdf' (pcm16 only): +-1 LSB of triangular noise in front of the rounding,
+    a hash of (`seed`, `first_index` + the sample's index in the payload) -- encoding a clip in pieces with the right
+    `first_index` gives the bytes of one call.  With none of the four given: p2phd_pcm_encode, as ever."""
     from . import _lib
     if encoding not in PCM_ENCODINGS:
         raise ValueError("pcm_encode: encoding must be one of %s, got %r" % (sorted(PCM_ENCODINGS), encoding))
     w, C, L, ld = _rows(waveform, "pcm_encode: waveform")
     fmt, nbytes = PCM_ENCODINGS[encoding]
     out = torch.empty((L * C * nbytes,), dtype=torch.uint8, device=w.device)
-    _lib.check(_lib.lib().p2phd_pcm_encode(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(out), _lib.stream_ptr()), "pcm_encode")
+    if gain is None and dither is None and seed == 0 and first_index == 0:
+        _lib.check(_lib.lib().p2phd_pcm_encode(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(out), _lib.stream_ptr()), "pcm_encode")
+        return out
+    check_dither(dither, encoding, "pcm_encode")
+    if gain is not None:
+        gain = _lib.require_gpu_tensor(gain, "pcm_encode: gain", torch.float32)
+        if gain.numel() != 1:
+            raise ValueError("pcm_encode: gain must hold one value, got shape %s" % (tuple(gain.shape),))
+    if int(first_index) < 0:
+        raise ValueError("pcm_encode: first_index must be >= 0, got %r" % (first_index,))
+    _lib.check(_lib.lib().p2phd_pcm_encode_ex(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(gain), 1 if dither else 0,
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), _lib.ptr(out), _lib.stream_ptr()),
+               "pcm_encode_ex")
     return out
+
+
+DITHERS = (None, 'tpdf')
+CLIP_MODES = ('clamp', 'guard', 'error')
+
+
+def check_dither(dither, encoding, who):
+    if dither not in DITHERS:
+        raise ValueError("%s: dither must be None or 'tpdf', got %r" % (who, dither))
+    if dither is not None and encoding != 'pcm16':
+        raise ValueError("%s: dither is for pcm16 (a 24-bit or float32 file carries the signal's own low bits), got encoding %r"
+                         % (who, encoding))
+
+
+def encoding_limit(encoding):
+    """The largest sample value the encoding holds: (2^(bits-1) - 1) / 2^(bits-1) for the integer ones, 1 for float32."""
+    half = {'pcm16': 32768.0, 'pcm24': 8388608.0}.get(encoding)
+    return 1.0 if half is None else (half - 1.0) / half
+
+
+def ceiling_from_dbfs(ceiling_dbfs, encoding):
+    """The `ceiling` of pcm_peaks for a level in dBFS (<= 0): 10^(dB / 20), or None -- the encoding's own limit -- where
+    that is not below the limit (or no level is given)."""
+    if ceiling_dbfs is None:
+        return None
+    level = 10.0 ** (float(ceiling_dbfs) / 20.0)
+    return level if level < encoding_limit(encoding) else None
+
+
+def _pcm_peaks_packed(waveform, encoding, ceiling, who):
+    """-> (the four results of pcm_peaks as views of one byte buffer, the buffer): one copy brings all of them back."""
+    from . import _lib
+    if encoding not in PCM_ENCODINGS:
+        raise ValueError("%s: encoding must be one of %s, got %r" % (who, sorted(PCM_ENCODINGS), encoding))
+    ceiling = 0.0 if ceiling is None else float(ceiling)
+    if not ceiling >= 0.0 or ceiling == float('inf'):
+        raise ValueError("%s: ceiling must be a finite level > 0, or None for the encoding's own limit, got %r" % (who, ceiling))
+    w, C, L, ld = _rows(waveform, "%s: waveform" % who)
+    buf = torch.empty((20 * C + 4,), dtype=torch.uint8, device=w.device)       # over[C] i64 | nonfinite[C] i64 | peak[C] f32 | gain f32
+    over, nonfinite = buf[:8 * C].view(torch.int64), buf[8 * C:16 * C].view(torch.int64)
+    peak, gain = buf[16 * C:20 * C].view(torch.float32), buf[20 * C:].view(torch.float32)
+    _lib.check(_lib.lib().p2phd_pcm_peak(_lib.ptr(w), L, C, max(ld, L), PCM_ENCODINGS[encoding][0], ceiling, _lib.ptr(peak),
+                                         _lib.ptr(over), _lib.ptr(nonfinite), _lib.ptr(gain), _lib.stream_ptr()), "pcm_peak")
+    return (peak, over, nonfinite, gain), buf
+
+
+def pcm_peaks(waveform, encoding='pcm16', ceiling=None):
+    """What `encoding` would meet in waveform [C, L] f32 on the GPU (rows contiguous) -> (peak [C] f32, over [C] i64,
+    nonfinite [C] i64, gain [1] f32), all on the GPU, nothing waited for: per channel the largest |x| among the finite samples,
+    the number of samples the encoder would clamp (above the encoding's limit or below -1; beyond +-1 for float32) and the
+    number of NaN / inf samples; and the one gain for all channels that brings the largest peak down to `ceiling` (a linear
+    level; None: the encoding's limit) -- 1 where it already is.  The same bits on every run."""
+    return _pcm_peaks_packed(waveform, encoding, ceiling, "pcm_peaks")[0]
+
+
+def check_output_options(encoding, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, who="enhance_file"):
+    """Validates the output-stage options; -> None when all of them are at their defaults (the plain encoder runs and
+    nothing is reported), else a dict {'clip', 'ceiling' (linear, or None), 'dither', 'seed', 'report'}."""
+    if encoding not in PCM_ENCODINGS:
+        raise ValueError("%s: encoding must be one of %s, got %r" % (who, sorted(PCM_ENCODINGS), encoding))
+    if clip not in CLIP_MODES:
+        raise ValueError("%s: clip must be one of %s, got %r" % (who, CLIP_MODES, clip))
+    check_dither(dither, encoding, who)
+    if ceiling_dbfs is not None:
+        if isinstance(ceiling_dbfs, bool) or not isinstance(ceiling_dbfs, (int, float)) or not -1000.0 <= ceiling_dbfs <= 0.0:
+            raise ValueError("%s: ceiling_dbfs must be a level <= 0 dBFS, got %r" % (who, ceiling_dbfs))
+        if clip != 'guard':
+            raise ValueError("%s: ceiling_dbfs is the level clip='guard' scales to; clip is %r" % (who, clip))
+    if isinstance(dither_seed, bool) or not isinstance(dither_seed, int):
+        raise ValueError("%s: dither_seed must be an int, got %r" % (who, dither_seed))
+    if clip == 'clamp' and ceiling_dbfs is None and dither is None and dither_seed == 0 and not report_peaks:
+        return None
+    return {'clip': clip, 'ceiling': ceiling_from_dbfs(ceiling_dbfs, encoding), 'dither': dither, 'seed': dither_seed,
+            'report': bool(report_peaks)}
+
+
+def _dbfs(level):
+    return 20.0 * math.log10(level) if level > 0.0 else float('-inf')
 
 
 def select_channels(channels, available):
@@ -375,18 +474,47 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding):
-        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload."""
+    def _write(self, path_out, sr, encoding, stage=None):
+        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
+        (check_output_options), or None for the plain encoder.  With a stage the peak kernel runs in front of the encoder,
+        which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
+        one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only."""
         from .data import wavio
-        dev = pcm_encode(sr.contiguous(), encoding)
-        host = self._pinned('out', dev.numel())[:dev.numel()]
-        host.copy_(dev, non_blocking=True)
+        w = sr.contiguous()
+        packed = None
+        if stage is None:
+            dev = pcm_encode(w, encoding)
+        else:
+            (peak, over, nonfinite, gain), packed = _pcm_peaks_packed(w, encoding, stage['ceiling'], "enhance_file")
+            dev = None if path_out is None else pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None,
+                                                           dither=stage['dither'], seed=stage['seed'])
+        host = None
+        if dev is not None:
+            host = self._pinned('out', dev.numel())[:dev.numel()]
+            host.copy_(dev, non_blocking=True)
+        if packed is not None:
+            stats = self._pinned('peaks', packed.numel())[:packed.numel()]
+            stats.copy_(packed, non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        folder = os.path.dirname(os.path.abspath(path_out))
-        os.makedirs(folder, exist_ok=True)
-        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), sr.shape[0], encoding)
+        output = None
+        if packed is not None:
+            C = w.shape[0]
+            raw = stats.numpy()
+            peak = [float(v) for v in raw[16 * C:20 * C].view('<f4')]
+            output = {'peak': peak, 'peak_dbfs': [_dbfs(v) for v in peak],
+                      'clipped': [int(v) for v in raw[:8 * C].view('<i8')], 'nonfinite': [int(v) for v in raw[8 * C:16 * C].view('<i8')],
+                      'gain': float(raw[20 * C:].view('<f4')[0]) if stage['clip'] == 'guard' else 1.0}
+            if stage['clip'] == 'error' and any(output['clipped']):
+                raise ValueError("%s: %d samples would clip in %s (peak %+.2f dBFS); nothing was written -- clip='guard' scales "
+                                 "the file down, encoding='float32' keeps the samples"
+                                 % (path_out, sum(output['clipped']), encoding, max(output['peak_dbfs'])))
+        if host is not None:
+            folder = os.path.dirname(os.path.abspath(path_out))
+            os.makedirs(folder, exist_ok=True)
+            wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), sr.shape[0], encoding)
+        return output
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False):
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None):
         from .data.audio_dataset import lr_round_trip
         from .util import util as U
         o = self.opt
@@ -412,14 +540,18 @@ class SuperResolver:
             metrics = U.compute_matrics(raw, lr, sr, o)
         elif has_hr:
             metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
-        if path_out is not None:
-            self._write(path_out, sr, encoding)
+        output = None
+        if path_out is not None or stage is not None:
+            output = self._write(path_out, sr, encoding, stage)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
         if extended_metrics:
             res['metrics_ext'] = ext
+        if stage is not None:
+            res['output'] = output
         return res
 
-    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False):
+    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
+                     clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -429,24 +561,39 @@ class SuperResolver:
         computed on that channel alone; 'info' is the input's wavio.WavInfo.  `extended_metrics`: the result gains
         'metrics_ext', util.compute_matrics_ext of all written channels from one device call -- a list with one dict
         (util.METRIC_ROW_NAMES -> float) per written channel, also with 'first'; None where 'metrics' is None -- and 'metrics'
-        holds the same rows' figures."""
-        return self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics)
+        holds the same rows' figures.
+        The output stage (all opt-in; 'sr' and the metrics are the unscaled clip whatever it does, only the written bytes
+        change).  `clip`: 'clamp' (default: the integer encodings clamp to their range, silently), 'guard' (the whole file, all
+        channels alike, is scaled down so that its peak sits at `ceiling_dbfs` -- None: the encoding's own limit; a file that
+        fits is left alone) or 'error' (ValueError naming the file, its peak and the clipped count, before anything is
+        written).  `dither`: None or 'tpdf' (pcm16 only: +-1 LSB of triangular noise in front of the rounding, fixed by
+        `dither_seed`).  `report_peaks`: measure only.  With any of the five given the result gains 'output': {'peak',
+        'peak_dbfs', 'clipped', 'nonfinite' (a list each, one entry per written channel, measured on the unscaled clip for
+        `encoding`), 'gain' (the factor applied: 1.0 unless 'guard' scaled)}."""
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
+        return self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage)
 
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
-                       extended_metrics=False):
+                       extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
         `report(record)` is called after every file.  Returns one record per file: {'path' (relative), 'rate', 'channels',
         'frames' (of the input), 'written_channels', 'out_frames', 'metrics' (as enhance_file(channels != 'first') returns
         them: a list per channel, or None), 'error' (None, or the text of what went wrong)}; with `extended_metrics` also
-        'metrics_ext' (as enhance_file returns it)."""
+        'metrics_ext' (as enhance_file returns it).  `clip`, `ceiling_dbfs`, `dither`, `dither_seed`, `report_peaks`: the output
+        stage of enhance_file, per file (a guard gain is one file's); file k of the plan is dithered with seed `dither_seed` + k;
+        with any of them given a record gains 'output' (as enhance_file returns it, None for a skipped file).  clip 'error'
+        ends the run at the first file that would clip."""
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
         records = []
-        for rel, path_in, path_out in plan_folder(dir_in, dir_out):
+        for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
                    'metrics': None, 'error': None}
             if extended_metrics:
                 rec['metrics_ext'] = None
+            if stage is not None:
+                rec['output'] = None
             try:
                 read = self._read(path_in)
             except (ValueError, OSError, EOFError, struct.error) as e:
@@ -454,13 +601,16 @@ class SuperResolver:
             else:
                 if seed is not None:
                     torch.manual_seed(int(seed))
-                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics)
+                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics,
+                                            None if stage is None else dict(stage, seed=dither_seed + k))
                 m, meta = res['metrics'], res['info']
                 rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
                            written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
                            metrics=[m] if m is not None and channels == 'first' else m)
                 if extended_metrics:
                     rec['metrics_ext'] = res['metrics_ext']
+                if stage is not None:
+                    rec['output'] = res['output']
             records.append(rec)
             if report is not None:
                 report(rec)
@@ -537,11 +687,16 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def metrics_rows(records, extended=False):
+METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
+
+
+def metrics_rows(records, extended=False, peaks=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
-    mean of a column then runs over its entries that are not NaN (a clip too short for one segment has no segmental SNR)."""
+    mean of a column then runs over its entries that are not NaN (a clip too short for one segment has no segmental SNR).
+    `peaks`: the records carry 'output' and a row ends with the columns of METRICS_COLUMNS_PEAKS -- the channel's peak in
+    dBFS, its clipped samples and the file's gain; the mean row holds their plain means."""
     rows = []
     if extended:
         for r in records:
@@ -549,21 +704,29 @@ def metrics_rows(records, extended=False):
                 rows.append((r['path'], c, r['out_frames']) + tuple(e[name] for name in METRICS_COLUMNS_EXT[3:]))
         if rows:
             rows.append(("mean", "", "") + tuple(_nanmean([row[k] for row in rows]) for k in range(3, len(METRICS_COLUMNS_EXT))))
-        return rows
-    for r in records:
-        for c, m in enumerate(r['metrics'] or ()):
-            rows.append((r['path'], c, r['out_frames'], m[0], m[1], m[2], m[6]))
-    if rows:
-        rows.append(("mean", "", "") + tuple(sum(row[k] for row in rows) / len(rows) for k in range(3, 7)))
+    else:
+        for r in records:
+            for c, m in enumerate(r['metrics'] or ()):
+                rows.append((r['path'], c, r['out_frames'], m[0], m[1], m[2], m[6]))
+        if rows:
+            rows.append(("mean", "", "") + tuple(sum(row[k] for row in rows) / len(rows) for k in range(3, 7)))
+    if peaks and rows:
+        tail = []
+        for r in records:
+            o = r['output']
+            for c in range(len((r['metrics_ext'] if extended else r['metrics']) or ())):
+                tail.append((o['peak_dbfs'][c], o['clipped'][c], o['gain']))
+        tail.append(tuple(sum(t[k] for t in tail) / len(tail) for k in range(3)))
+        rows = [row + t for row, t in zip(rows, tail)]
     return rows
 
 
-def write_metrics_csv(path, records, extended=False):
+def write_metrics_csv(path, records, extended=False, peaks=False):
     import csv
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS)
-        for row in metrics_rows(records, extended):
+        w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ()))
+        for row in metrics_rows(records, extended, peaks):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
@@ -600,6 +763,18 @@ def _parser():
     ap.add_argument("--lowband_fade", type=int, default=0, metavar="N",
                     help="--lowband input: cross-fade input and generator over the N spectrogram rows below that frequency "
                          "(default 0: a hard switch)")
+    ap.add_argument("--clip", default="clamp", choices=CLIP_MODES,
+                    help="samples beyond the range of --encoding: clamp them, silently (default); guard: scale the whole file down, "
+                         "all channels alike, so that its peak sits at --ceiling_dbfs; error: write nothing and stop")
+    ap.add_argument("--ceiling_dbfs", type=float, default=None, metavar="DB",
+                    help="--clip guard: the level the peak is brought down to, <= 0 (default: the limit of --encoding)")
+    ap.add_argument("--dither", default=None, choices=("tpdf",),
+                    help="pcm16 only: +-1 LSB of triangular noise in front of the rounding, so that the quantisation error of quiet "
+                         "passages is noise and not distortion")
+    ap.add_argument("--dither_seed", type=int, default=0, help="seed of --dither (file k of a folder uses seed + k)")
+    ap.add_argument("--report_peaks", action="store_true",
+                    help="print peak (dBFS), clipped and non-finite samples and the gain of every file; three more columns "
+                         "(peak_dbfs, clipped, gain) of --metrics_csv")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -622,6 +797,11 @@ def _print_metrics_ext(e, prefix=''):
     print('%sSSNR_LR: %.4f' % (prefix, e['ssnr_lr']))
 
 
+def _print_peaks(name, o):
+    print('%s: peak %s dBFS, %d clipped, %d non-finite, gain %.6f' % (name, ' '.join('%+.2f' % v for v in o['peak_dbfs']),
+                                                                    sum(o['clipped']), sum(o['nonfinite']), o['gain']))
+
+
 def _print_unwritten(name, available, written):
     if written < available:
         print('%s: %d of %d channels enhanced and written (--channels all writes every channel)' % (name, written, available))
@@ -634,6 +814,11 @@ def main(argv=None):
         folder_mode = check_paths(a.input, a.output)
     except ValueError as e:
         ap.error(str(e))
+    try:                                                                    # before anything is loaded
+        check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
+    except ValueError as e:
+        ap.error(str(e))
+    stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks)
     folder = os.path.abspath(a.load_pretrain)
     over = dict(checkpoints_dir=os.path.dirname(folder), name=os.path.basename(folder), load_pretrain='', continue_train=False)
     for k in ("which_epoch", "batchSize"):
@@ -662,6 +847,16 @@ def main(argv=None):
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
     rate = int(opt.hr_sampling_rate)
+    try:
+        return _run(a, sr, stage, seed, rate, folder_mode)
+    except ValueError as e:
+        if a.clip != 'error' or 'would clip' not in str(e):
+            raise
+        print('error: %s' % e, file=sys.stderr)                             # --clip error: the file that would clip
+        return 1
+
+
+def _run(a, sr, stage, seed, rate, folder_mode):
     if folder_mode:
         def report(r):
             if r['error'] is not None:
@@ -670,18 +865,20 @@ def main(argv=None):
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
             print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
+            if a.report_peaks:
+                _print_peaks(r['path'], r['output'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
-                                    extended_metrics=a.metrics_ext)
+                                    extended_metrics=a.metrics_ext, **stage)
         done = [r for r in records if r['error'] is None]
         print('%d of %d files enhanced, %d skipped' % (len(done), len(records), len(records) - len(done)))
-        rows = metrics_rows(records, a.metrics_ext)
+        rows = metrics_rows(records, a.metrics_ext)                       # (the printed means: no peak columns)
         if rows:
             print('mean over %d channels: MSE %.4f  SNR_SR %.4f  SNR_LR %.4f  LSD %.4f' % ((len(rows) - 1,) + rows[-1][3:7]))
             if a.metrics_ext:
                 print('mean over %d channels: LSD_LF %.4f  LSD_HF %.4f  SSNR_SR %.4f  SSNR_LR %.4f' % ((len(rows) - 1,) + rows[-1][7:]))
     else:
-        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding, extended_metrics=a.metrics_ext)
+        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding, extended_metrics=a.metrics_ext, **stage)
         m, written = res['metrics'], res['sr'].shape[0]
         ext = res.get('metrics_ext')
         _print_unwritten(a.input, res['info'].num_channels, written)
@@ -698,10 +895,12 @@ def main(argv=None):
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
+        if a.report_peaks:
+            _print_peaks(a.output, res['output'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
-                    'metrics': [m] if m is not None and a.channels == 'first' else m, 'metrics_ext': ext}]
+                    'metrics': [m] if m is not None and a.channels == 'first' else m, 'metrics_ext': ext, 'output': res.get('output')}]
     if a.metrics_csv:
-        write_metrics_csv(a.metrics_csv, records, a.metrics_ext)
+        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks)
         print('metrics: %s' % a.metrics_csv)
     return 0
 
