@@ -85,7 +85,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * "dlast", "c7" (the 7x7 end layers) and "thin_wgrad" (calls routed to them), "timed_pack" / "timed_frames" (the time-domain
  * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
  * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
- * ends, csrc/pcm.hip).  family == NULL with reset != 0 clears all.
+ * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
+ * generation, csrc/xover.hip).  family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -257,6 +258,35 @@ int p2phd_pcm_peak(const float* planar, int64_t frames, int channels, int64_t ld
                    int64_t* over, int64_t* nonfinite, float* gain, void* stream);
 int p2phd_pcm_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
                         uint64_t seed, int64_t first_index, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Time-domain crossover of whole-file generation, csrc/xover.hip.  Launch family "xover" (a p2phd_xover_fwd that launches
+ * counts 1).  Below the crossover frequency the result is the input, above it the generator's output:
+ *   out = sr + LP * (level * lr - sr)      ( = LP * (level * lr) + (delta - LP) * sr ),  LP a centred, zero-delay low-pass.
+ *
+ * p2phd_xover_taps_fill (HOST only, no device, as p2phd_resample_kernel_fill): the Kaiser-windowed sinc of `taps`
+ *   coefficients (odd, 1 <= taps <= 4095) with its -6 dB point at `cutoff` cycles per sample (0 < cutoff < 0.5), beta >= 0.
+ *   In float64, with n = k - (taps - 1) / 2 and sinc(x) = sin(pi x) / (pi x):
+ *     h[k] = 2 cutoff sinc(2 cutoff n) I0(beta sqrt(1 - (2 n / (taps - 1))^2)) / I0(beta)
+ *   divided by the float64 sum of all taps (DC gain 1), each tap then rounded once to fp32; h[k] and h[taps - 1 - k] hold the same
+ *   bits.  taps = 1: h = [1].  Bad arguments: P2PHD_EINVAL with an error text.
+ * p2phd_xover_fwd: sr, lr [C][ld_*] f32 (lr: the clip the generator was given, at the high rate and sample-aligned with sr),
+ *   taps_dev: `taps` f32 coefficients on the device -- the caller's table, of any shape: symmetry is not assumed or used.
+ *   With c0 = (taps - 1) / 2 and d[c][j] = level * lr[c][j] - sr[c][j] for 0 <= j < L, 0 outside (d is zero-extended, not the signals):
+ *     out[c][i] = sr[c][i] + sum_{k = 0}^{taps - 1} h[k] d[c][i + c0 - k],     0 <= i < L.
+ *   Arithmetic, fixed and independent of grid, tile and C: d is one rounded fp32 product and one rounded subtraction (NOT
+ *   contracted); the sum is ONE fp32 accumulator that starts at +0 and takes acc = fma(h[k], d, acc) for k ascending (the
+ *   products ARE contracted: one rounding per tap); then one rounded addition sr + acc.  So row c of a C-row call is bit for bit
+ *   the 1-row call on that row, a run repeats bit for bit, and taps = 1 with h = [1] gives sr + (level * lr - sr) in fp32.
+ *   Rows may start at any float, the pitches (>= L) are the caller's, all offsets are 64-bit.  `out` must not overlap sr or lr
+ *   (the address spans of their C rows are compared): P2PHD_EINVAL.  Even taps, taps > 4095, C > 65535, a null or misaligned
+ *   pointer: P2PHD_EINVAL.  L = 0 or C = 0: P2PHD_OK, nothing launched.  No atomics, no workspace.
+ * p2phd_xover_tile_len (host): outputs per workgroup of p2phd_xover_fwd (tests place their lengths around it).
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_xover_taps_fill(int taps, double cutoff, double beta, float* out);
+int p2phd_xover_fwd(const float* sr, int64_t ld_sr, const float* lr, int64_t ld_lr, float level, const float* taps_dev, int taps,
+                    int64_t C, int64_t L, float* out, int64_t ld_out, void* stream);
+int p2phd_xover_tile_len(void);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -52,6 +52,9 @@ SIGNATURES = {
     "p2phd_pcm_encode": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),
     "p2phd_pcm_peak": (_i32, [_vp, _i64, _i32, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "p2phd_pcm_encode_ex": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i32, C.c_uint64, _i64, _vp, _vp]),
+    "p2phd_xover_taps_fill": (_i32, [_i32, C.c_double, C.c_double, _vp]),
+    "p2phd_xover_fwd": (_i32, [_vp, _i64, _vp, _i64, _f32, _vp, _i32, _i64, _i64, _vp, _i64, _vp]),
+    "p2phd_xover_tile_len": (_i32, []),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

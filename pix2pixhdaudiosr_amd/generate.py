@@ -26,6 +26,10 @@ The output stage is opt-in and on the device too: `--report_peaks` (peak, clippe
 `--clip guard [--ceiling_dbfs X]` (one gain for the whole file so that nothing clips), `--clip error` (refuse to write a
 file that would clip) and `--dither tpdf` (PCM16).  Without them every byte written and every line printed is as before:
 the integer encodings clamp, silently.
+
+`--crossover input` (opt-in, csrc/xover.hip) puts a time-domain crossover behind the stitch: a linear-phase complementary
+filter pair, so that below `--crossover_hz` (default: 0.95 of the low rate's Nyquist frequency) the written clip is the input
+and above it the generator's output.
 """
 import argparse
 import ast
@@ -276,6 +280,95 @@ def check_lowband(lowband, lowband_fade, bins, up_ratio):
     return lowband, check_lowband_fade(lowband_fade, keep, "SuperResolver"), keep
 
 
+CROSSOVERS = (None, 'input')
+CROSSOVER_BETA = 8.96                                                       # Kaiser window, 90 dB
+CROSSOVER_ATTEN_DB = 90.0
+CROSSOVER_MAX_TAPS = 4095
+
+
+def crossover_width_hz(hr_rate, taps):
+    """Transition width of a Kaiser-windowed sinc of `taps` coefficients at 90 dB (Kaiser's formula), in Hz at `hr_rate`."""
+    return float('inf') if taps <= 1 else (CROSSOVER_ATTEN_DB - 7.95) * hr_rate / (14.36 * (taps - 1))
+
+
+def crossover_plan(hr_rate, lr_rate, crossover_hz=None, taps=None):
+    """The low-pass of the time-domain crossover, host arithmetic only -> (taps, cutoff, beta) for p2phd_xover_taps_fill:
+    `cutoff` = crossover_hz / hr_rate (cycles per sample, the -6 dB point), beta = 8.96.  `crossover_hz` defaults to 0.95 of
+    the low rate's Nyquist frequency; `taps` to the smallest odd count whose transition band, crossover_hz +- width / 2 with
+    width = (90 - 7.95) * hr_rate / (14.36 * (taps - 1)), ends at or below that frequency -- everything the filter takes
+    from the input is then something the input carried."""
+    hr_rate, lr_rate = float(hr_rate), float(lr_rate)
+    if not 0.0 < lr_rate < hr_rate:
+        raise ValueError("crossover_plan: nothing to cross over: the low rate %g must be above 0 and below the high rate %g" % (lr_rate, hr_rate))
+    nyquist = lr_rate / 2.0
+    if crossover_hz is None:
+        crossover_hz = 0.95 * nyquist
+    crossover_hz = float(crossover_hz)
+    if not 0.0 < crossover_hz < nyquist:
+        raise ValueError("crossover_plan: crossover_hz must lie in (0, %g), below the low rate's Nyquist frequency, got %g" % (nyquist, crossover_hz))
+
+    def fits(n):
+        return crossover_hz + crossover_width_hz(hr_rate, n) / 2.0 <= nyquist
+
+    if taps is None:
+        # n - 1 >= width constant / (2 * room), then to the odd count next to it and to the exact edge of `fits`
+        n = int(math.ceil((CROSSOVER_ATTEN_DB - 7.95) * hr_rate / (14.36 * 2.0 * (nyquist - crossover_hz)))) + 1
+        n = max(3, min(n | 1, 2 ** 40 + 1))
+        while n > 3 and fits(n - 2):
+            n -= 2
+        while not fits(n):
+            n += 2
+        if n > CROSSOVER_MAX_TAPS:
+            raise ValueError("crossover_plan: a transition band from %g Hz that ends at %g Hz needs %d taps at %g Hz, more than %d: lower "
+                             "crossover_hz" % (crossover_hz, nyquist, n, hr_rate, CROSSOVER_MAX_TAPS))
+        taps = n
+    else:
+        if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= CROSSOVER_MAX_TAPS or taps % 2 == 0:
+            raise ValueError("crossover_plan: taps must be an odd int in [1, %d], got %r" % (CROSSOVER_MAX_TAPS, taps))
+        if not fits(taps):
+            raise ValueError("crossover_plan: with %d taps the transition band is %g Hz wide and ends at %g Hz, above the low rate's Nyquist "
+                             "frequency %g Hz: use more taps or a lower crossover_hz"
+                             % (taps, crossover_width_hz(hr_rate, taps), crossover_hz + crossover_width_hz(hr_rate, taps) / 2.0, nyquist))
+    return taps, crossover_hz / hr_rate, CROSSOVER_BETA
+
+
+def crossover_coefficients(taps, cutoff, beta):
+    """The coefficients of p2phd_xover_taps_fill as a float32 tensor on the host (no GPU needed)."""
+    import ctypes
+    from . import _lib
+    h = torch.empty((max(int(taps), 1),), dtype=torch.float32)
+    _lib.check(_lib.lib().p2phd_xover_taps_fill(int(taps), float(cutoff), float(beta), ctypes.c_void_p(h.data_ptr())), "xover_taps_fill")
+    return h
+
+
+def crossover(sr, lr, level, taps_dev):
+    """sr, lr: [C, L] f32 on the GPU (rows contiguous, any row pitch), taps_dev: an odd number (<= 4095) of f32 coefficients on
+    the GPU -> a new [C, L]: sr + LP * (level * lr - sr), the difference zero-extended beyond the clip (p2phd_xover_fwd)."""
+    from . import _lib
+    s, C, L, ld_s = _rows(sr, "crossover: sr")
+    l, Cl, Ll, ld_l = _rows(lr, "crossover: lr")
+    if (C, L) != (Cl, Ll):
+        raise ValueError("crossover: sr and lr must have one shape, got %s and %s" % (tuple(s.shape), tuple(l.shape)))
+    h = _lib.require_gpu_tensor(taps_dev, "crossover: taps_dev", torch.float32)
+    if h.dim() != 1 or not 1 <= h.numel() <= CROSSOVER_MAX_TAPS or h.numel() % 2 == 0:
+        raise ValueError("crossover: taps_dev must hold an odd number of coefficients in [1, %d], got shape %s" % (CROSSOVER_MAX_TAPS, tuple(h.shape)))
+    out = torch.empty((C, L), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_xover_fwd(_lib.ptr(s), max(ld_s, L), _lib.ptr(l), max(ld_l, L), float(level), _lib.ptr(h), h.numel(), C, L,
+                                          _lib.ptr(out), max(L, 1), _lib.stream_ptr()), "xover_fwd")
+    return out
+
+
+def check_crossover(crossover, crossover_hz, crossover_taps, hr_rate, lr_rate):
+    """Validates the crossover options of SuperResolver -> None (off), or crossover_plan's (taps, cutoff, beta)."""
+    if crossover not in CROSSOVERS:
+        raise ValueError("SuperResolver: crossover must be None or 'input', got %r" % (crossover,))
+    if crossover is None:
+        if crossover_hz is not None or crossover_taps is not None:
+            raise ValueError("SuperResolver: crossover_hz / crossover_taps are options of crossover='input'; crossover is None")
+        return None
+    return crossover_plan(hr_rate, lr_rate, crossover_hz, crossover_taps)
+
+
 def plan_folder(dir_in, dir_out):
     """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
     output keeps the relative path under dir_out.  Other files are ignored."""
@@ -304,10 +397,17 @@ class SuperResolver:
     (the fourth value of `inference`) and only the rows from keep come from the generator (util.imdct, `lr_spectro`).
     `lowband_fade`: rows below keep over which the two are cross-faded, 0 (a hard switch at keep) .. keep.  Both are fixed
     for the object's life, so the captured chain holds them.  With up_ratio <= 1 keep is every row: 'input' is accepted and
-    returns the input's own transform round trip."""
+    returns the input's own transform round trip.
+    `crossover`: None (default), or 'input': behind the stitch the clip goes through a time-domain crossover (csrc/xover.hip),
+    out = sr + LP * ((gain / 2) * lr - sr) with LP a zero-delay Kaiser-windowed sinc: below `crossover_hz` (default 0.95 of the
+    low rate's Nyquist frequency) the result is the input at the level the pipeline returns a passed-through signal at, above
+    it the generator's output.  `crossover_taps`: the filter's length (odd, <= 4095; default: the shortest whose transition
+    band ends under that Nyquist frequency, crossover_plan).  Fixed for the object's life; the coefficients are filled once and
+    stay on the device.  One launch per clip, outside the captured chain; orthogonal to `lowband`.  Needs lr_sampling_rate <
+    hr_sampling_rate."""
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
-                 lowband_fade=0):
+                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None):
         from .models.mdct import IMDCT2, IMDCT4
         from .util import util as U
         self.model, self.opt = model, opt
@@ -343,6 +443,12 @@ class SuperResolver:
             reference_amplitude = self.overlap == 0.0
         self.reference_amplitude = bool(reference_amplitude) and self.mdct_type == 'mdct2'
         self.gain = math.sqrt(self.up_ratio - 1) * (1.0 if self.reference_amplitude else 2.0)
+        # The inverse-transform chain returns x / 2 for the spectrogram of x and the stitch multiplies by `gain`: a signal the
+        # generator passes through comes out as (gain / 2) * x, with or without reference_amplitude -- the level the input enters
+        # the crossover at.
+        self.crossover, self.crossover_hz, self.crossover_taps = crossover, crossover_hz, crossover_taps
+        self.crossover_plan = check_crossover(crossover, crossover_hz, crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
+        self._xover_taps = None                                             # the coefficients on the device, filled at first use
         self._g = None                                                      # captured chain of a full group
         self._pins = {}                                                     # pinned host buffers of the file path, grow-only
 
@@ -443,7 +549,12 @@ class SuperResolver:
                     out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz))
                 else:
                     out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz))
-        return segments_stitch_planar(out, C, stride, self.gain, L)
+        sr = segments_stitch_planar(out, C, stride, self.gain, L)
+        if self.crossover_plan is None:
+            return sr
+        if self._xover_taps is None:
+            self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
+        return crossover(sr, x, self.gain / 2.0, self._xover_taps)
 
     # -- files -------------------------------------------------------------------------------------
     def _pinned(self, slot, nbytes):
@@ -763,6 +874,14 @@ def _parser():
     ap.add_argument("--lowband_fade", type=int, default=0, metavar="N",
                     help="--lowband input: cross-fade input and generator over the N spectrogram rows below that frequency "
                          "(default 0: a hard switch)")
+    ap.add_argument("--crossover", default=None, choices=("input",),
+                    help="time-domain crossover behind the stitch: below --crossover_hz the written clip is the input itself, above "
+                         "it the generator's output (a linear-phase complementary filter pair; default: off)")
+    ap.add_argument("--crossover_hz", type=float, default=None, metavar="F",
+                    help="--crossover input: the crossover frequency (default: 0.95 of the low rate's Nyquist frequency)")
+    ap.add_argument("--crossover_taps", type=int, default=None, metavar="N",
+                    help="--crossover input: length of the filter, odd, <= 4095 (default: the shortest whose transition band ends "
+                         "under the low rate's Nyquist frequency)")
     ap.add_argument("--clip", default="clamp", choices=CLIP_MODES,
                     help="samples beyond the range of --encoding: clamp them, silently (default); guard: scale the whole file down, "
                          "all channels alike, so that its peak sits at --ceiling_dbfs; error: write nothing and stop")
@@ -832,6 +951,7 @@ def main(argv=None):
     try:                                                                    # before the model is built
         check_lowband(a.lowband, a.lowband_fade, int(opt.n_fft) if opt.mdct_type == 'mdct2' else int(opt.n_fft) // 2,
                       opt.hr_sampling_rate / opt.lr_sampling_rate)
+        check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
     except ValueError as e:
         ap.error(str(e))
     from .models.models import create_model
@@ -842,10 +962,13 @@ def main(argv=None):
         torch.manual_seed(int(seed))                                        # the mask noise: one run, one result
     sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
                        reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
-                       lowband=a.lowband, lowband_fade=a.lowband_fade)
+                       lowband=a.lowband, lowband_fade=a.lowband_fade, crossover=a.crossover, crossover_hz=a.crossover_hz,
+                       crossover_taps=a.crossover_taps)
     print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
+    if sr.crossover_plan is not None:                                       # (without the option: no line more than before)
+        print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
     rate = int(opt.hr_sampling_rate)
     try:
         return _run(a, sr, stage, seed, rate, folder_mode)

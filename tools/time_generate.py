@@ -17,12 +17,18 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             overlap 0.25: seconds of audio per second, best of --reps with the spread, and lsd_lf / lsd_hf of each output against
             a full-band original whose low-rate round trip is the input; log in --lowband_log
 
+  crossover (only when asked for) generate.SuperResolver(crossover=None) against crossover='input' (the default plan), geometry, clip
+            and repeats of `lowband`: seconds of audio per second, best of --reps with the spread, and lsd_lf / lsd_hf of each
+            output against the full-band original, and the energy of the two outputs' difference below the transition band and
+            above the low rate's Nyquist frequency; log in --crossover_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
 Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] [--reps 5] [--log profiles/time_generate.log]
         python tools/time_generate.py folder [--files 8] [--folder_log profiles/time_generate_folder.log]
         python tools/time_generate.py lowband [--lowband_log profiles/time_generate_lowband.log]
+        python tools/time_generate.py crossover [--crossover_log profiles/time_generate_crossover.log]
 """
 import argparse
 import os
@@ -164,6 +170,17 @@ def run_folder(seconds, reps, files, log):
 def run_lowband(seconds, reps, log):
     """Seconds of audio per second of the graphed pipeline at overlap 0.25 with the model's and with the input's low band, the
     runs of the variants interleaved so that a drift of the machine falls on all of them; and what each does to the two bands."""
+    _run_variants(seconds, reps, log, "lowband",
+                  [("lowband model          ", dict()), ("lowband input, fade 0  ", dict(lowband='input')),
+                   ("lowband input, fade 8  ", dict(lowband='input', lowband_fade=8))])
+
+
+def run_crossover(seconds, reps, log):
+    """The same comparison for the time-domain crossover: off against 'input' with the default plan, interleaved."""
+    _run_variants(seconds, reps, log, "crossover", [("crossover off         ", dict()), ("crossover input       ", dict(crossover='input'))])
+
+
+def _run_variants(seconds, reps, log, mode, variants):
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
     from pix2pixhdaudiosr_amd.generate import SuperResolver
@@ -175,11 +192,12 @@ def run_lowband(seconds, reps, log):
     hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
     hr = x + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float().cuda()[None]
     lr = lr_round_trip(hr, opt.hr_sampling_rate, opt.lr_sampling_rate, opt.hr_sampling_rate)[..., :n].contiguous()
-    variants = [("lowband model          ", dict()), ("lowband input, fade 0  ", dict(lowband='input')),
-                ("lowband input, fade 8  ", dict(lowband='input', lowband_fade=8))]
     srs = [SuperResolver(model, opt, overlap=0.25, **kw) for _, kw in variants]
-    lines = ["# tools/time_generate.py lowband: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; "
-             "%g s synthetic clip at 48 kHz, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    lines = ["# tools/time_generate.py %s: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; "
+             "%g s synthetic clip at 48 kHz, untrained weights, %d interleaved repeats" % (mode, seconds, reps)]
+    for sr in srs:
+        if sr.crossover_plan is not None:
+            lines.append("# crossover plan: %d taps, the input below %g Hz" % (sr.crossover_plan[0], sr.crossover_plan[1] * opt.hr_sampling_rate))
     outs = []
     for sr in srs:                                                 # warm-up and capture; the same noise seed for every variant
         sr.enhance_lr(lr)
@@ -199,6 +217,17 @@ def run_lowband(seconds, reps, log):
         lines.append("%s best %8.1f s of audio / s   spread %6.1f (worst %8.1f)   lsd_lf %.4f  lsd_hf %.4f  lsd %.4f   runs: %s"
                      % (name, rates[-1], rates[-1] - rates[0], rates[0], e['lsd_lf'], e['lsd_hf'], e['lsd'],
                         " ".join("%.1f" % (seconds / v) for v in tk)))
+    if mode == "crossover":
+        # both outputs come from one noise seed, so their difference is the crossover's work alone: where it sits in the spectrum
+        plan = srs[1].crossover_plan
+        rate, half = float(opt.hr_sampling_rate), opt.lr_sampling_rate / 2.0
+        width = (90.0 - 7.95) * rate / (14.36 * (plan[0] - 1))
+        c0 = (plan[0] - 1) // 2
+        Y0, Y1 = (torch.fft.rfft(y[0, c0:n - c0].double()) for y in outs)
+        f = torch.arange(Y0.numel(), device=Y0.device, dtype=torch.float64) * rate / (n - 2 * c0)
+        for name, band in (("below %g Hz" % (plan[1] * rate - width / 2), f <= plan[1] * rate - width / 2), ("above %g Hz" % half, f >= half)):
+            moved, was = (Y1 - Y0)[band].abs().pow(2).sum().item(), Y0[band].abs().pow(2).sum().item()
+            lines.append("energy of (crossover input - crossover off) %-14s %8.2f dB of that band of crossover off" % (name + ":", 10.0 * torch.log10(torch.tensor(moved / was)).item()))
     e = U.compute_matrics_ext(hr, lr, lr, opt)[0]
     lines.append("the input itself as output                                                                lsd_lf %.4f  lsd_hf %.4f  lsd %.4f"
                  % (e['lsd_lf'], e['lsd_hf'], e['lsd']))
@@ -238,10 +267,11 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
+    ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
@@ -250,6 +280,8 @@ def main():
         return run_folder(a.seconds, a.reps, a.files, a.folder_log)
     if a.mode == "lowband":
         return run_lowband(a.seconds, a.reps, a.lowband_log)
+    if a.mode == "crossover":
+        return run_crossover(a.seconds, a.reps, a.crossover_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
