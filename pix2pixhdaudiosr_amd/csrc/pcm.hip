@@ -1,21 +1,22 @@
-// Whole-file generation (pix2pixhdaudiosr_amd/generate.py): the PCM codec at the two ends of the file path, so that a file
+// Whole-file generation (pix2pixhdaudiosr_amd/generate/): the PCM codec at the two ends of the file path, so that a file
 // costs one copy of its payload to the device and one copy of the encoded payload back, with no per-sample host work.
 //
 //   decode  little-endian interleaved payload of a RIFF data chunk -> planar fp32 out[c * ld + n].  One int -> float
 //           conversion and an exact power-of-two scale (data/wavio.py load), so the result is the bits wavio.load returns.
-//   encode  planar fp32 -> interleaved payload: PCM16 / PCM24 (clamp, scale, round half to even; NaN -> 0) or a float32 bit copy.
+//   encode  planar fp32 -> interleaved payload, one kernel behind both entries: y = x * gain[0] (read from device memory: the
+//           peak launch in front needs no host round trip; no gain: y = x), v = y * 2^(bits-1) [+ d], r = rint(v) clamped to
+//           the integer range, NaN -> 0; float32 writes y, without gain as a bit copy.  d: TPDF dither of +-1 LSB for PCM16, a
+//           counter-based hash of (seed, index of the interleaved sample) -- a payload encoded in pieces, or twice, gets the same
+//           bytes.  p2phd_pcm_encode is p2phd_pcm_encode_ex without gain and dither: the bytes wavio.save writes, which clamps
+//           in front of the rounding -- the same integer for every float (tests/test_pcm_host.py holds both orders together).
 //
-// and the output stage in front of the encoder, for a file that must not clip silently (all opt-in: p2phd_pcm_encode is as it was):
+// and the output stage in front of the encoder, for a file that must not clip silently (opt-in):
 //
 //   peak       per channel max |x| over the finite samples, the number of samples the encoder of the format would clamp and
 //              the number of NaN / inf samples; one gain for all channels, gain = m > ceiling ? ceiling / m : 1 with m the
 //              largest channel peak.  A maximum of bit patterns and integer counts: the same bits on every run.  Workgroup
 //              partials are stored and folded by the last workgroup (common.h: fold_arrive_last), so nothing is zeroed before
 //              the launch and there is no float atomic.  HBM-bound: 16-byte pieces, four in flight per thread.
-//   encode_ex  y = x * gain[0] (read from device memory: the peak launch in front needs no host round trip), v = y * 2^(bits-1)
-//              [+ d], r = rint(v) clamped to the integer range, NaN -> 0; float32 writes y.  d: TPDF dither of +-1 LSB for
-//              PCM16, a counter-based hash of (seed, index of the interleaved sample) -- a payload encoded in pieces, or twice,
-//              gets the same bytes.  Without gain and dither: the bytes of `encode`.
 //
 // Streaming kernels, one thread per sample of the interleaved stream: the payload side is contiguous across a wave, the
 // planar side is `channels` contiguous runs.  The payload pointer has byte alignment only (24-bit samples, a data chunk
@@ -68,31 +69,6 @@ __global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const uint8_t* __r
   }
 }
 
-// clamp to [-1, (2^(bits-1) - 1) / 2^(bits-1)], times 2^(bits-1) (exact), round half to even; NaN -> 0
-template <int BITS> __device__ __forceinline__ uint32_t quantise(float x) {
-  constexpr float scale = (float)(1u << (BITS - 1));
-  constexpr float hi = (scale - 1.0f) / scale;
-  if (x != x) return 0u;
-  x = fminf(fmaxf(x, -1.0f), hi);
-  return (uint32_t)(int32_t)rintf(x * scale);
-}
-
-template <int FORMAT, int BYTES>
-__global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const uint32_t* __restrict__ planar, long frames, long channels, long ld,
-                                                              uint8_t* __restrict__ out, int aligned) {
-  const long total = frames * channels;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    const long n = e / channels, c = e - n * channels;
-    const uint32_t bits = planar[c * ld + n];
-    uint32_t v;
-    if (FORMAT == P2PHD_PCM_S16) v = quantise<16>(__uint_as_float(bits));
-    else if (FORMAT == P2PHD_PCM_S24) v = quantise<24>(__uint_as_float(bits));
-    else v = bits;
-    store_le<BYTES>(out + e * BYTES, v, aligned);
-  }
-}
-
-// ---- output stage: peak report, clip guard, dither ----------------------------------------------------------------------
 // TPDF dither of the interleaved sample with global index i, in LSB: the difference of the two 16-bit halves of a hash of
 // (seed, i), times 2^-16 -- exact in fp32, in (-1, 1), triangular.  fmix is the 32-bit finaliser of MurmurHash3.
 __device__ __forceinline__ uint32_t fmix(uint32_t h) {
@@ -104,35 +80,35 @@ __device__ __forceinline__ float tpdf(uint64_t seed, uint64_t i) {
   return (float)((int)(h & 0xFFFFu) - (int)(h >> 16)) * (1.0f / 65536.0f);
 }
 
-// y * 2^(bits-1) [+ d], round half to even, clamp to the integer range; NaN -> 0
-template <int BITS> __device__ __forceinline__ uint32_t quantise_ex(float y, float d, bool dither) {
+// y * 2^(bits-1) (exact) [+ d], round half to even, clamp to the integer range; NaN -> 0
+template <int BITS, bool DITHER> __device__ __forceinline__ uint32_t quantise(float y, float d) {
   constexpr float scale = (float)(1u << (BITS - 1));
   float v = y * scale;
-  if (dither) v = v + d;
+  if (DITHER) v = v + d;
   if (v != v) return 0u;
   return (uint32_t)(int32_t)fminf(fmaxf(rintf(v), -scale), scale - 1.0f);
 }
 
-template <int FORMAT, int BYTES, bool DITHER>
-__global__ __launch_bounds__(kThreads) void pcm_encode_ex_kernel(const uint32_t* __restrict__ planar, long frames, long channels, long ld,
-                                                                 const float* __restrict__ gain, uint64_t seed, uint64_t first_index,
-                                                                 uint8_t* __restrict__ out, int aligned) {
+template <int FORMAT, int BYTES, bool GAIN, bool DITHER>
+__global__ __launch_bounds__(kThreads) void pcm_encode_kernel(const uint32_t* __restrict__ planar, long frames, long channels, long ld,
+                                                              const float* __restrict__ gain, uint64_t seed, uint64_t first_index,
+                                                              uint8_t* __restrict__ out, int aligned) {
   const long total = frames * channels;
-  const bool scaled = gain != nullptr;
-  const float g = scaled ? *gain : 1.0f;
+  const float g = GAIN ? *gain : 1.0f;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const long n = e / channels, c = e - n * channels;
     const uint32_t bits = planar[c * ld + n];
-    const float y = scaled ? __uint_as_float(bits) * g : __uint_as_float(bits);
+    const float y = GAIN ? __uint_as_float(bits) * g : __uint_as_float(bits);
     const float d = DITHER ? tpdf(seed, first_index + (uint64_t)e) : 0.0f;
     uint32_t v;
-    if (FORMAT == P2PHD_PCM_S16) v = quantise_ex<16>(y, d, DITHER);
-    else if (FORMAT == P2PHD_PCM_S24) v = quantise_ex<24>(y, d, false);
-    else v = scaled ? __float_as_uint(y) : bits;               // no gain: a bit copy, a NaN keeps its payload
+    if (FORMAT == P2PHD_PCM_S16) v = quantise<16, DITHER>(y, d);
+    else if (FORMAT == P2PHD_PCM_S24) v = quantise<24, false>(y, d);
+    else v = GAIN ? __float_as_uint(y) : bits;                 // no gain: a bit copy, a NaN keeps its payload
     store_le<BYTES>(out + e * BYTES, v, aligned);
   }
 }
 
+// ---- output stage: peak report and the gain of the clip guard ------------------------------------------------------------
 // Peak statistics of one sample (the rare path: a piece that holds a sample above the format's limit or a non-finite one)
 template <int FORMAT> __device__ __forceinline__ void peak_tally(uint32_t bits, uint32_t& pk, unsigned long long& ov, unsigned long long& nf) {
   const uint32_t a = bits & 0x7FFFFFFFu;
@@ -247,20 +223,13 @@ void launch_decode(const void* bytes, int64_t frames, int channels, float* out, 
                      static_cast<const uint8_t*>(bytes), (long)frames, (long)channels, (long)ld, reinterpret_cast<uint32_t*>(out), aligned);
 }
 
-template <int FORMAT, int BYTES>
-void launch_encode(const float* planar, int64_t frames, int channels, int64_t ld, void* out, hipStream_t st) {
-  const int aligned = (reinterpret_cast<uintptr_t>(out) & (BYTES - 1)) == 0 && (BYTES & (BYTES - 1)) == 0;
-  hipLaunchKernelGGL((pcm_encode_kernel<FORMAT, BYTES>), dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st,
-                     reinterpret_cast<const uint32_t*>(planar), (long)frames, (long)channels, (long)ld, static_cast<uint8_t*>(out), aligned);
-}
-
 template <int FORMAT, int BYTES, bool DITHER>
-void launch_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, const float* gain, uint64_t seed, uint64_t first_index,
-                      void* out, hipStream_t st) {
+void launch_encode(const float* planar, int64_t frames, int channels, int64_t ld, const float* gain, uint64_t seed, uint64_t first_index,
+                   void* out, hipStream_t st) {
   const int aligned = (reinterpret_cast<uintptr_t>(out) & (BYTES - 1)) == 0 && (BYTES & (BYTES - 1)) == 0;
-  hipLaunchKernelGGL((pcm_encode_ex_kernel<FORMAT, BYTES, DITHER>), dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st,
-                     reinterpret_cast<const uint32_t*>(planar), (long)frames, (long)channels, (long)ld, gain, seed, first_index,
-                     static_cast<uint8_t*>(out), aligned);
+  const auto kernel = gain ? pcm_encode_kernel<FORMAT, BYTES, true, DITHER> : pcm_encode_kernel<FORMAT, BYTES, false, DITHER>;
+  hipLaunchKernelGGL(kernel, dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st, reinterpret_cast<const uint32_t*>(planar),
+                     (long)frames, (long)channels, (long)ld, gain, seed, first_index, static_cast<uint8_t*>(out), aligned);
 }
 
 // workgroups per row: enough to keep every CU busy with rows of any count, a partial table that fits the scratch region
@@ -270,14 +239,46 @@ int peak_grid(int64_t frames, int channels, size_t scratch_words) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
 }
 
+// The checks every entry shares: the shape of the planar side and the format -- one a data chunk can hold (decode), or one
+// of the three an output is written in (`encodable`)
+int check_rows(const char* what, int64_t frames, int channels, int64_t ld, int format, bool encodable) {
+  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "%s: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)", what,
+                (long long)frames, channels);
+  if (encodable)
+    P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32, "%s: format %d is not one of PCM16, PCM24, float32",
+                  what, format);
+  else
+    P2PHD_REQUIRE(format >= P2PHD_PCM_U8 && format <= P2PHD_PCM_F64, "%s: unknown format %d", what, format);
+  P2PHD_REQUIRE(ld >= frames, "%s: ld %lld is shorter than the %lld frames of a row", what, (long long)ld, (long long)frames);
+  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "%s: frames * channels too large", what);
+  return P2PHD_OK;
+}
+
+int encode_rows(const char* what, const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
+                uint64_t seed, int64_t first_index, void* out, void* stream) {
+  if (const int rc = check_rows(what, frames, channels, ld, format, true)) return rc;
+  P2PHD_REQUIRE(dither == 0 || (dither == 1 && format == P2PHD_PCM_S16), "%s: dither must be 0, or 1 (TPDF) with PCM16 (dither %d, format %d)", what,
+                dither, format);
+  P2PHD_REQUIRE(first_index >= 0, "%s: first_index %lld is negative", what, (long long)first_index);
+  if (frames == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(planar && out, "%s: null pointer", what);
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0, "%s: planar is not aligned to a float", what);
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(gain) & 3) == 0, "%s: planar or gain is not aligned to a float", what);
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t first = (uint64_t)first_index;
+  switch (format) {
+    case P2PHD_PCM_S16: (dither ? launch_encode<P2PHD_PCM_S16, 2, true> : launch_encode<P2PHD_PCM_S16, 2, false>)(planar, frames, channels, ld, gain, seed, first, out, st); break;
+    case P2PHD_PCM_S24: launch_encode<P2PHD_PCM_S24, 3, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
+    default:            launch_encode<P2PHD_PCM_F32, 4, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
+  }
+  ++p2phd::g_launch_count[p2phd::LC_PCM];
+  return p2phd::check_launch(what);
+}
+
 }  // namespace
 
 extern "C" int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels, int format, float* out, int64_t ld, void* stream) {
-  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_decode: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
-                (long long)frames, channels);
-  P2PHD_REQUIRE(format >= P2PHD_PCM_U8 && format <= P2PHD_PCM_F64, "pcm_decode: unknown format %d", format);
-  P2PHD_REQUIRE(ld >= frames, "pcm_decode: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
-  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_decode: frames * channels too large");
+  if (const int rc = check_rows("pcm_decode", frames, channels, ld, format, false)) return rc;
   if (frames == 0) return P2PHD_OK;
   P2PHD_REQUIRE(bytes && out, "pcm_decode: null pointer");
   P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "pcm_decode: out is not aligned to a float");
@@ -295,33 +296,17 @@ extern "C" int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels,
 }
 
 extern "C" int p2phd_pcm_encode(const float* planar, int64_t frames, int channels, int64_t ld, int format, void* out, void* stream) {
-  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_encode: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
-                (long long)frames, channels);
-  P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32,
-                "pcm_encode: format %d is not one of PCM16, PCM24, float32", format);
-  P2PHD_REQUIRE(ld >= frames, "pcm_encode: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
-  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_encode: frames * channels too large");
-  if (frames == 0) return P2PHD_OK;
-  P2PHD_REQUIRE(planar && out, "pcm_encode: null pointer");
-  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0, "pcm_encode: planar is not aligned to a float");
-  hipStream_t st = (hipStream_t)stream;
-  switch (format) {
-    case P2PHD_PCM_S16: launch_encode<P2PHD_PCM_S16, 2>(planar, frames, channels, ld, out, st); break;
-    case P2PHD_PCM_S24: launch_encode<P2PHD_PCM_S24, 3>(planar, frames, channels, ld, out, st); break;
-    default:            launch_encode<P2PHD_PCM_F32, 4>(planar, frames, channels, ld, out, st); break;
-  }
-  ++p2phd::g_launch_count[p2phd::LC_PCM];
-  return p2phd::check_launch("pcm_encode");
+  return encode_rows("pcm_encode", planar, frames, channels, ld, format, nullptr, 0, 0, 0, out, stream);
+}
+
+extern "C" int p2phd_pcm_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
+                                   uint64_t seed, int64_t first_index, void* out, void* stream) {
+  return encode_rows("pcm_encode_ex", planar, frames, channels, ld, format, gain, dither, seed, first_index, out, stream);
 }
 
 extern "C" int p2phd_pcm_peak(const float* planar, int64_t frames, int channels, int64_t ld, int format, float ceiling, float* peak,
                               int64_t* over, int64_t* nonfinite, float* gain, void* stream) {
-  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_peak: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
-                (long long)frames, channels);
-  P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32,
-                "pcm_peak: format %d is not one of PCM16, PCM24, float32", format);
-  P2PHD_REQUIRE(ld >= frames, "pcm_peak: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
-  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_peak: frames * channels too large");
+  if (const int rc = check_rows("pcm_peak", frames, channels, ld, format, true)) return rc;
   P2PHD_REQUIRE(peak && over && nonfinite && gain, "pcm_peak: null output pointer");
   P2PHD_REQUIRE(frames == 0 || planar, "pcm_peak: null pointer");
   P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0, "pcm_peak: planar is not aligned to a float");
@@ -343,33 +328,4 @@ extern "C" int p2phd_pcm_peak(const float* planar, int64_t frames, int channels,
   }
   ++p2phd::g_launch_count[p2phd::LC_PCM];
   return p2phd::check_launch("pcm_peak");
-}
-
-extern "C" int p2phd_pcm_encode_ex(const float* planar, int64_t frames, int channels, int64_t ld, int format, const float* gain, int dither,
-                                   uint64_t seed, int64_t first_index, void* out, void* stream) {
-  P2PHD_REQUIRE(frames >= 0 && channels >= 1 && channels <= 65535, "pcm_encode_ex: need frames >= 0 and 1 <= channels <= 65535 (frames %lld, channels %d)",
-                (long long)frames, channels);
-  P2PHD_REQUIRE(format == P2PHD_PCM_S16 || format == P2PHD_PCM_S24 || format == P2PHD_PCM_F32,
-                "pcm_encode_ex: format %d is not one of PCM16, PCM24, float32", format);
-  P2PHD_REQUIRE(dither == 0 || (dither == 1 && format == P2PHD_PCM_S16), "pcm_encode_ex: dither must be 0, or 1 (TPDF) with PCM16 (dither %d, format %d)",
-                dither, format);
-  P2PHD_REQUIRE(first_index >= 0, "pcm_encode_ex: first_index %lld is negative", (long long)first_index);
-  P2PHD_REQUIRE(ld >= frames, "pcm_encode_ex: ld %lld is shorter than the %lld frames of a row", (long long)ld, (long long)frames);
-  P2PHD_REQUIRE(frames <= (int64_t(1) << 40) / channels, "pcm_encode_ex: frames * channels too large");
-  if (frames == 0) return P2PHD_OK;
-  P2PHD_REQUIRE(planar && out, "pcm_encode_ex: null pointer");
-  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(gain) & 3) == 0,
-                "pcm_encode_ex: planar or gain is not aligned to a float");
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t first = (uint64_t)first_index;
-  switch (format) {
-    case P2PHD_PCM_S16:
-      if (dither) launch_encode_ex<P2PHD_PCM_S16, 2, true>(planar, frames, channels, ld, gain, seed, first, out, st);
-      else        launch_encode_ex<P2PHD_PCM_S16, 2, false>(planar, frames, channels, ld, gain, seed, first, out, st);
-      break;
-    case P2PHD_PCM_S24: launch_encode_ex<P2PHD_PCM_S24, 3, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
-    default:            launch_encode_ex<P2PHD_PCM_F32, 4, false>(planar, frames, channels, ld, gain, seed, first, out, st); break;
-  }
-  ++p2phd::g_launch_count[p2phd::LC_PCM];
-  return p2phd::check_launch("pcm_encode_ex");
 }

@@ -1,0 +1,42 @@
+"""Whole-file super-resolution: wav in, wav out, on the device from the waveform to the waveform.
+
+    python -m pix2pixhdaudiosr_amd.generate --input in.wav --output out.wav --load_pretrain DIR [--overlap 0.25]
+    python -m pix2pixhdaudiosr_amd.generate --input DIR_IN --output DIR_OUT --load_pretrain DIR --channels all [--metrics_csv m.csv [--metrics_ext]]
+
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    sr = SuperResolver(model, opt).enhance_file("in.wav", "out.wav")["sr"]
+
+The chain is the reference's generate_audio.py:27-47 -- segments of `opt.segment_length` samples, `model.inference` and
+`util.imdct` per group of `batchSize` segments, the pieces put back together and scaled by sqrt(up_ratio - 1) -- with two
+differences.  The segments are cut and joined by two kernels (csrc/stitch.hip), and by default neighbours share
+`overlap * segment_length` samples that are cross-faded, where the reference butts the pieces together.  `overlap=0` is the
+reference's chain exactly, its amplitude included: with MDCT2 the reference's output is half of sqrt(up_ratio - 1) * x,
+because its util.imdct halves what IMDCT2 already returns at unit gain.  With overlapping segments the pipeline returns the
+full amplitude -- 6 dB more; `SuperResolver(reference_amplitude=...)` and `--reference_amplitude 0|1` choose explicitly.
+
+A group is semantics: `to_spectro` normalises by the min / max of the whole batch tensor (pix2pixHD_model.py:165-168 of the
+reference), so a group holds exactly the segments the reference's loader would put in it and a last, smaller group runs at
+its own size -- padding it with silent segments would change its normalisation.  For the same reason a channel of a file is
+a clip of its own: a group never mixes channels, and channel c of a [C, L] clip is grouped exactly as the mono clip audio[c].
+
+The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
+decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
+
+The output stage is opt-in and on the device too: `--report_peaks` (peak, clipped and non-finite samples per channel),
+`--clip guard [--ceiling_dbfs X]` (one gain for the whole file so that nothing clips), `--clip error` (refuse to write a
+file that would clip) and `--dither tpdf` (PCM16).  Without them every byte written and every line printed is as before:
+the integer encodings clamp, silently.
+
+`--crossover input` (opt-in, csrc/xover.hip) puts a time-domain crossover behind the stitch: a linear-phase complementary
+filter pair, so that below `--crossover_hz` (default: 0.95 of the low rate's Nyquist frequency) the written clip is the input
+and above it the generator's output.
+"""
+from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
+from .ops import (PCM_FORMATS, crossover, crossover_coefficients, pcm_decode, pcm_encode, pcm_peaks, segments_gather,  # noqa: F401
+                  segments_gather_planar, segments_stitch, segments_stitch_planar)
+from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, LOWBANDS,  # noqa: F401
+                    PCM_ENCODINGS, ClipError, ceiling_from_dbfs, check_crossover, check_dither, check_encoding, check_lowband,
+                    check_output_options, check_paths, crossover_plan, crossover_width_hz, encoding_limit, plan_folder, segment_plan,
+                    select_channels, spectro_bins)
+from .report import METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_PEAKS, metrics_rows, write_metrics_csv        # noqa: F401
+from .resolver import SuperResolver                                                                              # noqa: F401

@@ -1,0 +1,214 @@
+"""Whole-file super-resolution: wav in, wav out, on the device from the waveform to the waveform.
+
+The command line of whole-file generation (python -m pix2pixhdaudiosr_amd.generate; the first line above is its --help
+description) and the options dump it starts from."""
+import argparse
+import ast
+import os
+import sys
+from types import SimpleNamespace
+
+import torch
+
+from .plans import (CLIP_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_lowband, check_output_options, check_paths,
+                    spectro_bins)
+from .report import _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .resolver import SuperResolver, per_channel_metrics
+
+
+def parse_opt_file(path):
+    """The `key: value` dump every reference run writes (options/base_options.py:102-107) -> dict.  Values go through
+    ast.literal_eval where that parses (numbers, booleans, None, lists), `inf` / `-inf` / `nan` become floats, anything
+    else stays a string.  The dashed first and last lines are skipped; any other line without `key: value` is an error."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError("options file %s does not exist (pass --opt_file; a reference run writes opt.txt beside its "
+                                "checkpoints)" % path)
+    out = {}
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            line = line.strip()
+            if not line or (line.startswith('-') and line.endswith('-')):
+                continue
+            key, sep, value = line.partition(':')
+            key, value = key.strip(), value.strip()
+            if not sep or not key.isidentifier():
+                raise ValueError("%s:%d: expected `key: value`, got %r" % (path, no, line))
+            try:
+                out[key] = ast.literal_eval(value)
+            except (ValueError, SyntaxError):
+                out[key] = float(value) if value in ('inf', '-inf', 'nan') else value
+    if not out:
+        raise ValueError("%s holds no `key: value` line" % path)
+    return out
+
+
+def opt_from_file(path, **overrides):
+    """Namespace for create_model from an options dump: the file's values, inference on GPU 0, then `overrides`."""
+    d = parse_opt_file(path)
+    d.update(gpu_ids=[0], isTrain=False)
+    d.update(overrides)
+    return SimpleNamespace(**d)
+
+
+def _channels_arg(text):
+    if text in ("all", "first"):
+        return text
+    try:
+        n = int(text)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError("expected all, first or a count >= 1, got %r" % text)
+    return n
+
+
+def _parser():
+    ap = argparse.ArgumentParser(prog="python -m pix2pixhdaudiosr_amd.generate", description=__doc__.split("\n")[0])
+    ap.add_argument("--input", required=True, help="wav file to enhance, or a folder: every *.wav below it")
+    ap.add_argument("--output", required=True, help="wav file to write (at hr_sampling_rate), or the folder that takes the "
+                                                    "outputs at the inputs' relative paths")
+    ap.add_argument("--channels", type=_channels_arg, default="first", metavar="all|first|N",
+                    help="channels of a file to enhance and write: the first one (default), all, or the first N; every "
+                         "channel is enhanced as a clip of its own")
+    ap.add_argument("--encoding", default="pcm16", choices=sorted(PCM_ENCODINGS), help="sample format of the output (default pcm16)")
+    ap.add_argument("--metrics_csv", default=None, metavar="PATH",
+                    help="write file, channel, frames, mse, snr_sr, snr_lr, lsd of every written channel that has a full-band "
+                         "original, and a last `mean` row")
+    ap.add_argument("--metrics_ext", action="store_true",
+                    help="also measure, per channel, the log-spectral distance below and from the low rate's Nyquist frequency "
+                         "(lsd_lf, lsd_hf) and the segmental SNR of the output and of the low-rate input (ssnr_sr, ssnr_lr): "
+                         "printed, and four more columns of --metrics_csv")
+    ap.add_argument("--load_pretrain", required=True, help="folder with <which_epoch>_net_G.pth (and opt.txt)")
+    ap.add_argument("--opt_file", default=None, help="options dump of the training run (default: <load_pretrain>/opt.txt)")
+    ap.add_argument("--which_epoch", default=None)
+    ap.add_argument("--overlap", type=float, default=0.25, help="shared fraction of neighbouring segments, 0 .. 0.5 (0: the reference's chain)")
+    ap.add_argument("--batchSize", type=int, default=None, help="segments per group")
+    ap.add_argument("--is_lr_input", action="store_true", help="the input is a low-rate clip: upsample it, no round trip")
+    ap.add_argument("--no_graph", action="store_true", help="run every group eagerly")
+    ap.add_argument("--reference_amplitude", type=int, choices=(0, 1), default=None,
+                    help="MDCT2 checkpoints: 1 keeps the half amplitude of the reference's generate_audio.py, 0 writes the full "
+                         "one, 6 dB more (default: 1 at --overlap 0, the reference-exact mode, else 0)")
+    ap.add_argument("--lowband", default="model", choices=LOWBANDS,
+                    help="where the band the input already had comes from: the generator's spectrogram like every other row "
+                         "(model, default), or the input's own spectrogram (input): only the rows from the low rate's Nyquist "
+                         "frequency up are then the generator's")
+    ap.add_argument("--lowband_fade", type=int, default=0, metavar="N",
+                    help="--lowband input: cross-fade input and generator over the N spectrogram rows below that frequency "
+                         "(default 0: a hard switch)")
+    ap.add_argument("--crossover", default=None, choices=("input",),
+                    help="time-domain crossover behind the stitch: below --crossover_hz the written clip is the input itself, above "
+                         "it the generator's output (a linear-phase complementary filter pair; default: off)")
+    ap.add_argument("--crossover_hz", type=float, default=None, metavar="F",
+                    help="--crossover input: the crossover frequency (default: 0.95 of the low rate's Nyquist frequency)")
+    ap.add_argument("--crossover_taps", type=int, default=None, metavar="N",
+                    help="--crossover input: length of the filter, odd, <= 4095 (default: the shortest whose transition band ends "
+                         "under the low rate's Nyquist frequency)")
+    ap.add_argument("--clip", default="clamp", choices=CLIP_MODES,
+                    help="samples beyond the range of --encoding: clamp them, silently (default); guard: scale the whole file down, "
+                         "all channels alike, so that its peak sits at --ceiling_dbfs; error: write nothing and stop")
+    ap.add_argument("--ceiling_dbfs", type=float, default=None, metavar="DB",
+                    help="--clip guard: the level the peak is brought down to, <= 0 (default: the limit of --encoding)")
+    ap.add_argument("--dither", default=None, choices=("tpdf",),
+                    help="pcm16 only: +-1 LSB of triangular noise in front of the rounding, so that the quantisation error of quiet "
+                         "passages is noise and not distortion")
+    ap.add_argument("--dither_seed", type=int, default=0, help="seed of --dither (file k of a folder uses seed + k)")
+    ap.add_argument("--report_peaks", action="store_true",
+                    help="print peak (dBFS), clipped and non-finite samples and the gain of every file; three more columns "
+                         "(peak_dbfs, clipped, gain) of --metrics_csv")
+    ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
+    ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
+                    help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
+                         "the one the reference's train.py, which writes opt.txt, is hard-wired to)")
+    return ap
+
+
+def main(argv=None):
+    ap = _parser()
+    a = ap.parse_args(argv)
+    try:                                                                    # before anything is loaded
+        folder_mode = check_paths(a.input, a.output)
+        check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
+    except ValueError as e:
+        ap.error(str(e))
+    stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks)
+    folder = os.path.abspath(a.load_pretrain)
+    over = dict(checkpoints_dir=os.path.dirname(folder), name=os.path.basename(folder), load_pretrain='', continue_train=False)
+    for k in ("which_epoch", "batchSize"):
+        if getattr(a, k) is not None:
+            over[k] = getattr(a, k)
+    if a.fp16:
+        over["fp16"] = True
+    opt = opt_from_file(a.opt_file or os.path.join(folder, "opt.txt"), **over)
+    if a.mdct_type is not None or not hasattr(opt, 'mdct_type'):
+        opt.mdct_type = a.mdct_type or os.environ.get('P2PHD_MDCT_TYPE', 'mdct2')
+    try:                                                                    # before the model is built
+        check_lowband(a.lowband, a.lowband_fade, spectro_bins(opt.n_fft, opt.mdct_type), opt.hr_sampling_rate / opt.lr_sampling_rate)
+        check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
+    except ValueError as e:
+        ap.error(str(e))
+    from ..models.models import create_model
+    model = create_model(opt)
+    model.eval()
+    seed = getattr(opt, 'seed', None)
+    if seed is not None:
+        torch.manual_seed(int(seed))                                        # the mask noise: one run, one result
+    sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
+                       reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
+                       lowband=a.lowband, lowband_fade=a.lowband_fade, crossover=a.crossover, crossover_hz=a.crossover_hz,
+                       crossover_taps=a.crossover_taps)
+    print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
+                                           "the model's" if sr.lowband == 'model' else
+                                           "the input's (fade over %d rows)" % sr.lowband_fade))
+    if sr.crossover_plan is not None:                                       # (without the option: no line more than before)
+        print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
+    rate = int(opt.hr_sampling_rate)
+    try:
+        return _run(a, sr, stage, seed, rate, folder_mode)
+    except ClipError as e:
+        print('error: %s' % e, file=sys.stderr)                             # --clip error: the file that would clip
+        return 1
+
+
+def _run(a, sr, stage, seed, rate, folder_mode):
+    if folder_mode:
+        def report(r):
+            if r['error'] is not None:
+                print('skipped %s: %s' % (r['path'], r['error']))
+                return
+            _print_unwritten(r['path'], r['channels'], r['written_channels'])
+            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
+                                                                   r['written_channels'], '' if r['written_channels'] == 1 else 's'))
+            if a.report_peaks:
+                _print_peaks(r['path'], r['output'])
+        # every file starts from the seed, so it comes out as a run of its own would write it
+        records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
+                                    extended_metrics=a.metrics_ext, **stage)
+        done = [r for r in records if r['error'] is None]
+        print('%d of %d files enhanced, %d skipped' % (len(done), len(records), len(records) - len(done)))
+        rows = metrics_rows(records, a.metrics_ext)                       # (the printed means: no peak columns)
+        if rows:
+            print('mean over %d channels: MSE %.4f  SNR_SR %.4f  SNR_LR %.4f  LSD %.4f' % ((len(rows) - 1,) + rows[-1][3:7]))
+            if a.metrics_ext:
+                print('mean over %d channels: LSD_LF %.4f  LSD_HF %.4f  SSNR_SR %.4f  SSNR_LR %.4f' % ((len(rows) - 1,) + rows[-1][7:]))
+    else:
+        res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding, extended_metrics=a.metrics_ext, **stage)
+        m, written = per_channel_metrics(res['metrics'], a.channels), res['sr'].shape[0]
+        ext = res.get('metrics_ext')
+        _print_unwritten(a.input, res['info'].num_channels, written)
+        for c, mc in enumerate(m or ()):
+            prefix = '' if a.channels == 'first' else 'channel %d ' % c
+            _print_metrics(mc, prefix)
+            if ext is not None:
+                _print_metrics_ext(ext[c], prefix)
+        if written == 1:
+            print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
+        else:
+            print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
+        if a.report_peaks:
+            _print_peaks(a.output, res['output'])
+        records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
+                    'metrics': m, 'metrics_ext': ext, 'output': res.get('output')}]
+    if a.metrics_csv:
+        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks)
+        print('metrics: %s' % a.metrics_csv)
+    return 0

@@ -1,0 +1,164 @@
+"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip and csrc/xover.hip as tensor functions."""
+import ctypes
+
+import torch
+
+from .. import _lib
+from .plans import CROSSOVER_MAX_TAPS, check_dither, check_encoding
+
+# (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
+PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
+
+
+def segments_gather(audio, T, stride, S):
+    """audio [L] f32 on the GPU -> [S, T]: row s holds audio[s * stride : s * stride + T], zeros beyond the end."""
+    a = _lib.require_gpu_tensor(audio, "segments_gather: audio", torch.float32)
+    if a.dim() != 1:
+        raise ValueError("segments_gather: expected a 1-D waveform, got shape %s" % (tuple(a.shape),))
+    out = torch.empty((max(int(S), 0), max(int(T), 0)), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().p2phd_segments_gather(_lib.ptr(a), a.numel(), int(T), int(stride), int(S), _lib.ptr(out),
+                                                _lib.stream_ptr()), "segments_gather")
+    return out
+
+
+def segments_stitch(seg, stride, gain=1.0, out_length=None):
+    """seg [S, T] f32 on the GPU -> [out_length] (default: the whole span): gain * the segments laid `stride` apart, the
+    T - stride shared samples of neighbours cross-faded with sin^2 / cos^2 weights."""
+    s = _lib.require_gpu_tensor(seg, "segments_stitch: seg", torch.float32)
+    if s.dim() != 2:
+        raise ValueError("segments_stitch: expected [S, T], got shape %s" % (tuple(s.shape),))
+    S, T = s.shape
+    L_out = (S - 1) * int(stride) + T if out_length is None else int(out_length)
+    out = torch.empty((max(L_out, 0),), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_segments_stitch(_lib.ptr(s), S, T, int(stride), float(gain), _lib.ptr(out), L_out,
+                                                _lib.stream_ptr()), "segments_stitch")
+    return out
+
+
+def _rows(t, name):
+    """A [C, L] f32 GPU tensor whose rows are contiguous (a row pitch >= L is fine) -> (tensor, C, L, pitch)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise _lib.P2PHDError("%s: expected a float32 tensor on the GPU (this build has no CPU path)" % name)
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError("%s: expected [C, L] with C >= 1, got shape %s" % (name, tuple(t.shape)))
+    C, L = t.shape
+    if L > 1 and t.stride(1) != 1 or C > 1 and t.stride(0) < L:
+        raise _lib.P2PHDError("%s: expected rows that are contiguous" % name)
+    return t, C, L, (t.stride(0) if C > 1 else max(L, 1))
+
+
+def segments_gather_planar(audio, T, stride, S):
+    """audio [C, L] f32 on the GPU (rows contiguous, any row pitch) -> [C * S, T], channel-major: row c * S + s holds
+    audio[c, s * stride : s * stride + T], zeros beyond the end.  One launch whatever C is."""
+    a, C, L, ld = _rows(audio, "segments_gather_planar: audio")
+    out = torch.empty((C * max(int(S), 0), max(int(T), 0)), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.lib().p2phd_segments_gather_planar(_lib.ptr(a), C, max(ld, L), L, int(T), int(stride), int(S), _lib.ptr(out),
+                                                       _lib.stream_ptr()), "segments_gather_planar")
+    return out
+
+
+def segments_stitch_planar(seg, C, stride, gain=1.0, out_length=None, ld=None):
+    """seg [C * S, T] f32 on the GPU, channel-major -> [C, out_length]: segments_stitch on every channel's S rows, in one
+    launch.  `ld`: row pitch of the buffer the result is a view of (default: out_length)."""
+    s = _lib.require_gpu_tensor(seg, "segments_stitch_planar: seg", torch.float32)
+    C = int(C)
+    if s.dim() != 2 or C < 1 or s.shape[0] % C:
+        raise ValueError("segments_stitch_planar: expected [C * S, T] with C = %d, got shape %s" % (C, tuple(s.shape)))
+    S, T = s.shape[0] // C, s.shape[1]
+    L_out = (S - 1) * int(stride) + T if out_length is None else int(out_length)
+    ld = max(L_out, 0) if ld is None else int(ld)
+    out = torch.empty((C, max(ld, 0)), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_segments_stitch_planar(_lib.ptr(s), C, S, T, int(stride), float(gain), _lib.ptr(out), ld, L_out,
+                                                       _lib.stream_ptr()), "segments_stitch_planar")
+    return out[:, :max(L_out, 0)]
+
+
+def pcm_decode(payload, frames, channels, format_tag, bits):
+    """payload: uint8 tensor on the GPU holding the interleaved little-endian samples of a data chunk (any byte offset into
+    its storage) -> [channels, frames] f32, bit-identical to what wavio.load returns for the file."""
+    b = _lib.require_gpu_tensor(payload, "pcm_decode: payload", torch.uint8)
+    fmt = PCM_FORMATS.get((int(format_tag), int(bits)))
+    if fmt is None:
+        raise ValueError("pcm_decode: unsupported format (tag %s, %s bit)" % (format_tag, bits))
+    frames, channels = int(frames), int(channels)
+    if b.numel() < frames * channels * (int(bits) // 8):
+        raise ValueError("pcm_decode: %d bytes do not hold %d frames of %d x %d bit" % (b.numel(), frames, channels, bits))
+    out = torch.empty((channels, frames), dtype=torch.float32, device=b.device)
+    _lib.check(_lib.lib().p2phd_pcm_decode(_lib.ptr(b), frames, channels, fmt, _lib.ptr(out), frames, _lib.stream_ptr()), "pcm_decode")
+    return out
+
+
+def pcm_encode(waveform, encoding='pcm16', gain=None, dither=None, seed=0, first_index=0):
+    """waveform [C, L] f32 on the GPU (rows contiguous) -> uint8 tensor of L * C samples, interleaved: the payload
+    wavio.write_payload takes.  'pcm16' gives the bytes wavio.save writes; NaN encodes as 0 in the integer formats.
+    `gain`: a float32 tensor of one element on the GPU (pcm_peaks' fourth value) that the kernel reads: every sample is
+    multiplied by it first.  `dither`: None or 'tpdf' (pcm16 only): +-1 LSB of triangular noise in front of the rounding,
+    a hash of (`seed`, `first_index` + the sample's index in the payload) -- encoding a clip in pieces with the right
+    `first_index` gives the bytes of one call."""
+    fmt, nbytes = check_encoding(encoding, "pcm_encode")
+    w, C, L, ld = _rows(waveform, "pcm_encode: waveform")
+    out = torch.empty((L * C * nbytes,), dtype=torch.uint8, device=w.device)
+    check_dither(dither, encoding, "pcm_encode")
+    if gain is not None:
+        gain = _lib.require_gpu_tensor(gain, "pcm_encode: gain", torch.float32)
+        if gain.numel() != 1:
+            raise ValueError("pcm_encode: gain must hold one value, got shape %s" % (tuple(gain.shape),))
+    if int(first_index) < 0:
+        raise ValueError("pcm_encode: first_index must be >= 0, got %r" % (first_index,))
+    _lib.check(_lib.lib().p2phd_pcm_encode_ex(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(gain), 1 if dither else 0,
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), _lib.ptr(out), _lib.stream_ptr()),
+               "pcm_encode_ex")
+    return out
+
+
+def _peak_views(buf, C):
+    """The packed peak buffer -- over[C] i64 | nonfinite[C] i64 | peak[C] f32 | gain f32, 20 * C + 4 bytes, on the device or
+    its copy on the host -> (peak, over, nonfinite, gain) as typed views."""
+    return (buf[16 * C:20 * C].view(torch.float32), buf[:8 * C].view(torch.int64), buf[8 * C:16 * C].view(torch.int64),
+            buf[20 * C:20 * C + 4].view(torch.float32))
+
+
+def _pcm_peaks_packed(waveform, encoding, ceiling, who):
+    """-> (the four results of pcm_peaks as views of one byte buffer, the buffer): one copy brings all of them back."""
+    fmt, _ = check_encoding(encoding, who)
+    ceiling = 0.0 if ceiling is None else float(ceiling)
+    if not ceiling >= 0.0 or ceiling == float('inf'):
+        raise ValueError("%s: ceiling must be a finite level > 0, or None for the encoding's own limit, got %r" % (who, ceiling))
+    w, C, L, ld = _rows(waveform, "%s: waveform" % who)
+    buf = torch.empty((20 * C + 4,), dtype=torch.uint8, device=w.device)
+    peak, over, nonfinite, gain = views = _peak_views(buf, C)
+    _lib.check(_lib.lib().p2phd_pcm_peak(_lib.ptr(w), L, C, max(ld, L), fmt, ceiling, _lib.ptr(peak),
+                                         _lib.ptr(over), _lib.ptr(nonfinite), _lib.ptr(gain), _lib.stream_ptr()), "pcm_peak")
+    return views, buf
+
+
+def pcm_peaks(waveform, encoding='pcm16', ceiling=None):
+    """What `encoding` would meet in waveform [C, L] f32 on the GPU (rows contiguous) -> (peak [C] f32, over [C] i64,
+    nonfinite [C] i64, gain [1] f32), all on the GPU, nothing waited for: per channel the largest |x| among the finite samples,
+    the number of samples the encoder would clamp (above the encoding's limit or below -1; beyond +-1 for float32) and the
+    number of NaN / inf samples; and the one gain for all channels that brings the largest peak down to `ceiling` (a linear
+    level; None: the encoding's limit) -- 1 where it already is.  The same bits on every run."""
+    return _pcm_peaks_packed(waveform, encoding, ceiling, "pcm_peaks")[0]
+
+
+def crossover_coefficients(taps, cutoff, beta):
+    """The coefficients of p2phd_xover_taps_fill as a float32 tensor on the host (no GPU needed)."""
+    h = torch.empty((max(int(taps), 1),), dtype=torch.float32)
+    _lib.check(_lib.lib().p2phd_xover_taps_fill(int(taps), float(cutoff), float(beta), ctypes.c_void_p(h.data_ptr())), "xover_taps_fill")
+    return h
+
+
+def crossover(sr, lr, level, taps_dev):
+    """sr, lr: [C, L] f32 on the GPU (rows contiguous, any row pitch), taps_dev: an odd number (<= 4095) of f32 coefficients on
+    the GPU -> a new [C, L]: sr + LP * (level * lr - sr), the difference zero-extended beyond the clip (p2phd_xover_fwd)."""
+    s, C, L, ld_s = _rows(sr, "crossover: sr")
+    l, Cl, Ll, ld_l = _rows(lr, "crossover: lr")
+    if (C, L) != (Cl, Ll):
+        raise ValueError("crossover: sr and lr must have one shape, got %s and %s" % (tuple(s.shape), tuple(l.shape)))
+    h = _lib.require_gpu_tensor(taps_dev, "crossover: taps_dev", torch.float32)
+    if h.dim() != 1 or not 1 <= h.numel() <= CROSSOVER_MAX_TAPS or h.numel() % 2 == 0:
+        raise ValueError("crossover: taps_dev must hold an odd number of coefficients in [1, %d], got shape %s" % (CROSSOVER_MAX_TAPS, tuple(h.shape)))
+    out = torch.empty((C, L), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_xover_fwd(_lib.ptr(s), max(ld_s, L), _lib.ptr(l), max(ld_l, L), float(level), _lib.ptr(h), h.numel(), C, L,
+                                          _lib.ptr(out), max(L, 1), _lib.stream_ptr()), "xover_fwd")
+    return out

@@ -1,0 +1,194 @@
+"""Whole-file generation: the host arithmetic and the validation of every option -- no tensor, no library."""
+import math
+import os
+
+# encoding of wavio.save / wavio.write_payload -> (P2PHD_PCM_* code of include/p2phd.h, bytes per sample)
+PCM_ENCODINGS = {'pcm16': (1, 2), 'pcm24': (2, 3), 'float32': (4, 4)}
+DITHERS = (None, 'tpdf')
+CLIP_MODES = ('clamp', 'guard', 'error')
+LOWBANDS = ('model', 'input')
+CROSSOVERS = (None, 'input')
+CROSSOVER_BETA = 8.96                                                       # Kaiser window, 90 dB
+CROSSOVER_ATTEN_DB = 90.0
+CROSSOVER_MAX_TAPS = 4095
+
+
+class ClipError(ValueError):
+    """clip='error': the file would clip; nothing was written."""
+
+
+def segment_plan(L, T, overlap=0.0):
+    """(S, stride, V) for a clip of L samples: segments of T samples that start every `stride = T - V` samples,
+    `V = int(overlap * T)` of them shared with the next one, `S = max(1, ceil((L - V) / stride))` segments -- the fewest
+    whose span (S - 1) * stride + T reaches L.  overlap 0: ceil(L / T), the count of the reference's seg_pad_audio."""
+    L, T = int(L), int(T)
+    if T < 1 or L < 0:
+        raise ValueError("segment_plan: need segment_length >= 1 and a length >= 0, got %d and %d" % (T, L))
+    if not 0.0 <= overlap <= 0.5:
+        raise ValueError("segment_plan: overlap must be in [0, 0.5], got %r" % (overlap,))
+    V = int(overlap * T)
+    stride = T - V
+    S = max(1, -((V - L) // stride))
+    return S, stride, V
+
+
+def select_channels(channels, available):
+    """How many leading channels of a file with `available` channels are enhanced and written: 'first' -> 1, 'all' -> every
+    one, an int N -> the first N (all of them where the file has fewer)."""
+    if channels == 'first':
+        return 1
+    if channels == 'all':
+        return int(available)
+    if isinstance(channels, bool) or not isinstance(channels, int) or channels < 1:
+        raise ValueError("channels must be 'first', 'all' or an int >= 1, got %r" % (channels,))
+    return min(channels, int(available))
+
+
+def check_encoding(encoding, who):
+    """-> (P2PHD_PCM_* code, bytes per sample) of an output encoding."""
+    if encoding not in PCM_ENCODINGS:
+        raise ValueError("%s: encoding must be one of %s, got %r" % (who, sorted(PCM_ENCODINGS), encoding))
+    return PCM_ENCODINGS[encoding]
+
+
+def check_dither(dither, encoding, who):
+    if dither not in DITHERS:
+        raise ValueError("%s: dither must be None or 'tpdf', got %r" % (who, dither))
+    if dither is not None and encoding != 'pcm16':
+        raise ValueError("%s: dither is for pcm16 (a 24-bit or float32 file carries the signal's own low bits), got encoding %r"
+                         % (who, encoding))
+
+
+def encoding_limit(encoding):
+    """The largest sample value the encoding holds: (2^(bits-1) - 1) / 2^(bits-1) for the integer ones, 1 for float32."""
+    half = {'pcm16': 32768.0, 'pcm24': 8388608.0}.get(encoding)
+    return 1.0 if half is None else (half - 1.0) / half
+
+
+def ceiling_from_dbfs(ceiling_dbfs, encoding):
+    """The `ceiling` of pcm_peaks for a level in dBFS (<= 0): 10^(dB / 20), or None -- the encoding's own limit -- where
+    that is not below the limit (or no level is given)."""
+    if ceiling_dbfs is None:
+        return None
+    level = 10.0 ** (float(ceiling_dbfs) / 20.0)
+    return level if level < encoding_limit(encoding) else None
+
+
+def check_output_options(encoding, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, who="enhance_file"):
+    """Validates the output-stage options; -> None when all of them are at their defaults (the encoder runs without gain
+    and dither and nothing is reported), else a dict {'clip', 'ceiling' (linear, or None), 'dither', 'seed', 'report'}."""
+    check_encoding(encoding, who)
+    if clip not in CLIP_MODES:
+        raise ValueError("%s: clip must be one of %s, got %r" % (who, CLIP_MODES, clip))
+    check_dither(dither, encoding, who)
+    if ceiling_dbfs is not None:
+        if isinstance(ceiling_dbfs, bool) or not isinstance(ceiling_dbfs, (int, float)) or not -1000.0 <= ceiling_dbfs <= 0.0:
+            raise ValueError("%s: ceiling_dbfs must be a level <= 0 dBFS, got %r" % (who, ceiling_dbfs))
+        if clip != 'guard':
+            raise ValueError("%s: ceiling_dbfs is the level clip='guard' scales to; clip is %r" % (who, clip))
+    if isinstance(dither_seed, bool) or not isinstance(dither_seed, int):
+        raise ValueError("%s: dither_seed must be an int, got %r" % (who, dither_seed))
+    if clip == 'clamp' and ceiling_dbfs is None and dither is None and dither_seed == 0 and not report_peaks:
+        return None
+    return {'clip': clip, 'ceiling': ceiling_from_dbfs(ceiling_dbfs, encoding), 'dither': dither, 'seed': dither_seed,
+            'report': bool(report_peaks)}
+
+
+def spectro_bins(n_fft, mdct_type):
+    """Rows of the spectrogram: MDCT2 keeps n_fft of them, MDCT4 half."""
+    return int(n_fft) if mdct_type == 'mdct2' else int(n_fft) // 2
+
+
+def check_lowband(lowband, lowband_fade, bins, up_ratio):
+    """Validates the low-band options of SuperResolver for a spectrogram of `bins` rows: `lowband` is 'model' or 'input' and
+    `lowband_fade` a whole number of rows in [0, keep], keep = int(bins / up_ratio) -- the rows the low-rate input carried
+    (all of them at up_ratio <= 1).  Returns (lowband, lowband_fade, keep)."""
+    from ..util.util import check_lowband_fade, lowband_keep_rows
+    if lowband not in LOWBANDS:
+        raise ValueError("SuperResolver: lowband must be 'model' or 'input', got %r" % (lowband,))
+    keep = lowband_keep_rows(bins, up_ratio)
+    return lowband, check_lowband_fade(lowband_fade, keep, "SuperResolver"), keep
+
+
+def crossover_width_hz(hr_rate, taps):
+    """Transition width of a Kaiser-windowed sinc of `taps` coefficients at 90 dB (Kaiser's formula), in Hz at `hr_rate`."""
+    return float('inf') if taps <= 1 else (CROSSOVER_ATTEN_DB - 7.95) * hr_rate / (14.36 * (taps - 1))
+
+
+def crossover_plan(hr_rate, lr_rate, crossover_hz=None, taps=None):
+    """The low-pass of the time-domain crossover, host arithmetic only -> (taps, cutoff, beta) for p2phd_xover_taps_fill:
+    `cutoff` = crossover_hz / hr_rate (cycles per sample, the -6 dB point), beta = 8.96.  `crossover_hz` defaults to 0.95 of
+    the low rate's Nyquist frequency; `taps` to the smallest odd count whose transition band, crossover_hz +- width / 2 with
+    width = (90 - 7.95) * hr_rate / (14.36 * (taps - 1)), ends at or below that frequency -- everything the filter takes
+    from the input is then something the input carried."""
+    hr_rate, lr_rate = float(hr_rate), float(lr_rate)
+    if not 0.0 < lr_rate < hr_rate:
+        raise ValueError("crossover_plan: nothing to cross over: the low rate %g must be above 0 and below the high rate %g" % (lr_rate, hr_rate))
+    nyquist = lr_rate / 2.0
+    if crossover_hz is None:
+        crossover_hz = 0.95 * nyquist
+    crossover_hz = float(crossover_hz)
+    if not 0.0 < crossover_hz < nyquist:
+        raise ValueError("crossover_plan: crossover_hz must lie in (0, %g), below the low rate's Nyquist frequency, got %g" % (nyquist, crossover_hz))
+
+    def fits(n):
+        return crossover_hz + crossover_width_hz(hr_rate, n) / 2.0 <= nyquist
+
+    if taps is None:
+        # n - 1 >= width constant / (2 * room), then to the odd count next to it and to the exact edge of `fits`
+        n = int(math.ceil((CROSSOVER_ATTEN_DB - 7.95) * hr_rate / (14.36 * 2.0 * (nyquist - crossover_hz)))) + 1
+        n = max(3, min(n | 1, 2 ** 40 + 1))
+        while n > 3 and fits(n - 2):
+            n -= 2
+        while not fits(n):
+            n += 2
+        if n > CROSSOVER_MAX_TAPS:
+            raise ValueError("crossover_plan: a transition band from %g Hz that ends at %g Hz needs %d taps at %g Hz, more than %d: lower "
+                             "crossover_hz" % (crossover_hz, nyquist, n, hr_rate, CROSSOVER_MAX_TAPS))
+        taps = n
+    else:
+        if isinstance(taps, bool) or not isinstance(taps, int) or not 1 <= taps <= CROSSOVER_MAX_TAPS or taps % 2 == 0:
+            raise ValueError("crossover_plan: taps must be an odd int in [1, %d], got %r" % (CROSSOVER_MAX_TAPS, taps))
+        if not fits(taps):
+            raise ValueError("crossover_plan: with %d taps the transition band is %g Hz wide and ends at %g Hz, above the low rate's Nyquist "
+                             "frequency %g Hz: use more taps or a lower crossover_hz"
+                             % (taps, crossover_width_hz(hr_rate, taps), crossover_hz + crossover_width_hz(hr_rate, taps) / 2.0, nyquist))
+    return taps, crossover_hz / hr_rate, CROSSOVER_BETA
+
+
+def check_crossover(crossover, crossover_hz, crossover_taps, hr_rate, lr_rate):
+    """Validates the crossover options of SuperResolver -> None (off), or crossover_plan's (taps, cutoff, beta)."""
+    if crossover not in CROSSOVERS:
+        raise ValueError("SuperResolver: crossover must be None or 'input', got %r" % (crossover,))
+    if crossover is None:
+        if crossover_hz is not None or crossover_taps is not None:
+            raise ValueError("SuperResolver: crossover_hz / crossover_taps are options of crossover='input'; crossover is None")
+        return None
+    return crossover_plan(hr_rate, lr_rate, crossover_hz, crossover_taps)
+
+
+def plan_folder(dir_in, dir_out):
+    """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
+    output keeps the relative path under dir_out.  Other files are ignored."""
+    if not os.path.isdir(dir_in):
+        raise NotADirectoryError("%s is not a directory" % dir_in)
+    if os.path.exists(dir_out) and not os.path.isdir(dir_out):
+        raise NotADirectoryError("--input is a directory, so --output must be one too: %s is a file" % dir_out)
+    rel = []
+    for root, _, files in os.walk(dir_in):
+        for f in files:
+            if f.lower().endswith('.wav'):
+                rel.append(os.path.relpath(os.path.join(root, f), dir_in))
+    return [(r, os.path.join(dir_in, r), os.path.join(dir_out, r)) for r in sorted(rel)]
+
+
+def check_paths(path_in, path_out):
+    """-> True for folder mode (both are directories; the output one may not exist yet), False for one file.  Mixing a file
+    and a directory is an error."""
+    if os.path.isdir(path_in):
+        if os.path.isfile(path_out):
+            raise ValueError("--input %s is a directory, so --output must be a directory too, and %s is a file" % (path_in, path_out))
+        return True
+    if os.path.isdir(path_out):
+        raise ValueError("--input %s is a file, so --output must be a file too, and %s is a directory" % (path_in, path_out))
+    return False

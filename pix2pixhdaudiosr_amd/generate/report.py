@@ -1,0 +1,75 @@
+"""Whole-file generation: the metrics table of --metrics_csv and the lines the command line prints per file."""
+import csv
+
+METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd")
+METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")     # --metrics_ext
+METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
+
+
+def _mean(values):
+    return sum(values) / len(values)
+
+
+def _nanmean(values):
+    kept = [v for v in values if v == v]
+    return sum(kept) / len(kept) if kept else float('nan')
+
+
+def _columns(extended, peaks):
+    """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
+    if extended:
+        cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
+    else:
+        cols = [(lambda r, c, k=k: r['metrics'][c][k], _mean) for k in (0, 1, 2, 6)]
+    if peaks:
+        cols += [(lambda r, c: r['output']['peak_dbfs'][c], _mean), (lambda r, c: r['output']['clipped'][c], _mean),
+                 (lambda r, c: r['output']['gain'], _mean)]
+    return cols
+
+
+def metrics_rows(records, extended=False, peaks=False):
+    """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
+    (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
+    nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
+    mean of a column then runs over its entries that are not NaN (a clip too short for one segment has no segmental SNR).
+    `peaks`: the records carry 'output' and a row ends with the columns of METRICS_COLUMNS_PEAKS -- the channel's peak in
+    dBFS, its clipped samples and the file's gain; the mean row holds their plain means."""
+    cols = _columns(extended, peaks)
+    rows = [(r['path'], c, r['out_frames']) + tuple(value(r, c) for value, _ in cols)
+            for r in records for c in range(len(r['metrics_ext' if extended else 'metrics'] or ()))]
+    if rows:
+        rows.append(("mean", "", "") + tuple(mean([row[3 + k] for row in rows]) for k, (_, mean) in enumerate(cols)))
+    return rows
+
+
+def write_metrics_csv(path, records, extended=False, peaks=False):
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ()))
+        for row in metrics_rows(records, extended, peaks):
+            w.writerow([repr(v) if isinstance(v, float) else v for v in row])
+
+
+def _print_metrics(m, prefix=''):
+    mse, snr_sr, snr_lr, _, _, _, lsd = m
+    print('%sMSE: %.4f' % (prefix, mse))                                    # generate_audio.py:53-59
+    print('%sSNR_SR: %.4f' % (prefix, snr_sr))
+    print('%sSNR_LR: %.4f' % (prefix, snr_lr))
+    print('%sLSD: %.4f' % (prefix, lsd))
+
+
+def _print_metrics_ext(e, prefix=''):
+    print('%sLSD_LF: %.4f' % (prefix, e['lsd_lf']))
+    print('%sLSD_HF: %.4f' % (prefix, e['lsd_hf']))
+    print('%sSSNR_SR: %.4f' % (prefix, e['ssnr_sr']))
+    print('%sSSNR_LR: %.4f' % (prefix, e['ssnr_lr']))
+
+
+def _print_peaks(name, o):
+    print('%s: peak %s dBFS, %d clipped, %d non-finite, gain %.6f' % (name, ' '.join('%+.2f' % v for v in o['peak_dbfs']),
+                                                                    sum(o['clipped']), sum(o['nonfinite']), o['gain']))
+
+
+def _print_unwritten(name, available, written):
+    if written < available:
+        print('%s: %d of %d channels enhanced and written (--channels all writes every channel)' % (name, written, available))

@@ -1,0 +1,377 @@
+"""Whole-file generation: SuperResolver -- a clip through the model group by group, and the file path around it."""
+import math
+import os
+import struct
+
+import torch
+
+from .ops import _pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar
+from .plans import ClipError, check_crossover, check_encoding, check_lowband, check_output_options, plan_folder, segment_plan, select_channels, spectro_bins
+
+
+def _dbfs(level):
+    return 20.0 * math.log10(level) if level > 0.0 else float('-inf')
+
+
+def first_channel_metrics(metrics, channels):
+    """The per-channel list of 7-tuples (or None) as enhance_file returns it: with 'first' the one tuple itself."""
+    return metrics[0] if metrics is not None and channels == 'first' else metrics
+
+
+def per_channel_metrics(metrics, channels):
+    """What enhance_file returned as 'metrics' -> the list with one 7-tuple per written channel (or None)."""
+    return [metrics] if metrics is not None and channels == 'first' else metrics
+
+
+class SuperResolver:
+    """`model`: anything with `.inference(lr_audio, inst, noise=None) -> (sr_spectro, lr_pha, norm_param, lr_spectro)`
+    (Pix2PixHDModel); its `mdct_type` picks the inverse transform.  `overlap`: shared fraction of a segment, [0, 0.5].
+    `batch`: segments per group (default opt.batchSize).  `graph`: capture the chain of a full group once and replay it
+    (options that draw random numbers inside the chain -- mask_mode 'mode1', the single-channel encodings -- run eagerly).
+    `reference_amplitude` (mdct2 only): True keeps the amplitude of the reference's generate_audio.py, which is
+    sqrt(up_ratio - 1) * x / 2 for a spectrogram that encodes x; False returns sqrt(up_ratio - 1) * x.  Default: True at
+    overlap 0, the reference-exact mode, False with overlapping segments.
+    `lowband`: 'model' (default) decodes every row of the generator's spectrogram; 'input' keeps the input's own low band:
+    the rows below keep = int(bins / up_ratio), which the low-rate input carried, are decoded from the input's spectrogram
+    (the fourth value of `inference`) and only the rows from keep come from the generator (util.imdct, `lr_spectro`).
+    `lowband_fade`: rows below keep over which the two are cross-faded, 0 (a hard switch at keep) .. keep.  Both are fixed
+    for the object's life, so the captured chain holds them.  With up_ratio <= 1 keep is every row: 'input' is accepted and
+    returns the input's own transform round trip.
+    `crossover`: None (default), or 'input': behind the stitch the clip goes through a time-domain crossover (csrc/xover.hip),
+    out = sr + LP * ((gain / 2) * lr - sr) with LP a zero-delay Kaiser-windowed sinc: below `crossover_hz` (default 0.95 of the
+    low rate's Nyquist frequency) the result is the input at the level the pipeline returns a passed-through signal at, above
+    it the generator's output.  `crossover_taps`: the filter's length (odd, <= 4095; default: the shortest whose transition
+    band ends under that Nyquist frequency, crossover_plan).  Fixed for the object's life; the coefficients are filled once and
+    stay on the device.  One launch per clip, outside the captured chain; orthogonal to `lowband`.  Needs lr_sampling_rate <
+    hr_sampling_rate."""
+
+    def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
+                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None):
+        from ..models.mdct import IMDCT2, IMDCT4
+        from ..util import util as U
+        self.model, self.opt = model, opt
+        self.T = int(opt.segment_length)
+        self.overlap = float(overlap)
+        segment_plan(0, self.T, self.overlap)                               # validates both
+        self.batch = int(batch if batch is not None else getattr(opt, 'batchSize', 1))
+        if self.batch < 1:
+            raise ValueError("SuperResolver: batch must be >= 1, got %d" % self.batch)
+        self.graph = bool(graph)
+        self.device = torch.device(getattr(model, 'device', None) or 'cuda')
+        self.up_ratio = opt.hr_sampling_rate / opt.lr_sampling_rate
+        self.mdct_type = getattr(model, 'mdct_type', None) or getattr(opt, 'mdct_type', None) or 'mdct4'
+        kw = dict(window=U.kbdwin, win_length=opt.win_length, hop_length=opt.hop_length, n_fft=opt.n_fft,
+                  center=getattr(opt, 'center', True), out_length=self.T, device=self.device)
+        if self.mdct_type == 'mdct2':
+            from ..dct.dct import IDCT
+            self._imdct = IMDCT2(idct_op=IDCT(), **kw)                      # generate_audio.py:23-25
+        elif self.mdct_type == 'mdct4':
+            self._imdct = IMDCT4(**kw)
+        else:
+            raise ValueError("SuperResolver: mdct_type must be 'mdct2' or 'mdct4', got %r" % (self.mdct_type,))
+        if self.up_ratio < 1:
+            raise ValueError("SuperResolver: lr_sampling_rate above hr_sampling_rate")
+        self.lowband, self.lowband_fade, _ = check_lowband(lowband, lowband_fade, spectro_bins(opt.n_fft, self.mdct_type), self.up_ratio)
+        # Both inverse transforms return x for the spectrogram of x and util.imdct halves that (util/util.py:127 of the
+        # reference), so the hand-composed chain is a factor 2 short of generate_audio.py:47's sqrt(up_ratio - 1) * x; the
+        # stitch gain puts the factor back.  The reference's own output (MDCT2, back-to-back segments; tests/golden/generate.npz)
+        # carries the halving, and overlap = 0 is the mode that reproduces the reference bit for bit: there -- and only for
+        # mdct2, nothing of the reference runs MDCT4 -- the factor is left out, unless the caller decides otherwise.
+        if reference_amplitude is None:
+            reference_amplitude = self.overlap == 0.0
+        self.reference_amplitude = bool(reference_amplitude) and self.mdct_type == 'mdct2'
+        self.gain = math.sqrt(self.up_ratio - 1) * (1.0 if self.reference_amplitude else 2.0)
+        # The inverse-transform chain returns x / 2 for the spectrogram of x and the stitch multiplies by `gain`: a signal the
+        # generator passes through comes out as (gain / 2) * x, with or without reference_amplitude -- the level the input enters
+        # the crossover at.
+        self.crossover, self.crossover_hz, self.crossover_taps = crossover, crossover_hz, crossover_taps
+        self.crossover_plan = check_crossover(crossover, crossover_hz, crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
+        self._xover_taps = None                                             # the coefficients on the device, filled at first use
+        self._g = None                                                      # captured chain of a full group
+        self._pins = {}                                                     # pinned host buffers of the file path, grow-only
+
+    # -- one group ---------------------------------------------------------------------------------
+    def noise_shape(self, b):
+        """Shape of the mask noise `inference` draws for a group of b segments (the model's `mask_noise_shape`), or None when
+        the model draws none."""
+        f = getattr(self.model, 'mask_noise_shape', None)
+        return f(b, self.T) if callable(f) else None
+
+    def _graph_ok(self):
+        """Random draws must stay outside the graph, or replay would repeat them: the mask noise is handed in, but mask_mode
+        'mode1' draws signs and the single-channel phase encodings draw phase noise inside to_spectro.  Those options run eagerly."""
+        o = self.opt
+        if getattr(o, 'mask', False) and getattr(o, 'mask_mode', None) == 'mode1':
+            return False
+        if not getattr(o, 'explicit_encoding', False):
+            return getattr(o, 'phase_encoding_mode', None) in (None, 'scale') and self.up_ratio <= 1     # (util.imdct's random sign)
+        return True
+
+    def _group(self, seg, noise):
+        """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44)."""
+        from ..util import util as U
+        sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
+        splice = {} if self.lowband == 'model' else dict(lr_spectro=lr_spectro, lowband_fade=self.lowband_fade)
+        audio = U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=self._imdct,
+                        up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)), **splice)
+        audio = audio.reshape(seg.shape[0], -1)
+        if audio.shape[1] != self.T:
+            raise ValueError("SuperResolver: segment_length %d does not come back from the transform (got %d samples): use "
+                             "a multiple of hop_length" % (self.T, audio.shape[1]))
+        return audio
+
+    def _run_graphed(self, seg, noise):
+        """The chain of a full group through a graph over static buffers.  The first use runs the chain once eagerly on the
+        buffers (packed weights, tables and workspaces exist before capture), then captures it; every use replays.  Weights
+        that changed since (load_network, an optimiser step) make the capture stale: it is redone."""
+        from .. import _ops
+        g = self._g
+        if g is None or g['epoch'] != _ops._WEIGHT_EPOCH[0]:
+            shape = self.noise_shape(self.batch)
+            g = self._g = {'epoch': _ops._WEIGHT_EPOCH[0], 'graph': None, 'out': None,
+                           'seg': torch.empty((self.batch, self.T), dtype=torch.float32, device=self.device),
+                           'noise': None if shape is None else torch.empty(shape, dtype=torch.float32, device=self.device)}
+        g['seg'].copy_(seg)
+        if g['noise'] is not None:
+            g['noise'].copy_(noise)
+        if g['graph'] is None:
+            self._group(g['seg'], g['noise'])
+            torch.cuda.synchronize()
+            # as _train_step_graphed captures: a side stream behind the current (step) stream, thread-local capture mode,
+            # no flush of the caching allocator
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.stream(side):
+                graph.capture_begin(capture_error_mode="thread_local")
+                g['out'] = self._group(g['seg'], g['noise'])
+                graph.capture_end()
+            torch.cuda.current_stream().wait_stream(side)
+            g['graph'] = graph
+        g['graph'].replay()
+        return g['out']
+
+    # -- one clip ----------------------------------------------------------------------------------
+    def enhance_lr(self, lr_audio, noise=None):
+        """lr_audio: [C, L] or [L] on the GPU, already at the high rate -> the generated clip [C, L] ([1, L] for [L]).  Every
+        channel is a clip of its own: its S segments are grouped as if it were a mono clip, so
+        enhance_lr(x)[c] == enhance_lr(x[c:c+1])[0] given the same noise rows.  `noise`: the mask noise of all C * S segments,
+        [C * S, channels, mask_rows, frames], channel-major, sliced per group; drawn per group (one torch.randn) when absent."""
+        run = getattr(self.model, '_on_step_stream', None)
+        with torch.no_grad():
+            return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
+
+    def _enhance_lr(self, lr_audio, noise):
+        x = lr_audio.to(self.device).float()
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError("enhance_lr: expected a [C, L] or [L] waveform, got shape %s" % (tuple(lr_audio.shape),))
+        x = x.contiguous()
+        C, L = x.shape
+        S, stride, V = segment_plan(L, self.T, self.overlap)
+        seg = segments_gather_planar(x, self.T, stride, S)
+        out = torch.empty_like(seg)
+        for c in range(C):
+            for s0 in range(0, S, self.batch):
+                b = min(self.batch, S - s0)
+                r0 = c * S + s0
+                shape = self.noise_shape(b)
+                nz = None
+                if shape is not None:
+                    nz = noise[r0:r0 + b] if noise is not None else torch.randn(shape, device=self.device)
+                    if tuple(nz.shape) != shape:
+                        raise ValueError("enhance_lr: noise for segments %d..%d of channel %d has shape %s, expected %s"
+                                         % (s0, s0 + b - 1, c, tuple(nz.shape), shape))
+                if self.graph and b == self.batch and self._graph_ok():
+                    out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz))
+                else:
+                    out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz))
+        sr = segments_stitch_planar(out, C, stride, self.gain, L)
+        if self.crossover_plan is None:
+            return sr
+        if self._xover_taps is None:
+            self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
+        return crossover(sr, x, self.gain / 2.0, self._xover_taps)
+
+    # -- files -------------------------------------------------------------------------------------
+    def _pinned(self, slot, nbytes):
+        """Grow-only pinned byte buffer `slot`, free to be overwritten: the copy that last read it has finished.  Allocating
+        one goes through the HIP runtime: call from the thread that owns the device."""
+        t, busy = self._pins.get(slot, (None, None))
+        if busy is not None:
+            busy.synchronize()
+        if t is None or t.numel() < nbytes:
+            t = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, pin_memory=True)
+        self._pins[slot] = (t, None)
+        return t
+
+    def _read(self, path, slot='in0'):
+        """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo)."""
+        from ..data import wavio
+        payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
+        return self._pins[slot][0][:len(payload)], meta, slot
+
+    def _decode(self, host, meta, slot):
+        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel."""
+        if host.numel() == 0:
+            return torch.zeros((meta.num_channels, 0), dtype=torch.float32, device=self.device)
+        dev = torch.empty((host.numel(),), dtype=torch.uint8, device=self.device)
+        dev.copy_(host, non_blocking=True)
+        busy = torch.cuda.Event()
+        busy.record()
+        self._pins[slot] = (self._pins[slot][0], busy)
+        return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
+
+    def _write(self, path_out, sr, encoding, stage=None):
+        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
+        (check_output_options), or None for the encoder alone.  With a stage the peak kernel runs in front of the encoder,
+        which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
+        one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only."""
+        w = sr.contiguous()
+        dev, packed = self._encode(w, path_out is not None, encoding, stage)
+        host, stats = self._fetch(dev, packed)
+        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding)
+        if host is not None:
+            self._save(path_out, host, sr.shape[0], encoding)
+        return output
+
+    def _encode(self, w, wanted, encoding, stage):
+        """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None)."""
+        if stage is None:
+            return pcm_encode(w, encoding), None
+        (_, _, _, gain), packed = _pcm_peaks_packed(w, encoding, stage['ceiling'], "enhance_file")
+        if not wanted:
+            return None, packed
+        return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
+
+    def _fetch(self, dev, packed):
+        """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
+        -> (the payload, the peak buffer) on the host."""
+        host = stats = None
+        if dev is not None:
+            host = self._pinned('out', dev.numel())[:dev.numel()]
+            host.copy_(dev, non_blocking=True)
+        if packed is not None:
+            stats = self._pinned('peaks', packed.numel())[:packed.numel()]
+            stats.copy_(packed, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return host, stats
+
+    @staticmethod
+    def _output(stats, C, stage, path_out, encoding):
+        """The fetched peak buffer of a C-channel clip -> the result's 'output'; ClipError where clip 'error' finds a clipped sample."""
+        peak, over, nonfinite, gain = (v.tolist() for v in _peak_views(stats, C))
+        output = {'peak': peak, 'peak_dbfs': [_dbfs(v) for v in peak], 'clipped': over, 'nonfinite': nonfinite,
+                  'gain': gain[0] if stage['clip'] == 'guard' else 1.0}
+        if stage['clip'] == 'error' and any(over):
+            raise ClipError("%s: %d samples would clip in %s (peak %+.2f dBFS); nothing was written -- clip='guard' scales "
+                            "the file down, encoding='float32' keeps the samples"
+                            % (path_out, sum(over), encoding, max(output['peak_dbfs'])))
+        return output
+
+    def _save(self, path_out, host, channels, encoding):
+        from ..data import wavio
+        os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
+        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), channels, encoding)
+
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None):
+        """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
+        7-tuple per written channel, or None."""
+        from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
+        from ..util import util as U
+        o = self.opt
+        host, meta, slot = read
+        check_encoding(encoding, "enhance_file")
+        k = select_channels(channels, meta.num_channels)
+        rate = meta.sample_rate
+        raw = self._decode(host, meta, slot)[:k]
+        lr = audio_dataset.lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
+        has_hr = not is_lr_input and int(rate) == int(o.hr_sampling_rate)
+        if has_hr:
+            lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
+        sr = self.enhance_lr(lr)
+        metrics = ext = None
+        if has_hr and extended_metrics:
+            # every written channel in one call and one copy back; the 7-tuples are read off the same rows
+            ext = U.compute_matrics_ext(raw, lr, sr, o)
+            metrics = [(e['mse'], e['snr_sr'], e['snr_lr'], 0, 0, 0, e['lsd']) for e in ext]
+        elif has_hr:
+            metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
+        output = None
+        if path_out is not None or stage is not None:
+            output = self._write(path_out, sr, encoding, stage)
+        res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+        if extended_metrics:
+            res['metrics_ext'] = ext
+        if stage is not None:
+            res['output'] = output
+        return res
+
+    def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
+                     clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
+        """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
+        already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
+        int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
+        output encoded on the device (csrc/pcm.hip).  Returns {'sr', 'lr', 'hr', 'metrics', 'info'}: [C, L] tensors on the GPU;
+        'hr' and 'metrics' are None unless the input is a full-band clip at the high rate; 'metrics' is
+        util.compute_matrics against the input with 'first', else a list with one such 7-tuple per written channel, each
+        computed on that channel alone; 'info' is the input's wavio.WavInfo.  `extended_metrics`: the result gains
+        'metrics_ext', util.compute_matrics_ext of all written channels from one device call -- a list with one dict
+        (util.METRIC_ROW_NAMES -> float) per written channel, also with 'first'; None where 'metrics' is None -- and 'metrics'
+        holds the same rows' figures.
+        The output stage (all opt-in; 'sr' and the metrics are the unscaled clip whatever it does, only the written bytes
+        change).  `clip`: 'clamp' (default: the integer encodings clamp to their range, silently), 'guard' (the whole file, all
+        channels alike, is scaled down so that its peak sits at `ceiling_dbfs` -- None: the encoding's own limit; a file that
+        fits is left alone) or 'error' (ClipError, a ValueError, naming the file, its peak and the clipped count, before anything is
+        written).  `dither`: None or 'tpdf' (pcm16 only: +-1 LSB of triangular noise in front of the rounding, fixed by
+        `dither_seed`).  `report_peaks`: measure only.  With any of the five given the result gains 'output': {'peak',
+        'peak_dbfs', 'clipped', 'nonfinite' (a list each, one entry per written channel, measured on the unscaled clip for
+        `encoding`), 'gain' (the factor applied: 1.0 unless 'guard' scaled)}."""
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
+        res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage)
+        res['metrics'] = first_channel_metrics(res['metrics'], channels)
+        return res
+
+    def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
+                       extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
+        """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
+        and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
+        generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
+        `report(record)` is called after every file.  Returns one record per file: {'path' (relative), 'rate', 'channels',
+        'frames' (of the input), 'written_channels', 'out_frames', 'metrics' (as enhance_file(channels != 'first') returns
+        them: a list per channel, or None), 'error' (None, or the text of what went wrong)}; with `extended_metrics` also
+        'metrics_ext' (as enhance_file returns it).  `clip`, `ceiling_dbfs`, `dither`, `dither_seed`, `report_peaks`: the output
+        stage of enhance_file, per file (a guard gain is one file's); file k of the plan is dithered with seed `dither_seed` + k;
+        with any of them given a record gains 'output' (as enhance_file returns it, None for a skipped file).  clip 'error'
+        ends the run at the first file that would clip."""
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
+        records = []
+        for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
+            rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
+                   'metrics': None, 'error': None}
+            if extended_metrics:
+                rec['metrics_ext'] = None
+            if stage is not None:
+                rec['output'] = None
+            try:
+                read = self._read(path_in)
+            except (ValueError, OSError, EOFError, struct.error) as e:
+                rec['error'] = '%s: %s' % (type(e).__name__, e)
+            else:
+                if seed is not None:
+                    torch.manual_seed(int(seed))
+                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics,
+                                            None if stage is None else dict(stage, seed=dither_seed + k))
+                meta = res['info']
+                rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
+                           written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
+                           metrics=res['metrics'])
+                if extended_metrics:
+                    rec['metrics_ext'] = res['metrics_ext']
+                if stage is not None:
+                    rec['output'] = res['output']
+            records.append(rec)
+            if report is not None:
+                report(rec)
+        return records

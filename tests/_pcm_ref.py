@@ -99,6 +99,20 @@ def encode_input(frames, channels, seed=0):
     return np.ascontiguousarray(v[:n].reshape(frames, channels).T)
 
 
+def quantise_edges(bits):
+    """float32 values at which the order of clamping and rounding could matter for `bits` (16: every code, 24: every 251st):
+    each code boundary k / 2^(bits-1) and half-way point (k + 1/2) / 2^(bits-1) with its neighbours 1 ulp either side, the
+    +-1030 codes around -2^(bits-1), 0 and 2^(bits-1) - 1 the same way, and every exponent with mantissa 0, 1, 0x400000 and
+    all-ones, both signs (denormals, +-inf and NaNs with payloads among them)."""
+    half = 1 << (bits - 1)
+    near = np.arange(-1030, 1031)
+    k = np.unique(np.concatenate([np.arange(-half, half, 1 if bits == 16 else 251), near - half, near, near + half - 1])).astype(np.float64)
+    points = (np.concatenate([k, k + 0.5]) / half).astype(np.float32)
+    grid = np.concatenate([points, np.nextafter(points, np.float32(4)), np.nextafter(points, np.float32(-4))])
+    pattern = ((np.arange(256, dtype=np.uint32) << 23)[:, None] | np.array([0, 1, 0x400000, 0x7FFFFF], dtype=np.uint32)[None, :]).ravel()
+    return np.concatenate([grid, np.concatenate([pattern, pattern | np.uint32(0x80000000)]).astype("<u4").view("<f4")])
+
+
 def wav_bytes(payload_bytes, rate, channels, name, extensible=False):
     """A RIFF/WAVE file image around a payload; `extensible`: the 40-byte WAVE_FORMAT_EXTENSIBLE fmt chunk."""
     tag, bits, _ = FORMATS[name]

@@ -173,3 +173,39 @@ def test_save_image_both_kinds(tmp_path, ext):
         want = np.round((flt.astype(np.float64) - flt.min()) * (255.0 / (float(flt.max()) - float(flt.min()))))
         np.testing.assert_array_equal(back, want.astype(np.uint8))
         assert back.min() == 0 and back.max() == 255
+
+
+# ------------------------------------------------------------------------------------------
+# the package: what pix2pixhdaudiosr_amd.generate exports, and python -m
+# ------------------------------------------------------------------------------------------
+PUBLIC = ["CROSSOVERS", "LOWBANDS", "METRICS_COLUMNS", "METRICS_COLUMNS_EXT", "METRICS_COLUMNS_PEAKS", "PCM_ENCODINGS", "PCM_FORMATS",
+          "CLIP_MODES", "DITHERS", "CROSSOVER_BETA", "CROSSOVER_ATTEN_DB", "CROSSOVER_MAX_TAPS", "SuperResolver", "_parser", "_run",
+          "ceiling_from_dbfs", "check_crossover", "check_dither", "check_lowband", "check_output_options", "check_paths", "crossover",
+          "crossover_coefficients", "crossover_plan", "crossover_width_hz", "encoding_limit", "main", "metrics_rows", "opt_from_file",
+          "parse_opt_file", "pcm_decode", "pcm_encode", "pcm_peaks", "plan_folder", "segment_plan", "segments_gather",
+          "segments_gather_planar", "segments_stitch", "segments_stitch_planar", "select_channels", "write_metrics_csv"]
+
+
+def test_public_names_resolve_to_the_submodules():
+    import importlib
+    import inspect
+    G = importlib.import_module("pix2pixhdaudiosr_amd.generate")
+    parts = {"pix2pixhdaudiosr_amd.generate." + m for m in ("ops", "plans", "resolver", "report", "cli")}
+    for name in PUBLIC:
+        obj = getattr(G, name)
+        if inspect.isfunction(obj) or inspect.isclass(obj):
+            assert obj.__module__ in parts, (name, obj.__module__)
+            assert getattr(importlib.import_module(obj.__module__), name) is obj
+    assert G.__doc__.startswith(G._parser().description)
+
+
+def test_python_m_prints_the_parser_help():
+    import subprocess
+    import sys
+    from pix2pixhdaudiosr_amd.generate import _parser
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-m", "pix2pixhdaudiosr_amd.generate", "--help"], cwd=root, capture_output=True, text=True,
+                       env=dict(os.environ, COLUMNS="200"))
+    assert p.returncode == 0, p.stderr
+    options = lambda text: [w for w in text.split() if w.startswith("--")]
+    assert options(p.stdout) == options(_parser().format_help()) and "--crossover_taps" in options(p.stdout)

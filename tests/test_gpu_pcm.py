@@ -139,6 +139,49 @@ def test_encode_nan_is_zero_and_errors():
     assert L.lib().p2phd_pcm_encode(L.ptr(x), 3, 2, 2, 1, L.ptr(out), _stream()) != 0 and b"ld" in L.lib().p2phd_last_error()
 
 
+def _both_entries(planar, frames, channels, ld, code, nbytes):
+    """The payload of p2phd_pcm_encode and of p2phd_pcm_encode_ex with a null gain and no dither, each between canaries."""
+    L = _lib()
+    got = []
+    for ex in (False, True):
+        raw, mid = _guarded(nbytes)
+        tail = (L.ptr(mid), _stream())
+        if ex:
+            L.check(L.lib().p2phd_pcm_encode_ex(L.ptr(planar), frames, channels, ld, code, None, 0, 0, 0, *tail), "pcm_encode_ex")
+        else:
+            L.check(L.lib().p2phd_pcm_encode(L.ptr(planar), frames, channels, ld, code, *tail), "pcm_encode")
+        torch.cuda.synchronize()
+        assert _untouched(raw, nbytes)
+        got.append(mid.cpu().numpy().tobytes())
+    return got
+
+
+@pytest.mark.parametrize("encoding", ["pcm16", "pcm24"])
+def test_both_entries_on_the_quantiser_edges(encoding):
+    """One kernel serves both entries: on every value at which clamping before or after the rounding could differ
+    (P.quantise_edges), as one row and as three rows with a row pitch, both write the bytes of the restatement."""
+    tag, bits, code = P.ENCODINGS[encoding]
+    edges = P.quantise_edges(bits)
+    n = len(edges) // 3 * 3
+    for channels, pad in ((1, 0), (3, 7)):
+        frames = n // channels
+        x = np.ascontiguousarray(edges[:n].reshape(channels, frames))
+        planar = torch.full((channels, frames + pad), float("nan"), device=DEV)
+        planar[:, :frames] = torch.from_numpy(x).to(DEV)
+        want = P.encode(x, encoding)
+        for got in _both_entries(planar, frames, channels, frames + pad, code, n * bits // 8):
+            assert got == want, (encoding, channels)
+
+
+def test_both_entries_copy_float32_bits():
+    """NaNs with payloads, +-inf, denormals: float32 without a gain is a bit copy through either entry."""
+    x = P.quantise_edges(16)[-2048:].reshape(2, 1024)
+    assert len(np.unique(x.view(np.uint32)[np.isnan(x)])) == 6 and np.isinf(x).sum() == 2 and (np.abs(x[x != 0]) < 1e-38).sum() == 4
+    planar = torch.from_numpy(x.copy()).to(DEV)
+    for got in _both_entries(planar, 1024, 2, 1024, P.ENCODINGS["float32"][2], x.size * 4):
+        assert np.array_equal(np.frombuffer(got, dtype="<u4"), np.ascontiguousarray(x.T).view(np.uint32).ravel())
+
+
 def test_pcm_launch_family():
     from pix2pixhdaudiosr_amd.generate import pcm_decode, pcm_encode
     lib = _lib().lib()

@@ -198,6 +198,23 @@ def test_new_arguments_reach_the_output_stage(stub, tmp_path):
     assert len(sr.calls) == n and not (tmp_path / "x.wav").exists() and not (tmp_path / "out2").exists()
 
 
+def test_clip_error_is_a_value_error_and_passes_through(stub, tmp_path):
+    from pix2pixhdaudiosr_amd.generate import ClipError
+    assert issubclass(ClipError, ValueError)
+    sr, src = stub
+    raised = ClipError("o.wav: 3 samples would clip")
+
+    def refuse(path_out, clip, encoding, stage=None):
+        raise raised
+    sr._write = refuse
+    with pytest.raises(ClipError) as e:
+        sr.enhance_file(str(src / "b.wav"), str(tmp_path / "o.wav"), is_lr_input=True, clip='error')
+    assert e.value is raised
+    with pytest.raises(ClipError) as e:
+        sr.enhance_folder(str(src), str(tmp_path / "out"), is_lr_input=True, clip='error')
+    assert e.value is raised
+
+
 def test_cli_options():
     from pix2pixhdaudiosr_amd.generate import _parser, main
     a = _parser().parse_args(BASE)
@@ -280,3 +297,26 @@ def test_metrics_rows_with_peaks(extended, tmp_path):
             rows = list(csv.reader(f))
         assert tuple(rows[0]) == base + (METRICS_COLUMNS_PEAKS if peaks else ())
         assert all(len(r) == len(rows[0]) for r in rows) and len(rows) == 5
+
+
+ROWS = [('a.wav', 0, 10, 1.0, 2.0, 3.0, 4.0), ('b.wav', 0, 20, 2.0, 3.0, 4.0, 5.0), ('b.wav', 1, 20, 3.0, 4.0, 5.0, 6.0),
+        ('mean', '', '', 2.0, 3.0, 4.0, 5.0)]
+ROWS_EXT = [(5.0, 6.0, 7.0, 8.0), (6.0, 7.0, 8.0, 9.0), (7.0, 8.0, 9.0, 10.0), (6.0, 7.0, 8.0, 9.0)]
+ROWS_PEAKS = [(-6.0, 0, 1.0), (4.5, 7, 0.5), (0.0, 1, 0.5), (-0.5, 2.6666666666666665, 0.6666666666666666)]
+
+
+@pytest.mark.parametrize("extended", [False, True])
+@pytest.mark.parametrize("peaks", [False, True])
+def test_metrics_rows_fixed_table(extended, peaks):
+    """The rows of _records() as the table was before metrics_rows became one loop over its columns, value for value."""
+    from pix2pixhdaudiosr_amd.generate import metrics_rows
+    want = [r + (e if extended else ()) + (p if peaks else ()) for r, e, p in zip(ROWS, ROWS_EXT, ROWS_PEAKS)]
+    got = metrics_rows(_records(), extended, peaks)
+    assert got == want and [[type(v) for v in r] for r in got] == [[type(v) for v in r] for r in want]
+    # the means of the two tables differ on a NaN: it propagates in the basic one and is left out in the extended one
+    recs = _records()
+    recs[0]['metrics'] = [(float('nan'),) + recs[0]['metrics'][0][1:]]
+    recs[0]['metrics_ext'][0]['mse'] = float('nan')
+    mean = metrics_rows(recs, extended, peaks)[-1]
+    assert (mean[3] == 2.5) if extended else (mean[3] != mean[3])
+    assert mean[4:] == want[-1][4:]

@@ -222,3 +222,22 @@ def test_metrics_rows_and_csv(tmp_path):
     for k in range(4):
         assert body[-1][k] == sum(r[k] for r in body[:-1]) / 3    # floats are written so that they read back exactly
     assert body[0] == [m(1)[0], m(1)[1], m(1)[2], m(1)[6]]
+
+
+# ------------------------------------------------------------------------------------------
+# why one encode kernel is enough: the order of clamping and rounding
+# ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bits", [16, 24])
+def test_clamping_before_or_after_the_rounding_gives_one_integer(bits):
+    """wavio.save clamps, scales and rounds; the kernel of csrc/pcm.hip scales, rounds and clamps (the order a gain and a
+    dither in front of the rounding need).  Both in float32, on P.quantise_edges: the same integer for every value."""
+    x = P.quantise_edges(bits)
+    assert len(x) > 400000 and np.isnan(x).any() and np.isinf(x).any()
+    scale = np.float32(2 ** (bits - 1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        first = np.rint(np.clip(x, np.float32(-1), (scale - np.float32(1)) / scale) * scale)
+        after = np.clip(np.rint(x * scale), -scale, scale - np.float32(1))
+        assert first.dtype == after.dtype == np.float32
+        first, after = (np.where(np.isnan(x), np.float32(0), v).astype(np.int32) for v in (first, after))
+    assert np.array_equal(first, after)
+    assert first.min() == -2 ** (bits - 1) and first.max() == 2 ** (bits - 1) - 1
