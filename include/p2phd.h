@@ -86,7 +86,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
  * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
  * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
- * generation, csrc/xover.hip).  family == NULL with reset != 0 clears all.
+ * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip).
+ * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
 int64_t p2phd_launch_count(const char* family, int reset);
@@ -287,6 +288,48 @@ int p2phd_xover_taps_fill(int taps, double cutoff, double beta, float* out);
 int p2phd_xover_fwd(const float* sr, int64_t ld_sr, const float* lr, int64_t ld_lr, float level, const float* taps_dev, int taps,
                     int64_t C, int64_t L, float* out, int64_t ld_out, void* stream);
 int p2phd_xover_tile_len(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Spectrogram picture of whole-file generation, csrc/specimg.hip.  Launch family "specimg" (p2phd_stft_db and
+ * p2phd_specimg_render count 1 each when they launch: 2 per picture).  Stacked panels, one per row of x, with one time axis
+ * (the whole clip, left to right), one frequency axis (0 at a panel's bottom row, the Nyquist frequency at its top row) and one
+ * dB scale.
+ *
+ * p2phd_specimg_tables_floats / _fill (HOST only): 3 n_fft floats -- tw[j] = exp(-2 pi i j / n_fft) as (cos, sin) pairs, then the
+ *   periodic Hann window w[i] = 0.5 (1 - cos(2 pi i / n_fft)) -- float64 arithmetic, rounded once to fp32.  The caller uploads them.
+ * p2phd_stft_db: x[R][ld] f32 rows of L samples (ld >= L; rows may start at any float; 64-bit offsets) -> db[R][F][K] f32,
+ *   K = n_fft / 2 + 1, F = 1 + L / hop (integer division): the frames of
+ *   torch.stft(x, n_fft, hop, window=hann_periodic, center=True, pad_mode='constant') -- frame f covers the samples
+ *   f hop - n_fft / 2 .. + n_fft - 1, zero outside [0, L) --
+ *     X[f][k] = sum_i w[i] x[f hop - n_fft / 2 + i] exp(-2 pi i k i / n_fft)
+ *     P       = (re^2 + im^2) (4 / n_fft)^2          a full-scale sine reads 0 dB; the factor is an exact power of two
+ *     db      = 10 log10f(max(P, 1e-20))             P <= 1e-20 is written as the constant -200: silence is one bit pattern
+ *   n_fft: a power of two in [64, 2048]; 1 <= hop <= n_fft; R <= 65535; at most 2^30 frames; else P2PHD_EINVAL with an error
+ *   text.  L = 0 or R = 0: P2PHD_OK, nothing launched.  Two neighbouring frames share one complex transform; no atomics, no
+ *   reduction across workgroups: the same bits on every run.
+ * p2phd_stft_db_frames (host): F for L >= 1 samples; 0 and an error text for arguments p2phd_stft_db would refuse (or L < 1).
+ * p2phd_specimg_render: db[R][F][K] -> img[R H + (R - 1) gap][W][3] u8.  Pixel (panel r, row y, column x), all index arithmetic
+ *   in integers with 64-bit products:
+ *     y' = H - 1 - y
+ *     frames f0 = floor(x F / W) .. f1 = max(f0 + 1, floor((x + 1) F / W))        (W > F repeats a frame, W < F pools)
+ *     bins   k0 = floor(y' K / H) .. k1 = max(k0 + 1, floor((y' + 1) K / H))      (H > K repeats a bin,  H < K pools)
+ *     v   = max of db[r][f][k] over f0 <= f < f1, k0 <= k < k1, folded with fmaxf from -inf (a NaN never wins)
+ *     lo  = *top_dev - range                          top_dev: ONE f32 on the device, read by the kernel (no host round trip)
+ *     t   = fmul_rn(v - lo, scale),  scale = 255 / range computed once on the host in fp32
+ *     idx = clamp((int)rintf(t), 0, 255);  v = +inf: 255;  v = -inf (or nothing but NaN): 0;  a NaN t (NaN or infinite top): 0
+ *     rgb = lut_dev[idx]                              lut_dev: 256 x 3 u8 on the device
+ *   Every step is one correctly rounded fp32 operation or an exact function, so a float32 restatement gives the same bytes.
+ *   The `gap` rows between two panels hold (64, 64, 64).  1 <= W, H <= 16384, 0 <= gap <= 64, range > 0 and finite, 1 <= K <= 4097,
+ *   1 <= F <= 2^30, R <= 65535; else P2PHD_EINVAL.  R = 0: P2PHD_OK, nothing launched.  Every db value is read once.
+ * p2phd_specimg_image_bytes (host): bytes of img for R >= 1 panels; 0 and an error text for bad arguments.
+ * ---------------------------------------------------------------------------------------- */
+size_t p2phd_specimg_tables_floats(int n_fft);
+int p2phd_specimg_tables_fill(int n_fft, float* host_out);
+int64_t p2phd_stft_db_frames(int64_t L, int n_fft, int hop);
+size_t p2phd_specimg_image_bytes(int64_t R, int W, int H, int gap);
+int p2phd_stft_db(const float* x, int64_t ld, int64_t R, int64_t L, int n_fft, int hop, const float* tables, float* db, void* stream);
+int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const float* top_dev, float range, const uint8_t* lut_dev, int W,
+                         int H, int gap, uint8_t* img, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

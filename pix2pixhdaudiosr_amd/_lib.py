@@ -55,6 +55,12 @@ SIGNATURES = {
     "p2phd_xover_taps_fill": (_i32, [_i32, C.c_double, C.c_double, _vp]),
     "p2phd_xover_fwd": (_i32, [_vp, _i64, _vp, _i64, _f32, _vp, _i32, _i64, _i64, _vp, _i64, _vp]),
     "p2phd_xover_tile_len": (_i32, []),
+    "p2phd_specimg_tables_floats": (_sz, [_i32]),
+    "p2phd_specimg_tables_fill": (_i32, [_i32, _vp]),
+    "p2phd_stft_db_frames": (_i64, [_i64, _i32, _i32]),
+    "p2phd_specimg_image_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "p2phd_stft_db": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "p2phd_specimg_render": (_i32, [_vp, _i64, _i64, _i32, _vp, _f32, _vp, _i32, _i32, _i32, _vp, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -1,0 +1,257 @@
+// Whole-file generation (pix2pixhdaudiosr_amd/generate): the spectrogram picture of the clips a file leaves on the device --
+// the input the generator was given, the generated clip and, where there is one, the original -- as stacked panels with one
+// time axis, one frequency axis and one dB scale.  Two launches per picture, launch family "specimg".
+//
+//   stft_db   db[r][f][k] = 10 log10(max(P, 1e-20)),  P = |sum_i w[i] x_r[f hop - n/2 + i] e^(-2 pi i k i / n)|^2 (4 / n)^2,
+//             w[i] = 0.5 (1 - cos(2 pi i / n)), x zero outside [0, L): the frames of torch.stft(center=True, pad_mode='constant')
+//             with a periodic Hann window, scaled so that a full-scale sine reads 0 dB (the window's DC gain is n / 2, a real sine
+//             of amplitude 1 carries 1 / 2 per side: |X| = n / 4).  P <= 1e-20 is written as the constant -200.
+//   render    pixel (panel r, row y, column x) = lut[idx] of the maximum of db over the frames and bins the pixel covers,
+//             idx = clamp(rint((v - (top - range)) * (255 / range)), 0, 255); `gap` grey rows between panels.
+//
+// stft_db: one workgroup takes up to kPairs pairs of neighbouring frames of one row.  A pair goes through ONE n-point complex
+// Stockham FFT in LDS (fft_wave.h, run by the whole workgroup): z = w x_a + i w x_b, separated by A[k] = (Z[k] + conj Z[-k]) / 2,
+// B[k] = (Z[k] - conj Z[-k]) / 2i -- the halves are folded into the power-of-two scale.  The 2 K values of a pair are contiguous
+// in the plane (frames f and f + 1 of one row): they are staged in the LDS buffer the transform left free and go out as one
+// span, float4 stores between a scalar head and tail (K = n / 2 + 1 is odd, so a span starts at any float).  Window and twiddles
+// come from the caller's table (p2phd_specimg_tables_fill: float64 on the host, rounded once).
+//
+// render: the plane is walked in UNITS so that every value is read once whether the picture pools frames or repeats them:
+// with W <= F a unit is a column (its frames [x F / W, (x + 1) F / W)), with W > F a unit is a frame (its columns
+// [ceil(f W / F), ceil((f + 1) W / F))).  A workgroup takes one panel and `xt` consecutive units; per unit the threads lie along
+// K (contiguous: coalesced reads), fold the unit's frames in registers and leave the K column maxima in LDS, from which the
+// threads -- now along y -- fold each pixel row's bins and store the palette index as a byte in LDS.  The pixels then go out
+// with consecutive threads on consecutive bytes of an image row.  fmaxf from -inf: NaN never wins, the order of a maximum does
+// not matter, so the picture is the same bits on every run.  No atomics, no workspace.
+#include "common.h"
+#include "convplan.h"
+#include "fft_wave.h"
+#include <cmath>
+#include <cstdint>
+
+namespace {
+using namespace p2phd_fft;
+
+constexpr int kThreads = 256;
+constexpr int kPairs = 4;                       // frame pairs per workgroup of stft_db: the table is loaded once for all of them
+constexpr int kMinFft = 64, kMaxFft = 2048;
+constexpr int kMaxSide = 16384, kMaxGap = 64;
+constexpr int kMaxBins = 4097;                  // render: K floats of column maxima in LDS
+constexpr int kIdxBytes = 24576, kMaxUnits = 32;   // render: H * xt palette indices in LDS
+constexpr float kFloorP = 1e-20f, kFloorDb = -200.0f;
+constexpr unsigned char kGapGrey = 64;
+
+__global__ __launch_bounds__(kThreads) void stft_db_kernel(const float* __restrict__ x, long ld, long L, int n, int hop, long F,
+                                                           const float* __restrict__ tables, float pscale, float* __restrict__ db) {
+  extern __shared__ float4 smem_raw[];
+  float2* buf0 = reinterpret_cast<float2*>(smem_raw);
+  float2* buf1 = buf0 + n;
+  float2* s_tw = buf1 + n;
+  float* s_win = reinterpret_cast<float*>(s_tw + n);
+  const int tid = threadIdx.x;
+  const int K = (n >> 1) + 1;
+  const float* row = x + (long)blockIdx.y * ld;
+  float* plane = db + (long)blockIdx.y * F * K;
+  for (int i = tid; i < n; i += kThreads) {
+    s_tw[i] = reinterpret_cast<const float2*>(tables)[i];
+    s_win[i] = tables[2 * n + i];
+  }
+  const long pairs = (F + 1) >> 1;
+  const long p_lo = (long)blockIdx.x * kPairs, p_hi = min(pairs, p_lo + kPairs);
+  __syncthreads();
+  for (long p = p_lo; p < p_hi; ++p) {
+    const long fa = 2 * p;
+    const bool two = fa + 1 < F;
+    const long ia = fa * hop - (n >> 1);                          // first sample of frame fa; frame fa + 1 starts hop later
+    for (int j = tid; j < n; j += kThreads) {
+      const long a = ia + j, b = a + hop;
+      const float w = s_win[j];
+      const float va = (a >= 0 && a < L) ? row[a] : 0.0f;
+      const float vb = (two && b >= 0 && b < L) ? row[b] : 0.0f;
+      buf0[j] = make_float2(w * va, w * vb);
+    }
+    __syncthreads();
+    const float2* Z = fft_coop(buf0, buf1, s_tw, n, tid, kThreads);
+    float* s_out = reinterpret_cast<float*>(Z == buf0 ? buf1 : buf0);      // 2 n floats, free: holds the pair's 2 K <= n + 2 values
+    for (int k = tid; k < K; k += kThreads) {
+      const float2 a = Z[k], m = Z[(n - k) & (n - 1)];
+      const float ax = a.x + m.x, ay = a.y - m.y;                 // 2 A[k]
+      const float bx = a.y + m.y, by = m.x - a.x;                 // 2 B[k]
+      const float pa = (ax * ax + ay * ay) * pscale, pb = (bx * bx + by * by) * pscale;
+      s_out[k] = pa <= kFloorP ? kFloorDb : 10.0f * log10f(pa);
+      s_out[K + k] = pb <= kFloorP ? kFloorDb : 10.0f * log10f(pb);
+    }
+    __syncthreads();
+    // the span [fa K, fa K + cnt) of the row's plane: scalar stores up to the first 16-byte boundary, float4 stores, scalar tail
+    float* dst = plane + fa * K;
+    const int cnt = two ? 2 * K : K;
+    const int head = min(cnt, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2);
+    const int quads = (cnt - head) >> 2;
+    if (tid < head) dst[tid] = s_out[tid];
+    for (int q = tid; q < quads; q += kThreads) {
+      const int o = head + 4 * q;
+      *reinterpret_cast<float4*>(dst + o) = make_float4(s_out[o], s_out[o + 1], s_out[o + 2], s_out[o + 3]);
+    }
+    const int tail0 = head + 4 * quads;
+    if (tid < cnt - tail0) dst[tail0 + tid] = s_out[tail0 + tid];
+    __syncthreads();                                              // s_out is read: the next pair may overwrite either buffer
+  }
+}
+
+// ceil(a * b / c) and floor(a * b / c) of non-negative arguments, 64-bit products
+__device__ __forceinline__ long mul_floor(long a, long b, long c) { return a * b / c; }
+__device__ __forceinline__ long mul_ceil(long a, long b, long c) { return (a * b + c - 1) / c; }
+
+__global__ __launch_bounds__(kThreads) void render_kernel(const float* __restrict__ db, long F, int K, const float* __restrict__ top,
+                                                          float range, float scale, const unsigned char* __restrict__ lut, int W, int H,
+                                                          int gap, int xt, unsigned char* __restrict__ img) {
+  extern __shared__ float4 smem_raw[];
+  float* s_col = reinterpret_cast<float*>(smem_raw);                          // K column maxima of the unit in hand
+  unsigned char* s_lut = reinterpret_cast<unsigned char*>(s_col + K);         // 768 bytes
+  unsigned char* s_idx = s_lut + 768;                                         // [H][xt] palette indices
+  const int tid = threadIdx.x;
+  const long r = blockIdx.y;
+  const bool pooled = (long)W <= F;                               // a unit is a column; else a unit is a frame
+  const long units = pooled ? (long)W : F;
+  const long u0 = (long)blockIdx.x * xt, u1 = min(units, u0 + xt);
+  const float* plane = db + r * F * K;
+  const float lo = *top - range;
+  const float ninf = -__builtin_huge_valf();
+  for (int i = tid; i < 768; i += kThreads) s_lut[i] = lut[i];
+  for (long u = u0; u < u1; ++u) {
+    const long f0 = pooled ? mul_floor(u, F, W) : u;
+    const long f1 = pooled ? max(f0 + 1, mul_floor(u + 1, F, W)) : u + 1;
+    for (int k = tid; k < K; k += kThreads) {
+      float v = ninf;
+      for (long f = f0; f < f1; ++f) v = fmaxf(v, plane[f * K + k]);
+      s_col[k] = v;
+    }
+    __syncthreads();
+    for (int y = tid; y < H; y += kThreads) {
+      const long yy = H - 1 - y;
+      const int k0 = (int)mul_floor(yy, K, H);
+      const int k1 = max(k0 + 1, (int)mul_floor(yy + 1, K, H));
+      float v = ninf;
+      for (int k = k0; k < k1; ++k) v = fmaxf(v, s_col[k]);
+      int idx;
+      if (v == __builtin_huge_valf()) idx = 255;
+      else if (v == ninf) idx = 0;                                // -inf, or nothing but NaN
+      else idx = (int)fminf(fmaxf(rintf(__fmul_rn(v - lo, scale)), 0.0f), 255.0f);      // (fmaxf: a NaN t gives 0)
+      s_idx[(long)y * xt + (int)(u - u0)] = (unsigned char)idx;
+    }
+    __syncthreads();
+  }
+  // the pixels of this panel's rows in the tile's columns [xa, xb), and the grey rows under the panel
+  const long xa = pooled ? u0 : mul_ceil(u0, W, F);
+  const long xb = pooled ? u1 : mul_ceil(u1, W, F);
+  const long seg = (xb - xa) * 3, pitch = (long)W * 3;
+  unsigned char* out = img + (r * (H + gap)) * pitch + xa * 3;
+  for (long q = tid; q < (long)H * seg; q += kThreads) {
+    const long y = q / seg, b = q - y * seg;
+    const long xo = b / 3;
+    const int c = (int)(b - xo * 3);
+    const long u = pooled ? xa + xo : mul_floor(xa + xo, F, W);
+    out[y * pitch + b] = s_lut[3 * (int)s_idx[y * xt + (int)(u - u0)] + c];
+  }
+  if (r + 1 < (long)gridDim.y)
+    for (long q = tid; q < (long)gap * seg; q += kThreads) {
+      const long y = q / seg, b = q - y * seg;
+      out[(H + y) * pitch + b] = kGapGrey;
+    }
+}
+
+int check_stft(int n_fft, int hop, const char* who) {
+  P2PHD_REQUIRE(p2phd::is_pow2(n_fft) && n_fft >= kMinFft && n_fft <= kMaxFft, "%s: n_fft must be a power of two in [%d, %d], got %d", who,
+                kMinFft, kMaxFft, n_fft);
+  P2PHD_REQUIRE(hop >= 1 && hop <= n_fft, "%s: hop must be in [1, n_fft = %d], got %d", who, n_fft, hop);
+  return P2PHD_OK;
+}
+
+int check_image(int64_t R, int W, int H, int gap, const char* who) {
+  P2PHD_REQUIRE(R >= 0 && R <= 65535, "%s: need 0 <= R <= 65535 panels, got %lld", who, (long long)R);
+  P2PHD_REQUIRE(W >= 1 && W <= kMaxSide && H >= 1 && H <= kMaxSide, "%s: width and height must be in [1, %d], got W %d, H %d", who, kMaxSide, W, H);
+  P2PHD_REQUIRE(gap >= 0 && gap <= kMaxGap, "%s: gap must be in [0, %d], got %d", who, kMaxGap, gap);
+  return P2PHD_OK;
+}
+
+}  // namespace
+
+extern "C" size_t p2phd_specimg_tables_floats(int n_fft) {
+  if (check_stft(n_fft, 1, "specimg tables") != P2PHD_OK) return 0;
+  return 3 * (size_t)n_fft;
+}
+
+extern "C" int p2phd_specimg_tables_fill(int n_fft, float* host_out) {
+  if (int rc = check_stft(n_fft, 1, "specimg tables")) return rc;
+  P2PHD_REQUIRE(host_out != nullptr, "specimg tables: null output");
+  const double pi = 3.14159265358979323846264338327950288;
+  for (int j = 0; j < n_fft; ++j) {
+    const double a = -2.0 * pi * j / n_fft;
+    host_out[2 * j] = (float)std::cos(a);
+    host_out[2 * j + 1] = (float)std::sin(a);
+    host_out[2 * n_fft + j] = (float)(0.5 * (1.0 - std::cos(2.0 * pi * j / n_fft)));
+  }
+  return P2PHD_OK;
+}
+
+extern "C" int64_t p2phd_stft_db_frames(int64_t L, int n_fft, int hop) {
+  if (check_stft(n_fft, hop, "stft_db_frames") != P2PHD_OK) return 0;
+  if (L < 1 || L > (int64_t(1) << 40)) {
+    p2phd::set_error("stft_db_frames: need 1 <= L <= 2^40 samples, got %lld", (long long)L);
+    return 0;
+  }
+  return 1 + L / hop;
+}
+
+extern "C" size_t p2phd_specimg_image_bytes(int64_t R, int W, int H, int gap) {
+  if (check_image(R, W, H, gap, "specimg_image_bytes") != P2PHD_OK) return 0;
+  if (R < 1) {
+    p2phd::set_error("specimg_image_bytes: a picture needs at least one panel");
+    return 0;
+  }
+  return ((size_t)R * (size_t)H + (size_t)(R - 1) * (size_t)gap) * (size_t)W * 3;
+}
+
+extern "C" int p2phd_stft_db(const float* x, int64_t ld, int64_t R, int64_t L, int n_fft, int hop, const float* tables, float* db,
+                             void* stream) {
+  if (int rc = check_stft(n_fft, hop, "stft_db")) return rc;
+  P2PHD_REQUIRE(R >= 0 && R <= 65535 && L >= 0 && L <= (int64_t(1) << 40), "stft_db: need 0 <= R <= 65535 and 0 <= L <= 2^40 (R %lld, L %lld)",
+                (long long)R, (long long)L);
+  P2PHD_REQUIRE(ld >= L && ld <= (int64_t(1) << 44), "stft_db: the row pitch %lld is shorter than the %lld samples of a row, or too large",
+                (long long)ld, (long long)L);
+  if (L == 0 || R == 0) return P2PHD_OK;
+  const int64_t F = 1 + L / hop;
+  P2PHD_REQUIRE(F <= (int64_t(1) << 30), "stft_db: %lld frames are more than 2^30: use a longer hop", (long long)F);
+  P2PHD_REQUIRE(x && tables && db, "stft_db: null pointer");
+  P2PHD_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(db)) & 3) == 0 && (reinterpret_cast<uintptr_t>(tables) & 7) == 0,
+                "stft_db: a pointer is not aligned (x, db: a float; tables: 8 bytes)");
+  const size_t lds = (size_t)n_fft * (3 * sizeof(float2) + sizeof(float));
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stft_db_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const float pscale = 4.0f / ((float)n_fft * (float)n_fft);      // (4 / n)^2 / 4, the halves of the separation: a power of two
+  const dim3 grid((unsigned)p2phd::cdiv((F + 1) / 2, kPairs), (unsigned)R);
+  hipLaunchKernelGGL(stft_db_kernel, grid, dim3(kThreads), lds, (hipStream_t)stream, x, (long)ld, (long)L, n_fft, hop, (long)F, tables, pscale,
+                     db);
+  ++p2phd::g_launch_count[p2phd::LC_SPECIMG];
+  return p2phd::check_launch("stft_db");
+}
+
+extern "C" int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const float* top_dev, float range, const uint8_t* lut_dev,
+                                    int W, int H, int gap, uint8_t* img, void* stream) {
+  if (int rc = check_image(R, W, H, gap, "specimg_render")) return rc;
+  P2PHD_REQUIRE(range > 0.0f && std::isfinite(range), "specimg_render: range must be finite and > 0 dB, got %g", (double)range);
+  P2PHD_REQUIRE(F >= 0 && F <= (int64_t(1) << 30) && K >= 1 && K <= kMaxBins, "specimg_render: need 0 <= F <= 2^30 frames and 1 <= K <= %d bins "
+                "(F %lld, K %d)", kMaxBins, (long long)F, K);
+  if (R == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(F >= 1, "specimg_render: a panel needs at least one frame");
+  P2PHD_REQUIRE(db && top_dev && lut_dev && img, "specimg_render: null pointer");
+  P2PHD_REQUIRE(((reinterpret_cast<uintptr_t>(db) | reinterpret_cast<uintptr_t>(top_dev)) & 3) == 0, "specimg_render: a pointer is not aligned to a float");
+  const int xt = std::max(1, std::min(kMaxUnits, kIdxBytes / H));
+  const int64_t units = std::min<int64_t>(W, F);
+  const size_t lds = (size_t)K * sizeof(float) + 768 + (size_t)H * (size_t)xt;
+  const float scale = 255.0f / range;
+  hipLaunchKernelGGL(render_kernel, dim3((unsigned)p2phd::cdiv(units, xt), (unsigned)R), dim3(kThreads), lds, (hipStream_t)stream, db, (long)F, K,
+                     top_dev, range, scale, lut_dev, W, H, gap, xt, img);
+  ++p2phd::g_launch_count[p2phd::LC_SPECIMG];
+  return p2phd::check_launch("specimg_render");
+}

@@ -30,13 +30,17 @@ the integer encodings clamp, silently.
 `--crossover input` (opt-in, csrc/xover.hip) puts a time-domain crossover behind the stitch: a linear-phase complementary
 filter pair, so that below `--crossover_hz` (default: 0.95 of the low rate's Nyquist frequency) the written clip is the input
 and above it the generator's output.
+
+`--spectrogram PATH` (opt-in, csrc/specimg.hip) also leaves a picture: the spectrograms of the input the generator was given,
+of the written clip and -- for a full-band input -- of the original, stacked on one time, frequency and dB scale, rendered
+on the device from the clips that are there at the end of enhance_file (`spectrogram_image`, `stft_db`, `spectrogram_rgb`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, crossover, crossover_coefficients, pcm_decode, pcm_encode, pcm_peaks, segments_gather,  # noqa: F401
-                  segments_gather_planar, segments_stitch, segments_stitch_planar)
+                  segments_gather_planar, segments_stitch, segments_stitch_planar, spectrogram_rgb, stft_db)
 from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, LOWBANDS,  # noqa: F401
-                    PCM_ENCODINGS, ClipError, ceiling_from_dbfs, check_crossover, check_dither, check_encoding, check_lowband,
-                    check_output_options, check_paths, crossover_plan, crossover_width_hz, encoding_limit, plan_folder, segment_plan,
-                    select_channels, spectro_bins)
+                    PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, ClipError, ceiling_from_dbfs, check_crossover,
+                    check_dither, check_encoding, check_lowband, check_output_options, check_paths, check_spectrogram, crossover_plan,
+                    crossover_width_hz, encoding_limit, plan_folder, segment_plan, select_channels, spectro_bins, spectrogram_lut)
 from .report import METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_PEAKS, metrics_rows, write_metrics_csv        # noqa: F401
-from .resolver import SuperResolver                                                                              # noqa: F401
+from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

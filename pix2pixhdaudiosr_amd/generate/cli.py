@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import torch
 
 from .plans import (CLIP_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_lowband, check_output_options, check_paths,
-                    spectro_bins)
+                    check_spectrogram, spectro_bins)
 from .report import _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
@@ -60,6 +60,35 @@ def _channels_arg(text):
     if n < 1:
         raise argparse.ArgumentTypeError("expected all, first or a count >= 1, got %r" % text)
     return n
+
+
+def _size_arg(text):
+    w, sep, h = text.lower().partition('x')
+    try:
+        return int(w), int(h)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected WIDTHxHEIGHT in pixels, such as 1600x512, got %r" % text)
+
+
+def _spectrogram_args(a, folder_mode):
+    """The spectrogram options of the command line -> the three keyword arguments of enhance_file / enhance_folder ({} without
+    --spectrogram); ValueError for a bad one."""
+    given = [n for n in ('channel', 'n_fft', 'hop', 'size', 'range_db', 'top_db') if getattr(a, 'spectrogram_' + n) is not None]
+    if a.spectrogram is None:
+        if given:
+            raise ValueError("--spectrogram_%s is an option of --spectrogram PATH" % given[0])
+        return {}
+    if folder_mode and os.path.isfile(a.spectrogram):
+        raise ValueError("--input is a directory, so --spectrogram must be a directory too, and %s is a file" % a.spectrogram)
+    if not folder_mode and os.path.isdir(a.spectrogram):
+        raise ValueError("--input is a file, so --spectrogram must be a file too, and %s is a directory" % a.spectrogram)
+    opts = {k: v for k, v in (('n_fft', a.spectrogram_n_fft), ('hop', a.spectrogram_hop), ('range_db', a.spectrogram_range_db),
+                              ('top_db', a.spectrogram_top_db)) if v is not None}
+    if a.spectrogram_size is not None:
+        opts['width'], opts['height'] = a.spectrogram_size
+    channel = 0 if a.spectrogram_channel is None else a.spectrogram_channel
+    check_spectrogram(channel=channel, who="generate", **opts)
+    return dict(spectrogram=a.spectrogram, spectrogram_channel=channel, spectrogram_opts=opts or None)
 
 
 def _parser():
@@ -115,11 +144,30 @@ def _parser():
     ap.add_argument("--report_peaks", action="store_true",
                     help="print peak (dBFS), clipped and non-finite samples and the gain of every file; three more columns "
                          "(peak_dbfs, clipped, gain) of --metrics_csv")
+    ap.add_argument("--spectrogram", default=None, metavar="PATH",
+                    help="also write a PNG with the spectrograms of the input the generator was given, of the written clip and, for "
+                         "a full-band input, of the original, top to bottom on one time, frequency and dB scale (a folder in folder "
+                         "mode: one picture per file, at the file's relative path + .png; default: off)")
+    ap.add_argument("--spectrogram_channel", type=int, default=None, metavar="N", help="--spectrogram: the written channel to show (default 0)")
+    ap.add_argument("--spectrogram_n_fft", type=int, default=None, metavar="N",
+                    help="--spectrogram: STFT length, a power of two in 64 .. 2048 (default 1024)")
+    ap.add_argument("--spectrogram_hop", type=int, default=None, metavar="N", help="--spectrogram: STFT hop in samples (default 256)")
+    ap.add_argument("--spectrogram_size", type=_size_arg, default=None, metavar="WxH",
+                    help="--spectrogram: pixels of one panel (default 1600x512)")
+    ap.add_argument("--spectrogram_range_db", type=float, default=None, metavar="DB",
+                    help="--spectrogram: dB below the top that reach the palette's first colour (default 90)")
+    ap.add_argument("--spectrogram_top_db", type=float, default=None, metavar="DB",
+                    help="--spectrogram: level of the palette's last colour, 0 = a full-scale sine (default: the picture's own maximum)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
                          "the one the reference's train.py, which writes opt.txt, is hard-wired to)")
     return ap
+
+
+def _print_spectrogram(p):
+    print('spectrogram: %s (%d panels, %d frames x %d bins, %.1f dB down from %+.1f dB)'
+          % (p['path'], p['panels'], p['frames'], p['bins'], p['range_db'], p['top_db']))
 
 
 def main(argv=None):
@@ -128,9 +176,10 @@ def main(argv=None):
     try:                                                                    # before anything is loaded
         folder_mode = check_paths(a.input, a.output)
         check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
+        picture = _spectrogram_args(a, folder_mode)
     except ValueError as e:
         ap.error(str(e))
-    stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks)
+    stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks, **picture)
     folder = os.path.abspath(a.load_pretrain)
     over = dict(checkpoints_dir=os.path.dirname(folder), name=os.path.basename(folder), load_pretrain='', continue_train=False)
     for k in ("which_epoch", "batchSize"):
@@ -180,6 +229,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
             if a.report_peaks:
                 _print_peaks(r['path'], r['output'])
+            if r.get('spectrogram') is not None:                           # (without the option: no line more than before)
+                _print_spectrogram(r['spectrogram'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -206,6 +257,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
         if a.report_peaks:
             _print_peaks(a.output, res['output'])
+        if res.get('spectrogram') is not None:
+            _print_spectrogram(res['spectrogram'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output')}]
     if a.metrics_csv:

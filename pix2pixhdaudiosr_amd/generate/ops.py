@@ -1,10 +1,11 @@
-"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip and csrc/xover.hip as tensor functions."""
+"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip and csrc/specimg.hip as
+tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from .plans import CROSSOVER_MAX_TAPS, check_dither, check_encoding
+from .plans import CROSSOVER_MAX_TAPS, check_dither, check_encoding, spectrogram_lut
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -162,3 +163,66 @@ def crossover(sr, lr, level, taps_dev):
     _lib.check(_lib.lib().p2phd_xover_fwd(_lib.ptr(s), max(ld_s, L), _lib.ptr(l), max(ld_l, L), float(level), _lib.ptr(h), h.numel(), C, L,
                                           _lib.ptr(out), max(L, 1), _lib.stream_ptr()), "xover_fwd")
     return out
+
+
+_SPECIMG_TABLES = {}                                                        # (n_fft, device) -> twiddles and window on the device
+_SPECIMG_LUT = {}                                                           # device -> the palette on the device
+
+
+def _specimg_tables(n_fft, device):
+    key = (int(n_fft), str(device))
+    t = _SPECIMG_TABLES.get(key)
+    if t is None:
+        n = _lib.lib().p2phd_specimg_tables_floats(int(n_fft))
+        if n == 0:
+            _lib.check(-1, "specimg_tables_floats")
+        host = torch.empty((n,), dtype=torch.float32)
+        _lib.check(_lib.lib().p2phd_specimg_tables_fill(int(n_fft), ctypes.c_void_p(host.data_ptr())), "specimg_tables_fill")
+        t = _SPECIMG_TABLES[key] = host.to(device)
+    return t
+
+
+def stft_db(rows, n_fft, hop):
+    """rows [R, L] f32 on the GPU (rows contiguous, any row pitch) -> [R, F, K] f32, F = 1 + L // hop, K = n_fft // 2 + 1: the
+    power of torch.stft(rows, n_fft, hop, window=hann_periodic, center=True, pad_mode='constant') in dB, scaled so that a
+    full-scale sine reads 0 and floored at -200 (p2phd_stft_db).  L = 0: an empty [R, 0, K].  Nothing is waited for."""
+    x, R, L, ld = _rows(rows, "stft_db: rows")
+    lib = _lib.lib()
+    F = 0
+    if L > 0:
+        F = lib.p2phd_stft_db_frames(L, int(n_fft), int(hop))
+        if F == 0:
+            _lib.check(-1, "stft_db_frames")
+    db = torch.empty((R, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
+    tables = _specimg_tables(n_fft, x.device) if L > 0 else None
+    _lib.check(lib.p2phd_stft_db(_lib.ptr(x), max(ld, L), R, L, int(n_fft), int(hop), _lib.ptr(tables), _lib.ptr(db), _lib.stream_ptr()), "stft_db")
+    return db
+
+
+def spectrogram_rgb(db, top, range_db, width, height, gap):
+    """db [R, F, K] f32 on the GPU -> the picture [R * height + (R - 1) * gap, width, 3] uint8 on the GPU: panel r shows
+    db[r] with time left to right and bin 0 in its bottom row, every pixel the maximum of the frames and bins it covers, coloured
+    by plans.spectrogram_lut from `top` - `range_db` (index 0) to `top` (index 255); `gap` grey rows between panels
+    (p2phd_specimg_render).  `top`: a float32 tensor of one element on the GPU, which the kernel reads -- db.amax() for the
+    picture's own maximum -- or a number.  Nothing is waited for."""
+    d = _lib.require_gpu_tensor(db, "spectrogram_rgb: db", torch.float32)
+    if d.dim() != 3 or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError("spectrogram_rgb: expected [R, F, K] with at least one panel and one frame, got shape %s" % (tuple(d.shape),))
+    R, F, K = d.shape
+    if isinstance(top, torch.Tensor):
+        top = _lib.require_gpu_tensor(top, "spectrogram_rgb: top", torch.float32)
+        if top.numel() != 1:
+            raise ValueError("spectrogram_rgb: top must hold one value, got shape %s" % (tuple(top.shape),))
+    else:
+        top = torch.full((1,), float(top), dtype=torch.float32, device=d.device)
+    lib = _lib.lib()
+    nbytes = lib.p2phd_specimg_image_bytes(R, int(width), int(height), int(gap))
+    if nbytes == 0:
+        _lib.check(-1, "specimg_image_bytes")
+    lut = _SPECIMG_LUT.get(str(d.device))
+    if lut is None:
+        lut = _SPECIMG_LUT[str(d.device)] = torch.from_numpy(spectrogram_lut()).to(d.device)
+    img = torch.empty((nbytes // (3 * int(width)), int(width), 3), dtype=torch.uint8, device=d.device)
+    _lib.check(lib.p2phd_specimg_render(_lib.ptr(d), R, F, K, _lib.ptr(top), float(range_db), _lib.ptr(lut), int(width), int(height), int(gap),
+                                        _lib.ptr(img), _lib.stream_ptr()), "specimg_render")
+    return img

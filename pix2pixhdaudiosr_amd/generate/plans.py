@@ -11,6 +11,13 @@ CROSSOVERS = (None, 'input')
 CROSSOVER_BETA = 8.96                                                       # Kaiser window, 90 dB
 CROSSOVER_ATTEN_DB = 90.0
 CROSSOVER_MAX_TAPS = 4095
+# the spectrogram picture (csrc/specimg.hip): STFT length and hop in samples, pixels of one panel, dB below the top that
+# reach the palette's first colour, grey rows between panels
+SPECTROGRAM_DEFAULTS = {'n_fft': 1024, 'hop': 256, 'width': 1600, 'height': 512, 'range_db': 90.0, 'gap': 2}
+SPECTROGRAM_MAX_SIDE = 16384
+SPECTROGRAM_MAX_GAP = 64
+# (index, (r, g, b)) anchors of spectrogram_lut
+SPECTROGRAM_LUT_ANCHORS = ((0, (0, 0, 4)), (64, (30, 20, 140)), (128, (180, 40, 150)), (192, (250, 140, 30)), (255, (255, 250, 190)))
 
 
 class ClipError(ValueError):
@@ -165,6 +172,53 @@ def check_crossover(crossover, crossover_hz, crossover_taps, hr_rate, lr_rate):
             raise ValueError("SuperResolver: crossover_hz / crossover_taps are options of crossover='input'; crossover is None")
         return None
     return crossover_plan(hr_rate, lr_rate, crossover_hz, crossover_taps)
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_spectrogram(n_fft=None, hop=None, width=None, height=None, range_db=None, gap=None, top_db=None, channel=0,
+                      who="enhance_file"):
+    """Validates the options of the spectrogram picture, None standing for SPECTROGRAM_DEFAULTS' value -> the plan
+    {'n_fft', 'hop', 'width', 'height', 'range_db', 'gap'} that ops.stft_db / ops.spectrogram_rgb take.  `n_fft`: a power of
+    two in [64, 2048]; `hop`: 1 .. n_fft; `width`, `height` (of one panel): 1 .. 16384; `range_db`: finite and > 0; `gap`:
+    0 .. 64; `top_db` (not part of the plan): None -- the picture's own maximum -- or a finite level; `channel`: an int >= 0.
+    A ValueError names the argument."""
+    d = SPECTROGRAM_DEFAULTS
+    n_fft, hop = (d['n_fft'] if n_fft is None else n_fft), (d['hop'] if hop is None else hop)
+    width, height = (d['width'] if width is None else width), (d['height'] if height is None else height)
+    range_db, gap = (d['range_db'] if range_db is None else range_db), (d['gap'] if gap is None else gap)
+    if not _is_int(n_fft) or not 64 <= n_fft <= 2048 or n_fft & (n_fft - 1):
+        raise ValueError("%s: spectrogram n_fft must be a power of two in [64, 2048], got %r" % (who, n_fft))
+    if not _is_int(hop) or not 1 <= hop <= n_fft:
+        raise ValueError("%s: spectrogram hop must be an int in [1, n_fft = %d], got %r" % (who, n_fft, hop))
+    for name, v in (('width', width), ('height', height)):
+        if not _is_int(v) or not 1 <= v <= SPECTROGRAM_MAX_SIDE:
+            raise ValueError("%s: spectrogram %s must be an int in [1, %d], got %r" % (who, name, SPECTROGRAM_MAX_SIDE, v))
+    if isinstance(range_db, bool) or not isinstance(range_db, (int, float)) or not 0.0 < range_db < float('inf'):
+        raise ValueError("%s: spectrogram range_db must be finite and > 0, got %r" % (who, range_db))
+    if not _is_int(gap) or not 0 <= gap <= SPECTROGRAM_MAX_GAP:
+        raise ValueError("%s: spectrogram gap must be an int in [0, %d], got %r" % (who, SPECTROGRAM_MAX_GAP, gap))
+    if top_db is not None and (isinstance(top_db, bool) or not isinstance(top_db, (int, float)) or not math.isfinite(top_db)):
+        raise ValueError("%s: spectrogram top_db must be None (the picture's own maximum) or a finite level in dB, got %r" % (who, top_db))
+    if not _is_int(channel) or channel < 0:
+        raise ValueError("%s: spectrogram channel must be an int >= 0, got %r" % (who, channel))
+    return {'n_fft': n_fft, 'hop': hop, 'width': width, 'height': height, 'range_db': float(range_db), 'gap': gap}
+
+
+def spectrogram_lut():
+    """The palette of the spectrogram picture: a 256 x 3 uint8 numpy array, index 0 the quietest.  Anchors
+    (SPECTROGRAM_LUT_ANCHORS): 0 (0, 0, 4) near-black, 64 (30, 20, 140) blue, 128 (180, 40, 150) magenta, 192 (250, 140, 30)
+    orange, 255 (255, 250, 190) pale yellow; between two anchors (i0, a) and (i1, b) every channel is
+    a + (b - a) * (i - i0) // (i1 - i0), integers throughout.  The integer Rec.601 luminance 299 r + 587 g + 114 b never
+    falls as the index rises, so a grey-scale print keeps the order."""
+    import numpy as np
+    lut = np.zeros((256, 3), dtype=np.uint8)
+    for (i0, a), (i1, b) in zip(SPECTROGRAM_LUT_ANCHORS[:-1], SPECTROGRAM_LUT_ANCHORS[1:]):
+        for i in range(i0, i1 + 1):
+            lut[i] = [a[c] + (b[c] - a[c]) * (i - i0) // (i1 - i0) for c in range(3)]
+    return lut
 
 
 def plan_folder(dir_in, dir_out):

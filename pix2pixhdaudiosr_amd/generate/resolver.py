@@ -5,8 +5,10 @@ import struct
 
 import torch
 
-from .ops import _pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar
-from .plans import ClipError, check_crossover, check_encoding, check_lowband, check_output_options, plan_folder, segment_plan, select_channels, spectro_bins
+from .ops import (_pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, pcm_decode, pcm_encode, segments_gather_planar,
+                  segments_stitch_planar, spectrogram_rgb, stft_db)
+from .plans import (ClipError, check_crossover, check_encoding, check_lowband, check_output_options, check_spectrogram, plan_folder, segment_plan,
+                    select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -21,6 +23,29 @@ def first_channel_metrics(metrics, channels):
 def per_channel_metrics(metrics, channels):
     """What enhance_file returned as 'metrics' -> the list with one 7-tuple per written channel (or None)."""
     return [metrics] if metrics is not None and channels == 'first' else metrics
+
+
+def _spectrogram(rows, top_db, plan):
+    """The device work of spectrogram_image -> (the picture, the dB planes, the top as a float32 tensor of one element)."""
+    db = stft_db(rows, plan['n_fft'], plan['hop'])
+    if db.shape[0] < 1 or db.shape[1] < 1:
+        raise ValueError("spectrogram_image: a picture needs at least one row of at least one sample, got shape %s" % (tuple(rows.shape),))
+    if top_db is None:
+        top = db.amax().reshape(1)
+    else:
+        top = torch.full((1,), float(top_db), dtype=torch.float32, device=db.device)
+    return spectrogram_rgb(db, top, plan['range_db'], plan['width'], plan['height'], plan['gap']), db, top
+
+
+def spectrogram_image(rows, top_db=None, **plan):
+    """rows [R, L] f32 on the GPU, one clip per panel -> the picture [R * height + (R - 1) * gap, width, 3] uint8 on the GPU
+    (util.save_image writes it once it is on the host): panel r is the spectrogram of rows[r] -- ops.stft_db, a Hann-windowed
+    STFT in dB where a full-scale sine reads 0 -- the whole clip left to right, 0 Hz in the panel's bottom row and the Nyquist
+    frequency in its top row; all panels share the dB scale, from `top_db` - range_db (the palette's first colour) to `top_db`
+    (its last).  `top_db`: None -- the largest value of all panels, taken on the device and read there by the renderer -- or
+    a fixed level.  `plan`: n_fft, hop, width, height (of one panel), range_db, gap (plans.check_spectrogram;
+    SPECTROGRAM_DEFAULTS where left out).  Two launches of the family "specimg", nothing is waited for."""
+    return _spectrogram(rows, top_db, check_spectrogram(top_db=top_db, who="spectrogram_image", **plan))[0]
 
 
 class SuperResolver:
@@ -223,14 +248,15 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
-        (check_output_options), or None for the encoder alone.  With a stage the peak kernel runs in front of the encoder,
+        (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
+        back with them, see _fetch.  With a stage the peak kernel runs in front of the encoder,
         which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
         one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only."""
         w = sr.contiguous()
-        dev, packed = self._encode(w, path_out is not None, encoding, stage)
-        host, stats = self._fetch(dev, packed)
+        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage)
+        host, stats = self._fetch(dev, packed, picture)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding)
         if host is not None:
             self._save(path_out, host, sr.shape[0], encoding)
@@ -245,10 +271,18 @@ class SuperResolver:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed):
+    def _fetch(self, dev, packed, picture=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
-        -> (the payload, the peak buffer) on the host."""
+        -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
+        copied behind the same synchronisation and replaced by their host copies."""
         host = stats = None
+        if picture is not None:
+            img, top = picture['image'], picture['top']
+            n = img.numel()
+            pin = self._pinned('picture', 4 + n)                           # the top's four bytes, then the pixels
+            pin[:4].copy_(top.view(torch.uint8), non_blocking=True)
+            pin[4:4 + n].copy_(img.reshape(-1), non_blocking=True)
+            picture['image'], picture['top'] = pin[4:4 + n].view(img.shape), pin[:4].view(torch.float32)
         if dev is not None:
             host = self._pinned('out', dev.numel())[:dev.numel()]
             host.copy_(dev, non_blocking=True)
@@ -275,15 +309,42 @@ class SuperResolver:
         os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
         wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), channels, encoding)
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None):
+    @staticmethod
+    def _check_picture_channel(spec, channels, available):
+        """ValueError where the spectrogram option asks for a channel that is not among the written ones."""
+        if spec is None:
+            return
+        k = select_channels(channels, available)
+        if spec['channel'] >= k:
+            raise ValueError("spectrogram_channel %d: the file has %d channel%s and channels=%r writes %d"
+                             % (spec['channel'], available, '' if available == 1 else 's', channels, k))
+
+    @staticmethod
+    def _render_picture(spec, lr, sr, hr):
+        """The device work of the spectrogram option: channel spec['channel'] of the clips a file leaves, one panel each."""
+        rows = torch.stack([t[spec['channel']] for t in (lr, sr, hr) if t is not None])
+        image, db, top = _spectrogram(rows, spec['top_db'], spec['plan'])
+        return {'image': image, 'top': top, 'panels': db.shape[0], 'frames': db.shape[1], 'bins': db.shape[2]}
+
+    @staticmethod
+    def _save_picture(spec, picture):
+        """The fetched picture -> the PNG -> the result's 'spectrogram'."""
+        from ..util import util as U
+        os.makedirs(os.path.dirname(os.path.abspath(spec['path'])), exist_ok=True)
+        U.save_image(picture['image'].numpy(), spec['path'])
+        return {'path': spec['path'], 'panels': picture['panels'], 'frames': picture['frames'], 'bins': picture['bins'],
+                'top_db': float(picture['top'][0]), 'range_db': spec['plan']['range_db']}
+
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
-        7-tuple per written channel, or None."""
+        7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
         host, meta, slot = read
         check_encoding(encoding, "enhance_file")
         k = select_channels(channels, meta.num_channels)
+        self._check_picture_channel(spec, channels, meta.num_channels)
         rate = meta.sample_rate
         raw = self._decode(host, meta, slot)[:k]
         lr = audio_dataset.lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
@@ -299,9 +360,12 @@ class SuperResolver:
         elif has_hr:
             metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
         output = None
-        if path_out is not None or stage is not None:
-            output = self._write(path_out, sr, encoding, stage)
+        picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
+        if path_out is not None or stage is not None or picture is not None:
+            output = self._write(path_out, sr, encoding, stage) if picture is None else self._write(path_out, sr, encoding, stage, picture)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+        if picture is not None:
+            res['spectrogram'] = self._save_picture(spec, picture)
         if extended_metrics:
             res['metrics_ext'] = ext
         if stage is not None:
@@ -309,7 +373,8 @@ class SuperResolver:
         return res
 
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
-                     clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
+                     clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
+                     spectrogram_channel=0, spectrogram_opts=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -327,14 +392,39 @@ class SuperResolver:
         written).  `dither`: None or 'tpdf' (pcm16 only: +-1 LSB of triangular noise in front of the rounding, fixed by
         `dither_seed`).  `report_peaks`: measure only.  With any of the five given the result gains 'output': {'peak',
         'peak_dbfs', 'clipped', 'nonfinite' (a list each, one entry per written channel, measured on the unscaled clip for
-        `encoding`), 'gain' (the factor applied: 1.0 unless 'guard' scaled)}."""
+        `encoding`), 'gain' (the factor applied: 1.0 unless 'guard' scaled)}.
+        `spectrogram` (opt-in): path of a PNG to write after the wav -- spectrogram_image of written channel
+        `spectrogram_channel`: the input the generator was given ('lr'), the generated clip ('sr', what is encoded into the wav)
+        and, where the result has one, the original ('hr'), top to bottom on one time, frequency and dB scale.
+        `spectrogram_opts`: None or a dict of n_fft, hop, width, height, range_db, gap, top_db (plans.check_spectrogram).  The
+        picture is rendered on the device (two launches, family "specimg") and comes back with the payload behind the same
+        synchronisation.  The result gains 'spectrogram': {'path', 'panels', 'frames', 'bins', 'top_db' (the level of the
+        palette's last colour), 'range_db'}.  A channel that is not among the written ones is a ValueError, before anything is
+        enhanced or written."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
-        res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage)
+        spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
+        res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
 
+    @staticmethod
+    def _spectrogram_spec(path, channel, opts, who):
+        """Validates the spectrogram option -> None (off), or {'path', 'channel', 'top_db', 'plan'}."""
+        if path is None:
+            if channel != 0 or opts is not None:
+                raise ValueError("%s: spectrogram_channel / spectrogram_opts are options of spectrogram=PATH; spectrogram is None" % who)
+            return None
+        opts = dict(opts or {})
+        top_db = opts.pop('top_db', None)
+        unknown = sorted(set(opts) - {'n_fft', 'hop', 'width', 'height', 'range_db', 'gap'})
+        if unknown:
+            raise ValueError("%s: unknown spectrogram_opts %s" % (who, unknown))
+        return {'path': os.fspath(path), 'channel': channel, 'top_db': top_db,
+                'plan': check_spectrogram(top_db=top_db, channel=channel, who=who, **opts)}
+
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
-                       extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False):
+                       extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
+                       spectrogram=None, spectrogram_channel=0, spectrogram_opts=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -344,8 +434,12 @@ class SuperResolver:
         'metrics_ext' (as enhance_file returns it).  `clip`, `ceiling_dbfs`, `dither`, `dither_seed`, `report_peaks`: the output
         stage of enhance_file, per file (a guard gain is one file's); file k of the plan is dithered with seed `dither_seed` + k;
         with any of them given a record gains 'output' (as enhance_file returns it, None for a skipped file).  clip 'error'
-        ends the run at the first file that would clip."""
+        ends the run at the first file that would clip.  `spectrogram`: a folder that takes one picture per enhanced file, at
+        <relative path>.png (enhance_file's `spectrogram`, `spectrogram_channel`, `spectrogram_opts`); a record then gains
+        'spectrogram' (as enhance_file returns it; None for a skipped file).  A file without channel `spectrogram_channel` is
+        reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
+        spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
@@ -354,15 +448,19 @@ class SuperResolver:
                 rec['metrics_ext'] = None
             if stage is not None:
                 rec['output'] = None
+            if spec is not None:
+                rec['spectrogram'] = None
             try:
                 read = self._read(path_in)
+                self._check_picture_channel(spec, channels, read[1].num_channels)
             except (ValueError, OSError, EOFError, struct.error) as e:
                 rec['error'] = '%s: %s' % (type(e).__name__, e)
             else:
                 if seed is not None:
                     torch.manual_seed(int(seed))
                 res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics,
-                                            None if stage is None else dict(stage, seed=dither_seed + k))
+                                            None if stage is None else dict(stage, seed=dither_seed + k),
+                                            None if spec is None else dict(spec, path=os.path.join(spec['path'], rel + '.png')))
                 meta = res['info']
                 rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
                            written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
@@ -371,6 +469,8 @@ class SuperResolver:
                     rec['metrics_ext'] = res['metrics_ext']
                 if stage is not None:
                     rec['output'] = res['output']
+                if spec is not None:
+                    rec['spectrogram'] = res['spectrogram']
             records.append(rec)
             if report is not None:
                 report(rec)

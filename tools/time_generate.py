@@ -22,6 +22,12 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             output against the full-band original, and the energy of the two outputs' difference below the transition band and
             above the low rate's Nyquist frequency; log in --crossover_log
 
+  spectrogram (only when asked for) generate.SuperResolver.enhance_file on one 15 s mono PCM16 clip with a full-band original, file to
+            file, without and with spectrogram=PATH (the default plan: three panels of 1600 x 512) in one process, the runs
+            interleaved: milliseconds per file, median and spread of --reps, and how the option's share splits into the two
+            kernels (timed alone, by events) and the rest (the copy back and the PNG encoder on the host); log in
+            --spectrogram_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -29,6 +35,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py folder [--files 8] [--folder_log profiles/time_generate_folder.log]
         python tools/time_generate.py lowband [--lowband_log profiles/time_generate_lowband.log]
         python tools/time_generate.py crossover [--crossover_log profiles/time_generate_crossover.log]
+        python tools/time_generate.py spectrogram [--spectrogram_log profiles/time_generate_spectrogram.log]
 """
 import argparse
 import os
@@ -180,6 +187,83 @@ def run_crossover(seconds, reps, log):
     _run_variants(seconds, reps, log, "crossover", [("crossover off         ", dict()), ("crossover input       ", dict(crossover='input'))])
 
 
+def _median(v):
+    v = sorted(v)
+    return 0.5 * (v[(len(v) - 1) // 2] + v[len(v) // 2])
+
+
+def run_spectrogram(seconds, reps, log):
+    """enhance_file, file to file, without and with the spectrogram picture: the same object, the same input, interleaved."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SPECTROGRAM_DEFAULTS, SuperResolver, spectrogram_rgb, stft_db
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x.cpu() + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float()[None]      # as the low-band run's original
+    sr = SuperResolver(model, opt, overlap=0.25)
+    d = SPECTROGRAM_DEFAULTS
+    lines = ["# tools/time_generate.py spectrogram: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz with a full-band original, file to file, untrained weights, %d interleaved repeats; "
+             "picture: 3 panels of %d x %d, STFT %d / %d" % (seconds, reps, d['width'], d['height'], d['n_fft'], d['hop'])]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out, png = (os.path.join(tmp, f) for f in ("in.wav", "out.wav", "out.png"))
+        wavio.save(src, hr, int(opt.hr_sampling_rate))
+        variants = (("spectrogram off", {}), ("spectrogram on ", dict(spectrogram=png)))
+        for _, kw in variants:                                     # warm-up: capture, tables, pinned buffers, page cache
+            res = sr.enhance_file(src, out, **kw)
+            sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in variants]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(variants):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(variants, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        lines.append("the option costs %.3f ms per file (difference of the medians), %.2f %% of the file without it"
+                     % (_median(ts[1]) - _median(ts[0]), 100.0 * (_median(ts[1]) - _median(ts[0])) / _median(ts[0])))
+        # the two kernels alone, by events, on the clips of the last run
+        rows = torch.stack([res['lr'][0], res['sr'][0], res['hr'][0]])
+        db = stft_db(rows, d['n_fft'], d['hop'])
+        top = db.amax().reshape(1)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        k_stft, k_render = [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            db = stft_db(rows, d['n_fft'], d['hop'])
+            ev[1].record()
+            img = spectrogram_rgb(db, top, d['range_db'], d['width'], d['height'], d['gap'])
+            ev[2].record()
+            torch.cuda.synchronize()
+            k_stft.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_render.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        plane, pixels = db.numel() * 4, img.numel()
+        lines.append("kernels alone (events, median of %d): stft_db %.1f us (%d frames x %d bins x 3 rows: %.1f MB written, %.0f GB/s), "
+                     "render %.1f us (%.1f MB read, %.1f MB of pixels)"
+                     % (reps, _median(k_stft[2:]), db.shape[1], db.shape[2], plane / 1e6, plane / (_median(k_stft[2:]) * 1e-6) / 1e9,
+                        _median(k_render[2:]), plane / 1e6, pixels / 1e6))
+        from pix2pixhdaudiosr_amd.util import util as U
+        host = img.cpu().numpy()
+        enc = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            U.save_image(host, png)
+            enc.append((time.perf_counter() - t0) * 1e3)
+        lines.append("util.save_image of the %d x %d picture on the host: %.3f ms (median of 3), %d bytes of PNG"
+                     % (host.shape[1], host.shape[0], _median(enc), os.path.getsize(png)))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def _run_variants(seconds, reps, log, mode, variants):
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
@@ -267,11 +351,12 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
     ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
+    ap.add_argument("--spectrogram_log", default=os.path.join(ROOT, "profiles", "time_generate_spectrogram.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
@@ -282,6 +367,8 @@ def main():
         return run_lowband(a.seconds, a.reps, a.lowband_log)
     if a.mode == "crossover":
         return run_crossover(a.seconds, a.reps, a.crossover_log)
+    if a.mode == "spectrogram":
+        return run_spectrogram(a.seconds, a.reps, a.spectrogram_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
