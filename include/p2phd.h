@@ -187,7 +187,7 @@ int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* 
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Whole-file generation (pix2pixhdaudiosr_amd/generate.py), csrc/stitch.hip.  Launch family "stitch".
+ * Whole-file generation (pix2pixhdaudiosr_amd/generate/), csrc/stitch.hip.  Launch family "stitch".
  *
  * p2phd_segments_gather: audio [L] f32 -> out [S, T] f32, out[s,i] = audio[s * stride + i], zero beyond L.  1 <= stride <= T;
  *   stride = T is seg_pad_audio of the reference (data/audio_dataset.py:124-135).

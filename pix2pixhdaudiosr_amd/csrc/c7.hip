@@ -14,12 +14,9 @@
 //   InstanceNorm statistics: every lane keeps shifted sums of its channels over the tile, merged across lanes with
 //     Chan's update once per wave, stored as this wave's slot of the same partial table the generic conv uses.
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
-
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int TH = 8, TW = 128;            // output tile
 constexpr int LROWS = TH + 7;              // input rows held (3 above, 3 below, 1 for the zero-weight tap row 7)
@@ -33,12 +30,6 @@ constexpr int srow_bytes(int nb) { return nb == 4 ? 176 : nb * 32 + 16; }
 // wavefront-scope fence: that lowers to s_waitcnt vmcnt(0) as well, i.e. it waits for every global load and store in
 // flight -- the row prefetch of c7_out_fwd and the output stores of c7_in_fwd ran at one memory round trip per step.
 __device__ __forceinline__ void lds_wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * (n - 1) - i;
-  return i;
-}
 
 // Weights in fragment order: wf[((half * NB + nb) * 4 + s) * 64 + lane] = 8 bf16:
 //   A[row = l & 15][k = 32 s + 8 (l >> 4) + j],  k = dw * 16 + dh * 2 + c,  value w[16 (half * NB + nb) + row][c][dh][dw]

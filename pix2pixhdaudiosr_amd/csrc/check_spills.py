@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Fail the build when a gconv / wgrad kernel of conv.hip uses scratch (see the Makefile rule for conv.o).  Further arguments
-name other kernels to hold to the same rule: substrings of their (mangled) names, as for metrics.o."""
+"""Fail the build when a kernel that must not spill uses scratch: check_spills.py REMARKS KERNEL...  REMARKS holds the compiler's
+-Rpass-analysis=kernel-resource-usage output of one object, each KERNEL is a substring of the (mangled) names meant; the Makefile's
+table says which files and kernels are held to the rule (gconv.hip and wgrad.hip for their hand-counted waits)."""
 import re
 import sys
 
+if len(sys.argv) < 3:
+    print("usage: check_spills.py REMARKS KERNEL...", file=sys.stderr)
+    sys.exit(2)
 text = open(sys.argv[1]).read()
-wanted = sys.argv[2:] or ["gconv_kernel", "gconv_pkernel", "wgrad_kernel"]
+wanted = sys.argv[2:]
 bad, seen = [], 0
 for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", text, re.S):
     name, scratch = m.group(1), int(m.group(2))
@@ -22,4 +26,4 @@ if bad or not seen:
     if not seen:
         print("check_spills: no %s kernel found in the resource remarks" % "/".join(wanted), file=sys.stderr)
     sys.exit(1)
-print(f"check_spills: {seen} {'MFMA' if len(sys.argv) < 3 else '/'.join(wanted)} kernels, no scratch")
+print(f"check_spills: {seen} {'/'.join(wanted)} kernels, no scratch")

@@ -1,5 +1,5 @@
 // C ABI of the convolution family: turns a reference-level layer description (Conv2d / ConvTranspose2d with
-// stride, padding and an optional ReflectionPad2d in front) into gather-convolution launches (conv.hip), using the
+// stride, padding and an optional ReflectionPad2d in front) into gather-convolution launches (gconv.hip), using the
 // W-fold forms (wfold.hip) for layers with <= 4 input or output channels.
 #include "convplan.h"
 #include <vector>

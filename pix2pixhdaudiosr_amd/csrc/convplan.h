@@ -1,4 +1,4 @@
-// Internal descriptor of one gather-convolution launch and the launchers implemented in conv.hip.
+// Internal descriptor of one gather-convolution launch and the launchers implemented in gconv.hip, wgrad.hip, wpack.hip and convaux.hip.
 #pragma once
 #include "common.h"
 #include <algorithm>
@@ -70,7 +70,7 @@ int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, in
 
 // launch counters (p2phd_launch_count): which kernel family a call really took -- tests assert that the benchmarked step runs
 // on the round-3..5 kernels and not on the generic loop behind them.  The dedicated routes (march, march_w, dfirst, dlast, c7,
-// thin_wgrad) are counted where convapi.hip picks them, the tile-level families (gconv .. tile128x192) inside conv.hip, where
+// thin_wgrad) are counted where convapi.hip picks them, the tile-level families (gconv .. tile128x192) inside gconv.hip, where
 // launch_gconv_cfg runs the tile gconv_choose_tile picked; p2phd_conv_gconv_tiles (convapi.hip) answers on the host which tile
 // that is -- every instantiation, also those without a family of their own (256 x 128 with the HALO loop)
 enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192,
@@ -180,6 +180,9 @@ int launch_stats_merge(const float* table, float* stats, int N, int slots, int n
 size_t wgrad_workspace_floats(const GDesc& d, int dtype, int M_rows, int M_rows_pad);
 int launch_wgrad(const GDesc& d, const WMap& m, int dtype, const void* rows, int Cp_r, int M_rows, int M_rows_pad,
                  const void* gat, float* dwp, float* dw, int accumulate, hipStream_t st);
+// wpack.hip, called by launch_wgrad: the `splits` packed slabs of dwp (slab_elems floats apart) summed into the master layout
+void launch_unpack_grad(const GDesc& d, const WMap& m, const float* dwp, float* dw, int splits, long slab_elems, int accumulate,
+                        hipStream_t st);
 int launch_pack_merged(const GDesc& d, int dtype, const float* w, void* wp, int rows_pad, int K, int C, int R, int S, int pad,
                        long s_k, long s_c, hipStream_t st);
 int launch_pack(const GDesc& d, const WMap& m, int dtype, const float* w, void* wp, int rows_pad, hipStream_t st);

@@ -14,15 +14,11 @@
 //     and leaves as two 16-byte pieces per lane: 1 KB of contiguous NHWC per store instruction;
 //   * the next block's four loads are issued before the current block's MFMAs (12 waves per CU keep ~50 KB in flight).
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
 
 using namespace p2phd;
-
-typedef p2phd_h16 bf16_t;
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned kOOB = 0xFFFFFFF0u;
 constexpr int kStagePitch = 64 * 2 + 16;                       // bytes per staged pixel row (16-byte pad: the 2-byte column writes of 4 pixels spread over banks)

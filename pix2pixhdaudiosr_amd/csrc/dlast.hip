@@ -13,18 +13,14 @@
 //               dyG[pixel][tap] = dy[hi - th + 2][wi - tw + 2] gathered from the one-channel gradient (2.3 MB: cache hits).
 //               The 16 x 128 block is transposed through a 4 KB LDS patch of the wave's own into 16-byte pieces of NHWC rows,
 //               with the skip / parked gradient added (`addend`) and, optionally, the first pass of the PRODUCER's
-//               InstanceNorm backward riding on the stores (conv.hip's fused store loop: p2phd_conv_dgrad_bsum) -- a lane keeps
+//               InstanceNorm backward riding on the stores (gconv.hip's fused store loop: p2phd_conv_dgrad_bsum) -- a lane keeps
 //               one 8-channel column for all its rows, so the sums stay in registers for the wave's whole run of pixels.
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
 
 using namespace p2phd;
-
-typedef p2phd_h16 bf16_t;
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned kOOB = 0xFFFFFFF0u;
 constexpr int kMaxKS = 16;                                    // forward: C / 32 k-steps, at most 512 channels (64 weight registers)

@@ -5,15 +5,9 @@
 // Losses reduce on the device into a float accumulator (no host sync); their backward kernels read the upstream
 // gradient from device memory too, so the whole step can be enqueued without the host waiting on a value.
 #include "common.h"
+#include "convdev.h"
 
 namespace {
-
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(bf16_t v) { return (float)v; }
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return (bf16_t)v; }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -24,10 +18,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   __syncthreads();
   return t;   // valid in thread 0
 }
-
-template <typename T> struct Elem;
-template <> struct Elem<float> { static constexpr int EPP = 4; };
-template <> struct Elem<bf16_t> { static constexpr int EPP = 8; };
 
 // kind 0: (a - target)^2 ; kind 1: |a - b|.  a,b are [P][Cp] with C valid channels.  out += coeff * sum / (P*C)
 // 16-byte pieces, two in flight per thread; pad channels are masked

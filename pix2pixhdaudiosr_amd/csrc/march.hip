@@ -19,18 +19,14 @@
 //     kernel waits for HBM.  DESIGN.md section 6, round 5);
 //   * InstanceNorm partials: every lane keeps running (count, mean, M2) of its channel over the whole march (Chan's
 //     update per step), merged across the four lanes of a channel at the end: one table slot per wave and launch, no atomics;
-//   * input-gradient launches can carry the producer's InstanceNorm-backward sums (the fused form of conv.hip's store
+//   * input-gradient launches can carry the producer's InstanceNorm-backward sums (the fused form of gconv.hip's store
 //     loop): the storing thread owns one 8-channel column for the whole march, so the sums stay in registers.
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
 
 using namespace p2phd;
-
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int kThreads = 768, kWaves = 12;
 constexpr unsigned kOOB = 0xFFFFFFF0u;
@@ -52,7 +48,7 @@ struct MarchArgs {
   int N, Hin, Win, Ho, Wo;
   int strips, nseg, seg_rows, slots;
   unsigned in_bytes;
-  // fused first pass of the PRODUCER's InstanceNorm backward (input-gradient launches; conv.hip GDesc::bs_*)
+  // fused first pass of the PRODUCER's InstanceNorm backward (input-gradient launches; convplan.h GDesc::bs_*)
   const bf16_t* bs_y;     // pre-normalisation output of the producer, shape of `out`
   const float* bs_stats;  // [N][CO][2] (mean, M2)
   float* bs_out;          // [N][strips * nseg][CO][2] or nullptr
@@ -77,7 +73,6 @@ __device__ __forceinline__ void lazy_table_fill(float* tab, const float* stats, 
 // kept short: bf16 -> f32 is a shift / mask on the packed dword, subtraction and multiplication go out as packed f32 pairs
 // (v_pk_add_f32 / v_pk_mul_f32: same roundings as the scalar forms), ReLU is one max, the padding mask is applied to the four
 // result dwords.  Table: [C][2] = (mean, rstd) interleaved, i.e. one float4 = two channels.
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ u32x4 lazy_norm8(u32x4 raw, const float* tab, int c0, float slope, bool ok) {
   u32x4 o;
 #pragma unroll
@@ -705,7 +700,6 @@ struct WGeom {
   static_assert(ROW48 % 16 == 0 && ROW96 % 16 == 0 && WS * 12 == kThreads, "march(W): geometry");
 };
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 __device__ __forceinline__ bf16x8 tr_pair(const char* p0, const char* p1) {
   typedef __attribute__((address_space(3))) s16x4* lp;
   bf16x8 v;

@@ -6,21 +6,13 @@
 // Reference semantics: models/networks.py:22 (InstanceNorm2d, eps 1e-5, biased variance, no affine, no running
 // stats), :188,233 (ReLU), :342-358 (LeakyReLU 0.2), :165,308 (AvgPool2d), :252 (residual add).
 #include "common.h"
+#include "convdev.h"
 namespace p2phd { extern int g_opt_wgrad_xcd; }   // 1 (default): XCD-aware workgroup order (core.hip)
 
 namespace {
 
 using p2phd::fold_store;
 using p2phd::fold_load;
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-template <typename T> struct Elem;
-template <> struct Elem<float> { static constexpr int EPP = 4; };
-template <> struct Elem<bf16_t> { static constexpr int EPP = 8; };
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(bf16_t v) { return (float)v; }
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return (bf16_t)v; }
 
 // The activation code is folded into ONE float per kernel (slope applied to negative pre-activations: 0 ReLU, 0.2
 // LeakyReLU, 1 none), so the per-element work is a compare + select instead of a chain of uniform branches on `act`
@@ -282,7 +274,7 @@ __global__ __launch_bounds__(256) void in_act_bwd_fused_kernel(const T* __restri
   // 1-D launch of cblocks x N workgroups.  A workgroup reads 16 * CGN bytes of every pixel -- half a 128-byte line for CGN = 4 --,
   // its neighbour in the channel direction the other half.  Workgroups are dealt round-robin over the 8 XCDs, so with the
   // plain order both halves of every line were fetched by two different L2s; the bijective chunk remap (as in wgrad_kernel,
-  // conv.hip) puts a contiguous run of logical ids on each XCD, neighbours 8 dispatch slots apart.
+  // wgrad.hip) puts a contiguous run of logical ids on each XCD, neighbours 8 dispatch slots apart.
   int bxl, nl;
   {
     const int Wg = (int)gridDim.x;
@@ -370,7 +362,7 @@ __global__ __launch_bounds__(256) void in_act_bwd_fused_kernel(const T* __restri
   }
   if (rx != nullptr) {
     // The conv this gradient belongs to sits behind ReflectionPad2d(1) (the residual trunk): its input-gradient GEMM reads dy
-    // plus the pair-sum rows / columns of the reflection's adjoint (conv.hip, pad_mode 3).  This workgroup has just written
+    // plus the pair-sum rows / columns of the reflection's adjoint (gconv.hip, pad_mode 3).  This workgroup has just written
     // every pixel of its channels of the plane, so it appends them itself -- rx [N][2 (W + 2) + 2 H][Cp]: row H = dy[0] +
     // dy[2], row H + 1 = dy[H-3] + dy[H-1] (W + 2 columns each, the last two being the column sums of those), then columns
     // W = dy[:,0] + dy[:,2] and W + 1 = dy[:,W-3] + dy[:,W-1] for rows < H -- instead of a copy pass over the whole gradient.

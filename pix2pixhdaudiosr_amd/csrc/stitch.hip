@@ -1,4 +1,4 @@
-// Whole-file generation (pix2pixhdaudiosr_amd/generate.py): the two ends of the waveform -> segments -> generator -> segments ->
+// Whole-file generation (pix2pixhdaudiosr_amd/generate/): the two ends of the waveform -> segments -> generator -> segments ->
 // waveform path that are not a transform or a conv.
 //
 //   gather  audio[L] -> seg[S,T], seg[s,i] = audio[s * stride + i], zero beyond L.  stride = T is the reference's

@@ -4,7 +4,7 @@
 //   * Conv2d(4, ndf, 4, stride 2, padding 2)        (:343, discriminator input) thin = x,  wide = dy
 // dW[wide ch][tap][thin ch] = sum over pixels q of wide[q][ch] * thin[q * stride + tap - pad][c]: a GEMM with M = wide
 // channels, N = taps x thin channels (98 / 64 columns), reduction over 0.5-4 M pixels, 39 GFLOP and 0.47 GB per launch:
-// HBM-bound.  The generic panel kernel (conv.hip) reached these layers through a materialised W-fold image at 1 TB/s.
+// HBM-bound.  The generic panel kernel (wgrad.hip) reached these layers through a materialised W-fold image at 1 TB/s.
 //
 // Here a workgroup marches over tiles of 8 grid rows: the thin tensor's halo of the tile is read once into LDS in
 // compact form; per step of 64 pixels (one row segment) the wide rows are copied global -> LDS (full 16-byte pieces, the
@@ -13,12 +13,9 @@
 // index = LDS row), exactly the fragment scheme of wgrad_kernel.  Accumulators stay in registers over the whole march;
 // every workgroup writes one [M][N] slab, a second kernel adds the slabs in a fixed order into the master layout.
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
-
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int RT = 8;                      // grid rows per tile
 constexpr int SEG = 64;                    // pixels per step
@@ -32,12 +29,6 @@ struct ThinDesc {
   int stride, pad, thin_reflect; // thin position = grid * stride + tap - pad; reflect or zero outside
   int M;                         // wide channels (<= 128)
 };
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * (n - 1) - i;
-  return i;
-}
 
 // byte offset of element (row, col) inside a panel image [64 rows][128 B] whose 16-byte chunks are XOR-swizzled for the
 // transposing reads (rows 2,3 mod 4 use the other half of the row; see wgrad_kernel)

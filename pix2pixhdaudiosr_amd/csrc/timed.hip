@@ -16,6 +16,7 @@
 // accesses off one bank).  All three kernels are streaming kernels: one pass over their operands, no reuse to exploit.
 #include "common.h"
 #include "convplan.h"
+#include "convdev.h"
 #include "fft_wave.h"
 #include <algorithm>
 #include <cmath>
@@ -24,7 +25,6 @@
 namespace {
 using namespace p2phd_fft;
 
-typedef p2phd_h16 bf16_t;
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
 

@@ -10,21 +10,9 @@
 //   and for the backward of an output-folded layer dyE[n,h,w',(tw,k)] = dy[n,h,w'-tw,k].
 // These three kernels are the cheap HBM-bound data movers around the GEMMs; tensors are NHWC with pitch 8.
 #include "convplan.h"
+#include "convdev.h"
 
 namespace {
-
-typedef p2phd_h16 bf16_t;                 // the library's 16-bit storage type: bf16, or fp16 in the -DP2PHD_F16 build (common.h)
-__device__ __forceinline__ float to_f(float v) { return v; }
-__device__ __forceinline__ float to_f(bf16_t v) { return (float)v; }
-template <typename T> __device__ __forceinline__ T from_f(float v);
-template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
-template <> __device__ __forceinline__ bf16_t from_f<bf16_t>(float v) { return (bf16_t)v; }
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * (n - 1) - i;
-  return i;
-}
 
 // Xe[n,h,wo,(tw*C + c)] = x[n,h,map(wo + tw - pad),c]   (map = reflect or zero), wo in [0,Wo)
 // One thread per 16-byte output piece; its elements are gathered into registers with compile-time indices (a per-pixel

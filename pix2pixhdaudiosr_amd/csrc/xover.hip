@@ -1,4 +1,4 @@
-// Whole-file generation (pix2pixhdaudiosr_amd/generate.py): the time-domain crossover behind the stitch.  Below the crossover
+// Whole-file generation (pix2pixhdaudiosr_amd/generate/): the time-domain crossover behind the stitch.  Below the crossover
 // frequency the written clip is the input, above it the generator's output:
 //
 //   out = sr + LP * (level * lr - sr)          LP: a centred (zero-delay) windowed-sinc low-pass of `taps` coefficients

@@ -7,7 +7,7 @@ reference (``model.1.weight``, ``scale0_layer0.0.weight`` ...) and torch optimis
 they see on the reference.  ``forward`` never calls those layers: at first use each ``nn.Sequential`` is
 compiled into fused steps  [ReflectionPad2d] -> Conv2d/ConvTranspose2d -> [InstanceNorm2d] -> [ReLU |
 LeakyReLU | Tanh] (-> [+ residual]), each of which is one implicit-GEMM MFMA launch plus at most one
-HBM-bound normalisation launch of libp2phd_hip.so (see _ops.py, csrc/conv.hip, csrc/norm.hip).
+HBM-bound normalisation launch of libp2phd_hip.so (see _ops.py, csrc/gconv.hip, csrc/wgrad.hip, csrc/norm.hip).
 
 Not implemented on this path (raise instead of falling back): BatchNorm ('--norm batch'), Dropout in
 ResnetBlock, the deprecated Encoder / Vgg19 / VGGLoss leftovers of upstream pix2pixHD.

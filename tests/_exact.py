@@ -72,7 +72,7 @@ HALO_DGRAD = [                                                          # input 
 ]
 TILE128X192_FWD = L("t128x192_192to1536", 192, 1536, 3, 1, 1, 1, 0, 0, (32, 16, 8))
 # (input gradient: a 128-pixel plane reaches this tile only with per-sample tiles, i.e. with the fused InstanceNorm-backward sums,
-# which zero-padded layers have: conv.hip gconv_choose_tile, `flat_m`)
+# which zero-padded layers have: gconv.hip gconv_choose_tile, `flat_m`)
 TILE128X192_DGRAD = L("t128x192_1152to64", 1152, 64, 3, 1, 1, 0, 0, 0, (32, 16, 8))
 SPLITK = [
     L("c3_64to96", 64, 96, 3, 1, 1, 1, 0, 0, (3, 40, 28)),
@@ -485,7 +485,7 @@ def stats_reference(y):
     return mean, dev2.sum((2, 3)), sum_bound(y.abs().sum((2, 3)) / P, P), sum_bound(dev2.sum((2, 3)), P)
 
 
-# yhat of the fused InstanceNorm-backward sums (csrc/conv.hip, store loop with GDesc::bs_out; the same formula in
+# yhat of the fused InstanceNorm-backward sums (csrc/gconv.hip, store loop with GDesc::bs_out; the same formula in
 # csrc/march.hip and csrc/dlast.hip): rstd = rsqrtf(fmaxf(M2 * inv_hw, 0) + eps), yh = (y - mean) * rstd.  With integer y and
 # mean, y - mean is exact.  inv_hw = 1.f / (H * W): one rounding; M2 * inv_hw: one; + eps: one -> the argument is within 3 u,
 # its inverse square root within 1.5 u; rsqrtf itself: 1 ulp = 2 u (HIP math API); the product with y - mean: one more.
@@ -505,7 +505,7 @@ def bsum_reference(dx, prev_y, mean, m2, eps, slope):
 
 
 def act_bwd_reference(g, x_act, slope, dtype):
-    """p2phd_conv_dgrad_act's store (csrc/conv.hip, store loop, `if (act_only)`):
+    """p2phd_conv_dgrad_act's store (csrc/gconv.hip, store loop, `if (act_only)`):
     vv[e] = from_f<TO>(to_f(vv[e]) * (to_f(yy[e]) > 0.f ? 1.f : slope_b)) -- the stored (exact) gradient times 1 or the fp32
     slope, rounded once to fp32 by the multiplication and once to the storage type."""
     s = torch.where(x_act > 0, torch.ones((), dtype=torch.float32), torch.tensor(slope, dtype=torch.float32))
@@ -513,7 +513,7 @@ def act_bwd_reference(g, x_act, slope, dtype):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# reflection extras (csrc/norm.hip, in_act_bwd_fused_kernel `if (rx != nullptr)`; read by the pad_mode 3 gather of conv.hip)
+# reflection extras (csrc/norm.hip, in_act_bwd_fused_kernel `if (rx != nullptr)`; read by the pad_mode 3 gather of gconv.hip)
 # ----------------------------------------------------------------------------------------------------------------------
 def reflect_extras(dy):
     """Extras block of dy [N, H, W, Cp] (any float dtype, host) in float64: [N][2 (W + 2) + 2 H][Cp] --
@@ -529,7 +529,7 @@ def reflect_extras(dy):
 
 
 def reflect_dgrad_from_extras(l, dy_nhwc, extras, w):
-    """The input gradient as the pad_mode 3 gather forms it (csrc/conv.hip gather table): a zero-padded transposed 3x3 conv of dy
+    """The input gradient as the pad_mode 3 gather forms it (csrc/gconv.hip gather table): a zero-padded transposed 3x3 conv of dy
     in which output row 1's tap onto row 2 reads virtual row H instead, output row H-2's tap onto row H-3 virtual row H + 1
     (columns likewise).  Host model, float64; used by the CPU test to pin the builder to the autograd reference."""
     N, H, W = l.shape

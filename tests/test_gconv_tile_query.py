@@ -1,5 +1,5 @@
 """The gather-GEMM's tile choice is pinned on the host: p2phd_conv_gconv_tiles (csrc/convapi.hip) says, without a GPU, which
-tile gconv_choose_tile (csrc/conv.hip) gives every generic launch of a layer.  Corpus: that of tests/test_conv_queries.py (the
+tile gconv_choose_tile (csrc/gconv.hip) gives every generic launch of a layer.  Corpus: that of tests/test_conv_queries.py (the
 bench layers of cfg2 / cfg3 / cfg5 at N = 1, 2, 8, 32 and the dedicated-kernel shapes, f32 and the 16-bit type, w_layout 1 where
 allowed) plus the layers of EXTRA, in every launch form and flag combination, on both libraries, under the default options and
 with each tile option set on its own.
@@ -42,7 +42,7 @@ MAX_LAUNCHES = 8
 EXTRA = [(27, (768, 32, 16, 768, 3, 3, 1, 1, 1, 0, 0)), (32, (192, 16, 8, 1536, 3, 3, 1, 1, 1, 0, 0)),
          (32, (1152, 16, 8, 64, 3, 3, 1, 1, 0, 0, 0)), (2, (128, 16, 16, 24, 3, 3, 1, 1, 1, 0, 0))]
 
-# the dispatch tables of csrc/conv.hip (kTilesF32 / kTilesFp8 / kTiles16): (bm, bn, mr, nr, nstage, halo)
+# the dispatch tables of csrc/gconv.hip (kTilesF32 / kTilesFp8 / kTiles16): (bm, bn, mr, nr, nstage, halo)
 EVERY_TYPE = [(128, 128, 2, 2, 2, 0), (128, 64, 2, 1, 2, 0), (128, 32, 1, 1, 2, 0),
               (256, 128, 2, 2, 3, 0), (256, 128, 2, 2, 2, 0), (256, 64, 2, 1, 3, 0), (256, 64, 2, 1, 2, 0)]
 TABLE = {"f32": EVERY_TYPE,

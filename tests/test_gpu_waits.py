@@ -3,7 +3,7 @@ pipelines, and a wrong one (a wave whose youngest load was not the piece the cou
 run in four.  `libp2phd_hip_chk.so` is the library built with -DP2PHD_CHECK_WAITS: every wave logs which LDS buffer each piece it
 issues fills and, at EVERY relaxed wait in front of a slab barrier -- the generic gather-GEMM loop on its 2- and 3-slot rings, the
 HALO loop, the weight-gradient loops (bf16 and f32) --, checks that none of the n pieces the wait leaves in flight targets a
-buffer read behind that barrier (csrc/conv.hip, P2PHD_CW_*).  ONE pass over the layer shapes, no repetition: the check is on the
+buffer read behind that barrier (csrc/gconv.hip and wgrad.hip, P2PHD_CW_* of waitcheck.h).  ONE pass over the layer shapes, no repetition: the check is on the
 issue order, which is deterministic, not on timing.  Sensitivity: the same build run with round 4's too-lax HALO wait
 (p2phd_set_option("cw_inject", 1)) must raise the flag."""
 import json
@@ -42,6 +42,7 @@ WORKER = textwrap.dedent('''
         assert torch.isfinite(gx).all() and torch.isfinite(gw).all()
 
     read()
+    assert read(0) == [0, 0, 0, 0]      # the reset cleared the flag of both code objects (gconv.hip, wgrad.hip)
     bf, f32 = torch.bfloat16, torch.float32
     names = ("gconv", "halo", "cls_skip", "wgrad", "tile256", "splitk")
     L.p2phd_launch_count(None, 1)
