@@ -86,7 +86,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * discriminator's pair pack and spectrogram <-> frames kernels, csrc/timed.hip), "stitch" (the segment gather and the
  * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
  * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
- * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip).
+ * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip), "loudness" (the
+ * BS.1770 hop energies and the gate of whole-file generation, csrc/loudness.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -330,6 +331,44 @@ size_t p2phd_specimg_image_bytes(int64_t R, int W, int H, int gap);
 int p2phd_stft_db(const float* x, int64_t ld, int64_t R, int64_t L, int n_fft, int hop, const float* tables, float* db, void* stream);
 int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const float* top_dev, float range, const uint8_t* lut_dev, int W,
                          int H, int gap, uint8_t* img, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Loudness of whole-file generation after ITU-R BS.1770-4 / EBU R 128, csrc/loudness.hip.  Launch family "loudness" (a
+ * p2phd_loudness_hops that launches and every p2phd_loudness_gate count 1 each: 2 per measured clip).
+ *
+ * p2phd_loudness_coeffs_fill (HOST only, no device, as p2phd_xover_taps_fill): the K-weighting filter pair for `rate`, float64:
+ *   out10 = b0 b1 b2 a1 a2 of the high shelf, then of the high-pass; y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2].
+ *   Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / rate), Vh = 10^(G / 20),
+ *   Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0,
+ *   b2 = (Vh - Vb K / Q + K^2) / a0, a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0.  High-pass: f0 = 38.13547087602444,
+ *   Q = 0.5003270373238773, the same K and a0 forms, b = (1, -2, 1), a1 and a2 as above.  At 48000 these are the coefficients
+ *   printed in BS.1770 to 9e-16.  `rate` must be a multiple of 10 in [8000, 384000] (a hop is rate / 10 samples), else P2PHD_EINVAL.
+ * p2phd_loudness_hops: planar [channels][ld] f32 rows of `frames` samples (layout and argument checks of p2phd_pcm_encode; rows
+ *   may start at any float) -> z [channels][J] float64 on the device, hop = rate / 10, J = frames / hop (integer division; the
+ *   samples behind J hop are not counted): z[c][j] = sum over the samples of hop j of y^2, y = row c through the shelf and then the
+ *   high-pass from zero state at sample 0.  State and sums are float64, the samples are read as fp32.  Parallel by zero-state
+ *   warm-up: hop j is computed from zero state at sample max(0, (j - 2) hop), 200 ms in front of it, and counts its own samples
+ *   only -- hops 0 .. 2 are the sequential recursion, later ones lack a state response that has decayed by the high-pass's double
+ *   pole over 200 ms (about 1e-17 of the state at any rate; below the float64 rounding of the recursion, 2^-53 / (1 - r)^2 = 4e-12).
+ *   So a NaN or infinite sample reaches its own hop and the two behind it, not the rest of the clip.  Every z[c][j] is written by
+ *   every call (nothing is zeroed before), by one work item in a fixed order: the same bits on every run, and row c of a
+ *   C-row call holds the bits of the 1-row call on that row.  J = 0: P2PHD_OK, nothing launched.  No atomics, no workspace.
+ * p2phd_loudness_gate: z [channels][J] (device) -> res4 (4 float64, device) and gain (1 f32, device), one workgroup, fixed-order
+ *   float64 sums; always launches.  weights: HOST pointer to `channels` f32 (finite, >= 0; NULL: all 1); 1 <= channels <= 64.
+ *     blocks   NB = max(J - 3, 0); P[c][b] = (((z[c][b] + z[c][b+1]) + z[c][b+2]) + z[c][b+3]) / (4 hop);
+ *              p[b] = sum_c weights[c] P[c][b], c ascending from 0; l[b] = -0.691 + 10 log10(p[b])
+ *     gating   A = {b : l[b] > -70};  Gamma = -0.691 + 10 log10(mean_A p) - 10;  B = {b in A : l[b] > Gamma};
+ *              I = -0.691 + 10 log10(mean_B p).  Both comparisons are evaluated as "not l <= threshold": a block whose level is NaN
+ *              stays in, so a NaN in z makes I NaN instead of being gated out.
+ *     res4     {I, max_b l[b] (fmax from -inf: a NaN never wins), Gamma, |B|}; with NB = 0 or A empty {-inf, -inf or the maximum, -inf, 0}
+ *     gain     T = *target_dev where target_dev != NULL (a device float64, e.g. another clip's res4: no host round trip), else
+ *              `target`; gain[0] = (float) 10^(clamp(T - I, -max_gain_db, +max_gain_db) / 20), float64 arithmetic rounded once;
+ *              gain[0] = 1 where T or I is not finite (target NaN: no target).  max_gain_db finite and >= 0.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_loudness_coeffs_fill(double rate, double* out10);
+int p2phd_loudness_hops(const float* planar, int64_t frames, int channels, int64_t ld, int rate, double* z, void* stream);
+int p2phd_loudness_gate(const double* z, int64_t J, int channels, int rate, const float* weights, double target, const double* target_dev,
+                        double max_gain_db, double* res4, float* gain, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

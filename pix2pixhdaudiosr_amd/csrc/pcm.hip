@@ -277,6 +277,10 @@ int encode_rows(const char* what, const float* planar, int64_t frames, int chann
 
 }  // namespace
 
+int p2phd::pcm_check_rows(const char* what, int64_t frames, int channels, int64_t ld, int format, bool encodable) {
+  return check_rows(what, frames, channels, ld, format, encodable);
+}
+
 extern "C" int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels, int format, float* out, int64_t ld, void* stream) {
   if (const int rc = check_rows("pcm_decode", frames, channels, ld, format, false)) return rc;
   if (frames == 0) return P2PHD_OK;

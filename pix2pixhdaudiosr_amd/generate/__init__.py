@@ -34,13 +34,22 @@ and above it the generator's output.
 `--spectrogram PATH` (opt-in, csrc/specimg.hip) also leaves a picture: the spectrograms of the input the generator was given,
 of the written clip and -- for a full-band input -- of the original, stacked on one time, frequency and dB scale, rendered
 on the device from the clips that are there at the end of enhance_file (`spectrogram_image`, `stft_db`, `spectrogram_rgb`).
+
+`--loudness report|input|LUFS` (opt-in, csrc/loudness.hip) measures the integrated loudness after ITU-R BS.1770-4 / EBU R 128 of
+the input the generator was given and of the generated clip on the device -- the level the pipeline writes depends on the
+checkpoint's rates, the transform and the overlap -- and, with `input` or a target such as -23, multiplies the clip by the one
+gain that brings it there, in front of the output stage (`loudness_hops`, `loudness_gate`, `loudness`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
-from .ops import (PCM_FORMATS, crossover, crossover_coefficients, pcm_decode, pcm_encode, pcm_peaks, segments_gather,  # noqa: F401
-                  segments_gather_planar, segments_stitch, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, LOWBANDS,  # noqa: F401
+from .ops import (PCM_FORMATS, crossover, crossover_coefficients, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
+                  loudness_hops, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
+                  segments_stitch_planar, spectrogram_rgb, stft_db)
+from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
+                    LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, ClipError, ceiling_from_dbfs, check_crossover,
-                    check_dither, check_encoding, check_lowband, check_output_options, check_paths, check_spectrogram, crossover_plan,
-                    crossover_width_hz, encoding_limit, plan_folder, segment_plan, select_channels, spectro_bins, spectrogram_lut)
-from .report import METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_PEAKS, metrics_rows, write_metrics_csv        # noqa: F401
+                    check_dither, check_encoding, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
+                    check_spectrogram, crossover_plan, crossover_width_hz, encoding_limit, loudness_channel_weights, plan_folder,
+                    segment_plan, select_channels, spectro_bins, spectrogram_lut)
+from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS, metrics_rows,  # noqa: F401
+                     write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

@@ -10,9 +10,9 @@ from types import SimpleNamespace
 
 import torch
 
-from .plans import (CLIP_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_lowband, check_output_options, check_paths,
-                    check_spectrogram, spectro_bins)
-from .report import _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .plans import (CLIP_MODES, LOUDNESS_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_loudness, check_lowband,
+                    check_output_options, check_paths, check_spectrogram, spectro_bins)
+from .report import _print_loudness, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -68,6 +68,26 @@ def _size_arg(text):
         return int(w), int(h)
     except ValueError:
         raise argparse.ArgumentTypeError("expected WIDTHxHEIGHT in pixels, such as 1600x512, got %r" % text)
+
+
+def _loudness_arg(text):
+    if text in LOUDNESS_MODES:
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected report, input or a target in LUFS such as -23, got %r" % text)
+
+
+def _loudness_args(a, hr_rate=None):
+    """The loudness options of the command line -> the keyword arguments of enhance_file / enhance_folder ({} without --loudness);
+    ValueError for a bad one.  `hr_rate`: None as long as the options file has not been read (the rate is then checked later)."""
+    if a.loudness is None:
+        if a.loudness_max_gain_db is not None:
+            raise ValueError("--loudness_max_gain_db is an option of --loudness")
+        return {}
+    check_loudness(a.loudness, 48000 if hr_rate is None else hr_rate, "generate", a.loudness_max_gain_db)
+    return dict(loudness=a.loudness, loudness_max_gain_db=a.loudness_max_gain_db)
 
 
 def _spectrogram_args(a, folder_mode):
@@ -158,6 +178,13 @@ def _parser():
                     help="--spectrogram: dB below the top that reach the palette's first colour (default 90)")
     ap.add_argument("--spectrogram_top_db", type=float, default=None, metavar="DB",
                     help="--spectrogram: level of the palette's last colour, 0 = a full-scale sine (default: the picture's own maximum)")
+    ap.add_argument("--loudness", type=_loudness_arg, default=None, metavar="report|input|LUFS",
+                    help="measure the integrated loudness (ITU-R BS.1770-4 / EBU R 128) of the input the generator was given and of "
+                         "the generated clip, and print both per file (report); also scale the written clip to the input's loudness "
+                         "(input) or to a target in LUFS, -70 .. 0, such as -23; three more columns (lufs_in, lufs_out, "
+                         "loudness_gain_db) of --metrics_csv (default: off)")
+    ap.add_argument("--loudness_max_gain_db", type=float, default=None, metavar="DB",
+                    help="--loudness input|LUFS: the largest gain applied, either way (default 40)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -177,6 +204,7 @@ def main(argv=None):
         folder_mode = check_paths(a.input, a.output)
         check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
         picture = _spectrogram_args(a, folder_mode)
+        picture.update(_loudness_args(a))
     except ValueError as e:
         ap.error(str(e))
     stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks, **picture)
@@ -193,6 +221,7 @@ def main(argv=None):
     try:                                                                    # before the model is built
         check_lowband(a.lowband, a.lowband_fade, spectro_bins(opt.n_fft, opt.mdct_type), opt.hr_sampling_rate / opt.lr_sampling_rate)
         check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
+        _loudness_args(a, opt.hr_sampling_rate)
     except ValueError as e:
         ap.error(str(e))
     from ..models.models import create_model
@@ -231,6 +260,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 _print_peaks(r['path'], r['output'])
             if r.get('spectrogram') is not None:                           # (without the option: no line more than before)
                 _print_spectrogram(r['spectrogram'])
+            if r.get('loudness') is not None:
+                _print_loudness(r['path'], r['loudness'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -259,9 +290,14 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_peaks(a.output, res['output'])
         if res.get('spectrogram') is not None:
             _print_spectrogram(res['spectrogram'])
+        if res.get('loudness') is not None:
+            _print_loudness(a.output, res['loudness'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
-                    'metrics': m, 'metrics_ext': ext, 'output': res.get('output')}]
+                    'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
     if a.metrics_csv:
-        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks)
+        if a.loudness is None:
+            write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks)
+        else:
+            write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, loudness=True)
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -1,11 +1,12 @@
-"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip and csrc/specimg.hip as
-tensor functions."""
+"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip and
+csrc/loudness.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from .plans import CROSSOVER_MAX_TAPS, check_dither, check_encoding, spectrogram_lut
+from .plans import (CROSSOVER_MAX_TAPS, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither, check_encoding, check_loudness_rate,
+                    spectrogram_lut)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -226,3 +227,73 @@ def spectrogram_rgb(db, top, range_db, width, height, gap):
     _lib.check(lib.p2phd_specimg_render(_lib.ptr(d), R, F, K, _lib.ptr(top), float(range_db), _lib.ptr(lut), int(width), int(height), int(gap),
                                         _lib.ptr(img), _lib.stream_ptr()), "specimg_render")
     return img
+
+
+def loudness_coefficients(rate):
+    """The K-weighting pair of p2phd_loudness_coeffs_fill as a float64 tensor of 10 on the host (no GPU needed): b0 b1 b2 a1 a2
+    of the high shelf, then of the high-pass.  A rate the entry refuses (not a multiple of 10 in [8000, 384000]) is a ValueError."""
+    try:
+        rate = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError("loudness_coefficients: the rate must be a number, got %r" % (rate,))
+    out = torch.empty((10,), dtype=torch.float64)
+    l = _lib.lib()
+    if l.p2phd_loudness_coeffs_fill(rate, ctypes.c_void_p(out.data_ptr())) != 0:
+        raise ValueError(l.p2phd_last_error().decode("utf-8", "replace"))
+    return out
+
+
+def loudness_hops(waveform, rate):
+    """waveform [C, L] f32 on the GPU (rows contiguous, any row pitch) -> z [C, L // hop] float64 on the GPU, hop = rate // 10: per
+    channel and 100 ms hop the energy of the K-weighted signal (p2phd_loudness_hops).  Nothing is waited for."""
+    rate = check_loudness_rate(rate, "loudness_hops")
+    w, C, L, ld = _rows(waveform, "loudness_hops: waveform")
+    z = torch.empty((C, L // (rate // 10)), dtype=torch.float64, device=w.device)
+    _lib.check(_lib.lib().p2phd_loudness_hops(_lib.ptr(w), L, C, max(ld, L), rate, _lib.ptr(z), _lib.stream_ptr()), "loudness_hops")
+    return z
+
+
+def loudness_gate(z, rate, weights=None, target=None, target_dev=None, max_gain_db=LOUDNESS_MAX_GAIN_DB, out=None):
+    """z [C, J] float64 on the GPU (loudness_hops) -> (res4, gain) on the GPU, nothing waited for: res4 = float64
+    {integrated loudness in LUFS, the loudest 400 ms block, the relative threshold, blocks behind both gates} and gain [1] f32, the
+    factor that brings the clip to the wanted level within +-`max_gain_db` -- 1 without one, or where a level is not finite
+    (p2phd_loudness_gate).  `weights`: one number per channel (None: all 1; plans.loudness_channel_weights).  The wanted level:
+    `target_dev`, a float64 tensor on the GPU whose first element the kernel reads (another clip's res4), else `target` in LUFS,
+    else none.  `out`: None, or a uint8 tensor of 40 bytes on the GPU that takes both (res4, then gain): the views are returned."""
+    rate = check_loudness_rate(rate, "loudness_gate")
+    zz = _lib.require_gpu_tensor(z, "loudness_gate: z", torch.float64)
+    if zz.dim() != 2 or not 1 <= zz.shape[0] <= LOUDNESS_MAX_CHANNELS:
+        raise ValueError("loudness_gate: expected z [C, J] with 1 <= C <= %d, got shape %s" % (LOUDNESS_MAX_CHANNELS, tuple(zz.shape)))
+    C, J = zz.shape
+    wbuf = None
+    if weights is not None:
+        wbuf = (ctypes.c_float * C)(*[float(v) for v in weights]) if len(weights) == C else None
+        if wbuf is None:
+            raise ValueError("loudness_gate: %d weights for %d channels" % (len(weights), C))
+    if target_dev is not None:
+        target_dev = _lib.require_gpu_tensor(target_dev, "loudness_gate: target_dev", torch.float64)
+        if target_dev.numel() < 1:
+            raise ValueError("loudness_gate: target_dev is empty")
+    if out is None:
+        out = torch.empty((40,), dtype=torch.uint8, device=zz.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "loudness_gate: out", torch.uint8)
+        if out.numel() != 40:
+            raise ValueError("loudness_gate: out must hold 40 bytes, got %d" % out.numel())
+    res4, gain = _loudness_views(out)
+    _lib.check(_lib.lib().p2phd_loudness_gate(_lib.ptr(zz), J, C, rate, wbuf, float('nan') if target is None else float(target),
+                                              _lib.ptr(target_dev), float(max_gain_db), _lib.ptr(res4), _lib.ptr(gain), _lib.stream_ptr()),
+               "loudness_gate")
+    return res4, gain
+
+
+def _loudness_views(buf):
+    """The packed result of one loudness_gate -- res4 [4] f64 | gain f32 | 4 spare bytes, on the device or its copy on the host ->
+    (res4, gain) as typed views."""
+    return buf[:32].view(torch.float64), buf[32:36].view(torch.float32)
+
+
+def loudness(waveform, rate, weights=None, target=None, target_dev=None, max_gain_db=LOUDNESS_MAX_GAIN_DB, out=None):
+    """loudness_hops and loudness_gate in a row: waveform [C, L] f32 on the GPU -> (res4, gain) on the GPU.  Two launches of the
+    family "loudness" (one where the clip is shorter than a hop), nothing is waited for."""
+    return loudness_gate(loudness_hops(waveform, rate), rate, weights, target, target_dev, max_gain_db, out)

@@ -16,6 +16,12 @@ CROSSOVER_MAX_TAPS = 4095
 SPECTROGRAM_DEFAULTS = {'n_fft': 1024, 'hop': 256, 'width': 1600, 'height': 512, 'range_db': 90.0, 'gap': 2}
 SPECTROGRAM_MAX_SIDE = 16384
 SPECTROGRAM_MAX_GAP = 64
+# the loudness option (csrc/loudness.hip): the largest gain, either way, that normalisation applies; the modes beside a target in LUFS;
+# the rates the K-weighting entry takes (a hop is rate / 10 samples); channels the gate takes
+LOUDNESS_MAX_GAIN_DB = 40.0
+LOUDNESS_MODES = ('report', 'input')
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
+LOUDNESS_MAX_CHANNELS = 64
 # (index, (r, g, b)) anchors of spectrogram_lut
 SPECTROGRAM_LUT_ANCHORS = ((0, (0, 0, 4)), (64, (30, 20, 140)), (128, (180, 40, 150)), (192, (250, 140, 30)), (255, (255, 250, 190)))
 
@@ -205,6 +211,49 @@ def check_spectrogram(n_fft=None, hop=None, width=None, height=None, range_db=No
     if not _is_int(channel) or channel < 0:
         raise ValueError("%s: spectrogram channel must be an int >= 0, got %r" % (who, channel))
     return {'n_fft': n_fft, 'hop': hop, 'width': width, 'height': height, 'range_db': float(range_db), 'gap': gap}
+
+
+def loudness_channel_weights(channels):
+    """The BS.1770 channel weights of a clip of `channels` channels: all 1, except six channels in WAVE order (L R C LFE Ls Rs),
+    where the LFE does not count and the surrounds count 1.41."""
+    channels = int(channels)
+    if channels < 1:
+        raise ValueError("loudness_channel_weights: need at least one channel, got %d" % channels)
+    return (1.0, 1.0, 1.0, 0.0, 1.41, 1.41) if channels == 6 else (1.0,) * channels
+
+
+def check_loudness_rate(rate, who):
+    """The rates p2phd_loudness_coeffs_fill takes: a multiple of 10 in [8000, 384000] Hz."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not LOUDNESS_MIN_RATE <= rate <= LOUDNESS_MAX_RATE \
+            or rate != int(rate) or int(rate) % 10:
+        raise ValueError("%s: loudness is measured in hops of rate / 10 samples: the rate must be a multiple of 10 in [%d, %d] Hz, got %r"
+                         % (who, LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE, rate))
+    return int(rate)
+
+
+def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None):
+    """Validates the loudness option for a file written at `hr_rate` -> None (off), or {'mode': 'report' | 'input' | 'target',
+    'target': the level in LUFS (None unless a number was given), 'max_gain_db'}.  `loudness`: None, 'report' (measure only),
+    'input' (the written clip as loud as the clip the generator was given) or a number in [-70, 0], the target in LUFS.
+    `max_gain_db`: None (LOUDNESS_MAX_GAIN_DB) or a finite level >= 0, an option of the option."""
+    if loudness is None:
+        if max_gain_db is not None:
+            raise ValueError("%s: loudness_max_gain_db is an option of loudness; loudness is None" % who)
+        return None
+    if max_gain_db is None:
+        max_gain_db = LOUDNESS_MAX_GAIN_DB
+    if isinstance(max_gain_db, bool) or not isinstance(max_gain_db, (int, float)) or not 0.0 <= max_gain_db < float('inf'):
+        raise ValueError("%s: loudness_max_gain_db must be finite and >= 0, got %r" % (who, max_gain_db))
+    if isinstance(loudness, str):
+        if loudness not in LOUDNESS_MODES:
+            raise ValueError("%s: loudness must be None, 'report', 'input' or a target in LUFS, got %r" % (who, loudness))
+        mode, target = loudness, None
+    else:
+        if isinstance(loudness, bool) or not isinstance(loudness, (int, float)) or not -70.0 <= loudness <= 0.0:
+            raise ValueError("%s: a loudness target must be a level in [-70, 0] LUFS, got %r" % (who, loudness))
+        mode, target = 'target', float(loudness)
+    check_loudness_rate(hr_rate, who)
+    return {'mode': mode, 'target': target, 'max_gain_db': float(max_gain_db)}
 
 
 def spectrogram_lut():

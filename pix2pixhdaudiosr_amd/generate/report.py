@@ -4,6 +4,7 @@ import csv
 METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd")
 METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")     # --metrics_ext
 METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
+METRICS_COLUMNS_LOUDNESS = ("lufs_in", "lufs_out", "loudness_gain_db")                  # --loudness
 
 
 def _mean(values):
@@ -15,7 +16,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks):
+def _columns(extended, peaks, loudness=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -24,17 +25,22 @@ def _columns(extended, peaks):
     if peaks:
         cols += [(lambda r, c: r['output']['peak_dbfs'][c], _mean), (lambda r, c: r['output']['clipped'][c], _mean),
                  (lambda r, c: r['output']['gain'], _mean)]
+    if loudness:
+        cols += [(lambda r, c: r['loudness']['input'], _mean), (lambda r, c: r['loudness']['output'], _mean),
+                 (lambda r, c: r['loudness']['gain_db'], _mean)]
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
     mean of a column then runs over its entries that are not NaN (a clip too short for one segment has no segmental SNR).
     `peaks`: the records carry 'output' and a row ends with the columns of METRICS_COLUMNS_PEAKS -- the channel's peak in
-    dBFS, its clipped samples and the file's gain; the mean row holds their plain means."""
-    cols = _columns(extended, peaks)
+    dBFS, its clipped samples and the file's gain; the mean row holds their plain means.  `loudness`: the records carry
+    'loudness' and a row ends with the columns of METRICS_COLUMNS_LOUDNESS -- the file's integrated loudness going in and as
+    written, in LUFS, and the gain between the generated and the written clip in dB; plain means again."""
+    cols = _columns(extended, peaks, loudness)
     rows = [(r['path'], c, r['out_frames']) + tuple(value(r, c) for value, _ in cols)
             for r in records for c in range(len(r['metrics_ext' if extended else 'metrics'] or ()))]
     if rows:
@@ -42,11 +48,12 @@ def metrics_rows(records, extended=False, peaks=False):
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ()))
-        for row in metrics_rows(records, extended, peaks):
+        w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
+                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()))
+        for row in metrics_rows(records, extended, peaks, loudness) if loudness else metrics_rows(records, extended, peaks):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
@@ -68,6 +75,10 @@ def _print_metrics_ext(e, prefix=''):
 def _print_peaks(name, o):
     print('%s: peak %s dBFS, %d clipped, %d non-finite, gain %.6f' % (name, ' '.join('%+.2f' % v for v in o['peak_dbfs']),
                                                                     sum(o['clipped']), sum(o['nonfinite']), o['gain']))
+
+
+def _print_loudness(name, l):
+    print('%s: loudness input %+.2f LUFS, output %+.2f LUFS, gain %+.2f dB' % (name, l['input'], l['output'], l['gain_db']))
 
 
 def _print_unwritten(name, available, written):

@@ -5,10 +5,10 @@ import struct
 
 import torch
 
-from .ops import (_pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, pcm_decode, pcm_encode, segments_gather_planar,
-                  segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (ClipError, check_crossover, check_encoding, check_lowband, check_output_options, check_spectrogram, plan_folder, segment_plan,
-                    select_channels, spectro_bins)
+from .ops import (_loudness_views, _pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, loudness, pcm_decode, pcm_encode,
+                  segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
+from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_loudness, check_lowband, check_output_options,
+                    check_spectrogram, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -248,15 +248,15 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
-        back with them, see _fetch.  With a stage the peak kernel runs in front of the encoder,
+        back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
         which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
         one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only."""
         w = sr.contiguous()
         dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage)
-        host, stats = self._fetch(dev, packed, picture)
+        host, stats = self._fetch(dev, packed, picture) if loudness is None else self._fetch(dev, packed, picture, loudness)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding)
         if host is not None:
             self._save(path_out, host, sr.shape[0], encoding)
@@ -271,11 +271,17 @@ class SuperResolver:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed, picture=None):
+    def _fetch(self, dev, packed, picture=None, loudness=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
         -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
-        copied behind the same synchronisation and replaced by their host copies."""
+        copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
+        (the two gate results, a device tensor) is copied and replaced likewise."""
         host = stats = None
+        if loudness is not None:
+            n = loudness['packed'].numel()
+            pin = self._pinned('loudness', n)[:n]
+            pin.copy_(loudness['packed'], non_blocking=True)
+            loudness['packed'] = pin
         if picture is not None:
             img, top = picture['image'], picture['top']
             n = img.numel()
@@ -335,9 +341,32 @@ class SuperResolver:
         return {'path': spec['path'], 'panels': picture['panels'], 'frames': picture['frames'], 'bins': picture['bins'],
                 'top_db': float(picture['top'][0]), 'range_db': spec['plan']['range_db']}
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None):
+    def _measure_loudness(self, loud, lr, sr):
+        """The device work of the loudness option: the clip the generator was given and the generated clip through the hop and
+        gate kernels (four launches of the family "loudness") -> {'packed': both gate results in one buffer of 80 bytes, 'gain':
+        the f32 on the device that brings `sr` to the wanted level (1 with 'report')}."""
+        rate = int(self.opt.hr_sampling_rate)
+        weights = loudness_channel_weights(sr.shape[0])
+        packed = torch.empty((80,), dtype=torch.uint8, device=sr.device)
+        res_in, _ = loudness(lr, rate, weights, out=packed[:40])
+        wanted = {'report': {}, 'input': {'target_dev': res_in}, 'target': {'target': loud['target']}}[loud['mode']]
+        _, gain = loudness(sr, rate, weights, max_gain_db=loud['max_gain_db'], out=packed[40:], **wanted)
+        return {'packed': packed, 'gain': gain}
+
+    @staticmethod
+    def _loudness_result(loud, measure):
+        """The fetched measurement -> the result's 'loudness'."""
+        (res_in, _), (res_out, gain) = _loudness_views(measure['packed'][:40]), _loudness_views(measure['packed'][40:])
+        level_in, measured = float(res_in[0]), float(res_out[0])
+        gain_db = 0.0 if loud['mode'] == 'report' else 20.0 * math.log10(float(gain[0]))
+        return {'input': level_in, 'measured': measured, 'gain_db': gain_db, 'output': measured + gain_db,
+                'momentary_max': float(res_out[1]) + gain_db,
+                'target': {'report': None, 'input': level_in, 'target': loud['target']}[loud['mode']]}
+
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
-        7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}."""
+        7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
+        `loud`: None, or the loudness option (check_loudness)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -345,6 +374,8 @@ class SuperResolver:
         check_encoding(encoding, "enhance_file")
         k = select_channels(channels, meta.num_channels)
         self._check_picture_channel(spec, channels, meta.num_channels)
+        if loud is not None and k > LOUDNESS_MAX_CHANNELS:
+            raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
         rate = meta.sample_rate
         raw = self._decode(host, meta, slot)[:k]
         lr = audio_dataset.lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
@@ -360,12 +391,21 @@ class SuperResolver:
         elif has_hr:
             metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
         output = None
+        measure = None
+        if loud is not None:
+            # behind the metrics, which moment-match and stay those of the unscaled clip; in front of everything that sees the written level
+            measure = self._measure_loudness(loud, lr, sr)
+            if loud['mode'] != 'report':
+                sr = sr * measure['gain']
         picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
-        if path_out is not None or stage is not None or picture is not None:
-            output = self._write(path_out, sr, encoding, stage) if picture is None else self._write(path_out, sr, encoding, stage, picture)
+        if path_out is not None or stage is not None or picture is not None or measure is not None:
+            extra = {} if measure is None else {'loudness': measure}
+            output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
         if picture is not None:
             res['spectrogram'] = self._save_picture(spec, picture)
+        if measure is not None:
+            res['loudness'] = self._loudness_result(loud, measure)
         if extended_metrics:
             res['metrics_ext'] = ext
         if stage is not None:
@@ -374,7 +414,7 @@ class SuperResolver:
 
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
-                     spectrogram_channel=0, spectrogram_opts=None):
+                     spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -400,10 +440,26 @@ class SuperResolver:
         picture is rendered on the device (two launches, family "specimg") and comes back with the payload behind the same
         synchronisation.  The result gains 'spectrogram': {'path', 'panels', 'frames', 'bins', 'top_db' (the level of the
         palette's last colour), 'range_db'}.  A channel that is not among the written ones is a ValueError, before anything is
-        enhanced or written."""
+        enhanced or written.
+        `loudness` (opt-in): the integrated loudness after ITU-R BS.1770-4 / EBU R 128 (csrc/loudness.hip; K-weighting, 400 ms
+        blocks, gates at -70 LUFS and 10 LU under the ungated mean; all written channels as one programme, weights
+        plans.loudness_channel_weights) of the clip the generator was given ('lr') and of the generated clip, and what is done
+        with it: 'report' measures only; 'input' makes the written clip as loud as 'lr'; a number in [-70, 0] makes it that loud,
+        in LUFS.  The gain, at most `loudness_max_gain_db` either way (None: 40 dB), multiplies the clip on the device in front of
+        the output stage: the peak report, the clip guard, the dither, the encoder, the picture and the result's 'sr' see the written
+        level; 'metrics' and 'metrics_ext' are those of the clip in front of the gain.  Four launches of the family "loudness" per
+        file; the figures come back with the payload behind the same synchronisation.  The result gains 'loudness': {'input',
+        'measured' (the generated clip in front of the gain), 'gain_db', 'output' (= measured + gain_db, the written clip unless the
+        output stage scales or clamps it), 'momentary_max' (the loudest 400 ms block of the written clip), 'target' (the level
+        aimed at, None with 'report')}, in LUFS; -inf for a clip shorter than 400 ms or a silent one, which is left as it is.  A
+        high rate that is not a multiple of 10 in [8000, 384000] Hz is a ValueError before the file is opened."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
-        res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec)
+        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db)
+        if loud is None:
+            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec)
+        else:
+            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
 
@@ -424,7 +480,7 @@ class SuperResolver:
 
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
-                       spectrogram=None, spectrogram_channel=0, spectrogram_opts=None):
+                       spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -437,9 +493,13 @@ class SuperResolver:
         ends the run at the first file that would clip.  `spectrogram`: a folder that takes one picture per enhanced file, at
         <relative path>.png (enhance_file's `spectrogram`, `spectrogram_channel`, `spectrogram_opts`); a record then gains
         'spectrogram' (as enhance_file returns it; None for a skipped file).  A file without channel `spectrogram_channel` is
-        reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written."""
+        reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written.
+        `loudness`, `loudness_max_gain_db`: enhance_file's, per file (every file is measured and normalised on its own); a record
+        then gains 'loudness' (as enhance_file returns it; None for a skipped file)."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
+        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db)
+        extra = {} if loud is None else {'loud': loud}
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
@@ -450,6 +510,8 @@ class SuperResolver:
                 rec['output'] = None
             if spec is not None:
                 rec['spectrogram'] = None
+            if loud is not None:
+                rec['loudness'] = None
             try:
                 read = self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
@@ -460,7 +522,7 @@ class SuperResolver:
                     torch.manual_seed(int(seed))
                 res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics,
                                             None if stage is None else dict(stage, seed=dither_seed + k),
-                                            None if spec is None else dict(spec, path=os.path.join(spec['path'], rel + '.png')))
+                                            None if spec is None else dict(spec, path=os.path.join(spec['path'], rel + '.png')), **extra)
                 meta = res['info']
                 rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
                            written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
@@ -471,6 +533,8 @@ class SuperResolver:
                     rec['output'] = res['output']
                 if spec is not None:
                     rec['spectrogram'] = res['spectrogram']
+                if loud is not None:
+                    rec['loudness'] = res['loudness']
             records.append(rec)
             if report is not None:
                 report(rec)

@@ -28,6 +28,10 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             kernels (timed alone, by events) and the rest (the copy back and the PNG encoder on the host); log in
             --spectrogram_log
 
+  loudness  (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, without the option and with
+            loudness='report' and loudness=-23 in one process, the runs interleaved: milliseconds per file, median and spread of
+            --reps, and the two kernels alone (hop energies, gate) by events on the clips of the last run; log in --loudness_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -36,6 +40,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py lowband [--lowband_log profiles/time_generate_lowband.log]
         python tools/time_generate.py crossover [--crossover_log profiles/time_generate_crossover.log]
         python tools/time_generate.py spectrogram [--spectrogram_log profiles/time_generate_spectrogram.log]
+        python tools/time_generate.py loudness [--loudness_log profiles/time_generate_loudness.log]
 """
 import argparse
 import os
@@ -264,6 +269,72 @@ def run_spectrogram(seconds, reps, log):
         f.write(text)
 
 
+def run_loudness(seconds, reps, log):
+    """enhance_file, file to file, without and with the loudness option: the same object, the same input, interleaved; then the two
+    kernels alone."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, loudness_gate, loudness_hops
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x.cpu() + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float()[None]      # as the spectrogram run's original
+    sr = SuperResolver(model, opt, overlap=0.25)
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py loudness: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz with a full-band original, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, hr, rate)
+        variants = (("loudness off   ", {}), ("loudness report", dict(loudness='report')), ("loudness -23   ", dict(loudness=-23.0)))
+        for _, kw in variants:                                     # warm-up: capture, pinned buffers, page cache
+            res = sr.enhance_file(src, out, **kw)
+            sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in variants]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(variants):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(variants, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        for k in (1, 2):
+            lines.append("%s costs %.3f ms per file (difference of the medians), %.2f %% of the file without it"
+                         % (variants[k][0].strip(), _median(ts[k]) - _median(ts[0]), 100.0 * (_median(ts[k]) - _median(ts[0])) / _median(ts[0])))
+        lines.append("the last file: %s" % ", ".join("%s %s" % (k, ("%+.3f" % v) if v is not None else "none") for k, v in sorted(res['loudness'].items())))
+        # the two kernels alone, by events, on the generated clip of the last run (one row of %d samples)
+        clip = res['sr'].contiguous()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        k_hops, k_gate = [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            z = loudness_hops(clip, rate)
+            ev[1].record()
+            loudness_gate(z, rate, target=-23.0)
+            ev[2].record()
+            torch.cuda.synchronize()
+            k_hops.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_gate.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        hop = rate // 10
+        steps = 3 * hop                                            # samples one work item walks: 200 ms of warm-up and its hop
+        us = _median(k_hops[2:])
+        lines.append("kernels alone (events, median of %d): loudness_hops %.1f us (%d hops of %d samples, %d workgroups of one wave, %d samples "
+                     "walked per work item: %.1f ns per sample of the float64 recursion, %.2f ms of audio per us), loudness_gate %.1f us (%d blocks)"
+                     % (reps, us, z.shape[1], hop, -(-z.shape[1] // 64), steps, us * 1e3 / steps, clip.shape[-1] / rate * 1e3 / us,
+                        _median(k_gate[2:]), max(z.shape[1] - 3, 0)))
+        lines.append("runs: loudness_hops %s; loudness_gate %s" % (" ".join("%.1f" % v for v in k_hops[2:]), " ".join("%.1f" % v for v in k_gate[2:])))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def _run_variants(seconds, reps, log, mode, variants):
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
@@ -351,12 +422,13 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
     ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
     ap.add_argument("--spectrogram_log", default=os.path.join(ROOT, "profiles", "time_generate_spectrogram.log"))
+    ap.add_argument("--loudness_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
@@ -369,6 +441,8 @@ def main():
         return run_crossover(a.seconds, a.reps, a.crossover_log)
     if a.mode == "spectrogram":
         return run_spectrogram(a.seconds, a.reps, a.spectrogram_log)
+    if a.mode == "loudness":
+        return run_loudness(a.seconds, a.reps, a.loudness_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
