@@ -64,6 +64,8 @@ int p2phd_device_info(char* name, int cap);
  *                      stride-2 pair, the discriminator's first / last layer, the two 7x7 layers, the reflection extras, the fast MDCT:
  *                      on (default; c7_generic / reflect_generic / mdct_generic = 1 select the generic path instead)
  *   "wgrad_tm" 0|128, "wgrad_xcd" 0|1, "mdct_iters" 0..8, "c7_abl"   weight-gradient row tile / XCD-aware order, experiment knobs
+ *   "truepeak_grid" n  workgroups per row of p2phd_truepeak at most (0 = one per tile, as far as the partial table has rows; 1 .. 65536:
+ *                      tests run the path on which a workgroup walks several tiles at a small size); the result's bits do not depend on it
  *   "cw_inject" 0|1    libp2phd_hip_chk.so only: selects round 4's too-lax HALO wait (sensitivity check of p2phd_wait_check) */
 int p2phd_set_option(const char* name, int value);
 /* zeroes the arrival tickets of the fixed-order reductions on `stream` (13 KB memset; see "Streams" above) */
@@ -87,7 +89,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
  * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
  * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip), "loudness" (the
- * BS.1770 hop energies and the gate of whole-file generation, csrc/loudness.hip).
+ * BS.1770 hop energies and the gate of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
+ * of whole-file generation, csrc/truepeak.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -369,6 +372,38 @@ int p2phd_loudness_coeffs_fill(double rate, double* out10);
 int p2phd_loudness_hops(const float* planar, int64_t frames, int channels, int64_t ld, int rate, double* z, void* stream);
 int p2phd_loudness_gate(const double* z, int64_t J, int channels, int rate, const float* weights, double target, const double* target_dev,
                         double max_gain_db, double* res4, float* gain, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * True peak of whole-file generation after ITU-R BS.1770-4 Annex 2 (oversample, take the largest magnitude), csrc/truepeak.hip.
+ * Launch family "truepeak" (a p2phd_truepeak with frames > 0 counts 1).
+ *
+ * p2phd_truepeak_taps_fill (HOST only, no device, as p2phd_xover_taps_fill): the polyphase table c[factor][P], phase-major, of a
+ *   Kaiser-windowed sinc interpolator; factor F = 1, 2 or 4, P = taps_per_phase even and in [4, 64], beta finite and >= 0.  In
+ *   float64, with tau = (k - (P / 2 - 1)) - p / F and sinc(x) = sin(pi x) / (pi x):
+ *     c[p][k] = sinc(tau) I0(beta sqrt(1 - (tau / (P / 2))^2)) / I0(beta)
+ *   each phase divided by its own float64 sum (DC gain 1), each coefficient then rounded once to fp32.  Phase 0 is written as the
+ *   unit impulse at k = P / 2 - 1, not computed.  c[p][k] and c[F - p][P - 1 - k] are written from one value: the same bits.  Bad
+ *   arguments: P2PHD_EINVAL with an error text.
+ * p2phd_truepeak: planar [channels][ld] f32 rows of `frames` = L samples (layout and argument checks of p2phd_pcm_peak; rows may
+ *   start at any float), table_dev: factor * P f32 on the device -- the caller's table, of any shape: neither the symmetry nor the
+ *   impulse of phase 0 is assumed or used (phase 0 is not read).  x~ is the row, 0 outside [0, L), every NaN or infinite sample taken
+ *   as 0 (p2phd_pcm_peak counts those).  For p = 1 .. F - 1 and i = -1 .. L - 1
+ *     y[i][p] = sum_{k = 0}^{P - 1} c[p][k] x~[i + k - (P / 2 - 1)]
+ *   as ONE fp32 accumulator that starts at +0 and takes acc = fma(c[p][k], x~, acc) for k ascending (one rounding per tap), so a
+ *   y has one bit pattern whatever the grid, the tile and the number of rows.  Phase 0 is not computed: it is |x~[i]|, i = 0 .. L - 1.
+ *   tpeak[c] = the maximum of all these magnitudes of row c, as a maximum of bit patterns: tpeak[c] >= the peak[c] of
+ *   p2phd_pcm_peak, always.  gain[0] = m > ceiling ? ceiling / m : 1 with m = max_c tpeak[c], one fp32 division: one gain for all
+ *   channels.  ceiling: finite and > 0.  Both outputs are device pointers, written by every call (frames = 0 included: zeros and
+ *   gain 1, not counted as a launch) without having been zeroed, and hold the same bits on every run: workgroup maxima folded by
+ *   the last workgroup; no float atomics, no host synchronisation, no workspace.  Like every fixed-order reduction of the library,
+ *   two calls must be ordered (see "Streams" above).  A bad factor or P, ceiling <= 0, a null or misaligned pointer, ld < frames:
+ *   P2PHD_EINVAL.
+ * p2phd_truepeak_tile_len (host): instants per workgroup tile of p2phd_truepeak (tests place their lengths around it).
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_truepeak_taps_fill(int factor, int taps_per_phase, double beta, float* out);
+int p2phd_truepeak(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int factor, int taps_per_phase,
+                   float ceiling, float* tpeak, float* gain, void* stream);
+int p2phd_truepeak_tile_len(void);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -64,6 +64,9 @@ SIGNATURES = {
     "p2phd_loudness_coeffs_fill": (_i32, [C.c_double, _vp]),
     "p2phd_loudness_hops": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),
     "p2phd_loudness_gate": (_i32, [_vp, _i64, _i32, _i32, _vp, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
+    "p2phd_truepeak_taps_fill": (_i32, [_i32, _i32, C.c_double, _vp]),
+    "p2phd_truepeak": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "p2phd_truepeak_tile_len": (_i32, []),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -1,0 +1,230 @@
+// Whole-file generation (pix2pixhdaudiosr_amd/generate/): the true peak of a clip after ITU-R BS.1770-4 Annex 2 -- oversample, take
+// the largest magnitude -- and the gain that brings it down to a ceiling.  Launch family "truepeak".
+//
+//   taps_fill  (host) the polyphase table c[F][P] of a Kaiser-windowed sinc interpolator, float64, every phase with DC gain 1,
+//              rounded once to fp32; phase 0 is the unit impulse, phases p and F - p mirror each other bit for bit.
+//   truepeak   x~ = the row, 0 outside [0, L), a NaN or infinite sample taken as 0;
+//              y[i][p] = sum_k c[p][k] x~[i + k - (P/2 - 1)]   for p = 1 .. F - 1 and i = -1 .. L - 1,   y[i][0] = x~[i], i = 0 .. L - 1;
+//              tpeak[c] = max |y| of row c, gain = m > ceiling ? ceiling / m : 1 with m the largest tpeak.
+//
+// Arithmetic of a y, the same whatever the grid, the tile or the number of rows: one fp32 accumulator that starts at +0 and takes
+// acc = fma(c[p][k], x~, acc) for k = 0, 1, .., P - 1 in that order (one rounding per tap).  Phase 0 is not computed: it is the
+// sample.  The peak is a maximum of the bit patterns of |y|, which does not depend on the order; the gain is one fp32 division.
+//
+// One workgroup per (tile of kTile instants, row); a row is a channel, on blockIdx.y.  (Where a clip has more tiles than the
+// partial table has rows, a workgroup walks several tiles.)  Instant j of a row stands for i = j - 1, so a row has L + 1 of them.
+// The tile's samples with their P - 1 halo are staged in LDS, the non-finite ones zeroed on load.  A thread owns kIn CONSECUTIVE
+// instants and keeps their kIn-wide sample window in registers: tap k + 1 needs the window of tap k shifted by one sample, so a
+// tap costs one LDS read and (F - 1) kIn fmas per thread -- all fractional phases are formed from the one window.  Lanes read
+// addresses kIn = 8 dwords apart; the staged array carries one pad dword per 8 (position p lives at p + p / 8), lane t reads
+// 9 t + const, and 9 is coprime to 32: conflict-free, as in xover.hip.  The table (at most 3 x 64 floats that count) is read at
+// the same address in every lane: scalar loads.  Workgroup maxima are stored and folded by the last workgroup (common.h:
+// fold_arrive_last), so nothing is zeroed before the launch and there is no float atomic.  LDS: (2048 + 64) * 9 / 8 floats and
+// the fold = 10.4 KiB per workgroup.  No workspace besides the partials.  No roofline claim: see DESIGN.md section 6.
+#include "common.h"
+#include "convplan.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+namespace {
+constexpr int kThreads = 256;
+constexpr int kIn = 8;                        // instants per thread (the pad rule below is written for 8)
+constexpr int kTile = kThreads * kIn;         // instants per workgroup and tile
+constexpr int kMinTaps = 4, kMaxTaps = 64;    // per phase
+
+__device__ __forceinline__ int pad8(int p) { return p + (p >> 3); }
+constexpr int lds_floats(int n) { return n + (n >> 3) + 1; }
+
+__device__ __forceinline__ void part_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t part_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+
+// NP = F - 1 fractional phases.  grid (gx, channels): workgroup (b, c) takes tiles b, b + gx, .. of row c.
+template <int NP>
+__global__ __launch_bounds__(kThreads) void truepeak_kernel(const float* __restrict__ planar, long ld, long L, const float* __restrict__ tab,
+                                                            int P, long tiles, float ceiling, uint32_t* __restrict__ part,
+                                                            unsigned* __restrict__ ticket, float* __restrict__ tpeak, float* __restrict__ gain) {
+  __shared__ float s_x[lds_floats(kTile + kMaxTaps)];
+  __shared__ uint32_t s_pk[kThreads];
+  const int tid = threadIdx.x, c = blockIdx.y, gx = gridDim.x, C = gridDim.y;
+  const float* row = planar + (long)c * ld;
+  const int half = P / 2 - 1;                                     // taps in front of the instant's own sample
+  const int base = tid * kIn;
+  uint32_t pk = 0u;
+  for (long tile = blockIdx.x; tile < tiles; tile += gx) {
+    const long j0 = tile * kTile;                                 // first instant of the tile: i = j0 - 1
+    const int len = (int)min((long)kTile, L + 1 - j0);            // instants of this tile, >= 1
+    const int len8 = (len + kIn - 1) & ~(kIn - 1);                // ... up to whole threads: everything a thread reads is staged
+    const int n = len8 + P - 1;                                   // staged samples: position q holds x~[j0 - 1 - half + q]
+    const long g0 = j0 - 1 - half;
+    for (int q = tid; q < n; q += kThreads) {
+      const long j = g0 + q;
+      uint32_t bits = 0u;
+      if (j >= 0 && j < L) {
+        bits = __float_as_uint(row[j]);
+        if ((bits & 0x7FFFFFFFu) >= 0x7F800000u) bits = 0u;       // NaN, +-inf: taken as 0
+      }
+      s_x[pad8(q)] = __uint_as_float(bits);
+    }
+    __syncthreads();
+    if (base < len) {
+      uint32_t m[kIn];
+      // phase 0: the instants' own samples (i = -1 holds x~ = 0)
+#pragma unroll
+      for (int r = 0; r < kIn; ++r) m[r] = abs_bits(s_x[pad8(base + r + half)]);
+      if (NP > 0) {
+        // instant r of this thread at tap k reads position base + r + k; w holds those samples at the current tap
+        float acc[NP > 0 ? NP : 1][kIn];
+        float w[kIn];
+#pragma unroll
+        for (int r = 0; r < kIn; ++r) {
+          w[r] = s_x[pad8(base + r)];
+#pragma unroll
+          for (int p = 0; p < NP; ++p) acc[p][r] = 0.0f;
+        }
+        int k = 0;
+        for (; k + kIn <= P; k += kIn) {
+          // eight taps with the window rotating through the registers: at step u the sample of instant r is w[(r + u) & 7]
+#pragma unroll
+          for (int u = 0; u < kIn; ++u) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+              const float ck = tab[(p + 1) * P + k + u];
+#pragma unroll
+              for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[(r + u) & (kIn - 1)], acc[p][r]);
+            }
+            // the next tap: every instant moves one sample up, instant 7 takes a new one (not read behind the last tap)
+            w[u & (kIn - 1)] = s_x[pad8(min(base + kIn + k + u, n - 1))];
+          }
+        }
+        for (; k < P; ++k) {                                      // the last taps mod 8, with the window in place
+#pragma unroll
+          for (int p = 0; p < NP; ++p) {
+            const float ck = tab[(p + 1) * P + k];
+#pragma unroll
+            for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[r], acc[p][r]);
+          }
+#pragma unroll
+          for (int r = 0; r + 1 < kIn; ++r) w[r] = w[r + 1];
+          w[kIn - 1] = s_x[pad8(min(base + kIn + k, n - 1))];
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int r = 0; r < kIn; ++r) m[r] = max(m[r], abs_bits(acc[p][r]));
+      }
+#pragma unroll
+      for (int r = 0; r < kIn; ++r)
+        if (base + r < len) pk = max(pk, m[r]);                   // instants behind i = L - 1 do not count
+    }
+    __syncthreads();                                              // every window read is done: the region takes the next tile
+  }
+  s_pk[tid] = pk;
+  __syncthreads();
+  for (int o = kThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) s_pk[tid] = max(s_pk[tid], s_pk[tid + o]);
+    __syncthreads();
+  }
+  if (tid == 0) part_store(part + (size_t)c * gx + blockIdx.x, s_pk[0]);
+  if (!p2phd::fold_arrive_last(ticket, (unsigned)(gx * C))) return;
+  // the last workgroup: wave w folds channels w, w + 4, ...; a maximum does not depend on the order
+  __shared__ uint32_t s_max[kThreads / 64];
+  const int lane = tid & 63, wave = tid >> 6;
+  uint32_t top = 0u;
+  for (int ch = wave; ch < C; ch += kThreads / 64) {
+    uint32_t p = 0u;
+    for (int b = lane; b < gx; b += 64) p = max(p, part_load(part + (size_t)ch * gx + b));
+    for (int s = 32; s > 0; s >>= 1) p = max(p, (uint32_t)__shfl_xor((int)p, s));
+    if (lane == 0) tpeak[ch] = __uint_as_float(p);
+    top = max(top, p);
+  }
+  if (lane == 0) s_max[wave] = top;
+  __syncthreads();
+  if (tid == 0) {
+    const float m = __uint_as_float(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    *gain = m > ceiling ? ceiling / m : 1.0f;
+  }
+}
+
+// I0(x), x >= 0: the power series sum_m ((x / 2)^2m / (m!)^2), every term positive; stops when a term no longer changes the sum
+double bessel_i0(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int m = 1; m < 1000; ++m) {
+    term *= q / ((double)m * (double)m);
+    const double next = sum + term;
+    if (next == sum) break;
+    sum = next;
+  }
+  return sum;
+}
+
+bool plan_ok(int factor, int taps_per_phase) {
+  return (factor == 1 || factor == 2 || factor == 4) && taps_per_phase >= kMinTaps && taps_per_phase <= kMaxTaps && (taps_per_phase & 1) == 0;
+}
+
+// workgroups per row: one per tile, as far as the partial table has rows (and the "truepeak_grid" option allows)
+int tile_grid(int64_t tiles, int channels, size_t scratch_words) {
+  int64_t cap = (int64_t)(scratch_words / (size_t)channels);
+  if (p2phd::g_opt_truepeak_grid > 0) cap = std::min<int64_t>(cap, p2phd::g_opt_truepeak_grid);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cap));
+}
+
+}  // namespace
+
+extern "C" int p2phd_truepeak_tile_len(void) { return kTile; }
+
+extern "C" int p2phd_truepeak_taps_fill(int factor, int taps_per_phase, double beta, float* out) {
+  P2PHD_REQUIRE(plan_ok(factor, taps_per_phase), "truepeak_taps_fill: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
+                kMinTaps, kMaxTaps, factor, taps_per_phase);
+  P2PHD_REQUIRE(beta >= 0.0 && std::isfinite(beta), "truepeak_taps_fill: beta must be finite and >= 0, got %g", beta);
+  P2PHD_REQUIRE(out != nullptr, "truepeak_taps_fill: null output");
+  const int F = factor, P = taps_per_phase, half = P / 2 - 1;
+  const double pi = 3.14159265358979323846, i0b = bessel_i0(beta);
+  for (int k = 0; k < P; ++k) out[k] = k == half ? 1.0f : 0.0f;   // phase 0: the unit impulse
+  std::vector<double> v((size_t)P);
+  for (int p = 1; 2 * p <= F; ++p) {
+    const bool own_mirror = 2 * p == F;                           // tau(P - 1 - k) = -tau(k): the phase mirrors itself
+    for (int k = 0; k < (own_mirror ? P / 2 : P); ++k) {
+      const double tau = (double)(k - half) - (double)p / (double)F;       // never 0: p / F is a proper fraction
+      const double y = pi * tau, r = tau / (double)(P / 2);
+      v[(size_t)k] = std::sin(y) / y * bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+      if (own_mirror) v[(size_t)(P - 1 - k)] = v[(size_t)k];
+    }
+    double sum = 0.0;
+    for (int k = 0; k < P; ++k) sum += v[(size_t)k];
+    for (int k = 0; k < P; ++k) {
+      const float ck = (float)(v[(size_t)k] / sum);
+      out[p * P + k] = ck;
+      out[(F - p) * P + (P - 1 - k)] = ck;                        // mirrored bit for bit
+    }
+  }
+  return P2PHD_OK;
+}
+
+extern "C" int p2phd_truepeak(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int factor, int taps_per_phase,
+                              float ceiling, float* tpeak, float* gain, void* stream) {
+  if (const int rc = p2phd::pcm_check_rows("truepeak", frames, channels, ld, P2PHD_PCM_F32, true)) return rc;
+  P2PHD_REQUIRE(plan_ok(factor, taps_per_phase), "truepeak: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
+                kMinTaps, kMaxTaps, factor, taps_per_phase);
+  P2PHD_REQUIRE(ceiling > 0.0f && std::isfinite(ceiling), "truepeak: ceiling must be finite and > 0, got %g", (double)ceiling);
+  P2PHD_REQUIRE(tpeak && gain && table_dev, "truepeak: null output or table pointer");
+  P2PHD_REQUIRE(frames == 0 || planar, "truepeak: null pointer");
+  P2PHD_REQUIRE(((reinterpret_cast<uintptr_t>(planar) | reinterpret_cast<uintptr_t>(table_dev) | reinterpret_cast<uintptr_t>(tpeak) |
+                  reinterpret_cast<uintptr_t>(gain)) & 3) == 0, "truepeak: a pointer is not aligned to a float");
+  hipStream_t st = (hipStream_t)stream;
+  const p2phd::FoldScratch fs = p2phd::fold_scratch(p2phd::FOLD_TRUEPEAK, st);
+  if (fs.part == nullptr) return P2PHD_EINVAL;                   // (refused: error text set by fold_scratch)
+  P2PHD_REQUIRE(fs.floats >= (size_t)channels, "truepeak: reduction scratch too small for %d channels", channels);
+  // frames = 0 launches too -- one tile that holds the instant i = -1 alone: the outputs (zeros, gain 1) are valid after every call
+  const int64_t tiles = p2phd::cdiv(frames + 1, (int64_t)kTile);
+  const dim3 grid(tile_grid(tiles, channels, fs.floats), channels);
+  uint32_t* part = reinterpret_cast<uint32_t*>(fs.part);
+  const auto kernel = factor == 4 ? truepeak_kernel<3> : factor == 2 ? truepeak_kernel<1> : truepeak_kernel<0>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, planar, (long)ld, (long)frames, table_dev, taps_per_phase, (long)tiles, ceiling, part,
+                     fs.ticket, tpeak, gain);
+  if (frames > 0) ++p2phd::g_launch_count[p2phd::LC_TRUEPEAK];
+  return p2phd::check_launch("truepeak");
+}

@@ -39,17 +39,22 @@ on the device from the clips that are there at the end of enhance_file (`spectro
 the input the generator was given and of the generated clip on the device -- the level the pipeline writes depends on the
 checkpoint's rates, the transform and the overlap -- and, with `input` or a target such as -23, multiplies the clip by the one
 gain that brings it there, in front of the output stage (`loudness_hops`, `loudness_gate`, `loudness`).
+
+`--true_peak` (opt-in, csrc/truepeak.hip) measures the true peak after ITU-R BS.1770-4 Annex 2 on the device -- the clip the
+encoder sees, oversampled to at least 192 kHz -- and reports it in dBTP; `--clip guard` then holds the true peak, not the sample
+peak, at `--ceiling_dbfs`, and `--clip error` refuses a file whose true peak exceeds the encoding's limit (`true_peaks`,
+`true_peak_coefficients`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, crossover, crossover_coefficients, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_hops, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
-                  segments_stitch_planar, spectrogram_rgb, stft_db)
+                  segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
 from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
                     LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
-                    PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, ClipError, ceiling_from_dbfs, check_crossover,
+                    PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
-                    check_spectrogram, crossover_plan, crossover_width_hz, encoding_limit, loudness_channel_weights, plan_folder,
-                    segment_plan, select_channels, spectro_bins, spectrogram_lut)
-from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS, metrics_rows,  # noqa: F401
-                     write_metrics_csv)
+                    check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, loudness_channel_weights, plan_folder,
+                    segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
+from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS,  # noqa: F401
+                     METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

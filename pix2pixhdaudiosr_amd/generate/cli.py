@@ -185,6 +185,11 @@ def _parser():
                          "loudness_gain_db) of --metrics_csv (default: off)")
     ap.add_argument("--loudness_max_gain_db", type=float, default=None, metavar="DB",
                     help="--loudness input|LUFS: the largest gain applied, either way (default 40)")
+    ap.add_argument("--true_peak", action="store_true",
+                    help="also measure the true peak (ITU-R BS.1770-4 Annex 2: the written clip oversampled to at least 192 kHz) and "
+                         "print it in dBTP with the peak line of every file; --clip guard then brings the true peak, not the sample "
+                         "peak, down to --ceiling_dbfs (read as dBTP) and --clip error also refuses a file whose true peak exceeds the "
+                         "limit of --encoding; one more column (true_peak_dbtp) of --metrics_csv (default: off)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -205,6 +210,8 @@ def main(argv=None):
         check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
         picture = _spectrogram_args(a, folder_mode)
         picture.update(_loudness_args(a))
+        if a.true_peak:
+            picture['true_peak'] = True
     except ValueError as e:
         ap.error(str(e))
     stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks, **picture)
@@ -256,7 +263,7 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
             print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
-            if a.report_peaks:
+            if a.report_peaks or a.true_peak:
                 _print_peaks(r['path'], r['output'])
             if r.get('spectrogram') is not None:                           # (without the option: no line more than before)
                 _print_spectrogram(r['spectrogram'])
@@ -286,7 +293,7 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
-        if a.report_peaks:
+        if a.report_peaks or a.true_peak:
             _print_peaks(a.output, res['output'])
         if res.get('spectrogram') is not None:
             _print_spectrogram(res['spectrogram'])
@@ -295,9 +302,7 @@ def _run(a, sr, stage, seed, rate, folder_mode):
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
     if a.metrics_csv:
-        if a.loudness is None:
-            write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks)
-        else:
-            write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, loudness=True)
+        extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
+        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

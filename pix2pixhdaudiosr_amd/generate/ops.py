@@ -1,12 +1,12 @@
-"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip and
-csrc/loudness.hip as tensor functions."""
+"""Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
+csrc/loudness.hip and csrc/truepeak.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
 from .plans import (CROSSOVER_MAX_TAPS, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither, check_encoding, check_loudness_rate,
-                    spectrogram_lut)
+                    spectrogram_lut, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -297,3 +297,47 @@ def loudness(waveform, rate, weights=None, target=None, target_dev=None, max_gai
     """loudness_hops and loudness_gate in a row: waveform [C, L] f32 on the GPU -> (res4, gain) on the GPU.  Two launches of the
     family "loudness" (one where the clip is shorter than a hop), nothing is waited for."""
     return loudness_gate(loudness_hops(waveform, rate), rate, weights, target, target_dev, max_gain_db, out)
+
+
+_TRUEPEAK_TABLES = {}                                                       # (factor, taps per phase, beta, device) -> the table on the device
+
+
+def true_peak_coefficients(factor, taps_per_phase, beta):
+    """The polyphase table of p2phd_truepeak_taps_fill as a float32 tensor [factor, taps_per_phase] on the host (no GPU needed)."""
+    c = torch.empty((max(int(factor), 1), max(int(taps_per_phase), 1)), dtype=torch.float32)
+    _lib.check(_lib.lib().p2phd_truepeak_taps_fill(int(factor), int(taps_per_phase), float(beta), ctypes.c_void_p(c.data_ptr())),
+               "truepeak_taps_fill")
+    return c
+
+
+def _true_peak_views(buf, C):
+    """The packed true-peak buffer -- tpeak[C] f32 | gain f32, 4 * C + 4 bytes, on the device or its copy on the host ->
+    (tpeak, gain) as typed views."""
+    return buf[:4 * C].view(torch.float32), buf[4 * C:4 * C + 4].view(torch.float32)
+
+
+def _true_peaks_packed(waveform, rate, ceiling, who):
+    """-> (the two results of true_peaks as views of one byte buffer, the buffer): one copy brings both back."""
+    plan = truepeak_plan(rate)
+    ceiling = 1.0 if ceiling is None else float(ceiling)
+    if not 0.0 < ceiling < float('inf'):
+        raise ValueError("%s: ceiling must be a finite level > 0, or None for 1, got %r" % (who, ceiling))
+    w, C, L, ld = _rows(waveform, "%s: waveform" % who)
+    key = (plan['factor'], plan['taps_per_phase'], plan['beta'], str(w.device))
+    table = _TRUEPEAK_TABLES.get(key)
+    if table is None:
+        table = _TRUEPEAK_TABLES[key] = true_peak_coefficients(*key[:3]).to(w.device)
+    buf = torch.empty((4 * C + 4,), dtype=torch.uint8, device=w.device)
+    tpeak, gain = views = _true_peak_views(buf, C)
+    _lib.check(_lib.lib().p2phd_truepeak(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(table), plan['factor'], plan['taps_per_phase'], ceiling,
+                                         _lib.ptr(tpeak), _lib.ptr(gain), _lib.stream_ptr()), "truepeak")
+    return views, buf
+
+
+def true_peaks(waveform, rate, ceiling=None):
+    """The true peak after ITU-R BS.1770-4 Annex 2 of waveform [C, L] f32 on the GPU (rows contiguous, any row pitch) at `rate` ->
+    (tpeak [C] f32, gain [1] f32) on the GPU, nothing waited for: per channel the largest magnitude of the clip oversampled to at
+    least 192 kHz (plans.truepeak_plan; a linear level, never below pcm_peaks' peak; NaN / inf samples count as 0), and the one
+    gain for all channels that brings the largest of them down to `ceiling` (a linear level; None: 1.0) -- 1 where it already
+    is (p2phd_truepeak).  One launch of the family "truepeak"; the same bits on every run."""
+    return _true_peaks_packed(waveform, rate, ceiling, "true_peaks")[0]

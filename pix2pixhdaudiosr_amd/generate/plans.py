@@ -22,6 +22,10 @@ LOUDNESS_MAX_GAIN_DB = 40.0
 LOUDNESS_MODES = ('report', 'input')
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
 LOUDNESS_MAX_CHANNELS = 64
+# the true-peak option (csrc/truepeak.hip): taps per phase and Kaiser beta of the interpolator; the oversampled rate it reaches
+TRUEPEAK_TAPS_PER_PHASE = 24
+TRUEPEAK_BETA = 9.0
+TRUEPEAK_MIN_OVERSAMPLED_RATE = 192000
 # (index, (r, g, b)) anchors of spectrogram_lut
 SPECTROGRAM_LUT_ANCHORS = ((0, (0, 0, 4)), (64, (30, 20, 140)), (128, (180, 40, 150)), (192, (250, 140, 30)), (255, (255, 250, 190)))
 
@@ -254,6 +258,34 @@ def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None):
         mode, target = 'target', float(loudness)
     check_loudness_rate(hr_rate, who)
     return {'mode': mode, 'target': target, 'max_gain_db': float(max_gain_db)}
+
+
+def truepeak_plan(rate):
+    """The interpolator of the true-peak measurement for a clip at `rate`, host arithmetic only -> {'factor', 'taps_per_phase': 24,
+    'beta': 9.0} for p2phd_truepeak_taps_fill: the factor is 4 below 96 kHz, 2 below 192 kHz and 1 from there on, so that the
+    oversampled rate is at least 192 kHz, as ITU-R BS.1770-4 Annex 2 asks."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 < rate < float('inf'):
+        raise ValueError("truepeak_plan: the rate must be a number > 0, got %r" % (rate,))
+    factor = 1
+    while factor < 4 and rate * factor < TRUEPEAK_MIN_OVERSAMPLED_RATE:
+        factor *= 2
+    return {'factor': factor, 'taps_per_phase': TRUEPEAK_TAPS_PER_PHASE, 'beta': TRUEPEAK_BETA}
+
+
+def check_true_peak(true_peak, stage, encoding, hr_rate, who="enhance_file"):
+    """Validates the true-peak option -> (stage, tp).  Off (False): the stage as it came and None.  On: the stage -- where every
+    output option is at its default, the one of a plain report, so that the result has its 'output' -- and {'rate', 'ceiling': the
+    linear level clip='guard' brings the true peak down to (the stage's ceiling, read as dBTP, else the encoding's limit), 'limit':
+    the encoding's limit, above which clip='error' refuses}."""
+    if not isinstance(true_peak, bool):
+        raise ValueError("%s: true_peak must be a bool, got %r" % (who, true_peak))
+    if not true_peak:
+        return stage, None
+    truepeak_plan(hr_rate)
+    if stage is None:
+        stage = {'clip': 'clamp', 'ceiling': None, 'dither': None, 'seed': 0, 'report': False}
+    limit = encoding_limit(encoding)
+    return stage, {'rate': hr_rate, 'ceiling': limit if stage['ceiling'] is None else stage['ceiling'], 'limit': limit}
 
 
 def spectrogram_lut():

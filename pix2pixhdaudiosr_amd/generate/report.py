@@ -5,6 +5,7 @@ METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd"
 METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")     # --metrics_ext
 METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
 METRICS_COLUMNS_LOUDNESS = ("lufs_in", "lufs_out", "loudness_gain_db")                  # --loudness
+METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                         # --true_peak
 
 
 def _mean(values):
@@ -16,7 +17,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False):
+def _columns(extended, peaks, loudness=False, true_peak=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -28,10 +29,12 @@ def _columns(extended, peaks, loudness=False):
     if loudness:
         cols += [(lambda r, c: r['loudness']['input'], _mean), (lambda r, c: r['loudness']['output'], _mean),
                  (lambda r, c: r['loudness']['gain_db'], _mean)]
+    if true_peak:
+        cols += [(lambda r, c: r['output']['true_peak_dbtp'][c], _mean)]
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -39,8 +42,10 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False):
     `peaks`: the records carry 'output' and a row ends with the columns of METRICS_COLUMNS_PEAKS -- the channel's peak in
     dBFS, its clipped samples and the file's gain; the mean row holds their plain means.  `loudness`: the records carry
     'loudness' and a row ends with the columns of METRICS_COLUMNS_LOUDNESS -- the file's integrated loudness going in and as
-    written, in LUFS, and the gain between the generated and the written clip in dB; plain means again."""
-    cols = _columns(extended, peaks, loudness)
+    written, in LUFS, and the gain between the generated and the written clip in dB; plain means again.  `true_peak`: the records' 'output'
+    carries the true peak and a row ends with the column of METRICS_COLUMNS_TRUE_PEAK -- the channel's true peak in dBTP, like
+    peak_dbfs measured on the clip in front of the guard's gain; its plain mean."""
+    cols = _columns(extended, peaks, loudness, true_peak) if true_peak else _columns(extended, peaks, loudness)
     rows = [(r['path'], c, r['out_frames']) + tuple(value(r, c) for value, _ in cols)
             for r in records for c in range(len(r['metrics_ext' if extended else 'metrics'] or ()))]
     if rows:
@@ -48,12 +53,13 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False):
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
-                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()))
-        for row in metrics_rows(records, extended, peaks, loudness) if loudness else metrics_rows(records, extended, peaks):
+                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ()))
+        extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
+        for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
 
@@ -73,8 +79,9 @@ def _print_metrics_ext(e, prefix=''):
 
 
 def _print_peaks(name, o):
-    print('%s: peak %s dBFS, %d clipped, %d non-finite, gain %.6f' % (name, ' '.join('%+.2f' % v for v in o['peak_dbfs']),
-                                                                    sum(o['clipped']), sum(o['nonfinite']), o['gain']))
+    true_peak = ', true peak %s dBTP' % ' '.join('%+.2f' % v for v in o['true_peak_dbtp']) if 'true_peak_dbtp' in o else ''
+    print('%s: peak %s dBFS%s, %d clipped, %d non-finite, gain %.6f' % (name, ' '.join('%+.2f' % v for v in o['peak_dbfs']), true_peak,
+                                                                      sum(o['clipped']), sum(o['nonfinite']), o['gain']))
 
 
 def _print_loudness(name, l):

@@ -5,10 +5,10 @@ import struct
 
 import torch
 
-from .ops import (_loudness_views, _pcm_peaks_packed, _peak_views, crossover, crossover_coefficients, loudness, pcm_decode, pcm_encode,
+from .ops import (_loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients, loudness, pcm_decode, pcm_encode,
                   segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
 from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_loudness, check_lowband, check_output_options,
-                    check_spectrogram, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
+                    check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -248,35 +248,48 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
         back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
         which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
-        one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only."""
+        one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only.  `true_peak`: the
+        true-peak option (check_true_peak; it comes with a stage): the true-peak kernel runs behind the peak kernel, on the same
+        clip, clip 'guard' takes its gain from it, and its figures come back likewise."""
         w = sr.contiguous()
-        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage)
-        host, stats = self._fetch(dev, packed, picture) if loudness is None else self._fetch(dev, packed, picture, loudness)
-        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding)
+        extra = {} if true_peak is None else {'true_peak': true_peak}
+        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **extra)
+        host, stats = self._fetch(dev, packed, picture, **(extra if loudness is None else dict(extra, loudness=loudness)))
+        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
         if host is not None:
             self._save(path_out, host, sr.shape[0], encoding)
         return output
 
-    def _encode(self, w, wanted, encoding, stage):
-        """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None)."""
+    def _encode(self, w, wanted, encoding, stage, true_peak=None):
+        """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None).
+        `true_peak`: None, or the true-peak option, which gains 'packed' (the packed true-peak buffer on the device); the guard's
+        gain is then the true-peak kernel's."""
         if stage is None:
             return pcm_encode(w, encoding), None
         (_, _, _, gain), packed = _pcm_peaks_packed(w, encoding, stage['ceiling'], "enhance_file")
+        if true_peak is not None:
+            (_, gain), true_peak['packed'] = _true_peaks_packed(w, true_peak['rate'], true_peak['ceiling'], "enhance_file")
         if not wanted:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed, picture=None, loudness=None):
+    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
         -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
         copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
-        (the two gate results, a device tensor) is copied and replaced likewise."""
+        (the two gate results, a device tensor) is copied and replaced likewise; `true_peak`: None, or a dict whose 'packed' (the
+        packed true-peak buffer) is, into a pinned slot of its own."""
         host = stats = None
+        if true_peak is not None:
+            n = true_peak['packed'].numel()
+            pin = self._pinned('true_peak', n)[:n]
+            pin.copy_(true_peak['packed'], non_blocking=True)
+            true_peak['packed'] = pin
         if loudness is not None:
             n = loudness['packed'].numel()
             pin = self._pinned('loudness', n)[:n]
@@ -299,11 +312,20 @@ class SuperResolver:
         return host, stats
 
     @staticmethod
-    def _output(stats, C, stage, path_out, encoding):
-        """The fetched peak buffer of a C-channel clip -> the result's 'output'; ClipError where clip 'error' finds a clipped sample."""
+    def _output(stats, C, stage, path_out, encoding, true_peak=None):
+        """The fetched peak buffer of a C-channel clip -> the result's 'output'; ClipError where clip 'error' finds a clipped sample.
+        `true_peak`: None, or the true-peak option with its fetched 'packed': the output gains 'true_peak' and 'true_peak_dbtp', its
+        'gain' is the true-peak kernel's, and clip 'error' also refuses a true peak above the encoding's limit."""
         peak, over, nonfinite, gain = (v.tolist() for v in _peak_views(stats, C))
+        if true_peak is not None:
+            tpeak, gain = (v.tolist() for v in _true_peak_views(true_peak['packed'], C))
         output = {'peak': peak, 'peak_dbfs': [_dbfs(v) for v in peak], 'clipped': over, 'nonfinite': nonfinite,
                   'gain': gain[0] if stage['clip'] == 'guard' else 1.0}
+        if true_peak is not None:
+            output.update(true_peak=tpeak, true_peak_dbtp=[_dbfs(v) for v in tpeak])
+            if stage['clip'] == 'error' and max(tpeak) > true_peak['limit']:
+                raise ClipError("%s: the true peak %+.2f dBTP is above the limit of %s (%d samples would clip); nothing was written -- "
+                                "clip='guard' scales the file down" % (path_out, max(output['true_peak_dbtp']), encoding, sum(over)))
         if stage['clip'] == 'error' and any(over):
             raise ClipError("%s: %d samples would clip in %s (peak %+.2f dBFS); nothing was written -- clip='guard' scales "
                             "the file down, encoding='float32' keeps the samples"
@@ -363,10 +385,10 @@ class SuperResolver:
                 'momentary_max': float(res_out[1]) + gain_db,
                 'target': {'report': None, 'input': level_in, 'target': loud['target']}[loud['mode']]}
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None):
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
         7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
-        `loud`: None, or the loudness option (check_loudness)."""
+        `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -400,6 +422,8 @@ class SuperResolver:
         picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
         if path_out is not None or stage is not None or picture is not None or measure is not None:
             extra = {} if measure is None else {'loudness': measure}
+            if tp is not None:
+                extra['true_peak'] = dict(tp)                              # (one file's: it takes the file's buffers)
             output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
         if picture is not None:
@@ -414,7 +438,7 @@ class SuperResolver:
 
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
-                     spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None):
+                     spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -452,14 +476,24 @@ class SuperResolver:
         'measured' (the generated clip in front of the gain), 'gain_db', 'output' (= measured + gain_db, the written clip unless the
         output stage scales or clamps it), 'momentary_max' (the loudest 400 ms block of the written clip), 'target' (the level
         aimed at, None with 'report')}, in LUFS; -inf for a clip shorter than 400 ms or a silent one, which is left as it is.  A
-        high rate that is not a multiple of 10 in [8000, 384000] Hz is a ValueError before the file is opened."""
+        high rate that is not a multiple of 10 in [8000, 384000] Hz is a ValueError before the file is opened.
+        `true_peak` (opt-in, a bool): also measure the true peak after ITU-R BS.1770-4 Annex 2 (csrc/truepeak.hip: the clip
+        oversampled to at least 192 kHz, plans.truepeak_plan) where the peak is measured -- on the clip the encoder sees, behind the
+        loudness gain and the crossover.  The result's 'output' -- which then exists also with every other output option at its
+        default -- gains 'true_peak' (linear) and 'true_peak_dbtp', a list each with one entry per written channel, measured on the
+        unscaled clip like 'peak'.  clip 'guard' then takes its gain from the true peak: `ceiling_dbfs` is read as dBTP (None: the
+        encoding's limit) and 'gain' reports it; clip 'error' also refuses a file whose samples fit but whose true peak exceeds the
+        encoding's limit; 'clamp' only reports.  One launch of the family "truepeak" per file; the figures come back with the payload
+        behind the same synchronisation."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
+        stage, tp = check_true_peak(true_peak, stage, encoding, self.opt.hr_sampling_rate)
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db)
+        extra = {} if tp is None else {'tp': tp}
         if loud is None:
-            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec)
+            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
         else:
-            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud)
+            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud, **extra)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
 
@@ -480,7 +514,8 @@ class SuperResolver:
 
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
-                       spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None):
+                       spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
+                       true_peak=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -495,11 +530,15 @@ class SuperResolver:
         'spectrogram' (as enhance_file returns it; None for a skipped file).  A file without channel `spectrogram_channel` is
         reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written.
         `loudness`, `loudness_max_gain_db`: enhance_file's, per file (every file is measured and normalised on its own); a record
-        then gains 'loudness' (as enhance_file returns it; None for a skipped file)."""
+        then gains 'loudness' (as enhance_file returns it; None for a skipped file).  `true_peak`: enhance_file's, per file; a
+        record's 'output' then carries the true-peak figures."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
+        stage, tp = check_true_peak(true_peak, stage, encoding, self.opt.hr_sampling_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db)
         extra = {} if loud is None else {'loud': loud}
+        if tp is not None:
+            extra['tp'] = tp
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,

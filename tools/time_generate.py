@@ -32,6 +32,10 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             loudness='report' and loudness=-23 in one process, the runs interleaved: milliseconds per file, median and spread of
             --reps, and the two kernels alone (hop energies, gate) by events on the clips of the last run; log in --loudness_log
 
+  truepeak  (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, without the option and with
+            true_peak=True, clip='guard' in one process, the runs interleaved: milliseconds per file, median and spread of --reps,
+            and p2phd_truepeak beside p2phd_pcm_peak alone, by events, on the clip of the last run; log in --truepeak_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -41,6 +45,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py crossover [--crossover_log profiles/time_generate_crossover.log]
         python tools/time_generate.py spectrogram [--spectrogram_log profiles/time_generate_spectrogram.log]
         python tools/time_generate.py loudness [--loudness_log profiles/time_generate_loudness.log]
+        python tools/time_generate.py truepeak [--truepeak_log profiles/time_generate_truepeak.log]
 """
 import argparse
 import os
@@ -335,6 +340,74 @@ def run_loudness(seconds, reps, log):
         f.write(text)
 
 
+def run_truepeak(seconds, reps, log):
+    """enhance_file, file to file, without the true-peak option and with it under clip='guard': the same object, the same input,
+    interleaved; then the true-peak kernel and the sample-peak kernel alone on the same clip."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, pcm_peaks, true_peaks, truepeak_plan
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x.cpu() + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float()[None]      # as the spectrogram run's original
+    sr = SuperResolver(model, opt, overlap=0.25)
+    rate = int(opt.hr_sampling_rate)
+    plan = truepeak_plan(rate)
+    lines = ["# tools/time_generate.py truepeak: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz with a full-band original, file to file, untrained weights, %d interleaved repeats" % (seconds, reps),
+             "# true-peak plan: factor %d, %d taps per phase, beta %g" % (plan['factor'], plan['taps_per_phase'], plan['beta'])]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, hr, rate)
+        variants = (("true_peak off         ", {}), ("true_peak, clip guard ", dict(true_peak=True, clip='guard')))
+        for _, kw in variants:                                     # warm-up: capture, pinned buffers, page cache
+            res = sr.enhance_file(src, out, **kw)
+            sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in variants]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(variants):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(variants, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        lines.append("%s costs %.3f ms per file (difference of the medians), %.2f %% of the file without it; it holds the peak report and the "
+                     "guard's gain in the encoder as well as the true-peak kernel"
+                     % (variants[1][0].strip(), _median(ts[1]) - _median(ts[0]), 100.0 * (_median(ts[1]) - _median(ts[0])) / _median(ts[0])))
+        o = res['output']
+        lines.append("the last file: peak %+.3f dBFS, true peak %+.3f dBTP, gain %.6f" % (o['peak_dbfs'][0], o['true_peak_dbtp'][0], o['gain']))
+        # the two kernels alone, by events, on the generated clip of the last run (one row)
+        clip = res['sr'].contiguous()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        k_true, k_peak = [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            true_peaks(clip, rate)
+            ev[1].record()
+            pcm_peaks(clip, 'pcm16')
+            ev[2].record()
+            torch.cuda.synchronize()
+            k_true.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_peak.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        L = clip.shape[-1]
+        us, us_peak = _median(k_true[2:]), _median(k_peak[2:])
+        fmas = (plan['factor'] - 1) * plan['taps_per_phase']
+        lines.append("kernels alone (events, median of %d, each with the allocation of its small result in front): p2phd_truepeak %.1f us (%d "
+                     "samples, %d fma per sample: %.2f Gfma/s, %.2f GB/s of samples read), p2phd_pcm_peak %.1f us: %.1f times the sample-peak kernel"
+                     % (reps, us, L, fmas, L * fmas / us * 1e-3, 4.0 * L / us * 1e-3, us_peak, us / us_peak))
+        lines.append("runs: p2phd_truepeak %s; p2phd_pcm_peak %s" % (" ".join("%.1f" % v for v in k_true[2:]), " ".join("%.1f" % v for v in k_peak[2:])))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def _run_variants(seconds, reps, log, mode, variants):
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
@@ -422,13 +495,14 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
     ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
     ap.add_argument("--spectrogram_log", default=os.path.join(ROOT, "profiles", "time_generate_spectrogram.log"))
     ap.add_argument("--loudness_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness.log"))
+    ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
@@ -443,6 +517,8 @@ def main():
         return run_spectrogram(a.seconds, a.reps, a.spectrogram_log)
     if a.mode == "loudness":
         return run_loudness(a.seconds, a.reps, a.loudness_log)
+    if a.mode == "truepeak":
+        return run_truepeak(a.seconds, a.reps, a.truepeak_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
