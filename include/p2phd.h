@@ -66,6 +66,8 @@ int p2phd_device_info(char* name, int cap);
  *   "wgrad_tm" 0|128, "wgrad_xcd" 0|1, "mdct_iters" 0..8, "c7_abl"   weight-gradient row tile / XCD-aware order, experiment knobs
  *   "truepeak_grid" n  workgroups per row of p2phd_truepeak at most (0 = one per tile, as far as the partial table has rows; 1 .. 65536:
  *                      tests run the path on which a workgroup walks several tiles at a small size); the result's bits do not depend on it
+ *   "limiter_grid" n   workgroups of p2phd_limiter_envelope and of p2phd_limiter_apply at most (0 = one per tile, as far as the partial table
+ *                      has rows; 1 .. 16384: tests run the path on which a workgroup walks several tiles); the result's bits do not depend on it
  *   "cw_inject" 0|1    libp2phd_hip_chk.so only: selects round 4's too-lax HALO wait (sensitivity check of p2phd_wait_check) */
 int p2phd_set_option(const char* name, int value);
 /* zeroes the arrival tickets of the fixed-order reductions on `stream` (13 KB memset; see "Streams" above) */
@@ -90,7 +92,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
  * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip), "loudness" (the
  * BS.1770 hop energies and the gate of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
- * of whole-file generation, csrc/truepeak.hip).
+ * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
+ * csrc/limiter.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -404,6 +407,39 @@ int p2phd_truepeak_taps_fill(int factor, int taps_per_phase, double beta, float*
 int p2phd_truepeak(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int factor, int taps_per_phase,
                    float ceiling, float* tpeak, float* gain, void* stream);
 int p2phd_truepeak_tile_len(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Look-ahead true-peak limiter of whole-file generation, csrc/limiter.hip (the definition is that file's header comment).
+ * Launch family "limiter": p2phd_limiter_envelope and p2phd_limiter_apply with frames > 0 count 1 each, 2 per clip.
+ *
+ * p2phd_limiter_window_fill (HOST only, no device): the smoothing window w[0 .. A], A = lookahead in [1, 1024], A + 1 floats:
+ *   in float64 w[k] = 0.5 - 0.5 cos(2 pi (k + 1) / (A + 2)), divided by the float64 sum, each rounded once to fp32; w[k] and w[A - k]
+ *   are written from one value: the same bits.
+ * p2phd_limiter_envelope: planar, frames, channels, ld, table_dev, factor, taps_per_phase, ceiling as p2phd_truepeak takes them.
+ *   r_out[frames] f32 on the device: r[i] = m[i] > ceiling ? ceiling / m[i] : 1 with m[i] the largest, over the channels, of
+ *   |x~[i]| and the fractional phases |y[i][p]|, |y[i - 1][p]| on both sides of sample i -- every y with the bits p2phd_truepeak
+ *   forms.  peak_in_out (one f32 on the device, written, not read): the largest m, which is the largest tpeak p2phd_truepeak
+ *   reports for the clip, bit for bit; 0 for frames = 0.  Maxima of bit patterns folded by the last workgroup: no float atomics,
+ *   nothing is zeroed beforehand, no host synchronisation.
+ * p2phd_limiter_apply: r[frames] f32 on the device (the envelope's, or any values in (0, 1]; taken as 1 outside [0, frames)),
+ *   lookahead A in [1, 1024], hold H in [0, 4096], window_dev: A + 1 f32 on the device (any values: neither the symmetry nor the
+ *   sum is assumed).  h[j] = min r[j - H .. j + A], d = 1.0f - h, s[i] = sum_k window[k] d[i - k] (one fp32 accumulator from +0, fma
+ *   in ascending k), g[i] = min(r[i], 1.0f - s[i]); out[c][i] = planar[c][i] * g[i] for every channel, rows out_ld apart (out may
+ *   not overlap planar); g_out: NULL, or frames f32 that take g.  stats_out: 8 bytes on the device -- the smallest g as f32 (1 where
+ *   nothing is reduced), then the number of i with g[i] < 1 as u32 (saturating) -- folded in a fixed order in the same launch.
+ *   A tile whose r within reach are all 1 copies its samples: the same bits as the multiply gives a finite sample.
+ *   frames = 0 is valid: the statistics are 1 and 0.
+ * Both share one region of the reduction scratch: the two calls (and any two calls of the family) must be ordered (see "Streams").
+ * A bad factor, P, lookahead or hold, ceiling <= 0, a null or misaligned pointer, ld < frames: P2PHD_EINVAL, nothing is launched.
+ * p2phd_limiter_tile_len (host): samples per workgroup tile of p2phd_limiter_apply; the envelope lays its tiles one sample closer
+ *   (tile_len - 1 apart), because a sample needs the instants on both of its sides.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_limiter_window_fill(int lookahead, float* out);
+int p2phd_limiter_envelope(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int factor, int taps_per_phase,
+                           float ceiling, float* r_out, float* peak_in_out, void* stream);
+int p2phd_limiter_apply(const float* planar, int64_t frames, int channels, int64_t ld, const float* r, int lookahead, int hold,
+                        const float* window_dev, float* out, int64_t out_ld, float* g_out, void* stats_out, void* stream);
+int p2phd_limiter_tile_len(void);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

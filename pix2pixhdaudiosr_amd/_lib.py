@@ -67,6 +67,10 @@ SIGNATURES = {
     "p2phd_truepeak_taps_fill": (_i32, [_i32, _i32, C.c_double, _vp]),
     "p2phd_truepeak": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "p2phd_truepeak_tile_len": (_i32, []),
+    "p2phd_limiter_window_fill": (_i32, [_i32, _vp]),
+    "p2phd_limiter_envelope": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "p2phd_limiter_apply": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "p2phd_limiter_tile_len": (_i32, []),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -44,17 +44,22 @@ gain that brings it there, in front of the output stage (`loudness_hops`, `loudn
 encoder sees, oversampled to at least 192 kHz -- and reports it in dBTP; `--clip guard` then holds the true peak, not the sample
 peak, at `--ceiling_dbfs`, and `--clip error` refuses a file whose true peak exceeds the encoding's limit (`true_peaks`,
 `true_peak_coefficients`).
+
+`--limiter` (opt-in, with `--clip guard`; csrc/limiter.hip) puts a look-ahead true-peak limiter in front of the guard: one gain
+curve for all channels turns down the crests that stand over `--ceiling_dbfs` and nothing else, so a file brought to a loudness
+target stays there where the guard's one gain would give the excess away (`limit`, `limiter_envelope`, `limiter_apply`,
+`limiter_window`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
-from .ops import (PCM_FORMATS, crossover, crossover_coefficients, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
+from .ops import (PCM_FORMATS, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_hops, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
 from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
-                    LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
+                    LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
-                    check_dither, check_encoding, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
-                    check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, loudness_channel_weights, plan_folder,
+                    check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
+                    check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, limiter_plan, loudness_channel_weights, plan_folder,
                     segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
-from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS,  # noqa: F401
+from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS,  # noqa: F401
                      METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

@@ -10,9 +10,9 @@ from types import SimpleNamespace
 
 import torch
 
-from .plans import (CLIP_MODES, LOUDNESS_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_loudness, check_lowband,
+from .plans import (CLIP_MODES, LOUDNESS_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_lowband,
                     check_output_options, check_paths, check_spectrogram, spectro_bins)
-from .report import _print_loudness, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .report import _print_limiter, _print_loudness, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -190,6 +190,15 @@ def _parser():
                          "print it in dBTP with the peak line of every file; --clip guard then brings the true peak, not the sample "
                          "peak, down to --ceiling_dbfs (read as dBTP) and --clip error also refuses a file whose true peak exceeds the "
                          "limit of --encoding; one more column (true_peak_dbtp) of --metrics_csv (default: off)")
+    ap.add_argument("--limiter", action="store_true",
+                    help="with --clip guard: a look-ahead true-peak limiter in front of the guard -- only the crests over --ceiling_dbfs "
+                         "are turned down, by one gain curve for all channels, so the loudness --loudness reached stays where the guard "
+                         "alone would scale the whole file down; measures the true peak as --true_peak does; one more line per file "
+                         "and two more columns (limiter_reduction_db, limited_samples) of --metrics_csv (default: off)")
+    ap.add_argument("--limiter_lookahead_ms", type=float, default=None, metavar="MS",
+                    help="--limiter: how far the gain curve looks ahead of a crest, which is also its attack time (default 5)")
+    ap.add_argument("--limiter_hold_ms", type=float, default=None, metavar="MS",
+                    help="--limiter: how long the curve holds a reduction behind a crest (default 20)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -207,11 +216,14 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:                                                                    # before anything is loaded
         folder_mode = check_paths(a.input, a.output)
-        check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
+        out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
         picture = _spectrogram_args(a, folder_mode)
         picture.update(_loudness_args(a))
         if a.true_peak:
             picture['true_peak'] = True
+        if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
+            check_limiter(a.limiter, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, 48000, "generate")
+            picture.update(limiter=True, limiter_lookahead_ms=a.limiter_lookahead_ms, limiter_hold_ms=a.limiter_hold_ms)
     except ValueError as e:
         ap.error(str(e))
     stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks, **picture)
@@ -229,6 +241,8 @@ def main(argv=None):
         check_lowband(a.lowband, a.lowband_fade, spectro_bins(opt.n_fft, opt.mdct_type), opt.hr_sampling_rate / opt.lr_sampling_rate)
         check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
         _loudness_args(a, opt.hr_sampling_rate)
+        if a.limiter:
+            check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate, "generate")
     except ValueError as e:
         ap.error(str(e))
     from ..models.models import create_model
@@ -263,8 +277,10 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
             print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
-            if a.report_peaks or a.true_peak:
+            if a.report_peaks or a.true_peak or a.limiter:
                 _print_peaks(r['path'], r['output'])
+            if a.limiter:
+                _print_limiter(r['output']['limiter'], r['out_frames'])
             if r.get('spectrogram') is not None:                           # (without the option: no line more than before)
                 _print_spectrogram(r['spectrogram'])
             if r.get('loudness') is not None:
@@ -293,8 +309,10 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
-        if a.report_peaks or a.true_peak:
+        if a.report_peaks or a.true_peak or a.limiter:
             _print_peaks(a.output, res['output'])
+        if a.limiter:
+            _print_limiter(res['output']['limiter'], res['sr'].shape[-1])
         if res.get('spectrogram') is not None:
             _print_spectrogram(res['spectrogram'])
         if res.get('loudness') is not None:
@@ -303,6 +321,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
     if a.metrics_csv:
         extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
+        if a.limiter:
+            extra['limiter'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

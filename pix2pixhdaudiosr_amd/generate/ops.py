@@ -1,12 +1,12 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip and csrc/truepeak.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip and csrc/limiter.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from .plans import (CROSSOVER_MAX_TAPS, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither, check_encoding, check_loudness_rate,
-                    spectrogram_lut, truepeak_plan)
+from .plans import (CROSSOVER_MAX_TAPS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
+                    check_encoding, check_loudness_rate, limiter_plan, spectrogram_lut, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -316,6 +316,15 @@ def _true_peak_views(buf, C):
     return buf[:4 * C].view(torch.float32), buf[4 * C:4 * C + 4].view(torch.float32)
 
 
+def _true_peak_table(plan, device):
+    """The table of truepeak_plan's `plan` on `device`, filled once."""
+    key = (plan['factor'], plan['taps_per_phase'], plan['beta'], str(device))
+    table = _TRUEPEAK_TABLES.get(key)
+    if table is None:
+        table = _TRUEPEAK_TABLES[key] = true_peak_coefficients(*key[:3]).to(device)
+    return table
+
+
 def _true_peaks_packed(waveform, rate, ceiling, who):
     """-> (the two results of true_peaks as views of one byte buffer, the buffer): one copy brings both back."""
     plan = truepeak_plan(rate)
@@ -323,10 +332,7 @@ def _true_peaks_packed(waveform, rate, ceiling, who):
     if not 0.0 < ceiling < float('inf'):
         raise ValueError("%s: ceiling must be a finite level > 0, or None for 1, got %r" % (who, ceiling))
     w, C, L, ld = _rows(waveform, "%s: waveform" % who)
-    key = (plan['factor'], plan['taps_per_phase'], plan['beta'], str(w.device))
-    table = _TRUEPEAK_TABLES.get(key)
-    if table is None:
-        table = _TRUEPEAK_TABLES[key] = true_peak_coefficients(*key[:3]).to(w.device)
+    table = _true_peak_table(plan, w.device)
     buf = torch.empty((4 * C + 4,), dtype=torch.uint8, device=w.device)
     tpeak, gain = views = _true_peak_views(buf, C)
     _lib.check(_lib.lib().p2phd_truepeak(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(table), plan['factor'], plan['taps_per_phase'], ceiling,
@@ -341,3 +347,108 @@ def true_peaks(waveform, rate, ceiling=None):
     gain for all channels that brings the largest of them down to `ceiling` (a linear level; None: 1.0) -- 1 where it already
     is (p2phd_truepeak).  One launch of the family "truepeak"; the same bits on every run."""
     return _true_peaks_packed(waveform, rate, ceiling, "true_peaks")[0]
+
+
+_LIMITER_WINDOWS = {}                                                       # (lookahead, device) -> the window on the device
+
+
+def limiter_window(lookahead):
+    """The smoothing window of p2phd_limiter_window_fill as a float32 tensor of `lookahead` + 1 on the host (no GPU needed):
+    a Hann window without its zeros, sum 1, symmetric bit for bit."""
+    A = int(lookahead)
+    w = torch.empty((max(A, 0) + 1,), dtype=torch.float32)
+    l = _lib.lib()
+    if l.p2phd_limiter_window_fill(A, ctypes.c_void_p(w.data_ptr())) != 0:
+        raise ValueError(l.p2phd_last_error().decode("utf-8", "replace"))
+    return w
+
+
+def _limiter_ceiling(ceiling, who):
+    ceiling = 1.0 if ceiling is None else float(ceiling)
+    if not 0.0 < ceiling < float('inf'):
+        raise ValueError("%s: ceiling must be a finite level > 0, or None for 1, got %r" % (who, ceiling))
+    return ceiling
+
+
+def limiter_envelope(waveform, rate_or_plan, ceiling=None, peak_out=None):
+    """waveform [C, L] f32 on the GPU (rows contiguous, any row pitch) -> (r [L] f32, peak [1] f32) on the GPU, nothing waited for:
+    r[i] = the gain that alone would bring sample i and the oversampled crests on both of its sides, in every channel, to
+    `ceiling` (a linear level; None: 1.0) -- 1 where they are under it -- and the clip's true peak, the largest of true_peaks'
+    (p2phd_limiter_envelope).  `rate_or_plan`: the clip's rate (plans.truepeak_plan picks the interpolator), or such a plan as a
+    dict, with 'table' (the [factor, taps_per_phase] f32 table on the GPU) where the caller brings its own.  `peak_out`: None, or a
+    float32 tensor of one element on the GPU that takes the peak.  One launch of the family "limiter"."""
+    plan = dict(rate_or_plan) if isinstance(rate_or_plan, dict) else truepeak_plan(rate_or_plan)
+    ceiling = _limiter_ceiling(ceiling, "limiter_envelope")
+    w, C, L, ld = _rows(waveform, "limiter_envelope: waveform")
+    table = plan.get('table')
+    if table is None:
+        table = _true_peak_table(plan, w.device)
+    else:
+        table = _lib.require_gpu_tensor(table, "limiter_envelope: table", torch.float32)
+        if not table.is_contiguous() or table.numel() != int(plan['factor']) * int(plan['taps_per_phase']):
+            raise ValueError("limiter_envelope: the table must hold factor * taps_per_phase contiguous floats, got shape %s" % (tuple(table.shape),))
+    r = torch.empty((L,), dtype=torch.float32, device=w.device)
+    if peak_out is None:
+        peak_out = torch.empty((1,), dtype=torch.float32, device=w.device)
+    else:
+        peak_out = _lib.require_gpu_tensor(peak_out, "limiter_envelope: peak_out", torch.float32)
+        if peak_out.numel() != 1:
+            raise ValueError("limiter_envelope: peak_out must hold one value, got shape %s" % (tuple(peak_out.shape),))
+    _lib.check(_lib.lib().p2phd_limiter_envelope(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(table), int(plan['factor']), int(plan['taps_per_phase']),
+                                                 ceiling, _lib.ptr(r), _lib.ptr(peak_out), _lib.stream_ptr()), "limiter_envelope")
+    return r, peak_out
+
+
+def _limiter_stats_views(buf):
+    """The 8 bytes of the limiter's statistics, on the device or their copy on the host -> (the smallest g as f32 [1], the number
+    of reduced samples [1]: the u32's bits in an int32, & 0xFFFFFFFF reads them) as typed views."""
+    return buf[:4].view(torch.float32), buf[4:8].view(torch.int32)
+
+
+def limiter_apply(waveform, r, plan, window_dev=None, stats_out=None, want_g=True):
+    """waveform [C, L] f32 on the GPU (rows contiguous, any row pitch), r [L] f32 on the GPU (limiter_envelope's, or any values in
+    (0, 1]), plan {'lookahead': A, 'hold': H} (plans.limiter_plan) -> (out [C, L], g [L], stats) on the GPU, nothing waited for:
+    the gain curve g -- the smoothed sliding minimum of r over H samples back and A ahead, never above r -- out = waveform * g in a
+    new buffer, and stats, a uint8 tensor of 8 bytes: the smallest g (f32) and the number of samples with g < 1 (u32)
+    (p2phd_limiter_apply).  `window_dev`: A + 1 f32 on the GPU (None: limiter_window(A), filled once per device); `stats_out`:
+    None, or the 8-byte uint8 tensor on the GPU that takes the statistics; `want_g` False: g is not written and None is returned
+    for it.  One launch of the family "limiter"."""
+    A, H = plan['lookahead'], plan['hold']
+    for name, v, lo, hi in (('lookahead', A, 1, LIMITER_MAX_LOOKAHEAD), ('hold', H, 0, LIMITER_MAX_HOLD)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError("limiter_apply: %s must be an int in [%d, %d], got %r" % (name, lo, hi, v))
+    w, C, L, ld = _rows(waveform, "limiter_apply: waveform")
+    rr = _lib.require_gpu_tensor(r, "limiter_apply: r", torch.float32)
+    if rr.dim() != 1 or rr.numel() != L or not rr.is_contiguous():
+        raise ValueError("limiter_apply: r must hold one contiguous value per sample (%d), got shape %s" % (L, tuple(rr.shape)))
+    if window_dev is None:
+        key = (A, str(w.device))
+        window_dev = _LIMITER_WINDOWS.get(key)
+        if window_dev is None:
+            window_dev = _LIMITER_WINDOWS[key] = limiter_window(A).to(w.device)
+    else:
+        window_dev = _lib.require_gpu_tensor(window_dev, "limiter_apply: window_dev", torch.float32)
+        if window_dev.dim() != 1 or window_dev.numel() != A + 1 or not window_dev.is_contiguous():
+            raise ValueError("limiter_apply: window_dev must hold lookahead + 1 = %d contiguous floats, got shape %s" % (A + 1, tuple(window_dev.shape)))
+    if stats_out is None:
+        stats_out = torch.empty((8,), dtype=torch.uint8, device=w.device)
+    else:
+        stats_out = _lib.require_gpu_tensor(stats_out, "limiter_apply: stats_out", torch.uint8)
+        if stats_out.numel() != 8:
+            raise ValueError("limiter_apply: stats_out must hold 8 bytes, got %d" % stats_out.numel())
+    out = torch.empty((C, L), dtype=torch.float32, device=w.device)
+    g = torch.empty((L,), dtype=torch.float32, device=w.device) if want_g else None
+    _lib.check(_lib.lib().p2phd_limiter_apply(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(rr), A, H, _lib.ptr(window_dev), _lib.ptr(out), max(L, 1),
+                                              _lib.ptr(g), _lib.ptr(stats_out), _lib.stream_ptr()), "limiter_apply")
+    return out, g, stats_out
+
+
+def limit(waveform, rate, ceiling=None, lookahead_ms=None, hold_ms=None):
+    """limiter_envelope and limiter_apply in a row: waveform [C, L] f32 on the GPU at `rate` -> (out [C, L], g [L], stats, peak
+    [1]) on the GPU -- the clip with its crests held at `ceiling` (a linear level; None: 1.0) by a gain curve that looks
+    `lookahead_ms` ahead and holds `hold_ms` (plans.limiter_plan), the curve, its statistics (limiter_apply) and the true peak the
+    clip came with.  The result's own true peak may lie a rounding over the ceiling: true_peaks' gain behind it removes that.  Two
+    launches of the family "limiter", nothing is waited for."""
+    plan = limiter_plan(rate, lookahead_ms, hold_ms)
+    r, peak = limiter_envelope(waveform, rate, ceiling)
+    return limiter_apply(waveform, r, plan) + (peak,)

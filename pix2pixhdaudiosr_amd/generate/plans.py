@@ -26,6 +26,12 @@ LOUDNESS_MAX_CHANNELS = 64
 TRUEPEAK_TAPS_PER_PHASE = 24
 TRUEPEAK_BETA = 9.0
 TRUEPEAK_MIN_OVERSAMPLED_RATE = 192000
+# the limiter option (csrc/limiter.hip): look-ahead and hold in ms where none is given -- a judgement about audibility (a short
+# hold lets the gain ride the crests of low tones), not a measured optimum -- and the kernel's caps in samples
+LIMITER_LOOKAHEAD_MS = 5.0
+LIMITER_HOLD_MS = 20.0
+LIMITER_MAX_LOOKAHEAD = 1024
+LIMITER_MAX_HOLD = 4096
 # (index, (r, g, b)) anchors of spectrogram_lut
 SPECTROGRAM_LUT_ANCHORS = ((0, (0, 0, 4)), (64, (30, 20, 140)), (128, (180, 40, 150)), (192, (250, 140, 30)), (255, (255, 250, 190)))
 
@@ -286,6 +292,49 @@ def check_true_peak(true_peak, stage, encoding, hr_rate, who="enhance_file"):
         stage = {'clip': 'clamp', 'ceiling': None, 'dither': None, 'seed': 0, 'report': False}
     limit = encoding_limit(encoding)
     return stage, {'rate': hr_rate, 'ceiling': limit if stage['ceiling'] is None else stage['ceiling'], 'limit': limit}
+
+
+def limiter_plan(rate, lookahead_ms=None, hold_ms=None):
+    """The look-ahead and the hold of the limiter for a clip at `rate`, host arithmetic only -> {'lookahead': A, 'hold': H} in
+    samples, round(ms * rate / 1000) each, A at least 1.  None: LIMITER_LOOKAHEAD_MS, LIMITER_HOLD_MS.  A value that needs more
+    than LIMITER_MAX_LOOKAHEAD / LIMITER_MAX_HOLD samples is a ValueError that names the largest ms allowed at that rate."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 < rate < float('inf'):
+        raise ValueError("limiter_plan: the rate must be a number > 0, got %r" % (rate,))
+    plan = {}
+    for key, name, ms, default, cap in (('lookahead', 'lookahead_ms', lookahead_ms, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_LOOKAHEAD),
+                                        ('hold', 'hold_ms', hold_ms, LIMITER_HOLD_MS, LIMITER_MAX_HOLD)):
+        if ms is None:
+            ms = default
+        if isinstance(ms, bool) or not isinstance(ms, (int, float)) or not 0.0 <= ms < float('inf'):
+            raise ValueError("limiter_plan: %s must be a finite number >= 0, got %r" % (name, ms))
+        n = int(round(ms * rate / 1000.0))
+        if n > cap:
+            raise ValueError("limiter_plan: %s %g is %d samples at %g Hz, more than %d: at most %g ms at that rate"
+                             % (name, ms, n, rate, cap, cap * 1000.0 / rate))
+        plan[key] = max(n, 1) if key == 'lookahead' else n
+    return plan
+
+
+def check_limiter(limiter, lookahead_ms, hold_ms, stage, encoding, hr_rate, who="enhance_file"):
+    """Validates the limiter option -> None (off), or {'lookahead', 'hold' (limiter_plan), 'lookahead_ms', 'hold_ms' (as given)}.
+    `limiter`: a bool.  It is an option of clip='guard' (`stage`: check_output_options' result), whose ceiling it holds the crests
+    under and whose one gain removes what is left; `lookahead_ms` and `hold_ms` are options of the option.  The caller switches the
+    true-peak measurement on with it (check_true_peak(True, ...)): the limiter's envelope is the true-peak one."""
+    if not isinstance(limiter, bool):
+        raise ValueError("%s: limiter must be a bool, got %r" % (who, limiter))
+    if not limiter:
+        if lookahead_ms is not None or hold_ms is not None:
+            raise ValueError("%s: limiter_lookahead_ms / limiter_hold_ms are options of limiter=True; limiter is False" % who)
+        return None
+    if stage is None or stage['clip'] != 'guard':
+        raise ValueError("%s: limiter is an option of clip='guard' (it holds the crests under the guard's ceiling and the guard's one "
+                         "gain removes what is left); clip is %r" % (who, 'clamp' if stage is None else stage['clip']))
+    check_encoding(encoding, who)
+    try:
+        plan = limiter_plan(hr_rate, lookahead_ms, hold_ms)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e))
+    return dict(plan, lookahead_ms=lookahead_ms, hold_ms=hold_ms)
 
 
 def spectrogram_lut():

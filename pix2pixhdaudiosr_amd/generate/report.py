@@ -6,6 +6,7 @@ METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr
 METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
 METRICS_COLUMNS_LOUDNESS = ("lufs_in", "lufs_out", "loudness_gain_db")                  # --loudness
 METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                         # --true_peak
+METRICS_COLUMNS_LIMITER = ("limiter_reduction_db", "limited_samples")                   # --limiter
 
 
 def _mean(values):
@@ -17,7 +18,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False, true_peak=False):
+def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -31,10 +32,12 @@ def _columns(extended, peaks, loudness=False, true_peak=False):
                  (lambda r, c: r['loudness']['gain_db'], _mean)]
     if true_peak:
         cols += [(lambda r, c: r['output']['true_peak_dbtp'][c], _mean)]
+    if limiter:
+        cols += [(lambda r, c: r['output']['limiter']['max_reduction_db'], _mean), (lambda r, c: r['output']['limiter']['limited_samples'], _mean)]
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -44,8 +47,13 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     'loudness' and a row ends with the columns of METRICS_COLUMNS_LOUDNESS -- the file's integrated loudness going in and as
     written, in LUFS, and the gain between the generated and the written clip in dB; plain means again.  `true_peak`: the records' 'output'
     carries the true peak and a row ends with the column of METRICS_COLUMNS_TRUE_PEAK -- the channel's true peak in dBTP, like
-    peak_dbfs measured on the clip in front of the guard's gain; its plain mean."""
-    cols = _columns(extended, peaks, loudness, true_peak) if true_peak else _columns(extended, peaks, loudness)
+    peak_dbfs measured on the clip in front of the guard's gain; its plain mean.  `limiter`: the records' 'output' carries 'limiter'
+    and a row ends with the columns of METRICS_COLUMNS_LIMITER -- the file's largest reduction in dB and its number of reduced samples;
+    plain means."""
+    if limiter:
+        cols = _columns(extended, peaks, loudness, true_peak, limiter)
+    else:
+        cols = _columns(extended, peaks, loudness, true_peak) if true_peak else _columns(extended, peaks, loudness)
     rows = [(r['path'], c, r['out_frames']) + tuple(value(r, c) for value, _ in cols)
             for r in records for c in range(len(r['metrics_ext' if extended else 'metrics'] or ()))]
     if rows:
@@ -53,12 +61,15 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
-                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ()))
+                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
+                   + (METRICS_COLUMNS_LIMITER if limiter else ()))
         extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
+        if limiter:
+            extra['limiter'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -91,3 +102,8 @@ def _print_loudness(name, l):
 def _print_unwritten(name, available, written):
     if written < available:
         print('%s: %d of %d channels enhanced and written (--channels all writes every channel)' % (name, written, available))
+
+
+def _print_limiter(l, frames):
+    print('limiter: %+.2f dB at most, %.1f %% of the samples, true peak in %+.2f dBTP'
+          % (l['max_reduction_db'], 100.0 * l['limited_samples'] / max(frames, 1), l['input_true_peak_dbtp']))

@@ -5,9 +5,9 @@ import struct
 
 import torch
 
-from .ops import (_loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients, loudness, pcm_decode, pcm_encode,
-                  segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_loudness, check_lowband, check_output_options,
+from .ops import (_limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+                  limiter_apply, limiter_envelope, loudness, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
+from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_limiter, check_loudness, check_lowband, check_output_options,
                     check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -248,16 +248,20 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
         back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
         which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
         one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only.  `true_peak`: the
         true-peak option (check_true_peak; it comes with a stage): the true-peak kernel runs behind the peak kernel, on the same
-        clip, clip 'guard' takes its gain from it, and its figures come back likewise."""
+        clip, clip 'guard' takes its gain from it, and its figures come back likewise.  `limiter`: the limiter option
+        (_limiter_option; it comes with a stage and the true-peak option): the limiter runs in front of the peak kernel, everything
+        behind it sees the limited clip, and its figures come back likewise."""
         w = sr.contiguous()
         extra = {} if true_peak is None else {'true_peak': true_peak}
+        if limiter is not None:
+            extra['limiter'] = limiter
         dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **extra)
         host, stats = self._fetch(dev, packed, picture, **(extra if loudness is None else dict(extra, loudness=loudness)))
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
@@ -265,12 +269,18 @@ class SuperResolver:
             self._save(path_out, host, sr.shape[0], encoding)
         return output
 
-    def _encode(self, w, wanted, encoding, stage, true_peak=None):
+    def _encode(self, w, wanted, encoding, stage, true_peak=None, limiter=None):
         """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None).
         `true_peak`: None, or the true-peak option, which gains 'packed' (the packed true-peak buffer on the device); the guard's
-        gain is then the true-peak kernel's."""
+        gain is then the true-peak kernel's.  `limiter`: None, or the limiter option, which gains 'packed' (12 bytes on the device:
+        the curve's statistics, then the true peak the clip came with); the two launches of the family "limiter" run first and the
+        peak kernels, the guard's gain and the encoder see the limited clip."""
         if stage is None:
             return pcm_encode(w, encoding), None
+        if limiter is not None:
+            packed = limiter['packed'] = torch.empty((12,), dtype=torch.uint8, device=w.device)
+            r, _ = limiter_envelope(w, limiter['rate'], limiter['ceiling'], peak_out=packed[8:].view(torch.float32))
+            w, _, _ = limiter_apply(w, r, limiter, stats_out=packed[:8], want_g=False)
         (_, _, _, gain), packed = _pcm_peaks_packed(w, encoding, stage['ceiling'], "enhance_file")
         if true_peak is not None:
             (_, gain), true_peak['packed'] = _true_peaks_packed(w, true_peak['rate'], true_peak['ceiling'], "enhance_file")
@@ -278,13 +288,19 @@ class SuperResolver:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None):
+    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
         -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
         copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
         (the two gate results, a device tensor) is copied and replaced likewise; `true_peak`: None, or a dict whose 'packed' (the
-        packed true-peak buffer) is, into a pinned slot of its own."""
+        packed true-peak buffer) is, into a pinned slot of its own; `limiter`: None, or a dict whose 'packed' (the limiter's 12
+        bytes) is, into another."""
         host = stats = None
+        if limiter is not None:
+            n = limiter['packed'].numel()
+            pin = self._pinned('limiter', n)[:n]
+            pin.copy_(limiter['packed'], non_blocking=True)
+            limiter['packed'] = pin
         if true_peak is not None:
             n = true_peak['packed'].numel()
             pin = self._pinned('true_peak', n)[:n]
@@ -312,10 +328,11 @@ class SuperResolver:
         return host, stats
 
     @staticmethod
-    def _output(stats, C, stage, path_out, encoding, true_peak=None):
+    def _output(stats, C, stage, path_out, encoding, true_peak=None, limiter=None):
         """The fetched peak buffer of a C-channel clip -> the result's 'output'; ClipError where clip 'error' finds a clipped sample.
         `true_peak`: None, or the true-peak option with its fetched 'packed': the output gains 'true_peak' and 'true_peak_dbtp', its
-        'gain' is the true-peak kernel's, and clip 'error' also refuses a true peak above the encoding's limit."""
+        'gain' is the true-peak kernel's, and clip 'error' also refuses a true peak above the encoding's limit.  `limiter`: None, or
+        the limiter option with its fetched 'packed': the output gains 'limiter', and every other figure is the limited clip's."""
         peak, over, nonfinite, gain = (v.tolist() for v in _peak_views(stats, C))
         if true_peak is not None:
             tpeak, gain = (v.tolist() for v in _true_peak_views(true_peak['packed'], C))
@@ -330,7 +347,24 @@ class SuperResolver:
             raise ClipError("%s: %d samples would clip in %s (peak %+.2f dBFS); nothing was written -- clip='guard' scales "
                             "the file down, encoding='float32' keeps the samples"
                             % (path_out, sum(over), encoding, max(output['peak_dbfs'])))
+        if limiter is not None:
+            gmin, count = _limiter_stats_views(limiter['packed'][:8])
+            output['limiter'] = {'lookahead': limiter['lookahead'], 'hold': limiter['hold'], 'max_reduction_db': _dbfs(float(gmin[0])),
+                                 'limited_samples': int(count[0]) & 0xFFFFFFFF,
+                                 'input_true_peak_dbtp': _dbfs(float(limiter['packed'][8:12].view(torch.float32)[0]))}
         return output
+
+    @staticmethod
+    def _limiter_option(limiter, lookahead_ms, hold_ms, true_peak, stage, encoding, hr_rate, who):
+        """check_limiter and check_true_peak for enhance_file / enhance_folder -> (stage, tp, lim): the limiter switches the
+        true-peak measurement on, and takes its rate and ceiling from it."""
+        lim = check_limiter(limiter, lookahead_ms, hold_ms, stage, encoding, hr_rate, who)
+        stage, tp = check_true_peak(true_peak, stage, encoding, hr_rate, who)
+        if lim is not None:
+            if tp is None:
+                stage, tp = check_true_peak(True, stage, encoding, hr_rate, who)
+            lim = {'lookahead': lim['lookahead'], 'hold': lim['hold'], 'rate': tp['rate'], 'ceiling': tp['ceiling']}
+        return stage, tp, lim
 
     def _save(self, path_out, host, channels, encoding):
         from ..data import wavio
@@ -385,10 +419,12 @@ class SuperResolver:
                 'momentary_max': float(res_out[1]) + gain_db,
                 'target': {'report': None, 'input': level_in, 'target': loud['target']}[loud['mode']]}
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None):
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
+                         lim=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
         7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
-        `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak)."""
+        `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak).  `lim`: None,
+    or the limiter option (_limiter_option)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -424,6 +460,8 @@ class SuperResolver:
             extra = {} if measure is None else {'loudness': measure}
             if tp is not None:
                 extra['true_peak'] = dict(tp)                              # (one file's: it takes the file's buffers)
+            if lim is not None:
+                extra['limiter'] = dict(lim)
             output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
         if picture is not None:
@@ -438,7 +476,8 @@ class SuperResolver:
 
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
-                     spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False):
+                     spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
+                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -484,12 +523,26 @@ class SuperResolver:
         unscaled clip like 'peak'.  clip 'guard' then takes its gain from the true peak: `ceiling_dbfs` is read as dBTP (None: the
         encoding's limit) and 'gain' reports it; clip 'error' also refuses a file whose samples fit but whose true peak exceeds the
         encoding's limit; 'clamp' only reports.  One launch of the family "truepeak" per file; the figures come back with the payload
-        behind the same synchronisation."""
+        behind the same synchronisation.
+        `limiter` (opt-in, a bool; an option of clip='guard'): a look-ahead true-peak limiter (csrc/limiter.hip) in front of the
+        guard.  Where a few crests stand over `ceiling_dbfs`, the guard alone scales the whole file down by the excess; the limiter
+        turns only the crests down -- one gain curve for all channels, the smoothed minimum of what every sample and the oversampled
+        crests next to it need, looking `limiter_lookahead_ms` ahead (None: 5 ms) and held for `limiter_hold_ms` (None: 20 ms;
+        plans.limiter_plan) -- and the loudness just reached stays.  It switches the true-peak measurement on as `true_peak` does.
+        The guard's one gain then runs on the limited clip and removes what is left, normally a rounding.  Two launches of the family
+        "limiter" per file, in front of the peak kernels; the figures come back with the payload behind the same synchronisation.
+        'output' gains 'limiter': {'lookahead', 'hold' (samples), 'max_reduction_db' (the curve's lowest point, <= 0),
+        'limited_samples' (samples with a gain under 1), 'input_true_peak_dbtp' (the true peak in front of the limiter)}; its 'peak',
+        'true_peak' and 'clipped' are then those of the limited clip and its 'gain' the guard's residual gain.  'sr' and the metrics
+        stay the clip in front of the output stage.  Anything but clip='guard' with it is a ValueError before the file is opened."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
-        stage, tp = check_true_peak(true_peak, stage, encoding, self.opt.hr_sampling_rate)
+        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
+                                              self.opt.hr_sampling_rate, "enhance_file")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db)
         extra = {} if tp is None else {'tp': tp}
+        if lim is not None:
+            extra['lim'] = lim
         if loud is None:
             res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
         else:
@@ -515,7 +568,7 @@ class SuperResolver:
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
-                       true_peak=False):
+                       true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -531,14 +584,18 @@ class SuperResolver:
         reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written.
         `loudness`, `loudness_max_gain_db`: enhance_file's, per file (every file is measured and normalised on its own); a record
         then gains 'loudness' (as enhance_file returns it; None for a skipped file).  `true_peak`: enhance_file's, per file; a
-        record's 'output' then carries the true-peak figures."""
+        record's 'output' then carries the true-peak figures.  `limiter`, `limiter_lookahead_ms`, `limiter_hold_ms`: enhance_file's,
+        per file; a record's 'output' then carries 'limiter'."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
-        stage, tp = check_true_peak(true_peak, stage, encoding, self.opt.hr_sampling_rate, "enhance_folder")
+        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
+                                              self.opt.hr_sampling_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db)
         extra = {} if loud is None else {'loud': loud}
         if tp is not None:
             extra['tp'] = tp
+        if lim is not None:
+            extra['lim'] = lim
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,

@@ -36,6 +36,12 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             true_peak=True, clip='guard' in one process, the runs interleaved: milliseconds per file, median and spread of --reps,
             and p2phd_truepeak beside p2phd_pcm_peak alone, by events, on the clip of the last run; log in --truepeak_log
 
+  limiter   (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, brought to a loudness target that
+            leaves its true peak 4 dB over a -1 dBTP ceiling: without any option, with the guard alone and with limiter=True in one
+            process, the runs interleaved: milliseconds per file, median and spread of --reps; the loudness of the two written
+            files, the residual overshoot (the limited clip's true peak over the ceiling in front of the guard's residual gain),
+            and the two kernels beside p2phd_truepeak alone, by events, on the clip of the last run; log in --limiter_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -46,6 +52,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py spectrogram [--spectrogram_log profiles/time_generate_spectrogram.log]
         python tools/time_generate.py loudness [--loudness_log profiles/time_generate_loudness.log]
         python tools/time_generate.py truepeak [--truepeak_log profiles/time_generate_truepeak.log]
+        python tools/time_generate.py limiter [--limiter_log profiles/time_generate_limiter.log]
 """
 import argparse
 import os
@@ -408,6 +415,99 @@ def run_truepeak(seconds, reps, log):
         f.write(text)
 
 
+def run_limiter(seconds, reps, log):
+    """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
+    guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
+    measure; then the limiter's two kernels and the true-peak kernel alone on the same clip."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import (SuperResolver, limiter_apply, limiter_envelope, limiter_plan, loudness, loudness_channel_weights,
+                                               true_peaks, truepeak_plan)
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x.cpu() + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float()[None]      # as the true-peak run's original
+    sr = SuperResolver(model, opt, overlap=0.25)
+    rate = int(opt.hr_sampling_rate)
+    plan, lplan = truepeak_plan(rate), limiter_plan(rate)
+    ceiling_db = -1.0
+    lines = ["# tools/time_generate.py limiter: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz with a full-band original, file to file, untrained weights, %d interleaved repeats" % (seconds, reps),
+             "# true-peak plan: factor %d, %d taps per phase, beta %g; limiter plan: look-ahead %d, hold %d samples; ceiling %+g dBTP"
+             % (plan['factor'], plan['taps_per_phase'], plan['beta'], lplan['lookahead'], lplan['hold'], ceiling_db)]
+
+    def written_loudness(path):
+        y, _ = wavio.load(path)
+        return float(loudness(y.cuda().contiguous(), rate, loudness_channel_weights(y.shape[0]))[0][0])
+
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, hr, rate)
+        torch.manual_seed(99)
+        first = sr.enhance_file(src, None, loudness='report', true_peak=True)
+        target = min(0.0, first['loudness']['measured'] + (ceiling_db + 4.0) - max(first['output']['true_peak_dbtp']))
+        lines.append("the generated clip: %.3f LUFS, true peak %+.3f dBTP; loudness target %.3f LUFS"
+                     % (first['loudness']['measured'], max(first['output']['true_peak_dbtp']), target))
+        stage = dict(loudness=target, clip='guard', ceiling_dbfs=ceiling_db)
+        variants = (("no output option      ", {}), ("loudness, guard alone ", dict(stage, true_peak=True)), ("loudness, limiter     ", dict(stage, limiter=True)))
+        results, levels = [], []
+        for _, kw in variants:                                     # warm-up: capture, pinned buffers, page cache; one noise seed
+            sr.enhance_file(src, out, **kw)
+            torch.manual_seed(99)
+            results.append(sr.enhance_file(src, out, **kw))
+            levels.append(written_loudness(out))
+        torch.cuda.synchronize()
+        ts = [[] for _ in variants]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(variants):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(variants, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        lines.append("the limiter costs %.3f ms per file over the guard alone (difference of the medians), %.2f %% of the file without an output option"
+                     % (_median(ts[2]) - _median(ts[1]), 100.0 * (_median(ts[2]) - _median(ts[1])) / _median(ts[0])))
+        og, ol = results[1]['output'], results[2]['output']
+        lim = ol['limiter']
+        lines.append("guard alone:  true peak %+.3f dBTP, gain %.6f; written %.3f LUFS (target %.3f)" % (og['true_peak_dbtp'][0], og['gain'], levels[1], target))
+        lines.append("limiter:      true peak in %+.3f dBTP, %+.3f dB at most, %d of %d samples (%.1f %%); limited clip %+.5f dBTP: residual overshoot "
+                     "%+.5f dB, residual gain %.7f; written %.3f LUFS: %.3f dB above the guard's"
+                     % (lim['input_true_peak_dbtp'], lim['max_reduction_db'], lim['limited_samples'], n, 100.0 * lim['limited_samples'] / n,
+                        ol['true_peak_dbtp'][0], ol['true_peak_dbtp'][0] - ceiling_db, ol['gain'], levels[2], levels[2] - levels[1]))
+        # the kernels alone, by events, on the clip of the last run behind the loudness gain (one row)
+        clip = results[2]['sr'].contiguous()
+        ceiling = 10.0 ** (ceiling_db / 20.0)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        k_env, k_app, k_true = [], [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            r, _ = limiter_envelope(clip, rate, ceiling)
+            ev[1].record()
+            limiter_apply(clip, r, lplan, want_g=False)
+            ev[2].record()
+            true_peaks(clip, rate)
+            ev[3].record()
+            torch.cuda.synchronize()
+            k_env.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_app.append(ev[1].elapsed_time(ev[2]) * 1e3)
+            k_true.append(ev[2].elapsed_time(ev[3]) * 1e3)
+        L = clip.shape[-1]
+        fmas = L * (lplan['lookahead'] + 1)
+        lines.append("kernels alone (events, median of %d, each with the allocation of its results in front): p2phd_limiter_envelope %.1f us, "
+                     "p2phd_limiter_apply %.1f us (%d samples, %.0f M fma in the curve where no tile is skipped: %.2f Gfma/s), p2phd_truepeak %.1f us"
+                     % (reps, _median(k_env[2:]), _median(k_app[2:]), L, fmas * 1e-6, fmas / _median(k_app[2:]) * 1e-3, _median(k_true[2:])))
+        lines.append("runs: envelope %s; apply %s; truepeak %s" % tuple(" ".join("%.1f" % v for v in k[2:]) for k in (k_env, k_app, k_true)))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def _run_variants(seconds, reps, log, mode, variants):
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data.audio_dataset import lr_round_trip
@@ -495,7 +595,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter"])
     ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
@@ -503,6 +603,7 @@ def main():
     ap.add_argument("--spectrogram_log", default=os.path.join(ROOT, "profiles", "time_generate_spectrogram.log"))
     ap.add_argument("--loudness_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness.log"))
     ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
+    ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
@@ -519,6 +620,8 @@ def main():
         return run_loudness(a.seconds, a.reps, a.loudness_log)
     if a.mode == "truepeak":
         return run_truepeak(a.seconds, a.reps, a.truepeak_log)
+    if a.mode == "limiter":
+        return run_limiter(a.seconds, a.reps, a.limiter_log)
     if a.mode is not None:
         return run_mode(a.mode, a.seconds, a.reps)
     lines = ["# tools/time_generate.py: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, %g s synthetic clip at 48 kHz" % a.seconds]
