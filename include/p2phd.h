@@ -91,7 +91,7 @@ int p2phd_probe_read(float* ms_out, int cap);
  * cross-fading stitch of whole-file generation, csrc/stitch.hip), "pcm" (the PCM decode, encode, peak report and extended encode of its file
  * ends, csrc/pcm.hip), "metrics_rows" (the per-row metrics, csrc/metrics.hip), "xover" (the time-domain crossover of whole-file
  * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip), "loudness" (the
- * BS.1770 hop energies and the gate of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
+ * BS.1770 hop energies, the gate and the loudness range of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
  * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
  * csrc/limiter.hip).
  * family == NULL with reset != 0 clears all.
@@ -340,7 +340,7 @@ int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const flo
 
 /* ------------------------------------------------------------------------------------------
  * Loudness of whole-file generation after ITU-R BS.1770-4 / EBU R 128, csrc/loudness.hip.  Launch family "loudness" (a
- * p2phd_loudness_hops that launches and every p2phd_loudness_gate count 1 each: 2 per measured clip).
+ * p2phd_loudness_hops that launches and every p2phd_loudness_gate count 1 each: 2 per measured clip; the loudness range, below, 2 more).
  *
  * p2phd_loudness_coeffs_fill (HOST only, no device, as p2phd_xover_taps_fill): the K-weighting filter pair for `rate`, float64:
  *   out10 = b0 b1 b2 a1 a2 of the high shelf, then of the high-pass; y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2].
@@ -370,11 +370,33 @@ int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const flo
  *     gain     T = *target_dev where target_dev != NULL (a device float64, e.g. another clip's res4: no host round trip), else
  *              `target`; gain[0] = (float) 10^(clamp(T - I, -max_gain_db, +max_gain_db) / 20), float64 arithmetic rounded once;
  *              gain[0] = 1 where T or I is not finite (target NaN: no target).  max_gain_db finite and >= 0.
+ *
+ * Loudness range after EBU Tech 3342 and the maximum short-term loudness, from the same z (1 launch each, family "loudness"):
+ * p2phd_loudness_short_term: z [channels][J] (device) -> p [NS] float64 (device), NS = max(J - 29, 0): the power of the 3 s block of
+ *   hops b .. b + 29 (100 ms step).  S[c] = ((z[c][b] + z[c][b+1]) + ..) + z[c][b+29], left to right, every block on its own (no
+ *   running sum: the bits of p[b] do not depend on b); P[c] = S[c] / (30.0 hop); p[b] = sum_c weights[c] P[c], c ascending from 0;
+ *   p[b] = p[b] (g g), g = (double) gain_dev[0], where gain_dev != NULL (one f32 on the DEVICE, read by the kernel: a gate's gain,
+ *   no host round trip).  Nothing contracted; one writer per element.  weights, channels, rate, J: as p2phd_loudness_gate.
+ *   NS = 0: P2PHD_OK, nothing launched.
+ * p2phd_loudness_range: p [NS] (device, read only; non-negative or NaN) -> res8 (8 float64, device), one workgroup; always launches.
+ *     gating   A = {b : p[b] > 1.1724653045822981e-07} (-70 LUFS as a power);  m = mean_A p (fixed-order sum);
+ *              B = {b in A : p[b] > 0.01 m} (20 LU under the mean).  A power equal to a threshold is out, and so is a NaN.
+ *     ranks    n = |B|, q = B's powers ascending; k_lo = ((n - 1) 10 + 50) / 100, k_hi = ((n - 1) 95 + 50) / 100 (integer division):
+ *              the round((n - 1) PRC / 100 + 1) of the Tech 3342 reference code, zero-based.  q[k] is the exact order statistic
+ *              (MSB-first radix select on the bit patterns, integer counts in LDS): no sort buffer, no workspace, no float atomics.
+ *     res8     {LRA = lufs(q[k_hi]) - lufs(q[k_lo]), lufs(q[k_lo]), lufs(q[k_hi]), lufs(0.01 m) (-inf with A empty), n,
+ *              lufs(max_b p[b]) (fmax from 0: a NaN never wins; -inf with NS = 0), q[k_lo], q[k_hi]}, lufs(x) = -0.691 + 10 log10(x).
+ *              n = 0: {0, -inf, -inf, .., 0, .., 0, 0}.  Any p[b] NaN: LRA, both levels and both powers are NaN (a broken clip shows);
+ *              the threshold, n and the maximum are those of the other blocks.  +inf is a value like any other: it makes m infinite,
+ *              so nothing is over 0.01 m and n = 0.  The same bits on every run and on every stream.
  * ---------------------------------------------------------------------------------------- */
 int p2phd_loudness_coeffs_fill(double rate, double* out10);
 int p2phd_loudness_hops(const float* planar, int64_t frames, int channels, int64_t ld, int rate, double* z, void* stream);
 int p2phd_loudness_gate(const double* z, int64_t J, int channels, int rate, const float* weights, double target, const double* target_dev,
                         double max_gain_db, double* res4, float* gain, void* stream);
+int p2phd_loudness_short_term(const double* z, int64_t J, int channels, int rate, const float* weights, const float* gain_dev, double* p,
+                              void* stream);
+int p2phd_loudness_range(const double* p, int64_t NS, double* res8, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * True peak of whole-file generation after ITU-R BS.1770-4 Annex 2 (oversample, take the largest magnitude), csrc/truepeak.hip.

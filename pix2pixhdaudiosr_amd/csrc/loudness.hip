@@ -1,10 +1,21 @@
-// Whole-file generation (pix2pixhdaudiosr_amd/generate/): integrated loudness after ITU-R BS.1770-4 / EBU R 128 and the gain
-// that brings a clip to a wanted level.  Launch family "loudness".
+// Whole-file generation (pix2pixhdaudiosr_amd/generate/): integrated loudness after ITU-R BS.1770-4 / EBU R 128, the gain
+// that brings a clip to a wanted level, and the loudness range after EBU Tech 3342.  Launch family "loudness".
 //
 //   coeffs_fill (host) the K-weighting pair for a sampling rate, float64: the high shelf, then the high-pass (b0 b1 b2 a1 a2 each).
 //   hops        z[c][j] = sum over hop j (rate / 10 samples, 100 ms) of y^2, y = row c through shelf and high-pass.
 //   gate        400 ms blocks of four hops at 75 % overlap, the channel weights, the absolute gate at -70 LUFS, the relative gate
 //               10 LU under the ungated mean -> {I, the loudest block, the relative threshold, blocks kept} and the gain to a target.
+//   short_term  p[b] = the power of the 3 s block of 30 hops that starts at hop b (100 ms step), the channels weighted, times the
+//               square of a gain read from device memory where one is given.  Every block sums its own 30 hops left to right: no
+//               running sum, so p[b] does not depend on where the block lies.
+//   range       p -> the loudness range: the absolute gate at -70 LUFS, the relative gate 20 LU under the mean of what passed, the
+//               10th and 95th percentile of what is left -> {LRA, both levels, the threshold, blocks kept, the loudest block, both
+//               selected powers}.  The percentiles are exact order statistics: a power behind the gates is positive, so it orders
+//               as its bit pattern read as an unsigned integer, and an MSB-first radix select -- eight passes over p, a 256-bin
+//               histogram of integer counts in LDS per wanted rank, a scan, a descent into the bin that holds the rank -- ends with
+//               the 64 bits of the wanted element.  Counts are integers (no float atomics), so the order in which the adds land does
+//               not show; the gates are re-evaluated per element from two thresholds, so there is no compacted copy and no
+//               workspace, and p is only read.
 //
 // The recursion made parallel: zero-state warm-up.  The work item of hop j starts from zero state at sample (j - 2) hop -- 200 ms in
 // front of its hop -- or at sample 0 where that is nearer (hops 0 .. 2 are the sequential recursion itself), runs both biquads
@@ -25,6 +36,7 @@
 // workspace, nothing that depends on scheduling: z[c][j] has one writer.
 #include "common.h"
 #include "convplan.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
@@ -204,6 +216,133 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(const doubl
   }
 }
 
+constexpr int kShortHops = 30;                // hops of a short-term block: 3 s
+constexpr int kShortThreads = 256;
+constexpr int kShortMaxGrid = 2048;           // workgroups at most; the blocks beyond are walked with the grid's stride
+constexpr int kRadixBins = 256;               // 8 bits per pass, eight passes over the 64 bits of a double
+constexpr double kAbsGatePower = 1.1724653045822981e-07;       // 10^((-70 + 0.691) / 10): the power of -70 LUFS
+static_assert(kRadixBins == kGateThreads, "the range kernel gives every thread one bin of the histogram");
+
+// grid-stride over the short-term blocks, one thread per block: p[b] = sum_c w[c] (z[c][b] + .. + z[c][b + 29]) / norm, times
+// g^2 where gain_dev is given.  Neighbouring threads read neighbouring hops, so every load of a wave is one contiguous run.
+__global__ __launch_bounds__(kShortThreads) void loudness_short_term_kernel(const double* __restrict__ z, long J, int C, double norm, GateWeights gw,
+                                                                            const float* __restrict__ gain_dev, double* __restrict__ p) {
+  const long NS = J - (kShortHops - 1);
+  double gg = 1.0;
+  if (gain_dev) { const double g = (double)gain_dev[0]; gg = g * g; }
+  for (long b = (long)blockIdx.x * kShortThreads + threadIdx.x; b < NS; b += (long)gridDim.x * kShortThreads) {
+    double acc = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double* zc = z + (long)c * J + b;
+      double S = zc[0] + zc[1];
+#pragma unroll
+      for (int i = 2; i < kShortHops; ++i) S = S + zc[i];
+      acc = acc + (double)gw.w[c] * (S / norm);
+    }
+    if (gain_dev) acc = acc * gg;
+    p[b] = acc;
+  }
+}
+
+// One workgroup of 256 threads.  Pass 0: the loudest block, whether a power is NaN, and the mean of the powers over the absolute
+// gate (thread t takes the blocks t, t + 256, .. in ascending order, the partial sums meet in gate_fold's tree).  Then the radix
+// select: in pass d every thread walks its blocks again, keeps those behind both gates whose top 8 d bits are the prefix found so
+// far and counts the next 8 bits into the histogram -- one histogram while both ranks share a prefix, two from where they part.
+// An inclusive scan over the 256 bins (eight doubling steps in LDS) gives every thread the ranks its bin holds; the one thread
+// whose bin holds the wanted rank publishes the bin and the rank within it.  Pass 0 also counts n, from which both ranks come.
+__global__ __launch_bounds__(kGateThreads) void loudness_range_kernel(const double* __restrict__ p, long NS, double* __restrict__ res8) {
+  __shared__ double s_sum[kGateThreads];
+  __shared__ long s_cnt[kGateThreads];
+  __shared__ double s_max[kGateThreads];
+  __shared__ unsigned long long s_hist[2][kRadixBins];
+  __shared__ unsigned long long s_scan[2][2][kRadixBins];
+  __shared__ unsigned long long s_pick[2][2];                     // per rank: the bin, the rank within the bin
+  const int tid = threadIdx.x;
+  const double ninf = -__builtin_inf(), nan = __builtin_nan("");
+  double sum = 0.0, top = 0.0;
+  long cnt = 0, bad = 0;
+  for (long b = tid; b < NS; b += kGateThreads) {
+    const double v = p[b];
+    top = fmax(top, v);                                           // (a NaN never wins)
+    if (v != v) ++bad;
+    if (v > kAbsGatePower) { sum = sum + v; ++cnt; }
+  }
+  s_max[tid] = top;
+  gate_fold(s_sum, s_cnt, sum, cnt);
+  for (int o = kGateThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) s_max[tid] = fmax(s_max[tid], s_max[tid + o]);
+    __syncthreads();
+  }
+  top = s_max[0];
+  double none = 0.0;
+  gate_fold(s_sum, s_cnt, none, bad);
+  // a power at or under a threshold is gated out; nothing is over +inf
+  const double rel = cnt > 0 ? 0.01 * (sum / (double)cnt) : __builtin_inf();
+
+  unsigned long long pre[2] = {0ull, 0ull}, rank[2] = {0ull, 0ull}, n = 0ull;
+  for (int d = 0; d < 8; ++d) {
+    const int shift = 56 - 8 * d;
+    const bool split = pre[0] != pre[1];
+    s_hist[0][tid] = 0ull; s_hist[1][tid] = 0ull;
+    __syncthreads();
+    for (long b = tid; b < NS; b += kGateThreads) {
+      const double v = p[b];
+      if (v > kAbsGatePower && v > rel) {
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+        const unsigned long long head = d == 0 ? 0ull : bits >> (shift + 8);
+        const int bin = (int)((bits >> shift) & (kRadixBins - 1));
+        if (head == pre[0]) atomicAdd(&s_hist[0][bin], 1ull);
+        if (split && head == pre[1]) atomicAdd(&s_hist[1][bin], 1ull);
+      }
+    }
+    __syncthreads();
+    const unsigned long long h0 = s_hist[0][tid], h1 = split ? s_hist[1][tid] : h0;
+    s_scan[0][0][tid] = h0; s_scan[1][0][tid] = h1;
+    __syncthreads();
+    int cur = 0;
+    for (int o = 1; o < kRadixBins; o <<= 1) {                     // eight steps: the result is in buffer 0 again
+      const unsigned long long a0 = s_scan[0][cur][tid] + (tid >= o ? s_scan[0][cur][tid - o] : 0ull);
+      const unsigned long long a1 = s_scan[1][cur][tid] + (tid >= o ? s_scan[1][cur][tid - o] : 0ull);
+      s_scan[0][cur ^ 1][tid] = a0; s_scan[1][cur ^ 1][tid] = a1;
+      __syncthreads();
+      cur ^= 1;
+    }
+    if (d == 0) {
+      n = s_scan[0][cur][kRadixBins - 1];
+      if (n > 0) { rank[0] = ((n - 1) * 10 + 50) / 100; rank[1] = ((n - 1) * 95 + 50) / 100; }
+    }
+    if (n == 0 || bad > 0) break;                                 // (the same for every thread)
+    const unsigned long long i0 = s_scan[0][cur][tid], i1 = s_scan[1][cur][tid];
+    if (h0 > 0 && i0 - h0 <= rank[0] && rank[0] < i0) { s_pick[0][0] = (unsigned long long)tid; s_pick[0][1] = rank[0] - (i0 - h0); }
+    if (h1 > 0 && i1 - h1 <= rank[1] && rank[1] < i1) { s_pick[1][0] = (unsigned long long)tid; s_pick[1][1] = rank[1] - (i1 - h1); }
+    __syncthreads();
+    pre[0] = (pre[0] << 8) | s_pick[0][0]; rank[0] = s_pick[0][1];
+    pre[1] = (pre[1] << 8) | s_pick[1][0]; rank[1] = s_pick[1][1];
+  }
+  if (tid == 0) {
+    double lra = 0.0, low = ninf, high = ninf, qlo = 0.0, qhi = 0.0;
+    if (bad > 0) {
+      lra = low = high = qlo = qhi = nan;
+    } else if (n > 0) {
+      qlo = __longlong_as_double((long long)pre[0]); qhi = __longlong_as_double((long long)pre[1]);
+      low = lufs(qlo); high = lufs(qhi);
+      lra = high - low;
+    }
+    res8[0] = lra; res8[1] = low; res8[2] = high; res8[3] = cnt > 0 ? lufs(rel) : ninf;
+    res8[4] = (double)n; res8[5] = lufs(top); res8[6] = qlo; res8[7] = qhi;
+  }
+}
+
+// the checks the gate and the short-term entry share
+int gate_weights_fill(const char* who, int channels, const float* weights, GateWeights& gw) {
+  for (int c = 0; c < kMaxGateChannels; ++c) gw.w[c] = 0.0f;
+  for (int c = 0; c < channels; ++c) {
+    gw.w[c] = weights ? weights[c] : 1.0f;
+    P2PHD_REQUIRE(std::isfinite(gw.w[c]) && gw.w[c] >= 0.0f, "%s: weight %d must be finite and >= 0, got %g", who, c, (double)gw.w[c]);
+  }
+  return P2PHD_OK;
+}
+
 }  // namespace
 
 extern "C" int p2phd_loudness_coeffs_fill(double rate, double* out10) {
@@ -241,14 +380,41 @@ extern "C" int p2phd_loudness_gate(const double* z, int64_t J, int channels, int
                 (reinterpret_cast<uintptr_t>(res4) & 7) == 0 && (reinterpret_cast<uintptr_t>(gain) & 3) == 0,
                 "loudness_gate: a pointer is not aligned to its type");
   GateWeights gw;
-  for (int c = 0; c < kMaxGateChannels; ++c) gw.w[c] = 0.0f;
-  for (int c = 0; c < channels; ++c) {
-    gw.w[c] = weights ? weights[c] : 1.0f;
-    P2PHD_REQUIRE(std::isfinite(gw.w[c]) && gw.w[c] >= 0.0f, "loudness_gate: weight %d must be finite and >= 0, got %g", c, (double)gw.w[c]);
-  }
+  if (const int rc = gate_weights_fill("loudness_gate", channels, weights, gw)) return rc;
   // every call launches: res4 and gain are valid after it whatever J is
   hipLaunchKernelGGL(loudness_gate_kernel, dim3(1), dim3(kGateThreads), 0, (hipStream_t)stream, z, (long)J, channels, 4.0 * (double)(rate / 10), gw,
                      target, target_dev, max_gain_db, res4, gain);
   ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
   return p2phd::check_launch("loudness_gate");
+}
+
+extern "C" int p2phd_loudness_short_term(const double* z, int64_t J, int channels, int rate, const float* weights, const float* gain_dev, double* p,
+                                         void* stream) {
+  P2PHD_REQUIRE(J >= 0 && J <= (int64_t(1) << 40) && channels >= 1 && channels <= kMaxGateChannels,
+                "loudness_short_term: need J >= 0 and 1 <= channels <= %d (J %lld, channels %d)", kMaxGateChannels, (long long)J, channels);
+  P2PHD_REQUIRE(rate_ok((double)rate), "loudness_short_term: rate must be a multiple of 10 in [8000, 384000] Hz (a hop is rate / 10 samples), got %d",
+                rate);
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(z) & 7) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(gain_dev) & 3) == 0, "loudness_short_term: a pointer is not aligned to its type");
+  GateWeights gw;
+  if (const int rc = gate_weights_fill("loudness_short_term", channels, weights, gw)) return rc;
+  const int64_t NS = J - (kShortHops - 1);
+  if (NS <= 0) return P2PHD_OK;
+  P2PHD_REQUIRE(z && p, "loudness_short_term: null pointer");
+  const unsigned grid = (unsigned)std::min<int64_t>(p2phd::cdiv(NS, kShortThreads), kShortMaxGrid);
+  hipLaunchKernelGGL(loudness_short_term_kernel, dim3(grid), dim3(kShortThreads), 0, (hipStream_t)stream, z, (long)J, channels,
+                     (double)kShortHops * (double)(rate / 10), gw, gain_dev, p);
+  ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
+  return p2phd::check_launch("loudness_short_term");
+}
+
+extern "C" int p2phd_loudness_range(const double* p, int64_t NS, double* res8, void* stream) {
+  P2PHD_REQUIRE(NS >= 0 && NS <= (int64_t(1) << 40), "loudness_range: need 0 <= NS <= 2^40, got %lld", (long long)NS);
+  P2PHD_REQUIRE(res8 && (p || NS == 0), "loudness_range: null pointer");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(p) & 7) == 0 && (reinterpret_cast<uintptr_t>(res8) & 7) == 0,
+                "loudness_range: a pointer is not aligned to a double");
+  // every call launches: res8 is valid after it whatever NS is
+  hipLaunchKernelGGL(loudness_range_kernel, dim3(1), dim3(kGateThreads), 0, (hipStream_t)stream, p, (long)NS, res8);
+  ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
+  return p2phd::check_launch("loudness_range");
 }

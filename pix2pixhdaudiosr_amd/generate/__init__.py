@@ -38,7 +38,10 @@ on the device from the clips that are there at the end of enhance_file (`spectro
 `--loudness report|input|LUFS` (opt-in, csrc/loudness.hip) measures the integrated loudness after ITU-R BS.1770-4 / EBU R 128 of
 the input the generator was given and of the generated clip on the device -- the level the pipeline writes depends on the
 checkpoint's rates, the transform and the overlap -- and, with `input` or a target such as -23, multiplies the clip by the one
-gain that brings it there, in front of the output stage (`loudness_hops`, `loudness_gate`, `loudness`).
+gain that brings it there, in front of the output stage (`loudness_hops`, `loudness_gate`, `loudness`).  `--loudness_range`, an
+option of it, adds the other two programme descriptors of R 128 from the same hop energies: the loudness range after EBU Tech
+3342 of both clips and the maximum short-term (3 s) loudness of the generated one, as the loudness stage leaves it
+(`loudness_short_term`, `loudness_range`).
 
 `--true_peak` (opt-in, csrc/truepeak.hip) measures the true peak after ITU-R BS.1770-4 Annex 2 on the device -- the clip the
 encoder sees, oversampled to at least 192 kHz -- and reports it in dBTP; `--clip guard` then holds the true peak, not the sample
@@ -52,7 +55,7 @@ target stays there where the guard's one gain would give the excess away (`limit
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
-                  loudness_hops, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
+                  loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
 from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
@@ -60,6 +63,6 @@ from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MA
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
                     check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, limiter_plan, loudness_channel_weights, plan_folder,
                     segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
-from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_PEAKS,  # noqa: F401
+from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_LOUDNESS_RANGE, METRICS_COLUMNS_PEAKS,  # noqa: F401
                      METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

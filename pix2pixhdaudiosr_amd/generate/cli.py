@@ -12,7 +12,7 @@ import torch
 
 from .plans import (CLIP_MODES, LOUDNESS_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_lowband,
                     check_output_options, check_paths, check_spectrogram, spectro_bins)
-from .report import _print_limiter, _print_loudness, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .report import _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -85,9 +85,14 @@ def _loudness_args(a, hr_rate=None):
     if a.loudness is None:
         if a.loudness_max_gain_db is not None:
             raise ValueError("--loudness_max_gain_db is an option of --loudness")
+        if a.loudness_range:
+            raise ValueError("--loudness_range is an option of --loudness")
         return {}
-    check_loudness(a.loudness, 48000 if hr_rate is None else hr_rate, "generate", a.loudness_max_gain_db)
-    return dict(loudness=a.loudness, loudness_max_gain_db=a.loudness_max_gain_db)
+    check_loudness(a.loudness, 48000 if hr_rate is None else hr_rate, "generate", a.loudness_max_gain_db, a.loudness_range)
+    kw = dict(loudness=a.loudness, loudness_max_gain_db=a.loudness_max_gain_db)
+    if a.loudness_range:
+        kw['loudness_range'] = True
+    return kw
 
 
 def _spectrogram_args(a, folder_mode):
@@ -185,6 +190,11 @@ def _parser():
                          "loudness_gain_db) of --metrics_csv (default: off)")
     ap.add_argument("--loudness_max_gain_db", type=float, default=None, metavar="DB",
                     help="--loudness input|LUFS: the largest gain applied, either way (default 40)")
+    ap.add_argument("--loudness_range", action="store_true",
+                    help="--loudness: also measure the loudness range (EBU Tech 3342: 3 s blocks, the 10th to the 95th percentile behind "
+                         "gates at -70 LUFS and 20 LU under the mean) of both clips and the maximum short-term loudness of the generated "
+                         "one, as the loudness stage leaves it; one more line per file and three more columns (lra_in, lra_out, "
+                         "short_term_max) of --metrics_csv (default: off)")
     ap.add_argument("--true_peak", action="store_true",
                     help="also measure the true peak (ITU-R BS.1770-4 Annex 2: the written clip oversampled to at least 192 kHz) and "
                          "print it in dBTP with the peak line of every file; --clip guard then brings the true peak, not the sample "
@@ -285,6 +295,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 _print_spectrogram(r['spectrogram'])
             if r.get('loudness') is not None:
                 _print_loudness(r['path'], r['loudness'])
+                if 'range' in r['loudness']:
+                    _print_loudness_range(r['path'], r['loudness']['range'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -317,12 +329,16 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_spectrogram(res['spectrogram'])
         if res.get('loudness') is not None:
             _print_loudness(a.output, res['loudness'])
+            if 'range' in res['loudness']:
+                _print_loudness_range(a.output, res['loudness']['range'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
     if a.metrics_csv:
         extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
         if a.limiter:
             extra['limiter'] = True
+        if a.loudness_range:
+            extra['loudness_range'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -299,6 +299,54 @@ def loudness(waveform, rate, weights=None, target=None, target_dev=None, max_gai
     return loudness_gate(loudness_hops(waveform, rate), rate, weights, target, target_dev, max_gain_db, out)
 
 
+LOUDNESS_SHORT_TERM_HOPS = 30                                               # a short-term block: 3 s of 100 ms hops
+
+
+def loudness_short_term(z, rate, weights=None, gain_dev=None):
+    """z [C, J] float64 on the GPU (loudness_hops) -> p [max(J - 29, 0)] float64 on the GPU, nothing waited for: the power of every
+    3 s block of 30 hops at a 100 ms step, the channels weighted as in loudness_gate (p2phd_loudness_short_term).  `gain_dev`: None,
+    or a float32 tensor on the GPU whose first element the kernel reads (a loudness_gate's gain): the powers are then those of the
+    clip times that gain.  One launch of the family "loudness"; none for a clip under 3 s."""
+    rate = check_loudness_rate(rate, "loudness_short_term")
+    zz = _lib.require_gpu_tensor(z, "loudness_short_term: z", torch.float64)
+    if zz.dim() != 2 or not 1 <= zz.shape[0] <= LOUDNESS_MAX_CHANNELS:
+        raise ValueError("loudness_short_term: expected z [C, J] with 1 <= C <= %d, got shape %s" % (LOUDNESS_MAX_CHANNELS, tuple(zz.shape)))
+    C, J = zz.shape
+    wbuf = None
+    if weights is not None:
+        wbuf = (ctypes.c_float * C)(*[float(v) for v in weights]) if len(weights) == C else None
+        if wbuf is None:
+            raise ValueError("loudness_short_term: %d weights for %d channels" % (len(weights), C))
+    if gain_dev is not None:
+        gain_dev = _lib.require_gpu_tensor(gain_dev, "loudness_short_term: gain_dev", torch.float32)
+        if gain_dev.numel() < 1:
+            raise ValueError("loudness_short_term: gain_dev is empty")
+    p = torch.empty((max(J - (LOUDNESS_SHORT_TERM_HOPS - 1), 0),), dtype=torch.float64, device=zz.device)
+    _lib.check(_lib.lib().p2phd_loudness_short_term(_lib.ptr(zz), J, C, rate, wbuf, _lib.ptr(gain_dev), _lib.ptr(p), _lib.stream_ptr()),
+               "loudness_short_term")
+    return p
+
+
+def loudness_range(p, out=None):
+    """p [NS] float64 on the GPU (loudness_short_term) -> res8 [8] float64 on the GPU, nothing waited for: {the loudness range in LU
+    after EBU Tech 3342 (gates at -70 LUFS and 20 LU under the mean of what passed, the 10th to the 95th percentile of the rest), the
+    level of the low and of the high percentile in LUFS, the relative threshold, blocks behind both gates, the loudest block (the
+    maximum short-term loudness), the two selected powers} (p2phd_loudness_range).  No block: range 0, levels -inf; a NaN block:
+    range and levels NaN.  `out`: None, or a float64 tensor of 8 on the GPU that takes the result.  One launch of the family
+    "loudness", for every NS; `p` is only read."""
+    pp = _lib.require_gpu_tensor(p, "loudness_range: p", torch.float64)
+    if pp.dim() != 1:
+        raise ValueError("loudness_range: expected p [NS], got shape %s" % (tuple(pp.shape),))
+    if out is None:
+        out = torch.empty((8,), dtype=torch.float64, device=pp.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "loudness_range: out", torch.float64)
+        if out.numel() != 8:
+            raise ValueError("loudness_range: out must hold 8 float64, got %d" % out.numel())
+    _lib.check(_lib.lib().p2phd_loudness_range(_lib.ptr(pp), pp.numel(), _lib.ptr(out), _lib.stream_ptr()), "loudness_range")
+    return out
+
+
 _TRUEPEAK_TABLES = {}                                                       # (factor, taps per phase, beta, device) -> the table on the device
 
 

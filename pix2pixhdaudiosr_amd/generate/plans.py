@@ -241,14 +241,19 @@ def check_loudness_rate(rate, who):
     return int(rate)
 
 
-def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None):
+def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None, loudness_range=False):
     """Validates the loudness option for a file written at `hr_rate` -> None (off), or {'mode': 'report' | 'input' | 'target',
     'target': the level in LUFS (None unless a number was given), 'max_gain_db'}.  `loudness`: None, 'report' (measure only),
     'input' (the written clip as loud as the clip the generator was given) or a number in [-70, 0], the target in LUFS.
-    `max_gain_db`: None (LOUDNESS_MAX_GAIN_DB) or a finite level >= 0, an option of the option."""
+    `max_gain_db`: None (LOUDNESS_MAX_GAIN_DB) or a finite level >= 0, an option of the option.  `loudness_range`: a bool, an option
+    of the option too (also measure the loudness range and the maximum short-term loudness); the dict then gains 'range': True."""
+    if not isinstance(loudness_range, bool):
+        raise ValueError("%s: loudness_range must be a bool, got %r" % (who, loudness_range))
     if loudness is None:
         if max_gain_db is not None:
             raise ValueError("%s: loudness_max_gain_db is an option of loudness; loudness is None" % who)
+        if loudness_range:
+            raise ValueError("%s: loudness_range is an option of loudness; loudness is None" % who)
         return None
     if max_gain_db is None:
         max_gain_db = LOUDNESS_MAX_GAIN_DB
@@ -263,7 +268,10 @@ def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None):
             raise ValueError("%s: a loudness target must be a level in [-70, 0] LUFS, got %r" % (who, loudness))
         mode, target = 'target', float(loudness)
     check_loudness_rate(hr_rate, who)
-    return {'mode': mode, 'target': target, 'max_gain_db': float(max_gain_db)}
+    loud = {'mode': mode, 'target': target, 'max_gain_db': float(max_gain_db)}
+    if loudness_range:
+        loud['range'] = True
+    return loud
 
 
 def truepeak_plan(rate):

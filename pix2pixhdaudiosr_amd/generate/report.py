@@ -5,6 +5,7 @@ METRICS_COLUMNS = ("file", "channel", "frames", "mse", "snr_sr", "snr_lr", "lsd"
 METRICS_COLUMNS_EXT = METRICS_COLUMNS + ("lsd_lf", "lsd_hf", "ssnr_sr", "ssnr_lr")     # --metrics_ext
 METRICS_COLUMNS_PEAKS = ("peak_dbfs", "clipped", "gain")                                # --report_peaks
 METRICS_COLUMNS_LOUDNESS = ("lufs_in", "lufs_out", "loudness_gain_db")                  # --loudness
+METRICS_COLUMNS_LOUDNESS_RANGE = ("lra_in", "lra_out", "short_term_max")               # --loudness_range (behind the loudness columns)
 METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                         # --true_peak
 METRICS_COLUMNS_LIMITER = ("limiter_reduction_db", "limited_samples")                   # --limiter
 
@@ -18,7 +19,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False):
+def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -30,6 +31,9 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False):
     if loudness:
         cols += [(lambda r, c: r['loudness']['input'], _mean), (lambda r, c: r['loudness']['output'], _mean),
                  (lambda r, c: r['loudness']['gain_db'], _mean)]
+    if loudness_range:
+        cols += [(lambda r, c: r['loudness']['range']['input'], _mean), (lambda r, c: r['loudness']['range']['output'], _mean),
+                 (lambda r, c: r['loudness']['range']['short_term_max'], _mean)]
     if true_peak:
         cols += [(lambda r, c: r['output']['true_peak_dbtp'][c], _mean)]
     if limiter:
@@ -37,7 +41,7 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False):
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -49,8 +53,12 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     carries the true peak and a row ends with the column of METRICS_COLUMNS_TRUE_PEAK -- the channel's true peak in dBTP, like
     peak_dbfs measured on the clip in front of the guard's gain; its plain mean.  `limiter`: the records' 'output' carries 'limiter'
     and a row ends with the columns of METRICS_COLUMNS_LIMITER -- the file's largest reduction in dB and its number of reduced samples;
-    plain means."""
-    if limiter:
+    plain means.  `loudness_range`: the records' 'loudness' carries 'range' and the columns of METRICS_COLUMNS_LOUDNESS_RANGE stand
+    behind the loudness columns -- the file's loudness range going in and as the loudness stage leaves it, in LU, and its maximum
+    short-term loudness in LUFS; plain means (a file under 3 s counts with 0.0 and -inf)."""
+    if loudness_range:
+        cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range)
+    elif limiter:
         cols = _columns(extended, peaks, loudness, true_peak, limiter)
     else:
         cols = _columns(extended, peaks, loudness, true_peak) if true_peak else _columns(extended, peaks, loudness)
@@ -61,15 +69,18 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
-                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
+                   + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_LOUDNESS_RANGE if loudness_range else ())
+                   + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
                    + (METRICS_COLUMNS_LIMITER if limiter else ()))
         extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
         if limiter:
             extra['limiter'] = True
+        if loudness_range:
+            extra['loudness_range'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -97,6 +108,11 @@ def _print_peaks(name, o):
 
 def _print_loudness(name, l):
     print('%s: loudness input %+.2f LUFS, output %+.2f LUFS, gain %+.2f dB' % (name, l['input'], l['output'], l['gain_db']))
+
+
+def _print_loudness_range(name, r):
+    print('%s: loudness range input %.2f LU, output %.2f LU (%+.2f .. %+.2f LUFS), short-term max %+.2f LUFS'
+          % (name, r['input'], r['output'], r['low'], r['high'], r['short_term_max']))
 
 
 def _print_unwritten(name, available, written):

@@ -6,7 +6,7 @@ import struct
 import torch
 
 from .ops import (_limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, loudness, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
+                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
 from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_limiter, check_loudness, check_lowband, check_output_options,
                     check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
@@ -400,24 +400,38 @@ class SuperResolver:
     def _measure_loudness(self, loud, lr, sr):
         """The device work of the loudness option: the clip the generator was given and the generated clip through the hop and
         gate kernels (four launches of the family "loudness") -> {'packed': both gate results in one buffer of 80 bytes, 'gain':
-        the f32 on the device that brings `sr` to the wanted level (1 with 'report')}."""
+        the f32 on the device that brings `sr` to the wanted level (1 with 'report')}.  With loud['range'] the hop energies of
+        either clip also go through the short-term and the range kernel (at most four launches more; the generated clip's powers
+        take the gain from device memory, so the figures are those of the clip as this stage leaves it) and 'packed' holds their
+        two res8 behind the gate results, 208 bytes in all."""
         rate = int(self.opt.hr_sampling_rate)
         weights = loudness_channel_weights(sr.shape[0])
-        packed = torch.empty((80,), dtype=torch.uint8, device=sr.device)
-        res_in, _ = loudness(lr, rate, weights, out=packed[:40])
+        ranged = loud.get('range', False)
+        packed = torch.empty((208 if ranged else 80,), dtype=torch.uint8, device=sr.device)
+        z_in = loudness_hops(lr, rate)
+        res_in, _ = loudness_gate(z_in, rate, weights, out=packed[:40])
         wanted = {'report': {}, 'input': {'target_dev': res_in}, 'target': {'target': loud['target']}}[loud['mode']]
-        _, gain = loudness(sr, rate, weights, max_gain_db=loud['max_gain_db'], out=packed[40:], **wanted)
+        z_out = loudness_hops(sr, rate)
+        _, gain = loudness_gate(z_out, rate, weights, max_gain_db=loud['max_gain_db'], out=packed[40:80], **wanted)
+        if ranged:
+            loudness_range(loudness_short_term(z_in, rate, weights), out=packed[80:144].view(torch.float64))
+            loudness_range(loudness_short_term(z_out, rate, weights, gain_dev=gain), out=packed[144:208].view(torch.float64))
         return {'packed': packed, 'gain': gain}
 
     @staticmethod
     def _loudness_result(loud, measure):
         """The fetched measurement -> the result's 'loudness'."""
-        (res_in, _), (res_out, gain) = _loudness_views(measure['packed'][:40]), _loudness_views(measure['packed'][40:])
+        (res_in, _), (res_out, gain) = _loudness_views(measure['packed'][:40]), _loudness_views(measure['packed'][40:80])
         level_in, measured = float(res_in[0]), float(res_out[0])
         gain_db = 0.0 if loud['mode'] == 'report' else 20.0 * math.log10(float(gain[0]))
-        return {'input': level_in, 'measured': measured, 'gain_db': gain_db, 'output': measured + gain_db,
-                'momentary_max': float(res_out[1]) + gain_db,
-                'target': {'report': None, 'input': level_in, 'target': loud['target']}[loud['mode']]}
+        result = {'input': level_in, 'measured': measured, 'gain_db': gain_db, 'output': measured + gain_db,
+                  'momentary_max': float(res_out[1]) + gain_db,
+                  'target': {'report': None, 'input': level_in, 'target': loud['target']}[loud['mode']]}
+        if loud.get('range', False):
+            r_in, r_out = (measure['packed'][a:a + 64].view(torch.float64).tolist() for a in (80, 144))
+            result['range'] = {'input': r_in[0], 'output': r_out[0], 'low': r_out[1], 'high': r_out[2], 'threshold': r_out[3],
+                               'blocks': int(r_out[4]), 'short_term_max': r_out[5]}
+        return result
 
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
                          lim=None):
@@ -477,7 +491,7 @@ class SuperResolver:
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
-                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None):
+                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -516,6 +530,16 @@ class SuperResolver:
         output stage scales or clamps it), 'momentary_max' (the loudest 400 ms block of the written clip), 'target' (the level
         aimed at, None with 'report')}, in LUFS; -inf for a clip shorter than 400 ms or a silent one, which is left as it is.  A
         high rate that is not a multiple of 10 in [8000, 384000] Hz is a ValueError before the file is opened.
+        `loudness_range` (opt-in, a bool; an option of `loudness`): also measure the loudness range after EBU Tech 3342 of both
+        clips and the maximum short-term loudness of the generated one, from the hop energies the loudness measurement already has:
+        3 s blocks at a 100 ms step, gates at -70 LUFS and 20 LU under the mean of what passed, the 10th to the 95th percentile of
+        what is left (exact order statistics, found on the device).  At most four launches more; the figures travel in the same
+        buffer behind the same synchronisation.  'loudness' gains 'range': {'input', 'output' (LU), 'low', 'high' (the two
+        percentile levels), 'threshold' (the relative gate), 'blocks' (behind both gates), 'short_term_max'}; 'low' to
+        'short_term_max' are the generated clip's, in LUFS, and all of them include the loudness gain: they describe the clip as
+        the loudness stage leaves it, like 'output'.  The limiter and the clip guard act behind this point, so a limited file's
+        range can be smaller than the figure, just as its integrated loudness can.  A clip under 3 s has range 0.0 and levels
+        -inf; a clip with a NaN block has range NaN.  Without `loudness` it is a ValueError before the file is opened.
         `true_peak` (opt-in, a bool): also measure the true peak after ITU-R BS.1770-4 Annex 2 (csrc/truepeak.hip: the clip
         oversampled to at least 192 kHz, plans.truepeak_plan) where the peak is measured -- on the clip the encoder sees, behind the
         loudness gain and the crossover.  The result's 'output' -- which then exists also with every other output option at its
@@ -539,7 +563,7 @@ class SuperResolver:
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_file")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
-        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db)
+        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range)
         extra = {} if tp is None else {'tp': tp}
         if lim is not None:
             extra['lim'] = lim
@@ -568,7 +592,7 @@ class SuperResolver:
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
-                       true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None):
+                       true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -582,7 +606,7 @@ class SuperResolver:
         <relative path>.png (enhance_file's `spectrogram`, `spectrogram_channel`, `spectrogram_opts`); a record then gains
         'spectrogram' (as enhance_file returns it; None for a skipped file).  A file without channel `spectrogram_channel` is
         reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written.
-        `loudness`, `loudness_max_gain_db`: enhance_file's, per file (every file is measured and normalised on its own); a record
+        `loudness`, `loudness_max_gain_db`, `loudness_range`: enhance_file's, per file (every file is measured and normalised on its own); a record
         then gains 'loudness' (as enhance_file returns it; None for a skipped file).  `true_peak`: enhance_file's, per file; a
         record's 'output' then carries the true-peak figures.  `limiter`, `limiter_lookahead_ms`, `limiter_hold_ms`: enhance_file's,
         per file; a record's 'output' then carries 'limiter'."""
@@ -590,7 +614,7 @@ class SuperResolver:
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
-        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db)
+        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range)
         extra = {} if loud is None else {'loud': loud}
         if tp is not None:
             extra['tp'] = tp

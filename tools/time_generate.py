@@ -30,7 +30,9 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
 
   loudness  (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, without the option and with
             loudness='report' and loudness=-23 in one process, the runs interleaved: milliseconds per file, median and spread of
-            --reps, and the two kernels alone (hop energies, gate) by events on the clips of the last run; log in --loudness_log
+            --reps, and the two kernels alone (hop energies, gate) by events on the clips of the last run; log in --loudness_log.
+            With --loudness_range the third variant is loudness='report', loudness_range=True, and the short-term and the range
+            kernel are timed alone beside the gate, on the clip's hop energies and on an hour's worth; log in --loudness_range_log
 
   truepeak  (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, without the option and with
             true_peak=True, clip='guard' in one process, the runs interleaved: milliseconds per file, median and spread of --reps,
@@ -51,6 +53,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py crossover [--crossover_log profiles/time_generate_crossover.log]
         python tools/time_generate.py spectrogram [--spectrogram_log profiles/time_generate_spectrogram.log]
         python tools/time_generate.py loudness [--loudness_log profiles/time_generate_loudness.log]
+        python tools/time_generate.py loudness --loudness_range [--loudness_range_log profiles/time_generate_loudness_range.log]
         python tools/time_generate.py truepeak [--truepeak_log profiles/time_generate_truepeak.log]
         python tools/time_generate.py limiter [--limiter_log profiles/time_generate_limiter.log]
 """
@@ -281,9 +284,33 @@ def run_spectrogram(seconds, reps, log):
         f.write(text)
 
 
-def run_loudness(seconds, reps, log):
+def _loudness_range_kernels(torch, z, rate, reps, what):
+    """The short-term and the range kernel alone on hop energies z [C, J], and the gate kernel beside them, by events -> a line."""
+    from pix2pixhdaudiosr_amd.generate import loudness_gate, loudness_range, loudness_short_term
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    k_short, k_range, k_gate = [], [], []
+    for _ in range(reps + 2):
+        ev[0].record()
+        p = loudness_short_term(z, rate)
+        ev[1].record()
+        loudness_range(p)
+        ev[2].record()
+        loudness_gate(z, rate)
+        ev[3].record()
+        torch.cuda.synchronize()
+        k_short.append(ev[0].elapsed_time(ev[1]) * 1e3)
+        k_range.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        k_gate.append(ev[2].elapsed_time(ev[3]) * 1e3)
+    return ("%s (events, median of %d): loudness_short_term %.1f us, loudness_range %.1f us (%d blocks: nine passes of one workgroup), "
+            "loudness_gate beside them %.1f us (%d blocks: two passes); runs: short-term %s; range %s; gate %s"
+            % (what, reps, _median(k_short[2:]), _median(k_range[2:]), p.numel(), _median(k_gate[2:]), max(z.shape[1] - 3, 0),
+               " ".join("%.1f" % v for v in k_short[2:]), " ".join("%.1f" % v for v in k_range[2:]), " ".join("%.1f" % v for v in k_gate[2:])))
+
+
+def run_loudness(seconds, reps, log, ranged=False):
     """enhance_file, file to file, without and with the loudness option: the same object, the same input, interleaved; then the two
-    kernels alone."""
+    kernels alone.  `ranged`: the variants are off, loudness='report' and the same with loudness_range=True, and the kernels alone
+    are the short-term and the range kernel, on the clip's hop energies and on an hour's worth (36 000 blocks)."""
     import tempfile
     torch, model, opt, x = _setup(seconds)
     from pix2pixhdaudiosr_amd.data import wavio
@@ -301,6 +328,9 @@ def run_loudness(seconds, reps, log):
         src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
         wavio.save(src, hr, rate)
         variants = (("loudness off   ", {}), ("loudness report", dict(loudness='report')), ("loudness -23   ", dict(loudness=-23.0)))
+        if ranged:
+            lines[0] = lines[0].replace("time_generate.py loudness:", "time_generate.py loudness --loudness_range:")
+            variants = variants[:2] + (("report + range ", dict(loudness='report', loudness_range=True)),)
         for _, kw in variants:                                     # warm-up: capture, pinned buffers, page cache
             res = sr.enhance_file(src, out, **kw)
             sr.enhance_file(src, out, **kw)
@@ -318,7 +348,12 @@ def run_loudness(seconds, reps, log):
         for k in (1, 2):
             lines.append("%s costs %.3f ms per file (difference of the medians), %.2f %% of the file without it"
                          % (variants[k][0].strip(), _median(ts[k]) - _median(ts[0]), 100.0 * (_median(ts[k]) - _median(ts[0])) / _median(ts[0])))
-        lines.append("the last file: %s" % ", ".join("%s %s" % (k, ("%+.3f" % v) if v is not None else "none") for k, v in sorted(res['loudness'].items())))
+        lines.append("the last file: %s" % ", ".join("%s %s" % (k, ("%+.3f" % v) if v is not None else "none") for k, v in sorted(res['loudness'].items())
+                                                     if k != 'range'))
+        if ranged:
+            lines.append("the range costs %.3f ms per file over loudness report (difference of the medians), %.2f %% of the file without either"
+                         % (_median(ts[2]) - _median(ts[1]), 100.0 * (_median(ts[2]) - _median(ts[1])) / _median(ts[0])))
+            lines.append("the last file's range: %s" % ", ".join("%s %+.3f" % kv for kv in sorted(res['loudness']['range'].items())))
         # the two kernels alone, by events, on the generated clip of the last run (one row of %d samples)
         clip = res['sr'].contiguous()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -340,6 +375,10 @@ def run_loudness(seconds, reps, log):
                      % (reps, us, z.shape[1], hop, -(-z.shape[1] // 64), steps, us * 1e3 / steps, clip.shape[-1] / rate * 1e3 / us,
                         _median(k_gate[2:]), max(z.shape[1] - 3, 0)))
         lines.append("runs: loudness_hops %s; loudness_gate %s" % (" ".join("%.1f" % v for v in k_hops[2:]), " ".join("%.1f" % v for v in k_gate[2:])))
+        if ranged:
+            lines.append(_loudness_range_kernels(torch, z, rate, reps, "range kernels alone, the clip"))
+            hour = torch.rand((1, 36029), dtype=torch.float64, device=z.device, generator=torch.Generator(z.device).manual_seed(9)) * hop
+            lines.append(_loudness_range_kernels(torch, hour, rate, reps, "range kernels alone, an hour of hops"))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
@@ -602,6 +641,8 @@ def main():
     ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
     ap.add_argument("--spectrogram_log", default=os.path.join(ROOT, "profiles", "time_generate_spectrogram.log"))
     ap.add_argument("--loudness_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness.log"))
+    ap.add_argument("--loudness_range", action="store_true", help="loudness mode: time loudness_range=True against loudness='report' and off")
+    ap.add_argument("--loudness_range_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness_range.log"))
     ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
     ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
@@ -617,6 +658,8 @@ def main():
     if a.mode == "spectrogram":
         return run_spectrogram(a.seconds, a.reps, a.spectrogram_log)
     if a.mode == "loudness":
+        if a.loudness_range:
+            return run_loudness(a.seconds, a.reps, a.loudness_range_log, ranged=True)
         return run_loudness(a.seconds, a.reps, a.loudness_log)
     if a.mode == "truepeak":
         return run_truepeak(a.seconds, a.reps, a.truepeak_log)
