@@ -295,6 +295,7 @@ extern "C" int p2phd_spectro_decode(const float* log_spectro, const float* norm_
   P2PHD_REQUIRE(alpha != 0.5f, "spectro_decode: alpha = 0.5 makes the explicit encoding singular");
   if (B == 0) return P2PHD_OK;
   P2PHD_REQUIRE(log_spectro && norm_min_max && spec, "spectro_decode: null pointer");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode: grid too large");
   dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
   hipLaunchKernelGGL(decode_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, log_spectro, norm_min_max, spec, (int)F, (int)M, alpha, min_value);
   return p2phd::check_launch("spectro_decode");
