@@ -340,7 +340,8 @@ int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const flo
 
 /* ------------------------------------------------------------------------------------------
  * Loudness of whole-file generation after ITU-R BS.1770-4 / EBU R 128, csrc/loudness.hip.  Launch family "loudness" (a
- * p2phd_loudness_hops that launches and every p2phd_loudness_gate count 1 each: 2 per measured clip; the loudness range, below, 2 more).
+ * p2phd_loudness_hops that launches and every p2phd_loudness_gate count 1 each: 2 per measured clip; the loudness range, below, 2 more; the album loudness,
+ * below them, 1 per clip and 1 per folder more).
  *
  * p2phd_loudness_coeffs_fill (HOST only, no device, as p2phd_xover_taps_fill): the K-weighting filter pair for `rate`, float64:
  *   out10 = b0 b1 b2 a1 a2 of the high shelf, then of the high-pass; y[n] = b0 x[n] + b1 x[n-1] + b2 x[n-2] - a1 y[n-1] - a2 y[n-2].
@@ -389,6 +390,19 @@ int p2phd_specimg_render(const float* db, int64_t R, int64_t F, int K, const flo
  *              n = 0: {0, -inf, -inf, .., 0, .., 0, 0}.  Any p[b] NaN: LRA, both levels and both powers are NaN (a broken clip shows);
  *              the threshold, n and the maximum are those of the other blocks.  +inf is a value like any other: it makes m infinite,
  *              so nothing is over 0.01 m and n = 0.  The same bits on every run and on every stream.
+ *
+ * Album loudness (EBU R 128: a folder as one programme), from the same z (1 launch each, family "loudness"):
+ * p2phd_loudness_blocks: z [channels][J] (device) -> p [NB] float64 (device), NB = max(J - 3, 0): p[b] of p2phd_loudness_gate's
+ *   "blocks" line, the very expression (one device function serves both), so p[b] holds the bits the gate computes in place.  `p`
+ *   is where the caller points: a slice of a buffer that takes the blocks of every file of a folder, one file behind the other -- a
+ *   block never spans two files.  Grid-parallel, one writer per element, nothing contracted; elements outside [0, NB) are not
+ *   touched.  weights, channels, rate, J: as p2phd_loudness_gate.  J < 4: P2PHD_OK, nothing launched.
+ * p2phd_loudness_gate_blocks: p [NB] (device, read only) -> res4 and gain as p2phd_loudness_gate leaves them ("gating", "res4",
+ *   "gain" above, with l[b] = -0.691 + 10 log10(p[b])); always launches.  One workgroup of 256: thread t sums the blocks t, t + 256,
+ *   .. in ascending order and the partial sums meet in the gate's tree -- both entries run one body -- so on the p of one file it
+ *   returns the bits p2phd_loudness_gate returns on that file's z, and on a folder's p the sums have one fixed order.  No atomics,
+ *   no workspace, the same bits on every run and on every stream.  The price of the one workgroup: the time grows with NB / 256
+ *   dependent steps of one compute unit (two passes over p) where a grid-wide fold would use the whole device.
  * ---------------------------------------------------------------------------------------- */
 int p2phd_loudness_coeffs_fill(double rate, double* out10);
 int p2phd_loudness_hops(const float* planar, int64_t frames, int channels, int64_t ld, int rate, double* z, void* stream);
@@ -397,6 +411,9 @@ int p2phd_loudness_gate(const double* z, int64_t J, int channels, int rate, cons
 int p2phd_loudness_short_term(const double* z, int64_t J, int channels, int rate, const float* weights, const float* gain_dev, double* p,
                               void* stream);
 int p2phd_loudness_range(const double* p, int64_t NS, double* res8, void* stream);
+int p2phd_loudness_blocks(const double* z, int64_t J, int channels, int rate, const float* weights, double* p, void* stream);
+int p2phd_loudness_gate_blocks(const double* p, int64_t NB, double target, const double* target_dev, double max_gain_db, double* res4,
+                               float* gain, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * True peak of whole-file generation after ITU-R BS.1770-4 Annex 2 (oversample, take the largest magnitude), csrc/truepeak.hip.

@@ -66,6 +66,8 @@ SIGNATURES = {
     "p2phd_loudness_gate": (_i32, [_vp, _i64, _i32, _i32, _vp, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
     "p2phd_loudness_short_term": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "p2phd_loudness_range": (_i32, [_vp, _i64, _vp, _vp]),
+    "p2phd_loudness_blocks": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "p2phd_loudness_gate_blocks": (_i32, [_vp, _i64, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
     "p2phd_truepeak_taps_fill": (_i32, [_i32, _i32, C.c_double, _vp]),
     "p2phd_truepeak": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "p2phd_truepeak_tile_len": (_i32, []),

@@ -5,6 +5,11 @@
 //   hops        z[c][j] = sum over hop j (rate / 10 samples, 100 ms) of y^2, y = row c through shelf and high-pass.
 //   gate        400 ms blocks of four hops at 75 % overlap, the channel weights, the absolute gate at -70 LUFS, the relative gate
 //               10 LU under the ungated mean -> {I, the loudest block, the relative threshold, blocks kept} and the gain to a target.
+//   blocks      p[b] = the channel-weighted power of 400 ms block b of one clip, the gate's own expression, written where the caller
+//               points: a slice of a buffer that holds the blocks of every file of a folder.
+//   gate_blocks the gate over such a buffer -- the folder as one programme (EBU R 128 album loudness).  The same body as `gate`,
+//               so for the blocks of one file it returns the bits `gate` returns for that file's z.  One workgroup on purpose: a
+//               grid-wide sum would need another summation order.
 //   short_term  p[b] = the power of the 3 s block of 30 hops that starts at hop b (100 ms step), the channels weighted, times the
 //               square of a gain read from device memory where one is given.  Every block sums its own 30 hops left to right: no
 //               running sum, so p[b] does not depend on where the block lies.
@@ -174,21 +179,32 @@ __device__ __forceinline__ void gate_fold(double* s_sum, long* s_cnt, double& su
   sum = s_sum[0]; cnt = s_cnt[0];
 }
 
-// One workgroup.  Thread t takes the blocks t, t + 256, .. in ascending order, the partial sums meet in a fixed tree.  A block
-// whose level is NaN passes both gates (the comparisons are "not at or below"), so a NaN in z reaches I instead of being gated out.
-__global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(const double* __restrict__ z, long J, int C, double norm, GateWeights gw,
-                                                                     double target, const double* __restrict__ target_dev, double max_gain_db,
-                                                                     double* __restrict__ res4, float* __restrict__ gain) {
+// The two places a 400 ms block's power comes from: the hop energies of one clip (computed where it is needed), or a buffer of
+// powers that loudness_blocks_kernel has filled.  block_power is the same function in both, so the bits are too.
+struct HopBlocks {
+  const double* __restrict__ z; long J; int C; double norm; const GateWeights& gw;
+  __device__ __forceinline__ double operator()(long b) const { return block_power(z, J, C, gw, norm, b); }
+};
+struct StoredBlocks {
+  const double* __restrict__ p;
+  __device__ __forceinline__ double operator()(long b) const { return p[b]; }
+};
+
+// The gate, whichever way the powers come.  One workgroup.  Thread t takes the blocks t, t + 256, .. in ascending order, the
+// partial sums meet in a fixed tree.  A block whose level is NaN passes both gates (the comparisons are "not at or below"), so a
+// NaN in z reaches I instead of being gated out.
+template <class Blocks>
+__device__ __forceinline__ void gate_body(const Blocks& power, long NB, double target, const double* __restrict__ target_dev, double max_gain_db,
+                                          double* __restrict__ res4, float* __restrict__ gain) {
   __shared__ double s_sum[kGateThreads];
   __shared__ long s_cnt[kGateThreads];
   __shared__ double s_max[kGateThreads];
   const int tid = threadIdx.x;
-  const long NB = J > 3 ? J - 3 : 0;
   const double ninf = -__builtin_inf();
   double sum = 0.0, top = ninf;
   long cnt = 0;
   for (long b = tid; b < NB; b += kGateThreads) {
-    const double p = block_power(z, J, C, gw, norm, b), l = lufs(p);
+    const double p = power(b), l = lufs(p);
     top = fmax(top, l);                                           // (a NaN never wins)
     if (!(l <= -70.0)) { sum = sum + p; ++cnt; }
   }
@@ -202,7 +218,7 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(const doubl
   const double gamma = cnt > 0 ? lufs(sum / (double)cnt) - 10.0 : ninf;
   sum = 0.0; cnt = 0;
   for (long b = tid; b < NB; b += kGateThreads) {
-    const double p = block_power(z, J, C, gw, norm, b), l = lufs(p);
+    const double p = power(b), l = lufs(p);
     if (!(l <= -70.0) && !(l <= gamma)) { sum = sum + p; ++cnt; }
   }
   gate_fold(s_sum, s_cnt, sum, cnt);
@@ -214,6 +230,31 @@ __global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(const doubl
     if (isfinite(T) && isfinite(I)) g = (float)pow(10.0, fmin(fmax(T - I, -max_gain_db), max_gain_db) / 20.0);
     gain[0] = g;
   }
+}
+
+__global__ __launch_bounds__(kGateThreads) void loudness_gate_kernel(const double* __restrict__ z, long J, int C, double norm, GateWeights gw,
+                                                                     double target, const double* __restrict__ target_dev, double max_gain_db,
+                                                                     double* __restrict__ res4, float* __restrict__ gain) {
+  gate_body(HopBlocks{z, J, C, norm, gw}, J > 3 ? J - 3 : 0, target, target_dev, max_gain_db, res4, gain);
+}
+
+// the gate over powers that are already there: the blocks of a whole folder, every file's behind the other's
+__global__ __launch_bounds__(kGateThreads) void loudness_gate_blocks_kernel(const double* __restrict__ p, long NB, double target,
+                                                                            const double* __restrict__ target_dev, double max_gain_db,
+                                                                            double* __restrict__ res4, float* __restrict__ gain) {
+  gate_body(StoredBlocks{p}, NB, target, target_dev, max_gain_db, res4, gain);
+}
+
+constexpr int kBlocksThreads = 256;
+constexpr int kBlocksMaxGrid = 2048;          // workgroups at most; the blocks beyond are walked with the grid's stride
+
+// grid-stride over the 400 ms blocks of one clip, one thread per block: p[b] = block_power(b), the gate's own expression.
+// Neighbouring threads read neighbouring hops, so every load of a wave is one contiguous run; p[b] has one writer.
+__global__ __launch_bounds__(kBlocksThreads) void loudness_blocks_kernel(const double* __restrict__ z, long J, int C, double norm, GateWeights gw,
+                                                                         double* __restrict__ p) {
+  const long NB = J - 3;
+  for (long b = (long)blockIdx.x * kBlocksThreads + threadIdx.x; b < NB; b += (long)gridDim.x * kBlocksThreads)
+    p[b] = block_power(z, J, C, gw, norm, b);
 }
 
 constexpr int kShortHops = 30;                // hops of a short-term block: 3 s
@@ -417,4 +458,37 @@ extern "C" int p2phd_loudness_range(const double* p, int64_t NS, double* res8, v
   hipLaunchKernelGGL(loudness_range_kernel, dim3(1), dim3(kGateThreads), 0, (hipStream_t)stream, p, (long)NS, res8);
   ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
   return p2phd::check_launch("loudness_range");
+}
+
+extern "C" int p2phd_loudness_blocks(const double* z, int64_t J, int channels, int rate, const float* weights, double* p, void* stream) {
+  P2PHD_REQUIRE(J >= 0 && J <= (int64_t(1) << 40) && channels >= 1 && channels <= kMaxGateChannels,
+                "loudness_blocks: need J >= 0 and 1 <= channels <= %d (J %lld, channels %d)", kMaxGateChannels, (long long)J, channels);
+  P2PHD_REQUIRE(rate_ok((double)rate), "loudness_blocks: rate must be a multiple of 10 in [8000, 384000] Hz (a hop is rate / 10 samples), got %d", rate);
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(z) & 7) == 0 && (reinterpret_cast<uintptr_t>(p) & 7) == 0,
+                "loudness_blocks: a pointer is not aligned to a double");
+  GateWeights gw;
+  if (const int rc = gate_weights_fill("loudness_blocks", channels, weights, gw)) return rc;
+  const int64_t NB = J - 3;
+  if (NB <= 0) return P2PHD_OK;
+  P2PHD_REQUIRE(z && p, "loudness_blocks: null pointer");
+  const unsigned grid = (unsigned)std::min<int64_t>(p2phd::cdiv(NB, kBlocksThreads), kBlocksMaxGrid);
+  hipLaunchKernelGGL(loudness_blocks_kernel, dim3(grid), dim3(kBlocksThreads), 0, (hipStream_t)stream, z, (long)J, channels,
+                     4.0 * (double)(rate / 10), gw, p);
+  ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
+  return p2phd::check_launch("loudness_blocks");
+}
+
+extern "C" int p2phd_loudness_gate_blocks(const double* p, int64_t NB, double target, const double* target_dev, double max_gain_db, double* res4,
+                                          float* gain, void* stream) {
+  P2PHD_REQUIRE(NB >= 0 && NB <= (int64_t(1) << 40), "loudness_gate_blocks: need 0 <= NB <= 2^40, got %lld", (long long)NB);
+  P2PHD_REQUIRE(max_gain_db >= 0.0 && std::isfinite(max_gain_db), "loudness_gate_blocks: max_gain_db must be finite and >= 0, got %g", max_gain_db);
+  P2PHD_REQUIRE(res4 && gain && (p || NB == 0), "loudness_gate_blocks: null pointer");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(p) & 7) == 0 && (reinterpret_cast<uintptr_t>(target_dev) & 7) == 0 &&
+                (reinterpret_cast<uintptr_t>(res4) & 7) == 0 && (reinterpret_cast<uintptr_t>(gain) & 3) == 0,
+                "loudness_gate_blocks: a pointer is not aligned to its type");
+  // every call launches: res4 and gain are valid after it whatever NB is
+  hipLaunchKernelGGL(loudness_gate_blocks_kernel, dim3(1), dim3(kGateThreads), 0, (hipStream_t)stream, p, (long)NB, target, target_dev, max_gain_db,
+                     res4, gain);
+  ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
+  return p2phd::check_launch("loudness_gate_blocks");
 }

@@ -41,7 +41,9 @@ checkpoint's rates, the transform and the overlap -- and, with `input` or a targ
 gain that brings it there, in front of the output stage (`loudness_hops`, `loudness_gate`, `loudness`).  `--loudness_range`, an
 option of it, adds the other two programme descriptors of R 128 from the same hop energies: the loudness range after EBU Tech
 3342 of both clips and the maximum short-term (3 s) loudness of the generated one, as the loudness stage leaves it
-(`loudness_short_term`, `loudness_range`).
+(`loudness_short_term`, `loudness_range`).  `--loudness_scope folder`, another option of it and of folder mode, treats the folder as
+one programme, as EBU R 128 normalises an album: both gates over the 400 ms blocks of all files, one loudness gain and one guard
+gain for all of them, every file measured before the first is written (generate/album.py; `loudness_blocks`, `loudness_gate_blocks`).
 
 `--true_peak` (opt-in, csrc/truepeak.hip) measures the true peak after ITU-R BS.1770-4 Annex 2 on the device -- the clip the
 encoder sees, oversampled to at least 192 kHz -- and reports it in dBTP; `--clip guard` then holds the true peak, not the sample
@@ -54,13 +56,13 @@ target stays there where the guard's one gain would give the excess away (`limit
 `limiter_window`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
-from .ops import (PCM_FORMATS, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_coefficients, loudness_gate,  # noqa: F401
-                  loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
+from .ops import (PCM_FORMATS, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
+                  loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
-from .plans import (CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
-                    LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOWBANDS,
+from .plans import (ALBUM_CACHE_BYTES, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
+                    LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
-                    check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_lowband, check_output_options, check_paths,
+                    check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,
                     check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, limiter_plan, loudness_channel_weights, plan_folder,
                     segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
 from .report import (METRICS_COLUMNS, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_LOUDNESS_RANGE, METRICS_COLUMNS_PEAKS,  # noqa: F401

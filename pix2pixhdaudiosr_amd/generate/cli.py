@@ -10,9 +10,9 @@ from types import SimpleNamespace
 
 import torch
 
-from .plans import (CLIP_MODES, LOUDNESS_MODES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_lowband,
+from .plans import (CLIP_MODES, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_paths, check_spectrogram, spectro_bins)
-from .report import _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .report import _print_album, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -79,19 +79,25 @@ def _loudness_arg(text):
         raise argparse.ArgumentTypeError("expected report, input or a target in LUFS such as -23, got %r" % text)
 
 
-def _loudness_args(a, hr_rate=None):
+def _loudness_args(a, hr_rate=None, folder_mode=False):
     """The loudness options of the command line -> the keyword arguments of enhance_file / enhance_folder ({} without --loudness);
-    ValueError for a bad one.  `hr_rate`: None as long as the options file has not been read (the rate is then checked later)."""
+    ValueError for a bad one.  `hr_rate`: None as long as the options file has not been read (the rate is then checked later).
+    `folder_mode`: whether --input is a folder, which --loudness_scope folder needs."""
     if a.loudness is None:
+        if a.loudness_scope != 'file':
+            raise ValueError("--loudness_scope folder is an option of --loudness")
         if a.loudness_max_gain_db is not None:
             raise ValueError("--loudness_max_gain_db is an option of --loudness")
         if a.loudness_range:
             raise ValueError("--loudness_range is an option of --loudness")
         return {}
-    check_loudness(a.loudness, 48000 if hr_rate is None else hr_rate, "generate", a.loudness_max_gain_db, a.loudness_range)
+    loud = check_loudness(a.loudness, 48000 if hr_rate is None else hr_rate, "generate", a.loudness_max_gain_db, a.loudness_range)
     kw = dict(loudness=a.loudness, loudness_max_gain_db=a.loudness_max_gain_db)
     if a.loudness_range:
         kw['loudness_range'] = True
+    if a.loudness_scope != 'file':
+        check_loudness_scope(a.loudness_scope, loud, "generate", folder_mode, a.limiter, a.spectrogram)
+        kw['loudness_scope'] = a.loudness_scope
     return kw
 
 
@@ -195,6 +201,12 @@ def _parser():
                          "gates at -70 LUFS and 20 LU under the mean) of both clips and the maximum short-term loudness of the generated "
                          "one, as the loudness stage leaves it; one more line per file and three more columns (lra_in, lra_out, "
                          "short_term_max) of --metrics_csv (default: off)")
+    ap.add_argument("--loudness_scope", default="file", choices=LOUDNESS_SCOPES,
+                    help="--loudness with a folder as --input: file (default) measures and normalises every file on its own; folder "
+                         "treats the folder as one programme, as EBU R 128 normalises an album -- one loudness over the blocks of all "
+                         "files, one gain (and with --clip guard one guard gain) for all of them, so the level differences between the "
+                         "files survive; one `album:` line more and one `album` row of --metrics_csv; not with --limiter, "
+                         "--loudness_range or --spectrogram")
     ap.add_argument("--true_peak", action="store_true",
                     help="also measure the true peak (ITU-R BS.1770-4 Annex 2: the written clip oversampled to at least 192 kHz) and "
                          "print it in dBTP with the peak line of every file; --clip guard then brings the true peak, not the sample "
@@ -228,7 +240,7 @@ def main(argv=None):
         folder_mode = check_paths(a.input, a.output)
         out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
         picture = _spectrogram_args(a, folder_mode)
-        picture.update(_loudness_args(a))
+        picture.update(_loudness_args(a, None, folder_mode))
         if a.true_peak:
             picture['true_peak'] = True
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
@@ -250,7 +262,7 @@ def main(argv=None):
     try:                                                                    # before the model is built
         check_lowband(a.lowband, a.lowband_fade, spectro_bins(opt.n_fft, opt.mdct_type), opt.hr_sampling_rate / opt.lr_sampling_rate)
         check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
-        _loudness_args(a, opt.hr_sampling_rate)
+        _loudness_args(a, opt.hr_sampling_rate, folder_mode)
         if a.limiter:
             check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate, "generate")
     except ValueError as e:
@@ -301,6 +313,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
         done = [r for r in records if r['error'] is None]
+        if a.loudness_scope == 'folder' and done:                          # (without the option: no line more than before)
+            _print_album(done[0]['album'])
         print('%d of %d files enhanced, %d skipped' % (len(done), len(records), len(records) - len(done)))
         rows = metrics_rows(records, a.metrics_ext)                       # (the printed means: no peak columns)
         if rows:
@@ -339,6 +353,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             extra['limiter'] = True
         if a.loudness_range:
             extra['loudness_range'] = True
+        if a.loudness_scope == 'folder':
+            extra['album'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -347,7 +347,62 @@ def loudness_range(p, out=None):
     return out
 
 
-_TRUEPEAK_TABLES = {}                                                       # (factor, taps per phase, beta, device) -> the table on the device
+def loudness_blocks(z, rate, weights=None, out=None):
+    """z [C, J] float64 on the GPU (loudness_hops) -> p [max(J - 3, 0)] float64 on the GPU, nothing waited for: the power of every
+    400 ms block of four hops at a 100 ms step, the channels weighted as in loudness_gate, whose own expression it is -- p[b] holds
+    the bits the gate computes in place (p2phd_loudness_blocks).  `out`: None, or a contiguous float64 tensor of exactly that many
+    elements on the GPU, for instance a slice of the buffer that collects the blocks of every file of a folder: it takes the powers
+    and is returned.  One launch of the family "loudness"; none for a clip under 400 ms."""
+    rate = check_loudness_rate(rate, "loudness_blocks")
+    zz = _lib.require_gpu_tensor(z, "loudness_blocks: z", torch.float64)
+    if zz.dim() != 2 or not 1 <= zz.shape[0] <= LOUDNESS_MAX_CHANNELS:
+        raise ValueError("loudness_blocks: expected z [C, J] with 1 <= C <= %d, got shape %s" % (LOUDNESS_MAX_CHANNELS, tuple(zz.shape)))
+    C, J = zz.shape
+    wbuf = None
+    if weights is not None:
+        wbuf = (ctypes.c_float * C)(*[float(v) for v in weights]) if len(weights) == C else None
+        if wbuf is None:
+            raise ValueError("loudness_blocks: %d weights for %d channels" % (len(weights), C))
+    NB = max(J - 3, 0)
+    if out is None:
+        p = torch.empty((NB,), dtype=torch.float64, device=zz.device)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float64:
+            raise _lib.P2PHDError("loudness_blocks: out: expected a float64 tensor on the GPU (this build has no CPU path)")
+        if out.dim() != 1 or out.numel() != NB or not out.is_contiguous():
+            raise ValueError("loudness_blocks: out must be a contiguous float64 tensor of %d elements, got shape %s" % (NB, tuple(out.shape)))
+        p = out
+    _lib.check(_lib.lib().p2phd_loudness_blocks(_lib.ptr(zz), J, C, rate, wbuf, _lib.ptr(p) if NB else None, _lib.stream_ptr()), "loudness_blocks")
+    return p
+
+
+def loudness_gate_blocks(p, target=None, target_dev=None, max_gain_db=LOUDNESS_MAX_GAIN_DB, out=None):
+    """p [NB] float64 on the GPU (loudness_blocks; the blocks of one file, or of every file of a folder one behind the other) ->
+    (res4, gain) on the GPU as loudness_gate returns them, nothing waited for: both gates over these blocks as one programme -- the
+    album loudness of EBU R 128 (p2phd_loudness_gate_blocks).  On the blocks of one file the bits are loudness_gate's on that file's z.
+    `target`, `target_dev`, `max_gain_db`, `out` (40 bytes): loudness_gate's.  One launch of the family "loudness", for every NB;
+    `p` is only read."""
+    pp = _lib.require_gpu_tensor(p, "loudness_gate_blocks: p", torch.float64)
+    if pp.dim() != 1:
+        raise ValueError("loudness_gate_blocks: expected p [NB], got shape %s" % (tuple(pp.shape),))
+    if target_dev is not None:
+        target_dev = _lib.require_gpu_tensor(target_dev, "loudness_gate_blocks: target_dev", torch.float64)
+        if target_dev.numel() < 1:
+            raise ValueError("loudness_gate_blocks: target_dev is empty")
+    if out is None:
+        out = torch.empty((40,), dtype=torch.uint8, device=pp.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "loudness_gate_blocks: out", torch.uint8)
+        if out.numel() != 40:
+            raise ValueError("loudness_gate_blocks: out must hold 40 bytes, got %d" % out.numel())
+    res4, gain = _loudness_views(out)
+    _lib.check(_lib.lib().p2phd_loudness_gate_blocks(_lib.ptr(pp) if pp.numel() else None, pp.numel(), float('nan') if target is None else float(target),
+                                                     _lib.ptr(target_dev), float(max_gain_db), _lib.ptr(res4), _lib.ptr(gain), _lib.stream_ptr()),
+               "loudness_gate_blocks")
+    return res4, gain
+
+
+_TRUEPEAK_TABLES = {}                                                    # (factor, taps per phase, beta, device) -> the table on the device
 
 
 def true_peak_coefficients(factor, taps_per_phase, beta):

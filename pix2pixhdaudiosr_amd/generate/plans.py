@@ -22,6 +22,10 @@ LOUDNESS_MAX_GAIN_DB = 40.0
 LOUDNESS_MODES = ('report', 'input')
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
 LOUDNESS_MAX_CHANNELS = 64
+# what one loudness gain is found for: every file on its own, or the folder as one programme (EBU R 128 album loudness); the bytes of
+# generated clips the folder pipeline keeps on the device between measuring and writing, beyond which a clip waits on the host
+LOUDNESS_SCOPES = ('file', 'folder')
+ALBUM_CACHE_BYTES = 4 << 30
 # the true-peak option (csrc/truepeak.hip): taps per phase and Kaiser beta of the interpolator; the oversampled rate it reaches
 TRUEPEAK_TAPS_PER_PHASE = 24
 TRUEPEAK_BETA = 9.0
@@ -272,6 +276,36 @@ def check_loudness(loudness, hr_rate, who="enhance_file", max_gain_db=None, loud
     if loudness_range:
         loud['range'] = True
     return loud
+
+
+def check_loudness_scope(loudness_scope, loud, who="enhance_folder", folder=True, limiter=False, spectrogram=None, album_cache_bytes=None):
+    """Validates the scope of the loudness option -> None ('file': every file is measured and normalised on its own), or
+    {'cache_bytes'} ('folder': the folder is one programme with one loudness gain and one guard gain).  `loud`: check_loudness'
+    result; `folder`: whether a folder is being enhanced; `limiter` (a bool) and `spectrogram` (None or a path): the options that
+    are not built for the folder scope, like loud['range'].  `album_cache_bytes`: None (ALBUM_CACHE_BYTES) or an int >= 0, an option
+    of the folder scope: the bytes of generated clips kept on the device between measuring and writing."""
+    if loudness_scope not in LOUDNESS_SCOPES:
+        raise ValueError("%s: loudness_scope must be 'file' or 'folder', got %r" % (who, loudness_scope))
+    if loudness_scope == 'file':
+        if album_cache_bytes is not None:
+            raise ValueError("%s: album_cache_bytes is an option of loudness_scope='folder'; loudness_scope is 'file'" % who)
+        return None
+    if not folder:
+        raise ValueError("%s: loudness_scope='folder' is an option of folder mode (enhance_folder, --input DIR): one file is no album" % who)
+    if loud is None:
+        raise ValueError("%s: loudness_scope='folder' is an option of loudness; loudness is None" % who)
+    if limiter:
+        raise ValueError("%s: limiter is not built for loudness_scope='folder': the guard gain it leaves behind is one file's" % who)
+    if loud.get('range', False):
+        raise ValueError("%s: loudness_range is not built for loudness_scope='folder': the range is measured per file" % who)
+    if spectrogram is not None:
+        raise ValueError("%s: spectrogram is not built for loudness_scope='folder': the picture is rendered while its file's clips are "
+                         "on the device" % who)
+    if album_cache_bytes is None:
+        album_cache_bytes = ALBUM_CACHE_BYTES
+    if not _is_int(album_cache_bytes) or album_cache_bytes < 0:
+        raise ValueError("%s: album_cache_bytes must be an int >= 0 (0: keep no generated clip on the device), got %r" % (who, album_cache_bytes))
+    return {'cache_bytes': int(album_cache_bytes)}
 
 
 def truepeak_plan(rate):

@@ -41,7 +41,7 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, lo
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -55,7 +55,9 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     and a row ends with the columns of METRICS_COLUMNS_LIMITER -- the file's largest reduction in dB and its number of reduced samples;
     plain means.  `loudness_range`: the records' 'loudness' carries 'range' and the columns of METRICS_COLUMNS_LOUDNESS_RANGE stand
     behind the loudness columns -- the file's loudness range going in and as the loudness stage leaves it, in LU, and its maximum
-    short-term loudness in LUFS; plain means (a file under 3 s counts with 0.0 and -inf)."""
+    short-term loudness in LUFS; plain means (a file under 3 s counts with 0.0 and -inf).  `album` (with `loudness`): the records
+    carry 'album' (loudness_scope='folder') and one row `album` stands behind `mean`: the folder's loudness going in and as written
+    and the one gain in the loudness columns, every other cell empty; the files' rows keep the tracks' own figures."""
     if loudness_range:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range)
     elif limiter:
@@ -66,10 +68,16 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
             for r in records for c in range(len(r['metrics_ext' if extended else 'metrics'] or ()))]
     if rows:
         rows.append(("mean", "", "") + tuple(mean([row[3 + k] for row in rows]) for k, (_, mean) in enumerate(cols)))
+    whole = next((r['album'] for r in records if r.get('album') is not None), None) if album and loudness else None
+    if whole is not None:
+        first = len(_columns(extended, peaks))                             # the loudness columns stand behind these
+        cells = [""] * len(cols)
+        cells[first:first + 3] = [whole['input'], whole['output'], whole['gain_db']]
+        rows.append(("album", "", "") + tuple(cells))
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
@@ -81,6 +89,8 @@ def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False
             extra['limiter'] = True
         if loudness_range:
             extra['loudness_range'] = True
+        if album:
+            extra['album'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -108,6 +118,11 @@ def _print_peaks(name, o):
 
 def _print_loudness(name, l):
     print('%s: loudness input %+.2f LUFS, output %+.2f LUFS, gain %+.2f dB' % (name, l['input'], l['output'], l['gain_db']))
+
+
+def _print_album(a):
+    print('album: loudness input %+.2f LUFS, measured %+.2f LUFS, gain %+.2f dB -> %+.2f LUFS (%d files, %d blocks)'
+          % (a['input'], a['measured'], a['gain_db'], a['output'], a['files'], a['blocks_out']))
 
 
 def _print_loudness_range(name, r):

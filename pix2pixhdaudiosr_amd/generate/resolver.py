@@ -7,8 +7,8 @@ import torch
 
 from .ops import (_limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_limiter, check_loudness, check_lowband, check_output_options,
-                    check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
+from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+                    check_output_options, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -491,7 +491,7 @@ class SuperResolver:
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
-                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False):
+                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file'):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -558,12 +558,14 @@ class SuperResolver:
         'output' gains 'limiter': {'lookahead', 'hold' (samples), 'max_reduction_db' (the curve's lowest point, <= 0),
         'limited_samples' (samples with a gain under 1), 'input_true_peak_dbtp' (the true peak in front of the limiter)}; its 'peak',
         'true_peak' and 'clipped' are then those of the limited clip and its 'gain' the guard's residual gain.  'sr' and the metrics
-        stay the clip in front of the output stage.  Anything but clip='guard' with it is a ValueError before the file is opened."""
+        stay the clip in front of the output stage.  Anything but clip='guard' with it is a ValueError before the file is opened.
+        `loudness_scope`: 'file'.  'folder' -- one gain for a whole folder -- is an option of enhance_folder and a ValueError here."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_file")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range)
+        check_loudness_scope(loudness_scope, loud, "enhance_file", folder=False)
         extra = {} if tp is None else {'tp': tp}
         if lim is not None:
             extra['lim'] = lim
@@ -592,7 +594,8 @@ class SuperResolver:
     def enhance_folder(self, dir_in, dir_out, is_lr_input=False, channels='first', encoding='pcm16', seed=None, report=None,
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
-                       true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False):
+                       true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
+                       loudness_scope='file', album_cache_bytes=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -606,15 +609,37 @@ class SuperResolver:
         <relative path>.png (enhance_file's `spectrogram`, `spectrogram_channel`, `spectrogram_opts`); a record then gains
         'spectrogram' (as enhance_file returns it; None for a skipped file).  A file without channel `spectrogram_channel` is
         reported like one that does not parse: its record carries the 'error' and neither its wav nor its picture is written.
-        `loudness`, `loudness_max_gain_db`, `loudness_range`: enhance_file's, per file (every file is measured and normalised on its own); a record
+        `loudness`, `loudness_max_gain_db`, `loudness_range`: enhance_file's, per file (every file is measured and normalised on its own, unless `loudness_scope` says otherwise); a record
         then gains 'loudness' (as enhance_file returns it; None for a skipped file).  `true_peak`: enhance_file's, per file; a
         record's 'output' then carries the true-peak figures.  `limiter`, `limiter_lookahead_ms`, `limiter_hold_ms`: enhance_file's,
-        per file; a record's 'output' then carries 'limiter'."""
+        per file; a record's 'output' then carries 'limiter'.
+        `loudness_scope` (an option of `loudness`): 'file' (default: the above), or 'folder': the folder is one programme, as EBU R 128
+        normalises an album (generate/album.py).  Every enhanced file's clip contributes its own 400 ms blocks (a block never spans
+        two files; its file's channel weights), both gates run over the union of them, for the generated clips and for the inputs
+        the generator was given, and one loudness gain -- towards the target, or with 'input' towards the inputs' album loudness,
+        clamped as above -- multiplies every file: the level differences between the files survive.  With clip 'guard' there is one
+        guard gain too: the largest peak (with `true_peak`: true peak) of any file behind the loudness gain sits at the ceiling.
+        With clip 'error' a folder in which any file would clip writes no file at all; the ClipError names the first such file of
+        the plan.  Every file is generated and measured before the first is written: the generated clips wait on the device while
+        they total at most `album_cache_bytes` (None: 4 GiB; 0: none) and on the host beyond that.  Six launches of the family
+        "loudness" per file and two per folder; one synchronisation brings back every figure of the folder, then one per file
+        written, as before.  A record's 'loudness' keeps its keys: 'input' and 'measured' are the track's own, 'gain_db' is the
+        album's, 'output' = 'measured' + 'gain_db', 'target' is the album's; a record gains 'album', the same dict in every
+        enhanced file's record (None for a skipped file): {'input', 'measured', 'gain_db', 'output', 'target' (the album's levels in
+        LUFS), 'files', 'blocks_in', 'blocks_out' (blocks of the inputs and of the generated clips), 'kept' (blocks of the generated
+        clips behind both gates)}; with an output stage its 'output' carries the folder's guard gain as 'gain' beside the file's own
+        peak figures.  `report` is called file by file in phase C, when the file has been written.  `limiter`, `loudness_range` and
+        `spectrogram` are not built for this scope: a ValueError each, as is the scope without `loudness`."""
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range)
+        album = check_loudness_scope(loudness_scope, loud, "enhance_folder", True, limiter, spectrogram, album_cache_bytes)
+        if album is not None:
+            from .album import enhance_album
+            return enhance_album(self, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album,
+                                 dither_seed)
         extra = {} if loud is None else {'loud': loud}
         if tp is not None:
             extra['tp'] = tp

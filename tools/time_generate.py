@@ -44,6 +44,13 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             files, the residual overshoot (the limited clip's true peak over the ceiling in front of the guard's residual gain),
             and the two kernels beside p2phd_truepeak alone, by events, on the clip of the last run; log in --limiter_log
 
+  album     (only when asked for) generate.SuperResolver.enhance_folder(channels='all') on a folder of --files stereo PCM16 clips of
+            --seconds each at different levels, files to files, in one process, the runs interleaved (nine repeats unless --reps says
+            otherwise): without loudness, loudness=-23 at loudness_scope 'file', at scope 'folder', and at scope 'folder' with
+            album_cache_bytes=0 (every generated clip waits on the host): milliseconds per folder, median and spread, and what
+            the scope costs over scope 'file'; then p2phd_loudness_blocks and p2phd_loudness_gate_blocks alone, by events, beside
+            p2phd_loudness_gate on the same hop energies, at the folder's block count and at 36 000 blocks; log in --album_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -56,6 +63,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py loudness --loudness_range [--loudness_range_log profiles/time_generate_loudness_range.log]
         python tools/time_generate.py truepeak [--truepeak_log profiles/time_generate_truepeak.log]
         python tools/time_generate.py limiter [--limiter_log profiles/time_generate_limiter.log]
+        python tools/time_generate.py album [--files 8] [--album_log profiles/time_generate_album.log]
 """
 import argparse
 import os
@@ -386,6 +394,86 @@ def run_loudness(seconds, reps, log, ranged=False):
         f.write(text)
 
 
+def _album_kernels(torch, NB, rate, reps, what):
+    """loudness_blocks and loudness_gate_blocks alone on random hop energies of NB blocks, and loudness_gate on the same hop
+    energies beside them, by events -> a line."""
+    from pix2pixhdaudiosr_amd.generate import loudness_blocks, loudness_gate, loudness_gate_blocks
+    z = torch.rand((1, NB + 3), dtype=torch.float64, device='cuda', generator=torch.Generator('cuda').manual_seed(9)) * (rate // 10)
+    p = torch.empty((NB,), dtype=torch.float64, device='cuda')
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    k_blocks, k_album, k_gate = [], [], []
+    for _ in range(reps + 2):
+        ev[0].record()
+        loudness_blocks(z, rate, out=p)
+        ev[1].record()
+        loudness_gate_blocks(p, target=-23.0)
+        ev[2].record()
+        loudness_gate(z, rate, target=-23.0)
+        ev[3].record()
+        torch.cuda.synchronize()
+        k_blocks.append(ev[0].elapsed_time(ev[1]) * 1e3)
+        k_album.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        k_gate.append(ev[2].elapsed_time(ev[3]) * 1e3)
+    return ("%s, %d blocks (events, median of %d): loudness_blocks %.1f us (%d workgroups), loudness_gate_blocks %.1f us (one workgroup, "
+            "two passes of %d steps per thread), loudness_gate on the same hops %.1f us; runs: blocks %s; gate_blocks %s; gate %s"
+            % (what, NB, reps, _median(k_blocks[2:]), min(-(-NB // 256), 2048), _median(k_album[2:]), -(-NB // 256), _median(k_gate[2:]),
+               " ".join("%.1f" % v for v in k_blocks[2:]), " ".join("%.1f" % v for v in k_album[2:]), " ".join("%.1f" % v for v in k_gate[2:])))
+
+
+def run_album(seconds, reps, files, log):
+    """enhance_folder, files to files, without loudness and with loudness=-23 at either scope: the same object, the same folder,
+    interleaved; then the two album kernels alone."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    sr = SuperResolver(model, opt, overlap=0.25)
+    rate = int(opt.hr_sampling_rate)
+    stereo = torch.cat([x, -0.7 * x.flip(-1)]).cpu()
+    lines = ["# tools/time_generate.py album: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; a folder of "
+             "%d stereo PCM16 clips of %g s at 48 kHz, file k at 0.85^k of the first, files to files, channels='all', untrained weights, %d "
+             "interleaved repeats" % (files, seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = os.path.join(tmp, "in"), os.path.join(tmp, "out")
+        os.makedirs(src)
+        for i in range(files):
+            wavio.save(os.path.join(src, "clip%03d.wav" % i), stereo * 0.85 ** i, rate)
+        variants = (("loudness off            ", {}), ("-23, scope file         ", dict(loudness=-23.0)),
+                    ("-23, scope folder       ", dict(loudness=-23.0, loudness_scope='folder')),
+                    ("-23, scope folder, no cache", dict(loudness=-23.0, loudness_scope='folder', album_cache_bytes=0)))
+        last = {}
+        for name, kw in variants:                                  # warm-up: capture, pinned buffers, page cache
+            sr.enhance_folder(src, out, channels='all', **kw)
+            last[name] = sr.enhance_folder(src, out, channels='all', **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in variants]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(variants):
+                t0 = time.perf_counter()
+                recs = sr.enhance_folder(src, out, channels='all', **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+                assert len(recs) == files and all(r['error'] is None and r['written_channels'] == 2 for r in recs)
+        for (name, _), tk in zip(variants, ts):
+            lines.append("%s  median %9.3f ms per folder   spread %7.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        lines.append("scope file costs %.3f ms per folder over no loudness (difference of the medians), %.2f %% of it"
+                     % (_median(ts[1]) - _median(ts[0]), 100.0 * (_median(ts[1]) - _median(ts[0])) / _median(ts[0])))
+        for k in (2, 3):
+            lines.append("%s costs %.3f ms per folder over scope file (difference of the medians), %.2f %% of it"
+                         % (variants[k][0].strip(), _median(ts[k]) - _median(ts[1]), 100.0 * (_median(ts[k]) - _median(ts[1])) / _median(ts[1])))
+        album = last[variants[2][0]][0]['album']
+        lines.append("the album: %s" % ", ".join("%s %s" % (k, ("%+.3f" % v) if isinstance(v, float) else v) for k, v in sorted(album.items())))
+        lines.append("the per-file gains at scope file: %s dB" % " ".join("%+.2f" % r['loudness']['gain_db'] for r in last[variants[1][0]]))
+        lines.append(_album_kernels(torch, album['blocks_out'], rate, reps, "kernels alone, the folder"))
+        lines.append(_album_kernels(torch, 36000, rate, reps, "kernels alone, an hour of blocks"))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+    with open(log, "w") as f:
+        f.write(text)
+
+
 def run_truepeak(seconds, reps, log):
     """enhance_file, file to file, without the true-peak option and with it under clip='guard': the same object, the same input,
     interleaved; then the true-peak kernel and the sample-peak kernel alone on the same clip."""
@@ -634,8 +722,9 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter"])
-    ap.add_argument("--files", type=int, default=8, help="folder mode: stereo clips in the folder")
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album"])
+    ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
+    ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
     ap.add_argument("--lowband_log", default=os.path.join(ROOT, "profiles", "time_generate_lowband.log"))
     ap.add_argument("--crossover_log", default=os.path.join(ROOT, "profiles", "time_generate_crossover.log"))
@@ -646,9 +735,13 @@ def main():
     ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
     ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
+    if a.mode == "album":
+        return run_album(a.seconds, 9 if a.reps is None else a.reps, a.files, a.album_log)
+    if a.reps is None:
+        a.reps = 5
     if a.mode == "folder":
         return run_folder(a.seconds, a.reps, a.files, a.folder_log)
     if a.mode == "lowband":
