@@ -70,7 +70,7 @@ int p2phd_device_info(char* name, int cap);
  *                      has rows; 1 .. 16384: tests run the path on which a workgroup walks several tiles); the result's bits do not depend on it
  *   "cw_inject" 0|1    libp2phd_hip_chk.so only: selects round 4's too-lax HALO wait (sensitivity check of p2phd_wait_check) */
 int p2phd_set_option(const char* name, int value);
-/* zeroes the arrival tickets of the fixed-order reductions on `stream` (13 KB memset; see "Streams" above) */
+/* zeroes the arrival tickets of the fixed-order reductions on `stream` (17 KB memset; see "Streams" above) */
 int p2phd_reduction_reset(void* stream);
 /* Measurement hook (bench.py's roofline): while armed, every launch of the implicit-GEMM conv kernel whose gathered
  * tensor has `cin_pitch` channels, whose GEMM-K is `kk` and whose pixel grid is hg x wg is bracketed by HIP events on its
@@ -93,7 +93,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * generation, csrc/xover.hip), "specimg" (the STFT and the renderer of its spectrogram picture, csrc/specimg.hip), "loudness" (the
  * BS.1770 hop energies, the gate and the loudness range of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
  * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
- * csrc/limiter.hip).
+ * csrc/limiter.hip), "bandwidth" (the long-term average spectrum and the band-edge decision of its bandwidth report,
+ * csrc/bandwidth.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -479,6 +480,51 @@ int p2phd_limiter_envelope(const float* planar, int64_t frames, int channels, in
 int p2phd_limiter_apply(const float* planar, int64_t frames, int channels, int64_t ld, const float* r, int lookahead, int hold,
                         const float* window_dev, float* out, int64_t out_ld, float* g_out, void* stats_out, void* stream);
 int p2phd_limiter_tile_len(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Effective bandwidth of whole-file generation, csrc/bandwidth.hip: where the band of a clip ends, read off its long-term average
+ * spectrum.  Launch family "bandwidth": p2phd_ltas counts 1 when F > 0 and R > 0, p2phd_bandwidth 1 when G > 0 -- 2 per clip.
+ *
+ * p2phd_ltas_frames (host): F = 1 + (L - n_fft) / hop for L >= n_fft, else 0 -- only the frames that lie wholly inside the clip,
+ *   frame f covering samples f hop .. f hop + n_fft - 1: torch.stft(center=False) with the periodic Hann window.  (Not the
+ *   center=True frames of p2phd_stft_db: the step under the window of a zero-padded edge frame leaks into every bin, and that floor
+ *   decides where a band seems to end.)  -1 and an error text for arguments p2phd_ltas would refuse.
+ * p2phd_ltas_chunk_frames (host): a compile-time constant, the frames of one chunk.
+ * p2phd_ltas_workspace_bytes (host): bytes of the workspace of a call, R * ceil(F / chunk) * K float64; 0 where F = 0 or R = 0 (and,
+ *   with an error text, for arguments p2phd_ltas would refuse).
+ * p2phd_ltas: x[R][ld] f32 rows of L samples (ld >= L; rows may start at any float; 64-bit offsets) -> psd[R][K] float64,
+ *   K = n_fft / 2 + 1.  Per frame and bin P = (re^2 + im^2) (4 / n_fft)^2 in fp32 -- the value p2phd_stft_db takes the logarithm
+ *   of: window and twiddles from the caller's `tables` (p2phd_specimg_tables_fill, n_fft of them on the device), two neighbouring
+ *   frames of a chunk through one complex transform.  psd[r][k] is the float64 sum of the frames' P (each P widened exactly) in one
+ *   fixed order: frames are taken in chunks of p2phd_ltas_chunk_frames() consecutive frames; a chunk's sum starts at +0 and takes
+ *   its frames in ascending order; the row's sum starts at +0 and takes the chunks' sums in ascending order.  One workgroup per
+ *   (row, chunk) keeps its bins' sums in float64 registers and stores one partial [K] into `workspace`; the last workgroup of a row
+ *   to arrive (an integer ticket of the library's reduction scratch, fence then atomic; see "Streams": two calls must be ordered)
+ *   folds the row's partials.  No float atomics, nothing is zeroed beforehand, one launch.  Row r of an R-row call holds the bits of
+ *   the one-row call on that row, and a run repeats bit for bit.  F = 0: psd is zero-filled (hipMemsetAsync, not counted), P2PHD_OK.
+ *   n_fft a power of two in [64, 2048], 1 <= hop <= n_fft, 0 <= R <= 65535, 0 <= L <= 2^40, F <= 2^30, psd and workspace aligned
+ *   to 8 bytes, x to 4, tables to 8: anything else is P2PHD_EINVAL with an error text, nothing launched.
+ * p2phd_bandwidth: psd[G Q][K] float64 (device) -> res[G][4] float64 (device), one workgroup per group, all arithmetic float64 in
+ *   the order written here, nothing contracted, so that a restatement on the host returns the same bits:
+ *     group    s[k] = ((psd[g Q][k] + psd[g Q + 1][k]) + ..) + psd[g Q + Q - 1][k]: the Q rows of a group (the channels of a clip)
+ *              are one programme, as with loudness
+ *     bands    band b covers the bins [b M, min(K, (b + 1) M)), M = band_bins; its level is ((s[b M] + s[b M + 1]) + ..) divided
+ *              by its bin count (one division)
+ *     ref      the largest band level: from 0.0, `if (level > ref) ref = level` over the bands -- a NaN (or a negative level)
+ *              never wins
+ *     thr      ref * rel, one rounded product; rel = 10^(-threshold_db / 10) is computed once on the host and passed as a double
+ *     b_top    the highest band with level > thr (strictly; a NaN fails)
+ *     k_top    the highest bin of band b_top with s[k] > thr -- one exists, since the band's mean is above thr
+ *     res      {k_top, b_top, ref, thr}; {-1, -1, ref, thr} when no band passes: silence (ref = 0), all NaN, an infinite level
+ *   No workspace, no atomics, one launch.  1 <= K <= 4097, 1 <= M <= K, Q >= 1, 0 <= G, G Q <= 2^31 - 1, rel finite and in (0, 1]:
+ *   anything else is P2PHD_EINVAL with an error text.  G = 0: P2PHD_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+int64_t p2phd_ltas_frames(int64_t L, int n_fft, int hop);
+int p2phd_ltas_chunk_frames(void);
+size_t p2phd_ltas_workspace_bytes(int64_t R, int64_t L, int n_fft, int hop);
+int p2phd_ltas(const float* x, int64_t ld, int64_t R, int64_t L, int n_fft, int hop, const float* tables, double* psd, void* workspace,
+               void* stream);
+int p2phd_bandwidth(const double* psd, int64_t G, int Q, int K, int band_bins, double rel, double* res, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -49,7 +49,7 @@ int imdct4_fast(const float* spec, int64_t B, int64_t n_frames, int n_fft, const
 // launches of the SAME family must be ordered: fold_scratch() remembers the region's last stream, the launch that follows
 // records the region's event behind itself (check_launch -> fold_launched), and a launch arriving on another stream first
 // makes that stream wait for the event -- the two launches are ordered on the device instead of mixing partials.
-enum FoldRegion { FOLD_IN_BWD = 0, FOLD_COLSUM = 1, FOLD_ACT_DB = 2, FOLD_LOSS = 3, FOLD_GCONV = 4, FOLD_PCM = 5, FOLD_TRUEPEAK = 6, FOLD_LIMITER = 7 };
+enum FoldRegion { FOLD_IN_BWD = 0, FOLD_COLSUM = 1, FOLD_ACT_DB = 2, FOLD_LOSS = 3, FOLD_GCONV = 4, FOLD_PCM = 5, FOLD_TRUEPEAK = 6, FOLD_LIMITER = 7, FOLD_LTAS = 8 };
 struct FoldScratch { float* part; unsigned* ticket; size_t floats; int tickets; };
 FoldScratch fold_scratch(int region, hipStream_t stream);   // part == nullptr: refused (error text set), see core.hip
 

@@ -29,10 +29,11 @@ int device_cus() {
 
 // scratch of the fixed-order cross-workgroup reductions (common.h): zero-initialised with the code object
 namespace {
-constexpr int kFoldRegions = 8;
-constexpr size_t kFoldFloats[kFoldRegions] = {size_t(4) << 20, size_t(1) << 20, size_t(1) << 20, 4096, size_t(16) << 20, size_t(5) << 16, size_t(1) << 16, size_t(1) << 16};
-constexpr int kFoldTickets[kFoldRegions] = {2048, 1024, 8, 8, 256, 8, 8, 8};
-constexpr int kFoldTicketsAll = 2048 + 1024 + 16 + 256 + 8 + 8 + 8;
+constexpr int kFoldRegions = 9;
+// (the last region, FOLD_LTAS, is tickets only: p2phd_ltas keeps its partials in the caller's workspace)
+constexpr size_t kFoldFloats[kFoldRegions] = {size_t(4) << 20, size_t(1) << 20, size_t(1) << 20, 4096, size_t(16) << 20, size_t(5) << 16, size_t(1) << 16, size_t(1) << 16, 0};
+constexpr int kFoldTickets[kFoldRegions] = {2048, 1024, 8, 8, 256, 8, 8, 8, 1024};
+constexpr int kFoldTicketsAll = 2048 + 1024 + 16 + 256 + 8 + 8 + 8 + 1024;
 __device__ float g_fold_part[(size_t(22) << 20) + 4096 + (size_t(7) << 16)];      // 90 MiB, zero-initialised with the code object
 __device__ unsigned g_fold_ticket[kFoldTicketsAll];
 }  // namespace
@@ -100,7 +101,7 @@ void fold_launched() {
 }  // namespace p2phd
 
 // Re-arms every arrival ticket of the fixed-order reductions (an aborted or faulted launch may have left one non-zero, which
-// would make every later launch of that kernel family fold at the wrong moment): a 13 KB memset on `stream`; the Python
+// would make every later launch of that kernel family fold at the wrong moment): a 17 KB memset on `stream`; the Python
 // mirror issues it once per training step beside its own per-step memset (_ops.begin_step).
 extern "C" int p2phd_reduction_reset(void* stream) {
   void* t = nullptr;
@@ -141,7 +142,7 @@ extern "C" int p2phd_set_option(const char* name, int value) {
 extern "C" int64_t p2phd_launch_count(const char* family, int reset) {
   static const char* names[p2phd::LC_FAMILIES] = {"gconv", "halo", "cls_skip", "march", "march_w", "wgrad", "splitk", "tile256", "tile128x192",
                                                        "dfirst", "dlast", "c7", "thin_wgrad", "timed_pack", "timed_frames", "stitch", "pcm",
-                                                       "metrics_rows", "xover", "specimg", "loudness", "truepeak", "limiter"};
+                                                       "metrics_rows", "xover", "specimg", "loudness", "truepeak", "limiter", "bandwidth"};
   if (family == nullptr) {                                       // all families at once
     if (reset) for (auto& c : p2phd::g_launch_count) c = 0;
     return 0;

@@ -76,6 +76,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
         if stage is not None:
             rec['output'] = None
         rec['loudness'] = rec['album'] = None
+        if getattr(sr, 'crossover_auto', False):                            # (without the option: no key more than before)
+            rec['crossover'] = None
         entry = {'rec': rec, 'k': k, 'path_out': path_out, 'clip': None}
         entries.append(entry)
         try:
@@ -90,6 +92,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
                    out_frames=clip.shape[-1], metrics=metrics)
         if extended_metrics:
             rec['metrics_ext'] = ext
+        if getattr(sr, 'crossover_auto', False):
+            rec['crossover'] = dict(sr.last_crossover)
         # the track's own figures, and its blocks into the folder's two buffers: six launches of the family "loudness"
         weights = loudness_channel_weights(clip.shape[0])
         track = entry['track'] = torch.empty((80,), dtype=torch.uint8, device=clip.device)

@@ -10,9 +10,9 @@ from types import SimpleNamespace
 
 import torch
 
-from .plans import (CLIP_MODES, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_output_options, check_paths, check_spectrogram, spectro_bins)
-from .report import _print_album, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+from .plans import (CLIP_MODES, CROSSOVER_AUTO, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+                    check_output_options, check_paths, check_spectrogram, check_bandwidth, spectro_bins)
+from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -77,6 +77,28 @@ def _loudness_arg(text):
         return float(text)
     except ValueError:
         raise argparse.ArgumentTypeError("expected report, input or a target in LUFS such as -23, got %r" % text)
+
+
+def _crossover_hz_arg(text):
+    if text == CROSSOVER_AUTO:
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected a frequency in Hz or auto, got %r" % text)
+
+
+def _bandwidth_args(a):
+    """The bandwidth options of the command line -> the keyword arguments of enhance_file / enhance_folder ({} without
+    --bandwidth); ValueError for a bad one."""
+    opts = {k: v for k, v in (('threshold_db', a.bandwidth_threshold_db), ('n_fft', a.bandwidth_n_fft), ('band_bins', a.bandwidth_band_bins))
+            if v is not None}
+    if not a.bandwidth:
+        if opts:
+            raise ValueError("--bandwidth_%s is an option of --bandwidth" % sorted(opts)[0])
+        return {}
+    check_bandwidth(True, opts or None, a.loudness_scope, "generate")
+    return dict(bandwidth=True, bandwidth_opts=opts or None)
 
 
 def _loudness_args(a, hr_rate=None, folder_mode=False):
@@ -158,8 +180,10 @@ def _parser():
     ap.add_argument("--crossover", default=None, choices=("input",),
                     help="time-domain crossover behind the stitch: below --crossover_hz the written clip is the input itself, above "
                          "it the generator's output (a linear-phase complementary filter pair; default: off)")
-    ap.add_argument("--crossover_hz", type=float, default=None, metavar="F",
-                    help="--crossover input: the crossover frequency (default: 0.95 of the low rate's Nyquist frequency)")
+    ap.add_argument("--crossover_hz", type=_crossover_hz_arg, default=None, metavar="F|auto",
+                    help="--crossover input: the crossover frequency (default: 0.95 of the low rate's Nyquist frequency); auto: measure "
+                         "where each input's band ends and keep of the input only that band -- the crossover at 0.95 of the band edge, "
+                         "never above the default; one `crossover:` line more per file")
     ap.add_argument("--crossover_taps", type=int, default=None, metavar="N",
                     help="--crossover input: length of the filter, odd, <= 4095 (default: the shortest whose transition band ends "
                          "under the low rate's Nyquist frequency)")
@@ -221,6 +245,18 @@ def _parser():
                     help="--limiter: how far the gain curve looks ahead of a crest, which is also its attack time (default 5)")
     ap.add_argument("--limiter_hold_ms", type=float, default=None, metavar="MS",
                     help="--limiter: how long the curve holds a reduction behind a crest (default 20)")
+    ap.add_argument("--bandwidth", action="store_true",
+                    help="report where the band of the input the generator was given, of the generated clip and, for a full-band input, "
+                         "of the original actually ends: the highest bin of the long-term average spectrum within "
+                         "--bandwidth_threshold_db of the strongest band; one more line per file, one per remark (an input that stops "
+                         "short of the low rate's Nyquist frequency, an original with nothing above it) and three more columns (bw_in, "
+                         "bw_out, bw_orig, in Hz) of --metrics_csv; not with --loudness_scope folder (default: off)")
+    ap.add_argument("--bandwidth_threshold_db", type=float, default=None, metavar="DB",
+                    help="--bandwidth: dB under the strongest band at which the band ends, in (0, 200] (default 60)")
+    ap.add_argument("--bandwidth_n_fft", type=int, default=None, metavar="N",
+                    help="--bandwidth: STFT length of the long-term average spectrum, a power of two in 64 .. 2048, hop N / 2 (default 2048)")
+    ap.add_argument("--bandwidth_band_bins", type=int, default=None, metavar="N",
+                    help="--bandwidth: bins per band whose mean level is compared with the threshold (default 8)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -241,6 +277,7 @@ def main(argv=None):
         out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
         picture = _spectrogram_args(a, folder_mode)
         picture.update(_loudness_args(a, None, folder_mode))
+        picture.update(_bandwidth_args(a))
         if a.true_peak:
             picture['true_peak'] = True
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
@@ -280,7 +317,9 @@ def main(argv=None):
     print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
-    if sr.crossover_plan is not None:                                       # (without the option: no line more than before)
+    if sr.crossover_auto:
+        print("crossover: the input below 0.95 of where its own band ends, at most %g Hz (auto)" % (sr.crossover_plan[1] * opt.hr_sampling_rate))
+    elif sr.crossover_plan is not None:                                     # (without the option: no line more than before)
         print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
     rate = int(opt.hr_sampling_rate)
     try:
@@ -309,6 +348,10 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 _print_loudness(r['path'], r['loudness'])
                 if 'range' in r['loudness']:
                     _print_loudness_range(r['path'], r['loudness']['range'])
+            if r.get('crossover') is not None:
+                _print_crossover(r['crossover'])
+            if r.get('bandwidth') is not None:
+                _print_bandwidth(r['path'], r['bandwidth'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -345,8 +388,14 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_loudness(a.output, res['loudness'])
             if 'range' in res['loudness']:
                 _print_loudness_range(a.output, res['loudness']['range'])
+        if res.get('crossover') is not None:
+            _print_crossover(res['crossover'])
+        if res.get('bandwidth') is not None:
+            _print_bandwidth(a.output, res['bandwidth'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
+        if a.bandwidth:
+            records[0]['bandwidth'] = res['bandwidth']
     if a.metrics_csv:
         extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
         if a.limiter:
@@ -355,6 +404,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             extra['loudness_range'] = True
         if a.loudness_scope == 'folder':
             extra['album'] = True
+        if a.bandwidth:
+            extra['bandwidth'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

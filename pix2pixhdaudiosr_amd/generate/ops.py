@@ -1,11 +1,11 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip and csrc/limiter.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip and csrc/bandwidth.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from .plans import (CROSSOVER_MAX_TAPS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
+from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
                     check_encoding, check_loudness_rate, limiter_plan, spectrogram_lut, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
@@ -452,7 +452,64 @@ def true_peaks(waveform, rate, ceiling=None):
     return _true_peaks_packed(waveform, rate, ceiling, "true_peaks")[0]
 
 
-_LIMITER_WINDOWS = {}                                                       # (lookahead, device) -> the window on the device
+def ltas(rows, n_fft, hop):
+    """rows [R, L] f32 on the GPU (rows contiguous, any row pitch) -> psd [R, K] float64 on the GPU, K = n_fft // 2 + 1: the long-term
+    average spectrum, the float64 sum in a fixed order of the fp32 powers |X|^2 (4 / n_fft)^2 (a full-scale sine carries 1 per
+    frame) of the F = 1 + (L - n_fft) // hop frames of torch.stft(rows, n_fft, hop, window=hann_periodic, center=False) -- only
+    frames that lie wholly inside the clip (p2phd_ltas).  L < n_fft: zeros.  One launch of the family "bandwidth" (none where F =
+    0); the same bits on every run, and row r of a call is the call on that row.  Nothing is waited for."""
+    x, R, L, ld = _rows(rows, "ltas: rows")
+    lib = _lib.lib()
+    F = lib.p2phd_ltas_frames(L, int(n_fft), int(hop))
+    if F < 0:
+        _lib.check(-1, "ltas_frames")
+    psd = torch.empty((R, int(n_fft) // 2 + 1), dtype=torch.float64, device=x.device)
+    tables = work = None
+    if F > 0:
+        tables = _specimg_tables(n_fft, x.device)
+        work = torch.empty((lib.p2phd_ltas_workspace_bytes(R, L, int(n_fft), int(hop)),), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.p2phd_ltas(_lib.ptr(x), max(ld, L), R, L, int(n_fft), int(hop), _lib.ptr(tables), _lib.ptr(psd), _lib.ptr(work),
+                              _lib.stream_ptr()), "ltas")
+    return psd
+
+
+def bandwidth_detect(psd, rows_per_group, band_bins, threshold_db, out=None):
+    """psd [G * Q, K] float64 on the GPU (ltas), Q = `rows_per_group` consecutive rows -- the channels of a clip -- forming one
+    programme -> res [G, 4] float64 on the GPU, nothing waited for: {k_top, b_top, ref, thr} -- the levels of the bands of
+    `band_bins` bins of the group's summed spectrum, ref the largest, thr = ref * 10^(-threshold_db / 10), b_top the highest band
+    above thr and k_top the highest bin of that band above thr: where the band ends; {-1, -1, ref, thr} where no band passes
+    (p2phd_bandwidth, whose float64 arithmetic include/p2phd.h writes down).  `out`: None, or a contiguous float64 tensor of G * 4
+    on the GPU that takes the result.  One launch of the family "bandwidth"."""
+    pp = _lib.require_gpu_tensor(psd, "bandwidth_detect: psd", torch.float64)
+    Q = int(rows_per_group)
+    if pp.dim() != 2 or Q < 1 or pp.shape[0] % Q:
+        raise ValueError("bandwidth_detect: expected psd [G * Q, K] with Q = %d, got shape %s" % (Q, tuple(pp.shape)))
+    G, K = pp.shape[0] // Q, pp.shape[1]
+    if out is None:
+        out = torch.empty((G, 4), dtype=torch.float64, device=pp.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "bandwidth_detect: out", torch.float64)
+        if out.numel() != G * 4:
+            raise ValueError("bandwidth_detect: out must hold %d float64, got %d" % (G * 4, out.numel()))
+    _lib.check(_lib.lib().p2phd_bandwidth(_lib.ptr(pp), G, Q, K, int(band_bins), bandwidth_rel(threshold_db), _lib.ptr(out), _lib.stream_ptr()),
+               "bandwidth")
+    return out.view(G, 4)
+
+
+def bandwidth(waveform, rate, plan=None, out=None):
+    """ltas and bandwidth_detect in a row: waveform [C, L] f32 on the GPU at `rate`, all channels one programme -> res [4] float64
+    on the GPU: res[0] * rate / n_fft is where the clip's band ends, in Hz (res[0] = -1: nothing passed -- silence, or a clip
+    shorter than n_fft).  `plan`: {'n_fft', 'hop', 'band_bins', 'threshold_db'} (plans.check_bandwidth; None: BANDWIDTH_DEFAULTS).
+    `rate` does not enter the device work: the figure is a bin.  `out`: None, or a float64 tensor of 4 on the GPU that takes the
+    result.  Two launches of the family "bandwidth" (one where the clip is shorter than n_fft), nothing is waited for."""
+    p = BANDWIDTH_DEFAULTS if plan is None else plan
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 < rate < float('inf'):
+        raise ValueError("bandwidth: the rate must be a number > 0, got %r" % (rate,))
+    psd = ltas(waveform, p['n_fft'], p['hop'])
+    return bandwidth_detect(psd, psd.shape[0], p['band_bins'], p['threshold_db'], out).view(4)
+
+
+_LIMITER_WINDOWS = {}                                                      # (lookahead, device) -> the window on the device
 
 
 def limiter_window(lookahead):

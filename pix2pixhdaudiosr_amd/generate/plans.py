@@ -11,6 +11,10 @@ CROSSOVERS = (None, 'input')
 CROSSOVER_BETA = 8.96                                                       # Kaiser window, 90 dB
 CROSSOVER_ATTEN_DB = 90.0
 CROSSOVER_MAX_TAPS = 4095
+CROSSOVER_AUTO = 'auto'                                                     # crossover_hz: follow the band each input has
+# the bandwidth report (csrc/bandwidth.hip): STFT length and hop of the long-term average spectrum, bins of a band, dB under the
+# strongest band at which the band ends
+BANDWIDTH_DEFAULTS = {'n_fft': 2048, 'hop': 1024, 'band_bins': 8, 'threshold_db': 60.0}
 # the spectrogram picture (csrc/specimg.hip): STFT length and hop in samples, pixels of one panel, dB below the top that
 # reach the palette's first colour, grey rows between panels
 SPECTROGRAM_DEFAULTS = {'n_fft': 1024, 'hop': 256, 'width': 1600, 'height': 512, 'range_db': 90.0, 'gap': 2}
@@ -184,14 +188,98 @@ def crossover_plan(hr_rate, lr_rate, crossover_hz=None, taps=None):
 
 
 def check_crossover(crossover, crossover_hz, crossover_taps, hr_rate, lr_rate):
-    """Validates the crossover options of SuperResolver -> None (off), or crossover_plan's (taps, cutoff, beta)."""
+    """Validates the crossover options of SuperResolver -> None (off), or crossover_plan's (taps, cutoff, beta).  crossover_hz
+    'auto' (the crossover follows each clip's own band, crossover_auto_plan): the plan of an input that reaches the low rate's
+    Nyquist frequency, which is the default one."""
     if crossover not in CROSSOVERS:
         raise ValueError("SuperResolver: crossover must be None or 'input', got %r" % (crossover,))
     if crossover is None:
         if crossover_hz is not None or crossover_taps is not None:
             raise ValueError("SuperResolver: crossover_hz / crossover_taps are options of crossover='input'; crossover is None")
         return None
+    if isinstance(crossover_hz, str):
+        if crossover_hz != CROSSOVER_AUTO:
+            raise ValueError("SuperResolver: crossover_hz must be None, a frequency in Hz or 'auto', got %r" % (crossover_hz,))
+        return crossover_auto_plan(hr_rate, lr_rate, float(lr_rate) / 2.0, crossover_taps)[0]
     return crossover_plan(hr_rate, lr_rate, crossover_hz, crossover_taps)
+
+
+def crossover_auto_floor_hz(hr_rate, taps=None):
+    """The lowest band edge crossover_auto_plan serves at `hr_rate`: with the crossover at 0.95 of the edge the transition band has
+    0.05 of the edge on its upper side, which must hold half the width of the longest filter (`taps`, None: CROSSOVER_MAX_TAPS) --
+    10 crossover_width_hz, a few parts in 10^9 more so that the plan's own `fits` test agrees in floating point."""
+    return 10.0 * crossover_width_hz(float(hr_rate), CROSSOVER_MAX_TAPS if taps is None else taps) * (1.0 + 1e-9)
+
+
+def crossover_auto_plan(hr_rate, lr_rate, edge_hz, taps=None):
+    """The crossover of crossover_hz='auto' for an input whose band ends at `edge_hz`, host arithmetic only -> ((taps, cutoff,
+    beta), edge): edge = `edge_hz` held inside [crossover_auto_floor_hz, the low rate's Nyquist frequency], and the filter is
+    crossover_plan(hr_rate, 2 * edge, None, taps) -- the plan of a low rate whose Nyquist frequency is the edge: the crossover at
+    0.95 of the edge, the transition band ending at the edge.  An input that reaches the low rate's Nyquist frequency gets
+    crossover_plan's default tuple, exactly."""
+    hr_rate, lr_rate = float(hr_rate), float(lr_rate)
+    if not 0.0 < lr_rate < hr_rate:
+        raise ValueError("crossover_plan: nothing to cross over: the low rate %g must be above 0 and below the high rate %g" % (lr_rate, hr_rate))
+    edge = float(edge_hz)
+    if not edge == edge:
+        raise ValueError("crossover_auto_plan: the band edge must be a number, got %r" % (edge_hz,))
+    nyquist = lr_rate / 2.0
+    edge = min(nyquist, max(edge, min(nyquist, crossover_auto_floor_hz(hr_rate, taps))))
+    return crossover_plan(hr_rate, 2.0 * edge, None, taps), edge
+
+
+def check_bandwidth(bandwidth=False, opts=None, loudness_scope='file', who="enhance_file"):
+    """Validates the bandwidth option -> None (off), or the plan {'n_fft', 'hop', 'band_bins', 'threshold_db'} that ops.bandwidth
+    takes.  `bandwidth`: a bool.  `opts`: None or a dict of those four, None or absent standing for BANDWIDTH_DEFAULTS' value (hop:
+    half of a given n_fft): `n_fft` a power of two in [64, 2048]; `hop` 1 .. n_fft; `band_bins` 1 .. n_fft / 2 + 1; `threshold_db`
+    in (0, 200].  They are options of the option.  The report is one file's: with loudness_scope 'folder' it is a ValueError, as
+    the spectrogram is.  A ValueError names the argument."""
+    if not isinstance(bandwidth, bool):
+        raise ValueError("%s: bandwidth must be a bool, got %r" % (who, bandwidth))
+    if opts is not None and not isinstance(opts, dict):
+        raise ValueError("%s: bandwidth_opts must be None or a dict, got %r" % (who, opts))
+    if not bandwidth:
+        if opts is not None:
+            raise ValueError("%s: bandwidth_opts are options of bandwidth=True; bandwidth is False" % who)
+        return None
+    if loudness_scope == 'folder':
+        raise ValueError("%s: bandwidth is not built for loudness_scope='folder': the report is measured per file" % who)
+    opts = {k: v for k, v in (opts or {}).items() if v is not None}
+    unknown = sorted(set(opts) - set(BANDWIDTH_DEFAULTS))
+    if unknown:
+        raise ValueError("%s: unknown bandwidth_opts %s" % (who, unknown))
+    d = BANDWIDTH_DEFAULTS
+    n_fft = opts.get('n_fft', d['n_fft'])
+    if not _is_int(n_fft) or not 64 <= n_fft <= 2048 or n_fft & (n_fft - 1):
+        raise ValueError("%s: bandwidth n_fft must be a power of two in [64, 2048], got %r" % (who, n_fft))
+    hop = opts.get('hop', d['hop'] if 'n_fft' not in opts else n_fft // 2)
+    if not _is_int(hop) or not 1 <= hop <= n_fft:
+        raise ValueError("%s: bandwidth hop must be an int in [1, n_fft = %d], got %r" % (who, n_fft, hop))
+    band_bins = opts.get('band_bins', d['band_bins'])
+    if not _is_int(band_bins) or not 1 <= band_bins <= n_fft // 2 + 1:
+        raise ValueError("%s: bandwidth band_bins must be an int in [1, n_fft / 2 + 1 = %d], got %r" % (who, n_fft // 2 + 1, band_bins))
+    threshold_db = opts.get('threshold_db', d['threshold_db'])
+    if isinstance(threshold_db, bool) or not isinstance(threshold_db, (int, float)) or not 0.0 < threshold_db <= 200.0:
+        raise ValueError("%s: bandwidth threshold_db must lie in (0, 200] dB, got %r" % (who, threshold_db))
+    return {'n_fft': n_fft, 'hop': hop, 'band_bins': band_bins, 'threshold_db': float(threshold_db)}
+
+
+def bandwidth_rel(threshold_db):
+    """What p2phd_bandwidth takes as `rel`: 10^(-threshold_db / 10), computed once."""
+    return 10.0 ** (-float(threshold_db) / 10.0)
+
+
+def bandwidth_notes(input_hz, original_hz, lr_nyquist):
+    """The two remarks of the bandwidth report, host logic: an input whose band ends under 0.9 of the low rate's Nyquist frequency,
+    and an original (None: there is none) whose band ends at or under 1.05 times that frequency."""
+    notes = []
+    if input_hz < 0.9 * lr_nyquist:
+        notes.append("the input's band ends at %.2f kHz, under the low rate's Nyquist frequency %.2f kHz: the generator was trained on "
+                     "inputs that reach it" % (input_hz / 1000.0, lr_nyquist / 1000.0))
+    if original_hz is not None and original_hz <= 1.05 * lr_nyquist:
+        notes.append("the original's band ends at %.2f kHz, the low rate's Nyquist frequency is %.2f kHz: the original carries nothing above "
+                     "it: LSD-HF compares against an empty band" % (original_hz / 1000.0, lr_nyquist / 1000.0))
+    return notes
 
 
 def _is_int(v):

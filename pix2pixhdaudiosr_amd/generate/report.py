@@ -8,6 +8,7 @@ METRICS_COLUMNS_LOUDNESS = ("lufs_in", "lufs_out", "loudness_gain_db")          
 METRICS_COLUMNS_LOUDNESS_RANGE = ("lra_in", "lra_out", "short_term_max")               # --loudness_range (behind the loudness columns)
 METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                         # --true_peak
 METRICS_COLUMNS_LIMITER = ("limiter_reduction_db", "limited_samples")                   # --limiter
+METRICS_COLUMNS_BANDWIDTH = ("bw_in", "bw_out", "bw_orig")                              # --bandwidth (behind every other column)
 
 
 def _mean(values):
@@ -19,7 +20,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False):
+def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False, bandwidth=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -38,10 +39,12 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, lo
         cols += [(lambda r, c: r['output']['true_peak_dbtp'][c], _mean)]
     if limiter:
         cols += [(lambda r, c: r['output']['limiter']['max_reduction_db'], _mean), (lambda r, c: r['output']['limiter']['limited_samples'], _mean)]
+    if bandwidth:
+        cols += [(lambda r, c, n=n: float('nan') if r['bandwidth'][n] is None else r['bandwidth'][n], _nanmean) for n in ('input', 'output', 'original')]
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False, bandwidth=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -57,8 +60,13 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     behind the loudness columns -- the file's loudness range going in and as the loudness stage leaves it, in LU, and its maximum
     short-term loudness in LUFS; plain means (a file under 3 s counts with 0.0 and -inf).  `album` (with `loudness`): the records
     carry 'album' (loudness_scope='folder') and one row `album` stands behind `mean`: the folder's loudness going in and as written
-    and the one gain in the loudness columns, every other cell empty; the files' rows keep the tracks' own figures."""
-    if loudness_range:
+    and the one gain in the loudness columns, every other cell empty; the files' rows keep the tracks' own figures.  `bandwidth`:
+    the records carry 'bandwidth' and a row ends, behind every other column, with the columns of METRICS_COLUMNS_BANDWIDTH -- where
+    the band of the file's input, of its generated clip and of its original ends, in Hz (the file's figures, the same in each of its
+    channels' rows); plain means."""
+    if bandwidth:
+        cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth)
+    elif loudness_range:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range)
     elif limiter:
         cols = _columns(extended, peaks, loudness, true_peak, limiter)
@@ -77,13 +85,14 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     return rows
 
 
-def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False):
+def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False,
+                      bandwidth=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
                    + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_LOUDNESS_RANGE if loudness_range else ())
                    + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
-                   + (METRICS_COLUMNS_LIMITER if limiter else ()))
+                   + (METRICS_COLUMNS_LIMITER if limiter else ()) + (METRICS_COLUMNS_BANDWIDTH if bandwidth else ()))
         extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
         if limiter:
             extra['limiter'] = True
@@ -91,6 +100,8 @@ def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False
             extra['loudness_range'] = True
         if album:
             extra['album'] = True
+        if bandwidth:
+            extra['bandwidth'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -138,3 +149,15 @@ def _print_unwritten(name, available, written):
 def _print_limiter(l, frames):
     print('limiter: %+.2f dB at most, %.1f %% of the samples, true peak in %+.2f dBTP'
           % (l['max_reduction_db'], 100.0 * l['limited_samples'] / max(frames, 1), l['input_true_peak_dbtp']))
+
+
+def _print_bandwidth(name, b):
+    original = '' if b['original'] is None else ', original %.2f kHz' % (b['original'] / 1000.0)
+    print("%s: bandwidth input %.2f kHz, output %.2f kHz%s (-%g dB, low rate's Nyquist %.2f kHz)"
+          % (name, b['input'] / 1000.0, b['output'] / 1000.0, original, b['threshold_db'], b['lr_nyquist'] / 1000.0))
+    for note in b['notes']:
+        print('%s: note: %s' % (name, note))
+
+
+def _print_crossover(x):
+    print('crossover: %.2f kHz, %d taps (input band ends at %.2f kHz)' % (x['hz'] / 1000.0, x['taps'], x['edge_hz'] / 1000.0))

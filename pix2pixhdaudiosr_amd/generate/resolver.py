@@ -5,9 +5,9 @@ import struct
 
 import torch
 
-from .ops import (_limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+from .ops import (bandwidth as _bandwidth, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (LOUDNESS_MAX_CHANNELS, ClipError, check_crossover, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -68,7 +68,14 @@ class SuperResolver:
     it the generator's output.  `crossover_taps`: the filter's length (odd, <= 4095; default: the shortest whose transition
     band ends under that Nyquist frequency, crossover_plan).  Fixed for the object's life; the coefficients are filled once and
     stay on the device.  One launch per clip, outside the captured chain; orthogonal to `lowband`.  Needs lr_sampling_rate <
-    hr_sampling_rate."""
+    hr_sampling_rate.  `crossover_hz` 'auto': the crossover follows the band each clip has.  The clip's band edge is measured on
+    the device in front of the generator (ops.bandwidth with BANDWIDTH_DEFAULTS, all channels one programme), edge = min(the low
+    rate's Nyquist frequency, where the band ends), and the filter is plans.crossover_auto_plan's: the crossover at 0.95 of the edge,
+    the transition band ending at the edge -- a telephone-band input in a 16 kHz file keeps its 3.4 kHz and the generator fills the
+    rest, where the fixed crossover would copy an empty band.  An input that reaches the Nyquist frequency gets the default plan and
+    the default bytes.  The 32 bytes of the measurement come back on a side stream behind an event recorded in front of the first
+    group, so the host waits for two small launches, not for the generator; coefficients are cached per band edge.
+    `last_crossover` then holds {'hz', 'taps', 'edge_hz'} of the latest clip."""
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
                  lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None):
@@ -112,6 +119,10 @@ class SuperResolver:
         self.crossover, self.crossover_hz, self.crossover_taps = crossover, crossover_hz, crossover_taps
         self.crossover_plan = check_crossover(crossover, crossover_hz, crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
         self._xover_taps = None                                             # the coefficients on the device, filled at first use
+        self.crossover_auto = crossover == 'input' and crossover_hz == CROSSOVER_AUTO
+        self._xover_auto = {}                                               # k_top -> (plan, edge, the coefficients on the device)
+        self._side = None                                                   # the stream the auto crossover's measurement comes back on
+        self.last_crossover = None                                          # auto: {'hz', 'taps', 'edge_hz'} of the latest clip
         self._g = None                                                      # captured chain of a full group
         self._pins = {}                                                     # pinned host buffers of the file path, grow-only
 
@@ -195,6 +206,11 @@ class SuperResolver:
         x = x.contiguous()
         C, L = x.shape
         S, stride, V = segment_plan(L, self.T, self.overlap)
+        measured = None
+        if self.crossover_auto:
+            # the two measurement launches and their event go in front of every group: the host then waits for them alone
+            measured = (_bandwidth(x, float(self.opt.hr_sampling_rate)), torch.cuda.Event())
+            measured[1].record()
         seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
         for c in range(C):
@@ -215,9 +231,41 @@ class SuperResolver:
         sr = segments_stitch_planar(out, C, stride, self.gain, L)
         if self.crossover_plan is None:
             return sr
+        if measured is not None:
+            return crossover(sr, x, self.gain / 2.0, self._auto_taps(*measured))
         if self._xover_taps is None:
             self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
         return crossover(sr, x, self.gain / 2.0, self._xover_taps)
+
+    def _auto_taps(self, res_dev, event):
+        """crossover_hz 'auto': the clip's measurement (ops.bandwidth's 32 bytes on the device, `event` recorded behind it) -> the
+        coefficients of the clip's crossover on the device.  The copy runs on a side stream behind the event and the host waits
+        for that copy alone: the groups queued since are not waited for."""
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        pin = self._pinned('xover_auto', 32)[:32]
+        self._side.wait_event(event)
+        with torch.cuda.stream(self._side):
+            pin.copy_(res_dev.view(torch.uint8), non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+        done.synchronize()
+        k_top = int(pin.view(torch.float64)[0])
+        entry = self._xover_auto.get(k_top)
+        if entry is None:
+            hr_rate, nyquist = float(self.opt.hr_sampling_rate), float(self.opt.lr_sampling_rate) / 2.0
+            edge = nyquist if k_top < 0 else min(nyquist, k_top * hr_rate / BANDWIDTH_DEFAULTS['n_fft'])
+            plan, edge = crossover_auto_plan(hr_rate, self.opt.lr_sampling_rate, edge, self.crossover_taps)
+            if plan == self.crossover_plan:                                 # the band reaches the Nyquist frequency: the fixed crossover's table
+                if self._xover_taps is None:
+                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
+                taps = self._xover_taps
+            else:
+                taps = crossover_coefficients(*plan).to(self.device)
+            entry = self._xover_auto[k_top] = (plan, edge, taps)
+        plan, edge, taps = entry
+        self.last_crossover = {'hz': plan[1] * float(self.opt.hr_sampling_rate), 'taps': plan[0], 'edge_hz': edge}
+        return taps
 
     # -- files -------------------------------------------------------------------------------------
     def _pinned(self, slot, nbytes):
@@ -248,7 +296,7 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
         back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
@@ -257,13 +305,17 @@ class SuperResolver:
         true-peak option (check_true_peak; it comes with a stage): the true-peak kernel runs behind the peak kernel, on the same
         clip, clip 'guard' takes its gain from it, and its figures come back likewise.  `limiter`: the limiter option
         (_limiter_option; it comes with a stage and the true-peak option): the limiter runs in front of the peak kernel, everything
-        behind it sees the limited clip, and its figures come back likewise."""
+        behind it sees the limited clip, and its figures come back likewise.  `bandwidth`: the bandwidth measurement
+        (_measure_bandwidth), whose packed results come back likewise."""
         w = sr.contiguous()
         extra = {} if true_peak is None else {'true_peak': true_peak}
         if limiter is not None:
             extra['limiter'] = limiter
         dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **extra)
-        host, stats = self._fetch(dev, packed, picture, **(extra if loudness is None else dict(extra, loudness=loudness)))
+        fetch = extra if loudness is None else dict(extra, loudness=loudness)
+        if bandwidth is not None:
+            fetch = dict(fetch, bandwidth=bandwidth)
+        host, stats = self._fetch(dev, packed, picture, **fetch)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
         if host is not None:
             self._save(path_out, host, sr.shape[0], encoding)
@@ -288,14 +340,19 @@ class SuperResolver:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None):
+    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
         -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
         copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
         (the two gate results, a device tensor) is copied and replaced likewise; `true_peak`: None, or a dict whose 'packed' (the
         packed true-peak buffer) is, into a pinned slot of its own; `limiter`: None, or a dict whose 'packed' (the limiter's 12
-        bytes) is, into another."""
+        bytes) is, into another; `bandwidth`: None, or a dict whose 'packed' (the clips' 32-byte results) is, into another."""
         host = stats = None
+        if bandwidth is not None:
+            n = bandwidth['packed'].numel()
+            pin = self._pinned('bandwidth', n)[:n]
+            pin.copy_(bandwidth['packed'], non_blocking=True)
+            bandwidth['packed'] = pin
         if limiter is not None:
             n = limiter['packed'].numel()
             pin = self._pinned('limiter', n)[:n]
@@ -433,12 +490,33 @@ class SuperResolver:
                                'blocks': int(r_out[4]), 'short_term_max': r_out[5]}
         return result
 
+    def _measure_bandwidth(self, bw, lr, sr, hr):
+        """The device work of the bandwidth option: the clip the generator was given, the generated clip and, where there is one, the
+        original through the spectrum and the decision kernel (two launches of the family "bandwidth" each; all channels of a clip
+        one programme) -> {'packed': their results of 32 bytes one behind the other, 'clips', 'frames'}."""
+        clips = [t for t in (lr, sr, hr) if t is not None]
+        packed = torch.empty((32 * len(clips),), dtype=torch.uint8, device=sr.device)
+        rate = float(self.opt.hr_sampling_rate)
+        for i, clip in enumerate(clips):
+            _bandwidth(clip, rate, bw, out=packed[32 * i:32 * i + 32].view(torch.float64))
+        L = sr.shape[-1]
+        return {'packed': packed, 'clips': len(clips), 'frames': 1 + (L - bw['n_fft']) // bw['hop'] if L >= bw['n_fft'] else 0}
+
+    def _bandwidth_result(self, bw, measure):
+        """The fetched measurement -> the result's 'bandwidth'."""
+        rate, nyquist = float(self.opt.hr_sampling_rate), float(self.opt.lr_sampling_rate) / 2.0
+        tops = [float(measure['packed'][32 * i:32 * i + 8].view(torch.float64)[0]) for i in range(measure['clips'])]
+        hz = [k * rate / bw['n_fft'] if k >= 0 else 0.0 for k in tops] + [None]
+        return {'input': hz[0], 'output': hz[1], 'original': hz[2], 'lr_nyquist': nyquist, 'threshold_db': bw['threshold_db'],
+                'n_fft': bw['n_fft'], 'hop': bw['hop'], 'band_bins': bw['band_bins'], 'frames': measure['frames'],
+                'notes': bandwidth_notes(hz[0], hz[2], nyquist)}
+
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
-                         lim=None):
+                         lim=None, bw=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
         7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
         `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak).  `lim`: None,
-    or the limiter option (_limiter_option)."""
+    or the limiter option (_limiter_option).  `bw`: None, or the bandwidth option (check_bandwidth)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -455,6 +533,10 @@ class SuperResolver:
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         sr = self.enhance_lr(lr)
+        # the generated clip behind the crossover and in front of the loudness gain: the figure is relative, a gain does not move it
+        band = None if bw is None else self._measure_bandwidth(bw, lr, sr, raw if has_hr else None)
+        auto = getattr(self, 'crossover_auto', False)                       # (an object built without __init__ has no crossover at all)
+        xover = dict(self.last_crossover) if auto else None
         metrics = ext = None
         if has_hr and extended_metrics:
             # every written channel in one call and one copy back; the 7-tuples are read off the same rows
@@ -470,8 +552,10 @@ class SuperResolver:
             if loud['mode'] != 'report':
                 sr = sr * measure['gain']
         picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
-        if path_out is not None or stage is not None or picture is not None or measure is not None:
+        if path_out is not None or stage is not None or picture is not None or measure is not None or band is not None:
             extra = {} if measure is None else {'loudness': measure}
+            if band is not None:
+                extra['bandwidth'] = band
             if tp is not None:
                 extra['true_peak'] = dict(tp)                              # (one file's: it takes the file's buffers)
             if lim is not None:
@@ -482,6 +566,10 @@ class SuperResolver:
             res['spectrogram'] = self._save_picture(spec, picture)
         if measure is not None:
             res['loudness'] = self._loudness_result(loud, measure)
+        if band is not None:
+            res['bandwidth'] = self._bandwidth_result(bw, band)
+        if xover is not None:
+            res['crossover'] = xover
         if extended_metrics:
             res['metrics_ext'] = ext
         if stage is not None:
@@ -491,7 +579,8 @@ class SuperResolver:
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
-                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file'):
+                     limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
+                     bandwidth=False, bandwidth_opts=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -559,7 +648,21 @@ class SuperResolver:
         'limited_samples' (samples with a gain under 1), 'input_true_peak_dbtp' (the true peak in front of the limiter)}; its 'peak',
         'true_peak' and 'clipped' are then those of the limited clip and its 'gain' the guard's residual gain.  'sr' and the metrics
         stay the clip in front of the output stage.  Anything but clip='guard' with it is a ValueError before the file is opened.
-        `loudness_scope`: 'file'.  'folder' -- one gain for a whole folder -- is an option of enhance_folder and a ValueError here."""
+        `loudness_scope`: 'file'.  'folder' -- one gain for a whole folder -- is an option of enhance_folder and a ValueError here.
+        `bandwidth` (opt-in, a bool): where the band of each clip actually ends (csrc/bandwidth.hip) -- of the clip the generator was
+        given ('lr'), of the generated clip (behind the crossover, in front of the loudness gain: the figure is relative to the clip's
+        own strongest band, so a gain does not move it) and, where the result has one, of the original: the long-term average
+        spectrum over the frames that lie wholly inside the clip (all written channels one programme), the levels of bands of
+        `band_bins` bins, and the highest bin of the highest band that stands within `threshold_db` of the strongest band.
+        `bandwidth_opts`: None or a dict of n_fft, hop, band_bins, threshold_db (plans.check_bandwidth; BANDWIDTH_DEFAULTS).  At
+        most six launches of the family "bandwidth" per file; the three results of 32 bytes come back with the payload behind the
+        same synchronisation.  The result gains 'bandwidth': {'input', 'output', 'original' (Hz, k_top * rate / n_fft; 0.0 where
+        nothing passed -- silence, a clip shorter than n_fft; 'original' None without one), 'lr_nyquist', 'threshold_db', 'n_fft',
+        'hop', 'band_bins', 'frames', 'notes' (a list of strings: an input whose band ends under 0.9 of the low rate's Nyquist
+        frequency; an original whose band ends at or under 1.05 times it, so that LSD-HF compares against an empty band)}.
+        With SuperResolver(crossover_hz='auto') -- whatever `bandwidth` is -- the result gains 'crossover': {'hz', 'taps', 'edge_hz'},
+        the crossover this clip got."""
+        bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_file")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_file")
@@ -569,6 +672,8 @@ class SuperResolver:
         extra = {} if tp is None else {'tp': tp}
         if lim is not None:
             extra['lim'] = lim
+        if bw is not None:
+            extra['bw'] = bw
         if loud is None:
             res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
         else:
@@ -595,7 +700,7 @@ class SuperResolver:
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
-                       loudness_scope='file', album_cache_bytes=None):
+                       loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -629,7 +734,11 @@ class SuperResolver:
         LUFS), 'files', 'blocks_in', 'blocks_out' (blocks of the inputs and of the generated clips), 'kept' (blocks of the generated
         clips behind both gates)}; with an output stage its 'output' carries the folder's guard gain as 'gain' beside the file's own
         peak figures.  `report` is called file by file in phase C, when the file has been written.  `limiter`, `loudness_range` and
-        `spectrogram` are not built for this scope: a ValueError each, as is the scope without `loudness`."""
+        `spectrogram` are not built for this scope: a ValueError each, as is the scope without `loudness`.
+        `bandwidth`, `bandwidth_opts`: enhance_file's, per file; a record then gains 'bandwidth' (as enhance_file returns it; None for
+        a skipped file).  Not built for loudness_scope 'folder' either: a ValueError.  With SuperResolver(crossover_hz='auto') a
+        record gains 'crossover' (the file's; None for a skipped file), in either scope."""
+        bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_folder")
@@ -645,6 +754,8 @@ class SuperResolver:
             extra['tp'] = tp
         if lim is not None:
             extra['lim'] = lim
+        if bw is not None:
+            extra['bw'] = bw
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
@@ -657,6 +768,10 @@ class SuperResolver:
                 rec['spectrogram'] = None
             if loud is not None:
                 rec['loudness'] = None
+            if bw is not None:
+                rec['bandwidth'] = None
+            if getattr(self, 'crossover_auto', False):
+                rec['crossover'] = None
             try:
                 read = self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
@@ -680,6 +795,10 @@ class SuperResolver:
                     rec['spectrogram'] = res['spectrogram']
                 if loud is not None:
                     rec['loudness'] = res['loudness']
+                if bw is not None:
+                    rec['bandwidth'] = res['bandwidth']
+                if 'crossover' in res:
+                    rec['crossover'] = res['crossover']
             records.append(rec)
             if report is not None:
                 report(rec)

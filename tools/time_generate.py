@@ -51,6 +51,13 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             the scope costs over scope 'file'; then p2phd_loudness_blocks and p2phd_loudness_gate_blocks alone, by events, beside
             p2phd_loudness_gate on the same hop energies, at the folder's block count and at 36 000 blocks; log in --album_log
 
+  bandwidth (only when asked for) generate.SuperResolver.enhance_file on that clip, file to file, without the option and with
+            bandwidth=True in one process, the runs interleaved (nine repeats unless --reps says otherwise): milliseconds per file,
+            median and spread; then crossover='input' with the fixed crossover against crossover_hz='auto' likewise (the wait for
+            the measurement's event shows there); then p2phd_ltas and p2phd_bandwidth alone, by events, at the clip's frame count
+            and at an hour's; with --off_only only the run without any option is timed (one process of an alternating comparison
+            with another checkout); log in --bandwidth_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -64,6 +71,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py truepeak [--truepeak_log profiles/time_generate_truepeak.log]
         python tools/time_generate.py limiter [--limiter_log profiles/time_generate_limiter.log]
         python tools/time_generate.py album [--files 8] [--album_log profiles/time_generate_album.log]
+        python tools/time_generate.py bandwidth [--off_only] [--bandwidth_log profiles/time_generate_bandwidth.log]
 """
 import argparse
 import os
@@ -542,6 +550,95 @@ def run_truepeak(seconds, reps, log):
         f.write(text)
 
 
+def run_bandwidth(seconds, reps, log, off_only=False):
+    """enhance_file, file to file, without the bandwidth option and with it -- the same object, the same input, interleaved; the
+    fixed crossover against crossover_hz='auto' likewise; then the two kernels alone at the clip's frame count and at an hour's."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    hr = x.cpu() + (hi + 0.001 * torch.randn(n, generator=g, dtype=torch.float64)).float()[None]      # as the spectrogram run's original
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py bandwidth: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz with a full-band original, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+
+    def interleaved(runs, src, out):
+        """runs: [(name, resolver, keyword arguments)] -> the milliseconds of every run, and the last result of each"""
+        last = [None] * len(runs)
+        for k, (_, sr, kw) in enumerate(runs):                      # warm-up: capture, pinned buffers, page cache
+            sr.enhance_file(src, out, **kw)
+            last[k] = sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, sr, kw) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        return ts, last
+
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, hr, rate)
+        sr = SuperResolver(model, opt, overlap=0.25)
+        if off_only:
+            interleaved([("no option            ", sr, {})], src, out)
+        else:
+            ts, last = interleaved([("bandwidth off        ", sr, {}), ("bandwidth            ", sr, dict(bandwidth=True))], src, out)
+            lines.append("bandwidth costs %.3f ms per file (difference of the medians), %.2f %% of the file without it: six launches and 96 bytes "
+                         "more in the copy back" % (_median(ts[1]) - _median(ts[0]), 100.0 * (_median(ts[1]) - _median(ts[0])) / _median(ts[0])))
+            b = last[1]['bandwidth']
+            lines.append("the last file: input %.2f kHz, output %.2f kHz, original %.2f kHz, %d frames" % (b['input'] / 1e3, b['output'] / 1e3, b['original'] / 1e3, b['frames']))
+            fixed, auto = SuperResolver(model, opt, overlap=0.25, crossover='input'), SuperResolver(model, opt, overlap=0.25, crossover='input', crossover_hz='auto')
+            ts, last = interleaved([("crossover fixed      ", fixed, {}), ("crossover auto       ", auto, {})], src, out)
+            lines.append("auto costs %.3f ms per file over the fixed crossover (difference of the medians): two launches, and the host waits for them "
+                         "and a 32-byte copy before it can queue the crossover -- the groups are queued by then, so the device does not idle; the "
+                         "last file: %r" % (_median(ts[1]) - _median(ts[0]), last[1]['crossover']))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _bandwidth_kernels(torch, x, rate, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _bandwidth_kernels(torch, x, rate, reps):
+    """p2phd_ltas and p2phd_bandwidth alone, by events (each with the allocation of its result, the first also of its workspace, in
+    front), on the 15 s clip and on an hour of it."""
+    from pix2pixhdaudiosr_amd.generate import BANDWIDTH_DEFAULTS as P, bandwidth_detect, ltas
+    lines = []
+    hour = x.repeat(1, -(-3600 * rate // x.shape[-1]))[:, :3600 * rate].contiguous()
+    for name, clip in (("the clip", x), ("an hour", hour)):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        k_ltas, k_dec = [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            psd = ltas(clip, P['n_fft'], P['hop'])
+            ev[1].record()
+            bandwidth_detect(psd, 1, P['band_bins'], P['threshold_db'])
+            ev[2].record()
+            torch.cuda.synchronize()
+            k_ltas.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_dec.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        L = clip.shape[-1]
+        F = 1 + (L - P['n_fft']) // P['hop']
+        us = _median(k_ltas[2:])
+        lines.append("kernels alone on %s (events, median of %d): p2phd_ltas %.1f us (%d samples, %d frames of %d: %.2f M frames/s, %.2f GB/s of "
+                     "samples read once), p2phd_bandwidth %.1f us" % (name, reps, us, L, F, P['n_fft'], F / us, 4.0 * L / us * 1e-3, _median(k_dec[2:])))
+        lines.append("runs: p2phd_ltas %s; p2phd_bandwidth %s" % (" ".join("%.1f" % v for v in k_ltas[2:]), " ".join("%.1f" % v for v in k_dec[2:])))
+    return "\n".join(lines) + "\n"
+
+
 def run_limiter(seconds, reps, log):
     """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
     guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
@@ -722,7 +819,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -734,12 +831,17 @@ def main():
     ap.add_argument("--loudness_range_log", default=os.path.join(ROOT, "profiles", "time_generate_loudness_range.log"))
     ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
     ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
+    ap.add_argument("--bandwidth_log", default=os.path.join(ROOT, "profiles", "time_generate_bandwidth.log"))
+    ap.add_argument("--off_only", action="store_true", help="bandwidth mode: time only the run without any option (no log unless --bandwidth_log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album and bandwidth mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "album":
         return run_album(a.seconds, 9 if a.reps is None else a.reps, a.files, a.album_log)
+    if a.mode == "bandwidth":
+        log = a.bandwidth_log if not a.off_only or "--bandwidth_log" in sys.argv else None
+        return run_bandwidth(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.reps is None:
         a.reps = 5
     if a.mode == "folder":
