@@ -94,7 +94,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * BS.1770 hop energies, the gate and the loudness range of whole-file generation, csrc/loudness.hip), "truepeak" (the oversampling true-peak measurement
  * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
  * csrc/limiter.hip), "bandwidth" (the long-term average spectrum and the band-edge decision of its bandwidth report,
- * csrc/bandwidth.hip).
+ * csrc/bandwidth.hip), "stereo" (the cross-spectrum and the band sums of its stereo image report and the mid/side matrix of
+ * stereo='ms', csrc/stereo.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -525,6 +526,51 @@ size_t p2phd_ltas_workspace_bytes(int64_t R, int64_t L, int n_fft, int hop);
 int p2phd_ltas(const float* x, int64_t ld, int64_t R, int64_t L, int n_fft, int hop, const float* tables, double* psd, void* workspace,
                void* stream);
 int p2phd_bandwidth(const double* psd, int64_t G, int Q, int K, int band_bins, double rel, double* res, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Stereo image of whole-file generation, csrc/stereo.hip: how the two channels of a clip relate below and above a split bin, read
+ * off their long-term cross-spectrum, and the mid/side matrix of SuperResolver(stereo='ms').  Launch family "stereo": p2phd_xspec
+ * counts 1 when F > 0 and G > 0, p2phd_stereo_bands 1 when G > 0 (2 per measured clip), p2phd_stereo_matrix 1 when L > 0 (2 per
+ * clip generated as mid / side: the encoder and the decoder).
+ *
+ * p2phd_xspec_workspace_bytes (host): bytes of the workspace of a call, G * ceil(F / chunk) * 4 * K float64 -- four times
+ *   p2phd_ltas's per row pair; F = p2phd_ltas_frames(L, n_fft, hop), chunk = p2phd_ltas_chunk_frames().  0 where F = 0 or G = 0 (and,
+ *   with an error text, for arguments p2phd_xspec would refuse).
+ * p2phd_xspec: x[2 G][ld] f32 rows of L samples (ld >= L; rows may start at any float; 64-bit offsets); rows 2 g and 2 g + 1 are the
+ *   left and the right channel of pair g -> xs[G][4][K] float64, K = n_fft / 2 + 1.  With A and B the transforms of the two
+ *   channels' Hann-windowed frame (p2phd_ltas's frames -- only those wholly inside the clip --, window, `tables` and (4 / n_fft)^2
+ *   scale; both channels of a frame through one complex transform, z = w x_L + i w x_R), per frame and bin in fp32:
+ *     row 0  |A|^2        row 1  |B|^2        row 2  Re(A conj B)        row 3  Im(A conj B)
+ *   xs[g][q][k] is the float64 sum of the frames' values (each widened exactly) in p2phd_ltas's fixed order: chunks of
+ *   p2phd_ltas_chunk_frames() consecutive frames, each summed from +0 ascending, the chunks' sums added from +0 ascending.  One
+ *   workgroup per (pair, chunk) stores one partial [4][K] into `workspace`; the last workgroup of a pair to arrive folds the pair's
+ *   partials, one of the four rows at a time.  The arrival tickets are those of p2phd_ltas (FOLD_LTAS, the tickets-only region of
+ *   the library's reduction scratch; see "Streams": a p2phd_ltas and a p2phd_xspec on two streams are ordered like two calls of
+ *   either).  No float atomics, nothing is zeroed beforehand, one launch.  Pair g of a G-pair call holds the bits of the one-pair
+ *   call on that pair, and a run repeats bit for bit.  F = 0: xs is zero-filled (hipMemsetAsync, not counted), P2PHD_OK.  G = 0:
+ *   P2PHD_OK, nothing launched.  n_fft a power of two in [64, 2048], 1 <= hop <= n_fft, 0 <= G <= 32767, 0 <= L <= 2^40, F <= 2^30,
+ *   xs and workspace aligned to 8 bytes, x to 4, tables to 8: anything else is P2PHD_EINVAL with an error text, nothing launched.
+ * p2phd_stereo_bands: xs[G][4][K] float64 (device) -> res[G][8] float64 (device) = {S_ll, S_rr, Re, Im} of the band [0, k_split),
+ *   then of the band [k_split, K): 64 bytes per pair, one workgroup of 256 lanes per pair.  Each of the eight sums over its band
+ *   [lo, hi) of its row v is float64 in this order, nothing contracted, so that a restatement on the host returns the same bits:
+ *     lanes    lane t (0 .. 255) starts at +0.0 and adds v[lo + t], v[lo + t + 256], v[lo + t + 512], .. below hi, ascending
+ *     tree     for o = 128, 64, .. 1: lane t < o takes s[t] = s[t] + s[t + o]; the sum is s[0]
+ *   NaN and infinity go through as IEEE arithmetic leaves them.  2 <= K <= 4097, 1 <= k_split <= K - 1, 0 <= G, pointers aligned to
+ *   8 bytes: anything else is P2PHD_EINVAL with an error text.  G = 0: P2PHD_OK, nothing launched.  No workspace, no atomics.
+ * p2phd_stereo_matrix: x[2][ld] f32 -> out[2][ld_out] f32, L samples a row: out0[i] = a * (x0[i] + s), out1[i] = a * (x0[i] - s) with
+ *   s = x1[i]; with guard_side != 0 a non-finite x1[i] (NaN, +inf, -inf) is read as +0 -- "no side here" -- while a non-finite
+ *   x0[i] stays what it is.  Plain fp32, one rounding per operation (one sum or difference, one product), nothing contracted: numpy
+ *   float32 repeats it bit for bit.  a = 0.5 without the guard is the encoder (mid, side) = ((L + R) / 2, (L - R) / 2), a = 1 with
+ *   the guard the decoder (L, R) = (M + S, M - S).  Grid-stride, float4 where both pointers are aligned to 16 bytes and both
+ *   pitches are multiples of 4, one launch.  In place is allowed as out == x with ld_out == ld; any other overlap of the two
+ *   buffers is refused.  ld, ld_out >= L, 0 <= L <= 2^40, a finite, pointers aligned to 4 bytes: anything else is P2PHD_EINVAL with
+ *   an error text.  L = 0: P2PHD_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+size_t p2phd_xspec_workspace_bytes(int64_t G, int64_t L, int n_fft, int hop);
+int p2phd_xspec(const float* x, int64_t ld, int64_t G, int64_t L, int n_fft, int hop, const float* tables, double* xs, void* workspace,
+                void* stream);
+int p2phd_stereo_bands(const double* xs, int64_t G, int K, int k_split, double* res, void* stream);
+int p2phd_stereo_matrix(const float* x, int64_t ld, int64_t L, float a, int guard_side, float* out, int64_t ld_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -80,6 +80,10 @@ SIGNATURES = {
     "p2phd_ltas_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "p2phd_ltas": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "p2phd_bandwidth": (_i32, [_vp, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp]),
+    "p2phd_xspec_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "p2phd_xspec": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "p2phd_stereo_bands": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "p2phd_stereo_matrix": (_i32, [_vp, _i64, _i64, _f32, _i32, _vp, _i64, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -60,17 +60,23 @@ generator was given, of the generated clip and, for a full-band input, of the or
 spectrum that still stands within `--bandwidth_threshold_db` (60) of the strongest band, found on the device, with a remark where
 the input stops short of the low rate's Nyquist frequency or the original carries nothing above it (`ltas`, `bandwidth_detect`,
 `bandwidth`).  `--crossover_hz auto` uses the same measurement per clip: the crossover keeps of the input only the band the input has.
+
+`--stereo_report` (opt-in, csrc/stereo.hip) reports how the two channels of a file written with two channels correlate below and
+above the low rate's Nyquist frequency -- for the input the generator was given, the generated clip and the original -- from the
+long-term cross-spectrum of the pair, with a remark where the generated clip's new band has lost the correlation of its low band
+(`cross_spectrum`, `stereo_bands`, `stereo_image`, `stereo_figures`).  `--stereo ms` (`SuperResolver(stereo='ms')`) is the remedy:
+mid and side are generated instead of left and right, so what the channels share is invented once (`stereo_matrix`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
-from .ops import (PCM_FORMATS, bandwidth, bandwidth_detect, ltas, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
+from .ops import (PCM_FORMATS, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
-from .plans import (ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
+from .plans import (ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,
                     check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, limiter_plan, loudness_channel_weights, plan_folder,
                     segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
 from .report import (METRICS_COLUMNS, METRICS_COLUMNS_BANDWIDTH, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_LOUDNESS_RANGE, METRICS_COLUMNS_PEAKS,  # noqa: F401
-                     METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
+                     METRICS_COLUMNS_STEREO, METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

@@ -82,6 +82,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
         entries.append(entry)
         try:
             read = sr._read(path_in)
+            if getattr(sr, 'stereo', 'lr') == 'ms':                         # (more than two channels: a skipped file with its reason)
+                sr._check_stereo_channels(channels, read[1].num_channels)
         except (ValueError, OSError, EOFError, struct.error) as e:
             rec['error'] = '%s: %s' % (type(e).__name__, e)
             continue

@@ -11,8 +11,8 @@ from types import SimpleNamespace
 import torch
 
 from .plans import (CLIP_MODES, CROSSOVER_AUTO, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_output_options, check_paths, check_spectrogram, check_bandwidth, spectro_bins)
-from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_unwritten, metrics_rows, write_metrics_csv
+                    check_output_options, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, spectro_bins)
+from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -99,6 +99,18 @@ def _bandwidth_args(a):
         return {}
     check_bandwidth(True, opts or None, a.loudness_scope, "generate")
     return dict(bandwidth=True, bandwidth_opts=opts or None)
+
+
+def _stereo_args(a):
+    """The stereo report options of the command line -> the keyword arguments of enhance_file / enhance_folder ({} without
+    --stereo_report); ValueError for a bad one."""
+    opts = {k: v for k, v in (('n_fft', a.stereo_n_fft), ('hop', a.stereo_hop)) if v is not None}
+    if not a.stereo_report:
+        if opts:
+            raise ValueError("--stereo_%s is an option of --stereo_report" % sorted(opts)[0])
+        return {}
+    check_stereo_report(True, opts or None, a.loudness_scope, "generate")
+    return dict(stereo_report=True, stereo_report_opts=opts or None)
 
 
 def _loudness_args(a, hr_rate=None, folder_mode=False):
@@ -257,6 +269,19 @@ def _parser():
                     help="--bandwidth: STFT length of the long-term average spectrum, a power of two in 64 .. 2048, hop N / 2 (default 2048)")
     ap.add_argument("--bandwidth_band_bins", type=int, default=None, metavar="N",
                     help="--bandwidth: bins per band whose mean level is compared with the threshold (default 8)")
+    ap.add_argument("--stereo", default="lr", choices=("lr", "ms"),
+                    help="how a two-channel file is generated: lr -- left and right each a clip of its own, so the band above the low "
+                         "rate's Nyquist frequency is invented twice; ms -- mid and side: what the channels share is invented once, only "
+                         "their difference on its own (one channel runs as with lr; more than two are refused) (default: lr)")
+    ap.add_argument("--stereo_report", action="store_true",
+                    help="report how the left and right channel of a file written with two channels correlate below and above the low "
+                         "rate's Nyquist frequency -- for the input the generator was given, the generated clip and, for a full-band "
+                         "input, the original; one more line per such file, one per remark, and four more columns (corr_lf_out, "
+                         "corr_hf_out, corr_hf_orig, side_hf_out_db) of --metrics_csv; not with --loudness_scope folder (default: off)")
+    ap.add_argument("--stereo_n_fft", type=int, default=None, metavar="N",
+                    help="--stereo_report: STFT length of the cross-spectrum, a power of two in 64 .. 2048 (default 2048)")
+    ap.add_argument("--stereo_hop", type=int, default=None, metavar="N",
+                    help="--stereo_report: hop of the cross-spectrum, 1 .. N of --stereo_n_fft (default: half of it)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -278,6 +303,7 @@ def main(argv=None):
         picture = _spectrogram_args(a, folder_mode)
         picture.update(_loudness_args(a, None, folder_mode))
         picture.update(_bandwidth_args(a))
+        picture.update(_stereo_args(a))
         if a.true_peak:
             picture['true_peak'] = True
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
@@ -313,7 +339,7 @@ def main(argv=None):
     sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
                        reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
                        lowband=a.lowband, lowband_fade=a.lowband_fade, crossover=a.crossover, crossover_hz=a.crossover_hz,
-                       crossover_taps=a.crossover_taps)
+                       crossover_taps=a.crossover_taps, **({} if a.stereo == 'lr' else {'stereo': a.stereo}))
     print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
@@ -321,6 +347,8 @@ def main(argv=None):
         print("crossover: the input below 0.95 of where its own band ends, at most %g Hz (auto)" % (sr.crossover_plan[1] * opt.hr_sampling_rate))
     elif sr.crossover_plan is not None:                                     # (without the option: no line more than before)
         print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
+    if sr.stereo == 'ms':                                                   # (without the option: no line more than before)
+        print('stereo: mid / side')
     rate = int(opt.hr_sampling_rate)
     try:
         return _run(a, sr, stage, seed, rate, folder_mode)
@@ -352,6 +380,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 _print_crossover(r['crossover'])
             if r.get('bandwidth') is not None:
                 _print_bandwidth(r['path'], r['bandwidth'])
+            if r.get('stereo') is not None:
+                _print_stereo(r['path'], r['stereo'])
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -392,10 +422,14 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_crossover(res['crossover'])
         if res.get('bandwidth') is not None:
             _print_bandwidth(a.output, res['bandwidth'])
+        if res.get('stereo') is not None:
+            _print_stereo(a.output, res['stereo'])
         records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
                     'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
         if a.bandwidth:
             records[0]['bandwidth'] = res['bandwidth']
+        if a.stereo_report:
+            records[0]['stereo'] = res['stereo']
     if a.metrics_csv:
         extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
         if a.limiter:
@@ -406,6 +440,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             extra['album'] = True
         if a.bandwidth:
             extra['bandwidth'] = True
+        if a.stereo_report:
+            extra['stereo'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -1,12 +1,12 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip and csrc/bandwidth.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip and csrc/stereo.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
 from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
-                    check_encoding, check_loudness_rate, limiter_plan, spectrogram_lut, truepeak_plan)
+                    check_encoding, check_loudness_rate, limiter_plan, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -507,6 +507,80 @@ def bandwidth(waveform, rate, plan=None, out=None):
         raise ValueError("bandwidth: the rate must be a number > 0, got %r" % (rate,))
     psd = ltas(waveform, p['n_fft'], p['hop'])
     return bandwidth_detect(psd, psd.shape[0], p['band_bins'], p['threshold_db'], out).view(4)
+
+
+def cross_spectrum(rows, n_fft, hop):
+    """rows [2 G, L] f32 on the GPU (rows contiguous, any row pitch), rows 2 g and 2 g + 1 the left and right channel of pair g
+    -> xs [G, 4, K] float64 on the GPU, K = n_fft // 2 + 1: the long-term cross-spectrum over ltas's frames (only those wholly
+    inside the clip), window and scale -- per bin the float64 sums in a fixed order of |A|^2, |B|^2, Re(A conj B) and Im(A conj B),
+    A and B the two channels' transforms (p2phd_xspec).  L < n_fft: zeros.  One launch of the family "stereo" (none where F = 0);
+    the same bits on every run, and pair g of a call is the call on that pair.  Nothing is waited for."""
+    x, R, L, ld = _rows(rows, "cross_spectrum: rows")
+    if R % 2:
+        raise ValueError("cross_spectrum: expected [2 * G, L], the left and right rows of G pairs, got shape %s" % (tuple(x.shape),))
+    G = R // 2
+    lib = _lib.lib()
+    F = lib.p2phd_ltas_frames(L, int(n_fft), int(hop))
+    if F < 0:
+        _lib.check(-1, "ltas_frames")
+    xs = torch.empty((G, 4, int(n_fft) // 2 + 1), dtype=torch.float64, device=x.device)
+    tables = work = None
+    if F > 0:
+        tables = _specimg_tables(n_fft, x.device)
+        work = torch.empty((lib.p2phd_xspec_workspace_bytes(G, L, int(n_fft), int(hop)),), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.p2phd_xspec(_lib.ptr(x), max(ld, L), G, L, int(n_fft), int(hop), _lib.ptr(tables), _lib.ptr(xs), _lib.ptr(work),
+                               _lib.stream_ptr()), "xspec")
+    return xs
+
+
+def stereo_bands(xs, k_split, out=None):
+    """xs [G, 4, K] float64 on the GPU (cross_spectrum) -> res [G, 8] float64 on the GPU, nothing waited for: {S_ll, S_rr, Re, Im}
+    summed over the bins [0, k_split), then over [k_split, K) (p2phd_stereo_bands, whose float64 order include/p2phd.h writes down).
+    `out`: None, or a contiguous float64 tensor of G * 8 on the GPU that takes the result.  One launch of the family "stereo"."""
+    xx = _lib.require_gpu_tensor(xs, "stereo_bands: xs", torch.float64)
+    if xx.dim() != 3 or xx.shape[1] != 4:
+        raise ValueError("stereo_bands: expected xs [G, 4, K], got shape %s" % (tuple(xx.shape),))
+    G, K = xx.shape[0], xx.shape[2]
+    if out is None:
+        out = torch.empty((G, 8), dtype=torch.float64, device=xx.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "stereo_bands: out", torch.float64)
+        if out.numel() != G * 8:
+            raise ValueError("stereo_bands: out must hold %d float64, got %d" % (G * 8, out.numel()))
+    _lib.check(_lib.lib().p2phd_stereo_bands(_lib.ptr(xx), G, K, int(k_split), _lib.ptr(out), _lib.stream_ptr()), "stereo_bands")
+    return out.view(G, 8)
+
+
+def stereo_image(waveform, hr_rate, lr_rate, plan=None, out=None):
+    """cross_spectrum and stereo_bands in a row: waveform [2, L] f32 on the GPU at `hr_rate` -> res [8] float64 on the GPU, the four
+    sums below and the four at and above the low rate's Nyquist frequency (plans.stereo_split_bin; plans.stereo_figures turns the
+    fetched eight into correlation, coherence, side level and balance).  `plan`: {'n_fft', 'hop'} (plans.check_stereo_report; None:
+    STEREO_DEFAULTS).  `out`: None, or a float64 tensor of 8 on the GPU that takes the result.  Two launches of the family "stereo"
+    (one where the clip is shorter than n_fft), nothing is waited for.  Anything but two rows is a ValueError."""
+    p = STEREO_DEFAULTS if plan is None else plan
+    if not isinstance(waveform, torch.Tensor) or waveform.dim() != 2 or waveform.shape[0] != 2:
+        raise ValueError("stereo_image: expected a waveform [2, L], left and right, got shape %s"
+                         % (tuple(waveform.shape) if isinstance(waveform, torch.Tensor) else type(waveform).__name__,))
+    k_split = stereo_split_bin(hr_rate, lr_rate, p['n_fft'])
+    return stereo_bands(cross_spectrum(waveform, p['n_fft'], p['hop']), k_split, out).view(8)
+
+
+def stereo_matrix(x, a, guard_side=False, out=None):
+    """x [2, L] f32 on the GPU (rows contiguous, any row pitch) -> a new [2, L]: row 0 = a * (x0 + s), row 1 = a * (x0 - s) with
+    s = x1 and, with `guard_side`, +0 where x1 is not finite (p2phd_stereo_matrix; plain fp32, what numpy float32 gives).  a = 0.5
+    encodes left / right as mid / side, a = 1 with the guard decodes.  `out`: None, or a [2, L] f32 tensor on the GPU that takes
+    the result -- `x` itself is allowed (in place), any other overlap is not.  One launch of the family "stereo" (none for L = 0)."""
+    xx, C, L, ld = _rows(x, "stereo_matrix: x")
+    if C != 2:
+        raise ValueError("stereo_matrix: expected [2, L], got shape %s" % (tuple(xx.shape),))
+    if out is None:
+        out = torch.empty((2, L), dtype=torch.float32, device=xx.device)
+    oo, Co, Lo, ld_o = _rows(out, "stereo_matrix: out")
+    if (Co, Lo) != (2, L):
+        raise ValueError("stereo_matrix: out must have the shape of x, got %s and %s" % (tuple(oo.shape), tuple(xx.shape)))
+    _lib.check(_lib.lib().p2phd_stereo_matrix(_lib.ptr(xx), max(ld, L), L, float(a), 1 if guard_side else 0, _lib.ptr(oo), max(ld_o, L),
+                                              _lib.stream_ptr()), "stereo_matrix")
+    return oo
 
 
 _LIMITER_WINDOWS = {}                                                      # (lookahead, device) -> the window on the device

@@ -1,6 +1,7 @@
 """Whole-file generation: the host arithmetic and the validation of every option -- no tensor, no library."""
 import math
 import os
+from fractions import Fraction
 
 # encoding of wavio.save / wavio.write_payload -> (P2PHD_PCM_* code of include/p2phd.h, bytes per sample)
 PCM_ENCODINGS = {'pcm16': (1, 2), 'pcm24': (2, 3), 'float32': (4, 4)}
@@ -15,6 +16,13 @@ CROSSOVER_AUTO = 'auto'                                                     # cr
 # the bandwidth report (csrc/bandwidth.hip): STFT length and hop of the long-term average spectrum, bins of a band, dB under the
 # strongest band at which the band ends
 BANDWIDTH_DEFAULTS = {'n_fft': 2048, 'hop': 1024, 'band_bins': 8, 'threshold_db': 60.0}
+# the stereo image report and the mid/side mode (csrc/stereo.hip): how a two-channel clip is generated -- 'lr': every channel a clip of
+# its own; 'ms': mid and side, so that what the channels share is invented once --, STFT length and hop of the cross-spectrum, and
+# how far the generated clip's correlation above the split may fall under the one below it before the report remarks on it (a
+# reporting threshold like the bandwidth notes' 0.9 / 1.05, not a measurement)
+STEREO_MODES = ('lr', 'ms')
+STEREO_DEFAULTS = {'n_fft': 2048, 'hop': 1024}
+STEREO_NOTE_DROP = 0.3
 # the spectrogram picture (csrc/specimg.hip): STFT length and hop in samples, pixels of one panel, dB below the top that
 # reach the palette's first colour, grey rows between panels
 SPECTROGRAM_DEFAULTS = {'n_fft': 1024, 'hop': 256, 'width': 1600, 'height': 512, 'range_db': 90.0, 'gap': 2}
@@ -280,6 +288,103 @@ def bandwidth_notes(input_hz, original_hz, lr_nyquist):
         notes.append("the original's band ends at %.2f kHz, the low rate's Nyquist frequency is %.2f kHz: the original carries nothing above "
                      "it: LSD-HF compares against an empty band" % (original_hz / 1000.0, lr_nyquist / 1000.0))
     return notes
+
+
+def stereo_split_bin(hr_rate, lr_rate, n_fft):
+    """The bin at which the stereo report splits the spectrum: the first bin of an n_fft-point transform at `hr_rate` that lies at or
+    above the low rate's Nyquist frequency, ceil(lr_rate n_fft / (2 hr_rate)) in exact arithmetic.  ValueError unless it lies in
+    [1, K - 1], K = n_fft / 2 + 1: both bands need a bin."""
+    for name, v in (('hr_rate', hr_rate), ('lr_rate', lr_rate)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 < v < float('inf'):
+            raise ValueError("stereo_split_bin: %s must be a number > 0, got %r" % (name, v))
+    if not _is_int(n_fft) or n_fft < 2:
+        raise ValueError("stereo_split_bin: n_fft must be an int >= 2, got %r" % (n_fft,))
+    k = math.ceil(Fraction(lr_rate) * n_fft / (2 * Fraction(hr_rate)))
+    K = n_fft // 2 + 1
+    if not 1 <= k <= K - 1:
+        raise ValueError("stereo_split_bin: the low rate's Nyquist frequency %g Hz falls on bin %d of %d at %g Hz: the split must lie in "
+                         "[1, %d]" % (lr_rate / 2.0, k, K, hr_rate, K - 1))
+    return k
+
+
+def check_stereo(stereo='lr', who="SuperResolver"):
+    """Validates the stereo mode -> the mode, one of STEREO_MODES."""
+    if stereo not in STEREO_MODES:
+        raise ValueError("%s: stereo must be 'lr' or 'ms', got %r" % (who, stereo))
+    return stereo
+
+
+def check_stereo_report(stereo_report=False, opts=None, loudness_scope='file', who="enhance_file"):
+    """Validates the stereo report option -> None (off), or the plan {'n_fft', 'hop'} that ops.stereo_image takes.  `stereo_report`:
+    a bool.  `opts`: None or a dict of those two, None or absent standing for STEREO_DEFAULTS' value (hop: half of a given n_fft):
+    `n_fft` a power of two in [64, 2048]; `hop` 1 .. n_fft.  They are options of the option.  The report is one file's: with
+    loudness_scope 'folder' it is a ValueError, as the bandwidth report is.  A ValueError names the argument."""
+    if not isinstance(stereo_report, bool):
+        raise ValueError("%s: stereo_report must be a bool, got %r" % (who, stereo_report))
+    if opts is not None and not isinstance(opts, dict):
+        raise ValueError("%s: stereo_report_opts must be None or a dict, got %r" % (who, opts))
+    if not stereo_report:
+        if opts is not None:
+            raise ValueError("%s: stereo_report_opts are options of stereo_report=True; stereo_report is False" % who)
+        return None
+    if loudness_scope == 'folder':
+        raise ValueError("%s: stereo_report is not built for loudness_scope='folder': the report is measured per file" % who)
+    opts = {k: v for k, v in (opts or {}).items() if v is not None}
+    unknown = sorted(set(opts) - set(STEREO_DEFAULTS))
+    if unknown:
+        raise ValueError("%s: unknown stereo_report_opts %s" % (who, unknown))
+    n_fft = opts.get('n_fft', STEREO_DEFAULTS['n_fft'])
+    if not _is_int(n_fft) or not 64 <= n_fft <= 2048 or n_fft & (n_fft - 1):
+        raise ValueError("%s: stereo_report n_fft must be a power of two in [64, 2048], got %r" % (who, n_fft))
+    hop = opts.get('hop', STEREO_DEFAULTS['hop'] if 'n_fft' not in opts else n_fft // 2)
+    if not _is_int(hop) or not 1 <= hop <= n_fft:
+        raise ValueError("%s: stereo_report hop must be an int in [1, n_fft = %d], got %r" % (who, n_fft, hop))
+    return {'n_fft': n_fft, 'hop': hop}
+
+
+def _ratio_db(num, den):
+    """10 log10(num / den) of two sums that are powers up to rounding: None where both vanish, +inf where only the denominator does,
+    -inf where only the numerator does (a sum a rounding error under zero counts as vanished); NaN stays NaN."""
+    if num != num or den != den:
+        return float('nan')
+    if den <= 0.0:
+        return None if num <= 0.0 else float('inf')
+    if num <= 0.0:
+        return float('-inf')
+    if num == float('inf') or den == float('inf'):
+        return float('nan') if num == den else (float('inf') if num > den else float('-inf'))
+    return 10.0 * math.log10(num / den)
+
+
+def stereo_figures(res8):
+    """The eight fetched sums of p2phd_stereo_bands ({S_ll, S_rr, Re, Im} below the split, then above it) -> {'low': figures, 'high':
+    figures}, host arithmetic in float64.  figures = {'corr': Re / sqrt(S_ll S_rr), the correlation of the band's two channels;
+    'coherence': hypot(Re, Im) / sqrt(S_ll S_rr), which a delay between the channels does not lower; 'side_db': 10 log10((S_ll + S_rr
+    - 2 Re) / (S_ll + S_rr + 2 Re)), the level of L - R against L + R; 'balance_db': 10 log10(S_ll / S_rr)}.  None where a
+    denominator is zero (an empty band, a silent channel), +-inf where a ratio is."""
+    v = [float(t) for t in res8]
+    if len(v) != 8:
+        raise ValueError("stereo_figures: expected the eight sums of two bands, got %d values" % len(v))
+    out = {}
+    for name, (ll, rr, re, im) in (('low', v[:4]), ('high', v[4:])):
+        prod = ll * rr
+        den = math.sqrt(prod) if prod > 0.0 else (float('nan') if prod != prod else 0.0)
+        out[name] = {'corr': None if den == 0.0 else re / den,
+                     'coherence': None if den == 0.0 else math.hypot(re, im) / den,
+                     'side_db': _ratio_db(ll + rr - 2.0 * re, ll + rr + 2.0 * re),
+                     'balance_db': _ratio_db(ll, rr)}
+    return out
+
+
+def stereo_notes(output, mode):
+    """The one remark of the stereo report, host logic.  `output`: the generated clip's {'low', 'high'} figures; `mode`: the mode
+    it was generated in.  With 'lr', a correlation above the split that is more than STEREO_NOTE_DROP under the one below it: the
+    channels' new band was invented twice, which stereo='ms' avoids."""
+    lo, hi = output['low']['corr'], output['high']['corr']
+    if mode != 'lr' or lo is None or hi is None or not hi < lo - STEREO_NOTE_DROP:
+        return []
+    return ["the generated clip's channels correlate %+.2f above the split and %+.2f below it: left and right were generated "
+            "independently; stereo='ms' (--stereo ms) generates what they share once" % (hi, lo)]
 
 
 def _is_int(v):

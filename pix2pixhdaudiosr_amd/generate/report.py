@@ -9,6 +9,7 @@ METRICS_COLUMNS_LOUDNESS_RANGE = ("lra_in", "lra_out", "short_term_max")        
 METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                         # --true_peak
 METRICS_COLUMNS_LIMITER = ("limiter_reduction_db", "limited_samples")                   # --limiter
 METRICS_COLUMNS_BANDWIDTH = ("bw_in", "bw_out", "bw_orig")                              # --bandwidth (behind every other column)
+METRICS_COLUMNS_STEREO = ("corr_lf_out", "corr_hf_out", "corr_hf_orig", "side_hf_out_db")   # --stereo_report (behind those too)
 
 
 def _mean(values):
@@ -20,7 +21,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False, bandwidth=False):
+def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False, bandwidth=False, stereo=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -41,10 +42,17 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, lo
         cols += [(lambda r, c: r['output']['limiter']['max_reduction_db'], _mean), (lambda r, c: r['output']['limiter']['limited_samples'], _mean)]
     if bandwidth:
         cols += [(lambda r, c, n=n: float('nan') if r['bandwidth'][n] is None else r['bandwidth'][n], _nanmean) for n in ('input', 'output', 'original')]
+    if stereo:
+        def figure(r, clip, band, name):
+            f = None if r.get('stereo') is None or r['stereo'][clip] is None else r['stereo'][clip][band][name]
+            return float('nan') if f is None else f
+        cols += [(lambda r, c, k=k: figure(r, *k), _nanmean) for k in (('output', 'low', 'corr'), ('output', 'high', 'corr'), ('original', 'high', 'corr'),
+                                                                    ('output', 'high', 'side_db'))]
     return cols
 
 
-def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False, bandwidth=False):
+def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False, bandwidth=False,
+                 stereo=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -63,8 +71,13 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     and the one gain in the loudness columns, every other cell empty; the files' rows keep the tracks' own figures.  `bandwidth`:
     the records carry 'bandwidth' and a row ends, behind every other column, with the columns of METRICS_COLUMNS_BANDWIDTH -- where
     the band of the file's input, of its generated clip and of its original ends, in Hz (the file's figures, the same in each of its
-    channels' rows); plain means."""
-    if bandwidth:
+    channels' rows); plain means.  `stereo`: the records carry 'stereo' and a row ends, behind those too, with the columns of
+    METRICS_COLUMNS_STEREO -- the generated clip's correlation below and above the split, the original's above it and the generated
+    clip's side level above it in dB (the file's figures; nan where the file has no stereo image or no such figure); means over
+    the rows that have one."""
+    if stereo:
+        cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth, stereo)
+    elif bandwidth:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth)
     elif loudness_range:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range)
@@ -86,13 +99,14 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
 
 
 def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False,
-                      bandwidth=False):
+                      bandwidth=False, stereo=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
                    + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_LOUDNESS_RANGE if loudness_range else ())
                    + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
-                   + (METRICS_COLUMNS_LIMITER if limiter else ()) + (METRICS_COLUMNS_BANDWIDTH if bandwidth else ()))
+                   + (METRICS_COLUMNS_LIMITER if limiter else ()) + (METRICS_COLUMNS_BANDWIDTH if bandwidth else ())
+                   + (METRICS_COLUMNS_STEREO if stereo else ()))
         extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
         if limiter:
             extra['limiter'] = True
@@ -102,6 +116,8 @@ def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False
             extra['album'] = True
         if bandwidth:
             extra['bandwidth'] = True
+        if stereo:
+            extra['stereo'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -161,3 +177,15 @@ def _print_bandwidth(name, b):
 
 def _print_crossover(x):
     print('crossover: %.2f kHz, %d taps (input band ends at %.2f kHz)' % (x['hz'] / 1000.0, x['taps'], x['edge_hz'] / 1000.0))
+
+
+def _corr(f):
+    return 'n/a' if f is None else '%+.2f' % f
+
+
+def _print_stereo(name, s):
+    clips = [(k, s[k]) for k in ('input', 'output', 'original') if s[k] is not None]
+    print('%s: stereo correlation below / above %.2f kHz: %s'
+          % (name, s['split_hz'] / 1000.0, ', '.join('%s %s / %s' % (k, _corr(f['low']['corr']), _corr(f['high']['corr'])) for k, f in clips)))
+    for note in s['notes']:
+        print('%s: note: %s' % (name, note))

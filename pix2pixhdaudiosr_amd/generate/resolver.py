@@ -5,9 +5,9 @@ import struct
 
 import torch
 
-from .ops import (bandwidth as _bandwidth, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+from .ops import (bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (BANDWIDTH_DEFAULTS, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -75,10 +75,17 @@ class SuperResolver:
     rest, where the fixed crossover would copy an empty band.  An input that reaches the Nyquist frequency gets the default plan and
     the default bytes.  The 32 bytes of the measurement come back on a side stream behind an event recorded in front of the first
     group, so the host waits for two small launches, not for the generator; coefficients are cached per band edge.
-    `last_crossover` then holds {'hz', 'taps', 'edge_hz'} of the latest clip."""
+    `last_crossover` then holds {'hz', 'taps', 'edge_hz'} of the latest clip.
+    `stereo`: 'lr' (the default) | 'ms', fixed for the object's life.  With 'lr' every channel is a clip of its own, so the band
+    above the low rate's Nyquist frequency of a two-channel clip is invented twice, independently.  'ms' generates mid and side
+    instead: a [2, L] clip is encoded as ((L + R) / 2, (L - R) / 2) (csrc/stereo.hip), goes through the unchanged per-channel
+    pipeline -- mask-noise row block 0 is the mid signal's, block 1 the side's; the crossover's low band is the encoded input -- and
+    is decoded as (M + S, M - S), a non-finite side sample read as 0: what the channels share is invented once.  The auto
+    crossover's measurement stays on left / right.  Two launches of the family "stereo" per two-channel clip; one channel runs as
+    with 'lr', more than two are a ValueError."""
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
-                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None):
+                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr'):
         from ..models.mdct import IMDCT2, IMDCT4
         from ..util import util as U
         self.model, self.opt = model, opt
@@ -123,6 +130,7 @@ class SuperResolver:
         self._xover_auto = {}                                               # k_top -> (plan, edge, the coefficients on the device)
         self._side = None                                                   # the stream the auto crossover's measurement comes back on
         self.last_crossover = None                                          # auto: {'hz', 'taps', 'edge_hz'} of the latest clip
+        self.stereo = check_stereo(stereo)
         self._g = None                                                      # captured chain of a full group
         self._pins = {}                                                     # pinned host buffers of the file path, grow-only
 
@@ -206,11 +214,19 @@ class SuperResolver:
         x = x.contiguous()
         C, L = x.shape
         S, stride, V = segment_plan(L, self.T, self.overlap)
+        ms = getattr(self, 'stereo', 'lr') == 'ms' and C != 1               # (one channel runs as ever, with no launch of the family)
+        if ms and C != 2:
+            raise ValueError("enhance_lr: stereo='ms' takes one or two channels, got %d" % C)
         measured = None
         if self.crossover_auto:
             # the two measurement launches and their event go in front of every group: the host then waits for them alone
             measured = (_bandwidth(x, float(self.opt.hr_sampling_rate)), torch.cuda.Event())
             measured[1].record()
+        if ms:
+            # behind the auto crossover's measurement, which stays on left / right: its plan is the one 'lr' gets.  From here on the
+            # two rows are mid and side -- the segments, the groups' normalisation, the mask-noise row blocks and the crossover's
+            # low band (a linear filter commutes with the matrix)
+            x = stereo_matrix(x, 0.5)
         seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
         for c in range(C):
@@ -229,13 +245,20 @@ class SuperResolver:
                 else:
                     out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz))
         sr = segments_stitch_planar(out, C, stride, self.gain, L)
-        if self.crossover_plan is None:
-            return sr
-        if measured is not None:
-            return crossover(sr, x, self.gain / 2.0, self._auto_taps(*measured))
-        if self._xover_taps is None:
-            self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
-        return crossover(sr, x, self.gain / 2.0, self._xover_taps)
+        if self.crossover_plan is not None:
+            if measured is not None:
+                taps = self._auto_taps(*measured)
+            else:
+                if self._xover_taps is None:
+                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
+                taps = self._xover_taps
+            sr = crossover(sr, x, self.gain / 2.0, taps)
+        if ms:
+            # back to left / right, in place.  A side signal of digital silence (dual mono) leaves the chain as NaN -- its group is
+            # scaled by 1 / (max - min) --: the decoder reads a non-finite side sample as "no side here"
+            sr = sr.contiguous()
+            stereo_matrix(sr, 1.0, guard_side=True, out=sr)
+        return sr
 
     def _auto_taps(self, res_dev, event):
         """crossover_hz 'auto': the clip's measurement (ops.bandwidth's 32 bytes on the device, `event` recorded behind it) -> the
@@ -296,7 +319,7 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
         back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
@@ -306,7 +329,7 @@ class SuperResolver:
         clip, clip 'guard' takes its gain from it, and its figures come back likewise.  `limiter`: the limiter option
         (_limiter_option; it comes with a stage and the true-peak option): the limiter runs in front of the peak kernel, everything
         behind it sees the limited clip, and its figures come back likewise.  `bandwidth`: the bandwidth measurement
-        (_measure_bandwidth), whose packed results come back likewise."""
+        (_measure_bandwidth), whose packed results come back likewise; `stereo`: the stereo measurement (_measure_stereo), likewise."""
         w = sr.contiguous()
         extra = {} if true_peak is None else {'true_peak': true_peak}
         if limiter is not None:
@@ -315,6 +338,8 @@ class SuperResolver:
         fetch = extra if loudness is None else dict(extra, loudness=loudness)
         if bandwidth is not None:
             fetch = dict(fetch, bandwidth=bandwidth)
+        if stereo is not None:
+            fetch = dict(fetch, stereo=stereo)
         host, stats = self._fetch(dev, packed, picture, **fetch)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
         if host is not None:
@@ -340,14 +365,20 @@ class SuperResolver:
             return None, packed
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
 
-    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None):
+    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
         -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
         copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
         (the two gate results, a device tensor) is copied and replaced likewise; `true_peak`: None, or a dict whose 'packed' (the
         packed true-peak buffer) is, into a pinned slot of its own; `limiter`: None, or a dict whose 'packed' (the limiter's 12
-        bytes) is, into another; `bandwidth`: None, or a dict whose 'packed' (the clips' 32-byte results) is, into another."""
+        bytes) is, into another; `bandwidth`: None, or a dict whose 'packed' (the clips' 32-byte results) is, into another; `stereo`:
+        None, or a dict whose 'packed' (the clips' 64-byte results) is, into another."""
         host = stats = None
+        if stereo is not None:
+            n = stereo['packed'].numel()
+            pin = self._pinned('stereo', n)[:n]
+            pin.copy_(stereo['packed'], non_blocking=True)
+            stereo['packed'] = pin
         if bandwidth is not None:
             n = bandwidth['packed'].numel()
             pin = self._pinned('bandwidth', n)[:n]
@@ -511,12 +542,38 @@ class SuperResolver:
                 'n_fft': bw['n_fft'], 'hop': bw['hop'], 'band_bins': bw['band_bins'], 'frames': measure['frames'],
                 'notes': bandwidth_notes(hz[0], hz[2], nyquist)}
 
+    def _measure_stereo(self, st, lr, sr, hr):
+        """The device work of the stereo report on a two-channel file: the clip the generator was given, the generated clip and,
+        where there is one, the original through the cross-spectrum and the band sums (two launches of the family "stereo" each) ->
+        {'packed': their results of 64 bytes one behind the other, 'clips', 'frames'}."""
+        clips = [t for t in (lr, sr, hr) if t is not None]
+        packed = torch.empty((64 * len(clips),), dtype=torch.uint8, device=sr.device)
+        hr_rate, lr_rate = self.opt.hr_sampling_rate, self.opt.lr_sampling_rate
+        for i, clip in enumerate(clips):
+            _stereo_image(clip, hr_rate, lr_rate, st, out=packed[64 * i:64 * i + 64].view(torch.float64))
+        L = sr.shape[-1]
+        return {'packed': packed, 'clips': len(clips), 'frames': 1 + (L - st['n_fft']) // st['hop'] if L >= st['n_fft'] else 0}
+
+    def _stereo_result(self, st, measure):
+        """The fetched measurement -> the result's 'stereo'."""
+        figures = [stereo_figures(measure['packed'][64 * i:64 * i + 64].view(torch.float64).tolist()) for i in range(measure['clips'])] + [None]
+        mode = getattr(self, 'stereo', 'lr')
+        k = stereo_split_bin(self.opt.hr_sampling_rate, self.opt.lr_sampling_rate, st['n_fft'])
+        return {'input': figures[0], 'output': figures[1], 'original': figures[2], 'split_hz': k * float(self.opt.hr_sampling_rate) / st['n_fft'],
+                'n_fft': st['n_fft'], 'hop': st['hop'], 'frames': measure['frames'], 'mode': mode, 'notes': stereo_notes(figures[1], mode)}
+
+    def _check_stereo_channels(self, channels, available):
+        """stereo='ms' generates one or two channels: a file of which more would be written is refused before anything runs."""
+        if getattr(self, 'stereo', 'lr') == 'ms' and select_channels(channels, available) > 2:
+            raise ValueError("stereo='ms' takes one or two channels, %d would be written" % select_channels(channels, available))
+
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
-                         lim=None, bw=None):
+                         lim=None, bw=None, st=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
         7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
         `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak).  `lim`: None,
-    or the limiter option (_limiter_option).  `bw`: None, or the bandwidth option (check_bandwidth)."""
+    or the limiter option (_limiter_option).  `bw`: None, or the bandwidth option (check_bandwidth).  `st`: None, or the stereo
+        report option (check_stereo_report)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -524,6 +581,7 @@ class SuperResolver:
         check_encoding(encoding, "enhance_file")
         k = select_channels(channels, meta.num_channels)
         self._check_picture_channel(spec, channels, meta.num_channels)
+        self._check_stereo_channels(channels, meta.num_channels)
         if loud is not None and k > LOUDNESS_MAX_CHANNELS:
             raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
         rate = meta.sample_rate
@@ -535,6 +593,8 @@ class SuperResolver:
         sr = self.enhance_lr(lr)
         # the generated clip behind the crossover and in front of the loudness gain: the figure is relative, a gain does not move it
         band = None if bw is None else self._measure_bandwidth(bw, lr, sr, raw if has_hr else None)
+        # likewise behind the crossover and the mid/side decode; a file written with another channel count has no stereo image
+        image = None if st is None or sr.shape[0] != 2 else self._measure_stereo(st, lr, sr, raw if has_hr else None)
         auto = getattr(self, 'crossover_auto', False)                       # (an object built without __init__ has no crossover at all)
         xover = dict(self.last_crossover) if auto else None
         metrics = ext = None
@@ -552,8 +612,10 @@ class SuperResolver:
             if loud['mode'] != 'report':
                 sr = sr * measure['gain']
         picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
-        if path_out is not None or stage is not None or picture is not None or measure is not None or band is not None:
+        if path_out is not None or stage is not None or picture is not None or measure is not None or band is not None or image is not None:
             extra = {} if measure is None else {'loudness': measure}
+            if image is not None:
+                extra['stereo'] = image
             if band is not None:
                 extra['bandwidth'] = band
             if tp is not None:
@@ -570,6 +632,8 @@ class SuperResolver:
             res['bandwidth'] = self._bandwidth_result(bw, band)
         if xover is not None:
             res['crossover'] = xover
+        if st is not None:
+            res['stereo'] = None if image is None else self._stereo_result(st, image)
         if extended_metrics:
             res['metrics_ext'] = ext
         if stage is not None:
@@ -580,7 +644,7 @@ class SuperResolver:
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
-                     bandwidth=False, bandwidth_opts=None):
+                     bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -661,8 +725,20 @@ class SuperResolver:
         'hop', 'band_bins', 'frames', 'notes' (a list of strings: an input whose band ends under 0.9 of the low rate's Nyquist
         frequency; an original whose band ends at or under 1.05 times it, so that LSD-HF compares against an empty band)}.
         With SuperResolver(crossover_hz='auto') -- whatever `bandwidth` is -- the result gains 'crossover': {'hz', 'taps', 'edge_hz'},
-        the crossover this clip got."""
+        the crossover this clip got.
+        `stereo_report` (opt-in, a bool): the stereo image of a file written with exactly two channels (csrc/stereo.hip) -- how its
+        left and right channel relate below and above the low rate's Nyquist frequency, for the clip the generator was given, for the
+        generated clip (behind the crossover and the mid/side decode, in front of the loudness gain, where the bandwidth report
+        measures) and, where the result has one, for the original: the long-term cross-spectrum over the frames wholly inside the
+        clip, summed over the bins below the split and over those at and above it (plans.stereo_split_bin), and on the host
+        plans.stereo_figures of the eight sums.  `stereo_report_opts`: None or a dict of n_fft, hop (plans.check_stereo_report;
+        STEREO_DEFAULTS).  At most six launches of the family "stereo" per file; the three results of 64 bytes come back with the
+        payload behind the same synchronisation.  The result gains 'stereo': {'input', 'output', 'original' ({'low', 'high'}, each
+        {'corr', 'coherence', 'side_db', 'balance_db'}; 'original' None without one), 'split_hz', 'n_fft', 'hop', 'frames', 'mode'
+        (the object's `stereo`), 'notes' (a list of strings: with mode 'lr', a generated clip whose correlation above the split is
+        more than STEREO_NOTE_DROP under the one below it)}; None for a file written with another channel count."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_file")
+        st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_file")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_file")
@@ -674,6 +750,8 @@ class SuperResolver:
             extra['lim'] = lim
         if bw is not None:
             extra['bw'] = bw
+        if st is not None:
+            extra['st'] = st
         if loud is None:
             res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
         else:
@@ -700,7 +778,8 @@ class SuperResolver:
                        extended_metrics=False, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False,
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
-                       loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None):
+                       loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
+                       stereo_report_opts=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -737,8 +816,13 @@ class SuperResolver:
         `spectrogram` are not built for this scope: a ValueError each, as is the scope without `loudness`.
         `bandwidth`, `bandwidth_opts`: enhance_file's, per file; a record then gains 'bandwidth' (as enhance_file returns it; None for
         a skipped file).  Not built for loudness_scope 'folder' either: a ValueError.  With SuperResolver(crossover_hz='auto') a
-        record gains 'crossover' (the file's; None for a skipped file), in either scope."""
+        record gains 'crossover' (the file's; None for a skipped file), in either scope.
+        `stereo_report`, `stereo_report_opts`: enhance_file's, per file; a record then gains 'stereo' (as enhance_file returns it; None
+        for a skipped file and for one written with another channel count than two).  Not built for loudness_scope 'folder': a
+        ValueError.  With SuperResolver(stereo='ms') a file of which more than two channels would be written is skipped, its record
+        carrying the 'error', in either scope."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
+        st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_folder")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
                                               self.opt.hr_sampling_rate, "enhance_folder")
@@ -756,6 +840,8 @@ class SuperResolver:
             extra['lim'] = lim
         if bw is not None:
             extra['bw'] = bw
+        if st is not None:
+            extra['st'] = st
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
@@ -772,9 +858,12 @@ class SuperResolver:
                 rec['bandwidth'] = None
             if getattr(self, 'crossover_auto', False):
                 rec['crossover'] = None
+            if st is not None:
+                rec['stereo'] = None
             try:
                 read = self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
+                self._check_stereo_channels(channels, read[1].num_channels)
             except (ValueError, OSError, EOFError, struct.error) as e:
                 rec['error'] = '%s: %s' % (type(e).__name__, e)
             else:
@@ -799,6 +888,8 @@ class SuperResolver:
                     rec['bandwidth'] = res['bandwidth']
                 if 'crossover' in res:
                     rec['crossover'] = res['crossover']
+                if st is not None:
+                    rec['stereo'] = res['stereo']
             records.append(rec)
             if report is not None:
                 report(rec)

@@ -58,6 +58,13 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             and at an hour's; with --off_only only the run without any option is timed (one process of an alternating comparison
             with another checkout); log in --bandwidth_log
 
+  stereo    (only when asked for) enhance_file on a two-channel clip of that length (a shared part and a part of each channel's own),
+            channels='all', file to file: without any option, with stereo_report=True and with SuperResolver(stereo='ms'), in one
+            process, the runs interleaved (nine repeats unless --reps says otherwise): milliseconds per file, median and spread;
+            then p2phd_xspec and p2phd_stereo_bands alone, by events, beside p2phd_ltas on the same two rows (the same number of
+            transforms), at the clip's frame count and at an hour's, and p2phd_stereo_matrix on the clip; with --off_only only the
+            run without any option is timed (one process of an alternating comparison with another checkout); log in --stereo_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -72,6 +79,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py limiter [--limiter_log profiles/time_generate_limiter.log]
         python tools/time_generate.py album [--files 8] [--album_log profiles/time_generate_album.log]
         python tools/time_generate.py bandwidth [--off_only] [--bandwidth_log profiles/time_generate_bandwidth.log]
+        python tools/time_generate.py stereo [--off_only] [--stereo_log profiles/time_generate_stereo.log]
 """
 import argparse
 import os
@@ -639,6 +647,115 @@ def _bandwidth_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_stereo(seconds, reps, log, off_only=False):
+    """enhance_file on a two-channel clip, file to file: without any option, with stereo_report=True (the same object) and with
+    SuperResolver(stereo='ms'), interleaved; then p2phd_xspec and p2phd_stereo_bands alone, by events, beside p2phd_ltas on the same two
+    rows, at the clip's frame count and at an hour's; and p2phd_stereo_matrix on the clip."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    n = x.shape[-1]
+    g = torch.Generator().manual_seed(8)
+    t = torch.arange(n, dtype=torch.float64) / opt.hr_sampling_rate
+    hi = sum(a * torch.sin(2 * torch.pi * f * t + p) for a, f, p in ((0.02, 5200.0, 0.3), (0.01, 9100.0, 1.1), (0.005, 15300.0, 2.2)))
+    mid = x.cpu()[:1] + hi.float()[None]
+    own = 0.02 * torch.randn((2, n), generator=g)                   # what each channel has of its own, full band
+    hr = mid + own
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py stereo: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s two-channel PCM16 clip at 48 kHz with a full-band original, file to file, channels='all', untrained weights, %d interleaved "
+             "repeats" % (seconds, reps)]
+
+    def interleaved(runs, src, out):
+        last = [None] * len(runs)
+        for k, (_, sr, kw) in enumerate(runs):                      # warm-up: capture, pinned buffers, page cache
+            sr.enhance_file(src, out, channels='all', **kw)
+            last[k] = sr.enhance_file(src, out, channels='all', **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, sr, kw) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, channels='all', **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        return ts, last
+
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, hr, rate)
+        sr = SuperResolver(model, opt, overlap=0.25)
+        if off_only:
+            interleaved([("no option            ", sr, {})], src, out)
+        else:
+            ms = SuperResolver(model, opt, overlap=0.25, stereo='ms')
+            ts, last = interleaved([("stereo off           ", sr, {}), ("stereo_report        ", sr, dict(stereo_report=True)), ("stereo='ms'          ", ms, {})],
+                                   src, out)
+            base = _median(ts[0])
+            lines.append("the report costs %.3f ms per file (difference of the medians), %.2f %% of the file without it: six launches and 192 bytes "
+                         "more in the copy back" % (_median(ts[1]) - base, 100.0 * (_median(ts[1]) - base) / base))
+            lines.append("the mode costs %.3f ms per file (difference of the medians), %.2f %%: two launches"
+                         % (_median(ts[2]) - base, 100.0 * (_median(ts[2]) - base) / base))
+            s = last[1]['stereo']
+            lines.append("the last file ('lr'): correlation below / above %.2f kHz: %s; %d frames; %d note(s)"
+                         % (s['split_hz'] / 1e3, ", ".join("%s %+.2f / %+.2f" % (k, s[k]['low']['corr'], s[k]['high']['corr']) for k in ('input', 'output', 'original')),
+                            s['frames'], len(s['notes'])))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _stereo_kernels(torch, hr.to(x.device), rate, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _stereo_kernels(torch, x, rate, reps):
+    """p2phd_xspec and p2phd_stereo_bands alone, by events (each with the allocation of its result, the first also of its workspace, in
+    front), beside p2phd_ltas on the same two rows, on the clip and on an hour of it; p2phd_stereo_matrix on the clip."""
+    from pix2pixhdaudiosr_amd.generate import STEREO_DEFAULTS as P, cross_spectrum, ltas, stereo_bands, stereo_matrix, stereo_split_bin
+    lines = []
+    k_split = stereo_split_bin(rate, 8000, P['n_fft'])
+    hour = x.repeat(1, -(-3600 * rate // x.shape[-1]))[:, :3600 * rate].contiguous()
+    for name, clip in (("the clip", x), ("an hour", hour)):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        k_x, k_b, k_l = [], [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            xs = cross_spectrum(clip, P['n_fft'], P['hop'])
+            ev[1].record()
+            stereo_bands(xs, k_split)
+            ev[2].record()
+            ltas(clip, P['n_fft'], P['hop'])
+            ev[3].record()
+            torch.cuda.synchronize()
+            k_x.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_b.append(ev[1].elapsed_time(ev[2]) * 1e3)
+            k_l.append(ev[2].elapsed_time(ev[3]) * 1e3)
+        L = clip.shape[-1]
+        F = 1 + (L - P['n_fft']) // P['hop']
+        lines.append("kernels alone on %s (events, median of %d; %d samples a row, %d frames of %d, %d transforms either way): p2phd_xspec %.1f us "
+                     "(spread %.1f), p2phd_ltas on the same two rows %.1f us (spread %.1f), p2phd_stereo_bands %.1f us"
+                     % (name, reps, L, F, P['n_fft'], F, _median(k_x[2:]), max(k_x[2:]) - min(k_x[2:]), _median(k_l[2:]), max(k_l[2:]) - min(k_l[2:]),
+                        _median(k_b[2:])))
+        lines.append("runs: p2phd_xspec %s; p2phd_ltas %s; p2phd_stereo_bands %s"
+                     % tuple(" ".join("%.1f" % v for v in k[2:]) for k in (k_x, k_l, k_b)))
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    k_m = []
+    for _ in range(reps + 2):
+        ev[0].record()
+        stereo_matrix(x, 0.5)
+        ev[1].record()
+        torch.cuda.synchronize()
+        k_m.append(ev[0].elapsed_time(ev[1]) * 1e3)
+    lines.append("p2phd_stereo_matrix on the clip (with the allocation of its result): %.1f us; runs: %s" % (_median(k_m[2:]), " ".join("%.1f" % v for v in k_m[2:])))
+    return "\n".join(lines) + "\n"
+
+
 def run_limiter(seconds, reps, log):
     """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
     guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
@@ -819,7 +936,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -832,13 +949,17 @@ def main():
     ap.add_argument("--truepeak_log", default=os.path.join(ROOT, "profiles", "time_generate_truepeak.log"))
     ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
     ap.add_argument("--bandwidth_log", default=os.path.join(ROOT, "profiles", "time_generate_bandwidth.log"))
-    ap.add_argument("--off_only", action="store_true", help="bandwidth mode: time only the run without any option (no log unless --bandwidth_log is given)")
+    ap.add_argument("--stereo_log", default=os.path.join(ROOT, "profiles", "time_generate_stereo.log"))
+    ap.add_argument("--off_only", action="store_true", help="bandwidth and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album and bandwidth mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "album":
         return run_album(a.seconds, 9 if a.reps is None else a.reps, a.files, a.album_log)
+    if a.mode == "stereo":
+        log = a.stereo_log if not a.off_only or "--stereo_log" in sys.argv else None
+        return run_stereo(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "bandwidth":
         log = a.bandwidth_log if not a.off_only or "--bandwidth_log" in sys.argv else None
         return run_bandwidth(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
