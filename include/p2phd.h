@@ -95,7 +95,7 @@ int p2phd_probe_read(float* ms_out, int cap);
  * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
  * csrc/limiter.hip), "bandwidth" (the long-term average spectrum and the band-edge decision of its bandwidth report,
  * csrc/bandwidth.hip), "stereo" (the cross-spectrum and the band sums of its stereo image report and the mid/side matrix of
- * stereo='ms', csrc/stereo.hip).
+ * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -571,6 +571,44 @@ int p2phd_xspec(const float* x, int64_t ld, int64_t G, int64_t L, int n_fft, int
                 void* stream);
 int p2phd_stereo_bands(const double* xs, int64_t G, int K, int k_split, double* res, void* stream);
 int p2phd_stereo_matrix(const float* x, int64_t ld, int64_t L, float a, int guard_side, float* out, int64_t ld_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rate converter of whole-file generation's output stage (--output_rate), csrc/rateconv.hip: a rational polyphase FIR from the
+ * model's rate to the rate that is written.  Launch family "rateconv" (a p2phd_rateconv_fwd with frames > 0 counts 1).  It is not the
+ * feeder's p2phd_resample_fwd, which restates the reference's training-time resampler and stays as it is.
+ * With g = gcd(in_rate, out_rate): o = in_rate / g, n = out_rate / g, P = taps_per_phase, half = P / 2 - 1.
+ *
+ * p2phd_rateconv_plan (HOST only, no device, as p2phd_xover_taps_fill): the filter for a passband and an attenuation, in float64.
+ *   nyq = min(in_rate, out_rate) / 2, fp = passband * nyq (flat up to here), fs = 2 nyq - fp (the stopband from here: aliases and
+ *   images fold only above fp), beta = 0.1102 (atten_db - 8.7), and Kaiser's length
+ *     P = 2 ceil((atten_db - 7.95) / (2 * 2.285 * 2 pi (fs - fp) / in_rate)).
+ *   Refused (P2PHD_EINVAL with an error text): in_rate == out_rate, a rate < 1, passband outside (0, 1), atten_db outside [40, 160],
+ *   P < 4 or P > 256, n * P > 2^20.  generate/plans.py holds the defaults (passband 0.907: 20 kHz at 44.1 kHz; 120 dB).
+ * p2phd_rateconv_taps_fill (HOST only): the table c[n][P], phase-major.  Phase p has frac = ((p o) mod n) / n; in float64, with
+ *   tau = (k - half) - frac, sinc(x) = sin(pi x) / (pi x) and cutoff = fc = 2 nyq / in_rate in (0, 1]:
+ *     c[p][k] = fc sinc(fc tau) I0(beta sqrt(1 - (tau / (P / 2))^2)) / I0(beta)
+ *   each phase divided by its own float64 sum (DC gain 1), each coefficient then rounded once to fp32.  o, n >= 1, P even and in
+ *   [4, 256], n * P <= 2^20, beta finite and >= 0; anything else: P2PHD_EINVAL.
+ * p2phd_rateconv_out_len (host): L_out = ceil(frames * n / o) for 0 <= frames <= 2^40; -1 with an error text otherwise.
+ * p2phd_rateconv_fwd: planar [channels][ld] f32 rows of `frames` = L samples (layout and argument checks of p2phd_truepeak; rows may
+ *   start at any float), table_dev: n * P f32 on the device, phase-major -- the caller's table, of any content.  out: [channels][out_ld]
+ *   f32 rows of out_frames = L_out samples, which must not overlap the input.  x~ is the row, 0 outside [0, L); a NaN or infinite
+ *   sample is a sample like any other.  Output m = j n + p with p = m mod n:
+ *     y[m] = sum_{k = 0}^{P - 1} c[p][k] x~[j o + (p o) div n + k - half],   m = 0 .. L_out - 1
+ *   as ONE fp32 accumulator that starts at +0 and takes acc = fma(c[p][k], x~, acc) for k ascending (one rounding per tap), so a y
+ *   has one bit pattern whatever the grid, the tile and the number of rows.  Every output is written by one thread: no atomics, no
+ *   workspace, nothing zeroed before the launch, no ordering rule between calls.  frames = 0: nothing is launched or written.  o and n
+ *   must differ and share no divisor; a bad o, n or P, out_frames != L_out, a pitch shorter than its row, a null or misaligned
+ *   pointer, an output that overlaps the input: P2PHD_EINVAL.
+ * p2phd_rateconv_tile_len (host): input samples of a row that one workgroup's run of blocks covers for this (o, n, P) (tests place
+ *   their lengths around its multiples); -1 for a bad shape.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_rateconv_plan(int in_rate, int out_rate, double passband, double atten_db, int* o, int* n, int* taps_per_phase, double* beta);
+int p2phd_rateconv_taps_fill(int o, int n, int taps_per_phase, double beta, double cutoff, float* out);
+int64_t p2phd_rateconv_out_len(int64_t frames, int in_rate, int out_rate);
+int p2phd_rateconv_fwd(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int o, int n, int taps_per_phase,
+                       float* out, int64_t out_frames, int64_t out_ld, void* stream);
+int64_t p2phd_rateconv_tile_len(int o, int n, int taps_per_phase);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -84,6 +84,11 @@ SIGNATURES = {
     "p2phd_xspec": (_i32, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "p2phd_stereo_bands": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "p2phd_stereo_matrix": (_i32, [_vp, _i64, _i64, _f32, _i32, _vp, _i64, _vp]),
+    "p2phd_rateconv_plan": (_i32, [_i32, _i32, C.c_double, C.c_double, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_double)]),
+    "p2phd_rateconv_taps_fill": (_i32, [_i32, _i32, _i32, C.c_double, C.c_double, _vp]),
+    "p2phd_rateconv_out_len": (_i64, [_i64, _i32, _i32]),
+    "p2phd_rateconv_fwd": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
+    "p2phd_rateconv_tile_len": (_i64, [_i32, _i32, _i32]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

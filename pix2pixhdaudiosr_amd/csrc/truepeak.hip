@@ -23,6 +23,7 @@
 // the fold = 10.4 KiB per workgroup.  No workspace besides the partials.  No roofline claim: see DESIGN.md section 6.
 #include "common.h"
 #include "convplan.h"
+#include "kaiser.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -148,18 +149,7 @@ __global__ __launch_bounds__(kThreads) void truepeak_kernel(const float* __restr
   }
 }
 
-// I0(x), x >= 0: the power series sum_m ((x / 2)^2m / (m!)^2), every term positive; stops when a term no longer changes the sum
-double bessel_i0(double x) {
-  const double q = 0.25 * x * x;
-  double term = 1.0, sum = 1.0;
-  for (int m = 1; m < 1000; ++m) {
-    term *= q / ((double)m * (double)m);
-    const double next = sum + term;
-    if (next == sum) break;
-    sum = next;
-  }
-  return sum;
-}
+using p2phd::bessel_i0;
 
 bool plan_ok(int factor, int taps_per_phase) {
   return (factor == 1 || factor == 2 || factor == 4) && taps_per_phase >= kMinTaps && taps_per_phase <= kMaxTaps && (taps_per_phase & 1) == 0;

@@ -22,6 +22,7 @@
 // No atomics, no workspace.  Microseconds to a few milliseconds beside the generator: no roofline claim.
 #include "common.h"
 #include "convplan.h"
+#include "kaiser.h"
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -95,18 +96,7 @@ __global__ __launch_bounds__(kThreads) void xover_kernel(const float* __restrict
   for (int p = tid; p < len; p += kThreads) out[tile0 + p] = sr[tile0 + p] + s_d[pad8(p)];
 }
 
-// I0(x), x >= 0: the power series sum_m ((x / 2)^2m / (m!)^2), every term positive; stops when a term no longer changes the sum
-double bessel_i0(double x) {
-  const double q = 0.25 * x * x;
-  double term = 1.0, sum = 1.0;
-  for (int m = 1; m < 1000; ++m) {
-    term *= q / ((double)m * (double)m);
-    const double next = sum + term;
-    if (next == sum) break;
-    sum = next;
-  }
-  return sum;
-}
+using p2phd::bessel_i0;
 
 bool spans_overlap(const float* a, int64_t ld_a, const float* b, int64_t ld_b, int64_t C, int64_t L) {
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import torch
 
 from .plans import (CLIP_MODES, CROSSOVER_AUTO, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_output_options, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, spectro_bins)
+                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
@@ -282,6 +282,11 @@ def _parser():
                     help="--stereo_report: STFT length of the cross-spectrum, a power of two in 64 .. 2048 (default 2048)")
     ap.add_argument("--stereo_hop", type=int, default=None, metavar="N",
                     help="--stereo_report: hop of the cross-spectrum, 1 .. N of --stereo_n_fft (default: half of it)")
+    ap.add_argument("--output_rate", type=int, default=None, metavar="HZ",
+                    help="write the file at this rate instead of the checkpoint's hr_sampling_rate, 44100 for instance: a polyphase rate "
+                         "converter (flat to 0.907 of the lower Nyquist frequency, 120 dB down where anything folds) in front of the "
+                         "loudness, true-peak and limiter stages, which then measure and hold what is written; one start-up line more; "
+                         "not with --spectrogram or --loudness_scope folder (default: off)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -306,6 +311,9 @@ def main(argv=None):
         picture.update(_stereo_args(a))
         if a.true_peak:
             picture['true_peak'] = True
+        if a.output_rate is not None:                                       # (the rate pair itself: once the options file has been read)
+            check_output_rate(a.output_rate, a.output_rate, "generate")
+            picture['output_rate'] = a.output_rate
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
             check_limiter(a.limiter, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, 48000, "generate")
             picture.update(limiter=True, limiter_lookahead_ms=a.limiter_lookahead_ms, limiter_hold_ms=a.limiter_hold_ms)
@@ -326,8 +334,12 @@ def main(argv=None):
         check_lowband(a.lowband, a.lowband_fade, spectro_bins(opt.n_fft, opt.mdct_type), opt.hr_sampling_rate / opt.lr_sampling_rate)
         check_crossover(a.crossover, a.crossover_hz, a.crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
         _loudness_args(a, opt.hr_sampling_rate, folder_mode)
+        rc = check_output_rate(a.output_rate, opt.hr_sampling_rate, "generate", a.loudness_scope, a.spectrogram)
+        if rc is not None and a.loudness is not None:
+            _loudness_args(a, rc['rate'], folder_mode)
         if a.limiter:
-            check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate, "generate")
+            check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate if rc is None else rc['rate'],
+                          "generate")
     except ValueError as e:
         ap.error(str(e))
     from ..models.models import create_model
@@ -349,7 +361,9 @@ def main(argv=None):
         print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
     if sr.stereo == 'ms':                                                   # (without the option: no line more than before)
         print('stereo: mid / side')
-    rate = int(opt.hr_sampling_rate)
+    if rc is not None:                                                      # (without the option: no line more than before)
+        print(output_rate_line(rc))
+    rate = int(opt.hr_sampling_rate) if rc is None else rc['rate']
     try:
         return _run(a, sr, stage, seed, rate, folder_mode)
     except ClipError as e:

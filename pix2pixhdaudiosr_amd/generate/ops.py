@@ -1,12 +1,12 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip and csrc/stereo.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip and csrc/rateconv.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
 from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
-                    check_encoding, check_loudness_rate, limiter_plan, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
+                    check_encoding, check_loudness_rate, limiter_plan, RATECONV_DEFAULTS, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -583,7 +583,93 @@ def stereo_matrix(x, a, guard_side=False, out=None):
     return oo
 
 
-_LIMITER_WINDOWS = {}                                                      # (lookahead, device) -> the window on the device
+_RATECONV_TABLES = {}                                                      # (o, n, taps per phase, beta, cutoff, device) -> the table on the device
+
+
+def rateconv_plan(in_rate, out_rate, passband=None, atten_db=None):
+    """The filter of the output stage's rate converter, host arithmetic only (p2phd_rateconv_plan, no GPU needed) -> {'in_rate',
+    'out_rate', 'o', 'n' (the rates over their greatest common divisor), 'taps_per_phase', 'beta', 'cutoff' (what
+    rateconv_coefficients takes: min(in, out) / in), 'passband_hz' (flat up to here), 'stopband_hz' (`atten_db` down from here; what
+    aliases or images lies above passband_hz), 'atten_db'}.  `passband`: the flat part as a fraction of the lower rate's Nyquist
+    frequency, `atten_db`: the stopband attenuation (None: RATECONV_DEFAULTS).  Equal rates, a rate that is no int >= 1 and a plan
+    the entry refuses -- rates so far apart, or with so small a common divisor, that the table is not built -- are a ValueError
+    with its text."""
+    for name, v in (('in_rate', in_rate), ('out_rate', out_rate)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < 2 ** 31:
+            raise ValueError("rateconv_plan: %s must be an int >= 1, got %r" % (name, v))
+    passband = RATECONV_DEFAULTS['passband'] if passband is None else passband
+    atten_db = RATECONV_DEFAULTS['atten_db'] if atten_db is None else atten_db
+    for name, v in (('passband', passband), ('atten_db', atten_db)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError("rateconv_plan: %s must be a number, got %r" % (name, v))
+    o, n, P, beta = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+    l = _lib.lib()
+    if l.p2phd_rateconv_plan(in_rate, out_rate, float(passband), float(atten_db), ctypes.byref(o), ctypes.byref(n), ctypes.byref(P),
+                             ctypes.byref(beta)) != 0:
+        raise ValueError(l.p2phd_last_error().decode("utf-8", "replace"))
+    nyquist = min(in_rate, out_rate) / 2.0
+    return {'in_rate': in_rate, 'out_rate': out_rate, 'o': o.value, 'n': n.value, 'taps_per_phase': P.value, 'beta': beta.value,
+            'cutoff': min(in_rate, out_rate) / float(in_rate), 'passband_hz': float(passband) * nyquist,
+            'stopband_hz': 2.0 * nyquist - float(passband) * nyquist, 'atten_db': float(atten_db)}
+
+
+def rateconv_coefficients(plan):
+    """The polyphase table of p2phd_rateconv_taps_fill for rateconv_plan's `plan` as a float32 tensor [n, taps_per_phase] on the host
+    (no GPU needed)."""
+    c = torch.empty((max(int(plan['n']), 1), max(int(plan['taps_per_phase']), 1)), dtype=torch.float32)
+    l = _lib.lib()
+    if l.p2phd_rateconv_taps_fill(int(plan['o']), int(plan['n']), int(plan['taps_per_phase']), float(plan['beta']), float(plan['cutoff']),
+                                  ctypes.c_void_p(c.data_ptr())) != 0:
+        raise ValueError(l.p2phd_last_error().decode("utf-8", "replace"))
+    return c
+
+
+def rateconv_out_len(frames, in_rate, out_rate):
+    """ceil(frames * out_rate / in_rate) in exact arithmetic (p2phd_rateconv_out_len): the samples of a converted row."""
+    l = _lib.lib()
+    v = l.p2phd_rateconv_out_len(int(frames), int(in_rate), int(out_rate))
+    if v < 0:
+        raise ValueError(l.p2phd_last_error().decode("utf-8", "replace"))
+    return v
+
+
+def rate_convert(x, in_rate, out_rate, plan=None, table=None, out=None):
+    """x [C, L] f32 on the GPU (rows contiguous, any row pitch) at `in_rate` -> [C, ceil(L out_rate / in_rate)] at `out_rate`: the
+    rational polyphase converter of csrc/rateconv.hip, every output one fp32 fma chain over the taps in ascending order
+    (p2phd_rateconv_fwd).  Equal rates: `x` itself, and nothing is launched.  `plan`: rateconv_plan's dict (None: the one of the two
+    rates with RATECONV_DEFAULTS); `table`: the [n, taps_per_phase] f32 table on the GPU where the caller brings its own (None:
+    rateconv_coefficients(plan), filled once per device); `out`: None, or a [C, L_out] f32 tensor on the GPU (rows contiguous, any
+    row pitch) that takes the result and must not overlap `x`.  One launch of the family "rateconv" (none for L = 0), nothing is
+    waited for."""
+    if in_rate == out_rate:
+        return x
+    if plan is None:
+        plan = rateconv_plan(in_rate, out_rate)
+    elif (plan['in_rate'], plan['out_rate']) != (in_rate, out_rate):
+        raise ValueError("rate_convert: the plan is one of %r -> %r Hz, the call says %r -> %r" % (plan['in_rate'], plan['out_rate'], in_rate, out_rate))
+    o, n, P = int(plan['o']), int(plan['n']), int(plan['taps_per_phase'])
+    w, C, L, ld = _rows(x, "rate_convert: x")
+    if table is None:
+        key = (o, n, P, plan['beta'], plan['cutoff'], str(w.device))
+        table = _RATECONV_TABLES.get(key)
+        if table is None:
+            table = _RATECONV_TABLES[key] = rateconv_coefficients(plan).to(w.device)
+    else:
+        table = _lib.require_gpu_tensor(table, "rate_convert: table", torch.float32)
+        if table.numel() != n * P:
+            raise ValueError("rate_convert: the table must hold n * taps_per_phase = %d contiguous floats, got shape %s" % (n * P, tuple(table.shape)))
+    L_out = rateconv_out_len(L, o, n)
+    if out is None:
+        out = torch.empty((C, L_out), dtype=torch.float32, device=w.device)
+    oo, Co, Lo, ld_o = _rows(out, "rate_convert: out")
+    if (Co, Lo) != (C, L_out):
+        raise ValueError("rate_convert: out must have the shape %s, got %s" % ((C, L_out), tuple(oo.shape)))
+    _lib.check(_lib.lib().p2phd_rateconv_fwd(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(table), o, n, P, _lib.ptr(oo), L_out, max(ld_o, L_out),
+                                             _lib.stream_ptr()), "rateconv_fwd")
+    return oo
+
+
+_LIMITER_WINDOWS = {}                                                    # (lookahead, device) -> the window on the device
 
 
 def limiter_window(lookahead):

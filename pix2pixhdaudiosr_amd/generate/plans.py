@@ -1,4 +1,5 @@
-"""Whole-file generation: the host arithmetic and the validation of every option -- no tensor, no library."""
+"""Whole-file generation: the host arithmetic and the validation of every option -- no tensor, no library (check_output_rate alone
+asks the library, for the converter's plan: the host entry point that can refuse it is the one that knows why)."""
 import math
 import os
 from fractions import Fraction
@@ -48,6 +49,10 @@ LIMITER_LOOKAHEAD_MS = 5.0
 LIMITER_HOLD_MS = 20.0
 LIMITER_MAX_LOOKAHEAD = 1024
 LIMITER_MAX_HOLD = 4096
+# the output-rate option (csrc/rateconv.hip): the converter's flat passband as a fraction of the lower rate's Nyquist frequency (0.907:
+# 20 kHz at 44.1 kHz) and its stopband attenuation in dB; the lowest rate that is written
+RATECONV_DEFAULTS = {'passband': 0.907, 'atten_db': 120.0}
+OUTPUT_MIN_RATE = 8000
 # (index, (r, g, b)) anchors of spectrogram_lut
 SPECTROGRAM_LUT_ANCHORS = ((0, (0, 0, 4)), (64, (30, 20, 140)), (128, (180, 40, 150)), (192, (250, 140, 30)), (255, (255, 250, 190)))
 
@@ -527,6 +532,40 @@ def check_true_peak(true_peak, stage, encoding, hr_rate, who="enhance_file"):
         stage = {'clip': 'clamp', 'ceiling': None, 'dither': None, 'seed': 0, 'report': False}
     limit = encoding_limit(encoding)
     return stage, {'rate': hr_rate, 'ceiling': limit if stage['ceiling'] is None else stage['ceiling'], 'limit': limit}
+
+
+def check_output_rate(output_rate, hr_rate, who="enhance_file", loudness_scope='file', spectrogram=None):
+    """Validates the output-rate option for a model that generates at `hr_rate` -> None (off: `output_rate` is None or the model's
+    rate, and nothing changes), or the option {'rate', 'model_rate', 'plan'}: `plan` is ops.rateconv_plan's dict for hr_rate ->
+    output_rate with RATECONV_DEFAULTS.  `output_rate`: an int >= 8000 Hz.  Not built with `spectrogram` (the picture's panels share
+    one frequency axis) or loudness_scope 'folder' (generate/album.py keeps its own copy of the flow); rates between which the
+    converter is not built are refused with p2phd_rateconv_plan's text.  A ValueError each, before a file is opened."""
+    if output_rate is None:
+        return None
+    if not _is_int(output_rate) or output_rate < OUTPUT_MIN_RATE:
+        raise ValueError("%s: output_rate must be an int >= %d Hz, got %r" % (who, OUTPUT_MIN_RATE, output_rate))
+    if hr_rate == output_rate:
+        return None
+    if hr_rate != int(hr_rate) or int(hr_rate) < 1:
+        raise ValueError("%s: output_rate converts from the model's rate, which must be a whole number of Hz, got %r" % (who, hr_rate))
+    if spectrogram is not None:
+        raise ValueError("%s: spectrogram is not built with output_rate: its panels share one frequency axis and the written clip "
+                         "would have another" % who)
+    if loudness_scope == 'folder':
+        raise ValueError("%s: output_rate is not built for loudness_scope='folder': the album flow writes at the model's rate" % who)
+    from .ops import rateconv_plan
+    try:
+        plan = rateconv_plan(int(hr_rate), output_rate)
+    except ValueError as e:
+        raise ValueError("%s: output_rate %d: %s" % (who, output_rate, e))
+    return {'rate': output_rate, 'model_rate': int(hr_rate), 'plan': plan}
+
+
+def output_rate_line(rc):
+    """The start-up line of the output-rate option."""
+    p = rc['plan']
+    return ('output rate: %d Hz (%d taps x %d phases, flat to %.2f kHz, -%g dB from %.2f kHz)'
+            % (rc['rate'], p['taps_per_phase'], p['n'], p['passband_hz'] / 1000.0, p['atten_db'], p['stopband_hz'] / 1000.0))
 
 
 def limiter_plan(rate, lookahead_ms=None, hold_ms=None):

@@ -6,9 +6,9 @@ import struct
 import torch
 
 from .ops import (bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
+                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
 from .plans import (BANDWIDTH_DEFAULTS, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_output_options, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
+                    check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -319,7 +319,7 @@ class SuperResolver:
         self._pins[slot] = (self._pins[slot][0], busy)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
         (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
         back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
@@ -329,7 +329,8 @@ class SuperResolver:
         clip, clip 'guard' takes its gain from it, and its figures come back likewise.  `limiter`: the limiter option
         (_limiter_option; it comes with a stage and the true-peak option): the limiter runs in front of the peak kernel, everything
         behind it sees the limited clip, and its figures come back likewise.  `bandwidth`: the bandwidth measurement
-        (_measure_bandwidth), whose packed results come back likewise; `stereo`: the stereo measurement (_measure_stereo), likewise."""
+        (_measure_bandwidth), whose packed results come back likewise; `stereo`: the stereo measurement (_measure_stereo), likewise.
+        `rate`: the rate the header states where it is not the model's (the output-rate option: `sr` is the converted clip)."""
         w = sr.contiguous()
         extra = {} if true_peak is None else {'true_peak': true_peak}
         if limiter is not None:
@@ -343,7 +344,7 @@ class SuperResolver:
         host, stats = self._fetch(dev, packed, picture, **fetch)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
         if host is not None:
-            self._save(path_out, host, sr.shape[0], encoding)
+            self._save(path_out, host, sr.shape[0], encoding, **({} if rate is None else {'rate': rate}))
         return output
 
     def _encode(self, w, wanted, encoding, stage, true_peak=None, limiter=None):
@@ -454,10 +455,10 @@ class SuperResolver:
             lim = {'lookahead': lim['lookahead'], 'hold': lim['hold'], 'rate': tp['rate'], 'ceiling': tp['ceiling']}
         return stage, tp, lim
 
-    def _save(self, path_out, host, channels, encoding):
+    def _save(self, path_out, host, channels, encoding, rate=None):
         from ..data import wavio
         os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
-        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate), channels, encoding)
+        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate if rate is None else rate), channels, encoding)
 
     @staticmethod
     def _check_picture_channel(spec, channels, available):
@@ -491,19 +492,21 @@ class SuperResolver:
         the f32 on the device that brings `sr` to the wanted level (1 with 'report')}.  With loud['range'] the hop energies of
         either clip also go through the short-term and the range kernel (at most four launches more; the generated clip's powers
         take the gain from device memory, so the figures are those of the clip as this stage leaves it) and 'packed' holds their
-        two res8 behind the gate results, 208 bytes in all."""
+        two res8 behind the gate results, 208 bytes in all.  With loud['out_rate'] (the output-rate option) `sr` is the converted
+        clip: it is measured at that rate, the input still at the model's."""
         rate = int(self.opt.hr_sampling_rate)
+        rate_out = loud.get('out_rate', rate)
         weights = loudness_channel_weights(sr.shape[0])
         ranged = loud.get('range', False)
         packed = torch.empty((208 if ranged else 80,), dtype=torch.uint8, device=sr.device)
         z_in = loudness_hops(lr, rate)
         res_in, _ = loudness_gate(z_in, rate, weights, out=packed[:40])
         wanted = {'report': {}, 'input': {'target_dev': res_in}, 'target': {'target': loud['target']}}[loud['mode']]
-        z_out = loudness_hops(sr, rate)
-        _, gain = loudness_gate(z_out, rate, weights, max_gain_db=loud['max_gain_db'], out=packed[40:80], **wanted)
+        z_out = loudness_hops(sr, rate_out)
+        _, gain = loudness_gate(z_out, rate_out, weights, max_gain_db=loud['max_gain_db'], out=packed[40:80], **wanted)
         if ranged:
             loudness_range(loudness_short_term(z_in, rate, weights), out=packed[80:144].view(torch.float64))
-            loudness_range(loudness_short_term(z_out, rate, weights, gain_dev=gain), out=packed[144:208].view(torch.float64))
+            loudness_range(loudness_short_term(z_out, rate_out, weights, gain_dev=gain), out=packed[144:208].view(torch.float64))
         return {'packed': packed, 'gain': gain}
 
     @staticmethod
@@ -567,13 +570,31 @@ class SuperResolver:
         if getattr(self, 'stereo', 'lr') == 'ms' and select_channels(channels, available) > 2:
             raise ValueError("stereo='ms' takes one or two channels, %d would be written" % select_channels(channels, available))
 
+    @staticmethod
+    def _output_rate_result(rc):
+        """The output-rate option -> the result's 'output_rate'."""
+        p = rc['plan']
+        return {'rate': rc['rate'], 'model_rate': rc['model_rate'], 'o': p['o'], 'n': p['n'], 'taps_per_phase': p['taps_per_phase'],
+                'passband_hz': p['passband_hz'], 'stopband_hz': p['stopband_hz'], 'atten_db': p['atten_db']}
+
+    def _output_rate_option(self, output_rate, who, loudness_scope, spectrogram):
+        """check_output_rate for enhance_file / enhance_folder -> (rc, the rate the output stage runs at)."""
+        rc = check_output_rate(output_rate, self.opt.hr_sampling_rate, who, loudness_scope, spectrogram)
+        return rc, (self.opt.hr_sampling_rate if rc is None else rc['rate'])
+
+    @staticmethod
+    def _loudness_at(loud, rc, who):
+        """With the output-rate option the loudness option learns the rate the generated clip is measured at, which must be one the
+        K-weighting entry takes."""
+        return loud if loud is None or rc is None else dict(loud, out_rate=check_loudness_rate(rc['rate'], who))
+
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
-                         lim=None, bw=None, st=None):
+                         lim=None, bw=None, st=None, rc=None):
         """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
         7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
         `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak).  `lim`: None,
     or the limiter option (_limiter_option).  `bw`: None, or the bandwidth option (check_bandwidth).  `st`: None, or the stereo
-        report option (check_stereo_report)."""
+        report option (check_stereo_report).  `rc`: None, or the output-rate option (check_output_rate)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         from ..util import util as U
         o = self.opt
@@ -606,6 +627,10 @@ class SuperResolver:
             metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
         output = None
         measure = None
+        if rc is not None:
+            # behind everything that compares the generated clip with the input and the original at the model's rate; in front of
+            # the loudness, peak and limiter stages, which measure and hold what is written.  One launch of the family "rateconv"
+            sr = rate_convert(sr, rc['model_rate'], rc['rate'], rc['plan'])
         if loud is not None:
             # behind the metrics, which moment-match and stay those of the unscaled clip; in front of everything that sees the written level
             measure = self._measure_loudness(loud, lr, sr)
@@ -622,6 +647,8 @@ class SuperResolver:
                 extra['true_peak'] = dict(tp)                              # (one file's: it takes the file's buffers)
             if lim is not None:
                 extra['limiter'] = dict(lim)
+            if rc is not None:
+                extra['rate'] = rc['rate']
             output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
         if picture is not None:
@@ -634,6 +661,8 @@ class SuperResolver:
             res['crossover'] = xover
         if st is not None:
             res['stereo'] = None if image is None else self._stereo_result(st, image)
+        if rc is not None:
+            res['output_rate'] = self._output_rate_result(rc)
         if extended_metrics:
             res['metrics_ext'] = ext
         if stage is not None:
@@ -644,7 +673,7 @@ class SuperResolver:
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
-                     bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None):
+                     bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -736,16 +765,29 @@ class SuperResolver:
         payload behind the same synchronisation.  The result gains 'stereo': {'input', 'output', 'original' ({'low', 'high'}, each
         {'corr', 'coherence', 'side_db', 'balance_db'}; 'original' None without one), 'split_hz', 'n_fft', 'hop', 'frames', 'mode'
         (the object's `stereo`), 'notes' (a list of strings: with mode 'lr', a generated clip whose correlation above the split is
-        more than STEREO_NOTE_DROP under the one below it)}; None for a file written with another channel count."""
+        more than STEREO_NOTE_DROP under the one below it)}; None for a file written with another channel count.
+        `output_rate` (opt-in; None or opt.hr_sampling_rate: nothing changes): write the file at this rate, an int >= 8000 Hz, 44100
+        for instance.  The generated clip goes through a rational polyphase converter (csrc/rateconv.hip; ops.rateconv_plan: a
+        Kaiser-windowed sinc, flat to 0.907 of the lower rate's Nyquist frequency, 120 dB down from where aliases or images would fold
+        under it) behind the metrics, the bandwidth and the stereo report, which compare the clips at the model's rate, and in front
+        of the loudness measurement of the generated clip, the true-peak measurement, the limiter, the guard and the encoder, which
+        all run on the converted clip at the output rate: the loudness, the true peak and the dither of the delivered file are the
+        ones this stage set.  The input's loudness is still measured at the model's rate.  One launch of the family "rateconv" per
+        file.  'sr' is then the clip at the output rate ('lr' and 'hr' stay at the model's) and the result gains 'output_rate':
+        {'rate', 'model_rate', 'o', 'n' (the two rates over their common divisor), 'taps_per_phase', 'passband_hz', 'stopband_hz',
+        'atten_db'}.  Not built with `spectrogram` or loudness_scope 'folder'; rates between which the filter is not built (48000 ->
+        8000, or a pair with a tiny common divisor) are refused: a ValueError each, before the file is opened."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_file")
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_file")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
-        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
-                                              self.opt.hr_sampling_rate, "enhance_file")
+        rc, out_rate = self._output_rate_option(output_rate, "enhance_file", loudness_scope, spectrogram)
+        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_file")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
-        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range)
+        loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range), rc, "enhance_file")
         check_loudness_scope(loudness_scope, loud, "enhance_file", folder=False)
         extra = {} if tp is None else {'tp': tp}
+        if rc is not None:
+            extra['rc'] = rc
         if lim is not None:
             extra['lim'] = lim
         if bw is not None:
@@ -779,7 +821,7 @@ class SuperResolver:
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
-                       stereo_report_opts=None):
+                       stereo_report_opts=None, output_rate=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -820,14 +862,17 @@ class SuperResolver:
         `stereo_report`, `stereo_report_opts`: enhance_file's, per file; a record then gains 'stereo' (as enhance_file returns it; None
         for a skipped file and for one written with another channel count than two).  Not built for loudness_scope 'folder': a
         ValueError.  With SuperResolver(stereo='ms') a file of which more than two channels would be written is skipped, its record
-        carrying the 'error', in either scope."""
+        carrying the 'error', in either scope.
+        `output_rate`: enhance_file's, one rate for every file; a record's 'out_frames' is then the written length at that rate and a
+        record gains 'output_rate' (as enhance_file returns it; None for a skipped file).  Not built for loudness_scope 'folder' or
+        with `spectrogram`: a ValueError."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_folder")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
-        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding,
-                                              self.opt.hr_sampling_rate, "enhance_folder")
+        rc, out_rate = self._output_rate_option(output_rate, "enhance_folder", loudness_scope, spectrogram)
+        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
-        loud = check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range)
+        loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range), rc, "enhance_folder")
         album = check_loudness_scope(loudness_scope, loud, "enhance_folder", True, limiter, spectrogram, album_cache_bytes)
         if album is not None:
             from .album import enhance_album
@@ -842,6 +887,8 @@ class SuperResolver:
             extra['bw'] = bw
         if st is not None:
             extra['st'] = st
+        if rc is not None:
+            extra['rc'] = rc
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
@@ -860,6 +907,8 @@ class SuperResolver:
                 rec['crossover'] = None
             if st is not None:
                 rec['stereo'] = None
+            if rc is not None:
+                rec['output_rate'] = None
             try:
                 read = self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
@@ -890,6 +939,8 @@ class SuperResolver:
                     rec['crossover'] = res['crossover']
                 if st is not None:
                     rec['stereo'] = res['stereo']
+                if rc is not None:
+                    rec['output_rate'] = res['output_rate']
             records.append(rec)
             if report is not None:
                 report(rec)

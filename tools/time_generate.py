@@ -80,6 +80,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py album [--files 8] [--album_log profiles/time_generate_album.log]
         python tools/time_generate.py bandwidth [--off_only] [--bandwidth_log profiles/time_generate_bandwidth.log]
         python tools/time_generate.py stereo [--off_only] [--stereo_log profiles/time_generate_stereo.log]
+        python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
 """
 import argparse
 import os
@@ -756,6 +757,84 @@ def _stereo_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_rateconv(seconds, reps, log, off_only=False):
+    """enhance_file on a mono clip, file to file: without any option and with output_rate=44100 (the same object), interleaved; then
+    p2phd_rateconv_fwd alone, by events, at the clip's length and at an hour's, beside the feeder's p2phd_resample_fwd at the same two
+    rates on the same clip."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py rateconv: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, x.cpu(), rate)
+        sr = SuperResolver(model, opt, overlap=0.25)
+        runs = [("no option            ", {})] if off_only else [("output_rate off      ", {}), ("output_rate 44100    ", dict(output_rate=44100))]
+        last = None
+        for _, kw in runs:                                          # warm-up: capture, pinned buffers, page cache, the table
+            sr.enhance_file(src, out, **kw)
+            last = sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        if not off_only:
+            base = _median(ts[0])
+            r = last['output_rate']
+            lines.append("the option costs %+.3f ms per file (difference of the medians), %+.2f %% of the file without it: one launch more, and the "
+                         "stages behind it, the encoder and the copy back handle %d samples where they handled %d (%d taps x %d phases)"
+                         % (_median(ts[1]) - base, 100.0 * (_median(ts[1]) - base) / base, last['sr'].shape[-1], x.shape[-1], r['taps_per_phase'], r['n']))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _rateconv_kernels(torch, x, rate, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _rateconv_kernels(torch, x, rate, reps):
+    """p2phd_rateconv_fwd alone, by events (with the allocation of its result in front), on the clip and on an hour of it, beside the
+    feeder's p2phd_resample_fwd (data.resample: the reference's 6-zero-crossing Hann sinc) at the same rates on the same rows."""
+    from pix2pixhdaudiosr_amd.data.resample import resample
+    from pix2pixhdaudiosr_amd.generate import rate_convert, rateconv_plan
+    plan = rateconv_plan(rate, 44100)
+    lines = []
+    hour = x.repeat(1, -(-3600 * rate // x.shape[-1]))[:, :3600 * rate].contiguous()
+    for name, clip in (("the clip", x), ("an hour", hour)):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        k_c, k_f = [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            y = rate_convert(clip, rate, 44100, plan)
+            ev[1].record()
+            z = resample(clip, rate, 44100)
+            ev[2].record()
+            torch.cuda.synchronize()
+            k_c.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_f.append(ev[1].elapsed_time(ev[2]) * 1e3)
+        Lo = y.shape[-1]
+        c, f = _median(k_c[2:]), _median(k_f[2:])
+        lines.append("kernels alone on %s (events, median of %d; %d samples in, %d out): p2phd_rateconv_fwd %.1f us (spread %.1f) = %.3f ns per output, "
+                     "%.1f Gfma/s over its %d taps; p2phd_resample_fwd on the same row %.1f us (spread %.1f) = %.3f ns per output (%d out)"
+                     % (name, reps, clip.shape[-1], Lo, c, max(k_c[2:]) - min(k_c[2:]), c * 1e3 / Lo, Lo * plan['taps_per_phase'] / c * 1e-3,
+                        plan['taps_per_phase'], f, max(k_f[2:]) - min(k_f[2:]), f * 1e3 / z.shape[-1], z.shape[-1]))
+        lines.append("runs: p2phd_rateconv_fwd %s; p2phd_resample_fwd %s" % tuple(" ".join("%.1f" % v for v in k[2:]) for k in (k_c, k_f)))
+        del y, z
+    return "\n".join(lines) + "\n"
+
+
 def run_limiter(seconds, reps, log):
     """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
     guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
@@ -936,7 +1015,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -950,9 +1029,10 @@ def main():
     ap.add_argument("--limiter_log", default=os.path.join(ROOT, "profiles", "time_generate_limiter.log"))
     ap.add_argument("--bandwidth_log", default=os.path.join(ROOT, "profiles", "time_generate_bandwidth.log"))
     ap.add_argument("--stereo_log", default=os.path.join(ROOT, "profiles", "time_generate_stereo.log"))
-    ap.add_argument("--off_only", action="store_true", help="bandwidth and stereo mode: time only the run without any option (no log unless the mode's log is given)")
+    ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
+    ap.add_argument("--off_only", action="store_true", help="bandwidth, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth and stereo mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "album":
@@ -960,6 +1040,9 @@ def main():
     if a.mode == "stereo":
         log = a.stereo_log if not a.off_only or "--stereo_log" in sys.argv else None
         return run_stereo(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "rateconv":
+        log = a.rateconv_log if not a.off_only or "--rateconv_log" in sys.argv else None
+        return run_rateconv(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "bandwidth":
         log = a.bandwidth_log if not a.off_only or "--bandwidth_log" in sys.argv else None
         return run_bandwidth(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
