@@ -754,6 +754,16 @@ int p2phd_instnorm_act_bwd_acc(int dtype, const void* g, const void* y, const fl
  * gradient into db instead of overwriting it.  Only for planes that take the two-pass form:
  * p2phd_instnorm_act_bwd_two_pass(dtype, N, HW, C) != 0 (small planes use a single register-resident launch). */
 int p2phd_instnorm_act_bwd_two_pass(int dtype, int N, int64_t HW, int C);
+/* Host query (no launch, no stream, no device call): the grid of a reduction launch whose partial rows live in the library's
+ * reduction scratch (see "Streams").  family "instnorm_bwd": the two-pass p2phd_instnorm_act_bwd / _acc on N samples of P pixels;
+ * family "act_bwd_db": p2phd_act_bwd_db on P pixels (N must be 1).  *rows_wanted = workgroups per sample the plane would take
+ * without the scratch limit, *rows_used = workgroups per sample of the launch that writes the partial rows: rows_used < rows_wanted
+ * says that the launch is clamped to its region (then the InstanceNorm apply pass still runs on rows_wanted), and
+ * rows_used * 256 is a multiple of the pieces per pixel (Cp / 8 in 16-bit storage, Cp / 4 in f32).  Both 0: nothing to launch, or
+ * an InstanceNorm plane that takes the single launch.  The launchers take their grids from the same function, and where they
+ * refuse (more samples than tickets, a region too small for one grid unit of rows, more channels than the backward kernels hold)
+ * the query returns P2PHD_EINVAL with their error text; an unknown family is P2PHD_EINVAL too. */
+int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C, int* rows_wanted, int* rows_used);
 /* Residual trunk (networks.py:231-252: ReflectionPad2d(1) + Conv2d 3x3 + InstanceNorm): the input gradient of such a conv reads
  * dy plus the pair-sum rows / columns of the reflection's adjoint.  For planes that take the single-launch InstanceNorm backward
  * the kernel that WRITES dy appends them: allocate dy with p2phd_conv_reflect_extras_elems(desc) extra elements right behind its

@@ -52,6 +52,9 @@ int imdct4_fast(const float* spec, int64_t B, int64_t n_frames, int n_fft, const
 enum FoldRegion { FOLD_IN_BWD = 0, FOLD_COLSUM = 1, FOLD_ACT_DB = 2, FOLD_LOSS = 3, FOLD_GCONV = 4, FOLD_PCM = 5, FOLD_TRUEPEAK = 6, FOLD_LIMITER = 7, FOLD_LTAS = 8 };
 struct FoldScratch { float* part; unsigned* ticket; size_t floats; int tickets; };
 FoldScratch fold_scratch(int region, hipStream_t stream);   // part == nullptr: refused (error text set), see core.hip
+// floats and tickets of a region, pointers null: host arithmetic on the table fold_scratch() hands out from -- no device call, no
+// stream, no ordering.  What sizes a launch by the scratch asks here, so that a host query can repeat the answer without a device.
+FoldScratch fold_capacity(int region);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ void fold_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

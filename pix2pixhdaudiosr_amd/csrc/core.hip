@@ -62,6 +62,11 @@ bool capturing(hipStream_t s) {
 
 thread_local int g_fold_pending = -1;
 
+FoldScratch fold_capacity(int region) {
+  if (region < 0 || region >= kFoldRegions) return FoldScratch{nullptr, nullptr, 0, 0};
+  return FoldScratch{nullptr, nullptr, kFoldFloats[region], kFoldTickets[region]};
+}
+
 // The region's partial rows and tickets, for a launch on `stream`.  One region serves ONE stream at a time.  Round 5 (advisor):
 // the region's last launch is remembered as an EVENT recorded behind it (fold_launched), never as a stream handle to be
 // queried later -- the handle may belong to a stream that has been destroyed since, and hipStreamQuery on it is undefined.
@@ -86,7 +91,8 @@ FoldScratch fold_scratch(int region, hipStream_t stream) {
   g_fold_pending_stream = stream;
   size_t fo = 0; int to = 0;
   for (int r = 0; r < region; ++r) { fo += kFoldFloats[r]; to += kFoldTickets[r]; }
-  return FoldScratch{f->part + fo, f->ticket + to, kFoldFloats[region], kFoldTickets[region]};
+  const FoldScratch cap_of = fold_capacity(region);
+  return FoldScratch{f->part + fo, f->ticket + to, cap_of.floats, cap_of.tickets};
 }
 
 void fold_launched() {

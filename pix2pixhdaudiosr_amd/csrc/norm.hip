@@ -7,6 +7,7 @@
 // stats), :188,233 (ReLU), :342-358 (LeakyReLU 0.2), :165,308 (AvgPool2d), :252 (residual add).
 #include "common.h"
 #include "convdev.h"
+#include <cstring>
 namespace p2phd { extern int g_opt_wgrad_xcd; }   // 1 (default): XCD-aware workgroup order (core.hip)
 
 namespace {
@@ -842,11 +843,75 @@ extern "C" int p2phd_instnorm_act_bwd_two_pass(int dtype, int N, int64_t HW, int
   return (N > 0 && HW > 0 && !bwd_single_launch(dtype, N, HW, C)) ? 1 : 0;
 }
 
+// ---- grids of the two launches that size themselves by a region of the reduction scratch ----------------------------------
+// Workgroups per sample: `wanted` is what the plane takes without the scratch limit (stationary_grid), `used` what the launch
+// that writes partial rows takes -- one row per workgroup has to fit the region, and the clamp keeps gridDim.x * 256 a multiple of
+// the pieces per pixel (the kernels are channel-stationary).  The launchers and p2phd_reduction_rows call these two functions and
+// nothing else restates the arithmetic or the refusals.
+struct FoldRows { int wanted = 0, used = 0; };
+
+// InstanceNorm backward.  Both 0: nothing to launch, or the plane takes the single launch.  `reduce` false (the apply pass alone):
+// `wanted` only, the scratch is not asked.
+static int instnorm_bwd_rows(int dtype, int N, int64_t HW, int C, bool reduce, FoldRows* r) {
+  *r = FoldRows{};
+  const int Cp = (C + 7) & ~7;
+  P2PHD_REQUIRE(Cp <= kMaxCp, "instnorm: at most %d channels", kMaxCp);
+  if (N == 0 || HW == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(N > 0 && HW > 0 && C >= 1, "instnorm_act_bwd: bad geometry");
+  if (bwd_single_launch(dtype, N, HW, C)) return P2PHD_OK;
+  const int epp = dtype == P2PHD_BF16 ? 8 : 4;
+  r->wanted = stationary_grid(HW, Cp / epp, N);
+  if (!reduce) return P2PHD_OK;
+  // partial table of the fixed-order reduction: one row of 2 * Cp floats per workgroup, one ticket per sample
+  const p2phd::FoldScratch cap = p2phd::fold_capacity(p2phd::FOLD_IN_BWD);
+  P2PHD_REQUIRE(N <= cap.tickets, "instnorm_act_bwd: at most %d samples per call", cap.tickets);
+  const int unit = stationary_unit(Cp / epp);
+  const long rows_max = (long)(cap.floats / (2 * (size_t)Cp * (size_t)N));
+  P2PHD_REQUIRE(rows_max >= unit, "instnorm_act_bwd: N * channels too large for the reduction scratch");
+  r->used = (int)std::min<long>(r->wanted, rows_max / unit * unit);
+  return P2PHD_OK;
+}
+
+// p2phd_act_bwd_db: one row of Cp floats per workgroup, one ticket.  Both 0: no pixels.
+static int act_bwd_db_rows(int dtype, int64_t n_pixels, int C, FoldRows* r) {
+  *r = FoldRows{};
+  const int Cp = (C + 7) & ~7;
+  P2PHD_REQUIRE(Cp <= kMaxCp, "act_bwd_db: at most %d channels", kMaxCp);
+  P2PHD_REQUIRE(n_pixels >= 0 && C >= 1, "act_bwd_db: bad geometry");
+  if (n_pixels == 0) return P2PHD_OK;
+  const int epp = dtype == P2PHD_BF16 ? 8 : 4;
+  const p2phd::FoldScratch cap = p2phd::fold_capacity(p2phd::FOLD_ACT_DB);
+  const int unit = stationary_unit(Cp / epp);
+  const long rows_max = (long)(cap.floats / (size_t)Cp);
+  P2PHD_REQUIRE(rows_max >= unit, "act_bwd_db: too many channels for the reduction scratch");
+  r->wanted = stationary_grid(n_pixels, Cp / epp, 1);
+  r->used = (int)std::min<long>(r->wanted, rows_max / unit * unit);
+  return P2PHD_OK;
+}
+
+extern "C" int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C, int* rows_wanted, int* rows_used) {
+  P2PHD_REQUIRE(family && rows_wanted && rows_used, "reduction_rows: null pointer");
+  *rows_wanted = *rows_used = 0;
+  if (dtype != P2PHD_BF16 && dtype != P2PHD_F32) { p2phd::set_error("reduction_rows: unsupported dtype %d", dtype); return P2PHD_EUNSUPPORTED; }
+  FoldRows rows;
+  if (!strcmp(family, "instnorm_bwd")) {
+    if (int rc = instnorm_bwd_rows(dtype, N, P, C, true, &rows)) return rc;
+  } else if (!strcmp(family, "act_bwd_db")) {
+    P2PHD_REQUIRE(N == 1, "reduction_rows: act_bwd_db reduces one plane (N = 1, P = all its pixels)");
+    if (int rc = act_bwd_db_rows(dtype, P, C, &rows)) return rc;
+  } else {
+    P2PHD_REQUIRE(false, "reduction_rows: unknown family \"%s\" (instnorm_bwd, act_bwd_db)", family);
+  }
+  *rows_wanted = rows.wanted; *rows_used = rows.used;
+  return P2PHD_OK;
+}
+
 static int instnorm_act_bwd_impl(int dtype, const void* g, const void* y, const float* stats, float* bstats, void* dy,
                                  float* db, int db_accumulate, int N, int64_t HW, int C, float eps, int act, void* stream,
                                  bool sums_given = false, void* rx = nullptr, int W = 0) {
   const int Cp = (C + 7) & ~7;
-  P2PHD_REQUIRE(Cp <= kMaxCp, "instnorm: at most %d channels", kMaxCp);
+  FoldRows rows;
+  if (int rc = instnorm_bwd_rows(dtype, N, HW, C, !sums_given, &rows)) return rc;
   if (N == 0 || HW == 0) return P2PHD_OK;
   P2PHD_REQUIRE(g && y && stats && (bstats || rx) && dy, "instnorm_act_bwd: null pointer");
   P2PHD_REQUIRE(rx == nullptr || (bwd_single_launch(dtype, N, HW, C) && W >= 4 && HW % W == 0 && HW / W >= 4),
@@ -867,16 +932,11 @@ static int instnorm_act_bwd_impl(int dtype, const void* g, const void* y, const 
 #undef P2PHD_FUSED_BWD
     return p2phd::check_launch("instnorm_act_bwd(fused)");
   }
-  dim3 grid(stationary_grid(HW, Cp / epp, N), N);
+  dim3 grid(rows.wanted, N);
   if (!sums_given) {
-    // partial table of the fixed-order reduction: one row of 2 * Cp floats per workgroup, one ticket per sample
     const p2phd::FoldScratch fs = p2phd::fold_scratch(p2phd::FOLD_IN_BWD, st);
     if (fs.part == nullptr) return P2PHD_EINVAL;                 // (refused: error text set by fold_scratch)
-    P2PHD_REQUIRE(N <= fs.tickets, "instnorm_act_bwd: at most %d samples per call", fs.tickets);
-    const int unit = stationary_unit(Cp / epp);
-    const long rows_max = (long)(fs.floats / (2 * (size_t)Cp * (size_t)N));
-    P2PHD_REQUIRE(rows_max >= unit, "instnorm_act_bwd: N * channels too large for the reduction scratch");
-    dim3 rgrid(std::min<long>(grid.x, rows_max / unit * unit), N);
+    dim3 rgrid(rows.used, N);                                    // (instnorm_bwd_rows: rows.used rows per sample fit the region)
     DISPATCH_T(dtype,
                hipLaunchKernelGGL(in_act_bwd_reduce_kernel<bf16_t>, rgrid, dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)y, stats, bstats, (long)HW, C, Cp, eps, act, fs.part, fs.ticket),
                hipLaunchKernelGGL(in_act_bwd_reduce_kernel<float>, rgrid, dim3(256), 0, st, (const float*)g, (const float*)y, stats, bstats, (long)HW, C, Cp, eps, act, fs.part, fs.ticket),
@@ -1004,8 +1064,8 @@ extern "C" int p2phd_nhwc_to_nchw(int dtype, const void* src, float* dst, int N,
 extern "C" int p2phd_act_bwd_db(int dtype, const void* g, const void* a, void* dx, int64_t n_pixels, int C, int act, float* db,
                                 int db_accumulate, void* stream) {
   const int Cp = (C + 7) & ~7;
-  P2PHD_REQUIRE(Cp <= kMaxCp, "act_bwd_db: at most %d channels", kMaxCp);
-  P2PHD_REQUIRE(n_pixels >= 0 && C >= 1, "act_bwd_db: bad geometry");
+  FoldRows rows;
+  if (int rc = act_bwd_db_rows(dtype, n_pixels, C, &rows)) return rc;
   P2PHD_REQUIRE(db != nullptr, "act_bwd_db: null bias-gradient pointer (use p2phd_act_bwd)");
   hipStream_t st = (hipStream_t)stream;
   if (n_pixels == 0) {
@@ -1013,14 +1073,10 @@ extern "C" int p2phd_act_bwd_db(int dtype, const void* g, const void* a, void* d
     return P2PHD_OK;
   }
   P2PHD_REQUIRE(g && a && dx, "act_bwd_db: null pointer");
-  const int epp = dtype == P2PHD_BF16 ? 8 : 4;
   // bias gradient with a REAL value (no normalisation behind the conv): summed in a fixed order, see in_act_bwd_reduce_kernel
   const p2phd::FoldScratch fs = p2phd::fold_scratch(p2phd::FOLD_ACT_DB, st);
   if (fs.part == nullptr) return P2PHD_EINVAL;                   // (refused: error text set by fold_scratch)
-  const int unit = stationary_unit(Cp / epp);
-  const long rows_max = (long)(fs.floats / (size_t)Cp);
-  P2PHD_REQUIRE(rows_max >= unit, "act_bwd_db: too many channels for the reduction scratch");
-  dim3 grid(std::min<long>(stationary_grid(n_pixels, Cp / epp, 1), rows_max / unit * unit));
+  dim3 grid(rows.used);                                          // (act_bwd_db_rows: one partial row per workgroup fits the region)
   DISPATCH_T(dtype,
              hipLaunchKernelGGL(act_bwd_db_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)a, (bf16_t*)dx, (long)n_pixels, C, Cp, act, db, db_accumulate, fs.part, fs.ticket),
              hipLaunchKernelGGL(act_bwd_db_kernel<float>, grid, dim3(256), 0, st, (const float*)g, (const float*)a, (float*)dx, (long)n_pixels, C, Cp, act, db, db_accumulate, fs.part, fs.ticket),

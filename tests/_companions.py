@@ -19,6 +19,8 @@ Plain helper: no fixtures, no test functions.  tests/test_companions_host.py pin
 and shows that the bounds are usable and that they bite; tests/test_gpu_companions.py runs the kernels against them.
 
 Layouts are the physical ones: activations [N, HW, Cp] (Cp = cpitch(C), pad channels zero), stats / bstats [N, Cp, 2]."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -120,6 +122,38 @@ IN_CASES = [
     (2, 17920, 16, 1, "a plane of more than 16384 pixels"),
 ]
 IN_IDS = [f"n{c[0]}_hw{c[1]}_c{c[2]}" for c in IN_CASES]
+# Two-pass planes whose reduce launch is CLAMPED to its region of the reduction scratch (csrc/norm.hip, instnorm_bwd_rows:
+# rows_max = 2^21 / (Cp N) partial rows per sample, rounded down to a multiple of the grid unit).  A list of its own: only the
+# backward tests walk it.  The tests ask p2phd_reduction_rows for the grids and assert used < wanted before they launch; the
+# figures in the descriptions are what the arithmetic gives today (wanted -> used per sample, 16-bit storage / f32).
+IN_CLAMP_CASES = [
+    (1, 2400, 4096, 1, "the most channels the kernels hold, one sample: rows_max 512; 600 -> 512 / 1200 -> 512"),
+    (8, 1100, 2048, 1, "configs[4] trunk width at its benchmarked batch: rows_max 128; 138 -> 128 / 256 -> 128"),
+    (3, 5000, 1536, 1, "configs[3] trunk width, cpr 192 / 384: grid unit 3, rows_max 455 rounds down to 453; 468 -> 453 / 681 -> 453"),
+]
+IN_CLAMP_IDS = [f"n{c[0]}_hw{c[1]}_c{c[2]}" for c in IN_CLAMP_CASES]
+# (P, C) of p2phd_act_bwd_db; the clamped ones: rows_max = 2^20 / Cp.  wanted -> used: (1100, 4096) 274 -> 256 / 548 -> 256 (the most
+# channels), (8000, 1536) 750 -> 681 / 1500 -> 681 (grid unit 3: rows_max 682 rounds down)
+ACT_DB_CASES = [(1, 3), (40, 40), (1320, 24), (700, 67), (5000, 200)]
+ACT_DB_CLAMP_CASES = [(1100, 4096), (8000, 1536)]
+
+
+def reduction_rows(lib, family, code, N, P, C):
+    """p2phd_reduction_rows (host arithmetic, no device): (return code, rows_wanted, rows_used) per sample."""
+    wanted, used = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    rc = lib.p2phd_reduction_rows(family.encode(), code, N, P, C, ctypes.byref(wanted), ctypes.byref(used))
+    return rc, wanted.value, used.value
+
+
+def clamped_rows(lib, family, code, N, P, C, epp):
+    """(wanted, used) of a case that a test means to run on the clamped path: asserts that it is one, and that the clamp left the
+    grid stride a multiple of the pieces per pixel."""
+    rc, wanted, used = reduction_rows(lib, family, code, N, P, C)
+    what = f"{family} N {N} P {P} C {C} dtype code {code}: wanted {wanted}, used {used}"
+    assert rc == 0, (what, lib.p2phd_last_error())
+    assert 1 <= used < wanted, what + ": not clamped by the reduction scratch (has the region grown?)"
+    assert used * 256 % (cpitch(C) // epp) == 0, what + ": the grid stride is no multiple of the pieces per pixel"
+    return wanted, used
 CH_7SIGMA, CH_ONMEAN, CH_CONST = 0, 1, 2                       # C >= 3 in every case; channel 3 (if any) is the second constant one
 ONMEAN = 0.25
 CONST = 0.5

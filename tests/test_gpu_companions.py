@@ -7,9 +7,14 @@ generator, and every element is compared with the float64 reference of tests/_co
 for bit where the operation is a single rounding).  tests/test_companions_host.py shows on the CPU that those bounds hold for a
 float32 emulation of the kernels and reject the listed mutants, and pins which backward form each InstanceNorm case takes.
 
-Left out on purpose: the cap of the reduce grid by the scratch (`rows_max`: needs N * Cp of 100 k and more on planes above 640
-pixels), the AvgPool grid-stride loop (starts at 2 M pieces) and the statistics merges (reached through the conv epilogue, covered
-by tests/test_gpu_conv_exact.py)."""
+The launches that shrink their grid to fit the library's reduction scratch (`rows_max` of the InstanceNorm backward's reduce pass
+and of p2phd_act_bwd_db) have cases of their own, K.IN_CLAMP_CASES and K.ACT_DB_CLAMP_CASES: each asks p2phd_reduction_rows
+(pinned on the host by tests/test_reduction_rows.py) and asserts that it IS clamped before it launches.  The same clamp of the
+column sum (csrc/convaux.hip, launch_colsum) is NOT tested: it engages from about 134 M elements (Cp = 4096 on more than 32 k
+pixels), out of reach of a test of seconds.
+
+Left out on purpose: the AvgPool grid-stride loop (starts at 2 M pieces) and the statistics merges (reached through the conv
+epilogue, covered by tests/test_gpu_conv_exact.py)."""
 import ctypes as C
 
 import numpy as np
@@ -202,6 +207,47 @@ def test_instnorm_backward_apply_alone(case, dt):
 
 
 @pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("case", K.IN_CLAMP_CASES, ids=K.IN_CLAMP_IDS)
+def test_instnorm_backward_with_the_reduce_grid_clamped_to_the_scratch(case, dt):
+    """The two-pass form where the reduce pass runs on FEWER workgroups per sample than the apply pass, because one partial row
+    per workgroup has to fit the reduction scratch (the configs[4] trunk at its benchmarked batch runs here).  p2phd_reduction_rows
+    proves the clamp before anything is launched.  Then as test_instnorm_backward: `bwd` and `acc` with two activations, dy per
+    element, both sums, db, guard bands, dy and bstats bit for bit on a second run; and the apply pass alone (it keeps the
+    unclamped grid) fed the reference sums, as test_instnorm_backward_apply_alone.  The float64 reference of each activation is
+    built once and serves the entries that use it."""
+    ops, Lb, code, epp = _setup(dt)
+    N, HW, Cc = case[:3]
+    assert Lb.p2phd_instnorm_act_bwd_two_pass(code, N, HW, Cc) == 1
+    wanted, used = K.clamped_rows(Lb, "instnorm_bwd", code, N, HW, Cc, epp)
+    print(f"instnorm_bwd {case[:3]} {dt}: rows wanted {wanted}, used {used}")
+    d, g = _in_dev(case, dt)
+    gen = torch.Generator().manual_seed(77)
+    ref = None
+    for entry, act in (("bwd", RELU), ("acc", LRELU)):
+        what = f"instnorm_act_bwd[{entry}] {case[:3]} {dt} act {act}, reduce grid {used} of {wanted}"
+        prefill = torch.randn(Cc, generator=gen) if entry == "acc" else None
+        dy, bst, db, _, rc = _run_bwd(Lb, ops, code, entry, g, d["y"].shape, DT[dt], N, HW, Cc, act, prefill)
+        ops.check(rc, what)
+        ref = K.instnorm_bwd_reference(d["g"], d["y"], d["stats"], HW, Cc, K.EPS, act)
+        bound = K.stored_bound(ref["dy"], ref["b32"], DT[dt])
+        K.bstats_check(bst, ref, Cc, what + " bstats")
+        K.assert_within(dy, ref["dy"], bound, what + " dy", Cc)
+        K.colsum_check(dy, db, Cc, what + " db", prefill)
+        dy2, bst2, _, _, rc = _run_bwd(Lb, ops, code, entry, g, d["y"].shape, DT[dt], N, HW, Cc, act, prefill)
+        ops.check(rc, what)
+        _same_bits(dy2, dy, what + " dy, second run")
+        _same_bits(bst2, bst, what + " bstats, second run")
+        del dy, dy2
+    what = f"instnorm_act_bwd_apply {case[:3]} {dt}, grid {wanted}"              # (ref, bound: those of LRELU)
+    sums = torch.stack([ref["s1"], ref["s2"]], -1).float().cuda()
+    dy, bst, db, _, rc = _run_bwd(Lb, ops, code, "apply", g, d["y"].shape, DT[dt], N, HW, Cc, LRELU, None, sums)
+    ops.check(rc, what)
+    _same_bits(bst, sums, what + " bstats is an input")
+    K.assert_within(dy, ref["dy"], bound, what + " dy", Cc)
+    K.colsum_check(dy, db, Cc, what + " db")
+
+
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("case", [c for c in K.IN_CASES if not c[3]], ids=[i for i, c in zip(K.IN_IDS, K.IN_CASES) if not c[3]])
 def test_instnorm_backward_single_launch_in_both_workgroup_orders(case, dt):
     ops, Lb, code, _ = _setup(dt)
@@ -263,11 +309,19 @@ def test_act_bwd(pieces, dt):
 
 
 @pytest.mark.parametrize("dt", DTS)
-@pytest.mark.parametrize("geom", [(1, 3), (40, 40), (1320, 24), (700, 67), (5000, 200)], ids=lambda g: "x".join(map(str, g)))
+@pytest.mark.parametrize("geom", K.ACT_DB_CASES + K.ACT_DB_CLAMP_CASES, ids=lambda g: "x".join(map(str, g)))
 def test_act_bwd_db(geom, dt):
-    ops, Lb, code, _ = _setup(dt)
+    """The K.ACT_DB_CLAMP_CASES run with the grid clamped to the reduction scratch (asserted through p2phd_reduction_rows before
+    the first launch), the others on the grid the plane asks for."""
+    ops, Lb, code, epp = _setup(dt)
     P, Cc = geom
     Cp = K.cpitch(Cc)
+    if geom in K.ACT_DB_CLAMP_CASES:
+        wanted, used = K.clamped_rows(Lb, "act_bwd_db", code, 1, P, Cc, epp)
+        print(f"act_bwd_db {geom} {dt}: rows wanted {wanted}, used {used}")
+    else:
+        rc, wanted, used = K.reduction_rows(Lb, "act_bwd_db", code, 1, P, Cc)
+        assert rc == 0 and used == wanted
     g, a = _act_operands((1, P, Cc), F32, P + Cc)
     g, a = K.physical(g, DT[dt]), K.physical(a, DT[dt])
     gd, ad = g.cuda(), a.cuda()
