@@ -95,7 +95,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * of whole-file generation, csrc/truepeak.hip), "limiter" (the envelope and the gain curve of its look-ahead true-peak limiter,
  * csrc/limiter.hip), "bandwidth" (the long-term average spectrum and the band-edge decision of its bandwidth report,
  * csrc/bandwidth.hip), "stereo" (the cross-spectrum and the band sums of its stereo image report and the mid/side matrix of
- * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip).
+ * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip), "normscope" (the range
+ * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -888,6 +889,29 @@ int p2phd_spectro_decode_signed(const float* log_spectro, const float* pha, cons
 int p2phd_spectro_decode_spliced(const float* sr_log_spectro, const float* lr_log_spectro, const float* pha,
                                  const float* norm_min_max, int64_t B, int64_t F, int64_t M, int channels,
                                  int keep_rows, int fade_rows, float min_value, float scale, float* spec, void* stream);
+
+/* One normalisation range for many encodes (whole-file generation, norm_scope='clip'): the range is found in a pass in front
+ * of the encodes, accumulated on the device, and handed to each of them.
+ * p2phd_spectro_range: the dB values p2phd_spectro_encode_ex computes for spec [B,F,M] (the same expressions in the same
+ *   order; none is written), their minimum and maximum folded into the two floats at minmax_io on the device:
+ *   minmax_io = (fminf(minmax_io[0], min), fmaxf(minmax_io[1], max)).  The caller starts it at (+inf, -inf); min and max do
+ *   not depend on the order of the fold, so one call on a tensor leaves the norm8[0:2] p2phd_spectro_encode_ex leaves for it,
+ *   bit for bit, and calls on the pieces of a tensor leave its range.  partials: p2phd_spectro_partials_floats(B,F,M) floats.
+ * p2phd_range_fold: the same fold for n plain floats (the mask noise; NaN entries are passed over, as the encode's statistics
+ *   pass them over).  partials: at least 4 * 1024 floats.
+ * p2phd_spectro_encode_given: p2phd_spectro_encode_ex with the statistics read from norm8 on the device instead of computed
+ *   -- [0], [1] the spectrum's min and max, [4], [5] the noise's (read only where noise rows are written), the layout that
+ *   entry leaves -- and nothing written to norm8.  Under the tensor's own statistics it writes that entry's log_spectro and
+ *   pha bit for bit, with one exception: a range of zero (max == min) gives the scale 0 where that entry divides by it, for
+ *   the spectrum and for the noise alike, so digital silence under its own range encodes as zeros, not NaN.
+ * Two launches (range, fold) or one (encode_given), none for B == 0 or n == 0; nothing allocated, no synchronisation, no
+ * atomics: capturable.  Launch family "normscope", one per call that launches. */
+int p2phd_spectro_range(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha, float min_value,
+                        float* minmax_io, float* partials, void* stream);
+int p2phd_range_fold(const float* x, int64_t n, float* minmax_io, float* partials, void* stream);
+int p2phd_spectro_encode_given(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha, float min_value,
+                               int mask_rows, int mask_mode, const float* noise, const float* noise_sign, const float* norm8,
+                               float* log_spectro, float* pha, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics (csrc/metrics.hip): compute_matrics (util/util.py:133-184).

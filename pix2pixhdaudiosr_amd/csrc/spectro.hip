@@ -10,6 +10,9 @@
 //   pass 2  normalises in place (:193) and overwrites the top mask rows with min-max-scaled noise (:196-226).
 // decode: log_spectro[B,2,M,F] -> spec[B,F,M] = (A0 - A1)/(2 alpha - 1), A = DB_to_amplitude(|x|(max-min)+min, 10, .5) - min_value
 #include "common.h"
+#include "convplan.h"
+#include <algorithm>
+#include <cstdint>
 
 namespace {
 
@@ -245,6 +248,133 @@ __global__ __launch_bounds__(256) void decode_spliced_kernel(const float* __rest
   }
 }
 
+// ---- one normalisation range for many encodes (whole-file generation, norm_scope='clip') ------------------------------------
+// The range is found in a pass in front of the encodes (range_kernel + range_fold_kernel, accumulated in two floats on the
+// device), then every encode reads it (encode_given_kernel) instead of reducing its own tensor.
+
+// What encode_pass1_kernel (CH = 2, 1: its dB values for the spectrum value s, the same expressions in the same order) or
+// stats4_kernel (CH = 0: the value itself) folds into its min and max.
+template <int CH>
+__device__ __forceinline__ void fold_minmax(float s, float alpha, float min_value, float& mn, float& mx) {
+  if (CH == 2) {
+    const float neg = 0.5f * (fabsf(s) - s);
+    const float pos = s + neg;
+    const float d0 = 20.f * log10f(fmaxf(alpha * pos + (1.f - alpha) * neg, min_value)) - 20.f;
+    const float d1 = 20.f * log10f(fmaxf((1.f - alpha) * pos + alpha * neg, min_value)) - 20.f;
+    mn = fminf(mn, fminf(d0, d1)); mx = fmaxf(mx, fmaxf(d0, d1));
+  } else if (CH == 1) {
+    const float d0 = 20.f * log10f(fmaxf(fabsf(s) + min_value, min_value)) - 20.f;
+    mn = fminf(mn, d0); mx = fmaxf(mx, d0);
+  } else {
+    mn = fminf(mn, s); mx = fmaxf(mx, s);
+  }
+}
+
+// (mn, mx) of a block of 256 threads; thread 0 holds the result
+__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
+  __shared__ float red[4][2];
+  for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o)); }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[w][0] = mn; red[w][1] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 1; i < 4; ++i) { mn = fminf(mn, red[i][0]); mx = fmaxf(mx, red[i][1]); }
+}
+
+// A streaming read of x[0, n): the first 4 * n4 floats as float4 (n4 = 0 where x is not 16-byte aligned), the rest one by one;
+// min and max do not depend on the order, so the tile walk of pass 1 is not repeated.  partials[2 * block] = (min, max).
+template <int CH>
+__global__ __launch_bounds__(256) void range_kernel(const float* __restrict__ x, long n, long n4, float alpha, float min_value,
+                                                    float* __restrict__ partials) {
+  float mn = INFINITY, mx = -INFINITY;
+  const long stride = (long)gridDim.x * 256;
+  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += stride) {
+    const float4 v = x4[e];
+    fold_minmax<CH>(v.x, alpha, min_value, mn, mx); fold_minmax<CH>(v.y, alpha, min_value, mn, mx);
+    fold_minmax<CH>(v.z, alpha, min_value, mn, mx); fold_minmax<CH>(v.w, alpha, min_value, mn, mx);
+  }
+  for (long e = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) fold_minmax<CH>(x[e], alpha, min_value, mn, mx);
+  block_minmax(mn, mx);
+  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = mn; partials[2 * blockIdx.x + 1] = mx; }
+}
+
+// minmax_io = (fminf(minmax_io[0], min of the partials), fmaxf(minmax_io[1], max of the partials)): one block, plain stores
+__global__ __launch_bounds__(256) void range_fold_kernel(const float* __restrict__ partials, int nblk, float* __restrict__ minmax_io) {
+  float mn = INFINITY, mx = -INFINITY;
+  for (int i = threadIdx.x; i < nblk; i += 256) { mn = fminf(mn, partials[2 * i]); mx = fmaxf(mx, partials[2 * i + 1]); }
+  block_minmax(mn, mx);
+  if (threadIdx.x == 0) { minmax_io[0] = fminf(minmax_io[0], mn); minmax_io[1] = fmaxf(minmax_io[1], mx); }
+}
+
+template <int CH>
+int launch_range(const float* x, long n, float alpha, float min_value, float* minmax_io, float* partials, hipStream_t st) {
+  const long n4 = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
+  const long items = n4 + (n - 4 * n4);
+  const int nb = (int)std::min<long>((items + 255) / 256, 1024);  // 2 * 1024 floats: inside the 4 * 1024 every caller's workspace has
+  hipLaunchKernelGGL(range_kernel<CH>, dim3(nb), dim3(256), 0, st, x, n, n4, alpha, min_value, partials);
+  hipLaunchKernelGGL(range_fold_kernel, dim3(1), dim3(256), 0, st, partials, nb, minmax_io);
+  return nb;
+}
+
+// encode_pass1_kernel and encode_pass2_kernel in one pass over the tile, the statistics read from norm8 = (min, max, -, -,
+// noise_min, noise_max, -, -): the dB values of the kept rows by pass 1's expressions, normalised by pass 2's; the mask rows
+// by pass 2's, their dB values never formed.  A range of zero gives the scale 0 where pass 2 divides by it.
+__global__ __launch_bounds__(256) void encode_given_kernel(const float* __restrict__ spec, const float* __restrict__ norm8,
+                                                           const float* __restrict__ noise, const float* __restrict__ noise_sign,
+                                                           float* __restrict__ out, float* __restrict__ pha, int F, int M,
+                                                           float alpha, float min_value, int channels, int mask_rows, int mask_mode) {
+  __shared__ float tile[32][33];
+  const int b = blockIdx.z, m0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  for (int i = 0; i < 4; ++i) {
+    const int f = f0 + ty + 8 * i, m = m0 + tx;
+    tile[ty + 8 * i][tx] = (f < F && m < M) ? spec[((size_t)b * F + f) * M + m] : 0.f;
+  }
+  const float mn = norm8[0], range = norm8[1] - norm8[0];
+  const float scale = range == 0.f ? 0.f : 1.f / range;
+  float nmn = 0.f, nscale = 0.f;
+  if (noise != nullptr) {
+    const float nrange = norm8[5] - norm8[4];
+    nmn = mask_mode == 0 ? 0.f : norm8[4];
+    nscale = nrange == 0.f ? 0.f : 1.f / nrange;
+  }
+  const int keep = M - mask_rows;
+  const size_t plane = (size_t)M * F;
+  __syncthreads();
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + ty + 8 * i, f = f0 + tx;
+    if (m < M && f < F) {
+      const float s = tile[tx][ty + 8 * i];
+      pha[((size_t)b * M + m) * F + f] = s > 0.f ? 1.f : (s < 0.f ? -1.f : 0.f);
+      const size_t o = ((size_t)b * channels * M + m) * F + f;
+      if (m < keep) {
+        if (channels == 2) {
+          const float neg = 0.5f * (fabsf(s) - s);
+          const float pos = s + neg;
+          const float d0 = 20.f * log10f(fmaxf(alpha * pos + (1.f - alpha) * neg, min_value)) - 20.f;
+          const float d1 = 20.f * log10f(fmaxf((1.f - alpha) * pos + alpha * neg, min_value)) - 20.f;
+          out[o] = (d0 - mn) * scale;
+          out[o + plane] = (d1 - mn) * scale;
+        } else {
+          const float d0 = 20.f * log10f(fmaxf(fabsf(s) + min_value, min_value)) - 20.f;
+          out[o] = (d0 - mn) * scale;
+        }
+      } else {
+        for (int c = 0; c < channels; ++c) {
+          float v = 0.f;
+          if (noise != nullptr) {
+            const size_t q = (((size_t)b * channels + c) * mask_rows + (m - keep)) * F + f;
+            v = (noise[q] - nmn) * nscale;
+            if (mask_mode == 1) v *= noise_sign[q];
+          }
+          out[o + c * plane] = v;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t p2phd_spectro_partials_floats(int64_t B, int64_t F, int64_t M) {
@@ -332,4 +462,46 @@ extern "C" int p2phd_spectro_decode_spliced(const float* sr_log_spectro, const f
   hipLaunchKernelGGL(decode_spliced_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, sr_log_spectro, lr_log_spectro, pha,
                      norm_min_max, spec, (int)F, (int)M, channels, keep_rows, fade_rows, min_value, scale);
   return p2phd::check_launch("spectro_decode_spliced");
+}
+
+extern "C" int p2phd_spectro_range(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha, float min_value,
+                                   float* minmax_io, float* partials, void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_range: bad geometry");
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_range: channels must be 2 (explicit encoding) or 1, got %d", channels);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(spec && minmax_io && partials, "spectro_range: null pointer");
+  const long n = (long)(B * F * M);
+  if (channels == 2) launch_range<2>(spec, n, alpha, min_value, minmax_io, partials, (hipStream_t)stream);
+  else launch_range<1>(spec, n, alpha, min_value, minmax_io, partials, (hipStream_t)stream);
+  ++p2phd::g_launch_count[p2phd::LC_NORMSCOPE];
+  return p2phd::check_launch("spectro_range");
+}
+
+extern "C" int p2phd_range_fold(const float* x, int64_t n, float* minmax_io, float* partials, void* stream) {
+  P2PHD_REQUIRE(n >= 0, "range_fold: bad length %lld", (long long)n);
+  if (n == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(x && minmax_io && partials, "range_fold: null pointer");
+  launch_range<0>(x, (long)n, 0.f, 0.f, minmax_io, partials, (hipStream_t)stream);
+  ++p2phd::g_launch_count[p2phd::LC_NORMSCOPE];
+  return p2phd::check_launch("range_fold");
+}
+
+extern "C" int p2phd_spectro_encode_given(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha,
+                                          float min_value, int mask_rows, int mask_mode, const float* noise,
+                                          const float* noise_sign, const float* norm8, float* log_spectro, float* pha,
+                                          void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_encode_given: bad geometry");
+  P2PHD_REQUIRE(mask_rows >= 0 && mask_rows <= M, "spectro_encode_given: mask_rows %d outside [0, %lld]", mask_rows, (long long)M);
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_encode_given: channels must be 2 (explicit encoding) or 1, got %d", channels);
+  P2PHD_REQUIRE(mask_mode >= 0 && mask_mode <= 2, "spectro_encode_given: mask_mode must be 0, 1 or 2, got %d", mask_mode);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(spec && log_spectro && pha && norm8, "spectro_encode_given: null pointer");
+  P2PHD_REQUIRE(!(mask_mode == 1 && noise != nullptr && mask_rows > 0 && noise_sign == nullptr),
+                "spectro_encode_given: mask mode1 needs the sign tensor");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_encode_given: grid too large");
+  dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(encode_given_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, spec, norm8, mask_rows > 0 ? noise : nullptr,
+                     noise_sign, log_spectro, pha, (int)F, (int)M, alpha, min_value, channels, mask_rows, mask_mode);
+  ++p2phd::g_launch_count[p2phd::LC_NORMSCOPE];
+  return p2phd::check_launch("spectro_encode_given");
 }

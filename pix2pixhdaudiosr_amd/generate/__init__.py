@@ -14,10 +14,18 @@ reference's chain exactly, its amplitude included: with MDCT2 the reference's ou
 because its util.imdct halves what IMDCT2 already returns at unit gain.  With overlapping segments the pipeline returns the
 full amplitude -- 6 dB more; `SuperResolver(reference_amplitude=...)` and `--reference_amplitude 0|1` choose explicitly.
 
-A group is semantics: `to_spectro` normalises by the min / max of the whole batch tensor (pix2pixHD_model.py:165-168 of the
-reference), so a group holds exactly the segments the reference's loader would put in it and a last, smaller group runs at
-its own size -- padding it with silent segments would change its normalisation.  For the same reason a channel of a file is
-a clip of its own: a group never mixes channels, and channel c of a [C, L] clip is grouped exactly as the mono clip audio[c].
+With the default `norm_scope='group'` a group is semantics: `to_spectro` normalises by the min / max of the whole batch tensor
+(pix2pixHD_model.py:165-168 of the reference), so a group holds exactly the segments the reference's loader would put in it and a
+last, smaller group runs at its own size -- padding it with silent segments would change its normalisation.  For the same reason
+a channel of a file is a clip of its own: a group never mixes channels, and channel c of a [C, L] clip is grouped exactly as the
+mono clip audio[c].
+
+`--norm_scope clip` (opt-in, `SuperResolver(norm_scope='clip')`; csrc/spectro.hip) takes the semantics out of the group: a clip is
+normalised by one range, the minimum and maximum of the dB spectrogram over all of its segments, found on the device in a pass in
+front of its first group and read there by every group's encode (`model.clip_norm`, `model.inference(..., norm=)`).  The written
+file then no longer depends on `--batchSize` beyond what the generator itself does with its batch, and a stretch of digital
+silence one group long -- a lead-in, a gap, the side signal of a dual-mono file -- is written as silence where the group's own
+range, max == min, writes NaN.  A channel is still a clip of its own, and a last, smaller group still runs at its own size.
 
 The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
 decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
@@ -76,7 +84,7 @@ from .cli import _parser, _run, main, opt_from_file, parse_opt_file             
 from .ops import (PCM_FORMATS, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
-from .plans import (OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
+from .plans import (NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,

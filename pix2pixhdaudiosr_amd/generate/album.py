@@ -78,6 +78,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
         rec['loudness'] = rec['album'] = None
         if getattr(sr, 'crossover_auto', False):                            # (without the option: no key more than before)
             rec['crossover'] = None
+        if getattr(sr, 'norm_scope', 'group') == 'clip':
+            rec['norm'] = None
         entry = {'rec': rec, 'k': k, 'path_out': path_out, 'clip': None}
         entries.append(entry)
         try:
@@ -96,6 +98,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
             rec['metrics_ext'] = ext
         if getattr(sr, 'crossover_auto', False):
             rec['crossover'] = dict(sr.last_crossover)
+        if getattr(sr, 'norm_scope', 'group') == 'clip':
+            rec['norm'] = sr.last_norm                                      # this file's ranges, [C, 2] on the device
         # the track's own figures, and its blocks into the folder's two buffers: six launches of the family "loudness"
         weights = loudness_channel_weights(clip.shape[0])
         track = entry['track'] = torch.empty((80,), dtype=torch.uint8, device=clip.device)

@@ -273,6 +273,11 @@ def _parser():
                     help="how a two-channel file is generated: lr -- left and right each a clip of its own, so the band above the low "
                          "rate's Nyquist frequency is invented twice; ms -- mid and side: what the channels share is invented once, only "
                          "their difference on its own (one channel runs as with lr; more than two are refused) (default: lr)")
+    ap.add_argument("--norm_scope", default="group", choices=("group", "clip"),
+                    help="what the dB spectrogram is normalised by: group -- the minimum and maximum of each group of --batchSize "
+                         "segments, the reference's chain: the output depends on the batch size, and a group of digital silence is "
+                         "written as NaN; clip -- one range per channel of a file, found on the device in a pass in front of its first "
+                         "group: the same file at every batch size, silence stays silence; one start-up line more (default: group)")
     ap.add_argument("--stereo_report", action="store_true",
                     help="report how the left and right channel of a file written with two channels correlate below and above the low "
                          "rate's Nyquist frequency -- for the input the generator was given, the generated clip and, for a full-band "
@@ -351,7 +356,8 @@ def main(argv=None):
     sr = SuperResolver(model, opt, overlap=a.overlap, graph=not a.no_graph,
                        reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
                        lowband=a.lowband, lowband_fade=a.lowband_fade, crossover=a.crossover, crossover_hz=a.crossover_hz,
-                       crossover_taps=a.crossover_taps, **({} if a.stereo == 'lr' else {'stereo': a.stereo}))
+                       crossover_taps=a.crossover_taps, **({} if a.stereo == 'lr' else {'stereo': a.stereo}),
+                       **({} if a.norm_scope == 'group' else {'norm_scope': a.norm_scope}))
     print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
@@ -361,6 +367,8 @@ def main(argv=None):
         print('crossover: the input below %g Hz (%d taps)' % (sr.crossover_plan[1] * opt.hr_sampling_rate, sr.crossover_plan[0]))
     if sr.stereo == 'ms':                                                   # (without the option: no line more than before)
         print('stereo: mid / side')
+    if sr.norm_scope == 'clip':                                             # (without the option: no line more than before)
+        print('normalisation: one range per clip')
     if rc is not None:                                                      # (without the option: no line more than before)
         print(output_rate_line(rc))
     rate = int(opt.hr_sampling_rate) if rc is None else rc['rate']

@@ -22,6 +22,9 @@ BANDWIDTH_DEFAULTS = {'n_fft': 2048, 'hop': 1024, 'band_bins': 8, 'threshold_db'
 # how far the generated clip's correlation above the split may fall under the one below it before the report remarks on it (a
 # reporting threshold like the bandwidth notes' 0.9 / 1.05, not a measurement)
 STEREO_MODES = ('lr', 'ms')
+# what the dB spectrogram is normalised by (csrc/spectro.hip): 'group' -- the minimum and maximum of each group of batchSize
+# segments, the reference's chain; 'clip' -- one range per clip, over all of its segments
+NORM_SCOPES = ('group', 'clip')
 STEREO_DEFAULTS = {'n_fft': 2048, 'hop': 1024}
 STEREO_NOTE_DROP = 0.3
 # the spectrogram picture (csrc/specimg.hip): STFT length and hop in samples, pixels of one panel, dB below the top that
@@ -317,6 +320,13 @@ def check_stereo(stereo='lr', who="SuperResolver"):
     if stereo not in STEREO_MODES:
         raise ValueError("%s: stereo must be 'lr' or 'ms', got %r" % (who, stereo))
     return stereo
+
+
+def check_norm_scope(norm_scope='group', who="SuperResolver"):
+    """Validates the normalisation scope -> the scope, one of NORM_SCOPES."""
+    if norm_scope not in NORM_SCOPES:
+        raise ValueError("%s: norm_scope must be 'group' or 'clip', got %r" % (who, norm_scope))
+    return norm_scope
 
 
 def check_stereo_report(stereo_report=False, opts=None, loudness_scope='file', who="enhance_file"):

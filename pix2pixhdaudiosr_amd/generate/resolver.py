@@ -7,7 +7,7 @@ import torch
 
 from .ops import (bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -82,16 +82,28 @@ class SuperResolver:
     pipeline -- mask-noise row block 0 is the mid signal's, block 1 the side's; the crossover's low band is the encoded input -- and
     is decoded as (M + S, M - S), a non-finite side sample read as 0: what the channels share is invented once.  The auto
     crossover's measurement stays on left / right.  Two launches of the family "stereo" per two-channel clip; one channel runs as
-    with 'lr', more than two are a ValueError."""
+    with 'lr', more than two are a ValueError.
+    `norm_scope`: 'group' (the default) | 'clip', fixed for the object's life: what the dB spectrogram is normalised by.  With
+    'group' it is the minimum and maximum of each group of `batch` segments, the reference's chain: the written file depends on
+    the batch size and on which segments share a group, and a group of digital silence (max == min) comes out as NaN.  With 'clip'
+    a clip -- one channel of a file; with stereo='ms' the mid or the side signal -- has one range, over all of its segments: a pass
+    in front of the clip's first group (model.clip_norm: the transform of every segment once more, one read of each spectrum,
+    nothing kept, nothing brought to the host) leaves it in 8 floats on the device and every group's encode reads it there
+    (model.inference(..., norm=)); the captured chain reads it from a static buffer filled in front of every replay, so one
+    capture serves every clip.  A range of zero scales by 0: a clip of digital silence is written as silence.  The launches are
+    those of the family "normscope": ceil(S / batch) range calls and one noise fold per clip, one encode per group.
+    `last_norm` then holds the [C, 2] tensor on the GPU of the latest call's (min, max) per clip, in dB."""
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
-                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr'):
+                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr', norm_scope='group'):
         from ..models.mdct import IMDCT2, IMDCT4
         from ..util import util as U
         self.model, self.opt = model, opt
         self.T = int(opt.segment_length)
         self.overlap = float(overlap)
         segment_plan(0, self.T, self.overlap)                               # validates both
+        self.norm_scope = check_norm_scope(norm_scope)
+        self.last_norm = None                                               # 'clip': [C, 2] on the GPU, the latest call's ranges
         self.batch = int(batch if batch is not None else getattr(opt, 'batchSize', 1))
         if self.batch < 1:
             raise ValueError("SuperResolver: batch must be >= 1, got %d" % self.batch)
@@ -151,10 +163,14 @@ class SuperResolver:
             return getattr(o, 'phase_encoding_mode', None) in (None, 'scale') and self.up_ratio <= 1     # (util.imdct's random sign)
         return True
 
-    def _group(self, seg, noise):
-        """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44)."""
+    def _group(self, seg, noise, norm=None):
+        """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44).
+        `norm`: None (norm_scope 'group': the model is called as ever), or the clip's norm8."""
         from ..util import util as U
-        sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
+        if norm is None:
+            sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
+        else:
+            sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise, norm=norm)
         splice = {} if self.lowband == 'model' else dict(lr_spectro=lr_spectro, lowband_fade=self.lowband_fade)
         audio = U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=self._imdct,
                         up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)), **splice)
@@ -164,22 +180,26 @@ class SuperResolver:
                              "a multiple of hop_length" % (self.T, audio.shape[1]))
         return audio
 
-    def _run_graphed(self, seg, noise):
+    def _run_graphed(self, seg, noise, norm=None):
         """The chain of a full group through a graph over static buffers.  The first use runs the chain once eagerly on the
         buffers (packed weights, tables and workspaces exist before capture), then captures it; every use replays.  Weights
-        that changed since (load_network, an optimiser step) make the capture stale: it is redone."""
+        that changed since (load_network, an optimiser step) make the capture stale: it is redone.  `norm` (norm_scope 'clip'):
+        the clip's norm8, copied into a static buffer the captured encode and decode read."""
         from .. import _ops
         g = self._g
         if g is None or g['epoch'] != _ops._WEIGHT_EPOCH[0]:
             shape = self.noise_shape(self.batch)
             g = self._g = {'epoch': _ops._WEIGHT_EPOCH[0], 'graph': None, 'out': None,
                            'seg': torch.empty((self.batch, self.T), dtype=torch.float32, device=self.device),
-                           'noise': None if shape is None else torch.empty(shape, dtype=torch.float32, device=self.device)}
+                           'noise': None if shape is None else torch.empty(shape, dtype=torch.float32, device=self.device),
+                           'norm': None if norm is None else torch.empty((8,), dtype=torch.float32, device=self.device)}
         g['seg'].copy_(seg)
+        if g['norm'] is not None:
+            g['norm'].copy_(norm)
         if g['noise'] is not None:
             g['noise'].copy_(noise)
         if g['graph'] is None:
-            self._group(g['seg'], g['noise'])
+            self._group(g['seg'], g['noise'], g['norm'])
             torch.cuda.synchronize()
             # as _train_step_graphed captures: a side stream behind the current (step) stream, thread-local capture mode,
             # no flush of the caching allocator
@@ -188,7 +208,7 @@ class SuperResolver:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.stream(side):
                 graph.capture_begin(capture_error_mode="thread_local")
-                g['out'] = self._group(g['seg'], g['noise'])
+                g['out'] = self._group(g['seg'], g['noise'], g['norm'])
                 graph.capture_end()
             torch.cuda.current_stream().wait_stream(side)
             g['graph'] = graph
@@ -200,7 +220,12 @@ class SuperResolver:
         """lr_audio: [C, L] or [L] on the GPU, already at the high rate -> the generated clip [C, L] ([1, L] for [L]).  Every
         channel is a clip of its own: its S segments are grouped as if it were a mono clip, so
         enhance_lr(x)[c] == enhance_lr(x[c:c+1])[0] given the same noise rows.  `noise`: the mask noise of all C * S segments,
-        [C * S, channels, mask_rows, frames], channel-major, sliced per group; drawn per group (one torch.randn) when absent."""
+        [C * S, channels, mask_rows, frames], channel-major, sliced per group; drawn per group (one torch.randn) when absent.
+        With norm_scope 'clip' the property holds as well, and a channel's range is taken in front of its first group: its S
+        segments go through model.clip_norm, the channel's rows of `noise` are folded as they are, and without `noise` the mask
+        noise of the channel is drawn in one torch.randn of [S, channels, mask_rows, frames] -- the range of the noise must be
+        known before the first group is encoded --, which holds S / batch times the memory of a group's draw for the length of the
+        channel: 4 * channels * mask_rows * frames bytes per segment, the (1 - 1 / up_ratio) part of a segment's encoded spectrogram."""
         run = getattr(self.model, '_on_step_stream', None)
         with torch.no_grad():
             return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
@@ -229,21 +254,41 @@ class SuperResolver:
             x = stereo_matrix(x, 0.5)
         seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
+        by_clip = getattr(self, 'norm_scope', 'group') == 'clip'             # (an object built without __init__ runs as ever)
+        if by_clip:
+            self.last_norm = torch.empty((C, 2), dtype=torch.float32, device=self.device)
+            if S == 0:                                                      # (no segment, no range: the empty fold)
+                self.last_norm[:, 0] = float('inf')
+                self.last_norm[:, 1] = float('-inf')
         for c in range(C):
+            norm = drawn = None
+            if by_clip and S > 0:
+                # the channel's range, in front of its first group; the noise every group of it will be given is folded with it
+                shape = self.noise_shape(S)
+                if shape is not None:
+                    drawn = noise[c * S:(c + 1) * S] if noise is not None else torch.randn(shape, device=self.device)
+                    if tuple(drawn.shape) != shape:
+                        raise ValueError("enhance_lr: noise for channel %d has shape %s, expected %s" % (c, tuple(drawn.shape), shape))
+                norm = self.model.clip_norm(seg[c * S:(c + 1) * S], noise=drawn, rows=self.batch)
+                self.last_norm[c].copy_(norm[:2])
             for s0 in range(0, S, self.batch):
                 b = min(self.batch, S - s0)
                 r0 = c * S + s0
                 shape = self.noise_shape(b)
                 nz = None
                 if shape is not None:
-                    nz = noise[r0:r0 + b] if noise is not None else torch.randn(shape, device=self.device)
+                    if drawn is not None:
+                        nz = drawn[s0:s0 + b]
+                    else:
+                        nz = noise[r0:r0 + b] if noise is not None else torch.randn(shape, device=self.device)
                     if tuple(nz.shape) != shape:
                         raise ValueError("enhance_lr: noise for segments %d..%d of channel %d has shape %s, expected %s"
                                          % (s0, s0 + b - 1, c, tuple(nz.shape), shape))
+                extra = () if norm is None else (norm,)
                 if self.graph and b == self.batch and self._graph_ok():
-                    out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz))
+                    out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz, *extra))
                 else:
-                    out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz))
+                    out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz, *extra))
         sr = segments_stitch_planar(out, C, stride, self.gain, L)
         if self.crossover_plan is not None:
             if measured is not None:
@@ -612,6 +657,7 @@ class SuperResolver:
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         sr = self.enhance_lr(lr)
+        norm = getattr(self, 'last_norm', None)                             # norm_scope 'clip': this file's ranges, on the device
         # the generated clip behind the crossover and in front of the loudness gain: the figure is relative, a gain does not move it
         band = None if bw is None else self._measure_bandwidth(bw, lr, sr, raw if has_hr else None)
         # likewise behind the crossover and the mid/side decode; a file written with another channel count has no stereo image
@@ -651,6 +697,8 @@ class SuperResolver:
                 extra['rate'] = rc['rate']
             output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
         res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
+        if getattr(self, 'norm_scope', 'group') == 'clip':                  # (without the option: no key more than before)
+            res['norm'] = norm
         if picture is not None:
             res['spectrogram'] = self._save_picture(spec, picture)
         if measure is not None:
@@ -909,6 +957,8 @@ class SuperResolver:
                 rec['stereo'] = None
             if rc is not None:
                 rec['output_rate'] = None
+            if getattr(self, 'norm_scope', 'group') == 'clip':
+                rec['norm'] = None
             try:
                 read = self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
@@ -941,6 +991,8 @@ class SuperResolver:
                     rec['stereo'] = res['stereo']
                 if rc is not None:
                     rec['output_rate'] = res['output_rate']
+                if 'norm' in res:
+                    rec['norm'] = res['norm']
             records.append(rec)
             if report is not None:
                 report(rec)

@@ -192,12 +192,16 @@ class Pix2PixHDModel(BaseModel):
     # ------------------------------------------------------------------------------------------
     # spectrogram codec (HIP: csrc/spectro.hip)
     # ------------------------------------------------------------------------------------------
-    def to_spectro(self, audio, mask=False, noise=None, phase_noise=None, noise_sign=None, _spec=None, _frames=None):
+    def to_spectro(self, audio, mask=False, noise=None, phase_noise=None, noise_sign=None, _spec=None, _frames=None, norm=None):
         """audio [B,T] -> (log_spectro [B,C,bins,frames] in [0,1], pha [B,1,bins,frames], norm dict); C = 2 with
         explicit_encoding, else 1 (pix2pixHD_model.py:142-227).  The random tensors the reference draws inside can be
         handed in (parity tests): ``noise`` [B,C,mask_rows,frames] (torch.randn of :202), ``noise_sign`` (+-1, the randint of
         :215 for mask_mode 'mode1'), ``phase_noise`` [B,1,bins,frames] (the rand / randn of :180-188).  With --use_time_D
-        the norm dict's 'frames' holds the windowed MDCT2 frames [B, frames, win] (:143-145, :227)."""
+        the norm dict's 'frames' holds the windowed MDCT2 frames [B, frames, win] (:143-145, :227).
+        ``norm`` (default None: the batch's own statistics, as above): a float32 tensor of 8 on the GPU, (min, max, -, -,
+        noise_min, noise_max, -, -) as `clip_norm` leaves it.  The encode then normalises by that range instead of the batch
+        tensor's (p2phd_spectro_encode_given; a range of zero scales by 0) and the norm dict's 'min', 'max' and '_minmax' are views
+        of it -- 'mean' and 'std' too, which this path does not compute."""
         if _spec is not None:
             spec, frames = _spec, _frames
         elif getattr(self, 'use_time_D', False):
@@ -213,8 +217,11 @@ class Pix2PixHDModel(BaseModel):
             phase_noise = (torch.rand if pem == 'uni_dist' else torch.randn)((B, 1, M, Fr), device=spec.device)
         log_spectro = torch.empty((B, C, M, Fr), dtype=torch.float32, device=spec.device)
         pha = torch.empty((B, 1, M, Fr), dtype=torch.float32, device=spec.device)
-        norm8 = torch.zeros(8, dtype=torch.float32, device=spec.device)
-        partials = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+        if norm is None:
+            norm8 = torch.zeros(8, dtype=torch.float32, device=spec.device)
+            partials = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+        else:
+            norm8 = self._check_norm8(norm, "to_spectro")
         mask_rows = 0
         mode = _opt(self.opt, 'mask_mode', None)
         if mask:
@@ -235,10 +242,16 @@ class Pix2PixHDModel(BaseModel):
                 noise = noise_sign = None
         else:
             noise = noise_sign = None
-        _lib.check(L.p2phd_spectro_encode_ex(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
-                                             mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
-                                             _lib.ptr(noise_sign), _lib.ptr(log_spectro), _lib.ptr(pha), _lib.ptr(norm8),
-                                             _lib.ptr(partials), _lib.stream_ptr()), "spectro_encode")
+        if norm is None:
+            _lib.check(L.p2phd_spectro_encode_ex(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
+                                                 mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
+                                                 _lib.ptr(noise_sign), _lib.ptr(log_spectro), _lib.ptr(pha), _lib.ptr(norm8),
+                                                 _lib.ptr(partials), _lib.stream_ptr()), "spectro_encode")
+        else:
+            _lib.check(L.p2phd_spectro_encode_given(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
+                                                    mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
+                                                    _lib.ptr(noise_sign), _lib.ptr(norm8), _lib.ptr(log_spectro), _lib.ptr(pha),
+                                                    _lib.stream_ptr()), "spectro_encode_given")
         if pem is not None:                                                 # :178-191 (single-channel encoding only)
             if pem == 'scale':
                 pha = pha * 0.5
@@ -251,6 +264,53 @@ class Pix2PixHDModel(BaseModel):
                 pha = pha * pn
         norm = {'min': norm8[0], 'max': norm8[1], 'mean': norm8[2], 'std': norm8[3], 'frames': frames, '_minmax': norm8[:2]}
         return log_spectro, pha, norm
+
+    def _check_norm8(self, norm, who):
+        if not isinstance(norm, torch.Tensor) or not norm.is_cuda or norm.dtype != torch.float32 or tuple(norm.shape) != (8,) \
+                or not norm.is_contiguous():
+            raise ValueError("%s: norm must be a contiguous float32 tensor of 8 on the GPU (clip_norm's), got %r"
+                             % (who, tuple(norm.shape) if isinstance(norm, torch.Tensor) else norm))
+        return norm
+
+    def clip_norm(self, segments, noise=None, rows=None):
+        """The pre-pass of one normalisation range for many batches (whole-file generation, norm_scope='clip'): `segments`
+        [S, T] on the GPU, the rows that will go through `inference(..., norm=)` -> norm8, a float32 tensor of 8 on the GPU:
+        [0], [1] the minimum and maximum of the dB spectrogram over all S rows, [4], [5] those of `noise` (the mask noise of all
+        S rows, [S, C, mask_rows, frames]; (+inf, -inf) without), the rest 0 -- the layout to_spectro's own statistics have.
+        The transform runs over chunks of `rows` rows (default opt.batchSize), each chunk folded into the two floats on the
+        device (p2phd_spectro_range) and its spectrum dropped; the noise goes through p2phd_range_fold.  Nothing comes back to
+        the host and nothing is waited for; the transform runs a second time where the rows are encoded.  Where the rows will be
+        encoded with mask noise, `noise` is the tensor the batches will be given; None leaves the noise range empty."""
+        x = segments.to(self.device).float()
+        if x.dim() != 2:
+            raise ValueError("clip_norm: expected [S, T] segments, got shape %s" % (tuple(segments.shape),))
+        x = x.contiguous()
+        S, T = x.shape
+        rows = int(rows if rows is not None else _opt(self.opt, 'batchSize', 1))
+        if rows < 1:
+            raise ValueError("clip_norm: rows must be >= 1, got %d" % rows)
+        L = _lib.lib()
+        C = 2 if _opt(self.opt, 'explicit_encoding', False) else 1
+        norm8 = torch.tensor([float('inf'), float('-inf'), 0.0, 0.0, float('inf'), float('-inf'), 0.0, 0.0], dtype=torch.float32).to(self.device)
+        partials = None
+        with torch.no_grad():
+            for r0 in range(0, S, rows):
+                spec = self._mdct(x[r0:r0 + rows]).contiguous()             # [b, frames, bins] f32
+                B, Fr, M = spec.shape
+                if partials is None:                                        # (the first chunk is the largest)
+                    partials = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+                _lib.check(L.p2phd_spectro_range(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
+                                                 _lib.ptr(norm8), _lib.ptr(partials), _lib.stream_ptr()), "spectro_range")
+            shape = self.mask_noise_shape(S, T)
+            if noise is not None and shape is not None:
+                if tuple(noise.shape) != shape:
+                    raise ValueError("clip_norm: noise has shape %s, expected %s" % (tuple(noise.shape), shape))
+                nz = noise.to(self.device).float().contiguous()
+                if partials is None:
+                    partials = torch.empty(4 * 1024, dtype=torch.float32, device=self.device)
+                _lib.check(L.p2phd_range_fold(_lib.ptr(nz), nz.numel(), _lib.ptr(norm8[4:]), _lib.ptr(partials), _lib.stream_ptr()),
+                           "range_fold")
+        return norm8
 
     def _mask_rows(self, bins):
         return int(bins * (1 - 1 / self.up_ratio))                          # pix2pixHD_model.py:199
@@ -502,8 +562,13 @@ class Pix2PixHDModel(BaseModel):
         self._loss_G = self._loss_D = None
         return [losses, None if not infer else sr_result]
 
-    def inference(self, lr_audio, inst, noise=None):
-        lr_spectro, lr_pha, _, _, _, _, _, lr_norm_param = self.encode_input(lr_audio, inst, None, noise=noise)
+    def inference(self, lr_audio, inst, noise=None, norm=None):
+        """`norm` (default None: the batch's own statistics): clip_norm's norm8, the range the batch is normalised by."""
+        if norm is None:
+            lr_spectro, lr_pha, _, _, _, _, _, lr_norm_param = self.encode_input(lr_audio, inst, None, noise=noise)
+        else:
+            with torch.no_grad():
+                lr_spectro, lr_pha, lr_norm_param = self.to_spectro(lr_audio, mask=bool(_opt(self.opt, 'mask', False)), noise=noise, norm=norm)
         with torch.no_grad():
             sr_spectro = self.netG.forward(lr_spectro)
         return sr_spectro, lr_pha, lr_norm_param, lr_spectro

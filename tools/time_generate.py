@@ -65,6 +65,13 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             transforms), at the clip's frame count and at an hour's, and p2phd_stereo_matrix on the clip; with --off_only only the
             run without any option is timed (one process of an alternating comparison with another checkout); log in --stereo_log
 
+  normscope (only when asked for) enhance_file on a mono clip of that length, file to file: SuperResolver as ever (norm_scope 'group')
+            against SuperResolver(norm_scope='clip'), in one process, the runs interleaved (nine repeats unless --reps says
+            otherwise): milliseconds per file, median and spread; then p2phd_spectro_range, p2phd_range_fold and
+            p2phd_spectro_encode_given alone, by events, on one group's spectrum and noise, beside p2phd_spectro_encode_ex on the same
+            tensors; with --off_only only the run without the option is timed (one process of an alternating comparison with another
+            checkout); log in --normscope_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -81,6 +88,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py bandwidth [--off_only] [--bandwidth_log profiles/time_generate_bandwidth.log]
         python tools/time_generate.py stereo [--off_only] [--stereo_log profiles/time_generate_stereo.log]
         python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
+        python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
 """
 import argparse
 import os
@@ -835,6 +843,102 @@ def _rateconv_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_normscope(seconds, reps, log, off_only=False):
+    """enhance_file on a mono clip, file to file: norm_scope 'group' (an object built without the option) and 'clip', interleaved;
+    then p2phd_spectro_range, p2phd_range_fold and p2phd_spectro_encode_given alone, by events, on one group's spectrum beside
+    p2phd_spectro_encode_ex on the same tensor."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py normscope: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, x.cpu(), rate)
+        runs = [("no option            ", SuperResolver(model, opt, overlap=0.25))]
+        if not off_only:
+            runs = [("norm_scope group     ", runs[0][1]), ("norm_scope clip      ", SuperResolver(model, opt, overlap=0.25, norm_scope='clip'))]
+        for _, sr in runs:                                          # warm-up: capture, pinned buffers, page cache
+            sr.enhance_file(src, out)
+            sr.enhance_file(src, out)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, sr) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        if not off_only:
+            base = _median(ts[0])
+            sr = runs[1][1]
+            S = -(-x.shape[-1] // int(sr.T * (1 - sr.overlap)))
+            lines.append("the option costs %+.3f ms per file (difference of the medians), %+.2f %% of the file without it: about %d segments through "
+                         "the transform once more in chunks of %d, one read of each spectrum, one noise fold and one draw of the clip's noise"
+                         % (_median(ts[1]) - base, 100.0 * (_median(ts[1]) - base) / base, S, sr.batch))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _normscope_kernels(torch, model, opt, x, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _normscope_kernels(torch, model, opt, x, reps):
+    """The three entries alone, by events, on the spectrum of one group of the clip (and its mask noise) and on 64 such groups in
+    one tensor, beside the encode they extend."""
+    from pix2pixhdaudiosr_amd import _lib
+    L = _lib.lib()
+    T, b = int(opt.segment_length), int(opt.batchSize)
+    seg = x[0, :b * T].reshape(b, T).contiguous()
+    with torch.no_grad():
+        one = model._mdct(seg).contiguous()
+    al, mv, st = float(opt.alpha), float(opt.min_value), _lib.stream_ptr()
+    lines = []
+    for what, k in (("one group", 1), ("64 groups", 64)):
+        spec = one.repeat(k, 1, 1).contiguous()
+        B, Fr, M = spec.shape
+        shape = model.mask_noise_shape(b, T)
+        noise = torch.randn((B,) + tuple(shape[1:]), device=spec.device)
+        R = shape[2]
+        part = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+        log, pha = torch.empty((B, 2, M, Fr), device=spec.device), torch.empty((B, 1, M, Fr), device=spec.device)
+        norm8 = torch.zeros(8, device=spec.device)
+        acc = torch.tensor([float('inf'), float('-inf')] * 4).to(spec.device)
+        calls = [("p2phd_spectro_encode_ex", lambda: L.p2phd_spectro_encode_ex(_lib.ptr(spec), B, Fr, M, 2, al, mv, R, 2, _lib.ptr(noise), None,
+                                                                               _lib.ptr(log), _lib.ptr(pha), _lib.ptr(norm8), _lib.ptr(part), st)),
+                 ("p2phd_spectro_range", lambda: L.p2phd_spectro_range(_lib.ptr(spec), B, Fr, M, 2, al, mv, _lib.ptr(acc), _lib.ptr(part), st)),
+                 ("p2phd_range_fold", lambda: L.p2phd_range_fold(_lib.ptr(noise), noise.numel(), _lib.ptr(acc[4:]), _lib.ptr(part), st)),
+                 ("p2phd_spectro_encode_given", lambda: L.p2phd_spectro_encode_given(_lib.ptr(spec), B, Fr, M, 2, al, mv, R, 2, _lib.ptr(noise), None,
+                                                                                     _lib.ptr(norm8), _lib.ptr(log), _lib.ptr(pha), st))]
+        lines.append("kernels alone on %s (events, median of %d): spectrum [%d, %d, %d] f32 = %.2f MB, noise %.2f MB, encoded %.2f MB"
+                     % (what, reps, B, Fr, M, spec.numel() * 4e-6, noise.numel() * 4e-6, (log.numel() + pha.numel()) * 4e-6))
+        # what each has to move at the least: the encode reads the spectrum and the noise twice and writes, reads and rewrites the planes
+        moved = {"p2phd_spectro_encode_ex": spec.numel() + 3 * log.numel() + pha.numel() + 2 * noise.numel(), "p2phd_spectro_range": spec.numel(),
+                 "p2phd_range_fold": noise.numel(), "p2phd_spectro_encode_given": spec.numel() + log.numel() + pha.numel() + noise.numel()}
+        for name, fn in calls:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            us = []
+            for _ in range(reps + 2):
+                ev[0].record()
+                _lib.check(fn(), name)
+                ev[1].record()
+                torch.cuda.synchronize()
+                us.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            m = _median(us[2:])
+            lines.append("%-28s %8.1f us (spread %.1f) = %.0f GB/s of the %.2f MB it has to move   runs: %s"
+                         % (name, m, max(us[2:]) - min(us[2:]), moved[name] * 4e-3 / m, moved[name] * 4e-6, " ".join("%.1f" % v for v in us[2:])))
+        del spec, noise, log, pha, part
+    return "\n".join(lines) + "\n"
+
+
 def run_limiter(seconds, reps, log):
     """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
     guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
@@ -1015,7 +1119,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1030,9 +1134,10 @@ def main():
     ap.add_argument("--bandwidth_log", default=os.path.join(ROOT, "profiles", "time_generate_bandwidth.log"))
     ap.add_argument("--stereo_log", default=os.path.join(ROOT, "profiles", "time_generate_stereo.log"))
     ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
-    ap.add_argument("--off_only", action="store_true", help="bandwidth, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
+    ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
+    ap.add_argument("--off_only", action="store_true", help="bandwidth, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, rateconv and stereo mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, normscope, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "album":
@@ -1043,6 +1148,9 @@ def main():
     if a.mode == "rateconv":
         log = a.rateconv_log if not a.off_only or "--rateconv_log" in sys.argv else None
         return run_rateconv(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "normscope":
+        log = a.normscope_log if not a.off_only or "--normscope_log" in sys.argv else None
+        return run_normscope(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "bandwidth":
         log = a.bandwidth_log if not a.off_only or "--bandwidth_log" in sys.argv else None
         return run_bandwidth(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
