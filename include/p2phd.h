@@ -96,7 +96,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * csrc/limiter.hip), "bandwidth" (the long-term average spectrum and the band-edge decision of its bandwidth report,
  * csrc/bandwidth.hip), "stereo" (the cross-spectrum and the band sums of its stereo image report and the mid/side matrix of
  * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip), "normscope" (the range
- * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything).
+ * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything),
+ * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -610,6 +611,44 @@ int64_t p2phd_rateconv_out_len(int64_t frames, int in_rate, int out_rate);
 int p2phd_rateconv_fwd(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int o, int n, int taps_per_phase,
                        float* out, int64_t out_frames, int64_t out_ld, void* stream);
 int64_t p2phd_rateconv_tile_len(int o, int n, int taps_per_phase);
+
+/* ------------------------------------------------------------------------------------------
+ * Noise-shaped dither of whole-file generation's output stage (--dither shaped), csrc/shaper.hip: an error-feedback quantiser in
+ * front of the 16-bit rounding, PCM16 only.  Launch family "shaper" (a p2phd_pcm_encode_shaped with frames > 0 counts 1).  The
+ * noise transfer function is 1 - sum_k h[k] z^-k: the quantisation noise leaves the band the ear hears best and gathers near the
+ * Nyquist frequency.  p2phd_pcm_encode_ex and its TPDF dither are unchanged.
+ *
+ * The recursion runs along time and rounds, so it is parallel by definition and not by approximation: a chunk length L = `chunk` (a
+ * multiple of 64 in [256, 2^20]) is part of what is computed.  The error history is zero at the start of every chunk: for channel c
+ * of C = `channels` and sample n of the chunk that starts at j L, e[m] = 0 for m < j L, and
+ *     y = x[c][n] * gain[0]              `gain`: device pointer read by the kernel, as in p2phd_pcm_encode_ex; NULL: y = x
+ *     v = y * 32768                      exact
+ *     u = v;  for k = K, K - 1, .., 1:  u = fmaf(-h[k], e[n - k], u)          one fmaf per tap, in this order: the newest error last
+ *     d = the TPDF dither of p2phd_pcm_encode_ex for (seed, i = first_index + n * channels + c)
+ *     w = u + d;  r = rintf(w)
+ *     stored = r clamped to [-32768, 32767];  w NaN -> 0                      what p2phd_pcm_encode_ex stores for w
+ *     e[n] = r - u  where w is finite, else 0                                 from the UNclamped r: |e| <= 1.5, no wind-up while clipping
+ *   A chunk at least as long as the row is the plain sequential recursion.  Consequences: K = 0, or every h[k] = 0, gives the bytes of
+ *   p2phd_pcm_encode_ex(dither = 1) on the same operands at any chunk length; a payload encoded in pieces has the bytes of one call if
+ *   and only if every piece starts on a chunk boundary, and a first_index that is not a multiple of chunk * channels is refused; a
+ *   sample's bits depend on the operands of its chunk alone, so runs, streams and grids repeat them.
+ * p2phd_pcm_encode_shaped: planar f32 rows in, interleaved little-endian int16 out, laid out and checked as for p2phd_pcm_encode_ex
+ *   (rows may start at any float, the payload at any byte).  `taps`: h[1..K] as K floats on the HOST (0 <= K <= 16; they travel as
+ *   kernel arguments; NULL with K = 0), finite.  frames = 0: nothing is launched or written.  K outside [0, 16], a bad chunk or
+ *   first_index, channels < 1, ld < frames, a null or misaligned pointer: P2PHD_EINVAL.  No workspace, no atomics, nothing zeroed
+ *   before the launch, no ordering rule between calls.
+ * p2phd_shaper_taps_fill (HOST only, no device, as p2phd_xover_taps_fill): the curve's h[1..K] into out (room for 16 floats) and K
+ *   into *K -- float64 literals rounded once to fp32.  curve_id 0 "lipshitz9": 2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281,
+ *   -0.569, 0.0847; 1 "e5": 2.033, -2.165, 1.959, -1.590, 0.6149; 2 "light3": 1.623, -0.982, 0.109 -- the 9-, 5- and 3-tap curves of
+ *   Lipshitz, Vanderkooy and Wannamaker (1991) for 44.1 kHz as commonly carried; written from memory, their provenance could not be
+ *   checked against a source, their behaviour under the recursion above is measured.
+ * p2phd_shaper_tile_len (host): samples of the time tile a workgroup stages at once (tests place their lengths around it); -1 for
+ *   channels outside [1, 65535] or a bad chunk.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_pcm_encode_shaped(const float* planar, int64_t frames, int channels, int64_t ld, const float* gain, const float* taps, int K,
+                            int64_t chunk, uint64_t seed, int64_t first_index, void* out, void* stream);
+int p2phd_shaper_taps_fill(int curve_id, float* out, int* K);
+int64_t p2phd_shaper_tile_len(int channels, int64_t chunk);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

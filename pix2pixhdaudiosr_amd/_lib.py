@@ -89,6 +89,9 @@ SIGNATURES = {
     "p2phd_rateconv_out_len": (_i64, [_i64, _i32, _i32]),
     "p2phd_rateconv_fwd": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
     "p2phd_rateconv_tile_len": (_i64, [_i32, _i32, _i32]),
+    "p2phd_pcm_encode_shaped": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i64, C.c_uint64, _i64, _vp, _vp]),
+    "p2phd_shaper_taps_fill": (_i32, [_i32, _vp, C.POINTER(_i32)]),
+    "p2phd_shaper_tile_len": (_i64, [_i32, _i64]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

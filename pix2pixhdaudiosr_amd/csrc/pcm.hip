@@ -23,6 +23,7 @@
 // at any file offset): typed loads / stores where the pointer is aligned to the sample size, byte accesses otherwise.
 #include "common.h"
 #include "convplan.h"
+#include "dither.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -69,16 +70,7 @@ __global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const uint8_t* __r
   }
 }
 
-// TPDF dither of the interleaved sample with global index i, in LSB: the difference of the two 16-bit halves of a hash of
-// (seed, i), times 2^-16 -- exact in fp32, in (-1, 1), triangular.  fmix is the 32-bit finaliser of MurmurHash3.
-__device__ __forceinline__ uint32_t fmix(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ float tpdf(uint64_t seed, uint64_t i) {
-  const uint32_t h = fmix((uint32_t)i ^ fmix((uint32_t)(i >> 32) ^ (uint32_t)seed ^ 0x9E3779B9u) ^ (uint32_t)(seed >> 32));
-  return (float)((int)(h & 0xFFFFu) - (int)(h >> 16)) * (1.0f / 65536.0f);
-}
+using p2phd::tpdf;                  // dither.h: the TPDF dither of an interleaved sample, shared with shaper.hip
 
 // y * 2^(bits-1) (exact) [+ d], round half to even, clamp to the integer range; NaN -> 0
 template <int BITS, bool DITHER> __device__ __forceinline__ uint32_t quantise(float y, float d) {

@@ -33,7 +33,9 @@ decoded there, the output is encoded there and comes back as the payload to writ
 The output stage is opt-in and on the device too: `--report_peaks` (peak, clipped and non-finite samples per channel),
 `--clip guard [--ceiling_dbfs X]` (one gain for the whole file so that nothing clips), `--clip error` (refuse to write a
 file that would clip) and `--dither tpdf` (PCM16).  Without them every byte written and every line printed is as before:
-the integer encodings clamp, silently.
+the integer encodings clamp, silently.  `--dither shaped` (csrc/shaper.hip; PCM16 written at 44100 or 48000 Hz) puts the same noise
+in front of an error-feedback quantiser that moves the 16-bit floor out of 2-5 kHz and up above 15 kHz (`--dither_curve`,
+`--dither_chunk`: the recursion starts again every chunk, which is what lets it run in parallel; `shaper_coefficients`).
 
 `--crossover input` (opt-in, csrc/xover.hip) puts a time-domain crossover behind the stitch: a linear-phase complementary
 filter pair, so that below `--crossover_hz` (default: 0.95 of the low rate's Nyquist frequency) the written clip is the input
@@ -82,9 +84,9 @@ front of the loudness, true-peak and limiter stages, which then measure and hold
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
-                  loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, segments_gather, segments_gather_planar, segments_stitch,
+                  loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, shaper_coefficients, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
-from .plans import (NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS,  # noqa: F401
+from .plans import (NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,

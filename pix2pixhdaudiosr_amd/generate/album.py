@@ -162,7 +162,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
             if stage is None:
                 dev = pcm_encode(w, encoding)
             else:
-                dev = pcm_encode(w, encoding, gain=guard_gain if guard else None, dither=stage['dither'], seed=dither_seed + e['k'])
+                dev = pcm_encode(w, encoding, gain=guard_gain if guard else None, dither=stage['dither'], seed=dither_seed + e['k'],
+                                 curve=stage.get('curve'), chunk=stage.get('chunk'))
             payload, _ = sr._fetch(dev, None)
             sr._save(e['path_out'], payload, w.shape[0], encoding)
             e['clip'] = None

@@ -10,7 +10,8 @@ from types import SimpleNamespace
 
 import torch
 
-from .plans import (CLIP_MODES, CROSSOVER_AUTO, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .ops import shaper_coefficients
+from .plans import (CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
@@ -204,9 +205,18 @@ def _parser():
                          "all channels alike, so that its peak sits at --ceiling_dbfs; error: write nothing and stop")
     ap.add_argument("--ceiling_dbfs", type=float, default=None, metavar="DB",
                     help="--clip guard: the level the peak is brought down to, <= 0 (default: the limit of --encoding)")
-    ap.add_argument("--dither", default=None, choices=("tpdf",),
+    ap.add_argument("--dither", default=None, choices=("tpdf", "shaped"),
                     help="pcm16 only: +-1 LSB of triangular noise in front of the rounding, so that the quantisation error of quiet "
-                         "passages is noise and not distortion")
+                         "passages is noise and not distortion; shaped (files written at 44100 or 48000 Hz): the same noise in front "
+                         "of an error-feedback quantiser that moves the 16-bit floor out of 2-5 kHz, where the ear hears best, and "
+                         "up above 15 kHz; one `dither:` line more at the start")
+    ap.add_argument("--dither_curve", default=None, choices=tuple(DITHER_CURVES),
+                    help="--dither shaped: the noise-shaping curve (default lipshitz9, 9 taps; e5 and light3 shape less and add less "
+                         "noise in total)")
+    ap.add_argument("--dither_chunk", type=int, default=None, metavar="N",
+                    help="--dither shaped: samples after which the quantiser's error history starts again at zero, a multiple of 64 in "
+                         "256 .. 1048576 (default 4096); chunks run in parallel, longer ones shape a little deeper, one at least as "
+                         "long as the file is the plain sequential recursion")
     ap.add_argument("--dither_seed", type=int, default=0, help="seed of --dither (file k of a folder uses seed + k)")
     ap.add_argument("--report_peaks", action="store_true",
                     help="print peak (dBFS), clipped and non-finite samples and the gain of every file; three more columns "
@@ -309,7 +319,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:                                                                    # before anything is loaded
         folder_mode = check_paths(a.input, a.output)
-        out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate")
+        out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate", a.dither_curve,
+                                         a.dither_chunk)
+        if a.output_rate is not None:                                       # (the model's rate: once the options file has been read)
+            check_dither(a.dither, a.encoding, "generate", a.output_rate, a.dither_curve, a.dither_chunk)
         picture = _spectrogram_args(a, folder_mode)
         picture.update(_loudness_args(a, None, folder_mode))
         picture.update(_bandwidth_args(a))
@@ -325,6 +338,8 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     stage = dict(clip=a.clip, ceiling_dbfs=a.ceiling_dbfs, dither=a.dither, dither_seed=a.dither_seed, report_peaks=a.report_peaks, **picture)
+    if a.dither == 'shaped':
+        stage.update(dither_curve=a.dither_curve, dither_chunk=a.dither_chunk)
     folder = os.path.abspath(a.load_pretrain)
     over = dict(checkpoints_dir=os.path.dirname(folder), name=os.path.basename(folder), load_pretrain='', continue_train=False)
     for k in ("which_epoch", "batchSize"):
@@ -342,6 +357,7 @@ def main(argv=None):
         rc = check_output_rate(a.output_rate, opt.hr_sampling_rate, "generate", a.loudness_scope, a.spectrogram)
         if rc is not None and a.loudness is not None:
             _loudness_args(a, rc['rate'], folder_mode)
+        check_dither(a.dither, a.encoding, "generate", opt.hr_sampling_rate if rc is None else rc['rate'], a.dither_curve, a.dither_chunk)
         if a.limiter:
             check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate if rc is None else rc['rate'],
                           "generate")
@@ -371,6 +387,8 @@ def main(argv=None):
         print('normalisation: one range per clip')
     if rc is not None:                                                      # (without the option: no line more than before)
         print(output_rate_line(rc))
+    if a.dither == 'shaped':                                                # (without the option: no line more than before)
+        print(dither_line(out_stage, shaper_coefficients(out_stage['curve']).numel()))
     rate = int(opt.hr_sampling_rate) if rc is None else rc['rate']
     try:
         return _run(a, sr, stage, seed, rate, folder_mode)

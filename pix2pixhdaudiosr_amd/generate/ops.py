@@ -1,11 +1,11 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip and csrc/rateconv.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip and csrc/shaper.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither,
+from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither, DITHER_CHUNK, DITHER_CURVES,
                     check_encoding, check_loudness_rate, limiter_plan, RATECONV_DEFAULTS, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
@@ -90,23 +90,50 @@ def pcm_decode(payload, frames, channels, format_tag, bits):
     return out
 
 
-def pcm_encode(waveform, encoding='pcm16', gain=None, dither=None, seed=0, first_index=0):
+def shaper_coefficients(curve):
+    """The taps h[1..K] of a noise-shaping curve (a name of DITHER_CURVES; p2phd_shaper_taps_fill) as a float32 tensor on the host (no
+    GPU needed): the noise transfer function of dither='shaped' is 1 - sum_k h[k] z^-k."""
+    if curve not in DITHER_CURVES:
+        raise ValueError("shaper_coefficients: curve must be one of %s, got %r" % (sorted(DITHER_CURVES), curve))
+    h = torch.zeros((16,), dtype=torch.float32)
+    K = ctypes.c_int32(0)
+    _lib.check(_lib.lib().p2phd_shaper_taps_fill(DITHER_CURVES[curve], ctypes.c_void_p(h.data_ptr()), ctypes.byref(K)), "shaper_taps_fill")
+    return h[:K.value].clone()
+
+
+def pcm_encode(waveform, encoding='pcm16', gain=None, dither=None, seed=0, first_index=0, curve=None, chunk=None):
     """waveform [C, L] f32 on the GPU (rows contiguous) -> uint8 tensor of L * C samples, interleaved: the payload
     wavio.write_payload takes.  'pcm16' gives the bytes wavio.save writes; NaN encodes as 0 in the integer formats.
     `gain`: a float32 tensor of one element on the GPU (pcm_peaks' fourth value) that the kernel reads: every sample is
     multiplied by it first.  `dither`: None or 'tpdf' (pcm16 only): +-1 LSB of triangular noise in front of the rounding,
     a hash of (`seed`, `first_index` + the sample's index in the payload) -- encoding a clip in pieces with the right
-    `first_index` gives the bytes of one call."""
+    `first_index` gives the bytes of one call.  'shaped' (pcm16 only; csrc/shaper.hip, p2phd_pcm_encode_shaped): the same dither in
+    front of an error-feedback quantiser with the taps of `curve` (a name of DITHER_CURVES, or a float32 tensor of at most 16 taps
+    on the host; None: 'lipshitz9'), whose error history starts at zero every `chunk` samples of a channel (None: 4096; a multiple
+    of 64 in [256, 2^20]) -- pieces give the bytes of one call where each starts on a chunk boundary, and a `first_index` that is
+    not a multiple of chunk * C is refused."""
     fmt, nbytes = check_encoding(encoding, "pcm_encode")
     w, C, L, ld = _rows(waveform, "pcm_encode: waveform")
     out = torch.empty((L * C * nbytes,), dtype=torch.uint8, device=w.device)
-    check_dither(dither, encoding, "pcm_encode")
+    taps = curve if isinstance(curve, torch.Tensor) else None
+    check_dither(dither, encoding, "pcm_encode", None, None if taps is not None and dither == 'shaped' else curve, chunk)
     if gain is not None:
         gain = _lib.require_gpu_tensor(gain, "pcm_encode: gain", torch.float32)
         if gain.numel() != 1:
             raise ValueError("pcm_encode: gain must hold one value, got shape %s" % (tuple(gain.shape),))
     if int(first_index) < 0:
         raise ValueError("pcm_encode: first_index must be >= 0, got %r" % (first_index,))
+    if dither == 'shaped':
+        if taps is None:
+            taps = shaper_coefficients('lipshitz9' if curve is None else curve)
+        if taps.is_cuda or taps.dtype != torch.float32 or taps.dim() != 1 or taps.numel() > 16:
+            raise ValueError("pcm_encode: curve must be a name or at most 16 float32 taps on the host, got %s %s on %s"
+                             % (tuple(taps.shape), taps.dtype, taps.device))
+        taps = taps.contiguous()
+        _lib.check(_lib.lib().p2phd_pcm_encode_shaped(_lib.ptr(w), L, C, max(ld, L), _lib.ptr(gain), ctypes.c_void_p(taps.data_ptr() if taps.numel() else None),
+                                                      taps.numel(), DITHER_CHUNK if chunk is None else int(chunk), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                      int(first_index), _lib.ptr(out), _lib.stream_ptr()), "pcm_encode_shaped")
+        return out
     _lib.check(_lib.lib().p2phd_pcm_encode_ex(_lib.ptr(w), L, C, max(ld, L), fmt, _lib.ptr(gain), 1 if dither else 0,
                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_index), _lib.ptr(out), _lib.stream_ptr()),
                "pcm_encode_ex")

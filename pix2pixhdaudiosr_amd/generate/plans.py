@@ -6,7 +6,14 @@ from fractions import Fraction
 
 # encoding of wavio.save / wavio.write_payload -> (P2PHD_PCM_* code of include/p2phd.h, bytes per sample)
 PCM_ENCODINGS = {'pcm16': (1, 2), 'pcm24': (2, 3), 'float32': (4, 4)}
-DITHERS = (None, 'tpdf')
+DITHERS = (None, 'tpdf', 'shaped')
+# the noise-shaped dither (csrc/shaper.hip): curve name -> curve id of p2phd_shaper_taps_fill (the first is the default); samples of a
+# chunk where none is given -- the error history starts at zero in every chunk, which is what makes the recursion parallel, and a
+# multiple of 64 in [DITHER_MIN_CHUNK, DITHER_MAX_CHUNK]; the written rates the curves are for
+DITHER_CURVES = {'lipshitz9': 0, 'e5': 1, 'light3': 2}
+DITHER_CHUNK = 4096
+DITHER_MIN_CHUNK, DITHER_MAX_CHUNK = 256, 1 << 20
+SHAPED_RATES = (44100, 48000)
 CLIP_MODES = ('clamp', 'guard', 'error')
 LOWBANDS = ('model', 'input')
 CROSSOVERS = (None, 'input')
@@ -98,12 +105,30 @@ def check_encoding(encoding, who):
     return PCM_ENCODINGS[encoding]
 
 
-def check_dither(dither, encoding, who):
+def check_dither(dither, encoding, who, rate=None, curve=None, chunk=None):
+    """Validates the dither option.  `curve` (a name of DITHER_CURVES) and `chunk` are options of dither='shaped'; `rate`: None, or
+    the rate the file is written at, which 'shaped' takes only from SHAPED_RATES (the curves are published for 44.1 kHz)."""
     if dither not in DITHERS:
-        raise ValueError("%s: dither must be None or 'tpdf', got %r" % (who, dither))
+        raise ValueError("%s: dither must be None, 'tpdf' or 'shaped', got %r" % (who, dither))
     if dither is not None and encoding != 'pcm16':
         raise ValueError("%s: dither is for pcm16 (a 24-bit or float32 file carries the signal's own low bits), got encoding %r"
                          % (who, encoding))
+    if dither != 'shaped':
+        if curve is not None or chunk is not None:
+            raise ValueError("%s: dither_curve / dither_chunk are options of dither='shaped'; dither is %r" % (who, dither))
+        return
+    if curve is not None and curve not in DITHER_CURVES:
+        raise ValueError("%s: dither_curve must be one of %s, got %r" % (who, sorted(DITHER_CURVES), curve))
+    if chunk is not None and (not _is_int(chunk) or not DITHER_MIN_CHUNK <= chunk <= DITHER_MAX_CHUNK or chunk % 64):
+        raise ValueError("%s: dither_chunk must be a multiple of 64 in [%d, %d], got %r" % (who, DITHER_MIN_CHUNK, DITHER_MAX_CHUNK, chunk))
+    if rate is not None and rate not in SHAPED_RATES:
+        raise ValueError("%s: dither='shaped' is for files written at %s Hz (its curves are published for 44.1 kHz), got %r Hz"
+                         % (who, ' or '.join(str(r) for r in SHAPED_RATES), rate))
+
+
+def dither_line(stage, taps):
+    """The start-up line of dither='shaped'; `taps`: how many the curve has."""
+    return 'dither: shaped (%s, %d taps, chunks of %d)' % (stage['curve'], taps, stage['chunk'])
 
 
 def encoding_limit(encoding):
@@ -121,13 +146,15 @@ def ceiling_from_dbfs(ceiling_dbfs, encoding):
     return level if level < encoding_limit(encoding) else None
 
 
-def check_output_options(encoding, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, who="enhance_file"):
+def check_output_options(encoding, clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, who="enhance_file",
+                         dither_curve=None, dither_chunk=None):
     """Validates the output-stage options; -> None when all of them are at their defaults (the encoder runs without gain
-    and dither and nothing is reported), else a dict {'clip', 'ceiling' (linear, or None), 'dither', 'seed', 'report'}."""
+    and dither and nothing is reported), else a dict {'clip', 'ceiling' (linear, or None), 'dither', 'seed', 'report'}; with
+    dither 'shaped' the dict also carries 'curve' and 'chunk' (`dither_curve`, `dither_chunk`, or the defaults)."""
     check_encoding(encoding, who)
     if clip not in CLIP_MODES:
         raise ValueError("%s: clip must be one of %s, got %r" % (who, CLIP_MODES, clip))
-    check_dither(dither, encoding, who)
+    check_dither(dither, encoding, who, None, dither_curve, dither_chunk)
     if ceiling_dbfs is not None:
         if isinstance(ceiling_dbfs, bool) or not isinstance(ceiling_dbfs, (int, float)) or not -1000.0 <= ceiling_dbfs <= 0.0:
             raise ValueError("%s: ceiling_dbfs must be a level <= 0 dBFS, got %r" % (who, ceiling_dbfs))
@@ -137,8 +164,12 @@ def check_output_options(encoding, clip='clamp', ceiling_dbfs=None, dither=None,
         raise ValueError("%s: dither_seed must be an int, got %r" % (who, dither_seed))
     if clip == 'clamp' and ceiling_dbfs is None and dither is None and dither_seed == 0 and not report_peaks:
         return None
-    return {'clip': clip, 'ceiling': ceiling_from_dbfs(ceiling_dbfs, encoding), 'dither': dither, 'seed': dither_seed,
-            'report': bool(report_peaks)}
+    stage = {'clip': clip, 'ceiling': ceiling_from_dbfs(ceiling_dbfs, encoding), 'dither': dither, 'seed': dither_seed,
+             'report': bool(report_peaks)}
+    if dither == 'shaped':
+        stage.update(curve=next(iter(DITHER_CURVES)) if dither_curve is None else dither_curve,
+                     chunk=DITHER_CHUNK if dither_chunk is None else dither_chunk)
+    return stage
 
 
 def spectro_bins(n_fft, mdct_type):

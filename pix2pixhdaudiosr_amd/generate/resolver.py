@@ -6,8 +6,8 @@ import struct
 import torch
 
 from .ops import (bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
+from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -409,7 +409,8 @@ class SuperResolver:
             (_, gain), true_peak['packed'] = _true_peaks_packed(w, true_peak['rate'], true_peak['ceiling'], "enhance_file")
         if not wanted:
             return None, packed
-        return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed']), packed
+        return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed'],
+                          curve=stage.get('curve'), chunk=stage.get('chunk')), packed
 
     def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
@@ -486,6 +487,8 @@ class SuperResolver:
             output['limiter'] = {'lookahead': limiter['lookahead'], 'hold': limiter['hold'], 'max_reduction_db': _dbfs(float(gmin[0])),
                                  'limited_samples': int(count[0]) & 0xFFFFFFFF,
                                  'input_true_peak_dbtp': _dbfs(float(limiter['packed'][8:12].view(torch.float32)[0]))}
+        if stage['dither'] == 'shaped':
+            output['dither'] = {'kind': 'shaped', 'curve': stage['curve'], 'taps': shaper_coefficients(stage['curve']).numel(), 'chunk': stage['chunk']}
         return output
 
     @staticmethod
@@ -721,7 +724,8 @@ class SuperResolver:
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
-                     bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None):
+                     bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
+                     dither_chunk=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -737,7 +741,14 @@ class SuperResolver:
         channels alike, is scaled down so that its peak sits at `ceiling_dbfs` -- None: the encoding's own limit; a file that
         fits is left alone) or 'error' (ClipError, a ValueError, naming the file, its peak and the clipped count, before anything is
         written).  `dither`: None or 'tpdf' (pcm16 only: +-1 LSB of triangular noise in front of the rounding, fixed by
-        `dither_seed`).  `report_peaks`: measure only.  With any of the five given the result gains 'output': {'peak',
+        `dither_seed`), or 'shaped' (pcm16 written at 44100 or 48000 Hz only; csrc/shaper.hip, one launch of the family "shaper" in
+        place of the encoder's): the same noise in front of an error-feedback quantiser that moves the 16-bit floor out of 2-5 kHz
+        and up above 15 kHz -- `dither_curve`: a name of plans.DITHER_CURVES (None: 'lipshitz9'); `dither_chunk`: samples after
+        which the error history starts again at zero, which is what makes the recursion parallel and part of what is computed
+        (None: 4096; a multiple of 64 in [256, 2^20]; one at least as long as the clip is the plain sequential recursion).  'output'
+        then gains 'dither': {'kind', 'curve', 'taps' (how many), 'chunk'}.  Another written rate, or either option without
+        'shaped', is a ValueError before the file is opened.
+        `report_peaks`: measure only.  With any of the five given the result gains 'output': {'peak',
         'peak_dbfs', 'clipped', 'nonfinite' (a list each, one entry per written channel, measured on the unscaled clip for
         `encoding`), 'gain' (the factor applied: 1.0 unless 'guard' scaled)}.
         `spectrogram` (opt-in): path of a PNG to write after the wav -- spectrogram_image of written channel
@@ -827,8 +838,9 @@ class SuperResolver:
         8000, or a pair with a tiny common divisor) are refused: a ValueError each, before the file is opened."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_file")
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_file")
-        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks)
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, dither_curve=dither_curve, dither_chunk=dither_chunk)
         rc, out_rate = self._output_rate_option(output_rate, "enhance_file", loudness_scope, spectrogram)
+        check_dither(dither, encoding, "enhance_file", out_rate, dither_curve, dither_chunk)
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_file")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
         loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range), rc, "enhance_file")
@@ -869,7 +881,7 @@ class SuperResolver:
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
-                       stereo_report_opts=None, output_rate=None):
+                       stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -877,7 +889,8 @@ class SuperResolver:
         'frames' (of the input), 'written_channels', 'out_frames', 'metrics' (as enhance_file(channels != 'first') returns
         them: a list per channel, or None), 'error' (None, or the text of what went wrong)}; with `extended_metrics` also
         'metrics_ext' (as enhance_file returns it).  `clip`, `ceiling_dbfs`, `dither`, `dither_seed`, `report_peaks`: the output
-        stage of enhance_file, per file (a guard gain is one file's); file k of the plan is dithered with seed `dither_seed` + k;
+        stage of enhance_file, per file (a guard gain is one file's); file k of the plan is dithered with seed `dither_seed` + k
+        (`dither_curve`, `dither_chunk`: enhance_file's, for dither 'shaped', in either loudness scope);
         with any of them given a record gains 'output' (as enhance_file returns it, None for a skipped file).  clip 'error'
         ends the run at the first file that would clip.  `spectrogram`: a folder that takes one picture per enhanced file, at
         <relative path>.png (enhance_file's `spectrogram`, `spectrogram_channel`, `spectrogram_opts`); a record then gains
@@ -916,8 +929,9 @@ class SuperResolver:
         with `spectrogram`: a ValueError."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_folder")
-        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder")
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder", dither_curve, dither_chunk)
         rc, out_rate = self._output_rate_option(output_rate, "enhance_folder", loudness_scope, spectrogram)
+        check_dither(dither, encoding, "enhance_folder", out_rate, dither_curve, dither_chunk)
         stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_folder")
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range), rc, "enhance_folder")

@@ -72,6 +72,13 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             tensors; with --off_only only the run without the option is timed (one process of an alternating comparison with another
             checkout); log in --normscope_log
 
+  dither    (only when asked for) enhance_file on a mono clip of that length, file to file: without any option, with dither='tpdf' and
+            with dither='shaped' (lipshitz9, chunks of 4096), in one process, the runs interleaved (nine repeats unless --reps says
+            otherwise): milliseconds per file, median and spread; then p2phd_pcm_encode_shaped alone, by events, at chunk 4096 and
+            1024 beside p2phd_pcm_encode_ex with TPDF on the same row, at the clip's length and at an hour's, and once with one chunk
+            for the whole clip -- the recursion as one sequential chain, the measured cost of not chunking; with --off_only only the
+            run without any option is timed (one process of an alternating comparison with another checkout); log in --dither_log
+
 Without a mode every one of the first four runs in a process of its own under its own time limit, in that order, and the run stops at
 the first that fails; the lines are also written to --log.
 
@@ -89,6 +96,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py stereo [--off_only] [--stereo_log profiles/time_generate_stereo.log]
         python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
         python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
+        python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
 """
 import argparse
 import os
@@ -843,6 +851,92 @@ def _rateconv_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_dither(seconds, reps, log, off_only=False):
+    """enhance_file on a mono clip, file to file: without any option, with dither='tpdf' and with dither='shaped' (the same object),
+    interleaved; then p2phd_pcm_encode_shaped alone, by events, at chunk 4096, at chunk 1024 and at one chunk for the whole row (the
+    plain sequential recursion), beside p2phd_pcm_encode_ex with TPDF, at the clip's length and at an hour's."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py dither: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, x.cpu(), rate)
+        sr = SuperResolver(model, opt, overlap=0.25)
+        runs = [("no option            ", {})] if off_only else [("dither off           ", {}), ("dither tpdf          ", dict(dither='tpdf')),
+                                                                  ("dither shaped        ", dict(dither='shaped'))]
+        for _, kw in runs:                                          # warm-up: capture, pinned buffers, page cache, code objects
+            sr.enhance_file(src, out, **kw)
+            sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        if not off_only:
+            t, sh = _median(ts[1]), _median(ts[2])
+            lines.append("shaped costs %+.3f ms per file over tpdf (difference of the medians), %+.2f %% of that file: the encoder's launch is "
+                         "replaced by the shaper's" % (sh - t, 100.0 * (sh - t) / t))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _dither_kernels(torch, x, rate, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _dither_kernels(torch, x, rate, reps):
+    """p2phd_pcm_encode_shaped alone, by events (with the allocation of its payload in front), on the clip and on an hour of it, at
+    three chunk lengths, beside p2phd_pcm_encode_ex with TPDF on the same row.  One chunk for the whole row -- the recursion as one
+    sequential chain -- is timed on the clip only, and once: it is the measured cost of not chunking."""
+    from pix2pixhdaudiosr_amd.generate import pcm_encode
+    lines = []
+    x = (0.25 * x / x.abs().max().clamp_min(1e-9)).contiguous()
+    hour = x.repeat(1, -(-3600 * rate // x.shape[-1]))[:, :3600 * rate].contiguous()
+    for name, clip in (("the clip", x), ("an hour", hour)):
+        kinds = [("p2phd_pcm_encode_ex tpdf", dict(dither='tpdf')), ("p2phd_pcm_encode_shaped chunk 4096", dict(dither='shaped', chunk=4096)),
+                 ("p2phd_pcm_encode_shaped chunk 1024", dict(dither='shaped', chunk=1024))]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(kinds) + 1)]
+        ks = [[] for _ in kinds]
+        for _ in range(reps + 2):
+            ev[0].record()
+            for k, (_, kw) in enumerate(kinds):
+                pcm_encode(clip, 'pcm16', seed=1, **kw)
+                ev[k + 1].record()
+            torch.cuda.synchronize()
+            for k in range(len(kinds)):
+                ks[k].append(ev[k].elapsed_time(ev[k + 1]) * 1e3)
+        L = clip.shape[-1]
+        lines.append("kernels alone on %s (events, median of %d; %d samples, lipshitz9): %s"
+                     % (name, reps, L, "; ".join("%s %.1f us (spread %.1f) = %.3f ns per sample%s"
+                                                 % (kn, _median(k[2:]), max(k[2:]) - min(k[2:]), _median(k[2:]) * 1e3 / L,
+                                                    ", %d lanes" % -(-L // kw['chunk']) if 'chunk' in kw else "")
+                                                 for (kn, kw), k in zip(kinds, ks))))
+        lines.append("runs: " + "; ".join("%s %s" % (kn, " ".join("%.1f" % v for v in k[2:])) for (kn, _), k in zip(kinds, ks)))
+    whole = 1 << 20                                                 # one chunk holds the clip: one lane walks it
+    if x.shape[-1] <= whole:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        pcm_encode(x, 'pcm16', dither='shaped', chunk=whole, seed=1)
+        ev[1].record()
+        torch.cuda.synchronize()
+        t = ev[0].elapsed_time(ev[1]) * 1e3
+        lines.append("the recursion as one sequential chain on the clip (chunk %d >= %d samples, one lane, one run): %.1f us = %.1f ns per sample"
+                     % (whole, x.shape[-1], t, t * 1e3 / x.shape[-1]))
+    return "\n".join(lines) + "\n"
+
+
 def run_normscope(seconds, reps, log, off_only=False):
     """enhance_file on a mono clip, file to file: norm_scope 'group' (an object built without the option) and 'clip', interleaved;
     then p2phd_spectro_range, p2phd_range_fold and p2phd_spectro_encode_given alone, by events, on one group's spectrum beside
@@ -1119,7 +1213,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1135,9 +1229,10 @@ def main():
     ap.add_argument("--stereo_log", default=os.path.join(ROOT, "profiles", "time_generate_stereo.log"))
     ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
-    ap.add_argument("--off_only", action="store_true", help="bandwidth, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
+    ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
+    ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, normscope, rateconv and stereo mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "album":
@@ -1148,6 +1243,9 @@ def main():
     if a.mode == "rateconv":
         log = a.rateconv_log if not a.off_only or "--rateconv_log" in sys.argv else None
         return run_rateconv(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "dither":
+        log = a.dither_log if not a.off_only or "--dither_log" in sys.argv else None
+        return run_dither(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "normscope":
         log = a.normscope_log if not a.off_only or "--normscope_log" in sys.argv else None
         return run_normscope(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
