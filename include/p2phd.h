@@ -97,7 +97,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * csrc/bandwidth.hip), "stereo" (the cross-spectrum and the band sums of its stereo image report and the mid/side matrix of
  * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip), "normscope" (the range
  * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything),
- * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip).
+ * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip), "flac" (the two kernels of its FLAC input,
+ * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */
@@ -649,6 +650,80 @@ int p2phd_pcm_encode_shaped(const float* planar, int64_t frames, int channels, i
                             int64_t chunk, uint64_t seed, int64_t first_index, void* out, void* stream);
 int p2phd_shaper_taps_fill(int curve_id, float* out, int* K);
 int64_t p2phd_shaper_tile_len(int channels, int64_t chunk);
+
+/* ------------------------------------------------------------------------------------------
+ * FLAC input, csrc/flac.hip: native FLAC streams (RFC 9639) for the feeder (host decoder) and for whole-file generation (device
+ * decoder).  Launch family "flac" (a p2phd_flac_decode with nframes > 0 counts 2: the frame kernel and the element-wise kernel).
+ *
+ * The subset: the "fLaC" marker, optionally behind an ID3v2 tag (skipped); any metadata blocks (STREAMINFO is read, SEEKTABLE is
+ * counted, the rest are skipped by length); 1 to 8 channels in all four channel assignments (independent, left/side, side/right,
+ * mid/side); 8, 12, 16, 20 and 24 bits per sample; fixed and variable block size with every block-size and sample-rate code and coded
+ * numbers of 1 to 7 bytes; CONSTANT, VERBATIM, FIXED (order 0 to 4) and LPC (order 1 to 32, precision 1 to 15, shift >= 0) subframes;
+ * wasted bits; Rice residuals with 4- and 5-bit parameters, partition orders 0 to 15 and escape partitions (raw width 0 included); a
+ * shorter last frame.  Refused with an error text: 32-bit samples, Ogg FLAC, a negative LPC shift, reserved codes, a sample rate,
+ * channel count or sample size that changes mid-stream.
+ *
+ * A frame table has one row of P2PHD_FLAC_ROW_WORDS int64 per frame: byte offset into the file, byte length, first sample (as the
+ * frame numbers it: frame number x the stream's block size, or the coded sample number), block size, channel assignment (0 .. 7:
+ * that many + 1 independent channels, 8 left/side, 9 side/right, 10 mid/side), bits per sample.  Decoders place frame f of a table at
+ * column first_sample[f] - first_sample[first frame decoded] of every output row.
+ *
+ * HOST only (no device, as p2phd_xover_taps_fill):
+ * p2phd_flac_info: the stream's STREAMINFO and where its first frame starts.  total_samples = 0: not stated (p2phd_flac_index counts).
+ * p2phd_flac_index: one row per frame into `table` (room for `cap` rows; cap = 0: the count alone) -> the number of frames, or -1
+ *   with an error text that names the frame's number and byte offset.  Verifies every header's CRC-8 and every frame's CRC-16, that
+ *   the frames chain without a gap from the first frame to the end of the file, that frame / sample numbers are consecutive, that
+ *   rate, channels and sample size are STREAMINFO's in every frame, and, where STREAMINFO states a total, that the frames hold it.
+ *   A frame ends at the first byte q behind its header where the CRC-16 of the frame's bytes so far closes and either the file ends
+ *   or the header of the following frame (good CRC-8, the expected number) stands: bytes inside a frame that look like a header do
+ *   not split it.  No sample is decoded.
+ * p2phd_flac_decode_host: the reference decoder.  Frames [first_frame, first_frame + frame_count) of `table` -> out[c * ld + column],
+ *   int32, the `channels` rows of the stream (decorrelation undone, wasted bits restored); a row whose assignment is not one of
+ *   `channels` channels is P2PHD_EINVAL, as on the device: nothing is written beyond the rows the caller has.  Prediction sums are 64-bit throughout; every
+ *   read is bounded by the frame's byte range of its table row: a frame whose bit stream runs past its end, or that holds a
+ *   reserved code, is P2PHD_EINVAL with a text that names the frame -- never an overrun.
+ * p2phd_flac_workspace_bytes: bytes of p2phd_flac_decode's workspace for `channels` rows of pitch `ld` (0: bad arguments).
+ * p2phd_flac_tile_len, p2phd_flac_frames_per_workgroup: samples per step of the element-wise kernel's workgroup and frames per
+ *   workgroup of the frame kernel (tests place their sizes around them).
+ *
+ * DEVICE:
+ * p2phd_flac_decode: the file's bytes and `nframes` table rows on the device -> out[c * ld + column] = integer x 2^-(bits-1) as fp32
+ *   (exact: the bits data/wavio.py's load returns for the same samples).  flac_frames_kernel: one lane per frame reads its frame in
+ *   8-byte pieces, decodes every subframe (64-bit prediction sums; coefficients and a history of 32 samples in LDS) and leaves the
+ *   integers in `workspace` (int32 [channels][ld]); flac_pcm_kernel: a workgroup per frame (at most 2^20 of them, each then walking several frames) undoes the decorrelation and scales.  A
+ *   lane never reads outside [offset, offset + length) of its row nor beyond nbytes, and writes nothing for a row that does not fit
+ *   (column + block size > ld).  A frame that runs out of bits or meets a reserved code is written as zeros in every channel and
+ *   recorded in *status_dev by an integer atomicMin of (frame index << 8 | reason), reason one of P2PHD_FLAC_E_*: the CALLER sets
+ *   *status_dev to P2PHD_FLAC_STATUS_NONE on the same stream in front of the call and reads it behind its own synchronisation.  A
+ *   frame's samples depend on nothing but its bytes and its row: the same bits on every run, stream and grid.  nframes = 0: nothing
+ *   is launched or written.  channels outside [1, 8], bits not one of the five, a null or misaligned pointer: P2PHD_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+#define P2PHD_FLAC_ROW_WORDS 6
+#define P2PHD_FLAC_OK          0
+#define P2PHD_FLAC_E_BITS      1   /* the bit stream runs past the frame's end */
+#define P2PHD_FLAC_E_RESERVED  2   /* a reserved code, a negative LPC shift, non-zero padding */
+#define P2PHD_FLAC_E_GEOMETRY  3   /* a partition or predictor order the block size does not allow */
+#define P2PHD_FLAC_E_LENGTH    4   /* the subframes end short of the frame's length */
+#define P2PHD_FLAC_E_ROW       5   /* a table row that does not fit the buffers, or whose assignment is not `channels` */
+#define P2PHD_FLAC_STATUS_NONE 0xFFFFFFFFFFFFFFFFull
+typedef struct p2phd_flac_streaminfo {
+  int32_t sample_rate, channels, bits, min_block, max_block, seek_points;
+  int64_t total_samples, first_frame_offset;
+  uint8_t md5[16];
+} p2phd_flac_streaminfo;
+int p2phd_flac_info(const void* bytes, int64_t nbytes, p2phd_flac_streaminfo* info);
+int64_t p2phd_flac_index(const void* bytes, int64_t nbytes, int64_t* table, int64_t cap);
+int p2phd_flac_decode_host(const void* bytes, int64_t nbytes, const int64_t* table, int64_t first_frame, int64_t frame_count, int channels,
+                           int32_t* out, int64_t ld);
+size_t p2phd_flac_workspace_bytes(int channels, int64_t ld);
+int p2phd_flac_tile_len(void);
+int p2phd_flac_frames_per_workgroup(void);
+int p2phd_flac_decode(const void* bytes_dev, int64_t nbytes, const int64_t* table_dev, int64_t nframes, int channels, int bits, float* out,
+                      int64_t ld, void* workspace, uint64_t* status_dev, void* stream);
+/* measurement only (tools/time_generate.py flac): p2phd_flac_decode's arguments and checks, launching the frame kernel alone (stage 1:
+ * out is not written) or the element-wise kernel alone (stage 2: it reads whatever the workspace holds).  Counts 1. */
+int p2phd_flac_decode_stage(int stage, const void* bytes_dev, int64_t nbytes, const int64_t* table_dev, int64_t nframes, int channels, int bits,
+                            float* out, int64_t ld, void* workspace, uint64_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

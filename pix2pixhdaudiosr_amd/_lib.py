@@ -92,6 +92,14 @@ SIGNATURES = {
     "p2phd_pcm_encode_shaped": (_i32, [_vp, _i64, _i32, _i64, _vp, _vp, _i32, _i64, C.c_uint64, _i64, _vp, _vp]),
     "p2phd_shaper_taps_fill": (_i32, [_i32, _vp, C.POINTER(_i32)]),
     "p2phd_shaper_tile_len": (_i64, [_i32, _i64]),
+    "p2phd_flac_info": (_i32, [_vp, _i64, _vp]),
+    "p2phd_flac_index": (_i64, [_vp, _i64, _vp, _i64]),
+    "p2phd_flac_decode_host": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64]),
+    "p2phd_flac_decode_stage": (_i32, [_i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "p2phd_flac_workspace_bytes": (_sz, [_i32, _i64]),
+    "p2phd_flac_tile_len": (_i32, []),
+    "p2phd_flac_frames_per_workgroup": (_i32, []),
+    "p2phd_flac_decode": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 import torch.utils.data as data
 
-from . import wavio
+from . import audiofile, wavio
 from .resample import resample
 
 
@@ -88,6 +88,7 @@ class AudioDataset(BaseDataset):
         self.n_fft = opt.n_fft
         self.hop_length = opt.hop_length
         self.win_length = opt.win_length
+        self.audio_formats = getattr(opt, 'audio_formats', 'wav')          # extensions a folder scan lists ('wav,flac' adds .flac)
         self.audio_file = self.get_files(opt.dataroot)
         self.center = opt.center
         self.opt = opt
@@ -100,13 +101,13 @@ class AudioDataset(BaseDataset):
         return 'AudioMDCTSpectrogramDataset'
 
     def readaudio(self, file_path):
-        metadata = wavio.info(file_path)
+        metadata = audiofile.info(file_path)                          # RIFF/WAVE or FLAC, by the file's first bytes
         max_audio_start = metadata.num_frames - self.segment_length
         if max_audio_start > 0:
             offset = torch.randint(low=0, high=max_audio_start, size=(1,)).item()
-            return wavio.load(file_path, frame_offset=offset, num_frames=self.segment_length)
+            return audiofile.load(file_path, frame_offset=offset, num_frames=self.segment_length)
         print("Warning: %s is shorter than segment_length" % file_path, metadata.num_frames)
-        return wavio.load(file_path)
+        return audiofile.load(file_path)
 
     def __getitem__(self, idx):
         file_path = self.audio_file[idx]
@@ -143,10 +144,17 @@ class AudioDataset(BaseDataset):
 
     def get_files(self, file_path):
         """Directory -> every .wav below it; otherwise a csv whose cells are paths relative to the csv's folder
-        (audio_dataset.py:64-79; the reference's extension test accepts anything, this build decodes RIFF/WAVE only)."""
+        (audio_dataset.py:64-79; the reference's extension test accepts anything, this build decodes RIFF/WAVE and FLAC).  A folder
+        scan lists .wav alone unless opt.audio_formats says otherwise ('wav,flac' adds .flac): a scan must not start to pick up
+        files it ignored.  A csv is taken as it stands; what a listed file is, its first bytes say."""
         if os.path.isdir(file_path):
+            formats = [f.strip().lower().lstrip('.') for f in str(getattr(self, 'audio_formats', None) or 'wav').split(',')]
+            unknown = [f for f in formats if f not in ('wav', 'flac')]
+            if unknown:
+                raise ValueError("audio_formats: of wav and flac, with commas; got %r" % (unknown,))
+            ends = tuple('.' + f for f in formats)
             found = [os.path.join(folder, name) for folder, _, names in os.walk(file_path, topdown=False)
-                     for name in names if name.lower().endswith(".wav")]
+                     for name in names if name.lower().endswith(ends)]
             print("Searching for audio file")
         else:
             base = os.path.dirname(file_path)
@@ -185,7 +193,7 @@ class AudioTestDataset(BaseDataset):
         self.center = opt.center
         self.dataroot = opt.dataroot
         self.device = torch.device(device if device is not None else 'cuda')
-        raw, self.in_sampling_rate = wavio.load(self.dataroot)
+        raw, self.in_sampling_rate = audiofile.load(self.dataroot)
         self.raw_audio = raw.to(self.device)
         self.audio_len = self.raw_audio.size(-1)
         print("Audio length:", self.audio_len)

@@ -1,0 +1,159 @@
+"""FLAC reader for the feeder and for whole-file generation (the reference reads .flac through torchaudio; this build has its own
+decoder, csrc/flac.hip): native FLAC streams, the subset include/p2phd.h writes down.  `info` / `load` have the shape of wavio's;
+samples come out as wavio.load returns the same samples from a WAV: float32 [channels, frames], integer x 2^-(bits-1).
+
+Everything here runs on the host (p2phd_flac_info / p2phd_flac_index / p2phd_flac_decode_host need no device): DataLoader workers
+have none.  The frame index of a file -- one row per frame, every CRC verified -- is built once per (path, size, mtime) and kept
+in a bounded cache of the process, so with the cache warm a random training segment costs one seek, one read of the covering
+frames' bytes and their decode.  Whole-file generation copies the file's bytes and the index to the device instead and decodes
+there (generate.flac_decode)."""
+import ctypes
+import hashlib
+import os
+from collections import OrderedDict, namedtuple
+
+import numpy as np
+import torch
+
+# the leading four fields are WavInfo's; num_flac_frames: rows of the frame index
+FlacInfo = namedtuple("FlacInfo", "sample_rate num_frames num_channels bits_per_sample min_block max_block first_frame_offset md5 seek_points "
+                                  "num_flac_frames")
+
+ROW = 6                                                                     # P2PHD_FLAC_ROW_WORDS: offset, length, first sample, block size, assignment, bits
+INDEX_CACHE_ENTRIES = 4096                                                  # files whose index the process keeps
+STATS = {"index_builds": 0, "index_hits": 0}                                # (tests read these)
+_CACHE = OrderedDict()                                                      # (path, size, mtime_ns) -> (FlacInfo, table)
+
+
+class _StreamInfo(ctypes.Structure):
+    """struct p2phd_flac_streaminfo (include/p2phd.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("sample_rate", "channels", "bits", "min_block", "max_block", "seek_points")] + \
+               [("total_samples", ctypes.c_int64), ("first_frame_offset", ctypes.c_int64), ("md5", ctypes.c_uint8 * 16)]
+
+
+def _lib():
+    from .. import _lib as L
+    return L.lib()
+
+
+def _err(name):
+    return ValueError("%s: %s" % (name, _lib().p2phd_last_error().decode("utf-8", "replace")))
+
+
+def _address(buf):
+    """(address, length, keep-alive) of a bytes-like object."""
+    a = np.frombuffer(buf, dtype=np.uint8)
+    return ctypes.c_void_p(a.ctypes.data if a.size else None), a.size, a
+
+
+def index_bytes(buf, name="<bytes>"):
+    """The whole stream as a bytes-like object -> (FlacInfo, table): table int64 [frames, 6], one row per frame
+    (p2phd_flac_index: every CRC-8 and CRC-16 verified, the frames chained without a gap, the sample numbers consecutive).
+    Anything the subset does not hold, and any corruption, is a ValueError that names `name` and the reason."""
+    lib = _lib()
+    addr, n, keep = _address(buf)
+    si = _StreamInfo()
+    if lib.p2phd_flac_info(addr, n, ctypes.byref(si)) != 0:
+        raise _err(name)
+    count = lib.p2phd_flac_index(addr, n, None, 0)
+    if count < 0:
+        raise _err(name)
+    table = np.zeros((count, ROW), dtype=np.int64)
+    if count and lib.p2phd_flac_index(addr, n, ctypes.c_void_p(table.ctypes.data), count) != count:
+        raise _err(name)
+    total = int(table[:, 3].sum()) if count else 0
+    meta = FlacInfo(si.sample_rate, total, si.channels, si.bits, si.min_block, si.max_block, si.first_frame_offset, bytes(si.md5), si.seek_points, count)
+    return meta, table
+
+
+def _indexed(path):
+    path = os.fspath(path)
+    st = os.stat(path)
+    key = (os.path.abspath(path), st.st_size, st.st_mtime_ns)
+    hit = _CACHE.get(key)
+    if hit is not None:
+        _CACHE.move_to_end(key)
+        STATS["index_hits"] += 1
+        return hit
+    with open(path, "rb") as f:
+        data = f.read()
+    hit = index_bytes(data, path)
+    hit[1].setflags(write=False)
+    STATS["index_builds"] += 1
+    _CACHE[key] = hit
+    while len(_CACHE) > INDEX_CACHE_ENTRIES:
+        _CACHE.popitem(last=False)
+    return hit
+
+
+def info(path):
+    """-> FlacInfo (num_frames: the samples the frames hold, counted where STREAMINFO states 0).  Builds, or re-uses, the file's index."""
+    return _indexed(path)[0]
+
+
+def decode_frames(buf, table, first, count, channels, name="<bytes>"):
+    """Frames [first, first + count) of `table`, whose offsets point into `buf` -> int32 [channels, samples] (p2phd_flac_decode_host)."""
+    rows = table[first:first + count]
+    total = int(rows[:, 3].sum()) if count else 0
+    out = np.zeros((channels, total), dtype=np.int32)
+    if count:
+        addr, n, keep = _address(buf)
+        t = np.ascontiguousarray(table, dtype=np.int64)
+        if _lib().p2phd_flac_decode_host(addr, n, ctypes.c_void_p(t.ctypes.data), int(first), int(count), int(channels), ctypes.c_void_p(out.ctypes.data), total) != 0:
+            raise _err(name)
+    return out
+
+
+def load(path, frame_offset=0, num_frames=-1):
+    """-> (float32 tensor [channels, frames], sample_rate), like wavio.load: only the FLAC frames that cover the window are read and
+    decoded (on the host)."""
+    meta, table = _indexed(path)
+    start = min(max(int(frame_offset), 0), meta.num_frames)
+    stop = meta.num_frames if num_frames < 0 else min(meta.num_frames, start + int(num_frames))
+    if stop <= start:
+        return torch.zeros((meta.num_channels, 0), dtype=torch.float32), meta.sample_rate
+    first_sample = table[:, 2] - table[0, 2]
+    f0 = int(np.searchsorted(first_sample, start, side="right")) - 1
+    f1 = int(np.searchsorted(first_sample, stop, side="left"))                # one behind the last covering frame
+    byte0, byte1 = int(table[f0, 0]), int(table[f1 - 1, 0] + table[f1 - 1, 1])
+    with open(path, "rb") as f:
+        f.seek(byte0)
+        data = f.read(byte1 - byte0)
+    if len(data) != byte1 - byte0:
+        raise ValueError("%s: short read of frames %d .. %d" % (path, f0, f1 - 1))
+    rows = table[f0:f1].copy()
+    rows[:, 0] -= byte0
+    pcm = decode_frames(data, rows, 0, f1 - f0, meta.num_channels, path)
+    lo = start - int(first_sample[f0])
+    a = pcm[:, lo:lo + (stop - start)].astype(np.float32) * np.float32(2.0 ** -(meta.bits_per_sample - 1))
+    return torch.from_numpy(np.ascontiguousarray(a)), meta.sample_rate
+
+
+def read_file(path, into=None):
+    """-> (bytes, FlacInfo, table): the whole file, undecoded (the device decodes it, generate.flac_decode), and its index, built
+    from those bytes.  `into`: as wavio.read_payload's -- a writable buffer at least as long as the file, or a callable that is given
+    the byte count and returns one (a pinned host tensor's memory); the bytes are a view of it, cut to size."""
+    with open(path, "rb") as f:
+        n = os.fstat(f.fileno()).st_size
+        buf = bytearray(n) if into is None else into(n) if callable(into) else into
+        buf = memoryview(buf).cast("B")
+        if len(buf) < n:
+            raise ValueError(f"{path}: the buffer holds {len(buf)} bytes, the file {n}")
+        if f.readinto(buf[:n]) != n:
+            raise ValueError(f"{path}: short read")
+    meta, table = index_bytes(buf[:n], os.fspath(path))
+    return buf[:n], meta, table
+
+
+def verify(path):
+    """Decodes the whole file on the host and compares the MD5 of its interleaved little-endian samples with STREAMINFO's -> True /
+    False; None where STREAMINFO's is all zeros ("not set")."""
+    meta, table = _indexed(path)
+    if meta.md5 == b"\0" * 16:
+        return None
+    with open(path, "rb") as f:
+        data = f.read()
+    pcm = decode_frames(data, table, 0, meta.num_flac_frames, meta.num_channels, path)
+    nb = (meta.bits_per_sample + 7) // 8
+    le = np.ascontiguousarray(pcm.T).astype("<i4").reshape(-1, 1).view(np.uint8)[:, :nb]
+    return hashlib.md5(np.ascontiguousarray(le).tobytes()).digest() == meta.md5

@@ -3,6 +3,7 @@ normalisation): one integrated loudness over the 400 ms blocks of every file, on
 so the level differences between the files survive.  Three phases: every file is generated and measured (A), the folder's figures
 are found and brought back behind one synchronisation (B), every file is encoded with the folder's gains and written (C)."""
 import math
+import os
 import struct
 
 import torch
@@ -58,9 +59,10 @@ def _generate(sr, read, is_lr_input, channels, encoding, extended_metrics):
     return lr, out, metrics, ext, meta
 
 
-def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album, dither_seed):
+def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album, dither_seed, plan=None, written=False, verify_input=False):
     """enhance_folder with loudness_scope='folder' -> its records.  `sr`: the SuperResolver; `stage`, `tp`, `loud`: the validated
-    options as enhance_folder holds them; `album`: check_loudness_scope's result."""
+    options as enhance_folder holds them; `album`: check_loudness_scope's result; `plan`: the folder's plan where the caller has made
+    it (None: plan_folder's default); `written`: a record gains 'written', the output's relative path; `verify_input`: enhance_file's, per FLAC file."""
     rate = int(sr.opt.hr_sampling_rate)
     scaled = loud['mode'] != 'report'
     guard = stage is not None and stage['clip'] == 'guard'
@@ -68,9 +70,11 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
     entries, kept_bytes = [], 0
 
     # -- A: generate and measure every file; keep its clip ---------------------------------------------
-    for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
+    for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out) if plan is None else plan):
         rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
                'metrics': None, 'error': None}
+        if written:
+            rec['written'] = os.path.relpath(path_out, dir_out)
         if extended_metrics:
             rec['metrics_ext'] = None
         if stage is not None:
@@ -83,7 +87,7 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
         entry = {'rec': rec, 'k': k, 'path_out': path_out, 'clip': None}
         entries.append(entry)
         try:
-            read = sr._read(path_in)
+            read = sr._read(path_in, verify=True) if verify_input else sr._read(path_in)
             if getattr(sr, 'stereo', 'lr') == 'ms':                         # (more than two channels: a skipped file with its reason)
                 sr._check_stereo_channels(channels, read[1].num_channels)
         except (ValueError, OSError, EOFError, struct.error) as e:

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import torch
 
 from .ops import shaper_coefficients
-from .plans import (CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
@@ -302,6 +302,12 @@ def _parser():
                          "converter (flat to 0.907 of the lower Nyquist frequency, 120 dB down where anything folds) in front of the "
                          "loudness, true-peak and limiter stages, which then measure and hold what is written; one start-up line more; "
                          "not with --spectrogram or --loudness_scope folder (default: off)")
+    ap.add_argument("--input_formats", default=None, metavar="LIST",
+                    help="a folder as --input: the extensions to list, of wav and flac, with commas (default: wav); x.flac is written as "
+                         "x.wav; a single --input file is read by what its first bytes say, whatever its name")
+    ap.add_argument("--verify_input", action="store_true",
+                    help="FLAC inputs: decode the file on the host first and refuse it where its samples do not have the MD5 its "
+                         "STREAMINFO states; one start-up line more (default: off)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -332,6 +338,12 @@ def main(argv=None):
         if a.output_rate is not None:                                       # (the rate pair itself: once the options file has been read)
             check_output_rate(a.output_rate, a.output_rate, "generate")
             picture['output_rate'] = a.output_rate
+        if a.input_formats is not None:
+            if not folder_mode:
+                raise ValueError("--input_formats is an option of a folder as --input")
+            picture['input_formats'] = check_input_formats(a.input_formats, "generate")
+        if a.verify_input:
+            picture['verify_input'] = True
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
             check_limiter(a.limiter, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, 48000, "generate")
             picture.update(limiter=True, limiter_lookahead_ms=a.limiter_lookahead_ms, limiter_hold_ms=a.limiter_hold_ms)
@@ -389,6 +401,8 @@ def main(argv=None):
         print(output_rate_line(rc))
     if a.dither == 'shaped':                                                # (without the option: no line more than before)
         print(dither_line(out_stage, shaper_coefficients(out_stage['curve']).numel()))
+    if a.verify_input:                                                      # (without the option: no line more than before)
+        print("input: every FLAC file's MD5 is checked on the host before it is read")
     rate = int(opt.hr_sampling_rate) if rc is None else rc['rate']
     try:
         return _run(a, sr, stage, seed, rate, folder_mode)
@@ -404,7 +418,7 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 print('skipped %s: %s' % (r['path'], r['error']))
                 return
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
-            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r['path']), r['out_frames'], rate,
+            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r.get('written', r['path'])), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
             if a.report_peaks or a.true_peak or a.limiter:
                 _print_peaks(r['path'], r['output'])

@@ -1,5 +1,5 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip and csrc/shaper.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip, csrc/shaper.hip and csrc/flac.hip as tensor functions."""
 import ctypes
 
 import torch
@@ -87,6 +87,43 @@ def pcm_decode(payload, frames, channels, format_tag, bits):
         raise ValueError("pcm_decode: %d bytes do not hold %d frames of %d x %d bit" % (b.numel(), frames, channels, bits))
     out = torch.empty((channels, frames), dtype=torch.float32, device=b.device)
     _lib.check(_lib.lib().p2phd_pcm_decode(_lib.ptr(b), frames, channels, fmt, _lib.ptr(out), frames, _lib.stream_ptr()), "pcm_decode")
+    return out
+
+
+FLAC_REASONS = {1: "its bit stream runs past the frame's end", 2: "a reserved code", 3: "an impossible partition or predictor order",
+                4: "its subframes end short of the frame's length", 5: "a table row that does not fit the buffers or the channel count"}
+
+
+def flac_decode(bytes_dev, table, info, check=True):
+    """bytes_dev: uint8 tensor on the GPU holding a FLAC file as it stands; table: its frame index, int64 [frames, 6] (data/flacio.py:
+    index_bytes / read_file), on the GPU or on the host (then copied); info: its FlacInfo -> [channels, num_frames] f32 on the GPU,
+    bit-identical to what flacio.load returns for the file (p2phd_flac_decode: two launches of the family "flac", none for a file
+    without frames).  `check` (default): waits for the decoder's status word and raises a ValueError that names the lowest frame that
+    did not decode (such a frame is zeros in the result).  check=False: nothing is waited for and (out, status) is returned --
+    status an int64 tensor of one element on the GPU, -1 for "every frame decoded", else frame << 8 | reason."""
+    b = _lib.require_gpu_tensor(bytes_dev, "flac_decode: bytes_dev", torch.uint8)
+    if isinstance(table, torch.Tensor) and table.is_cuda:
+        t = _lib.require_gpu_tensor(table, "flac_decode: table", torch.int64)
+    else:
+        t = torch.as_tensor(table, dtype=torch.int64).contiguous().to(b.device)
+    if t.dim() != 2 or t.shape[1] != 6:
+        raise ValueError("flac_decode: expected a table [frames, 6], got shape %s" % (tuple(t.shape),))
+    C, L, bits = int(info.num_channels), int(info.num_frames), int(info.bits_per_sample)
+    out = torch.zeros((C, L), dtype=torch.float32, device=b.device)
+    status = torch.full((1,), -1, dtype=torch.int64, device=b.device)
+    lib = _lib.lib()
+    if t.shape[0] and L:
+        n = lib.p2phd_flac_workspace_bytes(C, L)
+        if n == 0:
+            _lib.check(-1, "flac_workspace_bytes")
+        work = torch.empty((n,), dtype=torch.uint8, device=b.device)
+        _lib.check(lib.p2phd_flac_decode(_lib.ptr(b), b.numel(), _lib.ptr(t), t.shape[0], C, bits, _lib.ptr(out), L, _lib.ptr(work), _lib.ptr(status),
+                                         _lib.stream_ptr()), "flac_decode")
+    if not check:
+        return out, status
+    v = int(status.item())
+    if v != -1:
+        raise ValueError("flac_decode: frame %d does not decode: %s" % (v >> 8, FLAC_REASONS.get(v & 255, "reason %d" % (v & 255))))
     return out
 
 

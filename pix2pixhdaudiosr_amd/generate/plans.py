@@ -666,9 +666,31 @@ def spectrogram_lut():
     return lut
 
 
-def plan_folder(dir_in, dir_out):
+INPUT_FORMATS = ('wav', 'flac')                                             # extensions a folder scan can list
+
+
+def check_input_formats(formats, who="plan_folder"):
+    """`formats`: a sequence of extensions, or one string with commas ('wav,flac') -> a tuple of INPUT_FORMATS' members, lower case,
+    without duplicates; anything else is a ValueError."""
+    names = formats.split(',') if isinstance(formats, str) else list(formats)
+    out = []
+    for f in names:
+        f = f.strip().lower().lstrip('.') if isinstance(f, str) else f
+        if f not in INPUT_FORMATS:
+            raise ValueError("%s: input formats must be of %s, got %r" % (who, list(INPUT_FORMATS), formats))
+        if f not in out:
+            out.append(f)
+    if not out:
+        raise ValueError("%s: no input format given" % who)
+    return tuple(out)
+
+
+def plan_folder(dir_in, dir_out, formats=('wav',)):
     """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
-    output keeps the relative path under dir_out.  Other files are ignored."""
+    output keeps the relative path under dir_out.  Other files are ignored.  `formats`: the extensions that are listed
+    (check_input_formats; default: wav alone); every output is a wav, so x.flac is written as x.wav, and two inputs that would be
+    written to the same path are a ValueError."""
+    formats = check_input_formats(formats)
     if not os.path.isdir(dir_in):
         raise NotADirectoryError("%s is not a directory" % dir_in)
     if os.path.exists(dir_out) and not os.path.isdir(dir_out):
@@ -676,9 +698,16 @@ def plan_folder(dir_in, dir_out):
     rel = []
     for root, _, files in os.walk(dir_in):
         for f in files:
-            if f.lower().endswith('.wav'):
+            if f.lower().endswith(tuple('.' + x for x in formats)):
                 rel.append(os.path.relpath(os.path.join(root, f), dir_in))
-    return [(r, os.path.join(dir_in, r), os.path.join(dir_out, r)) for r in sorted(rel)]
+    plan, taken = [], {}
+    for r in sorted(rel):
+        out = r if r.lower().endswith('.wav') else os.path.splitext(r)[0] + '.wav'
+        if out in taken:
+            raise ValueError("%s and %s would both be written to %s" % (os.path.join(dir_in, taken[out]), os.path.join(dir_in, r), os.path.join(dir_out, out)))
+        taken[out] = r
+        plan.append((r, os.path.join(dir_in, r), os.path.join(dir_out, out)))
+    return plan
 
 
 def check_paths(path_in, path_out):

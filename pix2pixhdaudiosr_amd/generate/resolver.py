@@ -5,7 +5,7 @@ import struct
 
 import torch
 
-from .ops import (bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+from .ops import (flac_decode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
 from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
@@ -347,14 +347,44 @@ class SuperResolver:
         self._pins[slot] = (t, None)
         return t
 
-    def _read(self, path, slot='in0'):
-        """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo)."""
-        from ..data import wavio
+    def _read(self, path, slot='in0', verify=False):
+        """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo).  A file whose
+        first bytes say FLAC (data/audiofile.py) goes through _read_flac instead; `verify` is its."""
+        from ..data import audiofile, wavio
+        if audiofile.kind(path) == 'flac':
+            return self._read_flac(path, slot, verify)
         payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
         return self._pins[slot][0][:len(payload)], meta, slot
 
+    def _read_flac(self, path, slot, verify=False):
+        """Host work only: the whole FLAC file into pinned buffer `slot`, its frame index built on the host (every CRC verified;
+        anything the reader does not hold is a ValueError here, before a launch) and laid behind the bytes at the next multiple of
+        8 -> (bytes and table as one host tensor, FlacInfo): one copy takes both to the device.  `verify`: the file is first decoded
+        on the host and its MD5 compared with STREAMINFO's.  The slot remembers the file's name for _decode's error text."""
+        from ..data import flacio
+        if verify and flacio.verify(path) is False:
+            raise ValueError("%s: the decoded samples do not have the MD5 that STREAMINFO states" % path)
+        # room for the table of a file whose frames average 768 bytes or more; a file of smaller frames moves to a larger buffer once
+        payload, meta, table = flacio.read_file(path, into=lambda n: self._pinned(slot, n + n // 16 + 4096).numpy())
+        n = len(payload)
+        at = (n + 7) & ~7
+        pinned = self._pins[slot][0]
+        if pinned.numel() < at + table.nbytes:
+            grown = torch.empty((at + table.nbytes,), dtype=torch.uint8, pin_memory=True)
+            grown[:n].copy_(pinned[:n])
+            self._pins[slot] = (grown, None)
+            pinned = grown
+        pinned[n:at].zero_()
+        pinned[at:at + table.nbytes].copy_(torch.from_numpy(table).view(-1).view(torch.uint8))
+        if not hasattr(self, '_pin_names'):
+            self._pin_names = {}
+        self._pin_names[slot] = os.fspath(path)
+        return pinned[:at + table.nbytes], meta, slot
+
     def _decode(self, host, meta, slot):
-        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel."""
+        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel.  The bytes and table of a
+        FLAC file (_read_flac): one copy, the two kernels of the family "flac", and one wait for their status word -- a frame that
+        passed the index's CRCs and still does not decode is a ValueError that names it, before anything else is launched."""
         if host.numel() == 0:
             return torch.zeros((meta.num_channels, 0), dtype=torch.float32, device=self.device)
         dev = torch.empty((host.numel(),), dtype=torch.uint8, device=self.device)
@@ -362,6 +392,12 @@ class SuperResolver:
         busy = torch.cuda.Event()
         busy.record()
         self._pins[slot] = (self._pins[slot][0], busy)
+        if hasattr(meta, 'num_flac_frames'):
+            at = host.numel() - meta.num_flac_frames * 48
+            try:
+                return flac_decode(dev[:at], dev[at:].view(torch.int64).view(-1, 6), meta)
+            except ValueError as e:                                         # (the decoder's refusal, with the file it is about)
+                raise ValueError("%s: %s" % (getattr(self, '_pin_names', {}).get(slot, '<flac>'), e)) from None
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
     def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None):
@@ -725,14 +761,18 @@ class SuperResolver:
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
-                     dither_chunk=None):
+                     dither_chunk=None, verify_input=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
         output encoded on the device (csrc/pcm.hip).  Returns {'sr', 'lr', 'hr', 'metrics', 'info'}: [C, L] tensors on the GPU;
         'hr' and 'metrics' are None unless the input is a full-band clip at the high rate; 'metrics' is
         util.compute_matrics against the input with 'first', else a list with one such 7-tuple per written channel, each
-        computed on that channel alone; 'info' is the input's wavio.WavInfo.  `extended_metrics`: the result gains
+        computed on that channel alone; 'info' is the input's wavio.WavInfo.  A FLAC input (told by its first bytes, not its name) is
+        read as it stands: its bytes and frame index are copied and csrc/flac.hip decodes them on the device (two launches of the
+        family "flac" in place of the PCM decoder's one); 'info' is then its flacio.FlacInfo, everything else is what the same
+        samples in a wav give.  `verify_input`: a FLAC input is first decoded on the host and refused with a ValueError where its
+        samples do not have STREAMINFO's MD5.  `extended_metrics`: the result gains
         'metrics_ext', util.compute_matrics_ext of all written channels from one device call -- a list with one dict
         (util.METRIC_ROW_NAMES -> float) per written channel, also with 'first'; None where 'metrics' is None -- and 'metrics'
         holds the same rows' figures.
@@ -854,10 +894,11 @@ class SuperResolver:
             extra['bw'] = bw
         if st is not None:
             extra['st'] = st
+        read = self._read(path_in, verify=True) if verify_input else self._read(path_in)
         if loud is None:
-            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
+            res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
         else:
-            res = self._enhance_payload(self._read(path_in), path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud, **extra)
+            res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud, **extra)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
 
@@ -881,7 +922,8 @@ class SuperResolver:
                        spectrogram=None, spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None,
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
-                       stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None):
+                       stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
+                       verify_input=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -926,7 +968,11 @@ class SuperResolver:
         carrying the 'error', in either scope.
         `output_rate`: enhance_file's, one rate for every file; a record's 'out_frames' is then the written length at that rate and a
         record gains 'output_rate' (as enhance_file returns it; None for a skipped file).  Not built for loudness_scope 'folder' or
-        with `spectrogram`: a ValueError."""
+        with `spectrogram`: a ValueError.
+        `input_formats`: None (the above: *.wav only), or the extensions to list, ('wav', 'flac') for instance (plan_folder's
+        `formats`): x.flac is written as x.wav, a record then gains 'written' (the output's relative path), and two inputs that would
+        be written to one path are a ValueError before any file is opened.  `verify_input`: enhance_file's, per FLAC file; a mismatch
+        is a skipped file.  Both hold in either loudness scope."""
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_folder")
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder", dither_curve, dither_chunk)
@@ -936,10 +982,11 @@ class SuperResolver:
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
         loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range), rc, "enhance_folder")
         album = check_loudness_scope(loudness_scope, loud, "enhance_folder", True, limiter, spectrogram, album_cache_bytes)
+        plan = plan_folder(dir_in, dir_out) if input_formats is None else plan_folder(dir_in, dir_out, input_formats)
         if album is not None:
             from .album import enhance_album
             return enhance_album(self, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album,
-                                 dither_seed)
+                                 dither_seed, plan=plan, written=input_formats is not None, verify_input=verify_input)
         extra = {} if loud is None else {'loud': loud}
         if tp is not None:
             extra['tp'] = tp
@@ -952,9 +999,11 @@ class SuperResolver:
         if rc is not None:
             extra['rc'] = rc
         records = []
-        for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out)):
+        for k, (rel, path_in, path_out) in enumerate(plan):
             rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
                    'metrics': None, 'error': None}
+            if input_formats is not None:
+                rec['written'] = os.path.relpath(path_out, dir_out)
             if extended_metrics:
                 rec['metrics_ext'] = None
             if stage is not None:
@@ -974,7 +1023,7 @@ class SuperResolver:
             if getattr(self, 'norm_scope', 'group') == 'clip':
                 rec['norm'] = None
             try:
-                read = self._read(path_in)
+                read = self._read(path_in, verify=True) if verify_input else self._read(path_in)
                 self._check_picture_channel(spec, channels, read[1].num_channels)
                 self._check_stereo_channels(channels, read[1].num_channels)
             except (ValueError, OSError, EOFError, struct.error) as e:

@@ -8,6 +8,12 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
   seams     RMS of the first difference at the joins (the first sample of every segment but the first) relative to the
             first-difference RMS of the whole output, at overlap 0 and 0.25, same weights and noise seed
 
+  flac      (only when asked for) the input side on one 15 s mono 16-bit clip, the same samples as FLAC (encoded by tests/_flac_ref.py:
+            block size 4096, FIXED 2 and LPC 8 subframes in turn) and as wav: SuperResolver._read + _decode on the FLAC (index on the
+            host, csrc/flac.hip on the device), on the wav (read_payload, copy, p2phd_pcm_decode) and the host decoder followed by a
+            copy, interleaved, median and spread of --reps; then by events p2phd_flac_decode whole and each kernel alone beside
+            p2phd_pcm_decode, on the clip and on an hour of it; the host index and host decoder alone; log in --flac_log
+
   folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
             ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
             file, what the package did before the device codec) and generate.SuperResolver.enhance_folder(channels='all')
@@ -937,6 +943,137 @@ def _dither_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_flac(seconds, reps, log):
+    """The input side on the same samples, three ways, interleaved: the FLAC path of SuperResolver (_read: file bytes into the pinned
+    slot and the index on the host; _decode: one copy of bytes and table, the two kernels of the family "flac"), the WAV path
+    (read_payload, copy, p2phd_pcm_decode) and the host decoder followed by a copy (flacio.load -> .cuda()).  Then, by events, the
+    device decode whole and each kernel alone (p2phd_flac_decode_stage) beside p2phd_pcm_decode, on the clip and on an hour of it.  The
+    clip is encoded by the restatement tests/_flac_ref.py: mono, 16 bit, block size 4096, FIXED order 2 and LPC order 8 subframes in
+    turn.  The hour is the clip's bytes 240 times over with a table whose offsets and columns are shifted -- the device decoder reads
+    the table, not the frames' numbers; the host index cannot be run on such an hour and is stated as 240 times the clip's; the host decoder is run on it, three times."""
+    import tempfile
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _flac_ref as R
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd import _lib
+    from pix2pixhdaudiosr_amd.data import flacio, wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, flac_decode, pcm_decode
+    rate = int(opt.hr_sampling_rate)
+    q = torch.round(0.5 * x[0].cpu().double() * 32768.0).clamp(-32768, 32767).to(torch.int64)
+    ints = q.tolist()
+    lpc8 = dict(kind="lpc", coefs=[2048, -1024, 0, 0, 0, 0, 0, 0], precision=13, shift=10, porder=4, method=0)
+    fixed = dict(kind="fixed", order=2, porder=4)
+    last = len(ints) % 4096
+    t0 = time.perf_counter()
+    data, frames = R.make_stream([ints], 16, 4096, rate=rate, specs=lambda k, c: dict(fixed if k % 2 == 0 else lpc8, porder=4 if (k + 1) * 4096 <= len(ints) or last % 16 == 0 else 0))
+    t_enc = time.perf_counter() - t0
+    lines = ["# tools/time_generate.py flac: one %g s mono 16-bit clip at 48 kHz (%d samples), block size 4096, FIXED 2 / LPC 8 in turn, %d frames, %d bytes "
+             "as FLAC (%.1f %% of the PCM16 payload; the restatement took %.1f s to encode it); %d interleaved repeats"
+             % (seconds, len(ints), len(frames), len(data), 100.0 * len(data) / (2 * len(ints)), t_enc, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        pf, pw = os.path.join(tmp, "in.flac"), os.path.join(tmp, "in.wav")
+        with open(pf, "wb") as f:
+            f.write(data)
+        wavio.save(pw, (q.float() / 32768.0)[None], rate)
+        assert torch.equal(flacio.load(pf)[0], wavio.load(pw)[0])
+        sr = SuperResolver(model, opt, overlap=0.25)
+
+        def flac_path():
+            return sr._decode(*sr._read(pf))
+
+        def wav_path():
+            return sr._decode(*sr._read(pw))
+
+        def host_path():
+            return flacio.load(pf)[0].cuda()
+
+        def read_only():
+            return sr._read(pf)
+        runs = [("flac: _read + _decode (index on the host, device decode)", flac_path), ("flac: _read alone (file bytes, index)", read_only),
+                ("wav:  _read + _decode (read_payload, copy, pcm_decode) ", wav_path), ("flac: host decoder + copy (flacio.load, .cuda())      ", host_path)]
+        assert torch.equal(flac_path(), wav_path()) and torch.equal(host_path(), wav_path())
+        for _, fn in runs:
+            fn(); fn()
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, fn) in enumerate(runs):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+    meta, table = flacio.index_bytes(data)
+    raw = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+    pcm = torch.from_numpy(np.array(ints, dtype="<i2").view(np.uint8).copy()).cuda()
+    copies = 3600 * rate // len(ints)
+    big_table = np.concatenate([table + np.array([k * len(data), 0, k * len(ints), 0, 0, 0], dtype=np.int64) for k in range(copies)])
+    big_meta = meta._replace(num_frames=copies * len(ints), num_flac_frames=len(big_table))
+    def one_stage(stage, b, t, m):                                 # generate.flac_decode's allocations in front of one kernel alone
+        out = torch.zeros((1, m.num_frames), dtype=torch.float32, device=b.device)
+        status = torch.full((1,), -1, dtype=torch.int64, device=b.device)
+        work = torch.empty((_lib.lib().p2phd_flac_workspace_bytes(1, m.num_frames),), dtype=torch.uint8, device=b.device)
+        _lib.check(_lib.lib().p2phd_flac_decode_stage(stage, _lib.ptr(b), b.numel(), _lib.ptr(t), t.shape[0], 1, 16, _lib.ptr(out), m.num_frames,
+                                                      _lib.ptr(work), _lib.ptr(status), _lib.stream_ptr()), "flac_decode_stage")
+        return out
+
+    for name, b, t, m, payload in (("the clip", raw, torch.from_numpy(table.copy()).cuda(), meta, pcm),
+                                   ("an hour", raw.repeat(copies), torch.from_numpy(big_table).cuda(), big_meta, pcm.repeat(copies))):
+        kinds = [("p2phd_flac_decode, both kernels", 0), ("flac_frames_kernel alone", 1), ("flac_pcm_kernel alone", 2), ("p2phd_pcm_decode", None)]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(kinds) + 1)]
+        ks = [[] for _ in kinds]
+        for _ in range(reps + 2):
+            outs = []
+            ev[0].record()
+            for k, (_, stage) in enumerate(kinds):
+                if stage is None:
+                    outs.append(pcm_decode(payload, m.num_frames, 1, 1, 16))
+                elif stage == 0:
+                    outs.append(flac_decode(b, t, m, check=False)[0])
+                else:
+                    outs.append(one_stage(stage, b, t, m))
+                ev[k + 1].record()
+            torch.cuda.synchronize()
+            for k in range(len(kinds)):
+                ks[k].append(ev[k].elapsed_time(ev[k + 1]) * 1e3)
+            assert torch.equal(outs[0], outs[3])
+            del outs
+        L = m.num_frames
+        lines.append("by events on %s (median of %d, each with the allocation and zeroing of its result in front; %d samples, %d frames = %d waves of the frame kernel): %s"
+                     % (name, reps, L, m.num_flac_frames, -(-m.num_flac_frames // 64),
+                        "; ".join("%s %.1f us (spread %.1f) = %.3f ns per sample" % (kn, _median(k[2:]), max(k[2:]) - min(k[2:]), _median(k[2:]) * 1e3 / L)
+                                  for (kn, _), k in zip(kinds, ks))))
+        lines.append("runs: " + "; ".join("%s %s" % (kn, " ".join("%.1f" % v for v in k[2:])) for (kn, _), k in zip(kinds, ks)))
+    th, ti = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        flacio.index_bytes(data)
+        ti.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        flacio.decode_frames(data, table, 0, len(table), 1)
+        th.append((time.perf_counter() - t0) * 1e3)
+    big = data * copies
+    tb = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        flacio.decode_frames(big, big_table, 0, len(big_table), 1)
+        tb.append((time.perf_counter() - t0) * 1e3)
+    lines.append("on the host, one thread, the clip: index (every CRC) median %.3f ms = %.2f ns per byte; p2phd_flac_decode_host median %.3f ms = %.2f ns per sample.  "
+                 "The hour (the clip's bytes %d times over under a shifted table, as on the device): p2phd_flac_decode_host measured %s ms (3 runs, with the "
+                 "allocation of its int32 rows); its index is not measured -- the repeated frames' numbers do not chain -- and would be %d times the clip's, %.0f ms"
+                 % (_median(ti), _median(ti) * 1e6 / len(data), _median(th), _median(th) * 1e6 / len(ints), copies, " ".join("%.0f" % v for v in tb), copies,
+                    _median(ti) * copies))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_normscope(seconds, reps, log, off_only=False):
     """enhance_file on a mono clip, file to file: norm_scope 'group' (an object built without the option) and 'clip', interleaved;
     then p2phd_spectro_range, p2phd_range_fold and p2phd_spectro_encode_given alone, by events, on one group's spectrum beside
@@ -1213,7 +1350,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1230,11 +1367,14 @@ def main():
     ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
+    ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
+    if a.mode == "flac":
+        return run_flac(a.seconds, 9 if a.reps is None else a.reps, a.flac_log)
     if a.mode == "album":
         return run_album(a.seconds, 9 if a.reps is None else a.reps, a.files, a.album_log)
     if a.mode == "stereo":
