@@ -98,7 +98,11 @@ int p2phd_probe_read(float* ms_out, int cap);
  * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip), "normscope" (the range
  * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything),
  * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip), "flac" (the two kernels of its FLAC input,
- * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2).
+ * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), and the weight packs of p2phd_conv_pack_weights /
+ * p2phd_conv_fp8_pack_weights, one family per kernel of csrc/wpack.hip, counted per launch plan: "wpack_generic" (the tap walk),
+ * "wpack_dense", "wpack_transposed" (the two LDS re-orderings), "wpack_kmajor" (cast of K-major master weights), "wpack_kmajor_t"
+ * (their per-tap transpose), "wpack_merged" (merged sub-pixel launches, either tap order), "wpack_fp8" (the e4m3 quantiser with
+ * its amax and scale kernels), and "wpack_frag" (the fragment pack of a dedicated kernel behind the generic pack).
  * family == NULL with reset != 0 clears all.
  * Returns the count before the reset, -1 for an unknown name.  Counts launches recorded under graph capture once (at capture).
  * Test hook: proves which kernels a whole training step really runs on (train.py:148-184 at the benchmarked batch). */

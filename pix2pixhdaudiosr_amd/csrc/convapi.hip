@@ -412,6 +412,7 @@ extern "C" int p2phd_conv_pack_weights(const p2phd_conv_desc* c, int which, cons
     } else if (int rc = launch_pack(p.d, m, c->dtype, w, dst, p.rows_pad, st)) return rc;
   }
   char* frag = static_cast<char*>(packed) + L.tail_off * elem_size(c->dtype);
+  if (L.tail != TAIL_NONE) ++g_launch_count[LC_WPACK_FRAG];
   switch (L.tail) {
     case TAIL_MARCH: return march_pack(c, which, w, frag, st);
     case TAIL_DLAST: return dlast_pack(c, which, w, frag, st);

@@ -443,6 +443,7 @@ int launch_pack_merged(const GDesc& d, int dtype, const float* w, void* wp, int 
                        long s_k, long s_c, hipStream_t st) {
   const long total = (long)rows_pad * d.KK;
   const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
+  ++g_launch_count[LC_WPACK_MERGED];
   FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_merged_kernel<T>, dim3(blocks), dim3(256), 0, st, d, w, (T*)wp, rows_pad, K, C, R, S, pad, s_k, s_c));
   return check_launch("pack_weights(merged)");
 }
@@ -453,25 +454,30 @@ int launch_pack(const GDesc& d, const WMap& m, int dtype, const float* w, void* 
     const int row_len = d.nth * d.ntw * m.inner;
     const long total4 = (long)rows_pad * (d.KK / 4);
     const dim3 grid((unsigned)std::min<long>((total4 + 255) / 256, 8192));
+    ++g_launch_count[LC_WPACK_KMAJOR];
     FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kmajor_dense_kernel<T>, grid, dim3(256), 0, st, w, (T*)wp, m.rows, rows_pad, row_len, d.KK));
     return check_launch("pack_weights(k-major)");
   }
   if (kmajor_transposed_map(d, m)) {
     const dim3 grid((unsigned)((std::max(m.inner, d.Cp_in) + 63) / 64), (unsigned)((rows_pad + 63) / 64), (unsigned)(d.nth * d.ntw));
+    ++g_launch_count[LC_WPACK_KMAJOR_T];
     FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kmajor_transposed_kernel<T>, grid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(k-major transposed)");
   }
   if (dense_map(d, m)) {
     const dim3 dgrid((unsigned)((d.Cp_in + 63) / 64), (unsigned)((rows_pad + 3) / 4));
+    ++g_launch_count[LC_WPACK_DENSE];
     FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_dense_kernel<T>, dgrid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(dense)");
   }
   if (transposed_map(d, m)) {
     const dim3 tgrid((unsigned)((d.Cp_in + 63) / 64), (unsigned)((rows_pad + 15) / 16));
+    ++g_launch_count[LC_WPACK_TRANSPOSED];
     FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_transposed_kernel<T>, tgrid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
     return check_launch("pack_weights(transposed)");
   }
   const dim3 grid((unsigned)std::min((d.Cp_in + 63) / 64, 64), (unsigned)((rows_pad + 3) / 4));
+  ++g_launch_count[LC_WPACK_GENERIC];
   FOR_ELEM(dtype, T, hipLaunchKernelGGL(pack_kernel<T>, grid, dim3(64, 4), 0, st, d, m, w, (T*)wp, rows_pad));
   return check_launch("pack_weights");
 }
@@ -479,6 +485,7 @@ int launch_pack(const GDesc& d, const WMap& m, int dtype, const float* w, void* 
 int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, int rows_pad, float* scale2, unsigned* amax_bits,
                     hipStream_t st) {
   (void)hipMemsetAsync(amax_bits, 0, sizeof(unsigned), st);
+  ++g_launch_count[LC_WPACK_FP8];                                  // the quantiser with its amax and scale kernels: one family
   const long n = (long)m.rows * m.s_row;
   hipLaunchKernelGGL(amax_kernel, dim3((unsigned)std::max<long>(1, std::min<long>((n / 4 + 1023) / 1024, 2048))), dim3(256), 0, st, w, n, amax_bits);
   hipLaunchKernelGGL(fp8_scale_kernel, dim3(1), dim3(1), 0, st, amax_bits, scale2);

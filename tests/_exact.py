@@ -117,6 +117,15 @@ C7_OUT = [L("c7_48to2", 48, 2, 7, 1, 3, 1, 0, 0, (2, 16, 128)),
 FP8 = [L("trunk256", 256, 256, 3, 1, 1, 1, 0, 0, (2, 32, 16)),
        L("d256to512", 256, 512, 4, 1, 2, 0, 0, 0, (2, 17, 9))]
 
+# Small layers that reach the edges of the weight-pack kernels (csrc/wpack.hip; tests/test_gpu_wpack.py says which edge each one
+# is for).  The pack does not depend on the plane; these run forward and input gradient once on a pack into poisoned memory.
+WPACK = [L("wp_c72_k6", 72, 6, 3, 1, 1, 0, 0, 0, (1, 6, 5)),              # inner 72: a partly filled 64-column block; rows 6 / 72
+         L("wp_c2_k37_s2", 2, 37, 3, 2, 1, 0, 0, 0, (1, 9, 8)),           # C = 2: Cp = 8 > inner; rows 37; stride 2 keeps it off the W-fold
+         L("wp_c24_k7_2x2", 24, 7, 2, 1, 0, 0, 0, 0, (1, 6, 5)),          # 4 taps: a K tail behind taps * Cp
+         L("wp_c24_k72", 24, 72, 3, 1, 1, 1, 0, 0, (1, 5, 6)),            # input gradient: rows 24 = 1.5 bricks of 16, inner 72
+         L("wp_c5_k6_7x7", 5, 6, 7, 1, 3, 0, 0, 0, (1, 8, 9)),            # 49 taps, no W-fold (S * C = 35 > 32): the tap walk wraps its batches of 16
+         L("wp_kmajor_c64_k72", 64, 72, 3, 1, 1, 1, 0, 0, (1, 6, 5))]     # K-major eligible; K = 72 and rows_pad = 128 > C: tiles that hang over
+
 
 def at_batch(layer, n):
     return layer._replace(name=f"{layer.name}_n{n}", shape=(n,) + layer.shape[1:])
@@ -138,6 +147,7 @@ def case_table():
     t += [(l, ("fwd", "dgrad", "dgrad_add")) for l in DLAST]
     t += [(l, ("fwd", "dgrad")) for l in C7_OUT]
     t += [(l, ("fwd8",)) for l in FP8]
+    t += [(l, ("fwd", "dgrad")) for l in WPACK]
     return t
 
 

@@ -3,7 +3,9 @@
 Straight through the C ABI, one launch per check: operands are small integers chosen so that every partial sum is an integer
 the storage format holds, the expected output is that integer -- one bit pattern per element, pad channels included --, the
 output / workspace / gradient buffers sit between canaries, the workspace has exactly the size the library reports, and the
-launch counters prove which kernel family ran.  Where an option selects between a dedicated kernel and the path behind it,
+launch counters prove which kernel family ran.  The packed weights of every forward and input-gradient call come from the C
+entry, into a guarded buffer of exactly the reported size that held 0xFF (NaN in every float type, a non-zero e4m3 byte) before
+the pack: a launch that reads a byte the pack left unwritten cannot produce the integers.  Where an option selects between a dedicated kernel and the path behind it,
 both settings run: both equal the integers, hence each other.  InstanceNorm statistics and the fused backward sums are not
 exact; their bounds are derived in the helper."""
 import contextlib
@@ -14,6 +16,7 @@ import pytest
 import torch
 
 import _exact as X
+import _wpack as P
 
 pytestmark = pytest.mark.gpu
 
@@ -59,6 +62,15 @@ def _vp(g):
     return C.c_void_p(g.ptr())
 
 
+def _packed(ops, Lb, d, which, w, bufs):
+    """The layer's pack for the launch: p2phd_conv_pack_weights into a 0xFF-prefilled guarded buffer (which = "fp8": the e4m3
+    pack), entered into `bufs` so that its guards are checked with the others."""
+    g = P.pack_guarded_fp8(ops, Lb, d, w) if which == "fp8" else P.pack_guarded(ops, Lb, d, which, w)
+    X.check_guards({"packed": g}, f"pack_weights which={which}")
+    bufs["packed"] = g
+    return g
+
+
 def _check_stats(st, y_want, what):
     mean, m2, bm, b2 = X.stats_reference(y_want)
     K = y_want.shape[1]
@@ -82,16 +94,16 @@ def run_fwd(l, dt, act=NONE, stats=False, layout=0):
     if layout == 1:
         w = w.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)                       # K-major master weights
     b = o["b"].cuda()
-    wp = spec.packed(w, 0, d)
     ws = X.guarded(Lb.p2phd_conv_fwd_workspace_bytes(C.byref(d)))
     gy, y = X.guarded_like((N, Ho, Wo, X.cpitch(l.cout)), dtype)
     bufs = {"y": gy, "workspace": ws}
+    wp = _packed(ops, Lb, d, 0, w, bufs)
     st = None
     if stats:
         bufs["stats"], st = X.guarded_like((N, X.cpitch(l.cout), 2), torch.float32)
     what = f"fwd {l.name} {dt} act={act} stats={stats}"
     Lb.p2phd_launch_count(None, 1)
-    ops.check(Lb.p2phd_conv_fwd(C.byref(d), ops.ptr(x), ops.ptr(wp), ops.ptr(b), act, ops.ptr(y), ops.ptr(st), _vp(ws), ops.stream_ptr()), what)
+    ops.check(Lb.p2phd_conv_fwd(C.byref(d), ops.ptr(x), _vp(wp), ops.ptr(b), act, ops.ptr(y), ops.ptr(st), _vp(ws), ops.stream_ptr()), what)
     torch.cuda.synchronize()
     cnt = _count(Lb)
     X.check_guards(bufs, what)
@@ -114,11 +126,11 @@ def run_dgrad(l, dt, add=False, mode="plain", prev_act=RELU, layout=0):
     w = o["w"].cuda()
     if layout == 1:
         w = w.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)                       # K-major master weights
-    wp = spec.packed(w, 1, d)
     addend = X.to_nhwc(o["addend"], dtype).cuda() if add else None
     Cp = X.cpitch(l.cin)
     gx, dx = X.guarded_like((N, H, W, Cp), dtype)
     bufs = {"dx": gx}
+    wp = _packed(ops, Lb, d, 1, w, bufs)
     what = f"dgrad[{mode}] {l.name} {dt} addend={add}"
     want = o["want"]
     gen = torch.Generator().manual_seed(N * H + W)
@@ -126,13 +138,13 @@ def run_dgrad(l, dt, add=False, mode="plain", prev_act=RELU, layout=0):
     if mode == "plain":
         dy = dyh.cuda()
         ws = bufs["workspace"] = X.guarded(Lb.p2phd_conv_dgrad_workspace_bytes(C.byref(d)))
-        ops.check(Lb.p2phd_conv_dgrad(C.byref(d), ops.ptr(dy), ops.ptr(wp), ops.ptr(addend), ops.ptr(dx), _vp(ws), ops.stream_ptr()), what)
+        ops.check(Lb.p2phd_conv_dgrad(C.byref(d), ops.ptr(dy), _vp(wp), ops.ptr(addend), ops.ptr(dx), _vp(ws), ops.stream_ptr()), what)
     elif mode == "rx":
         ex = X.reflect_extras(dyh)                                                       # pair sums of integers: integers, exact in 16 bits
         n_rx = Lb.p2phd_conv_reflect_extras_elems(C.byref(d))
         assert n_rx == ex.numel() == N * (2 * (W + 2) + 2 * H) * X.cpitch(l.cout), (what, n_rx, ex.numel())
         dy = torch.cat([dyh.reshape(-1), ex.to(dtype).reshape(-1)]).cuda()
-        ops.check(Lb.p2phd_conv_dgrad_rx(C.byref(d), ops.ptr(dy), ops.ptr(wp), ops.ptr(addend), ops.ptr(dx), ops.stream_ptr()), what)
+        ops.check(Lb.p2phd_conv_dgrad_rx(C.byref(d), ops.ptr(dy), _vp(wp), ops.ptr(addend), ops.ptr(dx), ops.stream_ptr()), what)
     else:
         dy = dyh.cuda()
         assert Lb.p2phd_conv_dgrad_bsum_ok(C.byref(d)) == 1, what
@@ -140,7 +152,7 @@ def run_dgrad(l, dt, add=False, mode="plain", prev_act=RELU, layout=0):
         prev = X.int_tensor((N, l.cin, H, W), -3, 3, 0.8, gen)
         prev_p = X.to_nhwc(prev, dtype).cuda()
         if mode == "act":
-            ops.check(Lb.p2phd_conv_dgrad_act(C.byref(d), ops.ptr(dy), ops.ptr(wp), ops.ptr(addend), ops.ptr(dx), ops.ptr(prev_p), prev_act, _vp(ws),
+            ops.check(Lb.p2phd_conv_dgrad_act(C.byref(d), ops.ptr(dy), _vp(wp), ops.ptr(addend), ops.ptr(dx), ops.ptr(prev_p), prev_act, _vp(ws),
                                               ops.stream_ptr()), what)
         else:
             mean = X.int_tensor((N, l.cin), -1, 1, 0.5, gen)
@@ -149,7 +161,7 @@ def run_dgrad(l, dt, add=False, mode="plain", prev_act=RELU, layout=0):
             pst[:, :l.cin, 0], pst[:, :l.cin, 1] = mean, m2
             pst = pst.cuda()
             bufs["bstats"], bst = X.guarded_like((N, Cp, 2), torch.float32)
-            ops.check(Lb.p2phd_conv_dgrad_bsum(C.byref(d), ops.ptr(dy), ops.ptr(wp), ops.ptr(addend), ops.ptr(dx), ops.ptr(prev_p), ops.ptr(pst), prev_act,
+            ops.check(Lb.p2phd_conv_dgrad_bsum(C.byref(d), ops.ptr(dy), _vp(wp), ops.ptr(addend), ops.ptr(dx), ops.ptr(prev_p), ops.ptr(pst), prev_act,
                                                1e-5, ops.ptr(bst), _vp(ws), ops.stream_ptr()), what)
     torch.cuda.synchronize()
     cnt = _count(Lb)
@@ -441,18 +453,19 @@ def test_e4m3_forward(l):
     assert Lb.p2phd_conv_fp8_eligible(C.byref(d)) == 1
     Ho, Wo = spec.out_size(d)
     x8 = o["x"].to(torch.float8_e4m3fn).view(torch.uint8).permute(0, 2, 3, 1).contiguous().cuda()
-    wp8 = spec.packed_fp8(o["w"].cuda(), d)
+    packed = {}
+    wp8 = _packed(ops, Lb, d, "fp8", o["w"].cuda(), packed)
     b = o["b"].cuda()
     for stats in (False, True):
         ws = X.guarded(Lb.p2phd_conv_fwd_workspace_bytes(C.byref(d)))
         gy, y = X.guarded_like((N, Ho, Wo, X.cpitch(l.cout)), dtype)
-        bufs = {"y": gy, "workspace": ws}
+        bufs = {"y": gy, "workspace": ws, **packed}
         st = None
         if stats:
             bufs["stats"], st = X.guarded_like((N, X.cpitch(l.cout), 2), torch.float32)
         what = f"fwd_fp8 {l.name} stats={stats}"
         Lb.p2phd_launch_count(None, 1)
-        ops.check(Lb.p2phd_conv_fwd_fp8(C.byref(d), ops.ptr(x8), ops.ptr(wp8), ops.ptr(b), NONE, ops.ptr(y), ops.ptr(st), _vp(ws), ops.stream_ptr()), what)
+        ops.check(Lb.p2phd_conv_fwd_fp8(C.byref(d), ops.ptr(x8), _vp(wp8), ops.ptr(b), NONE, ops.ptr(y), ops.ptr(st), _vp(ws), ops.stream_ptr()), what)
         torch.cuda.synchronize()
         cnt = _count(Lb)
         X.check_guards(bufs, what)
