@@ -1,16 +1,17 @@
 """Whole-file generation: the folder pipeline of loudness_scope='folder' -- the folder is one programme (EBU R 128 album
 normalisation): one integrated loudness over the 400 ms blocks of every file, one loudness gain and one guard gain for all of them,
 so the level differences between the files survive.  Three phases: every file is generated and measured (A), the folder's figures
-are found and brought back behind one synchronisation (B), every file is encoded with the folder's gains and written (C)."""
+are found and brought back behind one synchronisation (B), every file is encoded with the folder's gains and written (C).
+What a file goes through in phase A is the per-file flow's own front and metrics stage, and its record is built and filled by the
+functions the per-file scope uses (generate/resolver.py); only what the folder has to itself is written here."""
 import math
-import os
-import struct
 
 import torch
 
 from .ops import (_loudness_views, _pcm_peaks_packed, _true_peaks_packed, loudness_blocks, loudness_gate, loudness_gate_blocks, loudness_hops,
                   pcm_encode)
-from .plans import LOUDNESS_MAX_CHANNELS, check_encoding, loudness_channel_weights, plan_folder, select_channels
+from .plans import loudness_channel_weights
+from .resolver import _set
 
 
 class _Blocks:
@@ -32,37 +33,12 @@ class _Blocks:
         return self.buf[:self.used]
 
 
-def _generate(sr, read, is_lr_input, channels, encoding, extended_metrics):
-    """The front of SuperResolver._enhance_payload: one file from its bytes to the generated clip and its metrics ->
-    (lr, the generated clip, metrics, metrics_ext, the input's WavInfo)."""
-    from ..data import audio_dataset                                        # (looked up per call: the tests replace lr_round_trip)
-    from ..util import util as U
-    o = sr.opt
-    host, meta, slot = read
-    check_encoding(encoding, "enhance_folder")
-    k = select_channels(channels, meta.num_channels)
-    if k > LOUDNESS_MAX_CHANNELS:
-        raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
-    rate = meta.sample_rate
-    raw = sr._decode(host, meta, slot)[:k]
-    lr = audio_dataset.lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
-    has_hr = not is_lr_input and int(rate) == int(o.hr_sampling_rate)
-    if has_hr:
-        lr = lr[..., :raw.shape[-1]]                                        # the round trip rounds the length up
-    out = sr.enhance_lr(lr)
-    metrics = ext = None
-    if has_hr and extended_metrics:
-        ext = U.compute_matrics_ext(raw, lr, out, o)
-        metrics = [(e['mse'], e['snr_sr'], e['snr_lr'], 0, 0, 0, e['lsd']) for e in ext]
-    elif has_hr:
-        metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], out[c:c + 1], o) for c in range(k)]
-    return lr, out, metrics, ext, meta
-
-
-def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album, dither_seed, plan=None, written=False, verify_input=False):
-    """enhance_folder with loudness_scope='folder' -> its records.  `sr`: the SuperResolver; `stage`, `tp`, `loud`: the validated
-    options as enhance_folder holds them; `album`: check_loudness_scope's result; `plan`: the folder's plan where the caller has made
-    it (None: plan_folder's default); `written`: a record gains 'written', the output's relative path; `verify_input`: enhance_file's, per FLAC file."""
+def enhance_album(sr, plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed, verify_input=False):
+    """enhance_folder with loudness_scope='folder' -> its records.  `sr`: the SuperResolver; `plan`: plan_folder's; `written_from`:
+    None, or the output folder where a record gains 'written'; `o`: the validated options as enhance_folder holds them, o.album
+    being check_loudness_scope's result; `verify_input`: enhance_file's, per FLAC file.  A file goes through the front and the
+    metrics stage of the per-file flow (SuperResolver._front, ._metrics) and leaves the record the per-file scope leaves."""
+    stage, tp, loud, album = o.stage, o.tp, o.loud, o.album
     rate = int(sr.opt.hr_sampling_rate)
     scaled = loud['mode'] != 'report'
     guard = stage is not None and stage['clip'] == 'guard'
@@ -70,40 +46,19 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
     entries, kept_bytes = [], 0
 
     # -- A: generate and measure every file; keep its clip ---------------------------------------------
-    for k, (rel, path_in, path_out) in enumerate(plan_folder(dir_in, dir_out) if plan is None else plan):
-        rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
-               'metrics': None, 'error': None}
-        if written:
-            rec['written'] = os.path.relpath(path_out, dir_out)
-        if extended_metrics:
-            rec['metrics_ext'] = None
-        if stage is not None:
-            rec['output'] = None
-        rec['loudness'] = rec['album'] = None
-        if getattr(sr, 'crossover_auto', False):                            # (without the option: no key more than before)
-            rec['crossover'] = None
-        if getattr(sr, 'norm_scope', 'group') == 'clip':
-            rec['norm'] = None
+    for k, (rel, path_in, path_out) in enumerate(plan):
+        rec = sr._blank_record(rel, path_out, written_from, extended_metrics, o)
         entry = {'rec': rec, 'k': k, 'path_out': path_out, 'clip': None}
         entries.append(entry)
-        try:
-            read = sr._read(path_in, verify=True) if verify_input else sr._read(path_in)
-            if getattr(sr, 'stereo', 'lr') == 'ms':                         # (more than two channels: a skipped file with its reason)
-                sr._check_stereo_channels(channels, read[1].num_channels)
-        except (ValueError, OSError, EOFError, struct.error) as e:
-            rec['error'] = '%s: %s' % (type(e).__name__, e)
+        read = sr._open(path_in, channels, verify_input, o, rec)
+        if read is None:
             continue
         if seed is not None:
             torch.manual_seed(int(seed))
-        lr, clip, metrics, ext, meta = _generate(sr, read, is_lr_input, channels, encoding, extended_metrics)
-        rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames, written_channels=clip.shape[0],
-                   out_frames=clip.shape[-1], metrics=metrics)
-        if extended_metrics:
-            rec['metrics_ext'] = ext
-        if getattr(sr, 'crossover_auto', False):
-            rec['crossover'] = dict(sr.last_crossover)
-        if getattr(sr, 'norm_scope', 'group') == 'clip':
-            rec['norm'] = sr.last_norm                                      # this file's ranges, [C, 2] on the device
+        f = sr._front(read, is_lr_input, channels, encoding, o, "enhance_folder")
+        sr._metrics(f, extended_metrics)
+        lr, clip = f.lr, f.clip
+        sr._fill_record(rec, {'info': f.meta, 'sr': clip, 'metrics': f.metrics, 'metrics_ext': f.ext, 'crossover': f.crossover, 'norm': f.norm})
         # the track's own figures, and its blocks into the folder's two buffers: six launches of the family "loudness"
         weights = loudness_channel_weights(clip.shape[0])
         track = entry['track'] = torch.empty((80,), dtype=torch.uint8, device=clip.device)
@@ -153,9 +108,8 @@ def enhance_album(sr, dir_in, dir_out, is_lr_input, channels, encoding, seed, re
     # -- C: clip 'error' for the whole folder first, then encode and write ------------------------------------
     for e in done:
         if stage is not None:
-            true_peak = None if tp is None else dict(tp, packed=e.pop('tpeaks'))
-            extra = {} if true_peak is None else {'true_peak': true_peak}
-            output = sr._output(e.pop('peaks'), e['rec']['written_channels'], stage, e['path_out'], encoding, **extra)
+            output = sr._output(e.pop('peaks'), e['rec']['written_channels'], stage, e['path_out'], encoding,
+                                **_set(true_peak=tp and dict(tp, packed=e.pop('tpeaks'))))
             output['gain'] = e.pop('guard') if guard else 1.0
             e['rec']['output'] = output
     records = []

@@ -579,7 +579,7 @@ def check_output_rate(output_rate, hr_rate, who="enhance_file", loudness_scope='
     """Validates the output-rate option for a model that generates at `hr_rate` -> None (off: `output_rate` is None or the model's
     rate, and nothing changes), or the option {'rate', 'model_rate', 'plan'}: `plan` is ops.rateconv_plan's dict for hr_rate ->
     output_rate with RATECONV_DEFAULTS.  `output_rate`: an int >= 8000 Hz.  Not built with `spectrogram` (the picture's panels share
-    one frequency axis) or loudness_scope 'folder' (generate/album.py keeps its own copy of the flow); rates between which the
+    one frequency axis) or loudness_scope 'folder' (generate/album.py runs the per-file flow up to the metrics only); rates between which the
     converter is not built are refused with p2phd_rateconv_plan's text.  A ValueError each, before a file is opened."""
     if output_rate is None:
         return None

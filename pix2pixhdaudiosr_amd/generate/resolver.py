@@ -2,6 +2,7 @@
 import math
 import os
 import struct
+from collections import namedtuple
 
 import torch
 
@@ -13,6 +14,34 @@ from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_st
 
 def _dbfs(level):
     return 20.0 * math.log10(level) if level > 0.0 else float('-inf')
+
+
+def _set(**keywords):
+    """Only what is set: the keywords that are not None, in the order given.  An option that is off never reaches a callee as a
+    keyword, so a callee that knows nothing of it (the stubs of the host tests, an override of before the option) is called as
+    it was before the option existed."""
+    return {k: v for k, v in keywords.items() if v is not None}
+
+
+# The validated options of enhance_file / enhance_folder (SuperResolver._options), each None where it is off: the output stage,
+# the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, and the album (loudness_scope 'folder').
+_Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album')
+
+# The keys a folder record may carry behind the eight it always has (and 'written'), in the record's order; each is also the key
+# of enhance_file's result that fills it ('album': enhance_album's own).
+_RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm')
+
+
+class _File:
+    """One file between the stages of the per-file flow: `clip` the generated clip as the latest stage left it, `lr` the clip the
+    generator was given, `hr` the original where the input is one (else None), `meta` the input's WavInfo / FlacInfo, `metrics` and
+    `ext` (None until the metrics stage, and without an original), `norm` and `crossover`: the object's last_norm and a copy of
+    its last_crossover behind this file's enhance_lr (None without norm_scope 'clip' / crossover_hz 'auto')."""
+    __slots__ = ('clip', 'lr', 'hr', 'meta', 'metrics', 'ext', 'norm', 'crossover')
+
+    def __init__(self, clip, lr, hr, meta, norm, crossover):
+        self.clip, self.lr, self.hr, self.meta, self.norm, self.crossover = clip, lr, hr, meta, norm, crossover
+        self.metrics = self.ext = None
 
 
 def first_channel_metrics(metrics, channels):
@@ -93,6 +122,9 @@ class SuperResolver:
     capture serves every clip.  A range of zero scales by 0: a clip of digital silence is written as silence.  The launches are
     those of the family "normscope": ceil(S / batch) range calls and one noise fold per clip, one encode per group.
     `last_norm` then holds the [C, 2] tensor on the GPU of the latest call's (min, max) per clip, in dB."""
+
+    # what an object built without __init__ (the stubs of the host tests) runs with: every option of the constructor off
+    stereo, norm_scope, crossover_auto, last_norm, last_crossover = 'lr', 'group', False, None, None
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
                  lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr', norm_scope='group'):
@@ -239,7 +271,7 @@ class SuperResolver:
         x = x.contiguous()
         C, L = x.shape
         S, stride, V = segment_plan(L, self.T, self.overlap)
-        ms = getattr(self, 'stereo', 'lr') == 'ms' and C != 1               # (one channel runs as ever, with no launch of the family)
+        ms = self.stereo == 'ms' and C != 1               # (one channel runs as ever, with no launch of the family)
         if ms and C != 2:
             raise ValueError("enhance_lr: stereo='ms' takes one or two channels, got %d" % C)
         measured = None
@@ -254,7 +286,7 @@ class SuperResolver:
             x = stereo_matrix(x, 0.5)
         seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
-        by_clip = getattr(self, 'norm_scope', 'group') == 'clip'             # (an object built without __init__ runs as ever)
+        by_clip = self.norm_scope == 'clip'
         if by_clip:
             self.last_norm = torch.empty((C, 2), dtype=torch.float32, device=self.device)
             if S == 0:                                                      # (no segment, no range: the empty fold)
@@ -401,31 +433,24 @@ class SuperResolver:
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
     def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None):
-        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload.  `stage`: the output-stage options
-        (check_output_options), or None for the encoder alone.  `picture`: the rendered spectrogram (_render_picture) to bring
-        back with them, see _fetch; `loudness`: the loudness measurement (_measure_loudness), likewise.  With a stage the peak kernel runs in front of the encoder,
-        which for clip 'guard' reads the gain from device memory, and the figures come back with the payload behind the
-        one synchronisation; they are returned as the result's 'output'.  path_out None: the figures only.  `true_peak`: the
-        true-peak option (check_true_peak; it comes with a stage): the true-peak kernel runs behind the peak kernel, on the same
-        clip, clip 'guard' takes its gain from it, and its figures come back likewise.  `limiter`: the limiter option
-        (_limiter_option; it comes with a stage and the true-peak option): the limiter runs in front of the peak kernel, everything
-        behind it sees the limited clip, and its figures come back likewise.  `bandwidth`: the bandwidth measurement
-        (_measure_bandwidth), whose packed results come back likewise; `stereo`: the stereo measurement (_measure_stereo), likewise.
-        `rate`: the rate the header states where it is not the model's (the output-rate option: `sr` is the converted clip)."""
+        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload; -> the result's 'output', or None
+        without a stage.  path_out None: the figures only.  `stage`: the output-stage options (check_output_options), or None for
+        the encoder alone.  Every other keyword is None or what one option of enhance_file brings, and a caller passes only those
+        that are set (_set):
+          true_peak, limiter   the option's own dict, one file's (check_true_peak, _limiter_option; either comes with a stage):
+                               _encode runs its kernels and leaves their packed figures in it, _output reads them
+          loudness, bandwidth, stereo   the measurement the per-file flow has already queued (_measure_*), a dict with 'packed'
+          picture              the rendered spectrogram (_render_picture)
+          rate                 the rate the header states where it is not the model's (the output-rate option: `sr` is converted)
+        The first six come back with the payload and the peak figures behind _fetch's one synchronisation."""
         w = sr.contiguous()
-        extra = {} if true_peak is None else {'true_peak': true_peak}
-        if limiter is not None:
-            extra['limiter'] = limiter
-        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **extra)
-        fetch = extra if loudness is None else dict(extra, loudness=loudness)
-        if bandwidth is not None:
-            fetch = dict(fetch, bandwidth=bandwidth)
-        if stereo is not None:
-            fetch = dict(fetch, stereo=stereo)
-        host, stats = self._fetch(dev, packed, picture, **fetch)
-        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **extra)
+        option = _set(true_peak=true_peak, limiter=limiter)
+        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **option)
+        host, stats = self._fetch(dev, packed, **_set(stereo=stereo, bandwidth=bandwidth, limiter=limiter, true_peak=true_peak, loudness=loudness,
+                                                      picture=picture))
+        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **option)
         if host is not None:
-            self._save(path_out, host, sr.shape[0], encoding, **({} if rate is None else {'rate': rate}))
+            self._save(path_out, host, sr.shape[0], encoding, **_set(rate=rate))
         return output
 
     def _encode(self, w, wanted, encoding, stage, true_peak=None, limiter=None):
@@ -448,44 +473,22 @@ class SuperResolver:
         return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed'],
                           curve=stage.get('curve'), chunk=stage.get('chunk')), packed
 
-    def _fetch(self, dev, packed, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None):
-        """The payload and the packed peak buffer (either may be None) into their pinned buffers behind one synchronisation
-        -> (the payload, the peak buffer) on the host.  `picture`: None, or a dict whose 'image' and 'top' (device tensors) are
-        copied behind the same synchronisation and replaced by their host copies.  `loudness`: None, or a dict whose 'packed'
-        (the two gate results, a device tensor) is copied and replaced likewise; `true_peak`: None, or a dict whose 'packed' (the
-        packed true-peak buffer) is, into a pinned slot of its own; `limiter`: None, or a dict whose 'packed' (the limiter's 12
-        bytes) is, into another; `bandwidth`: None, or a dict whose 'packed' (the clips' 32-byte results) is, into another; `stereo`:
-        None, or a dict whose 'packed' (the clips' 64-byte results) is, into another."""
+    def _fetch(self, dev, packed, picture=None, **measured):
+        """The payload and the packed peak buffer (either may be None) into their pinned buffers 'out' and 'peaks' behind one
+        synchronisation -> (the payload, the peak buffer) on the host.  `measured`: name -> a dict whose 'packed' (a device tensor:
+        the figures of 'stereo', 'bandwidth', 'limiter', 'true_peak', 'loudness') is copied into the pinned buffer of that name in
+        front of them, in the order given, and replaced by its host copy.  `picture`: None, or a dict whose 'image' and 'top' are
+        copied and replaced likewise, into one buffer: the top's four bytes, then the pixels."""
         host = stats = None
-        if stereo is not None:
-            n = stereo['packed'].numel()
-            pin = self._pinned('stereo', n)[:n]
-            pin.copy_(stereo['packed'], non_blocking=True)
-            stereo['packed'] = pin
-        if bandwidth is not None:
-            n = bandwidth['packed'].numel()
-            pin = self._pinned('bandwidth', n)[:n]
-            pin.copy_(bandwidth['packed'], non_blocking=True)
-            bandwidth['packed'] = pin
-        if limiter is not None:
-            n = limiter['packed'].numel()
-            pin = self._pinned('limiter', n)[:n]
-            pin.copy_(limiter['packed'], non_blocking=True)
-            limiter['packed'] = pin
-        if true_peak is not None:
-            n = true_peak['packed'].numel()
-            pin = self._pinned('true_peak', n)[:n]
-            pin.copy_(true_peak['packed'], non_blocking=True)
-            true_peak['packed'] = pin
-        if loudness is not None:
-            n = loudness['packed'].numel()
-            pin = self._pinned('loudness', n)[:n]
-            pin.copy_(loudness['packed'], non_blocking=True)
-            loudness['packed'] = pin
+        for name, m in measured.items():
+            n = m['packed'].numel()
+            pin = self._pinned(name, n)[:n]
+            pin.copy_(m['packed'], non_blocking=True)
+            m['packed'] = pin
         if picture is not None:
             img, top = picture['image'], picture['top']
             n = img.numel()
-            pin = self._pinned('picture', 4 + n)                           # the top's four bytes, then the pixels
+            pin = self._pinned('picture', 4 + n)
             pin[:4].copy_(top.view(torch.uint8), non_blocking=True)
             pin[4:4 + n].copy_(img.reshape(-1), non_blocking=True)
             picture['image'], picture['top'] = pin[4:4 + n].view(img.shape), pin[:4].view(torch.float32)
@@ -644,14 +647,14 @@ class SuperResolver:
     def _stereo_result(self, st, measure):
         """The fetched measurement -> the result's 'stereo'."""
         figures = [stereo_figures(measure['packed'][64 * i:64 * i + 64].view(torch.float64).tolist()) for i in range(measure['clips'])] + [None]
-        mode = getattr(self, 'stereo', 'lr')
+        mode = self.stereo
         k = stereo_split_bin(self.opt.hr_sampling_rate, self.opt.lr_sampling_rate, st['n_fft'])
         return {'input': figures[0], 'output': figures[1], 'original': figures[2], 'split_hz': k * float(self.opt.hr_sampling_rate) / st['n_fft'],
                 'n_fft': st['n_fft'], 'hop': st['hop'], 'frames': measure['frames'], 'mode': mode, 'notes': stereo_notes(figures[1], mode)}
 
     def _check_stereo_channels(self, channels, available):
         """stereo='ms' generates one or two channels: a file of which more would be written is refused before anything runs."""
-        if getattr(self, 'stereo', 'lr') == 'ms' and select_channels(channels, available) > 2:
+        if self.stereo == 'ms' and select_channels(channels, available) > 2:
             raise ValueError("stereo='ms' takes one or two channels, %d would be written" % select_channels(channels, available))
 
     @staticmethod
@@ -672,89 +675,150 @@ class SuperResolver:
         K-weighting entry takes."""
         return loud if loud is None or rc is None else dict(loud, out_rate=check_loudness_rate(rc['rate'], who))
 
-    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics=False, stage=None, spec=None, loud=None, tp=None,
-                         lim=None, bw=None, st=None, rc=None):
-        """One file from its bytes to the written output -> enhance_file's result, with 'metrics' in one shape: a list with one
-        7-tuple per written channel, or None.  `spec`: None, or the spectrogram option {'path', 'channel', 'top_db', 'plan'}.
-        `loud`: None, or the loudness option (check_loudness).  `tp`: None, or the true-peak option (check_true_peak).  `lim`: None,
-    or the limiter option (_limiter_option).  `bw`: None, or the bandwidth option (check_bandwidth).  `st`: None, or the stereo
-        report option (check_stereo_report).  `rc`: None, or the output-rate option (check_output_rate)."""
+    def _options(self, who, folder, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
+                 spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
+                 loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
+                 album_cache_bytes=None):
+        """The options of enhance_file (`folder` False) / enhance_folder (True), validated before a file is opened -> _Options.
+        The order of the checks decides which ValueError a bad combination raises first: it does not move."""
+        hr_rate = self.opt.hr_sampling_rate
+        bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, who)
+        st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, who)
+        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, who, dither_curve, dither_chunk)
+        rc, out_rate = self._output_rate_option(output_rate, who, loudness_scope, spectrogram)
+        check_dither(dither, encoding, who, out_rate, dither_curve, dither_chunk)
+        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, who)
+        spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, who)
+        loud = self._loudness_at(check_loudness(loudness, hr_rate, who, loudness_max_gain_db, loudness_range), rc, who)
+        album = check_loudness_scope(loudness_scope, loud, who, folder, limiter, spectrogram, album_cache_bytes)
+        return _Options(stage, tp, lim, spec, loud, bw, st, rc, album)
+
+    # -- one file: the stages of the flow, in the order their launches take on the stream ------------------------------
+    def _front(self, read, is_lr_input, channels, encoding, o, who):
+        """(a) What _read returned -> the checks that need the file's header, decode, the low-rate round trip, enhance_lr ->
+        the _File.  `who`: "enhance_file" on the per-file path, also from a folder; "enhance_folder" from the album."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
-        from ..util import util as U
-        o = self.opt
         host, meta, slot = read
-        check_encoding(encoding, "enhance_file")
+        check_encoding(encoding, who)
         k = select_channels(channels, meta.num_channels)
-        self._check_picture_channel(spec, channels, meta.num_channels)
+        self._check_picture_channel(o.spec, channels, meta.num_channels)
         self._check_stereo_channels(channels, meta.num_channels)
-        if loud is not None and k > LOUDNESS_MAX_CHANNELS:
+        if o.loud is not None and k > LOUDNESS_MAX_CHANNELS:
             raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
         rate = meta.sample_rate
         raw = self._decode(host, meta, slot)[:k]
-        lr = audio_dataset.lr_round_trip(raw, rate, o.lr_sampling_rate, o.hr_sampling_rate, is_lr_input)
-        has_hr = not is_lr_input and int(rate) == int(o.hr_sampling_rate)
+        lr = audio_dataset.lr_round_trip(raw, rate, self.opt.lr_sampling_rate, self.opt.hr_sampling_rate, is_lr_input)
+        has_hr = not is_lr_input and int(rate) == int(self.opt.hr_sampling_rate)
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
-        sr = self.enhance_lr(lr)
-        norm = getattr(self, 'last_norm', None)                             # norm_scope 'clip': this file's ranges, on the device
-        # the generated clip behind the crossover and in front of the loudness gain: the figure is relative, a gain does not move it
-        band = None if bw is None else self._measure_bandwidth(bw, lr, sr, raw if has_hr else None)
-        # likewise behind the crossover and the mid/side decode; a file written with another channel count has no stereo image
-        image = None if st is None or sr.shape[0] != 2 else self._measure_stereo(st, lr, sr, raw if has_hr else None)
-        auto = getattr(self, 'crossover_auto', False)                       # (an object built without __init__ has no crossover at all)
-        xover = dict(self.last_crossover) if auto else None
-        metrics = ext = None
-        if has_hr and extended_metrics:
-            # every written channel in one call and one copy back; the 7-tuples are read off the same rows
-            ext = U.compute_matrics_ext(raw, lr, sr, o)
-            metrics = [(e['mse'], e['snr_sr'], e['snr_lr'], 0, 0, 0, e['lsd']) for e in ext]
-        elif has_hr:
-            metrics = [U.compute_matrics(raw[c:c + 1], lr[c:c + 1], sr[c:c + 1], o) for c in range(k)]
+        clip = self.enhance_lr(lr)
+        # norm_scope 'clip': this file's ranges, on the device; crossover_hz 'auto': the crossover this file got
+        return _File(clip, lr, raw if has_hr else None, meta, self.last_norm, dict(self.last_crossover) if self.crossover_auto else None)
+
+    def _reports(self, f, o):
+        """(b) The bandwidth and the stereo measurement -> (band, image), None where off.  Both see the generated clip behind the
+        crossover and the mid/side decode and in front of the loudness gain: the figures are relative, a gain does not move them.
+        A file written with another channel count than two has no stereo image."""
+        band = None if o.bw is None else self._measure_bandwidth(o.bw, f.lr, f.clip, f.hr)
+        image = None if o.st is None or f.clip.shape[0] != 2 else self._measure_stereo(o.st, f.lr, f.clip, f.hr)
+        return band, image
+
+    def _metrics(self, f, extended_metrics):
+        """(c) Where the input is a full-band original: f.metrics, one 7-tuple per written channel, and with `extended_metrics`
+        f.ext -- every written channel in one call and one copy back, the 7-tuples read off the same rows."""
+        from ..util import util as U
+        if f.hr is not None and extended_metrics:
+            f.ext = U.compute_matrics_ext(f.hr, f.lr, f.clip, self.opt)
+            f.metrics = [(e['mse'], e['snr_sr'], e['snr_lr'], 0, 0, 0, e['lsd']) for e in f.ext]
+        elif f.hr is not None:
+            f.metrics = [U.compute_matrics(f.hr[c:c + 1], f.lr[c:c + 1], f.clip[c:c + 1], self.opt) for c in range(f.hr.shape[0])]
+
+    def _level(self, f, o):
+        """(d) The output rate, then the loudness measurement and its gain on f.clip -> the measurement, or None.  The converter
+        (one launch of the family "rateconv") sits behind everything that compares the generated clip with the input and the
+        original at the model's rate; the loudness stage behind the metrics, which moment-match and stay those of the unscaled
+        clip.  Both sit in front of everything that sees the written level."""
+        if o.rc is not None:
+            f.clip = rate_convert(f.clip, o.rc['model_rate'], o.rc['rate'], o.rc['plan'])
+        if o.loud is None:
+            return None
+        measure = self._measure_loudness(o.loud, f.lr, f.clip)
+        if o.loud['mode'] != 'report':
+            f.clip = f.clip * measure['gain']
+        return measure
+
+    def _deliver(self, f, path_out, encoding, extended_metrics, o, band, image, measure, picture):
+        """(f) _write -- the output stage, the encoder, the one synchronisation and the file -- where there is anything to encode
+        or to bring back, then enhance_file's result."""
         output = None
-        measure = None
-        if rc is not None:
-            # behind everything that compares the generated clip with the input and the original at the model's rate; in front of
-            # the loudness, peak and limiter stages, which measure and hold what is written.  One launch of the family "rateconv"
-            sr = rate_convert(sr, rc['model_rate'], rc['rate'], rc['plan'])
-        if loud is not None:
-            # behind the metrics, which moment-match and stay those of the unscaled clip; in front of everything that sees the written level
-            measure = self._measure_loudness(loud, lr, sr)
-            if loud['mode'] != 'report':
-                sr = sr * measure['gain']
-        picture = None if spec is None else self._render_picture(spec, lr, sr, raw if has_hr else None)
-        if path_out is not None or stage is not None or picture is not None or measure is not None or band is not None or image is not None:
-            extra = {} if measure is None else {'loudness': measure}
-            if image is not None:
-                extra['stereo'] = image
-            if band is not None:
-                extra['bandwidth'] = band
-            if tp is not None:
-                extra['true_peak'] = dict(tp)                              # (one file's: it takes the file's buffers)
-            if lim is not None:
-                extra['limiter'] = dict(lim)
-            if rc is not None:
-                extra['rate'] = rc['rate']
-            output = self._write(path_out, sr, encoding, stage, **extra) if picture is None else self._write(path_out, sr, encoding, stage, picture, **extra)
-        res = {'sr': sr, 'lr': lr, 'hr': raw if has_hr else None, 'metrics': metrics, 'info': meta}
-        if getattr(self, 'norm_scope', 'group') == 'clip':                  # (without the option: no key more than before)
-            res['norm'] = norm
+        if path_out is not None or o.stage is not None or any(m is not None for m in (picture, measure, band, image)):
+            output = self._write(path_out, f.clip, encoding, o.stage, **_set(
+                picture=picture, loudness=measure, stereo=image, bandwidth=band,
+                true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
+                rate=o.rc and o.rc['rate']))
+        res = {'sr': f.clip, 'lr': f.lr, 'hr': f.hr, 'metrics': f.metrics, 'info': f.meta}
+        if self.norm_scope == 'clip':                                       # (without the option: no key more than before)
+            res['norm'] = f.norm
         if picture is not None:
-            res['spectrogram'] = self._save_picture(spec, picture)
+            res['spectrogram'] = self._save_picture(o.spec, picture)
         if measure is not None:
-            res['loudness'] = self._loudness_result(loud, measure)
+            res['loudness'] = self._loudness_result(o.loud, measure)
         if band is not None:
-            res['bandwidth'] = self._bandwidth_result(bw, band)
-        if xover is not None:
-            res['crossover'] = xover
-        if st is not None:
-            res['stereo'] = None if image is None else self._stereo_result(st, image)
-        if rc is not None:
-            res['output_rate'] = self._output_rate_result(rc)
+            res['bandwidth'] = self._bandwidth_result(o.bw, band)
+        if f.crossover is not None:
+            res['crossover'] = f.crossover
+        if o.st is not None:
+            res['stereo'] = None if image is None else self._stereo_result(o.st, image)
+        if o.rc is not None:
+            res['output_rate'] = self._output_rate_result(o.rc)
         if extended_metrics:
-            res['metrics_ext'] = ext
-        if stage is not None:
+            res['metrics_ext'] = f.ext
+        if o.stage is not None:
             res['output'] = output
         return res
+
+    def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics, o):
+        """One file from its bytes (what _read returned) to the written output -> enhance_file's result, with 'metrics' in one
+        shape: a list with one 7-tuple per written channel, or None.  `o`: the _Options, its stage and spectrogram this file's."""
+        f = self._front(read, is_lr_input, channels, encoding, o, "enhance_file")
+        band, image = self._reports(f, o)
+        self._metrics(f, extended_metrics)
+        measure = self._level(f, o)
+        picture = None if o.spec is None else self._render_picture(o.spec, f.lr, f.clip, f.hr)       # (e)
+        return self._deliver(f, path_out, encoding, extended_metrics, o, band, image, measure, picture)
+
+    # -- a folder: what both loudness scopes share ---------------------------------------------------------------
+    def _blank_record(self, rel, path_out, written_from, extended_metrics, o):
+        """The record of a file that nothing is known of yet: the eight keys every record has, 'written' (with input_formats: the
+        output's path relative to the folder `written_from`; None: no such key), and one key of _RECORD_KEYS, None, per option
+        that is on."""
+        rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0, 'metrics': None, 'error': None}
+        if written_from is not None:
+            rec['written'] = os.path.relpath(path_out, written_from)
+        present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None,
+                       album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto, stereo=o.st is not None,
+                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip')
+        rec.update((key, None) for key in _RECORD_KEYS if present[key])
+        return rec
+
+    @staticmethod
+    def _fill_record(rec, res):
+        """The record of an enhanced file <- enhance_file's result, or as much of one as there is (the album's phase A)."""
+        meta = res['info']
+        rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames, written_channels=res['sr'].shape[0],
+                   out_frames=res['sr'].shape[-1], metrics=res['metrics'])
+        rec.update((key, res[key]) for key in _RECORD_KEYS if key in rec and key in res)
+
+    def _open(self, path_in, channels, verify_input, o, rec):
+        """_read and the checks that make a skipped file -> what _read returned, or None with the reason in rec['error']."""
+        try:
+            read = self._read(path_in, **_set(verify=True if verify_input else None))
+            self._check_picture_channel(o.spec, channels, read[1].num_channels)
+            self._check_stereo_channels(channels, read[1].num_channels)
+            return read
+        except (ValueError, OSError, EOFError, struct.error) as e:
+            rec['error'] = '%s: %s' % (type(e).__name__, e)
+            return None
 
     def enhance_file(self, path_in, path_out=None, is_lr_input=False, channels='first', encoding='pcm16', extended_metrics=False,
                      clip='clamp', ceiling_dbfs=None, dither=None, dither_seed=0, report_peaks=False, spectrogram=None,
@@ -876,29 +940,11 @@ class SuperResolver:
         {'rate', 'model_rate', 'o', 'n' (the two rates over their common divisor), 'taps_per_phase', 'passband_hz', 'stopband_hz',
         'atten_db'}.  Not built with `spectrogram` or loudness_scope 'folder'; rates between which the filter is not built (48000 ->
         8000, or a pair with a tiny common divisor) are refused: a ValueError each, before the file is opened."""
-        bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_file")
-        st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_file")
-        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, dither_curve=dither_curve, dither_chunk=dither_chunk)
-        rc, out_rate = self._output_rate_option(output_rate, "enhance_file", loudness_scope, spectrogram)
-        check_dither(dither, encoding, "enhance_file", out_rate, dither_curve, dither_chunk)
-        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_file")
-        spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_file")
-        loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_file", loudness_max_gain_db, loudness_range), rc, "enhance_file")
-        check_loudness_scope(loudness_scope, loud, "enhance_file", folder=False)
-        extra = {} if tp is None else {'tp': tp}
-        if rc is not None:
-            extra['rc'] = rc
-        if lim is not None:
-            extra['lim'] = lim
-        if bw is not None:
-            extra['bw'] = bw
-        if st is not None:
-            extra['st'] = st
-        read = self._read(path_in, verify=True) if verify_input else self._read(path_in)
-        if loud is None:
-            res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, **extra)
-        else:
-            res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, stage, spec, loud, **extra)
+        o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
+                          spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
+                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk)
+        read = self._read(path_in, **_set(verify=True if verify_input else None))
+        res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
 
@@ -973,89 +1019,25 @@ class SuperResolver:
         `formats`): x.flac is written as x.wav, a record then gains 'written' (the output's relative path), and two inputs that would
         be written to one path are a ValueError before any file is opened.  `verify_input`: enhance_file's, per FLAC file; a mismatch
         is a skipped file.  Both hold in either loudness scope."""
-        bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, "enhance_folder")
-        st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, "enhance_folder")
-        stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, "enhance_folder", dither_curve, dither_chunk)
-        rc, out_rate = self._output_rate_option(output_rate, "enhance_folder", loudness_scope, spectrogram)
-        check_dither(dither, encoding, "enhance_folder", out_rate, dither_curve, dither_chunk)
-        stage, tp, lim = self._limiter_option(limiter, limiter_lookahead_ms, limiter_hold_ms, true_peak, stage, encoding, out_rate, "enhance_folder")
-        spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, "enhance_folder")
-        loud = self._loudness_at(check_loudness(loudness, self.opt.hr_sampling_rate, "enhance_folder", loudness_max_gain_db, loudness_range), rc, "enhance_folder")
-        album = check_loudness_scope(loudness_scope, loud, "enhance_folder", True, limiter, spectrogram, album_cache_bytes)
-        plan = plan_folder(dir_in, dir_out) if input_formats is None else plan_folder(dir_in, dir_out, input_formats)
-        if album is not None:
+        o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
+                          spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
+                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
+                          album_cache_bytes)
+        plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats))
+        written_from = None if input_formats is None else dir_out          # a record then says where its file was written
+        if o.album is not None:
             from .album import enhance_album
-            return enhance_album(self, dir_in, dir_out, is_lr_input, channels, encoding, seed, report, extended_metrics, stage, tp, loud, album,
-                                 dither_seed, plan=plan, written=input_formats is not None, verify_input=verify_input)
-        extra = {} if loud is None else {'loud': loud}
-        if tp is not None:
-            extra['tp'] = tp
-        if lim is not None:
-            extra['lim'] = lim
-        if bw is not None:
-            extra['bw'] = bw
-        if st is not None:
-            extra['st'] = st
-        if rc is not None:
-            extra['rc'] = rc
+            return enhance_album(self, plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed, verify_input)
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan):
-            rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0,
-                   'metrics': None, 'error': None}
-            if input_formats is not None:
-                rec['written'] = os.path.relpath(path_out, dir_out)
-            if extended_metrics:
-                rec['metrics_ext'] = None
-            if stage is not None:
-                rec['output'] = None
-            if spec is not None:
-                rec['spectrogram'] = None
-            if loud is not None:
-                rec['loudness'] = None
-            if bw is not None:
-                rec['bandwidth'] = None
-            if getattr(self, 'crossover_auto', False):
-                rec['crossover'] = None
-            if st is not None:
-                rec['stereo'] = None
-            if rc is not None:
-                rec['output_rate'] = None
-            if getattr(self, 'norm_scope', 'group') == 'clip':
-                rec['norm'] = None
-            try:
-                read = self._read(path_in, verify=True) if verify_input else self._read(path_in)
-                self._check_picture_channel(spec, channels, read[1].num_channels)
-                self._check_stereo_channels(channels, read[1].num_channels)
-            except (ValueError, OSError, EOFError, struct.error) as e:
-                rec['error'] = '%s: %s' % (type(e).__name__, e)
-            else:
+            rec = self._blank_record(rel, path_out, written_from, extended_metrics, o)
+            read = self._open(path_in, channels, verify_input, o, rec)
+            if read is not None:
                 if seed is not None:
                     torch.manual_seed(int(seed))
-                res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics,
-                                            None if stage is None else dict(stage, seed=dither_seed + k),
-                                            None if spec is None else dict(spec, path=os.path.join(spec['path'], rel + '.png')), **extra)
-                meta = res['info']
-                rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames,
-                           written_channels=res['sr'].shape[0], out_frames=res['sr'].shape[-1],
-                           metrics=res['metrics'])
-                if extended_metrics:
-                    rec['metrics_ext'] = res['metrics_ext']
-                if stage is not None:
-                    rec['output'] = res['output']
-                if spec is not None:
-                    rec['spectrogram'] = res['spectrogram']
-                if loud is not None:
-                    rec['loudness'] = res['loudness']
-                if bw is not None:
-                    rec['bandwidth'] = res['bandwidth']
-                if 'crossover' in res:
-                    rec['crossover'] = res['crossover']
-                if st is not None:
-                    rec['stereo'] = res['stereo']
-                if rc is not None:
-                    rec['output_rate'] = res['output_rate']
-                if 'norm' in res:
-                    rec['norm'] = res['norm']
+                mine = o._replace(stage=o.stage and dict(o.stage, seed=dither_seed + k),
+                                  spec=o.spec and dict(o.spec, path=os.path.join(o.spec['path'], rel + '.png')))
+                self._fill_record(rec, self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, mine))
             records.append(rec)
             if report is not None:
                 report(rec)

@@ -315,6 +315,47 @@ def test_skipped_files_and_an_empty_folder(resolver, files, album, tmp_path):
     assert _run(resolver, empty, tmp_path / "none", loudness=-23.0, loudness_scope='folder') == [] and _count() == 0
 
 
+def _both_scopes(sr, src, dst):
+    kw = dict(loudness=-23.0, extended_metrics=True, input_formats=('wav',))
+    return _run(sr, src, dst / "file", **kw), _run(sr, src, dst / "folder", loudness_scope='folder', **kw)
+
+
+def test_both_scopes_leave_the_same_record_of_a_file(one_file, tmp_path):
+    """Everything a record carries in either scope -- the metrics, the clip's crossover and normalisation ranges, the written path --
+    is the same at scope 'file' and at scope 'folder', key for key and in the same order, for an enhanced file and for a skipped one."""
+    import shutil
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    model, opt = _tiny()
+    sr = SuperResolver(model, opt, crossover='input', crossover_hz='auto', norm_scope='clip')
+
+    def same(file_rec, folder_rec):
+        assert [k for k in folder_rec if k != 'album'] == list(file_rec) and 'album' in folder_rec
+        assert {'metrics_ext', 'loudness', 'crossover', 'written', 'norm'} <= set(file_rec)
+
+    a, b = _both_scopes(sr, one_file, tmp_path / "one")
+    assert len(a) == len(b) == 1 and a[0]['error'] is None and b[0]['error'] is None
+    same(a[0], b[0])
+    for key in ('metrics', 'metrics_ext', 'crossover', 'written'):
+        assert a[0][key] is not None and b[0][key] == a[0][key], key
+    assert a[0]['norm'].shape == (2, 2) and torch.equal(b[0]['norm'], a[0]['norm'])
+    assert _same_files(tmp_path / "one" / "file", tmp_path / "one" / "folder", ("only.wav",))
+    # beside a file of garbage bytes: the skipped record has the same keys in both scopes, and the enhanced file does not move
+    src = tmp_path / "in"
+    shutil.copytree(str(one_file), str(src))
+    (src / "broken.wav").write_bytes(b"RIFF not a wav file at all")
+    c, d = _both_scopes(sr, src, tmp_path / "two")
+    assert [r['path'] for r in c] == [r['path'] for r in d] == ["broken.wav", "only.wav"]
+    same(c[0], d[0])
+    same(c[1], d[1])
+    assert c[0]['error'] is not None and d[0]['error'] == c[0]['error'] and d[0]['album'] is None
+    assert {k: v for k, v in d[0].items() if k != 'album'} == c[0]
+    for key in ('metrics', 'metrics_ext', 'crossover', 'written'):
+        assert d[1][key] == c[1][key] == a[0][key], key
+    assert torch.equal(d[1]['norm'], c[1]['norm']) and torch.equal(c[1]['norm'], a[0]['norm'])
+    assert _same_files(tmp_path / "two" / "file", tmp_path / "two" / "folder", ("only.wav",))
+    assert _bytes(str(tmp_path / "two" / "file" / "only.wav")) == _bytes(str(tmp_path / "one" / "file" / "only.wav"))
+
+
 def test_dither_takes_the_seed_of_the_files_place_in_the_plan(resolver, files, tmp_path):
     """pcm16 with dither: file k is dithered with seed + k, as the per-file scope does it -- a one-file folder holding the plan's
     third file, dithered with seed + 2, is that file of the three-file run when both get the same gains ('report', clamp)."""
