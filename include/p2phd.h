@@ -98,7 +98,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * stereo='ms', csrc/stereo.hip), "rateconv" (the rate converter of its output stage, csrc/rateconv.hip), "normscope" (the range
  * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything),
  * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip), "flac" (the two kernels of its FLAC input,
- * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), and the weight packs of p2phd_conv_pack_weights /
+ * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), "flacenc" (the three kernels of its FLAC output, csrc/flacenc.hip:
+ * a p2phd_flac_encode counts 3), and the weight packs of p2phd_conv_pack_weights /
  * p2phd_conv_fp8_pack_weights, one family per kernel of csrc/wpack.hip, counted per launch plan: "wpack_generic" (the tap walk),
  * "wpack_dense", "wpack_transposed" (the two LDS re-orderings), "wpack_kmajor" (cast of K-major master weights), "wpack_kmajor_t"
  * (their per-tap transpose), "wpack_merged" (merged sub-pixel launches, either tap order), "wpack_fp8" (the e4m3 quantiser with
@@ -728,6 +729,68 @@ int p2phd_flac_decode(const void* bytes_dev, int64_t nbytes, const int64_t* tabl
  * out is not written) or the element-wise kernel alone (stage 2: it reads whatever the workspace holds).  Counts 1. */
 int p2phd_flac_decode_stage(int stage, const void* bytes_dev, int64_t nbytes, const int64_t* table_dev, int64_t nframes, int channels, int bits,
                             float* out, int64_t ld, void* workspace, uint64_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FLAC output, csrc/flacenc.hip: the payload of the PCM encoder (pcm16 / pcm24) -> the frames of a native FLAC stream that decodes
+ * to it byte for byte.  Launch family "flacenc" (a p2phd_flac_encode counts 3: the frame kernel, the scan of the frame lengths, the
+ * gather).  Restated in tests/_flac_enc_ref.py.
+ *
+ * THE STREAM CONTRACT.  The stream is a function of (payload, channels, bits, L, rate, block) alone, to the byte: host encoder,
+ * device encoder and restatement are compared with ==.  Every decision is taken on exact bit counts in 64-bit integers.
+ *
+ * Input: the interleaved little-endian payload, `bits` 16 or 24, `channels` C in 1..8, L >= 1 samples per channel, `rate` in
+ *   1..1048575, `block` in 16..65535.
+ * Framing: frames of `block` samples, the last one shorter (L - (frames - 1) * block); blocking-strategy bit 0, the frame number coded
+ *   (1 to 6 bytes).  Block-size code: 1 for 192, 2..5 for 576 << i, 8..15 for 256 << i, else 6 (8-bit trailer) for a size <= 256, else 7
+ *   (16-bit trailer).  Rate code: 1..11 for the rates of the table, else 13 (Hz in 16 bits) below 65536, else 14 (tens of Hz) where
+ *   the rate divides by 10 and the quotient is below 65536, else 0 (from STREAMINFO).  Sample-size code 4 / 6.  CRC-8 (poly 0x07)
+ *   closes the header, zero bits pad to the byte boundary, CRC-16 (poly 0x8005, init 0) closes the frame.
+ * Per coded channel, bps = bits, + 1 for a side channel, bs = the frame's samples:
+ *   CONSTANT (8 + bps bits) whenever all samples of the block are equal.
+ *   VERBATIM: 8 + bs * bps bits.
+ *   FIXED of order o in 0..4 with Rice partition order p in 0..min(8, trailing zeros of bs), a pair being admitted where
+ *   (bs >> p) > o: 8 + o * bps + 2 + 4 + the sum over the 2^p partitions of (pbits + min over k of [n * (k + 1) + sum of (u >> k)]),
+ *   u = (r << 1) ^ (r >> 31) the zig-zag of a residual r, n the partition's residuals (bs >> p, the first partition o fewer).
+ *   bits 16: method 0, pbits 4, k in 0..14; bits 24: method 1, pbits 5, k in 0..30.  No escape partitions, no wasted bits, no LPC.
+ *   Ties, a priority list: within a partition the smaller k; among the pairs (o, p) of equal bits the smaller p, and among those of
+ *   equal p the smaller o -- so an equally cheap (1, 0) is taken before (0, 1).  FIXED is taken only where its bits are strictly
+ *   fewer than VERBATIM's.
+ * Stereo (C == 2): the best bits of L, R, M = (L + R) >> 1 and S = L - R are found as above; the assignment is the cheapest of
+ *   independent (L + R), left/side (L + S), side/right (S + R), mid/side (M + S), ties in that order.  Any other C: independent.
+ * File (written by the caller, data/flacio.py): "fLaC", one STREAMINFO with the last-block flag (min_block = max_block = block, the
+ *   smallest and largest frame length, rate, channels, bits, total = L, MD5 of the payload or zeros), the frames.
+ *
+ * HOST only:
+ * p2phd_flac_encode_plan: -> *nframes = ceil(L / block); *max_stream_bytes = the frames' worst case (16 header bytes, every subframe
+ *   VERBATIM, the side channel's extra bit included, CRC-16: a true bound, FIXED being taken only where smaller);
+ *   *workspace_bytes of p2phd_flac_encode.
+ * p2phd_flac_encode_host: the reference encoder, one thread, no device: `stream` (room for cap >= max_stream_bytes) receives the
+ *   frames back to back, lengths[f] each frame's bytes, lengths[nframes] their total.  It decides and counts with the routines the
+ *   device encoder uses.
+ * p2phd_flac_encode_threads, p2phd_flac_encode_scan_threads, p2phd_flac_encode_window_words: lanes of a frame's workgroup (samples
+ *   per step of its writer), frames per step of the scan's one workgroup, and 32-bit words of the window of a frame's bit stream
+ *   that the frame kernel keeps in LDS and stores when a step ends beyond it (tests place their sizes around all three).
+ *
+ * DEVICE:
+ * p2phd_flac_encode: the same bytes and the same `lengths` from the payload on the device (any byte alignment), on `stream`.  One
+ *   workgroup per frame; it reads nothing outside the payload's channels * L * bits / 8 bytes, writes exactly lengths[nframes] bytes
+ *   of stream_dev and the nframes + 1 words of lengths_dev (8-byte aligned), and keeps each frame in a worst-case slot of `workspace`
+ *   (8-byte aligned, workspace_bytes >= the plan's) until the gather.  Integer sums only, no float, no atomics on global memory: the
+ *   same bytes on every run and stream.  A cap or workspace below the plan's, arguments outside the ranges above, a null or
+ *   misaligned pointer: P2PHD_EINVAL, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_flac_encode_plan(int channels, int bits, int64_t L, int block, int64_t* nframes, int64_t* max_stream_bytes, int64_t* workspace_bytes);
+int p2phd_flac_encode_threads(void);
+int p2phd_flac_encode_scan_threads(void);
+int p2phd_flac_encode_window_words(void);
+int p2phd_flac_encode_host(const void* payload, int channels, int bits, int64_t L, int rate, int block, void* stream, int64_t cap, int64_t* lengths);
+int p2phd_flac_encode(const void* payload_dev, int channels, int bits, int64_t L, int rate, int block, void* stream_dev, int64_t cap,
+                      int64_t* lengths_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* measurement only (tools/time_generate.py flacout): p2phd_flac_encode's arguments and checks, launching the frame kernel alone (stage 1:
+ * the frames stay in the workspace's slots, stream_dev and lengths_dev are not written) or the frame kernel without its CRC-16, which
+ * is then written as zeros (stage 2).  Counts 1. */
+int p2phd_flac_encode_stage(int stage, const void* payload_dev, int channels, int bits, int64_t L, int rate, int block, void* stream_dev, int64_t cap,
+                            int64_t* lengths_dev, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

@@ -100,6 +100,13 @@ SIGNATURES = {
     "p2phd_flac_tile_len": (_i32, []),
     "p2phd_flac_frames_per_workgroup": (_i32, []),
     "p2phd_flac_decode": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "p2phd_flac_encode_plan": (_i32, [_i32, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "p2phd_flac_encode_threads": (_i32, []),
+    "p2phd_flac_encode_scan_threads": (_i32, []),
+    "p2phd_flac_encode_window_words": (_i32, []),
+    "p2phd_flac_encode_host": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "p2phd_flac_encode": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "p2phd_flac_encode_stage": (_i32, [_i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

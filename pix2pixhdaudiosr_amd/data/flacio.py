@@ -6,7 +6,11 @@ Everything here runs on the host (p2phd_flac_info / p2phd_flac_index / p2phd_fla
 have none.  The frame index of a file -- one row per frame, every CRC verified -- is built once per (path, size, mtime) and kept
 in a bounded cache of the process, so with the cache warm a random training segment costs one seek, one read of the covering
 frames' bytes and their decode.  Whole-file generation copies the file's bytes and the index to the device instead and decodes
-there (generate.flac_decode)."""
+there (generate.flac_decode).
+
+FLAC writer (csrc/flacenc.hip, the stream contract of include/p2phd.h): `encode` is the host encoder p2phd_flac_encode_host,
+`write_stream` puts "fLaC" and STREAMINFO in front of encoded frames -- the host encoder's or the device encoder's
+(generate.flac_encode) -- and `save` is the twin of wavio.save."""
 import ctypes
 import hashlib
 import os
@@ -157,3 +161,106 @@ def verify(path):
     nb = (meta.bits_per_sample + 7) // 8
     le = np.ascontiguousarray(pcm.T).astype("<i4").reshape(-1, 1).view(np.uint8)[:, :nb]
     return hashlib.md5(np.ascontiguousarray(le).tobytes()).digest() == meta.md5
+
+
+# ---- writer ------------------------------------------------------------------------------------------------------------------
+DEFAULT_BLOCK = 4096
+ENCODINGS = {"pcm16": 16, "pcm24": 24}                                      # what a FLAC stream of this build holds
+
+
+def check_output(channels, bits, rate, block, what="flacio"):
+    """The writer's refusals, raised before a file is opened: the ranges of the stream contract."""
+    if bits not in (16, 24):
+        raise ValueError("%s: FLAC output holds pcm16 or pcm24 samples, not %r bits (float32 is not built)" % (what, bits))
+    if not 1 <= int(channels) <= 8:
+        raise ValueError("%s: FLAC output holds 1 to 8 channels, not %r" % (what, channels))
+    if not 16 <= int(block) <= 65535:
+        raise ValueError("%s: the FLAC block size must lie in 16 .. 65535, got %r" % (what, block))
+    if not 1 <= int(rate) <= 1048575:
+        raise ValueError("%s: the sample rate of a FLAC stream must lie in 1 .. 1048575, got %r" % (what, rate))
+
+
+def encode_plan(channels, bits, total, block=DEFAULT_BLOCK):
+    """-> (frames, worst-case bytes of the frames, workspace bytes of the device encoder): p2phd_flac_encode_plan."""
+    out = (ctypes.c_int64 * 3)()
+    addr = ctypes.addressof(out)
+    if _lib().p2phd_flac_encode_plan(int(channels), int(bits), int(total), int(block), ctypes.c_void_p(addr), ctypes.c_void_p(addr + 8),
+                                     ctypes.c_void_p(addr + 16)) != 0:
+        raise _err("flac_encode_plan")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def encode(samples_or_payload, channels=None, bits=16, rate=44100, block=DEFAULT_BLOCK):
+    """The host encoder (p2phd_flac_encode_host, one thread, no device).  `samples_or_payload`: the interleaved little-endian PCM
+    payload of `channels` channels as a bytes-like object, or an integer array [channels, samples] (or [samples]) whose values fit
+    `bits` -> (the frames back to back as bytes, lengths: int64 [frames + 1], each frame's bytes and their total)."""
+    if isinstance(samples_or_payload, np.ndarray) and samples_or_payload.dtype != np.uint8:
+        a = np.atleast_2d(samples_or_payload)
+        lim = 1 << (bits - 1)
+        if a.size and (a.min() < -lim or a.max() >= lim):
+            raise ValueError("flacio.encode: samples outside %d bits" % bits)
+        channels = a.shape[0]
+        le = np.ascontiguousarray(a.T).astype("<i4").reshape(-1, 1).view(np.uint8)[:, :bits // 8]
+        payload = np.ascontiguousarray(le).reshape(-1)
+    else:
+        payload = np.frombuffer(samples_or_payload, dtype=np.uint8)
+        if channels is None:
+            raise ValueError("flacio.encode: a payload needs its channel count")
+    check_output(channels, bits, rate, block, "flacio.encode")
+    align = int(channels) * bits // 8
+    if payload.size == 0 or payload.size % align:
+        raise ValueError("flacio.encode: %d bytes are not one or more whole frames of %d x %d bit" % (payload.size, channels, bits))
+    total = payload.size // align
+    frames, worst, _ = encode_plan(channels, bits, total, block)
+    out = np.empty(worst, dtype=np.uint8)
+    lengths = np.zeros(frames + 1, dtype=np.int64)
+    payload = np.ascontiguousarray(payload)
+    if _lib().p2phd_flac_encode_host(ctypes.c_void_p(payload.ctypes.data), int(channels), int(bits), total, int(rate), int(block),
+                                     ctypes.c_void_p(out.ctypes.data), worst, ctypes.c_void_p(lengths.ctypes.data)) != 0:
+        raise _err("flac_encode_host")
+    return out[:int(lengths[-1])].tobytes(), lengths
+
+
+def stream_header(lengths, rate, channels, bits, total, block, md5=None):
+    """"fLaC" and the one STREAMINFO block (last-block flag set) in front of frames of the given lengths (int64 [frames + 1], as the
+    encoders return them; the last entry, their total, is not a frame)."""
+    check_output(channels, bits, rate, block, "flacio.stream_header")
+    each = np.asarray(lengths, dtype=np.int64)[:-1]
+    if each.size == 0 or not 1 <= int(total) < 1 << 36:
+        raise ValueError("flacio.stream_header: no frames, or a total outside 1 .. 2^36 - 1")
+    md5 = b"\0" * 16 if md5 is None else bytes(md5)
+    if len(md5) != 16:
+        raise ValueError("flacio.stream_header: an MD5 has 16 bytes")
+    lo, hi = min(int(each.min()), 0xFFFFFF), min(int(each.max()), 0xFFFFFF)
+    v = (int(rate) << 44) | ((int(channels) - 1) << 41) | ((int(bits) - 1) << 36) | int(total)
+    info_block = int(block).to_bytes(2, "big") * 2 + lo.to_bytes(3, "big") + hi.to_bytes(3, "big") + v.to_bytes(8, "big") + md5
+    return b"fLaC" + bytes([0x80]) + len(info_block).to_bytes(3, "big") + info_block
+
+
+def write_stream(path, frames, lengths, rate, channels, bits, total, block, md5=None):
+    """The one place that turns encoded frames into a file: header, STREAMINFO, then frames[:lengths[-1]] (a bytes-like object or a
+    uint8 array, which may be longer: the device encoder's stream comes back at its worst-case size) -> the bytes written."""
+    head = stream_header(lengths, rate, channels, bits, total, block, md5)
+    n = int(np.asarray(lengths)[-1])
+    body = memoryview(frames).cast("B")
+    if len(body) < n:
+        raise ValueError("flacio.write_stream: %d bytes of frames, the lengths state %d" % (len(body), n))
+    with open(path, "wb") as f:
+        f.write(head)
+        f.write(body[:n])
+    return len(head) + n
+
+
+def save(path, waveform, sample_rate, encoding="pcm16", block=DEFAULT_BLOCK):
+    """The twin of wavio.save: waveform [channels, frames] or [frames], clamped and rounded by the same expression (wavio.payload_of),
+    encoded on the host, MD5 of the payload in STREAMINFO.  'float32' is refused: FLAC holds integers."""
+    from . import wavio
+    if encoding not in ENCODINGS:
+        raise ValueError("flacio.save: encoding must be one of %s, got %r (float32 is not built for FLAC)" % (sorted(ENCODINGS), encoding))
+    bits = ENCODINGS[encoding]
+    w = torch.as_tensor(waveform)
+    channels = 1 if w.dim() == 1 else w.shape[0]
+    check_output(channels, bits, sample_rate, block, "flacio.save")
+    pcm, channels = wavio.payload_of(w, encoding)
+    frames, lengths = encode(pcm, channels, bits, sample_rate, block)
+    return write_stream(path, frames, lengths, sample_rate, channels, bits, len(pcm) // (channels * bits // 8), block, hashlib.md5(pcm).digest())

@@ -108,10 +108,9 @@ def write_payload(path, payload, sample_rate, channels, encoding="pcm16"):
             f.write(b"\0")                                            # RIFF chunks are word-aligned
 
 
-def save(path, waveform, sample_rate, encoding="pcm16"):
-    """Writer (torchaudio.save's default for float input is float32; the reference's outputs are listened to, not re-read,
-    generate_audio.py:65): waveform [channels, frames] or [frames].  `encoding`: 'pcm16' (default) and 'pcm24' clamp to
-    [-1, 1 - 2^-(bits-1)], scale by 2^(bits-1) and round half to even; 'float32' writes the values as they are."""
+def payload_of(waveform, encoding="pcm16"):
+    """waveform [channels, frames] or [frames] -> (the interleaved little-endian payload, channels): the clamping and rounding of
+    `save`, shared with flacio.save."""
     if encoding not in ENCODINGS:
         raise ValueError(f"wavio: encoding must be one of {sorted(ENCODINGS)}, got {encoding!r}")
     w = torch.as_tensor(waveform).detach().cpu().float()
@@ -124,4 +123,12 @@ def save(path, waveform, sample_rate, encoding="pcm16"):
         pcm = np.ascontiguousarray(q.astype("<i4").reshape(-1, 1).view(np.uint8)[:, :3]).tobytes()
     else:
         pcm = w.T.contiguous().numpy().astype("<f4").tobytes()
-    write_payload(path, pcm, sample_rate, w.shape[0], encoding)
+    return pcm, w.shape[0]
+
+
+def save(path, waveform, sample_rate, encoding="pcm16"):
+    """Writer (torchaudio.save's default for float input is float32; the reference's outputs are listened to, not re-read,
+    generate_audio.py:65): waveform [channels, frames] or [frames].  `encoding`: 'pcm16' (default) and 'pcm24' clamp to
+    [-1, 1 - 2^-(bits-1)], scale by 2^(bits-1) and round half to even; 'float32' writes the values as they are."""
+    pcm, channels = payload_of(waveform, encoding)
+    write_payload(path, pcm, sample_rate, channels, encoding)

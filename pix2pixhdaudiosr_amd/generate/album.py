@@ -122,8 +122,14 @@ def enhance_album(sr, plan, written_from, is_lr_input, channels, encoding, seed,
             else:
                 dev = pcm_encode(w, encoding, gain=guard_gain if guard else None, dither=stage['dither'], seed=dither_seed + e['k'],
                                  curve=stage.get('curve'), chunk=stage.get('chunk'))
-            payload, _ = sr._fetch(dev, None)
-            sr._save(e['path_out'], payload, w.shape[0], encoding)
+            flac = o.flac and dict(o.flac)                                  # (one file's, as in the per-file flow)
+            extra = {}
+            if flac is not None:
+                dev, extra = sr._flac_stage(dev, w.shape[0], encoding, flac)
+            payload, _ = sr._fetch(dev, None, **extra)
+            sr._save(e['path_out'], payload, w.shape[0], encoding, **_set(flac=flac))
+            if flac is not None:
+                rec['flac'] = flac['result']
             e['clip'] = None
         records.append(rec)
         if report is not None:

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 import torch
 
 from .ops import shaper_coefficients
-from .plans import (check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
@@ -308,11 +308,26 @@ def _parser():
     ap.add_argument("--verify_input", action="store_true",
                     help="FLAC inputs: decode the file on the host first and refuse it where its samples do not have the MD5 its "
                          "STREAMINFO states; one start-up line more (default: off)")
+    ap.add_argument("--container", default="wav", choices=("wav", "flac"),
+                    help="what is written: wav, or a FLAC stream that decodes to the wav's data chunk byte for byte, encoded on the "
+                         "device (fixed predictors, Rice partitions, stereo decorrelation); pcm16 or pcm24 only; a folder's outputs "
+                         "are then named .flac; one line more per file (default: wav)")
+    ap.add_argument("--flac_block", type=int, default=None, metavar="N",
+                    help="--container flac: samples per FLAC frame, 16 .. 65535 (default 4096)")
+    ap.add_argument("--flac_md5", action="store_true",
+                    help="--container flac: write the MD5 of the samples into STREAMINFO; the payload is then copied back beside the "
+                         "stream, a second copy of the payload's size (default: off, the MD5 field is zeros)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
                          "the one the reference's train.py, which writes opt.txt, is hard-wired to)")
     return ap
+
+
+def _print_flac(path, f, encoding):
+    print('%s: FLAC %d bit, %d frames of %d, %d bytes (%.1f %% of the PCM)%s'
+          % (path, 24 if encoding == 'pcm24' else 16, f['frames'], f['block'], f['bytes'], 100.0 * f['bytes'] / f['pcm_bytes'],
+             '' if f['md5'] is None else ', MD5 ' + f['md5']))
 
 
 def _print_spectrogram(p):
@@ -344,6 +359,8 @@ def main(argv=None):
             picture['input_formats'] = check_input_formats(a.input_formats, "generate")
         if a.verify_input:
             picture['verify_input'] = True
+        if check_container(a.container, a.flac_block, a.flac_md5, a.encoding, a.output_rate or 48000, "generate") is not None:
+            picture.update(container=a.container, **{k: v for k, v in (('flac_block', a.flac_block), ('flac_md5', a.flac_md5 or None)) if v is not None})
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
             check_limiter(a.limiter, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, 48000, "generate")
             picture.update(limiter=True, limiter_lookahead_ms=a.limiter_lookahead_ms, limiter_hold_ms=a.limiter_hold_ms)
@@ -420,6 +437,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
             print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r.get('written', r['path'])), r['out_frames'], rate,
                                                                    r['written_channels'], '' if r['written_channels'] == 1 else 's'))
+            if r.get('flac') is not None:                                   # (without the option: no line more than before)
+                _print_flac(os.path.join(a.output, r['written']), r['flac'], a.encoding)
             if a.report_peaks or a.true_peak or a.limiter:
                 _print_peaks(r['path'], r['output'])
             if a.limiter:
@@ -462,6 +481,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
+        if res.get('flac') is not None:                                     # (without the option: no line more than before)
+            _print_flac(a.output, res['flac'], a.encoding)
         if a.report_peaks or a.true_peak or a.limiter:
             _print_peaks(a.output, res['output'])
         if a.limiter:

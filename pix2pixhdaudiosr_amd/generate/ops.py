@@ -1,5 +1,5 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip, csrc/shaper.hip and csrc/flac.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip, csrc/shaper.hip, csrc/flac.hip and csrc/flacenc.hip as tensor functions."""
 import ctypes
 
 import torch
@@ -125,6 +125,30 @@ def flac_decode(bytes_dev, table, info, check=True):
     if v != -1:
         raise ValueError("flac_decode: frame %d does not decode: %s" % (v >> 8, FLAC_REASONS.get(v & 255, "reason %d" % (v & 255))))
     return out
+
+
+def flac_encode(payload, channels, bits, rate, block=None):
+    """payload: uint8 tensor on the GPU, the interleaved little-endian samples pcm_encode leaves ('pcm16': bits 16, 'pcm24': bits 24;
+    a view at any byte offset) -> (stream, lengths) on the GPU: `stream` a uint8 tensor of the plan's worst-case size whose first
+    lengths[-1] bytes are the FLAC frames back to back (bytes behind them are not written), `lengths` int64 [frames + 1], each frame's
+    bytes and their total -- what data/flacio.py's write_stream puts behind its header, and byte for byte what flacio.encode gives for
+    the same payload (p2phd_flac_encode: three launches of the family "flacenc").  `block`: samples per frame (None: 4096).  Nothing
+    is waited for."""
+    from ..data import flacio
+    b = _lib.require_gpu_tensor(payload, "flac_encode: payload", torch.uint8)
+    block = flacio.DEFAULT_BLOCK if block is None else block
+    flacio.check_output(channels, bits, rate, block, "flac_encode")
+    align = int(channels) * int(bits) // 8
+    if b.dim() != 1 or b.numel() == 0 or b.numel() % align:
+        raise ValueError("flac_encode: %s bytes are not one or more whole frames of %d x %d bit" % (tuple(b.shape), channels, bits))
+    L = b.numel() // align
+    frames, worst, nwork = flacio.encode_plan(channels, bits, L, block)
+    stream = torch.empty((worst,), dtype=torch.uint8, device=b.device)
+    lengths = torch.empty((frames + 1,), dtype=torch.int64, device=b.device)
+    work = torch.empty((nwork // 8,), dtype=torch.int64, device=b.device)
+    _lib.check(_lib.lib().p2phd_flac_encode(_lib.ptr(b), int(channels), int(bits), L, int(rate), int(block), _lib.ptr(stream), worst, _lib.ptr(lengths),
+                                            _lib.ptr(work), nwork, _lib.stream_ptr()), "flac_encode")
+    return stream, lengths
 
 
 def shaper_coefficients(curve):

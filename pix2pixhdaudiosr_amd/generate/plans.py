@@ -685,11 +685,37 @@ def check_input_formats(formats, who="plan_folder"):
     return tuple(out)
 
 
-def plan_folder(dir_in, dir_out, formats=('wav',)):
+CONTAINERS = ('wav', 'flac')                                                # what the per-file flow can write
+FLAC_BLOCK = 4096                                                           # samples per FLAC frame where none is asked for
+
+
+def check_container(container, flac_block, flac_md5, encoding, rate, who):
+    """The container option of enhance_file / enhance_folder -> None ('wav': nothing changes), or {'block', 'md5'} for 'flac'.
+    `rate`: the rate that will be written.  A ValueError each: an unknown container; flac_block or flac_md5 without 'flac';
+    'flac' with an encoding that is not integer PCM, a block outside 16 .. 65535, a rate above 1048575 (STREAMINFO has 20 bits)."""
+    if container not in CONTAINERS:
+        raise ValueError("%s: container must be one of %s, got %r" % (who, list(CONTAINERS), container))
+    if container == 'wav':
+        if flac_block is not None or flac_md5:
+            raise ValueError("%s: flac_block / flac_md5 are options of container='flac'; container is 'wav'" % who)
+        return None
+    if encoding not in ('pcm16', 'pcm24'):
+        raise ValueError("%s: container='flac' holds integer samples: encoding must be 'pcm16' or 'pcm24', got %r" % (who, encoding))
+    block = FLAC_BLOCK if flac_block is None else flac_block
+    if isinstance(block, bool) or not isinstance(block, int) or not 16 <= block <= 65535:
+        raise ValueError("%s: flac_block must be an int in 16 .. 65535, got %r" % (who, flac_block))
+    if not 1 <= int(rate) <= 1048575:
+        raise ValueError("%s: container='flac' states the rate in 20 bits: at most 1048575 Hz, got %r" % (who, rate))
+    return {'block': block, 'md5': bool(flac_md5)}
+
+
+def plan_folder(dir_in, dir_out, formats=('wav',), ext='.wav'):
     """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
     output keeps the relative path under dir_out.  Other files are ignored.  `formats`: the extensions that are listed
-    (check_input_formats; default: wav alone); every output is a wav, so x.flac is written as x.wav, and two inputs that would be
-    written to the same path are a ValueError."""
+    (check_input_formats; default: wav alone); `ext`: the extension every output gets ('.wav'; '.flac' with container='flac'), so
+    with the default x.flac is written as x.wav, and two inputs that would be written to the same path are a ValueError."""
+    if ext not in ('.wav', '.flac'):
+        raise ValueError("plan_folder: ext must be '.wav' or '.flac', got %r" % (ext,))
     formats = check_input_formats(formats)
     if not os.path.isdir(dir_in):
         raise NotADirectoryError("%s is not a directory" % dir_in)
@@ -702,7 +728,7 @@ def plan_folder(dir_in, dir_out, formats=('wav',)):
                 rel.append(os.path.relpath(os.path.join(root, f), dir_in))
     plan, taken = [], {}
     for r in sorted(rel):
-        out = r if r.lower().endswith('.wav') else os.path.splitext(r)[0] + '.wav'
+        out = r if r.lower().endswith(ext) else os.path.splitext(r)[0] + ext
         if out in taken:
             raise ValueError("%s and %s would both be written to %s" % (os.path.join(dir_in, taken[out]), os.path.join(dir_in, r), os.path.join(dir_out, out)))
         taken[out] = r

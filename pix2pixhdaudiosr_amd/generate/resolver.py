@@ -1,4 +1,5 @@
 """Whole-file generation: SuperResolver -- a clip through the model group by group, and the file path around it."""
+import hashlib
 import math
 import os
 import struct
@@ -6,10 +7,10 @@ from collections import namedtuple
 
 import torch
 
-from .ops import (flac_decode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+from .ops import (flac_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
 from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
+                    check_container, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -24,12 +25,13 @@ def _set(**keywords):
 
 
 # The validated options of enhance_file / enhance_folder (SuperResolver._options), each None where it is off: the output stage,
-# the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, and the album (loudness_scope 'folder').
-_Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album')
+# the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, the album (loudness_scope 'folder')
+# and the FLAC container.
+_Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album flac', defaults=(None,))
 
 # The keys a folder record may carry behind the eight it always has (and 'written'), in the record's order; each is also the key
 # of enhance_file's result that fills it ('album': enhance_album's own).
-_RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm')
+_RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm', 'flac')
 
 
 class _File:
@@ -432,7 +434,8 @@ class SuperResolver:
                 raise ValueError("%s: %s" % (getattr(self, '_pin_names', {}).get(slot, '<flac>'), e)) from None
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None):
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,
+               flac=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload; -> the result's 'output', or None
         without a stage.  path_out None: the figures only.  `stage`: the output-stage options (check_output_options), or None for
         the encoder alone.  Every other keyword is None or what one option of enhance_file brings, and a caller passes only those
@@ -442,16 +445,35 @@ class SuperResolver:
           loudness, bandwidth, stereo   the measurement the per-file flow has already queued (_measure_*), a dict with 'packed'
           picture              the rendered spectrogram (_render_picture)
           rate                 the rate the header states where it is not the model's (the output-rate option: `sr` is converted)
+          flac                 the container option's own dict, one file's (check_container): the payload goes through the FLAC
+                               encoder on the device (_flac_stage) and the stream comes back in its place; it gains 'result'
         The first six come back with the payload and the peak figures behind _fetch's one synchronisation."""
         w = sr.contiguous()
         option = _set(true_peak=true_peak, limiter=limiter)
         dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **option)
+        extra = {}
+        if dev is not None and flac is not None:
+            dev, extra = self._flac_stage(dev, w.shape[0], encoding, flac, **_set(rate=rate))
         host, stats = self._fetch(dev, packed, **_set(stereo=stereo, bandwidth=bandwidth, limiter=limiter, true_peak=true_peak, loudness=loudness,
-                                                      picture=picture))
+                                                      picture=picture), **extra)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **option)
         if host is not None:
-            self._save(path_out, host, sr.shape[0], encoding, **_set(rate=rate))
+            self._save(path_out, host, sr.shape[0], encoding, **_set(rate=rate, flac=flac))
         return output
+
+    def _flac_stage(self, dev, channels, encoding, flac, rate=None):
+        """The payload on the device -> (the FLAC frames on the device at their worst-case size, what _fetch brings back beside
+        them): three launches of the family "flacenc".  `flac`: one file's container option, which gains what _save needs: the
+        frame lengths ('lengths', a dict whose 'packed' _fetch replaces by its host copy), with md5 the payload itself ('pcm',
+        likewise: a second copy of the payload's size), 'pcm_bytes', 'total' and 'rate'."""
+        bits = {'pcm16': 16, 'pcm24': 24}[encoding]
+        rate = int(self.opt.hr_sampling_rate if rate is None else rate)
+        stream, lengths = flac_encode(dev, channels, bits, rate, flac['block'])
+        flac.update(lengths={'packed': lengths.view(torch.uint8)}, pcm_bytes=dev.numel(), total=dev.numel() // (channels * bits // 8), rate=rate, bits=bits)
+        extra = {'flac': flac['lengths']}
+        if flac['md5']:
+            flac['pcm'] = extra['flac_pcm'] = {'packed': dev}
+        return stream, extra
 
     def _encode(self, w, wanted, encoding, stage, true_peak=None, limiter=None):
         """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None).
@@ -542,9 +564,18 @@ class SuperResolver:
             lim = {'lookahead': lim['lookahead'], 'hold': lim['hold'], 'rate': tp['rate'], 'ceiling': tp['ceiling']}
         return stage, tp, lim
 
-    def _save(self, path_out, host, channels, encoding, rate=None):
-        from ..data import wavio
+    def _save(self, path_out, host, channels, encoding, rate=None, flac=None):
+        """The one place that turns what _fetch brought back into a file: header + payload, or with `flac` (the container option
+        behind _flac_stage and _fetch) "fLaC", STREAMINFO and the frames' first lengths[-1] bytes; `flac` gains 'result'."""
+        from ..data import flacio, wavio
         os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
+        if flac is not None:
+            lengths = flac['lengths']['packed'].clone().view(torch.int64).numpy()
+            md5 = hashlib.md5(flac['pcm']['packed'].numpy()).digest() if flac['md5'] else None
+            n = flacio.write_stream(path_out, host.numpy(), lengths, flac['rate'], channels, flac['bits'], flac['total'], flac['block'], md5)
+            flac['result'] = {'block': flac['block'], 'frames': len(lengths) - 1, 'bytes': n, 'pcm_bytes': flac['pcm_bytes'],
+                              'md5': None if md5 is None else md5.hex()}
+            return
         wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate if rate is None else rate), channels, encoding)
 
     @staticmethod
@@ -678,7 +709,7 @@ class SuperResolver:
     def _options(self, who, folder, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                  spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                  loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                 album_cache_bytes=None):
+                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False):
         """The options of enhance_file (`folder` False) / enhance_folder (True), validated before a file is opened -> _Options.
         The order of the checks decides which ValueError a bad combination raises first: it does not move."""
         hr_rate = self.opt.hr_sampling_rate
@@ -691,7 +722,8 @@ class SuperResolver:
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, who)
         loud = self._loudness_at(check_loudness(loudness, hr_rate, who, loudness_max_gain_db, loudness_range), rc, who)
         album = check_loudness_scope(loudness_scope, loud, who, folder, limiter, spectrogram, album_cache_bytes)
-        return _Options(stage, tp, lim, spec, loud, bw, st, rc, album)
+        fl = check_container(container, flac_block, flac_md5, encoding, out_rate, who)
+        return _Options(stage, tp, lim, spec, loud, bw, st, rc, album, fl)
 
     # -- one file: the stages of the flow, in the order their launches take on the stream ------------------------------
     def _front(self, read, is_lr_input, channels, encoding, o, who):
@@ -703,6 +735,8 @@ class SuperResolver:
         k = select_channels(channels, meta.num_channels)
         self._check_picture_channel(o.spec, channels, meta.num_channels)
         self._check_stereo_channels(channels, meta.num_channels)
+        if o.flac is not None and k > 8:
+            raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % k)
         if o.loud is not None and k > LOUDNESS_MAX_CHANNELS:
             raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
         rate = meta.sample_rate
@@ -751,11 +785,12 @@ class SuperResolver:
         """(f) _write -- the output stage, the encoder, the one synchronisation and the file -- where there is anything to encode
         or to bring back, then enhance_file's result."""
         output = None
+        flac = o.flac and dict(o.flac)
         if path_out is not None or o.stage is not None or any(m is not None for m in (picture, measure, band, image)):
             output = self._write(path_out, f.clip, encoding, o.stage, **_set(
                 picture=picture, loudness=measure, stereo=image, bandwidth=band,
                 true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
-                rate=o.rc and o.rc['rate']))
+                rate=o.rc and o.rc['rate'], flac=flac))
         res = {'sr': f.clip, 'lr': f.lr, 'hr': f.hr, 'metrics': f.metrics, 'info': f.meta}
         if self.norm_scope == 'clip':                                       # (without the option: no key more than before)
             res['norm'] = f.norm
@@ -775,6 +810,8 @@ class SuperResolver:
             res['metrics_ext'] = f.ext
         if o.stage is not None:
             res['output'] = output
+        if flac is not None:                                                # (None where no file was asked for)
+            res['flac'] = flac.get('result')
         return res
 
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics, o):
@@ -797,7 +834,7 @@ class SuperResolver:
             rec['written'] = os.path.relpath(path_out, written_from)
         present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None,
                        album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto, stereo=o.st is not None,
-                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip')
+                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip', flac=o.flac is not None)
         rec.update((key, None) for key in _RECORD_KEYS if present[key])
         return rec
 
@@ -815,6 +852,8 @@ class SuperResolver:
             read = self._read(path_in, **_set(verify=True if verify_input else None))
             self._check_picture_channel(o.spec, channels, read[1].num_channels)
             self._check_stereo_channels(channels, read[1].num_channels)
+            if o.flac is not None and select_channels(channels, read[1].num_channels) > 8:
+                raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % select_channels(channels, read[1].num_channels))
             return read
         except (ValueError, OSError, EOFError, struct.error) as e:
             rec['error'] = '%s: %s' % (type(e).__name__, e)
@@ -825,7 +864,7 @@ class SuperResolver:
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
-                     dither_chunk=None, verify_input=False):
+                     dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -939,10 +978,22 @@ class SuperResolver:
         file.  'sr' is then the clip at the output rate ('lr' and 'hr' stay at the model's) and the result gains 'output_rate':
         {'rate', 'model_rate', 'o', 'n' (the two rates over their common divisor), 'taps_per_phase', 'passband_hz', 'stopband_hz',
         'atten_db'}.  Not built with `spectrogram` or loudness_scope 'folder'; rates between which the filter is not built (48000 ->
-        8000, or a pair with a tiny common divisor) are refused: a ValueError each, before the file is opened."""
+        8000, or a pair with a tiny common divisor) are refused: a ValueError each, before the file is opened.
+        `container`: 'wav' (default: nothing changes) or 'flac': the payload the encoder leaves on the device -- with the guard's
+        gain, the limiter, the dither and the output rate in it -- goes through the FLAC encoder there (csrc/flacenc.hip, three
+        launches of the family "flacenc"; the stream contract of include/p2phd.h: CONSTANT, VERBATIM and FIXED subframes, Rice
+        partitions, the four stereo assignments, every choice on exact bit counts), so that the file, decoded, is the data chunk the
+        wav would have held, byte for byte.  The frames come back at their worst-case size -- about what the wav path copies -- with
+        their lengths behind the same one synchronisation, and the host writes "fLaC", STREAMINFO and the frames.  `flac_block`:
+        samples per frame, 16 .. 65535 (None: 4096).  `flac_md5`: also bring the payload back (a second copy of its size) and write
+        its MD5 into STREAMINFO, which is otherwise zeros ("not computed").  The result gains 'flac': {'block', 'frames', 'bytes'
+        (the file's), 'pcm_bytes' (the payload's), 'md5' (hex, or None)}; None where no file is written.  encoding 'float32', more
+        than 8 written channels, a block outside the range, a written rate above 1048575 Hz, or either option without 'flac': a
+        ValueError before the output is opened."""
         o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
-                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk)
+                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
+                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None))
         read = self._read(path_in, **_set(verify=True if verify_input else None))
         res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
@@ -969,7 +1020,7 @@ class SuperResolver:
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
                        stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
-                       verify_input=False):
+                       verify_input=False, container='wav', flac_block=None, flac_md5=False):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -1018,13 +1069,16 @@ class SuperResolver:
         `input_formats`: None (the above: *.wav only), or the extensions to list, ('wav', 'flac') for instance (plan_folder's
         `formats`): x.flac is written as x.wav, a record then gains 'written' (the output's relative path), and two inputs that would
         be written to one path are a ValueError before any file is opened.  `verify_input`: enhance_file's, per FLAC file; a mismatch
-        is a skipped file.  Both hold in either loudness scope."""
+        is a skipped file.  Both hold in either loudness scope.
+        `container`, `flac_block`, `flac_md5`: enhance_file's; with 'flac' every output is named .flac (plan_folder's `ext`: x.wav is
+        written as x.flac, and x.wav beside x.flac in one folder is the same ValueError), a record gains 'written' and 'flac', and
+        the album flow writes through the same encoder and the same writer."""
         o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          album_cache_bytes)
-        plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats))
-        written_from = None if input_formats is None else dir_out          # a record then says where its file was written
+                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None))
+        plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
+        written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
         if o.album is not None:
             from .album import enhance_album
             return enhance_album(self, plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed, verify_input)

@@ -13,6 +13,9 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             host, csrc/flac.hip on the device), on the wav (read_payload, copy, p2phd_pcm_decode) and the host decoder followed by a
             copy, interleaved, median and spread of --reps; then by events p2phd_flac_decode whole and each kernel alone beside
             p2phd_pcm_decode, on the clip and on an hour of it; the host index and host decoder alone; log in --flac_log
+  flacout   (only when asked for) the output side: enhance_file with container wav / flac / flac with flac_md5 on one 15 s mono and one
+            stereo clip, interleaved, median and spread of --reps; then by events p2phd_flac_encode beside p2phd_pcm_encode_ex on the
+            written payloads, on the clip and on an hour of it; the host encoder alone; the streams' sizes; log in --flacout_log
 
   folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
             ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
@@ -1074,6 +1077,117 @@ def run_flac(seconds, reps, log):
             f.write(text)
 
 
+def run_flacout(seconds, reps, log):
+    """The output side, file to file: enhance_file with container 'wav' and 'flac' on one mono and one stereo 16-bit clip, interleaved.
+    Then, by events, p2phd_flac_encode (generate.flac_encode: its allocations in front) beside p2phd_pcm_encode_ex on the written
+    payloads, on the clip and on an hour of it (the payload repeated); the host encoder, one thread, on the clip; and the streams'
+    sizes.  The clips are the synthetic partials of the other modes through an untrained model: what they say about speech is
+    little."""
+    import tempfile
+    import numpy as np
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd import _lib
+    from pix2pixhdaudiosr_amd.data import flacio, wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, flac_encode, pcm_encode
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py flacout: one %g s clip at %d Hz (%d samples per channel), mono and stereo, pcm16, block size 4096; %d interleaved repeats"
+             % (seconds, rate, x.shape[-1], reps)]
+    payloads = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        sr = SuperResolver(model, opt, overlap=0.25)
+        for tag, clip in (("mono", 0.5 * x), ("stereo", torch.cat([0.5 * x, 0.4 * x.flip(-1) + 0.1 * x]))):
+            src = os.path.join(tmp, tag + "_in.wav")
+            wavio.save(src, clip.cpu(), rate)
+            pw, pf = os.path.join(tmp, tag + ".wav"), os.path.join(tmp, tag + ".flac")
+            runs = [("%s: container wav " % tag, lambda: sr.enhance_file(src, pw, channels='all')),
+                    ("%s: container flac" % tag, lambda: sr.enhance_file(src, pf, channels='all', container='flac')),
+                    ("%s: flac, flac_md5" % tag, lambda: sr.enhance_file(src, pf, channels='all', container='flac', flac_md5=True))]
+            for _, fn in runs:
+                fn(); fn()
+            torch.cuda.synchronize()
+            ts = [[] for _ in runs]
+            for _ in range(reps):
+                for k, (_, fn) in enumerate(runs):
+                    torch.manual_seed(3)
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            for (name, _), tk in zip(runs, ts):
+                lines.append("%s  median %8.3f ms   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                             % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+            torch.manual_seed(3)
+            sr.enhance_file(src, pw, channels='all')
+            torch.manual_seed(3)
+            res = sr.enhance_file(src, pf, channels='all', container='flac')
+            pay, _ = wavio.read_payload(pw)
+            payloads[tag] = (bytes(pay), clip.shape[0])
+            meta, table = flacio.index_bytes(open(pf, "rb").read())
+            assert flacio.decode_frames(open(pf, "rb").read(), table, 0, len(table), clip.shape[0]).T.astype("<i2").tobytes() == payloads[tag][0]
+            lines.append("%s: %d frames, %d bytes of FLAC for %d of PCM (%.1f %%); the worst-case stream that is copied back: %d bytes"
+                         % (tag, res['flac']['frames'], res['flac']['bytes'], res['flac']['pcm_bytes'], 100.0 * res['flac']['bytes'] / res['flac']['pcm_bytes'],
+                            flacio.encode_plan(clip.shape[0], 16, meta.num_frames, 4096)[1]))
+    for tag, (pay, C) in payloads.items():
+        dev = torch.frombuffer(bytearray(pay), dtype=torch.uint8).cuda()
+        L = len(pay) // (2 * C)
+        copies = 3600 * rate // L
+        planar = torch.from_numpy(np.frombuffer(pay, dtype="<i2").reshape(-1, C).T.astype(np.float32) / 32768.0).cuda().contiguous()
+        for name, b, w in (("the clip", dev, planar), ("an hour", dev.repeat(copies), planar.repeat(1, copies))):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ks = [[], []]
+            for _ in range(reps + 2):
+                ev[0].record()
+                out = flac_encode(b, C, 16, rate)
+                ev[1].record()
+                enc = pcm_encode(w, 'pcm16')
+                ev[2].record()
+                torch.cuda.synchronize()
+                ks[0].append(ev[0].elapsed_time(ev[1]) * 1e3)
+                ks[1].append(ev[1].elapsed_time(ev[2]) * 1e3)
+                total = int(out[1][-1].item())
+                del out, enc
+            n = b.numel() // (2 * C)
+            lines.append("by events on %s, %s (median of %d, allocations in front; %d samples per channel, %d frames, %d bytes of FLAC): p2phd_flac_encode %.1f us "
+                         "(spread %.1f) = %.3f ns per sample; p2phd_pcm_encode_ex %.1f us (spread %.1f) = %.3f ns per sample"
+                         % (name, tag, reps, n, -(-n // 4096), total, _median(ks[0][2:]), max(ks[0][2:]) - min(ks[0][2:]), _median(ks[0][2:]) * 1e3 / (n * C),
+                            _median(ks[1][2:]), max(ks[1][2:]) - min(ks[1][2:]), _median(ks[1][2:]) * 1e3 / (n * C)))
+            lines.append("runs: flac_encode %s; pcm_encode %s" % (" ".join("%.1f" % v for v in ks[0][2:]), " ".join("%.1f" % v for v in ks[1][2:])))
+            # the frame kernel alone with and without its CRC-16 (p2phd_flac_encode_stage, a measurement entry), flac_encode's allocations in front
+            nf, worst, nwork = flacio.encode_plan(C, 16, n, 4096)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ks = [[], []]
+            for _ in range(reps + 2):
+                ev[0].record()
+                for k, stage in enumerate((1, 2)):
+                    stream = torch.empty((worst,), dtype=torch.uint8, device=b.device)
+                    lens = torch.empty((nf + 1,), dtype=torch.int64, device=b.device)
+                    work = torch.empty((nwork // 8,), dtype=torch.int64, device=b.device)
+                    _lib.check(_lib.lib().p2phd_flac_encode_stage(stage, _lib.ptr(b), C, 16, n, rate, 4096, _lib.ptr(stream), worst, _lib.ptr(lens), _lib.ptr(work),
+                                                                  nwork, _lib.stream_ptr()), "flac_encode_stage")
+                    ev[k + 1].record()
+                torch.cuda.synchronize()
+                ks[0].append(ev[0].elapsed_time(ev[1]) * 1e3)
+                ks[1].append(ev[1].elapsed_time(ev[2]) * 1e3)
+                del stream, lens, work
+            with_crc, without = _median(ks[0][2:]), _median(ks[1][2:])
+            lines.append("by events on %s, %s: flacenc_frames_kernel alone %.1f us (spread %.1f), without its CRC-16 %.1f us (spread %.1f): the parallel CRC is %.1f us = %.1f %% "
+                         "of the frame kernel" % (name, tag, with_crc, max(ks[0][2:]) - min(ks[0][2:]), without, max(ks[1][2:]) - min(ks[1][2:]), with_crc - without,
+                                                  100.0 * (with_crc - without) / with_crc))
+        th = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            flacio.encode(pay, C, 16, rate)
+            th.append((time.perf_counter() - t0) * 1e3)
+        lines.append("on the host, one thread, the clip, %s: p2phd_flac_encode_host median %.3f ms (spread %.3f) = %.1f ns per sample; an hour would be %d times that, %.0f ms"
+                     % (tag, _median(th), max(th) - min(th), _median(th) * 1e6 / (L * C), copies, _median(th) * copies))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_normscope(seconds, reps, log, off_only=False):
     """enhance_file on a mono clip, file to file: norm_scope 'group' (an object built without the option) and 'clip', interleaved;
     then p2phd_spectro_range, p2phd_range_fold and p2phd_spectro_encode_given alone, by events, on one group's spectrum beside
@@ -1350,7 +1464,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1368,11 +1482,14 @@ def main():
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
+    ap.add_argument("--flacout_log", default=os.path.join(ROOT, "profiles", "time_generate_flacout.log"))
     ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
+    if a.mode == "flacout":
+        return run_flacout(a.seconds, 9 if a.reps is None else a.reps, a.flacout_log)
     if a.mode == "flac":
         return run_flac(a.seconds, 9 if a.reps is None else a.reps, a.flac_log)
     if a.mode == "album":
