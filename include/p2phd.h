@@ -946,6 +946,32 @@ int p2phd_instnorm_act_bwd_two_pass(int dtype, int N, int64_t HW, int C);
  * refuse (more samples than tickets, a region too small for one grid unit of rows, more channels than the backward kernels hold)
  * the query returns P2PHD_EINVAL with their error text; an unknown family is P2PHD_EINVAL too. */
 int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C, int* rows_wanted, int* rows_used);
+/* Host query (no launch, no stream, no device call): the grid of a grid-stride kernel -- min(cdiv(work items, 256), cap)
+ * workgroups of 256 threads, the work beyond walked with the grid's stride.  *wanted = workgroups (per row) without the cap,
+ * *used = workgroups launched: used < wanted says that the kernel loops.  *unit_work = how much of `work` one trip of the whole
+ * grid covers (work > 2 * unit_work: some thread takes a third trip).  The launchers take their grids from the same function.
+ * `work` per family, and the cap:
+ *   segments_gather(_planar), segments_stitch(_planar)   outputs per row (S * T, resp. L_out); a quad per thread; 16384
+ *   pcm_decode, pcm_encode, pcm_encode_ex                 interleaved samples (frames * channels); 16384
+ *   pcm_peak                                              frames per row, rows = channels; four 16-byte pieces in flight per
+ *                                                         thread; min(2048 / channels, what the reduction scratch holds)
+ *   stereo_matrix / stereo_matrix_scalar                  samples per row L, on the 16-byte path / the path of any alignment; 4096
+ *   loudness_blocks, loudness_short_term                  blocks (J - 3, resp. J - 29); 2048
+ *   avgpool3s2_fwd, avgpool3s2_bwd, nhwc_to_nchw, nchw_cat_to_nhwc   16-byte pieces of the NHWC side (N * pixels * Cp / 8 in
+ *                                                         16-bit storage, / 4 in f32: the pooled side forward); 8192
+ *   nchw_to_nhwc                                          elements N * C * HW; 8192
+ *   act_bwd                                               elements (a 16-byte piece per thread: dtype); 8192
+ *   loss_fwd / loss_bwd                                   padded elements P * Cp; the grid is sized by pieces of 8 elements and a
+ *                                                         thread has four 16-byte pieces in flight (dtype); 1024 / 2048
+ *   adam_step, adam_step_dev, adam_step_scaled            floats, a float4 per thread; 4096
+ *   grads_nonfinite  (inside adam_step_scaled)            floats, four float4 in flight per thread; 2048
+ *   timed_pack_pair                                       pixels, a quad per thread; 16384
+ *   spectro_encode, spectro_encode_ex                     elements channels * B * M * F of the normalisation pass; 8192
+ *   spectro_stats  (inside spectro_encode(_ex))           elements of the noise rows; 1024
+ *   spectro_range, range_fold / .._scalar                 floats, on the 16-byte path / the path of any alignment; 1024
+ * rows is looked at by pcm_peak only, dtype (P2PHD_F32, P2PHD_BF16) where a thread's piece depends on it.  work = 0: all three 0.
+ * An unknown family is P2PHD_EINVAL. */
+int p2phd_stream_grid(const char* family, int dtype, int64_t work, int rows, int64_t* unit_work, int* wanted, int* used);
 /* Residual trunk (networks.py:231-252: ReflectionPad2d(1) + Conv2d 3x3 + InstanceNorm): the input gradient of such a conv reads
  * dy plus the pair-sum rows / columns of the reflection's adjoint.  For planes that take the single-launch InstanceNorm backward
  * the kernel that WRITES dy appends them: allocate dy with p2phd_conv_reflect_extras_elems(desc) extra elements right behind its

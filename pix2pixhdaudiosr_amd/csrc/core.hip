@@ -1,6 +1,7 @@
 // Error channel, ABI version and device query of libp2phd_hip.so.
 #include "common.h"
 #include "convplan.h"
+#include "streamgrid.h"
 #include <cstring>
 
 namespace p2phd {
@@ -116,6 +117,21 @@ extern "C" int p2phd_reduction_reset(void* stream) {
     p2phd::set_error("reduction_reset: memset failed");
     return P2PHD_ELAUNCH;
   }
+  return P2PHD_OK;
+}
+
+// The grid of a grid-stride launch (streamgrid.h: the function the launchers take theirs from).  Host arithmetic only.
+extern "C" int p2phd_stream_grid(const char* family, int dtype, int64_t work, int rows, int64_t* unit_work, int* wanted, int* used) {
+  P2PHD_REQUIRE(family && unit_work && wanted && used, "stream_grid: null pointer");
+  *unit_work = 0; *wanted = *used = 0;
+  const p2phd::StreamFamily f = p2phd::stream_family(family);
+  P2PHD_REQUIRE(f != p2phd::SG_UNKNOWN, "stream_grid: unknown family \"%s\" (include/p2phd.h lists them)", family);
+  P2PHD_REQUIRE(dtype == P2PHD_BF16 || dtype == P2PHD_F32, "stream_grid: unsupported dtype %d", dtype);
+  P2PHD_REQUIRE(work >= 0 && work <= (int64_t(1) << 40) && rows >= 1 && rows <= 65535, "stream_grid: need 0 <= work <= 2^40 and 1 <= rows <= 65535 (work %lld, rows %d)",
+                (long long)work, rows);
+  if (work == 0) return P2PHD_OK;                                 // nothing to launch
+  const p2phd::StreamGrid g = p2phd::stream_grid_of(f, dtype, work, rows);
+  *unit_work = g.unit_work; *wanted = g.wanted; *used = g.used;
   return P2PHD_OK;
 }
 

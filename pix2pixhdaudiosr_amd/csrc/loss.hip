@@ -6,6 +6,7 @@
 // gradient from device memory too, so the whole step can be enqueued without the host waiting on a value.
 #include "common.h"
 #include "convdev.h"
+#include "streamgrid.h"
 
 namespace {
 
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
-inline int grid_for(long work, int cap = 2048) { return (int)std::max<long>(1, std::min<long>((work + 255) / 256, cap)); }
+// (streamgrid.h) `work`: padded elements P * Cp for the losses, floats for Adam and the non-finite scan
+inline int grid_of(p2phd::StreamFamily f, int dtype, long work) { return p2phd::stream_grid_of(f, dtype, work, 1).used; }
 
 
 // Device-resident step counter and learning rate: the launch arguments no longer change from step to step, so a whole
@@ -266,9 +268,9 @@ extern "C" int p2phd_loss_fwd(int kind, int dtype, const void* a, const void* b,
   const p2phd::FoldScratch fs = p2phd::fold_scratch(p2phd::FOLD_LOSS, st);
   if (fs.part == nullptr) return P2PHD_EINVAL;                   // (refused: error text set by fold_scratch)
   if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(loss_fwd_kernel<bf16_t>, dim3(grid_for(P * Cp / 8, 1024)), dim3(256), 0, st, kind, (const bf16_t*)a, (const bf16_t*)b, target, (long)P, C, Cp, coeff, out, fs.part, fs.ticket);
+    hipLaunchKernelGGL(loss_fwd_kernel<bf16_t>, dim3(grid_of(p2phd::SG_LOSS_FWD, dtype, P * Cp)), dim3(256), 0, st, kind, (const bf16_t*)a, (const bf16_t*)b, target, (long)P, C, Cp, coeff, out, fs.part, fs.ticket);
   else if (dtype == P2PHD_F32)
-    hipLaunchKernelGGL(loss_fwd_kernel<float>, dim3(grid_for(P * Cp / 8, 1024)), dim3(256), 0, st, kind, (const float*)a, (const float*)b, target, (long)P, C, Cp, coeff, out, fs.part, fs.ticket);
+    hipLaunchKernelGGL(loss_fwd_kernel<float>, dim3(grid_of(p2phd::SG_LOSS_FWD, dtype, P * Cp)), dim3(256), 0, st, kind, (const float*)a, (const float*)b, target, (long)P, C, Cp, coeff, out, fs.part, fs.ticket);
   else { p2phd::set_error("loss_fwd: unsupported dtype %d", dtype); return P2PHD_EUNSUPPORTED; }
   return p2phd::check_launch("loss_fwd");
 }
@@ -281,9 +283,9 @@ extern "C" int p2phd_loss_bwd(int kind, int dtype, const void* a, const void* b,
   const int Cp = (C + 7) & ~7;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == P2PHD_BF16)
-    hipLaunchKernelGGL(loss_bwd_kernel<bf16_t>, dim3(grid_for(P * Cp / 8)), dim3(256), 0, st, kind, (const bf16_t*)a, (const bf16_t*)b, target, (long)P, C, Cp, coeff, grad_out, (bf16_t*)da);
+    hipLaunchKernelGGL(loss_bwd_kernel<bf16_t>, dim3(grid_of(p2phd::SG_LOSS_BWD, dtype, P * Cp)), dim3(256), 0, st, kind, (const bf16_t*)a, (const bf16_t*)b, target, (long)P, C, Cp, coeff, grad_out, (bf16_t*)da);
   else if (dtype == P2PHD_F32)
-    hipLaunchKernelGGL(loss_bwd_kernel<float>, dim3(grid_for(P * Cp / 8)), dim3(256), 0, st, kind, (const float*)a, (const float*)b, target, (long)P, C, Cp, coeff, grad_out, (float*)da);
+    hipLaunchKernelGGL(loss_bwd_kernel<float>, dim3(grid_of(p2phd::SG_LOSS_BWD, dtype, P * Cp)), dim3(256), 0, st, kind, (const float*)a, (const float*)b, target, (long)P, C, Cp, coeff, grad_out, (float*)da);
   else { p2phd::set_error("loss_bwd: unsupported dtype %d", dtype); return P2PHD_EUNSUPPORTED; }
   return p2phd::check_launch("loss_bwd");
 }
@@ -296,7 +298,7 @@ extern "C" int p2phd_adam_step(float* params, const float* grads, float* exp_avg
   P2PHD_REQUIRE(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0, "adam: buffers must be 16-byte aligned");
   const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
   const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for((n + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_of(p2phd::SG_ADAM, P2PHD_F32, n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
                      exp_avg_sq, (long)n, lr, beta1, beta2, eps, (float)bc1, (float)std::sqrt(bc2), grad_scale);
   return p2phd::check_launch("adam_step");
 }
@@ -310,8 +312,8 @@ static int adam_step_dev_impl(float* params, const float* grads, float* exp_avg,
   if (n > 0) {
     P2PHD_REQUIRE(params && grads && exp_avg && exp_avg_sq, "adam_step_dev: null pointer");
     if (scaler != nullptr)
-      hipLaunchKernelGGL(grads_nonfinite_kernel, dim3(grid_for((n + 3) / 4, 2048)), dim3(256), 0, st, grads, (long)n, scaler + 3 + found_idx);
-    const dim3 grid(grid_for((n + 3) / 4, 4096));
+      hipLaunchKernelGGL(grads_nonfinite_kernel, dim3(grid_of(p2phd::SG_NONFINITE, P2PHD_F32, n)), dim3(256), 0, st, grads, (long)n, scaler + 3 + found_idx);
+    const dim3 grid(grid_of(p2phd::SG_ADAM, P2PHD_F32, n));
     hipLaunchKernelGGL(adam_dev_kernel, grid, dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, (long)n, lr_dev,
                        reinterpret_cast<const long long*>(step_dev), beta1, beta2, eps, grad_scale, (const float*)scaler, found_idx);
   }

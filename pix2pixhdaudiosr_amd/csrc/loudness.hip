@@ -41,6 +41,7 @@
 // workspace, nothing that depends on scheduling: z[c][j] has one writer.
 #include "common.h"
 #include "convplan.h"
+#include "streamgrid.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -260,6 +261,7 @@ __global__ __launch_bounds__(kBlocksThreads) void loudness_blocks_kernel(const d
 constexpr int kShortHops = 30;                // hops of a short-term block: 3 s
 constexpr int kShortThreads = 256;
 constexpr int kShortMaxGrid = 2048;           // workgroups at most; the blocks beyond are walked with the grid's stride
+static_assert(kBlocksThreads == 256 && kShortThreads == 256 && kBlocksMaxGrid == 2048 && kShortMaxGrid == 2048, "streamgrid.h, SG_LOUDNESS");
 constexpr int kRadixBins = 256;               // 8 bits per pass, eight passes over the 64 bits of a double
 constexpr double kAbsGatePower = 1.1724653045822981e-07;       // 10^((-70 + 0.691) / 10): the power of -70 LUFS
 static_assert(kRadixBins == kGateThreads, "the range kernel gives every thread one bin of the histogram");
@@ -442,7 +444,7 @@ extern "C" int p2phd_loudness_short_term(const double* z, int64_t J, int channel
   const int64_t NS = J - (kShortHops - 1);
   if (NS <= 0) return P2PHD_OK;
   P2PHD_REQUIRE(z && p, "loudness_short_term: null pointer");
-  const unsigned grid = (unsigned)std::min<int64_t>(p2phd::cdiv(NS, kShortThreads), kShortMaxGrid);
+  const unsigned grid = (unsigned)p2phd::stream_grid_of(p2phd::SG_LOUDNESS, P2PHD_F32, NS, 1).used;     // (streamgrid.h)
   hipLaunchKernelGGL(loudness_short_term_kernel, dim3(grid), dim3(kShortThreads), 0, (hipStream_t)stream, z, (long)J, channels,
                      (double)kShortHops * (double)(rate / 10), gw, gain_dev, p);
   ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];
@@ -471,7 +473,7 @@ extern "C" int p2phd_loudness_blocks(const double* z, int64_t J, int channels, i
   const int64_t NB = J - 3;
   if (NB <= 0) return P2PHD_OK;
   P2PHD_REQUIRE(z && p, "loudness_blocks: null pointer");
-  const unsigned grid = (unsigned)std::min<int64_t>(p2phd::cdiv(NB, kBlocksThreads), kBlocksMaxGrid);
+  const unsigned grid = (unsigned)p2phd::stream_grid_of(p2phd::SG_LOUDNESS, P2PHD_F32, NB, 1).used;     // (streamgrid.h)
   hipLaunchKernelGGL(loudness_blocks_kernel, dim3(grid), dim3(kBlocksThreads), 0, (hipStream_t)stream, z, (long)J, channels,
                      4.0 * (double)(rate / 10), gw, p);
   ++p2phd::g_launch_count[p2phd::LC_LOUDNESS];

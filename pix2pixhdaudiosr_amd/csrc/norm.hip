@@ -7,6 +7,7 @@
 // stats), :188,233 (ReLU), :342-358 (LeakyReLU 0.2), :165,308 (AvgPool2d), :252 (residual add).
 #include "common.h"
 #include "convdev.h"
+#include "streamgrid.h"
 #include <cstring>
 namespace p2phd { extern int g_opt_wgrad_xcd; }   // 1 (default): XCD-aware workgroup order (core.hip)
 
@@ -677,7 +678,7 @@ __global__ void nchw_cat_to_nhwc_kernel(CatSrc cs, int nsrc, T* __restrict__ dst
   }
 }
 
-inline int grid_for(long work, int cap = 8192) { return (int)std::max<long>(1, std::min<long>((work + 255) / 256, cap)); }
+inline int grid_for(long work) { return p2phd::stream_grid_of(p2phd::SG_ITEMS, P2PHD_F32, work, 1).used; }     // (streamgrid.h)
 
 #define DISPATCH_T(dtype, CALL_BF16, CALL_F32, name)                 \
   if ((dtype) == P2PHD_BF16) { CALL_BF16; }                          \
@@ -979,10 +980,11 @@ extern "C" int p2phd_act_bwd(int dtype, const void* g, const void* a, void* dx, 
   const int epp = dtype == P2PHD_BF16 ? 8 : 4;
   P2PHD_REQUIRE(n_elems % epp == 0, "act_bwd: element count must be a multiple of %d", epp);
   const long np = n_elems / epp;
+  const int grid = p2phd::stream_grid_of(p2phd::SG_ACT_BWD, dtype, n_elems, 1).used;      // (streamgrid.h: what p2phd_stream_grid("act_bwd") reports)
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype,
-             hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(grid_for(np)), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)a, (bf16_t*)dx, np, act),
-             hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid_for(np)), dim3(256), 0, st, (const float*)g, (const float*)a, (float*)dx, np, act),
+             hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)a, (bf16_t*)dx, np, act),
+             hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)g, (const float*)a, (float*)dx, np, act),
              "act_bwd");
   return p2phd::check_launch("act_bwd");
 }

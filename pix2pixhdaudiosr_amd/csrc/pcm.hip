@@ -24,6 +24,7 @@
 #include "common.h"
 #include "convplan.h"
 #include "dither.h"
+#include "streamgrid.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void pcm_peak_kernel(const float* __restr
   }
 }
 
-int sample_grid(int64_t samples) { return (int)std::max<int64_t>(1, std::min<int64_t>(p2phd::cdiv(samples, kThreads), 16384)); }
+int sample_grid(int64_t samples) { return p2phd::stream_grid_of(p2phd::SG_PCM, P2PHD_F32, samples, 1).used; }       // (streamgrid.h)
 
 template <int FORMAT, int BYTES>
 void launch_decode(const void* bytes, int64_t frames, int channels, float* out, int64_t ld, hipStream_t st) {
@@ -224,12 +225,9 @@ void launch_encode(const float* planar, int64_t frames, int channels, int64_t ld
                      (long)frames, (long)channels, (long)ld, gain, seed, first_index, static_cast<uint8_t*>(out), aligned);
 }
 
-// workgroups per row: enough to keep every CU busy with rows of any count, a partial table that fits the scratch region
-int peak_grid(int64_t frames, int channels, size_t scratch_words) {
-  const int64_t want = p2phd::cdiv(frames / 4, (int64_t)kThreads * kPeakU);
-  const int64_t cap = std::min<int64_t>(std::max<int64_t>(1, 2048 / channels), (int64_t)(scratch_words / ((size_t)kPeakWords * channels)));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
-}
+// workgroups per row (streamgrid.h, which holds kThreads, kPeakU and kPeakWords as numbers)
+static_assert(kThreads == 256 && kPeakU == 4 && kPeakWords == 5, "streamgrid.h, SG_PCM_PEAK");
+int peak_grid(int64_t frames, int channels) { return p2phd::stream_grid_of(p2phd::SG_PCM_PEAK, P2PHD_F32, frames, channels).used; }
 
 // The checks every entry shares: the shape of the planar side and the format -- one a data chunk can hold (decode), or one
 // of the three an output is written in (`encodable`)
@@ -313,7 +311,7 @@ extern "C" int p2phd_pcm_peak(const float* planar, int64_t frames, int channels,
   if (fs.part == nullptr) return P2PHD_EINVAL;                   // (refused: error text set by fold_scratch)
   P2PHD_REQUIRE(fs.floats >= (size_t)kPeakWords * channels, "pcm_peak: reduction scratch too small for %d channels", channels);
   // frames = 0 launches too: the outputs (zeros, gain 1) are valid after every call
-  const dim3 grid(peak_grid(frames, channels, fs.floats), channels);
+  const dim3 grid(peak_grid(frames, channels), channels);
   uint32_t* part = reinterpret_cast<uint32_t*>(fs.part);
   long long* ov = reinterpret_cast<long long*>(over);
   long long* nf = reinterpret_cast<long long*>(nonfinite);

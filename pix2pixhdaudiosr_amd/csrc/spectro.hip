@@ -11,6 +11,7 @@
 // decode: log_spectro[B,2,M,F] -> spec[B,F,M] = (A0 - A1)/(2 alpha - 1), A = DB_to_amplitude(|x|(max-min)+min, 10, .5) - min_value
 #include "common.h"
 #include "convplan.h"
+#include "streamgrid.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -310,8 +311,8 @@ __global__ __launch_bounds__(256) void range_fold_kernel(const float* __restrict
 template <int CH>
 int launch_range(const float* x, long n, float alpha, float min_value, float* minmax_io, float* partials, hipStream_t st) {
   const long n4 = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
-  const long items = n4 + (n - 4 * n4);
-  const int nb = (int)std::min<long>((items + 255) / 256, 1024);  // 2 * 1024 floats: inside the 4 * 1024 every caller's workspace has
+  // (streamgrid.h: n4 + (n - 4 * n4) items, at most 1024 workgroups) 2 * 1024 floats: inside the 4 * 1024 every caller's workspace has
+  const int nb = p2phd::stream_grid_of(n4 ? p2phd::SG_RANGE_VEC : p2phd::SG_RANGE_SCALAR, P2PHD_F32, n, 1).used;
   hipLaunchKernelGGL(range_kernel<CH>, dim3(nb), dim3(256), 0, st, x, n, n4, alpha, min_value, partials);
   hipLaunchKernelGGL(range_fold_kernel, dim3(1), dim3(256), 0, st, partials, nb, minmax_io);
   return nb;
@@ -401,12 +402,12 @@ extern "C" int p2phd_spectro_encode_ex(const float* spec, int64_t B, int64_t F, 
   float* nnorm = norm4 + 4;
   if (noise != nullptr && mask_rows > 0) {
     const long n = channels * B * mask_rows * F;
-    const int nb = (int)std::min<long>((n + 255) / 256, 1024);
+    const int nb = p2phd::stream_grid_of(p2phd::SG_SPECTRO_STATS, P2PHD_F32, n, 1).used;
     hipLaunchKernelGGL(stats4_kernel, dim3(nb), dim3(256), 0, st, noise, n, npart);
     hipLaunchKernelGGL(finalize4_kernel, dim3(1), dim3(256), 0, st, npart, nb, (double)n, nnorm);
   }
   const long total = channels * B * M * F;
-  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
+  const int blocks = p2phd::stream_grid_of(p2phd::SG_SPECTRO_ENCODE, P2PHD_F32, total, 1).used;
   hipLaunchKernelGGL(encode_pass2_kernel, dim3(blocks), dim3(256), 0, st, log_spectro, norm4, mask_rows > 0 ? noise : nullptr,
                      nnorm, (int)M, (int)F, mask_rows, total, mask_mode, noise_sign);
   return p2phd::check_launch("spectro_encode");

@@ -25,6 +25,7 @@
 // bands: one workgroup per pair, 256 lanes, a tree in LDS.  matrix: grid-stride, float4 where both pitches and pointers allow.
 #include "common.h"
 #include "convplan.h"
+#include "streamgrid.h"
 #include "fft_wave.h"
 #include <algorithm>
 #include <cmath>
@@ -276,8 +277,7 @@ extern "C" int p2phd_stereo_matrix(const float* x, int64_t ld, int64_t L, float 
   const uintptr_t xe = xa + (size_t)(ld + L) * sizeof(float), oe = oa + (size_t)(ld_out + L) * sizeof(float);
   P2PHD_REQUIRE((xa == oa && ld == ld_out) || xe <= oa || oe <= xa, "stereo_matrix: out overlaps x without being x at the same row pitch");
   const int vec = ((xa | oa) & 15) == 0 && ((ld | ld_out) & 3) == 0;
-  const int64_t work = vec ? p2phd::cdiv(L, 4) : L;
-  const int64_t blocks = std::min<int64_t>(std::max<int64_t>(p2phd::cdiv(work, kThreads), 1), 4096);
+  const int blocks = p2phd::stream_grid_of(vec ? p2phd::SG_STEREO_VEC : p2phd::SG_STEREO_SCALAR, P2PHD_F32, L, 2).used;     // (streamgrid.h)
   hipLaunchKernelGGL(stereo_matrix_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, x, (long)ld, (long)L, a, guard_side != 0,
                      out, (long)ld_out, vec);
   ++p2phd::g_launch_count[p2phd::LC_STEREO];

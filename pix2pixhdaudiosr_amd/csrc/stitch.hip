@@ -16,6 +16,7 @@
 // runs on at most half of the samples of a kernel that is a few microseconds long.
 #include "common.h"
 #include "convplan.h"
+#include "streamgrid.h"
 #include <algorithm>
 #include <cstdint>
 
@@ -90,10 +91,7 @@ __global__ __launch_bounds__(kThreads) void segments_stitch_kernel(const float* 
   }
 }
 
-int stream_grid(int64_t elems) {
-  const int64_t quads = (elems + 3) / 4;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(p2phd::cdiv(quads, kThreads), 16384));
-}
+int stream_grid(int64_t elems) { return p2phd::stream_grid_of(p2phd::SG_STITCH, P2PHD_F32, elems, 1).used; }     // (streamgrid.h)
 
 // every row's first element must be 16-byte aligned for the float4 paths: the bases, and the row pitches when C > 1
 bool rows_aligned(const void* a, const void* b, int64_t C, int64_t pitch_a, int64_t pitch_b) {

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "convplan.h"
 #include "convdev.h"
+#include "streamgrid.h"
 #include "fft_wave.h"
 #include <algorithm>
 #include <cmath>
@@ -235,8 +236,7 @@ extern "C" int p2phd_timed_pack_pair(int dtype, const float* lr_frames, const fl
   P2PHD_REQUIRE(dtype == P2PHD_BF16 || dtype == P2PHD_F32, "timed_pack_pair: unsupported dtype %d", dtype);
   P2PHD_REQUIRE(!mode_db || min_value > 0.f, "timed_pack_pair: min_value must be positive in dB mode");
   const int vec4 = ((reinterpret_cast<uintptr_t>(lr_frames) | reinterpret_cast<uintptr_t>(other_frames)) & 15) == 0;
-  const long quads = (long)((n_pixels + 3) / 4);
-  const int grid = (int)std::max<long>(1, std::min<long>((quads + kThreads - 1) / kThreads, 16384));
+  const int grid = p2phd::stream_grid_of(p2phd::SG_PACK_PAIR, dtype, n_pixels, 1).used;      // (streamgrid.h)
   hipStream_t st = (hipStream_t)stream;
 #define P2PHD_PACK(T, DB) \
   hipLaunchKernelGGL((pack_pair_kernel<T, DB>), dim3(grid), dim3(kThreads), 0, st, lr_frames, other_frames, (T*)dst, (long)n_pixels, vec4, min_value)

@@ -13,8 +13,10 @@ and of p2phd_act_bwd_db) have cases of their own, K.IN_CLAMP_CASES and K.ACT_DB_
 column sum (csrc/convaux.hip, launch_colsum) is NOT tested: it engages from about 134 M elements (Cp = 4096 on more than 32 k
 pixels), out of reach of a test of seconds.
 
-Left out on purpose: the AvgPool grid-stride loop (starts at 2 M pieces) and the statistics merges (reached through the conv
-epilogue, covered by tests/test_gpu_conv_exact.py)."""
+Every case here stays under the workgroup caps of the grid-stride loops or just beyond them; the loops' later trips -- AvgPool's
+(8192 workgroups = 2 M pieces), act_bwd's, the losses' and the Adam entries' with the scaler's scan -- are the subject of
+tests/test_gpu_long.py, at 2.5 trips, with the grids pinned by tests/test_long_host.py.  Left out on purpose: the statistics
+merges (reached through the conv epilogue, covered by tests/test_gpu_conv_exact.py)."""
 import ctypes as C
 
 import numpy as np
