@@ -775,7 +775,8 @@ int p2phd_flac_decode_stage(int stage, const void* bytes_dev, int64_t nbytes, co
  * p2phd_flac_encode: the same bytes and the same `lengths` from the payload on the device (any byte alignment), on `stream`.  One
  *   workgroup per frame; it reads nothing outside the payload's channels * L * bits / 8 bytes, writes exactly lengths[nframes] bytes
  *   of stream_dev and the nframes + 1 words of lengths_dev (8-byte aligned), and keeps each frame in a worst-case slot of `workspace`
- *   (8-byte aligned, workspace_bytes >= the plan's) until the gather.  Integer sums only, no float, no atomics on global memory: the
+ *   (8-byte aligned, workspace_bytes >= the plan's) until the gather.  Integer sums only, no float (with the LPC option below: float64 in the
+ *   one routine of its steps 2 and 3, in one lane, from exact integers, in a written order), no atomics on global memory: the
  *   same bytes on every run and stream.  A cap or workspace below the plan's, arguments outside the ranges above, a null or
  *   misaligned pointer: P2PHD_EINVAL, nothing is launched.
  * ---------------------------------------------------------------------------------------- */
@@ -791,6 +792,72 @@ int p2phd_flac_encode(const void* payload_dev, int channels, int bits, int64_t L
  * is then written as zeros (stage 2).  Counts 1. */
 int p2phd_flac_encode_stage(int stage, const void* payload_dev, int channels, int bits, int64_t L, int rate, int block, void* stream_dev, int64_t cap,
                             int64_t* lengths_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FLAC output, LPC, csrc/flacenc.hip: an opt-in extension of the stream contract above.  The option is lpc_order M in 0..12 (12: the
+ * largest order of FLAC's streamable subset up to 48 kHz).  With M = 0 the entries below give the bytes of p2phd_flac_encode_host /
+ * p2phd_flac_encode, through the same kernels.  With M > 0 `block` is at most 16384 (the subset's largest block: a coded channel
+ * as int32 is then 64 KiB); a larger one is refused.  Restated in tests/_flac_lpc_ref.py.
+ *
+ * THE STREAM CONTRACT for M > 0.  The stream is a function of (payload, channels, bits, L, rate, block, M) alone, to the byte: host
+ * encoder, device encoder and restatement are compared with ==.  Per coded channel of a frame, samples x[0..bs), bps as above,
+ * P = 13 bits of coefficient precision:
+ * 1. Analysis signal, integers only.  a[n] = x[n] >> max(0, bps - 16) (arithmetic).  Welch window in integers: d = 2 n - (bs - 1),
+ *    D = bs + 1, W[n] = ((D^2 - d^2) << 15) / D^2 (integer division).  v[n] = (a[n] W[n]) >> 15.  R[l] = sum over n = l .. bs - 1 of
+ *    v[n] v[n - l] for l = 0 .. Mo, Mo = min(M, bs - 1).  |R| < 2^46: exact in int64 in any order of summation, and exact as a
+ *    double.  R[0] = 0: no LPC candidate.
+ * 2. Levinson-Durbin in float64 from double(R): IEEE add, multiply and divide only, in exactly this order, never contracted (the
+ *    one __host__ __device__ routine both encoders call carries #pragma clang fp contract(off)).  err = R[0].  For i = 0 .. Mo - 1:
+ *    acc = R[i + 1]; for j = 0 .. i - 1: acc = acc - lp[j] R[i - j].  k = acc / err.  new[j] = lp[j] - k lp[i - 1 - j] for j < i,
+ *    new[i] = k.  err = err (1 - k k).  If err is not > 0 or not finite: stop, order i + 1 and all higher orders are not admitted.
+ *    Otherwise lp = new is the predictor of order o = i + 1: x^[n] = sum over j of lp[j] x[n - 1 - j].
+ * 3. Quantisation, float64, same rules.  cmax = max |lp[j]|; cmax = 0: the order is not admitted.  frexp(cmax) gives the exponent e;
+ *    shift = P - 1 - e; shift < 0: not admitted; else shift = min(shift, 15).  Error feedback in index order: ee = ee + ldexp(lp[j],
+ *    shift); q[j] = ee rounded half away from zero (floor(ee + 0.5) for ee >= 0, -floor(-ee + 0.5) otherwise), clamped to
+ *    -2^12 .. 2^12 - 1; ee = ee - q[j].
+ * 4. Residual.  r[n] = x[n] - ((sum over j < o of q[j] x[n - 1 - j]) >> shift) for n >= o, the sum in 64 bits, the shift arithmetic.
+ *    An order is admitted only where every |r[n]| < 2^28 (an integer maximum: order-free), which keeps the widths of the Rice sums.
+ *    Real payloads reach it (a low-passed block with full-scale alternation at its ends, which the window hides from the fit):
+ *    tests/_flac_lpc_cases.py, bound_side.
+ * 5. Cost of LPC (o, p), admitted where (bs >> p) > o, p in the range above: 8 + o bps + 4 + 5 + o P + 2 + 4 + the partitions' bits,
+ *    exactly as FIXED counts them: the same k ranges, the same smaller-k tie rule.
+ * 6. Choice.  The subframe is first chosen as above: CONSTANT, else VERBATIM, else FIXED.  An LPC pair replaces it only where its
+ *    bits are strictly fewer; among LPC pairs of equal bits the smaller p, then the smaller o.  All orders 1 .. Mo are tried: no order
+ *    estimate, no heuristic.  The stereo assignment is taken from the four best bit counts as above.
+ * Written: subframe type 32 | (o - 1), the o warm-up samples, precision - 1 = 12 in 4 bits, the shift in 5, the o coefficients in 13
+ *   bits each, then the residual as a FIXED subframe's.
+ * Consequences: the predictor of order o does not depend on M, so a frame never grows with M, and p2phd_flac_encode_plan's worst case
+ *   still bounds the stream and the workspace.
+ * Float: the decisions stay exact integer bit counts.  Float64 appears in steps 2 and 3 alone; they run in one thread (host) or one
+ *   lane (device), from exact integers, in the written order -- which is what makes their bits the same on both.
+ *
+ * HOST only:
+ * p2phd_flac_lpc_analyse: steps 1 to 3 of one block: `samples` int32 [bs] (1 <= bs <= 16384, each fitting bps, bps 16 / 17 / 24 / 25),
+ *   lpc_order M in 1..12 -> R int64 [13] (zeros above Mo); per order o = 1 .. 12, row o - 1: admitted[o - 1] (1 / 0: by steps 2 and
+ *   3; the residual bound of step 4 is the encoders'), shift[o - 1], q int32 [12][12] (row o - 1: its o coefficients, zeros behind;
+ *   all zeros where not admitted).
+ * p2phd_flac_lpc_fit: steps 2 and 3 alone, through the routine both encoders call, from any R int64 [orders + 1] (orders in 0..12, each
+ *   |R[l]| < 2^53) -> admitted, q, shift as above.  It exists so that the stop rule of step 2 can be held to the restatement: the
+ *   autocorrelation of a windowed block is positive definite, and no block was found whose err ends <= 0 (a pure alternating +-A does
+ *   not: the window keeps |k| below 1), so the tests feed it sequences R that no block produces.
+ * p2phd_flac_encode_lpc_host: p2phd_flac_encode_host with the option.
+ * DEVICE:
+ * p2phd_flac_encode_lpc: p2phd_flac_encode with the option; the same plan, the same workspace, the same refusals, and still 3
+ *   launches of the family "flacenc".  M > 0 runs the frame kernel's LPC instantiation: the workgroup keeps the coded channel's
+ *   block as int32 and its analysis signal as int16 in dynamic LDS beside the state of the other instantiation (4 bytes a sample; the
+ *   analysis signal in the LDS of the Rice sums where it fits, else 2 bytes a sample more: at most 139 920 bytes a workgroup), each lane sums its products v v into M + 1 int64 that are folded with LDS integer adds, lane 0 runs steps 2 and
+ *   3, and every admitted order goes through the Rice sums and the partition fold of the FIXED orders with its residuals read from
+ *   the image.  No atomics on global memory, no float outside lane 0's routine.
+ * p2phd_flac_encode_lpc_stage: p2phd_flac_encode_stage with the option (measurement only, counts 1).
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_flac_lpc_fit(const int64_t* R, int orders, int32_t* admitted, int32_t* q, int32_t* shift);
+int p2phd_flac_lpc_analyse(const int32_t* samples, int bs, int bps, int lpc_order, int32_t* admitted, int32_t* q, int32_t* shift, int64_t* R);
+int p2phd_flac_encode_lpc_host(const void* payload, int channels, int bits, int64_t L, int rate, int block, int lpc_order, void* stream, int64_t cap,
+                               int64_t* lengths);
+int p2phd_flac_encode_lpc(const void* payload_dev, int channels, int bits, int64_t L, int rate, int block, int lpc_order, void* stream_dev, int64_t cap,
+                          int64_t* lengths_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int p2phd_flac_encode_lpc_stage(int stage, const void* payload_dev, int channels, int bits, int64_t L, int rate, int block, int lpc_order, void* stream_dev,
+                                int64_t cap, int64_t* lengths_dev, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Activation tensors of the conv stack are NHWC ("channels last": [N, H, W, Cp]) with the channel

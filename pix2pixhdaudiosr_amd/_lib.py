@@ -107,6 +107,11 @@ SIGNATURES = {
     "p2phd_flac_encode_host": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp]),
     "p2phd_flac_encode": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "p2phd_flac_encode_stage": (_i32, [_i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "p2phd_flac_lpc_fit": (_i32, [_vp, _i32, _vp, _vp, _vp]),
+    "p2phd_flac_lpc_analyse": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "p2phd_flac_encode_lpc_host": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "p2phd_flac_encode_lpc": (_i32, [_vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "p2phd_flac_encode_lpc_stage": (_i32, [_i32, _vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
     "p2phd_channel_pitch": (_i32, [_i32]),
     "p2phd_conv_out_size": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "p2phd_conv_kmajor_ok": (_i32, [_vp]),

@@ -165,6 +165,8 @@ def verify(path):
 
 # ---- writer ------------------------------------------------------------------------------------------------------------------
 DEFAULT_BLOCK = 4096
+MAX_LPC_ORDER = 12                                                          # the option lpc_order: 0 (off) .. 12
+MAX_LPC_BLOCK = 16384                                                       # the largest block with lpc_order > 0
 ENCODINGS = {"pcm16": 16, "pcm24": 24}                                      # what a FLAC stream of this build holds
 
 
@@ -190,8 +192,18 @@ def encode_plan(channels, bits, total, block=DEFAULT_BLOCK):
     return int(out[0]), int(out[1]), int(out[2])
 
 
-def encode(samples_or_payload, channels=None, bits=16, rate=44100, block=DEFAULT_BLOCK):
-    """The host encoder (p2phd_flac_encode_host, one thread, no device).  `samples_or_payload`: the interleaved little-endian PCM
+def check_lpc(lpc_order, block, what="flacio"):
+    """The LPC option's refusals (include/p2phd.h, "FLAC output, LPC"): an int in 0 .. MAX_LPC_ORDER, and with it a block of at most
+    MAX_LPC_BLOCK."""
+    if isinstance(lpc_order, bool) or not isinstance(lpc_order, int) or not 0 <= lpc_order <= MAX_LPC_ORDER:
+        raise ValueError("%s: the LPC order must be an int in 0 .. %d, got %r" % (what, MAX_LPC_ORDER, lpc_order))
+    if lpc_order > 0 and int(block) > MAX_LPC_BLOCK:
+        raise ValueError("%s: with LPC subframes the FLAC block size is at most %d, got %r" % (what, MAX_LPC_BLOCK, block))
+
+
+def encode(samples_or_payload, channels=None, bits=16, rate=44100, block=DEFAULT_BLOCK, lpc_order=0):
+    """The host encoder (p2phd_flac_encode_host, one thread, no device; with lpc_order M > 0 p2phd_flac_encode_lpc_host: every LPC order
+    1 .. M is tried beside the fixed predictors, block at most 16384).  `samples_or_payload`: the interleaved little-endian PCM
     payload of `channels` channels as a bytes-like object, or an integer array [channels, samples] (or [samples]) whose values fit
     `bits` -> (the frames back to back as bytes, lengths: int64 [frames + 1], each frame's bytes and their total)."""
     if isinstance(samples_or_payload, np.ndarray) and samples_or_payload.dtype != np.uint8:
@@ -207,6 +219,7 @@ def encode(samples_or_payload, channels=None, bits=16, rate=44100, block=DEFAULT
         if channels is None:
             raise ValueError("flacio.encode: a payload needs its channel count")
     check_output(channels, bits, rate, block, "flacio.encode")
+    check_lpc(lpc_order, block, "flacio.encode")
     align = int(channels) * bits // 8
     if payload.size == 0 or payload.size % align:
         raise ValueError("flacio.encode: %d bytes are not one or more whole frames of %d x %d bit" % (payload.size, channels, bits))
@@ -215,8 +228,12 @@ def encode(samples_or_payload, channels=None, bits=16, rate=44100, block=DEFAULT
     out = np.empty(worst, dtype=np.uint8)
     lengths = np.zeros(frames + 1, dtype=np.int64)
     payload = np.ascontiguousarray(payload)
-    if _lib().p2phd_flac_encode_host(ctypes.c_void_p(payload.ctypes.data), int(channels), int(bits), total, int(rate), int(block),
-                                     ctypes.c_void_p(out.ctypes.data), worst, ctypes.c_void_p(lengths.ctypes.data)) != 0:
+    if lpc_order:
+        if _lib().p2phd_flac_encode_lpc_host(ctypes.c_void_p(payload.ctypes.data), int(channels), int(bits), total, int(rate), int(block), lpc_order,
+                                             ctypes.c_void_p(out.ctypes.data), worst, ctypes.c_void_p(lengths.ctypes.data)) != 0:
+            raise _err("flac_encode_lpc_host")
+    elif _lib().p2phd_flac_encode_host(ctypes.c_void_p(payload.ctypes.data), int(channels), int(bits), total, int(rate), int(block),
+                                       ctypes.c_void_p(out.ctypes.data), worst, ctypes.c_void_p(lengths.ctypes.data)) != 0:
         raise _err("flac_encode_host")
     return out[:int(lengths[-1])].tobytes(), lengths
 

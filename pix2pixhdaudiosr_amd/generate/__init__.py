@@ -89,7 +89,8 @@ Folder mode lists *.flac only with `--input_formats wav,flac` (`plan_folder(...,
 
 `--container flac` (opt-in, csrc/flacenc.hip) writes a FLAC stream instead of a wav: the payload `pcm_encode` leaves on the device goes
 through `flac_encode` there -- one workgroup per frame, fixed predictors, Rice partitions and the stereo assignments chosen on exact
-bit counts -- and the file, decoded, is the wav's data chunk byte for byte.  `--flac_block N` sets the frame length, `--flac_md5`
+bit counts -- and the file, decoded, is the wav's data chunk byte for byte.  `--flac_lpc N` also tries LPC subframes of every order
+up to N (a predictor fitted per block, still chosen on exact bit counts; the file is never longer), `--flac_block N` sets the frame length, `--flac_md5`
 brings the payload back as well and writes its MD5; a folder's outputs are then named .flac (`plan_folder(..., ext=)`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401

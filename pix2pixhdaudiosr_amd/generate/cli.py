@@ -317,6 +317,9 @@ def _parser():
     ap.add_argument("--flac_md5", action="store_true",
                     help="--container flac: write the MD5 of the samples into STREAMINFO; the payload is then copied back beside the "
                          "stream, a second copy of the payload's size (default: off, the MD5 field is zeros)")
+    ap.add_argument("--flac_lpc", type=int, default=None, metavar="N",
+                    help="--container flac: also try LPC subframes of every order 1 .. N, N in 0 .. 12 (a predictor fitted per block; "
+                         "--flac_block at most 16384); the file is never longer than without (default: off)")
     ap.add_argument("--fp16", action="store_true", help="16-bit activation storage")
     ap.add_argument("--mdct_type", default=None, choices=("mdct2", "mdct4"),
                     help="transform of the checkpoint (default: the options file's, else $P2PHD_MDCT_TYPE, else mdct2 -- "
@@ -325,9 +328,9 @@ def _parser():
 
 
 def _print_flac(path, f, encoding):
-    print('%s: FLAC %d bit, %d frames of %d, %d bytes (%.1f %% of the PCM)%s'
+    print('%s: FLAC %d bit, %d frames of %d, %d bytes (%.1f %% of the PCM)%s%s'
           % (path, 24 if encoding == 'pcm24' else 16, f['frames'], f['block'], f['bytes'], 100.0 * f['bytes'] / f['pcm_bytes'],
-             '' if f['md5'] is None else ', MD5 ' + f['md5']))
+             '' if f['md5'] is None else ', MD5 ' + f['md5'], ', LPC up to order %d' % f['lpc'] if f.get('lpc') else ''))
 
 
 def _print_spectrogram(p):
@@ -359,8 +362,10 @@ def main(argv=None):
             picture['input_formats'] = check_input_formats(a.input_formats, "generate")
         if a.verify_input:
             picture['verify_input'] = True
-        if check_container(a.container, a.flac_block, a.flac_md5, a.encoding, a.output_rate or 48000, "generate") is not None:
-            picture.update(container=a.container, **{k: v for k, v in (('flac_block', a.flac_block), ('flac_md5', a.flac_md5 or None)) if v is not None})
+        if check_container(a.container, a.flac_block, a.flac_md5, a.encoding, a.output_rate or 48000, "generate",
+                           **({} if a.flac_lpc is None else dict(flac_lpc=a.flac_lpc))) is not None:
+            picture.update(container=a.container, **{k: v for k, v in (('flac_block', a.flac_block), ('flac_md5', a.flac_md5 or None), ('flac_lpc', a.flac_lpc))
+                                                     if v is not None})
         if a.limiter or a.limiter_lookahead_ms is not None or a.limiter_hold_ms is not None:
             check_limiter(a.limiter, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, 48000, "generate")
             picture.update(limiter=True, limiter_lookahead_ms=a.limiter_lookahead_ms, limiter_hold_ms=a.limiter_hold_ms)

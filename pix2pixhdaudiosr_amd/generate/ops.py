@@ -127,17 +127,20 @@ def flac_decode(bytes_dev, table, info, check=True):
     return out
 
 
-def flac_encode(payload, channels, bits, rate, block=None):
+def flac_encode(payload, channels, bits, rate, block=None, lpc_order=0):
     """payload: uint8 tensor on the GPU, the interleaved little-endian samples pcm_encode leaves ('pcm16': bits 16, 'pcm24': bits 24;
     a view at any byte offset) -> (stream, lengths) on the GPU: `stream` a uint8 tensor of the plan's worst-case size whose first
     lengths[-1] bytes are the FLAC frames back to back (bytes behind them are not written), `lengths` int64 [frames + 1], each frame's
     bytes and their total -- what data/flacio.py's write_stream puts behind its header, and byte for byte what flacio.encode gives for
-    the same payload (p2phd_flac_encode: three launches of the family "flacenc").  `block`: samples per frame (None: 4096).  Nothing
+    the same payload (p2phd_flac_encode: three launches of the family "flacenc").  `block`: samples per frame (None: 4096).
+    `lpc_order` M in 0 .. 12: with M > 0 every LPC order 1 .. M is tried beside the fixed predictors (p2phd_flac_encode_lpc, the frame
+    kernel's LPC instantiation, still three launches; block at most 16384), byte for byte flacio.encode(..., lpc_order=M).  Nothing
     is waited for."""
     from ..data import flacio
     b = _lib.require_gpu_tensor(payload, "flac_encode: payload", torch.uint8)
     block = flacio.DEFAULT_BLOCK if block is None else block
     flacio.check_output(channels, bits, rate, block, "flac_encode")
+    flacio.check_lpc(lpc_order, block, "flac_encode")
     align = int(channels) * int(bits) // 8
     if b.dim() != 1 or b.numel() == 0 or b.numel() % align:
         raise ValueError("flac_encode: %s bytes are not one or more whole frames of %d x %d bit" % (tuple(b.shape), channels, bits))
@@ -146,6 +149,10 @@ def flac_encode(payload, channels, bits, rate, block=None):
     stream = torch.empty((worst,), dtype=torch.uint8, device=b.device)
     lengths = torch.empty((frames + 1,), dtype=torch.int64, device=b.device)
     work = torch.empty((nwork // 8,), dtype=torch.int64, device=b.device)
+    if lpc_order:
+        _lib.check(_lib.lib().p2phd_flac_encode_lpc(_lib.ptr(b), int(channels), int(bits), L, int(rate), int(block), lpc_order, _lib.ptr(stream), worst,
+                                                    _lib.ptr(lengths), _lib.ptr(work), nwork, _lib.stream_ptr()), "flac_encode_lpc")
+        return stream, lengths
     _lib.check(_lib.lib().p2phd_flac_encode(_lib.ptr(b), int(channels), int(bits), L, int(rate), int(block), _lib.ptr(stream), worst, _lib.ptr(lengths),
                                             _lib.ptr(work), nwork, _lib.stream_ptr()), "flac_encode")
     return stream, lengths

@@ -687,15 +687,21 @@ def check_input_formats(formats, who="plan_folder"):
 
 CONTAINERS = ('wav', 'flac')                                                # what the per-file flow can write
 FLAC_BLOCK = 4096                                                           # samples per FLAC frame where none is asked for
+FLAC_LPC_MAX = 12                                                           # the largest LPC order of the option flac_lpc
+FLAC_LPC_BLOCK = 16384                                                      # the largest block with flac_lpc > 0
 
 
-def check_container(container, flac_block, flac_md5, encoding, rate, who):
+def check_container(container, flac_block, flac_md5, encoding, rate, who, flac_lpc=None):
     """The container option of enhance_file / enhance_folder -> None ('wav': nothing changes), or {'block', 'md5'} for 'flac'.
     `rate`: the rate that will be written.  A ValueError each: an unknown container; flac_block or flac_md5 without 'flac';
-    'flac' with an encoding that is not integer PCM, a block outside 16 .. 65535, a rate above 1048575 (STREAMINFO has 20 bits)."""
+    'flac' with an encoding that is not integer PCM, a block outside 16 .. 65535, a rate above 1048575 (STREAMINFO has 20 bits).
+    `flac_lpc`: None, or the largest LPC order M the encoder tries, an int in 0 .. 12; the dict gains 'lpc': M where M > 0.  A
+    ValueError: without 'flac', outside the range, or M > 0 with a block above 16384."""
     if container not in CONTAINERS:
         raise ValueError("%s: container must be one of %s, got %r" % (who, list(CONTAINERS), container))
     if container == 'wav':
+        if flac_lpc is not None:
+            raise ValueError("%s: flac_lpc is an option of container='flac'; container is 'wav'" % who)
         if flac_block is not None or flac_md5:
             raise ValueError("%s: flac_block / flac_md5 are options of container='flac'; container is 'wav'" % who)
         return None
@@ -706,6 +712,13 @@ def check_container(container, flac_block, flac_md5, encoding, rate, who):
         raise ValueError("%s: flac_block must be an int in 16 .. 65535, got %r" % (who, flac_block))
     if not 1 <= int(rate) <= 1048575:
         raise ValueError("%s: container='flac' states the rate in 20 bits: at most 1048575 Hz, got %r" % (who, rate))
+    if flac_lpc is not None:
+        if isinstance(flac_lpc, bool) or not isinstance(flac_lpc, int) or not 0 <= flac_lpc <= FLAC_LPC_MAX:
+            raise ValueError("%s: flac_lpc must be an int in 0 .. %d, got %r" % (who, FLAC_LPC_MAX, flac_lpc))
+        if flac_lpc > 0 and block > FLAC_LPC_BLOCK:
+            raise ValueError("%s: with flac_lpc > 0 flac_block is at most %d, got %r" % (who, FLAC_LPC_BLOCK, block))
+        if flac_lpc > 0:
+            return {'block': block, 'md5': bool(flac_md5), 'lpc': flac_lpc}
     return {'block': block, 'md5': bool(flac_md5)}
 
 

@@ -468,7 +468,7 @@ class SuperResolver:
         likewise: a second copy of the payload's size), 'pcm_bytes', 'total' and 'rate'."""
         bits = {'pcm16': 16, 'pcm24': 24}[encoding]
         rate = int(self.opt.hr_sampling_rate if rate is None else rate)
-        stream, lengths = flac_encode(dev, channels, bits, rate, flac['block'])
+        stream, lengths = flac_encode(dev, channels, bits, rate, flac['block'], **_set(lpc_order=flac.get('lpc')))
         flac.update(lengths={'packed': lengths.view(torch.uint8)}, pcm_bytes=dev.numel(), total=dev.numel() // (channels * bits // 8), rate=rate, bits=bits)
         extra = {'flac': flac['lengths']}
         if flac['md5']:
@@ -574,7 +574,7 @@ class SuperResolver:
             md5 = hashlib.md5(flac['pcm']['packed'].numpy()).digest() if flac['md5'] else None
             n = flacio.write_stream(path_out, host.numpy(), lengths, flac['rate'], channels, flac['bits'], flac['total'], flac['block'], md5)
             flac['result'] = {'block': flac['block'], 'frames': len(lengths) - 1, 'bytes': n, 'pcm_bytes': flac['pcm_bytes'],
-                              'md5': None if md5 is None else md5.hex()}
+                              'md5': None if md5 is None else md5.hex(), **_set(lpc=flac.get('lpc'))}
             return
         wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate if rate is None else rate), channels, encoding)
 
@@ -709,7 +709,7 @@ class SuperResolver:
     def _options(self, who, folder, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                  spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                  loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False):
+                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
         """The options of enhance_file (`folder` False) / enhance_folder (True), validated before a file is opened -> _Options.
         The order of the checks decides which ValueError a bad combination raises first: it does not move."""
         hr_rate = self.opt.hr_sampling_rate
@@ -722,7 +722,7 @@ class SuperResolver:
         spec = self._spectrogram_spec(spectrogram, spectrogram_channel, spectrogram_opts, who)
         loud = self._loudness_at(check_loudness(loudness, hr_rate, who, loudness_max_gain_db, loudness_range), rc, who)
         album = check_loudness_scope(loudness_scope, loud, who, folder, limiter, spectrogram, album_cache_bytes)
-        fl = check_container(container, flac_block, flac_md5, encoding, out_rate, who)
+        fl = check_container(container, flac_block, flac_md5, encoding, out_rate, who, **_set(flac_lpc=flac_lpc))
         return _Options(stage, tp, lim, spec, loud, bw, st, rc, album, fl)
 
     # -- one file: the stages of the flow, in the order their launches take on the stream ------------------------------
@@ -864,7 +864,7 @@ class SuperResolver:
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
-                     dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False):
+                     dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -986,14 +986,16 @@ class SuperResolver:
         wav would have held, byte for byte.  The frames come back at their worst-case size -- about what the wav path copies -- with
         their lengths behind the same one synchronisation, and the host writes "fLaC", STREAMINFO and the frames.  `flac_block`:
         samples per frame, 16 .. 65535 (None: 4096).  `flac_md5`: also bring the payload back (a second copy of its size) and write
-        its MD5 into STREAMINFO, which is otherwise zeros ("not computed").  The result gains 'flac': {'block', 'frames', 'bytes'
+        its MD5 into STREAMINFO, which is otherwise zeros ("not computed").  `flac_lpc`: None, or the largest LPC order M in 0 .. 12 the
+        encoder tries beside the fixed predictors (include/p2phd.h, "FLAC output, LPC": every order 1 .. M, chosen on exact bit counts,
+        the file never longer than without it; flac_block at most 16384 with M > 0); 'flac' then gains 'lpc': M.  The result gains 'flac': {'block', 'frames', 'bytes'
         (the file's), 'pcm_bytes' (the payload's), 'md5' (hex, or None)}; None where no file is written.  encoding 'float32', more
         than 8 written channels, a block outside the range, a written rate above 1048575 Hz, or either option without 'flac': a
         ValueError before the output is opened."""
         o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None))
+                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc))
         read = self._read(path_in, **_set(verify=True if verify_input else None))
         res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
@@ -1020,7 +1022,7 @@ class SuperResolver:
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
                        stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
-                       verify_input=False, container='wav', flac_block=None, flac_md5=False):
+                       verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -1076,7 +1078,7 @@ class SuperResolver:
         o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None))
+                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc))
         plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
         written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
         if o.album is not None:

@@ -15,7 +15,9 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             p2phd_pcm_decode, on the clip and on an hour of it; the host index and host decoder alone; log in --flac_log
   flacout   (only when asked for) the output side: enhance_file with container wav / flac / flac with flac_md5 on one 15 s mono and one
             stereo clip, interleaved, median and spread of --reps; then by events p2phd_flac_encode beside p2phd_pcm_encode_ex on the
-            written payloads, on the clip and on an hour of it; the host encoder alone; the streams' sizes; log in --flacout_log
+            written payloads, on the clip and on an hour of it; the host encoder alone; the streams' sizes; log in --flacout_log;
+            with --flac_lpc N instead: container flac with flac_lpc=N against without, p2phd_flac_encode_lpc beside p2phd_flac_encode by
+            events on the clip and on the hour, the frame kernel's two instantiations alone, the sizes at M = 0, 4, 8, 12; log in --flaclpc_log
 
   folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
             ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
@@ -106,6 +108,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
         python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
         python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
+        python tools/time_generate.py flacout [--flac_lpc 12] [--flacout_log profiles/time_generate_flacout.log] [--flaclpc_log profiles/time_generate_flaclpc.log]
 """
 import argparse
 import os
@@ -1188,6 +1191,118 @@ def run_flacout(seconds, reps, log):
             f.write(text)
 
 
+def run_flaclpc(seconds, reps, log, M):
+    """flacout --flac_lpc M: the LPC option of the FLAC writer.  File to file: enhance_file with container 'flac' without the option and
+    with flac_lpc=M on one mono and one stereo 16-bit clip, interleaved.  Then, by events, p2phd_flac_encode_lpc (generate.flac_encode
+    with lpc_order=M: its allocations in front) beside p2phd_flac_encode on the written payloads, on the clip and on an hour of it,
+    and the frame kernel alone (p2phd_flac_encode_lpc_stage beside p2phd_flac_encode_stage); the host encoder on the clip; and the
+    streams' sizes at M = 0, 4, 8, 12.  The clips are the synthetic partials of the other modes through an untrained model."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd import _lib
+    from pix2pixhdaudiosr_amd.data import flacio, wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, flac_encode
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py flacout --flac_lpc %d: one %g s clip at %d Hz (%d samples per channel), mono and stereo, pcm16, block size 4096; %d "
+             "interleaved repeats" % (M, seconds, rate, x.shape[-1], reps)]
+    payloads = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        sr = SuperResolver(model, opt, overlap=0.25)
+        for tag, clip in (("mono", 0.5 * x), ("stereo", torch.cat([0.5 * x, 0.4 * x.flip(-1) + 0.1 * x]))):
+            src = os.path.join(tmp, tag + "_in.wav")
+            wavio.save(src, clip.cpu(), rate)
+            pw, pf = os.path.join(tmp, tag + ".wav"), os.path.join(tmp, tag + ".flac")
+            runs = [("%s: container flac          " % tag, lambda: sr.enhance_file(src, pf, channels='all', container='flac')),
+                    ("%s: container flac, flac_lpc=%-2d" % (tag, M), lambda: sr.enhance_file(src, pf, channels='all', container='flac', flac_lpc=M))]
+            for _, fn in runs:
+                fn(); fn()
+            torch.cuda.synchronize()
+            ts = [[] for _ in runs]
+            for _ in range(reps):
+                for k, (_, fn) in enumerate(runs):
+                    torch.manual_seed(3)
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            for (name, _), tk in zip(runs, ts):
+                lines.append("%s  median %8.3f ms   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                             % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+            torch.manual_seed(3)
+            sr.enhance_file(src, pw, channels='all')
+            pay, _ = wavio.read_payload(pw)
+            payloads[tag] = (bytes(pay), clip.shape[0])
+            sizes = []
+            for order in (0, 4, 8, 12):
+                torch.manual_seed(3)
+                res = sr.enhance_file(src, pf, channels='all', container='flac', flac_lpc=order)
+                data = open(pf, "rb").read()
+                meta, table = flacio.index_bytes(data)
+                assert flacio.decode_frames(data, table, 0, len(table), clip.shape[0]).T.astype("<i2").tobytes() == payloads[tag][0]
+                sizes.append("M = %d: %d bytes (%.1f %%)" % (order, res['flac']['bytes'], 100.0 * res['flac']['bytes'] / res['flac']['pcm_bytes']))
+            lines.append("%s, the synthetic clip through the untrained model, %d bytes of PCM: %s" % (tag, len(pay), "; ".join(sizes)))
+    for tag, (pay, C) in payloads.items():
+        dev = torch.frombuffer(bytearray(pay), dtype=torch.uint8).cuda()
+        L = len(pay) // (2 * C)
+        copies = 3600 * rate // L
+        for name, b in (("the clip", dev), ("an hour", dev.repeat(copies))):
+            n = b.numel() // (2 * C)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ks = [[], []]
+            for _ in range(reps + 2):
+                ev[0].record()
+                out0 = flac_encode(b, C, 16, rate)
+                ev[1].record()
+                out1 = flac_encode(b, C, 16, rate, lpc_order=M)
+                ev[2].record()
+                torch.cuda.synchronize()
+                ks[0].append(ev[0].elapsed_time(ev[1]) * 1e3)
+                ks[1].append(ev[1].elapsed_time(ev[2]) * 1e3)
+                totals = (int(out0[1][-1].item()), int(out1[1][-1].item()))
+                del out0, out1
+            lines.append("by events on %s, %s (median of %d, allocations in front; %d samples per channel, %d frames): p2phd_flac_encode %.1f us (spread %.1f), %d bytes; "
+                         "p2phd_flac_encode_lpc, lpc_order %d, %.1f us (spread %.1f), %d bytes: %.2f times the time, %.3f of the bytes"
+                         % (name, tag, reps, n, -(-n // 4096), _median(ks[0][2:]), max(ks[0][2:]) - min(ks[0][2:]), totals[0], M, _median(ks[1][2:]),
+                            max(ks[1][2:]) - min(ks[1][2:]), totals[1], _median(ks[1][2:]) / _median(ks[0][2:]), totals[1] / totals[0]))
+            lines.append("runs: flac_encode %s; flac_encode lpc_order %d %s" % (" ".join("%.1f" % v for v in ks[0][2:]), M, " ".join("%.1f" % v for v in ks[1][2:])))
+            nf, worst, nwork = flacio.encode_plan(C, 16, n, 4096)
+            ks = [[], []]
+            for _ in range(reps + 2):
+                ev[0].record()
+                for k in range(2):
+                    stream = torch.empty((worst,), dtype=torch.uint8, device=b.device)
+                    lens = torch.empty((nf + 1,), dtype=torch.int64, device=b.device)
+                    work = torch.empty((nwork // 8,), dtype=torch.int64, device=b.device)
+                    if k == 0:
+                        _lib.check(_lib.lib().p2phd_flac_encode_stage(1, _lib.ptr(b), C, 16, n, rate, 4096, _lib.ptr(stream), worst, _lib.ptr(lens), _lib.ptr(work), nwork,
+                                                                      _lib.stream_ptr()), "flac_encode_stage")
+                    else:
+                        _lib.check(_lib.lib().p2phd_flac_encode_lpc_stage(1, _lib.ptr(b), C, 16, n, rate, 4096, M, _lib.ptr(stream), worst, _lib.ptr(lens), _lib.ptr(work),
+                                                                          nwork, _lib.stream_ptr()), "flac_encode_lpc_stage")
+                    ev[k + 1].record()
+                torch.cuda.synchronize()
+                ks[0].append(ev[0].elapsed_time(ev[1]) * 1e3)
+                ks[1].append(ev[1].elapsed_time(ev[2]) * 1e3)
+                del stream, lens, work
+            lines.append("by events on %s, %s: flacenc_frames_kernel alone %.1f us (spread %.1f), its LPC instantiation at lpc_order %d %.1f us (spread %.1f): %.2f times"
+                         % (name, tag, _median(ks[0][2:]), max(ks[0][2:]) - min(ks[0][2:]), M, _median(ks[1][2:]), max(ks[1][2:]) - min(ks[1][2:]),
+                            _median(ks[1][2:]) / _median(ks[0][2:])))
+        th = [[], []]
+        for _ in range(reps):
+            for k, order in enumerate((0, M)):
+                t0 = time.perf_counter()
+                flacio.encode(pay, C, 16, rate, lpc_order=order)
+                th[k].append((time.perf_counter() - t0) * 1e3)
+        lines.append("on the host, one thread, the clip, %s: p2phd_flac_encode_host median %.3f ms (spread %.3f); p2phd_flac_encode_lpc_host, lpc_order %d, %.3f ms (spread %.3f)"
+                     % (tag, _median(th[0]), max(th[0]) - min(th[0]), M, _median(th[1]), max(th[1]) - min(th[1])))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_normscope(seconds, reps, log, off_only=False):
     """enhance_file on a mono clip, file to file: norm_scope 'group' (an object built without the option) and 'clip', interleaved;
     then p2phd_spectro_range, p2phd_range_fold and p2phd_spectro_encode_given alone, by events, on one group's spectrum beside
@@ -1483,11 +1598,15 @@ def main():
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--flacout_log", default=os.path.join(ROOT, "profiles", "time_generate_flacout.log"))
+    ap.add_argument("--flac_lpc", type=int, default=None, metavar="N", help="flacout mode: time the LPC option at order N against the writer without it (log in --flaclpc_log)")
+    ap.add_argument("--flaclpc_log", default=os.path.join(ROOT, "profiles", "time_generate_flaclpc.log"))
     ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
     ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
+    if a.mode == "flacout" and a.flac_lpc is not None:
+        return run_flaclpc(a.seconds, 9 if a.reps is None else a.reps, a.flaclpc_log, a.flac_lpc)
     if a.mode == "flacout":
         return run_flacout(a.seconds, 9 if a.reps is None else a.reps, a.flacout_log)
     if a.mode == "flac":
