@@ -99,7 +99,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * pre-pass and the encode under a given range of its norm_scope='clip', csrc/spectro.hip: one per call that launches anything),
  * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip), "flac" (the two kernels of its FLAC input,
  * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), "flacenc" (the three kernels of its FLAC output, csrc/flacenc.hip:
- * a p2phd_flac_encode counts 3), and the weight packs of p2phd_conv_pack_weights /
+ * a p2phd_flac_encode counts 3), "wavcodec" (the G.711 and IMA ADPCM decoders of its coded WAV input, csrc/wavcodec.hip: one per
+ * call with frames > 0), and the weight packs of p2phd_conv_pack_weights /
  * p2phd_conv_fp8_pack_weights, one family per kernel of csrc/wpack.hip, counted per launch plan: "wpack_generic" (the tap walk),
  * "wpack_dense", "wpack_transposed" (the two LDS re-orderings), "wpack_kmajor" (cast of K-major master weights), "wpack_kmajor_t"
  * (their per-tap transpose), "wpack_merged" (merged sub-pixel launches, either tap order), "wpack_fp8" (the e4m3 quantiser with
@@ -729,6 +730,69 @@ int p2phd_flac_decode(const void* bytes_dev, int64_t nbytes, const int64_t* tabl
  * out is not written) or the element-wise kernel alone (stage 2: it reads whatever the workspace holds).  Counts 1. */
 int p2phd_flac_decode_stage(int stage, const void* bytes_dev, int64_t nbytes, const int64_t* table_dev, int64_t nframes, int channels, int bits,
                             float* out, int64_t ld, void* workspace, uint64_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Coded WAV input, csrc/wavcodec.hip: RIFF/WAVE data chunks that hold G.711 mu-law (format tag 7), G.711 A-law (tag 6) or 4-bit
+ * IMA/DVI ADPCM (tag 0x11) for the feeder (host decoders) and for whole-file generation (device decoders).  Launch family
+ * "wavcodec" (a p2phd_g711_decode or p2phd_ima_decode with frames > 0 counts 1).  Integer arithmetic; a coded file decodes to exactly
+ * the samples its PCM16 twin holds, and every sample is scaled as data/wavio.py scales 16-bit PCM: float32(int16) * (1 / 32768).
+ * Restated in tests/_wavcodec_ref.py; MS ADPCM (tag 2), GSM 6.10, G.726 and MP3-in-WAV are not built (data/wavio.py refuses them).
+ *
+ * mu-law byte b:  u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84;
+ *                 sample = u & 0x80 ? -mag : mag                                                        (within +-32124)
+ * A-law byte b:   a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+ *                 sample = a & 0x80 ? mag : -mag                                                        (within +-32256)
+ * A G.711 payload is interleaved: byte n * C + c is frame n of channel c.
+ *
+ * IMA ADPCM, the block layout of a WAVE file: a block is `block_align` bytes.  Per channel it starts with a 4-byte header -- int16
+ * little-endian predictor, uint8 step index, one ignored byte -- and the predictor is the block's first output sample of that
+ * channel.  After the C headers come groups of 4 * C bytes: 4 bytes (8 nibbles) of channel 0, 4 of channel 1, ...; the low nibble of
+ * a byte comes first.  Samples per block: spb = 1 + 8 * (block_align - 4 * C) / (4 * C), which needs block_align >= 8 * C and
+ * (block_align - 4 * C) % (4 * C) == 0.  The step for nibble n with st = STEP[index]:
+ *     d = (st >> 3) + (n & 1 ? st >> 2 : 0) + (n & 2 ? st >> 1 : 0) + (n & 4 ? st : 0)
+ *     pred = clamp(n & 8 ? pred - d : pred + d, -32768, 32767);   index = clamp(index + {-1, -1, -1, -1, 2, 4, 6, 8}[n & 7], 0, 88)
+ * with STEP the 89-entry table 7, 8, 9, ..., 32767.  A header's step index is clamped to 0 .. 88 where it is loaded, by every
+ * decoder: no byte stream indexes past the table (p2phd_ima_scan_host is how a caller refuses such a file instead).
+ * `nbytes` of payload hold p2phd_ima_frames(nbytes, ...) frames: spb per whole block, and 1 + 8 * k for a trailing partial block
+ * that holds the C headers and k >= 0 whole groups; anything shorter is ignored.
+ *
+ * HOST only (no device, plain C++):
+ * p2phd_g711_decode_host: `frames` frames of `channels` interleaved bytes -> out[c * ld + n] f32.  law: P2PHD_G711_ULAW / _ALAW.
+ * p2phd_ima_frames: the frames `nbytes` hold (above); -1 with an error text for channels outside [1, 8] or a block_align the formula
+ *   does not admit.
+ * p2phd_ima_decode_host: frames [first_frame, first_frame + frame_count) of the payload -> out[c * ld + (n - first_frame)] f32.  Only
+ *   the blocks that cover the window are read; the window must lie inside p2phd_ima_frames(nbytes, ...).
+ * p2phd_ima_scan_host: walks the block headers of every block that holds a sample -> the first block one of whose step indices is
+ *   above 88, -1 where there is none, -2 with an error text for bad arguments.
+ * p2phd_ima_blocks_per_workgroup, p2phd_ima_max_workgroups: the blocks one workgroup of the device decoder stages per trip for a
+ *   layout (0: bad arguments), and the cap of its grid; more blocks than their product are walked with the grid's stride (tests
+ *   place their sizes around them).  p2phd_g711_max_workgroups: the cap of the G.711 decoder's grid, 256 lanes of one 16-byte piece
+ *   each per workgroup and trip.
+ *
+ * DEVICE (both decode through the routine the host entries call):
+ * p2phd_g711_decode: payload on the device at any byte offset -> out[c * ld + n] f32, n < frames; nothing else of a row is written.
+ *   Element-wise; a lane reads 16 bytes at once from the payload's first 16-byte boundary on.
+ * p2phd_ima_decode: `nbytes` of payload on the device at any byte offset -> the first `frames` frames (frames at most
+ *   p2phd_ima_frames(nbytes, ...): a `fact` chunk may cut inside a block) as out[c * ld + n] f32.  One launch: a workgroup stages
+ *   its blocks' bytes into LDS with coalesced reads, one lane runs one (block, channel) chain from LDS and stores each group's 8
+ *   samples as two 16-byte stores where they are aligned and all inside `frames`, one by one otherwise.  No atomics, no scratch.
+ *   The same bits on every run, stream and grid.  A block_align above 65024 is P2PHD_EINVAL here (the host entries take it): a
+ *   block then does not fit the 64 KiB of LDS beside the step table.
+ * frames = 0: nothing is launched or written.  channels outside [1, 8] (G.711: [1, 65535], as p2phd_pcm_decode), an unknown law, a
+ * block_align the formula does not admit, ld < frames, frames beyond the payload, a null or misaligned pointer: P2PHD_EINVAL.
+ * ---------------------------------------------------------------------------------------- */
+#define P2PHD_G711_ULAW 0   /* format tag 7 */
+#define P2PHD_G711_ALAW 1   /* format tag 6 */
+int p2phd_g711_decode_host(const void* bytes, int64_t frames, int channels, int law, float* out, int64_t ld);
+int64_t p2phd_ima_frames(int64_t nbytes, int channels, int block_align);
+int p2phd_ima_decode_host(const void* bytes, int64_t nbytes, int channels, int block_align, int64_t first_frame, int64_t frame_count,
+                          float* out, int64_t ld);
+int64_t p2phd_ima_scan_host(const void* bytes, int64_t nbytes, int channels, int block_align);
+int p2phd_ima_blocks_per_workgroup(int channels, int block_align);
+int p2phd_ima_max_workgroups(void);
+int p2phd_g711_max_workgroups(void);
+int p2phd_g711_decode(const void* bytes, int64_t frames, int channels, int law, float* out, int64_t ld, void* stream);
+int p2phd_ima_decode(const void* bytes, int64_t nbytes, int channels, int block_align, int64_t frames, float* out, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * FLAC output, csrc/flacenc.hip: the payload of the PCM encoder (pcm16 / pcm24) -> the frames of a native FLAC stream that decodes

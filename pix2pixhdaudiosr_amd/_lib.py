@@ -100,6 +100,15 @@ SIGNATURES = {
     "p2phd_flac_tile_len": (_i32, []),
     "p2phd_flac_frames_per_workgroup": (_i32, []),
     "p2phd_flac_decode": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "p2phd_g711_decode_host": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64]),
+    "p2phd_ima_frames": (_i64, [_i64, _i32, _i32]),
+    "p2phd_ima_decode_host": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _i64]),
+    "p2phd_ima_scan_host": (_i64, [_vp, _i64, _i32, _i32]),
+    "p2phd_ima_blocks_per_workgroup": (_i32, [_i32, _i32]),
+    "p2phd_ima_max_workgroups": (_i32, []),
+    "p2phd_g711_max_workgroups": (_i32, []),
+    "p2phd_g711_decode": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "p2phd_ima_decode": (_i32, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp]),
     "p2phd_flac_encode_plan": (_i32, [_i32, _i32, _i64, _i32, _vp, _vp, _vp]),
     "p2phd_flac_encode_threads": (_i32, []),
     "p2phd_flac_encode_scan_threads": (_i32, []),

@@ -1,7 +1,12 @@
 """RIFF/WAVE reader for the feeder (stands in for torchaudio.info / torchaudio.load of data/audio_dataset.py:31-38,99):
 header parse + a seek to the requested frame window, so a random training segment costs one read of segment_length
 frames, not the file.  PCM 8/16/24/32-bit and IEEE float, WAVE_FORMAT_EXTENSIBLE included; samples are scaled the way
-`torchaudio.load(normalize=True)` documents (signed PCM / 2^(bits-1)).  Host I/O only -- no arithmetic of the hot path."""
+`torchaudio.load(normalize=True)` documents (signed PCM / 2^(bits-1)).  Host I/O only -- no arithmetic of the hot path.
+
+Coded data chunks -- G.711 mu-law (tag 7), A-law (tag 6) and 4-bit IMA ADPCM (tag 0x11), the formats of telephone archives -- are
+decoded by the library's host entries (csrc/wavcodec.hip, plain C++) to exactly the samples the file's PCM16 twin holds, scaled as 16-bit
+PCM is; a window of an IMA file costs one read of the blocks that cover it.  MS ADPCM (tag 2), GSM 6.10, G.726 and MP3-in-WAV stay
+refused: no second decoder stands beside them to hold this one against."""
 import os
 import struct
 from collections import namedtuple
@@ -12,12 +17,61 @@ import torch
 WavInfo = namedtuple("WavInfo", "sample_rate num_frames num_channels bits_per_sample format_tag data_offset block_align")
 
 
-def info(path):
+# Coded data chunks (include/p2phd.h, "Coded WAV input"): format tag -> (name, bits per sample).  Decoded by csrc/wavcodec.hip to the
+# samples of the file's PCM16 twin: on the host here (`load`), on the device in whole-file generation (generate.g711_decode / ima_decode).
+CODED_TAGS = {6: ("A-law", 8), 7: ("mu-law", 8), 0x11: ("IMA ADPCM", 4)}
+CODED_MAX_CHANNELS = 8
+
+
+def ima_samples_per_block(channels, block_align):
+    """Samples per block and channel of IMA ADPCM in WAV, 1 + 8 * (block_align - 4C) / 4C; None for a block_align the layout does not
+    admit (below 8C, or not a whole number of 4C-byte groups behind the C headers)."""
+    c4 = 4 * int(channels)
+    if channels < 1 or block_align < 2 * c4 or (block_align - c4) % c4:
+        return None
+    return 1 + 8 * ((block_align - c4) // c4)
+
+
+def coded_frames(tag, channels, block_align, nbytes):
+    """The frames `nbytes` of a coded data chunk hold: G.711 one per `channels` bytes; IMA spb per whole block, plus 1 + 8k for a
+    trailing partial block that holds its headers and k >= 0 whole groups (anything shorter is ignored)."""
+    if tag != 0x11:
+        return nbytes // channels
+    spb, c4 = ima_samples_per_block(channels, block_align), 4 * channels
+    full, rest = divmod(nbytes, block_align)
+    return full * spb + (1 + 8 * (rest // c4 - 1) if rest >= c4 else 0)
+
+
+def _coded_info(path, tag, ch, rate, align, bits, fmt, extensible, fact, offset, there):
+    name, want = CODED_TAGS[tag]
+    if bits != want:
+        raise ValueError(f"{path}: {name} (tag {tag}) holds {want} bits per sample, the fmt chunk states {bits}")
+    if not 1 <= ch <= CODED_MAX_CHANNELS:
+        raise ValueError(f"{path}: {name} (tag {tag}) is read with 1 to {CODED_MAX_CHANNELS} channels, the fmt chunk states {ch}")
+    if tag == 0x11:
+        spb = ima_samples_per_block(ch, align)
+        if spb is None:
+            raise ValueError(f"{path}: IMA ADPCM needs a block_align of 4 * channels * (1 + groups) with groups >= 1, "
+                             f"the fmt chunk states {align} for {ch} ch")
+        if len(fmt) >= 20 and struct.unpack("<H", fmt[16:18])[0] >= 2:
+            stated = struct.unpack("<H", fmt[18:20])[0]
+            if stated != spb and not (extensible and stated == 0):
+                raise ValueError(f"{path}: the fmt chunk states {stated} samples per block, a block_align of {align} with {ch} ch holds {spb}")
+    elif align != ch:
+        raise ValueError(f"{path}: {name} (tag {tag}) needs a block_align of one byte per channel, the fmt chunk states {align} for {ch} ch")
+    frames = coded_frames(tag, ch, align, there)
+    if fact is not None:
+        frames = min(frames, fact)                                          # a fact chunk that claims more is cut to what is there
+    return WavInfo(rate, frames, ch, bits, tag, offset, align)
+
+
+def _parse(path):
+    """-> (WavInfo, the bytes of the data chunk that are in the file)."""
     with open(path, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
             raise ValueError(f"{path}: not a RIFF/WAVE file")
-        fmt = None
+        fmt = fact = None
         while True:
             hdr = f.read(8)
             if len(hdr) < 8:
@@ -27,24 +81,92 @@ def info(path):
                 fmt = f.read(size)
                 if size & 1:
                     f.seek(1, 1)
+            elif cid == b"fact" and size >= 4:
+                word = f.read(4)                                          # dwSampleLength: frames per channel (coded formats)
+                fact = struct.unpack("<I", word)[0] if len(word) == 4 else None
+                f.seek(size - 4 + (size & 1), 1)
             elif cid == b"data":
                 if fmt is None:
                     raise ValueError(f"{path}: data chunk before fmt chunk")
                 tag, ch, rate, _, align, bits = struct.unpack("<HHIIHH", fmt[:16])
-                if tag == 0xFFFE and len(fmt) >= 26:
+                extensible = tag == 0xFFFE and len(fmt) >= 26
+                if extensible:
                     tag = struct.unpack("<H", fmt[24:26])[0]
+                there = min(size, max(os.fstat(f.fileno()).st_size - f.tell(), 0))
+                if tag in CODED_TAGS:
+                    return _coded_info(path, tag, ch, rate, align, bits, fmt, extensible, fact, f.tell(), there), there
                 if tag not in (1, 3) or bits not in (8, 16, 24, 32, 64) or ch < 1 or align != ch * bits // 8:
                     raise ValueError(f"{path}: unsupported WAVE format (tag {tag}, {bits} bit, {ch} ch)")
-                return WavInfo(rate, size // align, ch, bits, tag, f.tell(), align)
+                return WavInfo(rate, size // align, ch, bits, tag, f.tell(), align), there
             else:
                 f.seek(size + (size & 1), 1)
 
 
+def info(path):
+    """-> WavInfo.  PCM and IEEE float: num_frames as the data chunk states them.  A coded file (CODED_TAGS): bits_per_sample 8 or 4,
+    the file's own block_align, num_frames the decoded frame count -- the `fact` chunk's where there is one, cut to what the data
+    chunk holds."""
+    return _parse(path)[0]
+
+
+def _lib():
+    from .. import _lib as L
+    return L.lib()
+
+
+def _load_coded(path, meta, there, start, stop):
+    """Frames [start, stop) of a coded data chunk, decoded on the host (p2phd_g711_decode_host / p2phd_ima_decode_host: plain C++, no
+    device): one seek and one read of the bytes -- for IMA the blocks -- that cover the window."""
+    import ctypes
+    C, n = meta.num_channels, stop - start
+    out = np.zeros((C, n), dtype=np.float32)
+    if n == 0:
+        return out
+    lib = _lib()
+    if meta.format_tag == 0x11:
+        spb = ima_samples_per_block(C, meta.block_align)
+        b0, b1 = start // spb, -(-stop // spb)
+        byte0, byte1 = b0 * meta.block_align, min(b1 * meta.block_align, there)
+    else:
+        b0, byte0, byte1 = 0, start * C, stop * C
+    with open(path, "rb") as f:
+        f.seek(meta.data_offset + byte0)
+        raw = np.frombuffer(f.read(byte1 - byte0), dtype=np.uint8)
+    if raw.size != byte1 - byte0:
+        raise ValueError(f"{path}: short read of the data chunk")
+    src, dst = ctypes.c_void_p(raw.ctypes.data), ctypes.c_void_p(out.ctypes.data)
+    if meta.format_tag == 0x11:
+        bad = lib.p2phd_ima_scan_host(src, raw.size, C, meta.block_align)
+        if bad >= 0:
+            raise ValueError(f"{path}: block {b0 + bad}: a step index above 88 in its header")
+        rc = -1 if bad != -1 else lib.p2phd_ima_decode_host(src, raw.size, C, meta.block_align, start - b0 * spb, n, dst, n)
+    else:
+        rc = lib.p2phd_g711_decode_host(src, n, C, 1 if meta.format_tag == 6 else 0, dst, n)
+    if rc != 0:
+        raise ValueError("%s: %s" % (path, lib.p2phd_last_error().decode("utf-8", "replace")))
+    return out
+
+
+def ima_scan(payload, channels, block_align, name="<bytes>"):
+    """The block headers of an IMA ADPCM payload (a bytes-like object), checked on the host (p2phd_ima_scan_host): a step index above
+    88 is a ValueError that names `name` and the block."""
+    import ctypes
+    a = np.frombuffer(payload, dtype=np.uint8)
+    lib = _lib()
+    bad = lib.p2phd_ima_scan_host(ctypes.c_void_p(a.ctypes.data if a.size else None), a.size, int(channels), int(block_align))
+    if bad >= 0:
+        raise ValueError(f"{name}: block {bad}: a step index above 88 in its header")
+    if bad != -1:
+        raise ValueError("%s: %s" % (name, lib.p2phd_last_error().decode("utf-8", "replace")))
+
+
 def load(path, frame_offset=0, num_frames=-1):
     """-> (float32 tensor [channels, frames], sample_rate), like torchaudio.load."""
-    meta = info(path)
+    meta, there = _parse(path)
     start = min(max(int(frame_offset), 0), meta.num_frames)
     stop = meta.num_frames if num_frames < 0 else min(meta.num_frames, start + int(num_frames))
+    if meta.format_tag in CODED_TAGS:
+        return torch.from_numpy(_load_coded(path, meta, there, start, max(stop, start))), meta.sample_rate
     with open(path, "rb") as f:
         f.seek(meta.data_offset + start * meta.block_align)
         raw = f.read((stop - start) * meta.block_align)
@@ -68,9 +190,21 @@ def read_payload(path, into=None):
     """-> (payload, WavInfo): the bytes of the data chunk, `num_frames * block_align` of them, undecoded (the device decodes
     them, generate.pcm_decode).  `into`: a writable buffer at least that long, or a callable that is given the byte count
     and returns one (a pinned host tensor's memory); the payload is a view of it, cut to size.  Default: a bytearray.  A
-    data chunk that promises more than the file holds is cut to the whole frames that are there, as `load` reads it."""
-    meta = info(path)
+    data chunk that promises more than the file holds is cut to the whole frames that are there, as `load` reads it.  A coded file
+    (CODED_TAGS): the data chunk's bytes as they stand -- every byte of it that is in the file; the WavInfo's num_frames says how many
+    frames the device decoder (generate.g711_decode / ima_decode) is to take from them."""
+    meta, held = _parse(path)
     with open(path, "rb") as f:
+        if meta.format_tag in CODED_TAGS:
+            n = held
+            buf = bytearray(n) if into is None else into(n) if callable(into) else into
+            buf = memoryview(buf).cast("B")
+            if len(buf) < n:
+                raise ValueError(f"{path}: the buffer holds {len(buf)} bytes, the data chunk {n}")
+            f.seek(meta.data_offset)
+            if f.readinto(buf[:n]) != n:
+                raise ValueError(f"{path}: short read of the data chunk")
+            return buf[:n], meta
         there = max(os.fstat(f.fileno()).st_size - meta.data_offset, 0) // meta.block_align
         if there < meta.num_frames:
             meta = meta._replace(num_frames=there)

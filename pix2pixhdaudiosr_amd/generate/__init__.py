@@ -87,6 +87,11 @@ and CRC-checked on the host, are copied once and decoded on the device, one lane
 Folder mode lists *.flac only with `--input_formats wav,flac` (`plan_folder(..., formats=)`; x.flac is written as x.wav), and
 `--verify_input` checks every FLAC file's MD5 on the host first.
 
+A wav whose data chunk is coded -- G.711 mu-law or A-law, 4-bit IMA ADPCM: telephone archives -- is read as it stands too
+(csrc/wavcodec.hip, data/wavio.py): the chunk's bytes are copied once and one launch of the family "wavcodec" decodes them to exactly
+the samples of the file's PCM16 twin (`g711_decode`, `ima_decode`, beside `pcm_decode`); an IMA block header with a step index above
+88 is refused on the host, naming file and block, before the copy.  No flag: a `.wav` is a `.wav`.
+
 `--container flac` (opt-in, csrc/flacenc.hip) writes a FLAC stream instead of a wav: the payload `pcm_encode` leaves on the device goes
 through `flac_encode` there -- one workgroup per frame, fixed predictors, Rice partitions and the stereo assignments chosen on exact
 bit counts -- and the file, decoded, is the wav's data chunk byte for byte.  `--flac_lpc N` also tries LPC subframes of every order
@@ -94,7 +99,7 @@ up to N (a predictor fitted per block, still chosen on exact bit counts; the fil
 brings the payload back as well and writes its MD5; a folder's outputs are then named .flac (`plan_folder(..., ext=)`).
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
-from .ops import (PCM_FORMATS, flac_decode, flac_encode, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
+from .ops import (PCM_FORMATS, G711_LAWS, g711_decode, ima_decode, flac_decode, flac_encode, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, shaper_coefficients, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
 from .plans import (INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401

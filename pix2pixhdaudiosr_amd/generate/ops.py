@@ -90,6 +90,37 @@ def pcm_decode(payload, frames, channels, format_tag, bits):
     return out
 
 
+G711_LAWS = {'ulaw': 0, 'alaw': 1}                                          # P2PHD_G711_* of include/p2phd.h (format tags 7 and 6)
+
+
+def g711_decode(payload, frames, channels, law):
+    """payload: uint8 tensor on the GPU holding the interleaved G.711 bytes of a data chunk (any byte offset into its storage); law:
+    'ulaw' (format tag 7) or 'alaw' (tag 6) -> [channels, frames] f32, bit-identical to what wavio.load returns for the file -- the
+    samples of its PCM16 twin (p2phd_g711_decode: one launch of the family "wavcodec", none for frames = 0)."""
+    b = _lib.require_gpu_tensor(payload, "g711_decode: payload", torch.uint8)
+    if law not in G711_LAWS:
+        raise ValueError("g711_decode: law must be one of %s, got %r" % (sorted(G711_LAWS), law))
+    frames, channels = int(frames), int(channels)
+    if frames < 0 or channels < 1 or b.numel() < frames * channels:
+        raise ValueError("g711_decode: %d bytes do not hold %d frames of %d channels" % (b.numel(), frames, channels))
+    out = torch.empty((channels, frames), dtype=torch.float32, device=b.device)
+    _lib.check(_lib.lib().p2phd_g711_decode(_lib.ptr(b), frames, channels, G711_LAWS[law], _lib.ptr(out), frames, _lib.stream_ptr()), "g711_decode")
+    return out
+
+
+def ima_decode(payload, frames, channels, block_align):
+    """payload: uint8 tensor on the GPU holding the IMA ADPCM blocks of a data chunk (any byte offset into its storage; a trailing
+    partial block counts with its whole groups) -> the first `frames` frames as [channels, frames] f32, bit-identical to what
+    wavio.load returns for the file (p2phd_ima_decode: one launch of the family "wavcodec", none for frames = 0).  A header's step
+    index above 88 is clamped, not refused: wavio.ima_scan is the host check that names such a block."""
+    b = _lib.require_gpu_tensor(payload, "ima_decode: payload", torch.uint8)
+    frames, channels = int(frames), int(channels)
+    out = torch.empty((channels if 1 <= channels <= 8 else 1, max(frames, 0)), dtype=torch.float32, device=b.device)
+    _lib.check(_lib.lib().p2phd_ima_decode(_lib.ptr(b), b.numel(), channels, int(block_align), frames, _lib.ptr(out), max(frames, 0),
+                                           _lib.stream_ptr()), "ima_decode")
+    return out
+
+
 FLAC_REASONS = {1: "its bit stream runs past the frame's end", 2: "a reserved code", 3: "an impossible partition or predictor order",
                 4: "its subframes end short of the frame's length", 5: "a table row that does not fit the buffers or the channel count"}
 

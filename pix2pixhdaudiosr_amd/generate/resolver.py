@@ -7,7 +7,7 @@ from collections import namedtuple
 
 import torch
 
-from .ops import (flac_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
+from .ops import (flac_decode, g711_decode, ima_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
 from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_container, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
@@ -383,11 +383,14 @@ class SuperResolver:
 
     def _read(self, path, slot='in0', verify=False):
         """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo).  A file whose
-        first bytes say FLAC (data/audiofile.py) goes through _read_flac instead; `verify` is its."""
+        first bytes say FLAC (data/audiofile.py) goes through _read_flac instead; `verify` is its.  A coded data chunk (G.711, IMA
+        ADPCM: wavio.CODED_TAGS) is read as it stands; an IMA block header with a step index above 88 is a ValueError here."""
         from ..data import audiofile, wavio
         if audiofile.kind(path) == 'flac':
             return self._read_flac(path, slot, verify)
         payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
+        if meta.format_tag == 0x11:                                         # IMA ADPCM: the block headers, before the copy (names file and block)
+            wavio.ima_scan(payload, meta.num_channels, meta.block_align, os.fspath(path))
         return self._pins[slot][0][:len(payload)], meta, slot
 
     def _read_flac(self, path, slot, verify=False):
@@ -416,7 +419,8 @@ class SuperResolver:
         return pinned[:at + table.nbytes], meta, slot
 
     def _decode(self, host, meta, slot):
-        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel.  The bytes and table of a
+        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel -- the PCM decoder's, or for a
+        coded chunk (meta.format_tag 6, 7, 0x11) one of the family "wavcodec".  The bytes and table of a
         FLAC file (_read_flac): one copy, the two kernels of the family "flac", and one wait for their status word -- a frame that
         passed the index's CRCs and still does not decode is a ValueError that names it, before anything else is launched."""
         if host.numel() == 0:
@@ -432,6 +436,10 @@ class SuperResolver:
                 return flac_decode(dev[:at], dev[at:].view(torch.int64).view(-1, 6), meta)
             except ValueError as e:                                         # (the decoder's refusal, with the file it is about)
                 raise ValueError("%s: %s" % (getattr(self, '_pin_names', {}).get(slot, '<flac>'), e)) from None
+        if meta.format_tag in (6, 7):                                       # G.711 A-law / mu-law (csrc/wavcodec.hip)
+            return g711_decode(dev, meta.num_frames, meta.num_channels, 'alaw' if meta.format_tag == 6 else 'ulaw')
+        if meta.format_tag == 0x11:                                         # IMA ADPCM; _read has scanned the block headers
+            return ima_decode(dev, meta.num_frames, meta.num_channels, meta.block_align)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
     def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,

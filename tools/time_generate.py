@@ -18,6 +18,10 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             written payloads, on the clip and on an hour of it; the host encoder alone; the streams' sizes; log in --flacout_log;
             with --flac_lpc N instead: container flac with flac_lpc=N against without, p2phd_flac_encode_lpc beside p2phd_flac_encode by
             events on the clip and on the hour, the frame kernel's two instantiations alone, the sizes at M = 0, 4, 8, 12; log in --flaclpc_log
+  wavcodec  (only when asked for) coded WAV input: one 15 s mono 8 kHz clip as G.711 mu-law, A-law and IMA ADPCM (written by
+            tests/_wavcodec_ref.py), each beside its PCM16 twin: enhance_file(is_lr_input) and _read + _decode alone, interleaved, median
+            and spread of --reps; then by events the two kernels of csrc/wavcodec.hip beside p2phd_pcm_decode, on the clip and on an hour
+            of it; the host entries on one thread; log in --wavcodec_log
 
   folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
             ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
@@ -109,6 +113,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
         python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
         python tools/time_generate.py flacout [--flac_lpc 12] [--flacout_log profiles/time_generate_flacout.log] [--flaclpc_log profiles/time_generate_flaclpc.log]
+        python tools/time_generate.py wavcodec [--wavcodec_log profiles/time_generate_wavcodec.log]
 """
 import argparse
 import os
@@ -1080,6 +1085,120 @@ def run_flac(seconds, reps, log):
             f.write(text)
 
 
+def run_wavcodec(seconds, reps, log):
+    """Coded WAV input (G.711 mu-law, A-law, IMA ADPCM with 256-byte blocks; csrc/wavcodec.hip) against the PCM16 twin of the same
+    samples: a mono telephone clip at 8 kHz, written by the restatement tests/_wavcodec_ref.py.  Interleaved: enhance_file
+    (is_lr_input) per file, and the input side alone (_read + _decode).  Then, by events, each decoder's kernel alone beside
+    p2phd_pcm_decode on the clip and on an hour of it (the clip's bytes 240 times over: G.711 is element-wise and IMA blocks are
+    independent), and the host entries on one thread."""
+    import ctypes
+    import tempfile
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _wavcodec_ref as R
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd import _lib
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, g711_decode, ima_decode, pcm_decode
+    rate, align = 8000, 256
+    n = int(seconds * rate)
+    ints = torch.round(0.5 * x[0, ::6][:n].cpu().double() * 32768.0).clamp(-32768, 32767).to(torch.int64).numpy()[None]
+    t0 = time.perf_counter()
+    ima = R.ima_encode(ints, align, partial=False)
+    t_enc = time.perf_counter() - t0
+    payloads = {"ulaw": R.g711_encode(ints, R.ULAW), "alaw": R.g711_encode(ints, R.ALAW), "ima": ima}
+    decoded = {"ulaw": R.g711_decode(payloads["ulaw"], n, 1, R.ULAW), "alaw": R.g711_decode(payloads["alaw"], n, 1, R.ALAW)}
+    lines = ["# tools/time_generate.py wavcodec: one %g s mono clip at 8 kHz (%d samples) as mu-law, A-law (%d bytes each) and IMA ADPCM (block_align %d, "
+             "505 samples a block, %d bytes; the restatement took %.1f s to encode it), each beside its PCM16 twin (%d bytes); %d interleaved repeats"
+             % (seconds, n, n, align, len(ima), t_enc, 2 * n, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = {}
+        for kind, tag in (("ulaw", R.TAG_ULAW), ("alaw", R.TAG_ALAW), ("ima", R.TAG_IMA)):
+            paths[kind] = os.path.join(tmp, kind + ".wav")
+            if kind == "ima":
+                R.write_coded_wav(paths[kind], tag, payloads[kind], rate, 1, block_align=align, fact=n)
+                decoded[kind] = wavio.load(paths[kind])[0].numpy()
+                R.write_pcm16_wav(os.path.join(tmp, "ima_pcm.wav"), np.rint(decoded[kind] * 32768.0).astype(np.int64), rate)
+            else:
+                R.write_coded_wav(paths[kind], tag, payloads[kind], rate, 1)
+                R.write_pcm16_wav(os.path.join(tmp, kind + "_pcm.wav"), decoded[kind], rate)
+            paths[kind + "_pcm"] = os.path.join(tmp, kind + "_pcm.wav")
+            assert torch.equal(wavio.load(paths[kind])[0], wavio.load(paths[kind + "_pcm"])[0])
+        sr = SuperResolver(model, opt, overlap=0.25)
+        out = os.path.join(tmp, "out.wav")
+        order = ["ulaw", "ulaw_pcm", "alaw", "alaw_pcm", "ima", "ima_pcm"]
+        for what, fn in (("enhance_file(is_lr_input), file to file", lambda k: sr.enhance_file(paths[k], out, is_lr_input=True)),
+                         ("_read + _decode alone", lambda k: sr._decode(*sr._read(paths[k])))):
+            for k in order:
+                fn(k); fn(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in order}
+            for _ in range(reps):
+                for k in order:
+                    t0 = time.perf_counter()
+                    fn(k)
+                    torch.cuda.synchronize()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            lines.append(what + ":")
+            for k in order:
+                tk = ts[k]
+                lines.append("  %-9s median %8.3f ms   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                             % (k, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+            for k in ("ulaw", "alaw", "ima"):
+                lines.append("  %s - its twin: %+.3f ms of medians; the twin's own spread %.3f ms"
+                             % (k, _median(ts[k]) - _median(ts[k + "_pcm"]), max(ts[k + "_pcm"]) - min(ts[k + "_pcm"])))
+    copies = 3600 * rate // n
+    dev = {k: torch.frombuffer(bytearray(v), dtype=torch.uint8).cuda() for k, v in payloads.items()}
+    dev["pcm"] = torch.from_numpy(ints[0].astype("<i2").view(np.uint8).copy()).cuda()
+    for name, c in (("the clip", 1), ("an hour", copies)):
+        b = {k: v.repeat(c) for k, v in dev.items()}
+        L = n * c
+        Lima = R.ima_frames(len(ima) * c, 1, align)
+        kinds = [("g711_decode_kernel mu-law", lambda: g711_decode(b["ulaw"], L, 1, 'ulaw')), ("g711_decode_kernel A-law", lambda: g711_decode(b["alaw"], L, 1, 'alaw')),
+                 ("ima_decode_kernel", lambda: ima_decode(b["ima"], Lima, 1, align)), ("p2phd_pcm_decode (PCM16)", lambda: pcm_decode(b["pcm"], L, 1, 1, 16))]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(kinds) + 1)]
+        ks = [[] for _ in kinds]
+        for _ in range(reps + 2):
+            outs = []
+            ev[0].record()
+            for k, (_, fn) in enumerate(kinds):
+                outs.append(fn())
+                ev[k + 1].record()
+            torch.cuda.synchronize()
+            for k in range(len(kinds)):
+                ks[k].append(ev[k].elapsed_time(ev[k + 1]) * 1e3)
+            del outs
+        lines.append("by events on %s (median of %d, each with the allocation of its result in front; %d samples, %d IMA blocks): %s"
+                     % (name, reps, L, -(-Lima // 505), "; ".join("%s %.1f us (spread %.1f) = %.4f ns per sample" % (kn, _median(k[2:]), max(k[2:]) - min(k[2:]), _median(k[2:]) * 1e3 / L)
+                                                                   for (kn, _), k in zip(kinds, ks))))
+        lines.append("runs: " + "; ".join("%s %s" % (kn, " ".join("%.1f" % v for v in k[2:])) for (kn, _), k in zip(kinds, ks)))
+    lib = _lib.lib()
+    for name, c, r in (("the clip", 1, reps), ("an hour", copies, 3)):
+        L = n * c
+        res = []
+        out_h = np.zeros(L + 505, dtype=np.float32)
+        for kind in ("ulaw", "alaw", "ima"):
+            src = np.frombuffer(payloads[kind] * c, dtype=np.uint8)
+            tk = []
+            for _ in range(r):
+                t0 = time.perf_counter()
+                if kind == "ima":
+                    rc = lib.p2phd_ima_decode_host(ctypes.c_void_p(src.ctypes.data), src.size, 1, align, 0, L, ctypes.c_void_p(out_h.ctypes.data), L)
+                else:
+                    rc = lib.p2phd_g711_decode_host(ctypes.c_void_p(src.ctypes.data), L, 1, 1 if kind == "alaw" else 0, ctypes.c_void_p(out_h.ctypes.data), L)
+                tk.append((time.perf_counter() - t0) * 1e3)
+                assert rc == 0
+            res.append("%s median %.3f ms = %.2f ns per sample (%s)" % (kind, _median(tk), _median(tk) * 1e6 / L, " ".join("%.3f" % v for v in tk)))
+        lines.append("on the host, one thread, %s (the host entry alone, into a buffer that exists): %s" % (name, "; ".join(res)))
+    lines.append("not measured here: the option-off path (a PCM input) and the benchmark step against the parent commit in alternating processes")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_flacout(seconds, reps, log):
     """The output side, file to file: enhance_file with container 'wav' and 'flac' on one mono and one stereo 16-bit clip, interleaved.
     Then, by events, p2phd_flac_encode (generate.flac_encode: its allocations in front) beside p2phd_pcm_encode_ex on the written
@@ -1579,7 +1698,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1597,6 +1716,7 @@ def main():
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
+    ap.add_argument("--wavcodec_log", default=os.path.join(ROOT, "profiles", "time_generate_wavcodec.log"))
     ap.add_argument("--flacout_log", default=os.path.join(ROOT, "profiles", "time_generate_flacout.log"))
     ap.add_argument("--flac_lpc", type=int, default=None, metavar="N", help="flacout mode: time the LPC option at order N against the writer without it (log in --flaclpc_log)")
     ap.add_argument("--flaclpc_log", default=os.path.join(ROOT, "profiles", "time_generate_flaclpc.log"))
@@ -1609,6 +1729,8 @@ def main():
         return run_flaclpc(a.seconds, 9 if a.reps is None else a.reps, a.flaclpc_log, a.flac_lpc)
     if a.mode == "flacout":
         return run_flacout(a.seconds, 9 if a.reps is None else a.reps, a.flacout_log)
+    if a.mode == "wavcodec":
+        return run_wavcodec(a.seconds, 9 if a.reps is None else a.reps, a.wavcodec_log)
     if a.mode == "flac":
         return run_flac(a.seconds, 9 if a.reps is None else a.reps, a.flac_log)
     if a.mode == "album":
