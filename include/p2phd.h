@@ -264,6 +264,21 @@ int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t
  *   (seed, i) = (0, 2^32) and (1, 0) draw the same value: harmless, the streams of two seeds are otherwise unrelated.
  *   gain = NULL and dither = 0: the bytes of p2phd_pcm_encode for every input (clamping before or after rounding gives the
  *   same codes).
+ *
+ * Big-endian containers (AIFF / AIFF-C, Sun/NeXT AU, NIST SPHERE; parsed by data/containers.py).  A file in one of the three
+ * decodes to exactly the float32 samples data/wavio.py load returns for its WAV twin, the RIFF file that holds the same samples:
+ *   integer PCM      the same width, little-endian, scaled by 2^-(8 * bytes - 1)
+ *   signed 8-bit s   the twin holds s + 128: the value is s / 128
+ *   float32          a bit copy after the byte swap; a NaN keeps its payload
+ *   float64          rounded to nearest even, as P2PHD_PCM_F64
+ *   G.711            the same bytes under format tags 6 / 7 (p2phd_g711_decode, "Coded WAV input" below), scaled as 16-bit PCM is
+ * p2phd_pcm_decode_ex: p2phd_pcm_decode with `flags`, an OR of
+ *   P2PHD_PCM_BIG_ENDIAN  the bytes of a sample stand most significant first (no effect with P2PHD_PCM_U8);
+ *   P2PHD_PCM_SIGNED8     with P2PHD_PCM_U8 only: the byte is a two's-complement sample.
+ *   flags = 0: the bits of p2phd_pcm_decode.  Layout, grid ("pcm_decode_ex" of p2phd_stream_grid) and argument checks are
+ *   p2phd_pcm_decode's: 2, 4 and 8-byte samples are read with one typed load and byte-swapped where the payload pointer is aligned to
+ *   the sample size and assembled byte-wise otherwise, 24-bit samples always byte-wise.  Counts 1 in "pcm"; frames = 0 launches
+ *   and counts nothing.  P2PHD_PCM_SIGNED8 with another format, an unknown flag bit: P2PHD_EINVAL.
  * ---------------------------------------------------------------------------------------- */
 #define P2PHD_PCM_U8  0   /* format tag 1,  8 bit */
 #define P2PHD_PCM_S16 1   /* format tag 1, 16 bit */
@@ -272,6 +287,9 @@ int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t
 #define P2PHD_PCM_F32 4   /* format tag 3, 32 bit */
 #define P2PHD_PCM_F64 5   /* format tag 3, 64 bit */
 int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels, int format, float* out, int64_t ld, void* stream);
+#define P2PHD_PCM_BIG_ENDIAN 1
+#define P2PHD_PCM_SIGNED8    2   /* with P2PHD_PCM_U8 only: the byte is a two's-complement sample */
+int p2phd_pcm_decode_ex(const void* bytes, int64_t frames, int channels, int format, int flags, float* out, int64_t ld, void* stream);
 int p2phd_pcm_encode(const float* planar, int64_t frames, int channels, int64_t ld, int format, void* out, void* stream);
 int p2phd_pcm_peak(const float* planar, int64_t frames, int channels, int64_t ld, int format, float ceiling, float* peak,
                    int64_t* over, int64_t* nonfinite, float* gain, void* stream);
@@ -1083,7 +1101,7 @@ int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C,
  * grid covers (work > 2 * unit_work: some thread takes a third trip).  The launchers take their grids from the same function.
  * `work` per family, and the cap:
  *   segments_gather(_planar), segments_stitch(_planar)   outputs per row (S * T, resp. L_out); a quad per thread; 16384
- *   pcm_decode, pcm_encode, pcm_encode_ex                 interleaved samples (frames * channels); 16384
+ *   pcm_decode(_ex), pcm_encode, pcm_encode_ex            interleaved samples (frames * channels); 16384
  *   pcm_peak                                              frames per row, rows = channels; four 16-byte pieces in flight per
  *                                                         thread; min(2048 / channels, what the reduction scratch holds)
  *   stereo_matrix / stereo_matrix_scalar                  samples per row L, on the 16-byte path / the path of any alignment; 4096

@@ -3,6 +3,8 @@
 //
 //   decode  little-endian interleaved payload of a RIFF data chunk -> planar fp32 out[c * ld + n].  One int -> float
 //           conversion and an exact power-of-two scale (data/wavio.py load), so the result is the bits wavio.load returns.
+//           p2phd_pcm_decode_ex: the same for the payloads of AIFF, AU and NIST SPHERE files -- big-endian samples (a byte swap
+//           behind the load) and signed 8-bit ones -- which decode to the bits of their WAV twin.
 //   encode  planar fp32 -> interleaved payload, one kernel behind both entries: y = x * gain[0] (read from device memory: the
 //           peak launch in front needs no host round trip; no gain: y = x), v = y * 2^(bits-1) [+ d], r = rint(v) clamped to
 //           the integer range, NaN -> 0; float32 writes y, without gain as a bit copy.  d: TPDF dither of +-1 LSB for PCM16, a
@@ -69,6 +71,65 @@ __global__ __launch_bounds__(kThreads) void pcm_decode_kernel(const uint8_t* __r
     const long n = e / channels, c = e - n * channels;
     out[c * ld + n] = decode_one<FORMAT>(src + e * BYTES, aligned);
   }
+}
+
+// ---- big-endian containers (AIFF, AU, NIST SPHERE: data/containers.py) ---------------------------------------------------
+// The sample at p as the little-endian load of its WAV twin would return it.  BE: the bytes stand in the other order -- a typed
+// load and a byte swap where the payload is aligned to the sample size, byte-wise otherwise (24-bit always), load_le's rule.
+template <int BYTES, bool BE> __device__ __forceinline__ uint64_t load_any(const uint8_t* __restrict__ p, int aligned) {
+  if (!BE || BYTES == 1) return load_le<BYTES>(p, aligned);
+  if (aligned) {
+    if (BYTES == 2) return __builtin_bswap16(*reinterpret_cast<const uint16_t*>(p));
+    if (BYTES == 4) return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(p));
+    if (BYTES == 8) return __builtin_bswap64(*reinterpret_cast<const uint64_t*>(p));
+  }
+  uint64_t v = 0;
+#pragma unroll
+  for (int b = 0; b < BYTES; ++b) v = (v << 8) | p[b];
+  return v;
+}
+
+// decode_one's conversions on a loaded sample.  SIGNED8 (U8 only): the byte is s, its twin holds s + 128: s / 128.
+template <int FORMAT, bool SIGNED8> __device__ __forceinline__ uint32_t convert_one(uint64_t v) {
+  if (FORMAT == P2PHD_PCM_U8) return __float_as_uint((SIGNED8 ? (float)(int8_t)v : (float)(int)v - 128.0f) * (1.0f / 128.0f));
+  if (FORMAT == P2PHD_PCM_S16) return __float_as_uint((float)(int16_t)v * (1.0f / 32768.0f));
+  if (FORMAT == P2PHD_PCM_S24) return __float_as_uint((float)((int32_t)((uint32_t)v << 8) >> 8) * (1.0f / 8388608.0f));
+  if (FORMAT == P2PHD_PCM_S32) return __float_as_uint((float)(int32_t)v * (1.0f / 2147483648.0f));
+  if (FORMAT == P2PHD_PCM_F32) return (uint32_t)v;                                         // bit copy: a NaN keeps its payload
+  return __float_as_uint((float)__longlong_as_double((long long)v));                      // round to nearest even
+}
+
+constexpr int pcm_bytes(int format) {
+  return format == P2PHD_PCM_U8 ? 1 : format == P2PHD_PCM_S16 ? 2 : format == P2PHD_PCM_S24 ? 3 : format == P2PHD_PCM_F64 ? 8 : 4;
+}
+
+// The grid-stride walk with the payload's alignment known at compile time, two samples of a thread loaded before either is converted.
+// pcm_decode_kernel gets both from the compiler (the test of `aligned` moved out of its loop, the loop unrolled by two with the loads in
+// front); with the byte swap behind the load it gives neither, and the decoder runs at two thirds of the little-endian rate on an hour.
+template <int FORMAT, bool BE, bool SIGNED8, bool ALIGNED>
+__device__ __forceinline__ void decode_ex_walk(const uint8_t* __restrict__ src, long total, long channels, long ld, uint32_t* __restrict__ out) {
+  constexpr int BYTES = pcm_bytes(FORMAT);
+  const long stride = (long)gridDim.x * blockDim.x;
+  long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; e + stride < total; e += 2 * stride) {
+    const long f = e + stride;
+    const uint64_t a = load_any<BYTES, BE>(src + e * BYTES, ALIGNED), b = load_any<BYTES, BE>(src + f * BYTES, ALIGNED);
+    const long n = e / channels, c = e - n * channels, m = f / channels, d = f - m * channels;
+    out[c * ld + n] = convert_one<FORMAT, SIGNED8>(a);
+    out[d * ld + m] = convert_one<FORMAT, SIGNED8>(b);
+  }
+  if (e < total) {
+    const long n = e / channels, c = e - n * channels;
+    out[c * ld + n] = convert_one<FORMAT, SIGNED8>(load_any<BYTES, BE>(src + e * BYTES, ALIGNED));
+  }
+}
+
+// pcm_decode_kernel's walk and layout, templated on (format, byte order, signedness)
+template <int FORMAT, bool BE, bool SIGNED8>
+__global__ __launch_bounds__(kThreads) void pcm_decode_ex_kernel(const uint8_t* __restrict__ src, long frames, long channels, long ld,
+                                                                 uint32_t* __restrict__ out, int aligned) {
+  if (aligned) decode_ex_walk<FORMAT, BE, SIGNED8, true>(src, frames * channels, channels, ld, out);
+  else decode_ex_walk<FORMAT, BE, SIGNED8, false>(src, frames * channels, channels, ld, out);
 }
 
 using p2phd::tpdf;                  // dither.h: the TPDF dither of an interleaved sample, shared with shaper.hip
@@ -216,6 +277,19 @@ void launch_decode(const void* bytes, int64_t frames, int channels, float* out, 
                      static_cast<const uint8_t*>(bytes), (long)frames, (long)channels, (long)ld, reinterpret_cast<uint32_t*>(out), aligned);
 }
 
+template <int FORMAT, bool BE, bool SIGNED8>
+void launch_decode_ex(const void* bytes, int64_t frames, int channels, float* out, int64_t ld, hipStream_t st) {
+  constexpr int BYTES = pcm_bytes(FORMAT);
+  const int aligned = (reinterpret_cast<uintptr_t>(bytes) & (BYTES - 1)) == 0 && (BYTES & (BYTES - 1)) == 0;
+  hipLaunchKernelGGL((pcm_decode_ex_kernel<FORMAT, BE, SIGNED8>), dim3(sample_grid(frames * channels)), dim3(kThreads), 0, st,
+                     static_cast<const uint8_t*>(bytes), (long)frames, (long)channels, (long)ld, reinterpret_cast<uint32_t*>(out), aligned);
+}
+
+template <int FORMAT>
+void launch_decode_order(bool be, const void* bytes, int64_t frames, int channels, float* out, int64_t ld, hipStream_t st) {
+  (be ? launch_decode_ex<FORMAT, true, false> : launch_decode_ex<FORMAT, false, false>)(bytes, frames, channels, out, ld, st);
+}
+
 template <int FORMAT, int BYTES, bool DITHER>
 void launch_encode(const float* planar, int64_t frames, int channels, int64_t ld, const float* gain, uint64_t seed, uint64_t first_index,
                    void* out, hipStream_t st) {
@@ -287,6 +361,31 @@ extern "C" int p2phd_pcm_decode(const void* bytes, int64_t frames, int channels,
   }
   ++p2phd::g_launch_count[p2phd::LC_PCM];
   return p2phd::check_launch("pcm_decode");
+}
+
+extern "C" int p2phd_pcm_decode_ex(const void* bytes, int64_t frames, int channels, int format, int flags, float* out, int64_t ld,
+                                   void* stream) {
+  if (const int rc = check_rows("pcm_decode_ex", frames, channels, ld, format, false)) return rc;
+  P2PHD_REQUIRE((flags & ~(P2PHD_PCM_BIG_ENDIAN | P2PHD_PCM_SIGNED8)) == 0, "pcm_decode_ex: unknown flag bits in %d", flags);
+  P2PHD_REQUIRE(!(flags & P2PHD_PCM_SIGNED8) || format == P2PHD_PCM_U8, "pcm_decode_ex: P2PHD_PCM_SIGNED8 goes with P2PHD_PCM_U8 only (format %d)",
+                format);
+  if (frames == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(bytes && out, "pcm_decode_ex: null pointer");
+  P2PHD_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "pcm_decode_ex: out is not aligned to a float");
+  hipStream_t st = (hipStream_t)stream;
+  const bool be = (flags & P2PHD_PCM_BIG_ENDIAN) != 0;
+  switch (format) {
+    case P2PHD_PCM_U8:                                            // a byte has no order
+      (flags & P2PHD_PCM_SIGNED8 ? launch_decode_ex<P2PHD_PCM_U8, false, true> : launch_decode_ex<P2PHD_PCM_U8, false, false>)(bytes, frames, channels, out, ld, st);
+      break;
+    case P2PHD_PCM_S16: launch_decode_order<P2PHD_PCM_S16>(be, bytes, frames, channels, out, ld, st); break;
+    case P2PHD_PCM_S24: launch_decode_order<P2PHD_PCM_S24>(be, bytes, frames, channels, out, ld, st); break;
+    case P2PHD_PCM_S32: launch_decode_order<P2PHD_PCM_S32>(be, bytes, frames, channels, out, ld, st); break;
+    case P2PHD_PCM_F32: launch_decode_order<P2PHD_PCM_F32>(be, bytes, frames, channels, out, ld, st); break;
+    default:            launch_decode_order<P2PHD_PCM_F64>(be, bytes, frames, channels, out, ld, st); break;
+  }
+  ++p2phd::g_launch_count[p2phd::LC_PCM];
+  return p2phd::check_launch("pcm_decode_ex");
 }
 
 extern "C" int p2phd_pcm_encode(const float* planar, int64_t frames, int channels, int64_t ld, int format, void* out, void* stream) {

@@ -18,7 +18,7 @@ struct StreamGrid {
 
 enum StreamFamily {
   SG_STITCH,            // segments_gather(_planar), segments_stitch(_planar): outputs per row, a quad per thread
-  SG_PCM,               // pcm_decode, pcm_encode(_ex): interleaved samples, one per thread
+  SG_PCM,               // pcm_decode(_ex), pcm_encode(_ex): interleaved samples, one per thread
   SG_PCM_PEAK,          // pcm_peak: frames per row; four 16-byte pieces in flight per thread; rows = channels
   SG_STEREO_VEC,        // stereo_matrix, aligned rows: a quad of samples per thread
   SG_STEREO_SCALAR,     // stereo_matrix, any alignment: a sample per thread
@@ -40,7 +40,7 @@ enum StreamFamily {
 inline StreamFamily stream_family(const char* name) {
   static const struct { const char* name; StreamFamily f; } table[] = {
       {"segments_gather", SG_STITCH}, {"segments_gather_planar", SG_STITCH}, {"segments_stitch", SG_STITCH},
-      {"segments_stitch_planar", SG_STITCH}, {"pcm_decode", SG_PCM}, {"pcm_encode", SG_PCM}, {"pcm_encode_ex", SG_PCM},
+      {"segments_stitch_planar", SG_STITCH}, {"pcm_decode", SG_PCM}, {"pcm_decode_ex", SG_PCM}, {"pcm_encode", SG_PCM}, {"pcm_encode_ex", SG_PCM},
       {"pcm_peak", SG_PCM_PEAK}, {"stereo_matrix", SG_STEREO_VEC}, {"stereo_matrix_scalar", SG_STEREO_SCALAR},
       {"loudness_blocks", SG_LOUDNESS}, {"loudness_short_term", SG_LOUDNESS}, {"avgpool3s2_fwd", SG_ITEMS},
       {"avgpool3s2_bwd", SG_ITEMS}, {"nchw_to_nhwc", SG_ITEMS}, {"nhwc_to_nchw", SG_ITEMS}, {"nchw_cat_to_nhwc", SG_ITEMS},

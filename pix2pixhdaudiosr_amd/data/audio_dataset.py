@@ -144,14 +144,16 @@ class AudioDataset(BaseDataset):
 
     def get_files(self, file_path):
         """Directory -> every .wav below it; otherwise a csv whose cells are paths relative to the csv's folder
-        (audio_dataset.py:64-79; the reference's extension test accepts anything, this build decodes RIFF/WAVE and FLAC).  A folder
-        scan lists .wav alone unless opt.audio_formats says otherwise ('wav,flac' adds .flac): a scan must not start to pick up
+        (audio_dataset.py:64-79; the reference's extension test accepts anything, this build decodes RIFF/WAVE, FLAC, AIFF, AU and
+        NIST SPHERE).  A folder scan lists .wav alone unless opt.audio_formats says otherwise ('wav,flac' adds .flac; aif, aiff, aifc, au,
+        snd and sph are the other names): a scan must not start to pick up
         files it ignored.  A csv is taken as it stands; what a listed file is, its first bytes say."""
         if os.path.isdir(file_path):
             formats = [f.strip().lower().lstrip('.') for f in str(getattr(self, 'audio_formats', None) or 'wav').split(',')]
-            unknown = [f for f in formats if f not in ('wav', 'flac')]
+            known = ('wav', 'flac', 'aif', 'aiff', 'aifc', 'au', 'snd', 'sph')
+            unknown = [f for f in formats if f not in known]
             if unknown:
-                raise ValueError("audio_formats: of wav and flac, with commas; got %r" % (unknown,))
+                raise ValueError("audio_formats: of %s, with commas; got %r" % (", ".join(known), unknown))
             ends = tuple('.' + f for f in formats)
             found = [os.path.join(folder, name) for folder, _, names in os.walk(file_path, topdown=False)
                      for name in names if name.lower().endswith(ends)]

@@ -92,6 +92,15 @@ A wav whose data chunk is coded -- G.711 mu-law or A-law, 4-bit IMA ADPCM: telep
 the samples of the file's PCM16 twin (`g711_decode`, `ima_decode`, beside `pcm_decode`); an IMA block header with a step index above
 88 is refused on the host, naming file and block, before the copy.  No flag: a `.wav` is a `.wav`.
 
+An AIFF / AIFF-C, Sun/NeXT AU or NIST SPHERE input (told by its first bytes -- 'FORM', '.snd', 'NIST' -- whatever its name: a TIMIT
+`.WAV` is a SPHERE file; data/containers.py) is read as it stands as well: the sound data is copied once and one launch decodes it to
+exactly the samples of the file's WAV twin -- `pcm_decode(..., big_endian=, signed8=)` for big-endian or signed 8-bit samples
+(p2phd_pcm_decode_ex in csrc/pcm.hip), plain `pcm_decode` for little-endian ones (AIFF-C 'sowt', SPHERE byte format 01), `g711_decode`
+for mu-law and A-law; the result's 'info' is a containers.AudioInfo, which leads with WavInfo's fields.  What is not read (AIFF-C ima4,
+MACE, G.722, GSM; AU's G.72x codes; shorten-coded SPHERE; a non-integer sample rate) is a ValueError that names the file and the
+coding before anything is launched, and a skipped file in folder mode.  Folder mode lists such files only with `--input_formats`
+(aif, aiff, aifc, au, snd, sph; x.aif is written as x.wav).
+
 `--container flac` (opt-in, csrc/flacenc.hip) writes a FLAC stream instead of a wav: the payload `pcm_encode` leaves on the device goes
 through `flac_encode` there -- one workgroup per frame, fixed predictors, Rice partitions and the stereo assignments chosen on exact
 bit counts -- and the file, decoded, is the wav's data chunk byte for byte.  `--flac_lpc N` also tries LPC subframes of every order

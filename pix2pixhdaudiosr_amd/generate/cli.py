@@ -303,8 +303,8 @@ def _parser():
                          "loudness, true-peak and limiter stages, which then measure and hold what is written; one start-up line more; "
                          "not with --spectrogram or --loudness_scope folder (default: off)")
     ap.add_argument("--input_formats", default=None, metavar="LIST",
-                    help="a folder as --input: the extensions to list, of wav and flac, with commas (default: wav); x.flac is written as "
-                         "x.wav; a single --input file is read by what its first bytes say, whatever its name")
+                    help="a folder as --input: the extensions to list, of wav, flac, aif, aiff, aifc, au, snd and sph, with commas (default: wav); "
+                         "x.flac or x.aif is written as x.wav; a single --input file is read by what its first bytes say, whatever its name")
     ap.add_argument("--verify_input", action="store_true",
                     help="FLAC inputs: decode the file on the host first and refuse it where its samples do not have the MD5 its "
                          "STREAMINFO states; one start-up line more (default: off)")

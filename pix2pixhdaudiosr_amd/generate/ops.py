@@ -75,9 +75,15 @@ def segments_stitch_planar(seg, C, stride, gain=1.0, out_length=None, ld=None):
     return out[:, :max(L_out, 0)]
 
 
-def pcm_decode(payload, frames, channels, format_tag, bits):
+PCM_BIG_ENDIAN, PCM_SIGNED8 = 1, 2                                          # P2PHD_PCM_* flags of include/p2phd.h
+
+
+def pcm_decode(payload, frames, channels, format_tag, bits, big_endian=False, signed8=False):
     """payload: uint8 tensor on the GPU holding the interleaved little-endian samples of a data chunk (any byte offset into
-    its storage) -> [channels, frames] f32, bit-identical to what wavio.load returns for the file."""
+    its storage) -> [channels, frames] f32, bit-identical to what wavio.load returns for the file.
+    `big_endian`, `signed8`: the payload of an AIFF, AU or SPHERE file (data/containers.py) -- most significant byte first, and 8-bit
+    samples in two's complement (8 bit only) -> the bits of its WAV twin (p2phd_pcm_decode_ex: one launch of the family "pcm" as
+    well).  With both false the call is p2phd_pcm_decode's."""
     b = _lib.require_gpu_tensor(payload, "pcm_decode: payload", torch.uint8)
     fmt = PCM_FORMATS.get((int(format_tag), int(bits)))
     if fmt is None:
@@ -86,6 +92,10 @@ def pcm_decode(payload, frames, channels, format_tag, bits):
     if b.numel() < frames * channels * (int(bits) // 8):
         raise ValueError("pcm_decode: %d bytes do not hold %d frames of %d x %d bit" % (b.numel(), frames, channels, bits))
     out = torch.empty((channels, frames), dtype=torch.float32, device=b.device)
+    if big_endian or signed8:
+        flags = (PCM_BIG_ENDIAN if big_endian else 0) | (PCM_SIGNED8 if signed8 else 0)
+        _lib.check(_lib.lib().p2phd_pcm_decode_ex(_lib.ptr(b), frames, channels, fmt, flags, _lib.ptr(out), frames, _lib.stream_ptr()), "pcm_decode_ex")
+        return out
     _lib.check(_lib.lib().p2phd_pcm_decode(_lib.ptr(b), frames, channels, fmt, _lib.ptr(out), frames, _lib.stream_ptr()), "pcm_decode")
     return out
 

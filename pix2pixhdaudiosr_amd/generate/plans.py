@@ -666,7 +666,8 @@ def spectrogram_lut():
     return lut
 
 
-INPUT_FORMATS = ('wav', 'flac')                                             # extensions a folder scan can list
+# extensions a folder scan can list: RIFF/WAVE, FLAC, and the big-endian containers of data/containers.py (AIFF / AIFF-C, AU, SPHERE)
+INPUT_FORMATS = ('wav', 'flac', 'aif', 'aiff', 'aifc', 'au', 'snd', 'sph')
 
 
 def check_input_formats(formats, who="plan_folder"):
@@ -726,7 +727,7 @@ def plan_folder(dir_in, dir_out, formats=('wav',), ext='.wav'):
     """[(relative path, input path, output path)] of every *.wav under dir_in, recursive, sorted by relative path; the
     output keeps the relative path under dir_out.  Other files are ignored.  `formats`: the extensions that are listed
     (check_input_formats; default: wav alone); `ext`: the extension every output gets ('.wav'; '.flac' with container='flac'), so
-    with the default x.flac is written as x.wav, and two inputs that would be written to the same path are a ValueError."""
+    with the default x.flac or x.aif is written as x.wav, and two inputs that would be written to the same path are a ValueError."""
     if ext not in ('.wav', '.flac'):
         raise ValueError("plan_folder: ext must be '.wav' or '.flac', got %r" % (ext,))
     formats = check_input_formats(formats)

@@ -384,10 +384,15 @@ class SuperResolver:
     def _read(self, path, slot='in0', verify=False):
         """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo).  A file whose
         first bytes say FLAC (data/audiofile.py) goes through _read_flac instead; `verify` is its.  A coded data chunk (G.711, IMA
-        ADPCM: wavio.CODED_TAGS) is read as it stands; an IMA block header with a step index above 88 is a ValueError here."""
-        from ..data import audiofile, wavio
-        if audiofile.kind(path) == 'flac':
+        ADPCM: wavio.CODED_TAGS) is read as it stands; an IMA block header with a step index above 88 is a ValueError here.  An
+        AIFF, AU or SPHERE file (data/containers.py) brings its sound data as it stands and a containers.AudioInfo."""
+        from ..data import audiofile, containers, wavio
+        kind = audiofile.kind(path)
+        if kind == 'flac':
             return self._read_flac(path, slot, verify)
+        if kind != 'wav':                                                   # AIFF, AU, SPHERE: the sound data as it stands, an AudioInfo
+            payload, meta = containers.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
+            return self._pins[slot][0][:len(payload)], meta, slot
         payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
         if meta.format_tag == 0x11:                                         # IMA ADPCM: the block headers, before the copy (names file and block)
             wavio.ima_scan(payload, meta.num_channels, meta.block_align, os.fspath(path))
@@ -440,6 +445,9 @@ class SuperResolver:
             return g711_decode(dev, meta.num_frames, meta.num_channels, 'alaw' if meta.format_tag == 6 else 'ulaw')
         if meta.format_tag == 0x11:                                         # IMA ADPCM; _read has scanned the block headers
             return ima_decode(dev, meta.num_frames, meta.num_channels, meta.block_align)
+        if getattr(meta, 'big_endian', False) or getattr(meta, 'signed8', False):     # an AudioInfo (data/containers.py)
+            return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample, big_endian=meta.big_endian,
+                              signed8=meta.signed8)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
     def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,
@@ -882,8 +890,10 @@ class SuperResolver:
         computed on that channel alone; 'info' is the input's wavio.WavInfo.  A FLAC input (told by its first bytes, not its name) is
         read as it stands: its bytes and frame index are copied and csrc/flac.hip decodes them on the device (two launches of the
         family "flac" in place of the PCM decoder's one); 'info' is then its flacio.FlacInfo, everything else is what the same
-        samples in a wav give.  `verify_input`: a FLAC input is first decoded on the host and refused with a ValueError where its
-        samples do not have STREAMINFO's MD5.  `extended_metrics`: the result gains
+        samples in a wav give.  An AIFF / AIFF-C, AU or NIST SPHERE input (first bytes 'FORM', '.snd', 'NIST'; data/containers.py) is
+        read as it stands too: one copy and one decoder launch, 'info' is its containers.AudioInfo, the rest is what its WAV twin
+        gives; a coding that is not read is a ValueError that names file and coding.  `verify_input`: a FLAC input is first decoded
+        on the host and refused with a ValueError where its samples do not have STREAMINFO's MD5.  `extended_metrics`: the result gains
         'metrics_ext', util.compute_matrics_ext of all written channels from one device call -- a list with one dict
         (util.METRIC_ROW_NAMES -> float) per written channel, also with 'first'; None where 'metrics' is None -- and 'metrics'
         holds the same rows' figures.

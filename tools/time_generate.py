@@ -22,6 +22,10 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             tests/_wavcodec_ref.py), each beside its PCM16 twin: enhance_file(is_lr_input) and _read + _decode alone, interleaved, median
             and spread of --reps; then by events the two kernels of csrc/wavcodec.hip beside p2phd_pcm_decode, on the clip and on an hour
             of it; the host entries on one thread; log in --wavcodec_log
+  containers  (only when asked for) AIFF, AU and NIST SPHERE input: one 15 s mono clip as AIFF 16-bit and SPHERE pcm at 48 kHz and as AU
+            mu-law at 8 kHz (written by tests/_containers_ref.py), each beside its WAV twin: enhance_file and _read + _decode alone,
+            interleaved, median and range of --reps; then by events p2phd_pcm_decode_ex (big-endian) at S16 / S24 / F32 beside
+            p2phd_pcm_decode on the byte-swapped twin, on the clip and on an hour of it; log in --containers_log
 
   folder    (only when asked for) a folder of identical 15 s stereo PCM16 clips, end to end from the files to the files, two
             ways in one process: the host-codec loop over channel-files (wavio.load -> enhance_lr -> wavio.save per mono
@@ -114,6 +118,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
         python tools/time_generate.py flacout [--flac_lpc 12] [--flacout_log profiles/time_generate_flacout.log] [--flaclpc_log profiles/time_generate_flaclpc.log]
         python tools/time_generate.py wavcodec [--wavcodec_log profiles/time_generate_wavcodec.log]
+        python tools/time_generate.py containers [--containers_log profiles/time_generate_containers.log]
 """
 import argparse
 import os
@@ -1199,6 +1204,104 @@ def run_wavcodec(seconds, reps, log):
             f.write(text)
 
 
+def run_containers(seconds, reps, log):
+    """AIFF, AU and NIST SPHERE input (data/containers.py, p2phd_pcm_decode_ex of csrc/pcm.hip) against the WAV twin of the same
+    samples, written by the restatement tests/_containers_ref.py: a mono clip at 48 kHz as AIFF 16-bit and as SPHERE pcm (byte format
+    10), and its 8 kHz decimation as AU mu-law (is_lr_input).  Interleaved: enhance_file per file, and the input side alone (_read +
+    _decode).  Then, by events, p2phd_pcm_decode_ex with P2PHD_PCM_BIG_ENDIAN at S16 / S24 / F32 beside p2phd_pcm_decode on the
+    byte-swapped twin -- the yardstick is the little-endian kernel of the same tree -- on the clip and on an hour of it (the clip's
+    bytes 240 times over)."""
+    import tempfile
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _containers_ref as R
+    import _wavcodec_ref as W
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import audiofile, wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, pcm_decode
+    rate = opt.hr_sampling_rate
+    n = int(seconds * rate)
+    ints = torch.round(0.5 * x[0, :n].cpu().double() * 32768.0).clamp(-32768, 32767).to(torch.int64).numpy()[None]
+    low = ints[:, ::6]
+    codes = W.g711_encode(low, W.ULAW)
+    lines = ["# tools/time_generate.py containers: one %g s mono clip at %d Hz (%d samples) as AIFF 16-bit and SPHERE pcm (big-endian), and its 8 kHz "
+             "decimation (%d samples) as AU mu-law, each beside its WAV twin; %d interleaved repeats" % (seconds, rate, n, low.shape[1], reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = {k: os.path.join(tmp, k) for k in ("aiff.aif", "aiff_twin.wav", "sphere.sph", "sphere_twin.wav", "au_ulaw.au", "au_ulaw_twin.wav")}
+        with open(paths["aiff.aif"], "wb") as f:
+            f.write(R.aiff(R.int_bytes(ints, 2), 1, n, 16, rate=rate))
+        with open(paths["sphere.sph"], "wb") as f:
+            f.write(R.sphere(R.int_bytes(ints, 2), R.sphere_fields(1, rate, 2, n, "pcm", "10")))
+        with open(paths["au_ulaw.au"], "wb") as f:
+            f.write(R.au(codes, 1, 8000, 1))
+        W.write_pcm16_wav(paths["aiff_twin.wav"], ints, rate)
+        W.write_pcm16_wav(paths["sphere_twin.wav"], ints, rate)
+        W.write_pcm16_wav(paths["au_ulaw_twin.wav"], W.g711_decode(codes, low.shape[1], 1, W.ULAW), 8000)
+        order = list(paths)
+        for a, b in zip(order[0::2], order[1::2]):
+            assert torch.equal(audiofile.load(paths[a])[0].view(torch.int32), wavio.load(paths[b])[0].view(torch.int32))
+        sr = SuperResolver(model, opt, overlap=0.25)
+        out = os.path.join(tmp, "out.wav")
+        for what, fn in (("enhance_file, file to file (the 8 kHz pair with is_lr_input)", lambda k: sr.enhance_file(paths[k], out, is_lr_input=k.startswith("au"))),
+                         ("_read + _decode alone", lambda k: sr._decode(*sr._read(paths[k])))):
+            for k in order:
+                fn(k); fn(k)
+            torch.cuda.synchronize()
+            ts = {k: [] for k in order}
+            for _ in range(reps):
+                for k in order:
+                    t0 = time.perf_counter()
+                    fn(k)
+                    torch.cuda.synchronize()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            lines.append(what + ":")
+            for k in order:
+                tk = ts[k]
+                lines.append("  %-16s median %8.3f ms   range %.3f .. %.3f   runs: %s" % (k, _median(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+            for a, b in zip(order[0::2], order[1::2]):
+                lines.append("  %s - its twin: %+.3f ms of medians; the twin's own spread %.3f ms" % (a, _median(ts[a]) - _median(ts[b]), max(ts[b]) - min(ts[b])))
+    i24 = ints * 256 + 37
+    f32 = (ints / 32768.0).astype(np.float32)
+    pay = {("S16", True): R.int_bytes(ints, 2), ("S16", False): R.int_bytes(ints, 2, False), ("S24", True): R.int_bytes(i24, 3),
+           ("S24", False): R.int_bytes(i24, 3, False), ("F32", True): R.float_bytes(f32, 4), ("F32", False): R.float_bytes(f32, 4, False)}
+    dev = {k: torch.frombuffer(bytearray(v), dtype=torch.uint8).cuda() for k, v in pay.items()}
+    fmt = {"S16": (1, 16), "S24": (1, 24), "F32": (3, 32)}
+    for name, c in (("the clip", 1), ("an hour", 3600 * rate // n)):
+        L = n * c
+        kinds = []
+        for f in ("S16", "S24", "F32"):
+            be, le = dev[(f, True)].repeat(c), dev[(f, False)].repeat(c)
+            kinds.append(("pcm_decode_ex %s big-endian" % f, lambda be=be, f=f: pcm_decode(be, L, 1, *fmt[f], big_endian=True)))
+            kinds.append(("pcm_decode %s" % f, lambda le=le, f=f: pcm_decode(le, L, 1, *fmt[f])))
+        assert all(torch.equal(kinds[i][1]().view(torch.int32), kinds[i + 1][1]().view(torch.int32)) for i in (0, 2, 4))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(kinds) + 1)]
+        ks = [[] for _ in kinds]
+        for _ in range(reps + 2):
+            outs = []
+            ev[0].record()
+            for k, (_, fn) in enumerate(kinds):
+                outs.append(fn())
+                ev[k + 1].record()
+            torch.cuda.synchronize()
+            for k in range(len(kinds)):
+                ks[k].append(ev[k].elapsed_time(ev[k + 1]) * 1e3)
+            del outs
+        lines.append("by events on %s (median of %d, each with the allocation of its result in front; %d samples):" % (name, reps, L))
+        for (kn, _), k in zip(kinds, ks):
+            lines.append("  %-28s %9.1f us (range %.1f .. %.1f) = %.4f ns per sample   runs: %s"
+                         % (kn, _median(k[2:]), min(k[2:]), max(k[2:]), _median(k[2:]) * 1e3 / L, " ".join("%.1f" % v for v in k[2:])))
+        for i in (0, 2, 4):
+            lines.append("  %s - %s: %+.1f us of medians; the little-endian kernel's own spread %.1f us"
+                         % (kinds[i][0], kinds[i + 1][0], _median(ks[i][2:]) - _median(ks[i + 1][2:]), max(ks[i + 1][2:]) - min(ks[i + 1][2:])))
+    lines.append("not measured here: the WAV path and the benchmark step against the parent commit in alternating processes")
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_flacout(seconds, reps, log):
     """The output side, file to file: enhance_file with container 'wav' and 'flac' on one mono and one stereo 16-bit clip, interleaved.
     Then, by events, p2phd_flac_encode (generate.flac_encode: its allocations in front) beside p2phd_pcm_encode_ex on the written
@@ -1698,7 +1801,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec", "containers"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1717,6 +1820,7 @@ def main():
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--wavcodec_log", default=os.path.join(ROOT, "profiles", "time_generate_wavcodec.log"))
+    ap.add_argument("--containers_log", default=os.path.join(ROOT, "profiles", "time_generate_containers.log"))
     ap.add_argument("--flacout_log", default=os.path.join(ROOT, "profiles", "time_generate_flacout.log"))
     ap.add_argument("--flac_lpc", type=int, default=None, metavar="N", help="flacout mode: time the LPC option at order N against the writer without it (log in --flaclpc_log)")
     ap.add_argument("--flaclpc_log", default=os.path.join(ROOT, "profiles", "time_generate_flaclpc.log"))
@@ -1729,6 +1833,8 @@ def main():
         return run_flaclpc(a.seconds, 9 if a.reps is None else a.reps, a.flaclpc_log, a.flac_lpc)
     if a.mode == "flacout":
         return run_flacout(a.seconds, 9 if a.reps is None else a.reps, a.flacout_log)
+    if a.mode == "containers":
+        return run_containers(a.seconds, 9 if a.reps is None else a.reps, a.containers_log)
     if a.mode == "wavcodec":
         return run_wavcodec(a.seconds, 9 if a.reps is None else a.reps, a.wavcodec_log)
     if a.mode == "flac":
