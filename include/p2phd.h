@@ -68,6 +68,8 @@ int p2phd_device_info(char* name, int cap);
  *                      tests run the path on which a workgroup walks several tiles at a small size); the result's bits do not depend on it
  *   "limiter_grid" n   workgroups of p2phd_limiter_envelope and of p2phd_limiter_apply at most (0 = one per tile, as far as the partial table
  *                      has rows; 1 .. 16384: tests run the path on which a workgroup walks several tiles); the result's bits do not depend on it
+ *   "speechlevel_grid" n  workgroups per row of p2phd_speechlevel_envelope and of p2phd_speechlevel_counts at most (0 = one per tile up to
+ *                      2048; 1 .. 16384: tests run the path on which a workgroup walks several tiles); the result's bits do not depend on it
  *   "cw_inject" 0|1    libp2phd_hip_chk.so only: selects round 4's too-lax HALO wait (sensitivity check of p2phd_wait_check) */
 int p2phd_set_option(const char* name, int value);
 /* zeroes the arrival tickets of the fixed-order reductions on `stream` (17 KB memset; see "Streams" above) */
@@ -100,7 +102,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * "shaper" (the noise-shaped dither of its PCM16 encoder, csrc/shaper.hip), "flac" (the two kernels of its FLAC input,
  * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), "flacenc" (the three kernels of its FLAC output, csrc/flacenc.hip:
  * a p2phd_flac_encode counts 3), "wavcodec" (the G.711 and IMA ADPCM decoders of its coded WAV input, csrc/wavcodec.hip: one per
- * call with frames > 0), and the weight packs of p2phd_conv_pack_weights /
+ * call with frames > 0), "speechlevel" (the envelope, the counts and the decision of its active speech level, csrc/speechlevel.hip:
+ * one per entry with frames > 0), and the weight packs of p2phd_conv_pack_weights /
  * p2phd_conv_fp8_pack_weights, one family per kernel of csrc/wpack.hip, counted per launch plan: "wpack_generic" (the tap walk),
  * "wpack_dense", "wpack_transposed" (the two LDS re-orderings), "wpack_kmajor" (cast of K-major master weights), "wpack_kmajor_t"
  * (their per-tap transpose), "wpack_merged" (merged sub-pixel launches, either tap order), "wpack_fp8" (the e4m3 quantiser with
@@ -443,6 +446,64 @@ int p2phd_loudness_range(const double* p, int64_t NS, double* res8, void* stream
 int p2phd_loudness_blocks(const double* z, int64_t J, int channels, int rate, const float* weights, double* p, void* stream);
 int p2phd_loudness_gate_blocks(const double* p, int64_t NB, double target, const double* target_dev, double max_gain_db, double* res4,
                                float* gain, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Active speech level of whole-file generation after ITU-T P.56 method B, csrc/speechlevel.hip.  Launch family "speechlevel":
+ * p2phd_speechlevel_envelope, p2phd_speechlevel_counts and p2phd_speechlevel_decide with frames > 0 count 1 each, 3 per measured
+ * clip, 6 per file (the clip the generator was given and the generated one).  The procedure is method B as the speech voltmeter
+ * of the ITU-T Software Tool Library implements it, WRITTEN FROM MEMORY (the Recommendation's text was not at hand), with a linear
+ * interpolation in dB where the tool bisects to 0.5 dB.  No 200 .. 5500 Hz weighting, no DC figure, no method A.
+ *
+ * Units: levels are in dBov for samples in [-1, 1): 10 log10(mean x^2); a full-scale sine reads -3.01.  P.56 is defined on one
+ * channel: every row is measured on its own.  The file's figure is that of the channel with the highest finite active level, the
+ * lowest channel index on a tie (no finite level: the first channel whose level is not -inf, else channel 0); one gain applies
+ * to all channels.  A file whose channels all have no activity has the level -inf and the gain 1.
+ *
+ * Constants, all float64, f = the rate, an int in 8000 .. 192000: g = exp(-1 / (0.03 f)); h = 1 - g; I = ceil(0.2 f) = (f + 4) / 5
+ * in integers; M = 15.9; the 15 thresholds c_j = 2^(j - 15), j = 0 .. 14; L = 256; gL = g squared eight times; hL = (256 h) gL.
+ * p2phd_speechlevel_consts_fill (HOST only): out8 = {g, h, gL, hL, M, c_0, L, I}, *hang = I; rate outside the range: P2PHD_EINVAL.
+ *
+ * Envelope: r_i = |x_i| (fp32 to float64, exact); p_i = (g p_{i-1}) + (h r_i); q_i = (g q_{i-1}) + (h p_i): every operation a
+ * separate IEEE double multiply or add, nothing contracted.  The parallel order is the contract.  Chunk k holds the samples
+ * [k L, k L + L), the last may be shorter.
+ *   1. the recursion from (0, 0) over each full chunk -> (zp_k, zq_k);
+ *   2. left to right over the chunks: P_0 = Q_0 = 0; Q_{k+1} = ((gL Q_k) + (hL P_k)) + zq_k; P_{k+1} = (gL P_k) + zp_k;
+ *   3. the recursion over each chunk again from (P_k, Q_k) -> q_i.
+ * Threshold index: m_i = the number of j with q_i >= c_j, a uint8 in 0 .. 15; a NaN q gives 0.
+ * Energy: s_k = the sum of x_i^2 over chunk k, left to right (each product exact in float64); sq = the sum of s_k, left to right.
+ * Activity: tm_i = max(m_{max(0, i - I)} .. m_i); a_j = #{i : tm_i > j}, int64 -- the 200 ms hangover counters of P.56 exactly
+ * (the thresholds are nested, so the trailing maximum of the index is the hangover of all of them).
+ * Decision, n frames: long_term = 10 log10(sq / n); for j with a_j > 0: A_j = 10 log10(sq / a_j), D_j = A_j - 20 log10(c_j).
+ *   a_0 = 0: no activity, the level is -inf, the activity 0, the bracket -1.  Otherwise the first j with D_j <= M: j = 0 gives A_0,
+ *   j > 0 gives A = A_{j-1} + t (A_j - A_{j-1}), t = (D_{j-1} - M) / (D_{j-1} - D_j); no such j before a_j = 0 or j = 15: the last
+ *   valid A_j (the bracket is that j).  activity = 10^((long_term - A) / 10).  A non-finite sq gives a non-finite level.
+ * Gain: T = *target_dev where target_dev != NULL (a device float64, e.g. the file figure of another clip's res: no host round
+ *   trip), else `target`; gain[0] = (float) 10^(clamp(T - A_file, -max_gain_db, +max_gain_db) / 20), float64 arithmetic rounded
+ *   once; gain[0] = 1 where T or A_file is not finite (target NaN: no target).  max_gain_db finite and >= 0.
+ *
+ * p2phd_speechlevel_workspace_bytes (host): bytes of the envelope's workspace, channels * ceil(frames / 256) * 24; 0 for frames <= 0.
+ * p2phd_speechlevel_tile_len (host): samples per workgroup tile of the envelope's and the counts' grids (16384).
+ * p2phd_speechlevel_envelope: planar [channels][ld] f32 rows (layout and checks of p2phd_pcm_encode; 1 <= channels <= 64; rows may
+ *   start at any float) -> m [channels][ld_m] uint8 (bytes behind `frames` of a row are not touched) and sq [channels] float64, on
+ *   the device; `workspace`: the caller's, of the queried size, 8-byte aligned, every byte the call reads it has written before;
+ *   after the call it holds, per row, P_k, Q_k and s_k as three float64 arrays of ceil(frames / 256) (what the tests compare bit for bit).
+ *   Three kernels behind one another on the stream (steps 1, 2, 3), counted as one launch.  frames = 0: P2PHD_OK, nothing launched.
+ * p2phd_speechlevel_counts: m -> a [channels][16] int64 (device), zeroed by the entry on the stream; a[c][15] is unused padding
+ *   and stays 0.  Integer counts met by integer atomics: the same bits on every run.  frames = 0: a is zeroed, nothing launched.
+ * p2phd_speechlevel_decide: sq, a -> res [(channels + 1)][4] float64 and gain (1 f32), device; one workgroup, always launches.
+ *   Row c = {active level, long-term level, activity, bracket j}; row `channels` = the file's figure {active, long-term, activity,
+ *   channel index}.  frames = 0: every row {-inf, -inf, 0, -1}, the file's {.., 0}, gain 1.
+ * The grids are capped at 2048 workgroups per row and walk the tiles beyond with their stride ("speechlevel_grid" of
+ * p2phd_set_option lowers the cap); the result's bits depend on neither.  No float atomics, no scratch, nothing waits on the host.
+ * ---------------------------------------------------------------------------------------- */
+int p2phd_speechlevel_consts_fill(int rate, double* out8, int* hang);
+size_t p2phd_speechlevel_workspace_bytes(int64_t frames, int channels);
+int p2phd_speechlevel_tile_len(void);
+int p2phd_speechlevel_envelope(const float* planar, int64_t frames, int channels, int64_t ld, int rate, uint8_t* m, int64_t ld_m, double* sq,
+                               void* workspace, void* stream);
+int p2phd_speechlevel_counts(const uint8_t* m, int64_t frames, int channels, int64_t ld_m, int rate, int64_t* a, void* stream);
+int p2phd_speechlevel_decide(const double* sq, const int64_t* a, int64_t frames, int channels, double target, const double* target_dev,
+                             double max_gain_db, double* res, float* gain, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * True peak of whole-file generation after ITU-R BS.1770-4 Annex 2 (oversample, take the largest magnitude), csrc/truepeak.hip.

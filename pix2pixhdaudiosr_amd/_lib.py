@@ -69,6 +69,12 @@ SIGNATURES = {
     "p2phd_loudness_range": (_i32, [_vp, _i64, _vp, _vp]),
     "p2phd_loudness_blocks": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "p2phd_loudness_gate_blocks": (_i32, [_vp, _i64, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
+    "p2phd_speechlevel_consts_fill": (_i32, [_i32, _vp, C.POINTER(_i32)]),
+    "p2phd_speechlevel_workspace_bytes": (_sz, [_i64, _i32]),
+    "p2phd_speechlevel_tile_len": (_i32, []),
+    "p2phd_speechlevel_envelope": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "p2phd_speechlevel_counts": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "p2phd_speechlevel_decide": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, C.c_double, _vp, _vp, _vp]),
     "p2phd_truepeak_taps_fill": (_i32, [_i32, _i32, C.c_double, _vp]),
     "p2phd_truepeak": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _f32, _vp, _vp, _vp]),
     "p2phd_truepeak_tile_len": (_i32, []),

@@ -76,7 +76,7 @@ int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, in
 enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192,
                     LC_DFIRST, LC_DLAST, LC_C7, LC_THIN_WGRAD, LC_TIMED_PACK, LC_TIMED_FRAMES, LC_STITCH, LC_PCM, LC_METRICS_ROWS,
                     LC_XOVER, LC_SPECIMG, LC_LOUDNESS, LC_TRUEPEAK, LC_LIMITER, LC_BANDWIDTH, LC_STEREO, LC_RATECONV, LC_NORMSCOPE,
-                    LC_SHAPER, LC_FLAC, LC_FLACENC, LC_WAVCODEC,
+                    LC_SHAPER, LC_FLAC, LC_FLACENC, LC_WAVCODEC, LC_SPEECHLEVEL,
                     // which weight pack p2phd_conv_pack_weights / p2phd_conv_fp8_pack_weights started (wpack.hip, one family per kernel;
                     // LC_WPACK_FRAG: the fragment pack of a dedicated kernel, counted in convapi.hip)
                     LC_WPACK_GENERIC, LC_WPACK_DENSE, LC_WPACK_TRANSPOSED, LC_WPACK_KMAJOR, LC_WPACK_KMAJOR_T, LC_WPACK_MERGED, LC_WPACK_FP8,
@@ -95,6 +95,7 @@ extern int g_opt_c7_generic;
 extern int g_opt_splitk_tail;       // 0: every tile is one workgroup, 1 (default): split-K tail where the cost model says so, 2: wherever possible (tests)
 extern int g_opt_truepeak_grid;     // > 0: workgroups per row of p2phd_truepeak at most (tests: several tiles per workgroup at a small size)
 extern int g_opt_limiter_grid;      // > 0: workgroups of p2phd_limiter_envelope / p2phd_limiter_apply at most (tests: several tiles per workgroup)
+extern int g_opt_speechlevel_grid; // > 0: workgroups per row of p2phd_speechlevel_envelope / p2phd_speechlevel_counts at most (tests: several tiles per workgroup)
 extern int g_opt_cus;               // > 0: CUs a conv launch may count on (a CU-masked compute stream); 0 = all of the device's
 int device_cus();                   // multiProcessorCount of the current device, cached per device
 extern int g_opt_reflect_generic;   // 1: reflect-padded 3x3 input gradients on the padded grid + fold (the general form)

@@ -14,7 +14,7 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace p2phd
 
-namespace p2phd { int g_opt_gconv_bm = 0; int g_opt_wgrad_tm = 0; int g_opt_wgrad_xcd = 1; int g_opt_march = 1; int g_opt_cls_skip = 1; int g_opt_gconv_halo = 1; int g_opt_cw_inject = 0; int g_opt_tile128x192 = 1; int g_opt_mdct_generic = 0; int g_opt_mdct_iters = 0; int g_opt_c7_generic = 0; int g_opt_dfirst = 1; int g_opt_dlast = 1; int g_opt_c7_abl = 0; int g_opt_reflect_generic = 0; int g_opt_splitk_tail = 1; int g_opt_truepeak_grid = 0; int g_opt_limiter_grid = 0; int g_opt_cus = 0;
+namespace p2phd { int g_opt_gconv_bm = 0; int g_opt_wgrad_tm = 0; int g_opt_wgrad_xcd = 1; int g_opt_march = 1; int g_opt_cls_skip = 1; int g_opt_gconv_halo = 1; int g_opt_cw_inject = 0; int g_opt_tile128x192 = 1; int g_opt_mdct_generic = 0; int g_opt_mdct_iters = 0; int g_opt_c7_generic = 0; int g_opt_dfirst = 1; int g_opt_dlast = 1; int g_opt_c7_abl = 0; int g_opt_reflect_generic = 0; int g_opt_splitk_tail = 1; int g_opt_truepeak_grid = 0; int g_opt_limiter_grid = 0; int g_opt_speechlevel_grid = 0; int g_opt_cus = 0;
 unsigned long long g_launch_count[LC_FAMILIES] = {};
 int device_cus() {
   static int cached[64] = {};
@@ -154,6 +154,7 @@ extern "C" int p2phd_set_option(const char* name, int value) {
   if (name && !strcmp(name, "cus") && value >= 0 && value <= 4096) { p2phd::g_opt_cus = value; return P2PHD_OK; }
   if (name && !strcmp(name, "truepeak_grid") && value >= 0 && value <= 65536) { p2phd::g_opt_truepeak_grid = value; return P2PHD_OK; }
   if (name && !strcmp(name, "limiter_grid") && value >= 0 && value <= 16384) { p2phd::g_opt_limiter_grid = value; return P2PHD_OK; }
+  if (name && !strcmp(name, "speechlevel_grid") && value >= 0 && value <= 16384) { p2phd::g_opt_speechlevel_grid = value; return P2PHD_OK; }
   if (name && !strcmp(name, "c7_abl")) { p2phd::g_opt_c7_abl = value; return P2PHD_OK; }
   if (name && !strcmp(name, "c7_generic") && (value == 0 || value == 1)) { p2phd::g_opt_c7_generic = value; return P2PHD_OK; }
   if (name && !strcmp(name, "mdct_generic") && (value == 0 || value == 1)) { p2phd::g_opt_mdct_generic = value; return P2PHD_OK; }
@@ -165,7 +166,7 @@ extern "C" int64_t p2phd_launch_count(const char* family, int reset) {
   static const char* names[p2phd::LC_FAMILIES] = {"gconv", "halo", "cls_skip", "march", "march_w", "wgrad", "splitk", "tile256", "tile128x192",
                                                        "dfirst", "dlast", "c7", "thin_wgrad", "timed_pack", "timed_frames", "stitch", "pcm",
                                                        "metrics_rows", "xover", "specimg", "loudness", "truepeak", "limiter", "bandwidth", "stereo", "rateconv",
-                                                       "normscope", "shaper", "flac", "flacenc", "wavcodec", "wpack_generic", "wpack_dense", "wpack_transposed",
+                                                       "normscope", "shaper", "flac", "flacenc", "wavcodec", "speechlevel", "wpack_generic", "wpack_dense", "wpack_transposed",
                                                        "wpack_kmajor", "wpack_kmajor_t", "wpack_merged", "wpack_fp8", "wpack_frag"};
   if (family == nullptr) {                                       // all families at once
     if (reset) for (auto& c : p2phd::g_launch_count) c = 0;

@@ -106,17 +106,24 @@ through `flac_encode` there -- one workgroup per frame, fixed predictors, Rice p
 bit counts -- and the file, decoded, is the wav's data chunk byte for byte.  `--flac_lpc N` also tries LPC subframes of every order
 up to N (a predictor fitted per block, still chosen on exact bit counts; the file is never longer), `--flac_block N` sets the frame length, `--flac_md5`
 brings the payload back as well and writes its MD5; a folder's outputs are then named .flac (`plan_folder(..., ext=)`).
+
+`--speech_level report|input|DBOV` (opt-in, csrc/speechlevel.hip) measures the active speech level after ITU-T P.56 method B -- the
+level while somebody is speaking, in dBov, with its activity factor -- of the same two clips, per channel, and brings the written
+clip to the input's level or to a level such as -26 with one gain for all channels, where the loudness gain would sit
+(`speech_level_envelope`, `speech_level_counts`, `speech_level_decide`, `speech_level`).  It excludes `--loudness`: one gain, one claim.
 """
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, G711_LAWS, g711_decode, ima_decode, flac_decode, flac_encode, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, shaper_coefficients, segments_gather, segments_gather_planar, segments_stitch,
-                  segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks)
+                  segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks,
+                  speech_level, speech_level_consts, speech_level_counts, speech_level_decide, speech_level_envelope)
 from .plans import (INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,
                     check_spectrogram, check_true_peak, crossover_plan, crossover_width_hz, encoding_limit, limiter_plan, loudness_channel_weights, plan_folder,
-                    segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan)
+                    segment_plan, select_channels, spectro_bins, spectrogram_lut, truepeak_plan,
+                    SPEECH_LEVEL_DEFAULTS, SPEECH_LEVEL_MODES, check_speech_level, check_speech_level_rate)
 from .report import (METRICS_COLUMNS, METRICS_COLUMNS_BANDWIDTH, METRICS_COLUMNS_EXT, METRICS_COLUMNS_LIMITER, METRICS_COLUMNS_LOUDNESS, METRICS_COLUMNS_LOUDNESS_RANGE, METRICS_COLUMNS_PEAKS,  # noqa: F401
-                     METRICS_COLUMNS_STEREO, METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
+                     METRICS_COLUMNS_SPEECH_LEVEL, METRICS_COLUMNS_STEREO, METRICS_COLUMNS_TRUE_PEAK, metrics_rows, write_metrics_csv)
 from .resolver import SuperResolver, spectrogram_image                                                                              # noqa: F401

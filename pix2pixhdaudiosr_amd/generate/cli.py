@@ -11,9 +11,9 @@ from types import SimpleNamespace
 import torch
 
 from .ops import shaper_coefficients
-from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MODES, check_lowband,
                     check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
-from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
+from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_speech_level, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
 
@@ -80,6 +80,15 @@ def _loudness_arg(text):
         raise argparse.ArgumentTypeError("expected report, input or a target in LUFS such as -23, got %r" % text)
 
 
+def _speech_level_arg(text):
+    if text in SPEECH_LEVEL_MODES:
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected report, input or a target in dBov such as -26, got %r" % text)
+
+
 def _crossover_hz_arg(text):
     if text == CROSSOVER_AUTO:
         return text
@@ -134,6 +143,17 @@ def _loudness_args(a, hr_rate=None, folder_mode=False):
         check_loudness_scope(a.loudness_scope, loud, "generate", folder_mode, a.limiter, a.spectrogram)
         kw['loudness_scope'] = a.loudness_scope
     return kw
+
+
+def _speech_level_args(a, rates=()):
+    """The speech-level options of the command line -> the keyword arguments of enhance_file / enhance_folder ({} without
+    --speech_level); ValueError for a bad one.  `rates`: the rates the clips are measured at, as far as they are known."""
+    sl = check_speech_level(a.speech_level, "generate", a.speech_level_max_gain_db, a.loudness)
+    if sl is None:
+        return {}
+    for rate in rates:
+        check_speech_level_rate(rate, "generate")
+    return dict(speech_level=a.speech_level, speech_level_max_gain_db=a.speech_level_max_gain_db)
 
 
 def _spectrogram_args(a, folder_mode):
@@ -240,6 +260,14 @@ def _parser():
                          "the generated clip, and print both per file (report); also scale the written clip to the input's loudness "
                          "(input) or to a target in LUFS, -70 .. 0, such as -23; three more columns (lufs_in, lufs_out, "
                          "loudness_gain_db) of --metrics_csv (default: off)")
+    ap.add_argument("--speech_level", type=_speech_level_arg, default=None, metavar="report|input|DBOV",
+                    help="measure the active speech level (ITU-T P.56 method B: the level while somebody is speaking, in dBov, and the "
+                         "activity factor) of the input the generator was given and of the generated clip, and print both per file "
+                         "(report); also bring the written clip to the input's active level (input) or to a level such as -26, with one "
+                         "gain for all channels in front of the output stage; three more columns (asl_in, asl_out, activity_out) of "
+                         "--metrics_csv; not with --loudness (default: off)")
+    ap.add_argument("--speech_level_max_gain_db", type=float, default=None, metavar="DB",
+                    help="--speech_level input|DBOV: the largest gain applied, either way, 0 .. 120 (default 40)")
     ap.add_argument("--loudness_max_gain_db", type=float, default=None, metavar="DB",
                     help="--loudness input|LUFS: the largest gain applied, either way (default 40)")
     ap.add_argument("--loudness_range", action="store_true",
@@ -351,6 +379,7 @@ def main(argv=None):
         picture.update(_loudness_args(a, None, folder_mode))
         picture.update(_bandwidth_args(a))
         picture.update(_stereo_args(a))
+        picture.update(_speech_level_args(a, () if a.output_rate is None else (a.output_rate,)))
         if a.true_peak:
             picture['true_peak'] = True
         if a.output_rate is not None:                                       # (the rate pair itself: once the options file has been read)
@@ -391,6 +420,7 @@ def main(argv=None):
         rc = check_output_rate(a.output_rate, opt.hr_sampling_rate, "generate", a.loudness_scope, a.spectrogram)
         if rc is not None and a.loudness is not None:
             _loudness_args(a, rc['rate'], folder_mode)
+        _speech_level_args(a, (opt.hr_sampling_rate,) if rc is None else (opt.hr_sampling_rate, rc['rate']))
         check_dither(a.dither, a.encoding, "generate", opt.hr_sampling_rate if rc is None else rc['rate'], a.dither_curve, a.dither_chunk)
         if a.limiter:
             check_limiter(True, a.limiter_lookahead_ms, a.limiter_hold_ms, out_stage, a.encoding, opt.hr_sampling_rate if rc is None else rc['rate'],
@@ -454,6 +484,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 _print_loudness(r['path'], r['loudness'])
                 if 'range' in r['loudness']:
                     _print_loudness_range(r['path'], r['loudness']['range'])
+            if r.get('speech_level') is not None:                          # (without the option: no line more than before)
+                _print_speech_level(r['path'], r['speech_level'])
             if r.get('crossover') is not None:
                 _print_crossover(r['crossover'])
             if r.get('bandwidth') is not None:
@@ -498,6 +530,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             _print_loudness(a.output, res['loudness'])
             if 'range' in res['loudness']:
                 _print_loudness_range(a.output, res['loudness']['range'])
+        if res.get('speech_level') is not None:                             # (without the option: no line more than before)
+            _print_speech_level(a.output, res['speech_level'])
         if res.get('crossover') is not None:
             _print_crossover(res['crossover'])
         if res.get('bandwidth') is not None:
@@ -510,6 +544,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             records[0]['bandwidth'] = res['bandwidth']
         if a.stereo_report:
             records[0]['stereo'] = res['stereo']
+        if a.speech_level is not None:
+            records[0]['speech_level'] = res['speech_level']
     if a.metrics_csv:
         extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
         if a.limiter:
@@ -522,6 +558,8 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             extra['bandwidth'] = True
         if a.stereo_report:
             extra['stereo'] = True
+        if a.speech_level is not None:
+            extra['speech_level'] = True
         write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -1,12 +1,12 @@
 """Whole-file generation: the device entry points of csrc/stitch.hip, csrc/pcm.hip, csrc/xover.hip, csrc/specimg.hip,
-csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip, csrc/shaper.hip, csrc/flac.hip and csrc/flacenc.hip as tensor functions."""
+csrc/loudness.hip, csrc/truepeak.hip, csrc/limiter.hip, csrc/bandwidth.hip, csrc/stereo.hip, csrc/rateconv.hip, csrc/shaper.hip, csrc/flac.hip, csrc/flacenc.hip and csrc/speechlevel.hip as tensor functions."""
 import ctypes
 
 import torch
 
 from .. import _lib
 from .plans import (BANDWIDTH_DEFAULTS, CROSSOVER_MAX_TAPS, bandwidth_rel, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, check_dither, DITHER_CHUNK, DITHER_CURVES,
-                    check_encoding, check_loudness_rate, limiter_plan, RATECONV_DEFAULTS, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
+                    check_encoding, check_loudness_rate, check_speech_level_rate, SPEECH_LEVEL_DEFAULTS, SPEECH_LEVEL_KERNEL_CHANNELS, limiter_plan, RATECONV_DEFAULTS, spectrogram_lut, STEREO_DEFAULTS, stereo_split_bin, truepeak_plan)
 
 # (format tag, bits per sample) of a RIFF fmt chunk -> P2PHD_PCM_* code of include/p2phd.h: the set wavio.info accepts
 PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
@@ -908,3 +908,114 @@ def limit(waveform, rate, ceiling=None, lookahead_ms=None, hold_ms=None):
     plan = limiter_plan(rate, lookahead_ms, hold_ms)
     r, peak = limiter_envelope(waveform, rate, ceiling)
     return limiter_apply(waveform, r, plan) + (peak,)
+
+
+def speech_level_consts(rate):
+    """The constants of p2phd_speechlevel_consts_fill on the host (no GPU needed) -> (float64 tensor of 8: g, h, gL, hL, M, the lowest
+    threshold, L, I; the hangover I in samples as an int)."""
+    rate = check_speech_level_rate(rate, "speech_level_consts")
+    out = torch.empty(8, dtype=torch.float64)
+    hang = ctypes.c_int32(0)
+    _lib.check(_lib.lib().p2phd_speechlevel_consts_fill(rate, ctypes.c_void_p(out.data_ptr()), ctypes.byref(hang)), "speech_level_consts")
+    return out, int(hang.value)
+
+
+def speech_level_envelope(waveform, rate, m=None, workspace=None):
+    """waveform [C, L] f32 on the GPU (rows contiguous, any row pitch) -> (m [C, L] uint8, sq [C] float64) on the GPU, nothing
+    waited for: per sample the number of thresholds the two-pole envelope stands at or over, per row the energy
+    (p2phd_speechlevel_envelope).  `m`: None, or a uint8 tensor [C, >= L] with contiguous rows that takes the indices (its first
+    L columns are returned); `workspace`: None, or a uint8 tensor of at least the queried bytes.  One launch of the family
+    "speechlevel"; none for an empty clip."""
+    rate = check_speech_level_rate(rate, "speech_level_envelope")
+    w, C, L, ld = _rows(waveform, "speech_level_envelope: waveform")
+    if C > SPEECH_LEVEL_KERNEL_CHANNELS:
+        raise ValueError("speech_level_envelope: at most %d rows, got %d" % (SPEECH_LEVEL_KERNEL_CHANNELS, C))
+    lib = _lib.lib()
+    if m is None:
+        m = torch.empty((C, (L + 3) // 4 * 4), dtype=torch.uint8, device=w.device)       # (rows on 4-byte boundaries: word stores)
+    else:
+        if not isinstance(m, torch.Tensor) or not m.is_cuda or m.dtype != torch.uint8 or m.dim() != 2 or m.shape[0] != C or m.shape[1] < L \
+                or (m.shape[1] > 1 and m.stride(1) != 1):
+            raise ValueError("speech_level_envelope: m must be a uint8 tensor [%d, >= %d] on the GPU with contiguous rows" % (C, L))
+    ld_m = m.stride(0) if C > 1 else max(m.shape[1], 1)
+    need = lib.p2phd_speechlevel_workspace_bytes(L, C)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=w.device)
+    else:
+        workspace = _lib.require_gpu_tensor(workspace, "speech_level_envelope: workspace", torch.uint8)
+        if workspace.numel() < need:
+            raise ValueError("speech_level_envelope: the workspace holds %d bytes, %d are needed" % (workspace.numel(), need))
+    sq = torch.empty((C,), dtype=torch.float64, device=w.device)
+    _lib.check(lib.p2phd_speechlevel_envelope(_lib.ptr(w), L, C, max(ld, L), rate, _lib.ptr(m), max(ld_m, L), _lib.ptr(sq), _lib.ptr(workspace),
+                                              _lib.stream_ptr()), "speech_level_envelope")
+    return m[:, :L], sq
+
+
+def speech_level_counts(m, rate):
+    """m [C, L] uint8 on the GPU (rows contiguous, any row pitch) -> a [C, 16] int64 on the GPU, nothing waited for: a[c][j] = the
+    samples of row c at which the trailing maximum of m over the 200 ms hangover is over j (p2phd_speechlevel_counts); column 15
+    is padding.  One launch of the family "speechlevel"; none for an empty clip."""
+    rate = check_speech_level_rate(rate, "speech_level_counts")
+    if not isinstance(m, torch.Tensor) or not m.is_cuda or m.dtype != torch.uint8:
+        raise _lib.P2PHDError("speech_level_counts: m: expected a uint8 tensor on the GPU (this build has no CPU path)")
+    if m.dim() != 2 or not 1 <= m.shape[0] <= SPEECH_LEVEL_KERNEL_CHANNELS:
+        raise ValueError("speech_level_counts: expected m [C, L] with 1 <= C <= %d, got shape %s" % (SPEECH_LEVEL_KERNEL_CHANNELS, tuple(m.shape)))
+    C, L = m.shape
+    if L > 1 and m.stride(1) != 1 or C > 1 and m.stride(0) < L:
+        raise _lib.P2PHDError("speech_level_counts: m: expected rows that are contiguous")
+    a = torch.empty((C, 16), dtype=torch.int64, device=m.device)
+    _lib.check(_lib.lib().p2phd_speechlevel_counts(_lib.ptr(m), L, C, max(m.stride(0) if C > 1 else L, L, 1), rate, _lib.ptr(a), _lib.stream_ptr()),
+               "speech_level_counts")
+    return a
+
+
+def speech_level_packed_bytes(channels):
+    """Bytes of the packed result of one speech_level_decide: res [(C + 1), 4] f64 | gain f32 | 4 spare bytes."""
+    return (int(channels) + 1) * 32 + 8
+
+
+def _speech_level_views(buf, channels):
+    """The packed result of one speech_level_decide, on the device or its copy on the host -> (res [(C + 1), 4] f64, gain [1] f32)."""
+    n = (int(channels) + 1) * 32
+    return buf[:n].view(torch.float64).view(int(channels) + 1, 4), buf[n:n + 4].view(torch.float32)
+
+
+def speech_level_decide(sq, a, frames, target=None, target_dev=None, max_gain_db=None, out=None):
+    """sq [C] float64 and a [C, 16] int64 on the GPU -> (res, gain) on the GPU, nothing waited for: res [(C + 1), 4] float64, row c =
+    {active speech level in dBov, long-term level, activity factor, the bracket's threshold}, row C = the file's figure {active,
+    long-term, activity, the channel it is}; gain [1] f32 brings the file's figure to the wanted level, at most `max_gain_db`
+    (None: 40) either way, 1 where no level is wanted or a level is not finite (p2phd_speechlevel_decide).  The wanted level:
+    `target_dev`, a float64 tensor on the GPU whose first element the kernel reads (another clip's res[C]: no host round trip), else
+    `target` (None: none).  `out`: None, or a uint8 tensor of speech_level_packed_bytes(C) on the GPU that takes both.  One
+    launch of the family "speechlevel"."""
+    sq = _lib.require_gpu_tensor(sq, "speech_level_decide: sq", torch.float64)
+    a = _lib.require_gpu_tensor(a, "speech_level_decide: a", torch.int64)
+    if sq.dim() != 1 or not 1 <= sq.shape[0] <= SPEECH_LEVEL_KERNEL_CHANNELS or tuple(a.shape) != (sq.shape[0], 16):
+        raise ValueError("speech_level_decide: expected sq [C] and a [C, 16] with 1 <= C <= %d, got shapes %s and %s"
+                         % (SPEECH_LEVEL_KERNEL_CHANNELS, tuple(sq.shape), tuple(a.shape)))
+    C = sq.shape[0]
+    if max_gain_db is None:
+        max_gain_db = SPEECH_LEVEL_DEFAULTS['max_gain_db']
+    if target_dev is not None:
+        target_dev = _lib.require_gpu_tensor(target_dev, "speech_level_decide: target_dev", torch.float64)
+        if target_dev.numel() < 1:
+            raise ValueError("speech_level_decide: target_dev is empty")
+    nbytes = speech_level_packed_bytes(C)
+    if out is None:
+        out = torch.empty((nbytes,), dtype=torch.uint8, device=sq.device)
+    else:
+        out = _lib.require_gpu_tensor(out, "speech_level_decide: out", torch.uint8)
+        if out.numel() != nbytes:
+            raise ValueError("speech_level_decide: out must hold %d bytes, got %d" % (nbytes, out.numel()))
+    res, gain = _speech_level_views(out, C)
+    _lib.check(_lib.lib().p2phd_speechlevel_decide(_lib.ptr(sq), _lib.ptr(a), int(frames), C, float('nan') if target is None else float(target),
+                                                   _lib.ptr(target_dev), float(max_gain_db), _lib.ptr(res), _lib.ptr(gain), _lib.stream_ptr()),
+               "speech_level_decide")
+    return res, gain
+
+
+def speech_level(clip, rate, target=None, target_dev=None, max_gain_db=None, out=None):
+    """speech_level_envelope, speech_level_counts and speech_level_decide in a row: clip [C, L] f32 on the GPU -> (res, gain) on the
+    GPU.  Three launches of the family "speechlevel" (none of the first two for an empty clip), nothing is waited for."""
+    m, sq = speech_level_envelope(clip, rate)
+    return speech_level_decide(sq, speech_level_counts(m, rate), clip.shape[1], target, target_dev, max_gain_db, out)

@@ -49,6 +49,13 @@ LOUDNESS_MAX_CHANNELS = 64
 # generated clips the folder pipeline keeps on the device between measuring and writing, beyond which a clip waits on the host
 LOUDNESS_SCOPES = ('file', 'folder')
 ALBUM_CACHE_BYTES = 4 << 30
+# the speech-level option (csrc/speechlevel.hip; ITU-T P.56 method B): the largest gain either way where none is given, the modes, the
+# rates the envelope's constants are filled for and the channels the decision takes in the file pipeline
+SPEECH_LEVEL_DEFAULTS = {'max_gain_db': 40.0}
+SPEECH_LEVEL_MODES = ('report', 'input')
+SPEECH_LEVEL_MIN_RATE, SPEECH_LEVEL_MAX_RATE = 8000, 192000
+SPEECH_LEVEL_MAX_CHANNELS = 8
+SPEECH_LEVEL_KERNEL_CHANNELS = 64
 # the true-peak option (csrc/truepeak.hip): taps per phase and Kaiser beta of the interpolator; the oversampled rate it reaches
 TRUEPEAK_TAPS_PER_PHASE = 24
 TRUEPEAK_BETA = 9.0
@@ -545,6 +552,41 @@ def check_loudness_scope(loudness_scope, loud, who="enhance_folder", folder=True
     if not _is_int(album_cache_bytes) or album_cache_bytes < 0:
         raise ValueError("%s: album_cache_bytes must be an int >= 0 (0: keep no generated clip on the device), got %r" % (who, album_cache_bytes))
     return {'cache_bytes': int(album_cache_bytes)}
+
+
+def check_speech_level_rate(rate, who):
+    """The rates p2phd_speechlevel_consts_fill takes: an int in [8000, 192000] Hz."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not SPEECH_LEVEL_MIN_RATE <= rate <= SPEECH_LEVEL_MAX_RATE or rate != int(rate):
+        raise ValueError("%s: the active speech level is measured at a whole rate in [%d, %d] Hz, got %r"
+                         % (who, SPEECH_LEVEL_MIN_RATE, SPEECH_LEVEL_MAX_RATE, rate))
+    return int(rate)
+
+
+def check_speech_level(value, who="enhance_file", max_gain_db=None, loudness=None):
+    """Validates the speech-level option -> None (off), or {'mode': 'report' | 'input' | 'target', 'target': the level in dBov (None
+    unless a number was given), 'max_gain_db'}.  `value`: None, 'report' (measure only), 'input' (the written clip at the active
+    speech level of the clip the generator was given) or a finite number in [-70, 0], the target in dBov.  `max_gain_db`: None
+    (SPEECH_LEVEL_DEFAULTS) or a level in [0, 120], an option of the option.  `loudness`: the loudness option, which claims the
+    same gain: both at once are refused (and with it loudness_range and loudness_scope='folder', options of that option)."""
+    if value is None:
+        if max_gain_db is not None:
+            raise ValueError("%s: speech_level_max_gain_db is an option of speech_level; speech_level is None" % who)
+        return None
+    if loudness is not None:
+        raise ValueError("%s: speech_level and loudness are two claims on the one gain in front of the output stage; give one of them" % who)
+    if max_gain_db is None:
+        max_gain_db = SPEECH_LEVEL_DEFAULTS['max_gain_db']
+    if isinstance(max_gain_db, bool) or not isinstance(max_gain_db, (int, float)) or not 0.0 <= max_gain_db <= 120.0:
+        raise ValueError("%s: speech_level_max_gain_db must be in [0, 120], got %r" % (who, max_gain_db))
+    if isinstance(value, str):
+        if value not in SPEECH_LEVEL_MODES:
+            raise ValueError("%s: speech_level must be None, 'report', 'input' or a target in dBov, got %r" % (who, value))
+        mode, target = value, None
+    else:
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not -70.0 <= value <= 0.0:
+            raise ValueError("%s: a speech_level target must be a finite level in [-70, 0] dBov, got %r" % (who, value))
+        mode, target = 'target', float(value)
+    return {'mode': mode, 'target': target, 'max_gain_db': float(max_gain_db)}
 
 
 def truepeak_plan(rate):

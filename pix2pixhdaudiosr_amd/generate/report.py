@@ -10,6 +10,7 @@ METRICS_COLUMNS_TRUE_PEAK = ("true_peak_dbtp",)                                 
 METRICS_COLUMNS_LIMITER = ("limiter_reduction_db", "limited_samples")                   # --limiter
 METRICS_COLUMNS_BANDWIDTH = ("bw_in", "bw_out", "bw_orig")                              # --bandwidth (behind every other column)
 METRICS_COLUMNS_STEREO = ("corr_lf_out", "corr_hf_out", "corr_hf_orig", "side_hf_out_db")   # --stereo_report (behind those too)
+METRICS_COLUMNS_SPEECH_LEVEL = ("asl_in", "asl_out", "activity_out")                    # --speech_level (behind every other column)
 
 
 def _mean(values):
@@ -21,7 +22,7 @@ def _nanmean(values):
     return sum(kept) / len(kept) if kept else float('nan')
 
 
-def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False, bandwidth=False, stereo=False):
+def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, loudness_range=False, bandwidth=False, stereo=False, speech_level=False):
     """The columns behind file, channel and frames: [(value for (record, channel), mean over the rows)]."""
     if extended:
         cols = [(lambda r, c, n=n: r['metrics_ext'][c][n], _nanmean) for n in METRICS_COLUMNS_EXT[3:]]
@@ -48,11 +49,13 @@ def _columns(extended, peaks, loudness=False, true_peak=False, limiter=False, lo
             return float('nan') if f is None else f
         cols += [(lambda r, c, k=k: figure(r, *k), _nanmean) for k in (('output', 'low', 'corr'), ('output', 'high', 'corr'), ('original', 'high', 'corr'),
                                                                     ('output', 'high', 'side_db'))]
+    if speech_level:
+        cols += [(lambda r, c, n=n: r['speech_level'][n], _mean) for n in ('input', 'output', 'activity')]
     return cols
 
 
 def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False, bandwidth=False,
-                 stereo=False):
+                 stereo=False, speech_level=False):
     """records of enhance_folder -> the rows of --metrics_csv: one per written channel that has metrics, then the `mean` row
     (the plain mean of each column over the rows above, what the reference's eval_matric.py averages); no mean row when
     nothing was measured.  `extended`: the records carry 'metrics_ext' and a row has the columns of METRICS_COLUMNS_EXT; the
@@ -74,8 +77,12 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
     channels' rows); plain means.  `stereo`: the records carry 'stereo' and a row ends, behind those too, with the columns of
     METRICS_COLUMNS_STEREO -- the generated clip's correlation below and above the split, the original's above it and the generated
     clip's side level above it in dB (the file's figures; nan where the file has no stereo image or no such figure); means over
-    the rows that have one."""
-    if stereo:
+    the rows that have one.  `speech_level`: the records carry 'speech_level' and a row ends, behind every other column, with the
+    columns of METRICS_COLUMNS_SPEECH_LEVEL -- the file's active speech level going in and as written, in dBov, and the written
+    clip's activity factor; plain means (a file without activity counts with -inf and 0)."""
+    if speech_level:
+        cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth, stereo, speech_level)
+    elif stereo:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth, stereo)
     elif bandwidth:
         cols = _columns(extended, peaks, loudness, true_peak, limiter, loudness_range, bandwidth)
@@ -99,14 +106,14 @@ def metrics_rows(records, extended=False, peaks=False, loudness=False, true_peak
 
 
 def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False, true_peak=False, limiter=False, loudness_range=False, album=False,
-                      bandwidth=False, stereo=False):
+                      bandwidth=False, stereo=False, speech_level=False):
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow((METRICS_COLUMNS_EXT if extended else METRICS_COLUMNS) + (METRICS_COLUMNS_PEAKS if peaks else ())
                    + (METRICS_COLUMNS_LOUDNESS if loudness else ()) + (METRICS_COLUMNS_LOUDNESS_RANGE if loudness_range else ())
                    + (METRICS_COLUMNS_TRUE_PEAK if true_peak else ())
                    + (METRICS_COLUMNS_LIMITER if limiter else ()) + (METRICS_COLUMNS_BANDWIDTH if bandwidth else ())
-                   + (METRICS_COLUMNS_STEREO if stereo else ()))
+                   + (METRICS_COLUMNS_STEREO if stereo else ()) + (METRICS_COLUMNS_SPEECH_LEVEL if speech_level else ()))
         extra = dict({'loudness': True} if loudness else {}, **({'true_peak': True} if true_peak else {}))
         if limiter:
             extra['limiter'] = True
@@ -118,6 +125,8 @@ def write_metrics_csv(path, records, extended=False, peaks=False, loudness=False
             extra['bandwidth'] = True
         if stereo:
             extra['stereo'] = True
+        if speech_level:
+            extra['speech_level'] = True
         for row in metrics_rows(records, extended, peaks, **extra):
             w.writerow([repr(v) if isinstance(v, float) else v for v in row])
 
@@ -145,6 +154,11 @@ def _print_peaks(name, o):
 
 def _print_loudness(name, l):
     print('%s: loudness input %+.2f LUFS, output %+.2f LUFS, gain %+.2f dB' % (name, l['input'], l['output'], l['gain_db']))
+
+
+def _print_speech_level(name, s):
+    print('%s: speech level input %+.2f dBov (activity %.1f %%), measured %+.2f dBov (activity %.1f %%), gain %+.2f dB -> %+.2f dBov'
+          % (name, s['input'], 100.0 * s['activity_input'], s['measured'], 100.0 * s['activity'], s['gain_db'], s['output']))
 
 
 def _print_album(a):

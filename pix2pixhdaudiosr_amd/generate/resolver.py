@@ -8,9 +8,9 @@ from collections import namedtuple
 import torch
 
 from .ops import (flac_decode, g711_decode, ima_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
+                  limiter_apply, limiter_envelope, speech_level as _speech_level, _speech_level_views, speech_level_packed_bytes, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
 from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_container, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
+                    check_container, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MAX_CHANNELS, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
 def _dbfs(level):
@@ -27,11 +27,11 @@ def _set(**keywords):
 # The validated options of enhance_file / enhance_folder (SuperResolver._options), each None where it is off: the output stage,
 # the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, the album (loudness_scope 'folder')
 # and the FLAC container.
-_Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album flac', defaults=(None,))
+_Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album flac sl', defaults=(None, None))
 
 # The keys a folder record may carry behind the eight it always has (and 'written'), in the record's order; each is also the key
 # of enhance_file's result that fills it ('album': enhance_album's own).
-_RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm', 'flac')
+_RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'speech_level', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm', 'flac')
 
 
 class _File:
@@ -450,7 +450,7 @@ class SuperResolver:
                               signed8=meta.signed8)
         return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
 
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,
+    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, speech_level=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,
                flac=None):
         """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload; -> the result's 'output', or None
         without a stage.  path_out None: the figures only.  `stage`: the output-stage options (check_output_options), or None for
@@ -458,7 +458,7 @@ class SuperResolver:
         that are set (_set):
           true_peak, limiter   the option's own dict, one file's (check_true_peak, _limiter_option; either comes with a stage):
                                _encode runs its kernels and leaves their packed figures in it, _output reads them
-          loudness, bandwidth, stereo   the measurement the per-file flow has already queued (_measure_*), a dict with 'packed'
+          loudness, speech_level, bandwidth, stereo   the measurement the per-file flow has already queued (_measure_*), a dict with 'packed'
           picture              the rendered spectrogram (_render_picture)
           rate                 the rate the header states where it is not the model's (the output-rate option: `sr` is converted)
           flac                 the container option's own dict, one file's (check_container): the payload goes through the FLAC
@@ -470,7 +470,7 @@ class SuperResolver:
         extra = {}
         if dev is not None and flac is not None:
             dev, extra = self._flac_stage(dev, w.shape[0], encoding, flac, **_set(rate=rate))
-        host, stats = self._fetch(dev, packed, **_set(stereo=stereo, bandwidth=bandwidth, limiter=limiter, true_peak=true_peak, loudness=loudness,
+        host, stats = self._fetch(dev, packed, **_set(stereo=stereo, bandwidth=bandwidth, limiter=limiter, true_peak=true_peak, loudness=loudness, speech_level=speech_level,
                                                       picture=picture), **extra)
         output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **option)
         if host is not None:
@@ -514,7 +514,7 @@ class SuperResolver:
     def _fetch(self, dev, packed, picture=None, **measured):
         """The payload and the packed peak buffer (either may be None) into their pinned buffers 'out' and 'peaks' behind one
         synchronisation -> (the payload, the peak buffer) on the host.  `measured`: name -> a dict whose 'packed' (a device tensor:
-        the figures of 'stereo', 'bandwidth', 'limiter', 'true_peak', 'loudness') is copied into the pinned buffer of that name in
+        the figures of 'stereo', 'bandwidth', 'limiter', 'true_peak', 'loudness', 'speech_level') is copied into the pinned buffer of that name in
         front of them, in the order given, and replaced by its host copy.  `picture`: None, or a dict whose 'image' and 'top' are
         copied and replaced likewise, into one buffer: the top's four bytes, then the pixels."""
         host = stats = None
@@ -658,6 +658,35 @@ class SuperResolver:
                                'blocks': int(r_out[4]), 'short_term_max': r_out[5]}
         return result
 
+    def _measure_speech_level(self, sl, lr, sr):
+        """The device work of the speech-level option: the clip the generator was given and the generated clip through the
+        envelope, the counts and the decision (six launches of the family "speechlevel") -> {'packed': both packed results in one
+        buffer, the input's first, 'gain': the f32 on the device that brings `sr` to the wanted active level (1 with 'report'),
+        'channels': the rows of either clip}.  With sl['out_rate'] (the output-rate option) `sr` is the converted clip: it is
+        measured at that rate, the input still at the model's."""
+        rate = int(self.opt.hr_sampling_rate)
+        rate_out = sl.get('out_rate', rate)
+        n_in, n_out = speech_level_packed_bytes(lr.shape[0]), speech_level_packed_bytes(sr.shape[0])
+        packed = torch.empty((n_in + n_out,), dtype=torch.uint8, device=sr.device)
+        res_in, _ = _speech_level(lr, rate, out=packed[:n_in])
+        wanted = {'report': {}, 'input': {'target_dev': res_in[lr.shape[0]]}, 'target': {'target': sl['target']}}[sl['mode']]
+        _, gain = _speech_level(sr, rate_out, max_gain_db=sl['max_gain_db'], out=packed[n_in:], **wanted)
+        return {'packed': packed, 'gain': gain, 'channels': (lr.shape[0], sr.shape[0])}
+
+    @staticmethod
+    def _speech_level_result(sl, measure):
+        """The fetched measurement -> the result's 'speech_level'."""
+        c_in, c_out = measure['channels']
+        n_in = speech_level_packed_bytes(c_in)
+        (res_in, _), (res_out, gain) = _speech_level_views(measure['packed'][:n_in], c_in), _speech_level_views(measure['packed'][n_in:], c_out)
+        res_in, res_out = res_in.tolist(), res_out.tolist()
+        level_in, measured = res_in[c_in][0], res_out[c_out][0]
+        gain_db = 0.0 if sl['mode'] == 'report' else 20.0 * math.log10(float(gain[0]))
+        return {'input': level_in, 'measured': measured, 'gain_db': gain_db, 'output': measured + gain_db,
+                'target': {'report': None, 'input': level_in, 'target': sl['target']}[sl['mode']],
+                'long_term': res_out[c_out][1] + gain_db, 'activity': res_out[c_out][2], 'activity_input': res_in[c_in][2],
+                'channels': [{'active': r[0] + gain_db, 'long_term': r[1] + gain_db, 'activity': r[2]} for r in res_out[:c_out]]}
+
     def _measure_bandwidth(self, bw, lr, sr, hr):
         """The device work of the bandwidth option: the clip the generator was given, the generated clip and, where there is one, the
         original through the spectrum and the decision kernel (two launches of the family "bandwidth" each; all channels of a clip
@@ -725,7 +754,8 @@ class SuperResolver:
     def _options(self, who, folder, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                  spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                  loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
+                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
+                 speech_level_max_gain_db=None):
         """The options of enhance_file (`folder` False) / enhance_folder (True), validated before a file is opened -> _Options.
         The order of the checks decides which ValueError a bad combination raises first: it does not move."""
         hr_rate = self.opt.hr_sampling_rate
@@ -739,7 +769,12 @@ class SuperResolver:
         loud = self._loudness_at(check_loudness(loudness, hr_rate, who, loudness_max_gain_db, loudness_range), rc, who)
         album = check_loudness_scope(loudness_scope, loud, who, folder, limiter, spectrogram, album_cache_bytes)
         fl = check_container(container, flac_block, flac_md5, encoding, out_rate, who, **_set(flac_lpc=flac_lpc))
-        return _Options(stage, tp, lim, spec, loud, bw, st, rc, album, fl)
+        sl = check_speech_level(speech_level, who, speech_level_max_gain_db, loudness)
+        if sl is not None:
+            check_speech_level_rate(hr_rate, who)
+            if rc is not None:
+                sl = dict(sl, out_rate=check_speech_level_rate(rc['rate'], who))
+        return _Options(stage, tp, lim, spec, loud, bw, st, rc, album, fl, sl)
 
     # -- one file: the stages of the flow, in the order their launches take on the stream ------------------------------
     def _front(self, read, is_lr_input, channels, encoding, o, who):
@@ -755,6 +790,8 @@ class SuperResolver:
             raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % k)
         if o.loud is not None and k > LOUDNESS_MAX_CHANNELS:
             raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
+        if o.sl is not None and k > SPEECH_LEVEL_MAX_CHANNELS:
+            raise ValueError("the active speech level is measured over at most %d channels, %d would be written" % (SPEECH_LEVEL_MAX_CHANNELS, k))
         rate = meta.sample_rate
         raw = self._decode(host, meta, slot)[:k]
         lr = audio_dataset.lr_round_trip(raw, rate, self.opt.lr_sampling_rate, self.opt.hr_sampling_rate, is_lr_input)
@@ -784,27 +821,32 @@ class SuperResolver:
             f.metrics = [U.compute_matrics(f.hr[c:c + 1], f.lr[c:c + 1], f.clip[c:c + 1], self.opt) for c in range(f.hr.shape[0])]
 
     def _level(self, f, o):
-        """(d) The output rate, then the loudness measurement and its gain on f.clip -> the measurement, or None.  The converter
+        """(d) The output rate, then the loudness or the speech-level measurement (the options exclude each other: one gain) and its
+        gain on f.clip -> (the loudness measurement, the speech-level measurement), None where off.  The converter
         (one launch of the family "rateconv") sits behind everything that compares the generated clip with the input and the
         original at the model's rate; the loudness stage behind the metrics, which moment-match and stay those of the unscaled
         clip.  Both sit in front of everything that sees the written level."""
         if o.rc is not None:
             f.clip = rate_convert(f.clip, o.rc['model_rate'], o.rc['rate'], o.rc['plan'])
-        if o.loud is None:
-            return None
-        measure = self._measure_loudness(o.loud, f.lr, f.clip)
-        if o.loud['mode'] != 'report':
-            f.clip = f.clip * measure['gain']
-        return measure
+        measure = speech = None
+        if o.sl is not None:
+            speech = self._measure_speech_level(o.sl, f.lr, f.clip)
+            if o.sl['mode'] != 'report':
+                f.clip = f.clip * speech['gain']
+        elif o.loud is not None:
+            measure = self._measure_loudness(o.loud, f.lr, f.clip)
+            if o.loud['mode'] != 'report':
+                f.clip = f.clip * measure['gain']
+        return measure, speech
 
-    def _deliver(self, f, path_out, encoding, extended_metrics, o, band, image, measure, picture):
+    def _deliver(self, f, path_out, encoding, extended_metrics, o, band, image, measure, speech, picture):
         """(f) _write -- the output stage, the encoder, the one synchronisation and the file -- where there is anything to encode
         or to bring back, then enhance_file's result."""
         output = None
         flac = o.flac and dict(o.flac)
-        if path_out is not None or o.stage is not None or any(m is not None for m in (picture, measure, band, image)):
+        if path_out is not None or o.stage is not None or any(m is not None for m in (picture, measure, speech, band, image)):
             output = self._write(path_out, f.clip, encoding, o.stage, **_set(
-                picture=picture, loudness=measure, stereo=image, bandwidth=band,
+                picture=picture, loudness=measure, speech_level=speech, stereo=image, bandwidth=band,
                 true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
                 rate=o.rc and o.rc['rate'], flac=flac))
         res = {'sr': f.clip, 'lr': f.lr, 'hr': f.hr, 'metrics': f.metrics, 'info': f.meta}
@@ -814,6 +856,8 @@ class SuperResolver:
             res['spectrogram'] = self._save_picture(o.spec, picture)
         if measure is not None:
             res['loudness'] = self._loudness_result(o.loud, measure)
+        if speech is not None:
+            res['speech_level'] = self._speech_level_result(o.sl, speech)
         if band is not None:
             res['bandwidth'] = self._bandwidth_result(o.bw, band)
         if f.crossover is not None:
@@ -836,9 +880,9 @@ class SuperResolver:
         f = self._front(read, is_lr_input, channels, encoding, o, "enhance_file")
         band, image = self._reports(f, o)
         self._metrics(f, extended_metrics)
-        measure = self._level(f, o)
+        measure, speech = self._level(f, o)
         picture = None if o.spec is None else self._render_picture(o.spec, f.lr, f.clip, f.hr)       # (e)
-        return self._deliver(f, path_out, encoding, extended_metrics, o, band, image, measure, picture)
+        return self._deliver(f, path_out, encoding, extended_metrics, o, band, image, measure, speech, picture)
 
     # -- a folder: what both loudness scopes share ---------------------------------------------------------------
     def _blank_record(self, rel, path_out, written_from, extended_metrics, o):
@@ -848,7 +892,7 @@ class SuperResolver:
         rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0, 'metrics': None, 'error': None}
         if written_from is not None:
             rec['written'] = os.path.relpath(path_out, written_from)
-        present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None,
+        present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None, speech_level=o.sl is not None,
                        album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto, stereo=o.st is not None,
                        output_rate=o.rc is not None, norm=self.norm_scope == 'clip', flac=o.flac is not None)
         rec.update((key, None) for key in _RECORD_KEYS if present[key])
@@ -870,6 +914,9 @@ class SuperResolver:
             self._check_stereo_channels(channels, read[1].num_channels)
             if o.flac is not None and select_channels(channels, read[1].num_channels) > 8:
                 raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % select_channels(channels, read[1].num_channels))
+            if o.sl is not None and select_channels(channels, read[1].num_channels) > SPEECH_LEVEL_MAX_CHANNELS:
+                raise ValueError("the active speech level is measured over at most %d channels, %d would be written"
+                                 % (SPEECH_LEVEL_MAX_CHANNELS, select_channels(channels, read[1].num_channels)))
             return read
         except (ValueError, OSError, EOFError, struct.error) as e:
             rec['error'] = '%s: %s' % (type(e).__name__, e)
@@ -880,7 +927,8 @@ class SuperResolver:
                      spectrogram_channel=0, spectrogram_opts=None, loudness=None, loudness_max_gain_db=None, true_peak=False,
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
-                     dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
+                     dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
+                     speech_level_max_gain_db=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -1009,11 +1057,27 @@ class SuperResolver:
         the file never longer than without it; flac_block at most 16384 with M > 0); 'flac' then gains 'lpc': M.  The result gains 'flac': {'block', 'frames', 'bytes'
         (the file's), 'pcm_bytes' (the payload's), 'md5' (hex, or None)}; None where no file is written.  encoding 'float32', more
         than 8 written channels, a block outside the range, a written rate above 1048575 Hz, or either option without 'flac': a
-        ValueError before the output is opened."""
+        ValueError before the output is opened.
+        `speech_level` (opt-in): the active speech level after ITU-T P.56 method B (csrc/speechlevel.hip; include/p2phd.h, "Active
+        speech level": the level while somebody is speaking, in dBov, with a 200 ms hangover, and the activity factor) of the clip the
+        generator was given ('lr', at the model's rate) and of the generated clip (behind the output-rate converter, at the rate
+        written), and what is done with it: 'report' measures only; 'input' brings the written clip to the input's active level; a
+        number in [-70, 0] brings it to that level in dBov (-26 is the convention of speech corpora and listening tests).  Every
+        channel is measured on its own; the file's figure is that of the channel with the highest active level and ONE gain, at most
+        `speech_level_max_gain_db` either way (None: 40 dB; 0 .. 120), multiplies all channels where the loudness gain would -- in
+        front of the true-peak measurement, the limiter, the guard, the dither and the encoder; 'sr' is the scaled clip.  Six
+        launches of the family "speechlevel" per file; the figures come back with the payload behind the same synchronisation.
+        The result gains 'speech_level': {'input' (the input's active level), 'measured' (the generated clip's in front of the
+        gain), 'gain_db', 'output' ('measured' + 'gain_db'), 'target' (None with 'report'), 'long_term' and 'activity' (the
+        generated clip's, the level with the gain), 'activity_input', 'channels': [{'active', 'long_term', 'activity'}, ..] (the
+        generated clip's rows, with the gain)}.  A clip without activity has the level -inf and the gain 1.  Not together with
+        `loudness` (two claims on one gain), not over more than 8 written channels, and only at rates in 8000 .. 192000: a
+        ValueError each, the first and the last before a file is opened."""
         o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc))
+                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
+                                 speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
         read = self._read(path_in, **_set(verify=True if verify_input else None))
         res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
@@ -1040,7 +1104,8 @@ class SuperResolver:
                        true_peak=False, limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False,
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
                        stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
-                       verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None):
+                       verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
+                       speech_level_max_gain_db=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -1092,11 +1157,15 @@ class SuperResolver:
         is a skipped file.  Both hold in either loudness scope.
         `container`, `flac_block`, `flac_md5`: enhance_file's; with 'flac' every output is named .flac (plan_folder's `ext`: x.wav is
         written as x.flac, and x.wav beside x.flac in one folder is the same ValueError), a record gains 'written' and 'flac', and
-        the album flow writes through the same encoder and the same writer."""
+        the album flow writes through the same encoder and the same writer.
+        `speech_level`, `speech_level_max_gain_db`: enhance_file's, per file; a record then gains 'speech_level' (as enhance_file
+        returns it; None for a skipped file).  A file of which more than 8 channels would be written is skipped, its record carrying
+        the 'error'."""
         o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc))
+                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
+                                                    speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
         plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
         written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
         if o.album is not None:

@@ -873,6 +873,87 @@ def _rateconv_kernels(torch, x, rate, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_speechlevel(seconds, reps, log, off_only=False):
+    """enhance_file on a mono clip, file to file: without any option, with speech_level='report' and with speech_level=-26 (the same
+    object), interleaved; then the three entries of csrc/speechlevel.hip alone, by events, at the clip's length and at an hour's."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    rate = int(opt.hr_sampling_rate)
+    lines = ["# tools/time_generate.py speechlevel: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz, file to file, untrained weights, %d interleaved repeats" % (seconds, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav"))
+        wavio.save(src, x.cpu(), rate)
+        sr = SuperResolver(model, opt, overlap=0.25)
+        runs = [("no option            ", {})] if off_only else [("speech_level off     ", {}), ("speech_level report  ", dict(speech_level='report')),
+                                                                  ("speech_level -26     ", dict(speech_level=-26.0))]
+        last = None
+        for _, kw in runs:                                          # warm-up: capture, pinned buffers, page cache
+            sr.enhance_file(src, out, **kw)
+            last = sr.enhance_file(src, out, **kw)
+        torch.cuda.synchronize()
+        ts = [[] for _ in runs]
+        for _ in range(reps):
+            for k, (_, kw) in enumerate(runs):
+                t0 = time.perf_counter()
+                sr.enhance_file(src, out, **kw)
+                torch.cuda.synchronize()
+                ts[k].append((time.perf_counter() - t0) * 1e3)
+        for (name, _), tk in zip(runs, ts):
+            lines.append("%s  median %8.3f ms per file   spread %6.3f (%.3f .. %.3f)   runs: %s"
+                         % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), " ".join("%.3f" % v for v in tk)))
+        if not off_only:
+            base = _median(ts[0])
+            s = last['speech_level']
+            for k in (1, 2):
+                lines.append("%s costs %+.3f ms per file (difference of the medians), %+.2f %% of the file without it: six launches more"
+                             % (runs[k][0].strip(), _median(ts[k]) - base, 100.0 * (_median(ts[k]) - base) / base))
+            lines.append("the clip: input %+.2f dBov (activity %.1f %%), measured %+.2f dBov (activity %.1f %%), gain %+.2f dB"
+                         % (s['input'], 100.0 * s['activity_input'], s['measured'], 100.0 * s['activity'], s['gain_db']))
+    text = "\n".join(lines) + "\n"
+    if not off_only:
+        text += _speechlevel_kernels(torch, x, rate, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _speechlevel_kernels(torch, x, rate, reps):
+    """The three entries alone, by events (with the allocation of their results in front), on the clip and on an hour of it."""
+    from pix2pixhdaudiosr_amd.generate import speech_level_counts, speech_level_decide, speech_level_envelope
+    lines = []
+    hour = x.repeat(1, -(-3600 * rate // x.shape[-1]))[:, :3600 * rate].contiguous()
+    for name, clip in (("the clip", x), ("an hour", hour)):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        k_e, k_c, k_d = [], [], []
+        for _ in range(reps + 2):
+            ev[0].record()
+            m, sq = speech_level_envelope(clip, rate)
+            ev[1].record()
+            a = speech_level_counts(m, rate)
+            ev[2].record()
+            speech_level_decide(sq, a, clip.shape[-1], target=-26.0)
+            ev[3].record()
+            torch.cuda.synchronize()
+            k_e.append(ev[0].elapsed_time(ev[1]) * 1e3)
+            k_c.append(ev[1].elapsed_time(ev[2]) * 1e3)
+            k_d.append(ev[2].elapsed_time(ev[3]) * 1e3)
+        n = clip.shape[-1]
+        e, c, d = (_median(k[2:]) for k in (k_e, k_c, k_d))
+        lines.append("kernels alone on %s (events, median of %d; %d samples): p2phd_speechlevel_envelope (three kernels) %.1f us (spread %.1f) = %.3f ns "
+                     "per sample, %.1f GB/s of input read twice and m written once; p2phd_speechlevel_counts %.1f us (spread %.1f) = %.3f ns per sample; "
+                     "p2phd_speechlevel_decide %.1f us (spread %.1f)"
+                     % (name, reps, n, e, max(k_e[2:]) - min(k_e[2:]), e * 1e3 / n, 9.0 * n / e * 1e-3, c, max(k_c[2:]) - min(k_c[2:]), c * 1e3 / n,
+                        d, max(k_d[2:]) - min(k_d[2:])))
+        lines.append("runs: envelope %s; counts %s; decide %s" % tuple(" ".join("%.1f" % v for v in k[2:]) for k in (k_e, k_c, k_d)))
+        del m, sq, a
+    return "\n".join(lines) + "\n"
+
+
 def run_dither(seconds, reps, log, off_only=False):
     """enhance_file on a mono clip, file to file: without any option, with dither='tpdf' and with dither='shaped' (the same object),
     interleaved; then p2phd_pcm_encode_shaped alone, by events, at chunk 4096, at chunk 1024 and at one chunk for the whole row (the
@@ -1801,7 +1882,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec", "containers"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1816,6 +1897,7 @@ def main():
     ap.add_argument("--bandwidth_log", default=os.path.join(ROOT, "profiles", "time_generate_bandwidth.log"))
     ap.add_argument("--stereo_log", default=os.path.join(ROOT, "profiles", "time_generate_stereo.log"))
     ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
+    ap.add_argument("--speechlevel_log", default=os.path.join(ROOT, "profiles", "time_generate_speechlevel.log"))
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
@@ -1824,9 +1906,9 @@ def main():
     ap.add_argument("--flacout_log", default=os.path.join(ROOT, "profiles", "time_generate_flacout.log"))
     ap.add_argument("--flac_lpc", type=int, default=None, metavar="N", help="flacout mode: time the LPC option at order N against the writer without it (log in --flaclpc_log)")
     ap.add_argument("--flaclpc_log", default=os.path.join(ROOT, "profiles", "time_generate_flaclpc.log"))
-    ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv and stereo mode: time only the run without any option (no log unless the mode's log is given)")
+    ap.add_argument("--off_only", action="store_true", help="bandwidth, dither, normscope, rateconv, speechlevel and stereo mode: time only the run without any option (no log unless the mode's log is given)")
     ap.add_argument("--seconds", type=float, default=15.0)
-    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv and stereo mode: 9)")
+    ap.add_argument("--reps", type=int, default=None, help="repeats (default 5; album, bandwidth, dither, normscope, rateconv, speechlevel and stereo mode: 9)")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "time_generate.log"))
     a = ap.parse_args()
     if a.mode == "flacout" and a.flac_lpc is not None:
@@ -1847,6 +1929,9 @@ def main():
     if a.mode == "rateconv":
         log = a.rateconv_log if not a.off_only or "--rateconv_log" in sys.argv else None
         return run_rateconv(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "speechlevel":
+        log = a.speechlevel_log if not a.off_only or "--speechlevel_log" in sys.argv else None
+        return run_speechlevel(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "dither":
         log = a.dither_log if not a.off_only or "--dither_log" in sys.argv else None
         return run_dither(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
