@@ -103,7 +103,8 @@ int p2phd_probe_read(float* ms_out, int cap);
  * csrc/flac.hip: a p2phd_flac_decode with nframes > 0 counts 2), "flacenc" (the three kernels of its FLAC output, csrc/flacenc.hip:
  * a p2phd_flac_encode counts 3), "wavcodec" (the G.711 and IMA ADPCM decoders of its coded WAV input, csrc/wavcodec.hip: one per
  * call with frames > 0), "speechlevel" (the envelope, the counts and the decision of its active speech level, csrc/speechlevel.hip:
- * one per entry with frames > 0), and the weight packs of p2phd_conv_pack_weights /
+ * one per entry with frames > 0), "normrows" (the per-row statistics, encode and decodes of its segment_norm, csrc/spectro.hip: one
+ * per call that launches anything), and the weight packs of p2phd_conv_pack_weights /
  * p2phd_conv_fp8_pack_weights, one family per kernel of csrc/wpack.hip, counted per launch plan: "wpack_generic" (the tap walk),
  * "wpack_dense", "wpack_transposed" (the two LDS re-orderings), "wpack_kmajor" (cast of K-major master weights), "wpack_kmajor_t"
  * (their per-tap transpose), "wpack_merged" (merged sub-pixel launches, either tap order), "wpack_fp8" (the e4m3 quantiser with
@@ -1179,6 +1180,7 @@ int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C,
  *   spectro_encode, spectro_encode_ex                     elements channels * B * M * F of the normalisation pass; 8192
  *   spectro_stats  (inside spectro_encode(_ex))           elements of the noise rows; 1024
  *   spectro_range, range_fold / .._scalar                 floats, on the 16-byte path / the path of any alignment; 1024
+ *   spectro_rows  (inside spectro_encode_rows)            floats F * M of one row, a float4 per thread: workgroups per row; 32
  * rows is looked at by pcm_peak only, dtype (P2PHD_F32, P2PHD_BF16) where a thread's piece depends on it.  work = 0: all three 0.
  * An unknown family is P2PHD_EINVAL. */
 int p2phd_stream_grid(const char* family, int dtype, int64_t work, int rows, int64_t* unit_work, int* wanted, int* used);
@@ -1329,6 +1331,31 @@ int p2phd_range_fold(const float* x, int64_t n, float* minmax_io, float* partial
 int p2phd_spectro_encode_given(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha, float min_value,
                                int mask_rows, int mask_mode, const float* noise, const float* noise_sign, const float* norm8,
                                float* log_spectro, float* pha, void* stream);
+
+/* One normalisation range per row (whole-file generation, segment_norm): the rows of a batch no longer know of one another.
+ * p2phd_spectro_encode_rows: p2phd_spectro_encode_ex applied to every row b of spec [B,F,M] on its own, in one call.  The
+ *   statistics of row b go into norm_rows [B,8] (device, out) at 8 b + {0, 1, 4, 5}: the minimum and maximum of the row's dB values
+ *   (p2phd_spectro_range's expressions, over all M bins and both channels) and of the row's [channels, mask_rows, F] noise
+ *   ((+inf, -inf) without noise or with mask_rows == 0); the other four entries are 0.  NaN entries are passed over.  The row is
+ *   then encoded as p2phd_spectro_encode_given encodes it under those eight floats: row b's log_spectro and pha are the bits
+ *   p2phd_spectro_encode_ex writes for that row alone, except that a range of zero scales by 0 (spectrum and noise alike), so a
+ *   row of digital silence encodes as zeros.  workspace: exactly p2phd_spectro_rows_partials_floats(B,F,M) floats (0 for a bad
+ *   geometry), all written before they are read: no state is kept between calls.  The 16-byte read path is taken per row, by
+ *   the alignment of that row's own base.  Three launches (statistics over a (chunk, row) grid, a fold per row, the encode).
+ * p2phd_spectro_decode_signed_rows, p2phd_spectro_decode_spliced_rows: p2phd_spectro_decode_signed and
+ *   p2phd_spectro_decode_spliced with the (min, max) of row b read at norm_rows[8 b], norm_rows[8 b + 1]; one launch each, the
+ *   same kernels.
+ * None launches for B == 0; B < 65536; nothing allocated, no synchronisation, no atomics: capturable.  Launch family
+ * "normrows", one per call that launches. */
+int64_t p2phd_spectro_rows_partials_floats(int64_t B, int64_t F, int64_t M);
+int p2phd_spectro_encode_rows(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha, float min_value,
+                              int mask_rows, int mask_mode, const float* noise, const float* noise_sign, float* norm_rows,
+                              float* log_spectro, float* pha, float* workspace, void* stream);
+int p2phd_spectro_decode_signed_rows(const float* log_spectro, const float* pha, const float* norm_rows, int64_t B, int64_t F,
+                                     int64_t M, int channels, int keep_rows, float min_value, float scale, float* spec, void* stream);
+int p2phd_spectro_decode_spliced_rows(const float* sr_log_spectro, const float* lr_log_spectro, const float* pha,
+                                      const float* norm_rows, int64_t B, int64_t F, int64_t M, int channels, int keep_rows,
+                                      int fade_rows, float min_value, float scale, float* spec, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics (csrc/metrics.hip): compute_matrics (util/util.py:133-184).

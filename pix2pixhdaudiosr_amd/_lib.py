@@ -188,6 +188,10 @@ SIGNATURES = {
     "p2phd_spectro_range": (_i32, [_vp, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
     "p2phd_range_fold": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "p2phd_spectro_encode_given": (_i32, [_vp, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "p2phd_spectro_rows_partials_floats": (_i64, [_i64, _i64, _i64]),
+    "p2phd_spectro_encode_rows": (_i32, [_vp, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "p2phd_spectro_decode_signed_rows": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _f32, _f32, _vp, _vp]),
+    "p2phd_spectro_decode_spliced_rows": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp]),
     "p2phd_stft_tables_floats": (_sz, [_i32]),
     "p2phd_stft_tables_fill": (_i32, [_i32, _vp]),
     "p2phd_metrics_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32, _i32]),

@@ -76,7 +76,7 @@ int launch_pack_fp8(const GDesc& d, const WMap& m, const float* w, void* wp8, in
 enum LaunchFamily { LC_GCONV = 0, LC_HALO, LC_CLS_SKIP, LC_MARCH, LC_MARCH_W, LC_WGRAD, LC_SPLITK, LC_TILE256, LC_TILE128X192,
                     LC_DFIRST, LC_DLAST, LC_C7, LC_THIN_WGRAD, LC_TIMED_PACK, LC_TIMED_FRAMES, LC_STITCH, LC_PCM, LC_METRICS_ROWS,
                     LC_XOVER, LC_SPECIMG, LC_LOUDNESS, LC_TRUEPEAK, LC_LIMITER, LC_BANDWIDTH, LC_STEREO, LC_RATECONV, LC_NORMSCOPE,
-                    LC_SHAPER, LC_FLAC, LC_FLACENC, LC_WAVCODEC, LC_SPEECHLEVEL,
+                    LC_SHAPER, LC_FLAC, LC_FLACENC, LC_WAVCODEC, LC_SPEECHLEVEL, LC_NORMROWS,
                     // which weight pack p2phd_conv_pack_weights / p2phd_conv_fp8_pack_weights started (wpack.hip, one family per kernel;
                     // LC_WPACK_FRAG: the fragment pack of a dedicated kernel, counted in convapi.hip)
                     LC_WPACK_GENERIC, LC_WPACK_DENSE, LC_WPACK_TRANSPOSED, LC_WPACK_KMAJOR, LC_WPACK_KMAJOR_T, LC_WPACK_MERGED, LC_WPACK_FP8,

@@ -166,7 +166,7 @@ extern "C" int64_t p2phd_launch_count(const char* family, int reset) {
   static const char* names[p2phd::LC_FAMILIES] = {"gconv", "halo", "cls_skip", "march", "march_w", "wgrad", "splitk", "tile256", "tile128x192",
                                                        "dfirst", "dlast", "c7", "thin_wgrad", "timed_pack", "timed_frames", "stitch", "pcm",
                                                        "metrics_rows", "xover", "specimg", "loudness", "truepeak", "limiter", "bandwidth", "stereo", "rateconv",
-                                                       "normscope", "shaper", "flac", "flacenc", "wavcodec", "speechlevel", "wpack_generic", "wpack_dense", "wpack_transposed",
+                                                       "normscope", "shaper", "flac", "flacenc", "wavcodec", "speechlevel", "normrows", "wpack_generic", "wpack_dense", "wpack_transposed",
                                                        "wpack_kmajor", "wpack_kmajor_t", "wpack_merged", "wpack_fp8", "wpack_frag"};
   if (family == nullptr) {                                       // all families at once
     if (reset) for (auto& c : p2phd::g_launch_count) c = 0;

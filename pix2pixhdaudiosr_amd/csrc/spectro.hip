@@ -157,10 +157,11 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ x
 // sign(ch0 - ch1) above (explicit encoding); single channel: sign = pha everywhere (the caller draws the random signs).
 __global__ __launch_bounds__(256) void decode_signed_kernel(const float* __restrict__ x, const float* __restrict__ pha,
                                                             const float* __restrict__ norm2, float* __restrict__ spec, int F, int M,
-                                                            int channels, int keep, float min_value, float scale) {
+                                                            int channels, int keep, float min_value, float scale, int norm_stride) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, m0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
   const int tx = threadIdx.x, ty = threadIdx.y;
+  norm2 += (size_t)b * norm_stride;                               // 0: one range for all rows; 8: row b's own (norm_rows)
   const float mn = norm2[0], range = norm2[1] - norm2[0];
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + ty + 8 * i, f = f0 + tx;
@@ -215,10 +216,11 @@ __device__ __forceinline__ float splice_blend(float s, float l, float w) {
 __global__ __launch_bounds__(256) void decode_spliced_kernel(const float* __restrict__ sr, const float* __restrict__ lr,
                                                              const float* __restrict__ pha, const float* __restrict__ norm2,
                                                              float* __restrict__ spec, int F, int M, int channels, int keep,
-                                                             int fade, float min_value, float scale) {
+                                                             int fade, float min_value, float scale, int norm_stride) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, m0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
   const int tx = threadIdx.x, ty = threadIdx.y;
+  norm2 += (size_t)b * norm_stride;                               // as in decode_signed_kernel
   const float mn = norm2[0], range = norm2[1] - norm2[0];
   const size_t plane = (size_t)M * F;
   const int lo = keep - fade;                                     // first fade row
@@ -324,7 +326,8 @@ int launch_range(const float* x, long n, float alpha, float min_value, float* mi
 __global__ __launch_bounds__(256) void encode_given_kernel(const float* __restrict__ spec, const float* __restrict__ norm8,
                                                            const float* __restrict__ noise, const float* __restrict__ noise_sign,
                                                            float* __restrict__ out, float* __restrict__ pha, int F, int M,
-                                                           float alpha, float min_value, int channels, int mask_rows, int mask_mode) {
+                                                           float alpha, float min_value, int channels, int mask_rows, int mask_mode,
+                                                           int norm_stride) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, m0 = blockIdx.x * 32, f0 = blockIdx.y * 32;
   const int tx = threadIdx.x, ty = threadIdx.y;
@@ -332,6 +335,7 @@ __global__ __launch_bounds__(256) void encode_given_kernel(const float* __restri
     const int f = f0 + ty + 8 * i, m = m0 + tx;
     tile[ty + 8 * i][tx] = (f < F && m < M) ? spec[((size_t)b * F + f) * M + m] : 0.f;
   }
+  norm8 += (size_t)b * norm_stride;                               // 0: one norm8 for all rows; 8: row b's own (norm_rows)
   const float mn = norm8[0], range = norm8[1] - norm8[0];
   const float scale = range == 0.f ? 0.f : 1.f / range;
   float nmn = 0.f, nscale = 0.f;
@@ -375,6 +379,66 @@ __global__ __launch_bounds__(256) void encode_given_kernel(const float* __restri
     }
   }
 }
+
+// ---- one normalisation range per row (whole-file generation, segment_norm) ---------------------------------------------------
+// rows_stats_kernel leaves (min, max, noise min, noise max) of a chunk of every row, rows_fold_kernel folds a row's chunks into
+// its norm8 (plain stores, no atomics: min and max do not depend on the order), and encode_given_kernel / the decodes read row
+// b's statistics at norm_rows + 8 b.
+
+// fold_minmax over x[0, n), this workgroup's share of `chunks`: float4 reads where this base is 16-byte aligned, else one by one
+template <int CH>
+__device__ __forceinline__ void fold_stream(const float* __restrict__ x, long n, int chunk, int chunks, float alpha, float min_value,
+                                            float& mn, float& mx) {
+  const long n4 = ((uintptr_t)x & 15) == 0 ? n / 4 : 0;
+  const long stride = (long)chunks * 256;
+  const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x);
+  for (long e = (long)chunk * 256 + threadIdx.x; e < n4; e += stride) {
+    const float4 v = x4[e];
+    fold_minmax<CH>(v.x, alpha, min_value, mn, mx); fold_minmax<CH>(v.y, alpha, min_value, mn, mx);
+    fold_minmax<CH>(v.z, alpha, min_value, mn, mx); fold_minmax<CH>(v.w, alpha, min_value, mn, mx);
+  }
+  for (long e = 4 * n4 + (long)chunk * 256 + threadIdx.x; e < n; e += stride) fold_minmax<CH>(x[e], alpha, min_value, mn, mx);
+}
+
+// grid (chunks, B): partials[4 (b chunks + chunk)] = (min, max) of the dB values of the chunk's share of row b's n = F M spectrum
+// values, then those of its share of row b's nn noise values ((+inf, -inf) without noise).  The alignment is that of each row's
+// own base: with n or nn no multiple of 4 the rows behind the first start off a 16-byte boundary.
+template <int CH>
+__global__ __launch_bounds__(256) void rows_stats_kernel(const float* __restrict__ spec, long n, const float* __restrict__ noise,
+                                                         long nn, float alpha, float min_value, float* __restrict__ partials) {
+  const int b = blockIdx.y;
+  float mn = INFINITY, mx = -INFINITY, nmn = INFINITY, nmx = -INFINITY;
+  fold_stream<CH>(spec + (size_t)b * n, n, blockIdx.x, gridDim.x, alpha, min_value, mn, mx);
+  if (noise != nullptr) fold_stream<0>(noise + (size_t)b * nn, nn, blockIdx.x, gridDim.x, 0.f, 0.f, nmn, nmx);
+  block_minmax(mn, mx);
+  __syncthreads();                                                // block_minmax's LDS words are read by thread 0 until here
+  block_minmax(nmn, nmx);
+  if (threadIdx.x == 0) {
+    float* p = partials + 4 * ((size_t)b * gridDim.x + blockIdx.x);
+    p[0] = mn; p[1] = mx; p[2] = nmn; p[3] = nmx;
+  }
+}
+
+// grid B, one wave: norm_rows[8 b] = (min, max, 0, 0, noise min, noise max, 0, 0) of row b's `chunks` partials
+__global__ __launch_bounds__(64) void rows_fold_kernel(const float* __restrict__ partials, int chunks, float* __restrict__ norm_rows) {
+  const int b = blockIdx.x;
+  float mn = INFINITY, mx = -INFINITY, nmn = INFINITY, nmx = -INFINITY;
+  for (int i = threadIdx.x; i < chunks; i += 64) {
+    const float* p = partials + 4 * ((size_t)b * chunks + i);
+    mn = fminf(mn, p[0]); mx = fmaxf(mx, p[1]); nmn = fminf(nmn, p[2]); nmx = fmaxf(nmx, p[3]);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, o)); mx = fmaxf(mx, __shfl_xor(mx, o));
+    nmn = fminf(nmn, __shfl_xor(nmn, o)); nmx = fmaxf(nmx, __shfl_xor(nmx, o));
+  }
+  if (threadIdx.x == 0) {
+    float* q = norm_rows + 8 * (size_t)b;
+    q[0] = mn; q[1] = mx; q[2] = 0.f; q[3] = 0.f; q[4] = nmn; q[5] = nmx; q[6] = 0.f; q[7] = 0.f;
+  }
+}
+
+// workgroups per row of rows_stats_kernel
+inline int rows_chunks(int64_t F, int64_t M) { return p2phd::stream_grid_of(p2phd::SG_SPECTRO_ROWS, P2PHD_F32, F * M, 1).used; }
 
 }  // namespace
 
@@ -443,7 +507,7 @@ extern "C" int p2phd_spectro_decode_signed(const float* log_spectro, const float
   P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode_signed: grid too large");
   dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
   hipLaunchKernelGGL(decode_signed_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, log_spectro, pha, norm_min_max, spec, (int)F,
-                     (int)M, channels, keep_rows, min_value, scale);
+                     (int)M, channels, keep_rows, min_value, scale, 0);
   return p2phd::check_launch("spectro_decode_signed");
 }
 
@@ -461,7 +525,7 @@ extern "C" int p2phd_spectro_decode_spliced(const float* sr_log_spectro, const f
   P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode_spliced: grid too large");
   dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
   hipLaunchKernelGGL(decode_spliced_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, sr_log_spectro, lr_log_spectro, pha,
-                     norm_min_max, spec, (int)F, (int)M, channels, keep_rows, fade_rows, min_value, scale);
+                     norm_min_max, spec, (int)F, (int)M, channels, keep_rows, fade_rows, min_value, scale, 0);
   return p2phd::check_launch("spectro_decode_spliced");
 }
 
@@ -502,7 +566,76 @@ extern "C" int p2phd_spectro_encode_given(const float* spec, int64_t B, int64_t 
   P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_encode_given: grid too large");
   dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
   hipLaunchKernelGGL(encode_given_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, spec, norm8, mask_rows > 0 ? noise : nullptr,
-                     noise_sign, log_spectro, pha, (int)F, (int)M, alpha, min_value, channels, mask_rows, mask_mode);
+                     noise_sign, log_spectro, pha, (int)F, (int)M, alpha, min_value, channels, mask_rows, mask_mode, 0);
   ++p2phd::g_launch_count[p2phd::LC_NORMSCOPE];
   return p2phd::check_launch("spectro_encode_given");
+}
+
+extern "C" int64_t p2phd_spectro_rows_partials_floats(int64_t B, int64_t F, int64_t M) {
+  if (B < 0 || F < 1 || M < 1) return 0;
+  return 4 * B * rows_chunks(F, M);
+}
+
+extern "C" int p2phd_spectro_encode_rows(const float* spec, int64_t B, int64_t F, int64_t M, int channels, float alpha,
+                                         float min_value, int mask_rows, int mask_mode, const float* noise,
+                                         const float* noise_sign, float* norm_rows, float* log_spectro, float* pha,
+                                         float* workspace, void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_encode_rows: bad geometry");
+  P2PHD_REQUIRE(mask_rows >= 0 && mask_rows <= M, "spectro_encode_rows: mask_rows %d outside [0, %lld]", mask_rows, (long long)M);
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_encode_rows: channels must be 2 (explicit encoding) or 1, got %d", channels);
+  P2PHD_REQUIRE(mask_mode >= 0 && mask_mode <= 2, "spectro_encode_rows: mask_mode must be 0, 1 or 2, got %d", mask_mode);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(spec && norm_rows && log_spectro && pha && workspace, "spectro_encode_rows: null pointer");
+  P2PHD_REQUIRE(!(mask_mode == 1 && noise != nullptr && mask_rows > 0 && noise_sign == nullptr),
+                "spectro_encode_rows: mask mode1 needs the sign tensor");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_encode_rows: grid too large");
+  hipStream_t st = (hipStream_t)stream;
+  if (mask_rows == 0) noise = nullptr;
+  const int chunks = rows_chunks(F, M);
+  const long n = (long)(F * M), nn = (long)channels * mask_rows * F;
+  if (channels == 2)
+    hipLaunchKernelGGL(rows_stats_kernel<2>, dim3(chunks, (unsigned)B), dim3(256), 0, st, spec, n, noise, nn, alpha, min_value, workspace);
+  else
+    hipLaunchKernelGGL(rows_stats_kernel<1>, dim3(chunks, (unsigned)B), dim3(256), 0, st, spec, n, noise, nn, alpha, min_value, workspace);
+  hipLaunchKernelGGL(rows_fold_kernel, dim3((unsigned)B), dim3(64), 0, st, workspace, chunks, norm_rows);
+  dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(encode_given_kernel, grid, dim3(32, 8), 0, st, spec, norm_rows, noise, noise_sign, log_spectro, pha, (int)F, (int)M,
+                     alpha, min_value, channels, mask_rows, mask_mode, 8);
+  ++p2phd::g_launch_count[p2phd::LC_NORMROWS];
+  return p2phd::check_launch("spectro_encode_rows");
+}
+
+extern "C" int p2phd_spectro_decode_signed_rows(const float* log_spectro, const float* pha, const float* norm_rows, int64_t B,
+                                                int64_t F, int64_t M, int channels, int keep_rows, float min_value, float scale,
+                                                float* spec, void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_decode_signed_rows: bad geometry");
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_decode_signed_rows: channels must be 1 or 2, got %d", channels);
+  P2PHD_REQUIRE(keep_rows >= 0 && keep_rows <= M, "spectro_decode_signed_rows: keep_rows %d outside [0, %lld]", keep_rows, (long long)M);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(log_spectro && pha && norm_rows && spec, "spectro_decode_signed_rows: null pointer");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode_signed_rows: grid too large");
+  dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(decode_signed_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, log_spectro, pha, norm_rows, spec, (int)F,
+                     (int)M, channels, keep_rows, min_value, scale, 8);
+  ++p2phd::g_launch_count[p2phd::LC_NORMROWS];
+  return p2phd::check_launch("spectro_decode_signed_rows");
+}
+
+extern "C" int p2phd_spectro_decode_spliced_rows(const float* sr_log_spectro, const float* lr_log_spectro, const float* pha,
+                                                 const float* norm_rows, int64_t B, int64_t F, int64_t M, int channels,
+                                                 int keep_rows, int fade_rows, float min_value, float scale, float* spec,
+                                                 void* stream) {
+  P2PHD_REQUIRE(B >= 0 && F >= 1 && M >= 1, "spectro_decode_spliced_rows: bad geometry");
+  P2PHD_REQUIRE(channels == 1 || channels == 2, "spectro_decode_spliced_rows: channels must be 1 or 2, got %d", channels);
+  P2PHD_REQUIRE(keep_rows >= 0 && keep_rows <= M, "spectro_decode_spliced_rows: keep_rows %d outside [0, %lld]", keep_rows, (long long)M);
+  P2PHD_REQUIRE(fade_rows >= 0 && fade_rows <= keep_rows, "spectro_decode_spliced_rows: fade_rows %d outside [0, keep_rows = %d]",
+                fade_rows, keep_rows);
+  if (B == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(sr_log_spectro && lr_log_spectro && pha && norm_rows && spec, "spectro_decode_spliced_rows: null pointer");
+  P2PHD_REQUIRE(B < 65536 && (F + 31) / 32 < 65536, "spectro_decode_spliced_rows: grid too large");
+  dim3 grid((unsigned)((M + 31) / 32), (unsigned)((F + 31) / 32), (unsigned)B);
+  hipLaunchKernelGGL(decode_spliced_kernel, grid, dim3(32, 8), 0, (hipStream_t)stream, sr_log_spectro, lr_log_spectro, pha,
+                     norm_rows, spec, (int)F, (int)M, channels, keep_rows, fade_rows, min_value, scale, 8);
+  ++p2phd::g_launch_count[p2phd::LC_NORMROWS];
+  return p2phd::check_launch("spectro_decode_spliced_rows");
 }

@@ -34,6 +34,7 @@ enum StreamFamily {
   SG_SPECTRO_STATS,     // spectro_encode(_ex), statistics of the noise rows: elements, one per thread
   SG_RANGE_VEC,         // spectro_range, range_fold, 16-byte aligned input: floats, a float4 per thread (+ a scalar tail)
   SG_RANGE_SCALAR,      // the same, any alignment: a float per thread
+  SG_SPECTRO_ROWS,      // spectro_encode_rows, statistics: workgroups per row over its F * M floats, a float4 per thread; grid.y = rows
   SG_UNKNOWN
 };
 
@@ -48,7 +49,8 @@ inline StreamFamily stream_family(const char* name) {
       {"adam_step_dev", SG_ADAM}, {"adam_step_scaled", SG_ADAM}, {"grads_nonfinite", SG_NONFINITE},
       {"timed_pack_pair", SG_PACK_PAIR}, {"spectro_encode", SG_SPECTRO_ENCODE}, {"spectro_encode_ex", SG_SPECTRO_ENCODE},
       {"spectro_stats", SG_SPECTRO_STATS}, {"spectro_range", SG_RANGE_VEC}, {"range_fold", SG_RANGE_VEC},
-      {"spectro_range_scalar", SG_RANGE_SCALAR}, {"range_fold_scalar", SG_RANGE_SCALAR}};
+      {"spectro_range_scalar", SG_RANGE_SCALAR}, {"range_fold_scalar", SG_RANGE_SCALAR},
+      {"spectro_rows", SG_SPECTRO_ROWS}};
   for (const auto& t : table)
     if (!strcmp(name, t.name)) return t.f;
   return SG_UNKNOWN;
@@ -95,6 +97,7 @@ inline StreamGrid stream_grid_of(StreamFamily f, int dtype, int64_t work, int ro
     case SG_SPECTRO_STATS:  return stream_capped(work, 1024, 1);
     case SG_RANGE_VEC:      return stream_capped(work / 4 + work % 4, 1024, 4);
     case SG_RANGE_SCALAR:   return stream_capped(work, 1024, 1);
+    case SG_SPECTRO_ROWS:   return stream_capped(cdiv(work, 4), 32, 4);
     default:                return StreamGrid{};
   }
 }

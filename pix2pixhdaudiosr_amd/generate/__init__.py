@@ -27,6 +27,14 @@ file then no longer depends on `--batchSize` beyond what the generator itself do
 silence one group long -- a lead-in, a gap, the side signal of a dual-mono file -- is written as silence where the group's own
 range, max == min, writes NaN.  A channel is still a clip of its own, and a last, smaller group still runs at its own size.
 
+`--segment_norm` (opt-in, `SuperResolver(segment_norm=True)`; csrc/spectro.hip, launch family "normrows") is the third way: one
+range per segment, what 'group' means at batch 1, at any batch.  The encode takes every row's own statistics on the device
+(`model.inference(..., norm='rows')`, `p2phd_spectro_encode_rows`) and `util.imdct` decodes every row under its own
+(`p2phd_spectro_decode_signed_rows`, `_spliced_rows`), so the rows of a group no longer know of one another: the C * S rows of a
+clip are walked in groups of `batch` without regard to channel (`group_rows_plan`), the last group is filled up with rows of
+zeros -- a zero row has a range of zero, encodes as zeros, and its output is dropped -- and every group, of every clip, replays
+the one captured graph.  No pre-pass, no held noise; a silent segment is written as silence.  Not with `norm_scope='clip'`.
+
 The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
 decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
 
@@ -117,7 +125,7 @@ from .ops import (PCM_FORMATS, G711_LAWS, g711_decode, ima_decode, flac_decode, 
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, shaper_coefficients, segments_gather, segments_gather_planar, segments_stitch,
                   segments_stitch_planar, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks,
                   speech_level, speech_level_consts, speech_level_counts, speech_level_decide, speech_level_envelope)
-from .plans import (INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
+from .plans import (INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, check_segment_norm, group_rows_plan, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,

@@ -12,7 +12,7 @@ import torch
 
 from .ops import shaper_coefficients
 from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MODES, check_lowband,
-                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_stereo_report, output_rate_line, spectro_bins)
+                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_segment_norm, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_speech_level, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
@@ -316,6 +316,11 @@ def _parser():
                          "segments, the reference's chain: the output depends on the batch size, and a group of digital silence is "
                          "written as NaN; clip -- one range per channel of a file, found on the device in a pass in front of its first "
                          "group: the same file at every batch size, silence stays silence; one start-up line more (default: group)")
+    ap.add_argument("--segment_norm", action="store_true",
+                    help="normalise every segment by its own range, what --norm_scope group means at --batchSize 1, at any batch size: "
+                         "the same file at every batch size, a silent segment stays silent, no pass in front of the first group; all "
+                         "channels of a file share groups and the last group is filled up with silent segments, so every group "
+                         "replays the one captured graph; one start-up line more; not with --norm_scope clip (default: off)")
     ap.add_argument("--stereo_report", action="store_true",
                     help="report how the left and right channel of a file written with two channels correlate below and above the low "
                          "rate's Nyquist frequency -- for the input the generator was given, the generated clip and, for a full-band "
@@ -371,6 +376,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:                                                                    # before anything is loaded
         folder_mode = check_paths(a.input, a.output)
+        check_segment_norm(a.segment_norm, a.norm_scope, "generate")
         out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate", a.dither_curve,
                                          a.dither_chunk)
         if a.output_rate is not None:                                       # (the model's rate: once the options file has been read)
@@ -437,7 +443,8 @@ def main(argv=None):
                        reference_amplitude=None if a.reference_amplitude is None else bool(a.reference_amplitude),
                        lowband=a.lowband, lowband_fade=a.lowband_fade, crossover=a.crossover, crossover_hz=a.crossover_hz,
                        crossover_taps=a.crossover_taps, **({} if a.stereo == 'lr' else {'stereo': a.stereo}),
-                       **({} if a.norm_scope == 'group' else {'norm_scope': a.norm_scope}))
+                       **({} if a.norm_scope == 'group' else {'norm_scope': a.norm_scope}),
+                       **({'segment_norm': True} if a.segment_norm else {}))
     print('amplitude: %s; low band: %s' % ("the reference's (half of sqrt(up_ratio - 1) * x)" if sr.reference_amplitude else 'full',
                                            "the model's" if sr.lowband == 'model' else
                                            "the input's (fade over %d rows)" % sr.lowband_fade))
@@ -449,6 +456,8 @@ def main(argv=None):
         print('stereo: mid / side')
     if sr.norm_scope == 'clip':                                             # (without the option: no line more than before)
         print('normalisation: one range per clip')
+    if sr.segment_norm:                                                     # (without the option: no line more than before)
+        print('normalisation: one range per segment')
     if rc is not None:                                                      # (without the option: no line more than before)
         print(output_rate_line(rc))
     if a.dither == 'shaped':                                                # (without the option: no line more than before)

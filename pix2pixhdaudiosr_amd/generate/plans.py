@@ -367,6 +367,32 @@ def check_norm_scope(norm_scope='group', who="SuperResolver"):
     return norm_scope
 
 
+def check_segment_norm(segment_norm=False, norm_scope='group', who="SuperResolver"):
+    """Validates the per-segment normalisation option -> the bool.  It is an option of its own beside `norm_scope`: with it every
+    segment has its own range, so there is no scope to choose, and together with norm_scope 'clip' it is a ValueError."""
+    if not isinstance(segment_norm, bool):
+        raise ValueError("%s: segment_norm must be a bool, got %r" % (who, segment_norm))
+    check_norm_scope(norm_scope, who)
+    if segment_norm and norm_scope != 'group':
+        raise ValueError("%s: segment_norm gives every segment its own range and norm_scope %r one per clip: choose one of the two"
+                         % (who, norm_scope))
+    return segment_norm
+
+
+def group_rows_plan(rows, batch):
+    """How segment_norm walks the `rows` = C * S channel-major rows of a clip in groups of `batch`, without regard to channel ->
+    a list of (r0, n): group g holds the rows r0 .. r0 + n - 1 and batch - n filler rows of zeros behind them.  Every row is in
+    exactly one group, n == batch in every group but the last, 1 <= n <= batch there; no rows, no groups."""
+    for name, v in (('rows', rows), ('batch', batch)):
+        if not _is_int(v):
+            raise ValueError("group_rows_plan: %s must be an int, got %r" % (name, v))
+    if rows < 0:
+        raise ValueError("group_rows_plan: rows must be >= 0, got %d" % rows)
+    if batch < 1:
+        raise ValueError("group_rows_plan: batch must be >= 1, got %d" % batch)
+    return [(r0, min(batch, rows - r0)) for r0 in range(0, rows, batch)]
+
+
 def check_stereo_report(stereo_report=False, opts=None, loudness_scope='file', who="enhance_file"):
     """Validates the stereo report option -> None (off), or the plan {'n_fft', 'hop'} that ops.stereo_image takes.  `stereo_report`:
     a bool.  `opts`: None or a dict of those two, None or absent standing for STEREO_DEFAULTS' value (hop: half of a given n_fft):

@@ -9,7 +9,7 @@ import torch
 
 from .ops import (flac_decode, g711_decode, ima_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
                   limiter_apply, limiter_envelope, speech_level as _speech_level, _speech_level_views, speech_level_packed_bytes, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_segment_norm, group_rows_plan, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_container, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MAX_CHANNELS, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -38,7 +38,7 @@ class _File:
     """One file between the stages of the per-file flow: `clip` the generated clip as the latest stage left it, `lr` the clip the
     generator was given, `hr` the original where the input is one (else None), `meta` the input's WavInfo / FlacInfo, `metrics` and
     `ext` (None until the metrics stage, and without an original), `norm` and `crossover`: the object's last_norm and a copy of
-    its last_crossover behind this file's enhance_lr (None without norm_scope 'clip' / crossover_hz 'auto')."""
+    its last_crossover behind this file's enhance_lr (None without norm_scope 'clip' or segment_norm / crossover_hz 'auto')."""
     __slots__ = ('clip', 'lr', 'hr', 'meta', 'metrics', 'ext', 'norm', 'crossover')
 
     def __init__(self, clip, lr, hr, meta, norm, crossover):
@@ -123,13 +123,24 @@ class SuperResolver:
     (model.inference(..., norm=)); the captured chain reads it from a static buffer filled in front of every replay, so one
     capture serves every clip.  A range of zero scales by 0: a clip of digital silence is written as silence.  The launches are
     those of the family "normscope": ceil(S / batch) range calls and one noise fold per clip, one encode per group.
-    `last_norm` then holds the [C, 2] tensor on the GPU of the latest call's (min, max) per clip, in dB."""
+    `last_norm` then holds the [C, 2] tensor on the GPU of the latest call's (min, max) per clip, in dB.
+    `segment_norm`: False (the default) | True, fixed for the object's life; not with norm_scope 'clip'.  Every segment is
+    normalised by its own range -- what 'group' means at batch 1, at any batch --: the encode takes each row's statistics on the
+    device (model.inference(..., norm='rows')) and util.imdct decodes each row under its own, the launches of the family
+    "normrows", two per group.  The rows of a group then no longer know of one another, so the C * S rows of a clip are walked in
+    groups of `batch` without regard to channel (plans.group_rows_plan) and the last group is filled up with rows of zeros, whose
+    range of zero encodes as zeros and whose output is dropped: every group has `batch` rows, the graphed run and the eager run
+    are the same launches, and one capture serves every clip, channel count and length.  The file does not depend on the batch
+    beyond what the generator itself does with it; a silent segment is written as silence.  No pre-pass, no held noise.
+    `last_norm` then holds the [C, S, 2] tensor on the GPU of the latest call's (min, max) per segment, in dB."""
 
     # what an object built without __init__ (the stubs of the host tests) runs with: every option of the constructor off
     stereo, norm_scope, crossover_auto, last_norm, last_crossover = 'lr', 'group', False, None, None
+    segment_norm = False
 
     def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
-                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr', norm_scope='group'):
+                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr', norm_scope='group',
+                 segment_norm=False):
         from ..models.mdct import IMDCT2, IMDCT4
         from ..util import util as U
         self.model, self.opt = model, opt
@@ -137,7 +148,9 @@ class SuperResolver:
         self.overlap = float(overlap)
         segment_plan(0, self.T, self.overlap)                               # validates both
         self.norm_scope = check_norm_scope(norm_scope)
-        self.last_norm = None                                               # 'clip': [C, 2] on the GPU, the latest call's ranges
+        self.segment_norm = check_segment_norm(segment_norm, self.norm_scope)
+        self.last_norm = None                             # 'clip': [C, 2] on the GPU, the latest call's ranges; segment_norm: [C, S, 2]
+        self._rows = None                                                   # segment_norm: the [batch, 8] table of the latest eager group
         self.batch = int(batch if batch is not None else getattr(opt, 'batchSize', 1))
         if self.batch < 1:
             raise ValueError("SuperResolver: batch must be >= 1, got %d" % self.batch)
@@ -199,12 +212,15 @@ class SuperResolver:
 
     def _group(self, seg, noise, norm=None):
         """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44).
-        `norm`: None (norm_scope 'group': the model is called as ever), or the clip's norm8."""
+        `norm`: None (norm_scope 'group': the model is called as ever), the clip's norm8, or 'rows' (segment_norm: every row
+        its own range; the group's [b, 8] table is left in self._rows)."""
         from ..util import util as U
         if norm is None:
             sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
         else:
             sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise, norm=norm)
+        if isinstance(norm, str):
+            self._rows = norm_param['rows']
         splice = {} if self.lowband == 'model' else dict(lr_spectro=lr_spectro, lowband_fade=self.lowband_fade)
         audio = U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=self._imdct,
                         up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)), **splice)
@@ -218,17 +234,19 @@ class SuperResolver:
         """The chain of a full group through a graph over static buffers.  The first use runs the chain once eagerly on the
         buffers (packed weights, tables and workspaces exist before capture), then captures it; every use replays.  Weights
         that changed since (load_network, an optimiser step) make the capture stale: it is redone.  `norm` (norm_scope 'clip'):
-        the clip's norm8, copied into a static buffer the captured encode and decode read."""
+        the clip's norm8, copied into a static buffer the captured encode and decode read; 'rows' (segment_norm) is handed on as
+        it is, and the table the captured encode writes is kept as g['rows']."""
         from .. import _ops
         g = self._g
+        by_rows = isinstance(norm, str)
         if g is None or g['epoch'] != _ops._WEIGHT_EPOCH[0]:
             shape = self.noise_shape(self.batch)
             g = self._g = {'epoch': _ops._WEIGHT_EPOCH[0], 'graph': None, 'out': None,
                            'seg': torch.empty((self.batch, self.T), dtype=torch.float32, device=self.device),
                            'noise': None if shape is None else torch.empty(shape, dtype=torch.float32, device=self.device),
-                           'norm': None if norm is None else torch.empty((8,), dtype=torch.float32, device=self.device)}
+                           'norm': norm if norm is None or by_rows else torch.empty((8,), dtype=torch.float32, device=self.device)}
         g['seg'].copy_(seg)
-        if g['norm'] is not None:
+        if g['norm'] is not None and not by_rows:
             g['norm'].copy_(norm)
         if g['noise'] is not None:
             g['noise'].copy_(noise)
@@ -246,8 +264,45 @@ class SuperResolver:
                 graph.capture_end()
             torch.cuda.current_stream().wait_stream(side)
             g['graph'] = graph
+            if by_rows:
+                g['rows'] = self._rows
         g['graph'].replay()
         return g['out']
+
+    def _group_rows(self, seg, noise):
+        """segment_norm: one full group, [batch, T] -> (the generated [batch, T], the group's [batch, 8] table of ranges on the
+        device), through the graph where the chain may be captured."""
+        if self.graph and self._graph_ok():
+            return self._run_graphed(seg, noise, 'rows'), self._g['rows']
+        return self._group(seg, noise, 'rows'), self._rows
+
+    def _walk_rows(self, seg, out, noise, C, S):
+        """segment_norm: the C * S channel-major rows of `seg` through _group_rows in groups of `batch`, without regard to channel
+        (plans.group_rows_plan); the last group is filled up with rows of zeros (and zeros for their rows of a given `noise`), whose
+        output is dropped.  Leaves `out` filled and `last_norm` [C, S, 2]; nothing is waited for."""
+        R = seg.shape[0]
+        ranges = torch.empty((R, 2), dtype=torch.float32, device=seg.device)
+        shape = self.noise_shape(self.batch)
+        for r0, n in group_rows_plan(R, self.batch):
+            rows = seg[r0:r0 + n]
+            fill = self.batch - n
+            if fill:
+                rows = torch.cat((rows, rows.new_zeros((fill, rows.shape[1]))))
+            nz = None
+            if shape is not None:
+                if noise is None:
+                    nz = torch.randn(shape, device=self.device)
+                else:
+                    nz = noise[r0:r0 + n]
+                    if tuple(nz.shape) != (n,) + tuple(shape[1:]):
+                        raise ValueError("enhance_lr: noise for rows %d..%d has shape %s, expected %s"
+                                         % (r0, r0 + n - 1, tuple(nz.shape), (n,) + tuple(shape[1:])))
+                    if fill:
+                        nz = torch.cat((nz, nz.new_zeros((fill,) + tuple(shape[1:]))))
+            audio, table = self._group_rows(rows, nz)
+            out[r0:r0 + n].copy_(audio[:n])
+            ranges[r0:r0 + n].copy_(table[:n, :2])
+        self.last_norm = ranges.view(C, S, 2)
 
     # -- one clip ----------------------------------------------------------------------------------
     def enhance_lr(self, lr_audio, noise=None):
@@ -259,7 +314,9 @@ class SuperResolver:
         segments go through model.clip_norm, the channel's rows of `noise` are folded as they are, and without `noise` the mask
         noise of the channel is drawn in one torch.randn of [S, channels, mask_rows, frames] -- the range of the noise must be
         known before the first group is encoded --, which holds S / batch times the memory of a group's draw for the length of the
-        channel: 4 * channels * mask_rows * frames bytes per segment, the (1 - 1 / up_ratio) part of a segment's encoded spectrogram."""
+        channel: 4 * channels * mask_rows * frames bytes per segment, the (1 - 1 / up_ratio) part of a segment's encoded spectrogram.
+        With segment_norm the property holds too, at every batch size, although the C * S rows share groups (_walk_rows): a row's
+        encode and decode see that row alone, and what the generator itself does with its batch is all that is left."""
         run = getattr(self.model, '_on_step_stream', None)
         with torch.no_grad():
             return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
@@ -294,7 +351,9 @@ class SuperResolver:
             if S == 0:                                                      # (no segment, no range: the empty fold)
                 self.last_norm[:, 0] = float('inf')
                 self.last_norm[:, 1] = float('-inf')
-        for c in range(C):
+        if self.segment_norm:
+            self._walk_rows(seg, out, noise, C, S)
+        for c in range(0 if self.segment_norm else C):                      # (segment_norm: the rows have been walked, above)
             norm = drawn = None
             if by_clip and S > 0:
                 # the channel's range, in front of its first group; the noise every group of it will be given is folded with it
@@ -799,7 +858,7 @@ class SuperResolver:
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         clip = self.enhance_lr(lr)
-        # norm_scope 'clip': this file's ranges, on the device; crossover_hz 'auto': the crossover this file got
+        # norm_scope 'clip', segment_norm: this file's ranges, on the device; crossover_hz 'auto': the crossover this file got
         return _File(clip, lr, raw if has_hr else None, meta, self.last_norm, dict(self.last_crossover) if self.crossover_auto else None)
 
     def _reports(self, f, o):
@@ -850,7 +909,7 @@ class SuperResolver:
                 true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
                 rate=o.rc and o.rc['rate'], flac=flac))
         res = {'sr': f.clip, 'lr': f.lr, 'hr': f.hr, 'metrics': f.metrics, 'info': f.meta}
-        if self.norm_scope == 'clip':                                       # (without the option: no key more than before)
+        if self.norm_scope == 'clip' or self.segment_norm:                  # (without the option: no key more than before)
             res['norm'] = f.norm
         if picture is not None:
             res['spectrogram'] = self._save_picture(o.spec, picture)
@@ -894,7 +953,7 @@ class SuperResolver:
             rec['written'] = os.path.relpath(path_out, written_from)
         present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None, speech_level=o.sl is not None,
                        album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto, stereo=o.st is not None,
-                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip', flac=o.flac is not None)
+                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip' or self.segment_norm, flac=o.flac is not None)
         rec.update((key, None) for key in _RECORD_KEYS if present[key])
         return rec
 

@@ -201,7 +201,12 @@ class Pix2PixHDModel(BaseModel):
         ``norm`` (default None: the batch's own statistics, as above): a float32 tensor of 8 on the GPU, (min, max, -, -,
         noise_min, noise_max, -, -) as `clip_norm` leaves it.  The encode then normalises by that range instead of the batch
         tensor's (p2phd_spectro_encode_given; a range of zero scales by 0) and the norm dict's 'min', 'max' and '_minmax' are views
-        of it -- 'mean' and 'std' too, which this path does not compute."""
+        of it -- 'mean' and 'std' too, which this path does not compute.
+        ``norm='rows'``: every row of the batch is normalised by its own range (p2phd_spectro_encode_rows: row b is what the
+        default path gives for audio[b:b + 1], a range of zero scales by 0).  The norm dict then carries 'rows', the [B, 8] table on
+        the GPU ((min, max, 0, 0, noise_min, noise_max, 0, 0) per row), 'min' and 'max', its columns 0 and 1 of shape [B], 'mean'
+        and 'std', columns 2 and 3 (zeros, not computed), and 'frames'; `util.imdct` decodes under it, the training-side
+        `denormalize`, `to_audio` and `to_frames` refuse it."""
         if _spec is not None:
             spec, frames = _spec, _frames
         elif getattr(self, 'use_time_D', False):
@@ -217,9 +222,13 @@ class Pix2PixHDModel(BaseModel):
             phase_noise = (torch.rand if pem == 'uni_dist' else torch.randn)((B, 1, M, Fr), device=spec.device)
         log_spectro = torch.empty((B, C, M, Fr), dtype=torch.float32, device=spec.device)
         pha = torch.empty((B, 1, M, Fr), dtype=torch.float32, device=spec.device)
+        by_rows = isinstance(norm, str) and norm == 'rows'
         if norm is None:
             norm8 = torch.zeros(8, dtype=torch.float32, device=spec.device)
             partials = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+        elif by_rows:
+            norm8 = torch.empty((B, 8), dtype=torch.float32, device=spec.device)
+            partials = torch.empty(L.p2phd_spectro_rows_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
         else:
             norm8 = self._check_norm8(norm, "to_spectro")
         mask_rows = 0
@@ -247,6 +256,12 @@ class Pix2PixHDModel(BaseModel):
                                                  mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
                                                  _lib.ptr(noise_sign), _lib.ptr(log_spectro), _lib.ptr(pha), _lib.ptr(norm8),
                                                  _lib.ptr(partials), _lib.stream_ptr()), "spectro_encode")
+        elif by_rows:
+            spec = spec.contiguous()
+            _lib.check(L.p2phd_spectro_encode_rows(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
+                                                   mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
+                                                   _lib.ptr(noise_sign), _lib.ptr(norm8), _lib.ptr(log_spectro), _lib.ptr(pha),
+                                                   _lib.ptr(partials), _lib.stream_ptr()), "spectro_encode_rows")
         else:
             _lib.check(L.p2phd_spectro_encode_given(_lib.ptr(spec), B, Fr, M, C, float(self.opt.alpha), float(self.opt.min_value),
                                                     mask_rows, {'mode0': 0, 'mode1': 1}.get(mode, 2), _lib.ptr(noise),
@@ -262,8 +277,17 @@ class Pix2PixHDModel(BaseModel):
                 elif pem == 'norm_dist2':
                     pn = pn.abs()
                 pha = pha * pn
+        if by_rows:
+            return log_spectro, pha, {'rows': norm8, 'min': norm8[:, 0], 'max': norm8[:, 1], 'mean': norm8[:, 2], 'std': norm8[:, 3],
+                                      'frames': frames}
         norm = {'min': norm8[0], 'max': norm8[1], 'mean': norm8[2], 'std': norm8[3], 'frames': frames, '_minmax': norm8[:2]}
         return log_spectro, pha, norm
+
+    @staticmethod
+    def _refuse_rows(norm_param, who):
+        if isinstance(norm_param, dict) and norm_param.get('rows') is not None:
+            raise ValueError("%s: a norm dict with one range per row (to_spectro(..., norm='rows')) is decoded by util.imdct; "
+                             "this entry serves training, which has one range per batch" % who)
 
     def _check_norm8(self, norm, who):
         if not isinstance(norm, torch.Tensor) or not norm.is_cuda or norm.dtype != torch.float32 or tuple(norm.shape) != (8,) \
@@ -333,11 +357,13 @@ class Pix2PixHDModel(BaseModel):
         return mm.contiguous()
 
     def denormalize(self, log_spectro, norm_param):
+        self._refuse_rows(norm_param, "denormalize")
         mm = self._minmax(norm_param)
         s = torch.abs(log_spectro) * (mm[1] - mm[0]) + mm[0]
         return 10.0 * torch.pow(10.0, s * 0.05) - self.opt.min_value        # DB_to_amplitude(s, 10, 0.5) - min_value
 
     def to_audio(self, log_spectro, norm_param, pha=None, pseudo_pha=None):
+        self._refuse_rows(norm_param, "to_audio")
         x = log_spectro.to(self.device).float().contiguous()
         B, _, M, Fr = x.shape
         spec = torch.empty((B, Fr, M), dtype=torch.float32, device=x.device)
@@ -365,6 +391,7 @@ class Pix2PixHDModel(BaseModel):
     def to_frames(self, log_spectro, norm_param):
         """Un-windowed time-domain frames of an MDCT2 spectrogram (pix2pixHD_model.py:251-258): differentiable, the
         IDCT runs on the HIP kernel; the small dB decode in front of it is plain tensor arithmetic."""
+        self._refuse_rows(norm_param, "to_frames")
         if not _opt(self.opt, 'explicit_encoding', False):
             return None                                                     # pix2pixHD_model.py:255-256
         if self.mdct_type != 'mdct2':
@@ -563,7 +590,8 @@ class Pix2PixHDModel(BaseModel):
         return [losses, None if not infer else sr_result]
 
     def inference(self, lr_audio, inst, noise=None, norm=None):
-        """`norm` (default None: the batch's own statistics): clip_norm's norm8, the range the batch is normalised by."""
+        """`norm` (default None: the batch's own statistics): clip_norm's norm8, the range the batch is normalised by, or 'rows':
+        every row by its own range (to_spectro)."""
         if norm is None:
             lr_spectro, lr_pha, _, _, _, _, _, lr_norm_param = self.encode_input(lr_audio, inst, None, noise=noise)
         else:

@@ -81,7 +81,10 @@ def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit
     decoded values with the input's weight cos^2(pi (j + 1/2) / (2 lowband_fade)).  This rests on one fact: the mask noise of
     `to_spectro` fills the top int(M * (1 - 1 / up_ratio)) rows, and M - int(M * (1 - 1 / up_ratio)) >= int(M / up_ratio)
     = keep, so every noise row is a row >= keep and the spliced rows of `lr_spectro` never hold noise.  With up_ratio <= 1
-    keep = M: every row is the input's, and the result is the input's own transform round trip."""
+    keep = M: every row is the input's, and the result is the input's own transform round trip.
+
+    A `norm_param` with 'rows' (the [B, 8] table of `to_spectro(..., norm='rows')`, one range per row) goes through the same two
+    kernels with row b's (min, max) read at rows[b, 0:2] (p2phd_spectro_decode_signed_rows, p2phd_spectro_decode_spliced_rows)."""
     from .. import _lib
     dev = spectro.device
     _lib.require_gpu_tensor(spectro, "spectro")
@@ -113,6 +116,22 @@ def imdct(spectro, pha, norm_param, _imdct, min_value=1e-7, up_ratio=1, explicit
         pseudo = (2 * torch.randint(low=0, high=2, size=(B, M, Fr), device=dev) - 1).float()
         p = torch.cat((p[:, :keep], pseudo[:, keep:]), dim=1)
     p = p.contiguous()
+    rows = norm_param.get('rows') if isinstance(norm_param, dict) else None
+    if rows is not None:                                                    # one range per row: to_spectro(..., norm='rows')
+        if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.float32 or tuple(rows.shape) != (B, 8):
+            raise ValueError(f"imdct: norm_param['rows'] must be a float32 tensor [{B}, 8] on the GPU, got "
+                             f"{tuple(rows.shape) if isinstance(rows, torch.Tensor) else rows!r}")
+        rows = rows.contiguous()
+        spec = torch.empty((B, Fr, M), dtype=torch.float32, device=dev)
+        if lr is not None:
+            _lib.check(_lib.lib().p2phd_spectro_decode_spliced_rows(_lib.ptr(x), _lib.ptr(lr), _lib.ptr(p), _lib.ptr(rows), B, Fr, M, Cc,
+                                                                    keep, fade, float(min_value), 1.0, _lib.ptr(spec), _lib.stream_ptr()),
+                       "spectro_decode_spliced_rows")
+        else:
+            _lib.check(_lib.lib().p2phd_spectro_decode_signed_rows(_lib.ptr(x), _lib.ptr(p), _lib.ptr(rows), B, Fr, M, Cc, keep,
+                                                                   float(min_value), 1.0, _lib.ptr(spec), _lib.stream_ptr()),
+                       "spectro_decode_signed_rows")
+        return _imdct(spec) / 2
     mm = torch.stack([torch.as_tensor(norm_param['min']).float().reshape(()),
                       torch.as_tensor(norm_param['max']).float().reshape(())]).to(dev).contiguous()
     spec = torch.empty((B, Fr, M), dtype=torch.float32, device=dev)

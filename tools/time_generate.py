@@ -91,6 +91,14 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             tensors; with --off_only only the run without the option is timed (one process of an alternating comparison with another
             checkout); log in --normscope_log
 
+  segnorm   (only when asked for) file to file, SuperResolver as ever (norm_scope 'group'), SuperResolver(norm_scope='clip') and
+            SuperResolver(segment_norm=True), in one process, the runs interleaved (nine repeats unless --reps says otherwise):
+            enhance_file on a mono clip of that length, then enhance_folder on eight two-channel clips of 2 s, where the eager last
+            groups of the first two would dominate, and of 1.5 s, where they do: milliseconds, median and spread; then p2phd_spectro_encode_rows beside
+            p2phd_spectro_encode_ex and p2phd_spectro_encode_given, and p2phd_spectro_decode_signed_rows beside
+            p2phd_spectro_decode_signed, alone, by events, on one group's spectrum and noise (the option-off path against another
+            checkout: normscope --off_only in either); log in --segnorm_log
+
   dither    (only when asked for) enhance_file on a mono clip of that length, file to file: without any option, with dither='tpdf' and
             with dither='shaped' (lipshitz9, chunks of 4096), in one process, the runs interleaved (nine repeats unless --reps says
             otherwise): milliseconds per file, median and spread; then p2phd_pcm_encode_shaped alone, by events, at chunk 4096 and
@@ -115,6 +123,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py stereo [--off_only] [--stereo_log profiles/time_generate_stereo.log]
         python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
         python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
+        python tools/time_generate.py segnorm [--segnorm_log profiles/time_generate_segment_norm.log]
         python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
         python tools/time_generate.py flacout [--flac_lpc 12] [--flacout_log profiles/time_generate_flacout.log] [--flaclpc_log profiles/time_generate_flaclpc.log]
         python tools/time_generate.py wavcodec [--wavcodec_log profiles/time_generate_wavcodec.log]
@@ -1702,6 +1711,120 @@ def _normscope_kernels(torch, model, opt, x, reps):
     return "\n".join(lines) + "\n"
 
 
+def run_segnorm(seconds, reps, log):
+    """File to file, norm_scope 'group' (an object built without any option), 'clip' and segment_norm, interleaved: enhance_file on
+    the mono clip, then enhance_folder on eight two-channel clips of 2 s (four segments a channel: one full group) and of 1.5 s (three:
+    the one group of every channel of 'group' and 'clip' runs eagerly); then p2phd_spectro_encode_rows beside p2phd_spectro_encode_ex and p2phd_spectro_encode_given, and the row decode
+    beside the plain one, alone, by events, on one group's spectrum."""
+    import tempfile
+    torch, model, opt, x = _setup(seconds)
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, segment_plan
+    rate = int(opt.hr_sampling_rate)
+    files, shorts = 8, (2.0, 1.5)
+    lines = ["# tools/time_generate.py segnorm: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed; one "
+             "%g s mono PCM16 clip at 48 kHz, file to file, and folders of %d two-channel clips of %s s, files to files, channels='all'; "
+             "untrained weights, %d interleaved repeats" % (seconds, files, " and ".join("%g" % v for v in shorts), reps)]
+    runs = [("norm_scope group     ", SuperResolver(model, opt, overlap=0.25)),
+            ("norm_scope clip      ", SuperResolver(model, opt, overlap=0.25, norm_scope='clip')),
+            ("segment_norm         ", SuperResolver(model, opt, overlap=0.25, segment_norm=True))]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out, d_out = (os.path.join(tmp, f) for f in ("in.wav", "out.wav", "out"))
+        wavio.save(src, x.cpu(), rate)
+        works = [("the %g s mono clip" % seconds, x.shape[-1], 1, lambda sr: sr.enhance_file(src, out))]
+        for short in shorts:
+            d_in = os.path.join(tmp, "in%g" % short)
+            os.makedirs(d_in)
+            n = int(short * rate)
+            for i in range(files):
+                a = x[:, i * 4000:i * 4000 + n]
+                wavio.save(os.path.join(d_in, "clip%03d.wav" % i), torch.cat([a, -0.7 * a.flip(-1)]).cpu() * 0.9 ** i, rate)
+            works.append(("the folder of %d two-channel clips of %g s" % (files, short), n, 2,
+                          lambda sr, d_in=d_in: sr.enhance_folder(d_in, d_out, channels='all')))
+        for what, length, C, work in works:
+            for _, sr in runs:                                      # warm-up: capture, pinned buffers, page cache
+                work(sr)
+                work(sr)
+            torch.cuda.synchronize()
+            ts = [[] for _ in runs]
+            for _ in range(reps):
+                for k, (_, sr) in enumerate(runs):
+                    t0 = time.perf_counter()
+                    work(sr)
+                    torch.cuda.synchronize()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            sr = runs[0][1]
+            S = segment_plan(length, sr.T, sr.overlap)[0]
+            lines.append("%s: %d segments per channel; 'group' and 'clip' walk each channel in %d replayed group%s of %d and %s; segment_norm walks a "
+                         "file's %d rows in %d replayed groups, %d filler row%s"
+                         % (what, S, S // sr.batch, '' if S // sr.batch == 1 else 's', sr.batch,
+                            "one eager group of %d" % (S % sr.batch) if S % sr.batch else "no eager group", C * S, -(-C * S // sr.batch),
+                            -C * S % sr.batch, '' if -C * S % sr.batch == 1 else 's'))
+            for (name, _), tk in zip(runs, ts):
+                lines.append("%s  median %8.3f ms   spread %6.3f (%.3f .. %.3f)   %+7.2f %% against group   runs: %s"
+                             % (name, _median(tk), max(tk) - min(tk), min(tk), max(tk), 100.0 * (_median(tk) - _median(ts[0])) / _median(ts[0]),
+                                " ".join("%.3f" % v for v in tk)))
+    text = "\n".join(lines) + "\n" + _segnorm_kernels(torch, model, opt, x, reps)
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _segnorm_kernels(torch, model, opt, x, reps):
+    """The row encode beside the encodes it stands in for and the row decode beside the plain one, alone, by events, on the spectrum
+    of one group of the clip (and its mask noise)."""
+    from pix2pixhdaudiosr_amd import _lib
+    L = _lib.lib()
+    T, b = int(opt.segment_length), int(opt.batchSize)
+    seg = x[0, :b * T].reshape(b, T).contiguous()
+    with torch.no_grad():
+        spec = model._mdct(seg).contiguous()
+    al, mv, st = float(opt.alpha), float(opt.min_value), _lib.stream_ptr()
+    B, Fr, M = spec.shape
+    shape = model.mask_noise_shape(b, T)
+    noise = torch.randn(shape, device=spec.device)
+    R = shape[2]
+    part = torch.empty(L.p2phd_spectro_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+    ws = torch.empty(L.p2phd_spectro_rows_partials_floats(B, Fr, M), dtype=torch.float32, device=spec.device)
+    log, pha = torch.empty((B, 2, M, Fr), device=spec.device), torch.empty((B, 1, M, Fr), device=spec.device)
+    back = torch.empty((B, Fr, M), device=spec.device)
+    norm8, rows = torch.zeros(8, device=spec.device), torch.zeros((B, 8), device=spec.device)
+    keep = M - R
+    calls = [("p2phd_spectro_encode_ex", lambda: L.p2phd_spectro_encode_ex(_lib.ptr(spec), B, Fr, M, 2, al, mv, R, 2, _lib.ptr(noise), None,
+                                                                           _lib.ptr(log), _lib.ptr(pha), _lib.ptr(norm8), _lib.ptr(part), st)),
+             ("p2phd_spectro_encode_given", lambda: L.p2phd_spectro_encode_given(_lib.ptr(spec), B, Fr, M, 2, al, mv, R, 2, _lib.ptr(noise), None,
+                                                                                 _lib.ptr(norm8), _lib.ptr(log), _lib.ptr(pha), st)),
+             ("p2phd_spectro_encode_rows", lambda: L.p2phd_spectro_encode_rows(_lib.ptr(spec), B, Fr, M, 2, al, mv, R, 2, _lib.ptr(noise), None,
+                                                                               _lib.ptr(rows), _lib.ptr(log), _lib.ptr(pha), _lib.ptr(ws), st)),
+             ("p2phd_spectro_decode_signed", lambda: L.p2phd_spectro_decode_signed(_lib.ptr(log), _lib.ptr(pha), _lib.ptr(norm8), B, Fr, M, 2, keep, mv,
+                                                                                   1.0, _lib.ptr(back), st)),
+             ("p2phd_spectro_decode_signed_rows", lambda: L.p2phd_spectro_decode_signed_rows(_lib.ptr(log), _lib.ptr(pha), _lib.ptr(rows), B, Fr, M, 2,
+                                                                                             keep, mv, 1.0, _lib.ptr(back), st))]
+    lines = ["kernels alone on one group (events, median of %d): spectrum [%d, %d, %d] f32 = %.2f MB, noise %.2f MB, encoded %.2f MB; the row "
+             "encode's workspace %d floats" % (reps, B, Fr, M, spec.numel() * 4e-6, noise.numel() * 4e-6, (log.numel() + pha.numel()) * 4e-6, ws.numel())]
+    # what each has to move at the least: the encode reads the spectrum and the noise twice and writes, reads and rewrites the planes;
+    # the row encode reads the spectrum and the noise twice and writes the planes once
+    enc = spec.numel() + log.numel() + pha.numel() + noise.numel()
+    dec = log.numel() + pha.numel() + back.numel()
+    moved = {"p2phd_spectro_encode_ex": spec.numel() + 3 * log.numel() + pha.numel() + 2 * noise.numel(), "p2phd_spectro_encode_given": enc,
+             "p2phd_spectro_encode_rows": enc + spec.numel() + noise.numel(), "p2phd_spectro_decode_signed": dec, "p2phd_spectro_decode_signed_rows": dec}
+    for name, fn in calls:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        us = []
+        for _ in range(reps + 2):
+            ev[0].record()
+            _lib.check(fn(), name)
+            ev[1].record()
+            torch.cuda.synchronize()
+            us.append(ev[0].elapsed_time(ev[1]) * 1e3)
+        m = _median(us[2:])
+        lines.append("%-34s %8.1f us (spread %.1f) = %.0f GB/s of the %.2f MB it has to move   runs: %s"
+                     % (name, m, max(us[2:]) - min(us[2:]), moved[name] * 4e-3 / m, moved[name] * 4e-6, " ".join("%.1f" % v for v in us[2:])))
+    return "\n".join(lines) + "\n"
+
+
 def run_limiter(seconds, reps, log):
     """enhance_file, file to file, at a loudness target that leaves the true peak 4 dB over a -1 dBTP ceiling: no output option, the
     guard alone, the limiter in front of the guard -- the same object, the same input, interleaved; what the two written files
@@ -1882,7 +2005,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "segnorm", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -1899,6 +2022,7 @@ def main():
     ap.add_argument("--rateconv_log", default=os.path.join(ROOT, "profiles", "time_generate_rateconv.log"))
     ap.add_argument("--speechlevel_log", default=os.path.join(ROOT, "profiles", "time_generate_speechlevel.log"))
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
+    ap.add_argument("--segnorm_log", default=os.path.join(ROOT, "profiles", "time_generate_segment_norm.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--wavcodec_log", default=os.path.join(ROOT, "profiles", "time_generate_wavcodec.log"))
@@ -1935,6 +2059,8 @@ def main():
     if a.mode == "dither":
         log = a.dither_log if not a.off_only or "--dither_log" in sys.argv else None
         return run_dither(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "segnorm":
+        return run_segnorm(a.seconds, 9 if a.reps is None else a.reps, a.segnorm_log)
     if a.mode == "normscope":
         log = a.normscope_log if not a.off_only or "--normscope_log" in sys.argv else None
         return run_normscope(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
