@@ -222,6 +222,19 @@ int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* 
  *   each (two "stitch" launches per clip whatever C is): audio [C][ld] -> out [C * S, T], channel-major (row c * S + s is
  *   segment s of channel c), and seg [C * S, T] -> out [C][ld], L_out samples per row, the rest of a row untouched.  Row c is
  *   bit-identical to the single-row entry on audio[c] / seg[c * S : (c + 1) * S].  Same errors, plus C < 1, ld < L, ld < L_out.
+ * p2phd_segments_gather_ragged / p2phd_segments_stitch_ragged: the same two over N clip rows that share only T and stride -- the
+ *   channels of several files -- in ONE launch each, one count of "stitch" per launch.  `table`, in HOST memory: N x 4 int64, row j
+ *   = (address of audio_j resp. out_j on the device, L_j, S_j, row0_j); row j owns rows row0_j .. row0_j + S_j - 1 of seg [rows, T].
+ *   The gather fills them from audio_j [L_j], the stitch writes out_j [L_j] from them; either is bit-identical to the planar entry
+ *   on that clip alone (C = 1), and a row takes the 16-byte paths by its own base's alignment.  The entry checks the table before
+ *   anything is launched (P2PHD_EINVAL): 1 <= N <= 65535; every L >= 0 and S >= 1; row0_0 = 0, row0_{j+1} = row0_j + S_j, the
+ *   last row closing at `rows`; an address non-null where L > 0 and a multiple of 4; T, stride, V = T - stride and rows * T as
+ *   above; stitch: L_j <= (S_j - 1) stride + T.  It then copies the checked table -- through pinned memory of its own, on `stream` --
+ *   into `table_dev`, p2phd_segments_ragged_table_bytes(N) bytes on the device that the caller keeps alive until the launch has
+ *   run, and the kernel reads that copy alone: what the caller does with `table` behind the call changes nothing.  Nothing is
+ *   waited for.  Not inside a stream capture (P2PHD_EINVAL).  A stitch whose every L is 0 launches nothing.  Grid: blockIdx.y =
+ *   clip row, grid.x from p2phd_stream_grid("segments_gather_ragged" / "segments_stitch_ragged") of the LONGEST row's outputs
+ *   (S_j * T resp. L_j); a shorter row's surplus workgroups leave at once.
  * ---------------------------------------------------------------------------------------- */
 int p2phd_segments_gather(const float* audio, int64_t L, int64_t T, int64_t stride, int64_t S, float* out, void* stream);
 int p2phd_segments_stitch(const float* seg, int64_t S, int64_t T, int64_t stride, float gain, float* out, int64_t L_out,
@@ -230,6 +243,11 @@ int p2phd_segments_gather_planar(const float* audio, int64_t C, int64_t ld, int6
                                  float* out, void* stream);
 int p2phd_segments_stitch_planar(const float* seg, int64_t C, int64_t S, int64_t T, int64_t stride, float gain, float* out,
                                  int64_t ld, int64_t L_out, void* stream);
+int64_t p2phd_segments_ragged_table_bytes(int64_t N);      /* 32 * N; 0 for an N outside 1 .. 65535 */
+int p2phd_segments_gather_ragged(const int64_t* table, int64_t N, int64_t T, int64_t stride, int64_t rows, float* seg, void* table_dev,
+                                 void* stream);
+int p2phd_segments_stitch_ragged(const float* seg, const int64_t* table, int64_t N, int64_t rows, int64_t T, int64_t stride, float gain,
+                                 void* table_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PCM codec of whole-file generation, csrc/pcm.hip.  Launch family "pcm" (a decode and an encode count 1 each; frames = 0
@@ -1163,6 +1181,8 @@ int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C,
  * grid covers (work > 2 * unit_work: some thread takes a third trip).  The launchers take their grids from the same function.
  * `work` per family, and the cap:
  *   segments_gather(_planar), segments_stitch(_planar)   outputs per row (S * T, resp. L_out); a quad per thread; 16384
+ *   segments_gather_ragged, segments_stitch_ragged       outputs of the longest clip row (S_j * T, resp. L_j); a quad per thread;
+ *                                                         1024 per clip row (grid.y = clip rows, up to 65535 of them)
  *   pcm_decode(_ex), pcm_encode, pcm_encode_ex            interleaved samples (frames * channels); 16384
  *   pcm_peak                                              frames per row, rows = channels; four 16-byte pieces in flight per
  *                                                         thread; min(2048 / channels, what the reduction scratch holds)

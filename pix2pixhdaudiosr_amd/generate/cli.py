@@ -12,7 +12,7 @@ import torch
 
 from .ops import shaper_coefficients
 from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MODES, check_lowband,
-                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_segment_norm, check_stereo_report, output_rate_line, spectro_bins)
+                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_segment_norm, check_pack_files, check_stereo_report, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_speech_level, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
@@ -321,6 +321,12 @@ def _parser():
                          "the same file at every batch size, a silent segment stays silent, no pass in front of the first group; all "
                          "channels of a file share groups and the last group is filled up with silent segments, so every group "
                          "replays the one captured graph; one start-up line more; not with --norm_scope clip (default: off)")
+    ap.add_argument("--pack_files", type=int, default=1, metavar="N",
+                    help="a folder as --input, with --segment_norm: up to N consecutive files share the generator's groups -- their "
+                         "segments are gathered and stitched in one launch each and walked as one clip's, so a folder of short "
+                         "utterances runs full groups where file by file each one's last group is filled up with silent segments; "
+                         "a file's own segments, ranges and (with a seed) mask noise stay those of N = 1; one start-up line more; not "
+                         "with --loudness_scope folder (default: 1, every file on its own)")
     ap.add_argument("--stereo_report", action="store_true",
                     help="report how the left and right channel of a file written with two channels correlate below and above the low "
                          "rate's Nyquist frequency -- for the input the generator was given, the generated clip and, for a full-band "
@@ -377,6 +383,8 @@ def main(argv=None):
     try:                                                                    # before anything is loaded
         folder_mode = check_paths(a.input, a.output)
         check_segment_norm(a.segment_norm, a.norm_scope, "generate")
+        if check_pack_files(a.pack_files, a.segment_norm, a.loudness_scope, "generate") > 1 and not folder_mode:
+            raise ValueError("--pack_files is an option of a folder as --input")
         out_stage = check_output_options(a.encoding, a.clip, a.ceiling_dbfs, a.dither, a.dither_seed, a.report_peaks, "generate", a.dither_curve,
                                          a.dither_chunk)
         if a.output_rate is not None:                                       # (the model's rate: once the options file has been read)
@@ -397,6 +405,8 @@ def main(argv=None):
             picture['input_formats'] = check_input_formats(a.input_formats, "generate")
         if a.verify_input:
             picture['verify_input'] = True
+        if a.pack_files > 1:
+            picture['pack_files'] = a.pack_files
         if check_container(a.container, a.flac_block, a.flac_md5, a.encoding, a.output_rate or 48000, "generate",
                            **({} if a.flac_lpc is None else dict(flac_lpc=a.flac_lpc))) is not None:
             picture.update(container=a.container, **{k: v for k, v in (('flac_block', a.flac_block), ('flac_md5', a.flac_md5 or None), ('flac_lpc', a.flac_lpc))
@@ -458,6 +468,8 @@ def main(argv=None):
         print('normalisation: one range per clip')
     if sr.segment_norm:                                                     # (without the option: no line more than before)
         print('normalisation: one range per segment')
+    if a.pack_files > 1:                                                    # (without the option: no line more than before)
+        print('packing: up to %d files share groups' % a.pack_files)
     if rc is not None:                                                      # (without the option: no line more than before)
         print(output_rate_line(rc))
     if a.dither == 'shaped':                                                # (without the option: no line more than before)

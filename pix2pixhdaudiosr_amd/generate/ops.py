@@ -75,7 +75,69 @@ def segments_stitch_planar(seg, C, stride, gain=1.0, out_length=None, ld=None):
     return out[:, :max(L_out, 0)]
 
 
-PCM_BIG_ENDIAN, PCM_SIGNED8 = 1, 2                                          # P2PHD_PCM_* flags of include/p2phd.h
+def _ragged_table(rows):
+    """[(address, L, S), ..] of the clip rows in order -> (the N x 4 int64 table of the ragged entries in host memory, with row0
+    filled in; the segment rows they close at)."""
+    words, at = [], 0
+    for addr, L, S in rows:
+        words.append((addr, L, S, at))
+        at += S
+    return torch.tensor(words, dtype=torch.int64).reshape(-1, 4), at
+
+
+def _ragged_table_dev(N, device):
+    """The device buffer a ragged entry copies its checked table into; stream-ordered like any tensor of the allocator."""
+    return torch.empty((max(int(_lib.lib().p2phd_segments_ragged_table_bytes(N)), 1),), dtype=torch.uint8, device=device)
+
+
+def segments_gather_ragged(clips, T, stride, S_list):
+    """clips: a list of [C_i, L_i] f32 tensors on the GPU (rows contiguous, any row pitch), S_list: segments per channel of each ->
+    seg [sum C_i * S_i, T]: clip after clip, each channel-major, the rows segments_gather_planar(clips[i], T, stride, S_list[i])
+    gives -- bit for bit -- in ONE launch for all of them.  Every channel takes the 16-byte path by its own base's alignment."""
+    if len(clips) != len(S_list) or not clips:
+        raise ValueError("segments_gather_ragged: expected as many segment counts as clips and at least one clip, got %d and %d"
+                         % (len(S_list), len(clips)))
+    rows, keep = [], []
+    for i, (clip, S) in enumerate(zip(clips, S_list)):
+        a, C, L, ld = _rows(clip, "segments_gather_ragged: clip %d" % i)
+        keep.append(a)
+        rows.extend((a.data_ptr() + 4 * c * ld if L else 0, L, int(S)) for c in range(C))
+    table, total = _ragged_table(rows)
+    dev = keep[0].device
+    out = torch.empty((max(total, 0), max(int(T), 0)), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().p2phd_segments_gather_ragged(table.data_ptr(), len(rows), int(T), int(stride), total, _lib.ptr(out),
+                                                       _lib.ptr(_ragged_table_dev(len(rows), dev)), _lib.stream_ptr()), "segments_gather_ragged")
+    return out
+
+
+def segments_stitch_ragged(seg, lengths, channel_counts, stride, gain=1.0):
+    """seg [sum C_i * S_i, T] f32 on the GPU as segments_gather_ragged lays it out, lengths: L_i, channel_counts: C_i (every channel
+    of clip i has S_i = the fewest segments whose span reaches L_i at this stride, at least one) -> a list of [C_i, L_i]: what
+    segments_stitch_planar gives on clip i's rows -- bit for bit -- in ONE launch for all of them."""
+    s = _lib.require_gpu_tensor(seg, "segments_stitch_ragged: seg", torch.float32)
+    if s.dim() != 2 or len(lengths) != len(channel_counts) or not lengths:
+        raise ValueError("segments_stitch_ragged: expected [rows, T] and as many lengths as channel counts, at least one")
+    T, stride = s.shape[1], int(stride)
+    if not 1 <= stride <= T:
+        raise ValueError("segments_stitch_ragged: stride must be in [1, T], got %d (T %d)" % (stride, T))
+    outs, rows = [], []
+    for L, C in zip(lengths, channel_counts):
+        L, C = int(L), int(C)
+        if L < 0 or C < 1:
+            raise ValueError("segments_stitch_ragged: need every length >= 0 and channel count >= 1, got %d and %d" % (L, C))
+        S = max(1, -((T - stride - L) // stride))
+        out = torch.empty((C, L), dtype=torch.float32, device=s.device)
+        outs.append(out)
+        rows.extend((out.data_ptr() + 4 * c * L if L else 0, L, S) for c in range(C))
+    table, total = _ragged_table(rows)
+    if total != s.shape[0]:
+        raise ValueError("segments_stitch_ragged: the clips take %d segment rows, seg has %d" % (total, s.shape[0]))
+    _lib.check(_lib.lib().p2phd_segments_stitch_ragged(_lib.ptr(s), table.data_ptr(), len(rows), total, T, stride, float(gain),
+                                                       _lib.ptr(_ragged_table_dev(len(rows), s.device)), _lib.stream_ptr()), "segments_stitch_ragged")
+    return outs
+
+
+PCM_BIG_ENDIAN, PCM_SIGNED8 = 1, 2                                       # P2PHD_PCM_* flags of include/p2phd.h
 
 
 def pcm_decode(payload, frames, channels, format_tag, bits, big_endian=False, signed8=False):

@@ -393,6 +393,42 @@ def group_rows_plan(rows, batch):
     return [(r0, min(batch, rows - r0)) for r0 in range(0, rows, batch)]
 
 
+PACK_MAX_BYTES = 1 << 30                                                    # the float32 clips one pack holds on the device at most
+
+
+def check_pack_files(pack_files=1, segment_norm=True, loudness_scope='file', who="enhance_folder"):
+    """Validates the folder option pack_files -> the int: how many consecutive files of a folder share generator groups, 1 (the
+    default) for none.  More than one needs segment_norm -- only then is a row of a group independent of its neighbours -- and is
+    not built for loudness_scope 'folder', whose phase A is not packed: a ValueError each."""
+    if isinstance(pack_files, bool) or not _is_int(pack_files) or pack_files < 1:
+        raise ValueError("%s: pack_files must be an int >= 1, got %r" % (who, pack_files))
+    if pack_files > 1 and not segment_norm:
+        raise ValueError("%s: pack_files %d lets the files of a folder share groups, which needs segment_norm: only there does a row "
+                         "of a group not depend on its neighbours" % (who, pack_files))
+    if pack_files > 1 and loudness_scope == 'folder':
+        raise ValueError("%s: pack_files is not built for loudness_scope 'folder' (the album's first pass is not packed)" % who)
+    return int(pack_files)
+
+
+def pack_plan(sizes, pack_files, max_bytes=PACK_MAX_BYTES):
+    """How a folder's accepted files form packs: `sizes` -- the bytes of every file's float32 clip, in plan order -> a list of packs,
+    each a list of consecutive indices into `sizes`.  A pack closes at `pack_files` files, and before the file with which its
+    clips would exceed `max_bytes`; a file larger than that is a pack of its own.  Every file is in exactly one pack, in order."""
+    pack_files = check_pack_files(pack_files, who="pack_plan")
+    if not _is_int(max_bytes) or max_bytes < 1:
+        raise ValueError("pack_plan: max_bytes must be an int >= 1, got %r" % (max_bytes,))
+    packs, held = [], 0
+    for i, size in enumerate(sizes):
+        if not _is_int(size) or size < 0:
+            raise ValueError("pack_plan: sizes must be ints >= 0, got %r" % (size,))
+        if not packs or len(packs[-1]) >= pack_files or held + size > max_bytes:
+            packs.append([])
+            held = 0
+        packs[-1].append(i)
+        held += size
+    return packs
+
+
 def check_stereo_report(stereo_report=False, opts=None, loudness_scope='file', who="enhance_file"):
     """Validates the stereo report option -> None (off), or the plan {'n_fft', 'hop'} that ops.stereo_image takes.  `stereo_report`:
     a bool.  `opts`: None or a dict of those two, None or absent standing for STEREO_DEFAULTS' value (hop: half of a given n_fft):

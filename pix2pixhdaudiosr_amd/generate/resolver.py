@@ -8,8 +8,8 @@ from collections import namedtuple
 import torch
 
 from .ops import (flac_decode, g711_decode, ima_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, speech_level as _speech_level, _speech_level_views, speech_level_packed_bytes, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_stitch_planar, shaper_coefficients, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_segment_norm, group_rows_plan, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
+                  limiter_apply, limiter_envelope, speech_level as _speech_level, _speech_level_views, speech_level_packed_bytes, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_gather_ragged, segments_stitch_planar, segments_stitch_ragged, shaper_coefficients, spectrogram_rgb, stft_db)
+from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_segment_norm, group_rows_plan, check_pack_files, pack_plan, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
                     check_container, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MAX_CHANNELS, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
 
 
@@ -32,6 +32,11 @@ _Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album flac sl
 # The keys a folder record may carry behind the eight it always has (and 'written'), in the record's order; each is also the key
 # of enhance_file's result that fills it ('album': enhance_album's own).
 _RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'speech_level', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm', 'flac')
+
+
+# One clip between the parts of enhance_lr / enhance_lr_many: `x` the [C, L] clip the rows are gathered from (mid and side with
+# stereo 'ms'), its segment plan, and `measured` -- the auto crossover's measurement on the device and the event behind it, or None.
+_Clip = namedtuple('_Clip', 'x C L S stride ms measured')
 
 
 class _File:
@@ -321,7 +326,9 @@ class SuperResolver:
         with torch.no_grad():
             return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
 
-    def _enhance_lr(self, lr_audio, noise):
+    def _before_rows(self, lr_audio):
+        """In front of the rows, per clip: the checks, the auto crossover's measurement and its event, the mid/side encode -> the
+        _Clip the rows and _behind_rows go on with."""
         x = lr_audio.to(self.device).float()
         if x.dim() == 1:
             x = x[None]
@@ -343,6 +350,65 @@ class SuperResolver:
             # two rows are mid and side -- the segments, the groups' normalisation, the mask-noise row blocks and the crossover's
             # low band (a linear filter commutes with the matrix)
             x = stereo_matrix(x, 0.5)
+        return _Clip(x, C, L, S, stride, ms, measured)
+
+    def _behind_rows(self, clip, sr):
+        """Behind the rows, per clip: the stitched [C, L] -> the crossover, fixed or auto, and the mid/side decode."""
+        if self.crossover_plan is not None:
+            if clip.measured is not None:
+                taps = self._auto_taps(*clip.measured)
+            else:
+                if self._xover_taps is None:
+                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
+                taps = self._xover_taps
+            sr = crossover(sr, clip.x, self.gain / 2.0, taps)
+        if clip.ms:
+            # back to left / right, in place.  A side signal of digital silence (dual mono) leaves the chain as NaN -- its group is
+            # scaled by 1 / (max - min) --: the decoder reads a non-finite side sample as "no side here"
+            sr = sr.contiguous()
+            stereo_matrix(sr, 1.0, guard_side=True, out=sr)
+        return sr
+
+    def enhance_lr_many(self, clips, noise=None):
+        """clips: a list of [C_i, L_i] (or [L_i]) waveforms on the GPU, already at the high rate -> the list of generated clips
+        [C_i, L_i]: enhance_lr on each, with the rows of all of them -- R = sum of C_i * S_i, clip after clip, each channel-major --
+        sharing groups.  Needs segment_norm (a ValueError otherwise): only there does a row not depend on its neighbours.  Each clip
+        goes through enhance_lr's part in front of the rows; one ragged gather (ops.segments_gather_ragged) lays all rows out, the
+        one walk of _walk_rows takes them through ceil(R / batch) full groups with fillers in the last group only, one ragged
+        stitch (ops.segments_stitch_ragged) brings every clip back, and each goes through enhance_lr's part behind the rows.  A
+        clip's rows, ranges and stitch are bit for bit those of enhance_lr on it alone; what the generator itself does with a
+        row's neighbours in the batch is all that differs.  `noise`: the mask noise of all R rows in that order, [R, channels,
+        mask_rows, frames]; drawn per group (one torch.randn) when absent.  `last_norm` then holds a list of [C_i, S_i, 2] views,
+        and with crossover_hz 'auto' `last_crossovers` the list of every clip's {'hz', 'taps', 'edge_hz'}."""
+        if not self.segment_norm:
+            raise ValueError("enhance_lr_many: the rows of several clips share groups, which needs segment_norm=True")
+        clips = list(clips)
+        if not clips:
+            return []
+        run = getattr(self.model, '_on_step_stream', None)
+        with torch.no_grad():
+            return run(self._enhance_lr_many, clips, noise) if callable(run) else self._enhance_lr_many(clips, noise)
+
+    def _enhance_lr_many(self, clips, noise):
+        fronts = [self._before_rows(c) for c in clips]
+        seg = segments_gather_ragged([f.x for f in fronts], self.T, fronts[0].stride, [f.S for f in fronts])
+        out = torch.empty_like(seg)
+        self._walk_rows(seg, out, noise, 1, seg.shape[0])
+        ranges, views, at = self.last_norm[0], [], 0
+        for f in fronts:
+            views.append(ranges[at:at + f.C * f.S].view(f.C, f.S, 2))
+            at += f.C * f.S
+        self.last_norm = views
+        stitched = segments_stitch_ragged(out, [f.L for f in fronts], [f.C for f in fronts], fronts[0].stride, self.gain)
+        done, self.last_crossovers = [], []
+        for f, sr in zip(fronts, stitched):
+            done.append(self._behind_rows(f, sr))
+            self.last_crossovers.append(dict(self.last_crossover) if self.crossover_auto else None)
+        return done
+
+    def _enhance_lr(self, lr_audio, noise):
+        clip = self._before_rows(lr_audio)
+        x, C, L, S, stride = clip.x, clip.C, clip.L, clip.S, clip.stride
         seg = segments_gather_planar(x, self.T, stride, S)
         out = torch.empty_like(seg)
         by_clip = self.norm_scope == 'clip'
@@ -382,21 +448,7 @@ class SuperResolver:
                     out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz, *extra))
                 else:
                     out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz, *extra))
-        sr = segments_stitch_planar(out, C, stride, self.gain, L)
-        if self.crossover_plan is not None:
-            if measured is not None:
-                taps = self._auto_taps(*measured)
-            else:
-                if self._xover_taps is None:
-                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
-                taps = self._xover_taps
-            sr = crossover(sr, x, self.gain / 2.0, taps)
-        if ms:
-            # back to left / right, in place.  A side signal of digital silence (dual mono) leaves the chain as NaN -- its group is
-            # scaled by 1 / (max - min) --: the decoder reads a non-finite side sample as "no side here"
-            sr = sr.contiguous()
-            stereo_matrix(sr, 1.0, guard_side=True, out=sr)
-        return sr
+        return self._behind_rows(clip, segments_stitch_planar(out, C, stride, self.gain, L))
 
     def _auto_taps(self, res_dev, event):
         """crossover_hz 'auto': the clip's measurement (ops.bandwidth's 32 bytes on the device, `event` recorded behind it) -> the
@@ -839,6 +891,13 @@ class SuperResolver:
     def _front(self, read, is_lr_input, channels, encoding, o, who):
         """(a) What _read returned -> the checks that need the file's header, decode, the low-rate round trip, enhance_lr ->
         the _File.  `who`: "enhance_file" on the per-file path, also from a folder; "enhance_folder" from the album."""
+        lr, hr, meta = self._front_clip(read, is_lr_input, channels, encoding, o, who)
+        clip = self.enhance_lr(lr)
+        # norm_scope 'clip', segment_norm: this file's ranges, on the device; crossover_hz 'auto': the crossover this file got
+        return _File(clip, lr, hr, meta, self.last_norm, dict(self.last_crossover) if self.crossover_auto else None)
+
+    def _front_clip(self, read, is_lr_input, channels, encoding, o, who):
+        """_front's part in front of enhance_lr -> (the clip the generator is given, the original or None, the input's info)."""
         from ..data import audio_dataset                                    # (looked up per call: the tests replace lr_round_trip)
         host, meta, slot = read
         check_encoding(encoding, who)
@@ -857,9 +916,7 @@ class SuperResolver:
         has_hr = not is_lr_input and int(rate) == int(self.opt.hr_sampling_rate)
         if has_hr:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
-        clip = self.enhance_lr(lr)
-        # norm_scope 'clip', segment_norm: this file's ranges, on the device; crossover_hz 'auto': the crossover this file got
-        return _File(clip, lr, raw if has_hr else None, meta, self.last_norm, dict(self.last_crossover) if self.crossover_auto else None)
+        return lr, raw if has_hr else None, meta
 
     def _reports(self, f, o):
         """(b) The bandwidth and the stereo measurement -> (band, image), None where off.  Both see the generated clip behind the
@@ -936,7 +993,10 @@ class SuperResolver:
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics, o):
         """One file from its bytes (what _read returned) to the written output -> enhance_file's result, with 'metrics' in one
         shape: a list with one 7-tuple per written channel, or None.  `o`: the _Options, its stage and spectrogram this file's."""
-        f = self._front(read, is_lr_input, channels, encoding, o, "enhance_file")
+        return self._finish(self._front(read, is_lr_input, channels, encoding, o, "enhance_file"), path_out, encoding, extended_metrics, o)
+
+    def _finish(self, f, path_out, encoding, extended_metrics, o):
+        """Stages (b) to (f) of one file behind its enhance_lr -> enhance_file's result."""
         band, image = self._reports(f, o)
         self._metrics(f, extended_metrics)
         measure, speech = self._level(f, o)
@@ -965,10 +1025,11 @@ class SuperResolver:
                    out_frames=res['sr'].shape[-1], metrics=res['metrics'])
         rec.update((key, res[key]) for key in _RECORD_KEYS if key in rec and key in res)
 
-    def _open(self, path_in, channels, verify_input, o, rec):
-        """_read and the checks that make a skipped file -> what _read returned, or None with the reason in rec['error']."""
+    def _open(self, path_in, channels, verify_input, o, rec, slot=None):
+        """_read and the checks that make a skipped file -> what _read returned, or None with the reason in rec['error'].  `slot`:
+        None, or the pinned buffer to read into where it is not _read's own."""
         try:
-            read = self._read(path_in, **_set(verify=True if verify_input else None))
+            read = self._read(path_in, **_set(slot=slot, verify=True if verify_input else None))
             self._check_picture_channel(o.spec, channels, read[1].num_channels)
             self._check_stereo_channels(channels, read[1].num_channels)
             if o.flac is not None and select_channels(channels, read[1].num_channels) > 8:
@@ -987,7 +1048,7 @@ class SuperResolver:
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
                      dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
-                     speech_level_max_gain_db=None):
+                     speech_level_max_gain_db=None, pack_files=1):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -1131,12 +1192,16 @@ class SuperResolver:
         generated clip's, the level with the gain), 'activity_input', 'channels': [{'active', 'long_term', 'activity'}, ..] (the
         generated clip's rows, with the gain)}.  A clip without activity has the level -inf and the gain 1.  Not together with
         `loudness` (two claims on one gain), not over more than 8 written channels, and only at rates in 8000 .. 192000: a
-        ValueError each, the first and the last before a file is opened."""
+        ValueError each, the first and the last before a file is opened.
+        `pack_files`: 1.  More -- files that share generator groups -- is an option of enhance_folder and a ValueError here, before
+        the file is opened; the two entry points take the same options."""
         o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
                           **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
                                  speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
+        if check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_file") > 1:
+            raise ValueError("enhance_file: pack_files %d lets the files of a folder share groups: it is an option of enhance_folder" % pack_files)
         read = self._read(path_in, **_set(verify=True if verify_input else None))
         res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
@@ -1164,7 +1229,7 @@ class SuperResolver:
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
                        stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
                        verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
-                       speech_level_max_gain_db=None):
+                       speech_level_max_gain_db=None, pack_files=1):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -1219,17 +1284,32 @@ class SuperResolver:
         the album flow writes through the same encoder and the same writer.
         `speech_level`, `speech_level_max_gain_db`: enhance_file's, per file; a record then gains 'speech_level' (as enhance_file
         returns it; None for a skipped file).  A file of which more than 8 channels would be written is skipped, its record carrying
-        the 'error'."""
+        the 'error'.
+        `pack_files` (an option of SuperResolver(segment_norm=True); 1, the default: nothing changes): up to this many consecutive
+        files of the plan that open share generator groups (plans.pack_plan: a pack also closes before the file with which its
+        float32 clips would exceed plans.PACK_MAX_BYTES; a larger file is a pack of its own; a file that does not open takes no
+        place).  Every file of a pack is read into a pinned buffer of its own ('pack0', 'pack1', ..), decoded and taken through the
+        low-rate round trip; one enhance_lr_many generates all of them, ceil(R / batch) groups for the R rows of the pack where file
+        by file each rounds up on its own; then each file goes through the stages behind enhance_lr as ever -- its own options,
+        `dither_seed` + k with k its place in the plan, its own synchronisation.  Records and `report` calls stay in plan order.  With
+        `seed` a file is given the mask noise a run of its own would draw: the generator is re-seeded per file and that file's
+        ceil(R_i / batch) draws of a full group are made, their first rows kept, and handed on as given noise.  A file's rows,
+        ranges and noise are then bit for bit those of pack_files=1; what the generator does with the other rows of a batch is all
+        that differs.  Without segment_norm, or with loudness_scope 'folder', a ValueError before a file is opened."""
         o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                           spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                           loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
                           album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
                                                     speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
+        pack_files = check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_folder")
         plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
         written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
         if o.album is not None:
             from .album import enhance_album
             return enhance_album(self, plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed, verify_input)
+        if pack_files > 1:
+            return self._enhance_packed(plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed,
+                                        verify_input, pack_files)
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan):
             rec = self._blank_record(rel, path_out, written_from, extended_metrics, o)
@@ -1243,4 +1323,68 @@ class SuperResolver:
             records.append(rec)
             if report is not None:
                 report(rec)
+        return records
+
+    # -- a folder whose files share groups (pack_files > 1) -----------------------------------------------------------
+    def _clip_bytes(self, meta, channels):
+        """The bytes of the float32 clip the generator is given for a file with this header: its written channels at the high rate."""
+        frames = -(-int(meta.num_frames) * int(self.opt.hr_sampling_rate) // max(int(meta.sample_rate), 1))
+        return 4 * select_channels(channels, meta.num_channels) * frames
+
+    def _pack_noise(self, seed, clips):
+        """`seed` with a pack: the mask noise of the pack's rows, every file's as a run of its own draws it -- the generator re-seeded,
+        ceil(R_i / batch) draws of a full group's shape as _walk_rows makes them, the first rows of each kept.  None where the model
+        draws none."""
+        shape = self.noise_shape(self.batch)
+        if shape is None:
+            return None
+        parts = []
+        for lr in clips:
+            rows = lr.shape[0] * segment_plan(lr.shape[-1], self.T, self.overlap)[0]
+            torch.manual_seed(int(seed))
+            parts.extend(torch.randn(shape, device=self.device)[:n] for _, n in group_rows_plan(rows, self.batch))
+        return torch.cat(parts)
+
+    def _enhance_packed(self, plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed,
+                        verify_input, pack_files):
+        """enhance_folder with pack_files > 1 -> the records.  The files are opened in plan order; `waiting` holds, in that order, the
+        records since the last pack was finished -- a file that opened with what its stages need, a skipped one with None -- and a
+        pack is finished when plans.pack_plan says that the file just opened starts the next one."""
+        records, waiting, sizes, opened = [], [], [], 0
+
+        def finish(upto):
+            held = [w for w in waiting[:upto] if w[1] is not None]
+            if held:
+                fronts = [self._front_clip(read, is_lr_input, channels, encoding, mine, "enhance_file") for _, (read, _, mine) in held]
+                lrs = [lr for lr, _, _ in fronts]
+                clips = self.enhance_lr_many(lrs, None if seed is None else self._pack_noise(seed, lrs))
+                norms, crossovers = self.last_norm, self.last_crossovers
+            i = 0
+            for rec, entry in waiting[:upto]:
+                if entry is not None:
+                    (lr, hr, meta), (_, path_out, mine) = fronts[i], entry
+                    f = _File(clips[i], lr, hr, meta, norms[i], crossovers[i])
+                    self._fill_record(rec, self._finish(f, path_out, encoding, extended_metrics, mine))
+                    i += 1
+                if report is not None:
+                    report(rec)
+            del waiting[:upto]
+            del sizes[:len(held)]
+
+        for k, (rel, path_in, path_out) in enumerate(plan):
+            rec = self._blank_record(rel, path_out, written_from, extended_metrics, o)
+            # pack_files + 1 buffers: the file that turns out to start the next pack is read while the pack before it still holds its own
+            read = self._open(path_in, channels, verify_input, o, rec, 'pack%d' % (opened % (pack_files + 1)))
+            records.append(rec)
+            if read is None:
+                waiting.append((rec, None))
+                continue
+            opened += 1
+            mine = o._replace(stage=o.stage and dict(o.stage, seed=dither_seed + k),
+                              spec=o.spec and dict(o.spec, path=os.path.join(o.spec['path'], rel + '.png')))
+            sizes.append(self._clip_bytes(read[1], channels))
+            if len(pack_plan(sizes, pack_files)) > 1:                       # this file starts the next pack: finish the one before it
+                finish(len(waiting))
+            waiting.append((rec, (read, path_out, mine)))
+        finish(len(waiting))
         return records

@@ -99,6 +99,12 @@ bf16, groups of 4, a 15 s synthetic 48 kHz clip, untrained weights.
             p2phd_spectro_decode_signed, alone, by events, on one group's spectrum and noise (the option-off path against another
             checkout: normscope --off_only in either); log in --segnorm_log
 
+  pack      (only when asked for) files to files with SuperResolver(segment_norm=True) at groups of 32, graphed: enhance_folder on 32 mono
+            clips of 3 s with pack_files 1, 4, 16 and 32, in one process, the runs interleaved (nine repeats unless --reps says
+            otherwise): milliseconds per folder, median and spread, and the groups each walks; then the ragged gather and stitch
+            alone, by events, beside the planar launches they replace on the same clips; with --off_only only pack_files 1 is timed
+            (the option-off folder run against another checkout: segnorm in either, which both have); log in --pack_log
+
   dither    (only when asked for) enhance_file on a mono clip of that length, file to file: without any option, with dither='tpdf' and
             with dither='shaped' (lipshitz9, chunks of 4096), in one process, the runs interleaved (nine repeats unless --reps says
             otherwise): milliseconds per file, median and spread; then p2phd_pcm_encode_shaped alone, by events, at chunk 4096 and
@@ -124,6 +130,7 @@ Usage:  python tools/time_generate.py [hand|eager|graphed|seams] [--seconds 15] 
         python tools/time_generate.py rateconv [--off_only] [--rateconv_log profiles/time_generate_rateconv.log]
         python tools/time_generate.py normscope [--off_only] [--normscope_log profiles/time_generate_norm_scope.log]
         python tools/time_generate.py segnorm [--segnorm_log profiles/time_generate_segment_norm.log]
+        python tools/time_generate.py pack [--off_only] [--pack_log profiles/time_generate_pack.log]
         python tools/time_generate.py dither [--off_only] [--dither_log profiles/time_generate_dither.log]
         python tools/time_generate.py flacout [--flac_lpc 12] [--flacout_log profiles/time_generate_flacout.log] [--flaclpc_log profiles/time_generate_flaclpc.log]
         python tools/time_generate.py wavcodec [--wavcodec_log profiles/time_generate_wavcodec.log]
@@ -1772,6 +1779,87 @@ def run_segnorm(seconds, reps, log):
             f.write(text)
 
 
+def run_pack(seconds, reps, log, off_only=False, files=32, clip_seconds=3.0, batch=32):
+    """Files to files with SuperResolver(segment_norm=True) at groups of `batch`: enhance_folder on `files` mono clips of
+    `clip_seconds` s with pack_files 1, 4, 16 and 32, interleaved in one process; then the ragged gather and stitch alone, by events,
+    beside the planar launches they replace on the same clips.  `off_only`: pack_files 1 alone (one process of an alternating
+    comparison with another checkout, whose `segnorm` mode times the same path)."""
+    import tempfile
+    torch, model, opt, x = _setup(max(seconds, clip_seconds + files * 0.1 + 1.0))
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver, segment_plan
+    rate = int(opt.hr_sampling_rate)
+    sr = SuperResolver(model, opt, overlap=0.25, batch=batch, segment_norm=True)
+    n = int(clip_seconds * rate)
+    S = segment_plan(n, sr.T, sr.overlap)[0]
+    packs = (1,) if off_only else (1, 4, 16, 32)
+    lines = ["# tools/time_generate.py pack: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of %d, overlap 0.25, graphed, segment_norm; a "
+             "folder of %d mono PCM16 clips of %g s at 48 kHz (%d rows each), files to files; untrained weights, %d interleaved repeats"
+             % (batch, files, clip_seconds, S, reps)]
+    with tempfile.TemporaryDirectory() as tmp:
+        d_in, d_out = os.path.join(tmp, "in"), os.path.join(tmp, "out")
+        os.makedirs(d_in)
+        clips = []
+        for i in range(files):
+            a = x[:, i * 4800:i * 4800 + n] * 0.97 ** i
+            clips.append(a.contiguous())
+            wavio.save(os.path.join(d_in, "clip%03d.wav" % i), a.cpu(), rate)
+        work = lambda k: sr.enhance_folder(d_in, d_out, **({} if k == 1 else {'pack_files': k}))     # noqa: E731
+        for k in packs:                                             # warm-up: capture, pinned buffers, page cache
+            work(k)
+            work(k)
+        torch.cuda.synchronize()
+        ts = [[] for _ in packs]
+        for _ in range(reps):
+            for j, k in enumerate(packs):
+                t0 = time.perf_counter()
+                work(k)
+                torch.cuda.synchronize()
+                ts[j].append((time.perf_counter() - t0) * 1e3)
+    for k, tk in zip(packs, ts):
+        groups = sum(-(-min(k, files - f0) * S // batch) for f0 in range(0, files, k))
+        lines.append("pack_files %2d  %3d groups of %d for %d rows  median %9.3f ms   spread %7.3f (%.3f .. %.3f)   %+7.2f %% against pack_files 1   runs: %s"
+                     % (k, groups, batch, files * S, _median(tk), max(tk) - min(tk), min(tk), max(tk), 100.0 * (_median(tk) - _median(ts[0])) / _median(ts[0]),
+                        " ".join("%.3f" % v for v in tk)))
+    text = "\n".join(lines) + "\n" + ("" if off_only else _pack_kernels(torch, sr, clips, reps))
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
+def _pack_kernels(torch, sr, clips, reps):
+    """The ragged gather and stitch of all clips in one launch each beside the planar launches, one per clip, that they replace:
+    by events around the whole of either, host work of the wrappers included -- what the stream sees."""
+    from pix2pixhdaudiosr_amd.generate import segment_plan, segments_gather_planar, segments_gather_ragged, segments_stitch_planar, segments_stitch_ragged
+    T = sr.T
+    S, stride, _ = segment_plan(clips[0].shape[-1], T, sr.overlap)
+    lengths, counts = [c.shape[-1] for c in clips], [c.shape[0] for c in clips]
+    seg = segments_gather_ragged(clips, T, stride, [S] * len(clips))
+    calls = [("gather, ragged: 1 launch", lambda: segments_gather_ragged(clips, T, stride, [S] * len(clips))),
+             ("gather, planar: %d launches" % len(clips), lambda: [segments_gather_planar(c, T, stride, S) for c in clips]),
+             ("stitch, ragged: 1 launch", lambda: segments_stitch_ragged(seg, lengths, counts, stride, sr.gain)),
+             ("stitch, planar: %d launches" % len(clips), lambda: [segments_stitch_planar(seg[i * S:(i + 1) * S], 1, stride, sr.gain, lengths[i])
+                                                                    for i in range(len(clips))])]
+    moved = 4e-6 * (sum(lengths) + seg.numel())
+    lines = ["the row ends alone on the %d clips (events, median of %d): %d rows of %d = %.2f MB of segments, %.2f MB of clips" % (len(clips), reps, seg.shape[0], T, seg.numel() * 4e-6, sum(lengths) * 4e-6)]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for name, fn in calls:
+        us = []
+        for _ in range(reps + 2):
+            torch.cuda.synchronize()
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            us.append(ev[0].elapsed_time(ev[1]) * 1e3)
+        m = _median(us[2:])
+        lines.append("%-28s %8.1f us (spread %.1f) = %.0f GB/s of the %.2f MB it has to move   runs: %s"
+                     % (name, m, max(us[2:]) - min(us[2:]), moved * 1e3 / m, moved, " ".join("%.1f" % v for v in us[2:])))
+    return "\n".join(lines) + "\n"
+
+
 def _segnorm_kernels(torch, model, opt, x, reps):
     """The row encode beside the encodes it stands in for and the row decode beside the plain one, alone, by events, on the spectrum
     of one group of the clip (and its mask noise)."""
@@ -2005,7 +2093,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "segnorm", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "segnorm", "pack", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -2023,6 +2111,7 @@ def main():
     ap.add_argument("--speechlevel_log", default=os.path.join(ROOT, "profiles", "time_generate_speechlevel.log"))
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--segnorm_log", default=os.path.join(ROOT, "profiles", "time_generate_segment_norm.log"))
+    ap.add_argument("--pack_log", default=os.path.join(ROOT, "profiles", "time_generate_pack.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--wavcodec_log", default=os.path.join(ROOT, "profiles", "time_generate_wavcodec.log"))
@@ -2059,6 +2148,9 @@ def main():
     if a.mode == "dither":
         log = a.dither_log if not a.off_only or "--dither_log" in sys.argv else None
         return run_dither(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "pack":
+        log = a.pack_log if not a.off_only or "--pack_log" in sys.argv else None
+        return run_pack(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
     if a.mode == "segnorm":
         return run_segnorm(a.seconds, 9 if a.reps is None else a.reps, a.segnorm_log)
     if a.mode == "normscope":
