@@ -3,7 +3,8 @@ normalisation): one integrated loudness over the 400 ms blocks of every file, on
 so the level differences between the files survive.  Three phases: every file is generated and measured (A), the folder's figures
 are found and brought back behind one synchronisation (B), every file is encoded with the folder's gains and written (C).
 What a file goes through in phase A is the per-file flow's own front and metrics stage, and its record is built and filled by the
-functions the per-file scope uses (generate/resolver.py); only what the folder has to itself is written here."""
+functions the per-file scope uses (generate/resolver.py), and it is written through the file path's own functions
+(generate/fileio.py); only what the folder has to itself is written here."""
 import math
 
 import torch

@@ -484,6 +484,37 @@ def main(argv=None):
         return 1
 
 
+def _print_report(a, name, wrote, r):
+    """The lines of one enhanced file behind its `wrote` line, an option's only where the option is on (without it: no line more
+    than before).  `r`: a folder record, or enhance_file's result in that shape; `name`: what the lines call the file; `wrote`: the
+    path that was written."""
+    if r.get('flac') is not None:
+        _print_flac(wrote, r['flac'], a.encoding)
+    if a.report_peaks or a.true_peak or a.limiter:
+        _print_peaks(name, r['output'])
+    if a.limiter:
+        _print_limiter(r['output']['limiter'], r['out_frames'])
+    if r.get('spectrogram') is not None:
+        _print_spectrogram(r['spectrogram'])
+    if r.get('loudness') is not None:
+        _print_loudness(name, r['loudness'])
+        if 'range' in r['loudness']:
+            _print_loudness_range(name, r['loudness']['range'])
+    if r.get('speech_level') is not None:
+        _print_speech_level(name, r['speech_level'])
+    if r.get('crossover') is not None:
+        _print_crossover(r['crossover'])
+    if r.get('bandwidth') is not None:
+        _print_bandwidth(name, r['bandwidth'])
+    if r.get('stereo') is not None:
+        _print_stereo(name, r['stereo'])
+
+
+# --metrics_csv: the argument that brings columns -> write_metrics_csv's flag for them (on: neither None, False nor scope 'file')
+_CSV_FLAGS = {'loudness': 'loudness', 'true_peak': 'true_peak', 'limiter': 'limiter', 'loudness_range': 'loudness_range', 'loudness_scope': 'album',
+              'bandwidth': 'bandwidth', 'stereo_report': 'stereo', 'speech_level': 'speech_level'}
+
+
 def _run(a, sr, stage, seed, rate, folder_mode):
     if folder_mode:
         def report(r):
@@ -491,28 +522,10 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 print('skipped %s: %s' % (r['path'], r['error']))
                 return
             _print_unwritten(r['path'], r['channels'], r['written_channels'])
-            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (os.path.join(a.output, r.get('written', r['path'])), r['out_frames'], rate,
-                                                                   r['written_channels'], '' if r['written_channels'] == 1 else 's'))
-            if r.get('flac') is not None:                                   # (without the option: no line more than before)
-                _print_flac(os.path.join(a.output, r['written']), r['flac'], a.encoding)
-            if a.report_peaks or a.true_peak or a.limiter:
-                _print_peaks(r['path'], r['output'])
-            if a.limiter:
-                _print_limiter(r['output']['limiter'], r['out_frames'])
-            if r.get('spectrogram') is not None:                           # (without the option: no line more than before)
-                _print_spectrogram(r['spectrogram'])
-            if r.get('loudness') is not None:
-                _print_loudness(r['path'], r['loudness'])
-                if 'range' in r['loudness']:
-                    _print_loudness_range(r['path'], r['loudness']['range'])
-            if r.get('speech_level') is not None:                          # (without the option: no line more than before)
-                _print_speech_level(r['path'], r['speech_level'])
-            if r.get('crossover') is not None:
-                _print_crossover(r['crossover'])
-            if r.get('bandwidth') is not None:
-                _print_bandwidth(r['path'], r['bandwidth'])
-            if r.get('stereo') is not None:
-                _print_stereo(r['path'], r['stereo'])
+            wrote = os.path.join(a.output, r.get('written', r['path']))
+            print('wrote %s (%d samples at %d Hz, %d channel%s)' % (wrote, r['out_frames'], rate, r['written_channels'],
+                                                                   '' if r['written_channels'] == 1 else 's'))
+            _print_report(a, r['path'], wrote, r)
         # every file starts from the seed, so it comes out as a run of its own would write it
         records = sr.enhance_folder(a.input, a.output, a.is_lr_input, a.channels, a.encoding, seed=seed, report=report,
                                     extended_metrics=a.metrics_ext, **stage)
@@ -539,48 +552,12 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
         else:
             print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
-        if res.get('flac') is not None:                                     # (without the option: no line more than before)
-            _print_flac(a.output, res['flac'], a.encoding)
-        if a.report_peaks or a.true_peak or a.limiter:
-            _print_peaks(a.output, res['output'])
-        if a.limiter:
-            _print_limiter(res['output']['limiter'], res['sr'].shape[-1])
-        if res.get('spectrogram') is not None:
-            _print_spectrogram(res['spectrogram'])
-        if res.get('loudness') is not None:
-            _print_loudness(a.output, res['loudness'])
-            if 'range' in res['loudness']:
-                _print_loudness_range(a.output, res['loudness']['range'])
-        if res.get('speech_level') is not None:                             # (without the option: no line more than before)
-            _print_speech_level(a.output, res['speech_level'])
-        if res.get('crossover') is not None:
-            _print_crossover(res['crossover'])
-        if res.get('bandwidth') is not None:
-            _print_bandwidth(a.output, res['bandwidth'])
-        if res.get('stereo') is not None:
-            _print_stereo(a.output, res['stereo'])
-        records = [{'path': os.path.basename(a.input), 'out_frames': res['sr'].shape[-1],
-                    'metrics': m, 'metrics_ext': ext, 'output': res.get('output'), 'loudness': res.get('loudness')}]
-        if a.bandwidth:
-            records[0]['bandwidth'] = res['bandwidth']
-        if a.stereo_report:
-            records[0]['stereo'] = res['stereo']
-        if a.speech_level is not None:
-            records[0]['speech_level'] = res['speech_level']
+        # the result in a record's shape: every option's key as enhance_file returned it, a record's own five beside them
+        records = [dict(res, path=os.path.basename(a.input), out_frames=res['sr'].shape[-1], metrics=m, metrics_ext=ext, output=res.get('output'),
+                        loudness=res.get('loudness'))]
+        _print_report(a, a.output, a.output, records[0])
     if a.metrics_csv:
-        extra = dict({} if a.loudness is None else {'loudness': True}, **({'true_peak': True} if a.true_peak else {}))
-        if a.limiter:
-            extra['limiter'] = True
-        if a.loudness_range:
-            extra['loudness_range'] = True
-        if a.loudness_scope == 'folder':
-            extra['album'] = True
-        if a.bandwidth:
-            extra['bandwidth'] = True
-        if a.stereo_report:
-            extra['stereo'] = True
-        if a.speech_level is not None:
-            extra['speech_level'] = True
-        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **extra)
+        on = lambda v: v is not None and v is not False and v != 'file'     # noqa: E731
+        write_metrics_csv(a.metrics_csv, records, a.metrics_ext, a.report_peaks, **{flag: True for arg, flag in _CSV_FLAGS.items() if on(getattr(a, arg))})
         print('metrics: %s' % a.metrics_csv)
     return 0

@@ -1,5 +1,6 @@
-"""Whole-file generation: SuperResolver -- a clip through the model group by group, and the file path around it."""
-import hashlib
+"""Whole-file generation: SuperResolver -- the options of the two entry points, the per-file flow between the rows of a clip
+(generate/rows.py) and the two ends of the file path (generate/fileio.py), a folder's records and the folder drivers."""
+import inspect
 import math
 import os
 import struct
@@ -7,22 +8,14 @@ from collections import namedtuple
 
 import torch
 
-from .ops import (flac_decode, g711_decode, ima_decode, flac_encode, bandwidth as _bandwidth, stereo_image as _stereo_image, stereo_matrix, _limiter_stats_views, _loudness_views, _pcm_peaks_packed, _peak_views, _true_peak_views, _true_peaks_packed, crossover, crossover_coefficients,
-                  limiter_apply, limiter_envelope, speech_level as _speech_level, _speech_level_views, speech_level_packed_bytes, loudness_gate, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, rate_convert, segments_gather_planar, segments_gather_ragged, segments_stitch_planar, segments_stitch_ragged, shaper_coefficients, spectrogram_rgb, stft_db)
-from .plans import (BANDWIDTH_DEFAULTS, check_norm_scope, check_segment_norm, group_rows_plan, check_pack_files, pack_plan, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, LOUDNESS_MAX_CHANNELS, ClipError, bandwidth_notes, check_bandwidth, check_crossover, crossover_auto_plan, check_dither, check_encoding, check_limiter, check_loudness, check_loudness_scope, check_lowband,
-                    check_container, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MAX_CHANNELS, check_loudness_rate, check_output_options, check_output_rate, check_spectrogram, check_true_peak, loudness_channel_weights, plan_folder, segment_plan, select_channels, spectro_bins)
-
-
-def _dbfs(level):
-    return 20.0 * math.log10(level) if level > 0.0 else float('-inf')
-
-
-def _set(**keywords):
-    """Only what is set: the keywords that are not None, in the order given.  An option that is off never reaches a callee as a
-    keyword, so a callee that knows nothing of it (the stubs of the host tests, an override of before the option) is called as
-    it was before the option existed."""
-    return {k: v for k, v in keywords.items() if v is not None}
-
+from .fileio import FilePath, _set                                                                                                  # noqa: F401
+from .ops import (_loudness_views, _speech_level_views, bandwidth as _bandwidth, loudness_gate, loudness_hops, loudness_range, loudness_short_term,
+                  rate_convert, spectrogram_rgb, speech_level as _speech_level, speech_level_packed_bytes, stereo_image as _stereo_image, stft_db)
+from .plans import (LOUDNESS_MAX_CHANNELS, SPEECH_LEVEL_MAX_CHANNELS, bandwidth_notes, check_bandwidth, check_container, check_dither, check_encoding,
+                    check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_output_options, check_output_rate, check_pack_files,
+                    check_spectrogram, check_speech_level, check_speech_level_rate, check_stereo_report, check_true_peak, group_rows_plan,
+                    loudness_channel_weights, pack_plan, plan_folder, segment_plan, select_channels, stereo_figures, stereo_notes, stereo_split_bin)
+from .rows import ClipPath
 
 # The validated options of enhance_file / enhance_folder (SuperResolver._options), each None where it is off: the output stage,
 # the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, the album (loudness_scope 'folder')
@@ -30,13 +23,21 @@ def _set(**keywords):
 _Options = namedtuple('_Options', 'stage tp lim spec loud bw st rc album flac sl', defaults=(None, None))
 
 # The keys a folder record may carry behind the eight it always has (and 'written'), in the record's order; each is also the key
-# of enhance_file's result that fills it ('album': enhance_album's own).
+# of enhance_file's result that fills it ('album': enhance_album's own).  Which of them a run has: SuperResolver._present.
 _RECORD_KEYS = ('metrics_ext', 'output', 'spectrogram', 'loudness', 'speech_level', 'album', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'norm', 'flac')
 
+# The same keys (but the album's) in the order enhance_file's result carries them behind the five it always has.
+_RESULT_KEYS = ('norm', 'spectrogram', 'loudness', 'speech_level', 'bandwidth', 'crossover', 'stereo', 'output_rate', 'metrics_ext', 'output', 'flac')
 
-# One clip between the parts of enhance_lr / enhance_lr_many: `x` the [C, L] clip the rows are gathered from (mid and side with
-# stereo 'ms'), its segment plan, and `measured` -- the auto crossover's measurement on the device and the event behind it, or None.
-_Clip = namedtuple('_Clip', 'x C L S stride ms measured')
+# The measurements that ride back with the payload: `key` of the result, of a record, of _write's keyword and of the pinned slot;
+# `field` of _Options; the method that queues the device work (-> a dict with 'packed') and the one that reads what _fetch brought
+# back.  `levels`: False -- taken in _reports on (lr, generated, original); True -- taken in _level on (lr, generated), and its 'gain'
+# multiplies the clip unless the option's mode is 'report'.  `channels`: None, or the one written channel count it is taken at.
+_Measured = namedtuple('_Measured', 'key field measure result levels channels')
+_MEASURED = (_Measured('bandwidth', 'bw', '_measure_bandwidth', '_bandwidth_result', False, None),
+             _Measured('stereo', 'st', '_measure_stereo', '_stereo_result', False, 2),
+             _Measured('speech_level', 'sl', '_measure_speech_level', '_speech_level_result', True, None),
+             _Measured('loudness', 'loud', '_measure_loudness', '_loudness_result', True, None))
 
 
 class _File:
@@ -84,7 +85,12 @@ def spectrogram_image(rows, top_db=None, **plan):
     return _spectrogram(rows, top_db, check_spectrogram(top_db=top_db, who="spectrogram_image", **plan))[0]
 
 
-class SuperResolver:
+def _named(local):
+    """The locals of an entry point -> those that are options of SuperResolver._options, by name."""
+    return {name: local[name] for name in _OPTION_NAMES if name in local}
+
+
+class SuperResolver(ClipPath, FilePath):
     """`model`: anything with `.inference(lr_audio, inst, noise=None) -> (sr_spectro, lr_pha, norm_param, lr_spectro)`
     (Pix2PixHDModel); its `mdct_type` picks the inverse transform.  `overlap`: shared fraction of a segment, [0, 0.5].
     `batch`: segments per group (default opt.batchSize).  `graph`: capture the chain of a full group once and replay it
@@ -139,546 +145,6 @@ class SuperResolver:
     beyond what the generator itself does with it; a silent segment is written as silence.  No pre-pass, no held noise.
     `last_norm` then holds the [C, S, 2] tensor on the GPU of the latest call's (min, max) per segment, in dB."""
 
-    # what an object built without __init__ (the stubs of the host tests) runs with: every option of the constructor off
-    stereo, norm_scope, crossover_auto, last_norm, last_crossover = 'lr', 'group', False, None, None
-    segment_norm = False
-
-    def __init__(self, model, opt, overlap=0.25, batch=None, graph=True, reference_amplitude=None, lowband='model',
-                 lowband_fade=0, crossover=None, crossover_hz=None, crossover_taps=None, stereo='lr', norm_scope='group',
-                 segment_norm=False):
-        from ..models.mdct import IMDCT2, IMDCT4
-        from ..util import util as U
-        self.model, self.opt = model, opt
-        self.T = int(opt.segment_length)
-        self.overlap = float(overlap)
-        segment_plan(0, self.T, self.overlap)                               # validates both
-        self.norm_scope = check_norm_scope(norm_scope)
-        self.segment_norm = check_segment_norm(segment_norm, self.norm_scope)
-        self.last_norm = None                             # 'clip': [C, 2] on the GPU, the latest call's ranges; segment_norm: [C, S, 2]
-        self._rows = None                                                   # segment_norm: the [batch, 8] table of the latest eager group
-        self.batch = int(batch if batch is not None else getattr(opt, 'batchSize', 1))
-        if self.batch < 1:
-            raise ValueError("SuperResolver: batch must be >= 1, got %d" % self.batch)
-        self.graph = bool(graph)
-        self.device = torch.device(getattr(model, 'device', None) or 'cuda')
-        self.up_ratio = opt.hr_sampling_rate / opt.lr_sampling_rate
-        self.mdct_type = getattr(model, 'mdct_type', None) or getattr(opt, 'mdct_type', None) or 'mdct4'
-        kw = dict(window=U.kbdwin, win_length=opt.win_length, hop_length=opt.hop_length, n_fft=opt.n_fft,
-                  center=getattr(opt, 'center', True), out_length=self.T, device=self.device)
-        if self.mdct_type == 'mdct2':
-            from ..dct.dct import IDCT
-            self._imdct = IMDCT2(idct_op=IDCT(), **kw)                      # generate_audio.py:23-25
-        elif self.mdct_type == 'mdct4':
-            self._imdct = IMDCT4(**kw)
-        else:
-            raise ValueError("SuperResolver: mdct_type must be 'mdct2' or 'mdct4', got %r" % (self.mdct_type,))
-        if self.up_ratio < 1:
-            raise ValueError("SuperResolver: lr_sampling_rate above hr_sampling_rate")
-        self.lowband, self.lowband_fade, _ = check_lowband(lowband, lowband_fade, spectro_bins(opt.n_fft, self.mdct_type), self.up_ratio)
-        # Both inverse transforms return x for the spectrogram of x and util.imdct halves that (util/util.py:127 of the
-        # reference), so the hand-composed chain is a factor 2 short of generate_audio.py:47's sqrt(up_ratio - 1) * x; the
-        # stitch gain puts the factor back.  The reference's own output (MDCT2, back-to-back segments; tests/golden/generate.npz)
-        # carries the halving, and overlap = 0 is the mode that reproduces the reference bit for bit: there -- and only for
-        # mdct2, nothing of the reference runs MDCT4 -- the factor is left out, unless the caller decides otherwise.
-        if reference_amplitude is None:
-            reference_amplitude = self.overlap == 0.0
-        self.reference_amplitude = bool(reference_amplitude) and self.mdct_type == 'mdct2'
-        self.gain = math.sqrt(self.up_ratio - 1) * (1.0 if self.reference_amplitude else 2.0)
-        # The inverse-transform chain returns x / 2 for the spectrogram of x and the stitch multiplies by `gain`: a signal the
-        # generator passes through comes out as (gain / 2) * x, with or without reference_amplitude -- the level the input enters
-        # the crossover at.
-        self.crossover, self.crossover_hz, self.crossover_taps = crossover, crossover_hz, crossover_taps
-        self.crossover_plan = check_crossover(crossover, crossover_hz, crossover_taps, opt.hr_sampling_rate, opt.lr_sampling_rate)
-        self._xover_taps = None                                             # the coefficients on the device, filled at first use
-        self.crossover_auto = crossover == 'input' and crossover_hz == CROSSOVER_AUTO
-        self._xover_auto = {}                                               # k_top -> (plan, edge, the coefficients on the device)
-        self._side = None                                                   # the stream the auto crossover's measurement comes back on
-        self.last_crossover = None                                          # auto: {'hz', 'taps', 'edge_hz'} of the latest clip
-        self.stereo = check_stereo(stereo)
-        self._g = None                                                      # captured chain of a full group
-        self._pins = {}                                                     # pinned host buffers of the file path, grow-only
-
-    # -- one group ---------------------------------------------------------------------------------
-    def noise_shape(self, b):
-        """Shape of the mask noise `inference` draws for a group of b segments (the model's `mask_noise_shape`), or None when
-        the model draws none."""
-        f = getattr(self.model, 'mask_noise_shape', None)
-        return f(b, self.T) if callable(f) else None
-
-    def _graph_ok(self):
-        """Random draws must stay outside the graph, or replay would repeat them: the mask noise is handed in, but mask_mode
-        'mode1' draws signs and the single-channel phase encodings draw phase noise inside to_spectro.  Those options run eagerly."""
-        o = self.opt
-        if getattr(o, 'mask', False) and getattr(o, 'mask_mode', None) == 'mode1':
-            return False
-        if not getattr(o, 'explicit_encoding', False):
-            return getattr(o, 'phase_encoding_mode', None) in (None, 'scale') and self.up_ratio <= 1     # (util.imdct's random sign)
-        return True
-
-    def _group(self, seg, noise, norm=None):
-        """[b, T] low-rate segments -> [b, T] generated ones, before the sqrt(up_ratio - 1) gain (generate_audio.py:34-44).
-        `norm`: None (norm_scope 'group': the model is called as ever), the clip's norm8, or 'rows' (segment_norm: every row
-        its own range; the group's [b, 8] table is left in self._rows)."""
-        from ..util import util as U
-        if norm is None:
-            sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise)
-        else:
-            sr_spectro, lr_pha, norm_param, lr_spectro = self.model.inference(seg, None, noise=noise, norm=norm)
-        if isinstance(norm, str):
-            self._rows = norm_param['rows']
-        splice = {} if self.lowband == 'model' else dict(lr_spectro=lr_spectro, lowband_fade=self.lowband_fade)
-        audio = U.imdct(spectro=sr_spectro.abs(), pha=lr_pha.squeeze(1), norm_param=norm_param, _imdct=self._imdct,
-                        up_ratio=self.up_ratio, explicit_encoding=bool(getattr(self.opt, 'explicit_encoding', False)), **splice)
-        audio = audio.reshape(seg.shape[0], -1)
-        if audio.shape[1] != self.T:
-            raise ValueError("SuperResolver: segment_length %d does not come back from the transform (got %d samples): use "
-                             "a multiple of hop_length" % (self.T, audio.shape[1]))
-        return audio
-
-    def _run_graphed(self, seg, noise, norm=None):
-        """The chain of a full group through a graph over static buffers.  The first use runs the chain once eagerly on the
-        buffers (packed weights, tables and workspaces exist before capture), then captures it; every use replays.  Weights
-        that changed since (load_network, an optimiser step) make the capture stale: it is redone.  `norm` (norm_scope 'clip'):
-        the clip's norm8, copied into a static buffer the captured encode and decode read; 'rows' (segment_norm) is handed on as
-        it is, and the table the captured encode writes is kept as g['rows']."""
-        from .. import _ops
-        g = self._g
-        by_rows = isinstance(norm, str)
-        if g is None or g['epoch'] != _ops._WEIGHT_EPOCH[0]:
-            shape = self.noise_shape(self.batch)
-            g = self._g = {'epoch': _ops._WEIGHT_EPOCH[0], 'graph': None, 'out': None,
-                           'seg': torch.empty((self.batch, self.T), dtype=torch.float32, device=self.device),
-                           'noise': None if shape is None else torch.empty(shape, dtype=torch.float32, device=self.device),
-                           'norm': norm if norm is None or by_rows else torch.empty((8,), dtype=torch.float32, device=self.device)}
-        g['seg'].copy_(seg)
-        if g['norm'] is not None and not by_rows:
-            g['norm'].copy_(norm)
-        if g['noise'] is not None:
-            g['noise'].copy_(noise)
-        if g['graph'] is None:
-            self._group(g['seg'], g['noise'], g['norm'])
-            torch.cuda.synchronize()
-            # as _train_step_graphed captures: a side stream behind the current (step) stream, thread-local capture mode,
-            # no flush of the caching allocator
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.stream(side):
-                graph.capture_begin(capture_error_mode="thread_local")
-                g['out'] = self._group(g['seg'], g['noise'], g['norm'])
-                graph.capture_end()
-            torch.cuda.current_stream().wait_stream(side)
-            g['graph'] = graph
-            if by_rows:
-                g['rows'] = self._rows
-        g['graph'].replay()
-        return g['out']
-
-    def _group_rows(self, seg, noise):
-        """segment_norm: one full group, [batch, T] -> (the generated [batch, T], the group's [batch, 8] table of ranges on the
-        device), through the graph where the chain may be captured."""
-        if self.graph and self._graph_ok():
-            return self._run_graphed(seg, noise, 'rows'), self._g['rows']
-        return self._group(seg, noise, 'rows'), self._rows
-
-    def _walk_rows(self, seg, out, noise, C, S):
-        """segment_norm: the C * S channel-major rows of `seg` through _group_rows in groups of `batch`, without regard to channel
-        (plans.group_rows_plan); the last group is filled up with rows of zeros (and zeros for their rows of a given `noise`), whose
-        output is dropped.  Leaves `out` filled and `last_norm` [C, S, 2]; nothing is waited for."""
-        R = seg.shape[0]
-        ranges = torch.empty((R, 2), dtype=torch.float32, device=seg.device)
-        shape = self.noise_shape(self.batch)
-        for r0, n in group_rows_plan(R, self.batch):
-            rows = seg[r0:r0 + n]
-            fill = self.batch - n
-            if fill:
-                rows = torch.cat((rows, rows.new_zeros((fill, rows.shape[1]))))
-            nz = None
-            if shape is not None:
-                if noise is None:
-                    nz = torch.randn(shape, device=self.device)
-                else:
-                    nz = noise[r0:r0 + n]
-                    if tuple(nz.shape) != (n,) + tuple(shape[1:]):
-                        raise ValueError("enhance_lr: noise for rows %d..%d has shape %s, expected %s"
-                                         % (r0, r0 + n - 1, tuple(nz.shape), (n,) + tuple(shape[1:])))
-                    if fill:
-                        nz = torch.cat((nz, nz.new_zeros((fill,) + tuple(shape[1:]))))
-            audio, table = self._group_rows(rows, nz)
-            out[r0:r0 + n].copy_(audio[:n])
-            ranges[r0:r0 + n].copy_(table[:n, :2])
-        self.last_norm = ranges.view(C, S, 2)
-
-    # -- one clip ----------------------------------------------------------------------------------
-    def enhance_lr(self, lr_audio, noise=None):
-        """lr_audio: [C, L] or [L] on the GPU, already at the high rate -> the generated clip [C, L] ([1, L] for [L]).  Every
-        channel is a clip of its own: its S segments are grouped as if it were a mono clip, so
-        enhance_lr(x)[c] == enhance_lr(x[c:c+1])[0] given the same noise rows.  `noise`: the mask noise of all C * S segments,
-        [C * S, channels, mask_rows, frames], channel-major, sliced per group; drawn per group (one torch.randn) when absent.
-        With norm_scope 'clip' the property holds as well, and a channel's range is taken in front of its first group: its S
-        segments go through model.clip_norm, the channel's rows of `noise` are folded as they are, and without `noise` the mask
-        noise of the channel is drawn in one torch.randn of [S, channels, mask_rows, frames] -- the range of the noise must be
-        known before the first group is encoded --, which holds S / batch times the memory of a group's draw for the length of the
-        channel: 4 * channels * mask_rows * frames bytes per segment, the (1 - 1 / up_ratio) part of a segment's encoded spectrogram.
-        With segment_norm the property holds too, at every batch size, although the C * S rows share groups (_walk_rows): a row's
-        encode and decode see that row alone, and what the generator itself does with its batch is all that is left."""
-        run = getattr(self.model, '_on_step_stream', None)
-        with torch.no_grad():
-            return run(self._enhance_lr, lr_audio, noise) if callable(run) else self._enhance_lr(lr_audio, noise)
-
-    def _before_rows(self, lr_audio):
-        """In front of the rows, per clip: the checks, the auto crossover's measurement and its event, the mid/side encode -> the
-        _Clip the rows and _behind_rows go on with."""
-        x = lr_audio.to(self.device).float()
-        if x.dim() == 1:
-            x = x[None]
-        if x.dim() != 2 or x.shape[0] < 1:
-            raise ValueError("enhance_lr: expected a [C, L] or [L] waveform, got shape %s" % (tuple(lr_audio.shape),))
-        x = x.contiguous()
-        C, L = x.shape
-        S, stride, V = segment_plan(L, self.T, self.overlap)
-        ms = self.stereo == 'ms' and C != 1               # (one channel runs as ever, with no launch of the family)
-        if ms and C != 2:
-            raise ValueError("enhance_lr: stereo='ms' takes one or two channels, got %d" % C)
-        measured = None
-        if self.crossover_auto:
-            # the two measurement launches and their event go in front of every group: the host then waits for them alone
-            measured = (_bandwidth(x, float(self.opt.hr_sampling_rate)), torch.cuda.Event())
-            measured[1].record()
-        if ms:
-            # behind the auto crossover's measurement, which stays on left / right: its plan is the one 'lr' gets.  From here on the
-            # two rows are mid and side -- the segments, the groups' normalisation, the mask-noise row blocks and the crossover's
-            # low band (a linear filter commutes with the matrix)
-            x = stereo_matrix(x, 0.5)
-        return _Clip(x, C, L, S, stride, ms, measured)
-
-    def _behind_rows(self, clip, sr):
-        """Behind the rows, per clip: the stitched [C, L] -> the crossover, fixed or auto, and the mid/side decode."""
-        if self.crossover_plan is not None:
-            if clip.measured is not None:
-                taps = self._auto_taps(*clip.measured)
-            else:
-                if self._xover_taps is None:
-                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
-                taps = self._xover_taps
-            sr = crossover(sr, clip.x, self.gain / 2.0, taps)
-        if clip.ms:
-            # back to left / right, in place.  A side signal of digital silence (dual mono) leaves the chain as NaN -- its group is
-            # scaled by 1 / (max - min) --: the decoder reads a non-finite side sample as "no side here"
-            sr = sr.contiguous()
-            stereo_matrix(sr, 1.0, guard_side=True, out=sr)
-        return sr
-
-    def enhance_lr_many(self, clips, noise=None):
-        """clips: a list of [C_i, L_i] (or [L_i]) waveforms on the GPU, already at the high rate -> the list of generated clips
-        [C_i, L_i]: enhance_lr on each, with the rows of all of them -- R = sum of C_i * S_i, clip after clip, each channel-major --
-        sharing groups.  Needs segment_norm (a ValueError otherwise): only there does a row not depend on its neighbours.  Each clip
-        goes through enhance_lr's part in front of the rows; one ragged gather (ops.segments_gather_ragged) lays all rows out, the
-        one walk of _walk_rows takes them through ceil(R / batch) full groups with fillers in the last group only, one ragged
-        stitch (ops.segments_stitch_ragged) brings every clip back, and each goes through enhance_lr's part behind the rows.  A
-        clip's rows, ranges and stitch are bit for bit those of enhance_lr on it alone; what the generator itself does with a
-        row's neighbours in the batch is all that differs.  `noise`: the mask noise of all R rows in that order, [R, channels,
-        mask_rows, frames]; drawn per group (one torch.randn) when absent.  `last_norm` then holds a list of [C_i, S_i, 2] views,
-        and with crossover_hz 'auto' `last_crossovers` the list of every clip's {'hz', 'taps', 'edge_hz'}."""
-        if not self.segment_norm:
-            raise ValueError("enhance_lr_many: the rows of several clips share groups, which needs segment_norm=True")
-        clips = list(clips)
-        if not clips:
-            return []
-        run = getattr(self.model, '_on_step_stream', None)
-        with torch.no_grad():
-            return run(self._enhance_lr_many, clips, noise) if callable(run) else self._enhance_lr_many(clips, noise)
-
-    def _enhance_lr_many(self, clips, noise):
-        fronts = [self._before_rows(c) for c in clips]
-        seg = segments_gather_ragged([f.x for f in fronts], self.T, fronts[0].stride, [f.S for f in fronts])
-        out = torch.empty_like(seg)
-        self._walk_rows(seg, out, noise, 1, seg.shape[0])
-        ranges, views, at = self.last_norm[0], [], 0
-        for f in fronts:
-            views.append(ranges[at:at + f.C * f.S].view(f.C, f.S, 2))
-            at += f.C * f.S
-        self.last_norm = views
-        stitched = segments_stitch_ragged(out, [f.L for f in fronts], [f.C for f in fronts], fronts[0].stride, self.gain)
-        done, self.last_crossovers = [], []
-        for f, sr in zip(fronts, stitched):
-            done.append(self._behind_rows(f, sr))
-            self.last_crossovers.append(dict(self.last_crossover) if self.crossover_auto else None)
-        return done
-
-    def _enhance_lr(self, lr_audio, noise):
-        clip = self._before_rows(lr_audio)
-        x, C, L, S, stride = clip.x, clip.C, clip.L, clip.S, clip.stride
-        seg = segments_gather_planar(x, self.T, stride, S)
-        out = torch.empty_like(seg)
-        by_clip = self.norm_scope == 'clip'
-        if by_clip:
-            self.last_norm = torch.empty((C, 2), dtype=torch.float32, device=self.device)
-            if S == 0:                                                      # (no segment, no range: the empty fold)
-                self.last_norm[:, 0] = float('inf')
-                self.last_norm[:, 1] = float('-inf')
-        if self.segment_norm:
-            self._walk_rows(seg, out, noise, C, S)
-        for c in range(0 if self.segment_norm else C):                      # (segment_norm: the rows have been walked, above)
-            norm = drawn = None
-            if by_clip and S > 0:
-                # the channel's range, in front of its first group; the noise every group of it will be given is folded with it
-                shape = self.noise_shape(S)
-                if shape is not None:
-                    drawn = noise[c * S:(c + 1) * S] if noise is not None else torch.randn(shape, device=self.device)
-                    if tuple(drawn.shape) != shape:
-                        raise ValueError("enhance_lr: noise for channel %d has shape %s, expected %s" % (c, tuple(drawn.shape), shape))
-                norm = self.model.clip_norm(seg[c * S:(c + 1) * S], noise=drawn, rows=self.batch)
-                self.last_norm[c].copy_(norm[:2])
-            for s0 in range(0, S, self.batch):
-                b = min(self.batch, S - s0)
-                r0 = c * S + s0
-                shape = self.noise_shape(b)
-                nz = None
-                if shape is not None:
-                    if drawn is not None:
-                        nz = drawn[s0:s0 + b]
-                    else:
-                        nz = noise[r0:r0 + b] if noise is not None else torch.randn(shape, device=self.device)
-                    if tuple(nz.shape) != shape:
-                        raise ValueError("enhance_lr: noise for segments %d..%d of channel %d has shape %s, expected %s"
-                                         % (s0, s0 + b - 1, c, tuple(nz.shape), shape))
-                extra = () if norm is None else (norm,)
-                if self.graph and b == self.batch and self._graph_ok():
-                    out[r0:r0 + b].copy_(self._run_graphed(seg[r0:r0 + b], nz, *extra))
-                else:
-                    out[r0:r0 + b].copy_(self._group(seg[r0:r0 + b], nz, *extra))
-        return self._behind_rows(clip, segments_stitch_planar(out, C, stride, self.gain, L))
-
-    def _auto_taps(self, res_dev, event):
-        """crossover_hz 'auto': the clip's measurement (ops.bandwidth's 32 bytes on the device, `event` recorded behind it) -> the
-        coefficients of the clip's crossover on the device.  The copy runs on a side stream behind the event and the host waits
-        for that copy alone: the groups queued since are not waited for."""
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        pin = self._pinned('xover_auto', 32)[:32]
-        self._side.wait_event(event)
-        with torch.cuda.stream(self._side):
-            pin.copy_(res_dev.view(torch.uint8), non_blocking=True)
-            done = torch.cuda.Event()
-            done.record()
-        done.synchronize()
-        k_top = int(pin.view(torch.float64)[0])
-        entry = self._xover_auto.get(k_top)
-        if entry is None:
-            hr_rate, nyquist = float(self.opt.hr_sampling_rate), float(self.opt.lr_sampling_rate) / 2.0
-            edge = nyquist if k_top < 0 else min(nyquist, k_top * hr_rate / BANDWIDTH_DEFAULTS['n_fft'])
-            plan, edge = crossover_auto_plan(hr_rate, self.opt.lr_sampling_rate, edge, self.crossover_taps)
-            if plan == self.crossover_plan:                                 # the band reaches the Nyquist frequency: the fixed crossover's table
-                if self._xover_taps is None:
-                    self._xover_taps = crossover_coefficients(*self.crossover_plan).to(self.device)
-                taps = self._xover_taps
-            else:
-                taps = crossover_coefficients(*plan).to(self.device)
-            entry = self._xover_auto[k_top] = (plan, edge, taps)
-        plan, edge, taps = entry
-        self.last_crossover = {'hz': plan[1] * float(self.opt.hr_sampling_rate), 'taps': plan[0], 'edge_hz': edge}
-        return taps
-
-    # -- files -------------------------------------------------------------------------------------
-    def _pinned(self, slot, nbytes):
-        """Grow-only pinned byte buffer `slot`, free to be overwritten: the copy that last read it has finished.  Allocating
-        one goes through the HIP runtime: call from the thread that owns the device."""
-        t, busy = self._pins.get(slot, (None, None))
-        if busy is not None:
-            busy.synchronize()
-        if t is None or t.numel() < nbytes:
-            t = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, pin_memory=True)
-        self._pins[slot] = (t, None)
-        return t
-
-    def _read(self, path, slot='in0', verify=False):
-        """Host I/O only: the file's data chunk into pinned buffer `slot` -> (the bytes as a host tensor, WavInfo).  A file whose
-        first bytes say FLAC (data/audiofile.py) goes through _read_flac instead; `verify` is its.  A coded data chunk (G.711, IMA
-        ADPCM: wavio.CODED_TAGS) is read as it stands; an IMA block header with a step index above 88 is a ValueError here.  An
-        AIFF, AU or SPHERE file (data/containers.py) brings its sound data as it stands and a containers.AudioInfo."""
-        from ..data import audiofile, containers, wavio
-        kind = audiofile.kind(path)
-        if kind == 'flac':
-            return self._read_flac(path, slot, verify)
-        if kind != 'wav':                                                   # AIFF, AU, SPHERE: the sound data as it stands, an AudioInfo
-            payload, meta = containers.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
-            return self._pins[slot][0][:len(payload)], meta, slot
-        payload, meta = wavio.read_payload(path, into=lambda n: self._pinned(slot, n).numpy())
-        if meta.format_tag == 0x11:                                         # IMA ADPCM: the block headers, before the copy (names file and block)
-            wavio.ima_scan(payload, meta.num_channels, meta.block_align, os.fspath(path))
-        return self._pins[slot][0][:len(payload)], meta, slot
-
-    def _read_flac(self, path, slot, verify=False):
-        """Host work only: the whole FLAC file into pinned buffer `slot`, its frame index built on the host (every CRC verified;
-        anything the reader does not hold is a ValueError here, before a launch) and laid behind the bytes at the next multiple of
-        8 -> (bytes and table as one host tensor, FlacInfo): one copy takes both to the device.  `verify`: the file is first decoded
-        on the host and its MD5 compared with STREAMINFO's.  The slot remembers the file's name for _decode's error text."""
-        from ..data import flacio
-        if verify and flacio.verify(path) is False:
-            raise ValueError("%s: the decoded samples do not have the MD5 that STREAMINFO states" % path)
-        # room for the table of a file whose frames average 768 bytes or more; a file of smaller frames moves to a larger buffer once
-        payload, meta, table = flacio.read_file(path, into=lambda n: self._pinned(slot, n + n // 16 + 4096).numpy())
-        n = len(payload)
-        at = (n + 7) & ~7
-        pinned = self._pins[slot][0]
-        if pinned.numel() < at + table.nbytes:
-            grown = torch.empty((at + table.nbytes,), dtype=torch.uint8, pin_memory=True)
-            grown[:n].copy_(pinned[:n])
-            self._pins[slot] = (grown, None)
-            pinned = grown
-        pinned[n:at].zero_()
-        pinned[at:at + table.nbytes].copy_(torch.from_numpy(table).view(-1).view(torch.uint8))
-        if not hasattr(self, '_pin_names'):
-            self._pin_names = {}
-        self._pin_names[slot] = os.fspath(path)
-        return pinned[:at + table.nbytes], meta, slot
-
-    def _decode(self, host, meta, slot):
-        """The host bytes of a data chunk -> [channels, frames] f32 on the GPU: one copy, one kernel -- the PCM decoder's, or for a
-        coded chunk (meta.format_tag 6, 7, 0x11) one of the family "wavcodec".  The bytes and table of a
-        FLAC file (_read_flac): one copy, the two kernels of the family "flac", and one wait for their status word -- a frame that
-        passed the index's CRCs and still does not decode is a ValueError that names it, before anything else is launched."""
-        if host.numel() == 0:
-            return torch.zeros((meta.num_channels, 0), dtype=torch.float32, device=self.device)
-        dev = torch.empty((host.numel(),), dtype=torch.uint8, device=self.device)
-        dev.copy_(host, non_blocking=True)
-        busy = torch.cuda.Event()
-        busy.record()
-        self._pins[slot] = (self._pins[slot][0], busy)
-        if hasattr(meta, 'num_flac_frames'):
-            at = host.numel() - meta.num_flac_frames * 48
-            try:
-                return flac_decode(dev[:at], dev[at:].view(torch.int64).view(-1, 6), meta)
-            except ValueError as e:                                         # (the decoder's refusal, with the file it is about)
-                raise ValueError("%s: %s" % (getattr(self, '_pin_names', {}).get(slot, '<flac>'), e)) from None
-        if meta.format_tag in (6, 7):                                       # G.711 A-law / mu-law (csrc/wavcodec.hip)
-            return g711_decode(dev, meta.num_frames, meta.num_channels, 'alaw' if meta.format_tag == 6 else 'ulaw')
-        if meta.format_tag == 0x11:                                         # IMA ADPCM; _read has scanned the block headers
-            return ima_decode(dev, meta.num_frames, meta.num_channels, meta.block_align)
-        if getattr(meta, 'big_endian', False) or getattr(meta, 'signed8', False):     # an AudioInfo (data/containers.py)
-            return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample, big_endian=meta.big_endian,
-                              signed8=meta.signed8)
-        return pcm_decode(dev, meta.num_frames, meta.num_channels, meta.format_tag, meta.bits_per_sample)
-
-    def _write(self, path_out, sr, encoding, stage=None, picture=None, loudness=None, speech_level=None, true_peak=None, limiter=None, bandwidth=None, stereo=None, rate=None,
-               flac=None):
-        """[C, L] on the GPU -> encoded on the device -> one copy back -> header + payload; -> the result's 'output', or None
-        without a stage.  path_out None: the figures only.  `stage`: the output-stage options (check_output_options), or None for
-        the encoder alone.  Every other keyword is None or what one option of enhance_file brings, and a caller passes only those
-        that are set (_set):
-          true_peak, limiter   the option's own dict, one file's (check_true_peak, _limiter_option; either comes with a stage):
-                               _encode runs its kernels and leaves their packed figures in it, _output reads them
-          loudness, speech_level, bandwidth, stereo   the measurement the per-file flow has already queued (_measure_*), a dict with 'packed'
-          picture              the rendered spectrogram (_render_picture)
-          rate                 the rate the header states where it is not the model's (the output-rate option: `sr` is converted)
-          flac                 the container option's own dict, one file's (check_container): the payload goes through the FLAC
-                               encoder on the device (_flac_stage) and the stream comes back in its place; it gains 'result'
-        The first six come back with the payload and the peak figures behind _fetch's one synchronisation."""
-        w = sr.contiguous()
-        option = _set(true_peak=true_peak, limiter=limiter)
-        dev, packed = (None, None) if path_out is None and stage is None else self._encode(w, path_out is not None, encoding, stage, **option)
-        extra = {}
-        if dev is not None and flac is not None:
-            dev, extra = self._flac_stage(dev, w.shape[0], encoding, flac, **_set(rate=rate))
-        host, stats = self._fetch(dev, packed, **_set(stereo=stereo, bandwidth=bandwidth, limiter=limiter, true_peak=true_peak, loudness=loudness, speech_level=speech_level,
-                                                      picture=picture), **extra)
-        output = None if stats is None else self._output(stats, w.shape[0], stage, path_out, encoding, **option)
-        if host is not None:
-            self._save(path_out, host, sr.shape[0], encoding, **_set(rate=rate, flac=flac))
-        return output
-
-    def _flac_stage(self, dev, channels, encoding, flac, rate=None):
-        """The payload on the device -> (the FLAC frames on the device at their worst-case size, what _fetch brings back beside
-        them): three launches of the family "flacenc".  `flac`: one file's container option, which gains what _save needs: the
-        frame lengths ('lengths', a dict whose 'packed' _fetch replaces by its host copy), with md5 the payload itself ('pcm',
-        likewise: a second copy of the payload's size), 'pcm_bytes', 'total' and 'rate'."""
-        bits = {'pcm16': 16, 'pcm24': 24}[encoding]
-        rate = int(self.opt.hr_sampling_rate if rate is None else rate)
-        stream, lengths = flac_encode(dev, channels, bits, rate, flac['block'], **_set(lpc_order=flac.get('lpc')))
-        flac.update(lengths={'packed': lengths.view(torch.uint8)}, pcm_bytes=dev.numel(), total=dev.numel() // (channels * bits // 8), rate=rate, bits=bits)
-        extra = {'flac': flac['lengths']}
-        if flac['md5']:
-            flac['pcm'] = extra['flac_pcm'] = {'packed': dev}
-        return stream, extra
-
-    def _encode(self, w, wanted, encoding, stage, true_peak=None, limiter=None):
-        """The device work of _write -> (the payload, or None when no file is `wanted`; the packed peak buffer, or None).
-        `true_peak`: None, or the true-peak option, which gains 'packed' (the packed true-peak buffer on the device); the guard's
-        gain is then the true-peak kernel's.  `limiter`: None, or the limiter option, which gains 'packed' (12 bytes on the device:
-        the curve's statistics, then the true peak the clip came with); the two launches of the family "limiter" run first and the
-        peak kernels, the guard's gain and the encoder see the limited clip."""
-        if stage is None:
-            return pcm_encode(w, encoding), None
-        if limiter is not None:
-            packed = limiter['packed'] = torch.empty((12,), dtype=torch.uint8, device=w.device)
-            r, _ = limiter_envelope(w, limiter['rate'], limiter['ceiling'], peak_out=packed[8:].view(torch.float32))
-            w, _, _ = limiter_apply(w, r, limiter, stats_out=packed[:8], want_g=False)
-        (_, _, _, gain), packed = _pcm_peaks_packed(w, encoding, stage['ceiling'], "enhance_file")
-        if true_peak is not None:
-            (_, gain), true_peak['packed'] = _true_peaks_packed(w, true_peak['rate'], true_peak['ceiling'], "enhance_file")
-        if not wanted:
-            return None, packed
-        return pcm_encode(w, encoding, gain=gain if stage['clip'] == 'guard' else None, dither=stage['dither'], seed=stage['seed'],
-                          curve=stage.get('curve'), chunk=stage.get('chunk')), packed
-
-    def _fetch(self, dev, packed, picture=None, **measured):
-        """The payload and the packed peak buffer (either may be None) into their pinned buffers 'out' and 'peaks' behind one
-        synchronisation -> (the payload, the peak buffer) on the host.  `measured`: name -> a dict whose 'packed' (a device tensor:
-        the figures of 'stereo', 'bandwidth', 'limiter', 'true_peak', 'loudness', 'speech_level') is copied into the pinned buffer of that name in
-        front of them, in the order given, and replaced by its host copy.  `picture`: None, or a dict whose 'image' and 'top' are
-        copied and replaced likewise, into one buffer: the top's four bytes, then the pixels."""
-        host = stats = None
-        for name, m in measured.items():
-            n = m['packed'].numel()
-            pin = self._pinned(name, n)[:n]
-            pin.copy_(m['packed'], non_blocking=True)
-            m['packed'] = pin
-        if picture is not None:
-            img, top = picture['image'], picture['top']
-            n = img.numel()
-            pin = self._pinned('picture', 4 + n)
-            pin[:4].copy_(top.view(torch.uint8), non_blocking=True)
-            pin[4:4 + n].copy_(img.reshape(-1), non_blocking=True)
-            picture['image'], picture['top'] = pin[4:4 + n].view(img.shape), pin[:4].view(torch.float32)
-        if dev is not None:
-            host = self._pinned('out', dev.numel())[:dev.numel()]
-            host.copy_(dev, non_blocking=True)
-        if packed is not None:
-            stats = self._pinned('peaks', packed.numel())[:packed.numel()]
-            stats.copy_(packed, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return host, stats
-
-    @staticmethod
-    def _output(stats, C, stage, path_out, encoding, true_peak=None, limiter=None):
-        """The fetched peak buffer of a C-channel clip -> the result's 'output'; ClipError where clip 'error' finds a clipped sample.
-        `true_peak`: None, or the true-peak option with its fetched 'packed': the output gains 'true_peak' and 'true_peak_dbtp', its
-        'gain' is the true-peak kernel's, and clip 'error' also refuses a true peak above the encoding's limit.  `limiter`: None, or
-        the limiter option with its fetched 'packed': the output gains 'limiter', and every other figure is the limited clip's."""
-        peak, over, nonfinite, gain = (v.tolist() for v in _peak_views(stats, C))
-        if true_peak is not None:
-            tpeak, gain = (v.tolist() for v in _true_peak_views(true_peak['packed'], C))
-        output = {'peak': peak, 'peak_dbfs': [_dbfs(v) for v in peak], 'clipped': over, 'nonfinite': nonfinite,
-                  'gain': gain[0] if stage['clip'] == 'guard' else 1.0}
-        if true_peak is not None:
-            output.update(true_peak=tpeak, true_peak_dbtp=[_dbfs(v) for v in tpeak])
-            if stage['clip'] == 'error' and max(tpeak) > true_peak['limit']:
-                raise ClipError("%s: the true peak %+.2f dBTP is above the limit of %s (%d samples would clip); nothing was written -- "
-                                "clip='guard' scales the file down" % (path_out, max(output['true_peak_dbtp']), encoding, sum(over)))
-        if stage['clip'] == 'error' and any(over):
-            raise ClipError("%s: %d samples would clip in %s (peak %+.2f dBFS); nothing was written -- clip='guard' scales "
-                            "the file down, encoding='float32' keeps the samples"
-                            % (path_out, sum(over), encoding, max(output['peak_dbfs'])))
-        if limiter is not None:
-            gmin, count = _limiter_stats_views(limiter['packed'][:8])
-            output['limiter'] = {'lookahead': limiter['lookahead'], 'hold': limiter['hold'], 'max_reduction_db': _dbfs(float(gmin[0])),
-                                 'limited_samples': int(count[0]) & 0xFFFFFFFF,
-                                 'input_true_peak_dbtp': _dbfs(float(limiter['packed'][8:12].view(torch.float32)[0]))}
-        if stage['dither'] == 'shaped':
-            output['dither'] = {'kind': 'shaped', 'curve': stage['curve'], 'taps': shaper_coefficients(stage['curve']).numel(), 'chunk': stage['chunk']}
-        return output
-
     @staticmethod
     def _limiter_option(limiter, lookahead_ms, hold_ms, true_peak, stage, encoding, hr_rate, who):
         """check_limiter and check_true_peak for enhance_file / enhance_folder -> (stage, tp, lim): the limiter switches the
@@ -691,29 +157,23 @@ class SuperResolver:
             lim = {'lookahead': lim['lookahead'], 'hold': lim['hold'], 'rate': tp['rate'], 'ceiling': tp['ceiling']}
         return stage, tp, lim
 
-    def _save(self, path_out, host, channels, encoding, rate=None, flac=None):
-        """The one place that turns what _fetch brought back into a file: header + payload, or with `flac` (the container option
-        behind _flac_stage and _fetch) "fLaC", STREAMINFO and the frames' first lengths[-1] bytes; `flac` gains 'result'."""
-        from ..data import flacio, wavio
-        os.makedirs(os.path.dirname(os.path.abspath(path_out)), exist_ok=True)
-        if flac is not None:
-            lengths = flac['lengths']['packed'].clone().view(torch.int64).numpy()
-            md5 = hashlib.md5(flac['pcm']['packed'].numpy()).digest() if flac['md5'] else None
-            n = flacio.write_stream(path_out, host.numpy(), lengths, flac['rate'], channels, flac['bits'], flac['total'], flac['block'], md5)
-            flac['result'] = {'block': flac['block'], 'frames': len(lengths) - 1, 'bytes': n, 'pcm_bytes': flac['pcm_bytes'],
-                              'md5': None if md5 is None else md5.hex(), **_set(lpc=flac.get('lpc'))}
-            return
-        wavio.write_payload(path_out, host.numpy(), int(self.opt.hr_sampling_rate if rate is None else rate), channels, encoding)
-
-    @staticmethod
-    def _check_picture_channel(spec, channels, available):
-        """ValueError where the spectrogram option asks for a channel that is not among the written ones."""
-        if spec is None:
-            return
+    def _check_written_channels(self, o, channels, available):
+        """ValueError where an option does not take the channels that would be written of a file with `available`, before
+        anything of the file runs -- on the per-file path the file's refusal, in a folder a skipped file (_open) --, in this order:
+        the spectrogram's channel is not among them; stereo='ms' generates one or two; a FLAC stream holds 8; the speech level is
+        measured over SPEECH_LEVEL_MAX_CHANNELS."""
+        if o.spec is None and self.stereo != 'ms' and o.flac is None and o.sl is None:
+            return                                                          # (`channels` itself is refused by _front_clip: never a skipped file)
         k = select_channels(channels, available)
-        if spec['channel'] >= k:
+        if o.spec is not None and o.spec['channel'] >= k:
             raise ValueError("spectrogram_channel %d: the file has %d channel%s and channels=%r writes %d"
-                             % (spec['channel'], available, '' if available == 1 else 's', channels, k))
+                             % (o.spec['channel'], available, '' if available == 1 else 's', channels, k))
+        if self.stereo == 'ms' and k > 2:
+            raise ValueError("stereo='ms' takes one or two channels, %d would be written" % k)
+        if o.flac is not None and k > 8:
+            raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % k)
+        if o.sl is not None and k > SPEECH_LEVEL_MAX_CHANNELS:
+            raise ValueError("the active speech level is measured over at most %d channels, %d would be written" % (SPEECH_LEVEL_MAX_CHANNELS, k))
 
     @staticmethod
     def _render_picture(spec, lr, sr, hr):
@@ -839,11 +299,6 @@ class SuperResolver:
         return {'input': figures[0], 'output': figures[1], 'original': figures[2], 'split_hz': k * float(self.opt.hr_sampling_rate) / st['n_fft'],
                 'n_fft': st['n_fft'], 'hop': st['hop'], 'frames': measure['frames'], 'mode': mode, 'notes': stereo_notes(figures[1], mode)}
 
-    def _check_stereo_channels(self, channels, available):
-        """stereo='ms' generates one or two channels: a file of which more would be written is refused before anything runs."""
-        if self.stereo == 'ms' and select_channels(channels, available) > 2:
-            raise ValueError("stereo='ms' takes one or two channels, %d would be written" % select_channels(channels, available))
-
     @staticmethod
     def _output_rate_result(rc):
         """The output-rate option -> the result's 'output_rate'."""
@@ -862,14 +317,16 @@ class SuperResolver:
         K-weighting entry takes."""
         return loud if loud is None or rc is None else dict(loud, out_rate=check_loudness_rate(rc['rate'], who))
 
-    def _options(self, who, folder, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
+    def _options(self, who, folder, *, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
                  spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
                  loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                 album_cache_bytes=None, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
-                 speech_level_max_gain_db=None):
+                 container, flac_block, flac_md5, flac_lpc, speech_level, speech_level_max_gain_db, album_cache_bytes=None):
         """The options of enhance_file (`folder` False) / enhance_folder (True), validated before a file is opened -> _Options.
-        The order of the checks decides which ValueError a bad combination raises first: it does not move."""
+        Each is handed over under the name the entry point has it by (_named): none can take another's place, and one that is
+        left out is a TypeError.  The order of the checks decides which ValueError a bad combination raises first: it does not
+        move.  container None reads as 'wav'."""
         hr_rate = self.opt.hr_sampling_rate
+        container = 'wav' if container is None else container
         bw = check_bandwidth(bandwidth, bandwidth_opts, loudness_scope, who)
         st = check_stereo_report(stereo_report, stereo_report_opts, loudness_scope, who)
         stage = check_output_options(encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, who, dither_curve, dither_chunk)
@@ -902,14 +359,11 @@ class SuperResolver:
         host, meta, slot = read
         check_encoding(encoding, who)
         k = select_channels(channels, meta.num_channels)
-        self._check_picture_channel(o.spec, channels, meta.num_channels)
-        self._check_stereo_channels(channels, meta.num_channels)
-        if o.flac is not None and k > 8:
-            raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % k)
+        self._check_written_channels(o, channels, meta.num_channels)
+        # only here, not in _open: in a folder it ends the run where the other channel limits skip the file; the speech
+        # level, checked above, excludes loudness, so the two never compete for which comes first
         if o.loud is not None and k > LOUDNESS_MAX_CHANNELS:
             raise ValueError("loudness is measured over at most %d channels, %d would be written" % (LOUDNESS_MAX_CHANNELS, k))
-        if o.sl is not None and k > SPEECH_LEVEL_MAX_CHANNELS:
-            raise ValueError("the active speech level is measured over at most %d channels, %d would be written" % (SPEECH_LEVEL_MAX_CHANNELS, k))
         rate = meta.sample_rate
         raw = self._decode(host, meta, slot)[:k]
         lr = audio_dataset.lr_round_trip(raw, rate, self.opt.lr_sampling_rate, self.opt.hr_sampling_rate, is_lr_input)
@@ -918,13 +372,24 @@ class SuperResolver:
             lr = lr[..., :raw.shape[-1]]                                    # the round trip rounds the length up
         return lr, raw if has_hr else None, meta
 
+    def _measure(self, f, o, levels):
+        """The measurements of _MEASURED with this `levels` whose option is on, queued in the table's order -> key -> the
+        measurement.  One that is taken at one channel count only is left out for a file written with another."""
+        taken = {}
+        for m in _MEASURED:
+            option = getattr(o, m.field)
+            if m.levels != levels or option is None or m.channels not in (None, f.clip.shape[0]):
+                continue
+            taken[m.key] = getattr(self, m.measure)(option, f.lr, f.clip, *(() if levels else (f.hr,)))
+            if levels and option['mode'] != 'report':
+                f.clip = f.clip * taken[m.key]['gain']
+        return taken
+
     def _reports(self, f, o):
-        """(b) The bandwidth and the stereo measurement -> (band, image), None where off.  Both see the generated clip behind the
-        crossover and the mid/side decode and in front of the loudness gain: the figures are relative, a gain does not move them.
-        A file written with another channel count than two has no stereo image."""
-        band = None if o.bw is None else self._measure_bandwidth(o.bw, f.lr, f.clip, f.hr)
-        image = None if o.st is None or f.clip.shape[0] != 2 else self._measure_stereo(o.st, f.lr, f.clip, f.hr)
-        return band, image
+        """(b) The bandwidth and the stereo measurement -> key -> the measurement, for those that are on.  Both see the generated
+        clip behind the crossover and the mid/side decode and in front of the loudness gain: the figures are relative, a gain
+        does not move them.  A file written with another channel count than two has no stereo image."""
+        return self._measure(f, o, False)
 
     def _metrics(self, f, extended_metrics):
         """(c) Where the input is a full-band original: f.metrics, one 7-tuple per written channel, and with `extended_metrics`
@@ -938,56 +403,42 @@ class SuperResolver:
 
     def _level(self, f, o):
         """(d) The output rate, then the loudness or the speech-level measurement (the options exclude each other: one gain) and its
-        gain on f.clip -> (the loudness measurement, the speech-level measurement), None where off.  The converter
+        gain on f.clip -> key -> the measurement, for the one that is on.  The converter
         (one launch of the family "rateconv") sits behind everything that compares the generated clip with the input and the
         original at the model's rate; the loudness stage behind the metrics, which moment-match and stay those of the unscaled
         clip.  Both sit in front of everything that sees the written level."""
         if o.rc is not None:
             f.clip = rate_convert(f.clip, o.rc['model_rate'], o.rc['rate'], o.rc['plan'])
-        measure = speech = None
-        if o.sl is not None:
-            speech = self._measure_speech_level(o.sl, f.lr, f.clip)
-            if o.sl['mode'] != 'report':
-                f.clip = f.clip * speech['gain']
-        elif o.loud is not None:
-            measure = self._measure_loudness(o.loud, f.lr, f.clip)
-            if o.loud['mode'] != 'report':
-                f.clip = f.clip * measure['gain']
-        return measure, speech
+        return self._measure(f, o, True)
 
-    def _deliver(self, f, path_out, encoding, extended_metrics, o, band, image, measure, speech, picture):
+    def _present(self, o, extended_metrics):
+        """Which of the optional keys (_RECORD_KEYS) this run's results and records carry: key -> bool.  The one table behind a
+        blank record and a result, so that a skipped file's record has the keys an enhanced one's has."""
+        return dict(metrics_ext=bool(extended_metrics), output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None,
+                    speech_level=o.sl is not None, album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto,
+                    stereo=o.st is not None, output_rate=o.rc is not None, norm=self.norm_scope == 'clip' or self.segment_norm,
+                    flac=o.flac is not None)
+
+    def _deliver(self, f, path_out, encoding, extended_metrics, o, measured, picture):
         """(f) _write -- the output stage, the encoder, the one synchronisation and the file -- where there is anything to encode
-        or to bring back, then enhance_file's result."""
+        or to bring back, then enhance_file's result: the five keys it always has, then those of _RESULT_KEYS that are present.
+        `measured`: what _reports and _level queued."""
         output = None
         flac = o.flac and dict(o.flac)
-        if path_out is not None or o.stage is not None or any(m is not None for m in (picture, measure, speech, band, image)):
-            output = self._write(path_out, f.clip, encoding, o.stage, **_set(
-                picture=picture, loudness=measure, speech_level=speech, stereo=image, bandwidth=band,
-                true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
+        if path_out is not None or o.stage is not None or picture is not None or measured:
+            output = self._write(path_out, f.clip, encoding, o.stage, **measured, **_set(
+                picture=picture, true_peak=o.tp and dict(o.tp), limiter=o.lim and dict(o.lim),    # (one file's: they take the file's buffers)
                 rate=o.rc and o.rc['rate'], flac=flac))
+        # where a present key's value comes from, read behind _write; a measurement that was not taken (the stereo image of a file
+        # not written with two channels) is None
+        source = {'norm': lambda: f.norm, 'spectrogram': lambda: self._save_picture(o.spec, picture), 'crossover': lambda: f.crossover,
+                  'output_rate': lambda: self._output_rate_result(o.rc), 'metrics_ext': lambda: f.ext, 'output': lambda: output,
+                  'flac': lambda: flac.get('result')}                       # (None where no file was asked for)
+        for m in _MEASURED:
+            source[m.key] = lambda m=m: getattr(self, m.result)(getattr(o, m.field), measured[m.key]) if m.key in measured else None
         res = {'sr': f.clip, 'lr': f.lr, 'hr': f.hr, 'metrics': f.metrics, 'info': f.meta}
-        if self.norm_scope == 'clip' or self.segment_norm:                  # (without the option: no key more than before)
-            res['norm'] = f.norm
-        if picture is not None:
-            res['spectrogram'] = self._save_picture(o.spec, picture)
-        if measure is not None:
-            res['loudness'] = self._loudness_result(o.loud, measure)
-        if speech is not None:
-            res['speech_level'] = self._speech_level_result(o.sl, speech)
-        if band is not None:
-            res['bandwidth'] = self._bandwidth_result(o.bw, band)
-        if f.crossover is not None:
-            res['crossover'] = f.crossover
-        if o.st is not None:
-            res['stereo'] = None if image is None else self._stereo_result(o.st, image)
-        if o.rc is not None:
-            res['output_rate'] = self._output_rate_result(o.rc)
-        if extended_metrics:
-            res['metrics_ext'] = f.ext
-        if o.stage is not None:
-            res['output'] = output
-        if flac is not None:                                                # (None where no file was asked for)
-            res['flac'] = flac.get('result')
+        present = self._present(o, extended_metrics)                        # (without an option: no key more than before)
+        res.update((key, source[key]()) for key in _RESULT_KEYS if present[key])
         return res
 
     def _enhance_payload(self, read, path_out, is_lr_input, channels, encoding, extended_metrics, o):
@@ -997,11 +448,11 @@ class SuperResolver:
 
     def _finish(self, f, path_out, encoding, extended_metrics, o):
         """Stages (b) to (f) of one file behind its enhance_lr -> enhance_file's result."""
-        band, image = self._reports(f, o)
+        measured = self._reports(f, o)
         self._metrics(f, extended_metrics)
-        measure, speech = self._level(f, o)
+        measured.update(self._level(f, o))
         picture = None if o.spec is None else self._render_picture(o.spec, f.lr, f.clip, f.hr)       # (e)
-        return self._deliver(f, path_out, encoding, extended_metrics, o, band, image, measure, speech, picture)
+        return self._deliver(f, path_out, encoding, extended_metrics, o, measured, picture)
 
     # -- a folder: what both loudness scopes share ---------------------------------------------------------------
     def _blank_record(self, rel, path_out, written_from, extended_metrics, o):
@@ -1011,9 +462,7 @@ class SuperResolver:
         rec = {'path': rel, 'rate': None, 'channels': None, 'frames': None, 'written_channels': 0, 'out_frames': 0, 'metrics': None, 'error': None}
         if written_from is not None:
             rec['written'] = os.path.relpath(path_out, written_from)
-        present = dict(metrics_ext=extended_metrics, output=o.stage is not None, spectrogram=o.spec is not None, loudness=o.loud is not None, speech_level=o.sl is not None,
-                       album=o.album is not None, bandwidth=o.bw is not None, crossover=self.crossover_auto, stereo=o.st is not None,
-                       output_rate=o.rc is not None, norm=self.norm_scope == 'clip' or self.segment_norm, flac=o.flac is not None)
+        present = self._present(o, extended_metrics)
         rec.update((key, None) for key in _RECORD_KEYS if present[key])
         return rec
 
@@ -1030,13 +479,7 @@ class SuperResolver:
         None, or the pinned buffer to read into where it is not _read's own."""
         try:
             read = self._read(path_in, **_set(slot=slot, verify=True if verify_input else None))
-            self._check_picture_channel(o.spec, channels, read[1].num_channels)
-            self._check_stereo_channels(channels, read[1].num_channels)
-            if o.flac is not None and select_channels(channels, read[1].num_channels) > 8:
-                raise ValueError("a FLAC stream holds at most 8 channels, %d would be written" % select_channels(channels, read[1].num_channels))
-            if o.sl is not None and select_channels(channels, read[1].num_channels) > SPEECH_LEVEL_MAX_CHANNELS:
-                raise ValueError("the active speech level is measured over at most %d channels, %d would be written"
-                                 % (SPEECH_LEVEL_MAX_CHANNELS, select_channels(channels, read[1].num_channels)))
+            self._check_written_channels(o, channels, read[1].num_channels)
             return read
         except (ValueError, OSError, EOFError, struct.error) as e:
             rec['error'] = '%s: %s' % (type(e).__name__, e)
@@ -1195,11 +638,7 @@ class SuperResolver:
         ValueError each, the first and the last before a file is opened.
         `pack_files`: 1.  More -- files that share generator groups -- is an option of enhance_folder and a ValueError here, before
         the file is opened; the two entry points take the same options."""
-        o = self._options("enhance_file", False, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
-                          spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
-                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
-                                 speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
+        o = self._options("enhance_file", False, **_named(locals()))
         if check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_file") > 1:
             raise ValueError("enhance_file: pack_files %d lets the files of a folder share groups: it is an option of enhance_folder" % pack_files)
         read = self._read(path_in, **_set(verify=True if verify_input else None))
@@ -1296,11 +735,7 @@ class SuperResolver:
         ceil(R_i / batch) draws of a full group are made, their first rows kept, and handed on as given noise.  A file's rows,
         ranges and noise are then bit for bit those of pack_files=1; what the generator does with the other rows of a batch is all
         that differs.  Without segment_norm, or with loudness_scope 'folder', a ValueError before a file is opened."""
-        o = self._options("enhance_folder", True, encoding, clip, ceiling_dbfs, dither, dither_seed, report_peaks, spectrogram, spectrogram_channel,
-                          spectrogram_opts, loudness, loudness_max_gain_db, true_peak, limiter, limiter_lookahead_ms, limiter_hold_ms, loudness_range,
-                          loudness_scope, bandwidth, bandwidth_opts, stereo_report, stereo_report_opts, output_rate, dither_curve, dither_chunk,
-                          album_cache_bytes, **_set(container=None if container == 'wav' else container, flac_block=flac_block, flac_md5=flac_md5 or None, flac_lpc=flac_lpc,
-                                                    speech_level=speech_level, speech_level_max_gain_db=speech_level_max_gain_db))
+        o = self._options("enhance_folder", True, **_named(locals()))
         pack_files = check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_folder")
         plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
         written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
@@ -1388,3 +823,7 @@ class SuperResolver:
             waiting.append((rec, (read, path_out, mine)))
         finish(len(waiting))
         return records
+
+
+# The options both entry points share (and enhance_folder's album_cache_bytes): the keyword-only parameters of _options.
+_OPTION_NAMES = tuple(name for name, p in inspect.signature(SuperResolver._options).parameters.items() if p.kind is p.KEYWORD_ONLY)

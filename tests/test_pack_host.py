@@ -177,7 +177,7 @@ def test_ragged_restatement_is_the_per_clip_restatement(T, stride):
 # ------------------------------------------------------------------------------------------
 def _on_the_host(monkeypatch):
     """The four launches of the row ends -> the restatements, as float32 tensors on the host."""
-    from pix2pixhdaudiosr_amd.generate import resolver
+    from pix2pixhdaudiosr_amd.generate import rows as resolver     # (where the four are looked up)
 
     def gather_ragged(clips, T, stride, S_list):
         assert [RG.segments(c.shape[1], T, stride) for c in clips] == list(S_list)
