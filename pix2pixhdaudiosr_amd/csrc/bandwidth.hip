@@ -12,7 +12,8 @@
 //              float64 in the order include/p2phd.h writes down, nothing contracted: a numpy restatement returns the same bits.
 //
 // ltas: one workgroup per (chunk, row).  A pair of neighbouring frames goes through ONE n-point complex Stockham FFT in LDS
-// (fft_wave.h, the whole workgroup), z = w x_a + i w x_b, separated as in stft_db; thread t owns the bins t, t + 256, .. (at most 5)
+// (fft_wave.h, the whole workgroup), z = w x_a + i w x_b, separated as in stft_db (specsum.h, which owns the chunked sum's layout,
+// constants and fold); thread t owns the bins t, t + 256, .. (at most 5)
 // and keeps their float64 sums in registers across the chunk's pairs.  LDS holds the two complex buffers and the 3 n / 4 twiddles
 // the radix-4 stages reach (22 n bytes: 44 KiB at n = 2048, three workgroups to a CU); the window is read from the caller's table
 // beside the samples -- n coalesced floats a pair, cache hits after the first.  The workgroup stores its partial [K] into the
@@ -30,21 +31,13 @@
 #include "common.h"
 #include "convplan.h"
 #include "fft_wave.h"
+#include "specsum.h"
 #include <cmath>
 #include <cstdint>
 
 namespace {
 using namespace p2phd_fft;
-
-constexpr int kThreads = 256;
-constexpr int kChunk = 8;                       // frames per workgroup of ltas (even: a pair never straddles two chunks)
-constexpr int kFoldAhead = 8;                   // partials a thread of the folding workgroup loads per bin before it adds them
-constexpr int kMinFft = 64, kMaxFft = 2048;
-constexpr int kOwn = (kMaxFft / 2 + 1 + kThreads - 1) / kThreads;      // bins per thread at most
-constexpr int kMaxBins = 4097;                  // bandwidth: K float64 sums in LDS
-
-__device__ __forceinline__ void part_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double part_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+using namespace p2phd::spec;       // kThreads, kChunk, kOwn, .. and the helpers of the chunked sum
 
 // grid (chunks, R).  ticket[r / rpt] counts the workgroups of rows [g rpt, min(R, (g + 1) rpt)): rpt = 1 unless R exceeds the tickets
 __global__ __launch_bounds__(kThreads, 3) void ltas_kernel(const float* __restrict__ x, long ld, int n, int hop, long F,
@@ -59,7 +52,7 @@ __global__ __launch_bounds__(kThreads, 3) void ltas_kernel(const float* __restri
   const long chunks = gridDim.x, c = blockIdx.x, r = blockIdx.y;
   const float* row = x + r * ld;
   const float* win = tables + 2 * n;
-  for (int i = tid; i < 3 * (n >> 2); i += kThreads) s_tw[i] = reinterpret_cast<const float2*>(tables)[i];
+  stage_twiddles(s_tw, tables, n, tid);
   double acc[kOwn];
 #pragma unroll
   for (int i = 0; i < kOwn; ++i) acc[i] = 0.0;
@@ -78,11 +71,9 @@ __global__ __launch_bounds__(kThreads, 3) void ltas_kernel(const float* __restri
     for (int i = 0; i < kOwn; ++i) {
       const int k = tid + i * kThreads;
       if (k < K) {
-        const float2 a = Z[k], m = Z[(n - k) & (n - 1)];
-        const float ax = a.x + m.x, ay = a.y - m.y;               // 2 A[k]
-        const float bx = a.y + m.y, by = m.x - a.x;               // 2 B[k]
-        acc[i] += (double)((ax * ax + ay * ay) * pscale);
-        if (two) acc[i] += (double)((bx * bx + by * by) * pscale);
+        const TwoReal z = separate(Z, n, k);
+        acc[i] += (double)((z.ax * z.ax + z.ay * z.ay) * pscale);
+        if (two) acc[i] += (double)((z.bx * z.bx + z.by * z.by) * pscale);
       }
     }
     __syncthreads();                                              // Z is read: the next pair may overwrite either buffer
@@ -96,45 +87,8 @@ __global__ __launch_bounds__(kThreads, 3) void ltas_kernel(const float* __restri
   const int g = (int)(r / rpt);
   const int r_lo = g * rpt, r_hi = min(R, r_lo + rpt);
   if (!p2phd::fold_arrive_last(ticket + g, (unsigned)((r_hi - r_lo) * chunks))) return;
-  // the fold: a thread adds its own bins' partials in chunk order; kFoldAhead chunks are loaded before they are added, so that a
-  // row of loads is in flight per thread instead of one (the order of the additions is the chunks' all the same)
-  for (long rr = r_lo; rr < r_hi; ++rr) {
-    const double* rows = part + rr * chunks * K;
-    double s[kOwn];
-#pragma unroll
-    for (int i = 0; i < kOwn; ++i) s[i] = 0.0;
-    long cc = 0;
-    for (; cc + kFoldAhead <= chunks; cc += kFoldAhead) {
-      double v[kOwn][kFoldAhead];
-#pragma unroll
-      for (int i = 0; i < kOwn; ++i) {
-        const int k = tid + i * kThreads;
-        if (k < K) {
-#pragma unroll
-          for (int u = 0; u < kFoldAhead; ++u) v[i][u] = part_load(rows + (cc + u) * K + k);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < kOwn; ++i) {
-        if (tid + i * kThreads < K) {
-#pragma unroll
-          for (int u = 0; u < kFoldAhead; ++u) s[i] += v[i][u];
-        }
-      }
-    }
-    for (; cc < chunks; ++cc) {
-#pragma unroll
-      for (int i = 0; i < kOwn; ++i) {
-        const int k = tid + i * kThreads;
-        if (k < K) s[i] += part_load(rows + cc * K + k);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < kOwn; ++i) {
-      const int k = tid + i * kThreads;
-      if (k < K) psd[rr * K + k] = s[i];
-    }
-  }
+  // the fold (specsum.h): a thread adds its own bins' partials in chunk order
+  for (long rr = r_lo; rr < r_hi; ++rr) fold_chunks(part + rr * chunks * K, K, chunks, K, tid, psd + rr * K);
 }
 
 __global__ __launch_bounds__(kThreads) void bandwidth_kernel(const double* __restrict__ psd, int Q, int K, int M, double rel,

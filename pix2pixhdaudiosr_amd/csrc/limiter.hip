@@ -28,9 +28,8 @@
 // The limited clip's own true peak can still lie a hair over c: the interpolator mixes neighbours that carry slightly different
 // gains.  The limiter does not promise otherwise; p2phd_pcm_peak / p2phd_truepeak and the guard's one gain run behind it unchanged.
 //
-// envelope kernel: the layout of truepeak_kernel, restated here rather than shared (truepeak.hip is untouched, so its registers
-// cannot move): 256 threads, a thread owns 8 consecutive instants and keeps their sample window in registers, the staged samples
-// carry one pad dword per 8 (conflict-free reads), the table is read uniformly (scalar loads).  Instant j stands for i = j - 1.
+// envelope kernel: the staging and the walk of truepeak_kernel, both from firwalk.h (stage_finite, polyphase_walk_up), which owns
+// the layout and the order of the fmas: the same code forms every y in both files.  Instant j stands for i = j - 1.
 // The channels are walked inside the workgroup with the maxima kept in registers, so one r per sample leaves.  m[i] needs the
 // fractional phases of instants i and i + 1: a tile of 2048 instants therefore yields 2047 samples, and tiles are laid 2047
 // apart -- one instant in 2048 is formed twice, to the same bits.  Workgroup maxima of the bit patterns are stored and folded by
@@ -39,13 +38,14 @@
 // minimum over W = A + H + 1 goes in two block passes: suffix minima and prefix minima of blocks of W, each a thread-local pass
 // over a chunk of consecutive positions, a segmented scan of the 256 chunk results, and a pass that hands the carry on up to the
 // chunk's first block edge; h = min(suffix[q], prefix[q + W - 1]).  Its cost does not grow with the window.  d is written in
-// place of the suffix minima, in the padded layout, and the sum takes the register-window walk of xover_kernel: a tap costs one
-// conflict-free LDS read and 8 fmas per thread.  The sums go back through LDS, so that r, x, g and out are read and written with
-// consecutive lanes on consecutive floats.  LDS: (2048 + 2 A + H) * 17 / 8 floats: 29 KiB at A = 240, H = 960, 68 KiB at the caps,
-// beside 6.3 KiB of scan and fold arrays.
+// place of the suffix minima, in the padded layout of firwalk.h, and the sum takes the register-window walk of xover_kernel: a tap
+// costs one conflict-free LDS read and 8 fmas per thread.  The sums go back through LDS, so that r, x, g and out are read and
+// written with consecutive lanes on consecutive floats.  LDS: (2048 + 2 A + H) * 17 / 8 floats: 29 KiB at A = 240, H = 960,
+// 68 KiB at the caps, beside 6.3 KiB of scan and fold arrays.
 // No roofline claim: see DESIGN.md section 6.
 #include "common.h"
 #include "convplan.h"
+#include "firwalk.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -55,20 +55,15 @@
 
 namespace {
 constexpr int kThreads = 256;
-constexpr int kIn = 8;                        // instants / samples per thread (the pad rule below is written for 8)
+constexpr int kIn = 8;                        // instants / samples per thread (firwalk.h)
 constexpr int kTile = kThreads * kIn;         // instants per envelope tile, samples per curve tile
 constexpr int kEnvStep = kTile - 1;           // samples an envelope tile yields
-constexpr int kMinTaps = 4, kMaxTaps = 64;    // per phase, as truepeak.hip
 constexpr int kMaxLookahead = 1024, kMaxHold = 4096;
 constexpr int kEnvParts = 16384;              // words of the fold region the envelope's partial maxima take
 constexpr int kStatWords = 3;                 // per workgroup of the curve kernel: min g, count (low, high)
 
-__device__ __forceinline__ int pad8(int p) { return p + (p >> 3); }
-constexpr size_t lds_floats(int n) { return (size_t)n + ((size_t)n >> 3) + 1; }
-
-__device__ __forceinline__ void part_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t part_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+using namespace p2phd::fir;
+static_assert(kThreads == kWalkThreads && kIn == 8, "firwalk.h is written for 256 threads of 8 outputs");
 
 // NP = F - 1 fractional phases.  grid (gx): workgroup b takes tiles b, b + gx, ..; tile t holds instants 2047 t .. 2047 t + 2047
 // and yields r of the samples 2047 t .. 2047 t + 2046.
@@ -95,57 +90,15 @@ __global__ __launch_bounds__(kThreads) void limiter_envelope_kernel(const float*
 #pragma unroll
     for (int r = 0; r < kIn; ++r) full[r] = frac[r] = 0u;
     for (int c = 0; c < C; ++c) {
-      const float* row = planar + (long)c * ld;
-      for (int q = tid; q < n; q += kThreads) {
-        const long j = g0 + q;
-        uint32_t bits = 0u;
-        if (j >= 0 && j < L) {
-          bits = __float_as_uint(row[j]);
-          if ((bits & 0x7FFFFFFFu) >= 0x7F800000u) bits = 0u;     // NaN, +-inf: taken as 0
-        }
-        s_x[pad8(q)] = __uint_as_float(bits);
-      }
+      stage_finite(s_x, planar + (long)c * ld, g0, n, L, tid);
       __syncthreads();
       if (base < len) {
         // phase 0: the instants' own samples (i = -1 holds x~ = 0)
 #pragma unroll
         for (int r = 0; r < kIn; ++r) full[r] = max(full[r], abs_bits(s_x[pad8(base + r + half)]));
-        if (NP > 0) {
-          // instant r of this thread at tap k reads position base + r + k; w holds those samples at the current tap
-          float acc[NP > 0 ? NP : 1][kIn];
-          float w[kIn];
-#pragma unroll
-          for (int r = 0; r < kIn; ++r) {
-            w[r] = s_x[pad8(base + r)];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) acc[p][r] = 0.0f;
-          }
-          int k = 0;
-          for (; k + kIn <= P; k += kIn) {
-            // eight taps with the window rotating through the registers: at step u the sample of instant r is w[(r + u) & 7]
-#pragma unroll
-            for (int u = 0; u < kIn; ++u) {
-#pragma unroll
-              for (int p = 0; p < NP; ++p) {
-                const float ck = tab[(p + 1) * P + k + u];
-#pragma unroll
-                for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[(r + u) & (kIn - 1)], acc[p][r]);
-              }
-              // the next tap: every instant moves one sample up, instant 7 takes a new one (not read behind the last tap)
-              w[u & (kIn - 1)] = s_x[pad8(min(base + kIn + k + u, n - 1))];
-            }
-          }
-          for (; k < P; ++k) {                                    // the last taps mod 8, with the window in place
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-              const float ck = tab[(p + 1) * P + k];
-#pragma unroll
-              for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[r], acc[p][r]);
-            }
-#pragma unroll
-            for (int r = 0; r + 1 < kIn; ++r) w[r] = w[r + 1];
-            w[kIn - 1] = s_x[pad8(min(base + kIn + k, n - 1))];
-          }
+        if constexpr (NP > 0) {
+          float acc[NP][kIn] = {};
+          polyphase_walk_up<NP, kIn>(s_x, tab, P, base, n, acc);
 #pragma unroll
           for (int p = 0; p < NP; ++p)
 #pragma unroll
@@ -169,23 +122,13 @@ __global__ __launch_bounds__(kThreads) void limiter_envelope_kernel(const float*
     }
     __syncthreads();                                              // (the maxima are read: the arrays take the next tile)
   }
-  s_pk[tid] = pk;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) s_pk[tid] = max(s_pk[tid], s_pk[tid + o]);
-    __syncthreads();
-  }
+  lds_max256(s_pk, tid, pk);
   if (tid == 0) part_store(part + blockIdx.x, s_pk[0]);
   if (!p2phd::fold_arrive_last(ticket, (unsigned)gx)) return;
   // the last workgroup: a maximum does not depend on the order
   uint32_t p = 0u;
   for (int b = tid; b < gx; b += kThreads) p = max(p, part_load(part + b));
-  s_pk[tid] = p;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) s_pk[tid] = max(s_pk[tid], s_pk[tid + o]);
-    __syncthreads();
-  }
+  lds_max256(s_pk, tid, p);
   if (tid == 0) *peak = __uint_as_float(s_pk[0]);
 }
 
@@ -234,6 +177,16 @@ __device__ __forceinline__ void block_minima(float* s_r, float* s_s, int n, int 
     }
   }
   __syncthreads();
+}
+
+// s_min[0], s_cnt[0] = the smallest gmin and the sum of cnt of the 256 threads (neither depends on the order); ends behind a barrier
+__device__ __forceinline__ void fold_stats(float* s_min, unsigned long long* s_cnt, int tid, float gmin, unsigned long long cnt) {
+  s_min[tid] = gmin; s_cnt[tid] = cnt;
+  __syncthreads();
+  for (int o = kThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) { s_min[tid] = fminf(s_min[tid], s_min[tid + o]); s_cnt[tid] += s_cnt[tid + o]; }
+    __syncthreads();
+  }
 }
 
 // grid (gx): workgroup b takes the tiles b, b + gx, .. of 2048 samples
@@ -329,12 +282,7 @@ __global__ __launch_bounds__(kThreads) void limiter_apply_kernel(const float* __
     }
     __syncthreads();                                              // (the sums are read: the region takes the next tile)
   }
-  s_v[0][tid] = gmin; s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) { s_v[0][tid] = fminf(s_v[0][tid], s_v[0][tid + o]); s_cnt[tid] += s_cnt[tid + o]; }
-    __syncthreads();
-  }
+  fold_stats(s_v[0], s_cnt, tid, gmin, cnt);
   if (tid == 0) {
     uint32_t* mine = part + (size_t)blockIdx.x * kStatWords;
     part_store(mine, __float_as_uint(s_v[0][0]));
@@ -349,20 +297,11 @@ __global__ __launch_bounds__(kThreads) void limiter_apply_kernel(const float* __
     gmin = fminf(gmin, __uint_as_float(part_load(its)));
     cnt += (unsigned long long)part_load(its + 1) | ((unsigned long long)part_load(its + 2) << 32);
   }
-  s_v[0][tid] = gmin; s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) { s_v[0][tid] = fminf(s_v[0][tid], s_v[0][tid + o]); s_cnt[tid] += s_cnt[tid + o]; }
-    __syncthreads();
-  }
+  fold_stats(s_v[0], s_cnt, tid, gmin, cnt);
   if (tid == 0) {
     stats[0] = __float_as_uint(s_v[0][0]);
     stats[1] = s_cnt[0] > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)s_cnt[0];
   }
-}
-
-bool table_ok(int factor, int taps_per_phase) {
-  return (factor == 1 || factor == 2 || factor == 4) && taps_per_phase >= kMinTaps && taps_per_phase <= kMaxTaps && (taps_per_phase & 1) == 0;
 }
 
 // workgroups: one per tile, as far as the partial table has rows (and the "limiter_grid" option allows)

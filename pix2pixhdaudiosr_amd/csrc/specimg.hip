@@ -26,17 +26,16 @@
 #include "common.h"
 #include "convplan.h"
 #include "fft_wave.h"
+#include "specsum.h"
 #include <cmath>
 #include <cstdint>
 
 namespace {
 using namespace p2phd_fft;
+using namespace p2phd::spec;                    // kThreads, kMinFft, kMaxFft, kMaxBins (render: K floats of column maxima in LDS), separate
 
-constexpr int kThreads = 256;
 constexpr int kPairs = 4;                       // frame pairs per workgroup of stft_db: the table is loaded once for all of them
-constexpr int kMinFft = 64, kMaxFft = 2048;
 constexpr int kMaxSide = 16384, kMaxGap = 64;
-constexpr int kMaxBins = 4097;                  // render: K floats of column maxima in LDS
 constexpr int kIdxBytes = 24576, kMaxUnits = 32;   // render: H * xt palette indices in LDS
 constexpr float kFloorP = 1e-20f, kFloorDb = -200.0f;
 constexpr unsigned char kGapGrey = 64;
@@ -74,10 +73,8 @@ __global__ __launch_bounds__(kThreads) void stft_db_kernel(const float* __restri
     const float2* Z = fft_coop(buf0, buf1, s_tw, n, tid, kThreads);
     float* s_out = reinterpret_cast<float*>(Z == buf0 ? buf1 : buf0);      // 2 n floats, free: holds the pair's 2 K <= n + 2 values
     for (int k = tid; k < K; k += kThreads) {
-      const float2 a = Z[k], m = Z[(n - k) & (n - 1)];
-      const float ax = a.x + m.x, ay = a.y - m.y;                 // 2 A[k]
-      const float bx = a.y + m.y, by = m.x - a.x;                 // 2 B[k]
-      const float pa = (ax * ax + ay * ay) * pscale, pb = (bx * bx + by * by) * pscale;
+      const TwoReal z = separate(Z, n, k);                          // 2 A[k], 2 B[k]
+      const float pa = (z.ax * z.ax + z.ay * z.ay) * pscale, pb = (z.bx * z.bx + z.by * z.by) * pscale;
       s_out[k] = pa <= kFloorP ? kFloorDb : 10.0f * log10f(pa);
       s_out[K + k] = pb <= kFloorP ? kFloorDb : 10.0f * log10f(pb);
     }

@@ -11,39 +11,33 @@
 //            writes down, nothing contracted: a numpy restatement returns the same bits.
 //   matrix   out0 = a (x0 + s), out1 = a (x0 - s), s = x1 (with guard_side: +0 where x1 is not finite); plain fp32.
 //
-// xspec has the geometry of ltas_kernel (bandwidth.hip): one workgroup of 256 threads per (chunk of 8 frames, pair), one n-point
-// complex Stockham FFT in LDS per frame (fft_wave.h).  The two slots of the complex transform carry the two CHANNELS of one frame,
-// z = w x_L + i w x_R, separated with stft_db's expressions, so the cross term costs four more multiplies per bin and no more
-// transforms; a chunk is eight transforms where ltas's is four.  Thread t owns the bins t, t + 256, .. (at most 5) and keeps their
-// four float64 sums in registers across the chunk (20 doubles).  LDS as ltas: 22 n bytes, 44 KiB at n = 2048, three workgroups to
-// a CU.  Partials [chunk][4][K] go to the caller's workspace; the last workgroup of a pair to arrive folds them in chunk order, ONE
-// quantity at a time with ltas's look-ahead of eight partials per bin (kOwn x kFoldAhead doubles in flight, as there: four
-// quantities at once would not fit three workgroups to a CU).  The arrival tickets are FOLD_LTAS's, the tickets-only region of
-// p2phd_ltas: the two kernels never run inside one another's launch, and fold_scratch orders launches of one region that arrive
-// on different streams, so an ltas and an xspec on two streams are ordered like two ltas calls are.  No float atomics.
+// xspec has the geometry of ltas_kernel (bandwidth.hip; the constants, the separation and the fold are specsum.h's): one workgroup
+// of 256 threads per (chunk of 8 frames, pair), one n-point complex Stockham FFT in LDS per frame (fft_wave.h). The two slots of
+// the complex transform carry the two CHANNELS of one frame, z = w x_L + i w x_R, separated with stft_db's expressions, so the
+// cross term costs four more multiplies per bin and no more transforms; a chunk is eight transforms where ltas's is four. Thread t
+// owns the bins t, t + 256, .. (at most 5) and keeps their four float64 sums in registers across the chunk (20 doubles). LDS as
+// ltas: 22 n bytes, 44 KiB at n = 2048, three workgroups to a CU. Partials [chunk][4][K] go to the caller's workspace; the last
+// workgroup of a pair to arrive folds them in chunk order, ONE quantity at a time with ltas's look-ahead of eight partials per bin
+// (kOwn x kFoldAhead doubles in flight, as there: four quantities at once would not fit three workgroups to a CU). The arrival
+// tickets are FOLD_LTAS's, the tickets-only region of p2phd_ltas: the two kernels never run inside one another's launch, and
+// fold_scratch orders launches of one region that arrive on different streams, so an ltas and an xspec on two streams are ordered
+// like two ltas calls are. No float atomics.
 //
 // bands: one workgroup per pair, 256 lanes, a tree in LDS.  matrix: grid-stride, float4 where both pitches and pointers allow.
 #include "common.h"
 #include "convplan.h"
 #include "streamgrid.h"
 #include "fft_wave.h"
+#include "specsum.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 namespace {
 using namespace p2phd_fft;
+using namespace p2phd::spec;       // kThreads, kChunk, kOwn, .. and the helpers of the chunked sum: p2phd_ltas's, by construction
 
-constexpr int kThreads = 256;
-constexpr int kChunk = 8;                       // frames per workgroup of xspec: p2phd_ltas_chunk_frames()
-constexpr int kFoldAhead = 8;                   // partials a thread of the folding workgroup loads per bin before it adds them
-constexpr int kMinFft = 64, kMaxFft = 2048;
-constexpr int kOwn = (kMaxFft / 2 + 1 + kThreads - 1) / kThreads;      // bins per thread at most
 constexpr int kQuant = 4;                       // |A|^2, |B|^2, Re(A conj B), Im(A conj B)
-constexpr int kMaxBins = 4097;                  // bands: as p2phd_bandwidth
-
-__device__ __forceinline__ void part_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double part_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // grid (chunks, G).  ticket[g / ppt] counts the workgroups of pairs [t ppt, min(G, (t + 1) ppt)): ppt = 1 unless G exceeds the tickets
 __global__ __launch_bounds__(kThreads, 3) void xspec_kernel(const float* __restrict__ x, long ld, int n, int hop, long F,
@@ -59,7 +53,7 @@ __global__ __launch_bounds__(kThreads, 3) void xspec_kernel(const float* __restr
   const float* left = x + 2 * g * ld;
   const float* right = left + ld;
   const float* win = tables + 2 * n;
-  for (int i = tid; i < 3 * (n >> 2); i += kThreads) s_tw[i] = reinterpret_cast<const float2*>(tables)[i];
+  stage_twiddles(s_tw, tables, n, tid);
   double acc[kQuant][kOwn];
 #pragma unroll
   for (int q = 0; q < kQuant; ++q)
@@ -80,13 +74,11 @@ __global__ __launch_bounds__(kThreads, 3) void xspec_kernel(const float* __restr
     for (int i = 0; i < kOwn; ++i) {
       const int k = tid + i * kThreads;
       if (k < K) {
-        const float2 a = Z[k], m = Z[(n - k) & (n - 1)];
-        const float ax = a.x + m.x, ay = a.y - m.y;               // 2 A[k]
-        const float bx = a.y + m.y, by = m.x - a.x;               // 2 B[k]
-        acc[0][i] += (double)((ax * ax + ay * ay) * pscale);
-        acc[1][i] += (double)((bx * bx + by * by) * pscale);
-        acc[2][i] += (double)((ax * bx + ay * by) * pscale);      // A conj B = (ax bx + ay by) + i (ay bx - ax by)
-        acc[3][i] += (double)((ay * bx - ax * by) * pscale);
+        const TwoReal z = separate(Z, n, k);
+        acc[0][i] += (double)((z.ax * z.ax + z.ay * z.ay) * pscale);
+        acc[1][i] += (double)((z.bx * z.bx + z.by * z.by) * pscale);
+        acc[2][i] += (double)((z.ax * z.bx + z.ay * z.by) * pscale);      // A conj B = (ax bx + ay by) + i (ay bx - ax by)
+        acc[3][i] += (double)((z.ay * z.bx - z.ax * z.by) * pscale);
       }
     }
     __syncthreads();                                              // Z is read: the next frame may overwrite either buffer
@@ -102,48 +94,10 @@ __global__ __launch_bounds__(kThreads, 3) void xspec_kernel(const float* __restr
   const int t = (int)(g / ppt);
   const int g_lo = t * ppt, g_hi = min(G, g_lo + ppt);
   if (!p2phd::fold_arrive_last(ticket + t, (unsigned)((g_hi - g_lo) * chunks))) return;
-  // the fold, one quantity of one pair at a time: a thread adds its own bins' partials in chunk order, kFoldAhead chunks loaded
-  // before they are added (the order of the additions is the chunks' all the same)
-  for (long gg = g_lo; gg < g_hi; ++gg) {
-    for (int q = 0; q < kQuant; ++q) {
-      const double* rows = part + gg * chunks * (long)(kQuant * K) + (long)q * K;
-      const long step = (long)kQuant * K;                          // from one chunk's partial to the next
-      double s[kOwn];
-#pragma unroll
-      for (int i = 0; i < kOwn; ++i) s[i] = 0.0;
-      long cc = 0;
-      for (; cc + kFoldAhead <= chunks; cc += kFoldAhead) {
-        double v[kOwn][kFoldAhead];
-#pragma unroll
-        for (int i = 0; i < kOwn; ++i) {
-          const int k = tid + i * kThreads;
-          if (k < K) {
-#pragma unroll
-            for (int u = 0; u < kFoldAhead; ++u) v[i][u] = part_load(rows + (cc + u) * step + k);
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < kOwn; ++i) {
-          if (tid + i * kThreads < K) {
-#pragma unroll
-            for (int u = 0; u < kFoldAhead; ++u) s[i] += v[i][u];
-          }
-        }
-      }
-      for (; cc < chunks; ++cc) {
-#pragma unroll
-        for (int i = 0; i < kOwn; ++i) {
-          const int k = tid + i * kThreads;
-          if (k < K) s[i] += part_load(rows + cc * step + k);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < kOwn; ++i) {
-        const int k = tid + i * kThreads;
-        if (k < K) xs[(gg * kQuant + q) * K + k] = s[i];
-      }
-    }
-  }
+  // the fold (specsum.h), one quantity of one pair at a time: a thread adds its own bins' partials in chunk order
+  const long step = (long)kQuant * K;                             // from one chunk's partial to the next
+  for (long gg = g_lo; gg < g_hi; ++gg)
+    for (int q = 0; q < kQuant; ++q) fold_chunks(part + gg * chunks * step + (long)q * K, step, chunks, K, tid, xs + (gg * kQuant + q) * K);
 }
 
 // grid (G).  The order of include/p2phd.h: per (band, row) lane t adds v[lo + t], v[lo + t + 256], .. to +0 in ascending order,

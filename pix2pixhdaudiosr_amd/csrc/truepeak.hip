@@ -13,16 +13,14 @@
 //
 // One workgroup per (tile of kTile instants, row); a row is a channel, on blockIdx.y.  (Where a clip has more tiles than the
 // partial table has rows, a workgroup walks several tiles.)  Instant j of a row stands for i = j - 1, so a row has L + 1 of them.
-// The tile's samples with their P - 1 halo are staged in LDS, the non-finite ones zeroed on load.  A thread owns kIn CONSECUTIVE
-// instants and keeps their kIn-wide sample window in registers: tap k + 1 needs the window of tap k shifted by one sample, so a
-// tap costs one LDS read and (F - 1) kIn fmas per thread -- all fractional phases are formed from the one window.  Lanes read
-// addresses kIn = 8 dwords apart; the staged array carries one pad dword per 8 (position p lives at p + p / 8), lane t reads
-// 9 t + const, and 9 is coprime to 32: conflict-free, as in xover.hip.  The table (at most 3 x 64 floats that count) is read at
-// the same address in every lane: scalar loads.  Workgroup maxima are stored and folded by the last workgroup (common.h:
-// fold_arrive_last), so nothing is zeroed before the launch and there is no float atomic.  LDS: (2048 + 64) * 9 / 8 floats and
-// the fold = 10.4 KiB per workgroup.  No workspace besides the partials.  No roofline claim: see DESIGN.md section 6.
+// The tile's samples with their P - 1 halo are staged in LDS, the non-finite ones zeroed on load, and every thread forms the
+// fractional phases of its 8 instants with the register-window walk of firwalk.h (polyphase_walk_up), which owns the layout and
+// the order of the fmas.  Workgroup maxima are stored and folded by the last workgroup (common.h: fold_arrive_last), so nothing
+// is zeroed before the launch and there is no float atomic.  LDS: (2048 + 64) * 9 / 8 floats and the fold = 10.4 KiB per
+// workgroup.  No workspace besides the partials.  No roofline claim: see DESIGN.md section 6.
 #include "common.h"
 #include "convplan.h"
+#include "firwalk.h"
 #include "kaiser.h"
 #include <algorithm>
 #include <cmath>
@@ -31,16 +29,11 @@
 
 namespace {
 constexpr int kThreads = 256;
-constexpr int kIn = 8;                        // instants per thread (the pad rule below is written for 8)
+constexpr int kIn = 8;                        // instants per thread (firwalk.h)
 constexpr int kTile = kThreads * kIn;         // instants per workgroup and tile
-constexpr int kMinTaps = 4, kMaxTaps = 64;    // per phase
 
-__device__ __forceinline__ int pad8(int p) { return p + (p >> 3); }
-constexpr int lds_floats(int n) { return n + (n >> 3) + 1; }
-
-__device__ __forceinline__ void part_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t part_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+using namespace p2phd::fir;
+static_assert(kThreads == kWalkThreads && kIn == 8, "firwalk.h is written for 256 threads of 8 outputs");
 
 // NP = F - 1 fractional phases.  grid (gx, channels): workgroup (b, c) takes tiles b, b + gx, .. of row c.
 template <int NP>
@@ -60,57 +53,16 @@ __global__ __launch_bounds__(kThreads) void truepeak_kernel(const float* __restr
     const int len8 = (len + kIn - 1) & ~(kIn - 1);                // ... up to whole threads: everything a thread reads is staged
     const int n = len8 + P - 1;                                   // staged samples: position q holds x~[j0 - 1 - half + q]
     const long g0 = j0 - 1 - half;
-    for (int q = tid; q < n; q += kThreads) {
-      const long j = g0 + q;
-      uint32_t bits = 0u;
-      if (j >= 0 && j < L) {
-        bits = __float_as_uint(row[j]);
-        if ((bits & 0x7FFFFFFFu) >= 0x7F800000u) bits = 0u;       // NaN, +-inf: taken as 0
-      }
-      s_x[pad8(q)] = __uint_as_float(bits);
-    }
+    stage_finite(s_x, row, g0, n, L, tid);
     __syncthreads();
     if (base < len) {
       uint32_t m[kIn];
       // phase 0: the instants' own samples (i = -1 holds x~ = 0)
 #pragma unroll
       for (int r = 0; r < kIn; ++r) m[r] = abs_bits(s_x[pad8(base + r + half)]);
-      if (NP > 0) {
-        // instant r of this thread at tap k reads position base + r + k; w holds those samples at the current tap
-        float acc[NP > 0 ? NP : 1][kIn];
-        float w[kIn];
-#pragma unroll
-        for (int r = 0; r < kIn; ++r) {
-          w[r] = s_x[pad8(base + r)];
-#pragma unroll
-          for (int p = 0; p < NP; ++p) acc[p][r] = 0.0f;
-        }
-        int k = 0;
-        for (; k + kIn <= P; k += kIn) {
-          // eight taps with the window rotating through the registers: at step u the sample of instant r is w[(r + u) & 7]
-#pragma unroll
-          for (int u = 0; u < kIn; ++u) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-              const float ck = tab[(p + 1) * P + k + u];
-#pragma unroll
-              for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[(r + u) & (kIn - 1)], acc[p][r]);
-            }
-            // the next tap: every instant moves one sample up, instant 7 takes a new one (not read behind the last tap)
-            w[u & (kIn - 1)] = s_x[pad8(min(base + kIn + k + u, n - 1))];
-          }
-        }
-        for (; k < P; ++k) {                                      // the last taps mod 8, with the window in place
-#pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            const float ck = tab[(p + 1) * P + k];
-#pragma unroll
-            for (int r = 0; r < kIn; ++r) acc[p][r] = __builtin_fmaf(ck, w[r], acc[p][r]);
-          }
-#pragma unroll
-          for (int r = 0; r + 1 < kIn; ++r) w[r] = w[r + 1];
-          w[kIn - 1] = s_x[pad8(min(base + kIn + k, n - 1))];
-        }
+      if constexpr (NP > 0) {
+        float acc[NP][kIn] = {};
+        polyphase_walk_up<NP, kIn>(s_x, tab, P, base, n, acc);
 #pragma unroll
         for (int p = 0; p < NP; ++p)
 #pragma unroll
@@ -122,12 +74,7 @@ __global__ __launch_bounds__(kThreads) void truepeak_kernel(const float* __restr
     }
     __syncthreads();                                              // every window read is done: the region takes the next tile
   }
-  s_pk[tid] = pk;
-  __syncthreads();
-  for (int o = kThreads / 2; o > 0; o >>= 1) {
-    if (tid < o) s_pk[tid] = max(s_pk[tid], s_pk[tid + o]);
-    __syncthreads();
-  }
+  lds_max256(s_pk, tid, pk);
   if (tid == 0) part_store(part + (size_t)c * gx + blockIdx.x, s_pk[0]);
   if (!p2phd::fold_arrive_last(ticket, (unsigned)(gx * C))) return;
   // the last workgroup: wave w folds channels w, w + 4, ...; a maximum does not depend on the order
@@ -151,10 +98,6 @@ __global__ __launch_bounds__(kThreads) void truepeak_kernel(const float* __restr
 
 using p2phd::bessel_i0;
 
-bool plan_ok(int factor, int taps_per_phase) {
-  return (factor == 1 || factor == 2 || factor == 4) && taps_per_phase >= kMinTaps && taps_per_phase <= kMaxTaps && (taps_per_phase & 1) == 0;
-}
-
 // workgroups per row: one per tile, as far as the partial table has rows (and the "truepeak_grid" option allows)
 int tile_grid(int64_t tiles, int channels, size_t scratch_words) {
   int64_t cap = (int64_t)(scratch_words / (size_t)channels);
@@ -167,7 +110,7 @@ int tile_grid(int64_t tiles, int channels, size_t scratch_words) {
 extern "C" int p2phd_truepeak_tile_len(void) { return kTile; }
 
 extern "C" int p2phd_truepeak_taps_fill(int factor, int taps_per_phase, double beta, float* out) {
-  P2PHD_REQUIRE(plan_ok(factor, taps_per_phase), "truepeak_taps_fill: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
+  P2PHD_REQUIRE(table_ok(factor, taps_per_phase), "truepeak_taps_fill: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
                 kMinTaps, kMaxTaps, factor, taps_per_phase);
   P2PHD_REQUIRE(beta >= 0.0 && std::isfinite(beta), "truepeak_taps_fill: beta must be finite and >= 0, got %g", beta);
   P2PHD_REQUIRE(out != nullptr, "truepeak_taps_fill: null output");
@@ -197,7 +140,7 @@ extern "C" int p2phd_truepeak_taps_fill(int factor, int taps_per_phase, double b
 extern "C" int p2phd_truepeak(const float* planar, int64_t frames, int channels, int64_t ld, const float* table_dev, int factor, int taps_per_phase,
                               float ceiling, float* tpeak, float* gain, void* stream) {
   if (const int rc = p2phd::pcm_check_rows("truepeak", frames, channels, ld, P2PHD_PCM_F32, true)) return rc;
-  P2PHD_REQUIRE(plan_ok(factor, taps_per_phase), "truepeak: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
+  P2PHD_REQUIRE(table_ok(factor, taps_per_phase), "truepeak: factor must be 1, 2 or 4 and taps_per_phase even and in [%d, %d], got %d and %d",
                 kMinTaps, kMaxTaps, factor, taps_per_phase);
   P2PHD_REQUIRE(ceiling > 0.0f && std::isfinite(ceiling), "truepeak: ceiling must be finite and > 0, got %g", (double)ceiling);
   P2PHD_REQUIRE(tpeak && gain && table_dev, "truepeak: null output or table pointer");

@@ -12,16 +12,15 @@
 // k = 0, 1, .., taps - 1 (the products ARE contracted: one rounding per tap); then one rounded addition sr[i] + acc.
 //
 // One workgroup per (tile of kTile outputs, row); a row is a channel, on blockIdx.y.  The tile's d with its taps - 1 halo is formed
-// on load and staged in LDS.  A thread owns kOut CONSECUTIVE outputs and keeps their kOut-wide window of d in registers: tap k + 1
-// needs the window of tap k shifted by one sample, so a tap costs one LDS read and kOut fmas per thread.  Lanes then read
-// addresses kOut = 8 dwords apart, which would be an 8-way bank conflict on the 32 banks of a 4-byte read; the staged array
-// therefore carries one pad dword per 8 (position p lives at p + p / 8): lane t reads 9 t + const, and 9 is coprime to 32, so
-// every read is conflict-free.  The taps are read uniformly from the caller's table (the same address in every lane: scalar
-// loads).  The sums go back through the same LDS region so that sr is read and out is written with consecutive lanes on
+// on load and staged in LDS in the padded layout of firwalk.h (256 threads, 8 CONSECUTIVE outputs a thread, one pad dword per 8
+// staged: conflict-free reads).  A thread keeps the 8-wide window of d of its outputs in registers: tap k + 1 needs the window of
+// tap k shifted by one sample, so a tap costs one LDS read and 8 fmas per thread; the taps are read uniformly (scalar loads).
+// The sums go back through the same LDS region so that sr is read and out is written with consecutive lanes on
 // consecutive floats, whatever the alignment of a row.  LDS: at most (2048 + 4094) * 9 / 8 floats = 27 KiB per workgroup.
 // No atomics, no workspace.  Microseconds to a few milliseconds beside the generator: no roofline claim.
 #include "common.h"
 #include "convplan.h"
+#include "firwalk.h"
 #include "kaiser.h"
 #include <cmath>
 #include <cstdint>
@@ -31,12 +30,13 @@
 
 namespace {
 constexpr int kThreads = 256;
-constexpr int kOut = 8;                       // outputs per thread (the pad rule below is written for 8)
+constexpr int kOut = 8;                       // outputs per thread (firwalk.h)
 constexpr int kTile = kThreads * kOut;        // outputs per workgroup
 constexpr int kMaxTaps = 4095;
 
-__device__ __forceinline__ int pad8(int p) { return p + (p >> 3); }
-constexpr size_t lds_floats(int n) { return (size_t)n + ((size_t)n >> 3) + 1; }
+using p2phd::fir::lds_floats;
+using p2phd::fir::pad8;
+static_assert(kOut == 8, "pad8 is written for 8 outputs a thread");
 
 __global__ __launch_bounds__(kThreads) void xover_kernel(const float* __restrict__ sr, long ld_sr, const float* __restrict__ lr, long ld_lr,
                                                          float level, const float* __restrict__ h, int taps, long L,
