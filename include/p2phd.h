@@ -235,6 +235,21 @@ int p2phd_timed_frames_bwd(const float* g_frames, const float* sr, const float* 
  *   waited for.  Not inside a stream capture (P2PHD_EINVAL).  A stitch whose every L is 0 launches nothing.  Grid: blockIdx.y =
  *   clip row, grid.x from p2phd_stream_grid("segments_gather_ragged" / "segments_stitch_ragged") of the LONGEST row's outputs
  *   (S_j * T resp. L_j); a shorter row's surplus workgroups leave at once.
+ * p2phd_segments_stitch_stream: the stitch of ONE WINDOW of a clip that goes through the pipeline in windows -- K consecutive
+ *   segments s0 .. s0 + K - 1 of each of C channels, seg [C * K, T] channel-major -- in one launch, one count of "stitch".
+ *   out[c * ld + n], 0 <= n < n_out <= (K - 1) stride + T, is the clip's stitched sample at position s0 stride + n: bit for bit
+ *   row c of p2phd_segments_stitch_planar on the whole clip's segments there, for every n < K stride, and for every n where the
+ *   window holds the clip's last segment (a sample at or beyond K stride of any other window also belongs to the segment behind
+ *   it, which this call has not seen).  The window's segment 0 cross-fades with `carry_in` [C][V], V = T - stride: the raw,
+ *   unscaled samples [stride, T) of each channel's segment s0 - 1, as the call on the window before left them in its `carry_out`.
+ *   `first` != 0: the window holds the clip's segment 0, which does not fade in; carry_in is not read (it may be NULL).
+ *   `carry_out` [C][V] receives this window's own tails, seg[c, K - 1, stride .. T); NULL: none are kept (the last window).  With
+ *   V = 0 neither is read or written.  The same row body as every other stitch: the fp64 sine, one rounding.  Grid: blockIdx.y =
+ *   channel, grid.x from p2phd_stream_grid("segments_stitch_stream") of n_out; a row takes the 16-byte paths by its own base in
+ *   seg and out.  No atomics, no scratch, capturable, nothing is waited for.  Errors (P2PHD_EINVAL): K < 1, T < 1, V outside
+ *   [0, T/2], C outside 1 .. 65535, n_out beyond the span, ld < n_out, first == 0 with V > 0 and carry_in NULL, carry_out
+ *   overlapping carry_in, seg or out (two carry buffers take turns), seg or out NULL.  n_out = 0 launches nothing and leaves
+ *   carry_out as it is.
  * ---------------------------------------------------------------------------------------- */
 int p2phd_segments_gather(const float* audio, int64_t L, int64_t T, int64_t stride, int64_t S, float* out, void* stream);
 int p2phd_segments_stitch(const float* seg, int64_t S, int64_t T, int64_t stride, float gain, float* out, int64_t L_out,
@@ -248,6 +263,8 @@ int p2phd_segments_gather_ragged(const int64_t* table, int64_t N, int64_t T, int
                                  void* stream);
 int p2phd_segments_stitch_ragged(const float* seg, const int64_t* table, int64_t N, int64_t rows, int64_t T, int64_t stride, float gain,
                                  void* table_dev, void* stream);
+int p2phd_segments_stitch_stream(const float* seg, int64_t C, int64_t K, int64_t T, int64_t stride, float gain, const float* carry_in,
+                                 float* carry_out, int first, float* out, int64_t ld, int64_t n_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * PCM codec of whole-file generation, csrc/pcm.hip.  Launch family "pcm" (a decode and an encode count 1 each; frames = 0
@@ -1183,6 +1200,8 @@ int p2phd_reduction_rows(const char* family, int dtype, int N, int64_t P, int C,
  *   segments_gather(_planar), segments_stitch(_planar)   outputs per row (S * T, resp. L_out); a quad per thread; 16384
  *   segments_gather_ragged, segments_stitch_ragged       outputs of the longest clip row (S_j * T, resp. L_j); a quad per thread;
  *                                                         1024 per clip row (grid.y = clip rows, up to 65535 of them)
+ *   segments_stitch_stream                                outputs per channel of the window (n_out); a quad per thread; 1024 per
+ *                                                         channel (grid.y = channels)
  *   pcm_decode(_ex), pcm_encode, pcm_encode_ex            interleaved samples (frames * channels); 16384
  *   pcm_peak                                              frames per row, rows = channels; four 16-byte pieces in flight per
  *                                                         thread; min(2048 / channels, what the reduction scratch holds)

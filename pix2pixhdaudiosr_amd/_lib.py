@@ -51,6 +51,7 @@ SIGNATURES = {
     "p2phd_segments_ragged_table_bytes": (_i64, [_i64]),
     "p2phd_segments_gather_ragged": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "p2phd_segments_stitch_ragged": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp]),
+    "p2phd_segments_stitch_stream": (_i32, [_vp, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _i32, _vp, _i64, _i64, _vp]),
     "p2phd_pcm_decode": (_i32, [_vp, _i64, _i32, _i32, _vp, _i64, _vp]),
     "p2phd_pcm_decode_ex": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
     "p2phd_pcm_encode": (_i32, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),

@@ -12,6 +12,9 @@
 // The `_ragged` entries run them over N clip rows that share nothing but T and stride -- channels of several files, each with its
 // own base, length L_j and segment count S_j, row j's segments at rows row0_j .. row0_j + S_j - 1 of one seg[rows, T] -- through
 // the same two row bodies (gather_row, stitch_row): a row's bits are the planar entry's on that clip alone.
+// The `_stream` entry stitches one window of a clip that is generated in windows -- K consecutive segments of every channel -- and
+// fades its first segment with the tail the window before left in a carry buffer, through stitch_row again: the windows' outputs
+// laid one behind the other are the planar stitch of the whole clip.
 //
 // Both are streaming kernels (one pass, no reuse, no atomics): one thread per four consecutive outputs, 16-byte accesses
 // where the addresses allow.  The cross-fade is evaluated in double and rounded once, so an output is the correctly rounded
@@ -76,20 +79,23 @@ __global__ __launch_bounds__(kThreads) void segments_gather_ragged_kernel(const 
   gather_row(audio, row[1], T, stride, total, out, vec4);
 }
 
-__device__ __forceinline__ float stitch_one(const float* __restrict__ seg, long n, long S, long T, long stride, long V, double gain,
-                                            double step) {
+// `head`: the tail of the segment in front of segment 0 -- head[i] is its sample i + stride, i < V -- or nullptr where segment 0 is
+// the clip's first (every entry but the streamed one).  A later segment's is inside `seg`.
+__device__ __forceinline__ float stitch_one(const float* __restrict__ seg, const float* __restrict__ head, long n, long S, long T, long stride,
+                                            long V, double gain, double step) {
   const long a = min(n / stride, S - 1);                          // the latest segment that covers n
   const long i = n - a * stride;
   const double cur = (double)seg[a * T + i];
-  if (a == 0 || i >= V) return (float)(gain * cur);
+  const float* tail = a > 0 ? seg + (a - 1) * T + stride : head;  // the previous segment's samples [stride, T)
+  if (tail == nullptr || i >= V) return (float)(gain * cur);
   const double sn = sin(((double)i + 0.5) * step);
   const double w = sn * sn;
-  return (float)(gain * (w * cur + (1.0 - w) * (double)seg[(a - 1) * T + i + stride]));
+  return (float)(gain * (w * cur + (1.0 - w) * (double)tail[i]));
 }
 
 // One row of a stitch: seg[S, T] -> out[L_out].  The body of every stitch kernel of this file.
-__device__ __forceinline__ void stitch_row(const float* __restrict__ seg, long S, long T, long stride, long V, float gain,
-                                           float* __restrict__ out, long L_out, int vec4) {
+__device__ __forceinline__ void stitch_row(const float* __restrict__ seg, const float* __restrict__ head, long S, long T, long stride, long V,
+                                           float gain, float* __restrict__ out, long L_out, int vec4) {
   const long quads = (L_out + 3) >> 2;
   const double step = V > 0 ? 3.14159265358979323846 / (2.0 * (double)V) : 0.0;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
@@ -98,25 +104,25 @@ __device__ __forceinline__ void stitch_row(const float* __restrict__ seg, long S
       const long a = min(n0 / stride, S - 1), i0 = n0 - a * stride;
       const long src = a * T + i0;
       float4 v;
-      if ((a == 0 || i0 >= V) && a == min((n0 + 3) / stride, S - 1) && (src & 3) == 0) {     // plain run of one segment
+      if (((a == 0 && head == nullptr) || i0 >= V) && a == min((n0 + 3) / stride, S - 1) && (src & 3) == 0) {     // plain run of one segment
         v = *reinterpret_cast<const float4*>(seg + src);
         v.x *= gain; v.y *= gain; v.z *= gain; v.w *= gain;
       } else {
-        v.x = stitch_one(seg, n0, S, T, stride, V, gain, step);
-        v.y = stitch_one(seg, n0 + 1, S, T, stride, V, gain, step);
-        v.z = stitch_one(seg, n0 + 2, S, T, stride, V, gain, step);
-        v.w = stitch_one(seg, n0 + 3, S, T, stride, V, gain, step);
+        v.x = stitch_one(seg, head, n0, S, T, stride, V, gain, step);
+        v.y = stitch_one(seg, head, n0 + 1, S, T, stride, V, gain, step);
+        v.z = stitch_one(seg, head, n0 + 2, S, T, stride, V, gain, step);
+        v.w = stitch_one(seg, head, n0 + 3, S, T, stride, V, gain, step);
       }
       *reinterpret_cast<float4*>(out + n0) = v;
     } else {
-      for (long n = n0; n < min(n0 + 4, L_out); ++n) out[n] = stitch_one(seg, n, S, T, stride, V, gain, step);
+      for (long n = n0; n < min(n0 + 4, L_out); ++n) out[n] = stitch_one(seg, head, n, S, T, stride, V, gain, step);
     }
   }
 }
 
 __global__ __launch_bounds__(kThreads) void segments_stitch_kernel(const float* __restrict__ seg, long S, long T, long stride, long V,
                                                                    float gain, float* __restrict__ out, long L_out, int vec4, long ld) {
-  stitch_row(seg + (long)blockIdx.y * S * T, S, T, stride, V, gain, out + (long)blockIdx.y * ld, L_out, vec4);
+  stitch_row(seg + (long)blockIdx.y * S * T, nullptr, S, T, stride, V, gain, out + (long)blockIdx.y * ld, L_out, vec4);
 }
 
 __global__ __launch_bounds__(kThreads) void segments_stitch_ragged_kernel(const float* __restrict__ seg, const long* __restrict__ table,
@@ -127,7 +133,28 @@ __global__ __launch_bounds__(kThreads) void segments_stitch_ragged_kernel(const 
   float* out = reinterpret_cast<float*>(row[0]);
   const float* mine = seg + row[3] * T;
   const int vec4 = ((reinterpret_cast<uintptr_t>(mine) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-  stitch_row(mine, row[2], T, stride, V, gain, out, L_out, vec4);
+  stitch_row(mine, nullptr, row[2], T, stride, V, gain, out, L_out, vec4);
+}
+
+// The streamed stitch: one window of a clip that goes through the pipeline in windows, K consecutive segments of each of C
+// channels.  blockIdx.y = channel.  Segment 0 of the window cross-fades with `carry_in`, the raw tail the window before it left
+// (nullptr: the window holds the clip's first segment), through the one row body, so a sample is the whole-clip stitch's at its
+// position, bit for bit.  The window's own last tail -- seg[c, K - 1, stride .. T) as it stands, unscaled -- goes to `carry_out` for
+// the window behind it: V floats per channel, written by the grid's first threads with plain stores.  The 16-byte paths are the
+// row's own: its base in `seg` and in `out` decide, not the launch.
+__global__ __launch_bounds__(kThreads) void segments_stitch_stream_kernel(const float* __restrict__ seg, long K, long T, long stride, long V,
+                                                                          float gain, const float* __restrict__ carry_in,
+                                                                          float* __restrict__ carry_out, float* __restrict__ out, long ld,
+                                                                          long n_out) {
+  const long c = blockIdx.y;
+  const float* mine = seg + c * K * T;
+  float* dst = out + c * ld;
+  const int vec4 = ((reinterpret_cast<uintptr_t>(mine) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  stitch_row(mine, carry_in != nullptr ? carry_in + c * V : nullptr, K, T, stride, V, gain, dst, n_out, vec4);
+  if (carry_out != nullptr) {
+    const float* tail = mine + (K - 1) * T + stride;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (long)gridDim.x * blockDim.x) carry_out[c * V + i] = tail[i];
+  }
 }
 
 int stream_grid(int64_t elems) { return p2phd::stream_grid_of(p2phd::SG_STITCH, P2PHD_F32, elems, 1).used; }     // (streamgrid.h)
@@ -278,6 +305,38 @@ extern "C" int p2phd_segments_stitch_ragged(const float* seg, const int64_t* tab
   if (int rc = send_table(what, table, N, table_dev, (hipStream_t)stream)) return rc;
   hipLaunchKernelGGL(segments_stitch_ragged_kernel, dim3(ragged_grid(longest), (unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, seg,
                      static_cast<const long*>(table_dev), (long)T, (long)stride, (long)(T - stride), gain);
+  ++p2phd::g_launch_count[p2phd::LC_STITCH];
+  return p2phd::check_launch(what);
+}
+
+extern "C" int p2phd_segments_stitch_stream(const float* seg, int64_t C, int64_t K, int64_t T, int64_t stride, float gain,
+                                            const float* carry_in, float* carry_out, int first, float* out, int64_t ld, int64_t n_out,
+                                            void* stream) {
+  const char* what = "segments_stitch_stream";
+  P2PHD_REQUIRE(K >= 1 && T >= 1, "%s: need K >= 1 and T >= 1 (K %lld, T %lld)", what, (long long)K, (long long)T);
+  const int64_t V = T - stride;
+  P2PHD_REQUIRE(V >= 0 && V <= T / 2, "%s: the overlap T - stride must be in [0, T/2], got %lld (T %lld)", what, (long long)V, (long long)T);
+  P2PHD_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535, got %lld", what, (long long)C);
+  P2PHD_REQUIRE(K <= (int64_t(1) << 40) / T / C, "%s: C * K * T too large", what);
+  P2PHD_REQUIRE(n_out >= 0 && n_out <= (K - 1) * stride + T, "%s: n_out %lld is beyond the %lld samples the segments span", what,
+                (long long)n_out, (long long)((K - 1) * stride + T));
+  P2PHD_REQUIRE(ld >= n_out, "%s: ld %lld is shorter than n_out %lld", what, (long long)ld, (long long)n_out);
+  const bool head = first == 0 && V > 0;                          // the window's segment 0 has a segment in front of it to fade with
+  P2PHD_REQUIRE(!head || carry_in != nullptr, "%s: a window behind the first needs carry_in (V %lld)", what, (long long)V);
+  if (carry_out != nullptr && V > 0) {
+    const auto overlaps = [&](const void* p, int64_t floats) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(carry_out), b = reinterpret_cast<uintptr_t>(p);
+      return p != nullptr && floats > 0 && a < b + (uintptr_t)floats * 4 && b < a + (uintptr_t)(C * V) * 4;
+    };
+    P2PHD_REQUIRE(!overlaps(carry_in, C * V) && !overlaps(seg, C * K * T) && !overlaps(out, n_out > 0 ? (C - 1) * ld + n_out : 0),
+                  "%s: carry_out overlaps carry_in, seg or out (two carry buffers take turns)", what);
+  }
+  if (n_out == 0) return P2PHD_OK;
+  P2PHD_REQUIRE(seg && out, "%s: null pointer", what);
+  const int grid = p2phd::stream_grid_of(p2phd::SG_STITCH_STREAM, P2PHD_F32, n_out, 1).used;     // (streamgrid.h)
+  hipLaunchKernelGGL(segments_stitch_stream_kernel, dim3(grid, (unsigned)C), dim3(kThreads), 0, (hipStream_t)stream, seg, (long)K, (long)T,
+                     (long)stride, (long)V, gain, head ? carry_in : static_cast<const float*>(nullptr), V > 0 ? carry_out : static_cast<float*>(nullptr),
+                     out, (long)ld, (long)n_out);
   ++p2phd::g_launch_count[p2phd::LC_STITCH];
   return p2phd::check_launch(what);
 }

@@ -19,6 +19,7 @@ struct StreamGrid {
 enum StreamFamily {
   SG_STITCH,            // segments_gather(_planar), segments_stitch(_planar): outputs per row, a quad per thread
   SG_STITCH_RAGGED,     // segments_gather_ragged, segments_stitch_ragged: outputs of the LONGEST clip row, a quad per thread; grid.y = clip rows
+  SG_STITCH_STREAM,     // segments_stitch_stream: outputs per row of one window, a quad per thread; grid.y = channels
   SG_PCM,               // pcm_decode(_ex), pcm_encode(_ex): interleaved samples, one per thread
   SG_PCM_PEAK,          // pcm_peak: frames per row; four 16-byte pieces in flight per thread; rows = channels
   SG_STEREO_VEC,        // stereo_matrix, aligned rows: a quad of samples per thread
@@ -43,6 +44,7 @@ inline StreamFamily stream_family(const char* name) {
   static const struct { const char* name; StreamFamily f; } table[] = {
       {"segments_gather", SG_STITCH}, {"segments_gather_planar", SG_STITCH}, {"segments_stitch", SG_STITCH},
       {"segments_stitch_planar", SG_STITCH}, {"segments_gather_ragged", SG_STITCH_RAGGED}, {"segments_stitch_ragged", SG_STITCH_RAGGED},
+      {"segments_stitch_stream", SG_STITCH_STREAM},
       {"pcm_decode", SG_PCM}, {"pcm_decode_ex", SG_PCM}, {"pcm_encode", SG_PCM}, {"pcm_encode_ex", SG_PCM},
       {"pcm_peak", SG_PCM_PEAK}, {"stereo_matrix", SG_STEREO_VEC}, {"stereo_matrix_scalar", SG_STEREO_SCALAR},
       {"loudness_blocks", SG_LOUDNESS}, {"loudness_short_term", SG_LOUDNESS}, {"avgpool3s2_fwd", SG_ITEMS},
@@ -76,6 +78,8 @@ inline StreamGrid stream_grid_of(StreamFamily f, int dtype, int64_t work, int ro
     // per clip row: a launch has up to 65535 rows of any lengths and every row gets the grid of the longest, so the cap is a row's
     // and small -- 1024 workgroups, four a CU, stream a lone long row; many short rows fill the chip by their count
     case SG_STITCH_RAGGED:  return stream_capped(cdiv(work, 4), 1024, 4);
+    // per channel of a window: a window is seconds long and a file's channels few, so the cap is the ragged rows'
+    case SG_STITCH_STREAM:  return stream_capped(cdiv(work, 4), 1024, 4);
     case SG_PCM:            return stream_capped(work, 16384, 1);
     case SG_PCM_PEAK: {
       // workgroups per row: enough to keep every CU busy with rows of any count, a partial table (5 words per workgroup) that

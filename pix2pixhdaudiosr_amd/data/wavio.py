@@ -219,8 +219,38 @@ def read_payload(path, into=None):
     return buf[:n], meta
 
 
+def read_frames(path, meta, start, stop, into=None):
+    """-> the bytes of frames [start, stop) of a file whose coding has a fixed size per frame (PCM, IEEE float, G.711: `meta` is the
+    file's WavInfo, or the AudioInfo of an AIFF, AU or SPHERE file, whose sound data is laid out the same way), undecoded: one seek
+    and one read.  `into`: as read_payload's.  The header is not parsed again; an IMA ADPCM file, whose frames share blocks, is a
+    ValueError, and so is a range outside the file's frames."""
+    if meta.format_tag == 0x11:
+        raise ValueError(f"{path}: IMA ADPCM has no fixed size per frame: a frame range of it is not read")
+    start, stop = int(start), int(stop)
+    if not 0 <= start <= stop <= meta.num_frames:
+        raise ValueError(f"{path}: frames {start}..{stop} are not inside the file's {meta.num_frames}")
+    n = (stop - start) * meta.block_align
+    buf = bytearray(n) if into is None else into(n) if callable(into) else into
+    buf = memoryview(buf).cast("B")
+    if len(buf) < n:
+        raise ValueError(f"{path}: the buffer holds {len(buf)} bytes, the frames {n}")
+    with open(path, "rb") as f:
+        f.seek(meta.data_offset + start * meta.block_align)
+        if n and f.readinto(buf[:n]) != n:
+            raise ValueError(f"{path}: short read of the data chunk")
+    return buf[:n]
+
+
+def frame_info(path):
+    """-> WavInfo with num_frames cut to the whole frames the file holds, as read_payload returns it: what read_frames is given."""
+    meta, held = _parse(path)
+    if meta.format_tag not in CODED_TAGS:
+        meta = meta._replace(num_frames=min(meta.num_frames, held // meta.block_align))
+    return meta
+
+
 # encoding -> (format tag, bits per sample)
-ENCODINGS = {"pcm16": (1, 16), "pcm24": (1, 24), "float32": (3, 32)}
+ENCODINGS ={"pcm16": (1, 16), "pcm24": (1, 24), "float32": (3, 32)}
 
 
 def write_payload(path, payload, sample_rate, channels, encoding="pcm16"):

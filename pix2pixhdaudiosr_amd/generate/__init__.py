@@ -41,6 +41,12 @@ N consecutive files of a folder share those groups: the rows of all their channe
 back in one launch (`segments_stitch_ragged`), so sixteen utterances of 6 rows run 3 groups of 32 and not 16.  Everything in front of
 and behind the rows stays per file; a file's rows, ranges and, with a seed, mask noise are those of a run of its own (`pack_plan`).
 
+`--stream_seconds W` (opt-in, an option of `--segment_norm`; `enhance_file(stream_seconds=W)`, generate/stream.py) sends a file through
+in windows of about W seconds -- whole segments, whole groups (`stream_plan`) -- each read, generated, stitched with the carry of the
+window before (`segments_stitch_stream`, csrc/stitch.hip), encoded and appended to the output while the next one is read: memory is
+a window's whatever the file's length, and the file is the unstreamed one byte for byte where the model draws no mask noise.  What
+needs the whole clip or a figure of the whole file is refused with it (`check_stream`).
+
 The two ends of the file path run on the device as well (csrc/pcm.hip): the data chunk of the input goes up as bytes and is
 decoded there, the output is encoded there and comes back as the payload to write; the host only moves bytes.
 
@@ -129,9 +135,9 @@ clip to the input's level or to a level such as -26 with one gain for all channe
 from .cli import _parser, _run, main, opt_from_file, parse_opt_file                                        # noqa: F401
 from .ops import (PCM_FORMATS, G711_LAWS, g711_decode, ima_decode, flac_decode, flac_encode, rate_convert, rateconv_coefficients, rateconv_out_len, rateconv_plan, bandwidth, bandwidth_detect, cross_spectrum, ltas, stereo_bands, stereo_image, stereo_matrix, crossover, crossover_coefficients, limit, limiter_apply, limiter_envelope, limiter_window, loudness, loudness_blocks, loudness_coefficients, loudness_gate,  # noqa: F401
                   loudness_gate_blocks, loudness_hops, loudness_range, loudness_short_term, pcm_decode, pcm_encode, pcm_peaks, shaper_coefficients, segments_gather, segments_gather_planar, segments_gather_ragged, segments_stitch,
-                  segments_stitch_planar, segments_stitch_ragged, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks,
+                  segments_stitch_planar, segments_stitch_ragged, segments_stitch_stream, spectrogram_rgb, stft_db, true_peak_coefficients, true_peaks,
                   speech_level, speech_level_consts, speech_level_counts, speech_level_decide, speech_level_envelope)
-from .plans import (INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, check_segment_norm, group_rows_plan, PACK_MAX_BYTES, check_pack_files, pack_plan, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
+from .plans import (check_stream, resample_geometry, resample_out_len, stream_plan, INPUT_FORMATS, check_input_formats, NORM_SCOPES, check_norm_scope, check_segment_norm, group_rows_plan, PACK_MAX_BYTES, check_pack_files, pack_plan, OUTPUT_MIN_RATE, RATECONV_DEFAULTS, check_output_rate, ALBUM_CACHE_BYTES, BANDWIDTH_DEFAULTS, STEREO_DEFAULTS, STEREO_MODES, STEREO_NOTE_DROP, check_stereo, check_stereo_report, stereo_figures, stereo_notes, stereo_split_bin, CROSSOVER_AUTO, bandwidth_notes, bandwidth_rel, check_bandwidth, crossover_auto_floor_hz, crossover_auto_plan, CLIP_MODES, CROSSOVER_ATTEN_DB, CROSSOVER_BETA, CROSSOVER_MAX_TAPS, CROSSOVERS, DITHERS, DITHER_CHUNK, DITHER_CURVES, SHAPED_RATES, dither_line,  # noqa: F401
                     LIMITER_HOLD_MS, LIMITER_LOOKAHEAD_MS, LIMITER_MAX_HOLD, LIMITER_MAX_LOOKAHEAD, LOUDNESS_MAX_CHANNELS, LOUDNESS_MAX_GAIN_DB, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS,
                     PCM_ENCODINGS, SPECTROGRAM_DEFAULTS, SPECTROGRAM_LUT_ANCHORS, TRUEPEAK_BETA, TRUEPEAK_TAPS_PER_PHASE, ClipError, ceiling_from_dbfs, check_crossover,
                     check_dither, check_encoding, check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_lowband, check_output_options, check_paths,

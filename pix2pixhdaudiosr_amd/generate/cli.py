@@ -12,7 +12,7 @@ import torch
 
 from .ops import shaper_coefficients
 from .plans import (check_container, check_input_formats, CLIP_MODES, CROSSOVER_AUTO, DITHER_CURVES, check_dither, dither_line, LOUDNESS_MODES, LOUDNESS_SCOPES, LOWBANDS, PCM_ENCODINGS, ClipError, check_crossover, check_limiter, check_loudness, check_loudness_scope, check_speech_level, check_speech_level_rate, SPEECH_LEVEL_MODES, check_lowband,
-                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_segment_norm, check_pack_files, check_stereo_report, output_rate_line, spectro_bins)
+                    check_output_options, check_output_rate, check_paths, check_spectrogram, check_bandwidth, check_segment_norm, check_pack_files, check_stereo_report, check_stream, select_channels, stream_plan, output_rate_line, spectro_bins)
 from .report import _print_album, _print_bandwidth, _print_crossover, _print_limiter, _print_loudness, _print_loudness_range, _print_speech_level, _print_metrics, _print_metrics_ext, _print_peaks, _print_stereo, _print_unwritten, metrics_rows, write_metrics_csv
 from .resolver import SuperResolver, per_channel_metrics
 
@@ -327,6 +327,13 @@ def _parser():
                          "utterances runs full groups where file by file each one's last group is filled up with silent segments; "
                          "a file's own segments, ranges and (with a seed) mask noise stay those of N = 1; one start-up line more; not "
                          "with --loudness_scope folder (default: 1, every file on its own)")
+    ap.add_argument("--stream_seconds", type=float, default=None, metavar="W",
+                    help="with --segment_norm: send every file through in windows of about W seconds -- whole segments, whole groups -- "
+                         "each read, generated, encoded and appended to the output while the next is read, so that memory is a "
+                         "window's whatever the file's length; the written file is the same where the model draws no mask noise, "
+                         "which is otherwise drawn in window order; PCM, float and G.711 inputs (not FLAC, not IMA ADPCM); not with "
+                         "the crossover, --container flac, --dither shaped, --pack_files, --output_rate, --metrics_ext or any option "
+                         "that measures the whole file; one start-up line more (default: off, a file is one unit)")
     ap.add_argument("--stereo_report", action="store_true",
                     help="report how the left and right channel of a file written with two channels correlate below and above the low "
                          "rate's Nyquist frequency -- for the input the generator was given, the generated clip and, for a full-band "
@@ -407,6 +414,11 @@ def main(argv=None):
             picture['verify_input'] = True
         if a.pack_files > 1:
             picture['pack_files'] = a.pack_files
+        if check_stream(a.stream_seconds, "generate", a.segment_norm, a.crossover, None, loudness=a.loudness, speech_level=a.speech_level, clip=a.clip,
+                        true_peak=a.true_peak, limiter=a.limiter, report_peaks=a.report_peaks, spectrogram=a.spectrogram, bandwidth=a.bandwidth,
+                        stereo_report=a.stereo_report, output_rate=a.output_rate, extended_metrics=a.metrics_ext, container=a.container,
+                        dither=a.dither, pack_files=a.pack_files, loudness_scope=a.loudness_scope) is not None:
+            picture['stream_seconds'] = a.stream_seconds
         if check_container(a.container, a.flac_block, a.flac_md5, a.encoding, a.output_rate or 48000, "generate",
                            **({} if a.flac_lpc is None else dict(flac_lpc=a.flac_lpc))) is not None:
             picture.update(container=a.container, **{k: v for k, v in (('flac_block', a.flac_block), ('flac_md5', a.flac_md5 or None), ('flac_lpc', a.flac_lpc))
@@ -470,6 +482,8 @@ def main(argv=None):
         print('normalisation: one range per segment')
     if a.pack_files > 1:                                                    # (without the option: no line more than before)
         print('packing: up to %d files share groups' % a.pack_files)
+    if a.stream_seconds is not None:                                        # (without the option: no line more than before)
+        print(_stream_line(a, sr, folder_mode))
     if rc is not None:                                                      # (without the option: no line more than before)
         print(output_rate_line(rc))
     if a.dither == 'shaped':                                                # (without the option: no line more than before)
@@ -482,6 +496,21 @@ def main(argv=None):
     except ClipError as e:
         print('error: %s' % e, file=sys.stderr)                             # --clip error: the file that would clip
         return 1
+
+
+def _stream_line(a, sr, folder_mode):
+    """--stream_seconds: the start-up line.  The segments per window follow from the written channel count (plans.stream_plan): a
+    single input's own, read from its header; a folder's files are counted as one channel each here and planned one by one."""
+    channels = 1
+    if not folder_mode:
+        try:
+            from ..data import audiofile
+            channels = select_channels(a.channels, audiofile.info(a.input).num_channels)
+        except (ValueError, OSError, EOFError):                             # (enhance_file says what is wrong with it)
+            pass
+    plan = stream_plan(0, sr.opt.hr_sampling_rate, sr.opt.lr_sampling_rate, sr.opt.hr_sampling_rate, True, sr.T, sr.overlap, channels, sr.batch,
+                       a.stream_seconds)
+    return 'streaming: windows of %d segments (%g s)' % (plan['K'], plan['K'] * plan['stride'] / float(sr.opt.hr_sampling_rate))
 
 
 def _print_report(a, name, wrote, r):
@@ -540,7 +569,9 @@ def _run(a, sr, stage, seed, rate, folder_mode):
                 print('mean over %d channels: LSD_LF %.4f  LSD_HF %.4f  SSNR_SR %.4f  SSNR_LR %.4f' % ((len(rows) - 1,) + rows[-1][7:]))
     else:
         res = sr.enhance_file(a.input, a.output, a.is_lr_input, a.channels, a.encoding, extended_metrics=a.metrics_ext, **stage)
-        m, written = per_channel_metrics(res['metrics'], a.channels), res['sr'].shape[0]
+        streamed = res.get('stream')                                        # (--stream_seconds: no clip comes back)
+        out_frames = res['sr'].shape[-1] if streamed is None else streamed['out_frames']
+        m, written = per_channel_metrics(res['metrics'], a.channels), (res['sr'] if streamed is None else res['norm']).shape[0]
         ext = res.get('metrics_ext')
         _print_unwritten(a.input, res['info'].num_channels, written)
         for c, mc in enumerate(m or ()):
@@ -549,11 +580,11 @@ def _run(a, sr, stage, seed, rate, folder_mode):
             if ext is not None:
                 _print_metrics_ext(ext[c], prefix)
         if written == 1:
-            print('wrote %s (%d samples at %d Hz)' % (a.output, res['sr'].shape[-1], rate))
+            print('wrote %s (%d samples at %d Hz)' % (a.output, out_frames, rate))
         else:
-            print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, res['sr'].shape[-1], rate, written))
+            print('wrote %s (%d samples at %d Hz, %d channels)' % (a.output, out_frames, rate, written))
         # the result in a record's shape: every option's key as enhance_file returned it, a record's own five beside them
-        records = [dict(res, path=os.path.basename(a.input), out_frames=res['sr'].shape[-1], metrics=m, metrics_ext=ext, output=res.get('output'),
+        records = [dict(res, path=os.path.basename(a.input), out_frames=out_frames, metrics=m, metrics_ext=ext, output=res.get('output'),
                         loudness=res.get('loudness'))]
         _print_report(a, a.output, a.output, records[0])
     if a.metrics_csv:

@@ -137,7 +137,33 @@ def segments_stitch_ragged(seg, lengths, channel_counts, stride, gain=1.0):
     return outs
 
 
-PCM_BIG_ENDIAN, PCM_SIGNED8 = 1, 2                                       # P2PHD_PCM_* flags of include/p2phd.h
+def segments_stitch_stream(seg, C, stride, gain=1.0, carry_in=None, carry_out=None, first=False, out_length=None):
+    """One window of a clip that is stitched in windows (p2phd_segments_stitch_stream): seg [C * K, T] f32 on the GPU, channel-major,
+    the K consecutive segments s0 .. s0 + K - 1 of every channel -> [C, out_length] (default K * stride: what a window that is not
+    the clip's last emits): the clip's stitched samples from position s0 * stride on, bit for bit those of segments_stitch_planar on
+    the whole clip (beyond K * stride only in the clip's last window).  `carry_in` [C, T - stride]: the carry_out of the call on the
+    window before; not read with `first` (the window holds the clip's segment 0).  `carry_out` [C, T - stride] or None: receives this
+    window's own raw tails; it may not overlap carry_in -- two buffers take turns.  One launch of the family "stitch"."""
+    s = _lib.require_gpu_tensor(seg, "segments_stitch_stream: seg", torch.float32)
+    C = int(C)
+    if s.dim() != 2 or C < 1 or s.shape[0] % C or s.shape[0] < C:
+        raise ValueError("segments_stitch_stream: expected [C * K, T] with C = %d and K >= 1, got shape %s" % (C, tuple(s.shape)))
+    K, T, stride = s.shape[0] // C, s.shape[1], int(stride)
+    V = T - stride
+    n_out = K * stride if out_length is None else int(out_length)
+    for name, t in (("carry_in", None if first else carry_in), ("carry_out", carry_out)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, "segments_stitch_stream: " + name, torch.float32)
+            if tuple(t.shape) != (C, max(V, 0)):
+                raise ValueError("segments_stitch_stream: %s must be [%d, %d], got shape %s" % (name, C, max(V, 0), tuple(t.shape)))
+    out = torch.empty((C, max(n_out, 0)), dtype=torch.float32, device=s.device)
+    _lib.check(_lib.lib().p2phd_segments_stitch_stream(_lib.ptr(s), C, K, T, stride, float(gain), None if first or carry_in is None else _lib.ptr(carry_in),
+                                                       None if carry_out is None else _lib.ptr(carry_out), 1 if first else 0, _lib.ptr(out),
+                                                       max(n_out, 0), n_out, _lib.stream_ptr()), "segments_stitch_stream")
+    return out
+
+
+PCM_BIG_ENDIAN, PCM_SIGNED8 = 1, 2                                      # P2PHD_PCM_* flags of include/p2phd.h
 
 
 def pcm_decode(payload, frames, channels, format_tag, bits, big_endian=False, signed8=False):

@@ -429,6 +429,109 @@ def pack_plan(sizes, pack_files, max_bytes=PACK_MAX_BYTES):
     return packs
 
 
+def resample_geometry(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """(o, n, width, klen) of data.resample between two rates -- p2phd_resample_geometry's arithmetic, restated for the host: o and
+    n are the rates over their common divisor, an output block of n samples reads the klen = 2 * width + o inputs from j * o - width."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq < 1 or new_freq < 1:
+        raise ValueError("resample_geometry: sample rates must be positive, got %d -> %d" % (orig_freq, new_freq))
+    gd = math.gcd(orig_freq, new_freq)
+    o, n = orig_freq // gd, new_freq // gd
+    width = int(math.ceil(lowpass_filter_width * o / (min(o, n) * rolloff)))
+    return o, n, width, 2 * width + o
+
+
+def resample_out_len(T, orig_freq, new_freq):
+    """p2phd_resample_out_len: ceil(T * new / orig)."""
+    gd = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // gd, int(new_freq) // gd
+    return (n * int(T) + o - 1) // o
+
+
+def check_stream(stream_seconds, who="enhance_file", segment_norm=False, crossover=None, hr_rate=None, loudness=None, speech_level=None,
+                 clip='clamp', true_peak=False, limiter=False, report_peaks=False, spectrogram=None, bandwidth=False, stereo_report=False,
+                 output_rate=None, extended_metrics=False, container='wav', dither=None, pack_files=1, loudness_scope='file'):
+    """Validates the option stream_seconds against everything it is not built with -> None (off), or the window's length in seconds.
+    A streamed file is never on the device as a whole: what needs the whole clip, or a figure of the whole file, is a ValueError
+    that names the option, before a file is opened."""
+    if stream_seconds is None:
+        return None
+    w = stream_seconds
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or not w > 0:
+        raise ValueError("%s: stream_seconds must be a finite number above 0, got %r" % (who, stream_seconds))
+    if not segment_norm:
+        raise ValueError("%s: stream_seconds sends a file through in windows, which needs segment_norm: only there does a segment's "
+                         "range not depend on the rest of the file" % who)
+    if crossover is not None:
+        raise ValueError("%s: stream_seconds is not built with the crossover (its filter reads across the windows)" % who)
+    whole = (('loudness', loudness is not None), ('speech_level', speech_level is not None), ('clip=%r' % (clip,), clip != 'clamp'),
+             ('true_peak', bool(true_peak)), ('limiter', bool(limiter)), ('report_peaks', bool(report_peaks)),
+             ('spectrogram', spectrogram is not None), ('bandwidth', bool(bandwidth)), ('stereo_report', bool(stereo_report)),
+             ('output_rate', output_rate is not None and (hr_rate is None or int(output_rate) != int(hr_rate))),
+             ('extended_metrics', bool(extended_metrics)), ("container='flac'", container == 'flac'), ("dither='shaped'", dither == 'shaped'),
+             ('pack_files > 1', not isinstance(pack_files, int) or pack_files > 1), ("loudness_scope='folder'", loudness_scope == 'folder'))
+    for name, on in whole:
+        if on:
+            raise ValueError("%s: stream_seconds is not built with %s: it needs the whole clip, or a figure of the whole file" % (who, name))
+    return float(w)
+
+
+def _stage_inputs(A, B, o, n, width, len_in):
+    """The inputs a window must hold so that a resampler stage's outputs [A, B) come out as in a run over the whole row: the range
+    widened outward to whole blocks, a halo of `width` in front -- rounded up to whole blocks, so that the window starts on one -- and
+    of width + o behind, cut at the ends of the row."""
+    j_a, j_b = A // n, -(-B // n)
+    a = max(0, (j_a - -(-width // o)) * o)
+    b = min(len_in, j_b * o + width + o)
+    return a, max(a, b)
+
+
+def stream_plan(frames, in_rate, lr_rate, hr_rate, is_lr_input, T, overlap, C, batch, stream_seconds):
+    """How a file of `frames` frames at `in_rate` goes through the pipeline in windows of about `stream_seconds` -> {'L', 'S',
+    'stride', 'V' (segment_plan's, of the whole clip: L follows from the header alone), 'K' (segments per channel and window),
+    'stages' (the resamplers of the low-rate round trip that are not the identity, [(orig, new, o, n, width, rows in, rows out)]),
+    'windows'}.  K = max(1, round(stream_seconds * hr_rate / stride)), rounded up to a multiple of batch / gcd(batch, C): the C * K
+    rows of a window fill whole groups and only the last window has filler rows.  A window: {'s0', 's1' (its segments [s0, s1) of
+    every channel), 'emit' (the output positions it writes, [s0 * stride, s1 * stride), the last window up to L: the windows'
+    ranges partition [0, L) in order), 'need' (the round-tripped clip it gathers from, [s0 * stride, (s1 - 1) * stride + T) cut to
+    [0, L)), 'read' (the frames of the file to read), 'cuts' (per stage, the slice of its output that is the next stage's input
+    -- the last one's: the needed range -- as local indices (lo, hi)), 'inputs' (per stage, the range of its input row the window
+    holds)}.  A stage's window starts on a multiple of its o, so output m of the whole row is the window's output m - (start / o) * n,
+    computed from the same operands in the same order wherever every input the sum reads is inside the window or outside the row."""
+    frames, C, batch, T = int(frames), int(C), int(batch), int(T)
+    if frames < 0 or C < 1 or batch < 1:
+        raise ValueError("stream_plan: need frames >= 0, C >= 1 and batch >= 1, got %d, %d and %d" % (frames, C, batch))
+    if isinstance(stream_seconds, bool) or not isinstance(stream_seconds, (int, float)) or not math.isfinite(stream_seconds) or not stream_seconds > 0:
+        raise ValueError("stream_plan: stream_seconds must be a finite number above 0, got %r" % (stream_seconds,))
+    chain = [(in_rate, hr_rate)] if is_lr_input else [(in_rate, lr_rate), (lr_rate, hr_rate)]
+    stages, n_in = [], frames
+    for orig, new in chain:
+        if int(orig) == int(new):
+            continue
+        o, n, width, _ = resample_geometry(orig, new)
+        n_out = resample_out_len(n_in, orig, new)
+        stages.append((int(orig), int(new), o, n, width, n_in, n_out))
+        n_in = n_out
+    L = frames if not is_lr_input and int(in_rate) == int(hr_rate) else n_in       # (the round trip rounds the length up: cut)
+    S, stride, V = segment_plan(L, T, overlap)
+    unit = batch // math.gcd(batch, C)
+    K = max(1, int(math.floor(stream_seconds * hr_rate / stride + 0.5)))
+    K = -(-K // unit) * unit
+    windows = []
+    for s0 in range(0, S, K):
+        s1 = min(S, s0 + K)
+        need = (min(s0 * stride, L), min((s1 - 1) * stride + T, L))
+        inputs, cuts, (A, B) = [], [], need
+        for _, _, o, n, width, rows_in, _ in reversed(stages):
+            a, b = _stage_inputs(A, B, o, n, width, rows_in)
+            cuts.append((A - a // o * n, B - a // o * n))
+            inputs.append((a, b))
+            A, B = a, b
+        windows.append({'s0': s0, 's1': s1, 'emit': (s0 * stride, L if s1 == S else s1 * stride), 'need': need, 'read': (A, B),
+                        'cuts': cuts[::-1], 'inputs': inputs[::-1]})
+    return {'L': L, 'S': S, 'stride': stride, 'V': V, 'K': K, 'stages': stages, 'windows': windows}
+
+
 def check_stereo_report(stereo_report=False, opts=None, loudness_scope='file', who="enhance_file"):
     """Validates the stereo report option -> None (off), or the plan {'n_fft', 'hop'} that ops.stereo_image takes.  `stereo_report`:
     a bool.  `opts`: None or a dict of those two, None or absent standing for STEREO_DEFAULTS' value (hop: half of a given n_fft):

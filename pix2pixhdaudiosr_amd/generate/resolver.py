@@ -13,9 +13,10 @@ from .ops import (_loudness_views, _speech_level_views, bandwidth as _bandwidth,
                   rate_convert, spectrogram_rgb, speech_level as _speech_level, speech_level_packed_bytes, stereo_image as _stereo_image, stft_db)
 from .plans import (LOUDNESS_MAX_CHANNELS, SPEECH_LEVEL_MAX_CHANNELS, bandwidth_notes, check_bandwidth, check_container, check_dither, check_encoding,
                     check_limiter, check_loudness, check_loudness_rate, check_loudness_scope, check_output_options, check_output_rate, check_pack_files,
-                    check_spectrogram, check_speech_level, check_speech_level_rate, check_stereo_report, check_true_peak, group_rows_plan,
+                    check_spectrogram, check_speech_level, check_speech_level_rate, check_stereo_report, check_stream, check_true_peak, group_rows_plan,
                     loudness_channel_weights, pack_plan, plan_folder, segment_plan, select_channels, stereo_figures, stereo_notes, stereo_split_bin)
 from .rows import ClipPath
+from .stream import StreamPath
 
 # The validated options of enhance_file / enhance_folder (SuperResolver._options), each None where it is off: the output stage,
 # the true-peak, limiter, spectrogram, loudness, bandwidth, stereo-report and output-rate options, the album (loudness_scope 'folder')
@@ -90,7 +91,7 @@ def _named(local):
     return {name: local[name] for name in _OPTION_NAMES if name in local}
 
 
-class SuperResolver(ClipPath, FilePath):
+class SuperResolver(ClipPath, FilePath, StreamPath):
     """`model`: anything with `.inference(lr_audio, inst, noise=None) -> (sr_spectro, lr_pha, norm_param, lr_spectro)`
     (Pix2PixHDModel); its `mdct_type` picks the inverse transform.  `overlap`: shared fraction of a segment, [0, 0.5].
     `batch`: segments per group (default opt.batchSize).  `graph`: capture the chain of a full group once and replay it
@@ -491,7 +492,7 @@ class SuperResolver(ClipPath, FilePath):
                      limiter=False, limiter_lookahead_ms=None, limiter_hold_ms=None, loudness_range=False, loudness_scope='file',
                      bandwidth=False, bandwidth_opts=None, stereo_report=False, stereo_report_opts=None, output_rate=None, dither_curve=None,
                      dither_chunk=None, verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
-                     speech_level_max_gain_db=None, pack_files=1):
+                     speech_level_max_gain_db=None, pack_files=1, stream_seconds=None):
         """wav -> the low-rate round trip of AudioTestDataset (or, with `is_lr_input`, a plain upsample of a clip that is
         already band-limited) -> enhance_lr -> wav at opt.hr_sampling_rate.  `channels`: 'first' (the default), 'all', or an
         int N (the first N).  `encoding` of the output: 'pcm16' | 'pcm24' | 'float32'.  The data chunk is decoded and the
@@ -637,14 +638,39 @@ class SuperResolver(ClipPath, FilePath):
         `loudness` (two claims on one gain), not over more than 8 written channels, and only at rates in 8000 .. 192000: a
         ValueError each, the first and the last before a file is opened.
         `pack_files`: 1.  More -- files that share generator groups -- is an option of enhance_folder and a ValueError here, before
-        the file is opened; the two entry points take the same options."""
+        the file is opened; the two entry points take the same options.
+        `stream_seconds` (opt-in, an option of SuperResolver(segment_norm=True); None, the default: nothing changes): the file goes
+        through the pipeline in windows of about this many seconds (generate/stream.py; plans.stream_plan: whole segments, whole
+        groups) -- each read, decoded, taken through the low-rate round trip, gathered, generated, stitched (csrc/stitch.hip,
+        p2phd_segments_stitch_stream: two launches of the family "stitch" per window), encoded and appended to the output while the
+        next is read -- so that device and pinned memory are a window's whatever the file's length and the first bytes are written
+        when the second window is queued.  The written file is byte for byte the one written without the option where the model
+        draws no mask noise and a row of the generator does not depend on its batch neighbours; a group's noise is one torch.randn
+        drawn in window order, the unstreamed order with one written channel only.  The result's 'sr', 'lr', 'hr' and 'metrics' are
+        None -- no clip is kept and nothing is compared --, 'norm' is the [C, S, 2] tensor as ever and the result gains 'stream':
+        {'windows', 'segments_per_window', 'groups', 'frames', 'out_frames', 'window_seconds'}.  Only samples of a fixed size stream
+        (PCM, float, G.711; WAV, AIFF, AU, SPHERE): a FLAC or IMA ADPCM input is a ValueError naming file and coding.  Not built with
+        anything that needs the whole clip or a figure of the whole file (plans.check_stream: the crossover, loudness, speech_level,
+        clip other than 'clamp', true_peak, limiter, report_peaks, spectrogram, bandwidth, stereo_report, output_rate,
+        extended_metrics, container 'flac', dither 'shaped', pack_files > 1, loudness_scope 'folder'), and not without
+        segment_norm: a ValueError each, before the file is opened."""
         o = self._options("enhance_file", False, **_named(locals()))
         if check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_file") > 1:
             raise ValueError("enhance_file: pack_files %d lets the files of a folder share groups: it is an option of enhance_folder" % pack_files)
+        window = self._stream_option("enhance_file", stream_seconds, locals())
+        if window is not None:
+            return self._enhance_stream(path_in, path_out, is_lr_input, channels, encoding, o, window)
         read = self._read(path_in, **_set(verify=True if verify_input else None))
         res = self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, o)
         res['metrics'] = first_channel_metrics(res['metrics'], channels)
         return res
+
+    def _stream_option(self, who, stream_seconds, local):
+        """check_stream for enhance_file / enhance_folder, on the entry point's own arguments -> None (off), or the window in seconds."""
+        names = ('loudness', 'speech_level', 'clip', 'true_peak', 'limiter', 'report_peaks', 'spectrogram', 'bandwidth', 'stereo_report',
+                 'output_rate', 'extended_metrics', 'container', 'dither', 'pack_files', 'loudness_scope')
+        return check_stream(stream_seconds, who, self.segment_norm, getattr(self, 'crossover', None), self.opt.hr_sampling_rate,
+                            **{name: local[name] for name in names})
 
     @staticmethod
     def _spectrogram_spec(path, channel, opts, who):
@@ -668,7 +694,7 @@ class SuperResolver(ClipPath, FilePath):
                        loudness_scope='file', album_cache_bytes=None, bandwidth=False, bandwidth_opts=None, stereo_report=False,
                        stereo_report_opts=None, output_rate=None, dither_curve=None, dither_chunk=None, input_formats=None,
                        verify_input=False, container='wav', flac_block=None, flac_md5=False, flac_lpc=None, speech_level=None,
-                       speech_level_max_gain_db=None, pack_files=1):
+                       speech_level_max_gain_db=None, pack_files=1, stream_seconds=None):
         """Every *.wav under dir_in (plan_folder: sorted, recursive) -> the same relative path under dir_out, with one model
         and one captured graph for the whole run.  A file that does not parse is reported and skipped.  `seed`: re-seed the
         generator in front of every file, so that a file comes out as a run of its own with that seed would write it.
@@ -734,9 +760,13 @@ class SuperResolver(ClipPath, FilePath):
         `seed` a file is given the mask noise a run of its own would draw: the generator is re-seeded per file and that file's
         ceil(R_i / batch) draws of a full group are made, their first rows kept, and handed on as given noise.  A file's rows,
         ranges and noise are then bit for bit those of pack_files=1; what the generator does with the other rows of a batch is all
-        that differs.  Without segment_norm, or with loudness_scope 'folder', a ValueError before a file is opened."""
+        that differs.  Without segment_norm, or with loudness_scope 'folder', a ValueError before a file is opened.
+        `stream_seconds`: enhance_file's, file by file on the per-file flow; a record gains 'stream' (as enhance_file returns it; None
+        for a skipped file) and 'norm'.  A file whose coding does not stream (FLAC, IMA ADPCM) is skipped, its record carrying the
+        'error'.  The same refusals, before a file is opened."""
         o = self._options("enhance_folder", True, **_named(locals()))
         pack_files = check_pack_files(pack_files, self.segment_norm, loudness_scope, "enhance_folder")
+        window = self._stream_option("enhance_folder", stream_seconds, locals())
         plan = plan_folder(dir_in, dir_out, **_set(formats=input_formats, ext='.flac' if o.flac is not None else None))
         written_from = None if input_formats is None and o.flac is None else dir_out          # a record then says where its file was written
         if o.album is not None:
@@ -745,6 +775,8 @@ class SuperResolver(ClipPath, FilePath):
         if pack_files > 1:
             return self._enhance_packed(plan, written_from, is_lr_input, channels, encoding, seed, report, extended_metrics, o, dither_seed,
                                         verify_input, pack_files)
+        if window is not None:
+            return self._stream_folder(plan, written_from, is_lr_input, channels, encoding, seed, report, o, dither_seed, window)
         records = []
         for k, (rel, path_in, path_out) in enumerate(plan):
             rec = self._blank_record(rel, path_out, written_from, extended_metrics, o)
@@ -755,6 +787,30 @@ class SuperResolver(ClipPath, FilePath):
                 mine = o._replace(stage=o.stage and dict(o.stage, seed=dither_seed + k),
                                   spec=o.spec and dict(o.spec, path=os.path.join(o.spec['path'], rel + '.png')))
                 self._fill_record(rec, self._enhance_payload(read, path_out, is_lr_input, channels, encoding, extended_metrics, mine))
+            records.append(rec)
+            if report is not None:
+                report(rec)
+        return records
+
+    def _stream_folder(self, plan, written_from, is_lr_input, channels, encoding, seed, report, o, dither_seed, window):
+        """enhance_folder with stream_seconds -> the records: every file streamed on its own (generate/stream.py); one that does not
+        parse, or whose coding does not stream, is a skipped file."""
+        records = []
+        for k, (rel, path_in, path_out) in enumerate(plan):
+            rec = self._blank_record(rel, path_out, written_from, False, o)
+            rec['stream'] = None
+            try:
+                meta = self._stream_info(path_in)
+                self._check_written_channels(o, channels, meta.num_channels)
+            except (ValueError, OSError, EOFError, struct.error) as e:
+                rec['error'] = '%s: %s' % (type(e).__name__, e)
+            else:
+                if seed is not None:
+                    torch.manual_seed(int(seed))
+                mine = o._replace(stage=o.stage and dict(o.stage, seed=dither_seed + k))
+                res = self._enhance_stream(path_in, path_out, is_lr_input, channels, encoding, mine, window)
+                rec.update(rate=meta.sample_rate, channels=meta.num_channels, frames=meta.num_frames, written_channels=res['norm'].shape[0],
+                           out_frames=res['stream']['out_frames'], norm=res['norm'], stream=res['stream'])
             records.append(rec)
             if report is not None:
                 report(rec)

@@ -1779,6 +1779,75 @@ def run_segnorm(seconds, reps, log):
             f.write(text)
 
 
+def run_stream(seconds, reps, log, long_seconds=600.0, windows=(1.0, 5.0, 30.0)):
+    """File to file with SuperResolver(segment_norm=True): enhance_file on the `seconds` s mono clip and on one of `long_seconds` s,
+    unstreamed and with stream_seconds of `windows`, interleaved in one process.  Per run: ms per file, the time until the first
+    payload is on the host and about to be written (unstreamed: the whole file's, at _save; streamed: the first window's, behind its
+    event), and the peak of torch.cuda.max_memory_allocated over the run."""
+    import tempfile
+    torch, model, opt, x = _setup(max(seconds, long_seconds))
+    from pix2pixhdaudiosr_amd.data import wavio
+    from pix2pixhdaudiosr_amd.generate import SuperResolver
+    rate = int(opt.hr_sampling_rate)
+    sr = SuperResolver(model, opt, overlap=0.25, segment_norm=True)
+    lines = ["# tools/time_generate.py stream: G3L2 ngf 48, n_fft 512 MDCT2, segment 32512, bf16, groups of 4, overlap 0.25, graphed, segment_norm; "
+             "mono PCM16 clips at 48 kHz, file to file; untrained weights, %d interleaved repeats" % reps]
+    first = [None]
+    save, event = sr._save, sr._stream_event
+
+    def saving(*a, **k):
+        first[0] = first[0] or time.perf_counter()
+        return save(*a, **k)
+
+    class Waited:
+        def __init__(self, ev):
+            self.ev = ev
+
+        def synchronize(self):
+            self.ev.synchronize()
+            first[0] = first[0] or time.perf_counter()
+
+    sr._save, sr._stream_event = saving, lambda: Waited(event())
+    runs = [None] + list(windows)
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "out.wav")
+        for length in (seconds, long_seconds):
+            src = os.path.join(tmp, "in%g.wav" % length)
+            wavio.save(src, x[:, :int(length * rate)].cpu(), rate)
+            work = lambda W: sr.enhance_file(src, out, **({} if W is None else {'stream_seconds': W}))     # noqa: E731
+            for W in runs:                                          # warm-up: capture, pinned buffers, page cache
+                work(W)
+                work(W)
+            torch.cuda.synchronize()
+            ts, firsts, peaks, info = [[] for _ in runs], [[] for _ in runs], [0] * len(runs), [None] * len(runs)
+            for _ in range(reps):
+                for j, W in enumerate(runs):
+                    torch.cuda.reset_peak_memory_stats()
+                    first[0] = None
+                    t0 = time.perf_counter()
+                    res = work(W)
+                    torch.cuda.synchronize()
+                    ts[j].append((time.perf_counter() - t0) * 1e3)
+                    firsts[j].append((first[0] - t0) * 1e3)
+                    peaks[j] = max(peaks[j], torch.cuda.max_memory_allocated())
+                    info[j] = res.get('stream')
+                    del res
+            lines.append("the %g s clip:" % length)
+            for j, W in enumerate(runs):
+                what = "unstreamed           " if W is None else "stream_seconds %-6g" % W
+                shape = "" if info[j] is None else "   %d windows of %d segments, %d groups" % (info[j]['windows'], info[j]['segments_per_window'], info[j]['groups'])
+                lines.append("%s  median %9.3f ms   spread %7.3f (%.3f .. %.3f)   %+7.2f %% against unstreamed   first payload after %9.3f ms   "
+                             "peak allocated %7.1f MiB%s   runs: %s"
+                             % (what, _median(ts[j]), max(ts[j]) - min(ts[j]), min(ts[j]), max(ts[j]), 100.0 * (_median(ts[j]) - _median(ts[0])) / _median(ts[0]),
+                                _median(firsts[j]), peaks[j] / 2.0 ** 20, shape, " ".join("%.3f" % v for v in ts[j])))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            f.write(text)
+
+
 def run_pack(seconds, reps, log, off_only=False, files=32, clip_seconds=3.0, batch=32):
     """Files to files with SuperResolver(segment_norm=True) at groups of `batch`: enhance_folder on `files` mono clips of
     `clip_seconds` s with pack_files 1, 4, 16 and 32, interleaved in one process; then the ragged gather and stitch alone, by events,
@@ -2093,7 +2162,7 @@ def run_mode(mode, seconds, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "segnorm", "pack", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
+    ap.add_argument("mode", nargs="?", default=None, choices=list(LIMITS) + ["folder", "lowband", "crossover", "spectrogram", "loudness", "truepeak", "limiter", "album", "bandwidth", "stereo", "rateconv", "normscope", "segnorm", "pack", "stream", "dither", "flac", "flacout", "wavcodec", "containers", "speechlevel"])
     ap.add_argument("--files", type=int, default=8, help="folder and album mode: stereo clips in the folder")
     ap.add_argument("--album_log", default=os.path.join(ROOT, "profiles", "time_generate_album.log"))
     ap.add_argument("--folder_log", default=os.path.join(ROOT, "profiles", "time_generate_folder.log"))
@@ -2112,6 +2181,7 @@ def main():
     ap.add_argument("--normscope_log", default=os.path.join(ROOT, "profiles", "time_generate_norm_scope.log"))
     ap.add_argument("--segnorm_log", default=os.path.join(ROOT, "profiles", "time_generate_segment_norm.log"))
     ap.add_argument("--pack_log", default=os.path.join(ROOT, "profiles", "time_generate_pack.log"))
+    ap.add_argument("--stream_log", default=os.path.join(ROOT, "profiles", "time_generate_stream.log"))
     ap.add_argument("--dither_log", default=os.path.join(ROOT, "profiles", "time_generate_dither.log"))
     ap.add_argument("--flac_log", default=os.path.join(ROOT, "profiles", "time_generate_flac.log"))
     ap.add_argument("--wavcodec_log", default=os.path.join(ROOT, "profiles", "time_generate_wavcodec.log"))
@@ -2151,6 +2221,8 @@ def main():
     if a.mode == "pack":
         log = a.pack_log if not a.off_only or "--pack_log" in sys.argv else None
         return run_pack(a.seconds, 9 if a.reps is None else a.reps, log, a.off_only)
+    if a.mode == "stream":
+        return run_stream(a.seconds, 9 if a.reps is None else a.reps, a.stream_log)
     if a.mode == "segnorm":
         return run_segnorm(a.seconds, 9 if a.reps is None else a.reps, a.segnorm_log)
     if a.mode == "normscope":
